@@ -2,6 +2,12 @@
 """bench.py — k-mers hashed+matched per second on MI355X, BASELINE.json's metric.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--mode queries-sharded|index-sharded]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times exactly K steps and prints one JSON line (`value`, `ms_per_step` = milliseconds of one timed
+step, `step_ms`).  `--full` adds everything else the line can carry: per-kernel HIP-event timing and rooflines, the self-check
+and the sharded == unsharded gate, the side lines (`aux`), the CPU baseline and the configs[4] side line.
+`--dump-outputs DIR` writes what the last timed step returned (rank 0) as float64 .npy files (see dump_outputs).
 
 Main line (BASELINE.json configs[3], the config the metric is quoted on; it fits one GPU):
 1M synthetic query proteins (~300 aa) searched against a 1M-protein index, protein k=10 scaled=1.
@@ -60,6 +66,12 @@ def parse_args():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-aux", action="store_true", help="skip the side measurements (sketch-only, end-to-end, device ceilings)")
     ap.add_argument("--cpu-sample-queries", type=int, default=0, help="0 = auto (aim at ~15 s of CPU search work)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: per-kernel timing + rooflines, self-check, "
+                         "sharded == unsharded gate, side lines, CPU baseline, configs[4] side line (the --no-* options "
+                         "drop parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (rank 0) to DIR/<name>.npy, float64, <= 64 MB in all")
     return ap.parse_args()
 
 
@@ -290,6 +302,67 @@ def window_stats(env, off, k):
     return w, (int(lens.max()) if lens.numel() else 0)
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20240601
+DUMP_SKETCH_SEQS = 2048          # sequences whose whole sketch is written (seeded sample)
+DUMP_SKETCH_HASHES = 1_000_000   # ... cut at whole sequences once they hold this many hashes
+DUMP_HIT_ROWS = 600_000          # hit rows written; a larger hit list is sampled (seeded, in row order)
+
+
+def _exact_f64(name, a):
+    """Integer column as float64 (the dump's dtype), refusing values float64 does not hold exactly."""
+    import numpy as np
+    a = np.asarray(a)
+    if a.size and a.dtype.kind in "iu":
+        assert int(a.max()) < (1 << 53) and int(a.min()) > -(1 << 53), f"{name}: values beyond 2^53"
+    return a.astype(np.float64)
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes {name: integer array} as DIR/<name>.npy in float64.  64-bit hashes travel as two exact 32-bit halves."""
+    import numpy as np
+    conv = {n: _exact_f64(n, a) for n, a in arrays.items()}
+    total = sum(a.nbytes for a in conv.values())
+    assert total <= DUMP_MAX_BYTES, f"dump of {total} bytes exceeds {DUMP_MAX_BYTES}"
+    os.makedirs(out_dir, exist_ok=True)
+    for n, a in conv.items():
+        np.save(os.path.join(out_dir, n + ".npy"), a)
+
+
+def hit_arrays(qid, tid, isect, nw):
+    """The hit list's four COO columns (host numpy), all rows or a seeded sample of them in row order (`hit_row`)."""
+    import numpy as np
+    n = len(qid)
+    rows = np.arange(n, dtype=np.int64)
+    if n > DUMP_HIT_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_HIT_ROWS, replace=False))
+    return {"hit_row": rows, "hit_query_id": qid[rows], "hit_target_id": tid[rows], "hit_intersect": isect[rows],
+            "hit_n_weighted": nw[rows]}
+
+
+def sketch_arrays(env, ksd, sk):
+    """A seeded sample of whole per-sequence sketches of a device-resident ``Sketches``: sequence ids, sketch sizes, hashes
+    (hi / lo 32 bits) and abundances; only the sampled rows leave the device."""
+    import numpy as np
+    torch = env.torch
+    offs, hashes, abunds = ksd.sketch_columns_as_torch(sk, env.dev)
+    offs_h = offs.cpu().numpy()
+    n = len(offs_h) - 1
+    ids = np.sort(np.random.default_rng(DUMP_SEED + 1).choice(n, min(n, DUMP_SKETCH_SEQS), replace=False))
+    sizes = offs_h[ids + 1] - offs_h[ids]
+    keep = np.cumsum(sizes) <= DUMP_SKETCH_HASHES
+    ids, sizes = ids[keep], sizes[keep]
+    total = int(sizes.sum())
+    # position of every sampled hash in the CSR: each sequence's start, repeated, plus the running index within it
+    starts = np.repeat(offs_h[ids] - (np.cumsum(sizes) - sizes), sizes)
+    idx = torch.from_numpy(starts + np.arange(total, dtype=np.int64)).to(env.dev)
+    h = hashes.index_select(0, idx).cpu().numpy().view(np.uint64) if total else np.empty(0, np.uint64)
+    a = abunds.index_select(0, idx).cpu().numpy() if total else np.empty(0, np.int32)
+    del offs, hashes, abunds, idx
+    return {"sketch_seq_id": ids, "sketch_size": sizes, "sketch_hash_hi": h >> np.uint64(32),
+            "sketch_hash_lo": h & np.uint64(0xFFFFFFFF), "sketch_abundance": a}
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # BASELINE configs[3]: queries sharded, index replicated
 # ---------------------------------------------------------------------------------------------------------------------
@@ -320,7 +393,7 @@ def run_queries_sharded(args, env, ks, synth, ksd):
         q_res, q_off, n_q_res = device_shard(env, qa_res, qa_off, s0, s1)
         n_q = s1 - s0
         q_base = s0
-        if not env.multi or rank != 0:
+        if not env.multi or rank != 0 or not args.full:
             del qa_res, qa_off  # (rank 0 of an N-rank job keeps the whole batch for the sharded == unsharded check)
     else:
         if rank != 0:
@@ -343,18 +416,21 @@ def run_queries_sharded(args, env, ks, synth, ksd):
     index = ctx.index_build(T)
     torch.cuda.synchronize(env.dev)
     index_build_s = time.time() - t0
-    # ... and once more with the pool warm (the first build pays for every hipMalloc of the context's pool)
-    T.free(); index.free()
-    torch.cuda.synchronize(env.dev)
-    t0 = time.time()
-    T = ctx.sketch_batch_device(t_res.data_ptr(), t_off.data_ptr(), args.targets, n_t_res, k, scaled, mol)
-    index = ctx.index_build(T)
-    torch.cuda.synchronize(env.dev)
-    index_build_warm_s = time.time() - t0
+    index_build_warm_s = None
+    if args.full:
+        # ... and once more with the pool warm (the first build pays for every hipMalloc of the context's pool)
+        T.free(); index.free()
+        torch.cuda.synchronize(env.dev)
+        t0 = time.time()
+        T = ctx.sketch_batch_device(t_res.data_ptr(), t_off.data_ptr(), args.targets, n_t_res, k, scaled, mol)
+        index = ctx.index_build(T)
+        torch.cuda.synchronize(env.dev)
+        index_build_warm_s = time.time() - t0
     n_t_postings = index.n_postings
 
     posting_bytes = [12]  # bytes per partitioned query posting (10 against a big index at scaled = 1, else 12)
     bucket_bytes = [12]   # ... and inside the join buckets, behind the bucket scatter (9 when the join prefix has 16 bits)
+    calls, last = [0], [None]  # the last timed step keeps its (sketches, hits) — what a caller receives — for --dump-outputs
 
     def step():
         # sketch for an immediate search: the sketch kernel also writes the postings pre-partitioned for the join; one call
@@ -367,34 +443,49 @@ def run_queries_sharded(args, env, ks, synth, ksd):
         posting_bytes[0] = Q.posting_bytes or 12
         bucket_bytes[0] = H.bucket_posting_bytes or posting_bytes[0]
         out = (Q.n_hashes, H.count, H.n_pair_instances)
-        H.free()
-        Q.free()
+        calls[0] += 1
+        if calls[0] == args.warmup + args.steps:
+            last[0] = (Q, H)
+        else:
+            H.free()
+            Q.free()
         return out
 
     stats = None
     for _ in range(args.warmup):
         stats = step()
 
-    # HIP events on the launch stream bracket the sketch tile kernel during the timed region (mode 2: a bracket around
-    # every launch would add ~20 us of idle queue per launch to each step)
-    ctx.timing_reset()
-    ctx.timing_enable(2)
-    c_before = counters(ctx)
+    if args.full:
+        # HIP events on the launch stream bracket the sketch tile kernel during the timed region (mode 2: a bracket around
+        # every launch would add ~20 us of idle queue per launch to each step)
+        ctx.timing_reset()
+        ctx.timing_enable(2)
+        c_before = counters(ctx)
     elapsed, stats = env.timed(step, args.steps)
-    c_after = counters(ctx)
     step_times = env.step_times()
-    ctx.timing_enable(False)
-    timing = ctx.timing()
-    # untimed extra pass with every launch bracketed, for the complete per-kernel table
-    ctx.timing_reset()
-    ctx.timing_enable(1)
-    for _ in range(2):
-        step()
-    ctx.timing_enable(False)
-    timing_all = {k_: (n_ / 2, ms_ / 2) for k_, (n_, ms_) in ctx.timing().items()}
-    check = self_check(env, ksd, ctx, index, q_res.data_ptr(), q_off.data_ptr(), n_q, n_q_res, q_maxlen)
-    gate = None
-    if env.multi and strong:
+    if args.full:
+        c_after = counters(ctx)
+        ctx.timing_enable(False)
+        timing = ctx.timing()
+    if last[0] is not None:
+        Q, H = last[0]
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, {**sketch_arrays(env, ksd, Q), **hit_arrays(*H.to_host()),
+                                             "totals": [n_q, Q.n_hashes, H.count, H.n_pair_instances]})
+        H.free(); Q.free()
+        del Q, H
+    last[0] = None
+    check = gate = None
+    if args.full:
+        # untimed extra pass with every launch bracketed, for the complete per-kernel table
+        ctx.timing_reset()
+        ctx.timing_enable(1)
+        for _ in range(2):
+            step()
+        ctx.timing_enable(False)
+        timing_all = {k_: (n_ / 2, ms_ / 2) for k_, (n_, ms_) in ctx.timing().items()}
+        check = self_check(env, ksd, ctx, index, q_res.data_ptr(), q_off.data_ptr(), n_q, n_q_res, q_maxlen)
+    if args.full and env.multi and strong:
         # every rank's hit list of its query shard, all-gathered (qid ranges ascend with the rank: the concatenation IS the
         # global order) == rank 0 searching all the queries by itself.  (A side check: an error in it — other than a mismatch
         # under KS_BENCH_REHEARSE / KS_BENCH_STRICT — is reported in the line, it does not cost the headline.)
@@ -415,7 +506,7 @@ def run_queries_sharded(args, env, ks, synth, ksd):
 
     # ---- SURVEY §8(d) side lines (rank 0, after the timed region; none of them is `value`)
     aux = None
-    if rank == 0 and not args.no_aux:
+    if args.full and rank == 0 and not args.no_aux:
         aux = {}
         torch.cuda.synchronize(env.dev)
         c0 = time.perf_counter()
@@ -475,6 +566,29 @@ def run_queries_sharded(args, env, ks, synth, ksd):
     n_q_hashes, n_hits, n_pairs = stats
     value = all_windows * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
+    sharding = (f"the same {args.queries // 1000}k queries cut into {world} residue-balanced shards" if strong
+                else f"{args.queries // 1000}k queries per GPU")
+    result = {
+        "metric": "k-mers hashed+matched/sec", "value": value, "unit": "k-mers/s", "n_gpus": args.gpus,
+        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step, "step_ms": step_times,
+        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u64",
+        "data": "synthetic",
+        "config": {"workload": f"{args.queries // 1000}k query proteins vs {args.targets // 1000}k-protein index, {mol} k={k} "
+                               f"scaled={scaled}" + (" (BASELINE configs[3]: 1M-vs-1M, k=10 scaled=1 protein, queries "
+                                                     "sharded across the GPUs, index replicated by broadcast)"
+                                                     if (args.queries, args.targets, k, scaled, mol) ==
+                                                     (1_000_000, 1_000_000, 10, 1, "protein") else ""),
+                   "queries": all_queries, "targets": args.targets, "ksize": k, "scaled": scaled, "moltype": mol,
+                   "entry": "ks_sketch_queries_device + ks_search" if args.two_calls else "ks_sketch_search_device",
+                   "parallelism": f"queries sharded x{world} ({sharding}), index replicated",
+                   "n_ranks": world, "collective_backend": env.backend},
+        "query_proteins_per_s": all_queries * args.steps / elapsed,
+        "query_windows": all_windows, "query_hashes": all_q_hashes, "index_postings": n_t_postings,
+        "hits": all_hits, "matched_posting_pairs": all_pairs,
+        "index_build_s": index_build_s, "datagen_s": gen_s,
+    }
+    if not args.full:
+        return result, (ctx, index, T)
 
     # ---- roofline (HIP-event durations on the launch stream, this process = rank 0's shard)
     # algorithmic bytes EXCLUDE scratch / sort passes.  Sketch, per launch: residues read + 12 B per unique
@@ -554,31 +668,12 @@ def run_queries_sharded(args, env, ks, synth, ksd):
         qh_off = q_off.cpu().numpy().view(np.uint64)
         cpu = cpu_baseline(args, T, qh_res, qh_off, k, scaled, mol)
 
-    sharding = (f"the same {args.queries // 1000}k queries cut into {world} residue-balanced shards" if strong
-                else f"{args.queries // 1000}k queries per GPU")
-    result = {
-        "metric": "k-mers hashed+matched/sec", "value": value, "unit": "k-mers/s", "n_gpus": args.gpus,
-        "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-        "step_ms": step_times, "timed_region_counters": counters_delta(c_before, c_after), "self_check": check,
-        "sharded_equals_unsharded": gate,
-        "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "u64",
-        "data": "synthetic",
-        "config": {"workload": f"{args.queries // 1000}k query proteins vs {args.targets // 1000}k-protein index, {mol} k={k} "
-                               f"scaled={scaled}" + (" (BASELINE configs[3]: 1M-vs-1M, k=10 scaled=1 protein, queries "
-                                                     "sharded across the GPUs, index replicated by broadcast)"
-                                                     if (args.queries, args.targets, k, scaled, mol) ==
-                                                     (1_000_000, 1_000_000, 10, 1, "protein") else ""),
-                   "queries": all_queries, "targets": args.targets, "ksize": k, "scaled": scaled, "moltype": mol,
-                   "entry": "ks_sketch_queries_device + ks_search" if args.two_calls else "ks_sketch_search_device",
-                   "parallelism": f"queries sharded x{world} ({sharding}), index replicated",
-                   "n_ranks": world, "collective_backend": env.backend},
-        "query_proteins_per_s": all_queries * args.steps / elapsed,
-        "query_windows": all_windows, "query_hashes": all_q_hashes, "index_postings": n_t_postings,
-        "hits": all_hits, "matched_posting_pairs": all_pairs,
-        "index_build_s": index_build_s, "index_build_warm_s": index_build_warm_s, "datagen_s": gen_s,
+    result.update({
+        "timed_region_counters": counters_delta(c_before, c_after), "self_check": check, "sharded_equals_unsharded": gate,
+        "index_build_warm_s": index_build_warm_s,
         "roofline": roofline, "step_roofline": step_roofline, "cpu_baseline": cpu,
         "roofline_other_kernels": roofline_others, "kernels": per_kernel, "aux": aux,
-    }
+    })
     if aux and isinstance(aux.get("device"), dict) and aux["device"].get("u64_gmul_per_s_measured") and "sketch_tiles" in timing:
         # integer-ALU line of the sketch kernel: 64-bit multiplies MurmurHash3 needs per window (8 at k = 10)
         muls = 4 * (k // 16) + (2 if k % 16 > 0 else 0) + (2 if k % 16 > 8 else 0) + 4  # blocks, tail k1 / k2, two fmix64
@@ -724,7 +819,7 @@ def cpu_baseline(args, T, q_res_h, q_off_h, k, scaled, mol):
 # ---------------------------------------------------------------------------------------------------------------------
 # BASELINE configs[4]: all-vs-all, index sharded by target id, hit lists all-gathered over RCCL
 # ---------------------------------------------------------------------------------------------------------------------
-def run_index_sharded(args, env, ks, synth, ksd, ctx=None, n_prot=None, k=24, scaled=5, mol="hp"):
+def run_index_sharded(args, env, ks, synth, ksd, ctx=None, n_prot=None, k=24, scaled=5, mol="hp", dump=False):
     import numpy as np
     torch = env.torch
     rank, world = env.rank, env.world
@@ -782,10 +877,23 @@ def run_index_sharded(args, env, ks, synth, ksd, ctx=None, n_prot=None, k=24, sc
     stats, rows = drain((stats, rows))
     rows = None  # (the warm-up's last hit list must not stay alive beside the three the timed loop keeps: one more list than the
                  # warm-up ever held at once = three fresh blocks = three hipMalloc calls inside the timed region, ~1.3 ms of one step)
-    c_before = counters(ctx)
+    if args.full:
+        c_before = counters(ctx)
     elapsed, (stats, rows) = env.timed(step, args.steps, finalize=drain)
-    c_after = counters(ctx)
     step_times = env.step_times()
+    if args.full:
+        c_after = counters(ctx)
+    n_gathered = int(rows[0].numel())
+    if dump and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {**hit_arrays(*[c.cpu().numpy() for c in rows]),
+                                         "totals": [n_prot, stats[0], n_gathered, stats[2]]})
+    if not args.full:
+        del rows
+        T.free(); index.free()
+        if own:
+            ctx.close()
+        return _index_sharded_result(args, env, elapsed, step_times, n_prot, k, scaled, mol, q_windows, stats, n_gathered,
+                                     index_build_s, gen_s) if rank == 0 else None
     # per-kernel table + roofline of this config (untimed pass with every launch bracketed by HIP events on the launch stream)
     n_t_postings = index.n_postings
     ctx.timing_reset()
@@ -817,7 +925,6 @@ def run_index_sharded(args, env, ks, synth, ksd, ctx=None, n_prot=None, k=24, sc
     # the gathered list is complete and holds every (qid, tid) pair once: checked once, outside the timed region, by sorting
     key = torch.sort(rows[0].to(torch.int64) << 32 | rows[1].to(torch.int64)).values
     ordered = bool((key[1:] > key[:-1]).all()) if key.numel() > 1 else True
-    n_gathered = int(rows[0].numel())
     local_hits_sum, = env.sum_ints([stats[1]])
     diag = int((rows[0] == rows[1]).sum())
     del rows, key
@@ -851,16 +958,29 @@ def run_index_sharded(args, env, ks, synth, ksd, ctx=None, n_prot=None, k=24, sc
         sketch_roofline = {"kernel": "sketch_tiles", "algorithmic_bytes_per_launch": sketch_bytes, "avg_launch_ms": sk[1] / sk[0],
                            "achieved": sketch_bytes / (sk[1] / sk[0] / 1e3) / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                            "frac": sketch_bytes / (sk[1] / sk[0] / 1e3) / 1e9 / HBM_PEAK_GBS, "traffic": traffic_tab.get("sketch_tiles.compact")}
-    return {
+    result = _index_sharded_result(args, env, elapsed, step_times, n_prot, k, scaled, mol, q_windows, stats, n_gathered,
+                                   index_build_s, gen_s)
+    result.update({
         "roofline": roofline, "sketch_roofline": sketch_roofline,
         "step_roofline": {"bound": "hbm", "algorithmic_bytes_per_step": step_bytes, "achieved": step_bytes / (ms_per_step / 1e3) / 1e9,
                           "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": step_bytes / (ms_per_step / 1e3) / 1e9 / HBM_PEAK_GBS,
                           "formula": "sketch (n_res + 12*N_Q + 8*n_seqs) + search (12*N_Q + 12*N_T + 16*N_hits), SURVEY 8(d)"},
         "kernels": {name: {"launches_per_step": n, "ms_per_step": ms} for name, (n, ms) in timing_all.items()},
+        "timed_region_counters": counters_delta(c_before, c_after), "self_check": check, "sharded_equals_unsharded": gate,
+        "hits_sum_over_shards": local_hits_sum, "gathered_equals_sum_of_shards": n_gathered == local_hits_sum,
+        "gathered_pairs_all_distinct": ordered, "self_hits": diag, "matched_posting_pairs_rank0": stats[2],
+    })
+    return result
+
+
+def _index_sharded_result(args, env, elapsed, step_times, n_prot, k, scaled, mol, q_windows, stats, n_gathered, index_build_s,
+                          gen_s):
+    """The configs[4] line of a plain run (rank 0); --full adds its checks and rooflines."""
+    world = env.world
+    return {
         "metric": "k-mers hashed+matched/sec", "value": q_windows * args.steps / elapsed, "unit": "k-mers/s",
         "n_gpus": args.gpus, "steps": args.steps, "warmup": max(args.warmup, 1), "ms_per_step": elapsed / args.steps * 1e3,
-        "step_ms": step_times, "timed_region_counters": counters_delta(c_before, c_after), "self_check": check,
-        "sharded_equals_unsharded": gate,
+        "step_ms": step_times,
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "u64", "data": "synthetic",
         "config": {"workload": f"all-vs-all containment, {n_prot // 1000}k proteins, {mol} k={k} scaled={scaled} "
                                f"(BASELINE configs[4]: index sharded by target id, per-shard hit lists all-gathered)",
@@ -870,8 +990,7 @@ def run_index_sharded(args, env, ks, synth, ksd, ctx=None, n_prot=None, k=24, sc
                                   f"transport words)",
                    "n_ranks": world, "collective_backend": env.backend},
         "query_proteins_per_s": n_prot * args.steps / elapsed, "query_windows": q_windows, "query_hashes": stats[0],
-        "hits_gathered": n_gathered, "hits_sum_over_shards": local_hits_sum, "gathered_equals_sum_of_shards": n_gathered == local_hits_sum,
-        "gathered_pairs_all_distinct": ordered, "self_hits": diag, "matched_posting_pairs_rank0": stats[2],
+        "hits_gathered": n_gathered,
         "hit_bytes_gathered_per_step": (8 if env.multi else 20) * n_gathered, "index_build_s": index_build_s, "datagen_s": gen_s,
     }
 
@@ -898,17 +1017,17 @@ def main():
     from kmerseek_amd import dist as ksd, synth
 
     if args.mode == "index-sharded":
-        result = run_index_sharded(args, env, ks, synth, ksd)
+        result = run_index_sharded(args, env, ks, synth, ksd, dump=True)
     else:
         result, (ctx, index, T) = run_queries_sharded(args, env, ks, synth, ksd)
         index.free(); T.free()
         c4 = None
-        if not args.no_config4:
+        if args.full and not args.no_config4:
             try:
                 c4 = run_index_sharded(args, env, ks, synth, ksd, ctx=ctx)
             except Exception as e:  # a side line must not cost the headline
                 c4 = {"error": repr(e)}
-        if result is not None:
+        if result is not None and args.full:
             result["config4_index_sharded"] = c4
         ctx.close()
     if rank == 0:

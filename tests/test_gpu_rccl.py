@@ -39,7 +39,7 @@ def test_dist_collectives_run_through_rccl_with_one_rank():
 
 def test_bench_takes_its_n_rank_path_over_rccl_with_one_rank():
     d = _run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--queries", "40000",
-              "--targets", "60000", "--c4-proteins", "20000", "--no-cpu-baseline", "--no-aux"],
+              "--targets", "60000", "--c4-proteins", "20000", "--full", "--no-cpu-baseline", "--no-aux"],
              {"KS_BENCH_FORCE_PG": "1", "KS_BENCH_STRICT": "1"}, 900)
     assert d["config"]["collective_backend"] == "nccl" and d["n_gpus"] == 1
     assert d["self_check"]["ok"] is True

@@ -1,7 +1,7 @@
 # The BASELINE configs that are not the headline, and the 125k-query shard that decides strong scaling, one bench line each.
 R=${R:-r4}
 mkdir -p gpurun_out
-B="python3 bench.py --no-cpu-baseline --no-config4 --no-aux --steps 20 --warmup 5"
+B="python3 bench.py --full --no-cpu-baseline --no-config4 --no-aux --steps 20 --warmup 5"
 $B --queries 10000 --targets 10000 --ksize 7 > gpurun_out/${R}_c2.json 2> gpurun_out/${R}_c2.err
 $B --queries 100000 --targets 100000 --ksize 16 --scaled 5 --moltype dayhoff > gpurun_out/${R}_c3.json 2> gpurun_out/${R}_c3.err
 $B --queries 125000 --targets 1000000 > gpurun_out/${R}_shard.json 2> gpurun_out/${R}_shard.err
