@@ -588,10 +588,11 @@ extern "C" int ks_hits_merge_by_qid_device(ks_ctx *ctx, const uint32_t *d_qid, c
         if (hipGetLastError() != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "merge launch failed");
     }
     if (st == KS_OK) { // a row whose query id lies beyond n_queries has no place in the merged order: the outputs would hold a gap
-        const ks_fetch_seg f = ks_fetch_words(n_dropped, ctx->h_pin, 1);
+        const u32 *dropped = (const u32 *)(ctx->h_pin + KS_PIN_READ);
+        const ks_fetch_seg f = ks_fetch_words(n_dropped, ctx->h_pin + KS_PIN_READ, 1);
         st = ks_stream_wait_fetch(ctx, &f, 1);
-        if (st == KS_OK && *(const u32 *)ctx->h_pin != 0)
-            st = ks_fail(ctx, KS_ERR_INVALID_ARG, "merge: %u rows carry a query id >= n_queries = %u", *(const u32 *)ctx->h_pin, n_queries);
+        if (st == KS_OK && *dropped != 0)
+            st = ks_fail(ctx, KS_ERR_INVALID_ARG, "merge: %u rows carry a query id >= n_queries = %u", *dropped, n_queries);
     }
     // (the scratch blocks go back to the pool in stream order: the next allocation on this context's stream comes behind the kernels)
     ks_pool_free(ctx, first); ks_pool_free(ctx, run);

@@ -78,7 +78,7 @@ struct ks_ctx {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> t_free;
     bool t_open = false; // the last ks_timer_begin recorded a start event
     // small pinned host scratch for counters read back from the device
-    u64 *h_pin = nullptr; // KS_PIN_WORDS x u64; [KS_PIN_SKETCH, +32): the control block of a sketch whose read-back is pending
+    u64 *h_pin = nullptr; // KS_PIN_WORDS x u64, one slot per read-back (KS_PIN_*)
     // matched posting pairs of recent searches (+ slack): sizes the next search's match list so the join runs once
     u64 pair_cap_hint = 0;
     // hit rows of recent searches (+ slack): sizes the next search's row arrays so that the row count can be read with the
@@ -183,6 +183,30 @@ static inline int ks_alloc(ks_ctx *ctx, T **out, size_t count) {
     return KS_OK;
 }
 
+// Pool blocks a host driver borrows for one call: given back (ks_pool_free, stream-ordered like every pool free) when the
+// owner goes out of scope, so that the drivers can return early through KS_TRY / KS_HIP.  A fixed table: no heap allocation.
+struct ks_scratch {
+    ks_ctx *ctx;
+    void *blk[16];
+    int n = 0;
+    explicit ks_scratch(ks_ctx *c) : ctx(c) {}
+    ks_scratch(const ks_scratch &) = delete;
+    ~ks_scratch() { for (int i = 0; i < n; i++) ks_pool_free(ctx, blk[i]); }
+    template <typename T> int alloc(T **out, size_t count) {
+        if (n == 16) return ks_fail(ctx, KS_ERR_HIP, "internal error: scratch table full");
+        KS_TRY(ks_alloc(ctx, out, count));
+        blk[n++] = *out;
+        return KS_OK;
+    }
+    void free(void *p) { if (forget(p)) ks_pool_free(ctx, p); } // early give-back (a retry sizes the block anew); nullptr: no-op
+    template <typename T> T *keep(T *p) { forget(p); return p; } // the block outlives the call (part of a result object)
+    bool forget(void *p) {
+        for (int i = 0; p && i < n; i++)
+            if (blk[i] == p) { blk[i] = blk[--n]; return true; }
+        return false;
+    }
+};
+
 // ---- opaque objects ----
 struct ks_sketches {
     ks_ctx *ctx;
@@ -232,8 +256,26 @@ struct ks_sketches {
     u32 pend_max_seq_len;
     int pend_planned;
 };
+
+// ---- the pinned host words (ctx->h_pin, KS_PIN_WORDS x u64): one slot per read-back, in u64 words.  No two slots overlap,
+// so words that are fetched in the same wait (join + pending sketch; row pass + scan status) never clobber each other.
+enum : u32 {
+    KS_PIN_JOIN = 0, KS_PIN_JOIN_WORDS = 128, // join: per segment (count, flags) as u32 pairs, 2 words apart (ks_search.hip)
+    KS_PIN_SKETCH = 128, KS_PIN_SKETCH_WORDS = 32, // the control block of a sketch whose read-back is pending ...
+    KS_PIN_SKETCH_SYNC = 160, KS_PIN_SKETCH_SYNC_WORDS = 32, // ... and of a sketch that waits for itself
+    KS_PIN_STAGE = 192,      // u32 uploaded by the sketch's ticket repeat (the status bits it keeps)
+    KS_PIN_ROWS = 193,       // 2 words, row pass: u32 (ticket, look-back flag) | u32 row count
+    KS_PIN_SCAN = 195,       // u32: a one-launch scan gave up a look-back (ks_scan_status_check)
+    KS_PIN_SORT_OFLOW = 196, // u32: a fixed capacity of the partitioned index sort did not hold
+    KS_PIN_READ = 197,       // 2 words, one-call read-backs: index build, union, merge, k-mer positions
+    KS_PIN_END = 199,
+};
 #define KS_PIN_WORDS 256
-#define KS_PIN_SKETCH 128
+static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
+                  KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
+                  KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
+                  KS_PIN_READ + 2 <= KS_PIN_END && KS_PIN_END <= KS_PIN_WORDS,
+              "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
 // one index posting as the join fetches it for a candidate match: one 16-byte load
 struct __attribute__((aligned(16))) ks_post {

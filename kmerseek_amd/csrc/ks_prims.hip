@@ -240,17 +240,17 @@ static int scan_generic(ks_ctx *ctx, const TIn *in, TOut *out, u64 n, TOut *d_to
 
 int ks_scan_status_fetch(ks_ctx *ctx) {
     if (!ctx->scan_ticket) return KS_OK;
-    KS_HIP(ctx, hipMemcpyAsync(ctx->h_pin + 40, ctx->scan_ticket + 1, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    KS_HIP(ctx, hipMemcpyAsync(ctx->h_pin + KS_PIN_SCAN, ctx->scan_ticket + 1, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     return KS_OK;
 }
 bool ks_scan_status_seg(ks_ctx *ctx, ks_fetch_seg *out) {
     if (!ctx->scan_ticket) return false;
-    *out = ks_fetch_words(ctx->scan_ticket + 1, ctx->h_pin + 40, 1);
+    *out = ks_fetch_words(ctx->scan_ticket + 1, ctx->h_pin + KS_PIN_SCAN, 1);
     return true;
 }
 int ks_scan_status_check(ks_ctx *ctx) {
-    if (!ctx->scan_ticket || *(u32 *)(ctx->h_pin + 40) == 0) return KS_OK;
-    *(u32 *)(ctx->h_pin + 40) = 0;
+    if (!ctx->scan_ticket || *(u32 *)(ctx->h_pin + KS_PIN_SCAN) == 0) return KS_OK;
+    *(u32 *)(ctx->h_pin + KS_PIN_SCAN) = 0;
     (void)hipMemsetAsync(ctx->scan_ticket + 1, 0, sizeof(u32), ctx->stream);
     return ks_fail(ctx, KS_ERR_HIP, "scan: look-back gave up waiting for a predecessor tile");
 }
@@ -775,26 +775,25 @@ int ks_index_sort_partitioned(ks_ctx *ctx, const u64 *keys_in, const u64 *vals_i
     const u32 pfxK = ks_join_prefix_mul(S, max_hash); // hi32(hash) * K: high word = sort bucket, low word = place inside it
     u64 *ak = nullptr, *av = nullptr, *bk = nullptr, *bv = nullptr, *dpos = nullptr;
     u32 *acur = nullptr, *bcur = nullptr, *oflow = nullptr;
-    int st = KS_OK;
     const u32 nA = 1u << hi;
     u64 capA = 0;
-#define PS_CHECK(x) do { st = (x); if (st != KS_OK) goto done; } while (0)
-    PS_CHECK(ks_alloc(ctx, &bcur, (size_t)n_buckets + 1));
-    PS_CHECK(ks_alloc(ctx, &oflow, 1));
-    PS_CHECK(ks_alloc(ctx, &dpos, (size_t)n_buckets + 1));
+    ks_scratch sc(ctx);
+    KS_TRY(sc.alloc(&bcur, (size_t)n_buckets + 1));
+    KS_TRY(sc.alloc(&oflow, 1));
+    KS_TRY(sc.alloc(&dpos, (size_t)n_buckets + 1));
     (void)hipMemsetAsync(bcur, 0, ((size_t)n_buckets + 1) * sizeof(u32), ctx->stream);
     (void)hipMemsetAsync(oflow, 0, sizeof(u32), ctx->stream);
     if (S > 0) {
-        PS_CHECK(ks_alloc(ctx, &bk, (size_t)n_buckets * bcap));
-        PS_CHECK(ks_alloc(ctx, &bv, (size_t)n_buckets * bcap));
+        KS_TRY(sc.alloc(&bk, (size_t)n_buckets * bcap));
+        KS_TRY(sc.alloc(&bv, (size_t)n_buckets * bcap));
     }
     if (hi > 0) { // pass A: dense input -> 2^hi regions on the high bits of the sort prefix
         const u64 perA = n >> hi;
         capA = perA + perA / 8 + 8192;
         capA = (capA + RS_TILE - 1) / RS_TILE * RS_TILE;
-        PS_CHECK(ks_alloc(ctx, &ak, (size_t)nA * capA));
-        PS_CHECK(ks_alloc(ctx, &av, (size_t)nA * capA));
-        PS_CHECK(ks_alloc(ctx, &acur, (size_t)nA));
+        KS_TRY(sc.alloc(&ak, (size_t)nA * capA));
+        KS_TRY(sc.alloc(&av, (size_t)nA * capA));
+        KS_TRY(sc.alloc(&acur, (size_t)nA));
         (void)hipMemsetAsync(acur, 0, (size_t)nA * sizeof(u32), ctx->stream);
         const u32 nblocks = (u32)((n + RS_TILE - 1) / RS_TILE);
         ks_timer_begin(ctx, "index_part_a");
@@ -814,27 +813,20 @@ int ks_index_sort_partitioned(ks_ctx *ctx, const u64 *keys_in, const u64 *vals_i
                            (const u32 *)nullptr, (u64)0, 0u, 0, n_buckets - 1, pfxK, 0u, bcur, bcap, oflow);
         ks_timer_end(ctx);
     } else { // a single bucket: the input is the bucket
-        if (n > BS_CAP) { *overflowed = 1; goto done; }
+        if (n > BS_CAP) { *overflowed = 1; return KS_OK; }
         const u32 cnt1 = (u32)n;
         (void)hipMemcpyAsync(bcur, &cnt1, sizeof(u32), hipMemcpyHostToDevice, ctx->stream);
     }
-    if (hipGetLastError() != hipSuccess) { st = ks_fail(ctx, KS_ERR_HIP, "index partition launch failed"); goto done; }
+    KS_HIP(ctx, hipGetLastError());
     // overflow flags decide before anything is sorted
-    if (hipMemcpyAsync(ctx->h_pin + 41, oflow, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-        hipStreamSynchronize(ctx->stream) != hipSuccess) { st = ks_fail(ctx, KS_ERR_HIP, "index partition status read failed"); goto done; }
-    if (*(u32 *)(ctx->h_pin + 41) != 0) { *overflowed = 1; goto done; }
-    PS_CHECK(ks_scan_u32_to_u64(ctx, bcur, dpos, n_buckets));
-    ks_timer_begin(ctx, "index_bucket_sort");
-    hipLaunchKernelGGL(k_bucket_sort, dim3(n_buckets), dim3(BS_THREADS), 0, ctx->stream, S ? (const u64 *)bk : keys_in,
-                       S ? (const u64 *)bv : vals_in, (const u32 *)bcur, S ? bcap : (u64)0, (const u64 *)dpos, pfxK, okeys, otids, oabunds,
-                       d_max_abund);
-    ks_timer_end(ctx);
-    if (hipGetLastError() != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "index bucket sort launch failed");
-done:
-    ks_pool_free(ctx, ak); ks_pool_free(ctx, av); ks_pool_free(ctx, bk); ks_pool_free(ctx, bv); ks_pool_free(ctx, dpos);
-    ks_pool_free(ctx, acur); ks_pool_free(ctx, bcur); ks_pool_free(ctx, oflow);
-    return st;
-#undef PS_CHECK
+    KS_HIP(ctx, hipMemcpyAsync(ctx->h_pin + KS_PIN_SORT_OFLOW, oflow, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (*(u32 *)(ctx->h_pin + KS_PIN_SORT_OFLOW) != 0) { *overflowed = 1; return KS_OK; }
+    KS_TRY(ks_scan_u32_to_u64(ctx, bcur, dpos, n_buckets));
+    KS_LAUNCH(ctx, "index_bucket_sort", k_bucket_sort, n_buckets, BS_THREADS, S ? (const u64 *)bk : keys_in,
+              S ? (const u64 *)bv : vals_in, (const u32 *)bcur, S ? bcap : (u64)0, (const u64 *)dpos, pfxK, okeys, otids, oabunds,
+              d_max_abund);
+    return KS_OK;
 }
 
 static const char *const rs_tag_names[3] = {"index", "qpart", "pairs"};

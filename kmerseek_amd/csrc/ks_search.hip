@@ -54,69 +54,52 @@ __global__ __launch_bounds__(256) void k_index_bmeta(const u64 *keys, const u64 
 
 #define JN_FP_PBITS 15 // indexes with this many join-prefix bits or more (> 50M postings) use the fingerprint layout (see the join)
 
-int ks_index_build_impl(ks_ctx *ctx, const ks_sketches *t, ks_index **out) {
-    if (!t || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(t))); // (the sort reads the hashes as one dense array)
-    ks_index *ix = new ks_index();
-    memset(ix, 0, sizeof *ix);
-    ix->ctx = ctx;
-    ix->params = t->params;
-    ix->n_targets = t->n_seqs;
-    ix->n_postings = t->n_hashes;
+static int index_build_run(ks_ctx *ctx, const ks_sketches *t, ks_index *ix) {
     const u64 n = t->n_hashes;
     u64 *k0 = nullptr, *k1 = nullptr, *v0 = nullptr, *v1 = nullptr;
     u32 *d_max = nullptr;
-    int st = KS_OK;
-#define IX_CHECK(x) do { st = (x); if (st != KS_OK) goto done; } while (0)
-#define IX_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { st = ks_fail(ctx, KS_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-    IX_CHECK(ks_alloc(ctx, &v0, (size_t)n));
-    IX_CHECK(ks_alloc(ctx, &ix->d_tids, (size_t)n));
-    IX_CHECK(ks_alloc(ctx, &ix->d_abunds, (size_t)n));
-    IX_CHECK(ks_alloc(ctx, &d_max, 1));
-    IX_HIP(hipMemsetAsync(d_max, 0, sizeof(u32), ctx->stream));
+    ks_scratch sc(ctx);
+    KS_TRY(sc.alloc(&v0, (size_t)n));
+    KS_TRY(ks_alloc(ctx, &ix->d_tids, (size_t)n));
+    KS_TRY(ks_alloc(ctx, &ix->d_abunds, (size_t)n));
+    KS_TRY(sc.alloc(&d_max, 1));
+    KS_HIP(ctx, hipMemsetAsync(d_max, 0, sizeof(u32), ctx->stream));
     if (n > 0) {
         // values = (abund << 32 | tid); keys are read straight from the sketches
-        ks_timer_begin(ctx, "fill_index_vals");
-        hipLaunchKernelGGL(k_fill_index_vals, dim3((t->n_seqs + 3) / 4), dim3(256), 0, ctx->stream, (const u64 *)t->d_offsets,
-                           (const u32 *)t->d_abunds, t->n_seqs, v0);
-        ks_timer_end(ctx);
-        IX_HIP(hipGetLastError());
+        KS_LAUNCH(ctx, "fill_index_vals", k_fill_index_vals, (t->n_seqs + 3) / 4, 256, (const u64 *)t->d_offsets,
+                  (const u32 *)t->d_abunds, t->n_seqs, v0);
         // three passes: partition on the sort prefix twice, sort the buckets in LDS (ks_prims.hip)
         int overflowed = 0;
-        IX_CHECK(ks_alloc(ctx, &k0, (size_t)n));
+        KS_TRY(sc.alloc(&k0, (size_t)n));
         if (!ks_dbg(ctx, KS_DBG_INDEX_LSD))
-            IX_CHECK(ks_index_sort_partitioned(ctx, t->d_hashes, v0, n, ks_max_hash(t->params.scaled), k0, ix->d_tids, ix->d_abunds, d_max,
-                                               &overflowed));
+            KS_TRY(ks_index_sort_partitioned(ctx, t->d_hashes, v0, n, ks_max_hash(t->params.scaled), k0, ix->d_tids, ix->d_abunds, d_max,
+                                             &overflowed));
         else
             overflowed = 1;
         if (!overflowed) {
-            ix->d_keys = k0; k0 = nullptr;
+            ix->d_keys = sc.keep(k0);
         } else {
             // skewed hashes (a fixed capacity did not hold): the always-correct 8-pass LSD sort
-            IX_CHECK(ks_alloc(ctx, &k1, (size_t)n));
-            IX_CHECK(ks_alloc(ctx, &v1, (size_t)n));
+            KS_TRY(sc.alloc(&k1, (size_t)n));
+            KS_TRY(sc.alloc(&v1, (size_t)n));
             const int shifts[8] = {0, 8, 16, 24, 32, 40, 48, 56};
             u64 *ks = nullptr, *vs = nullptr;
             // v0 holds the input values, so the first pass must land in (k1, v1): pass it as the "a" pair
-            IX_CHECK(ks_radix_sort_u64(ctx, KS_SORT_INDEX, t->d_hashes, v0, k1, v1, k0, v0, n, shifts, 8, &ks, &vs));
-            IX_HIP(hipMemsetAsync(d_max, 0, sizeof(u32), ctx->stream));
-            ks_timer_begin(ctx, "split_vals");
-            hipLaunchKernelGGL(k_split_vals, dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)vs, n, ix->d_tids, ix->d_abunds, d_max);
-            ks_timer_end(ctx);
-            IX_HIP(hipGetLastError());
+            KS_TRY(ks_radix_sort_u64(ctx, KS_SORT_INDEX, t->d_hashes, v0, k1, v1, k0, v0, n, shifts, 8, &ks, &vs));
+            KS_HIP(ctx, hipMemsetAsync(d_max, 0, sizeof(u32), ctx->stream));
+            KS_LAUNCH(ctx, "split_vals", k_split_vals, (u32)((n + 255) / 256), 256, (const u64 *)vs, n, ix->d_tids, ix->d_abunds, d_max);
             if (ks != k0 && ks != k1) { // (n == 1: nothing to sort, the keys are still the sketch's own array — found by the fuzz campaign)
-                IX_HIP(hipMemcpyAsync(k0, ks, (size_t)n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
+                KS_HIP(ctx, hipMemcpyAsync(k0, ks, (size_t)n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
                 ks = k0;
             }
-            if (ks == k0) { ix->d_keys = k0; k0 = nullptr; } else { ix->d_keys = k1; k1 = nullptr; }
+            ix->d_keys = sc.keep(ks);
         }
-        IX_HIP(hipMemcpyAsync(ctx->h_pin, d_max, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-        IX_HIP(hipStreamSynchronize(ctx->stream));
-        ix->max_abund = *(u32 *)ctx->h_pin;
+        u32 *const max_abund = (u32 *)(ctx->h_pin + KS_PIN_READ);
+        KS_HIP(ctx, hipMemcpyAsync(max_abund, d_max, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+        KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        ix->max_abund = *max_abund;
     } else {
-        IX_CHECK(ks_alloc(ctx, &k0, 1));
-        ix->d_keys = k0; k0 = nullptr;
+        KS_TRY(ks_alloc(ctx, &ix->d_keys, 1));
     }
     {
         // The layout of the join first (it sizes the buckets).  Indexes are joined on 4-byte fingerprints (streamed; a directory
@@ -135,46 +118,49 @@ int ks_index_build_impl(ks_ctx *ctx, const ks_sketches *t, ks_index **out) {
         ix->pbits = ks_join_pbits(ctx, n, 3072);
         const u32 nb = 1u << ix->pbits;
         const u32 K = ks_join_prefix_mul(ix->pbits, ks_max_hash(t->params.scaled));
-        IX_CHECK(ks_alloc(ctx, &ix->d_dir, (size_t)nb + 1));
-        ks_timer_begin(ctx, "bucket_dir");
-        hipLaunchKernelGGL(k_bucket_dir, dim3((nb + 256) / 256), dim3(256), 0, ctx->stream, (const u64 *)ix->d_keys, n, ix->pbits, K, ix->d_dir);
-        ks_timer_end(ctx);
-        IX_HIP(hipGetLastError());
+        KS_TRY(ks_alloc(ctx, &ix->d_dir, (size_t)nb + 1));
+        KS_LAUNCH(ctx, "bucket_dir", k_bucket_dir, (nb + 256) / 256, 256, (const u64 *)ix->d_keys, n, ix->pbits, K, ix->d_dir);
         if (ix->fp_layout) {
-        IX_CHECK(ks_alloc(ctx, &ix->d_fp, (size_t)(n ? n : 1)));
-        IX_CHECK(ks_alloc(ctx, &ix->d_post, (size_t)(n ? n : 1)));
-        ix->fp_shift = 32 - ix->pbits;
-        if (ks_dbg(ctx, KS_DBG_FP_COARSEN)) {
-            ix->fp_shift += atoi(ks_dbg(ctx, KS_DBG_FP_COARSEN));
-            if (ix->fp_shift > 63) ix->fp_shift = 63;
-        }
-        IX_CHECK(ks_alloc(ctx, &ix->d_bmeta, (size_t)nb));
-        hipLaunchKernelGGL(k_index_bmeta, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, (const u64 *)ix->d_keys, (const u64 *)ix->d_dir,
-                           nb, ix->fp_shift, ix->d_bmeta);
-        IX_HIP(hipGetLastError());
-        if (n > 0) {
-            ks_timer_begin(ctx, "index_finish");
-            hipLaunchKernelGGL(k_index_finish, dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const u64 *)ix->d_keys,
-                               (const u32 *)ix->d_tids, (const u32 *)ix->d_abunds, (const u64 *)ix->d_dir, n, ix->pbits, K, ix->fp_shift, ix->d_fp, ix->d_post);
-            ks_timer_end(ctx);
-            IX_HIP(hipGetLastError());
-        }
+            KS_TRY(ks_alloc(ctx, &ix->d_fp, (size_t)(n ? n : 1)));
+            KS_TRY(ks_alloc(ctx, &ix->d_post, (size_t)(n ? n : 1)));
+            ix->fp_shift = 32 - ix->pbits;
+            if (ks_dbg(ctx, KS_DBG_FP_COARSEN)) {
+                ix->fp_shift += atoi(ks_dbg(ctx, KS_DBG_FP_COARSEN));
+                if (ix->fp_shift > 63) ix->fp_shift = 63;
+            }
+            KS_TRY(ks_alloc(ctx, &ix->d_bmeta, (size_t)nb));
+            hipLaunchKernelGGL(k_index_bmeta, dim3((nb + 255) / 256), dim3(256), 0, ctx->stream, (const u64 *)ix->d_keys, (const u64 *)ix->d_dir,
+                               nb, ix->fp_shift, ix->d_bmeta);
+            KS_HIP(ctx, hipGetLastError());
+            if (n > 0)
+                KS_LAUNCH(ctx, "index_finish", k_index_finish, (u32)((n + 255) / 256), 256, (const u64 *)ix->d_keys, (const u32 *)ix->d_tids,
+                          (const u32 *)ix->d_abunds, (const u64 *)ix->d_dir, n, ix->pbits, K, ix->fp_shift, ix->d_fp, ix->d_post);
         }
     }
-    IX_CHECK(ks_scan_status_fetch(ctx));
-    IX_HIP(hipStreamSynchronize(ctx->stream));
-    IX_CHECK(ks_scan_status_check(ctx));
+    KS_TRY(ks_scan_status_fetch(ctx));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KS_TRY(ks_scan_status_check(ctx));
     if (ix->fp_layout) { // the sorted columns were the input of the finish pass only
         ks_pool_free(ctx, ix->d_keys); ks_pool_free(ctx, ix->d_tids); ks_pool_free(ctx, ix->d_abunds);
         ix->d_keys = nullptr; ix->d_tids = nullptr; ix->d_abunds = nullptr;
     }
-done:
-    ks_pool_free(ctx, k0); ks_pool_free(ctx, k1); ks_pool_free(ctx, v0); ks_pool_free(ctx, v1); ks_pool_free(ctx, d_max);
+    return KS_OK;
+}
+
+int ks_index_build_impl(ks_ctx *ctx, const ks_sketches *t, ks_index **out) {
+    if (!t || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(t))); // (the sort reads the hashes as one dense array)
+    ks_index *ix = new ks_index();
+    memset(ix, 0, sizeof *ix);
+    ix->ctx = ctx;
+    ix->params = t->params;
+    ix->n_targets = t->n_seqs;
+    ix->n_postings = t->n_hashes;
+    const int st = index_build_run(ctx, t, ix);
     if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_index_free(ix); return st; }
     *out = ix;
     return KS_OK;
-#undef IX_CHECK
-#undef IX_HIP
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1318,6 +1304,408 @@ __global__ __launch_bounds__(PF_THREADS) void k_pair_rows_fused(const u64 *keys,
     }
 }
 
+// ---- one search, in steps: partition of the query postings -> join (+ its segment-cap retry) -> match sort -> row pass
+
+// what the steps of one search share
+struct se_search {
+    const ks_index *ix;
+    const ks_sketches *q;
+    u64 n_q; // query postings (an upper bound while q->pending)
+    int pbits, tbits, qbits, abits;
+    u32 n_buckets, pfxK;
+    bool packed;   // a match is one 8-byte record (qid, tid, target abundance)
+    bool pre, f10; // the sketch's postings are the partition's input (pre), in their 10-byte form (f10)
+    u64 *dir_q;
+    // cursor block: segment s of the pair list counts at word s * JN_CUR_STRIDE; word 1 = "a query bucket overflowed"
+    // (k_bucket_scatter) (+ the join buckets' fill counts right behind it, bcur: one allocation, one memset)
+    unsigned long long *cursor;
+    u32 *bcur;
+    // the match list: n_segs segments of seg_cap records, seg_count[s] of them filled
+    u64 *pk0, *pk1;
+    u32 *pv0, *pv1;
+    u64 n_pairs, seg_cap, seg_count[JN_SEGS];
+    u32 n_segs;
+    bool stop; // nothing is produced: the list needs slicing (*split_pairs) or the pending sketch a repeat (*sketch_redo)
+};
+static_assert(2 * JN_SEGS <= KS_PIN_JOIN_WORDS, "pinned slot of the join's segment counts");
+
+// the query postings grouped on the top pbits hash bits (the join needs locality, not order)
+struct se_qview {
+    u64 *qk;
+    u32 *qv;
+    const u64 *q_lo, *q_hi;
+    int q_fmt;
+    int partition_path, bucket_posting_bytes; // (bucket_posting_bytes 0: no bucket scatter ran)
+    u64 *qk0, *qk1; // scratch of the partition
+    u32 *qv0, *qv1;
+};
+
+// The exact counts of a pending sketch, behind a wait that fetched its control block.  A sketch that has to be repeated
+// ends the search (Q.stop: nothing produced).
+static int se_finish_pending(se_search &Q, int *sketch_redo) {
+    if (!Q.q->pending) return KS_OK;
+    int redo = 0;
+    KS_TRY(ks_sketch_finish_pending(const_cast<ks_sketches *>(Q.q), &redo));
+    Q.n_q = Q.q->n_hashes;
+    if (redo) {
+        if (sketch_redo) *sketch_redo = redo;
+        Q.stop = true;
+    }
+    return KS_OK;
+}
+
+// ... behind a wait of its own (the partition starts from the CSR and needs the exact counts)
+static int se_wait_pending(ks_ctx *ctx, se_search &Q, int *sketch_redo) {
+    const ks_fetch_seg f = ks_sketch_pending_seg(Q.q);
+    KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
+    return se_finish_pending(Q, sketch_redo);
+}
+
+// way 0: histogram-free bucket scatter of the sketch kernel's regions (may overflow on skewed hashes);
+// way 1: the dense, always-correct partition (the sketch kernel's regions when they are the join buckets, segmented passes
+// on the high bits behind them, or LSD passes from the CSR)
+static int se_partition(ks_ctx *ctx, se_search &Q, int way, ks_scratch &sc, se_qview *V) {
+    const ks_sketches *q = Q.q;
+    const int pbits = Q.pbits;
+    const u32 n_buckets = Q.n_buckets;
+    memset(V, 0, sizeof *V);
+    if (way == 1 && Q.f10) Q.pre = false;
+    const u32 q_s = (way == 0 && Q.f10) ? q->part_s : 0u;
+    // behind the bucket scatter of a 16-bit join prefix both prefix bytes are implied by the bucket: 9-byte postings
+    // (KS_DEBUG_POSTINGS10 keeps the 10-byte form there)
+    V->q_fmt = q_s ? ((pbits == 16 && q_s == 48u && !ks_dbg(ctx, KS_DBG_POSTINGS10)) ? 2 : 1) : 0;
+    KS_HIP(ctx, hipMemsetAsync(Q.cursor, 0, ((size_t)JN_SEGS * JN_CUR_STRIDE + (way == 0 ? (n_buckets + 1) / 2 : 0)) * sizeof(u64), ctx->stream));
+    if (way == 0) {
+        const u64 per = Q.n_q / n_buckets;
+        const u32 bcap = (u32)(per + per / 8 + 512);
+        KS_TRY(sc.alloc(&V->qk0, (size_t)n_buckets * bcap));
+        KS_TRY(sc.alloc(&V->qv0, (size_t)n_buckets * bcap));
+        ks_rs_segments seg{q->part_len, q->part_cap, q->part_regions << q->part_sub_shift, q->part_sub_shift};
+        KS_TRY(ks_bucket_scatter_u32(ctx, q->part_keys, q->part_vals, &seg, 8, Q.pfxK, V->qk0, V->qv0, Q.bcur, bcap, Q.cursor, n_buckets >> 8,
+                                     V->q_fmt)); // (10-byte postings stay 10 bytes, or lose one more: the join decodes them)
+        V->bucket_posting_bytes = V->q_fmt == 2 ? 9 : (V->q_fmt == 1 ? 10 : 12);
+        KS_LAUNCH(ctx, "bucket_dir", k_region_dir, (n_buckets + 255) / 256, 256, (const u32 *)Q.bcur, (u64)bcap, n_buckets, Q.dir_q,
+                  Q.dir_q + n_buckets, n_buckets >> 8);
+        V->qk = V->qk0; V->qv = V->qv0; V->q_lo = Q.dir_q; V->q_hi = Q.dir_q + n_buckets;
+        V->partition_path = 1;
+    } else if (Q.pre && pbits <= 8) {
+        // the sketch kernel already wrote one region per bucket
+        V->qk = q->part_keys; V->qv = q->part_vals;
+        KS_LAUNCH(ctx, "bucket_dir", k_region_dir, (n_buckets + 255) / 256, 256, (const u32 *)q->part_len, q->part_cap, n_buckets, Q.dir_q,
+                  Q.dir_q + n_buckets, 0u);
+        V->q_lo = Q.dir_q; V->q_hi = Q.dir_q + n_buckets;
+        V->partition_path = 0;
+    } else {
+        const u64 n_q = Q.n_q;
+        if (!Q.pre) KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(q))); // (this partition starts from the CSR)
+        KS_TRY(sc.alloc(&V->qk0, (size_t)n_q)); KS_TRY(sc.alloc(&V->qk1, (size_t)n_q));
+        KS_TRY(sc.alloc(&V->qv0, (size_t)n_q)); KS_TRY(sc.alloc(&V->qv1, (size_t)n_q));
+        if (Q.pre) {
+            // the sketch kernel did the low digit; segmented (histogram + scan) passes on the high bits finish
+            int shifts[2], nsh = 0;
+            for (int sh = 8; sh < pbits; sh += 8) shifts[nsh++] = sh; // bits [8, pbits) of the join prefix
+            ks_rs_segments seg{q->part_len, q->part_cap, q->part_regions << q->part_sub_shift, q->part_sub_shift};
+            KS_TRY(ks_radix_sort_u32(ctx, KS_SORT_QPART, q->part_keys, q->part_vals, V->qk1, V->qv1, V->qk0, V->qv0, n_q, shifts, nsh,
+                                     &V->qk, &V->qv, &seg, Q.pfxK));
+        } else {
+            KS_LAUNCH(ctx, "fill_query_vals", k_fill_query_vals, (q->n_seqs + 3) / 4, 256, (const u64 *)q->d_offsets, q->n_seqs, V->qv0);
+            // hashes are read straight from the query sketches on the first pass (no staging copy);
+            // qv0 holds the input qids, so the first pass lands in (qk1, qv1)
+            int shifts[3], ns = 0;
+            for (int sh = 0; sh < pbits; sh += 8) shifts[ns++] = sh; // digits of the join prefix, low first
+            KS_TRY(ks_radix_sort_u32(ctx, KS_SORT_QPART, q->d_hashes, V->qv0, V->qk1, V->qv1, V->qk0, V->qv0, n_q, shifts, ns, &V->qk,
+                                     &V->qv, nullptr, Q.pfxK));
+        }
+        KS_LAUNCH(ctx, "bucket_dir", k_bucket_dir, (n_buckets + 256) / 256, 256, (const u64 *)V->qk, n_q, pbits, Q.pfxK, Q.dir_q);
+        V->q_lo = Q.dir_q; V->q_hi = Q.dir_q + 1;
+        V->partition_path = Q.pre ? 2 : 3;
+    }
+    return KS_OK;
+}
+
+// The join, with a retry if the match list outgrows its first guess.  Many (bucket, round) reservations: the list is cut
+// into segments with a cursor each (see the kernel) and made dense by one copy afterwards; few: one cursor, no copy.
+// *overflowed: a query bucket of way 0 overflowed (skewed hashes), the list is garbage.
+static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 cap, ks_scratch &sc, u64 *split_pairs, int *sketch_redo,
+                   bool *overflowed) {
+    const ks_index *ix = Q.ix;
+    const u32 n_buckets = Q.n_buckets;
+    const int q_fmt = V.q_fmt;
+    *overflowed = false;
+    {
+        const u64 per_bucket = Q.n_q / n_buckets, round = (u64)JN_THREADS * JN_E;
+        const u64 reservations = (u64)n_buckets * ((per_bucket + round - 1) / round ? (per_bucket + round - 1) / round : 1);
+        Q.n_segs = (ix->fp_layout && reservations >= 8192 && n_buckets >= JN_SEGS && !ks_dbg(ctx, KS_DBG_ONE_CURSOR)) ? JN_SEGS : 1;
+        if (ix->fp_layout && ks_dbg(ctx, KS_DBG_JOIN_SEGS) && n_buckets >= JN_SEGS) Q.n_segs = JN_SEGS; // (tests: small inputs through the segmented path)
+    }
+    const u32 n_segs = Q.n_segs;
+    Q.seg_cap = n_segs == 1 ? cap : cap / n_segs + cap / n_segs / 8 + 4096;
+    if (ks_dbg(ctx, KS_DBG_JOIN_SEG_CAP)) Q.seg_cap = strtoull(ks_dbg(ctx, KS_DBG_JOIN_SEG_CAP), nullptr, 10); // (tests: the retry)
+    const u64 *dir_t = ix->d_dir; // built with the index
+    const u64 *pin = ctx->h_pin + KS_PIN_JOIN;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        const u64 seg_cap = Q.seg_cap;
+        KS_TRY(sc.alloc(&Q.pk0, (size_t)(seg_cap * n_segs)));
+        if (!Q.packed) KS_TRY(sc.alloc(&Q.pv0, (size_t)(seg_cap * n_segs)));
+        if (attempt > 0) // (attempt 0: cleared with the flag word above; the flag word survives)
+            KS_HIP(ctx, hipMemset2DAsync(Q.cursor, (size_t)JN_CUR_STRIDE * sizeof(u64), 0, sizeof(u64), JN_SEGS, ctx->stream));
+        ks_timer_begin(ctx, "join_buckets");
+        // (few query postings per bucket: the table kernel; KS_DEBUG_JOIN_SPARSE = 0 / 1 forces the choice in the tests)
+        const bool sparse = ix->fp_layout && (ks_dbg(ctx, KS_DBG_JOIN_SPARSE) ? atoi(ks_dbg(ctx, KS_DBG_JOIN_SPARSE)) != 0
+                                                                             : Q.n_q / n_buckets <= (u64)JS_QCAP * 3 / 4);
+        if (sparse)
+            hipLaunchKernelGGL(q_fmt == 2 ? k_join_sparse<2> : (q_fmt ? k_join_sparse<1> : k_join_sparse<0>), dim3(n_buckets), dim3(JS_THREADS), 0, ctx->stream, (const u64 *)V.qk,
+                               (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta, V.q_lo,
+                               V.q_hi, dir_t, Q.pk0, Q.pv0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
+        else if (ix->fp_layout)
+            hipLaunchKernelGGL(q_fmt == 2 ? k_join_buckets<2> : (q_fmt ? k_join_buckets<1> : k_join_buckets<0>), dim3(n_buckets), dim3(JN_THREADS), 0, ctx->stream, (const u64 *)V.qk,
+                               (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta, V.q_lo,
+                               V.q_hi, dir_t, Q.pk0, Q.pv0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
+        else {
+            // workgroups per bucket: the matches per query posting of this context's previous search, when the buckets
+            // hold enough query postings to share (KS_DEBUG_JOIN_SPLIT forces it)
+            u32 split = 1;
+            if (ctx->pair_cap_hint > Q.n_q && Q.n_q / n_buckets >= 1024) { // (n_q may still be the pending sketch's upper bound)
+                const u64 dens2 = 2 * ctx->pair_cap_hint / Q.n_q;
+                split = dens2 >= 6 ? 4u : (dens2 >= 3 ? 2u : 1u); // 200k x 200k hp: 0.73 / 0.59 / 0.53 / 0.59 ms with 1 / 2 / 4 / 8
+            }
+            if (const char *f = ks_dbg(ctx, KS_DBG_JOIN_SPLIT)) { const int v = atoi(f); if (v >= 1 && v <= 16) split = (u32)v; }
+            hipLaunchKernelGGL(k_join_buckets_keys, dim3(n_buckets * split), dim3(JN_THREADS), 0, ctx->stream, (const u64 *)V.qk,
+                               (const u32 *)V.qv, (const u64 *)ix->d_keys, (const u32 *)ix->d_tids, (const u32 *)ix->d_abunds,
+                               V.q_lo, V.q_hi, dir_t, Q.pk0, Q.pv0, seg_cap, Q.cursor, Q.tbits, Q.abits, split);
+        }
+        ks_timer_end(ctx);
+        KS_HIP(ctx, hipGetLastError());
+        // the segment counts (+ the flag word beside the first): one copy, strided when the list is segmented
+        // (the kernel that stamps the host's flag writes them to the pinned block itself — with the control block of a
+        // pending sketch — instead of a copy dispatch per block in front of it)
+        {
+            ks_fetch_seg f[2];
+            f[0] = ks_fetch_seg{Q.cursor, (u32 *)pin, n_segs == 1 ? 1u : (u32)JN_SEGS, 4u, (u32)JN_CUR_STRIDE * 2u};
+            int nf = 1;
+            if (Q.q->pending) f[nf++] = ks_sketch_pending_seg(Q.q);
+            KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
+        }
+        KS_TRY(se_finish_pending(Q, sketch_redo));
+        if (Q.stop) return KS_OK;
+        Q.n_pairs = 0;
+        u64 seg_max = 0;
+        for (u32 s_ = 0; s_ < n_segs; s_++) {
+            Q.seg_count[s_] = pin[2 * s_];
+            Q.n_pairs += Q.seg_count[s_];
+            if (Q.seg_count[s_] > seg_max) seg_max = Q.seg_count[s_];
+        }
+        *overflowed = way == 0 && pin[1] != 0;
+        if (!*overflowed && Q.n_pairs >= KS_PAIR_LIMIT) { // saturated alphabets: the caller searches the queries in slices
+            *split_pairs = Q.n_pairs;
+            Q.stop = true;
+            return KS_OK;
+        }
+        if (*overflowed || seg_max <= seg_cap) return KS_OK;
+        if (attempt == 1)
+            return ks_fail(ctx, KS_ERR_CAPACITY, "search produced %llu matched posting pairs (segment cap %llu)",
+                           (unsigned long long)Q.n_pairs, (unsigned long long)seg_cap);
+        sc.free(Q.pk0); sc.free(Q.pv0); Q.pk0 = nullptr; Q.pv0 = nullptr;
+        Q.seg_cap = seg_max; // (same postings, same buckets, same segments: the repeat fits exactly)
+        ctx->join_retries++;
+    }
+    return KS_OK;
+}
+
+// sort matches by (qid, tid) on the live id bits only; *pk / *pv: the sorted list
+static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk, u32 **pv) {
+    const u64 n_pairs = Q.n_pairs;
+    const u32 n_segs = Q.n_segs;
+    const int tbits = Q.tbits, qbits = Q.qbits, abits = Q.abits;
+    const bool packed = Q.packed;
+    KS_TRY(sc.alloc(&Q.pk1, (size_t)n_pairs));
+    if (!packed) KS_TRY(sc.alloc(&Q.pv1, (size_t)n_pairs));
+    // Packed records go into the match sort as they lie: its first partition level reads the segments in place.  Only a list
+    // that sort declines (short lists, narrow keys: the LSD passes) or unpacked records are made dense by a copy first.
+    int msd = 0;
+    if (n_segs > 1 && packed) {
+        static_assert(JN_SEGS <= KS_MSD_MAX_SEGS, "segment table of the match sort");
+        ks_msd_segs sg;
+        sg.n = n_segs; sg.seg_cap = Q.seg_cap;
+        u32 t = 0;
+        for (u32 s_ = 0; s_ < n_segs; s_++) {
+            sg.tile_start[s_] = t; sg.count[s_] = (u32)Q.seg_count[s_];
+            t += (u32)((Q.seg_count[s_] + 8191) / 8192); // (MS_TILE records per level-1 tile, ks_msd.hip)
+        }
+        sg.tile_start[n_segs] = t;
+        for (u32 s_ = n_segs + 1; s_ <= KS_MSD_MAX_SEGS; s_++) sg.tile_start[s_] = t;
+        KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, abits, tbits + qbits, &msd, &sg));
+    }
+    if (n_segs > 1 && !msd) { // the segments -> one dense list (then the roles of the two buffers swap: the segmented one is the scratch)
+        jn_seg_table tab;
+        u64 acc = 0;
+        for (u32 s_ = 0; s_ < n_segs; s_++) { tab.prefix[s_] = acc; acc += Q.seg_count[s_]; }
+        tab.prefix[n_segs] = acc;
+        u64 seg_max = 0;
+        for (u32 s_ = 0; s_ < n_segs; s_++) if (Q.seg_count[s_] > seg_max) seg_max = Q.seg_count[s_];
+        KS_LAUNCH(ctx, "pairs_compact", k_pairs_compact, dim3((u32)((seg_max + 2047) / 2048), n_segs), 256, (const u64 *)Q.pk0,
+                  (const u32 *)Q.pv0, Q.seg_cap, tab, Q.pk1, Q.pv1);
+        u64 *tk = Q.pk0; Q.pk0 = Q.pk1; Q.pk1 = tk;
+        u32 *tv = Q.pv0; Q.pv0 = Q.pv1; Q.pv1 = tv;
+    }
+    *pk = nullptr;
+    *pv = nullptr;
+    int shifts[8], ns = 0;
+    for (int sh = 0; sh < tbits + qbits; sh += 8) shifts[ns++] = abits + sh;
+    // the match list (pk0, pv0) is scratch from here on: ping-pong with (pk1, pv1).  Packed records: three moves
+    // (two exact MSD partition levels + in-LDS bucket sort, ks_msd.hip) instead of one per 8 key bits
+    if (packed && !msd) KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, abits, tbits + qbits, &msd));
+    if (msd) *pk = Q.pk0;
+    else if (packed) KS_TRY(ks_radix_sort_keys(ctx, KS_SORT_PAIRS, Q.pk0, Q.pk0, Q.pk1, n_pairs, shifts, ns, pk));
+    else KS_TRY(ks_radix_sort_u32(ctx, KS_SORT_PAIRS, Q.pk0, Q.pv0, Q.pk0, Q.pv0, Q.pk1, Q.pv1, n_pairs, shifts, ns, pk, pv));
+    return KS_OK;
+}
+
+// run-length reduce of the sorted matches into H's rows: one fused pass for packed records (k_pair_rows_fused); heads + scan
+// + reduce when the abundances travel apart (ids + abundance wider than 64 bits)
+static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk, const u32 *pv, ks_scratch &sc) {
+    const u64 n_pairs = Q.n_pairs;
+    const int tbits = Q.tbits, abits = Q.abits;
+    const bool fused = Q.packed && !ks_dbg(ctx, KS_DBG_UNFUSED_ROWS);
+    const u32 gp = (u32)((n_pairs + 255) / 256);
+    const u32 pf_tiles = (u32)((n_pairs + PF_TILE - 1) / PF_TILE);
+    unsigned long long *pf_status = nullptr;
+    u32 *pf_ticket = nullptr, *heads = nullptr, *d_nrows = nullptr;
+    u32 *nrows_dev = nullptr;
+    if (!fused) { // (fused: the status words, the ticket pair and the row count lie in one block WITH the two row arrays the
+                  // pass adds into — allocated below, per attempt: one memset, one read-back)
+        KS_TRY(sc.alloc(&d_nrows, 1));
+        nrows_dev = d_nrows;
+        KS_TRY(sc.alloc(&heads, (size_t)n_pairs));
+        KS_LAUNCH(ctx, "pair_heads", k_pair_heads, gp, 256, pk, n_pairs, heads, abits);
+        KS_TRY(ks_scan_u32_inplace(ctx, heads, n_pairs, d_nrows));
+    }
+    // The row count is only known on the device here.  Instead of a round trip before the reduce, the row arrays take
+    // their size from the previous search of this context (+ 25 %) and the count is read with the final
+    // synchronisation; a search that produced more rows than that repeats the (cheap) reduce with exact arrays.
+    u64 rows_cap = n_pairs;
+    if (ctx->rows_hint && ctx->rows_hint < rows_cap && !ks_dbg(ctx, KS_DBG_NO_ROWS_HINT)) rows_cap = ctx->rows_hint;
+    u32 n_rows = 0;
+    const u32 *pin = (const u32 *)(ctx->h_pin + KS_PIN_ROWS); // ticket pair | row count
+    for (int attempt = 0; attempt < 3; attempt++) { // (repeats: more rows than the guess; a look-back that gave up)
+        KS_TRY(ks_alloc(ctx, &H->d_qid, (size_t)rows_cap)); KS_TRY(ks_alloc(ctx, &H->d_tid, (size_t)rows_cap));
+        {
+            // n_weighted (u64) | status words + ticket pair + row count (u64) | intersect (u32): zeroed together
+            const size_t st_words = fused ? (size_t)pf_tiles + 2 : 0, is_words = ((size_t)rows_cap + 1) / 2;
+            KS_TRY(ks_alloc(ctx, &H->d_block, (size_t)rows_cap + st_words + is_words));
+            H->d_nw = H->d_block;
+            H->d_isect = (u32 *)(H->d_block + rows_cap + st_words);
+            if (fused) {
+                pf_status = (unsigned long long *)(H->d_block + rows_cap);
+                pf_ticket = (u32 *)(pf_status + pf_tiles);
+                nrows_dev = pf_ticket + 2;
+            }
+            KS_HIP(ctx, hipMemsetAsync(H->d_block, 0, ((size_t)rows_cap + st_words + is_words) * sizeof(u64), ctx->stream));
+        }
+        if (fused)
+            KS_LAUNCH(ctx, "pair_rows", k_pair_rows_fused, pf_tiles, PF_THREADS, pk, n_pairs, H->d_qid, H->d_tid, H->d_isect,
+                      (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, nrows_dev,
+                      (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
+        else
+            KS_LAUNCH(ctx, "pair_reduce", k_pair_reduce, gp, 256, pk, pv, (const u32 *)heads, n_pairs, H->d_qid, H->d_tid, H->d_isect,
+                      (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap);
+        {
+            ks_fetch_seg f[2];
+            f[0] = fused ? ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4) // ticket pair + row count
+                         : ks_fetch_words(d_nrows, ctx->h_pin + KS_PIN_ROWS + 1, 1);
+            const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
+            KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
+        }
+        KS_TRY(ks_scan_status_check(ctx));
+        bool gave_up = fused && pin[1] != 0;
+        if (fused && ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY) && !ctx->rows_use_ticket) gave_up = true; // (tests)
+        if (gave_up) {
+            if (ctx->rows_use_ticket || attempt == 2) return ks_fail(ctx, KS_ERR_HIP, "search: row look-back gave up waiting for a predecessor tile");
+            ctx->rows_use_ticket = true; // dispatch order did not hold here: tickets from now on
+            ctx->rows_ticket_fallbacks++;
+        } else {
+            n_rows = pin[2]; // (fused: third word of the block fetched to the slot; else fetched there)
+            if (n_rows <= rows_cap) break;
+            rows_cap = n_rows;
+        }
+        ks_pool_free(ctx, H->d_qid); ks_pool_free(ctx, H->d_tid); ks_pool_free(ctx, H->d_block);
+        H->d_qid = H->d_tid = H->d_isect = nullptr; H->d_nw = nullptr; H->d_block = nullptr;
+    }
+    if (!H->d_qid) return ks_fail(ctx, KS_ERR_HIP, "search: the row pass did not settle");
+    H->n_hits = n_rows;
+    const u64 want = (u64)n_rows + n_rows / 4 + 4096;
+    ctx->rows_hint = want > ctx->rows_hint / 2 ? want : ctx->rows_hint / 2; // follows growth at once, decays slowly
+    return KS_OK;
+}
+
+static int se_no_hits(ks_ctx *ctx, ks_hits *H) {
+    KS_TRY(ks_alloc(ctx, &H->d_qid, 1)); KS_TRY(ks_alloc(ctx, &H->d_tid, 1));
+    KS_TRY(ks_alloc(ctx, &H->d_isect, 1)); KS_TRY(ks_alloc(ctx, &H->d_nw, 1));
+    return KS_OK;
+}
+
+static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits *H, u64 *split_pairs, int *sketch_redo, bool *stop) {
+    se_search Q;
+    memset(&Q, 0, sizeof Q);
+    Q.ix = ix; Q.q = q; Q.n_q = q->n_hashes;
+    const u64 n_t = ix->n_postings;
+    if (q->pending && (n_t == 0 || !(q->part_keys && q->part_pbits == ix->pbits && ix->pbits > 0))) {
+        // (no postings for this index: the partition starts from the CSR and needs the exact counts)
+        KS_TRY(se_wait_pending(ctx, Q, sketch_redo));
+        if ((*stop = Q.stop)) return KS_OK;
+    }
+    if (Q.n_q == 0 || n_t == 0) return se_no_hits(ctx, H);
+    Q.pbits = ix->pbits;
+    Q.n_buckets = 1u << Q.pbits;
+    Q.tbits = bits_for(ix->n_targets); // pair key = qid << tbits | tid
+    // a match is one 8-byte record (qid, tid, target abundance) whenever the three fit 64 bits — always, short of
+    // ~10^5 x 10^5 proteins with 2^30-fold repeats — so the match sort moves keys only; else ids and abundance travel apart
+    Q.qbits = bits_for(q->n_seqs);
+    Q.abits = bits_for_value(ix->max_abund);
+    Q.packed = Q.tbits + Q.qbits + Q.abits <= 64 && !ks_dbg(ctx, KS_DBG_UNPACKED_PAIRS);
+    if (!Q.packed) Q.abits = 0;
+    Q.pfxK = ks_join_prefix_mul(Q.pbits, ks_max_hash(ix->params.scaled));
+    ks_scratch sc(ctx);
+    KS_TRY(sc.alloc(&Q.dir_q, (size_t)2 * Q.n_buckets + 2));
+    KS_TRY(sc.alloc((u64 **)&Q.cursor, (size_t)JN_SEGS * JN_CUR_STRIDE + (Q.n_buckets + 1) / 2));
+    Q.bcur = (u32 *)(Q.cursor + (size_t)JN_SEGS * JN_CUR_STRIDE);
+    const bool pre_any = q->part_keys && q->part_pbits == Q.pbits && q->part_K == Q.pfxK && Q.pbits > 0;
+    // (10-byte postings are read by the bucket scatter and the fingerprint joins only: the dense fall-back starts from the
+    // CSR, and so does a search against an index they were not made for)
+    const bool f10_fits = ix->fp_layout && Q.pbits > 8 && q->part_s == 32u + (u32)ix->fp_shift;
+    Q.pre = pre_any && (q->part_s == 0 || f10_fits);
+    Q.f10 = Q.pre && q->part_s != 0;
+    if (q->pending && !Q.pre) {
+        KS_TRY(se_wait_pending(ctx, Q, sketch_redo));
+        if ((*stop = Q.stop)) return KS_OK;
+    }
+    u64 cap = Q.n_q < (1u << 20) ? (1u << 20) : Q.n_q;
+    if (ctx->pair_cap_hint > cap) cap = ctx->pair_cap_hint; // a workload that matched heavily last time will again
+    for (int way = (Q.pre && Q.pbits > 8) ? 0 : 1; way < 2; way++) {
+        se_qview V;
+        KS_TRY(se_partition(ctx, Q, way, sc, &V));
+        if (V.bucket_posting_bytes) H->bucket_posting_bytes = V.bucket_posting_bytes;
+        bool overflowed = false;
+        KS_TRY(se_join(ctx, Q, V, way, cap, sc, split_pairs, sketch_redo, &overflowed));
+        if ((*stop = Q.stop)) return KS_OK;
+        sc.free(V.qk0); sc.free(V.qk1); sc.free(V.qv0); sc.free(V.qv1);
+        if (!overflowed) {
+            H->partition_path = V.partition_path;
+            break;
+        }
+        // a bucket overflowed (skewed hashes): drop the partial result and partition the dense way
+        sc.free(Q.pk0); sc.free(Q.pv0); Q.pk0 = nullptr; Q.pv0 = nullptr;
+    }
+    H->n_pair_instances = Q.n_pairs;
+    const u64 want = Q.n_pairs + Q.n_pairs / 8;
+    ctx->pair_cap_hint = want > ctx->pair_cap_hint / 2 ? want : ctx->pair_cap_hint / 2; // follows growth at once, decays slowly
+    if (Q.n_pairs == 0) return se_no_hits(ctx, H);
+    u64 *pk = nullptr;
+    u32 *pv = nullptr;
+    KS_TRY(se_sort(ctx, Q, sc, &pk, &pv));
+    return se_rows(ctx, Q, H, pk, pv, sc);
+}
+
 // One search with the whole query batch in one match list.  *split_pairs != 0 on return (with KS_OK and *out == NULL) means
 // the list would hold that many records — more than one list can (2^32) — and nothing was produced: the caller splits.
 // q->pending (ks_sketch_search_device): the sketch launches are queued and nobody has waited for them; the first wait of
@@ -1335,361 +1723,11 @@ static int search_core(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks
     ks_hits *H = new ks_hits();
     memset(H, 0, sizeof *H);
     H->ctx = ctx;
-    u64 n_q = q->n_hashes;
-    const u64 n_t = ix->n_postings;
-    u64 *qk0 = nullptr, *qk1 = nullptr, *pk0 = nullptr, *pk1 = nullptr, *row_start = nullptr, *dir_q = nullptr;
-    u32 *qv0 = nullptr, *qv1 = nullptr, *pv0 = nullptr, *pv1 = nullptr, *heads = nullptr, *d_nrows = nullptr;
-    unsigned long long *cursor = nullptr, *pf_status = nullptr;
-    u32 *pf_ticket = nullptr;
-    int st = KS_OK;
-    bool split = false;
-    // the exact counts of a pending sketch, behind a wait; a sketch that has to be repeated ends the search (split: nothing produced)
-#define SE_FINISH_PENDING() do { if (q->pending) { int redo_ = 0; st = ks_sketch_finish_pending(const_cast<ks_sketches *>(q), &redo_); \
-        if (st != KS_OK) goto done; n_q = q->n_hashes; if (redo_) { if (sketch_redo) *sketch_redo = redo_; split = true; goto done; } } } while (0)
-#define SE_CHECK(x) do { st = (x); if (st != KS_OK) goto done; } while (0)
-#define SE_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { st = ks_fail(ctx, KS_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-    if (q->pending && (n_t == 0 || !(q->part_keys && q->part_pbits == ix->pbits && ix->pbits > 0))) {
-        // (no postings for this index: the partition starts from the CSR and needs the exact counts)
-        { const ks_fetch_seg f = ks_sketch_pending_seg(q); SE_CHECK(ks_stream_wait_fetch(ctx, &f, 1)); }
-        SE_FINISH_PENDING();
-    }
-    if (n_q == 0 || n_t == 0) {
-        SE_CHECK(ks_alloc(ctx, &H->d_qid, 1)); SE_CHECK(ks_alloc(ctx, &H->d_tid, 1));
-        SE_CHECK(ks_alloc(ctx, &H->d_isect, 1)); SE_CHECK(ks_alloc(ctx, &H->d_nw, 1));
-        *out = H;
-        return KS_OK;
-    }
-    {
-        // ---- query postings grouped on the top pbits hash bits (the join needs locality, not order)
-        const int pbits = ix->pbits;
-        const u32 n_buckets = 1u << pbits;
-        const int tbits = bits_for(ix->n_targets); // pair key = qid << tbits | tid
-        // a match is one 8-byte record (qid, tid, target abundance) whenever the three fit 64 bits — always, short of
-        // ~10^5 x 10^5 proteins with 2^30-fold repeats — so the match sort moves keys only; else ids and abundance travel apart
-        const int qbits = bits_for(q->n_seqs);
-        int abits = bits_for_value(ix->max_abund);
-        const bool packed = tbits + qbits + abits <= 64 && !ks_dbg(ctx, KS_DBG_UNPACKED_PAIRS);
-        if (!packed) abits = 0;
-        const u32 pfxK = ks_join_prefix_mul(pbits, ks_max_hash(ix->params.scaled));
-        SE_CHECK(ks_alloc(ctx, &dir_q, (size_t)2 * n_buckets + 2));
-        const u64 *dir_t = ix->d_dir; // built with the index
-        // cursor block: segment s of the pair list counts at word s * JN_CUR_STRIDE; word 1 = "a query bucket overflowed"
-        // (k_bucket_scatter)
-        // (+ the join buckets' fill counts right behind it: one allocation, one memset)
-        SE_CHECK(ks_alloc(ctx, (u64 **)&cursor, (size_t)JN_SEGS * JN_CUR_STRIDE + (n_buckets + 1) / 2));
-        u32 *const bcur = (u32 *)(cursor + (size_t)JN_SEGS * JN_CUR_STRIDE);
-        const bool pre_any = q->part_keys && q->part_pbits == pbits && q->part_K == pfxK && pbits > 0;
-        // (10-byte postings are read by the bucket scatter and the fingerprint joins only: the dense fall-back starts from the
-        // CSR, and so does a search against an index they were not made for)
-        const bool f10_fits = ix->fp_layout && pbits > 8 && q->part_s == 32u + (u32)ix->fp_shift;
-        bool pre = pre_any && (q->part_s == 0 || f10_fits);
-        const bool f10 = pre && q->part_s != 0;
-        if (q->pending && !pre) {
-            const ks_fetch_seg f = ks_sketch_pending_seg(q);
-            SE_CHECK(ks_stream_wait_fetch(ctx, &f, 1));
-            SE_FINISH_PENDING();
-        }
-        u64 cap = n_q < (1u << 20) ? (1u << 20) : n_q;
-        if (ctx->pair_cap_hint > cap) cap = ctx->pair_cap_hint; // a workload that matched heavily last time will again
-        u64 n_pairs = 0, seg_cap = 0, seg_count[JN_SEGS];
-        u32 n_segs = 1;
-        // way 0: histogram-free bucket scatter of the sketch kernel's regions (may overflow on skewed hashes);
-        // way 1: the dense, always-correct partition
-        for (int way = (pre && pbits > 8) ? 0 : 1; way < 2; way++) {
-            if (way == 1 && f10) pre = false;
-            const u32 q_s = (way == 0 && f10) ? q->part_s : 0u;
-            // behind the bucket scatter of a 16-bit join prefix both prefix bytes are implied by the bucket: 9-byte postings
-            // (KS_DEBUG_POSTINGS10 keeps the 10-byte form there)
-            const int q_fmt = q_s ? ((pbits == 16 && q_s == 48u && !ks_dbg(ctx, KS_DBG_POSTINGS10)) ? 2 : 1) : 0;
-            u64 *qk = nullptr;
-            u32 *qv = nullptr;
-            const u64 *q_lo = nullptr, *q_hi = nullptr;
-            SE_HIP(hipMemsetAsync(cursor, 0, ((size_t)JN_SEGS * JN_CUR_STRIDE + (way == 0 ? (n_buckets + 1) / 2 : 0)) * sizeof(u64), ctx->stream));
-            if (way == 0) {
-                const u64 per = n_q / n_buckets;
-                const u32 bcap = (u32)(per + per / 8 + 512);
-                SE_CHECK(ks_alloc(ctx, &qk0, (size_t)n_buckets * bcap));
-                SE_CHECK(ks_alloc(ctx, &qv0, (size_t)n_buckets * bcap));
-                ks_rs_segments seg{q->part_len, q->part_cap, q->part_regions << q->part_sub_shift, q->part_sub_shift};
-                SE_CHECK(ks_bucket_scatter_u32(ctx, q->part_keys, q->part_vals, &seg, 8, pfxK, qk0, qv0, bcur, bcap, cursor, n_buckets >> 8,
-                                               q_fmt)); // (10-byte postings stay 10 bytes, or lose one more: the join decodes them)
-                H->bucket_posting_bytes = q_fmt == 2 ? 9 : (q_fmt == 1 ? 10 : 12);
-                ks_timer_begin(ctx, "bucket_dir");
-                hipLaunchKernelGGL(k_region_dir, dim3((n_buckets + 255) / 256), dim3(256), 0, ctx->stream, (const u32 *)bcur, (u64)bcap,
-                                   n_buckets, dir_q, dir_q + n_buckets, n_buckets >> 8);
-                ks_timer_end(ctx);
-                qk = qk0; qv = qv0; q_lo = dir_q; q_hi = dir_q + n_buckets;
-            } else if (pre && pbits <= 8) {
-                // the sketch kernel already wrote one region per bucket
-                qk = q->part_keys; qv = q->part_vals;
-                ks_timer_begin(ctx, "bucket_dir");
-                hipLaunchKernelGGL(k_region_dir, dim3((n_buckets + 255) / 256), dim3(256), 0, ctx->stream, (const u32 *)q->part_len,
-                                   q->part_cap, n_buckets, dir_q, dir_q + n_buckets, 0u);
-                ks_timer_end(ctx);
-                q_lo = dir_q; q_hi = dir_q + n_buckets;
-            } else {
-                if (!pre) SE_CHECK(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(q))); // (this partition starts from the CSR)
-                SE_CHECK(ks_alloc(ctx, &qk0, (size_t)n_q)); SE_CHECK(ks_alloc(ctx, &qk1, (size_t)n_q));
-                SE_CHECK(ks_alloc(ctx, &qv0, (size_t)n_q)); SE_CHECK(ks_alloc(ctx, &qv1, (size_t)n_q));
-                if (pre) {
-                    // the sketch kernel did the low digit; segmented (histogram + scan) passes on the high bits finish
-                    int shifts[2], nsh = 0;
-                    for (int sh = 8; sh < pbits; sh += 8) shifts[nsh++] = sh; // bits [8, pbits) of the join prefix
-                    ks_rs_segments seg{q->part_len, q->part_cap, q->part_regions << q->part_sub_shift, q->part_sub_shift};
-                    SE_CHECK(ks_radix_sort_u32(ctx, KS_SORT_QPART, q->part_keys, q->part_vals, qk1, qv1, qk0, qv0, n_q, shifts, nsh,
-                                               &qk, &qv, &seg, pfxK));
-                } else {
-                    ks_timer_begin(ctx, "fill_query_vals");
-                    hipLaunchKernelGGL(k_fill_query_vals, dim3((q->n_seqs + 3) / 4), dim3(256), 0, ctx->stream, (const u64 *)q->d_offsets, q->n_seqs, qv0);
-                    ks_timer_end(ctx);
-                    SE_HIP(hipGetLastError());
-                    // hashes are read straight from the query sketches on the first pass (no staging copy);
-                    // qv0 holds the input qids, so the first pass lands in (qk1, qv1)
-                    int shifts[3], ns = 0;
-                    for (int sh = 0; sh < pbits; sh += 8) shifts[ns++] = sh; // digits of the join prefix, low first
-                    SE_CHECK(ks_radix_sort_u32(ctx, KS_SORT_QPART, q->d_hashes, qv0, qk1, qv1, qk0, qv0, n_q, shifts, ns, &qk, &qv,
-                                               nullptr, pfxK));
-                }
-                ks_timer_begin(ctx, "bucket_dir");
-                hipLaunchKernelGGL(k_bucket_dir, dim3((n_buckets + 256) / 256), dim3(256), 0, ctx->stream, (const u64 *)qk, n_q, pbits, pfxK, dir_q);
-                ks_timer_end(ctx);
-                q_lo = dir_q; q_hi = dir_q + 1;
-            }
-            SE_HIP(hipGetLastError());
-
-            // join, with a retry if the match list outgrows its first guess.  Many (bucket, round) reservations: the list is cut
-            // into segments with a cursor each (see the kernel) and made dense by one copy afterwards; few: one cursor, no copy.
-            bool overflowed = false;
-            {
-                const u64 per_bucket = n_q / n_buckets, round = (u64)JN_THREADS * JN_E;
-                const u64 reservations = (u64)n_buckets * ((per_bucket + round - 1) / round ? (per_bucket + round - 1) / round : 1);
-                n_segs = (ix->fp_layout && reservations >= 8192 && n_buckets >= JN_SEGS && !ks_dbg(ctx, KS_DBG_ONE_CURSOR)) ? JN_SEGS : 1;
-                if (ix->fp_layout && ks_dbg(ctx, KS_DBG_JOIN_SEGS) && n_buckets >= JN_SEGS) n_segs = JN_SEGS; // (tests: small inputs through the segmented path)
-            }
-            seg_cap = n_segs == 1 ? cap : cap / n_segs + cap / n_segs / 8 + 4096;
-            if (ks_dbg(ctx, KS_DBG_JOIN_SEG_CAP)) seg_cap = strtoull(ks_dbg(ctx, KS_DBG_JOIN_SEG_CAP), nullptr, 10); // (tests: the retry)
-            for (int attempt = 0; attempt < 2; attempt++) {
-                SE_CHECK(ks_alloc(ctx, &pk0, (size_t)(seg_cap * n_segs)));
-                if (!packed) SE_CHECK(ks_alloc(ctx, &pv0, (size_t)(seg_cap * n_segs)));
-                if (attempt > 0) // (attempt 0: cleared with the flag word above; the flag word survives)
-                    SE_HIP(hipMemset2DAsync(cursor, (size_t)JN_CUR_STRIDE * sizeof(u64), 0, sizeof(u64), JN_SEGS, ctx->stream));
-                ks_timer_begin(ctx, "join_buckets");
-                // (few query postings per bucket: the table kernel; KS_DEBUG_JOIN_SPARSE = 0 / 1 forces the choice in the tests)
-                const bool sparse = ix->fp_layout && (ks_dbg(ctx, KS_DBG_JOIN_SPARSE) ? atoi(ks_dbg(ctx, KS_DBG_JOIN_SPARSE)) != 0
-                                                                                     : n_q / n_buckets <= (u64)JS_QCAP * 3 / 4);
-                if (sparse)
-                    hipLaunchKernelGGL(q_fmt == 2 ? k_join_sparse<2> : (q_fmt ? k_join_sparse<1> : k_join_sparse<0>), dim3(n_buckets), dim3(JS_THREADS), 0, ctx->stream, (const u64 *)qk,
-                                       (const u32 *)qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta, q_lo,
-                                       q_hi, dir_t, pk0, pv0, seg_cap, cursor, n_segs - 1, tbits, abits, ix->fp_shift);
-                else if (ix->fp_layout)
-                    hipLaunchKernelGGL(q_fmt == 2 ? k_join_buckets<2> : (q_fmt ? k_join_buckets<1> : k_join_buckets<0>), dim3(n_buckets), dim3(JN_THREADS), 0, ctx->stream, (const u64 *)qk,
-                                       (const u32 *)qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta, q_lo,
-                                       q_hi, dir_t, pk0, pv0, seg_cap, cursor, n_segs - 1, tbits, abits, ix->fp_shift);
-                else {
-                    // workgroups per bucket: the matches per query posting of this context's previous search, when the buckets
-                    // hold enough query postings to share (KS_DEBUG_JOIN_SPLIT forces it)
-                    u32 split = 1;
-                    if (ctx->pair_cap_hint > n_q && n_q / n_buckets >= 1024) { // (n_q may still be the pending sketch's upper bound)
-                        const u64 dens2 = 2 * ctx->pair_cap_hint / n_q;
-                        split = dens2 >= 6 ? 4u : (dens2 >= 3 ? 2u : 1u); // 200k x 200k hp: 0.73 / 0.59 / 0.53 / 0.59 ms with 1 / 2 / 4 / 8
-                    }
-                    if (const char *f = ks_dbg(ctx, KS_DBG_JOIN_SPLIT)) { const int v = atoi(f); if (v >= 1 && v <= 16) split = (u32)v; }
-                    hipLaunchKernelGGL(k_join_buckets_keys, dim3(n_buckets * split), dim3(JN_THREADS), 0, ctx->stream, (const u64 *)qk,
-                                       (const u32 *)qv, (const u64 *)ix->d_keys, (const u32 *)ix->d_tids, (const u32 *)ix->d_abunds,
-                                       q_lo, q_hi, dir_t, pk0, pv0, seg_cap, cursor, tbits, abits, split);
-                }
-                ks_timer_end(ctx);
-                SE_HIP(hipGetLastError());
-                // the segment counts (+ the flag word beside the first): one copy, strided when the list is segmented
-                // (the kernel that stamps the host's flag writes them to the pinned block itself — with the control block of a
-                // pending sketch — instead of a copy dispatch per block in front of it)
-                {
-                    ks_fetch_seg f[2];
-                    f[0] = ks_fetch_seg{cursor, (u32 *)ctx->h_pin, n_segs == 1 ? 1u : (u32)JN_SEGS, 4u, (u32)JN_CUR_STRIDE * 2u};
-                    int nf = 1;
-                    if (q->pending) f[nf++] = ks_sketch_pending_seg(q);
-                    SE_CHECK(ks_stream_wait_fetch(ctx, f, nf));
-                }
-                SE_FINISH_PENDING();
-                n_pairs = 0;
-                u64 seg_max = 0;
-                for (u32 s_ = 0; s_ < n_segs; s_++) {
-                    seg_count[s_] = ctx->h_pin[2 * s_];
-                    n_pairs += seg_count[s_];
-                    if (seg_count[s_] > seg_max) seg_max = seg_count[s_];
-                }
-                overflowed = way == 0 && ctx->h_pin[1] != 0;
-                if (!overflowed && n_pairs >= KS_PAIR_LIMIT) { // saturated alphabets: the caller searches the queries in slices
-                    *split_pairs = n_pairs;
-                    split = true;
-                    goto done;
-                }
-                if (overflowed || seg_max <= seg_cap) break;
-                if (attempt == 1) {
-                    st = ks_fail(ctx, KS_ERR_CAPACITY, "search produced %llu matched posting pairs (segment cap %llu)",
-                                 (unsigned long long)n_pairs, (unsigned long long)seg_cap);
-                    goto done;
-                }
-                ks_pool_free(ctx, pk0); ks_pool_free(ctx, pv0); pk0 = nullptr; pv0 = nullptr;
-                seg_cap = seg_max; // (same postings, same buckets, same segments: the repeat fits exactly)
-                ctx->join_retries++;
-            }
-            ks_pool_free(ctx, qk0); ks_pool_free(ctx, qk1); ks_pool_free(ctx, qv0); ks_pool_free(ctx, qv1);
-            qk0 = qk1 = nullptr; qv0 = qv1 = nullptr;
-            if (!overflowed) {
-                H->partition_path = way == 0 ? 1 : (pre ? (pbits <= 8 ? 0 : 2) : 3);
-                break;
-            }
-            // a bucket overflowed (skewed hashes): drop the partial result and partition the dense way
-            ks_pool_free(ctx, pk0); ks_pool_free(ctx, pv0); pk0 = nullptr; pv0 = nullptr;
-        }
-        H->n_pair_instances = n_pairs;
-        {
-            const u64 want = n_pairs + n_pairs / 8;
-            ctx->pair_cap_hint = want > ctx->pair_cap_hint / 2 ? want : ctx->pair_cap_hint / 2; // follows growth at once, decays slowly
-        }
-        if (n_pairs == 0) {
-            SE_CHECK(ks_alloc(ctx, &H->d_qid, 1)); SE_CHECK(ks_alloc(ctx, &H->d_tid, 1));
-            SE_CHECK(ks_alloc(ctx, &H->d_isect, 1)); SE_CHECK(ks_alloc(ctx, &H->d_nw, 1));
-            goto done;
-        }
-        // sort matches by (qid, tid) on the live id bits only
-        SE_CHECK(ks_alloc(ctx, &pk1, (size_t)n_pairs));
-        if (!packed) SE_CHECK(ks_alloc(ctx, &pv1, (size_t)n_pairs));
-        // Packed records go into the match sort as they lie: its first partition level reads the segments in place.  Only a list
-        // that sort declines (short lists, narrow keys: the LSD passes) or unpacked records are made dense by a copy first.
-        int msd = 0;
-        if (n_segs > 1 && packed) {
-            static_assert(JN_SEGS <= KS_MSD_MAX_SEGS, "segment table of the match sort");
-            ks_msd_segs sg;
-            sg.n = n_segs; sg.seg_cap = seg_cap;
-            u32 t = 0;
-            for (u32 s_ = 0; s_ < n_segs; s_++) {
-                sg.tile_start[s_] = t; sg.count[s_] = (u32)seg_count[s_];
-                t += (u32)((seg_count[s_] + 8191) / 8192); // (MS_TILE records per level-1 tile, ks_msd.hip)
-            }
-            sg.tile_start[n_segs] = t;
-            for (u32 s_ = n_segs + 1; s_ <= KS_MSD_MAX_SEGS; s_++) sg.tile_start[s_] = t;
-            SE_CHECK(ks_sort_pairs_msd(ctx, pk0, pk1, n_pairs, abits, tbits + qbits, &msd, &sg));
-        }
-        if (n_segs > 1 && !msd) { // the segments -> one dense list (then the roles of the two buffers swap: the segmented one is the scratch)
-            jn_seg_table tab;
-            u64 acc = 0;
-            for (u32 s_ = 0; s_ < n_segs; s_++) { tab.prefix[s_] = acc; acc += seg_count[s_]; }
-            tab.prefix[n_segs] = acc;
-            u64 seg_max = 0;
-            for (u32 s_ = 0; s_ < n_segs; s_++) if (seg_count[s_] > seg_max) seg_max = seg_count[s_];
-            ks_timer_begin(ctx, "pairs_compact");
-            hipLaunchKernelGGL(k_pairs_compact, dim3((u32)((seg_max + 2047) / 2048), n_segs), dim3(256), 0, ctx->stream, (const u64 *)pk0,
-                               (const u32 *)pv0, seg_cap, tab, pk1, pv1);
-            ks_timer_end(ctx);
-            SE_HIP(hipGetLastError());
-            u64 *tk = pk0; pk0 = pk1; pk1 = tk;
-            u32 *tv = pv0; pv0 = pv1; pv1 = tv;
-        }
-        u64 *pk = nullptr;
-        u32 *pv = nullptr;
-        {
-            int shifts[8], ns = 0;
-            for (int sh = 0; sh < tbits + qbits; sh += 8) shifts[ns++] = abits + sh;
-            // the match list (pk0, pv0) is scratch from here on: ping-pong with (pk1, pv1).  Packed records: three moves
-            // (two exact MSD partition levels + in-LDS bucket sort, ks_msd.hip) instead of one per 8 key bits
-            if (packed && !msd) SE_CHECK(ks_sort_pairs_msd(ctx, pk0, pk1, n_pairs, abits, tbits + qbits, &msd));
-            if (msd) pk = pk0;
-            else if (packed) SE_CHECK(ks_radix_sort_keys(ctx, KS_SORT_PAIRS, pk0, pk0, pk1, n_pairs, shifts, ns, &pk));
-            else SE_CHECK(ks_radix_sort_u32(ctx, KS_SORT_PAIRS, pk0, pv0, pk0, pv0, pk1, pv1, n_pairs, shifts, ns, &pk, &pv));
-        }
-        // run-length reduce: one fused pass for packed records (k_pair_rows_fused); heads + scan + reduce when the
-        // abundances travel apart (ids + abundance wider than 64 bits)
-        const bool fused = packed && !ks_dbg(ctx, KS_DBG_UNFUSED_ROWS);
-        const u32 gp = (u32)((n_pairs + 255) / 256);
-        const u32 pf_tiles = (u32)((n_pairs + PF_TILE - 1) / PF_TILE);
-        u32 *nrows_dev = nullptr;
-        if (fused) { // status words, the ticket pair and the row count in one block WITH the two row arrays the pass adds into
-                     // (allocated below, per attempt): one memset, one read-back
-        } else {
-            SE_CHECK(ks_alloc(ctx, &d_nrows, 1));
-            nrows_dev = d_nrows;
-            SE_CHECK(ks_alloc(ctx, &heads, (size_t)n_pairs));
-            ks_timer_begin(ctx, "pair_heads");
-            hipLaunchKernelGGL(k_pair_heads, dim3(gp), dim3(256), 0, ctx->stream, (const u64 *)pk, n_pairs, heads, abits);
-            ks_timer_end(ctx);
-            SE_CHECK(ks_scan_u32_inplace(ctx, heads, n_pairs, d_nrows));
-        }
-        // The row count is only known on the device here.  Instead of a round trip before the reduce, the row arrays take
-        // their size from the previous search of this context (+ 25 %) and the count is read with the final
-        // synchronisation; a search that produced more rows than that repeats the (cheap) reduce with exact arrays.
-        u64 rows_cap = n_pairs;
-        if (ctx->rows_hint && ctx->rows_hint < rows_cap && !ks_dbg(ctx, KS_DBG_NO_ROWS_HINT)) rows_cap = ctx->rows_hint;
-        u32 n_rows = 0;
-        for (int attempt = 0; attempt < 3; attempt++) { // (repeats: more rows than the guess; a look-back that gave up)
-            SE_CHECK(ks_alloc(ctx, &H->d_qid, (size_t)rows_cap)); SE_CHECK(ks_alloc(ctx, &H->d_tid, (size_t)rows_cap));
-            {
-                // n_weighted (u64) | status words + ticket pair + row count (u64) | intersect (u32): zeroed together
-                const size_t st_words = fused ? (size_t)pf_tiles + 2 : 0, is_words = ((size_t)rows_cap + 1) / 2;
-                SE_CHECK(ks_alloc(ctx, &H->d_block, (size_t)rows_cap + st_words + is_words));
-                H->d_nw = H->d_block;
-                H->d_isect = (u32 *)(H->d_block + rows_cap + st_words);
-                if (fused) {
-                    pf_status = (unsigned long long *)(H->d_block + rows_cap);
-                    pf_ticket = (u32 *)(pf_status + pf_tiles);
-                    nrows_dev = pf_ticket + 2;
-                }
-                SE_HIP(hipMemsetAsync(H->d_block, 0, ((size_t)rows_cap + st_words + is_words) * sizeof(u64), ctx->stream));
-            }
-            if (fused) {
-                ks_timer_begin(ctx, "pair_rows");
-                hipLaunchKernelGGL(k_pair_rows_fused, dim3(pf_tiles), dim3(PF_THREADS), 0, ctx->stream, (const u64 *)pk, n_pairs, H->d_qid, H->d_tid,
-                                   H->d_isect, (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, nrows_dev,
-                                   (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
-                ks_timer_end(ctx);
-            } else {
-                ks_timer_begin(ctx, "pair_reduce");
-                hipLaunchKernelGGL(k_pair_reduce, dim3(gp), dim3(256), 0, ctx->stream, (const u64 *)pk, (const u32 *)pv, (const u32 *)heads,
-                                   n_pairs, H->d_qid, H->d_tid, H->d_isect, (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap);
-                ks_timer_end(ctx);
-            }
-            SE_HIP(hipGetLastError());
-            {
-                ks_fetch_seg f[2];
-                f[0] = fused ? ks_fetch_words(pf_ticket, ctx->h_pin + 1, 4) // ticket pair + row count
-                             : ks_fetch_words(d_nrows, ctx->h_pin + 2, 1);
-                const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
-                SE_CHECK(ks_stream_wait_fetch(ctx, f, nf));
-            }
-            SE_CHECK(ks_scan_status_check(ctx));
-            bool gave_up = fused && ((u32 *)(ctx->h_pin + 1))[1] != 0;
-            if (fused && ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY) && !ctx->rows_use_ticket) gave_up = true; // (tests)
-            if (gave_up) {
-                if (ctx->rows_use_ticket || attempt == 2) { st = ks_fail(ctx, KS_ERR_HIP, "search: row look-back gave up waiting for a predecessor tile"); goto done; }
-                ctx->rows_use_ticket = true; // dispatch order did not hold here: tickets from now on
-                ctx->rows_ticket_fallbacks++;
-            } else {
-                n_rows = *(u32 *)(ctx->h_pin + 2); // (fused: third word of the block copied to h_pin + 1; else copied there)
-                if (n_rows <= rows_cap) break;
-                rows_cap = n_rows;
-            }
-            ks_pool_free(ctx, H->d_qid); ks_pool_free(ctx, H->d_tid); ks_pool_free(ctx, H->d_block);
-            H->d_qid = H->d_tid = H->d_isect = nullptr; H->d_nw = nullptr; H->d_block = nullptr;
-        }
-        if (!H->d_qid) { st = ks_fail(ctx, KS_ERR_HIP, "search: the row pass did not settle"); goto done; }
-        H->n_hits = n_rows;
-        {
-            const u64 want = (u64)n_rows + n_rows / 4 + 4096;
-            ctx->rows_hint = want > ctx->rows_hint / 2 ? want : ctx->rows_hint / 2; // follows growth at once, decays slowly
-        }
-    }
-done:
-    ks_pool_free(ctx, qk0); ks_pool_free(ctx, qk1); ks_pool_free(ctx, qv0); ks_pool_free(ctx, qv1);
-    ks_pool_free(ctx, pk0); ks_pool_free(ctx, pk1); ks_pool_free(ctx, pv0); ks_pool_free(ctx, pv1);
-    ks_pool_free(ctx, heads); ks_pool_free(ctx, d_nrows); ks_pool_free(ctx, row_start); ks_pool_free(ctx, cursor);
-    ks_pool_free(ctx, dir_q); // (pf_status lies in the hit object's block)
-    if (st != KS_OK || split) { (void)hipStreamSynchronize(ctx->stream); ks_hits_free(H); return st; }
+    bool stop = false;
+    const int st = search_run(ctx, ix, q, H, split_pairs, sketch_redo, &stop);
+    if (st != KS_OK || stop) { (void)hipStreamSynchronize(ctx->stream); ks_hits_free(H); return st; }
     *out = H;
     return KS_OK;
-#undef SE_CHECK
-#undef SE_HIP
-#undef SE_FINISH_PENDING
 }
 
 __global__ __launch_bounds__(256) void k_rebase_offsets(const u64 *offs, u64 base, u32 n, u64 *out) {
@@ -1790,6 +1828,46 @@ __global__ __launch_bounds__(256) void k_union_emit(const u64 *keys, const u32 *
     abunds[r] = w > 0xffffffffULL ? 0xffffffffu : (u32)w;
 }
 
+static int union_run(ks_ctx *ctx, const ks_sketches *in, ks_sketches *U) {
+    const u64 n = in->n_hashes;
+    KS_TRY(ks_alloc(ctx, &U->d_offsets, 2));
+    if (n == 0) {
+        KS_HIP(ctx, hipMemsetAsync(U->d_offsets, 0, 2 * sizeof(u64), ctx->stream));
+        KS_TRY(ks_alloc(ctx, &U->d_hashes, 1)); KS_TRY(ks_alloc(ctx, &U->d_abunds, 1));
+        KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return KS_OK;
+    }
+    u64 *k0 = nullptr, *k1 = nullptr, *row_start = nullptr;
+    u32 *v0 = nullptr, *v1 = nullptr, *heads = nullptr, *d_nrows = nullptr;
+    ks_scratch sc(ctx);
+    KS_TRY(sc.alloc(&k0, (size_t)n)); KS_TRY(sc.alloc(&k1, (size_t)n));
+    KS_TRY(sc.alloc(&v0, (size_t)n)); KS_TRY(sc.alloc(&v1, (size_t)n));
+    const int shifts[8] = {0, 8, 16, 24, 32, 40, 48, 56};
+    u64 *ks = nullptr;
+    u32 *vs = nullptr;
+    KS_TRY(ks_radix_sort_u32(ctx, KS_SORT_PAIRS, in->d_hashes, in->d_abunds, k0, v0, k1, v1, n, shifts, 8, &ks, &vs));
+    KS_TRY(sc.alloc(&heads, (size_t)n));
+    KS_TRY(sc.alloc(&d_nrows, 1));
+    const u32 g = (u32)((n + 255) / 256);
+    KS_LAUNCH(ctx, "pair_heads", k_pair_heads, g, 256, (const u64 *)ks, n, heads, 0);
+    KS_TRY(ks_scan_u32_inplace(ctx, heads, n, d_nrows));
+    u64 *const rb = ctx->h_pin + KS_PIN_READ;
+    KS_HIP(ctx, hipMemcpyAsync(rb, d_nrows, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const u32 n_rows = *(u32 *)rb;
+    U->n_hashes = U->n_slots = n_rows;
+    KS_TRY(sc.alloc(&row_start, (size_t)n_rows + 1));
+    KS_TRY(ks_alloc(ctx, &U->d_hashes, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &U->d_abunds, (size_t)n_rows));
+    KS_LAUNCH(ctx, "pair_rows", k_pair_rows, g, 256, (const u64 *)ks, (const u32 *)heads, n, n_rows, row_start, 0);
+    KS_LAUNCH(ctx, "union_emit", k_union_emit, (n_rows + 255) / 256, 256, (const u64 *)ks, (const u32 *)vs, (const u64 *)row_start, n_rows,
+              U->d_hashes, U->d_abunds);
+    rb[0] = 0; rb[1] = n_rows;
+    KS_HIP(ctx, hipMemcpyAsync(U->d_offsets, rb, 2 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    KS_TRY(ks_scan_status_fetch(ctx));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return ks_scan_status_check(ctx);
+}
+
 int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out) {
     if (!in || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_HIP(ctx, hipSetDevice(ctx->device));
@@ -1797,59 +1875,8 @@ int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out) {
     ks_sketches *U = new ks_sketches();
     memset(U, 0, sizeof *U);
     U->ctx = ctx; U->params = in->params; U->n_seqs = 1; U->n_windows = in->n_windows;
-    const u64 n = in->n_hashes;
-    u64 *k0 = nullptr, *k1 = nullptr, *row_start = nullptr;
-    u32 *v0 = nullptr, *v1 = nullptr, *heads = nullptr, *d_nrows = nullptr;
-    int st = KS_OK;
-#define UN_CHECK(x) do { st = (x); if (st != KS_OK) goto done; } while (0)
-#define UN_HIP(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { st = ks_fail(ctx, KS_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-    UN_CHECK(ks_alloc(ctx, &U->d_offsets, 2));
-    if (n == 0) {
-        UN_HIP(hipMemsetAsync(U->d_offsets, 0, 2 * sizeof(u64), ctx->stream));
-        UN_CHECK(ks_alloc(ctx, &U->d_hashes, 1)); UN_CHECK(ks_alloc(ctx, &U->d_abunds, 1));
-        UN_HIP(hipStreamSynchronize(ctx->stream));
-        goto done;
-    }
-    {
-        UN_CHECK(ks_alloc(ctx, &k0, (size_t)n)); UN_CHECK(ks_alloc(ctx, &k1, (size_t)n));
-        UN_CHECK(ks_alloc(ctx, &v0, (size_t)n)); UN_CHECK(ks_alloc(ctx, &v1, (size_t)n));
-        const int shifts[8] = {0, 8, 16, 24, 32, 40, 48, 56};
-        u64 *ks = nullptr;
-        u32 *vs = nullptr;
-        UN_CHECK(ks_radix_sort_u32(ctx, KS_SORT_PAIRS, in->d_hashes, in->d_abunds, k0, v0, k1, v1, n, shifts, 8, &ks, &vs));
-        UN_CHECK(ks_alloc(ctx, &heads, (size_t)n));
-        UN_CHECK(ks_alloc(ctx, &d_nrows, 1));
-        const u32 g = (u32)((n + 255) / 256);
-        ks_timer_begin(ctx, "pair_heads");
-        hipLaunchKernelGGL(k_pair_heads, dim3(g), dim3(256), 0, ctx->stream, (const u64 *)ks, n, heads, 0);
-        ks_timer_end(ctx);
-        UN_CHECK(ks_scan_u32_inplace(ctx, heads, n, d_nrows));
-        UN_HIP(hipMemcpyAsync(ctx->h_pin, d_nrows, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-        UN_HIP(hipStreamSynchronize(ctx->stream));
-        const u32 n_rows = *(u32 *)ctx->h_pin;
-        U->n_hashes = U->n_slots = n_rows;
-        UN_CHECK(ks_alloc(ctx, &row_start, (size_t)n_rows + 1));
-        UN_CHECK(ks_alloc(ctx, &U->d_hashes, (size_t)n_rows)); UN_CHECK(ks_alloc(ctx, &U->d_abunds, (size_t)n_rows));
-        ks_timer_begin(ctx, "pair_rows");
-        hipLaunchKernelGGL(k_pair_rows, dim3(g), dim3(256), 0, ctx->stream, (const u64 *)ks, (const u32 *)heads, n, n_rows, row_start, 0);
-        ks_timer_end(ctx);
-        ks_timer_begin(ctx, "union_emit");
-        hipLaunchKernelGGL(k_union_emit, dim3((n_rows + 255) / 256), dim3(256), 0, ctx->stream, (const u64 *)ks, (const u32 *)vs,
-                           (const u64 *)row_start, n_rows, U->d_hashes, U->d_abunds);
-        ks_timer_end(ctx);
-        UN_HIP(hipGetLastError());
-        ctx->h_pin[0] = 0; ctx->h_pin[1] = n_rows;
-        UN_HIP(hipMemcpyAsync(U->d_offsets, ctx->h_pin, 2 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-        UN_CHECK(ks_scan_status_fetch(ctx));
-        UN_HIP(hipStreamSynchronize(ctx->stream));
-        UN_CHECK(ks_scan_status_check(ctx));
-    }
-done:
-    ks_pool_free(ctx, k0); ks_pool_free(ctx, k1); ks_pool_free(ctx, v0); ks_pool_free(ctx, v1);
-    ks_pool_free(ctx, heads); ks_pool_free(ctx, d_nrows); ks_pool_free(ctx, row_start);
+    const int st = union_run(ctx, in, U);
     if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_sketches_free(U); return st; }
     *out = U;
     return KS_OK;
-#undef UN_CHECK
-#undef UN_HIP
 }

@@ -223,7 +223,27 @@ KS_DEV u32 sk_digit(u64 h, u32 K, u32 kshift, u32 mask) {
     return (kshift ? (hi >> kshift) : __umulhi(hi, K)) & mask;
 }
 
-#define SK_CTL_WORDS 32 // control block of a sketch call (see sketch_attempt)
+// The control block of a sketch call: every small word the host zeroes before / reads after the launches, in u64 words
+// (one memset, one device -> host copy per read-back instead of one per word: each is a dispatch of its own on this runtime).
+// The posting cursors and the tiles' status words sit right behind it, in the same allocation.
+enum : u32 {
+    SK_CTL_WINDOWS = 0, SK_CTL_MAX_LEN = 1, // k-mer windows of the batch, longest sequence (k_seq_stats)
+    SK_CTL_N_PK_LONG = 2,                   // sequences longer than PK_MAX_LEN (the long ones of a packed plan)
+    SK_CTL_MED = 4, SK_CTL_LONG = 4 + SK_NR, // + c: medium (deferred, fit a tile of their own) / long (deferred, do not) sequences under stride c
+    SK_CTL_TICKET = 20,   // u32 pair: tile ticket | status bits (SK_ST_*)
+    SK_CTL_CLS = 21,      // u32 pair: medium | long sequences found (k_find_long)
+    SK_CTL_PK_TILES = 22, // u32: tiles of a packed plan
+    SK_CTL_TOTAL = 23,    // kept hashes (= CSR slots)
+    SK_CTL_DROPS = 24,    // kept hashes that repeat an earlier one of their sequence (slots the CSR leaves empty)
+    SK_CTL_LB_ROUNDS = 25, // look-back rounds (SK_LB_STATS builds only)
+    SK_CTL_WORDS = 32,
+    SK_CTL_CURSORS = SK_CTL_WORDS, SK_CTL_CURSOR_WORDS = 1024, // posting cursors: 2048 x u32
+    SK_CTL_TILE_STATUS = SK_CTL_CURSORS + SK_CTL_CURSOR_WORDS,  // the tiles' status words, when the plan knew their number
+};
+static_assert(SK_CTL_LONG + SK_NR <= SK_CTL_TICKET && SK_CTL_LB_ROUNDS < SK_CTL_WORDS, "sketch control block layout");
+static_assert(SK_CTL_WORDS <= KS_PIN_SKETCH_WORDS && SK_CTL_WORDS <= KS_PIN_SKETCH_SYNC_WORDS, "pinned slots of the sketch read-back");
+// status bits of the control block (SK_CTL_TICKET, second word)
+enum : u32 { SK_ST_LOOKBACK = 1u, SK_ST_POSTINGS = 2u, SK_ST_COMPACT = 4u };
 #define SK_SEQ_CAP 254 // sequence boundaries of a tile staged in LDS (tiles with more fall back to global reads)
 // per-element code: sequence (relative to the tile's first, 8 bits) | bucket (12 bits) | arrival slot (12 bits)
 #define SK_BO_B(x) (((x) >> 12) & 0xfffu)
@@ -1800,16 +1820,14 @@ int ks_kmerpos_tiles_launch(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32
     u32 *tile_first = nullptr, *ticket = nullptr;
     unsigned long long *status = nullptr;
     u64 *total = nullptr;
-    int st = ks_alloc(ctx, &tile_first, (size_t)n_tiles + 1);
-    if (st == KS_OK) st = ks_alloc(ctx, (u64 **)&status, (size_t)n_tiles);
-    if (st == KS_OK) st = ks_alloc(ctx, &ticket, 2);
-    if (st == KS_OK) st = ks_alloc(ctx, &total, 1);
-    if (st == KS_OK) {
-        ks_timer_begin(ctx, "kmerpos_plan");
-        hipLaunchKernelGGL(k_kmerpos_plan, dim3((n_tiles + 256) / 256), dim3(256), 0, ctx->stream, d_offs, n_seqs, n_tiles, tile_first);
-        ks_timer_end(ctx);
-    }
-    for (int attempt = 0; st == KS_OK && attempt < 2; attempt++) {
+    ks_scratch sc(ctx);
+    KS_TRY(sc.alloc(&tile_first, (size_t)n_tiles + 1));
+    KS_TRY(sc.alloc((u64 **)&status, (size_t)n_tiles));
+    KS_TRY(sc.alloc(&ticket, 2));
+    KS_TRY(sc.alloc(&total, 1));
+    KS_LAUNCH(ctx, "kmerpos_plan", k_kmerpos_plan, (n_tiles + 256) / 256, 256, d_offs, n_seqs, n_tiles, tile_first);
+    u64 *const rb = ctx->h_pin + KS_PIN_READ; // total | ticket pair
+    for (int attempt = 0; attempt < 2; attempt++) {
         const bool use_ticket = ctx->sketch_use_ticket || attempt == 1;
         (void)hipMemsetAsync(status, 0, (size_t)n_tiles * sizeof(u64), ctx->stream);
         (void)hipMemsetAsync(ticket, 0, 2 * sizeof(u32), ctx->stream);
@@ -1820,29 +1838,22 @@ int ks_kmerpos_tiles_launch(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32
         A.tile_status = status; A.ticket = ticket; A.total = total; A.out_seq = d_seq; A.out_start = d_start; A.out_hash = d_hash;
         A.n_res = n_res; A.max_hash = ks_max_hash(p->scaled); A.seed = p->seed; A.n_seqs = n_seqs; A.k = p->ksize; A.n_tiles = n_tiles;
         A.use_ticket = use_ticket ? 1u : 0u;
-        ks_timer_begin(ctx, "kmerpos_tiles");
-        hipLaunchKernelGGL(k_kmerpos_tiles, dim3(n_tiles), dim3(SK_THREADS), 0, ctx->stream, A);
-        ks_timer_end(ctx);
-        if (hipGetLastError() != hipSuccess) { st = ks_fail(ctx, KS_ERR_HIP, "k-mer position launch failed"); break; }
-        if (hipMemcpyAsync(ctx->h_pin, total, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipMemcpyAsync(ctx->h_pin + 1, ticket, 2 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess ||
-            hipStreamSynchronize(ctx->stream) != hipSuccess) {
-            st = ks_fail(ctx, KS_ERR_HIP, "k-mer position status read failed");
-            break;
-        }
-        bool gave_up = ((u32 *)(ctx->h_pin + 1))[1] != 0;
+        KS_LAUNCH(ctx, "kmerpos_tiles", k_kmerpos_tiles, n_tiles, SK_THREADS, A);
+        KS_HIP(ctx, hipMemcpyAsync(rb, total, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+        KS_HIP(ctx, hipMemcpyAsync(rb + 1, ticket, 2 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+        KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        bool gave_up = ((u32 *)(rb + 1))[1] != 0;
         if (!use_ticket && ks_dbg(ctx, KS_DBG_FORCE_TICKET_RETRY)) gave_up = true; // exercises the repeat
-        if (!gave_up) { *n_out = ctx->h_pin[0]; break; }
-        if (use_ticket) { st = ks_fail(ctx, KS_ERR_HIP, "k-mer positions: look-back gave up waiting for a predecessor tile"); break; }
+        if (!gave_up) { *n_out = rb[0]; break; }
+        if (use_ticket) return ks_fail(ctx, KS_ERR_HIP, "k-mer positions: look-back gave up waiting for a predecessor tile");
         ctx->sketch_use_ticket = true; // dispatch order did not hold here: tickets from now on (shared with the sketch tiles)
         ctx->sketch_ticket_fallbacks++;
     }
-    ks_pool_free(ctx, tile_first); ks_pool_free(ctx, status); ks_pool_free(ctx, ticket); ks_pool_free(ctx, total);
-    return st;
+    return KS_OK;
 }
 
-// out[0] = k-mer windows, out[1] = longest sequence; under tile stride cand[c] (a tile spans `span` residues from its
-// start): out[4 + c] = medium sequences (deferred, fit a tile of their own), out[4 + SK_NR + c] = long ones (deferred, do not)
+// The statistics words of the control block (SK_CTL_*): windows, longest sequence, and under tile stride cand[c] (a tile
+// spans `span` residues from its start) the medium and long sequences that are deferred
 struct sk_cands { u32 r[SK_NR]; };
 __global__ __launch_bounds__(256) void k_seq_stats(const u64 *offs, u32 n_seqs, u32 k, u32 span, sk_cands cand, u64 *out) {
     u64 w = 0, mx = 0;
@@ -1873,7 +1884,7 @@ __global__ __launch_bounds__(256) void k_seq_stats(const u64 *offs, u32 n_seqs, 
 #pragma unroll
         for (int c = 0; c < SK_NR; c++) { nd[c] += __shfl_down(nd[c], d, 64); nl[c] += __shfl_down(nl[c], d, 64); }
     }
-    if ((threadIdx.x & 63) == 0 && npk) atomicAdd((unsigned long long *)&out[2], (unsigned long long)npk);
+    if ((threadIdx.x & 63) == 0 && npk) atomicAdd((unsigned long long *)&out[SK_CTL_N_PK_LONG], (unsigned long long)npk);
     // one set of device atomics per WORKGROUP (they all hit the same few words: per wave they were the whole run time)
     __shared__ u64 red[4][2 + 2 * SK_NR];
     const u32 wave = threadIdx.x >> 6;
@@ -1888,10 +1899,449 @@ __global__ __launch_bounds__(256) void k_seq_stats(const u64 *offs, u32 n_seqs, 
         u64 v = red[0][j];
         for (u32 q = 1; q < 4; q++) v = j == 1 ? (red[q][j] > v ? red[q][j] : v) : v + red[q][j];
         if (v) {
-            if (j == 1) atomicMax((unsigned long long *)&out[1], (unsigned long long)v);
-            else atomicAdd((unsigned long long *)&out[j == 0 ? 0 : 4 + (j - 2)], (unsigned long long)v);
+            if (j == 1) atomicMax((unsigned long long *)&out[SK_CTL_MAX_LEN], (unsigned long long)v);
+            else atomicAdd((unsigned long long *)&out[j == 0 ? SK_CTL_WINDOWS : SK_CTL_MED + (j - 2)], (unsigned long long)v);
         }
     }
+}
+
+// ---- one attempt at a batch, in steps: plan (host arithmetic) -> statistics + tile planning -> stride -> outputs ->
+// deferred (medium / long) sequences -> shared tiles -> decode of the control block
+
+// the batch an attempt sketches
+struct sk_call {
+    const u8 *d_res;
+    const u64 *d_offs;
+    u32 n_seqs;
+    u64 n_res;
+    u32 max_seq_len;
+    const ks_params *p;
+};
+
+// the shape of an attempt: pure host arithmetic (sk_plan_shape, sk_plan_stride, sk_plan_outputs), no HIP calls
+struct sk_plan {
+    bool planned;  // the caller gave max_seq_len
+    bool compact;  // compacting variant: bucket space = positions / c_div, span = residues per shared tile (see k_sketch_tiles<0, 1>)
+    bool packed;   // packed tiles (whole sequences packed greedily into each tile, see k_pack_walk) for the plain variant
+    u32 c_div, span, pk_chunk, pk_chunks;
+    sk_cands cand;
+    // Packed plan without the round trip: with every sequence <= L = max_seq_len <= PK_MAX_LEN a tile is closed by a sequence
+    // that does not fit, so it holds more than SK_MED_MAX - 15 - L residues (one short tile per chunk besides): when that bound
+    // is within 2x of the typical count, the launch takes it as its grid and the tiles beyond the device-side count return at
+    // once.  (Worth ~20 us per call: small batches; a 1M-protein launch would not notice either way.)
+    u64 pk_bound;
+    u64 tiles_hint; // tile status words that lie in the control block (zeroed with it)
+    // stride (with a plan from max_seq_len: n_med / n_long are upper bounds, the true counts stay on the device)
+    u32 real_max, tile_R;
+    u64 n_med, n_long;
+    u64 win_bound;  // k-mer windows of the batch, or an upper bound (n_res) until the final read
+    u64 pk_n_tiles; // packed plan: tiles of the batch (read back with the statistics, or an upper bound: pk_bound)
+    u64 out_cap;
+    // posting geometry (part_pbits == 0: no postings), see ks_sketches
+    int part_pbits;
+    u32 part_K, part_regions, part_sub_shift, part_kshift, part_s;
+    u64 part_cap;
+};
+
+static void sk_plan_shape(const ks_ctx *ctx, const sk_call &C, int variant, sk_plan *P) {
+    memset(P, 0, sizeof *P);
+    const ks_params *p = C.p;
+    P->planned = C.max_seq_len > 0 && !ks_dbg(ctx, KS_DBG_NO_PLAN);
+    P->compact = (variant & 1) && p->scaled >= 2 && !ks_dbg(ctx, KS_DBG_NO_COMPACT);
+    P->c_div = P->compact ? (p->scaled < 64 ? p->scaled : 64u) : 1u;
+    P->span = SK_TILE;
+    if (P->compact) {
+        u64 sp = (u64)P->c_div * 3840; // span / c_div + SK_SEQ_CAP + 1 < SK_TILE buckets
+        if (sp > 8ull * SK_TILE) sp = 8ull * SK_TILE;
+        P->span = (u32)(sp / 512 * 512);
+        if (const char *f = ks_dbg(ctx, KS_DBG_SPAN)) { // tuning aid
+            const u32 v = (u32)atoi(f) / 512 * 512;
+            if (v >= SK_TILE && v <= sp) P->span = v;
+        }
+    }
+    P->packed = !P->compact && !ks_dbg(ctx, KS_DBG_NO_PACK);
+    // (the walk of a chunk is a serial chain, ~0.5 us per tile: small batches take shorter chunks — more waves, shorter
+    // chains — at the price of one partly filled tile per chunk)
+    P->pk_chunk = C.n_seqs >= 262144 ? PK_CHUNK : (C.n_seqs >= 32768 ? 256u : 64u);
+    P->pk_chunks = (C.n_seqs + P->pk_chunk - 1) / P->pk_chunk;
+    for (int c = 0; c < SK_NR; c++) P->cand.r[c] = sk_r_cand_host[c] + (P->span - SK_TILE);
+    P->tile_R = sk_r_cand_host[0];
+    if (P->packed && P->planned && C.max_seq_len <= PK_MAX_LEN && !ks_dbg(ctx, KS_DBG_PLAN_SYNC)) {
+        const u64 b = C.n_res / (SK_MED_MAX - 15 - C.max_seq_len + 1) + P->pk_chunks + 1;
+        const u64 typical = C.n_res / 3800 + P->pk_chunks + 1;
+        if (b <= 2 * typical + 256 && b <= C.n_seqs) P->pk_bound = b;
+        else if (C.n_seqs <= 2 * typical + 256) P->pk_bound = C.n_seqs; // (a tile holds at least one sequence)
+    }
+    // The tile count is known here when the plan needs no round trip (an upper bound otherwise: a launch with more tiles
+    // takes a status array of its own).
+    P->tiles_hint = P->packed ? P->pk_bound : C.n_res / P->cand.r[0] + 2;
+}
+
+// no upper bound on the sequence length from the caller (or a packed plan that needs its tile count): the plan (tile
+// stride, deferred sequences, slab size) comes from the batch itself, at the price of one device -> host round trip before
+// the tiles are launched
+static bool sk_plan_reads_stats(const sk_plan &P) { return !P.pk_bound && (!P.planned || P.packed); }
+
+// stats: the statistics words of the control block as read back (sk_plan_reads_stats), else nullptr
+static int sk_plan_stride(ks_ctx *ctx, const sk_call &C, const u64 *stats, sk_plan *P) {
+    if (P->pk_bound) {
+        P->real_max = C.max_seq_len;
+        P->win_bound = C.n_res;
+        P->tile_R = 0; P->n_med = 0; P->n_long = 0; // nothing is deferred: every sequence fits a tile
+        P->pk_n_tiles = P->pk_bound;
+    } else if (stats) {
+        P->win_bound = stats[SK_CTL_WINDOWS];
+        if (P->packed) P->pk_n_tiles = *(const u32 *)(stats + SK_CTL_PK_TILES);
+        if (stats[SK_CTL_MAX_LEN] > 0xfffffff0ULL) return ks_fail(ctx, KS_ERR_INVALID_ARG, "sequence longer than 2^32 residues");
+        P->real_max = (u32)stats[SK_CTL_MAX_LEN];
+        // tile stride: fewest (tiles x sub-tiles + 1.75 x medium + 20 x long sequences), see sk_r_cand
+        double best = 0;
+        const double per_tile = (double)P->span / SK_TILE;
+        for (int c = 0; c < SK_NR; c++) {
+            if (c >= SK_NR - 2 && (u64)P->real_max + P->cand.r[c] + 15 > P->span) continue; // uncounted strides
+            const double cost = (double)(C.n_res / P->cand.r[c] + 1) * per_tile + 1.75 * (double)stats[SK_CTL_MED + c] +
+                                20.0 * (double)stats[SK_CTL_LONG + c];
+            if (c == 0 || cost < best) { best = cost; P->tile_R = P->cand.r[c]; P->n_med = stats[SK_CTL_MED + c]; P->n_long = stats[SK_CTL_LONG + c]; }
+        }
+        if (const char *force = ks_dbg(ctx, KS_DBG_TILE_R)) // tuning aid: one of sk_r_cand (counted strides only)
+            for (int c = 0; c < SK_NR - 2; c++)
+                if (atoi(force) == (int)sk_r_cand_host[c]) { P->tile_R = P->cand.r[c]; P->n_med = stats[SK_CTL_MED + c]; P->n_long = stats[SK_CTL_LONG + c]; }
+        if (P->packed) { P->tile_R = 0; P->n_med = 0; P->n_long = stats[SK_CTL_N_PK_LONG]; } // nothing is deferred for its position
+    } else {
+        // max_seq_len given: everything the launches need follows from it, and what is only known on the device (how
+        // many sequences are deferred) is read there by kernels with fixed grids.  The widest stride whose tiles hold
+        // every sequence wherever it starts, else the stride the cost model picks for proteome-like batches.
+        P->real_max = C.max_seq_len;
+        P->win_bound = C.n_res;
+        P->tile_R = P->cand.r[3];
+        for (int c = SK_NR - 1; c >= SK_NR - 2; c--)
+            if ((u64)P->real_max + P->cand.r[c] + 15 <= P->span) { P->tile_R = P->cand.r[c]; break; }
+        const bool may_defer = (u64)P->real_max + P->tile_R + 15 > P->span;
+        const u64 n_t = C.n_res / P->tile_R + 1; // at most one deferred sequence per tile (the last that starts in it)
+        P->n_med = may_defer ? n_t : 0;
+        P->n_long = (may_defer && P->real_max > SK_MED_MAX) ? n_t : 0;
+    }
+    return KS_OK;
+}
+
+static void sk_plan_outputs(const ks_ctx *ctx, const sk_call &C, int variant, int part_pbits, int part_fmt10, sk_plan *P) {
+    const ks_params *p = C.p;
+    const u64 n_windows = P->win_bound;
+    // The tile kernel writes the final arrays in place (no compaction pass).  At scaled = 1 every window may be kept;
+    // at scaled > 1 the arrays are sized by the expected 1 / scaled of the windows plus a quarter, and a batch that keeps
+    // more (repeats whose hash falls under the threshold) is repeated with the full size.
+    P->out_cap = n_windows;
+    if (!(variant & 2) && p->scaled >= 2) {
+        const u64 want = n_windows / p->scaled + n_windows / (4ull * p->scaled) + 65536;
+        if (want < P->out_cap) P->out_cap = want;
+    }
+    if (const char *f = ks_dbg(ctx, KS_DBG_OUT_CAP)) // exercises the repeat on small inputs
+        if (!(variant & 2) && strtoull(f, nullptr, 10) < P->out_cap) P->out_cap = strtoull(f, nullptr, 10);
+    if (!(part_pbits > 0 && n_windows > 0 && n_windows < 0xffff0000ULL)) return;
+    // first partition digit: the low 8 bits of the join's hash prefix (the whole prefix if it is <= 8 bits)
+    const int dbits = part_pbits < 8 ? part_pbits : 8;
+    P->part_pbits = part_pbits;
+    P->part_K = ks_join_prefix_mul(part_pbits, ks_max_hash(p->scaled));
+    P->part_regions = 1u << dbits;
+    // one sub-region per XCD when a second partition pass follows (its tiles are per-segment anyway); when the
+    // regions ARE the join buckets (<= 8 prefix bits) they must stay contiguous
+    // (... as many as leave a sub-region >= 64k postings: the bucket scatter works on tiles of 8,192 postings per sub-region, and
+    // a 125k-query shard of the 1M workload cut 2,048 ways fills 2.2 of them — 0.25 ms against 0.17 with 512 sub-regions;
+    // 10k queries: 44 -> 22 us with 256 — while the 1M batch wants all 2,048: fewer posting cursors cost its sketch kernel
+    // 2.49 -> 2.61 ms)
+    P->part_sub_shift = 0u;
+    if (part_pbits > 8)
+        while (P->part_sub_shift < 3u && (n_windows / p->scaled) >> (8u + P->part_sub_shift + 1u) >= 65536u) P->part_sub_shift++;
+    if (const char *f = ks_dbg(ctx, KS_DBG_SUBSHIFT)) { const int v = atoi(f); if (part_pbits > 8 && v >= 0 && v <= 3) P->part_sub_shift = (u32)v; }
+    const u32 n_segs = P->part_regions << P->part_sub_shift;
+    const u64 per = n_windows / p->scaled / n_segs + 1; // FracMinHash keeps ~1/scaled of the windows
+    u64 cap = per + per / 4 + 8192;                   // uniform hashes fill regions evenly; skew -> fallback
+    cap = (cap + 8191) / 8192 * 8192;
+    P->part_cap = cap;
+    P->part_kshift = (P->part_K & (P->part_K - 1)) == 0 && P->part_K > 1 ? 32u - (u32)__builtin_ctz(P->part_K) : 0u;
+    // 10-byte postings: when the caller's join reads them (big indexes: the fingerprint joins), the digit is a bit field
+    // of the hash (scaled = 1) below a second partition level, and the sequence ids fit 24 bits
+    if (part_fmt10 && P->part_kshift && part_pbits > 8 && C.n_seqs < (1u << 24) && !ks_dbg(ctx, KS_DBG_POSTINGS12))
+        P->part_s = 32u + P->part_kshift;
+}
+
+// device words and scratch blocks the launch steps share (the scratch blocks belong to the attempt's ks_scratch)
+struct sk_bufs {
+    u32 *ticket, *n_cls, *d_ntiles; // in the control block
+    u32 *tile_first;
+    u64 *tile_g0;
+    u32 *med_ids, *long_ids;
+    u64 *lg_hash;
+    u32 *lg_abund;
+};
+
+// the control block (zeroed), the statistics and, for a packed plan, the tile plan
+static int sk_launch_stats(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const sk_plan &P, ks_scratch &sc, sk_bufs &B) {
+    const size_t ctl_words = (size_t)SK_CTL_TILE_STATUS + P.tiles_hint + 1;
+    KS_TRY(ks_alloc(ctx, &S->ctl_block, ctl_words));
+    u64 *const ctl = S->ctl_block;
+    KS_HIP(ctx, hipMemsetAsync(ctl, 0, ctl_words * sizeof(u64), ctx->stream));
+    B.ticket = (u32 *)(ctl + SK_CTL_TICKET); B.n_cls = (u32 *)(ctl + SK_CTL_CLS); B.d_ntiles = (u32 *)(ctl + SK_CTL_PK_TILES);
+    u32 g = (C.n_seqs + 1023) / 1024;
+    if (g > 512) g = 512;
+    KS_LAUNCH(ctx, "seq_stats", k_seq_stats, g, 256, C.d_offs, C.n_seqs, C.p->ksize, P.span, P.cand, ctl);
+    if (P.packed) {
+        // The tile count of a packed plan is only known on the device and sizes the launch: it is read back with the
+        // statistics (one round trip whether or not the caller gave max_seq_len), unless pk_bound stands in.
+        u32 *pk_tiles = nullptr, *pk_cnt = nullptr;
+        KS_TRY(sc.alloc(&pk_tiles, (size_t)C.n_seqs));
+        KS_TRY(sc.alloc(&pk_cnt, (size_t)P.pk_chunks));
+        KS_TRY(sc.alloc(&B.tile_first, (size_t)C.n_seqs + 1)); // (a tile holds at least one sequence)
+        KS_TRY(sc.alloc(&B.tile_g0, (size_t)C.n_seqs + 1));
+        ks_timer_begin(ctx, "tile_plan");
+        hipLaunchKernelGGL(k_pack_walk, dim3(P.pk_chunks), dim3(64), 0, ctx->stream, C.d_offs, C.n_seqs, P.pk_chunk, pk_tiles, pk_cnt);
+        hipLaunchKernelGGL(k_pack_fill, dim3(P.pk_chunks), dim3(256), 0, ctx->stream, C.d_offs, C.n_seqs, P.pk_chunk, (const u32 *)pk_tiles,
+                           (const u32 *)pk_cnt, P.pk_chunks, B.tile_first, B.tile_g0, B.d_ntiles);
+        ks_timer_end(ctx);
+        KS_HIP(ctx, hipGetLastError());
+    }
+    return KS_OK;
+}
+
+// ---- medium / long sequences first: their unique counts feed the tile kernel's CSR prefix
+static int sk_launch_deferred(ks_ctx *ctx, const sk_call &C, const sk_plan &P, sk_args &A, ks_scratch &sc, sk_bufs &B) {
+    const u64 n_med = P.n_med, n_long = P.n_long;
+    if (n_med + n_long > 0) {
+        KS_TRY(sc.alloc(&A.kept, (size_t)C.n_seqs));
+        KS_TRY(sc.alloc(&B.lg_hash, (size_t)C.n_res + 1));
+        KS_TRY(sc.alloc(&B.lg_abund, (size_t)C.n_res + 1));
+        KS_TRY(sc.alloc(&B.med_ids, (size_t)n_med + 1));
+        KS_TRY(sc.alloc(&B.long_ids, (size_t)n_long + 1));
+        KS_LAUNCH(ctx, "find_long", k_find_long, (C.n_seqs + 255) / 256, 256, C.d_offs, C.n_seqs, P.tile_R, P.span, B.med_ids,
+                  B.long_ids, B.n_cls, (u32)n_med, (u32)n_long);
+    }
+    if (n_med > 0) {
+        sk_args M = A; // (keeps the posting arguments: a medium tile emits its own postings)
+        M.out_hash = B.lg_hash; M.out_abund = B.lg_abund; M.le_cap = SK_TILE; M.seq_list = B.med_ids; // local start <= 15, length <= SK_MED_MAX
+        M.out_cap = ~0ULL;
+        M.n_list = B.n_cls; M.n_list_cap = (u32)n_med;
+        KS_LAUNCH(ctx, "sketch_medium", (k_sketch_tiles<1, 0, 0>), (u32)(n_med < 2048 ? n_med : 2048), SK_THREADS, M);
+    }
+    if (n_long > 0) {
+        // slab: 3 u64 + 4 u32 arrays of (max_len + 1) per workgroup, capped at ~2 GiB total
+        const u64 stride = (u64)P.real_max + 1;
+        const u64 per_wg = stride * (3 * 8 + 4 * 4);
+        u64 grid = (2ULL << 30) / per_wg;
+        if (grid < 1) grid = 1;
+        if (grid > n_long) grid = n_long;
+        if (grid > 512) grid = 512;
+        u64 *slab64 = nullptr;
+        u32 *slab32 = nullptr;
+        KS_TRY(sc.alloc(&slab64, (size_t)(grid * stride * 3)));
+        KS_TRY(sc.alloc(&slab32, (size_t)(grid * stride * 4)));
+        sk_long_args L;
+        L.a = A; L.long_ids = B.long_ids; L.n_long = B.n_cls; L.long_cap = (u32)n_long; L.max_len = P.real_max;
+        L.slab_keys = slab64; L.slab_tmp = slab64 + grid * stride; L.slab_sorted = slab64 + 2 * grid * stride;
+        L.slab_cnt = slab32; L.slab_ord = slab32 + grid * stride; L.slab_flag = slab32 + 2 * grid * stride;
+        L.slab_ab = slab32 + 3 * grid * stride;
+        L.lg_hash = B.lg_hash; L.lg_abund = B.lg_abund;
+        KS_LAUNCH(ctx, "sketch_long", k_sketch_long, (u32)grid, SK_THREADS, L);
+    }
+    return KS_OK;
+}
+
+// ---- shared tiles: hash + sort/unique + CSR placement in one kernel (decoupled look-back across tiles), then the runs of
+// the medium / long sequences into their CSR slots.  A launch in dispatch order whose look-back gave up is repeated with
+// ticket ids.  allow_defer: the first launch may leave its read-back to the caller's next wait (S->pending).
+static int sk_launch_tiles(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const sk_plan &P, sk_args &A, int allow_defer, ks_scratch &sc,
+                           sk_bufs &B) {
+    const u64 n_tiles = P.packed ? P.pk_n_tiles : C.n_res / P.tile_R + 1;
+    if (n_tiles > 0x7ffffff0ULL) return ks_fail(ctx, KS_ERR_INVALID_ARG, "batch too large");
+    unsigned long long *tile_status = (unsigned long long *)(S->ctl_block + SK_CTL_TILE_STATUS); // (zeroed with the control block)
+    if (n_tiles > P.tiles_hint) {
+        KS_TRY(sc.alloc(&tile_status, (size_t)n_tiles + 1));
+        KS_HIP(ctx, hipMemsetAsync(tile_status, 0, (size_t)n_tiles * sizeof(unsigned long long), ctx->stream));
+    }
+    if (!P.packed) {
+        KS_TRY(sc.alloc(&B.tile_first, (size_t)n_tiles + 1));
+        KS_LAUNCH(ctx, "tile_plan", k_tile_plan, (u32)((n_tiles + 256) / 256), 256, C.d_offs, C.n_seqs, (u32)n_tiles, P.tile_R, B.tile_first);
+    }
+    A.seq_list = B.tile_first; A.le_cap = P.span - 16; A.R = P.tile_R; A.span = P.span; A.tile_g0 = B.tile_g0;
+    if (P.packed) A.max_len_tile = PK_MAX_LEN;
+    if (P.compact) { A.c_div = P.c_div; A.c_rcp = (u32)(((1ULL << 32) + P.c_div - 1) / P.c_div); }
+    A.out_hash = S->d_hashes; A.out_abund = S->d_abunds; A.csr = S->d_offsets;
+    A.tile_status = tile_status; A.n_tiles = (u32)n_tiles;
+    A.n_tiles_dev = P.pk_bound ? B.d_ntiles : nullptr;
+    // posting cursors as the medium tiles left them (a repeated launch starts from here)
+    u32 *part_snap = nullptr;
+    if (A.part_cursor && P.n_med > 0) { // (without medium tiles the cursors are still zero: a repeat just clears them)
+        KS_TRY(sc.alloc(&part_snap, 2048));
+        KS_HIP(ctx, hipMemcpyAsync(part_snap, A.part_cursor, 2048 * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    const u64 *rb = ctx->h_pin + KS_PIN_SKETCH_SYNC;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        A.use_ticket = (ctx->sketch_use_ticket || attempt == 1) ? 1u : 0u;
+        A.debug_skip_tile = 0xffffffffu;
+        if (!A.use_ticket && ks_dbg(ctx, KS_DBG_LOOKBACK_SKIP)) A.debug_skip_tile = (u32)atoi(ks_dbg(ctx, KS_DBG_LOOKBACK_SKIP)); // (tests: a real expired spin)
+        if (attempt == 1) { // the dispatch-order launch gave up a look-back: start the tiles over, ids by ticket
+            ctx->sketch_use_ticket = true;
+            ctx->sketch_ticket_fallbacks++;
+            KS_HIP(ctx, hipMemsetAsync(tile_status, 0, (size_t)n_tiles * sizeof(unsigned long long), ctx->stream));
+            // (keeps the status bits the medium tiles set before the loop — "postings not emitted" — and drops only
+            // the look-back flag of the first attempt)
+            const u32 keep_bits = ((const u32 *)(rb + SK_CTL_TICKET))[1] & SK_ST_POSTINGS;
+            KS_HIP(ctx, hipMemsetAsync(B.ticket, 0, 2 * sizeof(u32), ctx->stream));
+            if (keep_bits) {
+                u32 *stage = (u32 *)(ctx->h_pin + KS_PIN_STAGE);
+                *stage = keep_bits;
+                KS_HIP(ctx, hipMemcpyAsync(B.ticket + 1, stage, sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+            }
+            if (part_snap) KS_HIP(ctx, hipMemcpyAsync(A.part_cursor, part_snap, 2048 * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
+            else if (A.part_cursor) KS_HIP(ctx, hipMemsetAsync(A.part_cursor, 0, 2048 * sizeof(u32), ctx->stream));
+        }
+        ks_timer_begin(ctx, "sketch_tiles");
+        // (the k-mer sizes of the reference's defaults and of BASELINE's configs run kernels with k folded in:
+        // src/rust/main.rs:28 k = 10, src/python/kmerseek/index.py:79-81 k = 24; any other size: the generic kernel)
+#define SK_LAUNCH_TILES(CMP_, KC_) hipLaunchKernelGGL((k_sketch_tiles<0, CMP_, KC_>), dim3((u32)n_tiles), dim3(SK_THREADS), 0, ctx->stream, A)
+        if (P.compact) {
+            if (C.p->ksize == 16) SK_LAUNCH_TILES(1, 16);
+            else if (C.p->ksize == 24) SK_LAUNCH_TILES(1, 24);
+            else SK_LAUNCH_TILES(1, 0);
+        } else {
+            if (C.p->ksize == 10) SK_LAUNCH_TILES(0, 10);
+            else if (C.p->ksize == 7) SK_LAUNCH_TILES(0, 7);
+            else SK_LAUNCH_TILES(0, 0);
+        }
+#undef SK_LAUNCH_TILES
+        ks_timer_end(ctx);
+        KS_HIP(ctx, hipGetLastError());
+
+        // ---- runs of medium / long sequences into their CSR slots
+        if (P.n_med > 0) // medium runs: copy only (their tiles emitted their own postings)
+            KS_LAUNCH(ctx, "place_long", k_place_long, (u32)(P.n_med < 1024 ? P.n_med : 1024), 256, (const u32 *)B.med_ids,
+                      (const u32 *)B.n_cls, (u32)P.n_med, C.d_offs, (const u64 *)S->d_offsets, (const u32 *)S->d_counts,
+                      (const u64 *)B.lg_hash, (const u32 *)B.lg_abund, S->d_hashes, S->d_abunds, P.out_cap, (u64 *)nullptr,
+                      (u32 *)nullptr, (u32 *)nullptr, (u64)0, 0u, 0u, 0u, B.ticket, 0u);
+        if (P.n_long > 0)
+            KS_LAUNCH(ctx, "place_long", k_place_long, (u32)(P.n_long < 1024 ? P.n_long : 1024), 256, (const u32 *)B.long_ids,
+                      (const u32 *)(B.n_cls + 1), (u32)P.n_long, C.d_offs, (const u64 *)S->d_offsets, (const u32 *)S->d_counts,
+                      (const u64 *)B.lg_hash, (const u32 *)B.lg_abund, S->d_hashes, S->d_abunds, P.out_cap, A.part_keys,
+                      A.part_vals, A.part_cursor, A.part_cap, A.part_K, A.part_mask, A.part_sub_shift, B.ticket, A.part_s);
+        // total + look-back error flag to the host
+        if (allow_defer && attempt == 0 && (P.pk_bound || (P.planned && !P.packed)) && !ks_dbg(ctx, KS_DBG_FORCE_TICKET_RETRY)) {
+            // the caller's next wait on this stream (the search's) stands in for this one and brings the control block along
+            // (ks_sketch_pending_seg); the scratch of this call goes back to the pool and is reused in stream order
+            S->pend_stats = S->ctl_block;
+            S->pending = 1; S->pend_out_cap = P.out_cap; S->pend_max_seq_len = C.max_seq_len; S->pend_planned = P.planned ? 1 : 0;
+            S->n_hashes = S->n_slots = P.out_cap; // (upper bounds until ks_sketch_finish_pending)
+            return KS_OK;
+        }
+        {
+            const ks_fetch_seg f = ks_fetch_words(S->ctl_block, ctx->h_pin + KS_PIN_SKETCH_SYNC, SK_CTL_WORDS * 2);
+            KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
+        }
+        u32 &status_w = ((u32 *)(ctx->h_pin + KS_PIN_SKETCH_SYNC + SK_CTL_TICKET))[1];
+        if (attempt == 0 && !A.use_ticket && ks_dbg(ctx, KS_DBG_FORCE_TICKET_RETRY)) status_w |= SK_ST_LOOKBACK; // exercises the repeat
+        if (!(status_w & SK_ST_LOOKBACK) || A.use_ticket) break;
+    }
+#ifdef SK_LB_STATS
+    fprintf(stderr, "[SK_LB_STATS] tiles %llu look-back rounds %llu\n", (unsigned long long)n_tiles, (unsigned long long)rb[SK_CTL_LB_ROUNDS]);
+#endif
+    return KS_OK;
+}
+
+// What a fetched control block says, in order of precedence; the values are the redo codes of ks_sketch_finish_pending.
+enum { SK_OUT_FINE = 0, SK_OUT_COMPACT = 1, SK_OUT_CAP = 2, SK_OUT_LOOKBACK = 3, SK_OUT_POSTINGS = 4 };
+
+// One decode of a fetched control block (the synchronous read-back or a pending sketch's): S's counts, the max_seq_len
+// check, and the outcome of the status bits (SK_OUT_*)
+static int sk_decode(ks_ctx *ctx, ks_sketches *S, const u64 *ctl, u64 out_cap, u32 max_seq_len, bool planned, int *outcome) {
+    *outcome = SK_OUT_FINE;
+    // the CSR's slots hold the kept hashes; the distinct ones (the sketches) are fewer by the repeats
+    S->n_slots = ctl[SK_CTL_TOTAL];
+    S->n_hashes = S->n_slots - (ctl[SK_CTL_DROPS] < S->n_slots ? ctl[SK_CTL_DROPS] : S->n_slots);
+    S->gapped = S->n_hashes != S->n_slots;
+    if (planned) {
+        S->n_windows = ctl[SK_CTL_WINDOWS];
+        if (ctl[SK_CTL_MAX_LEN] > (u64)max_seq_len) // the plan was made for shorter sequences: nothing of this launch can be trusted
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "max_seq_len = %u, but the batch holds a sequence of %llu residues", max_seq_len,
+                           (unsigned long long)ctl[SK_CTL_MAX_LEN]);
+    }
+    const u32 status = ((const u32 *)(ctl + SK_CTL_TICKET))[1];
+    if (status & SK_ST_LOOKBACK) *outcome = SK_OUT_LOOKBACK;      // a look-back gave up
+    else if (status & SK_ST_COMPACT) *outcome = SK_OUT_COMPACT;   // a compacting tile overflowed: the plain variant always fits
+    else if (S->n_slots > out_cap) *outcome = SK_OUT_CAP;         // more kept hashes than the bounded outputs hold
+    else if (status & SK_ST_POSTINGS) *outcome = SK_OUT_POSTINGS; // a region overflowed (skewed hashes) or a tile could not code its sequences
+    return KS_OK;
+}
+
+static int sketch_attempt_run(ks_ctx *ctx, ks_sketches *S, const sk_call &C, int part_pbits, int part_fmt10, int variant, int allow_defer,
+                              int *redo) {
+    const ks_params *p = C.p;
+    KS_TRY(ks_alloc(ctx, &S->d_offsets, (size_t)C.n_seqs + 1));
+    KS_TRY(ks_alloc(ctx, &S->d_counts, (size_t)C.n_seqs + 1));
+    if (C.n_seqs == 0) {
+        KS_HIP(ctx, hipMemsetAsync(S->d_offsets, 0, sizeof(u64), ctx->stream));
+        KS_TRY(ks_alloc(ctx, &S->d_hashes, 1));
+        KS_TRY(ks_alloc(ctx, &S->d_abunds, 1));
+        return ks_stream_wait(ctx);
+    }
+    sk_plan P;
+    sk_plan_shape(ctx, C, variant, &P);
+    ks_scratch sc(ctx);
+    sk_bufs B;
+    memset(&B, 0, sizeof B);
+    KS_TRY(sk_launch_stats(ctx, S, C, P, sc, B));
+    const u64 *stats = nullptr;
+    if (sk_plan_reads_stats(P)) {
+        const ks_fetch_seg f = ks_fetch_words(S->ctl_block, ctx->h_pin + KS_PIN_SKETCH_SYNC, SK_CTL_WORDS * 2);
+        KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
+        stats = ctx->h_pin + KS_PIN_SKETCH_SYNC;
+    }
+    KS_TRY(sk_plan_stride(ctx, C, stats, &P));
+    S->n_windows = P.win_bound;
+    sk_plan_outputs(ctx, C, variant, part_pbits, part_fmt10, &P);
+    KS_TRY(ks_alloc(ctx, &S->d_hashes, (size_t)P.out_cap));
+    KS_TRY(ks_alloc(ctx, &S->d_abunds, (size_t)P.out_cap));
+
+    sk_args A;
+    memset(&A, 0, sizeof A);
+    A.res = C.d_res; A.offs = C.d_offs; A.n_seqs = C.n_seqs; A.n_res = C.n_res; A.k = p->ksize; A.seed = p->seed;
+    A.max_hash = ks_max_hash(p->scaled);
+    {
+        u64 sf = (1ULL << 48) / ((A.max_hash >> 32) + 1ULL);
+        A.sfix = sf > 0x7fffffffULL ? 0x7fffffffu : (u32)sf; // smaller only coarsens the buckets
+    }
+    A.lut = ctx->d_lut + 256 * p->moltype;
+    A.upper_only = p->moltype == KS_PROTEIN ? 1u : 0u;
+    if (const char *f = ks_dbg(ctx, KS_DBG_QCAP)) A.debug_qcap = (u32)atoi(f);
+    A.counts = S->d_counts;
+    A.drops_out = S->ctl_block + SK_CTL_DROPS;
+    A.span = SK_TILE; A.c_div = 1; A.c_rcp = 0; A.out_cap = P.out_cap; A.max_len_tile = 0xffffffffu; A.R = 1;
+    A.ticket = B.ticket; A.total_out = S->ctl_block + SK_CTL_TOTAL;
+    if (P.part_pbits) {
+        S->part_pbits = P.part_pbits; S->part_K = P.part_K; S->part_regions = P.part_regions; S->part_sub_shift = P.part_sub_shift;
+        S->part_cap = P.part_cap; S->part_s = P.part_s;
+        // (+ SK_TILE spare slots behind the last region: where a tile drops a digit that does not fit its region)
+        const size_t n_slots = (size_t)(P.part_cap * (P.part_regions << P.part_sub_shift)) + SK_TILE;
+        KS_TRY(ks_alloc(ctx, &S->part_keys, n_slots));
+        KS_TRY(ks_alloc(ctx, &S->part_vals, n_slots));
+        S->part_len = (u32 *)(S->ctl_block + SK_CTL_CURSORS); // (zeroed with the control block)
+        A.part_keys = S->part_keys; A.part_vals = S->part_vals; A.part_cursor = S->part_len; A.part_cap = P.part_cap;
+        A.part_K = P.part_K; A.part_mask = P.part_regions - 1; A.part_sub_shift = P.part_sub_shift;
+        A.part_kshift = P.part_kshift; A.part_s = P.part_s;
+    }
+    KS_TRY(sk_launch_deferred(ctx, C, P, A, sc, B));
+    KS_TRY(sk_launch_tiles(ctx, S, C, P, A, allow_defer, sc, B));
+    if (S->pending) return KS_OK;
+
+    int outcome = SK_OUT_FINE;
+    KS_TRY(sk_decode(ctx, S, ctx->h_pin + KS_PIN_SKETCH_SYNC, P.out_cap, C.max_seq_len, P.planned, &outcome));
+    switch (outcome) {
+    case SK_OUT_LOOKBACK: return ks_fail(ctx, KS_ERR_HIP, "sketch: tile look-back timed out"); // (after the ticket repeat)
+    case SK_OUT_COMPACT:
+    case SK_OUT_CAP: *redo = outcome; return KS_OK;
+    case SK_OUT_POSTINGS: // no postings: ks_search repartitions from the CSR instead
+        ks_pool_free(ctx, S->part_keys); ks_pool_free(ctx, S->part_vals); // (part_len lies in the control block)
+        S->part_keys = nullptr; S->part_vals = nullptr; S->part_len = nullptr; S->part_pbits = 0;
+        return KS_OK;
+    }
+    return KS_OK;
 }
 
 // One attempt at a batch.  variant bit 0: the compacting tile kernel may be used (scaled > 1); bit 1: outputs sized by the
@@ -1907,387 +2357,8 @@ static int sketch_attempt(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n
     S->n_seqs = n_seqs;
     *out = nullptr;
     *redo = 0;
-
-    int st = KS_OK;
-    u64 *d_stats = nullptr;
-    u32 *kept = nullptr;
-    u32 *med_ids = nullptr, *long_ids = nullptr, *n_cls = nullptr, *tile_first = nullptr, *ticket = nullptr, *part_snap = nullptr;
-    unsigned long long *tile_status = nullptr, *tile_status_free = nullptr;
-    u64 *slab64 = nullptr, *lg_hash = nullptr;
-    u32 *slab32 = nullptr, *lg_abund = nullptr;
-    u64 n_med = 0, n_long = 0, out_cap = 0; // (with a plan from max_seq_len: upper bounds, the true counts stay on the device)
-    u64 win_bound = 0;                      // k-mer windows of the batch, or an upper bound (n_res) until the final read
-    u32 real_max = 0, tile_R = sk_r_cand_host[0];
-    const bool planned = max_seq_len > 0 && !ks_dbg(ctx, KS_DBG_NO_PLAN);
-    u32 *pk_tiles = nullptr, *pk_cnt = nullptr, *d_ntiles = nullptr;
-    u64 *tile_g0 = nullptr;
-    u64 pk_n_tiles = 0; // packed plan: tiles of the batch (read back with the statistics, or an upper bound: pk_bound)
-    // Packed plan without the round trip: with every sequence <= L = max_seq_len <= PK_MAX_LEN a tile is closed by a sequence
-    // that does not fit, so it holds more than SK_MED_MAX - 15 - L residues (one short tile per chunk besides): when that bound
-    // is within 2x of the typical count, the launch takes it as its grid and the tiles beyond the device-side count return at
-    // once.  (Worth ~20 us per call: small batches; a 1M-protein launch would not notice either way.)
-    u64 pk_bound = 0;
-    u64 tiles_hint = 0; // tile status words that lie in the control block (zeroed with it)
-    // compacting variant: bucket space = positions / c_div, span = residues per shared tile (see k_sketch_tiles<0, 1>)
-    const bool compact = (variant & 1) && p->scaled >= 2 && !ks_dbg(ctx, KS_DBG_NO_COMPACT);
-    const u32 c_div = compact ? (p->scaled < 64 ? p->scaled : 64u) : 1u;
-    u32 span = SK_TILE;
-    if (compact) {
-        u64 sp = (u64)c_div * 3840; // span / c_div + SK_SEQ_CAP + 1 < SK_TILE buckets
-        if (sp > 8ull * SK_TILE) sp = 8ull * SK_TILE;
-        span = (u32)(sp / 512 * 512);
-        if (const char *f = ks_dbg(ctx, KS_DBG_SPAN)) { // tuning aid
-            const u32 v = (u32)atoi(f) / 512 * 512;
-            if (v >= SK_TILE && v <= sp) span = v;
-        }
-    }
-    // packed tiles (whole sequences packed greedily into each tile, see k_pack_walk) for the plain variant
-    const bool packed = !compact && !ks_dbg(ctx, KS_DBG_NO_PACK);
-    // (the walk of a chunk is a serial chain, ~0.5 us per tile: small batches take shorter chunks — more waves, shorter
-    // chains — at the price of one partly filled tile per chunk)
-    const u32 pk_chunk = n_seqs >= 262144 ? PK_CHUNK : (n_seqs >= 32768 ? 256u : 64u);
-    const u32 pk_chunks = (n_seqs + pk_chunk - 1) / pk_chunk;
-    sk_cands cand;
-    for (int c = 0; c < SK_NR; c++) cand.r[c] = sk_r_cand_host[c] + (span - SK_TILE);
-#define SK_CHECK(x) do { st = (x); if (st != KS_OK) goto done; } while (0)
-#define SK_HIPCHECK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { st = ks_fail(ctx, KS_ERR_HIP, "%s: %s", #x, hipGetErrorString(e_)); goto done; } } while (0)
-
-    SK_CHECK(ks_alloc(ctx, &S->d_offsets, (size_t)n_seqs + 1));
-    SK_CHECK(ks_alloc(ctx, &S->d_counts, (size_t)n_seqs + 1));
-    if (n_seqs == 0) {
-        SK_HIPCHECK(hipMemsetAsync(S->d_offsets, 0, sizeof(u64), ctx->stream));
-        SK_CHECK(ks_alloc(ctx, &S->d_hashes, 1));
-        SK_CHECK(ks_alloc(ctx, &S->d_abunds, 1));
-        SK_CHECK(ks_stream_wait(ctx));
-        *out = S;
-        return KS_OK;
-    }
-    {
-        // windows, longest sequence, medium / long counts per candidate stride
-        // every small word the host zeroes before / reads after the launches lives in ONE control block — one memset, one
-        // device -> host copy per read-back instead of one per word (each is a dispatch of its own on this runtime):
-        // [0, 20) statistics, [20] ticket + status bits, [21] medium / long counts, [22] tiles of a packed plan, [23] kept hashes
-        // ... and the posting cursors (2048 x u32) and the tiles' status words sit right behind them: ONE allocation that the
-        // sketches object owns, ONE memset per call.  The tile count is known here when the plan needs no round trip (an
-        // upper bound otherwise: a launch with more tiles takes a status array of its own).
-        if (packed && planned && max_seq_len <= PK_MAX_LEN && !ks_dbg(ctx, KS_DBG_PLAN_SYNC)) {
-            const u64 b = n_res / (SK_MED_MAX - 15 - max_seq_len + 1) + pk_chunks + 1;
-            const u64 typical = n_res / 3800 + pk_chunks + 1;
-            if (b <= 2 * typical + 256 && b <= n_seqs) pk_bound = b;
-            else if (n_seqs <= 2 * typical + 256) pk_bound = n_seqs; // (a tile holds at least one sequence)
-        }
-        tiles_hint = packed ? pk_bound : n_res / cand.r[0] + 2;
-        SK_CHECK(ks_alloc(ctx, &S->ctl_block, (size_t)SK_CTL_WORDS + 1024 + tiles_hint + 1));
-        d_stats = S->ctl_block;
-        SK_HIPCHECK(hipMemsetAsync(d_stats, 0, ((size_t)SK_CTL_WORDS + 1024 + tiles_hint + 1) * sizeof(u64), ctx->stream));
-        ticket = (u32 *)(d_stats + 20); n_cls = (u32 *)(d_stats + 21); d_ntiles = (u32 *)(d_stats + 22);
-        u32 g = (n_seqs + 1023) / 1024;
-        if (g > 512) g = 512;
-        ks_timer_begin(ctx, "seq_stats");
-        hipLaunchKernelGGL(k_seq_stats, dim3(g), dim3(256), 0, ctx->stream, d_offs, n_seqs, p->ksize, span, cand, d_stats);
-        ks_timer_end(ctx);
-        if (packed) {
-            // The tile count of a packed plan is only known on the device and sizes the launch: it is read back here, with
-            // the statistics (one round trip whether or not the caller gave max_seq_len).
-            SK_CHECK(ks_alloc(ctx, &pk_tiles, (size_t)n_seqs));
-            SK_CHECK(ks_alloc(ctx, &pk_cnt, (size_t)pk_chunks));
-            SK_CHECK(ks_alloc(ctx, &tile_first, (size_t)n_seqs + 1)); // (a tile holds at least one sequence)
-            SK_CHECK(ks_alloc(ctx, &tile_g0, (size_t)n_seqs + 1));
-            ks_timer_begin(ctx, "tile_plan");
-            hipLaunchKernelGGL(k_pack_walk, dim3(pk_chunks), dim3(64), 0, ctx->stream, d_offs, n_seqs, pk_chunk, pk_tiles, pk_cnt);
-            hipLaunchKernelGGL(k_pack_fill, dim3(pk_chunks), dim3(256), 0, ctx->stream, d_offs, n_seqs, pk_chunk, (const u32 *)pk_tiles,
-                               (const u32 *)pk_cnt, pk_chunks, tile_first, tile_g0, d_ntiles);
-            ks_timer_end(ctx);
-            SK_HIPCHECK(hipGetLastError());
-        }
-        if (pk_bound) {
-            real_max = max_seq_len;
-            win_bound = n_res;
-            tile_R = 0; n_med = 0; n_long = 0; // nothing is deferred: every sequence fits a tile
-            pk_n_tiles = pk_bound;
-        } else if (!planned || packed) {
-            // no upper bound on the sequence length from the caller: the plan (tile stride, deferred sequences, slab size)
-            // comes from the batch itself, at the price of one device -> host round trip before the tiles are launched
-            {
-                const ks_fetch_seg f = ks_fetch_words(d_stats, ctx->h_pin, SK_CTL_WORDS * 2);
-                SK_CHECK(ks_stream_wait_fetch(ctx, &f, 1));
-            }
-            win_bound = ctx->h_pin[0];
-            if (packed) pk_n_tiles = *(u32 *)(ctx->h_pin + 22);
-            if (ctx->h_pin[1] > 0xfffffff0ULL) { st = ks_fail(ctx, KS_ERR_INVALID_ARG, "sequence longer than 2^32 residues"); goto done; }
-            real_max = (u32)ctx->h_pin[1];
-            // tile stride: fewest (tiles x sub-tiles + 1.75 x medium + 20 x long sequences), see sk_r_cand
-            double best = 0;
-            const double per_tile = (double)span / SK_TILE;
-            for (int c = 0; c < SK_NR; c++) {
-                if (c >= SK_NR - 2 && (u64)real_max + cand.r[c] + 15 > span) continue; // uncounted strides
-                const double cost = (double)(n_res / cand.r[c] + 1) * per_tile + 1.75 * (double)ctx->h_pin[4 + c] +
-                                    20.0 * (double)ctx->h_pin[4 + SK_NR + c];
-                if (c == 0 || cost < best) { best = cost; tile_R = cand.r[c]; n_med = ctx->h_pin[4 + c]; n_long = ctx->h_pin[4 + SK_NR + c]; }
-            }
-            if (const char *force = ks_dbg(ctx, KS_DBG_TILE_R)) // tuning aid: one of sk_r_cand (counted strides only)
-                for (int c = 0; c < SK_NR - 2; c++)
-                    if (atoi(force) == (int)sk_r_cand_host[c]) { tile_R = cand.r[c]; n_med = ctx->h_pin[4 + c]; n_long = ctx->h_pin[4 + SK_NR + c]; }
-            if (packed) { tile_R = 0; n_med = 0; n_long = ctx->h_pin[2]; } // nothing is deferred for its position
-        } else {
-            // max_seq_len given: everything the launches need follows from it, and what is only known on the device (how
-            // many sequences are deferred) is read there by kernels with fixed grids.  The widest stride whose tiles hold
-            // every sequence wherever it starts, else the stride the cost model picks for proteome-like batches.
-            real_max = max_seq_len;
-            win_bound = n_res;
-            tile_R = cand.r[3];
-            for (int c = SK_NR - 1; c >= SK_NR - 2; c--)
-                if ((u64)real_max + cand.r[c] + 15 <= span) { tile_R = cand.r[c]; break; }
-            const bool may_defer = (u64)real_max + tile_R + 15 > span;
-            const u64 n_t = n_res / tile_R + 1; // at most one deferred sequence per tile (the last that starts in it)
-            n_med = may_defer ? n_t : 0;
-            n_long = (may_defer && real_max > SK_MED_MAX) ? n_t : 0;
-        }
-        S->n_windows = win_bound;
-    }
-    {
-        // The tile kernel writes the final arrays in place (no compaction pass).  At scaled = 1 every window may be kept;
-        // at scaled > 1 the arrays are sized by the expected 1 / scaled of the windows plus a quarter, and a batch that keeps
-        // more (repeats whose hash falls under the threshold) is repeated with the full size.
-        out_cap = S->n_windows;
-        if (!(variant & 2) && p->scaled >= 2) {
-            const u64 want = S->n_windows / p->scaled + S->n_windows / (4ull * p->scaled) + 65536;
-            if (want < out_cap) out_cap = want;
-        }
-        if (const char *f = ks_dbg(ctx, KS_DBG_OUT_CAP)) // exercises the repeat on small inputs
-            if (!(variant & 2) && strtoull(f, nullptr, 10) < out_cap) out_cap = strtoull(f, nullptr, 10);
-        SK_CHECK(ks_alloc(ctx, &S->d_hashes, (size_t)out_cap));
-        SK_CHECK(ks_alloc(ctx, &S->d_abunds, (size_t)out_cap));
-
-        sk_args A;
-        memset(&A, 0, sizeof A);
-        A.res = d_res; A.offs = d_offs; A.n_seqs = n_seqs; A.n_res = n_res; A.k = p->ksize; A.seed = p->seed;
-        A.max_hash = ks_max_hash(p->scaled);
-        {
-            u64 sf = (1ULL << 48) / ((A.max_hash >> 32) + 1ULL);
-            A.sfix = sf > 0x7fffffffULL ? 0x7fffffffu : (u32)sf; // smaller only coarsens the buckets
-        }
-        A.lut = ctx->d_lut + 256 * p->moltype;
-        A.upper_only = p->moltype == KS_PROTEIN ? 1u : 0u;
-        if (const char *f = ks_dbg(ctx, KS_DBG_QCAP)) A.debug_qcap = (u32)atoi(f);
-        A.counts = S->d_counts;
-        A.drops_out = d_stats + 24;
-        A.span = SK_TILE; A.c_div = 1; A.c_rcp = 0; A.out_cap = out_cap; A.max_len_tile = 0xffffffffu; A.R = 1;
-        A.ticket = ticket; A.total_out = d_stats + 23;
-        if (part_pbits > 0 && S->n_windows > 0 && S->n_windows < 0xffff0000ULL) {
-            // first partition digit: the low 8 bits of the join's hash prefix (the whole prefix if it is <= 8 bits)
-            const int dbits = part_pbits < 8 ? part_pbits : 8;
-            S->part_pbits = part_pbits;
-            S->part_K = ks_join_prefix_mul(part_pbits, A.max_hash);
-            S->part_regions = 1u << dbits;
-            // one sub-region per XCD when a second partition pass follows (its tiles are per-segment anyway); when the
-            // regions ARE the join buckets (<= 8 prefix bits) they must stay contiguous
-            // (... as many as leave a sub-region >= 64k postings: the bucket scatter works on tiles of 8,192 postings per sub-region, and
-            // a 125k-query shard of the 1M workload cut 2,048 ways fills 2.2 of them — 0.25 ms against 0.17 with 512 sub-regions;
-            // 10k queries: 44 -> 22 us with 256 — while the 1M batch wants all 2,048: fewer posting cursors cost its sketch kernel
-            // 2.49 -> 2.61 ms)
-            S->part_sub_shift = 0u;
-            if (part_pbits > 8)
-                while (S->part_sub_shift < 3u && (S->n_windows / p->scaled) >> (8u + S->part_sub_shift + 1u) >= 65536u) S->part_sub_shift++;
-            if (const char *f = ks_dbg(ctx, KS_DBG_SUBSHIFT)) { const int v = atoi(f); if (part_pbits > 8 && v >= 0 && v <= 3) S->part_sub_shift = (u32)v; }
-            const u32 n_segs = S->part_regions << S->part_sub_shift;
-            const u64 per = S->n_windows / p->scaled / n_segs + 1; // FracMinHash keeps ~1/scaled of the windows
-            u64 cap = per + per / 4 + 8192;                 // uniform hashes fill regions evenly; skew -> fallback
-            cap = (cap + 8191) / 8192 * 8192;
-            S->part_cap = cap;
-            // (+ SK_TILE spare slots behind the last region: where a tile drops a digit that does not fit its region)
-            SK_CHECK(ks_alloc(ctx, &S->part_keys, (size_t)(cap * n_segs) + SK_TILE));
-            SK_CHECK(ks_alloc(ctx, &S->part_vals, (size_t)(cap * n_segs) + SK_TILE));
-            S->part_len = (u32 *)(S->ctl_block + SK_CTL_WORDS); // (zeroed with the control block)
-            A.part_keys = S->part_keys; A.part_vals = S->part_vals; A.part_cursor = S->part_len; A.part_cap = cap;
-            A.part_K = S->part_K; A.part_mask = S->part_regions - 1; A.part_sub_shift = S->part_sub_shift;
-            A.part_kshift = (S->part_K & (S->part_K - 1)) == 0 && S->part_K > 1 ? 32u - (u32)__builtin_ctz(S->part_K) : 0u;
-            // 10-byte postings: when the caller's join reads them (big indexes: the fingerprint joins), the digit is a bit field
-            // of the hash (scaled = 1) below a second partition level, and the sequence ids fit 24 bits
-            if (part_fmt10 && A.part_kshift && part_pbits > 8 && n_seqs < (1u << 24) && !ks_dbg(ctx, KS_DBG_POSTINGS12))
-                A.part_s = S->part_s = 32u + A.part_kshift;
-        }
-
-        // ---- medium / long sequences first: their unique counts feed the tile kernel's CSR prefix
-        if (n_med + n_long > 0) {
-            SK_CHECK(ks_alloc(ctx, &kept, (size_t)n_seqs));
-            A.kept = kept;
-            SK_CHECK(ks_alloc(ctx, &lg_hash, (size_t)n_res + 1));
-            SK_CHECK(ks_alloc(ctx, &lg_abund, (size_t)n_res + 1));
-            SK_CHECK(ks_alloc(ctx, &med_ids, (size_t)n_med + 1));
-            SK_CHECK(ks_alloc(ctx, &long_ids, (size_t)n_long + 1));
-            ks_timer_begin(ctx, "find_long");
-            hipLaunchKernelGGL(k_find_long, dim3((n_seqs + 255) / 256), dim3(256), 0, ctx->stream, d_offs, n_seqs, tile_R, span, med_ids, long_ids, n_cls,
-                               (u32)n_med, (u32)n_long);
-            ks_timer_end(ctx);
-            SK_HIPCHECK(hipGetLastError());
-        }
-        if (n_med > 0) {
-            sk_args M = A; // (keeps the posting arguments: a medium tile emits its own postings)
-            M.out_hash = lg_hash; M.out_abund = lg_abund; M.le_cap = SK_TILE; M.seq_list = med_ids; // local start <= 15, length <= SK_MED_MAX
-            M.out_cap = ~0ULL;
-            M.n_list = n_cls; M.n_list_cap = (u32)n_med;
-            ks_timer_begin(ctx, "sketch_medium");
-            hipLaunchKernelGGL((k_sketch_tiles<1, 0, 0>), dim3((u32)(n_med < 2048 ? n_med : 2048)), dim3(SK_THREADS), 0, ctx->stream, M);
-            ks_timer_end(ctx);
-            SK_HIPCHECK(hipGetLastError());
-        }
-        if (n_long > 0) {
-            // slab: 3 u64 + 4 u32 arrays of (max_len + 1) per workgroup, capped at ~2 GiB total
-            const u64 stride = (u64)real_max + 1;
-            const u64 per_wg = stride * (3 * 8 + 4 * 4);
-            u64 grid = (2ULL << 30) / per_wg;
-            if (grid < 1) grid = 1;
-            if (grid > n_long) grid = n_long;
-            if (grid > 512) grid = 512;
-            SK_CHECK(ks_alloc(ctx, &slab64, (size_t)(grid * stride * 3)));
-            SK_CHECK(ks_alloc(ctx, &slab32, (size_t)(grid * stride * 4)));
-            sk_long_args L;
-            L.a = A; L.long_ids = long_ids; L.n_long = n_cls; L.long_cap = (u32)n_long; L.max_len = real_max;
-            L.slab_keys = slab64; L.slab_tmp = slab64 + grid * stride; L.slab_sorted = slab64 + 2 * grid * stride;
-            L.slab_cnt = slab32; L.slab_ord = slab32 + grid * stride; L.slab_flag = slab32 + 2 * grid * stride;
-            L.slab_ab = slab32 + 3 * grid * stride;
-            L.lg_hash = lg_hash; L.lg_abund = lg_abund;
-            ks_timer_begin(ctx, "sketch_long");
-            hipLaunchKernelGGL(k_sketch_long, dim3((u32)grid), dim3(SK_THREADS), 0, ctx->stream, L);
-            ks_timer_end(ctx);
-            SK_HIPCHECK(hipGetLastError());
-        }
-
-        // ---- shared tiles: hash + sort/unique + CSR placement in one kernel (decoupled look-back across tiles)
-        const u64 n_tiles = packed ? pk_n_tiles : n_res / tile_R + 1;
-        if (n_tiles > 0x7ffffff0ULL) { st = ks_fail(ctx, KS_ERR_INVALID_ARG, "batch too large"); goto done; }
-        unsigned long long *tile_status_own = nullptr;
-        if (n_tiles <= tiles_hint) tile_status = (unsigned long long *)(S->ctl_block + SK_CTL_WORDS + 1024); // (zeroed with the control block)
-        else {
-            SK_CHECK(ks_alloc(ctx, &tile_status_own, (size_t)n_tiles + 1));
-            tile_status = tile_status_own;
-            SK_HIPCHECK(hipMemsetAsync(tile_status, 0, (size_t)n_tiles * sizeof(unsigned long long), ctx->stream));
-        }
-        tile_status_free = tile_status_own;
-        if (!packed) {
-            SK_CHECK(ks_alloc(ctx, &tile_first, (size_t)n_tiles + 1));
-            ks_timer_begin(ctx, "tile_plan");
-            hipLaunchKernelGGL(k_tile_plan, dim3((u32)((n_tiles + 256) / 256)), dim3(256), 0, ctx->stream, d_offs, n_seqs, (u32)n_tiles, tile_R, tile_first);
-            ks_timer_end(ctx);
-        }
-        A.seq_list = tile_first; A.le_cap = span - 16; A.R = tile_R; A.span = span; A.tile_g0 = tile_g0;
-        if (packed) A.max_len_tile = PK_MAX_LEN;
-        if (compact) { A.c_div = c_div; A.c_rcp = (u32)(((1ULL << 32) + c_div - 1) / c_div); }
-        A.out_hash = S->d_hashes; A.out_abund = S->d_abunds; A.csr = S->d_offsets;
-        A.tile_status = tile_status; A.n_tiles = (u32)n_tiles;
-        A.n_tiles_dev = pk_bound ? d_ntiles : nullptr;
-        // posting cursors as the medium tiles left them (a repeated launch starts from here)
-        if (A.part_cursor && n_med > 0) { // (without medium tiles the cursors are still zero: a repeat just clears them)
-            SK_CHECK(ks_alloc(ctx, &part_snap, 2048));
-            SK_HIPCHECK(hipMemcpyAsync(part_snap, A.part_cursor, 2048 * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        for (int attempt = 0; attempt < 2; attempt++) {
-            A.use_ticket = (ctx->sketch_use_ticket || attempt == 1) ? 1u : 0u;
-            A.debug_skip_tile = 0xffffffffu;
-            if (!A.use_ticket && ks_dbg(ctx, KS_DBG_LOOKBACK_SKIP)) A.debug_skip_tile = (u32)atoi(ks_dbg(ctx, KS_DBG_LOOKBACK_SKIP)); // (tests: a real expired spin)
-            if (attempt == 1) { // the dispatch-order launch gave up a look-back: start the tiles over, ids by ticket
-                ctx->sketch_use_ticket = true;
-                ctx->sketch_ticket_fallbacks++;
-                SK_HIPCHECK(hipMemsetAsync(tile_status, 0, (size_t)n_tiles * sizeof(unsigned long long), ctx->stream));
-                // (keeps the status bits the medium tiles set before the loop — "postings not emitted" — and drops only
-                // the look-back flag of the first attempt)
-                const u32 keep_bits = ((u32 *)(ctx->h_pin + 20))[1] & 2u;
-                SK_HIPCHECK(hipMemsetAsync(ticket, 0, 2 * sizeof(u32), ctx->stream));
-                if (keep_bits) {
-                    ((u32 *)(ctx->h_pin + 30))[0] = keep_bits;
-                    SK_HIPCHECK(hipMemcpyAsync(ticket + 1, ctx->h_pin + 30, sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
-                }
-                if (part_snap) SK_HIPCHECK(hipMemcpyAsync(A.part_cursor, part_snap, 2048 * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-                else if (A.part_cursor) SK_HIPCHECK(hipMemsetAsync(A.part_cursor, 0, 2048 * sizeof(u32), ctx->stream));
-            }
-            ks_timer_begin(ctx, "sketch_tiles");
-            // (the k-mer sizes of the reference's defaults and of BASELINE's configs run kernels with k folded in:
-            // src/rust/main.rs:28 k = 10, src/python/kmerseek/index.py:79-81 k = 24; any other size: the generic kernel)
-#define SK_LAUNCH_TILES(CMP_, KC_) hipLaunchKernelGGL((k_sketch_tiles<0, CMP_, KC_>), dim3((u32)n_tiles), dim3(SK_THREADS), 0, ctx->stream, A)
-            if (compact) {
-                if (p->ksize == 16) SK_LAUNCH_TILES(1, 16);
-                else if (p->ksize == 24) SK_LAUNCH_TILES(1, 24);
-                else SK_LAUNCH_TILES(1, 0);
-            } else {
-                if (p->ksize == 10) SK_LAUNCH_TILES(0, 10);
-                else if (p->ksize == 7) SK_LAUNCH_TILES(0, 7);
-                else SK_LAUNCH_TILES(0, 0);
-            }
-#undef SK_LAUNCH_TILES
-            ks_timer_end(ctx);
-            SK_HIPCHECK(hipGetLastError());
-
-            // ---- runs of medium / long sequences into their CSR slots
-            if (n_med > 0) {
-                ks_timer_begin(ctx, "place_long");
-                // medium runs: copy only (their tiles emitted their own postings)
-                hipLaunchKernelGGL(k_place_long, dim3((u32)(n_med < 1024 ? n_med : 1024)), dim3(256), 0, ctx->stream, (const u32 *)med_ids,
-                                   (const u32 *)n_cls, (u32)n_med, d_offs,
-                                   (const u64 *)S->d_offsets, (const u32 *)S->d_counts, (const u64 *)lg_hash, (const u32 *)lg_abund, S->d_hashes, S->d_abunds, out_cap,
-                                   (u64 *)nullptr, (u32 *)nullptr, (u32 *)nullptr, (u64)0, 0u, 0u, 0u, ticket, 0u);
-                ks_timer_end(ctx);
-            }
-            if (n_long > 0) {
-                ks_timer_begin(ctx, "place_long");
-                hipLaunchKernelGGL(k_place_long, dim3((u32)(n_long < 1024 ? n_long : 1024)), dim3(256), 0, ctx->stream, (const u32 *)long_ids,
-                                   (const u32 *)(n_cls + 1), (u32)n_long, d_offs,
-                                   (const u64 *)S->d_offsets, (const u32 *)S->d_counts, (const u64 *)lg_hash, (const u32 *)lg_abund, S->d_hashes, S->d_abunds, out_cap,
-                                   A.part_keys, A.part_vals, A.part_cursor, A.part_cap, A.part_K, A.part_mask, A.part_sub_shift, ticket, A.part_s);
-                ks_timer_end(ctx);
-            }
-            SK_HIPCHECK(hipGetLastError());
-            // total + look-back error flag to the host
-            if (allow_defer && attempt == 0 && (pk_bound || (planned && !packed)) && !ks_dbg(ctx, KS_DBG_FORCE_TICKET_RETRY)) {
-                // the caller's next wait on this stream (the search's) stands in for this one and brings the control block along
-                // (ks_sketch_pending_seg); everything else of this call that is freed below is reused in stream order
-                S->pend_stats = d_stats;
-                S->pending = 1; S->pend_out_cap = out_cap; S->pend_max_seq_len = max_seq_len; S->pend_planned = planned ? 1 : 0;
-                S->n_hashes = S->n_slots = out_cap; // (upper bounds until ks_sketch_finish_pending)
-                break;
-            }
-            {
-                const ks_fetch_seg f = ks_fetch_words(d_stats, ctx->h_pin, SK_CTL_WORDS * 2);
-                SK_CHECK(ks_stream_wait_fetch(ctx, &f, 1));
-            }
-            u32 &status_w = ((u32 *)(ctx->h_pin + 20))[1];
-            if (attempt == 0 && !A.use_ticket && ks_dbg(ctx, KS_DBG_FORCE_TICKET_RETRY)) status_w |= 1u; // exercises the repeat
-            if (!(status_w & 1u) || A.use_ticket) break;
-        }
-        if (S->pending) goto done;
-        // the CSR's slots hold the kept hashes; the distinct ones (the sketches) are fewer by the repeats
-        S->n_slots = ctx->h_pin[23];
-#ifdef SK_LB_STATS
-        fprintf(stderr, "[SK_LB_STATS] tiles %llu look-back rounds %llu\n", (unsigned long long)n_tiles, (unsigned long long)ctx->h_pin[25]);
-#endif
-        S->n_hashes = S->n_slots - (ctx->h_pin[24] < S->n_slots ? ctx->h_pin[24] : S->n_slots);
-        S->gapped = S->n_hashes != S->n_slots;
-        if (planned) {
-            S->n_windows = ctx->h_pin[0];
-            if (ctx->h_pin[1] > (u64)max_seq_len) { // the plan was made for shorter sequences: nothing of this launch can be trusted
-                st = ks_fail(ctx, KS_ERR_INVALID_ARG, "max_seq_len = %u, but the batch holds a sequence of %llu residues", max_seq_len,
-                             (unsigned long long)ctx->h_pin[1]);
-                goto done;
-            }
-        }
-        {
-            const u32 status = ((u32 *)(ctx->h_pin + 20))[1];
-            if (status & 1u) { st = ks_fail(ctx, KS_ERR_HIP, "sketch: tile look-back timed out"); goto done; }
-            if (status & 4u) { *redo = 1; goto done; }          // a compacting tile overflowed: the plain variant always fits
-            if (S->n_slots > out_cap) { *redo = 2; goto done; } // more kept hashes than the bounded outputs hold
-            if (status & 2u) { // a region overflowed (skewed hashes) or a tile could not code its sequences: no postings,
-                               // ks_search repartitions from the CSR instead
-                ks_pool_free(ctx, S->part_keys); ks_pool_free(ctx, S->part_vals); // (part_len lies in the control block)
-                S->part_keys = nullptr; S->part_vals = nullptr; S->part_len = nullptr; S->part_pbits = 0;
-            }
-        }
-    }
-
-done:
-    ks_pool_free(ctx, kept); ks_pool_free(ctx, tile_first); ks_pool_free(ctx, tile_status_free); ks_pool_free(ctx, part_snap);
-    ks_pool_free(ctx, med_ids); ks_pool_free(ctx, long_ids);
-    ks_pool_free(ctx, slab64); ks_pool_free(ctx, slab32); ks_pool_free(ctx, lg_hash); ks_pool_free(ctx, lg_abund);
-    ks_pool_free(ctx, pk_tiles); ks_pool_free(ctx, pk_cnt); ks_pool_free(ctx, tile_g0);
+    const sk_call C{d_res, d_offs, n_seqs, n_res, max_seq_len, p};
+    const int st = sketch_attempt_run(ctx, S, C, part_pbits, part_fmt10, variant, allow_defer, redo);
     if (st != KS_OK || *redo) {
         (void)hipStreamSynchronize(ctx->stream);
         ks_sketches_free(S);
@@ -2295,8 +2366,6 @@ done:
     }
     *out = S;
     return KS_OK;
-#undef SK_CHECK
-#undef SK_HIPCHECK
 }
 
 ks_fetch_seg ks_sketch_pending_seg(const ks_sketches *S) {
@@ -2306,25 +2375,10 @@ ks_fetch_seg ks_sketch_pending_seg(const ks_sketches *S) {
 int ks_sketch_finish_pending(ks_sketches *S, int *redo) {
     *redo = 0;
     if (!S || !S->pending) return KS_OK;
-    ks_ctx *ctx = S->ctx;
-    const u64 *stats = ctx->h_pin + KS_PIN_SKETCH;
     S->pending = 0;
     S->pend_stats = nullptr; // (lies in the control block, which the object keeps)
-    S->n_slots = stats[23];
-    S->n_hashes = S->n_slots - (stats[24] < S->n_slots ? stats[24] : S->n_slots);
-    S->gapped = S->n_hashes != S->n_slots;
-    if (S->pend_planned) {
-        S->n_windows = stats[0];
-        if (stats[1] > (u64)S->pend_max_seq_len)
-            return ks_fail(ctx, KS_ERR_INVALID_ARG, "max_seq_len = %u, but the batch holds a sequence of %llu residues", S->pend_max_seq_len,
-                           (unsigned long long)stats[1]);
-    }
-    const u32 status = ((const u32 *)(stats + 20))[1];
-    if (status & 1u) *redo = 3;                       // a look-back gave up: the plain call repeats the launch with tickets
-    else if (status & 4u) *redo = 1;                  // a compacting tile overflowed
-    else if (S->n_slots > S->pend_out_cap) *redo = 2;  // more kept hashes than the bounded outputs hold
-    else if (status & 2u) *redo = 4;                  // postings dropped (skewed hashes): whoever read them read garbage
-    return KS_OK;
+    // (a look-back that gave up: the plain call repeats the launch with tickets; postings dropped: whoever read them read garbage)
+    return sk_decode(S->ctx, S, S->ctx->h_pin + KS_PIN_SKETCH, S->pend_out_cap, S->pend_max_seq_len, S->pend_planned != 0, redo);
 }
 
 int ks_sketch_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res, u32 max_seq_len,
