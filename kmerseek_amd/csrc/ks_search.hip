@@ -11,8 +11,8 @@
 //   queries: postings (hash u64, qid u32) radix-PARTITIONED on the top P <= 16 hash bits only — the join
 //            needs locality, not order: each query posting binary-searches its full 64-bit hash in the
 //            LDS-staged index keys of its bucket.
-//   matches: (qid<<32|tid, abund) appended through a wave-aggregated atomic cursor, radix-sorted on the
-//            live id bits, then run-length reduced to COO sorted by (qid, tid).
+//   matches: one 8-byte record (qid << tbits | tid) << abits | abund per match, appended through a wave-aggregated atomic
+//            cursor, sorted on the live id bits, then run-length reduced to COO sorted by (qid, tid).
 #include "ks_device.h"
 
 // one wave per sequence: value[j] = f(seq id) for every posting j of the sequence
@@ -283,9 +283,8 @@ KS_DEV u32 jn_lower_bound_keys(const u64 *lk, u32 n, u64 h) {
 // reserve the round's slice of the pair list with ONE device-wide atomic, then write from registers.
 __global__ __launch_bounds__(JN_THREADS) void k_join_buckets_keys(const u64 *qkeys, const u32 *qids, const u64 *ikeys,
                                                              const u32 *itids, const u32 *iabunds, const u64 *q_lo,
-                                                             const u64 *q_hi, const u64 *dir_t, u64 *pair_keys,
-                                                             u32 *pair_vals, u64 cap, unsigned long long *cursor,
-                                                             int tbits, int abits, u32 split) {
+                                                             const u64 *q_hi, const u64 *dir_t, u64 *pair_keys, u64 cap,
+                                                             unsigned long long *cursor, int tbits, int abits, u32 split) {
     __shared__ u64 lk[JN_CAP_KEYS];
     __shared__ u32 wlist[JN_THREADS / 64][JK_WLIST]; // per-wave list of the round's pairs (query | index posting << 13)
     __shared__ u32 scan_smem[JN_THREADS / 64 + 1];
@@ -380,8 +379,7 @@ __global__ __launch_bounds__(JN_THREADS) void k_join_buckets_keys(const u64 *qke
                             const u32 q = qids[q0 + (en & 0x1fffu)];
                             const u64 jp = c0 + (en >> 13);
                             const u64 ids = ((u64)q << tbits) | itids[jp]; // ids packed tight: fewer sort passes
-                            if (pair_vals) { pair_keys[slot] = ids; pair_vals[slot] = iabunds[jp]; }
-                            else pair_keys[slot] = (ids << abits) | iabunds[jp]; // one 8-byte record per match
+                            pair_keys[slot] = (ids << abits) | iabunds[jp]; // one 8-byte record per match
                         }
                     }
                     __builtin_amdgcn_wave_barrier();
@@ -399,20 +397,15 @@ __global__ __launch_bounds__(JN_THREADS) void k_join_buckets_keys(const u64 *qke
                         // (four postings of the run at a time: their id / abundance loads are in flight together — an
                         // all-vs-all emits ~20 records per lane and round, and one memory latency per record was the kernel)
                         for (u32 j = 0; j < c; j += 4) {
-                            u32 tt[4], aa[4];
+                            u64 rec[4];
 #pragma unroll
                             for (u32 u = 0; u < 4; u++) {
                                 const bool on = j + u < c && slot + u < cap;
-                                tt[u] = on ? itids[j0 + j + u] : 0u;
-                                aa[u] = on ? iabunds[j0 + j + u] : 0u;
+                                rec[u] = on ? ((((u64)q << tbits) | itids[j0 + j + u]) << abits) | iabunds[j0 + j + u] : 0ULL;
                             }
 #pragma unroll
                             for (u32 u = 0; u < 4; u++)
-                                if (j + u < c && slot + u < cap) {
-                                    const u64 ids = ((u64)q << tbits) | tt[u];
-                                    if (pair_vals) { pair_keys[slot + u] = ids; pair_vals[slot + u] = aa[u]; }
-                                    else pair_keys[slot + u] = (ids << abits) | aa[u];
-                                }
+                                if (j + u < c && slot + u < cap) pair_keys[slot + u] = rec[u];
                             slot += (c - j) < 4u ? (c - j) : 4u;
                         }
                     }
@@ -559,8 +552,7 @@ template <int F10> struct jn_qfmt {
 template <int F10>
 __global__ __launch_bounds__(JN_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6))) void k_join_buckets(
     const u64 *qkeys, const u32 *qids, const u32 *ifp, const ks_post *ipost, const ks_bmeta *bmeta, const u64 *q_lo, const u64 *q_hi,
-    const u64 *dir_t, u64 *pair_keys, u32 *pair_vals, u64 cap, unsigned long long *cursors, u32 seg_mask, int tbits, int abits,
-    int fp_shift) {
+    const u64 *dir_t, u64 *pair_keys, u64 cap, unsigned long long *cursors, u32 seg_mask, int tbits, int abits, int fp_shift) {
     __shared__ u32 lk[JN_CAP + JN_PROBES]; // (+ slack: the probes of a slot read JN_PROBES entries whatever it holds)
     __shared__ unsigned short ldir[JN_DIR + 2]; // ldir[j] = staged fingerprints whose slot (jn_slot) is < j
     __shared__ u32 wlist[JN_THREADS / 64][JN_WLIST]; // per-wave candidate list: query slot | index posting << 13
@@ -585,7 +577,6 @@ __global__ __launch_bounds__(JN_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6
     const u32 seg = bkt & seg_mask;
     unsigned long long *cursor = cursors + (size_t)seg * JN_CUR_STRIDE;
     pair_keys += (u64)seg * cap;
-    if (pair_vals) pair_vals += (u64)seg * cap;
     const u64 kbase = bm.base; // the bucket's first key: the fingerprints count from it
     const u32 dirM = bm.slot_mul;
     // The first round's query postings are requested before the fingerprints are staged: the two latencies overlap.
@@ -712,7 +703,7 @@ __global__ __launch_bounds__(JN_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6
             const u32 wtotal = (u32)__builtin_amdgcn_readlane((int)wincl, 63); // candidates of this wave (a scalar: v_readlane, no LDS round trip)
             u32 conf = 0;                             // confirmed pairs this lane will write
             u64 rk[JN_WLIST / 64];
-            u32 rv[JN_WLIST / 64], okm = 0; // okm: bit it set = slot it of this lane holds a confirmed pair
+            u32 okm = 0; // okm: bit it set = slot it of this lane holds a confirmed pair
             if (wtotal <= JN_WLIST) { // uniform per wave
                 u32 p = wincl - mine;
                 while (cand) {
@@ -750,8 +741,7 @@ __global__ __launch_bounds__(JN_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6
                     const u32 ptid = praw[it].z, pab = praw[it].w;
                     const bool ok = k < wtotal && QF.same(pkey, hcand[it]); // confirmed
                     const u64 ids = ((u64)qcand[it] << tbits) | ptid; // ids packed tight: fewer sort passes
-                    rk[it] = ok ? (pair_vals ? ids : ((ids << abits) | pab)) : 0ULL; // packed: one 8-byte record per match
-                    rv[it] = ok ? pab : 0u;
+                    rk[it] = ok ? ((ids << abits) | pab) : 0ULL; // one 8-byte record per match
                     okm |= ok ? (1u << it) : 0u;
                     conf += ok ? 1u : 0u;
                 }
@@ -806,10 +796,7 @@ __global__ __launch_bounds__(JN_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6
 #pragma unroll
                     for (int it = 0; it < JN_WLIST / 64; it++) {
                         if ((okm >> it) & 1u) {
-                            if (slot < cap) {
-                                pair_keys[slot] = rk[it];
-                                if (pair_vals) pair_vals[slot] = rv[it];
-                            }
+                            if (slot < cap) pair_keys[slot] = rk[it];
                             slot++;
                         }
                     }
@@ -827,8 +814,7 @@ __global__ __launch_bounds__(JN_THREADS) __attribute__((amdgpu_waves_per_eu(6, 6
                             if (slot < cap) {
                                 const ks_post pt = postc[j0 + j];
                                 const u64 ids = ((u64)q << tbits) | pt.tid;
-                                if (pair_vals) { pair_keys[slot] = ids; pair_vals[slot] = pt.abund; }
-                                else pair_keys[slot] = (ids << abits) | pt.abund;
+                                pair_keys[slot] = (ids << abits) | pt.abund;
                             }
                         }
                     }
@@ -866,8 +852,7 @@ static_assert(JN_DIR % JS_DIR == 0 && ((JN_DIR / JS_DIR) & (JN_DIR / JS_DIR - 1)
 template <int F10>
 __global__ __launch_bounds__(JS_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8))) void k_join_sparse(
     const u64 *qkeys, const u32 *qids, const u32 *ifp, const ks_post *ipost, const ks_bmeta *bmeta, const u64 *q_lo, const u64 *q_hi,
-    const u64 *dir_t, u64 *pair_keys, u32 *pair_vals, u64 cap, unsigned long long *cursors, u32 seg_mask, int tbits, int abits,
-    int fp_shift) {
+    const u64 *dir_t, u64 *pair_keys, u64 cap, unsigned long long *cursors, u32 seg_mask, int tbits, int abits, int fp_shift) {
     __shared__ u64 qh[JS_QCAP];                       // query hashes, in slot order
     __shared__ u32 qf[JS_QCAP + 2];                   // their fingerprints (+ 2: the probes read two entries of a slot whatever it holds)
     __shared__ unsigned short qi[JS_QCAP];            // their place in the bucket's posting list
@@ -885,7 +870,6 @@ __global__ __launch_bounds__(JS_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8
     const u32 seg = bkt & seg_mask;
     unsigned long long *cursor = cursors + (size_t)seg * JN_CUR_STRIDE;
     pair_keys += (u64)seg * cap;
-    if (pair_vals) pair_vals += (u64)seg * cap;
     const u64 kbase = bm.base;
     const u32 dirM = bm.slot_mul;
     for (u64 q0 = qs; q0 < qe; q0 += JS_QCAP) { // slices of the bucket's queries (one, normally)
@@ -994,7 +978,7 @@ __global__ __launch_bounds__(JS_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8
             if (wtotal <= (u32)JS_WLIST) {
                 // lane k confirms and emits candidate k
                 u64 rk[JS_WLIST / 64];
-                u32 rv[JS_WLIST / 64], okm = 0, conf = 0;
+                u32 okm = 0, conf = 0;
                 // (posting — one 16-byte load — and query id requested for both rounds before anything is compared: see k_join_buckets)
                 uint4 praw[JS_WLIST / 64];
                 u32 qcand[JS_WLIST / 64], rcand[JS_WLIST / 64];
@@ -1013,8 +997,7 @@ __global__ __launch_bounds__(JS_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8
                     const u32 ptid = praw[it].z, pab = praw[it].w;
                     const bool ok = k < wtotal && pkey == qh[rcand[it]];
                     const u64 ids = ((u64)qcand[it] << tbits) | ptid;
-                    rk[it] = ok ? (pair_vals ? ids : ((ids << abits) | pab)) : 0ULL;
-                    rv[it] = ok ? pab : 0u;
+                    rk[it] = (ids << abits) | pab; // (stored only under okm)
                     okm |= ok ? (1u << it) : 0u;
                     conf += ok ? 1u : 0u;
                 }
@@ -1028,10 +1011,7 @@ __global__ __launch_bounds__(JS_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8
 #pragma unroll
                     for (int it = 0; it < JS_WLIST / 64; it++)
                         if ((okm >> it) & 1u) {
-                            if (slot < cap) {
-                                pair_keys[slot] = rk[it];
-                                if (pair_vals) pair_vals[slot] = rv[it];
-                            }
+                            if (slot < cap) pair_keys[slot] = rk[it];
                             slot++;
                         }
                 }
@@ -1049,8 +1029,7 @@ __global__ __launch_bounds__(JS_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8
                                 const u64 slot = atomicAdd(cursor, 1ULL);
                                 if (slot < cap) {
                                     const u64 ids = ((u64)QF.qid(qkr, qir, qi[r]) << tbits) | pt.tid;
-                                    if (pair_vals) { pair_keys[slot] = ids; pair_vals[slot] = pt.abund; }
-                                    else pair_keys[slot] = (ids << abits) | pt.abund;
+                                    pair_keys[slot] = (ids << abits) | pt.abund;
                                 }
                             }
                         }
@@ -1063,97 +1042,51 @@ __global__ __launch_bounds__(JS_THREADS) __attribute__((amdgpu_waves_per_eu(7, 8
 
 // the segments of the pair list (seg_cap records apart, prefix[s+1] - prefix[s] of them filled) -> one dense list
 struct jn_seg_table { u64 prefix[JN_SEGS + 1]; };
-__global__ __launch_bounds__(256) void k_pairs_compact(const u64 *src_k, const u32 *src_v, u64 seg_cap, jn_seg_table tab, u64 *dst_k, u32 *dst_v) {
+__global__ __launch_bounds__(256) void k_pairs_compact(const u64 *src_k, u64 seg_cap, jn_seg_table tab, u64 *dst_k) {
     const u32 s = blockIdx.y;
     const u64 n = tab.prefix[s + 1] - tab.prefix[s], i0 = (u64)blockIdx.x * 2048;
     const u64 *sk = src_k + (u64)s * seg_cap;
     u64 *dk = dst_k + tab.prefix[s];
     u64 kk[8]; // (requested together, then stored)
-    u32 vv[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const u64 i = i0 + (u64)j * 256 + threadIdx.x;
         kk[j] = i < n ? sk[i] : 0ULL;
-        vv[j] = (src_v && i < n) ? src_v[(u64)s * seg_cap + i] : 0u;
     }
 #pragma unroll
     for (int j = 0; j < 8; j++) {
         const u64 i = i0 + (u64)j * 256 + threadIdx.x;
-        if (i < n) {
-            dk[i] = kk[j];
-            if (src_v) dst_v[tab.prefix[s] + i] = vv[j];
-        }
+        if (i < n) dk[i] = kk[j];
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// pair reduce: sorted (qid<<32|tid, abund) -> COO rows
+// run boundaries of a sorted key list (union_run): heads, then the first record of every run
 // ---------------------------------------------------------------------------------------------
-// `abits` low bits of a key are payload (the packed abundance, 0 when the values travel separately): rows are runs of
-// equal keys >> abits
-__global__ __launch_bounds__(256) void k_pair_heads(const u64 *keys, u64 n, u32 *heads, int abits) {
+__global__ __launch_bounds__(256) void k_pair_heads(const u64 *keys, u64 n, u32 *heads) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    heads[i] = (i == 0 || (keys[i] >> abits) != (keys[i - 1] >> abits)) ? 1u : 0u;
+    heads[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
 }
 
 // hidx = exclusive scan of heads; row r starts where hidx steps from r to r+1
-__global__ __launch_bounds__(256) void k_pair_rows(const u64 *keys, const u32 *hidx, u64 n, u32 n_rows, u64 *row_start, int abits) {
+__global__ __launch_bounds__(256) void k_pair_rows(const u64 *keys, const u32 *hidx, u64 n, u32 n_rows, u64 *row_start) {
     u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    bool head = (i == 0) || (keys[i] >> abits) != (keys[i - 1] >> abits);
+    bool head = (i == 0) || keys[i] != keys[i - 1];
     if (head) row_start[hidx[i]] = i;
     if (i == 0) row_start[n_rows] = n;
 }
 
-// One pass over the sorted match list, coalesced: element i belongs to row hidx[i] (+1 if it is not a head, -1 based);
-// a wave sums abundance and count per row with a segmented shuffle scan and the last lane of each row segment adds the
-// partial to the row (rows span waves, so the adds are atomic: ~2 per wave).  Heads write the ids.
-// Rows beyond `rows_cap` are dropped (the row arrays are sized from the previous search's row count; the host repeats
-// this launch with exact arrays when the true count — known only after the scan — is larger).
-__global__ __launch_bounds__(256) void k_pair_reduce(const u64 *keys, const u32 *vals, const u32 *hidx, u64 n, u32 *qid,
-                                                     u32 *tid, u32 *isect, unsigned long long *nw, int tbits, int abits, u32 rows_cap) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    const u32 lane = threadIdx.x & 63;
-    const bool live = i < n;
-    u64 k = 0, w = 0;
-    u32 row = 0xffffffffu, c = 0;
-    bool head = false;
-    if (live) {
-        k = keys[i];
-        head = i == 0 || (keys[i - 1] >> abits) != (k >> abits);
-        row = hidx[i] - (head ? 0u : 1u);
-        w = vals ? (u64)vals[i] : (k & ((1ULL << abits) - 1ULL));
-        c = 1;
-        if (head && row < rows_cap) {
-            const u64 ids = k >> abits;
-            qid[row] = (u32)(ids >> tbits);
-            tid[row] = (u32)(ids & ((1ULL << tbits) - 1ULL));
-        }
-    }
-    // inclusive segmented scan (segments = equal row, rows ascend)
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u64 ow = __shfl_up(w, d, 64);
-        const u32 oc = __shfl_up(c, d, 64), orow = __shfl_up(row, d, 64);
-        if (lane >= (u32)d && orow == row) { w += ow; c += oc; }
-    }
-    const u32 nrow = __shfl_down(row, 1, 64);
-    // (plain stores for rows that sit wholly inside a wave were measured slower than these fire-and-forget adds)
-    if (live && (lane == 63 || nrow != row) && row < rows_cap) {
-        atomicAdd(&isect[row], c);
-        atomicAdd(&nw[row], (unsigned long long)w);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------
-// Sorted match list -> COO rows in ONE pass (packed records): heads, their prefix over the whole list and the per-row
-// sums used to be three passes (k_pair_heads, a device-wide scan, k_pair_reduce) — 0.23 ms of the 1M x 1M step and a quarter
-// of the all-vs-all one, where two records in three open a row.  Here a tile of PF_TILE records keeps its keys in
-// registers: sweep 1 marks the heads (bit per round) and counts them per (round, wave); wave 0 turns the 32 counts into
-// offsets and chains the tile's total through a decoupled look-back (ticket-ordered tiles, 8-byte {flag, value} words);
-// sweep 2 gives every record its row and sums count / abundance per row with the segmented shuffle scan of k_pair_reduce
-// (rows span waves and tiles, so the partial sums are added atomically: ~2 atomics per wave and round).
+// Sorted match list -> COO rows in ONE pass: heads, their prefix over the whole list and the per-row sums used to be three
+// passes (heads, a device-wide scan, a reduce) — 0.23 ms of the 1M x 1M step and a quarter of the all-vs-all one, where two
+// records in three open a row.  Here a tile of PF_TILE records keeps its keys in registers: sweep 1 marks the heads (bit per
+// round) and counts them per (round, wave); wave 0 turns the 32 counts into offsets and chains the tile's total through a
+// decoupled look-back (ticket-ordered tiles, 8-byte {flag, value} words); sweep 2 gives every record its row and sums
+// count / abundance per row with a segmented scan (rows span waves and tiles, so the partial sums are added atomically:
+// ~2 atomics per wave and round).  Rows beyond `rows_cap` are dropped (the row arrays are sized from the previous search's
+// row count; the host repeats this launch with exact arrays when the true count is larger).
 // ---------------------------------------------------------------------------------------------
 #define PF_THREADS 256
 #define PF_IPT 8
@@ -1313,7 +1246,6 @@ struct se_search {
     u64 n_q; // query postings (an upper bound while q->pending)
     int pbits, tbits, qbits, abits;
     u32 n_buckets, pfxK;
-    bool packed;   // a match is one 8-byte record (qid, tid, target abundance)
     bool pre, f10; // the sketch's postings are the partition's input (pre), in their 10-byte form (f10)
     u64 *dir_q;
     // cursor block: segment s of the pair list counts at word s * JN_CUR_STRIDE; word 1 = "a query bucket overflowed"
@@ -1322,10 +1254,9 @@ struct se_search {
     u32 *bcur;
     // the match list: n_segs segments of seg_cap records, seg_count[s] of them filled
     u64 *pk0, *pk1;
-    u32 *pv0, *pv1;
     u64 n_pairs, seg_cap, seg_count[JN_SEGS];
     u32 n_segs;
-    bool stop; // nothing is produced: the list needs slicing (*split_pairs) or the pending sketch a repeat (*sketch_redo)
+    bool stop; // nothing is produced: the batch needs slicing (se_split) or the pending sketch a repeat (*sketch_redo)
 };
 static_assert(2 * JN_SEGS <= KS_PIN_JOIN_WORDS, "pinned slot of the join's segment counts");
 
@@ -1446,7 +1377,6 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
     for (int attempt = 0; attempt < 2; attempt++) {
         const u64 seg_cap = Q.seg_cap;
         KS_TRY(sc.alloc(&Q.pk0, (size_t)(seg_cap * n_segs)));
-        if (!Q.packed) KS_TRY(sc.alloc(&Q.pv0, (size_t)(seg_cap * n_segs)));
         if (attempt > 0) // (attempt 0: cleared with the flag word above; the flag word survives)
             KS_HIP(ctx, hipMemset2DAsync(Q.cursor, (size_t)JN_CUR_STRIDE * sizeof(u64), 0, sizeof(u64), JN_SEGS, ctx->stream));
         ks_timer_begin(ctx, "join_buckets");
@@ -1456,11 +1386,11 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
         if (sparse)
             hipLaunchKernelGGL(q_fmt == 2 ? k_join_sparse<2> : (q_fmt ? k_join_sparse<1> : k_join_sparse<0>), dim3(n_buckets), dim3(JS_THREADS), 0, ctx->stream, (const u64 *)V.qk,
                                (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta, V.q_lo,
-                               V.q_hi, dir_t, Q.pk0, Q.pv0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
+                               V.q_hi, dir_t, Q.pk0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
         else if (ix->fp_layout)
             hipLaunchKernelGGL(q_fmt == 2 ? k_join_buckets<2> : (q_fmt ? k_join_buckets<1> : k_join_buckets<0>), dim3(n_buckets), dim3(JN_THREADS), 0, ctx->stream, (const u64 *)V.qk,
                                (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta, V.q_lo,
-                               V.q_hi, dir_t, Q.pk0, Q.pv0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
+                               V.q_hi, dir_t, Q.pk0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
         else {
             // workgroups per bucket: the matches per query posting of this context's previous search, when the buckets
             // hold enough query postings to share (KS_DEBUG_JOIN_SPLIT forces it)
@@ -1472,7 +1402,7 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
             if (const char *f = ks_dbg(ctx, KS_DBG_JOIN_SPLIT)) { const int v = atoi(f); if (v >= 1 && v <= 16) split = (u32)v; }
             hipLaunchKernelGGL(k_join_buckets_keys, dim3(n_buckets * split), dim3(JN_THREADS), 0, ctx->stream, (const u64 *)V.qk,
                                (const u32 *)V.qv, (const u64 *)ix->d_keys, (const u32 *)ix->d_tids, (const u32 *)ix->d_abunds,
-                               V.q_lo, V.q_hi, dir_t, Q.pk0, Q.pv0, seg_cap, Q.cursor, Q.tbits, Q.abits, split);
+                               V.q_lo, V.q_hi, dir_t, Q.pk0, seg_cap, Q.cursor, Q.tbits, Q.abits, split);
         }
         ks_timer_end(ctx);
         KS_HIP(ctx, hipGetLastError());
@@ -1505,25 +1435,23 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
         if (attempt == 1)
             return ks_fail(ctx, KS_ERR_CAPACITY, "search produced %llu matched posting pairs (segment cap %llu)",
                            (unsigned long long)Q.n_pairs, (unsigned long long)seg_cap);
-        sc.free(Q.pk0); sc.free(Q.pv0); Q.pk0 = nullptr; Q.pv0 = nullptr;
+        sc.free(Q.pk0); Q.pk0 = nullptr;
         Q.seg_cap = seg_max; // (same postings, same buckets, same segments: the repeat fits exactly)
         ctx->join_retries++;
     }
     return KS_OK;
 }
 
-// sort matches by (qid, tid) on the live id bits only; *pk / *pv: the sorted list
-static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk, u32 **pv) {
+// sort matches by (qid, tid) on the live id bits only; *pk: the sorted list
+static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk) {
     const u64 n_pairs = Q.n_pairs;
     const u32 n_segs = Q.n_segs;
     const int tbits = Q.tbits, qbits = Q.qbits, abits = Q.abits;
-    const bool packed = Q.packed;
     KS_TRY(sc.alloc(&Q.pk1, (size_t)n_pairs));
-    if (!packed) KS_TRY(sc.alloc(&Q.pv1, (size_t)n_pairs));
-    // Packed records go into the match sort as they lie: its first partition level reads the segments in place.  Only a list
-    // that sort declines (short lists, narrow keys: the LSD passes) or unpacked records are made dense by a copy first.
+    // The records go into the match sort as they lie: its first partition level reads the segments in place.  Only a list
+    // that sort declines (short lists, narrow keys: the LSD passes) is made dense by a copy first.
     int msd = 0;
-    if (n_segs > 1 && packed) {
+    if (n_segs > 1) {
         static_assert(JN_SEGS <= KS_MSD_MAX_SEGS, "segment table of the match sort");
         ks_msd_segs sg;
         sg.n = n_segs; sg.seg_cap = Q.seg_cap;
@@ -1543,88 +1471,63 @@ static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk, u32 **pv
         tab.prefix[n_segs] = acc;
         u64 seg_max = 0;
         for (u32 s_ = 0; s_ < n_segs; s_++) if (Q.seg_count[s_] > seg_max) seg_max = Q.seg_count[s_];
-        KS_LAUNCH(ctx, "pairs_compact", k_pairs_compact, dim3((u32)((seg_max + 2047) / 2048), n_segs), 256, (const u64 *)Q.pk0,
-                  (const u32 *)Q.pv0, Q.seg_cap, tab, Q.pk1, Q.pv1);
+        KS_LAUNCH(ctx, "pairs_compact", k_pairs_compact, dim3((u32)((seg_max + 2047) / 2048), n_segs), 256, (const u64 *)Q.pk0, Q.seg_cap,
+                  tab, Q.pk1);
         u64 *tk = Q.pk0; Q.pk0 = Q.pk1; Q.pk1 = tk;
-        u32 *tv = Q.pv0; Q.pv0 = Q.pv1; Q.pv1 = tv;
     }
-    *pk = nullptr;
-    *pv = nullptr;
+    // the match list pk0 is scratch from here on: ping-pong with pk1.  Three moves (two exact MSD partition levels + in-LDS
+    // bucket sort, ks_msd.hip) instead of one per 8 key bits
+    if (!msd) KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, abits, tbits + qbits, &msd));
+    if (msd) {
+        *pk = Q.pk0;
+        return KS_OK;
+    }
     int shifts[8], ns = 0;
     for (int sh = 0; sh < tbits + qbits; sh += 8) shifts[ns++] = abits + sh;
-    // the match list (pk0, pv0) is scratch from here on: ping-pong with (pk1, pv1).  Packed records: three moves
-    // (two exact MSD partition levels + in-LDS bucket sort, ks_msd.hip) instead of one per 8 key bits
-    if (packed && !msd) KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, abits, tbits + qbits, &msd));
-    if (msd) *pk = Q.pk0;
-    else if (packed) KS_TRY(ks_radix_sort_keys(ctx, KS_SORT_PAIRS, Q.pk0, Q.pk0, Q.pk1, n_pairs, shifts, ns, pk));
-    else KS_TRY(ks_radix_sort_u32(ctx, KS_SORT_PAIRS, Q.pk0, Q.pv0, Q.pk0, Q.pv0, Q.pk1, Q.pv1, n_pairs, shifts, ns, pk, pv));
-    return KS_OK;
+    return ks_radix_sort_keys(ctx, KS_SORT_PAIRS, Q.pk0, Q.pk0, Q.pk1, n_pairs, shifts, ns, pk);
 }
 
-// run-length reduce of the sorted matches into H's rows: one fused pass for packed records (k_pair_rows_fused); heads + scan
-// + reduce when the abundances travel apart (ids + abundance wider than 64 bits)
-static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk, const u32 *pv, ks_scratch &sc) {
+// run-length reduce of the sorted matches into H's rows: one fused pass (k_pair_rows_fused)
+static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk) {
     const u64 n_pairs = Q.n_pairs;
     const int tbits = Q.tbits, abits = Q.abits;
-    const bool fused = Q.packed && !ks_dbg(ctx, KS_DBG_UNFUSED_ROWS);
-    const u32 gp = (u32)((n_pairs + 255) / 256);
     const u32 pf_tiles = (u32)((n_pairs + PF_TILE - 1) / PF_TILE);
-    unsigned long long *pf_status = nullptr;
-    u32 *pf_ticket = nullptr, *heads = nullptr, *d_nrows = nullptr;
-    u32 *nrows_dev = nullptr;
-    if (!fused) { // (fused: the status words, the ticket pair and the row count lie in one block WITH the two row arrays the
-                  // pass adds into — allocated below, per attempt: one memset, one read-back)
-        KS_TRY(sc.alloc(&d_nrows, 1));
-        nrows_dev = d_nrows;
-        KS_TRY(sc.alloc(&heads, (size_t)n_pairs));
-        KS_LAUNCH(ctx, "pair_heads", k_pair_heads, gp, 256, pk, n_pairs, heads, abits);
-        KS_TRY(ks_scan_u32_inplace(ctx, heads, n_pairs, d_nrows));
-    }
-    // The row count is only known on the device here.  Instead of a round trip before the reduce, the row arrays take
+    // The row count is only known on the device here.  Instead of a round trip before the pass, the row arrays take
     // their size from the previous search of this context (+ 25 %) and the count is read with the final
-    // synchronisation; a search that produced more rows than that repeats the (cheap) reduce with exact arrays.
+    // synchronisation; a search that produced more rows than that repeats the (cheap) pass with exact arrays.
     u64 rows_cap = n_pairs;
     if (ctx->rows_hint && ctx->rows_hint < rows_cap && !ks_dbg(ctx, KS_DBG_NO_ROWS_HINT)) rows_cap = ctx->rows_hint;
     u32 n_rows = 0;
     const u32 *pin = (const u32 *)(ctx->h_pin + KS_PIN_ROWS); // ticket pair | row count
     for (int attempt = 0; attempt < 3; attempt++) { // (repeats: more rows than the guess; a look-back that gave up)
         KS_TRY(ks_alloc(ctx, &H->d_qid, (size_t)rows_cap)); KS_TRY(ks_alloc(ctx, &H->d_tid, (size_t)rows_cap));
-        {
-            // n_weighted (u64) | status words + ticket pair + row count (u64) | intersect (u32): zeroed together
-            const size_t st_words = fused ? (size_t)pf_tiles + 2 : 0, is_words = ((size_t)rows_cap + 1) / 2;
-            KS_TRY(ks_alloc(ctx, &H->d_block, (size_t)rows_cap + st_words + is_words));
-            H->d_nw = H->d_block;
-            H->d_isect = (u32 *)(H->d_block + rows_cap + st_words);
-            if (fused) {
-                pf_status = (unsigned long long *)(H->d_block + rows_cap);
-                pf_ticket = (u32 *)(pf_status + pf_tiles);
-                nrows_dev = pf_ticket + 2;
-            }
-            KS_HIP(ctx, hipMemsetAsync(H->d_block, 0, ((size_t)rows_cap + st_words + is_words) * sizeof(u64), ctx->stream));
-        }
-        if (fused)
-            KS_LAUNCH(ctx, "pair_rows", k_pair_rows_fused, pf_tiles, PF_THREADS, pk, n_pairs, H->d_qid, H->d_tid, H->d_isect,
-                      (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, nrows_dev,
-                      (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
-        else
-            KS_LAUNCH(ctx, "pair_reduce", k_pair_reduce, gp, 256, pk, pv, (const u32 *)heads, n_pairs, H->d_qid, H->d_tid, H->d_isect,
-                      (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap);
+        // n_weighted (u64) | status words + ticket pair + row count (u64) | intersect (u32): one block, zeroed together, per
+        // attempt (one memset, one read-back)
+        const size_t st_words = (size_t)pf_tiles + 2, is_words = ((size_t)rows_cap + 1) / 2;
+        KS_TRY(ks_alloc(ctx, &H->d_block, (size_t)rows_cap + st_words + is_words));
+        H->d_nw = H->d_block;
+        H->d_isect = (u32 *)(H->d_block + rows_cap + st_words);
+        unsigned long long *const pf_status = (unsigned long long *)(H->d_block + rows_cap);
+        u32 *const pf_ticket = (u32 *)(pf_status + pf_tiles);
+        KS_HIP(ctx, hipMemsetAsync(H->d_block, 0, ((size_t)rows_cap + st_words + is_words) * sizeof(u64), ctx->stream));
+        KS_LAUNCH(ctx, "pair_rows", k_pair_rows_fused, pf_tiles, PF_THREADS, pk, n_pairs, H->d_qid, H->d_tid, H->d_isect,
+                  (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, pf_ticket + 2,
+                  (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
         {
             ks_fetch_seg f[2];
-            f[0] = fused ? ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4) // ticket pair + row count
-                         : ks_fetch_words(d_nrows, ctx->h_pin + KS_PIN_ROWS + 1, 1);
+            f[0] = ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4); // ticket pair + row count
             const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
             KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
         }
         KS_TRY(ks_scan_status_check(ctx));
-        bool gave_up = fused && pin[1] != 0;
-        if (fused && ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY) && !ctx->rows_use_ticket) gave_up = true; // (tests)
+        bool gave_up = pin[1] != 0;
+        if (ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY) && !ctx->rows_use_ticket) gave_up = true; // (tests)
         if (gave_up) {
             if (ctx->rows_use_ticket || attempt == 2) return ks_fail(ctx, KS_ERR_HIP, "search: row look-back gave up waiting for a predecessor tile");
             ctx->rows_use_ticket = true; // dispatch order did not hold here: tickets from now on
             ctx->rows_ticket_fallbacks++;
         } else {
-            n_rows = pin[2]; // (fused: third word of the block fetched to the slot; else fetched there)
+            n_rows = pin[2];
             if (n_rows <= rows_cap) break;
             rows_cap = n_rows;
         }
@@ -1644,7 +1547,14 @@ static int se_no_hits(ks_ctx *ctx, ks_hits *H) {
     return KS_OK;
 }
 
-static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits *H, u64 *split_pairs, int *sketch_redo, bool *stop) {
+// Why a search produced nothing and its query batch has to be searched in slices: the match list would hold `pairs` records
+// (more than one list can), or the records of more than `seqs` query sequences would not fit their width.
+struct se_split {
+    u64 pairs;
+    u32 seqs;
+};
+
+static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits *H, se_split *split, int *sketch_redo, bool *stop) {
     se_search Q;
     memset(&Q, 0, sizeof Q);
     Q.ix = ix; Q.q = q; Q.n_q = q->n_hashes;
@@ -1657,13 +1567,26 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_
     if (Q.n_q == 0 || n_t == 0) return se_no_hits(ctx, H);
     Q.pbits = ix->pbits;
     Q.n_buckets = 1u << Q.pbits;
-    Q.tbits = bits_for(ix->n_targets); // pair key = qid << tbits | tid
-    // a match is one 8-byte record (qid, tid, target abundance) whenever the three fit 64 bits — always, short of
-    // ~10^5 x 10^5 proteins with 2^30-fold repeats — so the match sort moves keys only; else ids and abundance travel apart
+    // a match is one 8-byte record (qid << tbits | tid) << abits | target abundance, so the match sort moves keys only.  A
+    // batch whose three fields do not fit (~10^5 x 10^5 proteins with 2^30-fold repeats) is searched in slices of at most
+    // 2^(64 - tbits - abits) sequences: stop before anything is launched.  (KS_DEBUG_RECORD_BITS lowers the width: tests.)
+    Q.tbits = bits_for(ix->n_targets);
     Q.qbits = bits_for(q->n_seqs);
     Q.abits = bits_for_value(ix->max_abund);
-    Q.packed = Q.tbits + Q.qbits + Q.abits <= 64 && !ks_dbg(ctx, KS_DBG_UNPACKED_PAIRS);
-    if (!Q.packed) Q.abits = 0;
+    int width = 64;
+    if (const char *f = ks_dbg(ctx, KS_DBG_RECORD_BITS)) { const int v = atoi(f); if (v >= 1 && v < 64) width = v; }
+    if (Q.tbits + Q.qbits + Q.abits > width) {
+        if (q->pending) {
+            KS_TRY(se_wait_pending(ctx, Q, sketch_redo));
+            if ((*stop = Q.stop)) return KS_OK;
+        }
+        if (Q.tbits + Q.abits >= width)
+            return ks_fail(ctx, KS_ERR_CAPACITY, "search: %d target id bits + %d abundance bits leave no query id bit in a %d-bit match record",
+                           Q.tbits, Q.abits, width);
+        split->seqs = 1u << (width - Q.tbits - Q.abits); // the most sequences with bits_for(n) <= the bits left
+        *stop = true;
+        return KS_OK;
+    }
     Q.pfxK = ks_join_prefix_mul(Q.pbits, ks_max_hash(ix->params.scaled));
     ks_scratch sc(ctx);
     KS_TRY(sc.alloc(&Q.dir_q, (size_t)2 * Q.n_buckets + 2));
@@ -1686,7 +1609,7 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_
         KS_TRY(se_partition(ctx, Q, way, sc, &V));
         if (V.bucket_posting_bytes) H->bucket_posting_bytes = V.bucket_posting_bytes;
         bool overflowed = false;
-        KS_TRY(se_join(ctx, Q, V, way, cap, sc, split_pairs, sketch_redo, &overflowed));
+        KS_TRY(se_join(ctx, Q, V, way, cap, sc, &split->pairs, sketch_redo, &overflowed));
         if ((*stop = Q.stop)) return KS_OK;
         sc.free(V.qk0); sc.free(V.qk1); sc.free(V.qv0); sc.free(V.qv1);
         if (!overflowed) {
@@ -1694,25 +1617,25 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_
             break;
         }
         // a bucket overflowed (skewed hashes): drop the partial result and partition the dense way
-        sc.free(Q.pk0); sc.free(Q.pv0); Q.pk0 = nullptr; Q.pv0 = nullptr;
+        sc.free(Q.pk0); Q.pk0 = nullptr;
     }
     H->n_pair_instances = Q.n_pairs;
     const u64 want = Q.n_pairs + Q.n_pairs / 8;
     ctx->pair_cap_hint = want > ctx->pair_cap_hint / 2 ? want : ctx->pair_cap_hint / 2; // follows growth at once, decays slowly
     if (Q.n_pairs == 0) return se_no_hits(ctx, H);
     u64 *pk = nullptr;
-    u32 *pv = nullptr;
-    KS_TRY(se_sort(ctx, Q, sc, &pk, &pv));
-    return se_rows(ctx, Q, H, pk, pv, sc);
+    KS_TRY(se_sort(ctx, Q, sc, &pk));
+    return se_rows(ctx, Q, H, pk);
 }
 
-// One search with the whole query batch in one match list.  *split_pairs != 0 on return (with KS_OK and *out == NULL) means
-// the list would hold that many records — more than one list can (2^32) — and nothing was produced: the caller splits.
+// One search with the whole query batch in one match list.  A non-zero *split on return (with KS_OK and *out == NULL) means
+// that the list would hold more records than one list can (2^32), or that the batch has more sequences than the match
+// records have id bits for, and nothing was produced: the caller splits.
 // q->pending (ks_sketch_search_device): the sketch launches are queued and nobody has waited for them; the first wait of
 // the search stands in, and q's counts are upper bounds until then.  *sketch_redo != 0 on return (KS_OK, *out == NULL): the
 // sketch has to be repeated the plain way (ks_sketch_finish_pending) and nothing was produced.
-static int search_core(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, u64 *split_pairs, int *sketch_redo = nullptr) {
-    *split_pairs = 0;
+static int search_core(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, se_split *split, int *sketch_redo = nullptr) {
+    *split = se_split{};
     *out = nullptr;
     if (sketch_redo) *sketch_redo = 0;
     if (!ix || !q || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
@@ -1724,7 +1647,7 @@ static int search_core(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks
     memset(H, 0, sizeof *H);
     H->ctx = ctx;
     bool stop = false;
-    const int st = search_run(ctx, ix, q, H, split_pairs, sketch_redo, &stop);
+    const int st = search_run(ctx, ix, q, H, split, sketch_redo, &stop);
     if (st != KS_OK || stop) { (void)hipStreamSynchronize(ctx->stream); ks_hits_free(H); return st; }
     *out = H;
     return KS_OK;
@@ -1740,18 +1663,20 @@ __global__ __launch_bounds__(256) void k_add_u32(u32 *a, u64 n, u32 v) {
 }
 
 // ks_search: one match list when it fits; otherwise the query sequences are searched in contiguous slices whose lists
-// fit (a slice is a view of the batch's CSR: hits of different query ranges are disjoint and stay ordered by qid).
+// and records fit (a slice is a view of the batch's CSR: hits of different query ranges are disjoint and stay ordered by
+// qid; its qids are numbered from 0, so a slice of few sequences needs few id bits).
 int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo) {
     if (!out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    u64 need = 0;
+    se_split need;
     int st = search_core(ctx, ix, q, out, &need, sketch_redo);
-    if (st != KS_OK || need == 0) return st;
+    if (st != KS_OK || (need.pairs == 0 && need.seqs == 0)) return st;
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(q))); // (a slice is a view of the batch's plain CSR)
-    // ---- slices of roughly equal posting counts, each expected to produce KS_PAIR_LIMIT / 4 records
+    // ---- slices of roughly equal posting counts, each expected to produce KS_PAIR_LIMIT / 4 records, of at most max_seqs sequences
     std::vector<u64> offs((size_t)q->n_seqs + 1);
     KS_HIP(ctx, hipMemcpyAsync(offs.data(), q->d_offsets, offs.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    u64 n_slices = need / (KS_PAIR_LIMIT / 4) + 1;
+    u64 n_slices = need.pairs / (KS_PAIR_LIMIT / 4) + 1;
+    const u32 max_seqs = need.seqs ? need.seqs : q->n_seqs;
     std::vector<ks_hits *> parts;
     std::vector<u32> firsts;
     auto cleanup = [&]() { for (auto *h : parts) ks_hits_free(h); };
@@ -1759,7 +1684,7 @@ int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hit
     while (a < q->n_seqs) {
         const u64 want = q->n_hashes / n_slices + 1;
         u32 b = a + 1;
-        while (b < q->n_seqs && offs[b + 1] - offs[a] <= want) b++;
+        while (b < q->n_seqs && b - a < max_seqs && offs[b + 1] - offs[a] <= want) b++;
         for (;;) { // search sequences [a, b); halve the slice while it still overflows
             ks_sketches V;
             memset(&V, 0, sizeof V);
@@ -1770,13 +1695,13 @@ int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hit
             hipLaunchKernelGGL(k_rebase_offsets, dim3((V.n_seqs + 256) / 256), dim3(256), 0, ctx->stream, (const u64 *)q->d_offsets + a, offs[a],
                                V.n_seqs + 1, V.d_offsets);
             ks_hits *h = nullptr;
-            u64 more = 0;
+            se_split more;
             st = search_core(ctx, ix, &V, &h, &more);
             (void)hipStreamSynchronize(ctx->stream);
             ks_pool_free(ctx, V.d_offsets);
             if (st != KS_OK) { cleanup(); return st; }
-            if (more == 0) { parts.push_back(h); firsts.push_back(a); break; }
-            if (b - a == 1) { cleanup(); return ks_fail(ctx, KS_ERR_CAPACITY, "one query sequence matches %llu postings: beyond the match-list limit", (unsigned long long)more); }
+            if (more.pairs == 0 && more.seqs == 0) { parts.push_back(h); firsts.push_back(a); break; }
+            if (b - a == 1) { cleanup(); return ks_fail(ctx, KS_ERR_CAPACITY, "one query sequence matches %llu postings: beyond the match-list limit", (unsigned long long)more.pairs); }
             b = a + (b - a) / 2;
             n_slices *= 2;
         }
@@ -1849,7 +1774,7 @@ static int union_run(ks_ctx *ctx, const ks_sketches *in, ks_sketches *U) {
     KS_TRY(sc.alloc(&heads, (size_t)n));
     KS_TRY(sc.alloc(&d_nrows, 1));
     const u32 g = (u32)((n + 255) / 256);
-    KS_LAUNCH(ctx, "pair_heads", k_pair_heads, g, 256, (const u64 *)ks, n, heads, 0);
+    KS_LAUNCH(ctx, "pair_heads", k_pair_heads, g, 256, (const u64 *)ks, n, heads);
     KS_TRY(ks_scan_u32_inplace(ctx, heads, n, d_nrows));
     u64 *const rb = ctx->h_pin + KS_PIN_READ;
     KS_HIP(ctx, hipMemcpyAsync(rb, d_nrows, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
@@ -1858,7 +1783,7 @@ static int union_run(ks_ctx *ctx, const ks_sketches *in, ks_sketches *U) {
     U->n_hashes = U->n_slots = n_rows;
     KS_TRY(sc.alloc(&row_start, (size_t)n_rows + 1));
     KS_TRY(ks_alloc(ctx, &U->d_hashes, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &U->d_abunds, (size_t)n_rows));
-    KS_LAUNCH(ctx, "pair_rows", k_pair_rows, g, 256, (const u64 *)ks, (const u32 *)heads, n, n_rows, row_start, 0);
+    KS_LAUNCH(ctx, "pair_rows", k_pair_rows, g, 256, (const u64 *)ks, (const u32 *)heads, n, n_rows, row_start);
     KS_LAUNCH(ctx, "union_emit", k_union_emit, (n_rows + 255) / 256, 256, (const u64 *)ks, (const u32 *)vs, (const u64 *)row_start, n_rows,
               U->d_hashes, U->d_abunds);
     rb[0] = 0; rb[1] = n_rows;

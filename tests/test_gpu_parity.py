@@ -757,20 +757,36 @@ def test_bucket_scatter_overflow_falls_back_to_dense_partition(ctx):
         assert np.array_equal(g, w)
 
 
-def test_unpacked_match_records_equal_packed(ctx, monkeypatch):
-    """Matches normally travel as one 8-byte record (ids + target abundance packed); the 12-byte key + value form is
-    kept for id / abundance ranges that do not fit 64 bits.  Both must give the same rows."""
+def test_search_slices_the_queries_when_the_records_are_too_wide(ctx, monkeypatch):
+    """A match travels as one 8-byte record ((qid << tbits | tid) << abits | target abundance).  A batch whose ids and
+    abundance do not fit is searched in query slices of at most 2^(width - tbits - abits) sequences: with the width lowered
+    (debug knob) to slices of 32 queries, the same rows as the unsliced search, also when the sketch of the batch is still
+    pending (one-call sketch + search).  Target ids and abundance that fill the record on their own leave no room for even
+    one query: refused, and the context goes on working."""
     t_res, t_offs = synth.proteome(3000, stream=23)
     q_res, q_offs = synth.queries(1500, t_res, t_offs, stream=24)
     T = ctx.sketch_batch(t_res, t_offs, 7, 1, "hp")  # hp k=7: heavy repeats, abundances well above 1
     Q = ctx.sketch_batch(q_res, q_offs, 7, 1, "hp")
     ix = ctx.index_build(T)
-    a = ctx.search(ix, Q).to_host()
-    monkeypatch.setenv("KS_DEBUG_UNPACKED_PAIRS", "1")
-    b = ctx.search(ix, Q).to_host()
-    monkeypatch.delenv("KS_DEBUG_UNPACKED_PAIRS")
+    whole = ctx.search(ix, Q)
+    a = whole.to_host()
     assert len(a[0]) > 0
-    for x, y in zip(a, b):
+    tbits, abits = (3000 - 1).bit_length(), int(T.to_host()[2].max()).bit_length()
+    assert abits > 1
+    monkeypatch.setenv("KS_DEBUG_RECORD_BITS", str(tbits + abits + 5))
+    sliced = ctx.search(ix, Q)
+    b = sliced.to_host()
+    _, fused = ctx.sketch_search(ix, q_res, q_offs, want_sketches=False)
+    c = fused.to_host()
+    assert sliced.n_pair_instances == whole.n_pair_instances == fused.n_pair_instances
+    for x, y, z in zip(a, b, c):
+        assert np.array_equal(x, y) and np.array_equal(x, z)
+    monkeypatch.setenv("KS_DEBUG_RECORD_BITS", str(tbits + abits))
+    with pytest.raises(ks.KmerseekError) as e:
+        ctx.search(ix, Q)
+    assert e.value.status == ks._lib.KS_ERR_CAPACITY and "abundance bits" in str(e.value)
+    monkeypatch.delenv("KS_DEBUG_RECORD_BITS")
+    for x, y in zip(a, ctx.search(ix, Q).to_host()):
         assert np.array_equal(x, y)
 
 
@@ -997,8 +1013,10 @@ def test_match_sort_msd_equals_lsd_and_survives_skew(ctx):
     want = base.to_host()
     key = want[0].astype(np.uint64) << np.uint64(32) | want[1].astype(np.uint64)
     assert np.all(key[1:] > key[:-1]) and int(want[2].sum()) == base.n_pair_instances
+    # match records with 11 bits left for the query id: three query slices of <= 2048 sequences
+    record_bits = (len(seqs_t) - 1).bit_length() + int(T.to_host()[2].max()).bit_length() + 11
     for env in ({"KS_DEBUG_PAIRS_LSD": "1"}, {"KS_DEBUG_MSD_LDS_CAP": "64"}, {"KS_DEBUG_MSD_LDS_CAP": "700"},
-                {"KS_DEBUG_UNPACKED_PAIRS": "1"}, {"KS_DEBUG_UNFUSED_ROWS": "1"}, {"KS_DEBUG_NO_ROWS_HINT": "1"}):
+                {"KS_DEBUG_RECORD_BITS": str(record_bits)}, {"KS_DEBUG_NO_ROWS_HINT": "1"}):
         os.environ.update(env)
         try:
             got = ctx.search(ix, Q).to_host()

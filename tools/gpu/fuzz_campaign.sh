@@ -16,7 +16,7 @@ SEED=304 run fp_sparse_segs_coarse KS_DEBUG_JOIN_FP=1 KS_DEBUG_JOIN_SPARSE=1 KS_
 SEED=305 run fp_staged_segs_coarse KS_DEBUG_JOIN_FP=1 KS_DEBUG_JOIN_SPARSE=0 KS_DEBUG_JOIN_SEGS=1 KS_DEBUG_FP_COARSEN=10
 SEED=306 run rows_ticket_planless KS_DEBUG_ROWS_TICKET=1 KS_DEBUG_NO_PLAN=1
 SEED=307 run nocompact_nopack KS_DEBUG_NO_COMPACT=1 KS_DEBUG_NO_PACK=1
-SEED=308 run lsd_paths KS_DEBUG_PAIRS_LSD=1 KS_DEBUG_INDEX_LSD=1 KS_DEBUG_UNPACKED_PAIRS=1
+SEED=308 run lsd_paths KS_DEBUG_PAIRS_LSD=1 KS_DEBUG_INDEX_LSD=1
 fi
 if [ "$PART" != 1 ]; then
 SEED=310 run full_lists KS_DEBUG_QCAP=2
