@@ -73,12 +73,13 @@ extern "C" int ks_sketch_batch(ks_ctx *ctx, const uint8_t *residues, const uint6
 // k-mer its distinct hashes fill only the head of the slot.  One gather (one wave per sequence) closes the gaps: new offsets =
 // exclusive scan of the distinct counts.  Only batches with repeats pay for it, and only when something reads the arrays as a
 // plain CSR (copies to the host, the device accessors of the ABI, an index build, a search that starts from the CSR, a union).
+// cap: entries nh / na hold (n_hashes); a scan total beyond it is a count mismatch, which the host reports — nothing lands behind cap.
 __global__ __launch_bounds__(256) void k_dense_gather(const u64 *old_offs, const u64 *new_offs, const u64 *oh, const u32 *oa, u32 n_seqs,
-                                                      u64 *nh, u32 *na) {
+                                                      u64 *nh, u32 *na, u64 cap) {
     const u32 s = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (s >= n_seqs) return;
     const u64 src = old_offs[s], dst = new_offs[s], n = new_offs[s + 1] - dst;
-    for (u64 j = threadIdx.x & 63; j < n; j += 64) { nh[dst + j] = oh[src + j]; na[dst + j] = oa[src + j]; }
+    for (u64 j = threadIdx.x & 63; j < n && dst + j < cap; j += 64) { nh[dst + j] = oh[src + j]; na[dst + j] = oa[src + j]; }
 }
 
 int ks_sketches_make_dense(ks_ctx *ctx, ks_sketches *S) {
@@ -95,13 +96,21 @@ int ks_sketches_make_dense(ks_ctx *ctx, ks_sketches *S) {
     if (st == KS_OK && S->n_seqs) {
         ks_timer_begin(ctx, "dense_gather");
         hipLaunchKernelGGL(k_dense_gather, dim3((S->n_seqs + 3) / 4), dim3(256), 0, ctx->stream, (const u64 *)S->d_offsets, (const u64 *)no,
-                           (const u64 *)S->d_hashes, (const u32 *)S->d_abunds, S->n_seqs, nh, na);
+                           (const u64 *)S->d_hashes, (const u32 *)S->d_abunds, S->n_seqs, nh, na, S->n_hashes);
         ks_timer_end(ctx);
         if (hipGetLastError() != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "dense gather launch failed");
     }
+    // the scan total (the distinct counts summed) must be the n_hashes the arrays were sized by: read with the scan status
+    u64 *const total = ctx->h_pin + KS_PIN_DENSE;
+    *total = 0;
+    if (st == KS_OK && hipMemcpyAsync(total, no + S->n_seqs, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
+        st = ks_fail(ctx, KS_ERR_HIP, "dense gather read-back failed");
     if (st == KS_OK) st = ks_scan_status_fetch(ctx);
     if (st == KS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "dense gather failed");
     if (st == KS_OK) st = ks_scan_status_check(ctx);
+    if (st == KS_OK && *total != S->n_hashes)
+        st = ks_fail(ctx, KS_ERR_HIP, "internal error: sketch counts sum to %llu, but the batch holds %llu distinct hashes",
+                     (unsigned long long)*total, (unsigned long long)S->n_hashes);
     if (st != KS_OK) { ks_pool_free(ctx, no); ks_pool_free(ctx, nh); ks_pool_free(ctx, na); return st; }
     ks_pool_free(ctx, S->d_offsets); ks_pool_free(ctx, S->d_hashes); ks_pool_free(ctx, S->d_abunds);
     S->d_offsets = no; S->d_hashes = nh; S->d_abunds = na;

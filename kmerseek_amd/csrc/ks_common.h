@@ -268,13 +268,14 @@ enum : u32 {
     KS_PIN_SCAN = 195,       // u32: a one-launch scan gave up a look-back (ks_scan_status_check)
     KS_PIN_SORT_OFLOW = 196, // u32: a fixed capacity of the partitioned index sort did not hold
     KS_PIN_READ = 197,       // 2 words, one-call read-backs: index build, union, merge, k-mer positions
-    KS_PIN_END = 199,
+    KS_PIN_DENSE = 199,      // u64: the scan total of ks_sketches_make_dense
+    KS_PIN_END = 200,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_END && KS_PIN_END <= KS_PIN_WORDS,
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_END && KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
 // one index posting as the join fetches it for a candidate match: one 16-byte load

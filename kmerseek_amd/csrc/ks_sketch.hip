@@ -234,13 +234,16 @@ enum : u32 {
     SK_CTL_CLS = 21,      // u32 pair: medium | long sequences found (k_find_long)
     SK_CTL_PK_TILES = 22, // u32: tiles of a packed plan
     SK_CTL_TOTAL = 23,    // kept hashes (= CSR slots)
-    SK_CTL_DROPS = 24,    // kept hashes that repeat an earlier one of their sequence (slots the CSR leaves empty)
+    SK_CTL_DROPS = 24,    // kept hashes that repeat an earlier one of their sequence (slots the CSR leaves empty): shared tiles
     SK_CTL_LB_ROUNDS = 25, // look-back rounds (SK_LB_STATS builds only)
+    SK_CTL_DROPS_DEF = 26, // ... and the same of the medium / long sequences (their launches precede the ticket repeat, which
+                           //     clears only the shared tiles' word)
     SK_CTL_WORDS = 32,
     SK_CTL_CURSORS = SK_CTL_WORDS, SK_CTL_CURSOR_WORDS = 1024, // posting cursors: 2048 x u32
     SK_CTL_TILE_STATUS = SK_CTL_CURSORS + SK_CTL_CURSOR_WORDS,  // the tiles' status words, when the plan knew their number
 };
-static_assert(SK_CTL_LONG + SK_NR <= SK_CTL_TICKET && SK_CTL_LB_ROUNDS < SK_CTL_WORDS, "sketch control block layout");
+static_assert(SK_CTL_LONG + SK_NR <= SK_CTL_TICKET && SK_CTL_LB_ROUNDS < SK_CTL_WORDS && SK_CTL_DROPS_DEF < SK_CTL_WORDS,
+              "sketch control block layout");
 static_assert(SK_CTL_WORDS <= KS_PIN_SKETCH_WORDS && SK_CTL_WORDS <= KS_PIN_SKETCH_SYNC_WORDS, "pinned slots of the sketch read-back");
 // status bits of the control block (SK_CTL_TICKET, second word)
 enum : u32 { SK_ST_LOOKBACK = 1u, SK_ST_POSTINGS = 2u, SK_ST_COMPACT = 4u };
@@ -2106,8 +2109,11 @@ static int sk_launch_stats(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
 // ---- medium / long sequences first: their unique counts feed the tile kernel's CSR prefix
 static int sk_launch_deferred(ks_ctx *ctx, const sk_call &C, const sk_plan &P, sk_args &A, ks_scratch &sc, sk_bufs &B) {
     const u64 n_med = P.n_med, n_long = P.n_long;
+    // (the shared tiles read a deferred sequence's kept count from here even when the plan deferred nothing: a max_seq_len
+    // hint that is too small leaves a longer sequence to them, and the call then fails with KS_ERR_INVALID_ARG — the values
+    // read are never used, the pointer must be valid)
+    KS_TRY(sc.alloc(&A.kept, (size_t)C.n_seqs));
     if (n_med + n_long > 0) {
-        KS_TRY(sc.alloc(&A.kept, (size_t)C.n_seqs));
         KS_TRY(sc.alloc(&B.lg_hash, (size_t)C.n_res + 1));
         KS_TRY(sc.alloc(&B.lg_abund, (size_t)C.n_res + 1));
         KS_TRY(sc.alloc(&B.med_ids, (size_t)n_med + 1));
@@ -2167,6 +2173,7 @@ static int sk_launch_tiles(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
     A.out_hash = S->d_hashes; A.out_abund = S->d_abunds; A.csr = S->d_offsets;
     A.tile_status = tile_status; A.n_tiles = (u32)n_tiles;
     A.n_tiles_dev = P.pk_bound ? B.d_ntiles : nullptr;
+    A.drops_out = S->ctl_block + SK_CTL_DROPS;
     // posting cursors as the medium tiles left them (a repeated launch starts from here)
     u32 *part_snap = nullptr;
     if (A.part_cursor && P.n_med > 0) { // (without medium tiles the cursors are still zero: a repeat just clears them)
@@ -2182,6 +2189,8 @@ static int sk_launch_tiles(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
             ctx->sketch_use_ticket = true;
             ctx->sketch_ticket_fallbacks++;
             KS_HIP(ctx, hipMemsetAsync(tile_status, 0, (size_t)n_tiles * sizeof(unsigned long long), ctx->stream));
+            // (every tile of the first attempt counted its repeats, and the repeat counts them again)
+            KS_HIP(ctx, hipMemsetAsync(A.drops_out, 0, sizeof(u64), ctx->stream));
             // (keeps the status bits the medium tiles set before the loop — "postings not emitted" — and drops only
             // the look-back flag of the first attempt)
             const u32 keep_bits = ((const u32 *)(rb + SK_CTL_TICKET))[1] & SK_ST_POSTINGS;
@@ -2254,7 +2263,8 @@ static int sk_decode(ks_ctx *ctx, ks_sketches *S, const u64 *ctl, u64 out_cap, u
     *outcome = SK_OUT_FINE;
     // the CSR's slots hold the kept hashes; the distinct ones (the sketches) are fewer by the repeats
     S->n_slots = ctl[SK_CTL_TOTAL];
-    S->n_hashes = S->n_slots - (ctl[SK_CTL_DROPS] < S->n_slots ? ctl[SK_CTL_DROPS] : S->n_slots);
+    const u64 drops = ctl[SK_CTL_DROPS] + ctl[SK_CTL_DROPS_DEF];
+    S->n_hashes = S->n_slots - (drops < S->n_slots ? drops : S->n_slots);
     S->gapped = S->n_hashes != S->n_slots;
     if (planned) {
         S->n_windows = ctl[SK_CTL_WINDOWS];
@@ -2311,7 +2321,7 @@ static int sketch_attempt_run(ks_ctx *ctx, ks_sketches *S, const sk_call &C, int
     A.upper_only = p->moltype == KS_PROTEIN ? 1u : 0u;
     if (const char *f = ks_dbg(ctx, KS_DBG_QCAP)) A.debug_qcap = (u32)atoi(f);
     A.counts = S->d_counts;
-    A.drops_out = S->ctl_block + SK_CTL_DROPS;
+    A.drops_out = S->ctl_block + SK_CTL_DROPS_DEF; // (the deferred launches; sk_launch_tiles points the shared tiles at SK_CTL_DROPS)
     A.span = SK_TILE; A.c_div = 1; A.c_rcp = 0; A.out_cap = P.out_cap; A.max_len_tile = 0xffffffffu; A.R = 1;
     A.ticket = B.ticket; A.total_out = S->ctl_block + SK_CTL_TOTAL;
     if (P.part_pbits) {

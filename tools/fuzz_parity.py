@@ -1,12 +1,15 @@
 """Randomised differential test of the HIP path against the oracle (sketch, k-mer positions, search).
 
-    python tools/fuzz_parity.py [--cases N] [--seed S]
+    python tools/fuzz_parity.py [--cases N] [--seed S] [--entries] [--knob NAME=VALUE ...]
 
 Every case draws k, scaled, moltype, a length distribution (peptides / proteome-like / long / degenerate), an alphabet
 (full, 2-letter, single residue, with ambiguity codes and lower case) and a batch size, sketches it through the C ABI and
 compares with the oracle bit for bit; every third case also builds an index and searches it.  Prints one line per failure.
+With --entries every case also goes through ks_sketch_batch_device, and the one-call search takes, with a hint of 0, the exact
+longest sequence or more.  --knob sets a KS_DEBUG_* knob around every case (the context follows the environment).
 """
 import argparse
+import contextlib
 import os
 import sys
 
@@ -48,10 +51,49 @@ def draw_batch(rng):
     return res, offs
 
 
-def run(cases: int, seed: int) -> int:
-    """Runs `cases` random cases; prints one line per failure; returns the number of failures."""
+@contextlib.contextmanager
+def knobs_set(knobs):
+    """KS_DEBUG_<name> = value for each knob inside the block (a follow_debug_env context reads them on every call)."""
+    old = {n: os.environ.get("KS_DEBUG_" + n) for n in knobs}
+    os.environ.update({"KS_DEBUG_" + n: str(v) for n, v in knobs.items()})
+    try:
+        yield
+    finally:
+        for n, v in old.items():
+            if v is None:
+                os.environ.pop("KS_DEBUG_" + n, None)
+            else:
+                os.environ["KS_DEBUG_" + n] = v
+
+
+STAT_KEYS = ("ticket_fallbacks", "compact_fallbacks", "cap_fallbacks", "join_retries", "rows_ticket_fallbacks", "deferred", "redos")
+
+
+def _add_stats(ctx, stats):
+    if stats is None:
+        return
+    cur = {**ctx.sketch_stats(), **ctx.search_stats(), **ctx.fused_stats()}
+    for key in STAT_KEYS:
+        stats[key] = stats.get(key, 0) + cur[key]
+
+
+def _hint(erng, offs):
+    """0 (the batch is measured), the exact longest sequence, or more than that"""
+    mx = int((offs[1:] - offs[:-1]).max()) if len(offs) > 1 else 0
+    c = int(erng.integers(0, 3))
+    return 0 if c == 0 else (mx if c == 1 else mx + int(erng.integers(1, 5000)))
+
+
+def run(cases: int, seed: int, knobs=None, entries: bool = False, ctx_per_case: bool = False, stats=None) -> int:
+    """Runs `cases` random cases; prints one line per failure; returns the number of failures.
+    knobs: {name: value} of KS_DEBUG_* knobs set around every case.  entries: every case also goes through
+    ks_sketch_batch_device, and the one-call search takes a random hint (0, exact, more).  ctx_per_case: a fresh context per
+    case (forced repeats: a context that repeated once keeps the repeat's scheme).  stats: summed counters of the contexts
+    (STAT_KEYS).  The batches do not depend on knobs or entries: one seed, the same cases."""
     rng = np.random.default_rng(seed)
-    ctx = ks.Context(0, follow_debug_env=True)
+    erng = np.random.default_rng([seed, 1])  # (the entry choices: a stream of their own)
+    knobs = knobs or {}
+    ctx = None
     bad = 0
     for case in range(cases):
         k = int(rng.choice([1, 2, 3, 5, 7, 8, 9, 10, 15, 16, 17, 21, 24, 31, 32, 33, 48, 64, 100, 128]))
@@ -59,61 +101,99 @@ def run(cases: int, seed: int) -> int:
         mol = str(rng.choice(["protein", "dayhoff", "hp"]))
         res, offs = draw_batch(rng)
         tag = f"case {case}: k={k} scaled={scaled} {mol} n_seqs={len(offs) - 1} n_res={len(res)}"
-        try:
-            S = ctx.sketch_batch(res, offs, k, scaled, mol)
-            got = S.to_host()
-            want = oracle.sketch_batch(res, offs, k, scaled, mol, n_threads=8)
-            if not all(np.array_equal(g, w) for g, w in zip(got, want)):
-                print("SKETCH MISMATCH", tag); bad += 1; continue
-            # (process_kmers hashes the validated, already upper-case sequence as given — src/rust/index.rs:749-786 — so the
-            # oracle's position pass does not fold case; lower-case input never reaches it in the reference)
-            if case % 4 == 1 and len(res) < 200000 and not np.any((res >= 97) & (res <= 122)):
-                ps, pst, ph = ctx.kmer_positions(res, offs, k, scaled, mol)
-                o, mins, _ = want
-                ws, wst, wh = [], [], []
-                for i in range(len(offs) - 1):
-                    st, hh = oracle.kmer_positions(bytes(res[int(offs[i]):int(offs[i + 1])]), k, mol, mins[int(o[i]):int(o[i + 1])])
-                    ws.append(np.full(len(st), i, np.uint32)); wst.append(st); wh.append(hh)
-                if not (np.array_equal(ps, np.concatenate(ws)) and np.array_equal(pst, np.concatenate(wst)) and np.array_equal(ph, np.concatenate(wh))):
-                    ws_, wst_, wh_ = np.concatenate(ws), np.concatenate(wst), np.concatenate(wh)
-                    m = min(len(ps), len(ws_))
-                    d = np.nonzero((ps[:m] != ws_[:m]) | (pst[:m] != wst_[:m]) | (ph[:m] != wh_[:m]))[0]
-                    j = int(d[0]) if len(d) else m
-                    ctxt = ""
-                    if j < len(ws_):
-                        sq, st0 = int(ws_[j]), int(wst_[j])
-                        ctxt = f" want(seq={sq},start={st0},h={int(wh_[j])}) window={bytes(res[int(offs[sq]) + st0:int(offs[sq]) + st0 + k])!r} seqlen={int(offs[sq + 1] - offs[sq])} seqoff={int(offs[sq])}"
-                    if j < len(ps):
-                        ctxt += f" got(seq={int(ps[j])},start={int(pst[j])},h={int(ph[j])})"
-                    print("POSITIONS MISMATCH", tag, f"n_got={len(ps)} n_want={len(ws_)} first_diff={j}" + ctxt); bad += 1; continue
-            if case % 3 == 0:
-                res2, offs2 = draw_batch(rng)
-                if rng.random() < 0.5 and len(offs) > 2:  # make the queries overlap the targets
-                    cut = int(offs[len(offs) // 2])
-                    res2 = np.concatenate([res[:cut], res2]).astype(np.uint8)
-                    offs2 = np.concatenate([offs[:len(offs) // 2], offs2 + np.uint64(cut)]).astype(np.uint64)
-                Q = ctx.sketch_batch(res2, offs2, k, scaled, mol)
-                ix = ctx.index_build(S)
-                h = ctx.search(ix, Q).to_host()
-                qo, qm, _ = Q.to_host()
-                w = oracle.manysearch(qo, qm, want[0], want[1], want[2], n_threads=8)
-                if not all(np.array_equal(x, y) for x, y in zip(h, w)):
-                    print("SEARCH MISMATCH", tag, f"n_q={len(offs2) - 1} hits={len(h[0])}/{len(w[0])}"); bad += 1; continue
-                d_res, d_off = ctx.to_device(res2), ctx.to_device(offs2)
-                Q2 = ctx.sketch_queries_device(ix, d_res.ptr, d_off.ptr, len(offs2) - 1, len(res2))
-                h2 = ctx.search(ix, Q2).to_host()
-                if not all(np.array_equal(x, y) for x, y in zip(h2, w)):
-                    print("FUSED SEARCH MISMATCH", tag); bad += 1; continue
-                # one call (ks_sketch_search_device), with the bound that lets it defer the sketch's read-back
-                mx = int((offs2[1:] - offs2[:-1]).max()) if len(offs2) > 1 else 0
-                Q3, H3 = ctx.sketch_search_device(ix, d_res.ptr, d_off.ptr, len(offs2) - 1, len(res2), max_seq_len=mx)
-                if not (all(np.array_equal(x, y) for x, y in zip(H3.to_host(), w)) and
-                        all(np.array_equal(x, y) for x, y in zip(Q3.to_host(), Q.to_host()))):
-                    print("ONE-CALL SEARCH MISMATCH", tag); bad += 1; continue
-        except Exception as e:  # noqa: BLE001
-            print("ERROR", tag, repr(e)); bad += 1
+        if ctx is None or ctx_per_case:
+            if ctx is not None:
+                _add_stats(ctx, stats)
+                ctx.close()
+            ctx = ks.Context(0, follow_debug_env=True)
+        with knobs_set(knobs):
+            bad += _case(ctx, rng, erng, case, k, scaled, mol, res, offs, tag, entries)
+    _add_stats(ctx, stats)
     ctx.close()
     return bad
+
+
+def run_staged_copy(seed: int, knobs=None) -> int:
+    """One host batch above the staged-copy threshold (4 MiB of residues): sketch vs oracle.  Returns the number of failures."""
+    from kmerseek_amd import synth
+    res, offs = synth.proteome(16000, stream=seed)
+    assert len(res) >= 4 << 20
+    ctx = ks.Context(0, follow_debug_env=True)
+    try:
+        with knobs_set(knobs or {}):
+            got = ctx.sketch_batch(res, offs, 10, 1, "protein").to_host()
+        if not all(np.array_equal(g, w) for g, w in zip(got, oracle.sketch_batch(res, offs, 10, 1, "protein", n_threads=8))):
+            print("SKETCH MISMATCH staged copy"); return 1
+    finally:
+        ctx.close()
+    return 0
+
+
+def _case(ctx, rng, erng, case, k, scaled, mol, res, offs, tag, entries) -> int:
+    """One case of run(): 0 if it matches the oracle, 1 otherwise (with one line printed)."""
+    try:
+        S = ctx.sketch_batch(res, offs, k, scaled, mol)
+        got = S.to_host()
+        want = oracle.sketch_batch(res, offs, k, scaled, mol, n_threads=8)
+        if not all(np.array_equal(g, w) for g, w in zip(got, want)):
+            print("SKETCH MISMATCH", tag); return 1
+        if entries:
+            hint = _hint(erng, offs)
+            d_res, d_off = ctx.to_device(res), ctx.to_device(offs)
+            got = ctx.sketch_batch_device(d_res.ptr, d_off.ptr, len(offs) - 1, len(res), k, scaled, mol, max_seq_len=hint).to_host()
+            if not all(np.array_equal(g, w) for g, w in zip(got, want)):
+                print("DEVICE SKETCH MISMATCH", tag, f"max_seq_len={hint}"); return 1
+        # (process_kmers hashes the validated, already upper-case sequence as given — src/rust/index.rs:749-786 — so the
+        # oracle's position pass does not fold case; lower-case input never reaches it in the reference)
+        if case % 4 == 1 and len(res) < 200000 and not np.any((res >= 97) & (res <= 122)):
+            ps, pst, ph = ctx.kmer_positions(res, offs, k, scaled, mol)
+            o, mins, _ = want
+            ws, wst, wh = [], [], []
+            for i in range(len(offs) - 1):
+                st, hh = oracle.kmer_positions(bytes(res[int(offs[i]):int(offs[i + 1])]), k, mol, mins[int(o[i]):int(o[i + 1])])
+                ws.append(np.full(len(st), i, np.uint32)); wst.append(st); wh.append(hh)
+            if not (np.array_equal(ps, np.concatenate(ws)) and np.array_equal(pst, np.concatenate(wst)) and np.array_equal(ph, np.concatenate(wh))):
+                ws_, wst_, wh_ = np.concatenate(ws), np.concatenate(wst), np.concatenate(wh)
+                m = min(len(ps), len(ws_))
+                d = np.nonzero((ps[:m] != ws_[:m]) | (pst[:m] != wst_[:m]) | (ph[:m] != wh_[:m]))[0]
+                j = int(d[0]) if len(d) else m
+                ctxt = ""
+                if j < len(ws_):
+                    sq, st0 = int(ws_[j]), int(wst_[j])
+                    ctxt = f" want(seq={sq},start={st0},h={int(wh_[j])}) window={bytes(res[int(offs[sq]) + st0:int(offs[sq]) + st0 + k])!r} seqlen={int(offs[sq + 1] - offs[sq])} seqoff={int(offs[sq])}"
+                if j < len(ps):
+                    ctxt += f" got(seq={int(ps[j])},start={int(pst[j])},h={int(ph[j])})"
+                print("POSITIONS MISMATCH", tag, f"n_got={len(ps)} n_want={len(ws_)} first_diff={j}" + ctxt); return 1
+        if case % 3 == 0:
+            res2, offs2 = draw_batch(rng)
+            if rng.random() < 0.5 and len(offs) > 2:  # make the queries overlap the targets
+                cut = int(offs[len(offs) // 2])
+                res2 = np.concatenate([res[:cut], res2]).astype(np.uint8)
+                offs2 = np.concatenate([offs[:len(offs) // 2], offs2 + np.uint64(cut)]).astype(np.uint64)
+            Q = ctx.sketch_batch(res2, offs2, k, scaled, mol)
+            ix = ctx.index_build(S)
+            h = ctx.search(ix, Q).to_host()
+            qo, qm, _ = Q.to_host()
+            w = oracle.manysearch(qo, qm, want[0], want[1], want[2], n_threads=8)
+            if not all(np.array_equal(x, y) for x, y in zip(h, w)):
+                print("SEARCH MISMATCH", tag, f"n_q={len(offs2) - 1} hits={len(h[0])}/{len(w[0])}"); return 1
+            d_res, d_off = ctx.to_device(res2), ctx.to_device(offs2)
+            Q2 = ctx.sketch_queries_device(ix, d_res.ptr, d_off.ptr, len(offs2) - 1, len(res2))
+            h2 = ctx.search(ix, Q2).to_host()
+            if not all(np.array_equal(x, y) for x, y in zip(h2, w)):
+                print("FUSED SEARCH MISMATCH", tag); return 1
+            # one call (ks_sketch_search_device), with the bound that lets it defer the sketch's read-back (--entries: a
+            # random one of 0, exact, more)
+            mx = int((offs2[1:] - offs2[:-1]).max()) if len(offs2) > 1 else 0
+            if entries:
+                mx = _hint(erng, offs2)
+            Q3, H3 = ctx.sketch_search_device(ix, d_res.ptr, d_off.ptr, len(offs2) - 1, len(res2), max_seq_len=mx)
+            if not (all(np.array_equal(x, y) for x, y in zip(H3.to_host(), w)) and
+                    all(np.array_equal(x, y) for x, y in zip(Q3.to_host(), Q.to_host()))):
+                print("ONE-CALL SEARCH MISMATCH", tag); return 1
+    except Exception as e:  # noqa: BLE001
+        print("ERROR", tag, repr(e)); return 1
+    return 0
 
 
 def run_big(cases: int, seed: int) -> int:
@@ -193,8 +273,11 @@ def main():
     ap.add_argument("--cases", type=int, default=200)
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--big", action="store_true", help="few large batches instead of many small ones")
+    ap.add_argument("--entries", action="store_true", help="also ks_sketch_batch_device, and random hints for the one-call search")
+    ap.add_argument("--knob", action="append", default=[], help="NAME=VALUE: KS_DEBUG_NAME around every case (repeatable)")
     a = ap.parse_args()
-    bad = run_big(a.cases, a.seed) if a.big else run(a.cases, a.seed)
+    knobs = dict(kv.split("=", 1) for kv in a.knob)
+    bad = run_big(a.cases, a.seed) if a.big else run(a.cases, a.seed, knobs=knobs, entries=a.entries)
     print(f"{a.cases} cases, {bad} failures")
     sys.exit(1 if bad else 0)
 
