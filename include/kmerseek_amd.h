@@ -299,6 +299,38 @@ int ks_hits_merge_by_qid_device(ks_ctx *ctx, const uint32_t *d_qid, const uint32
                                 uint32_t *d_out_qid, uint32_t *d_out_tid, uint32_t *d_out_intersect, uint64_t *d_out_n_weighted);
 void ks_hits_free(ks_hits *h);
 
+/* ---- search options (opt-in; the entries above are these with opts == NULL) --------------------------------------------- */
+
+/* Per row, the statistics of the target abundances of the shared hashes that the manysearch columns average_abund /
+ * median_abund / std_abund need (src/python/kmerseek/search.py:125-141): with it the match records of a row are sorted by
+ * abundance too, and one pass over them computes
+ *   median2 = 2 x the median (exact: the middle value doubled for an odd count, the sum of the two middle values otherwise),
+ *   ss      = the sum of (a - mean)^2 over the row in f64, with sum += a, mean = sum / n, ss += (a - mean) * (a - mean)
+ *             evaluated in that order over the ascending abundances (no contraction into fma): bit-identical to a host
+ *             loop that does the same.  std = sqrt(ss / n) and mean = n_weighted / n stay with the caller. */
+#define KS_SEARCH_ABUND_STATS 1u
+typedef struct ks_search_opts {
+    uint32_t flags;         /* KS_SEARCH_* */
+    uint32_t reserved;      /* 0 */
+    double min_containment; /* keep a row iff (double)intersect / (double)|q| >= this (|q| = the query's distinct hashes);
+                               0 keeps every row.  Negative or NaN: KS_ERR_INVALID_ARG.  Kept rows stay in (qid, tid) order. */
+} ks_search_opts;
+/* ks_search / ks_sketch_search_device / ks_sketch_search with options.  opts == NULL or all zero: exactly the plain call.
+ * Options are checked before any device work. */
+int ks_search_ex(ks_ctx *ctx, const ks_index *index, const ks_sketches *queries, const ks_search_opts *opts, ks_hits **out);
+int ks_sketch_search_device_ex(ks_ctx *ctx, const ks_index *index, const uint8_t *d_residues, const uint64_t *d_seq_offsets,
+                               uint32_t n_seqs, uint64_t n_residues, uint32_t max_seq_len, const ks_search_opts *opts,
+                               ks_sketches **sketches_out, ks_hits **hits_out);
+int ks_sketch_search_ex(ks_ctx *ctx, const ks_index *index, const uint8_t *residues, const uint64_t *seq_offsets,
+                        uint32_t n_seqs, const ks_search_opts *opts, ks_sketches **sketches_out, ks_hits **hits_out);
+/* 1 if h was produced with KS_SEARCH_ABUND_STATS (the two columns below exist), else 0 */
+int ks_hits_has_abund_stats(const ks_hits *h);
+/* device columns (ks_hits_count entries, valid until ks_hits_free), NULL without KS_SEARCH_ABUND_STATS */
+const uint64_t *ks_hits_device_median2(const ks_hits *h);
+const double *ks_hits_device_abund_ss(const ks_hits *h);
+/* either destination may be NULL; KS_ERR_INVALID_ARG for hits without the statistics */
+int ks_hits_copy_abund_stats_to_host(ks_ctx *ctx, const ks_hits *h, uint64_t *median2, double *ss);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Per-kernel HIP-event timing on ctx's stream.  enable: 0 off; 1 events bracket every launch (~20 us of idle queue

@@ -124,9 +124,12 @@ class ProteomeIndex {
     // they are laid out once as a device-resident ks_index (rebuilt after the next store_signatures) and every call is one
     // ks_sketch_search of the whole query batch.  Queries go through the same pre-step as create_protein_signature
     // (validate / resolve; `upper` = the FASTA path's upper-casing); rows come out ordered by (query, match key).
-    std::vector<SearchResult> search(const std::vector<std::pair<std::string, std::string>> &queries, bool upper = false);
+    // min_containment > 0 keeps the rows whose containment (intersect / distinct query hashes) is at least that — branchwater
+    // manysearch's `threshold` — filtered on the device; 0 keeps every row.
+    std::vector<SearchResult> search(const std::vector<std::pair<std::string, std::string>> &queries, bool upper = false,
+                                     double min_containment = 0.0);
     // every record of a FASTA file (plain / gzip / zstd / bzip2 / xz) as queries, `batch_size` records per GPU batch
-    std::vector<SearchResult> search_fasta(const std::string &fasta_path, size_t batch_size = 100000);
+    std::vector<SearchResult> search_fasta(const std::string &fasta_path, size_t batch_size = 100000, double min_containment = 0.0);
     // the two-line form a consumer streams into the reference's CSV: column names in file order
     static const std::vector<std::string> &search_columns();
 

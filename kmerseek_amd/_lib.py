@@ -37,6 +37,13 @@ class ks_residue_error(C.Structure):
     _fields_ = [("seq_index", C.c_uint32), ("position", C.c_uint32), ("residue", C.c_uint8)]
 
 
+KS_SEARCH_ABUND_STATS = 1
+
+
+class ks_search_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("min_containment", C.c_double)]
+
+
 class ks_kernel_time(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -114,6 +121,14 @@ SIGNATURES = {
     "ks_hits_unpack64_device": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.c_int, _vp, _vp, _vp, _vp]),
     "ks_hits_merge_by_qid_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(C.c_uint64), C.c_uint32, C.c_uint32, _vp, _vp, _vp, _vp]),
     "ks_hits_free": (None, [_vp]),
+    "ks_search_ex": (C.c_int, [_vp, _vp, _vp, C.POINTER(ks_search_opts), _pp]),
+    "ks_sketch_search_device_ex": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, C.POINTER(ks_search_opts), _pp,
+                                             _pp]),
+    "ks_sketch_search_ex": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.POINTER(ks_search_opts), _pp, _pp]),
+    "ks_hits_has_abund_stats": (C.c_int, [_vp]),
+    "ks_hits_device_median2": (_vp, [_vp]),
+    "ks_hits_device_abund_ss": (_vp, [_vp]),
+    "ks_hits_copy_abund_stats_to_host": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ks_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ks_timing_reset": (C.c_int, [_vp]),
     "ks_timing_get": (C.c_int, [_vp, C.POINTER(ks_kernel_time), C.c_uint32, _u32p]),

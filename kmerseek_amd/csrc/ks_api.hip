@@ -320,13 +320,21 @@ extern "C" int ks_search(ks_ctx *ctx, const ks_index *index, const ks_sketches *
     return ks_search_impl(ctx, index, queries, out);
     });
 }
+extern "C" int ks_search_ex(ks_ctx *ctx, const ks_index *index, const ks_sketches *queries, const ks_search_opts *opts, ks_hits **out) {
+    return ks_guard(ctx, [&]() -> int {
+    KS_TRY(ks_search_opts_check(ctx, opts));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    return ks_search_impl(ctx, index, queries, out, nullptr, opts);
+    });
+}
 // One call for "sketch this query batch and search it": the sketch launches are queued WITHOUT the wait at their end, the
 // search's partition and join follow on the same stream with sizes taken from upper bounds, and the search's first wait
 // brings the sketch's control block back together with the join's counts — two waits per step instead of three.  A batch whose
 // sketch has to be repeated (an economy that did not fit, dropped postings, a look-back that gave up: all rare) is simply
 // done again with the two plain calls.
 static int sketch_search_impl(ks_ctx *ctx, const ks_index *index, const uint8_t *d_residues, const uint64_t *d_seq_offsets, uint32_t n_seqs,
-                              uint64_t n_residues, uint32_t max_seq_len, ks_sketches **sketches_out, ks_hits **hits_out) {
+                              uint64_t n_residues, uint32_t max_seq_len, const ks_search_opts *opts, ks_sketches **sketches_out,
+                              ks_hits **hits_out) {
     *hits_out = nullptr;
     if (sketches_out) *sketches_out = nullptr;
     const int fmt10 = (index->fp_layout && index->fp_shift == 32 - index->pbits) ? 1 : 0;
@@ -337,7 +345,7 @@ static int sketch_search_impl(ks_ctx *ctx, const ks_index *index, const uint8_t 
     if (st != KS_OK) return st;
     const bool deferred = S->pending != 0;
     int redo = 0;
-    st = ks_search_impl(ctx, index, S, &H, &redo);
+    st = ks_search_impl(ctx, index, S, &H, &redo, opts);
     if (S->pending) { // (the search failed before its first wait)
         const ks_fetch_seg f = ks_sketch_pending_seg(S);
         int r2 = 0;
@@ -350,7 +358,7 @@ static int sketch_search_impl(ks_ctx *ctx, const ks_index *index, const uint8_t 
         ks_sketches_free(S); S = nullptr;
         ctx->fused_redos++;
         st = ks_sketch_device_impl(ctx, d_residues, d_seq_offsets, n_seqs, n_residues, max_seq_len, &index->params, index->pbits, fmt10, 0, &S);
-        if (st == KS_OK) st = ks_search_impl(ctx, index, S, &H);
+        if (st == KS_OK) st = ks_search_impl(ctx, index, S, &H, nullptr, opts);
     }
     if (st != KS_OK) { ks_hits_free(H); ks_sketches_free(S); return st; }
     if (deferred) ctx->fused_deferred++;
@@ -359,20 +367,31 @@ static int sketch_search_impl(ks_ctx *ctx, const ks_index *index, const uint8_t 
     return KS_OK;
 }
 
+extern "C" int ks_sketch_search_device_ex(ks_ctx *ctx, const ks_index *index, const uint8_t *d_residues,
+                                          const uint64_t *d_seq_offsets, uint32_t n_seqs, uint64_t n_residues,
+                                          uint32_t max_seq_len, const ks_search_opts *opts, ks_sketches **sketches_out,
+                                          ks_hits **hits_out) {
+    return ks_guard(ctx, [&]() -> int {
+    KS_TRY(ks_search_opts_check(ctx, opts));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!index || !hits_out || (!d_seq_offsets) || (!d_residues && n_residues)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    return sketch_search_impl(ctx, index, d_residues, d_seq_offsets, n_seqs, n_residues, max_seq_len, opts, sketches_out, hits_out);
+    });
+}
 extern "C" int ks_sketch_search_device(ks_ctx *ctx, const ks_index *index, const uint8_t *d_residues,
                                        const uint64_t *d_seq_offsets, uint32_t n_seqs, uint64_t n_residues,
                                        uint32_t max_seq_len, ks_sketches **sketches_out, ks_hits **hits_out) {
     return ks_guard(ctx, [&]() -> int {
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (!index || !hits_out || (!d_seq_offsets) || (!d_residues && n_residues)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    return sketch_search_impl(ctx, index, d_residues, d_seq_offsets, n_seqs, n_residues, max_seq_len, sketches_out, hits_out);
+    return ks_sketch_search_device_ex(ctx, index, d_residues, d_seq_offsets, n_seqs, n_residues, max_seq_len, nullptr, sketches_out,
+                                      hits_out);
     });
 }
 
 // ... and from host arrays (the batch is uploaded, its longest record is known from the offsets: the read-back is always folded)
-extern "C" int ks_sketch_search(ks_ctx *ctx, const ks_index *index, const uint8_t *residues, const uint64_t *seq_offsets,
-                                uint32_t n_seqs, ks_sketches **sketches_out, ks_hits **hits_out) {
+extern "C" int ks_sketch_search_ex(ks_ctx *ctx, const ks_index *index, const uint8_t *residues, const uint64_t *seq_offsets,
+                                   uint32_t n_seqs, const ks_search_opts *opts, ks_sketches **sketches_out, ks_hits **hits_out) {
     return ks_guard(ctx, [&]() -> int {
+    KS_TRY(ks_search_opts_check(ctx, opts));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!index || !hits_out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     u8 *d_res = nullptr;
@@ -380,11 +399,17 @@ extern "C" int ks_sketch_search(ks_ctx *ctx, const ks_index *index, const uint8_
     u64 n_res = 0;
     u32 max_len = 0;
     int st = upload_batch(ctx, residues, seq_offsets, n_seqs, &d_res, &d_offs, &n_res, &max_len);
-    if (st == KS_OK) st = sketch_search_impl(ctx, index, d_res, d_offs, n_seqs, n_res, max_len, sketches_out, hits_out);
+    if (st == KS_OK) st = sketch_search_impl(ctx, index, d_res, d_offs, n_seqs, n_res, max_len, opts, sketches_out, hits_out);
     (void)hipStreamSynchronize(ctx->stream);
     ks_pool_free(ctx, d_res);
     ks_pool_free(ctx, d_offs);
     return st;
+    });
+}
+extern "C" int ks_sketch_search(ks_ctx *ctx, const ks_index *index, const uint8_t *residues, const uint64_t *seq_offsets,
+                                uint32_t n_seqs, ks_sketches **sketches_out, ks_hits **hits_out) {
+    return ks_guard(ctx, [&]() -> int {
+    return ks_sketch_search_ex(ctx, index, residues, seq_offsets, n_seqs, nullptr, sketches_out, hits_out);
     });
 }
 extern "C" uint64_t ks_hits_count(const ks_hits *h) { return h ? h->n_hits : 0; }
@@ -609,11 +634,30 @@ extern "C" int ks_hits_merge_by_qid_device(ks_ctx *ctx, const uint32_t *d_qid, c
     });
 }
 
+extern "C" int ks_hits_has_abund_stats(const ks_hits *h) { return h && h->has_stats ? 1 : 0; }
+extern "C" const uint64_t *ks_hits_device_median2(const ks_hits *h) { return h && h->has_stats ? h->d_median2 : nullptr; }
+extern "C" const double *ks_hits_device_abund_ss(const ks_hits *h) { return h && h->has_stats ? h->d_ss : nullptr; }
+extern "C" int ks_hits_copy_abund_stats_to_host(ks_ctx *ctx, const ks_hits *h, uint64_t *median2, double *ss) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!h) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    if (!h->has_stats) return ks_fail(ctx, KS_ERR_INVALID_ARG, "these hits were searched without KS_SEARCH_ABUND_STATS");
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)h->n_hits;
+    if (n && median2) KS_TRY(ks_copy_d2h(ctx, median2, h->d_median2, n * sizeof(u64)));
+    if (n && ss) KS_TRY(ks_copy_d2h(ctx, ss, h->d_ss, n * sizeof(double)));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KS_OK;
+    });
+}
+
 extern "C" void ks_hits_free(ks_hits *h) {
     if (!h) return;
     ks_pool_free(h->ctx, h->d_qid);
     ks_pool_free(h->ctx, h->d_tid);
     if (h->d_block) ks_pool_free(h->ctx, h->d_block); // (d_isect and d_nw lie inside it)
     else { ks_pool_free(h->ctx, h->d_isect); ks_pool_free(h->ctx, h->d_nw); }
+    ks_pool_free(h->ctx, h->d_median2);
+    ks_pool_free(h->ctx, h->d_ss);
     delete h;
 }

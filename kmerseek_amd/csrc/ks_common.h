@@ -322,6 +322,10 @@ struct ks_hits {
     u64 *d_nw;
     // != NULL: d_nw and d_isect point INTO this block (with the row pass's status words: one allocation, one memset)
     u64 *d_block;
+    // KS_SEARCH_ABUND_STATS: per row 2 x median and sum of squared deviations of the shared target abundances
+    bool has_stats;
+    u64 *d_median2;
+    double *d_ss;
 };
 
 struct ks_kmerpos {
@@ -407,7 +411,10 @@ int ks_kmerpos_tiles_launch(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32
 int ks_kmerpos_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res,
                            const ks_params *p, ks_kmerpos **out);
 int ks_index_build_impl(ks_ctx *ctx, const ks_sketches *t, ks_index **out);
-int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo = nullptr);
+// opts: NULL or validated (ks_search_opts_check); NULL and all-zero options run the same launches
+int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo = nullptr,
+                   const ks_search_opts *opts = nullptr);
+int ks_search_opts_check(ks_ctx *ctx, const ks_search_opts *opts);
 int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out);
 
 int ks_check_params(ks_ctx *ctx, const ks_params *p);

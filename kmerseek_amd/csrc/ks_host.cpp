@@ -463,9 +463,11 @@ void ProteomeIndex::ensure_device_index() {
     if (st != KS_OK) { dev_index_ = nullptr; drop_device_index(); throw gpu_error(ctx_, st, "ks_index_build"); }
 }
 
-std::vector<SearchResult> ProteomeIndex::search(const std::vector<std::pair<std::string, std::string>> &queries, bool upper) {
+std::vector<SearchResult> ProteomeIndex::search(const std::vector<std::pair<std::string, std::string>> &queries, bool upper,
+                                                double min_containment) {
     std::vector<SearchResult> rows;
     const size_t nq = queries.size();
+    if (!(min_containment >= 0.0)) throw IndexError(IndexError::ValidationError, "Validation error: min_containment must be >= 0");
     if (nq == 0 || signatures_.empty()) return rows;
     if (nq > 0xfffffff0ULL) throw IndexError(IndexError::ValidationError, "Validation error: too many query records in one batch");
     std::vector<std::string> processed;
@@ -473,46 +475,41 @@ std::vector<SearchResult> ProteomeIndex::search(const std::vector<std::pair<std:
     std::vector<uint8_t> res;
     prepare_records(queries, upper, processed, offs, res);
     ensure_device_index();
-    // ---- one call: sketch the query batch and join it against the resident index
+    // ---- one call: sketch the query batch, join it against the resident index, the rows' abundance statistics (and the
+    // containment filter) on the device
     ks_sketches *S = nullptr;
     ks_hits *H = nullptr;
-    int st = ks_sketch_search(ctx_, dev_index_, res.data(), offs.data(), (uint32_t)nq, &S, &H);
-    if (st != KS_OK) throw gpu_error(ctx_, st, "ks_sketch_search");
+    const ks_search_opts opts{KS_SEARCH_ABUND_STATS, 0, min_containment};
+    int st = ks_sketch_search_ex(ctx_, dev_index_, res.data(), offs.data(), (uint32_t)nq, &opts, &S, &H);
+    if (st != KS_OK) throw gpu_error(ctx_, st, "ks_sketch_search_ex");
     const uint64_t nh = ks_hits_count(H);
     std::vector<uint32_t> qid(nh + 1), tid(nh + 1), isect(nh + 1);
-    std::vector<uint64_t> nw(nh + 1);
+    std::vector<uint64_t> nw(nh + 1), median2(nh + 1);
+    std::vector<double> ss(nh + 1);
     std::vector<uint64_t> qo(nq + 1), qm(ks_sketches_n_hashes(S) + 1);
     st = ks_hits_copy_to_host(ctx_, H, qid.data(), tid.data(), isect.data(), nw.data());
+    if (st == KS_OK) st = ks_hits_copy_abund_stats_to_host(ctx_, H, median2.data(), ss.data());
     if (st == KS_OK) st = ks_sketches_copy_to_host(ctx_, S, qo.data(), qm.data(), nullptr);
     ks_hits_free(H);
     ks_sketches_free(S);
     if (st != KS_OK) throw gpu_error(ctx_, st, "copy of the search result");
-    // ---- rows: f64 ratios of the integer results (formulas: SURVEY.md 8(a) row a10)
+    // ---- rows: f64 ratios of the integer results (formulas: SURVEY.md 8(a) row a10).  The abundance columns are those of the
+    // sorted shared target abundances a[0..n): mean = (sum a) / n, median, sqrt(sum (a - mean)^2 / n).  The device replays the
+    // f64 sums in ascending order (ks_search_opts); sum a, added in f64, is n_weighted itself while every partial sum is an
+    // integer below 2^53.
     rows.reserve(nh);
     const double k3 = (double)(ksize_ * PROTEIN_TO_MINHASH_RATIO);
     std::vector<std::string> q_md5(nq);
-    std::vector<double> shared;
     for (uint64_t r = 0; r < nh; r++) {
         const uint32_t q = qid[r], t = tid[r];
         const ProteinSignature &g = *dev_order_[t];
         const uint64_t *qmins = qm.data() + qo[q];
         const size_t n_q = (size_t)(qo[q + 1] - qo[q]), n_t = g.mins.size();
-        // the match's abundances of the shared hashes: a sorted merge of the two sketches
-        shared.clear();
-        for (size_t i = 0, j = 0; i < n_q && j < n_t;) {
-            if (qmins[i] < g.mins[j]) i++;
-            else if (g.mins[j] < qmins[i]) j++;
-            else { shared.push_back((double)g.abunds[j]); i++; j++; }
-        }
-        if (shared.size() != isect[r])
+        const size_t n = isect[r];
+        if (n == 0 || n > n_q || n > n_t)
             throw IndexError(IndexError::Gpu, "search: a row's intersect does not match the sketches it was computed from");
-        std::sort(shared.begin(), shared.end());
-        const size_t n = shared.size();
-        double sum = 0;
-        for (double x : shared) sum += x;
-        const double mean = sum / (double)n;
-        double ss = 0;
-        for (double x : shared) ss += (x - mean) * (x - mean);
+        if (nw[r] >= (1ULL << 53))
+            throw IndexError(IndexError::Gpu, "search: a row's abundance sum is beyond the exact range of f64");
         SearchResult o;
         o.query_name = queries[q].second;
         if (q_md5[q].empty()) q_md5[q] = sourmash_md5(qmins, n_q, ksize_);
@@ -529,9 +526,9 @@ std::vector<SearchResult> ProteomeIndex::search(const std::vector<std::pair<std:
         o.containment = cq;
         o.jaccard = I / (double)(n_q + n_t - isect[r]);
         o.max_containment = std::max(cq, ct);
-        o.average_abund = mean;
-        o.median_abund = (n % 2) ? shared[n / 2] : (shared[n / 2 - 1] + shared[n / 2]) / 2.0;
-        o.std_abund = std::sqrt(ss / (double)n);
+        o.average_abund = (double)nw[r] / (double)n;
+        o.median_abund = (double)median2[r] / 2.0;
+        o.std_abund = std::sqrt(ss[r] / (double)n);
         o.query_containment_ani = std::pow(cq, 1.0 / k3);
         o.match_containment_ani = std::pow(ct, 1.0 / k3);
         o.average_containment_ani = (o.query_containment_ani + o.match_containment_ani) / 2.0;
@@ -545,11 +542,13 @@ std::vector<SearchResult> ProteomeIndex::search(const std::vector<std::pair<std:
     return rows;
 }
 
-std::vector<SearchResult> ProteomeIndex::search_fasta(const std::string &fasta_path, size_t batch_size) {
+std::vector<SearchResult> ProteomeIndex::search_fasta(const std::string &fasta_path, size_t batch_size, double min_containment) {
     std::vector<SearchResult> rows;
+    if (!(min_containment >= 0.0)) throw IndexError(IndexError::ValidationError, "Validation error: min_containment must be >= 0");
     for_each_fasta_batch(fasta_path, batch_size ? batch_size : 100000, 0,
                          [&](std::vector<std::pair<std::string, std::string>> &batch) {
-                             std::vector<SearchResult> part = search(batch, true); // the FASTA path upper-cases (index.rs:1000)
+                             // (the FASTA path upper-cases, index.rs:1000)
+                             std::vector<SearchResult> part = search(batch, true, min_containment);
                              for (auto &r : part) rows.push_back(std::move(r));
                          },
                          nullptr);
@@ -893,6 +892,17 @@ int ksh_index_search(ksh_index *ix, const char *const *sequences, const char *co
     })
 }
 
+int ksh_index_search_ex(ksh_index *ix, const char *const *sequences, const char *const *names, uint32_t n, int upper,
+                        double min_containment, char **json_out, char *err, size_t err_cap) {
+    KSH_GUARD({
+        if (!ix || !json_out || (n && (!sequences || !names))) throw IndexError(IndexError::ValidationError, "Validation error: NULL argument");
+        std::vector<std::pair<std::string, std::string>> recs(n);
+        for (uint32_t i = 0; i < n; i++) recs[i] = {sequences[i], names[i]};
+        *json_out = dup_string(json_rows(ix->ix->search(recs, upper != 0, min_containment)));
+        if (!*json_out) throw std::bad_alloc();
+    })
+}
+
 // sourmash md5sum of a sketch (what the search rows' query_md5 / match_md5 columns hold); needs no GPU
 int ksh_sourmash_md5(const uint64_t *mins, uint64_t n, uint32_t protein_ksize, char *out33) {
     if ((!mins && n) || !out33) return 1;
@@ -907,6 +917,15 @@ int ksh_index_search_fasta(ksh_index *ix, const char *fasta_path, uint64_t batch
     KSH_GUARD({
         if (!ix || !json_out || !fasta_path) throw IndexError(IndexError::ValidationError, "Validation error: NULL argument");
         *json_out = dup_string(json_rows(ix->ix->search_fasta(fasta_path, (size_t)batch_size)));
+        if (!*json_out) throw std::bad_alloc();
+    })
+}
+
+int ksh_index_search_fasta_ex(ksh_index *ix, const char *fasta_path, uint64_t batch_size, double min_containment, char **json_out,
+                              char *err, size_t err_cap) {
+    KSH_GUARD({
+        if (!ix || !json_out || !fasta_path) throw IndexError(IndexError::ValidationError, "Validation error: NULL argument");
+        *json_out = dup_string(json_rows(ix->ix->search_fasta(fasta_path, (size_t)batch_size, min_containment)));
         if (!*json_out) throw std::bad_alloc();
     })
 }

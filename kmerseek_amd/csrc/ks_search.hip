@@ -1237,6 +1237,117 @@ __global__ __launch_bounds__(PF_THREADS) void k_pair_rows_fused(const u64 *keys,
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// KS_SEARCH_ABUND_STATS: per-row statistics of the shared target abundances.  The match sort then also orders the abundance
+// bits, so the records of row r — [row_start[r], row_start[r] + isect[r]) of the sorted list — ascend in abundance, and the
+// statistics replay a host loop over the sorted abundances operation for operation: sum += a, mean = sum / n, then
+// ss += (a - mean) * (a - mean), in ascending order, rounded after every operation (no contraction into fma).  Most rows hold
+// one or two records: a lane per row.  A row longer than RA_LONG is listed for k_row_abund_stats_long instead, where a wave
+// loads it 64 records at a time and adds them in order from registers — a self-hit at scaled = 1 is as long as the sequence,
+// and one lane walking it through memory would hold its workgroup's other 255 lanes for the whole walk.
+// ---------------------------------------------------------------------------------------------
+#define RA_LONG 64
+
+__global__ __launch_bounds__(256) void k_row_abund_stats(const u64 *pk, const u64 *row_start, const u32 *isect, const u32 *n_rows_dev,
+                                                         u32 rows_cap, int abits, u64 *median2, double *ss, u32 *long_rows) {
+#pragma clang fp contract(off)
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 n_rows = *n_rows_dev < rows_cap ? *n_rows_dev : rows_cap; // (more rows than the arrays: the host repeats the pass)
+    if (r >= n_rows) return;
+    const u32 n = isect[r];
+    const u64 *a = pk + row_start[r];
+    const u64 am = (1ULL << abits) - 1ULL;
+    if (n > RA_LONG) { long_rows[1 + atomicAdd(&long_rows[0], 1u)] = r; return; }
+    if (n == 0) { median2[r] = 0; ss[r] = 0.0; return; } // (no row: only after a look-back that gave up, which is repeated)
+    double sum = 0.0;
+    for (u32 j = 0; j < n; j++) sum += (double)(a[j] & am);
+    const double mean = sum / (double)n;
+    double acc = 0.0;
+    for (u32 j = 0; j < n; j++) {
+        const double d = (double)(a[j] & am) - mean;
+        acc += d * d;
+    }
+    ss[r] = acc;
+    median2[r] = (n & 1u) ? 2ULL * (a[n / 2] & am) : (a[n / 2 - 1] & am) + (a[n / 2] & am);
+}
+
+// the rows k_row_abund_stats listed: one wave per row (a fixed grid striding over the list); each chunk of 64 records is loaded
+// coalesced, one per lane, and added in order through readlane (every lane keeps the same sums)
+KS_DEV double ra_readlane_f64(double v, int j) {
+    const u64 b = (u64)__double_as_longlong(v);
+    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)b, j), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(b >> 32), j);
+    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
+}
+
+__global__ __launch_bounds__(256) void k_row_abund_stats_long(const u64 *pk, const u64 *row_start, const u32 *isect, const u32 *long_rows,
+                                                              int abits, u64 *median2, double *ss) {
+#pragma clang fp contract(off)
+    const u32 lane = threadIdx.x & 63, n_waves = gridDim.x * (blockDim.x / 64);
+    const u32 n_long = long_rows[0];
+    const u64 am = (1ULL << abits) - 1ULL;
+    for (u32 w = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); w < n_long; w += n_waves) { // (uniform per wave)
+        const u32 r = long_rows[1 + w];
+        const u32 n = isect[r];
+        const u64 *a = pk + row_start[r];
+        double sum = 0.0;
+        for (u32 c = 0; c < n; c += 64) {
+            const double x = c + lane < n ? (double)(a[c + lane] & am) : 0.0;
+            const u32 m = n - c < 64u ? n - c : 64u;
+            for (u32 j = 0; j < m; j++) sum += ra_readlane_f64(x, (int)j);
+        }
+        const double mean = sum / (double)n;
+        double acc = 0.0;
+        for (u32 c = 0; c < n; c += 64) {
+            const double d = c + lane < n ? (double)(a[c + lane] & am) - mean : 0.0;
+            const double t = d * d;
+            const u32 m = n - c < 64u ? n - c : 64u;
+            for (u32 j = 0; j < m; j++) acc += ra_readlane_f64(t, (int)j);
+        }
+        if (lane == 0) {
+            ss[r] = acc;
+            median2[r] = (n & 1u) ? 2ULL * (a[n / 2] & am) : (a[n / 2 - 1] & am) + (a[n / 2] & am);
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// min_containment: a stable compaction of the row columns.  k_rows_keep writes the keep flag of every row (the host's f64
+// test: (double)intersect / (double)|q| >= min_containment, |q| = the query's distinct hashes), an exclusive scan turns the
+// flags into destinations (its total, the kept count, lands beside the row count: one read-back), k_rows_filter moves the kept
+// rows, recomputing the same flag.
+// ---------------------------------------------------------------------------------------------
+struct rf_cols {
+    const u32 *qid, *tid, *isect;
+    const u64 *nw, *median2;
+    const double *ss;
+};
+
+KS_DEV bool rf_kept(const rf_cols &in, u32 r, const u64 *q_offsets, const u32 *q_counts, u32 n_queries, double min_c) {
+    const u32 q = in.qid[r];
+    if (q >= n_queries) return false; // (a row without a head: only after a look-back that gave up, which is repeated)
+    const u64 nq = q_counts ? (u64)q_counts[q] : q_offsets[q + 1] - q_offsets[q];
+    return (double)in.isect[r] / (double)nq >= min_c;
+}
+
+__global__ __launch_bounds__(256) void k_rows_keep(rf_cols in, const u32 *n_rows_dev, u32 rows_cap, const u64 *q_offsets, const u32 *q_counts,
+                                                   u32 n_queries, double min_c, u32 *flags) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows_cap) return;
+    const u32 n_rows = *n_rows_dev < rows_cap ? *n_rows_dev : rows_cap;
+    flags[r] = (r < n_rows && rf_kept(in, r, q_offsets, q_counts, n_queries, min_c)) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_rows_filter(rf_cols in, const u32 *n_rows_dev, u32 rows_cap, const u64 *q_offsets, const u32 *q_counts,
+                                                     u32 n_queries, double min_c, const u32 *dst, u32 *qid, u32 *tid, u32 *isect, u64 *nw,
+                                                     u64 *median2, double *ss) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    const u32 n_rows = *n_rows_dev < rows_cap ? *n_rows_dev : rows_cap;
+    if (r >= n_rows || !rf_kept(in, r, q_offsets, q_counts, n_queries, min_c)) return;
+    const u32 o = dst[r];
+    qid[o] = in.qid[r]; tid[o] = in.tid[r]; isect[o] = in.isect[r]; nw[o] = in.nw[r];
+    if (median2) { median2[o] = in.median2[r]; ss[o] = in.ss[r]; }
+}
+
 // ---- one search, in steps: partition of the query postings -> join (+ its segment-cap retry) -> match sort -> row pass
 
 // what the steps of one search share
@@ -1257,6 +1368,8 @@ struct se_search {
     u64 n_pairs, seg_cap, seg_count[JN_SEGS];
     u32 n_segs;
     bool stop; // nothing is produced: the batch needs slicing (se_split) or the pending sketch a repeat (*sketch_redo)
+    bool stats;   // KS_SEARCH_ABUND_STATS: the match sort orders the abundance bits too, the row pass is followed by the statistics
+    double min_c; // > 0: the rows are filtered on their containment
 };
 static_assert(2 * JN_SEGS <= KS_PIN_JOIN_WORDS, "pinned slot of the join's segment counts");
 
@@ -1442,11 +1555,12 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
     return KS_OK;
 }
 
-// sort matches by (qid, tid) on the live id bits only; *pk: the sorted list
+// sort matches by (qid, tid) on the live id bits only (with Q.stats: by (qid, tid, abundance), all live bits); *pk: the sorted list
 static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk) {
     const u64 n_pairs = Q.n_pairs;
     const u32 n_segs = Q.n_segs;
     const int tbits = Q.tbits, qbits = Q.qbits, abits = Q.abits;
+    const int lo_bit = Q.stats ? 0 : abits, nbits = tbits + qbits + (Q.stats ? abits : 0);
     KS_TRY(sc.alloc(&Q.pk1, (size_t)n_pairs));
     // The records go into the match sort as they lie: its first partition level reads the segments in place.  Only a list
     // that sort declines (short lists, narrow keys: the LSD passes) is made dense by a copy first.
@@ -1462,7 +1576,7 @@ static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk) {
         }
         sg.tile_start[n_segs] = t;
         for (u32 s_ = n_segs + 1; s_ <= KS_MSD_MAX_SEGS; s_++) sg.tile_start[s_] = t;
-        KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, abits, tbits + qbits, &msd, &sg));
+        KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, lo_bit, nbits, &msd, &sg));
     }
     if (n_segs > 1 && !msd) { // the segments -> one dense list (then the roles of the two buffers swap: the segmented one is the scratch)
         jn_seg_table tab;
@@ -1477,18 +1591,70 @@ static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk) {
     }
     // the match list pk0 is scratch from here on: ping-pong with pk1.  Three moves (two exact MSD partition levels + in-LDS
     // bucket sort, ks_msd.hip) instead of one per 8 key bits
-    if (!msd) KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, abits, tbits + qbits, &msd));
+    if (!msd) KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, lo_bit, nbits, &msd));
     if (msd) {
         *pk = Q.pk0;
         return KS_OK;
     }
     int shifts[8], ns = 0;
-    for (int sh = 0; sh < tbits + qbits; sh += 8) shifts[ns++] = abits + sh;
+    for (int sh = 0; sh < nbits; sh += 8) shifts[ns++] = lo_bit + sh;
     return ks_radix_sort_keys(ctx, KS_SORT_PAIRS, Q.pk0, Q.pk0, Q.pk1, n_pairs, shifts, ns, pk);
 }
 
-// run-length reduce of the sorted matches into H's rows: one fused pass (k_pair_rows_fused)
-static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk) {
+// the row columns of H (and the statistics) back to the pool
+static void se_free_cols(ks_ctx *ctx, ks_hits *H) {
+    ks_pool_free(ctx, H->d_qid); ks_pool_free(ctx, H->d_tid);
+    if (H->d_block) ks_pool_free(ctx, H->d_block); // (d_isect and d_nw lie inside it)
+    else { ks_pool_free(ctx, H->d_isect); ks_pool_free(ctx, H->d_nw); }
+    ks_pool_free(ctx, H->d_median2); ks_pool_free(ctx, H->d_ss);
+    H->d_qid = H->d_tid = H->d_isect = nullptr;
+    H->d_nw = H->d_block = H->d_median2 = nullptr;
+    H->d_ss = nullptr;
+}
+
+#define RA_LONG_GRID 256 // workgroups of k_row_abund_stats_long (4 waves each, striding over the long rows)
+
+// Behind the row pass of one attempt and before its wait: the statistics into H's columns (Q.stats) and the rows that pass
+// the containment test into F (Q.min_c > 0).  The kernels take the row count from the device (ticket[2]; an attempt with more
+// rows than rows_cap is repeated anyway) and the scan of the keep flags writes the kept count to ticket[3], which the row
+// pass's read-back brings home with the row count: no wait of its own.
+static int se_rows_post(ks_ctx *ctx, const se_search &Q, ks_hits *H, ks_hits *F, const u64 *pk, u32 rows_cap, u32 *ticket, ks_scratch &sc) {
+    const u32 *n_rows_dev = ticket + 2;
+    const u32 g = (rows_cap + 255) / 256;
+    if (Q.stats) {
+        u64 *row_start = nullptr;
+        u32 *long_rows = nullptr; // [0] count, then row ids
+        KS_TRY(sc.alloc(&row_start, (size_t)rows_cap + 1));
+        KS_TRY(sc.alloc(&long_rows, (size_t)rows_cap + 1));
+        KS_TRY(ks_alloc(ctx, &H->d_median2, rows_cap));
+        KS_TRY(ks_alloc(ctx, &H->d_ss, rows_cap));
+        KS_HIP(ctx, hipMemsetAsync(long_rows, 0, sizeof(u32), ctx->stream));
+        KS_TRY(ks_scan_u32_to_u64(ctx, H->d_isect, row_start, rows_cap)); // (rows past the count have intersect 0)
+        KS_LAUNCH(ctx, "row_abund_stats", k_row_abund_stats, g, 256, pk, (const u64 *)row_start, (const u32 *)H->d_isect, n_rows_dev,
+                  rows_cap, Q.abits, H->d_median2, H->d_ss, long_rows);
+        KS_LAUNCH(ctx, "row_abund_stats_long", k_row_abund_stats_long, RA_LONG_GRID, 256, pk, (const u64 *)row_start,
+                  (const u32 *)H->d_isect, (const u32 *)long_rows, Q.abits, H->d_median2, H->d_ss);
+    }
+    if (Q.min_c > 0) {
+        const ks_sketches *q = Q.q;
+        const u32 *counts = q->gapped ? q->d_counts : nullptr; // (a gapped batch: distinct hashes per query; else the CSR's runs)
+        const rf_cols in{H->d_qid, H->d_tid, H->d_isect, H->d_nw, H->d_median2, H->d_ss};
+        u32 *flags = nullptr;
+        KS_TRY(sc.alloc(&flags, rows_cap));
+        KS_LAUNCH(ctx, "rows_keep", k_rows_keep, g, 256, in, n_rows_dev, rows_cap, (const u64 *)q->d_offsets, counts, q->n_seqs, Q.min_c,
+                  flags);
+        KS_TRY(ks_scan_u32_inplace(ctx, flags, rows_cap, ticket + 3));
+        KS_TRY(ks_alloc(ctx, &F->d_qid, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_tid, rows_cap));
+        KS_TRY(ks_alloc(ctx, &F->d_isect, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_nw, rows_cap));
+        if (Q.stats) { KS_TRY(ks_alloc(ctx, &F->d_median2, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_ss, rows_cap)); }
+        KS_LAUNCH(ctx, "rows_filter", k_rows_filter, g, 256, in, n_rows_dev, rows_cap, (const u64 *)q->d_offsets, counts, q->n_seqs, Q.min_c,
+                  (const u32 *)flags, F->d_qid, F->d_tid, F->d_isect, F->d_nw, F->d_median2, F->d_ss);
+    }
+    return KS_OK;
+}
+
+// run-length reduce of the sorted matches into H's rows: one fused pass (k_pair_rows_fused); F: see se_rows_post
+static int se_rows_run(ks_ctx *ctx, const se_search &Q, ks_hits *H, ks_hits &F, const u64 *pk) {
     const u64 n_pairs = Q.n_pairs;
     const int tbits = Q.tbits, abits = Q.abits;
     const u32 pf_tiles = (u32)((n_pairs + PF_TILE - 1) / PF_TILE);
@@ -1498,11 +1664,13 @@ static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk) {
     u64 rows_cap = n_pairs;
     if (ctx->rows_hint && ctx->rows_hint < rows_cap && !ks_dbg(ctx, KS_DBG_NO_ROWS_HINT)) rows_cap = ctx->rows_hint;
     u32 n_rows = 0;
-    const u32 *pin = (const u32 *)(ctx->h_pin + KS_PIN_ROWS); // ticket pair | row count
+    const u32 *pin = (const u32 *)(ctx->h_pin + KS_PIN_ROWS); // ticket pair | row count | kept rows (min_containment)
+    const bool post = Q.stats || Q.min_c > 0;
     for (int attempt = 0; attempt < 3; attempt++) { // (repeats: more rows than the guess; a look-back that gave up)
+        ks_scratch sc(ctx); // (the statistics' and the filter's scratch of this attempt)
         KS_TRY(ks_alloc(ctx, &H->d_qid, (size_t)rows_cap)); KS_TRY(ks_alloc(ctx, &H->d_tid, (size_t)rows_cap));
-        // n_weighted (u64) | status words + ticket pair + row count (u64) | intersect (u32): one block, zeroed together, per
-        // attempt (one memset, one read-back)
+        // n_weighted (u64) | status words + ticket pair + row count + kept count (u64) | intersect (u32): one block, zeroed
+        // together, per attempt (one memset, one read-back)
         const size_t st_words = (size_t)pf_tiles + 2, is_words = ((size_t)rows_cap + 1) / 2;
         KS_TRY(ks_alloc(ctx, &H->d_block, (size_t)rows_cap + st_words + is_words));
         H->d_nw = H->d_block;
@@ -1513,9 +1681,10 @@ static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk) {
         KS_LAUNCH(ctx, "pair_rows", k_pair_rows_fused, pf_tiles, PF_THREADS, pk, n_pairs, H->d_qid, H->d_tid, H->d_isect,
                   (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, pf_ticket + 2,
                   (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
+        if (post) KS_TRY(se_rows_post(ctx, Q, H, &F, pk, (u32)rows_cap, pf_ticket, sc));
         {
             ks_fetch_seg f[2];
-            f[0] = ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4); // ticket pair + row count
+            f[0] = ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4); // ticket pair + row count + kept count
             const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
             KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
         }
@@ -1531,19 +1700,35 @@ static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk) {
             if (n_rows <= rows_cap) break;
             rows_cap = n_rows;
         }
-        ks_pool_free(ctx, H->d_qid); ks_pool_free(ctx, H->d_tid); ks_pool_free(ctx, H->d_block);
-        H->d_qid = H->d_tid = H->d_isect = nullptr; H->d_nw = nullptr; H->d_block = nullptr;
+        se_free_cols(ctx, H);
+        se_free_cols(ctx, &F);
     }
     if (!H->d_qid) return ks_fail(ctx, KS_ERR_HIP, "search: the row pass did not settle");
     H->n_hits = n_rows;
     const u64 want = (u64)n_rows + n_rows / 4 + 4096;
     ctx->rows_hint = want > ctx->rows_hint / 2 ? want : ctx->rows_hint / 2; // follows growth at once, decays slowly
+    if (Q.min_c > 0) { // the kept rows replace the row pass's columns
+        se_free_cols(ctx, H);
+        H->d_qid = F.d_qid; H->d_tid = F.d_tid; H->d_isect = F.d_isect; H->d_nw = F.d_nw;
+        H->d_median2 = F.d_median2; H->d_ss = F.d_ss;
+        H->n_hits = pin[3];
+        memset(&F, 0, sizeof F);
+    }
     return KS_OK;
+}
+
+static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk) {
+    ks_hits F; // the filtered columns (Q.min_c > 0) until they replace H's
+    memset(&F, 0, sizeof F);
+    const int st = se_rows_run(ctx, Q, H, F, pk);
+    se_free_cols(ctx, &F); // (nothing left after a success)
+    return st;
 }
 
 static int se_no_hits(ks_ctx *ctx, ks_hits *H) {
     KS_TRY(ks_alloc(ctx, &H->d_qid, 1)); KS_TRY(ks_alloc(ctx, &H->d_tid, 1));
     KS_TRY(ks_alloc(ctx, &H->d_isect, 1)); KS_TRY(ks_alloc(ctx, &H->d_nw, 1));
+    if (H->has_stats) { KS_TRY(ks_alloc(ctx, &H->d_median2, 1)); KS_TRY(ks_alloc(ctx, &H->d_ss, 1)); }
     return KS_OK;
 }
 
@@ -1554,10 +1739,14 @@ struct se_split {
     u32 seqs;
 };
 
-static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits *H, se_split *split, int *sketch_redo, bool *stop) {
+static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, const ks_search_opts *opts, ks_hits *H, se_split *split,
+                      int *sketch_redo, bool *stop) {
     se_search Q;
     memset(&Q, 0, sizeof Q);
     Q.ix = ix; Q.q = q; Q.n_q = q->n_hashes;
+    Q.stats = opts && (opts->flags & KS_SEARCH_ABUND_STATS);
+    Q.min_c = opts ? opts->min_containment : 0.0;
+    H->has_stats = Q.stats;
     const u64 n_t = ix->n_postings;
     if (q->pending && (n_t == 0 || !(q->part_keys && q->part_pbits == ix->pbits && ix->pbits > 0))) {
         // (no postings for this index: the partition starts from the CSR and needs the exact counts)
@@ -1634,7 +1823,8 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_
 // q->pending (ks_sketch_search_device): the sketch launches are queued and nobody has waited for them; the first wait of
 // the search stands in, and q's counts are upper bounds until then.  *sketch_redo != 0 on return (KS_OK, *out == NULL): the
 // sketch has to be repeated the plain way (ks_sketch_finish_pending) and nothing was produced.
-static int search_core(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, se_split *split, int *sketch_redo = nullptr) {
+static int search_core(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, const ks_search_opts *opts, ks_hits **out, se_split *split,
+                       int *sketch_redo = nullptr) {
     *split = se_split{};
     *out = nullptr;
     if (sketch_redo) *sketch_redo = 0;
@@ -1647,7 +1837,7 @@ static int search_core(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks
     memset(H, 0, sizeof *H);
     H->ctx = ctx;
     bool stop = false;
-    const int st = search_run(ctx, ix, q, H, split, sketch_redo, &stop);
+    const int st = search_run(ctx, ix, q, opts, H, split, sketch_redo, &stop);
     if (st != KS_OK || stop) { (void)hipStreamSynchronize(ctx->stream); ks_hits_free(H); return st; }
     *out = H;
     return KS_OK;
@@ -1664,11 +1854,12 @@ __global__ __launch_bounds__(256) void k_add_u32(u32 *a, u64 n, u32 v) {
 
 // ks_search: one match list when it fits; otherwise the query sequences are searched in contiguous slices whose lists
 // and records fit (a slice is a view of the batch's CSR: hits of different query ranges are disjoint and stay ordered by
-// qid; its qids are numbered from 0, so a slice of few sequences needs few id bits).
-int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo) {
+// qid; its qids are numbered from 0, so a slice of few sequences needs few id bits).  Options apply per slice: a slice's rows are
+// its queries' rows, filtered on the same per-query sizes, with their statistics.
+int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo, const ks_search_opts *opts) {
     if (!out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     se_split need;
-    int st = search_core(ctx, ix, q, out, &need, sketch_redo);
+    int st = search_core(ctx, ix, q, opts, out, &need, sketch_redo);
     if (st != KS_OK || (need.pairs == 0 && need.seqs == 0)) return st;
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(q))); // (a slice is a view of the batch's plain CSR)
     // ---- slices of roughly equal posting counts, each expected to produce KS_PAIR_LIMIT / 4 records, of at most max_seqs sequences
@@ -1696,7 +1887,7 @@ int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hit
                                V.n_seqs + 1, V.d_offsets);
             ks_hits *h = nullptr;
             se_split more;
-            st = search_core(ctx, ix, &V, &h, &more);
+            st = search_core(ctx, ix, &V, opts, &h, &more);
             (void)hipStreamSynchronize(ctx->stream);
             ks_pool_free(ctx, V.d_offsets);
             if (st != KS_OK) { cleanup(); return st; }
@@ -1712,12 +1903,15 @@ int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hit
     memset(H, 0, sizeof *H);
     H->ctx = ctx;
     H->partition_path = 3;
+    H->has_stats = opts && (opts->flags & KS_SEARCH_ABUND_STATS);
     for (auto *h : parts) { H->n_hits += h->n_hits; H->n_pair_instances += h->n_pair_instances; }
     const size_t tot = H->n_hits ? (size_t)H->n_hits : 1;
     st = ks_alloc(ctx, &H->d_qid, tot);
     if (st == KS_OK) st = ks_alloc(ctx, &H->d_tid, tot);
     if (st == KS_OK) st = ks_alloc(ctx, &H->d_isect, tot);
     if (st == KS_OK) st = ks_alloc(ctx, &H->d_nw, tot);
+    if (st == KS_OK && H->has_stats) st = ks_alloc(ctx, &H->d_median2, tot);
+    if (st == KS_OK && H->has_stats) st = ks_alloc(ctx, &H->d_ss, tot);
     u64 at = 0;
     for (size_t i = 0; i < parts.size() && st == KS_OK; i++) {
         const u64 n = parts[i]->n_hits;
@@ -1726,7 +1920,10 @@ int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hit
             if (hipMemcpyAsync(H->d_qid + at, parts[i]->d_qid, n * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
                 hipMemcpyAsync(H->d_tid + at, parts[i]->d_tid, n * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
                 hipMemcpyAsync(H->d_isect + at, parts[i]->d_isect, n * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(H->d_nw + at, parts[i]->d_nw, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+                hipMemcpyAsync(H->d_nw + at, parts[i]->d_nw, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+                (H->has_stats &&
+                 (hipMemcpyAsync(H->d_median2 + at, parts[i]->d_median2, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
+                  hipMemcpyAsync(H->d_ss + at, parts[i]->d_ss, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)))
                 st = ks_fail(ctx, KS_ERR_HIP, "hit concatenation failed");
             at += n;
         }
@@ -1791,6 +1988,15 @@ static int union_run(ks_ctx *ctx, const ks_sketches *in, ks_sketches *U) {
     KS_TRY(ks_scan_status_fetch(ctx));
     KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return ks_scan_status_check(ctx);
+}
+
+int ks_search_opts_check(ks_ctx *ctx, const ks_search_opts *o) {
+    if (!o) return KS_OK;
+    const char *why = o->reserved ? "reserved must be 0"
+                    : (o->flags & ~KS_SEARCH_ABUND_STATS) ? "unknown flags"
+                    : !(o->min_containment >= 0.0) ? "min_containment must be >= 0 (and not NaN)" : nullptr;
+    if (!why) return KS_OK;
+    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "search options: %s", why) : KS_ERR_INVALID_ARG;
 }
 
 int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out) {

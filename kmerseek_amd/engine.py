@@ -77,6 +77,13 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def search_opts(min_containment: float = 0.0, abund_stats: bool = False) -> Optional[_lib.ks_search_opts]:
+    """The ks_search_opts of the keyword arguments, or None for the defaults (the plain entry points are called then)."""
+    if not abund_stats and min_containment == 0.0:
+        return None
+    return _lib.ks_search_opts(_lib.KS_SEARCH_ABUND_STATS if abund_stats else 0, 0, float(min_containment))
+
+
 class _FollowDebugEnv:
     """Library proxy of a diagnostic context: re-reads the KS_DEBUG_* variables before every call (the library itself reads
     them only when a context is created).  The tests use it to force the rarely taken paths on one context."""
@@ -242,21 +249,37 @@ class Context:
         return Sketches(self, out)
 
     def sketch_search_device(self, index: "Index", d_residues: int, d_offsets: int, n_seqs: int, n_residues: int,
-                             max_seq_len: int = 0, want_sketches: bool = True):
+                             max_seq_len: int = 0, want_sketches: bool = True, *, min_containment: float = 0.0,
+                             abund_stats: bool = False):
         """ks_sketch_search_device: sketch a query batch and search it against `index` in one call (two host waits instead
-        of three).  Returns (Sketches or None, Hits); same results as sketch_queries_device + search."""
+        of three).  Returns (Sketches or None, Hits); same results as sketch_queries_device + search.  The keywords are
+        those of `search`."""
         sk, hits = C.c_void_p(), C.c_void_p()
-        self._check(self._L.ks_sketch_search_device(self._h, index._h, C.c_void_p(d_residues), C.c_void_p(d_offsets), n_seqs,
-                                                    n_residues, max_seq_len, C.byref(sk) if want_sketches else None, C.byref(hits)))
+        opts = search_opts(min_containment, abund_stats)
+        if opts is None:
+            st = self._L.ks_sketch_search_device(self._h, index._h, C.c_void_p(d_residues), C.c_void_p(d_offsets), n_seqs,
+                                                 n_residues, max_seq_len, C.byref(sk) if want_sketches else None, C.byref(hits))
+        else:
+            st = self._L.ks_sketch_search_device_ex(self._h, index._h, C.c_void_p(d_residues), C.c_void_p(d_offsets), n_seqs,
+                                                    n_residues, max_seq_len, C.byref(opts), C.byref(sk) if want_sketches else None,
+                                                    C.byref(hits))
+        self._check(st)
         return (Sketches(self, sk) if want_sketches else None), Hits(self, hits)
 
-    def sketch_search(self, index: "Index", residues: np.ndarray, offsets: np.ndarray, want_sketches: bool = True):
+    def sketch_search(self, index: "Index", residues: np.ndarray, offsets: np.ndarray, want_sketches: bool = True, *,
+                      min_containment: float = 0.0, abund_stats: bool = False):
         """ks_sketch_search: the same from host arrays (upload, sketch, search).  Returns (Sketches or None, Hits)."""
         residues = np.ascontiguousarray(residues, dtype=np.uint8)
         offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
         sk, hits = C.c_void_p(), C.c_void_p()
-        self._check(self._L.ks_sketch_search(self._h, index._h, _ptr(residues), _ptr(offsets), len(offsets) - 1,
-                                             C.byref(sk) if want_sketches else None, C.byref(hits)))
+        opts = search_opts(min_containment, abund_stats)
+        if opts is None:
+            st = self._L.ks_sketch_search(self._h, index._h, _ptr(residues), _ptr(offsets), len(offsets) - 1,
+                                          C.byref(sk) if want_sketches else None, C.byref(hits))
+        else:
+            st = self._L.ks_sketch_search_ex(self._h, index._h, _ptr(residues), _ptr(offsets), len(offsets) - 1, C.byref(opts),
+                                             C.byref(sk) if want_sketches else None, C.byref(hits))
+        self._check(st)
         return (Sketches(self, sk) if want_sketches else None), Hits(self, hits)
 
     def fused_stats(self) -> Dict[str, int]:
@@ -317,9 +340,15 @@ class Context:
         self._check(self._L.ks_index_build(self._h, targets._h, C.byref(out)))
         return Index(self, out)
 
-    def search(self, index: "Index", queries: "Sketches") -> "Hits":
+    def search(self, index: "Index", queries: "Sketches", *, min_containment: float = 0.0, abund_stats: bool = False) -> "Hits":
+        """ks_search.  min_containment > 0 keeps the rows with intersect / (distinct query hashes) >= min_containment;
+        abund_stats adds the per-row abundance statistics (Hits.abund_stats_to_host).  The defaults call ks_search itself."""
         out = C.c_void_p()
-        self._check(self._L.ks_search(self._h, index._h, queries._h, C.byref(out)))
+        opts = search_opts(min_containment, abund_stats)
+        if opts is None:
+            self._check(self._L.ks_search(self._h, index._h, queries._h, C.byref(out)))
+        else:
+            self._check(self._L.ks_search_ex(self._h, index._h, queries._h, C.byref(opts), C.byref(out)))
         return Hits(self, out)
 
     # ---- measurement ----
@@ -532,3 +561,15 @@ class Hits(_Owned):
         self._ctx._check(self._ctx._L.ks_hits_copy_to_host(self._ctx._h, self._h, _ptr(qid), _ptr(tid), _ptr(isect),
                                                            _ptr(nw)))
         return qid, tid, isect, nw
+
+    @property
+    def has_abund_stats(self) -> bool:
+        return bool(self._ctx._L.ks_hits_has_abund_stats(self._h))
+
+    def abund_stats_to_host(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(median2 u64, ss f64) per row of a search with abund_stats=True: 2 x the median and the sum of squared deviations
+        from the mean of the shared target abundances (median = median2 / 2, std = sqrt(ss / intersect))."""
+        n = self.count
+        median2 = np.zeros(n, np.uint64); ss = np.zeros(n, np.float64)
+        self._ctx._check(self._ctx._L.ks_hits_copy_abund_stats_to_host(self._ctx._h, self._h, _ptr(median2), _ptr(ss)))
+        return median2, ss

@@ -31,6 +31,10 @@ HOST_SIGNATURES = {
     "ksh_index_search": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint32, C.c_int,
                                    C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
     "ksh_index_search_fasta": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
+    "ksh_index_search_ex": (C.c_int, [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_char_p), C.c_uint32, C.c_int,
+                                      C.c_double, C.POINTER(C.c_void_p), C.c_char_p, C.c_size_t]),
+    "ksh_index_search_fasta_ex": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint64, C.c_double, C.POINTER(C.c_void_p), C.c_char_p,
+                                            C.c_size_t]),
     "ksh_sourmash_md5": (C.c_int, [C.POINTER(C.c_uint64), C.c_uint64, C.c_uint32, C.c_char_p]),
     "ksh_index_signature_count": (C.c_uint64, [C.c_void_p]),
     "ksh_index_combined_minhash_size": (C.c_uint64, [C.c_void_p]),
@@ -227,20 +231,22 @@ class ProteomeIndex:
 
     # -- search (added: SURVEY 8(b); the reference's crate has none — rows of branchwater manysearch,
     #    src/python/kmerseek/search.py:125-141, for the signatures this index holds) -------------------------------------
-    def search(self, records: Sequence[Tuple[str, str]], upper: bool = False) -> List[dict]:
+    def search(self, records: Sequence[Tuple[str, str]], upper: bool = False, min_containment: float = 0.0) -> List[dict]:
         """(sequence, name) query records against the stored signatures: one dict per (query, match) pair that shares a
-        hash, keys = SEARCH_COLUMNS.  Queries are validated / resolved like create_protein_signature's input."""
+        hash, keys = SEARCH_COLUMNS.  Queries are validated / resolved like create_protein_signature's input.
+        min_containment > 0 keeps only the rows whose containment is at least that (manysearch's threshold)."""
         n = len(records)
         seqs = (C.c_char_p * n)(*[r[0].encode() for r in records])
         names = (C.c_char_p * n)(*[r[1].encode() for r in records])
         out = C.c_void_p()
-        _call(self._L.ksh_index_search, self._h, seqs, names, n, 1 if upper else 0, C.byref(out))
+        _call(self._L.ksh_index_search_ex, self._h, seqs, names, n, 1 if upper else 0, float(min_containment), C.byref(out))
         return json.loads(_take_string(self._L, out))
 
-    def search_fasta(self, fasta_path, batch_size: int = 100000) -> List[dict]:
+    def search_fasta(self, fasta_path, batch_size: int = 100000, min_containment: float = 0.0) -> List[dict]:
         """Every record of a FASTA file (plain / gzip / zstd / bzip2 / xz) as queries (upper-cased, as the FASTA path does)."""
         out = C.c_void_p()
-        _call(self._L.ksh_index_search_fasta, self._h, str(fasta_path).encode(), batch_size, C.byref(out))
+        _call(self._L.ksh_index_search_fasta_ex, self._h, str(fasta_path).encode(), batch_size, float(min_containment),
+              C.byref(out))
         return json.loads(_take_string(self._L, out))
 
     # -- getters ------------------------------------------------------------------------------------
@@ -379,16 +385,17 @@ class PyProteomeIndex:
         return self.index.signature_count()
 
     # -- search_*: records -> manysearch rows against the stored signatures --------------------------------------------
-    def search_fasta(self, fasta_path, output=None, batch_size: int = 100000) -> List[dict]:
+    def search_fasta(self, fasta_path, output=None, batch_size: int = 100000, threshold: float = 0.0) -> List[dict]:
         """Every record of a FASTA file searched against the index; with `output` the rows are also written as the
-        reference's 22-column CSV."""
-        rows = self.index.search_fasta(fasta_path, batch_size)
+        reference's 22-column CSV.  threshold: manysearch's containment threshold (rows with containment >= threshold;
+        0 keeps every row that shares a hash)."""
+        rows = self.index.search_fasta(fasta_path, batch_size, min_containment=threshold)
         if output is not None:
             write_search_csv(rows, output)
         return rows
 
-    def search_sequences(self, records: Sequence[Tuple[str, str]], output=None) -> List[dict]:
-        rows = self.index.search(list(records), upper=False)
+    def search_sequences(self, records: Sequence[Tuple[str, str]], output=None, threshold: float = 0.0) -> List[dict]:
+        rows = self.index.search(list(records), upper=False, min_containment=threshold)
         if output is not None:
             write_search_csv(rows, output)
         return rows
