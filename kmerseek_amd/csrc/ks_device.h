@@ -116,8 +116,10 @@ KS_DEV u32 ks_xcd_block() {
 // polls — not by an iteration count: a predecessor that is merely slow (a shared GPU, several ranks rehearsing on one
 // device) must not look like a protocol violation.  ~2 s.
 #define KS_SPIN_TICKS 200000000LL
-KS_DEV bool ks_spin_expired(long long t0, u32 &polls) {
-    return ((++polls) & 1023u) == 0 && wall_clock64() - t0 > KS_SPIN_TICKS;
+struct ks_spin { long long t0; u32 polls; }; // one per look-back: all its rounds share the bound
+KS_DEV ks_spin ks_spin_begin() { return {wall_clock64(), 0u}; }
+KS_DEV bool ks_spin_expired(ks_spin &s) {
+    return ((++s.polls) & 1023u) == 0 && wall_clock64() - s.t0 > KS_SPIN_TICKS;
 }
 
 // ---- wave / block exclusive scans (u32) ----
@@ -156,6 +158,9 @@ KS_DEV u32 ks_lane_below(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (in
 
 // Block-wide exclusive scan; `smem` must hold (blockDim.x/64 + 1) u32.  Returns the exclusive
 // prefix of v; *total receives the block sum.  Contains three __syncthreads().
+// The scan a new kernel should take: any block size, and smem is the caller's again on return.  sk_block_excl_scan1 / 2
+// (ks_sketch.hip) are for SK_THREADS-thread kernels that count barriers and registers: one barrier, but smem stays in use
+// until the caller's next barrier.
 KS_DEV u32 ks_block_excl_scan(u32 v, u32 *smem, u32 *total) {
     const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
     u32 incl = ks_wave_incl_scan(v);
@@ -178,6 +183,53 @@ KS_DEV u64 ks_ballot(bool p) { return __ballot(p); }
 KS_DEV u32 ks_lane_lt_count(u64 mask) {
     // number of set bits of mask in lanes below this one
     return __builtin_amdgcn_mbcnt_hi((u32)(mask >> 32), __builtin_amdgcn_mbcnt_lo((u32)mask, 0));
+}
+
+// ---- decoupled look-back ----
+// Tiles that place their output behind their predecessors' (k_sketch_tiles, k_kmerpos_tiles, k_pair_rows_fused,
+// k_scan_lookback) chain their totals through one 8-byte status word per tile, `flag << 62 | value`: a tile publishes its
+// aggregate (flag 1; tile 0 its inclusive prefix at once), one wave sums its predecessors' words back to the nearest
+// inclusive prefix (flag 2), 64 at a time, and the tile re-publishes aggregate + that sum as its own inclusive prefix.
+// A word that is not published yet (flag 0) is polled under the bound of ks_spin_expired; when the bound expires the lane
+// raises bit 0 of *gave_up, counts the word as prefix 0 and goes on — the launch's output is wrong, nothing hangs, and the
+// host repeats the launch with tile ids from an atomic ticket.  Publishing, re-publishing and what the prefix is used for
+// stay with the kernels; the words are stored and loaded relaxed at agent scope.
+#define KS_LB_AGG (1ULL << 62)
+#define KS_LB_PRE (2ULL << 62)
+#define KS_LB_VAL_MASK ((1ULL << 62) - 1)
+
+// One wave's round: lane l looks at predecessor idx - l (none before tile 0: inclusive prefix 0).  `word(i)` returns
+// predecessor i's status word, 0 while it is not published.  Returns the sum over the lanes at or before the wave's first
+// inclusive prefix (uniform); *is_pre = the lanes that saw one (0: none, the walk goes on at idx - 64).  Holds a ballot and
+// DPP moves: EVERY lane of the wave must enter, so the caller's guard is wave-uniform.
+template <typename Word>
+KS_DEV u64 ks_lookback_round(i64 idx, u32 lane, Word word, ks_spin &spin, u32 *gave_up, u64 *is_pre) {
+    const i64 mine = idx - (i64)lane;
+    u64 v = KS_LB_PRE;
+    if (mine >= 0) {
+        v = word(mine);
+        while ((v >> 62) == 0 && !ks_spin_expired(spin)) {
+            __builtin_amdgcn_s_sleep(1);
+            v = word(mine);
+        }
+    }
+    if ((v >> 62) == 0) { atomicOr(gave_up, 1u); v = KS_LB_PRE; }
+    *is_pre = __ballot((v >> 62) == 2);
+    const u32 first = *is_pre ? (u32)__ffsll((long long)*is_pre) - 1u : 64u;
+    return ks_wave_sum64(lane <= first ? (v & KS_LB_VAL_MASK) : 0);
+}
+// The walk of a single wave (all 64 lanes enter): exclusive prefix of tile > 0.
+template <typename Word>
+KS_DEV u64 ks_lookback_walk(u32 tile, u32 lane, Word word, u32 *gave_up) {
+    u64 excl = 0;
+    ks_spin spin = ks_spin_begin();
+    u64 is_pre = 0;
+    for (i64 idx = (i64)tile - 1; !is_pre; idx -= 64) excl += ks_lookback_round(idx, lane, word, spin, gave_up, &is_pre);
+    return excl;
+}
+// status words in a plain array
+KS_DEV auto ks_lookback_words(const unsigned long long *status) {
+    return [status](i64 i) -> u64 { return __hip_atomic_load(&status[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); };
 }
 
 // Stable rank of an 8-bit digit inside one wave ("match-any" by eight ballots): returns d << 16 | (records of digit d the wave

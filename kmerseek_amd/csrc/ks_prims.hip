@@ -111,11 +111,9 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_small(T *data, u64 n) {
 // at the latest, and RING < 2^24).  Saves two launches (reduce + scan of the sums) per scan and the memset a fresh
 // status array would need: a step of the search runs seven scans.
 #define SCAN_RING (1u << 20)
-#define SCAN_FLAG_AGG 1ULL
-#define SCAN_FLAG_PRE 2ULL
 #define SCAN_VAL_BITS 38
-KS_DEV unsigned long long scan_word(u64 flag, u32 gtile, u64 value) {
-    return (flag << 62) | ((u64)(gtile & 0xffffffu) << SCAN_VAL_BITS) | value;
+KS_DEV unsigned long long scan_word(u64 flag /* KS_LB_AGG / KS_LB_PRE */, u32 gtile, u64 value) {
+    return flag | ((u64)(gtile & 0xffffffu) << SCAN_VAL_BITS) | value;
 }
 template <typename TIn, typename TOut>
 __global__ __launch_bounds__(SCAN_THREADS) void k_scan_lookback(const TIn *in, TOut *out, u64 n, TOut *total_out,
@@ -141,40 +139,20 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_lookback(const TIn *in, T
     const TOut ex = block_excl_scan_t<TOut>(s, smem, &total);
     const u32 g = ticket_base + tile; // global tile number
     if (tid == 0)
-        __hip_atomic_store(&ring[g % SCAN_RING], scan_word(tile == 0 ? SCAN_FLAG_PRE : SCAN_FLAG_AGG, g, (u64)total),
+        __hip_atomic_store(&ring[g % SCAN_RING], scan_word(tile == 0 ? KS_LB_PRE : KS_LB_AGG, g, (u64)total),
                            __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (tid < 64) {
         u64 excl = 0;
         if (tile > 0) {
-            i64 idx = (i64)tile - 1;
-            bool done = false;
-            u32 spins = 0;
-            const long long spin_t0 = wall_clock64();
-            while (!done) {
-                const i64 mine = idx - (i64)tid;
-                u64 flag = SCAN_FLAG_PRE, val = 0; // before tile 0: inclusive prefix 0
-                if (mine >= 0) {
-                    const u32 gp = ticket_base + (u32)mine;
-                    const u64 want = (u64)(gp & 0xffffffu);
-                    for (;;) {
-                        const u64 w = __hip_atomic_load(&ring[gp % SCAN_RING], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        flag = w >> 62;
-                        if (flag != 0 && ((w >> SCAN_VAL_BITS) & 0xffffffu) == want) { val = w & ((1ULL << SCAN_VAL_BITS) - 1ULL); break; }
-                        flag = 0;
-                        if (ks_spin_expired(spin_t0, spins)) break;
-                        __builtin_amdgcn_s_sleep(1);
-                    }
-                }
-                if (flag == 0) { atomicOr(&ticket[1], 1u); flag = SCAN_FLAG_PRE; val = 0; } // gave up: the host reports it
-                const u64 is_pre = __ballot(flag == SCAN_FLAG_PRE);
-                const u32 first = is_pre ? (u32)__ffsll((long long)is_pre) - 1u : 64u;
-                u64 contrib = tid <= first ? val : 0;
-                contrib = ks_wave_sum64(contrib);
-                excl += contrib;
-                if (is_pre) done = true; else idx -= 64;
-            }
+            // predecessor i's word in the shared layout; one that carries a foreign tag (a left-over in the ring) is not published
+            const auto word = [=](i64 i) -> u64 {
+                const u32 gp = ticket_base + (u32)i;
+                const u64 w = __hip_atomic_load(&ring[gp % SCAN_RING], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                return ((w >> SCAN_VAL_BITS) & 0xffffffu) == (u64)(gp & 0xffffffu) ? w & ~(0xffffffULL << SCAN_VAL_BITS) : 0;
+            };
+            excl = ks_lookback_walk(tile, tid, word, &ticket[1]);
             if (tid == 0)
-                __hip_atomic_store(&ring[g % SCAN_RING], scan_word(SCAN_FLAG_PRE, g, excl + (u64)total), __ATOMIC_RELAXED,
+                __hip_atomic_store(&ring[g % SCAN_RING], scan_word(KS_LB_PRE, g, excl + (u64)total), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
         if (tid == 0) base_s = excl;

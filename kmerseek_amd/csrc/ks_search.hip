@@ -1092,9 +1092,6 @@ __global__ __launch_bounds__(256) void k_pair_rows(const u64 *keys, const u32 *h
 #define PF_IPT 8
 #define PF_TILE (PF_THREADS * PF_IPT)
 #define PF_WAVES (PF_THREADS / 64)
-#define PF_FLAG_AGG (1ULL << 62)
-#define PF_FLAG_PRE (2ULL << 62)
-#define PF_VAL_MASK ((1ULL << 62) - 1)
 
 __global__ __launch_bounds__(PF_THREADS) void k_pair_rows_fused(const u64 *keys, u64 n, u32 *qid, u32 *tid, u32 *isect, unsigned long long *nw,
                                                                 int tbits, int abits, u32 rows_cap, unsigned long long *status,
@@ -1149,33 +1146,12 @@ __global__ __launch_bounds__(PF_THREADS) void k_pair_rows_fused(const u64 *keys,
         const u32 total = (u32)__builtin_amdgcn_readlane((int)incl, 63);
         if (lane < PF_IPT * PF_WAVES) wcount[lane / PF_WAVES][lane % PF_WAVES] = incl - c;
         if (lane == 0)
-            __hip_atomic_store(&status[tile], (tile == 0 ? PF_FLAG_PRE : PF_FLAG_AGG) | (u64)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&status[tile], (tile == 0 ? KS_LB_PRE : KS_LB_AGG) | (u64)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         u64 excl = 0;
         if (tile > 0) {
-            i64 idx = (i64)tile - 1;
-            bool done = false;
-            u32 polls = 0;
-            const long long t0 = wall_clock64();
-            while (!done) {
-                const i64 mine = idx - (i64)lane;
-                u64 v = PF_FLAG_PRE; // before tile 0: inclusive prefix 0
-                if (mine >= 0) {
-                    v = __hip_atomic_load(&status[mine], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    while ((v >> 62) == 0 && !ks_spin_expired(t0, polls)) {
-                        __builtin_amdgcn_s_sleep(1);
-                        v = __hip_atomic_load(&status[mine], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if ((v >> 62) == 0) { atomicOr(&ticket[1], 1u); v = PF_FLAG_PRE; } // gave up: the host reports it
-                const u64 is_pre = __ballot((v >> 62) == 2);
-                const u32 first = is_pre ? (u32)__ffsll((long long)is_pre) - 1u : 64u;
-                u64 contrib = lane <= first ? (v & PF_VAL_MASK) : 0;
-                contrib = ks_wave_sum64(contrib);
-                excl += contrib;
-                if (is_pre) done = true; else idx -= 64;
-            }
+            excl = ks_lookback_walk(tile, lane, ks_lookback_words(status), &ticket[1]); // gave up: the host reports it
             if (lane == 0)
-                __hip_atomic_store(&status[tile], PF_FLAG_PRE | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&status[tile], KS_LB_PRE | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (lane == 0) {
             base_s = excl;

@@ -125,10 +125,6 @@ struct sk_args {
     u32 part_sub_shift;    // sub-regions per region = 1 << shift; a workgroup writes sub-region blockIdx.x & (that - 1)
 };
 
-#define SK_FLAG_AGG (1ULL << 62)
-#define SK_FLAG_PRE (2ULL << 62)
-#define SK_VAL_MASK ((1ULL << 62) - 1)
-
 // bucket multiplier: bucket = umulhi(h >> 32, mul) < n_windows for every kept h (h <= max_hash)
 KS_DEV u32 sk_bucket_mul(u32 nw, u32 sfix) {
     u64 m = ((u64)nw * sfix) >> 16;
@@ -167,6 +163,57 @@ KS_DEV u64 sk_hash_window(const u64 *w /* LDS words starting at pos8 */, u32 k_r
     return m.finish((u64)k);
 }
 
+// h[i] = hash of the window at byte pos8 + H + i, i < NW (the calls stay unrolled: every offset is a compile-time constant)
+template <int H, int NW, int KC = 0, int I = 0>
+KS_DEV void sk_hash_windows(u64 *h, const u64 *w, u32 k_rt, u64 seed) {
+    if constexpr (I < NW) {
+        h[I] = sk_hash_window<H + I, KC>(w, k_rt, seed);
+        sk_hash_windows<H, NW, KC, I + 1>(h, w, k_rt, seed);
+    }
+}
+
+// Staging a tile's residues, 16 B per lane, is two steps so that a kernel can REQUEST the bytes early and store them later:
+// 16 residue bytes at g (16-byte aligned), zero-filled behind the batch ...
+KS_DEV uint4 sk_load16(const u8 *res, u64 n_res, u64 g) {
+#ifdef SK_NT_RES
+    if (g + 16 <= n_res) { const u32 *p4 = (const u32 *)(res + g); return make_uint4(__builtin_nontemporal_load(p4), __builtin_nontemporal_load(p4 + 1), __builtin_nontemporal_load(p4 + 2), __builtin_nontemporal_load(p4 + 3)); }
+#else
+    if (g + 16 <= n_res) return *(const uint4 *)(res + g);
+#endif
+    u32 t[4] = {0, 0, 0, 0};
+    for (u32 b = 0; b < 16 && g + b < n_res; b++) t[b >> 2] |= (u32)res[g + b] << (8 * (b & 3));
+    return make_uint4(t[0], t[1], t[2], t[3]);
+}
+// ... and the 16 bytes through the encode table (256 bytes in LDS)
+KS_DEV uint4 sk_encode16(uint4 v, const u8 *lut_s, bool upper_only /* uniform */) {
+    const u32 in[4] = {v.x, v.y, v.z, v.w};
+    u32 o[4];
+    if (upper_only) { // moltype protein: the table only upper-cases — four bytes at a time, no table, no barrier for it
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            const u32 y = in[d] & 0x7f7f7f7fu; // (no carry between bytes: 0x7f + 0x1f < 0x100)
+            const u32 lower = (y + 0x1f1f1f1fu) & ~(y + 0x05050505u) & ~in[d] & 0x80808080u; // bytes in 'a' .. 'z'
+            o[d] = in[d] ^ (lower >> 2);
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < 4; d++)
+            o[d] = (u32)lut_s[in[d] & 255u] | ((u32)lut_s[(in[d] >> 8) & 255u] << 8) |
+                   ((u32)lut_s[(in[d] >> 16) & 255u] << 16) | ((u32)lut_s[in[d] >> 24] << 24);
+    }
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// first s in [lo, hi) whose local end `end_of(s)` lies beyond `key` (hi if there is none): the sequence that holds position key
+template <typename EndOf>
+KS_DEV u32 sk_seq_beyond(u32 lo, u32 hi, u32 key, EndOf end_of) {
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (end_of(mid) > key) hi = mid; else lo = mid + 1;
+    }
+    return lo;
+}
+
 // does the sequence at residue offset `start` with `len` residues end outside its shared tile's LDS window?
 KS_DEV bool sk_deferred(u64 start, u64 len, u32 R, u32 span) { return start % R + len > span - 16; }
 // floor(x / d) for x < 2^32 / d with rcp = ceil(2^32 / d) (d = 1: rcp does not fit, handled apart)
@@ -177,6 +224,8 @@ KS_DEV u32 sk_div(u32 x, u32 d, u32 rcp) { return d == 1 ? x : __umulhi(x, rcp);
 // reads + a compare / select / add each per thread — a quarter of phase 3's vector instructions): lane j < 8 of every wave
 // reads total j, three DPP steps scan the eight, and the wave's own base / the tile total are READ from lanes wave - 1 / 7
 // (the wave number is uniform: v_readlane).
+// These scans are the tile kernel's own (SK_THREADS threads, one barrier, smem live until the caller's next barrier); a new
+// kernel that is not short of barriers takes ks_block_excl_scan (ks_device.h), which has neither condition.
 KS_DEV u32 sk_wave_totals_scan(const u32 *smem, u32 lane, u32 wave_u /* uniform */, u32 *total) {
     constexpr u32 NW = SK_THREADS / 64;
     static_assert(NW <= 16, "one DPP row");
@@ -393,16 +442,7 @@ KS_DEV void sk_cmp_half(const sk_args &A, const sk_bounds &B, sk_seq &q, const u
     u64 h[NW];
     u32 keep = 0, sr[2] = {0, 0}; // keep mask of the NW windows, their sequences (one byte each)
     if (active) {
-        h[0] = sk_hash_window<H + 0, KC>(wl, A.k, A.seed);
-        h[1] = sk_hash_window<H + 1, KC>(wl, A.k, A.seed);
-        h[2] = sk_hash_window<H + 2, KC>(wl, A.k, A.seed);
-        h[3] = sk_hash_window<H + 3, KC>(wl, A.k, A.seed);
-        if constexpr (NW == 8) {
-            h[4] = sk_hash_window<H + 4, KC>(wl, A.k, A.seed);
-            h[5] = sk_hash_window<H + 5, KC>(wl, A.k, A.seed);
-            h[6] = sk_hash_window<H + 6, KC>(wl, A.k, A.seed);
-            h[7] = sk_hash_window<H + 7, KC>(wl, A.k, A.seed);
-        }
+        sk_hash_windows<H, NW, KC>(h, wl, A.k, A.seed);
         if ((KC ? (u32)KC : A.k) >= SK_E) { // (uniform) one sequence per thread (see sk_place_window)
             const u32 srel = q.s - s_first;
 #pragma unroll
@@ -515,34 +555,6 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
         __syncthreads();
         tile = tile_s;
     }
-    auto load_chunk = [&](u64 g) -> uint4 { // 16 residue bytes at g (16-byte aligned), zero-filled behind the batch
-#ifdef SK_NT_RES
-        if (g + 16 <= A.n_res) { const u32 *p4 = (const u32 *)(A.res + g); return make_uint4(__builtin_nontemporal_load(p4), __builtin_nontemporal_load(p4 + 1), __builtin_nontemporal_load(p4 + 2), __builtin_nontemporal_load(p4 + 3)); }
-#else
-        if (g + 16 <= A.n_res) return *(const uint4 *)(A.res + g);
-#endif
-        u32 t[4] = {0, 0, 0, 0};
-        for (u32 b = 0; b < 16 && g + b < A.n_res; b++) t[b >> 2] |= (u32)A.res[g + b] << (8 * (b & 3));
-        return make_uint4(t[0], t[1], t[2], t[3]);
-    };
-    auto stage_chunk = [&](uint4 v) { // through the encode LUT into the tile's residue buffer, 16 B per lane
-        const u32 in[4] = {v.x, v.y, v.z, v.w};
-        u32 o[4];
-        if (A.upper_only) { // (uniform) moltype protein: the table only upper-cases — four bytes at a time, no table, no barrier for it
-#pragma unroll
-            for (int d = 0; d < 4; d++) {
-                const u32 y = in[d] & 0x7f7f7f7fu; // (no carry between bytes: 0x7f + 0x1f < 0x100)
-                const u32 lower = (y + 0x1f1f1f1fu) & ~(y + 0x05050505u) & ~in[d] & 0x80808080u; // bytes in 'a' .. 'z'
-                o[d] = in[d] ^ (lower >> 2);
-            }
-        } else {
-#pragma unroll
-            for (int d = 0; d < 4; d++)
-                o[d] = (u32)lut_s[in[d] & 255u] | ((u32)lut_s[(in[d] >> 8) & 255u] << 8) |
-                       ((u32)lut_s[(in[d] >> 16) & 255u] << 16) | ((u32)lut_s[in[d] >> 24] << 24);
-        }
-        *(uint4 *)(res_b + (size_t)tid * 16) = make_uint4(o[0], o[1], o[2], o[3]);
-    };
     uint4 rv = make_uint4(0, 0, 0, 0);
     const bool packed = MODE == 0 && !CMP && A.R == 0; // (uniform) packed tiles: the window starts where the plan says
     // The plan entries of the tile — where its residues start, its first and last sequence — are three independent loads: all
@@ -556,10 +568,10 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
     if (MODE == 1) { s_first = A.seq_list[tile]; s_end = s_first + 1; }
     else { s_first = A.seq_list[tile]; s_end = A.seq_list[tile + 1]; }
     if (!A.upper_only && tid < 256) lut_s[tid] = (u8)lut_v;
-    if (MODE == 0 && tid < NCH) rv = load_chunk((packed ? g0p : (u64)tile * A.R) + (u64)tid * 16); // R is a multiple of 16
+    if (MODE == 0 && tid < NCH) rv = sk_load16(A.res, A.n_res, (packed ? g0p : (u64)tile * A.R) + (u64)tid * 16); // R is a multiple of 16
     if (s_first >= s_end) {
         if (MODE == 0 && tid == 0)
-            __hip_atomic_store(&A.tile_status[tile], SK_FLAG_AGG | 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.tile_status[tile], KS_LB_AGG | 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
     // local coordinates: MODE 0 counts from the tile's first byte, MODE 1 from the (aligned) start of its sequence
@@ -580,12 +592,12 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
         if (span_end > g0 + SK_TILE) span_end = g0 + SK_TILE;
         if (tid < NCH) {
             const u64 g = g0 + (u64)tid * 16;
-            if (g < span_end) rv = load_chunk(g);
+            if (g < span_end) rv = sk_load16(A.res, A.n_res, g);
         }
         __syncthreads(); // lut_s
     }
     if (MODE == 0 && !A.upper_only) __syncthreads(); // the LUT (the tile's global loads are in flight; the zeroed LDS state is first touched behind the next barrier)
-    if (tid < NCH) stage_chunk(rv);
+    if (tid < NCH) *(uint4 *)(res_b + (size_t)tid * 16) = sk_encode16(rv, lut_s, A.upper_only);
     __syncthreads();
 
     SK_STAMP_AT(1);
@@ -596,13 +608,7 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
     const bool onerun = kk >= SK_E; // (uniform; compile-time for the folded k-mer sizes) see the note behind sk_place_window
     {
         // first sequence of the tile whose end lies beyond q0 — whose LAST WINDOW lies at or beyond q0 when k >= SK_E
-        const u32 key = onerun ? q0 + kk - 1u : q0;
-        u32 lo = s_first, hi = s_end;
-        while (lo < hi) {
-            u32 mid = lo + ((hi - lo) >> 1);
-            if (B.at(mid + 1) > key) hi = mid; else lo = mid + 1;
-        }
-        q.s = lo;
+        q.s = sk_seq_beyond(s_first, s_end, onerun ? q0 + kk - 1u : q0, [&](u32 s) { return B.at(s + 1); });
         sk_load_seq(q, A, B, s_end);
     }
     const u64 *wl = res_w + tid; // word at byte q0
@@ -626,22 +632,16 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
         const u32 n_sub = B.in_lds ? (end_l + SK_TILE - 1) / SK_TILE : 0; // (more sequences than the LDS table holds: flagged below)
         for (u32 sub = 0; sub < n_sub; sub++) {
             if (sub > 0) {
-                if (tid < NCH) stage_chunk(rv);
+                if (tid < NCH) *(uint4 *)(res_b + (size_t)tid * 16) = sk_encode16(rv, lut_s, A.upper_only);
                 __syncthreads();
             }
             SK_STAMP_AT(9); // (stamps 9 .. 11: the compacting loop's stage / hash + append / closing barrier)
             if (sub + 1 < n_sub && tid < NCH) // next sub-tile's residues travel while this one is hashed
-                rv = load_chunk((u64)tile * A.R + (u64)(sub + 1) * SK_TILE + (u64)tid * 16);
+                rv = sk_load16(A.res, A.n_res, (u64)tile * A.R + (u64)(sub + 1) * SK_TILE + (u64)tid * 16);
             const u32 p0 = sub * SK_TILE + q0;
             const bool active = p0 < end_l;
             if (active) { // the sequence that holds (or follows) position p0 — whose last window lies at or beyond it when k >= SK_E
-                const u32 key = onerun ? p0 + kk - 1u : p0;
-                u32 lo = s_first, hi = s_end;
-                while (lo < hi) {
-                    u32 mid = lo + ((hi - lo) >> 1);
-                    if (B.at(mid + 1) > key) hi = mid; else lo = mid + 1;
-                }
-                q.s = lo;
+                q.s = sk_seq_beyond(s_first, s_end, onerun ? p0 + kk - 1u : p0, [&](u32 s) { return B.at(s + 1); });
                 sk_load_seq(q, A, B, s_end);
             }
             // all eight windows behind one scan and one cursor atomic where the eight live hashes fit the register budget next to
@@ -663,7 +663,7 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
             // used — the host repeats the batch with the plain variant — but the look-back chain must not stall
             if (tid == 0) {
                 atomicOr(&A.ticket[1], 4u);
-                __hip_atomic_store(&A.tile_status[tile], (tile == 0 ? SK_FLAG_PRE : SK_FLAG_AGG) | 0ULL, __ATOMIC_RELAXED,
+                __hip_atomic_store(&A.tile_status[tile], (tile == 0 ? KS_LB_PRE : KS_LB_AGG) | 0ULL, __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
             }
             return;
@@ -704,14 +704,7 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
     // a tile's sequences end, on average, two thirds of the way through its SK_TILE positions: the threads behind
     // the last residue (whole waves, mostly) have nothing to hash
     if (q0 < B.at(s_end)) {
-        h[0] = sk_hash_window<0, KC>(wl, A.k, A.seed);
-        h[1] = sk_hash_window<1, KC>(wl, A.k, A.seed);
-        h[2] = sk_hash_window<2, KC>(wl, A.k, A.seed);
-        h[3] = sk_hash_window<3, KC>(wl, A.k, A.seed);
-        h[4] = sk_hash_window<4, KC>(wl, A.k, A.seed);
-        h[5] = sk_hash_window<5, KC>(wl, A.k, A.seed);
-        h[6] = sk_hash_window<6, KC>(wl, A.k, A.seed);
-        h[7] = sk_hash_window<7, KC>(wl, A.k, A.seed);
+        sk_hash_windows<0, SK_E, KC>(h, wl, A.k, A.seed);
         if (onerun) {
             const u32 srel = q.s - B.s_first;
             const u32 s24 = (srel < 254u ? srel : 254u) << 24;
@@ -853,7 +846,7 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
     u64 agg = n_kept;
     for (u32 e = 0; e < ne; e++) agg += ext_cnt[e];
     if (MODE == 0 && tid == 0 && tile != A.debug_skip_tile)
-        __hip_atomic_store(&A.tile_status[tile], (tile == 0 ? SK_FLAG_PRE : SK_FLAG_AGG) | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&A.tile_status[tile], (tile == 0 ? KS_LB_PRE : KS_LB_AGG) | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
     SK_STAMP_AT(3);
     // ---- phase 4: scatter kept hashes into bucket order; sorted position at which every sequence's run starts
@@ -1249,25 +1242,11 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
 #endif
             const u32 lane = tid & 63u, wave = tid >> 6;
             i64 idx = (i64)tile - 1;
-            u32 spins = 0;
-            const long long spin_t0 = wall_clock64();
+            ks_spin spin = ks_spin_begin();
             for (;;) {
                 if (wave < SK_LB_WAVES) { // (uniform per wave: the other waves only meet the barrier — they used to reduce a wave of dummies)
-                    const i64 mine = idx - (i64)tid;
-                    u64 v = SK_FLAG_PRE; // before tile 0: inclusive prefix 0
-                    if (mine >= 0) {
-                        v = __hip_atomic_load(&A.tile_status[mine], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        while ((v >> 62) == 0 && !ks_spin_expired(spin_t0, spins)) {
-                            __builtin_amdgcn_s_sleep(1);
-                            v = __hip_atomic_load(&A.tile_status[mine], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                    }
-                    if ((v >> 62) == 0) { atomicOr(&A.ticket[1], 1u); v = SK_FLAG_PRE; } // spin bound expired: flag the error, do not hang
-                    const u64 is_pre = __ballot((v >> 62) == 2);
-                    // lanes at or before the wave's first inclusive prefix contribute
-                    const u32 first = is_pre ? (u32)__ffsll((long long)is_pre) - 1u : 64u;
-                    u64 contrib = lane <= first ? (v & SK_VAL_MASK) : 0;
-                    contrib = ks_wave_sum64(contrib);
+                    u64 is_pre;
+                    const u64 contrib = ks_lookback_round(idx - 64 * (i64)wave, lane, ks_lookback_words(A.tile_status), spin, &A.ticket[1], &is_pre);
                     if (lane == 0) { lb_sum[wave] = contrib; lb_pre[wave] = is_pre ? 1u : 0u; }
                 }
                 __syncthreads(); // (the first one also orders everything placed between publication and look-back)
@@ -1283,7 +1262,7 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
                 __syncthreads(); // (lb_sum / lb_pre are written again)
             }
             if (tid == 0 && tile != A.debug_skip_tile)
-                __hip_atomic_store(&A.tile_status[tile], SK_FLAG_PRE | (excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&A.tile_status[tile], KS_LB_PRE | (excl + agg), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         } else {
             __syncthreads();
         }
@@ -1491,21 +1470,8 @@ __global__ __launch_bounds__(SK_THREADS) void k_sketch_long(sk_long_args L) {
             const u64 g0 = gbase & ~15ULL;
             const u32 shift = (u32)(gbase - g0);
             for (u32 c = tid; c < (SK_TILE + SK_PAD) / 16; c += SK_THREADS) {
-                u64 g = g0 + (u64)c * 16;
-                u32 t[4] = {0, 0, 0, 0};
-                if (g < e) {
-                    if (g + 16 <= A.n_res) {
-                        uint4 v = *(const uint4 *)(A.res + g);
-                        t[0] = v.x; t[1] = v.y; t[2] = v.z; t[3] = v.w;
-                    } else {
-                        for (u32 bb = 0; bb < 16 && g + bb < A.n_res; bb++) t[bb >> 2] |= (u32)A.res[g + bb] << (8 * (bb & 3));
-                    }
-#pragma unroll
-                    for (int d = 0; d < 4; d++)
-                        t[d] = (u32)lut_s[t[d] & 255u] | ((u32)lut_s[(t[d] >> 8) & 255u] << 8) |
-                               ((u32)lut_s[(t[d] >> 16) & 255u] << 16) | ((u32)lut_s[t[d] >> 24] << 24);
-                }
-                *(uint4 *)(res_b + (size_t)c * 16) = make_uint4(t[0], t[1], t[2], t[3]);
+                const u64 g = g0 + (u64)c * 16;
+                *(uint4 *)(res_b + (size_t)c * 16) = g < e ? sk_encode16(sk_load16(A.res, A.n_res, g), lut_s, false) : make_uint4(0, 0, 0, 0);
             }
             __syncthreads();
             // window w = w0 + j lives at LDS byte shift + j; j strided over threads
@@ -1674,16 +1640,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_kmerpos_tiles(kp_args A) {
     if (tid < 256) lut_v = A.lut[tid];
     const u64 g0 = (u64)tile * KP_R;
     uint4 rv = make_uint4(0, 0, 0, 0);
-    if (tid < NCH) {
-        const u64 g = g0 + (u64)tid * 16;
-        if (g + 16 <= A.n_res) {
-            rv = *(const uint4 *)(A.res + g);
-        } else {
-            u32 t[4] = {0, 0, 0, 0};
-            for (u32 b = 0; b < 16 && g + b < A.n_res; b++) t[b >> 2] |= (u32)A.res[g + b] << (8 * (b & 3));
-            rv = make_uint4(t[0], t[1], t[2], t[3]);
-        }
-    }
+    if (tid < NCH) rv = sk_load16(A.res, A.n_res, g0 + (u64)tid * 16);
     const u32 s_first = A.tile_first[tile];
     u32 s_last = A.tile_first[tile + 1]; // the sequence that holds the next tile's first position also ends here or later
     if (s_last >= A.n_seqs) s_last = A.n_seqs ? A.n_seqs - 1 : 0;
@@ -1696,15 +1653,7 @@ __global__ __launch_bounds__(SK_THREADS) void k_kmerpos_tiles(kp_args A) {
         }
     if (tid < 256) lut_s[tid] = (u8)lut_v;
     __syncthreads(); // the table
-    if (tid < NCH) {
-        const u32 in[4] = {rv.x, rv.y, rv.z, rv.w};
-        u32 o[4];
-#pragma unroll
-        for (int d = 0; d < 4; d++)
-            o[d] = (u32)lut_s[in[d] & 255u] | ((u32)lut_s[(in[d] >> 8) & 255u] << 8) |
-                   ((u32)lut_s[(in[d] >> 16) & 255u] << 16) | ((u32)lut_s[in[d] >> 24] << 24);
-        *(uint4 *)((u8 *)res_w + (size_t)tid * 16) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
+    if (tid < NCH) *(uint4 *)((u8 *)res_w + (size_t)tid * 16) = sk_encode16(rv, lut_s, false);
     __syncthreads();
     auto end_of = [&](u32 s) -> u32 { // local end of sequence s (s_first <= s <= s_last)
         if (in_lds) return lend[s - s_first];
@@ -1720,21 +1669,9 @@ __global__ __launch_bounds__(SK_THREADS) void k_kmerpos_tiles(kp_args A) {
     for (int i = 0; i < SK_E; i++) { h[i] = 0; sq[i] = 0xffffffffu; }
     if (ns && g0 + q0 < A.n_res) {
         // the sequence that holds position q0: first one (from s_first) whose end lies beyond q0
-        u32 lo = s_first, hi = s_last;
-        while (lo < hi) {
-            const u32 mid = lo + ((hi - lo) >> 1);
-            if (end_of(mid) > q0) hi = mid; else lo = mid + 1;
-        }
-        u32 s = lo, e = end_of(s);
+        u32 s = sk_seq_beyond(s_first, s_last, q0, end_of), e = end_of(s); // (s_last is inclusive: the answer when no earlier one is)
         const u64 *wl = res_w + tid;
-        h[0] = sk_hash_window<0>(wl, A.k, A.seed);
-        h[1] = sk_hash_window<1>(wl, A.k, A.seed);
-        h[2] = sk_hash_window<2>(wl, A.k, A.seed);
-        h[3] = sk_hash_window<3>(wl, A.k, A.seed);
-        h[4] = sk_hash_window<4>(wl, A.k, A.seed);
-        h[5] = sk_hash_window<5>(wl, A.k, A.seed);
-        h[6] = sk_hash_window<6>(wl, A.k, A.seed);
-        h[7] = sk_hash_window<7>(wl, A.k, A.seed);
+        sk_hash_windows<0, SK_E>(h, wl, A.k, A.seed);
 #pragma unroll
         for (int i = 0; i < SK_E; i++) {
             const u32 p = q0 + i;
@@ -1746,37 +1683,16 @@ __global__ __launch_bounds__(SK_THREADS) void k_kmerpos_tiles(kp_args A) {
     }
     u32 total;
     const u32 ex = ks_block_excl_scan(n_keep, scan_smem, &total);
-    // ---- decoupled look-back over the tiles' kept counts (see k_sketch_tiles)
+    // ---- decoupled look-back over the tiles' kept counts (protocol: ks_device.h)
     if (tid == 0)
-        __hip_atomic_store(&A.tile_status[tile], (tile == 0 ? SK_FLAG_PRE : SK_FLAG_AGG) | (u64)total, __ATOMIC_RELAXED,
+        __hip_atomic_store(&A.tile_status[tile], (tile == 0 ? KS_LB_PRE : KS_LB_AGG) | (u64)total, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     if (tid < 64) {
         u64 excl = 0;
         if (tile > 0) {
-            i64 idx = (i64)tile - 1;
-            bool done = false;
-            u32 spins = 0;
-            const long long spin_t0 = wall_clock64();
-            while (!done) {
-                const i64 mine = idx - (i64)tid;
-                u64 v = SK_FLAG_PRE;
-                if (mine >= 0) {
-                    v = __hip_atomic_load(&A.tile_status[mine], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    while ((v >> 62) == 0 && !ks_spin_expired(spin_t0, spins)) {
-                        __builtin_amdgcn_s_sleep(1);
-                        v = __hip_atomic_load(&A.tile_status[mine], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                }
-                if ((v >> 62) == 0) { atomicOr(&A.ticket[1], 1u); v = SK_FLAG_PRE; }
-                const u64 is_pre = __ballot((v >> 62) == 2);
-                const u32 first = is_pre ? (u32)__ffsll((long long)is_pre) - 1u : 64u;
-                u64 contrib = tid <= first ? (v & SK_VAL_MASK) : 0;
-                contrib = ks_wave_sum64(contrib);
-                excl += contrib;
-                if (is_pre) done = true; else idx -= 64;
-            }
+            excl = ks_lookback_walk(tile, tid, ks_lookback_words(A.tile_status), &A.ticket[1]);
             if (tid == 0)
-                __hip_atomic_store(&A.tile_status[tile], SK_FLAG_PRE | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&A.tile_status[tile], KS_LB_PRE | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (tid == 0) {
             base_s = excl;
