@@ -71,6 +71,7 @@ typedef struct ks_sketches ks_sketches; /* device-resident CSR: offsets[n+1], ha
 typedef struct ks_index ks_index;       /* device-resident inverted index: postings sorted by hash */
 typedef struct ks_hits ks_hits;         /* device-resident COO (qid, tid, intersect, n_weighted) */
 typedef struct ks_kmerpos ks_kmerpos;   /* device-resident (seq, start, hash) triples */
+typedef struct ks_matchpos ks_matchpos; /* device-resident CSR over hit rows: (query start, target start) of shared k-mers */
 
 /* ---- library / context ------------------------------------------------------------------ */
 
@@ -232,6 +233,7 @@ int ks_kmer_positions(ks_ctx *ctx, const uint8_t *residues, const uint64_t *seq_
 int ks_kmer_positions_device(ks_ctx *ctx, const uint8_t *d_residues, const uint64_t *d_seq_offsets, uint32_t n_seqs,
                              uint64_t n_residues, const ks_params *params, ks_kmerpos **out);
 uint64_t ks_kmerpos_count(const ks_kmerpos *p);
+void ks_kmerpos_params(const ks_kmerpos *p, ks_params *out); /* the parameters the table was made with */
 int ks_kmerpos_copy_to_host(ks_ctx *ctx, const ks_kmerpos *p, uint32_t *seq, uint32_t *start,
                             uint64_t *hash);
 void ks_kmerpos_free(ks_kmerpos *p);
@@ -330,6 +332,52 @@ const uint64_t *ks_hits_device_median2(const ks_hits *h);
 const double *ks_hits_device_abund_ss(const ks_hits *h);
 /* either destination may be NULL; KS_ERR_INVALID_ARG for hits without the statistics */
 int ks_hits_copy_abund_stats_to_host(ks_ctx *ctx, const ks_hits *h, uint64_t *median2, double *ss);
+
+/* ---- match positions: where each hit's shared k-mers lie ------------------------------------------------------------------ */
+
+/* Replaces the k-mer join of `kmerseek search --extract-kmers` (src/python/kmerseek/search.py:195-240: query and target k-mer
+ * tables joined on the hash, restricted to the search hits): for every row r = (qid, tid) of `hits`, the multiset
+ *     { (a.start, b.start) : a in q_pos, a.seq = qid, b in t_pos, b.seq = tid, a.hash = b.hash }
+ * ordered by (query start, target start) — a hash that repeats m times in the query and n times in the target gives m x n
+ * pairs.  q_pos / t_pos: the ks_kmer_positions* tables of the query batch and of the targets `hits` was searched on, made
+ * with the same ks_params (else KS_ERR_INVALID_ARG); hits: from any search entry, thresholded ones included — equal hashes of
+ * a (query, target) pair that is not a row of `hits` give no pair.  Every row of a search shares a hash, so it owns at least
+ * one pair (at least `intersect`, exactly `intersect` when neither sequence repeats a k-mer): a row without pairs means the
+ * three inputs do not belong together, and the call fails with KS_ERR_INVALID_ARG.
+ * Result (device-resident):
+ *   row_offsets u64[n_rows + 1]  row r owns pairs [row_offsets[r], row_offsets[r + 1]);  n_rows = ks_hits_count(hits)
+ *   q_start, t_start u32[n_pairs]
+ *   q_lo, q_hi, t_lo, t_hi u32[n_rows]  per row the smallest start and the largest start + ksize on either side: the
+ *                                query_start / match_start of the reference's stitched row and an upper bound of its *_end
+ * One stream, synchronous on return; all scratch comes from the context's pool. */
+typedef struct ks_matchpos_opts {
+    uint32_t flags;     /* none defined: 0 */
+    uint32_t reserved;  /* 0 */
+    uint64_t max_pairs; /* refuse more than this many pairs; 0 = the library's own limit (what the device memory and one sort
+                           take).  The pairs are counted — as the join finds them, before the rows a thresholded search dropped
+                           are taken out: that many have to be materialised — BEFORE the pair arrays are allocated; beyond the
+                           limit the call fails with KS_ERR_CAPACITY and ks_last_error carries the count (low-complexity hp
+                           k-mers make the sum of q(h) x t(h) explode: the caller can say no). */
+} ks_matchpos_opts;
+/* opts == NULL: the defaults.  Options are checked before any device work. */
+int ks_match_positions(ks_ctx *ctx, const ks_kmerpos *q_pos, const ks_kmerpos *t_pos, const ks_hits *hits,
+                       const ks_matchpos_opts *opts, ks_matchpos **out);
+uint64_t ks_matchpos_n_rows(const ks_matchpos *m);
+uint64_t ks_matchpos_n_pairs(const ks_matchpos *m);
+/* hit-row slices the call ran in (1 unless row index + both starts need more than 64 key bits).  Diagnostic. */
+uint32_t ks_matchpos_n_slices(const ks_matchpos *m);
+/* device pointers, valid until ks_matchpos_free */
+const uint64_t *ks_matchpos_device_row_offsets(const ks_matchpos *m);
+const uint32_t *ks_matchpos_device_q_start(const ks_matchpos *m);
+const uint32_t *ks_matchpos_device_t_start(const ks_matchpos *m);
+const uint32_t *ks_matchpos_device_q_lo(const ks_matchpos *m);
+const uint32_t *ks_matchpos_device_q_hi(const ks_matchpos *m);
+const uint32_t *ks_matchpos_device_t_lo(const ks_matchpos *m);
+const uint32_t *ks_matchpos_device_t_hi(const ks_matchpos *m);
+/* any destination may be NULL */
+int ks_matchpos_copy_to_host(ks_ctx *ctx, const ks_matchpos *m, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
+                             uint32_t *q_lo, uint32_t *q_hi, uint32_t *t_lo, uint32_t *t_hi);
+void ks_matchpos_free(ks_matchpos *m);
 
 /* ---- measurement --------------------------------------------------------------------------- */
 

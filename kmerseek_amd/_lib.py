@@ -44,6 +44,10 @@ class ks_search_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("min_containment", C.c_double)]
 
 
+class ks_matchpos_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("max_pairs", C.c_uint64)]
+
+
 class ks_kernel_time(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -100,6 +104,7 @@ SIGNATURES = {
     "ks_kmer_positions": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _parp, _pp]),
     "ks_kmer_positions_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _parp, _pp]),
     "ks_kmerpos_count": (C.c_uint64, [_vp]),
+    "ks_kmerpos_params": (None, [_vp, _parp]),
     "ks_kmerpos_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ks_kmerpos_free": (None, [_vp]),
     "ks_index_build": (C.c_int, [_vp, _vp, _pp]),
@@ -129,6 +134,19 @@ SIGNATURES = {
     "ks_hits_device_median2": (_vp, [_vp]),
     "ks_hits_device_abund_ss": (_vp, [_vp]),
     "ks_hits_copy_abund_stats_to_host": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ks_match_positions": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ks_matchpos_opts), _pp]),
+    "ks_matchpos_n_rows": (C.c_uint64, [_vp]),
+    "ks_matchpos_n_pairs": (C.c_uint64, [_vp]),
+    "ks_matchpos_n_slices": (C.c_uint32, [_vp]),
+    "ks_matchpos_device_row_offsets": (_vp, [_vp]),
+    "ks_matchpos_device_q_start": (_vp, [_vp]),
+    "ks_matchpos_device_t_start": (_vp, [_vp]),
+    "ks_matchpos_device_q_lo": (_vp, [_vp]),
+    "ks_matchpos_device_q_hi": (_vp, [_vp]),
+    "ks_matchpos_device_t_lo": (_vp, [_vp]),
+    "ks_matchpos_device_t_hi": (_vp, [_vp]),
+    "ks_matchpos_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ks_matchpos_free": (None, [_vp]),
     "ks_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ks_timing_reset": (C.c_int, [_vp]),
     "ks_timing_get": (C.c_int, [_vp, C.POINTER(ks_kernel_time), C.c_uint32, _u32p]),

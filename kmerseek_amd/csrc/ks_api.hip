@@ -224,7 +224,7 @@ int ks_kmerpos_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 
     KS_HIP(ctx, hipSetDevice(ctx->device));
     ks_kmerpos *K = new ks_kmerpos();
     memset(K, 0, sizeof *K);
-    K->ctx = ctx;
+    K->ctx = ctx; K->params = *p; K->n_seqs = n_seqs;
     int st = KS_OK;
     // every residue position starts at most one window: n_res bounds the table
     const size_t cap = (n_res == 0 || n_seqs == 0) ? 1 : (size_t)n_res;
@@ -268,6 +268,7 @@ extern "C" int ks_kmer_positions_device(ks_ctx *ctx, const uint8_t *d_residues, 
 }
 
 extern "C" uint64_t ks_kmerpos_count(const ks_kmerpos *p) { return p ? p->n : 0; }
+extern "C" void ks_kmerpos_params(const ks_kmerpos *p, ks_params *out) { if (p && out) *out = p->params; }
 
 extern "C" int ks_kmerpos_copy_to_host(ks_ctx *ctx, const ks_kmerpos *p, uint32_t *seq, uint32_t *start, uint64_t *hash) {
     return ks_guard(ctx, [&]() -> int {

@@ -45,7 +45,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -330,9 +330,21 @@ struct ks_hits {
 
 struct ks_kmerpos {
     ks_ctx *ctx;
+    ks_params params; // what the table was made with (ks_match_positions joins only tables of equal parameters)
+    u32 n_seqs;       // sequences of the batch: d_seq values are below it
     u64 n;
     u32 *d_seq, *d_start;
     u64 *d_hash;
+};
+
+// pairs of window starts that share a hash, grouped by hit row (ks_matchpos.hip)
+struct ks_matchpos {
+    ks_ctx *ctx;
+    u64 n_rows, n_pairs;
+    u32 n_slices;
+    u64 *d_row_offsets;          // n_rows + 1
+    u32 *d_qstart, *d_tstart;    // n_pairs
+    u32 *d_qlo, *d_qhi, *d_tlo, *d_thi; // n_rows
 };
 
 // ---- device-wide primitives (ks_scan.hip, ks_sort.hip) ----
@@ -411,6 +423,7 @@ int ks_kmerpos_tiles_launch(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32
 int ks_kmerpos_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res,
                            const ks_params *p, ks_kmerpos **out);
 int ks_index_build_impl(ks_ctx *ctx, const ks_sketches *t, ks_index **out);
+int ks_matchpos_opts_check(ks_ctx *ctx, const ks_matchpos_opts *opts);
 // opts: NULL or validated (ks_search_opts_check); NULL and all-zero options run the same launches
 int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo = nullptr,
                    const ks_search_opts *opts = nullptr);

@@ -334,6 +334,36 @@ class Context:
             self._L.ks_kmerpos_free(out)
         return seq, start, h
 
+    def kmer_positions_table(self, residues: np.ndarray, offsets: np.ndarray, ksize: int, scaled: int, moltype: str,
+                             seed: int = SEED) -> "KmerPositions":
+        """kmer_positions, with the table left on the device (the input of `match_positions`)."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        p = make_params(ksize, scaled, moltype, seed)
+        out = C.c_void_p()
+        self._check(self._L.ks_kmer_positions(self._h, _ptr(residues), _ptr(offsets), len(offsets) - 1, C.byref(p),
+                                              C.byref(out)))
+        return KmerPositions(self, out)
+
+    def kmer_positions_table_device(self, d_residues: int, d_offsets: int, n_seqs: int, n_residues: int, ksize: int, scaled: int,
+                                    moltype: str, seed: int = SEED) -> "KmerPositions":
+        """kmer_positions_device, with the table left on the device."""
+        p = make_params(ksize, scaled, moltype, seed)
+        out = C.c_void_p()
+        self._check(self._L.ks_kmer_positions_device(self._h, C.c_void_p(d_residues), C.c_void_p(d_offsets), n_seqs, n_residues,
+                                                     C.byref(p), C.byref(out)))
+        return KmerPositions(self, out)
+
+    def match_positions(self, q_pos: "KmerPositions", t_pos: "KmerPositions", hits: "Hits", max_pairs: int = 0) -> "MatchPositions":
+        """ks_match_positions: per row of `hits` the (query start, target start) pairs of the windows that share a kept hash,
+        ordered by (query start, target start), and the extents they span.  q_pos / t_pos: the k-mer position tables of the
+        query batch and of the targets the hits were searched on (same parameters).  max_pairs > 0 refuses a larger join
+        with KS_ERR_CAPACITY before the pairs are allocated (the message carries the count); 0: the library's own limit."""
+        out = C.c_void_p()
+        opts = _lib.ks_matchpos_opts(0, 0, int(max_pairs))
+        self._check(self._L.ks_match_positions(self._h, q_pos._h, t_pos._h, hits._h, C.byref(opts), C.byref(out)))
+        return MatchPositions(self, out)
+
     # ---- index / search ----
     def index_build(self, targets: "Sketches") -> "Index":
         out = C.c_void_p()
@@ -499,6 +529,55 @@ class Sketches(_Owned):
         self._ctx._check(self._ctx._L.ks_sketches_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(hashes),
                                                                _ptr(abunds)))
         return offs, hashes, abunds
+
+
+class KmerPositions(_Owned):
+    """Device-resident (seq, start, hash) triples of the kept windows of a batch (ks_kmerpos), ordered by (seq, start)."""
+    _free = "ks_kmerpos_free"
+
+    @property
+    def count(self) -> int:
+        return int(self._ctx._L.ks_kmerpos_count(self._h))
+
+    def to_host(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        n = self.count
+        seq = np.zeros(n, np.uint32); start = np.zeros(n, np.uint32); h = np.zeros(n, np.uint64)
+        self._ctx._check(self._ctx._L.ks_kmerpos_copy_to_host(self._ctx._h, self._h, _ptr(seq), _ptr(start), _ptr(h)))
+        return seq, start, h
+
+
+class MatchPositions(_Owned):
+    """Device-resident CSR over hit rows (ks_matchpos): row r of the hits owns pairs [row_offsets[r], row_offsets[r + 1])."""
+    _free = "ks_matchpos_free"
+    _COLUMNS = ("row_offsets", "q_start", "t_start", "q_lo", "q_hi", "t_lo", "t_hi")
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_matchpos_n_rows(self._h))
+
+    @property
+    def n_pairs(self) -> int:
+        return int(self._ctx._L.ks_matchpos_n_pairs(self._h))
+
+    @property
+    def n_slices(self) -> int:
+        """Hit-row slices the call ran in (1 unless row index and starts do not fit one 64-bit key).  Diagnostic."""
+        return int(self._ctx._L.ks_matchpos_n_slices(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (row_offsets u64[n_rows + 1], q_start / t_start u32[n_pairs], q_lo, q_hi, t_lo, t_hi u32[n_rows])."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_matchpos_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """(row_offsets u64[n_rows + 1], q_start, t_start u32[n_pairs], q_lo, q_hi, t_lo, t_hi u32[n_rows])."""
+        nr, npairs = self.n_rows, self.n_pairs
+        offs = np.zeros(nr + 1, np.uint64)
+        qs = np.zeros(npairs, np.uint32); ts = np.zeros(npairs, np.uint32)
+        ext = [np.zeros(nr, np.uint32) for _ in range(4)]
+        self._ctx._check(self._ctx._L.ks_matchpos_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(qs), _ptr(ts),
+                                                               *[_ptr(e) for e in ext]))
+        return (offs, qs, ts, *ext)
 
 
 class Index(_Owned):

@@ -328,3 +328,80 @@ def search_extract_kmers(query_fasta: str, target_fasta: str, ksize: int, scaled
     finally:
         if own:
             ctx.close()
+
+
+def stitch_match_positions(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, row_offsets,
+                           q_start, t_start, ksize: int, moltype: str) -> List[dict]:
+    """The stitched rows of search.py:195-240 from the device's join (Context.match_positions): hit row r = (qid[r], tid[r])
+    owns the (query start, target start) pairs [row_offsets[r], row_offsets[r + 1]), ordered by (query start, target start) —
+    the order `stitch_hits` reaches by sorting on start_query.  The k-mer strings are sliced from the records; the stitcher's
+    quirks (`single_stitch_together_kmers`) apply unchanged.  The device joins on the 64-bit hash alone, the reference on
+    (encoded, hashval): the encoded k-mers of every pair are asserted equal here.
+
+    One row per match_name comes out while all hits belong to ONE query, as the reference's group_by("match_name") gives it
+    (the case its tests pin).  With several queries the reference would mix the k-mers of different queries that hit the same
+    target into one region; here the rows are grouped by (query, match) then."""
+    qid = np.asarray(qid).tolist(); tid = np.asarray(tid).tolist()
+    offs = np.asarray(row_offsets).tolist()
+    qs_all = np.asarray(q_start).tolist(); ts_all = np.asarray(t_start).tolist()
+    single_query = len(set(qid)) <= 1
+    groups = {}
+    for r, (q, t) in enumerate(zip(qid, tid)):
+        qn, qseq = q_records[q]
+        tn, tseq = t_records[t]
+        rows = groups.setdefault(tn if single_query else (qn, tn), [])
+        for a, b in zip(qs_all[offs[r]:offs[r + 1]], ts_all[offs[r]:offs[r + 1]]):
+            kq = qseq[a:a + ksize].decode().upper()
+            kt = tseq[b:b + ksize].decode().upper()
+            enc = encode_kmer(kq, moltype)
+            assert enc == encode_kmer(kt, moltype), f"hash collision: {kq} ({qn} at {a}) and {kt} ({tn} at {b}) share a hash"
+            rows.append({"query_name": qn, "match_name": tn, "kmer_query": kq, "kmer_match": kt, "encoded": enc,
+                         "start_query": a, "start_match": b})
+    out = []
+    for rows in groups.values():
+        rows.sort(key=lambda r: r["start_query"])  # (already so inside a hit row; a stable merge where hit rows share a group)
+        match_name = rows[0]["match_name"]
+        # search.py:79-81: the query k-mers are stitched with the MATCH positions (as the reference does)
+        query = single_stitch_together_kmers([r["kmer_query"] for r in rows], [r["start_match"] for r in rows])
+        alpha = single_stitch_together_kmers([r["encoded"] for r in rows], [r["start_query"] for r in rows])
+        match = single_stitch_together_kmers([r["kmer_match"] for r in rows], [r["start_match"] for r in rows])
+        assert len(query) == len(alpha) == len(match)
+        length = len(query)
+        ms = min(r["start_match"] for r in rows)
+        qs = min(r["start_query"] for r in rows)
+        qn = rows[0]["query_name"]
+        out.append({"match_name": match_name, "query_name": qn, "query_start": qs, "query_end": qs + length,
+                    "query": query, "match_start": ms, "match_end": ms + length, "match": match, "encoded": alpha,
+                    "length": length,
+                    "to_print": f"\n---\nQuery Name: {qn}\nMatch Name: {match_name}\nquery: {query} ({qs}-{qs + length})\n"
+                                f"alpha: {alpha}\nmatch: {match} ({ms}-{ms + length})"})
+    out.sort(key=lambda r: (r["query_start"], r["query_end"]))
+    return out
+
+
+def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int, scaled: int, moltype: str,
+                                ctx: Optional[Context] = None) -> List[dict]:
+    """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
+    tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
+    Same rows as `search_extract_kmers`."""
+    own = ctx is None
+    ctx = ctx or Context(0)
+    try:
+        from .engine import pack
+        q_recs, t_recs = read_fasta(query_fasta), read_fasta(target_fasta)
+        q_res, q_off = pack([s for _, s in q_recs])
+        t_res, t_off = pack([s for _, s in t_recs])
+        Q = ctx.sketch_batch(q_res, q_off, ksize, scaled, moltype)
+        T = ctx.sketch_batch(t_res, t_off, ksize, scaled, moltype)
+        hits = ctx.search(ctx.index_build(T), Q)
+        qp = ctx.kmer_positions_table(q_res, q_off, ksize, scaled, moltype)
+        tp = ctx.kmer_positions_table(t_res, t_off, ksize, scaled, moltype)
+        mp = ctx.match_positions(qp, tp, hits)
+        qid, tid, _, _ = hits.to_host()
+        offs, qs, ts = mp.to_host()[:3]
+        for o in (mp, qp, tp, hits, Q, T):
+            o.free()
+        return stitch_match_positions(q_recs, t_recs, qid, tid, offs, qs, ts, ksize, moltype)
+    finally:
+        if own:
+            ctx.close()

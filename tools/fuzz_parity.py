@@ -1,12 +1,12 @@
 """Randomised differential test of the HIP path against the oracle (sketch, k-mer positions, search).
 
-    python tools/fuzz_parity.py [--cases N] [--seed S] [--entries] [--knob NAME=VALUE ...]
+    python tools/fuzz_parity.py [--cases N] [--seed S] [--entries] [--matchpos] [--knob NAME=VALUE ...]
 
 Every case draws k, scaled, moltype, a length distribution (peptides / proteome-like / long / degenerate), an alphabet
 (full, 2-letter, single residue, with ambiguity codes and lower case) and a batch size, sketches it through the C ABI and
 compares with the oracle bit for bit; every third case also builds an index and searches it.  Prints one line per failure.
 With --entries every case also goes through ks_sketch_batch_device, and the one-call search takes, with a hint of 0, the exact
-longest sequence or more.  --knob sets a KS_DEBUG_* knob around every case (the context follows the environment).
+longest sequence or more.  --matchpos runs match-position cases instead (run_matchpos).  --knob sets a KS_DEBUG_* knob around every case (the context follows the environment).
 """
 import argparse
 import contextlib
@@ -196,6 +196,97 @@ def _case(ctx, rng, erng, case, k, scaled, mol, res, offs, tag, entries) -> int:
     return 0
 
 
+def _join_tables(q_tab, t_tab, hit_qid, hit_tid, ksize):
+    """numpy restatement of ks_match_positions on host copies of the two k-mer tables: (row_offsets, q_start, t_start, q_lo,
+    q_hi, t_lo, t_hi) for the hit rows (qid, tid), pairs ordered by (row, query start, target start)."""
+    (q_seq, q_start, q_hash), (t_seq, t_start, t_hash) = q_tab, t_tab
+    n_rows = len(hit_qid)
+    order = np.argsort(t_hash, kind="stable")
+    th = t_hash[order]
+    lo = np.searchsorted(th, q_hash, side="left").astype(np.int64)
+    cnt = np.searchsorted(th, q_hash, side="right").astype(np.int64) - lo
+    qi = np.repeat(np.arange(len(q_hash), dtype=np.int64), cnt)
+    ti = order[np.repeat(lo, cnt) + (np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt))]
+    pair_key = (q_seq[qi].astype(np.uint64) << np.uint64(32)) | t_seq[ti].astype(np.uint64)
+    hit_key = (hit_qid.astype(np.uint64) << np.uint64(32)) | hit_tid.astype(np.uint64)
+    row = np.searchsorted(hit_key, pair_key)
+    found = (row < n_rows) & (hit_key[np.minimum(row, max(n_rows - 1, 0))] == pair_key) if n_rows else np.zeros(len(qi), bool)
+    row, a, b = row[found], q_start[qi][found], t_start[ti][found]
+    o = np.lexsort((b, a, row))
+    row, a, b = row[o], a[o].astype(np.uint32), b[o].astype(np.uint32)
+    offs = np.zeros(n_rows + 1, np.uint64)
+    offs[1:] = np.cumsum(np.bincount(row, minlength=n_rows))
+    first, last = offs[:-1].astype(np.int64), offs[1:].astype(np.int64) - 1
+    if n_rows == 0 or len(a) == 0 or np.any(last < first):
+        return offs, a, b, None
+    ext = (a[first], a[last] + np.uint32(ksize), np.minimum.reduceat(b, first), np.maximum.reduceat(b, first) + np.uint32(ksize))
+    return offs, a, b, ext
+
+
+MATCHPOS_MAX_PAIRS = 4_000_000  # low-complexity batches join into far more: those cases check the refusal instead
+
+
+def run_matchpos(cases: int, seed: int, knobs=None) -> int:
+    """Match-position cases: a target batch, a query batch that overlaps it, search (every other case thresholded), the two
+    k-mer tables, ks_match_positions with max_pairs = MATCHPOS_MAX_PAIRS — compared with a numpy join of the host copies of the
+    same tables and hits (which the other cases hold against the oracle).  A join beyond the limit must be refused with
+    KS_ERR_CAPACITY and the count.  Returns the number of failures."""
+    from kmerseek_amd import _lib
+    rng = np.random.default_rng(seed)
+    knobs = knobs or {}
+    bad = n_refused = 0
+    ctx = ks.Context(0, follow_debug_env=True)
+    for case in range(cases):
+        k = int(rng.choice([3, 5, 7, 8, 10, 15, 16, 17, 21, 24, 32, 48]))
+        scaled = int(rng.choice([1, 1, 1, 2, 5, 10]))
+        mol = str(rng.choice(["protein", "dayhoff", "hp"]))
+        t_res, t_off = draw_batch(rng)
+        q_res, q_off = draw_batch(rng)
+        if len(t_off) > 2:  # the queries overlap the targets
+            cut = int(t_off[len(t_off) // 2])
+            q_res = np.concatenate([t_res[:cut], q_res]).astype(np.uint8)
+            q_off = np.concatenate([t_off[:len(t_off) // 2], q_off + np.uint64(cut)]).astype(np.uint64)
+        min_c = 0.0 if case % 2 == 0 else float(rng.choice([0.05, 0.3, 0.8]))
+        tag = f"matchpos case {case}: k={k} scaled={scaled} {mol} n_t={len(t_off) - 1} n_q={len(q_off) - 1} min_containment={min_c}"
+        try:
+            with knobs_set(knobs):
+                T = ctx.sketch_batch(t_res, t_off, k, scaled, mol)
+                Q = ctx.sketch_batch(q_res, q_off, k, scaled, mol)
+                hits = ctx.search(ctx.index_build(T), Q, min_containment=min_c)
+                qp = ctx.kmer_positions_table(q_res, q_off, k, scaled, mol)
+                tp = ctx.kmer_positions_table(t_res, t_off, k, scaled, mol)
+                q_tab, t_tab = qp.to_host(), tp.to_host()
+                n_join = int(np.sum(np.searchsorted(np.sort(t_tab[2]), q_tab[2], side="right") -
+                                    np.searchsorted(np.sort(t_tab[2]), q_tab[2], side="left")))
+                in_use = ctx.pool_stats()["bytes_in_use"]
+                try:
+                    mp = ctx.match_positions(qp, tp, hits, max_pairs=MATCHPOS_MAX_PAIRS)
+                except ks.KmerseekError as e:
+                    if hits.count and n_join > MATCHPOS_MAX_PAIRS and e.status == _lib.KS_ERR_CAPACITY and str(n_join) in str(e) \
+                            and ctx.pool_stats()["bytes_in_use"] == in_use:
+                        n_refused += 1
+                        continue
+                    raise
+                if hits.count and n_join > MATCHPOS_MAX_PAIRS:
+                    print("MATCHPOS NOT REFUSED", tag, f"join={n_join}"); bad += 1; continue
+                got = mp.to_host()
+            qid, tid, isect, _ = hits.to_host()
+            offs, a, b, ext = _join_tables(q_tab, t_tab, qid, tid, k)
+            ok = np.array_equal(got[0], offs) and np.array_equal(got[1], a) and np.array_equal(got[2], b) and \
+                np.all((offs[1:] - offs[:-1]) >= isect)
+            if ok and len(qid):
+                ok = ext is not None and all(np.array_equal(g, w) for g, w in zip(got[3:], ext))
+            if not ok:
+                print("MATCHPOS MISMATCH", tag, f"rows={len(qid)} pairs={len(got[1])}/{len(a)} slices={mp.n_slices}"); bad += 1
+            for o in (mp, qp, tp, hits, Q, T):
+                o.free()
+        except Exception as e:  # noqa: BLE001
+            print("ERROR", tag, repr(e)); bad += 1
+    ctx.close()
+    print(f"matchpos: {n_refused} of {cases} cases refused by max_pairs")
+    return bad
+
+
 def run_big(cases: int, seed: int) -> int:
     """Batches of 5k-60k proteins (many tiles, look-back chains, full partition paths): sketch vs oracle; search by the
     fused path (postings from the sketch kernel) vs the plain path, and partitioned vs LSD index build — GPU vs GPU,
@@ -274,10 +365,14 @@ def main():
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--big", action="store_true", help="few large batches instead of many small ones")
     ap.add_argument("--entries", action="store_true", help="also ks_sketch_batch_device, and random hints for the one-call search")
+    ap.add_argument("--matchpos", action="store_true", help="match-position cases (ks_match_positions against a numpy join)")
     ap.add_argument("--knob", action="append", default=[], help="NAME=VALUE: KS_DEBUG_NAME around every case (repeatable)")
     a = ap.parse_args()
     knobs = dict(kv.split("=", 1) for kv in a.knob)
-    bad = run_big(a.cases, a.seed) if a.big else run(a.cases, a.seed, knobs=knobs, entries=a.entries)
+    if a.matchpos:
+        bad = run_matchpos(a.cases, a.seed, knobs=knobs)
+    else:
+        bad = run_big(a.cases, a.seed) if a.big else run(a.cases, a.seed, knobs=knobs, entries=a.entries)
     print(f"{a.cases} cases, {bad} failures")
     sys.exit(1 if bad else 0)
 

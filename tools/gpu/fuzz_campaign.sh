@@ -1,12 +1,12 @@
 # Differential fuzz campaign (tools/fuzz_parity.py against the oracle) over the forced-path configurations.  R = round tag of the
-# logs; PART=1 / PART=2 run half of it (one gpurun call holds ~20 minutes).
+# logs; PART=1 / PART=2 run half of it (one call holds ~20 minutes), PART=3 only the match-position lines.
 R=${R:-r4}
 PART=${PART:-0}
 CASES=${CASES:-350}
 OFS=${OFS:-0}   # added to every seed: a fresh campaign
 mkdir -p gpurun_out
 run() { name=$1; shift; env "$@" timeout -k 10 500 python tools/fuzz_parity.py --cases $CASES --seed $((SEED + OFS)) > gpurun_out/${R}_fz_$name.log 2>&1; echo "$name rc=$? $(tail -1 gpurun_out/${R}_fz_$name.log)"; }
-if [ "$PART" != 2 ]; then
+if [ "$PART" != 2 ] && [ "$PART" != 3 ]; then
 SEED=301 run default A=1
 SEED=315 run key_columns KS_DEBUG_JOIN_FP=0
 SEED=318 run key_columns_split KS_DEBUG_JOIN_FP=0 KS_DEBUG_JOIN_SPLIT=3
@@ -18,7 +18,7 @@ SEED=306 run rows_ticket_planless KS_DEBUG_ROWS_TICKET=1 KS_DEBUG_NO_PLAN=1
 SEED=307 run nocompact_nopack KS_DEBUG_NO_COMPACT=1 KS_DEBUG_NO_PACK=1
 SEED=308 run lsd_paths KS_DEBUG_PAIRS_LSD=1 KS_DEBUG_INDEX_LSD=1
 fi
-if [ "$PART" != 1 ]; then
+if [ "$PART" != 1 ] && [ "$PART" != 3 ]; then
 SEED=310 run full_lists KS_DEBUG_QCAP=2
 SEED=311 run nopack KS_DEBUG_NO_PACK=1
 SEED=312 run nopack_full_lists KS_DEBUG_NO_PACK=1 KS_DEBUG_QCAP=1
@@ -31,4 +31,15 @@ SEED=316 KS_DEBUG_JOIN_FP=1 KS_DEBUG_JOIN_SEGS=1 timeout -k 10 500 python tools/
 # ... and against indexes joined on 16 prefix bits (forced: KS_DEBUG_BUCKET): 9-byte postings behind the bucket scatter, both joins
 SEED=319 KS_DEBUG_JOIN_FP=1 KS_DEBUG_BUCKET=64 KS_DEBUG_JOIN_SPARSE=0 timeout -k 10 500 python tools/fuzz_parity.py --big --cases 12 --seed $((319 + OFS)) > gpurun_out/${R}_fz_big_nine_staged.log 2>&1; echo "big_nine_staged rc=$? $(tail -1 gpurun_out/${R}_fz_big_nine_staged.log)"
 SEED=320 KS_DEBUG_JOIN_FP=1 KS_DEBUG_BUCKET=64 KS_DEBUG_JOIN_SPARSE=1 timeout -k 10 500 python tools/fuzz_parity.py --big --cases 12 --seed $((320 + OFS)) > gpurun_out/${R}_fz_big_nine_sparse.log 2>&1; echo "big_nine_sparse rc=$? $(tail -1 gpurun_out/${R}_fz_big_nine_sparse.log)"
+fi
+if [ "$PART" != 1 ] && [ "$PART" != 2 ]; then
+# matchpos: ks_match_positions against a numpy join of the same tables — plain, with the hit rows forced into slices, and with the
+# LSD sorts (MCASES cases each; every other case searches with a containment threshold)
+MCASES=${MCASES:-120}
+LOGS=${LOGS:-bench_out}   # where these lines keep their logs
+mkdir -p "$LOGS"
+mrun() { name=$1; shift; env "$@" timeout -k 10 400 python tools/fuzz_parity.py --matchpos --cases $MCASES --seed $((SEED + OFS)) > $LOGS/${R}_fz_$name.log 2>&1; echo "$name rc=$? $(tail -1 $LOGS/${R}_fz_$name.log)"; }
+SEED=330 mrun matchpos A=1
+SEED=331 mrun matchpos_slices KS_DEBUG_MATCHPOS_ROW_BITS=4
+SEED=332 mrun matchpos_lsd KS_DEBUG_PAIRS_LSD=1 KS_DEBUG_SCAN_3PASS=1
 fi
