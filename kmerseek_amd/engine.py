@@ -430,6 +430,18 @@ class DeviceBuffer:
     def ptr(self) -> int:
         return int(self._p.value or 0)
 
+    def to_host(self, dtype, count: Optional[int] = None) -> np.ndarray:
+        """The first `count` items of `dtype` (default: the whole buffer) as a host array (ks_dev_download: ordered behind the
+        work queued on the context's stream, returns when the copy is done)."""
+        dt = np.dtype(dtype)
+        n = self.nbytes // dt.itemsize if count is None else int(count)
+        if n * dt.itemsize > self.nbytes:
+            raise ValueError(f"{n} x {dt} does not fit a buffer of {self.nbytes} bytes")
+        out = np.empty(n, dt)
+        if n:
+            self._ctx._check(self._ctx._L.ks_dev_download(self._ctx._h, _ptr(out), self._p, out.nbytes))
+        return out
+
     def free(self):
         if self._p is not None and self._ctx._h:
             self._ctx._L.ks_dev_free(self._ctx._h, self._p)

@@ -12,6 +12,7 @@
 import csv
 import math
 import os
+import sys
 
 import numpy as np
 import pytest
@@ -21,6 +22,9 @@ pytestmark = pytest.mark.gpu
 import kmerseek_amd as ks
 from kmerseek_amd import host, synth
 from oracle import oracle
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from crafted_sketches import keep as _keep, replica as _replica  # noqa: E402  (the host's row loop and keep test live there)
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 PROTEIN = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", np.uint8)
@@ -94,23 +98,6 @@ def _sketches(res, offs, k, scaled, mol):
     return o, m, a
 
 
-def _replica(q_mins, t_mins, t_ab):
-    """ks_host.cpp's row loop before the statistics moved to the device: the shared target abundances, sorted, then
-    sequential f64 sums.  (Python floats are IEEE doubles; no contraction.)"""
-    _, _, ti = np.intersect1d(q_mins, t_mins, assume_unique=True, return_indices=True)
-    shared = sorted(float(x) for x in t_ab[ti])
-    n = len(shared)
-    s = 0.0
-    for x in shared:
-        s += x
-    mean = s / float(n)
-    ss = 0.0
-    for x in shared:
-        ss += (x - mean) * (x - mean)
-    median = shared[n // 2] if n % 2 else (shared[n // 2 - 1] + shared[n // 2]) / 2.0
-    return n, mean, median, ss
-
-
 def _run(ctx, entry, ix, q_res, q_offs, k, scaled, mol, **kw):
     """The rows ((qid, tid, isect, nw), Hits) of one entry point."""
     if entry == "search":
@@ -154,13 +141,6 @@ def _check_stats(rows, H, qs, ts, label, n_oracle=40):
         assert math.isclose(math.sqrt(ss[r] / n), w["std_abund"], rel_tol=1e-12, abs_tol=1e-300), (label, r)
         assert math.isclose(float(nw[r]) / n, w["average_abund"], rel_tol=1e-12), (label, r)
     return median2, ss
-
-
-def _keep(rows, qs, thr):
-    qo = qs[0]
-    qsize = (qo[1:] - qo[:-1]).astype(np.float64)
-    c = rows[2].astype(np.float64) / qsize[rows[0].astype(np.int64)]
-    return c >= thr
 
 
 def _eq_rows(got, want, label):

@@ -1,12 +1,13 @@
 """Randomised differential test of the HIP path against the oracle (sketch, k-mer positions, search).
 
-    python tools/fuzz_parity.py [--cases N] [--seed S] [--entries] [--matchpos] [--knob NAME=VALUE ...]
+    python tools/fuzz_parity.py [--cases N] [--seed S] [--entries] [--matchpos] [--crafted] [--knob NAME=VALUE ...]
 
 Every case draws k, scaled, moltype, a length distribution (peptides / proteome-like / long / degenerate), an alphabet
 (full, 2-letter, single residue, with ambiguity codes and lower case) and a batch size, sketches it through the C ABI and
 compares with the oracle bit for bit; every third case also builds an index and searches it.  Prints one line per failure.
 With --entries every case also goes through ks_sketch_batch_device, and the one-call search takes, with a hint of 0, the exact
-longest sequence or more.  --matchpos runs match-position cases instead (run_matchpos).  --knob sets a KS_DEBUG_* knob around every case (the context follows the environment).
+longest sequence or more.  --matchpos runs match-position cases instead (run_matchpos), --crafted hand-made
+sketches on the edges of the search arithmetic (run_crafted: no residues, no oracle — numpy references).  --knob sets a KS_DEBUG_* knob around every case (the context follows the environment).
 """
 import argparse
 import contextlib
@@ -287,6 +288,89 @@ def run_matchpos(cases: int, seed: int, knobs=None) -> int:
     return bad
 
 
+def run_crafted(cases: int, seed: int, knobs=None) -> int:
+    """Hand-made sketches (ks_sketches_from_host) instead of residues: random mixtures of the ingredients of
+    tests/crafted_sketches.py — hashes on both sides of join-bucket boundaries, clusters that share their prefix, 1 and
+    max_hash, abundances from the edge set (0 .. 2^32 - 1) — with at most 400 targets and 400 queries.  Search rows, matched
+    pairs, the per-row statistics, one containment threshold and the union are compared with the numpy / Python references
+    there.  Returns the number of failures."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import crafted_sketches as cs
+    rng = np.random.default_rng([seed, 2])
+    knobs = knobs or {}
+    bad = 0
+    ctx = ks.Context(0, follow_debug_env=True)
+    try:
+        for case in range(cases):
+            bad += _crafted_case(ctx, cs, rng, case, knobs)
+    finally:
+        ctx.close()
+    return bad
+
+
+def _crafted_case(ctx, cs, rng, case, knobs) -> int:
+    """One case of run_crafted(): 0 if it matches the references, 1 otherwise (with one line printed)."""
+    scaled = int(rng.choice([1, 1, 3, 5, 1000, cs.U32_MAX]))
+    mh = cs.max_hash(scaled)
+    n_t, n_q = int(rng.integers(1, 401)), int(rng.integers(1, 401))
+    pool = [1, mh, mh - 1]
+    for pbits in rng.choice(cs.PBITS_EDGES, 2, replace=False).tolist():
+        K = cs.prefix_mul(pbits, mh)
+        top = cs.join_prefix(mh, K)
+        for b in (rng.integers(1, top + 1, 150).tolist() if top else []):
+            w = ((b << 32) + K - 1) // K
+            pool += [x for x in ((w << 32) - 1, w << 32) if 0 < x <= mh]
+    for _ in range(int(rng.integers(1, 5))):  # clusters: equal prefixes, equal fingerprints, consecutive values
+        base, width = int(rng.integers(1, mh, dtype=np.uint64, endpoint=True)), 1 << int(rng.integers(1, 34))
+        pool += [min(base + int(x), mh) for x in rng.integers(0, width, int(rng.integers(20, 400)))]
+    pool += rng.integers(1, mh, 200, dtype=np.uint64, endpoint=True).tolist()
+    pool = np.array(sorted(set(pool)), np.uint64)
+    edges = np.asarray(cs.ABUND_EDGES if rng.random() < 0.85 else (0,), np.uint32)
+    tag = f"crafted case {case}: scaled={scaled} n_t={n_t} n_q={n_q} hashes={len(pool)} abundances={'edges' if len(edges) > 1 else '0'}"
+    held = []
+    try:
+        in_t = pool[rng.random(len(pool)) < 0.8]
+        in_q = np.concatenate([in_t[rng.random(len(in_t)) < 0.6], pool[rng.random(len(pool)) < 0.25]])
+        ct, cq = int(rng.integers(1, 5)), int(rng.integers(1, 4))
+        th, qh = np.tile(in_t, ct), np.tile(in_q, cq)
+        T = cs._csr(rng.integers(0, n_t, len(th)), th, rng.choice(edges, len(th)), n_t)
+        Q = cs._csr(rng.integers(0, n_q, len(qh)), qh, np.ones(len(qh)), n_q)
+        cs.check_valid(T, scaled); cs.check_valid(Q, scaled)
+        rows = cs.ref_join(T, Q)
+        assert int(rows[2].sum()) < cs.PAIR_BOUND
+        thr = float(rng.choice([1e-300, 0.05, 0.5, 1.0]))
+        sel = cs.keep(rows, Q, thr)
+        with knobs_set(knobs):
+            dT = ctx.sketches_from_host(*T, 10, scaled, "protein"); held.append(dT)
+            dQ = ctx.sketches_from_host(*Q, 10, scaled, "protein"); held.append(dQ)
+            ix = ctx.index_build(dT); held.append(ix)
+            H = ctx.search(ix, dQ, abund_stats=True); held.append(H)
+            got, (m2, ss) = H.to_host(), H.abund_stats_to_host()
+            pairs = H.n_pair_instances
+            Hp = ctx.search(ix, dQ); held.append(Hp)
+            plain = Hp.to_host()
+            Hk = ctx.search(ix, dQ, min_containment=thr); held.append(Hk)
+            kept = Hk.to_host()
+            U = dT.union(); held.append(U)
+            union = U.to_host()
+        if not (all(np.array_equal(g, w) for g, w in zip(got, rows)) and all(np.array_equal(g, w) for g, w in zip(plain, rows))
+                and pairs == int(rows[2].sum())):
+            print("CRAFTED SEARCH MISMATCH", tag, f"hits={len(got[0])}/{len(rows[0])} pairs={pairs}/{int(rows[2].sum())}"); return 1
+        want_m2, want_ss = cs.ref_stats(rows, T, Q)
+        if not (np.array_equal(m2, want_m2) and np.array_equal(ss.view(np.uint64), want_ss.view(np.uint64))):
+            print("CRAFTED STATISTICS MISMATCH", tag); return 1
+        if not all(np.array_equal(g, w[sel]) for g, w in zip(kept, rows)):
+            print("CRAFTED THRESHOLD MISMATCH", tag, f"min_containment={thr}"); return 1
+        if not all(np.array_equal(g, w) for g, w in zip(union, cs.ref_union(T))):
+            print("CRAFTED UNION MISMATCH", tag); return 1
+    except Exception as e:  # noqa: BLE001
+        print("ERROR", tag, repr(e)); return 1
+    finally:
+        for o in reversed(held):  # (device objects of the case, on every path)
+            o.free()
+    return 0
+
+
 def run_big(cases: int, seed: int) -> int:
     """Batches of 5k-60k proteins (many tiles, look-back chains, full partition paths): sketch vs oracle; search by the
     fused path (postings from the sketch kernel) vs the plain path, and partitioned vs LSD index build — GPU vs GPU,
@@ -366,11 +450,14 @@ def main():
     ap.add_argument("--big", action="store_true", help="few large batches instead of many small ones")
     ap.add_argument("--entries", action="store_true", help="also ks_sketch_batch_device, and random hints for the one-call search")
     ap.add_argument("--matchpos", action="store_true", help="match-position cases (ks_match_positions against a numpy join)")
+    ap.add_argument("--crafted", action="store_true", help="hand-made sketches on the edges of the search arithmetic (numpy references)")
     ap.add_argument("--knob", action="append", default=[], help="NAME=VALUE: KS_DEBUG_NAME around every case (repeatable)")
     a = ap.parse_args()
     knobs = dict(kv.split("=", 1) for kv in a.knob)
     if a.matchpos:
         bad = run_matchpos(a.cases, a.seed, knobs=knobs)
+    elif a.crafted:
+        bad = run_crafted(a.cases, a.seed, knobs=knobs)
     else:
         bad = run_big(a.cases, a.seed) if a.big else run(a.cases, a.seed, knobs=knobs, entries=a.entries)
     print(f"{a.cases} cases, {bad} failures")
