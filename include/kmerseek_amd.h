@@ -379,6 +379,55 @@ int ks_matchpos_copy_to_host(ks_ctx *ctx, const ks_matchpos *m, uint64_t *row_of
                              uint32_t *q_lo, uint32_t *q_hi, uint32_t *t_lo, uint32_t *t_hi);
 void ks_matchpos_free(ks_matchpos *m);
 
+/* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
+
+/* Replaces the two sums behind the columns that branchwater multisearch adds with "calculate probability of overlap between
+ * target and query" switched on (src/python/kmerseek/search.py:144-158): prob_overlap and tf_idf_score.
+ *
+ * Corpus table of a sketch set S, one entry per distinct hash h of S, ascending:
+ *   abund_sum(h) u64  the abundances of h summed over the sketches that hold it — exact, no saturation (ks_sketches_union
+ *                     saturates at 2^32 - 1; this does not)
+ *   doc_freq(h)  u32  the number of sketches that hold h
+ *   total(S)     u64  all abundances of S summed
+ * n_docs counts every sketch of the set, empty ones included. */
+typedef struct ks_corpus ks_corpus;
+int ks_corpus_build(ks_ctx *ctx, const ks_sketches *sketches, ks_corpus **out);
+uint64_t ks_corpus_n_hashes(const ks_corpus *c);
+uint32_t ks_corpus_n_docs(const ks_corpus *c);
+uint64_t ks_corpus_total_abund(const ks_corpus *c);
+/* any destination may be NULL */
+int ks_corpus_copy_to_host(ks_ctx *ctx, const ks_corpus *c, uint64_t *hashes, uint64_t *abund_sum, uint32_t *doc_freq);
+void ks_corpus_free(ks_corpus *c);
+
+/* Per row r = (q, t) of `hits`, over the hashes q and t share, in ascending hash order, starting from 0.0:
+ *   prob_overlap[r] += ((double)abund_sum_Q(h) / (double)total(Q)) * ((double)abund_sum_T(h) / (double)total(T))
+ *   tf_idf[r]       += ((double)abund_q(h) / (double)(sum of q's abundances)) * idf[doc_freq_T(h)]
+ *   idf[d] = log(((double)1 + n_targets) / ((double)1 + d)) + 1.0      natural log, evaluated on the host (libm) and uploaded
+ * in IEEE f64, every operation rounded on its own (no fma contraction, no reassociation): bit-identical to a host loop that
+ * does the same.  The columns derived from them stay with the caller (kmerseek_amd/wire.py):
+ *   prob_overlap_adjusted = prob_overlap * (double)(n_queries * n_targets);
+ *   containment_adjusted = ((double)intersect / (double)|q|) / prob_overlap_adjusted, and its log10.
+ * queries / targets: the sets `hits` was searched on, made with the same ks_params; q_corpus / t_corpus: their corpus tables
+ * (n_docs must equal the set's sequence count); hits: from any search entry, thresholded ones included.  The row pass counts
+ * the shared hashes it adds: a count that is not the row's intersect, or an id beyond a set, means the inputs do not belong
+ * together — KS_ERR_INVALID_ARG, and ks_last_error names the first such row.  A query whose abundances sum to 0 (or a set
+ * whose total is 0) divides 0 by 0: its rows hold NaN.  One stream, synchronous on return; scratch comes from the pool. */
+typedef struct ks_signif ks_signif;
+typedef struct ks_signif_opts {
+    uint32_t flags;    /* none defined: 0 */
+    uint32_t reserved; /* 0 */
+} ks_signif_opts;
+/* opts == NULL: the defaults.  Options are checked before any device work. */
+int ks_hits_significance(ks_ctx *ctx, const ks_sketches *queries, const ks_sketches *targets, const ks_corpus *q_corpus,
+                         const ks_corpus *t_corpus, const ks_hits *hits, const ks_signif_opts *opts, ks_signif **out);
+uint64_t ks_signif_n_rows(const ks_signif *s);
+/* device columns (ks_signif_n_rows entries, valid until ks_signif_free) */
+const double *ks_signif_device_prob_overlap(const ks_signif *s);
+const double *ks_signif_device_tf_idf(const ks_signif *s);
+/* either destination may be NULL */
+int ks_signif_copy_to_host(ks_ctx *ctx, const ks_signif *s, double *prob_overlap, double *tf_idf);
+void ks_signif_free(ks_signif *s);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Per-kernel HIP-event timing on ctx's stream.  enable: 0 off; 1 events bracket every launch (~20 us of idle queue

@@ -48,6 +48,10 @@ class ks_matchpos_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("max_pairs", C.c_uint64)]
 
 
+class ks_signif_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ks_kernel_time(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -147,6 +151,18 @@ SIGNATURES = {
     "ks_matchpos_device_t_hi": (_vp, [_vp]),
     "ks_matchpos_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ks_matchpos_free": (None, [_vp]),
+    "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
+    "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
+    "ks_corpus_n_docs": (C.c_uint32, [_vp]),
+    "ks_corpus_total_abund": (C.c_uint64, [_vp]),
+    "ks_corpus_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
+    "ks_corpus_free": (None, [_vp]),
+    "ks_hits_significance": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ks_signif_opts), _pp]),
+    "ks_signif_n_rows": (C.c_uint64, [_vp]),
+    "ks_signif_device_prob_overlap": (_vp, [_vp]),
+    "ks_signif_device_tf_idf": (_vp, [_vp]),
+    "ks_signif_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ks_signif_free": (None, [_vp]),
     "ks_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ks_timing_reset": (C.c_int, [_vp]),
     "ks_timing_get": (C.c_int, [_vp, C.POINTER(ks_kernel_time), C.c_uint32, _u32p]),

@@ -1,0 +1,412 @@
+// ks_signif.hip — ks_corpus_build / ks_hits_significance: does a hit's overlap mean anything?  Per hit row (qid, tid) the two
+// sums that branchwater multisearch prints as prob_overlap and tf_idf_score (src/python/kmerseek/search.py:144-158,
+// "calculate probability of overlap between target and query" switched on), over the hashes the two sketches share, in
+// ascending hash order, starting from 0.0:
+//     prob_overlap += ((double)abund_sum_Q(h) / (double)total(Q)) * ((double)abund_sum_T(h) / (double)total(T))
+//     tf_idf       += ((double)abund_q(h) / (double)sum of q's abundances) * idf[doc_freq_T(h)]
+// IEEE f64, one rounding per operation (no contraction into fma), no reassociation: bit-identical to a host loop that does
+// the same.  idf[] is made on the host with libm's log and uploaded — the device never evaluates a logarithm.
+//
+//   corpus   per sketch set, once: the hashes sorted (the union's sort), one run-length pass -> per distinct hash its abundance
+//            sum (u64, exact), the number of sketches that hold it, and the set's grand total
+//   weights  one pass over the query CSR (a wave per query): the query's abundance sum, then per posting both corpus tables
+//            searched and the two products stored as f64 (pw, tw) — a row only adds
+//   rows     hit rows are ordered by (qid, tid).  A lane per short row walks the shorter run and searches the longer one from
+//            where the last search ended; a row with |q| + |t| above SG_CUT is listed for k_sg_rows_wave, where the lanes of
+//            one wave take 64 consecutive hashes of the shorter run, a ballot marks the shared ones, and their terms are added
+//            serially in lane order through readlane (every lane keeps the same sums).  No f64 atomics, no tree reductions.
+// The row pass counts what it adds: a count that is not the row's intersect means hits, sketches and corpora do not belong
+// together (KS_ERR_INVALID_ARG; ks_last_error names the first such row).
+#include <cmath>
+
+#include "ks_device.h"
+
+#define SG_CUT 128        // |q| + |t| above this: the wave path (KS_DEBUG_SIGNIF_WAVE_ROWS = 1 / 0 sends every row one way)
+#define SG_WAVE_GRID 1024 // workgroups of k_sg_rows_wave (4 waves each, striding over the listed rows)
+enum { SG_BAD_ID = 0, SG_BAD_COUNT = 1, SG_BAD_CORPUS = 2 }; // words of the control block
+
+// the run boundaries of a sorted key list, as the union takes them (ks_search.hip)
+__global__ __launch_bounds__(256) void k_pair_heads(const u64 *keys, u64 n, u32 *heads);
+__global__ __launch_bounds__(256) void k_pair_rows(const u64 *keys, const u32 *hidx, u64 n, u32 n_rows, u64 *row_start);
+
+struct ks_corpus {
+    ks_ctx *ctx;
+    ks_params params;
+    u32 n_docs;      // sketches of the set, empty ones included
+    u64 n_postings;  // (hash, sketch) pairs of the set: what it was built from
+    u64 n_hashes;    // distinct hashes
+    u64 total;       // sum of all abundances
+    u32 max_doc_freq;
+    u64 *d_hash, *d_sum;
+    u32 *d_df;
+};
+
+struct ks_signif {
+    ks_ctx *ctx;
+    u64 n_rows;
+    double *d_prob, *d_tfidf;
+};
+
+// ---- corpus ----------------------------------------------------------------------------------------------------------------
+// acc[0] += the abundances of the whole set, acc[1] = the largest doc_freq (both exact: integer atomics, one per wave)
+__global__ __launch_bounds__(256) void k_corpus_emit(const u64 *keys, const u32 *vals, const u64 *row_start, u32 n_rows, u64 *hashes,
+                                                     u64 *sums, u32 *df, unsigned long long *acc) {
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x; // (no early return: the wave sum takes all 64 lanes)
+    u64 w = 0;
+    u32 d = 0;
+    if (r < n_rows) {
+        const u64 b = row_start[r], e = row_start[r + 1];
+        for (u64 j = b; j < e; j++) w += vals[j];
+        d = (u32)(e - b); // a sketch holds a hash once: postings of the run = sketches that hold it
+        hashes[r] = keys[b]; sums[r] = w; df[r] = d;
+    }
+    const u64 ws = ks_wave_sum64(w);
+#pragma unroll
+    for (int s = 32; s; s >>= 1) { const u32 o = (u32)__shfl_xor((int)d, s); d = o > d ? o : d; }
+    if ((threadIdx.x & 63) == 0) {
+        if (ws) atomicAdd(&acc[0], (unsigned long long)ws);
+        atomicMax(&acc[1], (unsigned long long)d);
+    }
+}
+
+static int corpus_run(ks_ctx *ctx, const ks_sketches *in, ks_corpus *C) {
+    const u64 n = in->n_hashes;
+    if (n == 0) { // no hash anywhere: an empty table, total 0
+        KS_TRY(ks_alloc(ctx, &C->d_hash, 1)); KS_TRY(ks_alloc(ctx, &C->d_sum, 1)); KS_TRY(ks_alloc(ctx, &C->d_df, 1));
+        return KS_OK;
+    }
+    if (n >= 0xfffffff0ULL) return ks_fail(ctx, KS_ERR_CAPACITY, "corpus: %llu postings exceed one sort", (unsigned long long)n);
+    u64 *k0 = nullptr, *k1 = nullptr, *row_start = nullptr, *acc = nullptr;
+    u32 *v0 = nullptr, *v1 = nullptr, *heads = nullptr, *d_nrows = nullptr;
+    ks_scratch sc(ctx);
+    KS_TRY(sc.alloc(&k0, (size_t)n)); KS_TRY(sc.alloc(&k1, (size_t)n));
+    KS_TRY(sc.alloc(&v0, (size_t)n)); KS_TRY(sc.alloc(&v1, (size_t)n));
+    const int shifts[8] = {0, 8, 16, 24, 32, 40, 48, 56};
+    u64 *ks = nullptr;
+    u32 *vs = nullptr;
+    KS_TRY(ks_radix_sort_u32(ctx, KS_SORT_PAIRS, in->d_hashes, in->d_abunds, k0, v0, k1, v1, n, shifts, 8, &ks, &vs));
+    KS_TRY(sc.alloc(&heads, (size_t)n));
+    KS_TRY(sc.alloc(&d_nrows, 1));
+    KS_TRY(sc.alloc(&acc, 2));
+    KS_HIP(ctx, hipMemsetAsync(acc, 0, 2 * sizeof(u64), ctx->stream));
+    const u32 g = (u32)((n + 255) / 256);
+    KS_LAUNCH(ctx, "pair_heads", k_pair_heads, g, 256, (const u64 *)ks, n, heads);
+    KS_TRY(ks_scan_u32_inplace(ctx, heads, n, d_nrows));
+    u64 *const rb = ctx->h_pin + KS_PIN_READ;
+    KS_HIP(ctx, hipMemcpyAsync(rb, d_nrows, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+    KS_TRY(ks_scan_status_fetch(ctx));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KS_TRY(ks_scan_status_check(ctx));
+    const u32 n_rows = *(u32 *)rb;
+    if (n_rows == 0 || n_rows > n) return ks_fail(ctx, KS_ERR_HIP, "internal error: %u runs in %llu sorted postings", n_rows, (unsigned long long)n);
+    C->n_hashes = n_rows;
+    KS_TRY(sc.alloc(&row_start, (size_t)n_rows + 1));
+    KS_TRY(ks_alloc(ctx, &C->d_hash, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &C->d_sum, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &C->d_df, (size_t)n_rows));
+    KS_LAUNCH(ctx, "pair_rows", k_pair_rows, g, 256, (const u64 *)ks, (const u32 *)heads, n, n_rows, row_start);
+    KS_LAUNCH(ctx, "corpus_emit", k_corpus_emit, (n_rows + 255) / 256, 256, (const u64 *)ks, (const u32 *)vs, (const u64 *)row_start, n_rows,
+              C->d_hash, C->d_sum, C->d_df, (unsigned long long *)acc);
+    KS_HIP(ctx, hipMemcpyAsync(rb, acc, 2 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    C->total = rb[0];
+    C->max_doc_freq = (u32)rb[1];
+    return KS_OK;
+}
+
+extern "C" int ks_corpus_build(ks_ctx *ctx, const ks_sketches *sketches, ks_corpus **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!sketches || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (sketches->ctx != ctx) return ks_fail(ctx, KS_ERR_INVALID_ARG, "corpus: sketches of another context");
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(sketches))); // (the sort reads the hashes as one dense array)
+    ks_corpus *C = new ks_corpus();
+    memset(C, 0, sizeof *C);
+    C->ctx = ctx; C->params = sketches->params; C->n_docs = sketches->n_seqs; C->n_postings = sketches->n_hashes;
+    const int st = corpus_run(ctx, sketches, C);
+    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_corpus_free(C); return st; }
+    *out = C;
+    return KS_OK;
+    });
+}
+
+extern "C" uint64_t ks_corpus_n_hashes(const ks_corpus *c) { return c ? c->n_hashes : 0; }
+extern "C" uint32_t ks_corpus_n_docs(const ks_corpus *c) { return c ? c->n_docs : 0; }
+extern "C" uint64_t ks_corpus_total_abund(const ks_corpus *c) { return c ? c->total : 0; }
+
+extern "C" int ks_corpus_copy_to_host(ks_ctx *ctx, const ks_corpus *c, uint64_t *hashes, uint64_t *abund_sum, uint32_t *doc_freq) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !c) return KS_ERR_INVALID_ARG;
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)c->n_hashes;
+    if (n && hashes) KS_TRY(ks_copy_d2h(ctx, hashes, c->d_hash, n * sizeof(u64)));
+    if (n && abund_sum) KS_TRY(ks_copy_d2h(ctx, abund_sum, c->d_sum, n * sizeof(u64)));
+    if (n && doc_freq) KS_TRY(ks_copy_d2h(ctx, doc_freq, c->d_df, n * sizeof(u32)));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KS_OK;
+    });
+}
+
+extern "C" void ks_corpus_free(ks_corpus *c) {
+    if (!c) return;
+    ks_pool_free(c->ctx, c->d_hash); ks_pool_free(c->ctx, c->d_sum); ks_pool_free(c->ctx, c->d_df);
+    delete c;
+}
+
+// ---- weights ---------------------------------------------------------------------------------------------------------------
+// number of entries of a[0, n) below h
+KS_DEV u32 sg_lower_bound(const u64 *a, u32 n, u64 h) {
+    u32 lo = 0, hi = n;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < h) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
+struct sg_table {
+    const u64 *hash, *sum;
+    const u32 *df;
+    u32 n;
+    double total; // (double)total(S)
+};
+
+// One wave per query: its abundance sum, then per posting the two products.  A hash that the target corpus does not hold gets
+// 0 twice (no row can use it); one that the QUERY corpus does not hold raises *flag: that corpus is not this set's.
+__global__ __launch_bounds__(256) void k_sg_weights(const u64 *q_off, const u64 *q_hash, const u32 *q_abund, u32 n_seqs, sg_table CQ, sg_table CT,
+                                                    const double *idf, double *pw, double *tw, unsigned long long *flag) {
+#pragma clang fp contract(off)
+    const u32 s = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (s >= n_seqs) return; // (uniform per wave)
+    const u64 b = q_off[s], e = q_off[s + 1];
+    u64 part = 0;
+    for (u64 j = b + lane; j < e; j += 64) part += q_abund[j];
+    const double q_sum = (double)ks_wave_sum64(part);
+    for (u64 j = b + lane; j < e; j += 64) {
+        const u64 h = q_hash[j];
+        const u32 iq = sg_lower_bound(CQ.hash, CQ.n, h), it = sg_lower_bound(CT.hash, CT.n, h);
+        const bool in_q = iq < CQ.n && CQ.hash[iq] == h, in_t = it < CT.n && CT.hash[it] == h;
+        if (!in_q) atomicOr(flag, 1ULL);
+        double p = 0.0, t = 0.0;
+        if (in_q && in_t) {
+            const double fq = (double)CQ.sum[iq] / CQ.total, ft = (double)CT.sum[it] / CT.total;
+            p = fq * ft;
+            const double tf = (double)q_abund[j] / q_sum;
+            t = tf * idf[CT.df[it]];
+        }
+        pw[j] = p; tw[j] = t;
+    }
+}
+
+// ---- rows ------------------------------------------------------------------------------------------------------------------
+struct sg_rows_in {
+    const u64 *q_off, *q_hash, *t_off, *t_hash;
+    const double *pw, *tw;
+    const u32 *qid, *tid, *isect;
+    u32 n_rows, n_q, n_t;
+};
+
+// bad[why] = the first row that cannot be right for that reason
+KS_DEV void sg_bad(unsigned long long *bad, u32 r, u32 why) { atomicMin(&bad[why], (unsigned long long)r); }
+
+KS_DEV double sg_readlane_f64(double v, int j) {
+    const u64 b = (u64)__double_as_longlong(v);
+    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)b, j), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(b >> 32), j);
+    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
+}
+
+// A lane per row.  mode: 0 every row here, 1 every row to the wave kernel, 2 by length.  wave_rows[0] counts the listed rows.
+__global__ __launch_bounds__(256) void k_sg_rows(sg_rows_in R, int mode, double *prob, double *tfidf, u32 *wave_rows, unsigned long long *bad) {
+#pragma clang fp contract(off)
+    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R.n_rows) return;
+    const u32 q = R.qid[r], t = R.tid[r];
+    if (q >= R.n_q || t >= R.n_t) { sg_bad(bad, r, SG_BAD_ID); prob[r] = 0.0; tfidf[r] = 0.0; return; }
+    const u64 qb = R.q_off[q], tb = R.t_off[t];
+    const u32 nq = (u32)(R.q_off[q + 1] - qb), nt = (u32)(R.t_off[t + 1] - tb);
+    if (mode == 1 || (mode == 2 && (u64)nq + nt > SG_CUT)) { wave_rows[1 + atomicAdd(&wave_rows[0], 1u)] = r; return; }
+    // the shorter run is walked, the longer one searched — from where the last search ended: both ascend
+    const bool walk_q = nq <= nt;
+    const u64 *wh = walk_q ? R.q_hash + qb : R.t_hash + tb, *sh = walk_q ? R.t_hash + tb : R.q_hash + qb;
+    const u32 nw = walk_q ? nq : nt, ns = walk_q ? nt : nq;
+    double po = 0.0, tf = 0.0;
+    u32 cnt = 0, from = 0;
+    for (u32 i = 0; i < nw && from < ns; i++) {
+        const u64 h = wh[i];
+        from += sg_lower_bound(sh + from, ns - from, h);
+        if (from < ns && sh[from] == h) {
+            const u64 p = qb + (walk_q ? i : from); // the QUERY posting: the weights are its
+            po += R.pw[p];
+            tf += R.tw[p];
+            cnt++;
+        }
+    }
+    if (cnt != R.isect[r]) sg_bad(bad, r, SG_BAD_COUNT);
+    prob[r] = po; tfidf[r] = tf;
+}
+
+// The listed rows, one wave per row (a fixed grid striding over the list).  Each chunk of 64 hashes of the shorter run is loaded
+// coalesced, every lane searches the longer run for its hash, and the shared ones' terms are added in lane order: ascending hash.
+__global__ __launch_bounds__(256) void k_sg_rows_wave(sg_rows_in R, const u32 *wave_rows, double *prob, double *tfidf, unsigned long long *bad) {
+#pragma clang fp contract(off)
+    const u32 lane = threadIdx.x & 63, n_waves = gridDim.x * (blockDim.x / 64);
+    const u32 n_list = wave_rows[0] < R.n_rows ? wave_rows[0] : R.n_rows;
+    for (u32 w = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); w < n_list; w += n_waves) { // (uniform per wave)
+        const u32 r = wave_rows[1 + w];
+        const u32 q = R.qid[r], t = R.tid[r]; // (in range: k_sg_rows lists no other row)
+        const u64 qb = R.q_off[q], tb = R.t_off[t];
+        const u32 nq = (u32)(R.q_off[q + 1] - qb), nt = (u32)(R.t_off[t + 1] - tb);
+        const bool walk_q = nq <= nt;
+        const u64 *wh = walk_q ? R.q_hash + qb : R.t_hash + tb, *sh = walk_q ? R.t_hash + tb : R.q_hash + qb;
+        const u32 nw = walk_q ? nq : nt, ns = walk_q ? nt : nq;
+        double po = 0.0, tf = 0.0;
+        u32 cnt = 0;
+        for (u32 c = 0; c < nw; c += 64) {
+            const u32 i = c + lane;
+            bool found = false;
+            u32 at = 0;
+            if (i < nw) {
+                const u64 h = wh[i];
+                at = sg_lower_bound(sh, ns, h);
+                found = at < ns && sh[at] == h;
+            }
+            const u64 p = qb + (walk_q ? i : at);
+            const double x = found ? R.pw[p] : 0.0, y = found ? R.tw[p] : 0.0;
+            u64 m = __ballot(found);
+            cnt += (u32)__popcll((long long)m);
+            while (m) { // (uniform: every lane keeps the same sums)
+                const int j = __ffsll((long long)m) - 1;
+                m &= m - 1;
+                po += sg_readlane_f64(x, j);
+                tf += sg_readlane_f64(y, j);
+            }
+        }
+        if (lane == 0) {
+            if (cnt != R.isect[r]) sg_bad(bad, r, SG_BAD_COUNT);
+            prob[r] = po; tfidf[r] = tf;
+        }
+    }
+}
+
+static int signif_opts_check(ks_ctx *ctx, const ks_signif_opts *o) {
+    if (!o) return KS_OK;
+    const char *why = o->reserved ? "reserved must be 0" : o->flags ? "unknown flags" : nullptr;
+    if (!why) return KS_OK;
+    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "significance options: %s", why) : KS_ERR_INVALID_ARG;
+}
+
+static bool sg_same_params(const ks_params &a, const ks_params &b) {
+    return a.ksize == b.ksize && a.scaled == b.scaled && a.moltype == b.moltype && a.seed == b.seed && a.flags == b.flags;
+}
+
+static int signif_run(ks_ctx *ctx, const ks_sketches *Q, const ks_sketches *T, const ks_corpus *CQ, const ks_corpus *CT, const ks_hits *H,
+                      ks_signif *S) {
+    const u64 n_rows = H->n_hits;
+    S->n_rows = n_rows;
+    KS_TRY(ks_alloc(ctx, &S->d_prob, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &S->d_tfidf, (size_t)n_rows));
+    if (n_rows == 0) return KS_OK;
+    if (n_rows >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "significance: 2^32 or more hit rows");
+    if (Q->n_hashes == 0 || T->n_hashes == 0)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: %llu hit rows, but a sketch set is empty: the inputs do not belong together",
+                       (unsigned long long)n_rows);
+
+    ks_scratch sc(ctx);
+    double *pw = nullptr, *tw = nullptr, *idf = nullptr;
+    u32 *wave_rows = nullptr;
+    u64 *ctl = nullptr; // [SG_BAD_ID], [SG_BAD_COUNT]: the first such row (all ones: none); [SG_BAD_CORPUS]: a query hash outside the query corpus
+    KS_TRY(sc.alloc(&pw, (size_t)Q->n_hashes)); KS_TRY(sc.alloc(&tw, (size_t)Q->n_hashes));
+    KS_TRY(sc.alloc(&idf, (size_t)CT->max_doc_freq + 1));
+    KS_TRY(sc.alloc(&wave_rows, (size_t)n_rows + 1));
+    KS_TRY(sc.alloc(&ctl, 3));
+    KS_HIP(ctx, hipMemsetAsync(ctl, 0xff, 2 * sizeof(u64), ctx->stream));
+    KS_HIP(ctx, hipMemsetAsync(ctl + SG_BAD_CORPUS, 0, sizeof(u64), ctx->stream));
+    KS_HIP(ctx, hipMemsetAsync(wave_rows, 0, sizeof(u32), ctx->stream));
+    // smooth idf over the document frequencies the target corpus holds: libm's log, here on the host
+    std::vector<double> h_idf((size_t)CT->max_doc_freq + 1);
+    for (size_t d = 0; d < h_idf.size(); d++) h_idf[d] = std::log(((double)1 + (double)T->n_seqs) / ((double)1 + (double)d)) + 1.0;
+    KS_TRY(ks_copy_h2d(ctx, idf, h_idf.data(), h_idf.size() * sizeof(double)));
+
+    const sg_table tq = {CQ->d_hash, CQ->d_sum, CQ->d_df, (u32)CQ->n_hashes, (double)CQ->total};
+    const sg_table tt = {CT->d_hash, CT->d_sum, CT->d_df, (u32)CT->n_hashes, (double)CT->total};
+    KS_LAUNCH(ctx, "signif_weights", k_sg_weights, (Q->n_seqs + 3) / 4, 256, (const u64 *)Q->d_offsets, (const u64 *)Q->d_hashes,
+              (const u32 *)Q->d_abunds, Q->n_seqs, tq, tt, (const double *)idf, pw, tw, (unsigned long long *)(ctl + SG_BAD_CORPUS));
+    int mode = 2;
+    if (const char *f = ks_dbg(ctx, KS_DBG_SIGNIF_WAVE_ROWS)) mode = atoi(f) != 0 ? 1 : 0; // (tests: small inputs take both paths)
+    const sg_rows_in R = {Q->d_offsets, Q->d_hashes, T->d_offsets, T->d_hashes, pw, tw, H->d_qid, H->d_tid, H->d_isect,
+                          (u32)n_rows, Q->n_seqs, T->n_seqs};
+    KS_LAUNCH(ctx, "signif_rows", k_sg_rows, (u32)((n_rows + 255) / 256), 256, R, mode, S->d_prob, S->d_tfidf, wave_rows,
+              (unsigned long long *)ctl);
+    if (mode != 0)
+        KS_LAUNCH(ctx, "signif_rows_wave", k_sg_rows_wave, SG_WAVE_GRID, 256, R, (const u32 *)wave_rows, S->d_prob, S->d_tfidf,
+                  (unsigned long long *)ctl);
+    u64 *const rb = ctx->h_pin + KS_PIN_SIGNIF;
+    const ks_fetch_seg f = ks_fetch_words(ctl, rb, 6);
+    KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
+    if (rb[SG_BAD_ID] != ~0ULL)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: hit row %llu names a query or target beyond the sketch sets (%u queries, %u targets)",
+                       (unsigned long long)rb[SG_BAD_ID], Q->n_seqs, T->n_seqs);
+    if (rb[SG_BAD_CORPUS] != 0)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: a query hash is not in the query corpus: the corpus was built from another set");
+    if (rb[SG_BAD_COUNT] != ~0ULL)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG,
+                       "significance: hit row %llu does not share `intersect` hashes in these sketches: hits and sketches do not belong together",
+                       (unsigned long long)rb[SG_BAD_COUNT]);
+    return KS_OK;
+}
+
+extern "C" int ks_hits_significance(ks_ctx *ctx, const ks_sketches *queries, const ks_sketches *targets, const ks_corpus *q_corpus,
+                                    const ks_corpus *t_corpus, const ks_hits *hits, const ks_signif_opts *opts, ks_signif **out) {
+    return ks_guard(ctx, [&]() -> int {
+    KS_TRY(signif_opts_check(ctx, opts));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!queries || !targets || !q_corpus || !t_corpus || !hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (queries->ctx != ctx || targets->ctx != ctx || q_corpus->ctx != ctx || t_corpus->ctx != ctx || hits->ctx != ctx)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: an input of another context");
+    const ks_params &a = queries->params, &b = targets->params;
+    if (!sg_same_params(a, b))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: the sketch sets were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)",
+                       a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
+    const struct { const ks_corpus *c; const ks_sketches *s; const char *side; } pairs[2] = {{q_corpus, queries, "query"}, {t_corpus, targets, "target"}};
+    for (const auto &p : pairs) {
+        if (p.c->n_docs != p.s->n_seqs)
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: the %s corpus counts %u sketches, the %s set holds %u: a corpus of another set",
+                           p.side, p.c->n_docs, p.side, p.s->n_seqs);
+        if (!sg_same_params(p.c->params, p.s->params) || p.c->n_postings != p.s->n_hashes)
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: the %s corpus was built from another set (parameters or size differ)", p.side);
+    }
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(queries))); // (the passes read both sets as plain CSRs)
+    KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(targets)));
+    ks_signif *S = new ks_signif();
+    memset(S, 0, sizeof *S);
+    S->ctx = ctx;
+    int st = signif_run(ctx, queries, targets, q_corpus, t_corpus, hits, S);
+    if (st == KS_OK && hits->n_hits == 0) st = ks_stream_wait(ctx);
+    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_signif_free(S); return st; }
+    *out = S;
+    return KS_OK;
+    });
+}
+
+extern "C" uint64_t ks_signif_n_rows(const ks_signif *s) { return s ? s->n_rows : 0; }
+extern "C" const double *ks_signif_device_prob_overlap(const ks_signif *s) { return s ? s->d_prob : nullptr; }
+extern "C" const double *ks_signif_device_tf_idf(const ks_signif *s) { return s ? s->d_tfidf : nullptr; }
+
+extern "C" int ks_signif_copy_to_host(ks_ctx *ctx, const ks_signif *s, double *prob_overlap, double *tf_idf) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !s) return KS_ERR_INVALID_ARG;
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t n = (size_t)s->n_rows;
+    if (n && prob_overlap) KS_TRY(ks_copy_d2h(ctx, prob_overlap, s->d_prob, n * sizeof(double)));
+    if (n && tf_idf) KS_TRY(ks_copy_d2h(ctx, tf_idf, s->d_tfidf, n * sizeof(double)));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KS_OK;
+    });
+}
+
+extern "C" void ks_signif_free(ks_signif *s) {
+    if (!s) return;
+    ks_pool_free(s->ctx, s->d_prob); ks_pool_free(s->ctx, s->d_tfidf);
+    delete s;
+}

@@ -364,6 +364,27 @@ class Context:
         self._check(self._L.ks_match_positions(self._h, q_pos._h, t_pos._h, hits._h, C.byref(opts), C.byref(out)))
         return MatchPositions(self, out)
 
+    def significance(self, queries: "Sketches", targets: "Sketches", hits: "Hits", q_corpus: Optional["Corpus"] = None,
+                     t_corpus: Optional["Corpus"] = None) -> "Significance":
+        """ks_hits_significance: per row of `hits` the two f64 sums behind multisearch's prob_overlap and tf_idf_score, over the
+        hashes the row's query and target share (include/kmerseek_amd.h has the definitions).  queries / targets: the sets the
+        hits were searched on.  A corpus table that is not passed is built here (Sketches.corpus) and freed again — pass them
+        when several hit lists share a set."""
+        own = []
+        try:
+            if q_corpus is None:
+                q_corpus = queries.corpus(); own.append(q_corpus)
+            if t_corpus is None:
+                t_corpus = targets.corpus(); own.append(t_corpus)
+            out = C.c_void_p()
+            opts = _lib.ks_signif_opts(0, 0)
+            self._check(self._L.ks_hits_significance(self._h, queries._h, targets._h, q_corpus._h, t_corpus._h, hits._h, C.byref(opts),
+                                                     C.byref(out)))
+            return Significance(self, out)
+        finally:
+            for c in own:
+                c.free()
+
     # ---- index / search ----
     def index_build(self, targets: "Sketches") -> "Index":
         out = C.c_void_p()
@@ -529,6 +550,13 @@ class Sketches(_Owned):
         self._ctx._check(self._ctx._L.ks_sketches_union(self._ctx._h, self._h, C.byref(out)))
         return Sketches(self._ctx, out)
 
+    def corpus(self) -> "Corpus":
+        """Corpus table of the set (ks_corpus_build): per distinct hash its abundance sum (u64, no saturation) and the number
+        of sketches that hold it, plus the set's total abundance — what `Context.significance` weighs shared hashes with."""
+        out = C.c_void_p()
+        self._ctx._check(self._ctx._L.ks_corpus_build(self._ctx._h, self._h, C.byref(out)))
+        return Corpus(self._ctx, out)
+
     def to_host(self, pinned: bool = False) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
         """(offsets u64[n+1], hashes u64, abunds u32) on the host.  pinned=True returns arrays in pinned memory
         (Context.pinned_empty): one DMA at link rate instead of staged copies — what large sketch sets should use."""
@@ -590,6 +618,52 @@ class MatchPositions(_Owned):
         self._ctx._check(self._ctx._L.ks_matchpos_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(qs), _ptr(ts),
                                                                *[_ptr(e) for e in ext]))
         return (offs, qs, ts, *ext)
+
+
+class Corpus(_Owned):
+    """Device-resident corpus table of a sketch set (ks_corpus): distinct hashes ascending, abundance sums, document frequencies."""
+    _free = "ks_corpus_free"
+
+    @property
+    def n_hashes(self) -> int:
+        return int(self._ctx._L.ks_corpus_n_hashes(self._h))
+
+    @property
+    def n_docs(self) -> int:
+        """Sketches of the set, empty ones included."""
+        return int(self._ctx._L.ks_corpus_n_docs(self._h))
+
+    @property
+    def total_abund(self) -> int:
+        return int(self._ctx._L.ks_corpus_total_abund(self._h))
+
+    def to_host(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(hashes u64, abund_sum u64, doc_freq u32), n_hashes entries each."""
+        n = self.n_hashes
+        h = np.zeros(n, np.uint64); a = np.zeros(n, np.uint64); d = np.zeros(n, np.uint32)
+        self._ctx._check(self._ctx._L.ks_corpus_copy_to_host(self._ctx._h, self._h, _ptr(h), _ptr(a), _ptr(d)))
+        return h, a, d
+
+
+class Significance(_Owned):
+    """Device-resident f64 columns over hit rows (ks_signif): prob_overlap and tf_idf, row r belongs to row r of the hits."""
+    _free = "ks_signif_free"
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_signif_n_rows(self._h))
+
+    def device_ptrs(self) -> Tuple[int, int]:
+        """Raw device pointers of the columns (prob_overlap f64, tf_idf f64), `n_rows` entries each."""
+        L = self._ctx._L
+        return tuple(int(f(self._h) or 0) for f in (L.ks_signif_device_prob_overlap, L.ks_signif_device_tf_idf))
+
+    def to_host(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(prob_overlap f64, tf_idf f64) per hit row."""
+        n = self.n_rows
+        po = np.zeros(n, np.float64); tf = np.zeros(n, np.float64)
+        self._ctx._check(self._ctx._L.ks_signif_copy_to_host(self._ctx._h, self._h, _ptr(po), _ptr(tf)))
+        return po, tf
 
 
 class Index(_Owned):

@@ -5,6 +5,9 @@
                         (gzipped JSON signatures + SOURMASH-MANIFEST.csv).
 * ``do_manysearch()`` — drop-in for src/python/kmerseek/search.py:125-141 (branchwater ``do_manysearch`` with threshold 0,
                         abundance on, output_all off): writes the 22-column CSV pinned by tests/test_search.py:33-39.
+* ``do_multisearch()`` — drop-in for src/python/kmerseek/search.py:144-158 (branchwater ``do_multisearch`` with threshold 0, no
+                        ANI, probability of overlap on, output_all off): the 16-column CSV of the reference's fixture
+                        tests/testdata/index/ced9-bcl2-first25.hp.k16.manysearch.csv.
 Hashing, sorting, joining and counting all run in the HIP library; this module only formats.  The ratio columns are
 f64 arithmetic on the integer results (formulas: SURVEY.md §8(a) row a10).
 """
@@ -29,6 +32,12 @@ MANYSEARCH_COLUMNS = [
     "match_md5", "jaccard", "max_containment", "average_abund", "median_abund", "std_abund",
     "query_containment_ani", "match_containment_ani", "average_containment_ani", "max_containment_ani",
     "n_weighted_found", "total_weighted_hashes", "containment_target_in_query", "f_weighted_target_in_query",
+]
+
+MULTISEARCH_COLUMNS = [
+    "query_name", "query_md5", "match_name", "match_md5", "containment", "max_containment", "jaccard", "intersect_hashes",
+    "ksize", "scaled", "moltype", "prob_overlap", "prob_overlap_adjusted", "containment_adjusted",
+    "containment_adjusted_log10", "tf_idf_score",
 ]
 
 
@@ -205,6 +214,90 @@ def do_manysearch(query_sig: str, target_sig: str, output: str, ksize: int, scal
         rows = manysearch_rows(qn, qo, qm, tn, to, tm, ta, hits, ksize, scaled, moltype)
         with open(output, "w", newline="") as f:
             w = csv.DictWriter(f, fieldnames=MANYSEARCH_COLUMNS, lineterminator="\n")
+            w.writeheader()
+            w.writerows(rows)
+        return len(rows)
+    finally:
+        if own:
+            ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# do_multisearch()  — src/python/kmerseek/search.py:144-158
+# ---------------------------------------------------------------------------------------------------------
+def format_f64(x: float) -> str:
+    """An f64 as the reference's CSV prints it: the shortest digits that read back as the same value, never an exponent,
+    and '.0' behind a whole number (2.0, 0.000023191094619666044)."""
+    x = float(x)
+    if math.isnan(x):
+        return "NaN"
+    if math.isinf(x):
+        return "inf" if x > 0 else "-inf"
+    r = repr(x)
+    if "e" not in r and "E" not in r:
+        return r
+    from decimal import Decimal
+    t = format(Decimal(r), "f")
+    return t if "." in t else t + ".0"
+
+
+def multisearch_rows(q_names, q_off, q_mins, t_names, t_off, t_mins, hits, prob_overlap, tf_idf, ksize: int, scaled: int,
+                     moltype: str) -> List[dict]:
+    """The 16 CSV columns for every COO hit (qid, tid, intersect, n_weighted) with its two significance sums
+    (Context.significance).  Derived here, in f64: prob_overlap_adjusted = prob_overlap * (n_queries * n_targets) — every
+    sequence of either batch counts, empty sketches included —, containment_adjusted = containment / prob_overlap_adjusted
+    and its log10."""
+    qid, tid, isect, _ = hits
+    n_comparisons = float((len(q_off) - 1) * (len(t_off) - 1))
+    md5_q, md5_t = {}, {}
+    rows = []
+    for q, t, i, po, tf in zip(qid.tolist(), tid.tolist(), isect.tolist(), np.asarray(prob_overlap, np.float64).tolist(),
+                               np.asarray(tf_idf, np.float64).tolist()):
+        qm = q_mins[int(q_off[q]):int(q_off[q + 1])]
+        tm = t_mins[int(t_off[t]):int(t_off[t + 1])]
+        nq, nt = len(qm), len(tm)
+        if q not in md5_q:
+            md5_q[q] = sourmash_md5(qm, ksize)
+        if t not in md5_t:
+            md5_t[t] = sourmash_md5(tm, ksize)
+        cq, ct = float(i) / float(nq), float(i) / float(nt)
+        adj = po * n_comparisons
+        c_adj = cq / adj if adj != 0.0 else math.inf  # (f64 division: cq > 0, every row shares a hash)
+        c_log = math.log10(c_adj) if 0.0 < c_adj < math.inf else (-math.inf if c_adj == 0.0 else c_adj)
+        rows.append({
+            "query_name": q_names[q], "query_md5": md5_q[q], "match_name": t_names[t], "match_md5": md5_t[t],
+            "containment": format_f64(cq), "max_containment": format_f64(max(cq, ct)), "jaccard": format_f64(float(i) / float(nq + nt - i)),
+            "intersect_hashes": format_f64(float(i)), "ksize": 3 * ksize, "scaled": scaled, "moltype": moltype,
+            "prob_overlap": format_f64(po), "prob_overlap_adjusted": format_f64(adj), "containment_adjusted": format_f64(c_adj),
+            "containment_adjusted_log10": format_f64(c_log), "tf_idf_score": format_f64(tf),
+        })
+    return rows
+
+
+def do_multisearch(query_sig: str, target_sig: str, output: str, ksize: int, scaled: int, moltype: str,
+                   ctx: Optional[Context] = None) -> int:
+    """Search every sketch of query_sig (.sig.zip) against every sketch of target_sig and weigh every hit (prob_overlap,
+    tf_idf_score and the columns derived from them); CSV rows for pairs that share at least one hash.  Returns the number of
+    rows written."""
+    own = ctx is None
+    ctx = ctx or Context(0)
+    try:
+        qn, qo, qm, qa, qk, qs, qmol = read_sig_zip(query_sig)
+        tn, to, tm, ta, tk, ts, tmol = read_sig_zip(target_sig)
+        for have in ((qk, qs, qmol), (tk, ts, tmol)):
+            if have != (ksize, scaled, moltype):
+                raise ValueError(f"sketch parameters {have} do not match the requested {(ksize, scaled, moltype)}")
+        Q = ctx.sketches_from_host(qo, qm, qa, ksize, scaled, moltype)
+        T = ctx.sketches_from_host(to, tm, ta, ksize, scaled, moltype)
+        ix = ctx.index_build(T)
+        hits = ctx.search(ix, Q)
+        sig = ctx.significance(Q, T, hits)
+        po, tf = sig.to_host()
+        rows = multisearch_rows(qn, qo, qm, tn, to, tm, hits.to_host(), po, tf, ksize, scaled, moltype)
+        for o in (sig, hits, ix, Q, T):
+            o.free()
+        with open(output, "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=MULTISEARCH_COLUMNS, lineterminator="\n")
             w.writeheader()
             w.writerows(rows)
         return len(rows)
