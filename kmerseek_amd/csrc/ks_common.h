@@ -403,6 +403,16 @@ int ks_sort_pairs_msd(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbit
 int ks_radix_sort_u64(ks_ctx *ctx, int tag, const u64 *keys_in, const u64 *vals_in, u64 *ka, u64 *va, u64 *kb, u64 *vb,
                       u64 n, const int *shifts, int n_shifts, u64 **keys_out, u64 **vals_out);
 
+// ---- sorted list -> runs -> one record per run (ks_rows.hip) ----
+// a dense sketch set sorted by hash: keys / vals (hashes, abundances) and row_start[n_rows + 1] in the caller's scratch
+struct ks_runs { u64 *keys; u32 *vals; u64 *row_start; u32 n_rows; };
+int ks_sorted_runs(ks_ctx *ctx, const ks_sketches *in, ks_scratch &sc, ks_runs *out);
+// a row list for ks_row_list_push (ks_device.h): room for n_rows rows behind its count, the count zeroed
+int ks_row_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t n_rows, u32 **list);
+// what the row half needs from one search; the sorted match list pk becomes H's rows (n_pairs == 0: none, pk is not read)
+struct ks_rows_in { const ks_sketches *q; u64 n_pairs; int tbits, abits; bool stats; double min_c; };
+int ks_search_rows(ks_ctx *ctx, const ks_rows_in &R, ks_hits *H, const u64 *pk);
+
 // ---- pipelines (ks_sketch.hip, ks_search.hip) ----
 // part_pbits > 0: also emit postings partitioned for a join on the top part_pbits hash bits
 // allow_defer: the first attempt may return with ks_sketches::pending set (no wait at the end), see there
@@ -424,7 +434,6 @@ int ks_kmerpos_tiles_launch(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32
 int ks_kmerpos_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res,
                            const ks_params *p, ks_kmerpos **out);
 int ks_index_build_impl(ks_ctx *ctx, const ks_sketches *t, ks_index **out);
-int ks_matchpos_opts_check(ks_ctx *ctx, const ks_matchpos_opts *opts);
 // opts: NULL or validated (ks_search_opts_check); NULL and all-zero options run the same launches
 int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo = nullptr,
                    const ks_search_opts *opts = nullptr);
@@ -432,6 +441,10 @@ int ks_search_opts_check(ks_ctx *ctx, const ks_search_opts *opts);
 int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out);
 
 int ks_check_params(ks_ctx *ctx, const ks_params *p);
+// two objects were made with the same parameters: all five fields
+bool ks_same_params(const ks_params &a, const ks_params &b);
+// the flags / reserved words of an options struct: "<what> options: reserved must be 0" / "... unknown flags"; ctx may be NULL
+int ks_opts_words_check(ks_ctx *ctx, const char *what, u32 flags, u32 allowed, u32 reserved);
 // gapped slots -> plain CSR (see ks_sketches); no-op for dense sketches.  Enqueued on ctx's stream.
 int ks_sketches_make_dense(ks_ctx *ctx, ks_sketches *s);
 

@@ -57,6 +57,15 @@ extern "C" uint64_t ks_max_hash(uint32_t scaled) {
     return (uint64_t)v;
 }
 
+bool ks_same_params(const ks_params &a, const ks_params &b) {
+    return a.ksize == b.ksize && a.scaled == b.scaled && a.moltype == b.moltype && a.seed == b.seed && a.flags == b.flags;
+}
+int ks_opts_words_check(ks_ctx *ctx, const char *what, u32 flags, u32 allowed, u32 reserved) {
+    const char *why = reserved ? "reserved must be 0" : (flags & ~allowed) ? "unknown flags" : nullptr;
+    if (!why) return KS_OK;
+    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "%s options: %s", what, why) : KS_ERR_INVALID_ARG;
+}
+
 int ks_check_params(ks_ctx *ctx, const ks_params *p) {
     if (!p) return ks_fail(ctx, KS_ERR_INVALID_ARG, "params is NULL");
     if (p->moltype > KS_HP)

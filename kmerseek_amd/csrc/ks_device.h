@@ -155,6 +155,56 @@ KS_DEV u64 ks_wave_sum64(u64 v) {
 }
 // value of the lane below (lane 0: 0)
 KS_DEV u32 ks_lane_below(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); } // wave_shr:1
+// largest value over the 64 lanes of a wave (every lane gets it)
+KS_DEV u32 ks_wave_max_u32(u32 v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) { const u32 o = (u32)__shfl_xor((int)v, d); v = o > v ? o : v; }
+    return v;
+}
+// number of entries of the ascending a[0, n) below x = the first i with a[i] >= x
+template <typename T> KS_DEV u32 ks_lower_bound(const T *a, u32 n, T x) {
+    u32 lo = 0, hi = n;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo) >> 1);
+        if (a[mid] < x) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+KS_DEV u32 ks_lower_bound_u64(const u64 *a, u32 n, u64 x) { return ks_lower_bound<u64>(a, n, x); }
+KS_DEV u32 ks_lower_bound_u32(const u32 *a, u32 n, u32 x) { return ks_lower_bound<u32>(a, n, x); }
+// sum of the abundances of one run [b, e) of a sorted posting list (the union's and the corpus's record per distinct hash)
+KS_DEV u64 ks_run_abund_sum(const u32 *vals, u64 b, u64 e) { u64 w = 0; for (u64 j = b; j < e; j++) w += vals[j]; return w; }
+
+// ---- short rows by a lane, long rows by a wave ----
+// A pass with a lane per row pushes the rows that are too long for one lane onto a list (list[0] counts, the rows follow:
+// ks_row_list_alloc on the host); a fixed grid of 4-wave workgroups strides over it, a wave per row, 64 elements per chunk, and
+// adds what it sums serially in lane order through readlane (every lane keeps the same sums): a host loop's f64 results.
+KS_DEV void ks_row_list_push(u32 *list, u32 r) { list[1 + atomicAdd(&list[0], 1u)] = r; }
+// row(r) for every listed row, one wave each (r is wave-uniform); a count beyond n_rows — the most the list can hold — is cut
+template <typename Row> KS_DEV void ks_row_list_walk(const u32 *list, u32 n_rows, Row row) {
+    const u32 n_waves = gridDim.x * (blockDim.x / 64);
+    const u32 n_list = list[0] < n_rows ? list[0] : n_rows;
+    for (u32 w = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); w < n_list; w += n_waves) row(list[1 + w]);
+}
+KS_DEV double ks_readlane_f64(double v, int j) {
+    const u64 b = (u64)__double_as_longlong(v);
+    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)b, j), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(b >> 32), j);
+    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
+}
+// acc += lane j's x (and acc2 += lane j's x2, in the same walk) for every set bit j of m, ascending.  m is wave-uniform; it
+// is taken from the first lane so that the walk runs on the scalar unit also where the compiler cannot see that.
+KS_DEV void ks_wave_add_ordered(u64 m, double &acc, double x, double &acc2, double x2) {
+#pragma clang fp contract(off)
+    m = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(m >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)m);
+    while (m) {
+        const int j = __ffsll((long long)m) - 1;
+        m &= m - 1;
+        acc += ks_readlane_f64(x, j); acc2 += ks_readlane_f64(x2, j);
+    }
+}
+KS_DEV void ks_wave_add_ordered(u64 m, double &acc, double x) { double none = 0.0; ks_wave_add_ordered(m, acc, x, none, 0.0); }
+// the mask of the lanes below n (n <= 64)
+KS_DEV u64 ks_lanes_below(u32 n) { return n >= 64u ? ~0ULL : (1ULL << n) - 1ULL; }
 
 // Block-wide exclusive scan; `smem` must hold (blockDim.x/64 + 1) u32.  Returns the exclusive
 // prefix of v; *total receives the block sum.  Contains three __syncthreads().

@@ -21,18 +21,12 @@
 #define MP_STAGE 4096 // query windows of a tile whose scanned counts are staged in LDS (16 KB); more: searched in memory
 #define MP_NONE 0xffffffffu
 
-KS_DEV u32 mp_wave_max(u32 v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) { const u32 o = (u32)__shfl_xor((int)v, d); v = o > v ? o : v; }
-    return v;
-}
-
 // targets: (seq, start) as the value column of the hash sort + the longest start
 __global__ __launch_bounds__(256) void k_mp_pack(const u32 *seq, const u32 *start, u32 n, u64 *val, u32 *max_start) {
     const u32 i = blockIdx.x * 256 + threadIdx.x;
     u32 s = 0;
     if (i < n) { s = start[i]; val[i] = ((u64)seq[i] << 32) | s; }
-    s = mp_wave_max(s);
+    s = ks_wave_max_u32(s);
     if ((threadIdx.x & 63) == 0 && s) atomicMax(max_start, s);
 }
 
@@ -56,7 +50,7 @@ __global__ __launch_bounds__(256) void k_mp_count(const u64 *q_hash, const u32 *
         lo[i] = a;
         cnt[i] = b - a;
     }
-    s = mp_wave_max(s);
+    s = ks_wave_max_u32(s);
     if ((threadIdx.x & 63) == 0 && s) atomicMax(max_start, s);
 }
 
@@ -64,12 +58,7 @@ __global__ __launch_bounds__(256) void k_mp_count(const u64 *q_hash, const u32 *
 __global__ __launch_bounds__(256) void k_mp_row_begin(const u32 *qid, u32 n_rows, u32 n_qseqs, u32 *row_begin) {
     const u32 q = blockIdx.x * 256 + threadIdx.x;
     if (q > n_qseqs) return;
-    u32 lo = 0, hi = n_rows;
-    while (lo < hi) {
-        const u32 mid = lo + ((hi - lo) >> 1);
-        if (qid[mid] < q) lo = mid + 1; else hi = mid;
-    }
-    row_begin[q] = lo;
+    row_begin[q] = ks_lower_bound_u32(qid, n_rows, q);
 }
 
 // last index in [lo, hi] whose off[] is <= p (off[lo] <= p holds)
@@ -219,13 +208,6 @@ __global__ __launch_bounds__(256) void k_mp_rows(const u64 *keys, u64 n_cand, mp
 
 static int mp_bits(u64 v) { int b = 1; while (b < 64 && (v >> b)) b++; return b; }
 
-int ks_matchpos_opts_check(ks_ctx *ctx, const ks_matchpos_opts *o) {
-    if (!o) return KS_OK;
-    const char *why = o->reserved ? "reserved must be 0" : o->flags ? "unknown flags" : nullptr;
-    if (!why) return KS_OK;
-    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "match position options: %s", why) : KS_ERR_INVALID_ARG;
-}
-
 // the sort of one slice's keys on their live bits; *sorted = where they ended up (ka or kb)
 static int mp_sort_keys(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int nbits, u64 **sorted) {
     int msd = 0;
@@ -371,13 +353,13 @@ static int mp_run(ks_ctx *ctx, const ks_kmerpos *Q, const ks_kmerpos *T, const k
 extern "C" int ks_match_positions(ks_ctx *ctx, const ks_kmerpos *q_pos, const ks_kmerpos *t_pos, const ks_hits *hits,
                                   const ks_matchpos_opts *opts, ks_matchpos **out) {
     return ks_guard(ctx, [&]() -> int {
-    KS_TRY(ks_matchpos_opts_check(ctx, opts));
+    if (opts) KS_TRY(ks_opts_words_check(ctx, "match position", opts->flags, 0, opts->reserved));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!q_pos || !t_pos || !hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
     if (q_pos->ctx != ctx || t_pos->ctx != ctx || hits->ctx != ctx) return ks_fail(ctx, KS_ERR_INVALID_ARG, "match positions: an input of another context");
     const ks_params &a = q_pos->params, &b = t_pos->params;
-    if (a.ksize != b.ksize || a.scaled != b.scaled || a.moltype != b.moltype || a.seed != b.seed || a.flags != b.flags)
+    if (!ks_same_params(a, b))
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "match positions: the tables were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)",
                        a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
     KS_HIP(ctx, hipSetDevice(ctx->device));

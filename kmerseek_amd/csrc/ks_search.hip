@@ -12,7 +12,7 @@
 //            needs locality, not order: each query posting binary-searches its full 64-bit hash in the
 //            LDS-staged index keys of its bucket.
 //   matches: one 8-byte record (qid << tbits | tid) << abits | abund per match, appended through a wave-aggregated atomic
-//            cursor, sorted on the live id bits, then run-length reduced to COO sorted by (qid, tid).
+//            cursor, sorted on the live id bits, then run-length reduced to COO sorted by (qid, tid) (ks_rows.hip).
 #include "ks_device.h"
 
 // one wave per sequence: value[j] = f(seq id) for every posting j of the sequence
@@ -1060,270 +1060,6 @@ __global__ __launch_bounds__(256) void k_pairs_compact(const u64 *src_k, u64 seg
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// run boundaries of a sorted key list (union_run): heads, then the first record of every run
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pair_heads(const u64 *keys, u64 n, u32 *heads) {
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    heads[i] = (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u;
-}
-
-// hidx = exclusive scan of heads; row r starts where hidx steps from r to r+1
-__global__ __launch_bounds__(256) void k_pair_rows(const u64 *keys, const u32 *hidx, u64 n, u32 n_rows, u64 *row_start) {
-    u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    bool head = (i == 0) || keys[i] != keys[i - 1];
-    if (head) row_start[hidx[i]] = i;
-    if (i == 0) row_start[n_rows] = n;
-}
-
-// ---------------------------------------------------------------------------------------------
-// Sorted match list -> COO rows in ONE pass: heads, their prefix over the whole list and the per-row sums used to be three
-// passes (heads, a device-wide scan, a reduce) — 0.23 ms of the 1M x 1M step and a quarter of the all-vs-all one, where two
-// records in three open a row.  Here a tile of PF_TILE records keeps its keys in registers: sweep 1 marks the heads (bit per
-// round) and counts them per (round, wave); wave 0 turns the 32 counts into offsets and chains the tile's total through a
-// decoupled look-back (ticket-ordered tiles, 8-byte {flag, value} words); sweep 2 gives every record its row and sums
-// count / abundance per row with a segmented scan (rows span waves and tiles, so the partial sums are added atomically:
-// ~2 atomics per wave and round).  Rows beyond `rows_cap` are dropped (the row arrays are sized from the previous search's
-// row count; the host repeats this launch with exact arrays when the true count is larger).
-// ---------------------------------------------------------------------------------------------
-#define PF_THREADS 256
-#define PF_IPT 8
-#define PF_TILE (PF_THREADS * PF_IPT)
-#define PF_WAVES (PF_THREADS / 64)
-
-__global__ __launch_bounds__(PF_THREADS) void k_pair_rows_fused(const u64 *keys, u64 n, u32 *qid, u32 *tid, u32 *isect, unsigned long long *nw,
-                                                                int tbits, int abits, u32 rows_cap, unsigned long long *status,
-                                                                u32 *ticket /* [0] tile ids, [1] a look-back gave up */, u32 *n_rows_out,
-                                                                int use_ticket) {
-    __shared__ u32 tile_s;
-    __shared__ u32 wcount[PF_IPT][PF_WAVES]; // heads per (round, wave), then exclusive offsets inside the tile
-    __shared__ unsigned long long base_s;
-    const u32 tid_ = threadIdx.x, lane = tid_ & 63, wave = tid_ >> 6;
-    // Tile ids in dispatch order (blockIdx.x): workgroups start in that order on this hardware, so a tile's predecessors are
-    // running or done when it looks back.  That is not a documented guarantee: the look-back spins for a bounded time, and a
-    // launch in which one gave up is repeated with ids from an atomic ticket (order of arrival; ~12 ns per ticket on one
-    // address — 10^4 tiles are 0.1 ms of queueing, most of this kernel's former run time).
-    if (use_ticket) { // uniform
-        if (tid_ == 0) tile_s = atomicAdd(&ticket[0], 1u);
-        __syncthreads();
-    }
-    const u32 tile = use_ticket ? tile_s : blockIdx.x;
-    const u64 b0 = (u64)tile * PF_TILE;
-    u64 key[PF_IPT];
-    u32 headbits = 0;
-    // sweep 1: record i of round r is b0 + r * PF_THREADS + tid (coalesced); a head opens a row
-#pragma unroll
-    for (int r = 0; r < PF_IPT; r++) {
-        const u64 i = b0 + (u64)r * PF_THREADS + tid_;
-        key[r] = i < n ? keys[i] : 0;
-    }
-    // The previous record: the lane below's (two DPP moves, no LDS crossbar), except for lane 0, whose predecessor sits in the
-    // previous wave / round / tile: lane r of the wave loads it for round r — one register pair and ONE memory latency for all
-    // rounds (a load inside the loop was waited for in every round: eight dependent latencies per tile).
-    u64 pp = 0;
-    {
-        const u64 iw = b0 + (u64)lane * PF_THREADS + (tid_ & ~63u); // lane r: where this wave's round r starts
-        if (lane < PF_IPT && iw > 0 && iw < n) pp = keys[iw - 1];
-    }
-#pragma unroll
-    for (int r = 0; r < PF_IPT; r++) {
-        const u64 i = b0 + (u64)r * PF_THREADS + tid_;
-        const u64 below = ((u64)ks_lane_below((u32)(key[r] >> 32)) << 32) | ks_lane_below((u32)key[r]);
-        const u64 first = ((u64)(u32)__builtin_amdgcn_readlane((int)(u32)(pp >> 32), r) << 32) | (u32)__builtin_amdgcn_readlane((int)(u32)pp, r);
-        const u64 prev = lane ? below : first;
-        const bool head = i < n && (i == 0 || (prev >> abits) != (key[r] >> abits));
-        headbits |= head ? (1u << r) : 0u;
-        const u64 m = __ballot(head);
-        if (lane == 0) wcount[r][wave] = (u32)__popcll(m);
-    }
-    __syncthreads();
-    // wave 0: exclusive offsets of the 32 (round, wave) groups in record order, tile total, look-back
-    if (wave == 0) {
-        const u32 c = lane < PF_IPT * PF_WAVES ? wcount[lane / PF_WAVES][lane % PF_WAVES] : 0u;
-        const u32 incl = ks_wave_incl_scan(c);
-        const u32 total = (u32)__builtin_amdgcn_readlane((int)incl, 63);
-        if (lane < PF_IPT * PF_WAVES) wcount[lane / PF_WAVES][lane % PF_WAVES] = incl - c;
-        if (lane == 0)
-            __hip_atomic_store(&status[tile], (tile == 0 ? KS_LB_PRE : KS_LB_AGG) | (u64)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        u64 excl = 0;
-        if (tile > 0) {
-            excl = ks_lookback_walk(tile, lane, ks_lookback_words(status), &ticket[1]); // gave up: the host reports it
-            if (lane == 0)
-                __hip_atomic_store(&status[tile], KS_LB_PRE | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (lane == 0) {
-            base_s = excl;
-            if (b0 + PF_TILE >= n) *n_rows_out = (u32)(excl + total); // the last tile knows the row count
-        }
-    }
-    __syncthreads();
-    const u64 base = base_s;
-    // sweep 2: rows and per-row sums
-#pragma unroll
-    for (int r = 0; r < PF_IPT; r++) {
-        const u64 i = b0 + (u64)r * PF_THREADS + tid_;
-        const bool live = i < n;
-        const bool head = (headbits >> r) & 1u;
-        const u64 m = __ballot(head);
-        // heads at or before this record, over the whole list, minus one = its row
-        const u64 row64 = base + wcount[r][wave] + ks_lane_lt_count(m) + (head ? 1u : 0u) - 1u;
-        const u32 row = live ? (u32)row64 : 0xffffffffu;
-        u64 w = live ? (key[r] & ((1ULL << abits) - 1ULL)) : 0;
-        u32 c = live ? 1u : 0u;
-        if (head && row < rows_cap) {
-            const u64 ids = key[r] >> abits;
-            qid[row] = (u32)(ids >> tbits);
-            tid[row] = (u32)(ids & ((1ULL << tbits) - 1ULL));
-        }
-        // Inclusive segmented scan (segments = equal row; rows ascend, so a lane whose source has my row continues my segment) with DPP
-        // moves only: four row_shr steps inside the rows of 16, row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3 — the
-        // __shfl_up form was 25 ds_bpermute per round, 213 per thread: the LDS crossbar was this kernel (19 M wave-level permutes
-        // for the 49 M records of a 200k all-vs-all).  A lane without a source reads `rowx`, which is not its row: it adds nothing.
-        {
-            const u32 rowx = row ^ 1u;
-            u32 wl = (u32)w, wh = (u32)(w >> 32);
-#define PF_SEG_STEP(CTRL, RMASK) do { \
-                const u32 orow = (u32)__builtin_amdgcn_update_dpp((int)rowx, (int)row, CTRL, RMASK, 0xf, false); \
-                const u32 oc = (u32)__builtin_amdgcn_update_dpp(0, (int)c, CTRL, RMASK, 0xf, false); \
-                const u32 ol = (u32)__builtin_amdgcn_update_dpp(0, (int)wl, CTRL, RMASK, 0xf, false); \
-                const u32 oh = (u32)__builtin_amdgcn_update_dpp(0, (int)wh, CTRL, RMASK, 0xf, false); \
-                const bool same = orow == row; \
-                const u64 nw_ = (((u64)wh << 32) | wl) + (same ? (((u64)oh << 32) | ol) : 0ULL); \
-                c += same ? oc : 0u; wl = (u32)nw_; wh = (u32)(nw_ >> 32); } while (0)
-            PF_SEG_STEP(0x111, 0xf); // row_shr:1
-            PF_SEG_STEP(0x112, 0xf); // row_shr:2
-            PF_SEG_STEP(0x114, 0xf); // row_shr:4
-            PF_SEG_STEP(0x118, 0xf); // row_shr:8
-            PF_SEG_STEP(0x142, 0xa); // row_bcast:15 -> rows 1 and 3
-            PF_SEG_STEP(0x143, 0xc); // row_bcast:31 -> rows 2 and 3
-#undef PF_SEG_STEP
-            w = ((u64)wh << 32) | wl;
-        }
-        const u32 nrow = (u32)__builtin_amdgcn_update_dpp((int)(row ^ 1u), (int)row, 0x130, 0xf, 0xf, false); // wave_shl:1 (lane 63: not its row)
-        // (Measured dead end: STORING the rows whose records all sit inside one wave — most rows of an all-vs-all search are one or
-        // two records — instead of adding them: 0.45 -> 0.83 ms at 200k x 200k hp.  Scattered 4- / 8-byte stores of a wave cost
-        // more than the same no-return atomics, which the L2 merges line by line.  Handing the head lanes' ids to lanes 0 .. heads-1
-        // through LDS so that qid[] / tid[] leave coalesced: no change, 0.453 ms either way.)
-        if (live && (lane == 63 || nrow != row) && row < rows_cap) {
-            atomicAdd(&isect[row], c);
-            atomicAdd(&nw[row], (unsigned long long)w);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// KS_SEARCH_ABUND_STATS: per-row statistics of the shared target abundances.  The match sort then also orders the abundance
-// bits, so the records of row r — [row_start[r], row_start[r] + isect[r]) of the sorted list — ascend in abundance, and the
-// statistics replay a host loop over the sorted abundances operation for operation: sum += a, mean = sum / n, then
-// ss += (a - mean) * (a - mean), in ascending order, rounded after every operation (no contraction into fma).  Most rows hold
-// one or two records: a lane per row.  A row longer than RA_LONG is listed for k_row_abund_stats_long instead, where a wave
-// loads it 64 records at a time and adds them in order from registers — a self-hit at scaled = 1 is as long as the sequence,
-// and one lane walking it through memory would hold its workgroup's other 255 lanes for the whole walk.
-// ---------------------------------------------------------------------------------------------
-#define RA_LONG 64
-
-__global__ __launch_bounds__(256) void k_row_abund_stats(const u64 *pk, const u64 *row_start, const u32 *isect, const u32 *n_rows_dev,
-                                                         u32 rows_cap, int abits, u64 *median2, double *ss, u32 *long_rows) {
-#pragma clang fp contract(off)
-    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    const u32 n_rows = *n_rows_dev < rows_cap ? *n_rows_dev : rows_cap; // (more rows than the arrays: the host repeats the pass)
-    if (r >= n_rows) return;
-    const u32 n = isect[r];
-    const u64 *a = pk + row_start[r];
-    const u64 am = (1ULL << abits) - 1ULL;
-    if (n > RA_LONG) { long_rows[1 + atomicAdd(&long_rows[0], 1u)] = r; return; }
-    if (n == 0) { median2[r] = 0; ss[r] = 0.0; return; } // (no row: only after a look-back that gave up, which is repeated)
-    double sum = 0.0;
-    for (u32 j = 0; j < n; j++) sum += (double)(a[j] & am);
-    const double mean = sum / (double)n;
-    double acc = 0.0;
-    for (u32 j = 0; j < n; j++) {
-        const double d = (double)(a[j] & am) - mean;
-        acc += d * d;
-    }
-    ss[r] = acc;
-    median2[r] = (n & 1u) ? 2ULL * (a[n / 2] & am) : (a[n / 2 - 1] & am) + (a[n / 2] & am);
-}
-
-// the rows k_row_abund_stats listed: one wave per row (a fixed grid striding over the list); each chunk of 64 records is loaded
-// coalesced, one per lane, and added in order through readlane (every lane keeps the same sums)
-KS_DEV double ra_readlane_f64(double v, int j) {
-    const u64 b = (u64)__double_as_longlong(v);
-    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)b, j), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(b >> 32), j);
-    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
-}
-
-__global__ __launch_bounds__(256) void k_row_abund_stats_long(const u64 *pk, const u64 *row_start, const u32 *isect, const u32 *long_rows,
-                                                              int abits, u64 *median2, double *ss) {
-#pragma clang fp contract(off)
-    const u32 lane = threadIdx.x & 63, n_waves = gridDim.x * (blockDim.x / 64);
-    const u32 n_long = long_rows[0];
-    const u64 am = (1ULL << abits) - 1ULL;
-    for (u32 w = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); w < n_long; w += n_waves) { // (uniform per wave)
-        const u32 r = long_rows[1 + w];
-        const u32 n = isect[r];
-        const u64 *a = pk + row_start[r];
-        double sum = 0.0;
-        for (u32 c = 0; c < n; c += 64) {
-            const double x = c + lane < n ? (double)(a[c + lane] & am) : 0.0;
-            const u32 m = n - c < 64u ? n - c : 64u;
-            for (u32 j = 0; j < m; j++) sum += ra_readlane_f64(x, (int)j);
-        }
-        const double mean = sum / (double)n;
-        double acc = 0.0;
-        for (u32 c = 0; c < n; c += 64) {
-            const double d = c + lane < n ? (double)(a[c + lane] & am) - mean : 0.0;
-            const double t = d * d;
-            const u32 m = n - c < 64u ? n - c : 64u;
-            for (u32 j = 0; j < m; j++) acc += ra_readlane_f64(t, (int)j);
-        }
-        if (lane == 0) {
-            ss[r] = acc;
-            median2[r] = (n & 1u) ? 2ULL * (a[n / 2] & am) : (a[n / 2 - 1] & am) + (a[n / 2] & am);
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// min_containment: a stable compaction of the row columns.  k_rows_keep writes the keep flag of every row (the host's f64
-// test: (double)intersect / (double)|q| >= min_containment, |q| = the query's distinct hashes), an exclusive scan turns the
-// flags into destinations (its total, the kept count, lands beside the row count: one read-back), k_rows_filter moves the kept
-// rows, recomputing the same flag.
-// ---------------------------------------------------------------------------------------------
-struct rf_cols {
-    const u32 *qid, *tid, *isect;
-    const u64 *nw, *median2;
-    const double *ss;
-};
-
-KS_DEV bool rf_kept(const rf_cols &in, u32 r, const u64 *q_offsets, const u32 *q_counts, u32 n_queries, double min_c) {
-    const u32 q = in.qid[r];
-    if (q >= n_queries) return false; // (a row without a head: only after a look-back that gave up, which is repeated)
-    const u64 nq = q_counts ? (u64)q_counts[q] : q_offsets[q + 1] - q_offsets[q];
-    return (double)in.isect[r] / (double)nq >= min_c;
-}
-
-__global__ __launch_bounds__(256) void k_rows_keep(rf_cols in, const u32 *n_rows_dev, u32 rows_cap, const u64 *q_offsets, const u32 *q_counts,
-                                                   u32 n_queries, double min_c, u32 *flags) {
-    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows_cap) return;
-    const u32 n_rows = *n_rows_dev < rows_cap ? *n_rows_dev : rows_cap;
-    flags[r] = (r < n_rows && rf_kept(in, r, q_offsets, q_counts, n_queries, min_c)) ? 1u : 0u;
-}
-
-__global__ __launch_bounds__(256) void k_rows_filter(rf_cols in, const u32 *n_rows_dev, u32 rows_cap, const u64 *q_offsets, const u32 *q_counts,
-                                                     u32 n_queries, double min_c, const u32 *dst, u32 *qid, u32 *tid, u32 *isect, u64 *nw,
-                                                     u64 *median2, double *ss) {
-    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    const u32 n_rows = *n_rows_dev < rows_cap ? *n_rows_dev : rows_cap;
-    if (r >= n_rows || !rf_kept(in, r, q_offsets, q_counts, n_queries, min_c)) return;
-    const u32 o = dst[r];
-    qid[o] = in.qid[r]; tid[o] = in.tid[r]; isect[o] = in.isect[r]; nw[o] = in.nw[r];
-    if (median2) { median2[o] = in.median2[r]; ss[o] = in.ss[r]; }
-}
-
 // ---- one search, in steps: partition of the query postings -> join (+ its segment-cap retry) -> match sort -> row pass
 
 // what the steps of one search share
@@ -1577,136 +1313,8 @@ static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk) {
     return ks_radix_sort_keys(ctx, KS_SORT_PAIRS, Q.pk0, Q.pk0, Q.pk1, n_pairs, shifts, ns, pk);
 }
 
-// the row columns of H (and the statistics) back to the pool
-static void se_free_cols(ks_ctx *ctx, ks_hits *H) {
-    ks_pool_free(ctx, H->d_qid); ks_pool_free(ctx, H->d_tid);
-    if (H->d_block) ks_pool_free(ctx, H->d_block); // (d_isect and d_nw lie inside it)
-    else { ks_pool_free(ctx, H->d_isect); ks_pool_free(ctx, H->d_nw); }
-    ks_pool_free(ctx, H->d_median2); ks_pool_free(ctx, H->d_ss);
-    H->d_qid = H->d_tid = H->d_isect = nullptr;
-    H->d_nw = H->d_block = H->d_median2 = nullptr;
-    H->d_ss = nullptr;
-}
-
-#define RA_LONG_GRID 256 // workgroups of k_row_abund_stats_long (4 waves each, striding over the long rows)
-
-// Behind the row pass of one attempt and before its wait: the statistics into H's columns (Q.stats) and the rows that pass
-// the containment test into F (Q.min_c > 0).  The kernels take the row count from the device (ticket[2]; an attempt with more
-// rows than rows_cap is repeated anyway) and the scan of the keep flags writes the kept count to ticket[3], which the row
-// pass's read-back brings home with the row count: no wait of its own.
-static int se_rows_post(ks_ctx *ctx, const se_search &Q, ks_hits *H, ks_hits *F, const u64 *pk, u32 rows_cap, u32 *ticket, ks_scratch &sc) {
-    const u32 *n_rows_dev = ticket + 2;
-    const u32 g = (rows_cap + 255) / 256;
-    if (Q.stats) {
-        u64 *row_start = nullptr;
-        u32 *long_rows = nullptr; // [0] count, then row ids
-        KS_TRY(sc.alloc(&row_start, (size_t)rows_cap + 1));
-        KS_TRY(sc.alloc(&long_rows, (size_t)rows_cap + 1));
-        KS_TRY(ks_alloc(ctx, &H->d_median2, rows_cap));
-        KS_TRY(ks_alloc(ctx, &H->d_ss, rows_cap));
-        KS_HIP(ctx, hipMemsetAsync(long_rows, 0, sizeof(u32), ctx->stream));
-        KS_TRY(ks_scan_u32_to_u64(ctx, H->d_isect, row_start, rows_cap)); // (rows past the count have intersect 0)
-        KS_LAUNCH(ctx, "row_abund_stats", k_row_abund_stats, g, 256, pk, (const u64 *)row_start, (const u32 *)H->d_isect, n_rows_dev,
-                  rows_cap, Q.abits, H->d_median2, H->d_ss, long_rows);
-        KS_LAUNCH(ctx, "row_abund_stats_long", k_row_abund_stats_long, RA_LONG_GRID, 256, pk, (const u64 *)row_start,
-                  (const u32 *)H->d_isect, (const u32 *)long_rows, Q.abits, H->d_median2, H->d_ss);
-    }
-    if (Q.min_c > 0) {
-        const ks_sketches *q = Q.q;
-        const u32 *counts = q->gapped ? q->d_counts : nullptr; // (a gapped batch: distinct hashes per query; else the CSR's runs)
-        const rf_cols in{H->d_qid, H->d_tid, H->d_isect, H->d_nw, H->d_median2, H->d_ss};
-        u32 *flags = nullptr;
-        KS_TRY(sc.alloc(&flags, rows_cap));
-        KS_LAUNCH(ctx, "rows_keep", k_rows_keep, g, 256, in, n_rows_dev, rows_cap, (const u64 *)q->d_offsets, counts, q->n_seqs, Q.min_c,
-                  flags);
-        KS_TRY(ks_scan_u32_inplace(ctx, flags, rows_cap, ticket + 3));
-        KS_TRY(ks_alloc(ctx, &F->d_qid, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_tid, rows_cap));
-        KS_TRY(ks_alloc(ctx, &F->d_isect, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_nw, rows_cap));
-        if (Q.stats) { KS_TRY(ks_alloc(ctx, &F->d_median2, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_ss, rows_cap)); }
-        KS_LAUNCH(ctx, "rows_filter", k_rows_filter, g, 256, in, n_rows_dev, rows_cap, (const u64 *)q->d_offsets, counts, q->n_seqs, Q.min_c,
-                  (const u32 *)flags, F->d_qid, F->d_tid, F->d_isect, F->d_nw, F->d_median2, F->d_ss);
-    }
-    return KS_OK;
-}
-
-// run-length reduce of the sorted matches into H's rows: one fused pass (k_pair_rows_fused); F: see se_rows_post
-static int se_rows_run(ks_ctx *ctx, const se_search &Q, ks_hits *H, ks_hits &F, const u64 *pk) {
-    const u64 n_pairs = Q.n_pairs;
-    const int tbits = Q.tbits, abits = Q.abits;
-    const u32 pf_tiles = (u32)((n_pairs + PF_TILE - 1) / PF_TILE);
-    // The row count is only known on the device here.  Instead of a round trip before the pass, the row arrays take
-    // their size from the previous search of this context (+ 25 %) and the count is read with the final
-    // synchronisation; a search that produced more rows than that repeats the (cheap) pass with exact arrays.
-    u64 rows_cap = n_pairs;
-    if (ctx->rows_hint && ctx->rows_hint < rows_cap && !ks_dbg(ctx, KS_DBG_NO_ROWS_HINT)) rows_cap = ctx->rows_hint;
-    u32 n_rows = 0;
-    const u32 *pin = (const u32 *)(ctx->h_pin + KS_PIN_ROWS); // ticket pair | row count | kept rows (min_containment)
-    const bool post = Q.stats || Q.min_c > 0;
-    for (int attempt = 0; attempt < 3; attempt++) { // (repeats: more rows than the guess; a look-back that gave up)
-        ks_scratch sc(ctx); // (the statistics' and the filter's scratch of this attempt)
-        KS_TRY(ks_alloc(ctx, &H->d_qid, (size_t)rows_cap)); KS_TRY(ks_alloc(ctx, &H->d_tid, (size_t)rows_cap));
-        // n_weighted (u64) | status words + ticket pair + row count + kept count (u64) | intersect (u32): one block, zeroed
-        // together, per attempt (one memset, one read-back)
-        const size_t st_words = (size_t)pf_tiles + 2, is_words = ((size_t)rows_cap + 1) / 2;
-        KS_TRY(ks_alloc(ctx, &H->d_block, (size_t)rows_cap + st_words + is_words));
-        H->d_nw = H->d_block;
-        H->d_isect = (u32 *)(H->d_block + rows_cap + st_words);
-        unsigned long long *const pf_status = (unsigned long long *)(H->d_block + rows_cap);
-        u32 *const pf_ticket = (u32 *)(pf_status + pf_tiles);
-        KS_HIP(ctx, hipMemsetAsync(H->d_block, 0, ((size_t)rows_cap + st_words + is_words) * sizeof(u64), ctx->stream));
-        KS_LAUNCH(ctx, "pair_rows", k_pair_rows_fused, pf_tiles, PF_THREADS, pk, n_pairs, H->d_qid, H->d_tid, H->d_isect,
-                  (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, pf_ticket + 2,
-                  (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
-        if (post) KS_TRY(se_rows_post(ctx, Q, H, &F, pk, (u32)rows_cap, pf_ticket, sc));
-        {
-            ks_fetch_seg f[2];
-            f[0] = ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4); // ticket pair + row count + kept count
-            const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
-            KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
-        }
-        KS_TRY(ks_scan_status_check(ctx));
-        bool gave_up = pin[1] != 0;
-        if (ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY) && !ctx->rows_use_ticket) gave_up = true; // (tests)
-        if (gave_up) {
-            if (ctx->rows_use_ticket || attempt == 2) return ks_fail(ctx, KS_ERR_HIP, "search: row look-back gave up waiting for a predecessor tile");
-            ctx->rows_use_ticket = true; // dispatch order did not hold here: tickets from now on
-            ctx->rows_ticket_fallbacks++;
-        } else {
-            n_rows = pin[2];
-            if (n_rows <= rows_cap) break;
-            rows_cap = n_rows;
-        }
-        se_free_cols(ctx, H);
-        se_free_cols(ctx, &F);
-    }
-    if (!H->d_qid) return ks_fail(ctx, KS_ERR_HIP, "search: the row pass did not settle");
-    H->n_hits = n_rows;
-    const u64 want = (u64)n_rows + n_rows / 4 + 4096;
-    ctx->rows_hint = want > ctx->rows_hint / 2 ? want : ctx->rows_hint / 2; // follows growth at once, decays slowly
-    if (Q.min_c > 0) { // the kept rows replace the row pass's columns
-        se_free_cols(ctx, H);
-        H->d_qid = F.d_qid; H->d_tid = F.d_tid; H->d_isect = F.d_isect; H->d_nw = F.d_nw;
-        H->d_median2 = F.d_median2; H->d_ss = F.d_ss;
-        H->n_hits = pin[3];
-        memset(&F, 0, sizeof F);
-    }
-    return KS_OK;
-}
-
-static int se_rows(ks_ctx *ctx, const se_search &Q, ks_hits *H, const u64 *pk) {
-    ks_hits F; // the filtered columns (Q.min_c > 0) until they replace H's
-    memset(&F, 0, sizeof F);
-    const int st = se_rows_run(ctx, Q, H, F, pk);
-    se_free_cols(ctx, &F); // (nothing left after a success)
-    return st;
-}
-
-static int se_no_hits(ks_ctx *ctx, ks_hits *H) {
-    KS_TRY(ks_alloc(ctx, &H->d_qid, 1)); KS_TRY(ks_alloc(ctx, &H->d_tid, 1));
-    KS_TRY(ks_alloc(ctx, &H->d_isect, 1)); KS_TRY(ks_alloc(ctx, &H->d_nw, 1));
-    if (H->has_stats) { KS_TRY(ks_alloc(ctx, &H->d_median2, 1)); KS_TRY(ks_alloc(ctx, &H->d_ss, 1)); }
-    return KS_OK;
-}
+// what the row half (ks_rows.hip) needs from a search; a search that matched nothing has n_pairs == 0
+static ks_rows_in se_rows_in(const se_search &Q) { return ks_rows_in{Q.q, Q.n_pairs, Q.tbits, Q.abits, Q.stats, Q.min_c}; }
 
 // Why a search produced nothing and its query batch has to be searched in slices: the match list would hold `pairs` records
 // (more than one list can), or the records of more than `seqs` query sequences would not fit their width.
@@ -1729,7 +1337,7 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, con
         KS_TRY(se_wait_pending(ctx, Q, sketch_redo));
         if ((*stop = Q.stop)) return KS_OK;
     }
-    if (Q.n_q == 0 || n_t == 0) return se_no_hits(ctx, H);
+    if (Q.n_q == 0 || n_t == 0) return ks_search_rows(ctx, se_rows_in(Q), H, nullptr);
     Q.pbits = ix->pbits;
     Q.n_buckets = 1u << Q.pbits;
     // a match is one 8-byte record (qid << tbits | tid) << abits | target abundance, so the match sort moves keys only.  A
@@ -1787,10 +1395,9 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, con
     H->n_pair_instances = Q.n_pairs;
     const u64 want = Q.n_pairs + Q.n_pairs / 8;
     ctx->pair_cap_hint = want > ctx->pair_cap_hint / 2 ? want : ctx->pair_cap_hint / 2; // follows growth at once, decays slowly
-    if (Q.n_pairs == 0) return se_no_hits(ctx, H);
     u64 *pk = nullptr;
-    KS_TRY(se_sort(ctx, Q, sc, &pk));
-    return se_rows(ctx, Q, H, pk);
+    if (Q.n_pairs) KS_TRY(se_sort(ctx, Q, sc, &pk));
+    return ks_search_rows(ctx, se_rows_in(Q), H, pk);
 }
 
 // One search with the whole query batch in one match list.  A non-zero *split on return (with KS_OK and *out == NULL) means
@@ -1911,79 +1518,9 @@ int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hit
     return KS_OK;
 }
 
-// ---------------------------------------------------------------------------------------------
-// union of all sketches with summed abundances: the "combined minhash" of ProteomeIndex::store_signatures
-// (src/rust/index.rs:800-830, add_many_with_abund under a mutex there; here one sort + run-length reduce)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_union_emit(const u64 *keys, const u32 *vals, const u64 *row_start, u32 n_rows,
-                                                    u64 *hashes, u32 *abunds) {
-    u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rows) return;
-    u64 b = row_start[r], e = row_start[r + 1];
-    u64 w = 0;
-    for (u64 j = b; j < e; j++) w += vals[j];
-    hashes[r] = keys[b];
-    abunds[r] = w > 0xffffffffULL ? 0xffffffffu : (u32)w;
-}
-
-static int union_run(ks_ctx *ctx, const ks_sketches *in, ks_sketches *U) {
-    const u64 n = in->n_hashes;
-    KS_TRY(ks_alloc(ctx, &U->d_offsets, 2));
-    if (n == 0) {
-        KS_HIP(ctx, hipMemsetAsync(U->d_offsets, 0, 2 * sizeof(u64), ctx->stream));
-        KS_TRY(ks_alloc(ctx, &U->d_hashes, 1)); KS_TRY(ks_alloc(ctx, &U->d_abunds, 1));
-        KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return KS_OK;
-    }
-    u64 *k0 = nullptr, *k1 = nullptr, *row_start = nullptr;
-    u32 *v0 = nullptr, *v1 = nullptr, *heads = nullptr, *d_nrows = nullptr;
-    ks_scratch sc(ctx);
-    KS_TRY(sc.alloc(&k0, (size_t)n)); KS_TRY(sc.alloc(&k1, (size_t)n));
-    KS_TRY(sc.alloc(&v0, (size_t)n)); KS_TRY(sc.alloc(&v1, (size_t)n));
-    const int shifts[8] = {0, 8, 16, 24, 32, 40, 48, 56};
-    u64 *ks = nullptr;
-    u32 *vs = nullptr;
-    KS_TRY(ks_radix_sort_u32(ctx, KS_SORT_PAIRS, in->d_hashes, in->d_abunds, k0, v0, k1, v1, n, shifts, 8, &ks, &vs));
-    KS_TRY(sc.alloc(&heads, (size_t)n));
-    KS_TRY(sc.alloc(&d_nrows, 1));
-    const u32 g = (u32)((n + 255) / 256);
-    KS_LAUNCH(ctx, "pair_heads", k_pair_heads, g, 256, (const u64 *)ks, n, heads);
-    KS_TRY(ks_scan_u32_inplace(ctx, heads, n, d_nrows));
-    u64 *const rb = ctx->h_pin + KS_PIN_READ;
-    KS_HIP(ctx, hipMemcpyAsync(rb, d_nrows, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const u32 n_rows = *(u32 *)rb;
-    U->n_hashes = U->n_slots = n_rows;
-    KS_TRY(sc.alloc(&row_start, (size_t)n_rows + 1));
-    KS_TRY(ks_alloc(ctx, &U->d_hashes, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &U->d_abunds, (size_t)n_rows));
-    KS_LAUNCH(ctx, "pair_rows", k_pair_rows, g, 256, (const u64 *)ks, (const u32 *)heads, n, n_rows, row_start);
-    KS_LAUNCH(ctx, "union_emit", k_union_emit, (n_rows + 255) / 256, 256, (const u64 *)ks, (const u32 *)vs, (const u64 *)row_start, n_rows,
-              U->d_hashes, U->d_abunds);
-    rb[0] = 0; rb[1] = n_rows;
-    KS_HIP(ctx, hipMemcpyAsync(U->d_offsets, rb, 2 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    KS_TRY(ks_scan_status_fetch(ctx));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return ks_scan_status_check(ctx);
-}
-
 int ks_search_opts_check(ks_ctx *ctx, const ks_search_opts *o) {
     if (!o) return KS_OK;
-    const char *why = o->reserved ? "reserved must be 0"
-                    : (o->flags & ~KS_SEARCH_ABUND_STATS) ? "unknown flags"
-                    : !(o->min_containment >= 0.0) ? "min_containment must be >= 0 (and not NaN)" : nullptr;
-    if (!why) return KS_OK;
-    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "search options: %s", why) : KS_ERR_INVALID_ARG;
-}
-
-int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out) {
-    if (!in || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(in)));
-    ks_sketches *U = new ks_sketches();
-    memset(U, 0, sizeof *U);
-    U->ctx = ctx; U->params = in->params; U->n_seqs = 1; U->n_windows = in->n_windows;
-    const int st = union_run(ctx, in, U);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_sketches_free(U); return st; }
-    *out = U;
-    return KS_OK;
+    KS_TRY(ks_opts_words_check(ctx, "search", o->flags, KS_SEARCH_ABUND_STATS, o->reserved));
+    if (o->min_containment >= 0.0) return KS_OK;
+    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "search options: min_containment must be >= 0 (and not NaN)") : KS_ERR_INVALID_ARG;
 }

@@ -7,7 +7,7 @@
 // IEEE f64, one rounding per operation (no contraction into fma), no reassociation: bit-identical to a host loop that does
 // the same.  idf[] is made on the host with libm's log and uploaded — the device never evaluates a logarithm.
 //
-//   corpus   per sketch set, once: the hashes sorted (the union's sort), one run-length pass -> per distinct hash its abundance
+//   corpus   per sketch set, once: the hashes sorted and cut into runs (ks_sorted_runs) -> per distinct hash its abundance
 //            sum (u64, exact), the number of sketches that hold it, and the set's grand total
 //   weights  one pass over the query CSR (a wave per query): the query's abundance sum, then per posting both corpus tables
 //            searched and the two products stored as f64 (pw, tw) — a row only adds
@@ -22,12 +22,8 @@
 #include "ks_device.h"
 
 #define SG_CUT 128        // |q| + |t| above this: the wave path (KS_DEBUG_SIGNIF_WAVE_ROWS = 1 / 0 sends every row one way)
-#define SG_WAVE_GRID 1024 // workgroups of k_sg_rows_wave (4 waves each, striding over the listed rows)
+#define SG_WAVE_GRID 1024 // workgroups of k_sg_rows_wave (4 waves each, striding over the listed rows; see RA_LONG_GRID, ks_rows.hip)
 enum { SG_BAD_ID = 0, SG_BAD_COUNT = 1, SG_BAD_CORPUS = 2 }; // words of the control block
-
-// the run boundaries of a sorted key list, as the union takes them (ks_search.hip)
-__global__ __launch_bounds__(256) void k_pair_heads(const u64 *keys, u64 n, u32 *heads);
-__global__ __launch_bounds__(256) void k_pair_rows(const u64 *keys, const u32 *hidx, u64 n, u32 n_rows, u64 *row_start);
 
 struct ks_corpus {
     ks_ctx *ctx;
@@ -56,13 +52,12 @@ __global__ __launch_bounds__(256) void k_corpus_emit(const u64 *keys, const u32 
     u32 d = 0;
     if (r < n_rows) {
         const u64 b = row_start[r], e = row_start[r + 1];
-        for (u64 j = b; j < e; j++) w += vals[j];
+        w = ks_run_abund_sum(vals, b, e);
         d = (u32)(e - b); // a sketch holds a hash once: postings of the run = sketches that hold it
         hashes[r] = keys[b]; sums[r] = w; df[r] = d;
     }
     const u64 ws = ks_wave_sum64(w);
-#pragma unroll
-    for (int s = 32; s; s >>= 1) { const u32 o = (u32)__shfl_xor((int)d, s); d = o > d ? o : d; }
+    d = ks_wave_max_u32(d);
     if ((threadIdx.x & 63) == 0) {
         if (ws) atomicAdd(&acc[0], (unsigned long long)ws);
         atomicMax(&acc[1], (unsigned long long)d);
@@ -76,35 +71,18 @@ static int corpus_run(ks_ctx *ctx, const ks_sketches *in, ks_corpus *C) {
         return KS_OK;
     }
     if (n >= 0xfffffff0ULL) return ks_fail(ctx, KS_ERR_CAPACITY, "corpus: %llu postings exceed one sort", (unsigned long long)n);
-    u64 *k0 = nullptr, *k1 = nullptr, *row_start = nullptr, *acc = nullptr;
-    u32 *v0 = nullptr, *v1 = nullptr, *heads = nullptr, *d_nrows = nullptr;
     ks_scratch sc(ctx);
-    KS_TRY(sc.alloc(&k0, (size_t)n)); KS_TRY(sc.alloc(&k1, (size_t)n));
-    KS_TRY(sc.alloc(&v0, (size_t)n)); KS_TRY(sc.alloc(&v1, (size_t)n));
-    const int shifts[8] = {0, 8, 16, 24, 32, 40, 48, 56};
-    u64 *ks = nullptr;
-    u32 *vs = nullptr;
-    KS_TRY(ks_radix_sort_u32(ctx, KS_SORT_PAIRS, in->d_hashes, in->d_abunds, k0, v0, k1, v1, n, shifts, 8, &ks, &vs));
-    KS_TRY(sc.alloc(&heads, (size_t)n));
-    KS_TRY(sc.alloc(&d_nrows, 1));
+    ks_runs R;
+    KS_TRY(ks_sorted_runs(ctx, in, sc, &R));
+    const u32 n_rows = R.n_rows;
+    u64 *acc = nullptr;
     KS_TRY(sc.alloc(&acc, 2));
     KS_HIP(ctx, hipMemsetAsync(acc, 0, 2 * sizeof(u64), ctx->stream));
-    const u32 g = (u32)((n + 255) / 256);
-    KS_LAUNCH(ctx, "pair_heads", k_pair_heads, g, 256, (const u64 *)ks, n, heads);
-    KS_TRY(ks_scan_u32_inplace(ctx, heads, n, d_nrows));
-    u64 *const rb = ctx->h_pin + KS_PIN_READ;
-    KS_HIP(ctx, hipMemcpyAsync(rb, d_nrows, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-    KS_TRY(ks_scan_status_fetch(ctx));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    KS_TRY(ks_scan_status_check(ctx));
-    const u32 n_rows = *(u32 *)rb;
-    if (n_rows == 0 || n_rows > n) return ks_fail(ctx, KS_ERR_HIP, "internal error: %u runs in %llu sorted postings", n_rows, (unsigned long long)n);
     C->n_hashes = n_rows;
-    KS_TRY(sc.alloc(&row_start, (size_t)n_rows + 1));
     KS_TRY(ks_alloc(ctx, &C->d_hash, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &C->d_sum, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &C->d_df, (size_t)n_rows));
-    KS_LAUNCH(ctx, "pair_rows", k_pair_rows, g, 256, (const u64 *)ks, (const u32 *)heads, n, n_rows, row_start);
-    KS_LAUNCH(ctx, "corpus_emit", k_corpus_emit, (n_rows + 255) / 256, 256, (const u64 *)ks, (const u32 *)vs, (const u64 *)row_start, n_rows,
-              C->d_hash, C->d_sum, C->d_df, (unsigned long long *)acc);
+    KS_LAUNCH(ctx, "corpus_emit", k_corpus_emit, (n_rows + 255) / 256, 256, (const u64 *)R.keys, (const u32 *)R.vals, (const u64 *)R.row_start,
+              n_rows, C->d_hash, C->d_sum, C->d_df, (unsigned long long *)acc);
+    u64 *const rb = ctx->h_pin + KS_PIN_READ;
     KS_HIP(ctx, hipMemcpyAsync(rb, acc, 2 * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     C->total = rb[0];
@@ -154,16 +132,6 @@ extern "C" void ks_corpus_free(ks_corpus *c) {
 }
 
 // ---- weights ---------------------------------------------------------------------------------------------------------------
-// number of entries of a[0, n) below h
-KS_DEV u32 sg_lower_bound(const u64 *a, u32 n, u64 h) {
-    u32 lo = 0, hi = n;
-    while (lo < hi) {
-        const u32 mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < h) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 struct sg_table {
     const u64 *hash, *sum;
     const u32 *df;
@@ -184,7 +152,7 @@ __global__ __launch_bounds__(256) void k_sg_weights(const u64 *q_off, const u64 
     const double q_sum = (double)ks_wave_sum64(part);
     for (u64 j = b + lane; j < e; j += 64) {
         const u64 h = q_hash[j];
-        const u32 iq = sg_lower_bound(CQ.hash, CQ.n, h), it = sg_lower_bound(CT.hash, CT.n, h);
+        const u32 iq = ks_lower_bound_u64(CQ.hash, CQ.n, h), it = ks_lower_bound_u64(CT.hash, CT.n, h);
         const bool in_q = iq < CQ.n && CQ.hash[iq] == h, in_t = it < CT.n && CT.hash[it] == h;
         if (!in_q) atomicOr(flag, 1ULL);
         double p = 0.0, t = 0.0;
@@ -209,12 +177,6 @@ struct sg_rows_in {
 // bad[why] = the first row that cannot be right for that reason
 KS_DEV void sg_bad(unsigned long long *bad, u32 r, u32 why) { atomicMin(&bad[why], (unsigned long long)r); }
 
-KS_DEV double sg_readlane_f64(double v, int j) {
-    const u64 b = (u64)__double_as_longlong(v);
-    const u32 lo = (u32)__builtin_amdgcn_readlane((int)(u32)b, j), hi = (u32)__builtin_amdgcn_readlane((int)(u32)(b >> 32), j);
-    return __longlong_as_double((long long)(((u64)hi << 32) | lo));
-}
-
 // A lane per row.  mode: 0 every row here, 1 every row to the wave kernel, 2 by length.  wave_rows[0] counts the listed rows.
 __global__ __launch_bounds__(256) void k_sg_rows(sg_rows_in R, int mode, double *prob, double *tfidf, u32 *wave_rows, unsigned long long *bad) {
 #pragma clang fp contract(off)
@@ -224,7 +186,7 @@ __global__ __launch_bounds__(256) void k_sg_rows(sg_rows_in R, int mode, double 
     if (q >= R.n_q || t >= R.n_t) { sg_bad(bad, r, SG_BAD_ID); prob[r] = 0.0; tfidf[r] = 0.0; return; }
     const u64 qb = R.q_off[q], tb = R.t_off[t];
     const u32 nq = (u32)(R.q_off[q + 1] - qb), nt = (u32)(R.t_off[t + 1] - tb);
-    if (mode == 1 || (mode == 2 && (u64)nq + nt > SG_CUT)) { wave_rows[1 + atomicAdd(&wave_rows[0], 1u)] = r; return; }
+    if (mode == 1 || (mode == 2 && (u64)nq + nt > SG_CUT)) { ks_row_list_push(wave_rows, r); return; }
     // the shorter run is walked, the longer one searched — from where the last search ended: both ascend
     const bool walk_q = nq <= nt;
     const u64 *wh = walk_q ? R.q_hash + qb : R.t_hash + tb, *sh = walk_q ? R.t_hash + tb : R.q_hash + qb;
@@ -233,7 +195,7 @@ __global__ __launch_bounds__(256) void k_sg_rows(sg_rows_in R, int mode, double 
     u32 cnt = 0, from = 0;
     for (u32 i = 0; i < nw && from < ns; i++) {
         const u64 h = wh[i];
-        from += sg_lower_bound(sh + from, ns - from, h);
+        from += ks_lower_bound_u64(sh + from, ns - from, h);
         if (from < ns && sh[from] == h) {
             const u64 p = qb + (walk_q ? i : from); // the QUERY posting: the weights are its
             po += R.pw[p];
@@ -245,14 +207,11 @@ __global__ __launch_bounds__(256) void k_sg_rows(sg_rows_in R, int mode, double 
     prob[r] = po; tfidf[r] = tf;
 }
 
-// The listed rows, one wave per row (a fixed grid striding over the list).  Each chunk of 64 hashes of the shorter run is loaded
-// coalesced, every lane searches the longer run for its hash, and the shared ones' terms are added in lane order: ascending hash.
+// The listed rows, a wave per row (ks_row_list_walk).  Each chunk of 64 hashes of the shorter run is loaded coalesced, every lane
+// searches the longer run for its hash, and the shared ones' terms are added in lane order: ascending hash.
 __global__ __launch_bounds__(256) void k_sg_rows_wave(sg_rows_in R, const u32 *wave_rows, double *prob, double *tfidf, unsigned long long *bad) {
-#pragma clang fp contract(off)
-    const u32 lane = threadIdx.x & 63, n_waves = gridDim.x * (blockDim.x / 64);
-    const u32 n_list = wave_rows[0] < R.n_rows ? wave_rows[0] : R.n_rows;
-    for (u32 w = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); w < n_list; w += n_waves) { // (uniform per wave)
-        const u32 r = wave_rows[1 + w];
+    const u32 lane = threadIdx.x & 63;
+    ks_row_list_walk(wave_rows, R.n_rows, [&](u32 r) {
         const u32 q = R.qid[r], t = R.tid[r]; // (in range: k_sg_rows lists no other row)
         const u64 qb = R.q_off[q], tb = R.t_off[t];
         const u32 nq = (u32)(R.q_off[q + 1] - qb), nt = (u32)(R.t_off[t + 1] - tb);
@@ -267,36 +226,20 @@ __global__ __launch_bounds__(256) void k_sg_rows_wave(sg_rows_in R, const u32 *w
             u32 at = 0;
             if (i < nw) {
                 const u64 h = wh[i];
-                at = sg_lower_bound(sh, ns, h);
+                at = ks_lower_bound_u64(sh, ns, h);
                 found = at < ns && sh[at] == h;
             }
             const u64 p = qb + (walk_q ? i : at);
             const double x = found ? R.pw[p] : 0.0, y = found ? R.tw[p] : 0.0;
-            u64 m = __ballot(found);
+            const u64 m = __ballot(found);
             cnt += (u32)__popcll((long long)m);
-            while (m) { // (uniform: every lane keeps the same sums)
-                const int j = __ffsll((long long)m) - 1;
-                m &= m - 1;
-                po += sg_readlane_f64(x, j);
-                tf += sg_readlane_f64(y, j);
-            }
+            ks_wave_add_ordered(m, po, x, tf, y);
         }
         if (lane == 0) {
             if (cnt != R.isect[r]) sg_bad(bad, r, SG_BAD_COUNT);
             prob[r] = po; tfidf[r] = tf;
         }
-    }
-}
-
-static int signif_opts_check(ks_ctx *ctx, const ks_signif_opts *o) {
-    if (!o) return KS_OK;
-    const char *why = o->reserved ? "reserved must be 0" : o->flags ? "unknown flags" : nullptr;
-    if (!why) return KS_OK;
-    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "significance options: %s", why) : KS_ERR_INVALID_ARG;
-}
-
-static bool sg_same_params(const ks_params &a, const ks_params &b) {
-    return a.ksize == b.ksize && a.scaled == b.scaled && a.moltype == b.moltype && a.seed == b.seed && a.flags == b.flags;
+    });
 }
 
 static int signif_run(ks_ctx *ctx, const ks_sketches *Q, const ks_sketches *T, const ks_corpus *CQ, const ks_corpus *CT, const ks_hits *H,
@@ -312,15 +255,14 @@ static int signif_run(ks_ctx *ctx, const ks_sketches *Q, const ks_sketches *T, c
 
     ks_scratch sc(ctx);
     double *pw = nullptr, *tw = nullptr, *idf = nullptr;
-    u32 *wave_rows = nullptr;
+    u32 *wave_rows = nullptr; // the rows of k_sg_rows_wave
     u64 *ctl = nullptr; // [SG_BAD_ID], [SG_BAD_COUNT]: the first such row (all ones: none); [SG_BAD_CORPUS]: a query hash outside the query corpus
     KS_TRY(sc.alloc(&pw, (size_t)Q->n_hashes)); KS_TRY(sc.alloc(&tw, (size_t)Q->n_hashes));
     KS_TRY(sc.alloc(&idf, (size_t)CT->max_doc_freq + 1));
-    KS_TRY(sc.alloc(&wave_rows, (size_t)n_rows + 1));
+    KS_TRY(ks_row_list_alloc(ctx, sc, (size_t)n_rows, &wave_rows));
     KS_TRY(sc.alloc(&ctl, 3));
     KS_HIP(ctx, hipMemsetAsync(ctl, 0xff, 2 * sizeof(u64), ctx->stream));
     KS_HIP(ctx, hipMemsetAsync(ctl + SG_BAD_CORPUS, 0, sizeof(u64), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(wave_rows, 0, sizeof(u32), ctx->stream));
     // smooth idf over the document frequencies the target corpus holds: libm's log, here on the host
     std::vector<double> h_idf((size_t)CT->max_doc_freq + 1);
     for (size_t d = 0; d < h_idf.size(); d++) h_idf[d] = std::log(((double)1 + (double)T->n_seqs) / ((double)1 + (double)d)) + 1.0;
@@ -357,14 +299,14 @@ static int signif_run(ks_ctx *ctx, const ks_sketches *Q, const ks_sketches *T, c
 extern "C" int ks_hits_significance(ks_ctx *ctx, const ks_sketches *queries, const ks_sketches *targets, const ks_corpus *q_corpus,
                                     const ks_corpus *t_corpus, const ks_hits *hits, const ks_signif_opts *opts, ks_signif **out) {
     return ks_guard(ctx, [&]() -> int {
-    KS_TRY(signif_opts_check(ctx, opts));
+    if (opts) KS_TRY(ks_opts_words_check(ctx, "significance", opts->flags, 0, opts->reserved));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!queries || !targets || !q_corpus || !t_corpus || !hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
     if (queries->ctx != ctx || targets->ctx != ctx || q_corpus->ctx != ctx || t_corpus->ctx != ctx || hits->ctx != ctx)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: an input of another context");
     const ks_params &a = queries->params, &b = targets->params;
-    if (!sg_same_params(a, b))
+    if (!ks_same_params(a, b))
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: the sketch sets were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)",
                        a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
     const struct { const ks_corpus *c; const ks_sketches *s; const char *side; } pairs[2] = {{q_corpus, queries, "query"}, {t_corpus, targets, "target"}};
@@ -372,7 +314,7 @@ extern "C" int ks_hits_significance(ks_ctx *ctx, const ks_sketches *queries, con
         if (p.c->n_docs != p.s->n_seqs)
             return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: the %s corpus counts %u sketches, the %s set holds %u: a corpus of another set",
                            p.side, p.c->n_docs, p.side, p.s->n_seqs);
-        if (!sg_same_params(p.c->params, p.s->params) || p.c->n_postings != p.s->n_hashes)
+        if (!ks_same_params(p.c->params, p.s->params) || p.c->n_postings != p.s->n_hashes)
             return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: the %s corpus was built from another set (parameters or size differ)", p.side);
     }
     KS_HIP(ctx, hipSetDevice(ctx->device));

@@ -131,14 +131,6 @@ KS_DEV u32 sk_bucket_mul(u32 nw, u32 sfix) {
     return m > 0xffffffffULL ? 0xffffffffu : (u32)m;
 }
 
-KS_DEV u32 sk_lower_bound(const u64 *a, u32 lo, u32 hi, u64 x) { // first i in [lo,hi) with a[i] >= x
-    while (lo < hi) {
-        u32 mid = lo + ((hi - lo) >> 1);
-        if (a[mid] < x) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-
 // hash of the window that starts at LDS byte `pos8 + I` where pos8 is 8-byte aligned.  KC != 0: k is the compile-time
 // constant KC (the launches of the common k-mer sizes): the block loop, the tail branches and the byte masks fold away and a
 // tail of <= 4 bytes multiplies as a 32-bit value — ~56 instead of ~90 vector instructions per window at k = 10, where
@@ -429,7 +421,7 @@ __global__ __launch_bounds__(256) void k_pack_fill(const u64 *offs, u32 n_seqs, 
 __global__ __launch_bounds__(256) void k_tile_plan(const u64 *offs, u32 n_seqs, u32 n_tiles, u32 R, u32 *tile_first) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t > n_tiles) return;
-    tile_first[t] = t == n_tiles ? n_seqs : sk_lower_bound(offs, 0, n_seqs, (u64)t * R);
+    tile_first[t] = t == n_tiles ? n_seqs : ks_lower_bound_u64(offs, n_seqs, (u64)t * R);
 }
 
 // Compacting variant, windows [p0 + H, p0 + H + NW) of a thread: hash, keep what passes the threshold, append to the LDS list
@@ -1613,7 +1605,7 @@ __global__ __launch_bounds__(256) void k_kmerpos_plan(const u64 *offs, u32 n_seq
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t > n_tiles) return;
     // first s with offs[s + 1] > t * KP_R
-    tile_first[t] = sk_lower_bound(offs + 1, 0, n_seqs, (u64)t * KP_R + 1);
+    tile_first[t] = ks_lower_bound_u64(offs + 1, n_seqs, (u64)t * KP_R + 1);
 }
 
 __global__ __launch_bounds__(SK_THREADS) void k_kmerpos_tiles(kp_args A) {

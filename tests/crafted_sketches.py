@@ -4,7 +4,8 @@ Every other search test starts from residues, so every hash it ever saw came out
 window count.  The families here are valid inputs of ks_sketches_from_host (strictly ascending per sequence,
 0 < h <= max_hash(scaled)) that sit on the edges of the search arithmetic instead: hashes on the join-bucket boundaries, all
 postings in one bucket, buckets of one key, consecutive integers, match records that use all 64 bits, abundances 0 and
-2^32 - 1, abundance sums around the union's saturation point.  Each family asserts its own property while it is built, so
+2^32 - 1, abundance sums around the union's saturation point, rows whose lengths sit on the thresholds of the lane / wave
+row splits.  Each family asserts its own property while it is built, so
 importing the case proves the input is what its name says.  No GPU is needed here (tests/test_crafted_cpu.py).
 
 families() yields (name, ksize, scaled, moltype, T, Q) with T = (offs u64, mins u64, ab u32) and Q likewise."""
@@ -320,11 +321,53 @@ def union_saturation():
     return "union_saturation", 10, 1, "protein", T, Q
 
 
+ROW_SHARED = (1, 2, 63, 64, 65, 127, 128, 129, 192, 193)  # both sides of RA_LONG (ks_rows.hip) and of the 64-element chunk edges
+RA_LONG = 64   # a row with more shared hashes is listed for the wave kernel of the statistics
+SG_CUT = 128   # |q| + |t| above it: the wave kernel of the significance pass (ks_signif.hip)
+
+
+def row_lengths():
+    """Rows whose lengths sit on the thresholds of the two lane / wave splits: query 0 holds 193 hashes and target i shares
+    exactly ROW_SHARED[i] of them (a random subset) beside five of its own; query 1 holds 64 hashes, and the last two targets,
+    of 64 and 65 hashes, make |q| + |t| 128 and 129 with it.  Abundances come from the edge set on both sides."""
+    rng = np.random.default_rng(108)
+    edges = np.asarray(ABUND_EDGES, np.uint32)
+    pool = np.unique(rng.integers(1 << 20, 1 << 63, 700, dtype=np.uint64) * np.uint64(2))  # even; the targets' own hashes are odd
+    q0, q1 = pool[:193], pool[193:257]
+    assert len(pool) >= 257 and len(q0) == 193 and len(q1) == 64
+    want, seq, h = {}, [], []
+    for t, n in enumerate(ROW_SHARED):
+        hs = rng.choice(q0, n, replace=False).tolist() + [2 * (10 * t + j) + 1 for j in range(5)]
+        seq += [t] * len(hs); h += hs
+        want[(0, t)] = n
+    for t, (n, size) in enumerate(((40, 64), (41, 65)), len(ROW_SHARED)):
+        hs = rng.choice(q1, n, replace=False).tolist() + [2 * (10 * t + j) + 1 for j in range(size - n)]
+        seq += [t] * len(hs); h += hs
+        want[(1, t)] = n
+    n_t = len(ROW_SHARED) + 2
+    T = _csr(seq, h, rng.choice(edges, len(h)), n_t)
+    qh = np.concatenate([q0, q1])
+    Q = _csr([0] * 193 + [1] * 64, qh, rng.choice(edges[1:], len(qh)), 2)
+    rows = ref_join(T, Q)
+    got = {(int(q), int(t)): int(n) for q, t, n in zip(rows[0], rows[1], rows[2])}
+    assert got == want, got  # the intersect of every row is the intended number, and there is no other row
+    assert set(ROW_SHARED) >= {RA_LONG - 1, RA_LONG, RA_LONG + 1, 127, 128, 129, 192, 193}
+    sizes_q, sizes_t = np.diff(Q[0]).astype(np.int64), np.diff(T[0]).astype(np.int64)
+    assert sorted(int(sizes_q[q] + sizes_t[t]) for q, t in want if q == 1) == [SG_CUT, SG_CUT + 1]
+    assert int(sizes_q[0]) == 193 and all(int(sizes_q[0] + sizes_t[t]) > SG_CUT for q, t in want if q == 0)
+    for (q, t), n in want.items():  # every long row mixes abundances: the order of its f64 additions shows
+        if n >= RA_LONG - 1:
+            ab = _seq((T[0], T[2], None), t)
+            assert len(set(ab.tolist())) >= 4
+    return "row_lengths", 10, 1, "protein", T, Q
+
+
 _BUILDERS = ([lambda s=s: prefix_edges(s) for s in PREFIX_SCALED] +
              [one_bucket, flat_bucket_single, flat_bucket_runs, lambda: consecutive(1), lambda: consecutive(5), wide_records, zero_abund,
-              union_saturation])
+              union_saturation, row_lengths])
 NAMES = [f"prefix_edges_s{s}" for s in PREFIX_SCALED] + ["one_bucket", "flat_bucket_single", "flat_bucket_runs", "consecutive_s1",
-                                                         "consecutive_s5", "wide_records", "zero_abund", "union_saturation"]
+                                                         "consecutive_s5", "wide_records", "zero_abund", "union_saturation",
+                                                         "row_lengths"]
 _CACHE = {}
 
 

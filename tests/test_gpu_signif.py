@@ -219,6 +219,21 @@ def test_crafted_sketches_on_both_row_paths(monkeypatch):
             assert hits[2][r] == 1 and tf[r] == 9.0 / 10.0
 
 
+def test_row_lengths_family_on_both_row_paths(monkeypatch):
+    """rows on both sides of SG_CUT and of the 64-hash chunk edges of the wave kernel (crafted_sketches.row_lengths)"""
+    _, k, scaled, mol, T, Q = cs.family("row_lengths")
+    assert cs.SG_CUT == SG_CUT
+    want_hits = signif_ref.join(Q, T)
+    assert want_hits[2].tolist() == list(cs.ROW_SHARED) + [40, 41]
+    with ks.Context(0, follow_debug_env=True) as c:
+        for mode in MODES:
+            if mode is None:
+                monkeypatch.delenv("KS_DEBUG_SIGNIF_WAVE_ROWS", raising=False)
+            else:
+                monkeypatch.setenv("KS_DEBUG_SIGNIF_WAVE_ROWS", mode)
+            _compare(c, Q, T, k, scaled, mol, want_hits=want_hits)
+
+
 # ---- corpus ----------------------------------------------------------------------------------------------------------------
 def _corpus_case(ctx, S, k, scaled, mol):
     d = _upload(ctx, S, k, scaled, mol)
