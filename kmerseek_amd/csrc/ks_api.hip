@@ -213,7 +213,7 @@ extern "C" void ks_sketches_free(ks_sketches *s) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// k-mer positions (ProteomeIndex::process_kmers, src/rust/index.rs:749-786): k_kmerpos_tiles in ks_sketch.hip.
+// k-mer positions (ProteomeIndex::process_kmers, src/rust/index.rs:749-786): k_kmerpos_tiles in ks_kmerpos.hip.
 // NOTE: the Rust path hashes the validated sequence as given (no upper-casing inside process_kmers);
 // inputs that reach it are already upper-case, so the LUT's case folding is unobservable.
 // ---------------------------------------------------------------------------------------------

@@ -429,6 +429,15 @@ bool ks_scan_status_seg(ks_ctx *ctx, ks_fetch_seg *out);
 int ks_join_pbits(const ks_ctx *ctx, u64 n_postings, u64 per_bucket);
 // multiplier of ks_join_prefix (ks_device.h) for a join on pbits prefix bits of hashes kept below max_hash
 u32 ks_join_prefix_mul(int pbits, u64 max_hash);
+// ---- the deferred sequences of a sketch call (ks_sketch_long.hip) ----
+struct sk_args; // the launch arguments of a sketch call (ks_tile.h)
+// their lists (n_cls[0] medium, n_cls[1] long ones listed, on the device) and the side buffers their runs are produced in
+struct ks_deferred { u32 *med_ids, *long_ids, *n_cls; u64 *lg_hash; u32 *lg_abund; };
+// the listed long sequences (at most n_long, none longer than max_len) sketched into the side buffers; the slabs come from sc
+int ks_sketch_long_launch(ks_ctx *ctx, const sk_args &A, const ks_deferred &D, u64 n_long, u32 max_len, ks_scratch &sc);
+// after the shared tiles (A: their launch): the runs of the listed medium / long sequences into their CSR slots
+int ks_sketch_place_launch(ks_ctx *ctx, const sk_args &A, const ks_deferred &D, u64 n_med, u64 n_long);
+// ---- k-mer positions (ks_kmerpos.hip, ks_api.hip) ----
 int ks_kmerpos_tiles_launch(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res, const ks_params *p, u32 *d_seq,
                             u32 *d_start, u64 *d_hash, u64 *n_out);
 int ks_kmerpos_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res,

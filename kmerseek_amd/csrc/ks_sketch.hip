@@ -24,16 +24,13 @@
 //     look-back over the tiles' distinct counts gives the tile its place in the final CSR: one coalesced stream out.
 //   * A sequence that starts inside a tile's residue range but does not END inside the tile's LDS window (at most
 //     one per tile, the last) is deferred: if it fits a tile on its own ("medium") it gets one in a second launch of
-//     the same kernel; longer ones take the same algorithm with its arrays in a global scratch slab (k_sketch_long),
-//     one workgroup per sequence.  (Packed tiles — the plain variant — hold whole sequences: only sequences longer than a
-//     tile go to the slab path.)
-#include "ks_device.h"
+//     the same kernel; longer ones take the same algorithm with its arrays in a global scratch slab (k_sketch_long,
+//     ks_sketch_long.hip), one workgroup per sequence.  (Packed tiles — the plain variant — hold whole sequences: only
+//     sequences longer than a tile go to the slab path.)
+// What a kernel needs to stage and hash a tile (sizes, sk_args, sk_load16 / sk_encode16, sk_hash_windows) is ks_tile.h;
+// the k-mer position table, which uses the same kit, is ks_kmerpos.hip.
+#include "ks_tile.h"
 
-#ifndef SK_THREADS
-#define SK_THREADS 512
-#endif
-#define SK_E 8
-#define SK_TILE (SK_THREADS * SK_E) // 4096 LDS positions
 #define SK_MED_MAX (SK_TILE - 16)   // longest sequence that still fits one tile on its own ("medium")
 // Tile t takes the sequences that START in residues [t * R, (t+1) * R) and stages SK_TILE bytes from t * R: a larger
 // stride R fills more of the tile's positions with windows but defers more sequences (one that starts at local position
@@ -42,7 +39,6 @@
 // saves ~26 ns, a deferred sequence costs ~45 ns (MI355X, 1M-protein batches).
 #define SK_NR 8
 static const u32 sk_r_cand_host[SK_NR] = {2544, 2800, 3056, 3312, 3568, 3824, 3952, 4016};
-#define SK_PAD 160                  // >= KS_MAX_KSIZE + 24: slack behind the last residue for word reads
 #ifndef SK_MINW
 #define SK_MINW 6                   // waves per SIMD to compile for: 3 workgroups of 8 waves per CU
 #endif
@@ -73,138 +69,6 @@ extern "C" void ks_debug_read_stamps(unsigned long long *out, int reset) {
 #else
 #define SK_STAMP_AT(i) do { } while (0)
 #endif
-
-struct sk_args {
-    const u8 *res;
-    const u64 *offs;
-    u32 n_seqs;
-    u64 n_res;
-    u32 k;
-    u64 seed;
-    u64 max_hash;
-    u32 sfix;     // floor(2^48 / ((max_hash >> 32) + 1)): bucket multiplier = (n_windows * sfix) >> 16
-    const u8 *lut; // 256-byte encode table for this moltype
-    u32 upper_only; // the table only upper-cases (moltype protein): applied arithmetically
-    u32 R;         // tile stride in residues (see sk_r_cand); 0 = packed tiles (tile_g0 gives each tile's first residue)
-    const u64 *tile_g0; // packed tiles: 16-byte aligned residue offset the tile's LDS window starts at
-    u32 span;      // residues a shared tile covers from tile * R: SK_TILE, or more for the compacting variant (scaled > 1)
-    u32 c_div, c_rcp; // compacting variant: bucket space is positions / c_div (c_rcp = ceil(2^32 / c_div))
-    u64 out_cap;   // capacity of out_hash / out_abund (MODE 0): writes beyond it are dropped and the host repeats larger
-    u32 use_ticket; // tile ids from the atomic ticket (1) or from blockIdx.x (0)
-    u32 debug_qcap;      // diagnostics (KS_DEBUG_QCAP): capacity of the bucket lists of phase 3 (0 = what fits)
-    u32 debug_skip_tile; // diagnostics (KS_DEBUG_LOOKBACK_SKIP): this tile never publishes — its successors' spins really expire
-    u32 le_cap;    // a sequence whose LOCAL end lies beyond this is not this launch's business
-    u32 max_len_tile; // ... nor is one longer than this (packed tiles: PK_MAX_LEN, so that "long" means the same everywhere)
-    const u32 *seq_list; // MODE 0: tile_first[n_tiles + 1] (tile -> first sequence); MODE 1: the medium sequences
-    const u32 *n_list;   // MODE 1: device-resident length of seq_list
-    u32 n_list_cap;      // ... and the allocated length (the smaller one counts)
-    // MODE 0 writes the final CSR directly: hashes / abunds at csr positions, csr[s] per sequence
-    u64 *out_hash;  // MODE 0: final hashes [n_windows]; MODE 1: lg_hash [n_res] (run of sequence s starts at offs[s])
-    u32 *out_abund;
-    u64 *csr;       // [n_seqs + 1] final CSR offsets (MODE 0)
-    u64 *total_out; // MODE 0: the batch's kept-hash total once more, next to the other words the host reads back
-    u32 *counts;    // [n_seqs] DISTINCT hashes of every sequence (ks_sketches::d_counts): written by whoever sketches the sequence
-    u32 *kept;      // [n_seqs] kept hashes (repeats included) of medium / long sequences (written by MODE 1 / k_sketch_long, read by
-                    // MODE 0: a deferred sequence's slot in the CSR is as long as its kept count)
-    u64 *drops_out; // kept hashes that repeat an earlier one of their sequence, summed over the batch (slots the CSR leaves empty)
-    // decoupled look-back across tiles (MODE 0)
-    unsigned long long *tile_status; // [n_tiles] (flag << 62) | value; flag 1 = tile aggregate, 2 = inclusive prefix
-    u32 *ticket;    // [0] dynamic tile id, [1] status bits: 1 = a bounded spin expired, 2 = postings not emitted for some tile,
-                    //     4 = a compacting tile kept more hashes (or holds more sequences) than its LDS lists take
-    u32 n_tiles;
-    const u32 *n_tiles_dev; // MODE 0, optional: the tiles there really are (a launch sized by an upper bound: the rest return)
-    // optional: postings (hash, sequence) partitioned on the low 8 bits of the join prefix into <= 256 fixed-capacity
-    // regions, written while the vector ALU is the bottleneck — the query side's first partition pass of ks_search
-    u64 *part_keys;   // [256 * part_cap] or NULL
-    u32 *part_vals;
-    u32 *part_cursor; // [256] records placed per region so far
-    u64 part_cap;
-    u32 part_K, part_mask; // region = ks_join_prefix(h, part_K) & part_mask
-    u32 part_kshift;       // != 0: part_K = 2^(32 - part_kshift), the prefix is a shift (sk_digit)
-    u32 part_s;            // != 0: 10-byte postings (ks_sketches::part_s): sequence id bits 0..7 ride in hash bits [part_s, part_s + 8)
-    u32 part_sub_shift;    // sub-regions per region = 1 << shift; a workgroup writes sub-region blockIdx.x & (that - 1)
-};
-
-// bucket multiplier: bucket = umulhi(h >> 32, mul) < n_windows for every kept h (h <= max_hash)
-KS_DEV u32 sk_bucket_mul(u32 nw, u32 sfix) {
-    u64 m = ((u64)nw * sfix) >> 16;
-    return m > 0xffffffffULL ? 0xffffffffu : (u32)m;
-}
-
-// hash of the window that starts at LDS byte `pos8 + I` where pos8 is 8-byte aligned.  KC != 0: k is the compile-time
-// constant KC (the launches of the common k-mer sizes): the block loop, the tail branches and the byte masks fold away and a
-// tail of <= 4 bytes multiplies as a 32-bit value — ~56 instead of ~90 vector instructions per window at k = 10, where
-// the hash phase is what the vector ALU is busy with (profiles/).
-template <int I, int KC = 0>
-KS_DEV u64 sk_hash_window(const u64 *w /* LDS words starting at pos8 */, u32 k_rt, u64 seed) {
-    const u32 k = KC ? (u32)KC : k_rt;
-    ks_murmur m;
-    m.init(seed);
-    const u32 nb = k >> 4, t = k & 15;
-    u32 j = 0;
-    for (u32 b = 0; b < nb; b++, j += 2) {
-        u64 a0 = w[j], a1 = w[j + 1], a2 = w[j + 2];
-        m.block(ks_funnel<I>(a0, a1), ks_funnel<I>(a1, a2));
-    }
-    if (t) {
-        u64 a0 = w[j], a1 = w[j + 1], a2 = w[j + 2];
-        u64 k1 = ks_funnel<I>(a0, a1), k2 = ks_funnel<I>(a1, a2);
-        if (t > 8) k2 &= ks_mask_bytes(t - 8); else { k1 &= ks_mask_bytes(t); k2 = 0; }
-        m.tail(k1, k2, t);
-    }
-    return m.finish((u64)k);
-}
-
-// h[i] = hash of the window at byte pos8 + H + i, i < NW (the calls stay unrolled: every offset is a compile-time constant)
-template <int H, int NW, int KC = 0, int I = 0>
-KS_DEV void sk_hash_windows(u64 *h, const u64 *w, u32 k_rt, u64 seed) {
-    if constexpr (I < NW) {
-        h[I] = sk_hash_window<H + I, KC>(w, k_rt, seed);
-        sk_hash_windows<H, NW, KC, I + 1>(h, w, k_rt, seed);
-    }
-}
-
-// Staging a tile's residues, 16 B per lane, is two steps so that a kernel can REQUEST the bytes early and store them later:
-// 16 residue bytes at g (16-byte aligned), zero-filled behind the batch ...
-KS_DEV uint4 sk_load16(const u8 *res, u64 n_res, u64 g) {
-#ifdef SK_NT_RES
-    if (g + 16 <= n_res) { const u32 *p4 = (const u32 *)(res + g); return make_uint4(__builtin_nontemporal_load(p4), __builtin_nontemporal_load(p4 + 1), __builtin_nontemporal_load(p4 + 2), __builtin_nontemporal_load(p4 + 3)); }
-#else
-    if (g + 16 <= n_res) return *(const uint4 *)(res + g);
-#endif
-    u32 t[4] = {0, 0, 0, 0};
-    for (u32 b = 0; b < 16 && g + b < n_res; b++) t[b >> 2] |= (u32)res[g + b] << (8 * (b & 3));
-    return make_uint4(t[0], t[1], t[2], t[3]);
-}
-// ... and the 16 bytes through the encode table (256 bytes in LDS)
-KS_DEV uint4 sk_encode16(uint4 v, const u8 *lut_s, bool upper_only /* uniform */) {
-    const u32 in[4] = {v.x, v.y, v.z, v.w};
-    u32 o[4];
-    if (upper_only) { // moltype protein: the table only upper-cases — four bytes at a time, no table, no barrier for it
-#pragma unroll
-        for (int d = 0; d < 4; d++) {
-            const u32 y = in[d] & 0x7f7f7f7fu; // (no carry between bytes: 0x7f + 0x1f < 0x100)
-            const u32 lower = (y + 0x1f1f1f1fu) & ~(y + 0x05050505u) & ~in[d] & 0x80808080u; // bytes in 'a' .. 'z'
-            o[d] = in[d] ^ (lower >> 2);
-        }
-    } else {
-#pragma unroll
-        for (int d = 0; d < 4; d++)
-            o[d] = (u32)lut_s[in[d] & 255u] | ((u32)lut_s[(in[d] >> 8) & 255u] << 8) |
-                   ((u32)lut_s[(in[d] >> 16) & 255u] << 16) | ((u32)lut_s[in[d] >> 24] << 24);
-    }
-    return make_uint4(o[0], o[1], o[2], o[3]);
-}
-
-// first s in [lo, hi) whose local end `end_of(s)` lies beyond `key` (hi if there is none): the sequence that holds position key
-template <typename EndOf>
-KS_DEV u32 sk_seq_beyond(u32 lo, u32 hi, u32 key, EndOf end_of) {
-    while (lo < hi) {
-        const u32 mid = lo + ((hi - lo) >> 1);
-        if (end_of(mid) > key) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
 
 // does the sequence at residue offset `start` with `len` residues end outside its shared tile's LDS window?
 KS_DEV bool sk_deferred(u64 start, u64 len, u32 R, u32 span) { return start % R + len > span - 16; }
@@ -288,7 +152,6 @@ static_assert(SK_CTL_LONG + SK_NR <= SK_CTL_TICKET && SK_CTL_LB_ROUNDS < SK_CTL_
 static_assert(SK_CTL_WORDS <= KS_PIN_SKETCH_WORDS && SK_CTL_WORDS <= KS_PIN_SKETCH_SYNC_WORDS, "pinned slots of the sketch read-back");
 // status bits of the control block (SK_CTL_TICKET, second word)
 enum : u32 { SK_ST_LOOKBACK = 1u, SK_ST_POSTINGS = 2u, SK_ST_COMPACT = 4u };
-#define SK_SEQ_CAP 254 // sequence boundaries of a tile staged in LDS (tiles with more fall back to global reads)
 // per-element code: sequence (relative to the tile's first, 8 bits) | bucket (12 bits) | arrival slot (12 bits)
 #define SK_BO_B(x) (((x) >> 12) & 0xfffu)
 #define SK_BO_O(x) ((x) & 0xfffu)
@@ -1366,26 +1229,6 @@ __global__ __launch_bounds__(SK_THREADS, MODE == 1 ? 4 : SK_MINW) void k_sketch_
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// long sequences: same algorithm, arrays in a global scratch slab, one workgroup per sequence
-// ---------------------------------------------------------------------------------------------
-struct sk_long_args {
-    sk_args a;
-    const u32 *long_ids;
-    const u32 *n_long;
-    u32 long_cap;  // allocated entries of long_ids
-    u32 max_len;   // slab sizing
-    u64 *slab_keys; // [grid][max_len]   window-order hashes (0 = dropped)
-    u64 *slab_tmp;  // [grid][max_len]   bucket-ordered hashes
-    u64 *slab_sorted; // [grid][max_len]
-    u32 *slab_cnt;  // [grid][max_len+1] bucket counts -> starts
-    u32 *slab_ord;  // [grid][max_len]   arrival slot per window
-    u32 *slab_flag; // [grid][max_len+1] representative flags -> distinct ranks
-    u32 *slab_ab;   // [grid][max_len]
-    u64 *lg_hash;   // [n_res] output of long sequences (own buffer: a tile-packed run may overlap a long span)
-    u32 *lg_abund;  // [n_res]
-};
-
 // n_cls[0] = medium sequences (own tile), n_cls[1] = long sequences (global-slab path)
 __global__ __launch_bounds__(256) void k_find_long(const u64 *offs, u32 n_seqs, u32 R, u32 span, u32 *med_ids, u32 *long_ids, u32 *n_cls,
                                                    u32 med_cap, u32 long_cap) {
@@ -1411,356 +1254,6 @@ __global__ __launch_bounds__(256) void k_find_long(const u64 *offs, u32 n_seqs, 
         // small — dropped here, reported by the host, which compares the hint with the measured maximum)
         if (cls == c && base + ks_lane_lt_count(m) < (c == 0 ? med_cap : long_cap)) (c == 0 ? med_ids : long_ids)[base + ks_lane_lt_count(m)] = s;
     }
-}
-
-// block-wide exclusive scan of a global u32 array in place; returns the total (uniform)
-KS_DEV u32 sk_block_scan_global(u32 *a, u32 n, u32 *scan_smem) {
-    u32 carry = 0;
-    for (u32 base = 0; base < n; base += SK_THREADS) {
-        u32 i = base + threadIdx.x;
-        u32 v = i < n ? a[i] : 0;
-        u32 total;
-        u32 ex = ks_block_excl_scan(v, scan_smem, &total);
-        if (i < n) a[i] = carry + ex;
-        carry += total;
-    }
-    return carry;
-}
-
-// All cross-thread traffic goes through global memory inside ONE workgroup: barriers carry
-// agent-scope fences so L1-resident lines written by atomics / other waves are re-read (rare path).
-#define SK_LONG_SYNC() do { __threadfence(); __syncthreads(); } while (0)
-
-__global__ __launch_bounds__(SK_THREADS) void k_sketch_long(sk_long_args L) {
-    __shared__ __attribute__((aligned(16))) u64 res_w[(SK_TILE + SK_PAD) / 8];
-    __shared__ u32 scan_smem[SK_THREADS / 64 + 1];
-    __shared__ u8 lut_s[256];
-    const sk_args &A = L.a;
-    const u32 tid = threadIdx.x;
-    u8 *res_b = (u8 *)res_w;
-    if (tid < 256) lut_s[tid] = A.lut[tid];
-    const u32 n_long = L.n_long[1] < L.long_cap ? L.n_long[1] : L.long_cap;
-    const u64 slab = (u64)blockIdx.x * ((u64)L.max_len + 1);
-    u64 *keys = L.slab_keys + slab, *tmp = L.slab_tmp + slab, *sorted = L.slab_sorted + slab;
-    u32 *cnt = L.slab_cnt + slab, *ord = L.slab_ord + slab, *flag = L.slab_flag + slab, *abd = L.slab_ab + slab;
-
-    for (u32 li = blockIdx.x; li < n_long; li += gridDim.x) {
-        const u32 s = L.long_ids[li];
-        const u64 b = A.offs[s], e = A.offs[s + 1];
-        if (e - b > L.max_len) { // the caller's max_seq_len hint was too small: the host reports it (real maximum != hint)
-            if (tid == 0) { A.counts[s] = 0; A.kept[s] = 0; }
-            continue;
-        }
-        const u32 len = (u32)(e - b);
-        const u32 nw = len >= A.k ? len - A.k + 1 : 0;
-        const u32 mul = sk_bucket_mul(nw, A.sfix);
-        for (u32 i = tid; i <= nw; i += SK_THREADS) { cnt[i] = 0; flag[i] = 0; }
-        SK_LONG_SYNC();
-        // hash in chunks of SK_TILE windows staged through LDS
-        for (u32 w0 = 0; w0 < nw; w0 += SK_TILE) {
-            const u64 gbase = b + w0;
-            const u64 g0 = gbase & ~15ULL;
-            const u32 shift = (u32)(gbase - g0);
-            for (u32 c = tid; c < (SK_TILE + SK_PAD) / 16; c += SK_THREADS) {
-                const u64 g = g0 + (u64)c * 16;
-                *(uint4 *)(res_b + (size_t)c * 16) = g < e ? sk_encode16(sk_load16(A.res, A.n_res, g), lut_s, false) : make_uint4(0, 0, 0, 0);
-            }
-            __syncthreads();
-            // window w = w0 + j lives at LDS byte shift + j; j strided over threads
-            for (u32 j = tid; j < SK_TILE && w0 + j < nw; j += SK_THREADS) {
-                const u32 pos = shift + j;
-                const u64 *w = res_w + (pos >> 3);
-                const u32 bs = pos & 7;
-                ks_murmur m;
-                m.init(A.seed);
-                const u32 nb = A.k >> 4, t = A.k & 15;
-                u32 jj = 0;
-                for (u32 bl = 0; bl < nb; bl++, jj += 2)
-                    m.block(ks_funnel_rt(w[jj], w[jj + 1], bs), ks_funnel_rt(w[jj + 1], w[jj + 2], bs));
-                if (t) {
-                    u64 k1 = ks_funnel_rt(w[jj], w[jj + 1], bs), k2 = ks_funnel_rt(w[jj + 1], w[jj + 2], bs);
-                    if (t > 8) k2 &= ks_mask_bytes(t - 8); else { k1 &= ks_mask_bytes(t); k2 = 0; }
-                    m.tail(k1, k2, t);
-                }
-                u64 h = m.finish((u64)A.k);
-                bool keep = h != 0 && h <= A.max_hash;
-                keys[w0 + j] = keep ? h : 0;
-                if (keep) ord[w0 + j] = atomicAdd(&cnt[__umulhi((u32)(h >> 32), mul)], 1u);
-            }
-            __syncthreads();
-        }
-        SK_LONG_SYNC();
-        const u32 n_kept = sk_block_scan_global(cnt, nw + 1, scan_smem);
-        SK_LONG_SYNC();
-        for (u32 w = tid; w < nw; w += SK_THREADS) {
-            u64 h = keys[w];
-            if (h) tmp[cnt[__umulhi((u32)(h >> 32), mul)] + ord[w]] = h;
-        }
-        SK_LONG_SYNC();
-        for (u32 w = tid; w < nw; w += SK_THREADS) {
-            u64 h = keys[w];
-            if (!h) continue;
-            const u32 bk = __umulhi((u32)(h >> 32), mul), o = ord[w];
-            const u32 sb = cnt[bk], c = cnt[bk + 1] - sb;
-            u32 less = 0, eq = 0, eqb = 0;
-            for (u32 j = 0; j < c; j++) {
-                u64 x = tmp[sb + j];
-                less += x < h;
-                eq += x == h;
-                eqb += (x == h) & (j < o);
-            }
-            if (eqb == 0) {
-                const u32 p = sb + less;
-                sorted[p] = h;
-                abd[p] = eq;
-                flag[p] = 1;
-            }
-        }
-        SK_LONG_SYNC();
-        const u32 n_distinct = sk_block_scan_global(flag, n_kept + 1, scan_smem);
-        SK_LONG_SYNC();
-        for (u32 p = tid; p < n_kept; p += SK_THREADS) {
-            if (flag[p + 1] != flag[p]) {
-                L.lg_hash[b + flag[p]] = sorted[p];
-                L.lg_abund[b + flag[p]] = abd[p];
-            }
-        }
-        if (tid == 0) {
-            A.counts[s] = n_distinct; A.kept[s] = n_kept;
-            if (n_kept != n_distinct) atomicAdd((unsigned long long *)A.drops_out, (unsigned long long)(n_kept - n_distinct));
-        }
-        SK_LONG_SYNC();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// CSR assembly: only medium / long sequences need a copy (their runs were produced in side buffers
-// before the tile kernel fixed their CSR positions); one workgroup per such sequence.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_place_long(const u32 *ids, const u32 *n_ids_dev, u32 ids_cap, const u64 *offs, const u64 *csr, const u32 *counts, const u64 *lg_hash,
-                                                    const u32 *lg_abund, u64 *hashes, u32 *abunds, u64 out_cap, u64 *part_keys,
-                                                    u32 *part_vals, u32 *part_cursor, u64 part_cap, u32 part_K,
-                                                    u32 part_mask, u32 part_sub_shift, u32 *status, u32 part_s) {
-    // a compacting tile that overflowed wrote no CSR offsets for its sequences (the host repeats the batch): nothing
-    // here may be trusted then
-    if (__hip_atomic_load(&status[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 4u) return;
-    const u32 n_ids = *n_ids_dev < ids_cap ? *n_ids_dev : ids_cap; // (only known on the device: a fixed grid strides over the list)
-    for (u32 li = blockIdx.x; li < n_ids; li += gridDim.x) {
-    const u32 s = ids[li];
-    const u64 dst = csr[s], src = offs[s];
-    u64 n = counts[s]; // (distinct hashes: the head of the sequence's slot)
-    if (n > offs[s + 1] - src) n = offs[s + 1] - src; // (a run is never longer than its sequence)
-    for (u64 i = threadIdx.x; i < n; i += 256) {
-        const u64 h = lg_hash[src + i];
-        if (dst + i < out_cap) {
-            hashes[dst + i] = h;
-            abunds[dst + i] = lg_abund[src + i];
-        }
-        if (part_keys) { // long sequences are rare: one device atomic per posting is fine here
-            const u32 dg = ((ks_join_prefix(h, part_K) & part_mask) << part_sub_shift) | (blockIdx.x & ((1u << part_sub_shift) - 1u));
-            const u64 slot = atomicAdd(&part_cursor[dg], 1u);
-            if (slot < part_cap) {
-                if (part_s) {
-                    part_keys[(u64)dg * part_cap + slot] = (h & ~(0xffULL << part_s)) | ((u64)(s & 0xffu) << part_s);
-                    ((u16 *)part_vals)[(u64)dg * part_cap + slot] = (u16)(s >> 8);
-                } else {
-                    part_keys[(u64)dg * part_cap + slot] = h;
-                    part_vals[(u64)dg * part_cap + slot] = s;
-                }
-            } else {
-                atomicOr(&status[1], 2u);
-            }
-        }
-    }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// k-mer position table (ProteomeIndex::process_kmers, src/rust/index.rs:749-786; KmerInfo of kmer.rs:6-12):
-// (sequence, start, hash) of every kept window, ordered by (sequence, start), in ONE pass.
-// A tile is a fixed range of KP_R residue positions (windows of any sequence: there is no per-sequence sort here, so
-// no deferral): residues staged through the LUT like the sketch kernel, 8 windows hashed per thread from LDS, kept
-// windows compacted in position order, and the tile's slice of the output found by the same decoupled look-back
-// (ticket-ordered tiles, 8-byte {flag, value} status words) the sketch kernel uses for its CSR.
-// Not fused into k_sketch_tiles on purpose: that kernel is instruction-bound at its register limit (78 of 80 VGPRs),
-// and this one re-hashes at the rate the 16 B per window of output allow anyway.
-// ---------------------------------------------------------------------------------------------
-#define KP_R SK_TILE
-struct kp_args {
-    const u8 *res;
-    const u64 *offs;
-    const u8 *lut;
-    const u32 *tile_first;          // first sequence whose END lies beyond the tile's first position
-    unsigned long long *tile_status;
-    u32 *ticket;                    // [0] tile ids, [1] look-back gave up
-    u64 *total;                     // kept windows of the whole batch (written by the last tile)
-    u32 *out_seq, *out_start;
-    u64 *out_hash;
-    u64 n_res, max_hash, seed;
-    u32 n_seqs, k, n_tiles;
-    u32 use_ticket;                 // tile ids from the atomic ticket (1) or from blockIdx.x (0), as in k_sketch_tiles
-};
-
-__global__ __launch_bounds__(256) void k_kmerpos_plan(const u64 *offs, u32 n_seqs, u32 n_tiles, u32 *tile_first) {
-    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t > n_tiles) return;
-    // first s with offs[s + 1] > t * KP_R
-    tile_first[t] = ks_lower_bound_u64(offs + 1, n_seqs, (u64)t * KP_R + 1);
-}
-
-__global__ __launch_bounds__(SK_THREADS) void k_kmerpos_tiles(kp_args A) {
-    __shared__ __attribute__((aligned(16))) u64 res_w[(SK_TILE + SK_PAD) / 8];
-    __shared__ __attribute__((aligned(16))) u64 stage[SK_TILE]; // compacted output staging: hashes, then (seq, start)
-    __shared__ u32 lend[SK_SEQ_CAP + 2]; // local END of the tile's sequences (clamped)
-    __shared__ u8 lut_s[256];
-    __shared__ u32 scan_smem[SK_THREADS / 64 + 1];
-    __shared__ u32 tile_s;
-    __shared__ unsigned long long base_s;
-    const u32 tid = threadIdx.x;
-    constexpr u32 NCH = (SK_TILE + SK_PAD) / 16;
-    // (tile ids in dispatch order; a launch whose look-back gave up is repeated with ticket ids: 73k tickets on one address
-    // were 0.9 ms of queueing for a 1M-protein batch)
-    u32 tile = blockIdx.x;
-    if (A.use_ticket) { // (uniform; the repeat launch only)
-        if (tid == 0) tile_s = atomicAdd(&A.ticket[0], 1u);
-        __syncthreads();
-        tile = tile_s;
-    }
-    // the encode table's byte, the tile's residues and its sequence range are requested together (the table byte used to be
-    // stored — i.e. waited for — before anything else was asked for: see k_sketch_tiles)
-    u32 lut_v = 0;
-    if (tid < 256) lut_v = A.lut[tid];
-    const u64 g0 = (u64)tile * KP_R;
-    uint4 rv = make_uint4(0, 0, 0, 0);
-    if (tid < NCH) rv = sk_load16(A.res, A.n_res, g0 + (u64)tid * 16);
-    const u32 s_first = A.tile_first[tile];
-    u32 s_last = A.tile_first[tile + 1]; // the sequence that holds the next tile's first position also ends here or later
-    if (s_last >= A.n_seqs) s_last = A.n_seqs ? A.n_seqs - 1 : 0;
-    const u32 ns = s_first < A.n_seqs ? s_last - s_first + 1 : 0;
-    const bool in_lds = ns <= SK_SEQ_CAP;
-    if (in_lds)
-        for (u32 i = tid; i < ns; i += SK_THREADS) {
-            const u64 v = A.offs[s_first + i + 1] - g0; // ends beyond the tile's first position: never negative
-            lend[i] = v > 0x7fffffffULL ? 0x7fffffffu : (u32)v;
-        }
-    if (tid < 256) lut_s[tid] = (u8)lut_v;
-    __syncthreads(); // the table
-    if (tid < NCH) *(uint4 *)((u8 *)res_w + (size_t)tid * 16) = sk_encode16(rv, lut_s, false);
-    __syncthreads();
-    auto end_of = [&](u32 s) -> u32 { // local end of sequence s (s_first <= s <= s_last)
-        if (in_lds) return lend[s - s_first];
-        const u64 v = A.offs[s + 1] - g0;
-        return v > 0x7fffffffULL ? 0x7fffffffu : (u32)v;
-    };
-
-    const u32 q0 = tid * SK_E;
-    u64 h[SK_E];
-    u32 sq[SK_E]; // sequence of a kept window, ~0 = not kept
-    u32 n_keep = 0;
-#pragma unroll
-    for (int i = 0; i < SK_E; i++) { h[i] = 0; sq[i] = 0xffffffffu; }
-    if (ns && g0 + q0 < A.n_res) {
-        // the sequence that holds position q0: first one (from s_first) whose end lies beyond q0
-        u32 s = sk_seq_beyond(s_first, s_last, q0, end_of), e = end_of(s); // (s_last is inclusive: the answer when no earlier one is)
-        const u64 *wl = res_w + tid;
-        sk_hash_windows<0, SK_E>(h, wl, A.k, A.seed);
-#pragma unroll
-        for (int i = 0; i < SK_E; i++) {
-            const u32 p = q0 + i;
-            while (s < s_last && p >= e) { s++; e = end_of(s); }
-            // offsets are cumulative, so p lies inside sequence s as soon as p < e; the window must fit before e
-            const bool keep = p < e && p + A.k <= e && h[i] != 0 && h[i] <= A.max_hash;
-            if (keep) { sq[i] = s; n_keep++; }
-        }
-    }
-    u32 total;
-    const u32 ex = ks_block_excl_scan(n_keep, scan_smem, &total);
-    // ---- decoupled look-back over the tiles' kept counts (protocol: ks_device.h)
-    if (tid == 0)
-        __hip_atomic_store(&A.tile_status[tile], (tile == 0 ? KS_LB_PRE : KS_LB_AGG) | (u64)total, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    if (tid < 64) {
-        u64 excl = 0;
-        if (tile > 0) {
-            excl = ks_lookback_walk(tile, tid, ks_lookback_words(A.tile_status), &A.ticket[1]);
-            if (tid == 0)
-                __hip_atomic_store(&A.tile_status[tile], KS_LB_PRE | (excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        if (tid == 0) {
-            base_s = excl;
-            if (tile == A.n_tiles - 1) *A.total = excl + total;
-        }
-    }
-    __syncthreads();
-    // kept windows leave through LDS in compacted order, so the three output streams are written as whole cache lines
-    // (per-thread runs of <= 8 entries would touch 64 different 32-byte sectors per store instruction)
-    const u64 base = base_s;
-    {
-        u32 o = ex;
-#pragma unroll
-        for (int i = 0; i < SK_E; i++)
-            if (sq[i] != 0xffffffffu) stage[o++] = h[i];
-    }
-    __syncthreads();
-    for (u32 i = tid; i < total; i += SK_THREADS) A.out_hash[base + i] = stage[i];
-    __syncthreads();
-    {
-        u32 *st_seq = (u32 *)stage, *st_start = st_seq + SK_TILE;
-        u32 o = ex;
-#pragma unroll
-        for (int i = 0; i < SK_E; i++)
-            if (sq[i] != 0xffffffffu) {
-                st_seq[o] = sq[i];
-                st_start[o] = (u32)(g0 + q0 + i - A.offs[sq[i]]);
-                o++;
-            }
-        __syncthreads();
-        for (u32 i = tid; i < total; i += SK_THREADS) {
-            A.out_seq[base + i] = st_seq[i];
-            A.out_start[base + i] = st_start[i];
-        }
-    }
-}
-
-// d_seq / d_start / d_hash are sized by the batch's window count (an upper bound on the kept windows)
-int ks_kmerpos_tiles_launch(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res, const ks_params *p, u32 *d_seq,
-                            u32 *d_start, u64 *d_hash, u64 *n_out) {
-    const u64 n_tiles64 = (n_res + KP_R - 1) / KP_R;
-    if (n_tiles64 > 0x7ffffff0ULL) return ks_fail(ctx, KS_ERR_INVALID_ARG, "batch too large");
-    const u32 n_tiles = (u32)n_tiles64;
-    u32 *tile_first = nullptr, *ticket = nullptr;
-    unsigned long long *status = nullptr;
-    u64 *total = nullptr;
-    ks_scratch sc(ctx);
-    KS_TRY(sc.alloc(&tile_first, (size_t)n_tiles + 1));
-    KS_TRY(sc.alloc((u64 **)&status, (size_t)n_tiles));
-    KS_TRY(sc.alloc(&ticket, 2));
-    KS_TRY(sc.alloc(&total, 1));
-    KS_LAUNCH(ctx, "kmerpos_plan", k_kmerpos_plan, (n_tiles + 256) / 256, 256, d_offs, n_seqs, n_tiles, tile_first);
-    u64 *const rb = ctx->h_pin + KS_PIN_READ; // total | ticket pair
-    for (int attempt = 0; attempt < 2; attempt++) {
-        const bool use_ticket = ctx->sketch_use_ticket || attempt == 1;
-        (void)hipMemsetAsync(status, 0, (size_t)n_tiles * sizeof(u64), ctx->stream);
-        (void)hipMemsetAsync(ticket, 0, 2 * sizeof(u32), ctx->stream);
-        (void)hipMemsetAsync(total, 0, sizeof(u64), ctx->stream);
-        kp_args A;
-        memset(&A, 0, sizeof A);
-        A.res = d_res; A.offs = d_offs; A.lut = ctx->d_lut + 256 * p->moltype; A.tile_first = tile_first;
-        A.tile_status = status; A.ticket = ticket; A.total = total; A.out_seq = d_seq; A.out_start = d_start; A.out_hash = d_hash;
-        A.n_res = n_res; A.max_hash = ks_max_hash(p->scaled); A.seed = p->seed; A.n_seqs = n_seqs; A.k = p->ksize; A.n_tiles = n_tiles;
-        A.use_ticket = use_ticket ? 1u : 0u;
-        KS_LAUNCH(ctx, "kmerpos_tiles", k_kmerpos_tiles, n_tiles, SK_THREADS, A);
-        KS_HIP(ctx, hipMemcpyAsync(rb, total, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-        KS_HIP(ctx, hipMemcpyAsync(rb + 1, ticket, 2 * sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
-        KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        bool gave_up = ((u32 *)(rb + 1))[1] != 0;
-        if (!use_ticket && ks_dbg(ctx, KS_DBG_FORCE_TICKET_RETRY)) gave_up = true; // exercises the repeat
-        if (!gave_up) { *n_out = rb[0]; break; }
-        if (use_ticket) return ks_fail(ctx, KS_ERR_HIP, "k-mer positions: look-back gave up waiting for a predecessor tile");
-        ctx->sketch_use_ticket = true; // dispatch order did not hold here: tickets from now on (shared with the sketch tiles)
-        ctx->sketch_ticket_fallbacks++;
-    }
-    return KS_OK;
 }
 
 // The statistics words of the control block (SK_CTL_*): windows, longest sequence, and under tile stride cand[c] (a tile
@@ -1978,12 +1471,10 @@ static void sk_plan_outputs(const ks_ctx *ctx, const sk_call &C, int variant, in
 
 // device words and scratch blocks the launch steps share (the scratch blocks belong to the attempt's ks_scratch)
 struct sk_bufs {
-    u32 *ticket, *n_cls, *d_ntiles; // in the control block
+    u32 *ticket, *d_ntiles; // in the control block (as is def.n_cls)
     u32 *tile_first;
     u64 *tile_g0;
-    u32 *med_ids, *long_ids;
-    u64 *lg_hash;
-    u32 *lg_abund;
+    ks_deferred def;
 };
 
 // the control block (zeroed), the statistics and, for a packed plan, the tile plan
@@ -1992,7 +1483,7 @@ static int sk_launch_stats(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
     KS_TRY(ks_alloc(ctx, &S->ctl_block, ctl_words));
     u64 *const ctl = S->ctl_block;
     KS_HIP(ctx, hipMemsetAsync(ctl, 0, ctl_words * sizeof(u64), ctx->stream));
-    B.ticket = (u32 *)(ctl + SK_CTL_TICKET); B.n_cls = (u32 *)(ctl + SK_CTL_CLS); B.d_ntiles = (u32 *)(ctl + SK_CTL_PK_TILES);
+    B.ticket = (u32 *)(ctl + SK_CTL_TICKET); B.def.n_cls = (u32 *)(ctl + SK_CTL_CLS); B.d_ntiles = (u32 *)(ctl + SK_CTL_PK_TILES);
     u32 g = (C.n_seqs + 1023) / 1024;
     if (g > 512) g = 512;
     KS_LAUNCH(ctx, "seq_stats", k_seq_stats, g, 256, C.d_offs, C.n_seqs, C.p->ksize, P.span, P.cand, ctl);
@@ -2022,40 +1513,21 @@ static int sk_launch_deferred(ks_ctx *ctx, const sk_call &C, const sk_plan &P, s
     // read are never used, the pointer must be valid)
     KS_TRY(sc.alloc(&A.kept, (size_t)C.n_seqs));
     if (n_med + n_long > 0) {
-        KS_TRY(sc.alloc(&B.lg_hash, (size_t)C.n_res + 1));
-        KS_TRY(sc.alloc(&B.lg_abund, (size_t)C.n_res + 1));
-        KS_TRY(sc.alloc(&B.med_ids, (size_t)n_med + 1));
-        KS_TRY(sc.alloc(&B.long_ids, (size_t)n_long + 1));
-        KS_LAUNCH(ctx, "find_long", k_find_long, (C.n_seqs + 255) / 256, 256, C.d_offs, C.n_seqs, P.tile_R, P.span, B.med_ids,
-                  B.long_ids, B.n_cls, (u32)n_med, (u32)n_long);
+        KS_TRY(sc.alloc(&B.def.lg_hash, (size_t)C.n_res + 1)); // (own buffers: a tile-packed run may overlap a long span)
+        KS_TRY(sc.alloc(&B.def.lg_abund, (size_t)C.n_res + 1));
+        KS_TRY(sc.alloc(&B.def.med_ids, (size_t)n_med + 1));
+        KS_TRY(sc.alloc(&B.def.long_ids, (size_t)n_long + 1));
+        KS_LAUNCH(ctx, "find_long", k_find_long, (C.n_seqs + 255) / 256, 256, C.d_offs, C.n_seqs, P.tile_R, P.span, B.def.med_ids,
+                  B.def.long_ids, B.def.n_cls, (u32)n_med, (u32)n_long);
     }
     if (n_med > 0) {
         sk_args M = A; // (keeps the posting arguments: a medium tile emits its own postings)
-        M.out_hash = B.lg_hash; M.out_abund = B.lg_abund; M.le_cap = SK_TILE; M.seq_list = B.med_ids; // local start <= 15, length <= SK_MED_MAX
+        M.out_hash = B.def.lg_hash; M.out_abund = B.def.lg_abund; M.le_cap = SK_TILE; M.seq_list = B.def.med_ids; // local start <= 15, length <= SK_MED_MAX
         M.out_cap = ~0ULL;
-        M.n_list = B.n_cls; M.n_list_cap = (u32)n_med;
+        M.n_list = B.def.n_cls; M.n_list_cap = (u32)n_med;
         KS_LAUNCH(ctx, "sketch_medium", (k_sketch_tiles<1, 0, 0>), (u32)(n_med < 2048 ? n_med : 2048), SK_THREADS, M);
     }
-    if (n_long > 0) {
-        // slab: 3 u64 + 4 u32 arrays of (max_len + 1) per workgroup, capped at ~2 GiB total
-        const u64 stride = (u64)P.real_max + 1;
-        const u64 per_wg = stride * (3 * 8 + 4 * 4);
-        u64 grid = (2ULL << 30) / per_wg;
-        if (grid < 1) grid = 1;
-        if (grid > n_long) grid = n_long;
-        if (grid > 512) grid = 512;
-        u64 *slab64 = nullptr;
-        u32 *slab32 = nullptr;
-        KS_TRY(sc.alloc(&slab64, (size_t)(grid * stride * 3)));
-        KS_TRY(sc.alloc(&slab32, (size_t)(grid * stride * 4)));
-        sk_long_args L;
-        L.a = A; L.long_ids = B.long_ids; L.n_long = B.n_cls; L.long_cap = (u32)n_long; L.max_len = P.real_max;
-        L.slab_keys = slab64; L.slab_tmp = slab64 + grid * stride; L.slab_sorted = slab64 + 2 * grid * stride;
-        L.slab_cnt = slab32; L.slab_ord = slab32 + grid * stride; L.slab_flag = slab32 + 2 * grid * stride;
-        L.slab_ab = slab32 + 3 * grid * stride;
-        L.lg_hash = B.lg_hash; L.lg_abund = B.lg_abund;
-        KS_LAUNCH(ctx, "sketch_long", k_sketch_long, (u32)grid, SK_THREADS, L);
-    }
+    if (n_long > 0) KS_TRY(ks_sketch_long_launch(ctx, A, B.def, n_long, P.real_max, sc));
     return KS_OK;
 }
 
@@ -2129,16 +1601,7 @@ static int sk_launch_tiles(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
         KS_HIP(ctx, hipGetLastError());
 
         // ---- runs of medium / long sequences into their CSR slots
-        if (P.n_med > 0) // medium runs: copy only (their tiles emitted their own postings)
-            KS_LAUNCH(ctx, "place_long", k_place_long, (u32)(P.n_med < 1024 ? P.n_med : 1024), 256, (const u32 *)B.med_ids,
-                      (const u32 *)B.n_cls, (u32)P.n_med, C.d_offs, (const u64 *)S->d_offsets, (const u32 *)S->d_counts,
-                      (const u64 *)B.lg_hash, (const u32 *)B.lg_abund, S->d_hashes, S->d_abunds, P.out_cap, (u64 *)nullptr,
-                      (u32 *)nullptr, (u32 *)nullptr, (u64)0, 0u, 0u, 0u, B.ticket, 0u);
-        if (P.n_long > 0)
-            KS_LAUNCH(ctx, "place_long", k_place_long, (u32)(P.n_long < 1024 ? P.n_long : 1024), 256, (const u32 *)B.long_ids,
-                      (const u32 *)(B.n_cls + 1), (u32)P.n_long, C.d_offs, (const u64 *)S->d_offsets, (const u32 *)S->d_counts,
-                      (const u64 *)B.lg_hash, (const u32 *)B.lg_abund, S->d_hashes, S->d_abunds, P.out_cap, A.part_keys,
-                      A.part_vals, A.part_cursor, A.part_cap, A.part_K, A.part_mask, A.part_sub_shift, B.ticket, A.part_s);
+        KS_TRY(ks_sketch_place_launch(ctx, A, B.def, P.n_med, P.n_long));
         // total + look-back error flag to the host
         if (allow_defer && attempt == 0 && (P.pk_bound || (P.planned && !P.packed)) && !ks_dbg(ctx, KS_DBG_FORCE_TICKET_RETRY)) {
             // the caller's next wait on this stream (the search's) stands in for this one and brings the control block along

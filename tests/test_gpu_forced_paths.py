@@ -4,6 +4,8 @@
   repeat has counts to get wrong: sketches, n_hashes, the dense view, postings and hits, k-mer positions;
 - max_seq_len hints that are too small, through every entry that takes one and every plan that trusts one: refused with
   KS_ERR_INVALID_ARG, nothing leaked, the context still right afterwards; exact hints at the tile-size boundaries;
+- the slab path and the copy of the deferred runs (ks_sketch_long.hip) on batches of three sequences: every branch of the two
+  kernels, sketches against the oracle, their postings through the one-call sketch + search;
 - the randomised differential test (tools/fuzz_parity.py) under every knob set, bit for bit against the oracle."""
 import importlib.util
 import os
@@ -18,7 +20,7 @@ from kmerseek_amd import synth
 from oracle import oracle
 
 PROTEIN = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", np.uint8)
-PK_MAX_LEN = 4064  # longest sequence a packed tile holds (ks_sketch.hip)
+PK_MAX_LEN = 4064  # longest sequence a packed tile holds (ks_sketch.hip, next to SK_MED_MAX)
 SK_MED_MAX = 4080  # longest sequence that fits one tile on its own
 
 
@@ -303,6 +305,129 @@ def test_exact_max_seq_len_at_the_tile_boundaries(monkeypatch, plan):
                 if H is not None:
                     _eq(H.to_host(), hits, f"{plan} real {real} {entry} hits")
             d_res.free(); d_off.free()
+    finally:
+        ctx.close()
+
+
+# ---------------------------------------------------------------- B2b: the slab path and the deferred runs, three sequences
+# One sequence beyond SK_MED_MAX (the slab path: k_sketch_long, then k_place_long with its postings), one of 4,070 residues
+# (a tile of its own under plain tiles: the copy-only k_place_long launch) and a short one.  "homopolymer": the long one
+# repeats one k-mer 4,991 / 4,985 times — kept != distinct, so the slab path adds to the drop count and its flag scan has
+# gaps to close ('E' because its dayhoff 16-mer passes the threshold at scaled = 5).  The sequences are cut from the targets
+# (and the targets hold a run of E) so that every query has hits and the long sequences' postings carry them.
+LONG_SETTINGS = {"protein": ("protein", 10, 1), "dayhoff": ("dayhoff", 16, 5)}
+# way -> (knobs, max_seq_len given).  At scaled = 5 the compacting tiles span 19,200 residues and defer none of these
+# sequences (only the homopolymer batch, whose tile overflows, is repeated without them): NO_COMPACT takes the dayhoff
+# batches to the same two kernels.
+LONG_WAYS = {
+    "plain": ({}, False),
+    "hint": ({}, True),
+    "no_pack": ({"KS_DEBUG_NO_PACK": "1"}, False),
+    "hint_no_pack": ({"KS_DEBUG_NO_PACK": "1"}, True),  # lists sized by upper bounds, longer than what is listed
+    "no_compact": ({"KS_DEBUG_NO_COMPACT": "1"}, False),
+    "no_compact_no_pack": ({"KS_DEBUG_NO_COMPACT": "1", "KS_DEBUG_NO_PACK": "1"}, False),
+}
+_long_cache = {}
+
+
+def _assert_long_launches(timing, setting, batch, knobs, what):
+    """The launches of the slab path and of the deferred copies ran (Context.timing): a case that stops reaching them fails."""
+    scaled = LONG_SETTINGS[setting][2]
+    long_path = scaled == 1 or "KS_DEBUG_NO_COMPACT" in knobs or batch == "homopolymer"
+    medium = long_path and "KS_DEBUG_NO_PACK" in knobs  # plain tiles: the 4,070 residues end outside their shared tile
+    if long_path:
+        assert "sketch_long" in timing and timing.get("place_long", (0, 0.0))[0] >= 1 + medium, (what, timing)
+    if medium:
+        assert "sketch_medium" in timing, (what, timing)
+
+
+def _long_targets():
+    if "t" not in _long_cache:
+        t_res, t_off = synth.proteome(200, stream=77)
+        seqs = [bytes(t_res[int(t_off[i]):int(t_off[i + 1])]) for i in range(200)]
+        seqs.insert(100, seqs[3][:50] + b"E" * 40 + seqs[4][:50])
+        _long_cache["t"] = ks.pack(seqs)
+    return _long_cache["t"]
+
+
+def _long_case(batch, setting):
+    """(query batch, target batch, oracle query sketches, oracle target sketches, oracle hits), computed once per pair"""
+    key = (batch, setting)
+    if key not in _long_cache:
+        mol, k, scaled = LONG_SETTINGS[setting]
+        t_res, t_off = _long_targets()
+        first = b"E" * 5000 if batch == "homopolymer" else bytes(t_res[:5000])
+        q = ks.pack([first, bytes(t_res[6000:6000 + 4070]), bytes(t_res[int(t_off[50]):int(t_off[50]) + 30])])
+        assert [int(x) for x in q[1][1:] - q[1][:-1]] == [5000, 4070, 30]
+        wq = oracle.sketch_batch(q[0], q[1], k, scaled, mol, n_threads=4)
+        wt = oracle.sketch_batch(t_res, t_off, k, scaled, mol, n_threads=4)
+        _long_cache[key] = (q, (t_res, t_off), wq, wt, oracle.manysearch(wq[0], wq[1], *wt, n_threads=4))
+    return _long_cache[key]
+
+
+@pytest.mark.parametrize("way", list(LONG_WAYS))
+@pytest.mark.parametrize("setting", list(LONG_SETTINGS))
+@pytest.mark.parametrize("batch", ["random", "homopolymer"])
+def test_long_and_medium_sequences_of_a_three_sequence_batch(monkeypatch, batch, setting, way):
+    """Sketches equal the oracle's exactly, whichever of the plans takes the 5,000- and the 4,070-residue sequence."""
+    mol, k, scaled = LONG_SETTINGS[setting]
+    knobs, hint = LONG_WAYS[way]
+    (res, offs), _, want, _, _ = _long_case(batch, setting)
+    if batch == "homopolymer":
+        assert int(want[2][0]) == 5000 - k + 1 and int(want[0][1]) == 1  # the long sequence: one hash, kept 5000 - k + 1 times
+    for key, v in knobs.items():
+        monkeypatch.setenv(key, v)
+    ctx = ks.Context(0, follow_debug_env=True)
+    try:
+        d_res, d_off = ctx.to_device(res), ctx.to_device(offs)
+        ctx.timing_enable(True)
+        S = ctx.sketch_batch_device(d_res.ptr, d_off.ptr, 3, len(res), k, scaled, mol, max_seq_len=5000 if hint else 0)
+        assert S.n_hashes == len(want[1])
+        _eq(S.to_host(), want, f"{batch} {setting} {way}")
+        _assert_long_launches(ctx.timing(), setting, batch, knobs, f"{batch} {setting} {way}")
+    finally:
+        ctx.close()
+
+
+# 10-byte postings need a join on more than 8 prefix bits whose prefix is a bit field of the hash (scaled = 1), against an
+# index in the fingerprint layout: small buckets make the 201-protein index one.  At scaled = 5 the same knobs leave 12 bytes.
+LONG_POSTINGS = {
+    "12": {},
+    "10": {"KS_DEBUG_JOIN_FP": "1", "KS_DEBUG_BUCKET": "64"},
+}
+
+
+@pytest.mark.parametrize("fmt", list(LONG_POSTINGS))
+@pytest.mark.parametrize("setting,no_compact", [("protein", False), ("dayhoff", False), ("dayhoff", True)])
+@pytest.mark.parametrize("batch", ["random", "homopolymer"])
+def test_long_sequences_as_queries_of_the_one_call_search(monkeypatch, batch, setting, no_compact, fmt):
+    """The same batches as the query side of ks_sketch_search_device: the long sequence's postings come from k_place_long, in
+    the 12-byte and in the 10-byte form.  Hits equal those of the two calls (sketch_batch, which makes no postings, then
+    search) and the oracle's; with and without max_seq_len."""
+    mol, k, scaled = LONG_SETTINGS[setting]
+    (res, offs), (t_res, t_off), want, _, want_hits = _long_case(batch, setting)
+    assert set(want_hits[0].tolist()) == {0, 1, 2}, "every query must have hits"
+    for key, v in LONG_POSTINGS[fmt].items():
+        monkeypatch.setenv(key, v)
+    if no_compact:
+        monkeypatch.setenv("KS_DEBUG_NO_COMPACT", "1")
+    ctx = ks.Context(0, follow_debug_env=True)
+    try:
+        ix = ctx.index_build(ctx.sketch_batch(t_res, t_off, k, scaled, mol))
+        two_calls = ctx.search(ix, ctx.sketch_batch(res, offs, k, scaled, mol)).to_host()
+        _eq(two_calls, want_hits, f"{batch} {setting} two calls vs oracle")
+        d_res, d_off = ctx.to_device(res), ctx.to_device(offs)
+        for bound in (5000, 0):
+            ctx.timing_enable(True)
+            ctx.timing_reset()
+            Q, H = ctx.sketch_search_device(ix, d_res.ptr, d_off.ptr, 3, len(res), max_seq_len=bound)
+            _assert_long_launches(ctx.timing(), setting, batch, {"KS_DEBUG_NO_COMPACT": "1"} if no_compact else {},
+                                  f"{batch} {setting} {fmt} bound {bound}")
+            assert Q.posting_bytes == (10 if fmt == "10" and scaled == 1 else 12)
+            assert H.partition_path != 3, "the search must read the sketch's postings"
+            _eq(Q.to_host(), want, f"{batch} {setting} {fmt} bound {bound} sketches")
+            _eq(H.to_host(), two_calls, f"{batch} {setting} {fmt} bound {bound} hits")
+            Q.free(); H.free()
     finally:
         ctx.close()
 
