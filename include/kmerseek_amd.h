@@ -428,6 +428,46 @@ const double *ks_signif_device_tf_idf(const ks_signif *s);
 int ks_signif_copy_to_host(ks_ctx *ctx, const ks_signif *s, double *prob_overlap, double *tf_idf);
 void ks_signif_free(ks_signif *s);
 
+/* ---- best hits per query: top-k by a rank key ------------------------------------------------------------------------------ */
+
+/* The k best rows of every query of an existing hit list (BLAST's max_target_seqs), as a pass of its own: it composes with a
+ * thresholded search, with the ks_hits_significance columns as the rank key and with a gathered multi-GPU hit list.
+ * Sizes: |q| and |t| are the distinct hash counts of the row's query and target sketch.  `queries` may be NULL for
+ * KS_BEST_INTERSECT and KS_BEST_SCORE, `targets` unless the key needs |t|; a non-NULL set's sequence count bounds the ids.
+ * Scores are f64 with one rounding per operation (the division is correctly rounded: a host computes the same bits).
+ * Order inside one query: row a beats row b iff score(a) > score(b), or the scores are equal and tid(a) < tid(b); -0.0 equals
+ * +0.0, NaN compares below every number (-inf included) and NaNs are equal to each other.
+ * rank(r) = the number of rows of r's query that beat r; a row is kept iff rank < k.  Ranks inside a query are therefore
+ * 0, 1, 2 ... without gaps, and ties at the cut are settled by the smaller tid.
+ * *out: a new ks_hits with the kept rows STILL ordered by (qid, tid) (a valid input of ks_match_positions and
+ * ks_hits_significance), all four row columns, the two statistics columns if the input has them, and per row `rank` and
+ * `src_row`, the row's index in the input list (a caller gathers its own per-row columns through it).  n_pair_instances,
+ * partition_path and bucket_posting_bytes are copied.  The input is unchanged and stays valid.  An empty input, or queries
+ * without rows, give an empty or shorter list; with k at or above the longest query's row count the output is the input plus
+ * the two columns.
+ * KS_ERR_INVALID_ARG (options first, before any device work, also with ctx == NULL): k == 0; an unknown rank_by; non-zero
+ * flags / reserved; d_score NULL with KS_BEST_SCORE or non-NULL without it; a needed set NULL; then: sets of different
+ * ks_params; a qid or tid beyond its set; a |q| or |t| of 0 on a row whose key needs it (ks_last_error names the first such
+ * row).  One stream, one wait (the kept count comes back with it); scratch comes from the pool. */
+#define KS_BEST_INTERSECT          0u  /* score = (double)intersect (same order as the query's containment: |q| is common to a query's rows) */
+#define KS_BEST_TARGET_CONTAINMENT 1u  /* (double)intersect / (double)|t| */
+#define KS_BEST_MAX_CONTAINMENT    2u  /* (double)intersect / (double)min(|q|, |t|) */
+#define KS_BEST_JACCARD            3u  /* (double)intersect / (double)(|q| + |t| - intersect), the denominator in u64 */
+#define KS_BEST_SCORE              4u  /* d_score[r]: a caller-owned device column of ks_hits_count(hits) doubles */
+typedef struct ks_best_opts {
+    uint32_t rank_by;  /* KS_BEST_* */
+    uint32_t k;        /* rows kept per query, >= 1 */
+    uint32_t flags;    /* 0 */
+    uint32_t reserved; /* 0 */
+} ks_best_opts;
+int ks_hits_best(ks_ctx *ctx, const ks_hits *hits, const ks_sketches *queries, const ks_sketches *targets,
+                 const double *d_score, const ks_best_opts *opts, ks_hits **out);
+/* device columns (ks_hits_count entries, valid until ks_hits_free); NULL unless h came from ks_hits_best */
+const uint32_t *ks_hits_device_rank(const ks_hits *h);
+const uint32_t *ks_hits_device_src_row(const ks_hits *h);
+/* either destination may be NULL; KS_ERR_INVALID_ARG for hits that did not come from ks_hits_best */
+int ks_hits_copy_best_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t *rank, uint32_t *src_row);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Per-kernel HIP-event timing on ctx's stream.  enable: 0 off; 1 events bracket every launch (~20 us of idle queue

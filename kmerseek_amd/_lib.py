@@ -52,6 +52,13 @@ class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+KS_BEST_INTERSECT, KS_BEST_TARGET_CONTAINMENT, KS_BEST_MAX_CONTAINMENT, KS_BEST_JACCARD, KS_BEST_SCORE = 0, 1, 2, 3, 4
+
+
+class ks_best_opts(C.Structure):
+    _fields_ = [("rank_by", C.c_uint32), ("k", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ks_kernel_time(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -163,6 +170,10 @@ SIGNATURES = {
     "ks_signif_device_tf_idf": (_vp, [_vp]),
     "ks_signif_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ks_signif_free": (None, [_vp]),
+    "ks_hits_best": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ks_best_opts), _pp]),
+    "ks_hits_device_rank": (_vp, [_vp]),
+    "ks_hits_device_src_row": (_vp, [_vp]),
+    "ks_hits_copy_best_to_host": (C.c_int, [_vp, _vp, _vp, _vp]),
     "ks_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ks_timing_reset": (C.c_int, [_vp]),
     "ks_timing_get": (C.c_int, [_vp, C.POINTER(ks_kernel_time), C.c_uint32, _u32p]),

@@ -660,5 +660,7 @@ extern "C" void ks_hits_free(ks_hits *h) {
     else { ks_pool_free(h->ctx, h->d_isect); ks_pool_free(h->ctx, h->d_nw); }
     ks_pool_free(h->ctx, h->d_median2);
     ks_pool_free(h->ctx, h->d_ss);
+    ks_pool_free(h->ctx, h->d_rank);
+    ks_pool_free(h->ctx, h->d_src_row);
     delete h;
 }

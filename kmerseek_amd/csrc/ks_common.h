@@ -45,7 +45,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -270,13 +270,15 @@ enum : u32 {
     KS_PIN_READ = 197,       // 2 words, one-call read-backs: index build, union, merge, k-mer positions
     KS_PIN_DENSE = 199,      // u64: the scan total of ks_sketches_make_dense
     KS_PIN_SIGNIF = 200,     // 3 words, significance: first row with an id out of range | first row with another shared count | corpus flag
-    KS_PIN_END = 203,
+    KS_PIN_BEST = 203,       // 3 words, best hits: first row with an id out of range | first row with an empty sketch | kept rows
+    KS_PIN_END = 206,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_END && KS_PIN_END <= KS_PIN_WORDS,
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_END &&
+                  KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
 // one index posting as the join fetches it for a candidate match: one 16-byte load
@@ -327,6 +329,8 @@ struct ks_hits {
     bool has_stats;
     u64 *d_median2;
     double *d_ss;
+    // ks_hits_best: per kept row its rank inside its query and its row in the input list; NULL for every other hit list
+    u32 *d_rank, *d_src_row;
 };
 
 struct ks_kmerpos {

@@ -58,7 +58,7 @@ __global__ __launch_bounds__(256) void k_mp_count(const u64 *q_hash, const u32 *
 __global__ __launch_bounds__(256) void k_mp_row_begin(const u32 *qid, u32 n_rows, u32 n_qseqs, u32 *row_begin) {
     const u32 q = blockIdx.x * 256 + threadIdx.x;
     if (q > n_qseqs) return;
-    row_begin[q] = ks_lower_bound_u32(qid, n_rows, q);
+    row_begin[q] = ks_query_row_begin(qid, n_rows, q);
 }
 
 // last index in [lo, hi] whose off[] is <= p (off[lo] <= p holds)

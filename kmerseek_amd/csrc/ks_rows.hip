@@ -251,14 +251,8 @@ __global__ __launch_bounds__(256) void k_row_abund_stats_long(const u64 *pk, con
 // min_containment: a stable compaction of the row columns.  k_rows_keep writes the keep flag of every row (the host's f64
 // test: (double)intersect / (double)|q| >= min_containment, |q| = the query's distinct hashes), an exclusive scan turns the
 // flags into destinations (its total, the kept count, lands beside the row count: one read-back), k_rows_filter moves the kept
-// rows, recomputing the same flag.
+// rows (rf_cols / rf_move, ks_device.h), recomputing the same flag.
 // ---------------------------------------------------------------------------------------------
-struct rf_cols {
-    const u32 *qid, *tid, *isect;
-    const u64 *nw, *median2;
-    const double *ss;
-};
-
 KS_DEV bool rf_kept(const rf_cols &in, u32 r, const u64 *q_offsets, const u32 *q_counts, u32 n_queries, double min_c) {
     const u32 q = in.qid[r];
     if (q >= n_queries) return false; // (a row without a head: only after a look-back that gave up, which is repeated)
@@ -280,9 +274,7 @@ __global__ __launch_bounds__(256) void k_rows_filter(rf_cols in, const u32 *n_ro
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     const u32 n_rows = *n_rows_dev < rows_cap ? *n_rows_dev : rows_cap;
     if (r >= n_rows || !rf_kept(in, r, q_offsets, q_counts, n_queries, min_c)) return;
-    const u32 o = dst[r];
-    qid[o] = in.qid[r]; tid[o] = in.tid[r]; isect[o] = in.isect[r]; nw[o] = in.nw[r];
-    if (median2) { median2[o] = in.median2[r]; ss[o] = in.ss[r]; }
+    rf_move(in, r, dst[r], qid, tid, isect, nw, median2, ss);
 }
 
 // the row columns of H (and the statistics) back to the pool

@@ -84,6 +84,10 @@ def search_opts(min_containment: float = 0.0, abund_stats: bool = False) -> Opti
     return _lib.ks_search_opts(_lib.KS_SEARCH_ABUND_STATS if abund_stats else 0, 0, float(min_containment))
 
 
+BEST_RANK_BY = {"intersect": _lib.KS_BEST_INTERSECT, "target_containment": _lib.KS_BEST_TARGET_CONTAINMENT,
+                "max_containment": _lib.KS_BEST_MAX_CONTAINMENT, "jaccard": _lib.KS_BEST_JACCARD, "score": _lib.KS_BEST_SCORE}
+
+
 class _FollowDebugEnv:
     """Library proxy of a diagnostic context: re-reads the KS_DEBUG_* variables before every call (the library itself reads
     them only when a context is created).  The tests use it to force the rarely taken paths on one context."""
@@ -385,6 +389,26 @@ class Context:
             for c in own:
                 c.free()
 
+    def best_hits(self, hits: "Hits", k: int, rank_by: str = "intersect", queries: Optional["Sketches"] = None,
+                  targets: Optional["Sketches"] = None, score=None) -> "Hits":
+        """ks_hits_best: the k best rows of every query of `hits`, still ordered by (qid, tid), with each kept row's rank
+        inside its query and its row in `hits` (Hits.best_to_host).  rank_by: intersect | target_containment (needs
+        `targets`) | max_containment | jaccard (need both sets) | score — `score` is a device column of hits.count f64, as a
+        raw pointer or an object with data_ptr() (e.g. one of Significance.device_ptrs()); with `score` given and rank_by
+        left at its default, rank_by becomes score.  Ties go to the smaller tid; NaN scores rank last."""
+        if score is not None and rank_by == "intersect":
+            rank_by = "score"
+        if rank_by not in BEST_RANK_BY:
+            raise ValueError(f"rank_by must be one of {', '.join(BEST_RANK_BY)}, not {rank_by!r}")
+        if not 0 <= int(k) < 2 ** 32:
+            raise ValueError(f"k = {k} does not fit 32 bits")
+        d_score = None if score is None else C.c_void_p(int(score.data_ptr()) if hasattr(score, "data_ptr") else int(score))
+        opts = _lib.ks_best_opts(BEST_RANK_BY[rank_by], int(k), 0, 0)
+        out = C.c_void_p()
+        self._check(self._L.ks_hits_best(self._h, hits._h, None if queries is None else queries._h,
+                                         None if targets is None else targets._h, d_score, C.byref(opts), C.byref(out)))
+        return Hits(self, out)
+
     # ---- index / search ----
     def index_build(self, targets: "Sketches") -> "Index":
         out = C.c_void_p()
@@ -658,6 +682,16 @@ class Significance(_Owned):
         L = self._ctx._L
         return tuple(int(f(self._h) or 0) for f in (L.ks_signif_device_prob_overlap, L.ks_signif_device_tf_idf))
 
+    @property
+    def prob_overlap_ptr(self) -> int:
+        """Device pointer of the prob_overlap column (`Context.best_hits(score=...)`)."""
+        return self.device_ptrs()[0]
+
+    @property
+    def tf_idf_ptr(self) -> int:
+        """Device pointer of the tf_idf column (`Context.best_hits(score=...)`)."""
+        return self.device_ptrs()[1]
+
     def to_host(self) -> Tuple[np.ndarray, np.ndarray]:
         """(prob_overlap f64, tf_idf f64) per hit row."""
         n = self.n_rows
@@ -738,3 +772,13 @@ class Hits(_Owned):
         median2 = np.zeros(n, np.uint64); ss = np.zeros(n, np.float64)
         self._ctx._check(self._ctx._L.ks_hits_copy_abund_stats_to_host(self._ctx._h, self._h, _ptr(median2), _ptr(ss)))
         return median2, ss
+
+    def best_to_host(self) -> Optional[Tuple[np.ndarray, np.ndarray]]:
+        """(rank u32, src_row u32) per row of a `Context.best_hits` result: the row's rank inside its query (0 = best) and its
+        row in the hit list it was chosen from.  None for hits that did not come from best_hits."""
+        if not self._ctx._L.ks_hits_device_rank(self._h):
+            return None
+        n = self.count
+        rank = np.zeros(n, np.uint32); src = np.zeros(n, np.uint32)
+        self._ctx._check(self._ctx._L.ks_hits_copy_best_to_host(self._ctx._h, self._h, _ptr(rank), _ptr(src)))
+        return rank, src

@@ -197,9 +197,10 @@ def manysearch_rows(q_names, q_off, q_mins, t_names, t_off, t_mins, t_abund, hit
 
 
 def do_manysearch(query_sig: str, target_sig: str, output: str, ksize: int, scaled: int, moltype: str,
-                  ctx: Optional[Context] = None) -> int:
+                  ctx: Optional[Context] = None, top_k: int = 0, rank_by: str = "intersect") -> int:
     """Search every sketch of query_sig (.sig.zip) against every sketch of target_sig; CSV rows for pairs that share
-    at least one hash.  Returns the number of rows written."""
+    at least one hash.  top_k > 0 keeps only the top_k best matches of every query (Context.best_hits; rank_by: intersect |
+    target_containment | max_containment | jaccard), in the same order as before.  Returns the number of rows written."""
     own = ctx is None
     ctx = ctx or Context(0)
     try:
@@ -210,7 +211,10 @@ def do_manysearch(query_sig: str, target_sig: str, output: str, ksize: int, scal
                 raise ValueError(f"sketch parameters {have} do not match the requested {(ksize, scaled, moltype)}")
         Q = ctx.sketches_from_host(qo, qm, qa, ksize, scaled, moltype)
         T = ctx.sketches_from_host(to, tm, ta, ksize, scaled, moltype)
-        hits = ctx.search(ctx.index_build(T), Q).to_host()
+        hits = ctx.search(ctx.index_build(T), Q)
+        if top_k > 0:
+            hits = ctx.best_hits(hits, top_k, rank_by, queries=Q, targets=T)
+        hits = hits.to_host()
         rows = manysearch_rows(qn, qo, qm, tn, to, tm, ta, hits, ksize, scaled, moltype)
         with open(output, "w", newline="") as f:
             w = csv.DictWriter(f, fieldnames=MANYSEARCH_COLUMNS, lineterminator="\n")
@@ -275,10 +279,12 @@ def multisearch_rows(q_names, q_off, q_mins, t_names, t_off, t_mins, hits, prob_
 
 
 def do_multisearch(query_sig: str, target_sig: str, output: str, ksize: int, scaled: int, moltype: str,
-                   ctx: Optional[Context] = None) -> int:
+                   ctx: Optional[Context] = None, top_k: int = 0, rank_by: str = "intersect") -> int:
     """Search every sketch of query_sig (.sig.zip) against every sketch of target_sig and weigh every hit (prob_overlap,
-    tf_idf_score and the columns derived from them); CSV rows for pairs that share at least one hash.  Returns the number of
-    rows written."""
+    tf_idf_score and the columns derived from them); CSV rows for pairs that share at least one hash.  top_k > 0 keeps only the
+    top_k best matches of every query, in the same order as before: by one of do_manysearch's keys (the hits are thinned
+    first and only the kept rows are weighed), or by tf_idf_score (every row is weighed, the best are chosen by that column
+    on the device, and the kept rows' sums are gathered through src_row).  Returns the number of rows written."""
     own = ctx is None
     ctx = ctx or Context(0)
     try:
@@ -291,8 +297,20 @@ def do_multisearch(query_sig: str, target_sig: str, output: str, ksize: int, sca
         T = ctx.sketches_from_host(to, tm, ta, ksize, scaled, moltype)
         ix = ctx.index_build(T)
         hits = ctx.search(ix, Q)
-        sig = ctx.significance(Q, T, hits)
-        po, tf = sig.to_host()
+        if top_k > 0 and rank_by == "tf_idf_score":
+            sig = ctx.significance(Q, T, hits)
+            best = ctx.best_hits(hits, top_k, score=sig.tf_idf_ptr)
+            src = best.best_to_host()[1]
+            po, tf = (c[src] for c in sig.to_host())
+            hits.free()
+            hits = best
+        else:
+            if top_k > 0:
+                best = ctx.best_hits(hits, top_k, rank_by, queries=Q, targets=T)
+                hits.free()
+                hits = best
+            sig = ctx.significance(Q, T, hits)
+            po, tf = sig.to_host()
         rows = multisearch_rows(qn, qo, qm, tn, to, tm, hits.to_host(), po, tf, ksize, scaled, moltype)
         for o in (sig, hits, ix, Q, T):
             o.free()
