@@ -72,6 +72,7 @@ typedef struct ks_index ks_index;       /* device-resident inverted index: posti
 typedef struct ks_hits ks_hits;         /* device-resident COO (qid, tid, intersect, n_weighted) */
 typedef struct ks_kmerpos ks_kmerpos;   /* device-resident (seq, start, hash) triples */
 typedef struct ks_matchpos ks_matchpos; /* device-resident CSR over hit rows: (query start, target start) of shared k-mers */
+typedef struct ks_regions ks_regions;   /* device-resident CSR over hit rows: the colinear regions those pairs chain into */
 
 /* ---- library / context ------------------------------------------------------------------ */
 
@@ -378,6 +379,58 @@ const uint32_t *ks_matchpos_device_t_hi(const ks_matchpos *m);
 int ks_matchpos_copy_to_host(ks_ctx *ctx, const ks_matchpos *m, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
                              uint32_t *q_lo, uint32_t *q_hi, uint32_t *t_lo, uint32_t *t_hi);
 void ks_matchpos_free(ks_matchpos *m);
+
+/* ---- match regions: each hit's pairs chained by diagonal ------------------------------------------------------------------- */
+
+/* The last step before the reference's output line, `query:start-end` found in `target:start-end`: every hit row's pairs
+ * chained into maximal colinear regions.  The reference's stitcher (src/python/kmerseek/search.py:37-121) takes all pairs of
+ * a match for ONE contiguous colinear run and returns a wrong region when they are not (two unrelated k-mers, a multi-domain
+ * protein); this pass returns every run.  All arithmetic is in integers.
+ *   pair of hit row r: (a, b) = (query start, target start); its diagonal d = b - a (signed); the pairs of a row are distinct
+ *   region: a maximal set of pairs of one row and one d in which, sorted by a, consecutive pairs satisfy
+ *           a_next - a_prev <= ksize + max_gap   (max_gap = 0: the windows overlap or abut)
+ *   ksize: that of the tables the ks_matchpos was made from.
+ * Per region:
+ *   q_start = the smallest a;  t_start = q_start + d
+ *   length  = the largest a + ksize - q_start — the same on both sides: the region is [q_start, q_start + length) in the
+ *             query and [t_start, t_start + length) in the target, 0-based half-open as the reference's columns
+ *   n_kmers = the number of pairs
+ *   covered = sum over consecutive pairs of min(ksize, a_next - a_prev), + ksize: the residues under at least one shared
+ *             window (= length when max_gap = 0)
+ * Regions with fewer than min_kmers pairs are dropped after chaining (0 and 1 keep everything); a row may keep none.
+ * Result (device-resident):
+ *   row_offsets u64[n_rows + 1]   row r owns regions [row_offsets[r], row_offsets[r + 1]);  n_rows = ks_matchpos_n_rows(mp)
+ *   q_start, t_start, length, n_kmers, covered u32[n_regions]    inside a row ordered by (q_start, t_start)
+ * The result never depends on the internal path (slices, sort variant, wave or workgroup).  A ks_matchpos without rows or
+ * pairs gives a valid empty result.  max_gap is clamped so that ksize + max_gap stays a u32.
+ * KS_ERR_INVALID_ARG: non-zero flags / reserved (checked before any device work), NULL arguments, an input of another
+ * context.  KS_ERR_CAPACITY: the diagonal and the start fill the 64-bit sort key on their own (starts beyond 2^31), or more
+ * than 2^38 / ksize pairs (only reachable with ksize > 64).
+ * One stream, synchronous on return, two host waits (the region count comes back with the first); all scratch comes from the
+ * context's pool: 52 bytes per pair. */
+typedef struct ks_regions_opts {
+    uint32_t flags;     /* none defined: 0 */
+    uint32_t min_kmers; /* drop regions with fewer pairs; 0 = 1 = keep all */
+    uint32_t max_gap;   /* residues two consecutive windows of a region may leave uncovered between them */
+    uint32_t reserved;  /* 0 */
+} ks_regions_opts;
+/* opts == NULL: the defaults (min_kmers 1, max_gap 0) */
+int ks_match_regions(ks_ctx *ctx, const ks_matchpos *mp, const ks_regions_opts *opts, ks_regions **out);
+uint64_t ks_regions_n_rows(const ks_regions *r);
+uint64_t ks_regions_n_regions(const ks_regions *r);
+/* hit-row slices the chaining ran in (1 unless row index, diagonal and start need more than 64 key bits).  Diagnostic. */
+uint32_t ks_regions_n_slices(const ks_regions *r);
+/* device pointers, valid until ks_regions_free */
+const uint64_t *ks_regions_device_row_offsets(const ks_regions *r);
+const uint32_t *ks_regions_device_q_start(const ks_regions *r);
+const uint32_t *ks_regions_device_t_start(const ks_regions *r);
+const uint32_t *ks_regions_device_length(const ks_regions *r);
+const uint32_t *ks_regions_device_n_kmers(const ks_regions *r);
+const uint32_t *ks_regions_device_covered(const ks_regions *r);
+/* any destination may be NULL */
+int ks_regions_copy_to_host(ks_ctx *ctx, const ks_regions *r, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
+                            uint32_t *length, uint32_t *n_kmers, uint32_t *covered);
+void ks_regions_free(ks_regions *r);
 
 /* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
 

@@ -48,6 +48,10 @@ class ks_matchpos_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("max_pairs", C.c_uint64)]
 
 
+class ks_regions_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("min_kmers", C.c_uint32), ("max_gap", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -158,6 +162,18 @@ SIGNATURES = {
     "ks_matchpos_device_t_hi": (_vp, [_vp]),
     "ks_matchpos_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ks_matchpos_free": (None, [_vp]),
+    "ks_match_regions": (C.c_int, [_vp, _vp, C.POINTER(ks_regions_opts), _pp]),
+    "ks_regions_n_rows": (C.c_uint64, [_vp]),
+    "ks_regions_n_regions": (C.c_uint64, [_vp]),
+    "ks_regions_n_slices": (C.c_uint32, [_vp]),
+    "ks_regions_device_row_offsets": (_vp, [_vp]),
+    "ks_regions_device_q_start": (_vp, [_vp]),
+    "ks_regions_device_t_start": (_vp, [_vp]),
+    "ks_regions_device_length": (_vp, [_vp]),
+    "ks_regions_device_n_kmers": (_vp, [_vp]),
+    "ks_regions_device_covered": (_vp, [_vp]),
+    "ks_regions_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ks_regions_free": (None, [_vp]),
     "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
     "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
     "ks_corpus_n_docs": (C.c_uint32, [_vp]),

@@ -45,7 +45,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -271,13 +271,14 @@ enum : u32 {
     KS_PIN_DENSE = 199,      // u64: the scan total of ks_sketches_make_dense
     KS_PIN_SIGNIF = 200,     // 3 words, significance: first row with an id out of range | first row with another shared count | corpus flag
     KS_PIN_BEST = 203,       // 3 words, best hits: first row with an id out of range | first row with an empty sketch | kept rows
-    KS_PIN_END = 206,
+    KS_PIN_REGIONS = 206,    // u32: match regions kept (ks_regions.hip)
+    KS_PIN_END = 207,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -345,12 +346,50 @@ struct ks_kmerpos {
 // pairs of window starts that share a hash, grouped by hit row (ks_matchpos.hip)
 struct ks_matchpos {
     ks_ctx *ctx;
+    ks_params params;            // of the tables the pairs were joined from (ks_match_regions chains with their ksize)
     u64 n_rows, n_pairs;
     u32 n_slices;
+    u32 max_qs, max_ts;          // the longest query / target start of the tables: bounds of q_start / t_start
     u64 *d_row_offsets;          // n_rows + 1
     u32 *d_qstart, *d_tstart;    // n_pairs
     u32 *d_qlo, *d_qhi, *d_tlo, *d_thi; // n_rows
 };
+
+// chained pairs of one hit row: maximal colinear runs of shared k-mers (ks_regions.hip)
+struct ks_regions {
+    ks_ctx *ctx;
+    u64 n_rows, n_regions;
+    u32 n_slices;
+    u64 *d_row_offsets;                                 // n_rows + 1
+    u32 *d_qstart, *d_tstart, *d_length, *d_nkmers, *d_covered; // n_regions
+};
+
+// ---- passes whose sort key is `hit row | fields of the pair` (ks_matchpos.hip, ks_regions.hip) ----
+// Row index and fields that do not fit 64 bits together: the hit rows are cut into slices, each sorted with a key of its own
+// whose row field counts from the slice's first row.  A record of another slice carries the row value one past the slice:
+// the sort takes it to the end.
+struct ks_slice_fmt {
+    int pt, pqt;          // bits of the lowest field, of all fields below the row
+    u32 row0, slice_rows; // rows [row0, row0 + slice_rows) are this slice's
+};
+struct ks_row_slices {
+    u64 per_slice, n_slices;
+    int low_bits; // the key bits below the row field
+    ks_slice_fmt fmt(u64 s, u64 n_rows, int pt) const {
+        ks_slice_fmt F;
+        F.pt = pt; F.pqt = low_bits;
+        F.row0 = (u32)(s * per_slice);
+        F.slice_rows = (u32)(n_rows - F.row0 < per_slice ? n_rows - F.row0 : per_slice);
+        return F;
+    }
+};
+int ks_key_bits(u64 v); // bits of v (at least 1)
+// the slices of n_rows (>= 1) hit rows under a key with low_bits bits below the row; dbg_id: the knob that narrows the row
+// field (tests: small inputs take the slice path).  KS_ERR_CAPACITY ("<what>: ...") when no key bit is left for a row.
+int ks_row_slices_plan(ks_ctx *ctx, int dbg_id, const char *what, int low_bits, u64 n_rows, ks_row_slices *out);
+// the sort of n keys in ka on their nbits live bits (ks_sort_pairs_msd, LSD passes for short lists); kb: scratch of the
+// same size; *sorted = where they ended up (ka or kb)
+int ks_sort_live_keys(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int nbits, u64 **sorted);
 
 // ---- device-wide primitives (ks_scan.hip, ks_sort.hip) ----
 // exclusive scan of n u32 values into u64 (out[n] = total is also written: out has n+1 entries)

@@ -172,6 +172,23 @@ template <typename T> KS_DEV u32 ks_lower_bound(const T *a, u32 n, T x) {
 }
 KS_DEV u32 ks_lower_bound_u64(const u64 *a, u32 n, u64 x) { return ks_lower_bound<u64>(a, n, x); }
 KS_DEV u32 ks_lower_bound_u32(const u32 *a, u32 n, u32 x) { return ks_lower_bound<u32>(a, n, x); }
+// last index in [lo, hi] whose off[] is <= p (off[lo] <= p holds): the owner of element p in a CSR
+KS_DEV u32 ks_last_le_u64(const u64 *off, u32 lo, u32 hi, u64 p) {
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo + 1) >> 1);
+        if (off[mid] <= p) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+// the same among n ascending u32 (a tile's offsets relative to its begin, staged in LDS); a[0] <= x holds
+KS_DEV u32 ks_last_le_u32(const u32 *a, u32 n, u32 x) {
+    u32 lo = 0, hi = n - 1;
+    while (lo < hi) {
+        const u32 mid = lo + ((hi - lo + 1) >> 1);
+        if (a[mid] <= x) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
 // Hit rows are ordered by (qid, tid): the rows of query q are the segment [ks_query_row_begin(q), ks_query_row_begin(q + 1)).
 // The first row whose qid is >= q (n_rows: none) — ks_match_positions' row_begin table and the segments of ks_hits_best.
 KS_DEV u32 ks_query_row_begin(const u32 *qid, u32 n_rows, u32 q) { return ks_lower_bound_u32(qid, n_rows, q); }

@@ -61,19 +61,7 @@ __global__ __launch_bounds__(256) void k_mp_row_begin(const u32 *qid, u32 n_rows
     row_begin[q] = ks_query_row_begin(qid, n_rows, q);
 }
 
-// last index in [lo, hi] whose off[] is <= p (off[lo] <= p holds)
-KS_DEV u32 mp_last_le(const u64 *off, u32 lo, u32 hi, u64 p) {
-    while (lo < hi) {
-        const u32 mid = lo + ((hi - lo + 1) >> 1);
-        if (off[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-struct mp_key_fmt {
-    int pt, pqt;         // bits of the target start, of both starts
-    u32 row0, slice_rows; // rows [row0, row0 + slice_rows) are this slice's; the key's row field counts from row0
-};
+typedef ks_slice_fmt mp_key_fmt; // pt / pqt: bits of the target start, of both starts
 
 // The hot kernel.  Candidate pair p belongs to the query window i with off[i] <= p < off[i + 1] and is its (p - off[i])-th
 // match: target record lo[i] + (p - off[i]) of the hash-sorted table.  Windows without a match have off[i] == off[i + 1] and
@@ -86,7 +74,7 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_expand(const u64 *off, u32 n_
     const u32 tid = threadIdx.x;
     const u64 begin = (u64)blockIdx.x * MP_TILE;
     const u64 end = begin + MP_TILE < n_cand ? begin + MP_TILE : n_cand;
-    if (tid < 2) s_w[tid] = mp_last_le(off, 0, n_q - 1, tid == 0 ? begin : end - 1); // (off[0] == 0 <= p)
+    if (tid < 2) s_w[tid] = ks_last_le_u64(off, 0, n_q - 1, tid == 0 ? begin : end - 1); // (off[0] == 0 <= p)
     __syncthreads();
     const u32 w_first = s_w[0], w_last = s_w[1], span = w_last - w_first + 1;
     const bool staged = span <= MP_STAGE;
@@ -105,15 +93,11 @@ __global__ __launch_bounds__(MP_THREADS) void k_mp_expand(const u64 *off, u32 n_
         w[it] = w_first; j[it] = 0;
         if (!live[it]) continue;
         if (staged) {
-            u32 a = 0, b = span - 1;
-            while (a < b) {
-                const u32 mid = a + ((b - a + 1) >> 1);
-                if (s_rel[mid] <= rel) a = mid; else b = mid - 1;
-            }
+            const u32 a = ks_last_le_u32(s_rel, span, rel);
             w[it] = w_first + a;
             j[it] = a ? rel - s_rel[a] : (u32)(p - off_first);
         } else {
-            w[it] = mp_last_le(off, w_first, w_last, p);
+            w[it] = ks_last_le_u64(off, w_first, w_last, p);
             j[it] = (u32)(p - off[w[it]]);
         }
     }
@@ -206,16 +190,29 @@ __global__ __launch_bounds__(256) void k_mp_rows(const u64 *keys, u64 n_cand, mp
     }
 }
 
-static int mp_bits(u64 v) { int b = 1; while (b < 64 && (v >> b)) b++; return b; }
+int ks_key_bits(u64 v) { int b = 1; while (b < 64 && (v >> b)) b++; return b; }
 
-// the sort of one slice's keys on their live bits; *sorted = where they ended up (ka or kb)
-static int mp_sort_keys(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int nbits, u64 **sorted) {
+int ks_sort_live_keys(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int nbits, u64 **sorted) {
     int msd = 0;
     KS_TRY(ks_sort_pairs_msd(ctx, ka, kb, n, 0, nbits, &msd));
     if (msd) { *sorted = ka; return KS_OK; }
     int shifts[8], ns = 0;
     for (int sh = 0; sh < nbits; sh += 8) shifts[ns++] = sh;
     return ks_radix_sort_keys(ctx, KS_SORT_PAIRS, ka, ka, kb, n, shifts, ns, sorted);
+}
+
+int ks_row_slices_plan(ks_ctx *ctx, int dbg_id, const char *what, int low_bits, u64 n_rows, ks_row_slices *out) {
+    int row_bits = 64 - low_bits;
+    if (row_bits > 31) row_bits = 31;
+    if (const char *f = ks_dbg(ctx, dbg_id)) { // (tests: small inputs take the slice path)
+        const int v = atoi(f);
+        if (v >= 1 && v < row_bits) row_bits = v;
+    }
+    if (row_bits < 1) return ks_fail(ctx, KS_ERR_CAPACITY, "%s: the pair fields take %d key bits and leave none for a row", what, low_bits);
+    out->low_bits = low_bits;
+    out->per_slice = ((1ULL << row_bits) - 1ULL) < n_rows ? ((1ULL << row_bits) - 1ULL) : n_rows;
+    out->n_slices = (n_rows + out->per_slice - 1) / out->per_slice;
+    return KS_OK;
 }
 
 static int mp_run(ks_ctx *ctx, const ks_kmerpos *Q, const ks_kmerpos *T, const ks_hits *H, u64 max_pairs, ks_matchpos *M) {
@@ -247,7 +244,7 @@ static int mp_run(ks_ctx *ctx, const ks_kmerpos *Q, const ks_kmerpos *T, const k
     KS_LAUNCH(ctx, "matchpos_pack", k_mp_pack, (n_t + 255) / 256, 256, (const u32 *)T->d_seq, (const u32 *)T->d_start, n_t, tv0, ctl + 1);
     {
         int shifts[8], ns = 0;
-        const int hbits = mp_bits(ks_max_hash(T->params.scaled));
+        const int hbits = ks_key_bits(ks_max_hash(T->params.scaled));
         for (int sh = 0; sh < hbits; sh += 8) shifts[ns++] = sh;
         KS_TRY(ks_radix_sort_u64(ctx, KS_SORT_INDEX, T->d_hash, tv0, ka, va, kb, vb, n_t, shifts, ns, &t_hash, &t_val));
     }
@@ -300,16 +297,11 @@ static int mp_run(ks_ctx *ctx, const ks_kmerpos *Q, const ks_kmerpos *T, const k
                        (unsigned long long)n_rows);
 
     // the key: row | query start | target start
-    const int pq = mp_bits(max_qs), pt = mp_bits(max_ts);
-    int row_bits = 64 - pq - pt;
-    if (row_bits > 31) row_bits = 31;
-    if (const char *f = ks_dbg(ctx, KS_DBG_MATCHPOS_ROW_BITS)) { // (tests: small inputs take the slice path)
-        const int v = atoi(f);
-        if (v >= 1 && v < row_bits) row_bits = v;
-    }
-    if (row_bits < 1) return ks_fail(ctx, KS_ERR_CAPACITY, "match positions: starts of %d + %d bits leave no key bit for a row", pq, pt);
-    const u64 per_slice = ((1ULL << row_bits) - 1ULL) < n_rows ? ((1ULL << row_bits) - 1ULL) : n_rows;
-    const u64 n_slices = (n_rows + per_slice - 1) / per_slice;
+    const int pq = ks_key_bits(max_qs), pt = ks_key_bits(max_ts);
+    M->max_qs = max_qs; M->max_ts = max_ts;
+    ks_row_slices SL;
+    KS_TRY(ks_row_slices_plan(ctx, KS_DBG_MATCHPOS_ROW_BITS, "match positions", pq + pt, n_rows, &SL));
+    const u64 n_slices = SL.n_slices;
     M->n_slices = (u32)n_slices;
 
     u32 *row_begin = nullptr;
@@ -324,14 +316,11 @@ static int mp_run(ks_ctx *ctx, const ks_kmerpos *Q, const ks_kmerpos *T, const k
     KS_LAUNCH(ctx, "matchpos_row_begin", k_mp_row_begin, (Q->n_seqs + 256) / 256, 256, (const u32 *)H->d_qid, (u32)n_rows, Q->n_seqs, row_begin);
     const u32 g_expand = (u32)((n_cand + MP_TILE - 1) / MP_TILE), g_rows = (u32)((n_cand + 1 + 255) / 256);
     for (u64 s = 0; s < n_slices; s++) {
-        mp_key_fmt F;
-        F.pt = pt; F.pqt = pq + pt;
-        F.row0 = (u32)(s * per_slice);
-        F.slice_rows = (u32)(n_rows - F.row0 < per_slice ? n_rows - F.row0 : per_slice);
+        const mp_key_fmt F = SL.fmt(s, n_rows, pt);
         KS_LAUNCH(ctx, "matchpos_expand", k_mp_expand, g_expand, MP_THREADS, (const u64 *)off, n_q, (const u32 *)lo, (const u32 *)Q->d_seq,
                   (const u32 *)Q->d_start, (const u64 *)t_val, (const u32 *)row_begin, (const u32 *)H->d_tid, F, n_cand, k0);
         u64 *sorted = nullptr;
-        KS_TRY(mp_sort_keys(ctx, k0, k1, n_cand, F.pqt + mp_bits(F.slice_rows), &sorted));
+        KS_TRY(ks_sort_live_keys(ctx, k0, k1, n_cand, F.pqt + ks_key_bits(F.slice_rows), &sorted));
         KS_LAUNCH(ctx, "matchpos_rows", k_mp_rows, g_rows, 256, (const u64 *)sorted, n_cand, F, Q->params.ksize, base + s, M->d_row_offsets,
                   M->d_qstart, M->d_tstart, M->d_qlo, M->d_qhi, M->d_tlo, M->d_thi, ctl + 2,
                   s + 1 == n_slices ? M->d_row_offsets + n_rows : (u64 *)nullptr);
@@ -366,6 +355,7 @@ extern "C" int ks_match_positions(ks_ctx *ctx, const ks_kmerpos *q_pos, const ks
     ks_matchpos *M = new ks_matchpos();
     memset(M, 0, sizeof *M);
     M->ctx = ctx;
+    M->params = q_pos->params;
     const int st = mp_run(ctx, q_pos, t_pos, hits, opts ? opts->max_pairs : 0, M);
     if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_matchpos_free(M); return st; }
     *out = M;

@@ -368,6 +368,19 @@ class Context:
         self._check(self._L.ks_match_positions(self._h, q_pos._h, t_pos._h, hits._h, C.byref(opts), C.byref(out)))
         return MatchPositions(self, out)
 
+    def match_regions(self, mp: "MatchPositions", max_gap: int = 0, min_kmers: int = 1) -> "Regions":
+        """ks_match_regions: every hit row's pairs chained into maximal colinear regions — pairs of one diagonal (target start -
+        query start) whose query starts, ascending, step by at most ksize + max_gap.  Per region q_start, t_start, length (the
+        same on both sides), n_kmers and covered (residues under a shared window); inside a row ordered by (q_start, t_start).
+        Regions with fewer than min_kmers pairs are dropped: a row may keep none."""
+        for name, v in (("max_gap", max_gap), ("min_kmers", min_kmers)):
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError(f"{name} = {v} does not fit 32 bits")
+        out = C.c_void_p()
+        opts = _lib.ks_regions_opts(0, int(min_kmers), int(max_gap), 0)
+        self._check(self._L.ks_match_regions(self._h, mp._h, C.byref(opts), C.byref(out)))
+        return Regions(self, out)
+
     def significance(self, queries: "Sketches", targets: "Sketches", hits: "Hits", q_corpus: Optional["Corpus"] = None,
                      t_corpus: Optional["Corpus"] = None) -> "Significance":
         """ks_hits_significance: per row of `hits` the two f64 sums behind multisearch's prob_overlap and tf_idf_score, over the
@@ -642,6 +655,37 @@ class MatchPositions(_Owned):
         self._ctx._check(self._ctx._L.ks_matchpos_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(qs), _ptr(ts),
                                                                *[_ptr(e) for e in ext]))
         return (offs, qs, ts, *ext)
+
+
+class Regions(_Owned):
+    """Device-resident CSR over hit rows (ks_regions): row r of the hits owns regions [row_offsets[r], row_offsets[r + 1])."""
+    _free = "ks_regions_free"
+    _COLUMNS = ("row_offsets", "q_start", "t_start", "length", "n_kmers", "covered")
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_regions_n_rows(self._h))
+
+    @property
+    def n_regions(self) -> int:
+        return int(self._ctx._L.ks_regions_n_regions(self._h))
+
+    @property
+    def n_slices(self) -> int:
+        """Hit-row slices the chaining ran in (1 unless row index, diagonal and start do not fit one 64-bit key).  Diagnostic."""
+        return int(self._ctx._L.ks_regions_n_slices(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (row_offsets u64[n_rows + 1], q_start / t_start / length / n_kmers / covered u32[n_regions])."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_regions_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """(row_offsets u64[n_rows + 1], q_start, t_start, length, n_kmers, covered u32[n_regions])."""
+        offs = np.zeros(self.n_rows + 1, np.uint64)
+        cols = [np.zeros(self.n_regions, np.uint32) for _ in range(5)]
+        self._ctx._check(self._ctx._L.ks_regions_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
+        return (offs, *cols)
 
 
 class Corpus(_Owned):

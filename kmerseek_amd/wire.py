@@ -490,11 +490,36 @@ def stitch_match_positions(q_records: Sequence[Tuple[str, bytes]], t_records: Se
     return out
 
 
+def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, regions_host,
+                moltype: str) -> List[dict]:
+    """One row per region of the device's chaining (Context.match_regions; regions_host = Regions.to_host()): hit row
+    r = (qid[r], tid[r]) owns regions [row_offsets[r], row_offsets[r + 1]).  The stitched columns of search.py:195-240 —
+    query / match / encoded are the residues the region spans, sliced from the records (a region lies on one diagonal, so
+    no stitching is left to do) — plus n_kmers and covered.  Where a match is one colinear run the row equals the
+    reference's stitched row; where it is not, every run gets a row of its own.  Sorted by (query's place in q_records,
+    query_start, query_end)."""
+    offs, q_start, t_start, length, n_kmers, covered = [np.asarray(c).tolist() for c in regions_host]
+    out = []
+    for r, (q, t) in enumerate(zip(np.asarray(qid).tolist(), np.asarray(tid).tolist())):
+        qn, qseq = q_records[q]
+        tn, tseq = t_records[t]
+        for g in range(offs[r], offs[r + 1]):
+            a, b, n = q_start[g], t_start[g], length[g]
+            query = qseq[a:a + n].decode().upper()
+            out.append((q, {"match_name": tn, "query_name": qn, "query_start": a, "query_end": a + n, "query": query,
+                            "match_start": b, "match_end": b + n, "match": tseq[b:b + n].decode().upper(),
+                            "encoded": encode_kmer(query, moltype), "length": n, "n_kmers": n_kmers[g], "covered": covered[g]}))
+    out.sort(key=lambda e: (e[0], e[1]["query_start"], e[1]["query_end"]))
+    return [row for _, row in out]
+
+
 def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int, scaled: int, moltype: str,
-                                ctx: Optional[Context] = None) -> List[dict]:
+                                ctx: Optional[Context] = None, regions: bool = False, max_gap: int = 0,
+                                min_kmers: int = 1) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
-    Same rows as `search_extract_kmers`."""
+    Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
+    max_gap / min_kmers) and only the regions come to the host: the rows of `region_rows`, one per colinear run."""
     own = ctx is None
     ctx = ctx or Context(0)
     try:
@@ -509,6 +534,12 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
         tp = ctx.kmer_positions_table(t_res, t_off, ksize, scaled, moltype)
         mp = ctx.match_positions(qp, tp, hits)
         qid, tid, _, _ = hits.to_host()
+        if regions:
+            rg = ctx.match_regions(mp, max_gap=max_gap, min_kmers=min_kmers)
+            rg_host = rg.to_host()
+            for o in (rg, mp, qp, tp, hits, Q, T):
+                o.free()
+            return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype)
         offs, qs, ts = mp.to_host()[:3]
         for o in (mp, qp, tp, hits, Q, T):
             o.free()

@@ -224,6 +224,12 @@ def _join_tables(q_tab, t_tab, hit_qid, hit_tid, ksize):
     return offs, a, b, ext
 
 
+def _regions_ref():
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import regions_ref
+    return regions_ref
+
+
 MATCHPOS_MAX_PAIRS = 4_000_000  # low-complexity batches join into far more: those cases check the refusal instead
 
 
@@ -231,7 +237,8 @@ def run_matchpos(cases: int, seed: int, knobs=None) -> int:
     """Match-position cases: a target batch, a query batch that overlaps it, search (every other case thresholded), the two
     k-mer tables, ks_match_positions with max_pairs = MATCHPOS_MAX_PAIRS — compared with a numpy join of the host copies of the
     same tables and hits (which the other cases hold against the oracle).  A join beyond the limit must be refused with
-    KS_ERR_CAPACITY and the count.  Returns the number of failures."""
+    KS_ERR_CAPACITY and the count.  The pairs that agree are then chained (ks_match_regions, random max_gap / min_kmers) and
+    compared with the numpy chaining of tests/regions_ref.py.  Returns the number of failures."""
     from kmerseek_amd import _lib
     rng = np.random.default_rng(seed)
     knobs = knobs or {}
@@ -279,6 +286,15 @@ def run_matchpos(cases: int, seed: int, knobs=None) -> int:
                 ok = ext is not None and all(np.array_equal(g, w) for g, w in zip(got[3:], ext))
             if not ok:
                 print("MATCHPOS MISMATCH", tag, f"rows={len(qid)} pairs={len(got[1])}/{len(a)} slices={mp.n_slices}"); bad += 1
+            else:  # the region pass on the same pairs, against the numpy chaining of tests/regions_ref.py
+                max_gap, min_kmers = int(rng.choice([0, 0, 1, k, 2 ** 32 - 1])), int(rng.choice([0, 1, 2, 5]))
+                with knobs_set(knobs):
+                    rg = ctx.match_regions(mp, max_gap=max_gap, min_kmers=min_kmers)
+                    got_rg = rg.to_host()
+                    rg.free()
+                want_rg = _regions_ref().chain(offs, a, b, k, max_gap, min_kmers)
+                if not all(np.array_equal(g, w) for g, w in zip(got_rg, want_rg)):
+                    print("REGIONS MISMATCH", tag, f"max_gap={max_gap} min_kmers={min_kmers} regions={len(got_rg[1])}/{len(want_rg[1])}"); bad += 1
             for o in (mp, qp, tp, hits, Q, T):
                 o.free()
         except Exception as e:  # noqa: BLE001

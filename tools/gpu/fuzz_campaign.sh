@@ -42,4 +42,6 @@ mrun() { name=$1; shift; env "$@" timeout -k 10 400 python tools/fuzz_parity.py 
 SEED=330 mrun matchpos A=1
 SEED=331 mrun matchpos_slices KS_DEBUG_MATCHPOS_ROW_BITS=4
 SEED=332 mrun matchpos_lsd KS_DEBUG_PAIRS_LSD=1 KS_DEBUG_SCAN_3PASS=1
+# regions: every case above also chains its pairs (ks_match_regions against tests/regions_ref.py); here with the chaining in slices
+SEED=333 mrun regions_slices KS_DEBUG_REGIONS_ROW_BITS=3
 fi
