@@ -26,8 +26,25 @@ extern "C" int ks_sketch_queries_device(ks_ctx *ctx, const ks_index *index, cons
     });
 }
 
-static int upload_batch(ks_ctx *ctx, const uint8_t *residues, const uint64_t *seq_offsets, uint32_t n_seqs,
-                        u8 **d_res, u64 **d_offs, u64 *n_res, u32 *max_len) {
+// A batch uploaded from host arrays for one call.  Its two blocks go back to the pool when the owner leaves scope, behind a
+// wait: the uploads read the caller's arrays and the call's launches read the blocks.
+struct ks_upload {
+    ks_ctx *ctx;
+    u8 *d_res = nullptr;
+    u64 *d_offs = nullptr;
+    u64 n_res = 0;
+    u32 max_len = 0;
+    explicit ks_upload(ks_ctx *c) : ctx(c) {}
+    ks_upload(const ks_upload &) = delete;
+    ~ks_upload() {
+        (void)hipStreamSynchronize(ctx->stream);
+        ks_pool_free(ctx, d_res);
+        ks_pool_free(ctx, d_offs);
+    }
+    int upload(const uint8_t *residues, const uint64_t *seq_offsets, uint32_t n_seqs);
+};
+
+int ks_upload::upload(const uint8_t *residues, const uint64_t *seq_offsets, uint32_t n_seqs) {
     if (!seq_offsets) return ks_fail(ctx, KS_ERR_INVALID_ARG, "seq_offsets is NULL");
     u64 total = seq_offsets[n_seqs];
     u64 mx = 0;
@@ -40,12 +57,12 @@ static int upload_batch(ks_ctx *ctx, const uint8_t *residues, const uint64_t *se
     if (mx > 0xfffffff0ULL) return ks_fail(ctx, KS_ERR_INVALID_ARG, "sequence longer than 2^32 residues");
     if (total && !residues) return ks_fail(ctx, KS_ERR_INVALID_ARG, "residues is NULL");
     KS_HIP(ctx, hipSetDevice(ctx->device));
-    KS_TRY(ks_alloc(ctx, d_res, (size_t)total + 16));
-    KS_TRY(ks_alloc(ctx, d_offs, (size_t)n_seqs + 1));
-    if (total) KS_TRY(ks_copy_h2d(ctx, *d_res, residues, (size_t)total));
-    KS_HIP(ctx, hipMemcpyAsync(*d_offs, seq_offsets, ((size_t)n_seqs + 1) * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    *n_res = total;
-    *max_len = (u32)mx;
+    KS_TRY(ks_alloc(ctx, &d_res, (size_t)total + 16));
+    KS_TRY(ks_alloc(ctx, &d_offs, (size_t)n_seqs + 1));
+    if (total) KS_TRY(ks_copy_h2d(ctx, d_res, residues, (size_t)total));
+    KS_HIP(ctx, hipMemcpyAsync(d_offs, seq_offsets, ((size_t)n_seqs + 1) * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    n_res = total;
+    max_len = (u32)mx;
     return KS_OK;
 }
 
@@ -55,16 +72,9 @@ extern "C" int ks_sketch_batch(ks_ctx *ctx, const uint8_t *residues, const uint6
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "out is NULL");
     KS_TRY(ks_check_params(ctx, params));
-    u8 *d_res = nullptr;
-    u64 *d_offs = nullptr;
-    u64 n_res = 0;
-    u32 max_len = 0;
-    int st = upload_batch(ctx, residues, seq_offsets, n_seqs, &d_res, &d_offs, &n_res, &max_len);
-    if (st == KS_OK) st = ks_sketch_device_impl(ctx, d_res, d_offs, n_seqs, n_res, max_len, params, 0, 0, 0, out);
-    (void)hipStreamSynchronize(ctx->stream);
-    ks_pool_free(ctx, d_res);
-    ks_pool_free(ctx, d_offs);
-    return st;
+    ks_upload U(ctx);
+    KS_TRY(U.upload(residues, seq_offsets, n_seqs));
+    return ks_sketch_device_impl(ctx, U.d_res, U.d_offs, n_seqs, U.n_res, U.max_len, params, 0, 0, 0, out);
     });
 }
 
@@ -87,33 +97,28 @@ int ks_sketches_make_dense(ks_ctx *ctx, ks_sketches *S) {
     if (S->pending) return ks_fail(ctx, KS_ERR_INVALID_ARG, "sketches with a pending read-back cannot be made dense");
     if (!S->d_counts) return ks_fail(ctx, KS_ERR_HIP, "internal error: gapped sketches without per-sequence counts");
     KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_scratch sc(ctx); // (the new arrays are scratch until they replace the old ones)
     u64 *no = nullptr, *nh = nullptr;
     u32 *na = nullptr;
-    int st = ks_alloc(ctx, &no, (size_t)S->n_seqs + 1);
-    if (st == KS_OK) st = ks_alloc(ctx, &nh, (size_t)S->n_hashes);
-    if (st == KS_OK) st = ks_alloc(ctx, &na, (size_t)S->n_hashes);
-    if (st == KS_OK) st = ks_scan_u32_to_u64(ctx, S->d_counts, no, S->n_seqs);
-    if (st == KS_OK && S->n_seqs) {
-        ks_timer_begin(ctx, "dense_gather");
-        hipLaunchKernelGGL(k_dense_gather, dim3((S->n_seqs + 3) / 4), dim3(256), 0, ctx->stream, (const u64 *)S->d_offsets, (const u64 *)no,
-                           (const u64 *)S->d_hashes, (const u32 *)S->d_abunds, S->n_seqs, nh, na, S->n_hashes);
-        ks_timer_end(ctx);
-        if (hipGetLastError() != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "dense gather launch failed");
-    }
+    KS_TRY(sc.alloc(&no, (size_t)S->n_seqs + 1));
+    KS_TRY(sc.alloc(&nh, (size_t)S->n_hashes));
+    KS_TRY(sc.alloc(&na, (size_t)S->n_hashes));
+    KS_TRY(ks_scan_u32_to_u64(ctx, S->d_counts, no, S->n_seqs));
+    if (S->n_seqs)
+        KS_LAUNCH(ctx, "dense_gather", k_dense_gather, (S->n_seqs + 3) / 4, 256, (const u64 *)S->d_offsets, (const u64 *)no,
+                  (const u64 *)S->d_hashes, (const u32 *)S->d_abunds, S->n_seqs, nh, na, S->n_hashes);
     // the scan total (the distinct counts summed) must be the n_hashes the arrays were sized by: read with the scan status
     u64 *const total = ctx->h_pin + KS_PIN_DENSE;
     *total = 0;
-    if (st == KS_OK && hipMemcpyAsync(total, no + S->n_seqs, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess)
-        st = ks_fail(ctx, KS_ERR_HIP, "dense gather read-back failed");
-    if (st == KS_OK) st = ks_scan_status_fetch(ctx);
-    if (st == KS_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "dense gather failed");
-    if (st == KS_OK) st = ks_scan_status_check(ctx);
-    if (st == KS_OK && *total != S->n_hashes)
-        st = ks_fail(ctx, KS_ERR_HIP, "internal error: sketch counts sum to %llu, but the batch holds %llu distinct hashes",
-                     (unsigned long long)*total, (unsigned long long)S->n_hashes);
-    if (st != KS_OK) { ks_pool_free(ctx, no); ks_pool_free(ctx, nh); ks_pool_free(ctx, na); return st; }
+    KS_HIP(ctx, hipMemcpyAsync(total, no + S->n_seqs, sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
+    KS_TRY(ks_scan_status_fetch(ctx));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    KS_TRY(ks_scan_status_check(ctx));
+    if (*total != S->n_hashes)
+        return ks_fail(ctx, KS_ERR_HIP, "internal error: sketch counts sum to %llu, but the batch holds %llu distinct hashes",
+                       (unsigned long long)*total, (unsigned long long)S->n_hashes);
     ks_pool_free(ctx, S->d_offsets); ks_pool_free(ctx, S->d_hashes); ks_pool_free(ctx, S->d_abunds);
-    S->d_offsets = no; S->d_hashes = nh; S->d_abunds = na;
+    S->d_offsets = sc.keep(no); S->d_hashes = sc.keep(nh); S->d_abunds = sc.keep(na);
     S->n_slots = S->n_hashes;
     S->gapped = false;
     return KS_OK;
@@ -144,11 +149,10 @@ extern "C" int ks_sketches_copy_to_host(ks_ctx *ctx, const ks_sketches *s, uint6
     if (!ctx || !s) return KS_ERR_INVALID_ARG;
     KS_HIP(ctx, hipSetDevice(ctx->device));
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(s)));
-    if (offsets) KS_HIP(ctx, hipMemcpyAsync(offsets, s->d_offsets, ((size_t)s->n_seqs + 1) * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
-    if (hashes && s->n_hashes) KS_TRY(ks_copy_d2h(ctx, hashes, s->d_hashes, (size_t)s->n_hashes * sizeof(u64)));
-    if (abunds && s->n_hashes) KS_TRY(ks_copy_d2h(ctx, abunds, s->d_abunds, (size_t)s->n_hashes * sizeof(u32)));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    const size_t n = (size_t)s->n_hashes;
+    return ks_columns_to_host(ctx, {{offsets, s->d_offsets, ((size_t)s->n_seqs + 1) * sizeof(u64)},
+                                    {hashes, s->d_hashes, n * sizeof(u64)},
+                                    {abunds, s->d_abunds, n * sizeof(u32)}});
     });
 }
 
@@ -175,20 +179,18 @@ extern "C" int ks_sketches_from_host(ks_ctx *ctx, const uint64_t *offsets, const
         }
     }
     KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_sketches *S = new ks_sketches();
-    memset(S, 0, sizeof *S);
-    S->ctx = ctx; S->params = *params; S->n_seqs = n_seqs; S->n_hashes = S->n_slots = n; S->n_windows = 0;
-    int st = ks_alloc(ctx, &S->d_offsets, (size_t)n_seqs + 1);
-    if (st == KS_OK) st = ks_alloc(ctx, &S->d_hashes, (size_t)n);
-    if (st == KS_OK) st = ks_alloc(ctx, &S->d_abunds, (size_t)n);
-    if (st != KS_OK) { ks_sketches_free(S); return st; }
-    hipError_t e = hipMemcpyAsync(S->d_offsets, offsets, ((size_t)n_seqs + 1) * sizeof(u64), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(S->d_hashes, hashes, (size_t)n * sizeof(u64), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && n) e = hipMemcpyAsync(S->d_abunds, abunds, (size_t)n * sizeof(u32), hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { ks_sketches_free(S); return ks_fail(ctx, KS_ERR_HIP, "upload failed: %s", hipGetErrorString(e)); }
-    *out = S;
-    return KS_OK;
+    ks_result<ks_sketches> S(ctx, out, ks_sketches_free);
+    S->params = *params; S->n_seqs = n_seqs; S->n_hashes = S->n_slots = n;
+    KS_TRY(ks_alloc(ctx, &S->d_offsets, (size_t)n_seqs + 1));
+    KS_TRY(ks_alloc(ctx, &S->d_hashes, (size_t)n));
+    KS_TRY(ks_alloc(ctx, &S->d_abunds, (size_t)n));
+    KS_HIP(ctx, hipMemcpyAsync(S->d_offsets, offsets, ((size_t)n_seqs + 1) * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    if (n) {
+        KS_HIP(ctx, hipMemcpyAsync(S->d_hashes, hashes, (size_t)n * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+        KS_HIP(ctx, hipMemcpyAsync(S->d_abunds, abunds, (size_t)n * sizeof(u32), hipMemcpyHostToDevice, ctx->stream));
+    }
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return S.commit();
     });
 }
 
@@ -222,20 +224,16 @@ int ks_kmerpos_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 
     KS_TRY(ks_check_params(ctx, p));
     if (((uintptr_t)d_res & 15) != 0) return ks_fail(ctx, KS_ERR_INVALID_ARG, "d_residues must be 16-byte aligned");
     KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_kmerpos *K = new ks_kmerpos();
-    memset(K, 0, sizeof *K);
-    K->ctx = ctx; K->params = *p; K->n_seqs = n_seqs;
-    int st = KS_OK;
+    ks_result<ks_kmerpos> K(ctx, out, ks_kmerpos_free);
+    K->params = *p; K->n_seqs = n_seqs;
     // every residue position starts at most one window: n_res bounds the table
     const size_t cap = (n_res == 0 || n_seqs == 0) ? 1 : (size_t)n_res;
-    st = ks_alloc(ctx, &K->d_seq, cap);
-    if (st == KS_OK) st = ks_alloc(ctx, &K->d_start, cap);
-    if (st == KS_OK) st = ks_alloc(ctx, &K->d_hash, cap);
-    if (st == KS_OK && n_res != 0 && n_seqs != 0)
-        st = ks_kmerpos_tiles_launch(ctx, d_res, d_offs, n_seqs, n_res, p, K->d_seq, K->d_start, K->d_hash, &K->n);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_kmerpos_free(K); return st; }
-    *out = K;
-    return KS_OK;
+    KS_TRY(ks_alloc(ctx, &K->d_seq, cap));
+    KS_TRY(ks_alloc(ctx, &K->d_start, cap));
+    KS_TRY(ks_alloc(ctx, &K->d_hash, cap));
+    if (n_res != 0 && n_seqs != 0)
+        KS_TRY(ks_kmerpos_tiles_launch(ctx, d_res, d_offs, n_seqs, n_res, p, K->d_seq, K->d_start, K->d_hash, &K->n));
+    return K.commit();
 }
 
 extern "C" int ks_kmer_positions(ks_ctx *ctx, const uint8_t *residues, const uint64_t *seq_offsets, uint32_t n_seqs,
@@ -244,16 +242,9 @@ extern "C" int ks_kmer_positions(ks_ctx *ctx, const uint8_t *residues, const uin
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "out is NULL");
     KS_TRY(ks_check_params(ctx, params));
-    u8 *d_res = nullptr;
-    u64 *d_offs = nullptr;
-    u64 n_res = 0;
-    u32 max_len = 0;
-    int st = upload_batch(ctx, residues, seq_offsets, n_seqs, &d_res, &d_offs, &n_res, &max_len);
-    if (st == KS_OK) st = ks_kmerpos_device_impl(ctx, d_res, d_offs, n_seqs, n_res, params, out);
-    (void)hipStreamSynchronize(ctx->stream);
-    ks_pool_free(ctx, d_res);
-    ks_pool_free(ctx, d_offs);
-    return st;
+    ks_upload U(ctx);
+    KS_TRY(U.upload(residues, seq_offsets, n_seqs));
+    return ks_kmerpos_device_impl(ctx, U.d_res, U.d_offs, n_seqs, U.n_res, params, out);
     });
 }
 
@@ -273,14 +264,8 @@ extern "C" void ks_kmerpos_params(const ks_kmerpos *p, ks_params *out) { if (p &
 extern "C" int ks_kmerpos_copy_to_host(ks_ctx *ctx, const ks_kmerpos *p, uint32_t *seq, uint32_t *start, uint64_t *hash) {
     return ks_guard(ctx, [&]() -> int {
     if (!ctx || !p) return KS_ERR_INVALID_ARG;
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    if (p->n) {
-        if (seq) KS_TRY(ks_copy_d2h(ctx, seq, p->d_seq, (size_t)p->n * sizeof(u32)));
-        if (start) KS_TRY(ks_copy_d2h(ctx, start, p->d_start, (size_t)p->n * sizeof(u32)));
-        if (hash) KS_TRY(ks_copy_d2h(ctx, hash, p->d_hash, (size_t)p->n * sizeof(u64)));
-    }
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    const size_t n = (size_t)p->n;
+    return ks_columns_to_host(ctx, {{seq, p->d_seq, n * sizeof(u32)}, {start, p->d_start, n * sizeof(u32)}, {hash, p->d_hash, n * sizeof(u64)}});
     });
 }
 
@@ -395,16 +380,9 @@ extern "C" int ks_sketch_search_ex(ks_ctx *ctx, const ks_index *index, const uin
     KS_TRY(ks_search_opts_check(ctx, opts));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!index || !hits_out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    u8 *d_res = nullptr;
-    u64 *d_offs = nullptr;
-    u64 n_res = 0;
-    u32 max_len = 0;
-    int st = upload_batch(ctx, residues, seq_offsets, n_seqs, &d_res, &d_offs, &n_res, &max_len);
-    if (st == KS_OK) st = sketch_search_impl(ctx, index, d_res, d_offs, n_seqs, n_res, max_len, opts, sketches_out, hits_out);
-    (void)hipStreamSynchronize(ctx->stream);
-    ks_pool_free(ctx, d_res);
-    ks_pool_free(ctx, d_offs);
-    return st;
+    ks_upload U(ctx);
+    KS_TRY(U.upload(residues, seq_offsets, n_seqs));
+    return sketch_search_impl(ctx, index, U.d_res, U.d_offs, n_seqs, U.n_res, U.max_len, opts, sketches_out, hits_out);
     });
 }
 extern "C" int ks_sketch_search(ks_ctx *ctx, const ks_index *index, const uint8_t *residues, const uint64_t *seq_offsets,
@@ -427,16 +405,9 @@ extern "C" int ks_hits_copy_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t *qid
                                     uint64_t *n_weighted) {
     return ks_guard(ctx, [&]() -> int {
     if (!ctx || !h) return KS_ERR_INVALID_ARG;
-    KS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)h->n_hits;
-    if (n) {
-        if (qid) KS_TRY(ks_copy_d2h(ctx, qid, h->d_qid, n * sizeof(u32)));
-        if (tid) KS_TRY(ks_copy_d2h(ctx, tid, h->d_tid, n * sizeof(u32)));
-        if (intersect) KS_TRY(ks_copy_d2h(ctx, intersect, h->d_isect, n * sizeof(u32)));
-        if (n_weighted) KS_TRY(ks_copy_d2h(ctx, n_weighted, h->d_nw, n * sizeof(u64)));
-    }
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    return ks_columns_to_host(ctx, {{qid, h->d_qid, n * sizeof(u32)}, {tid, h->d_tid, n * sizeof(u32)},
+                                    {intersect, h->d_isect, n * sizeof(u32)}, {n_weighted, h->d_nw, n * sizeof(u64)}});
     });
 }
 extern "C" const uint32_t *ks_hits_device_qid(const ks_hits *h) { return h ? h->d_qid : nullptr; }
@@ -601,37 +572,29 @@ extern "C" int ks_hits_merge_by_qid_device(ks_ctx *ctx, const uint32_t *d_qid, c
     if (!d_qid || !d_tid || !d_intersect || !d_n_weighted || !d_out_qid || !d_out_tid || !d_out_intersect || !d_out_n_weighted)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_HIP(ctx, hipSetDevice(ctx->device));
+    // (the scratch blocks go back to the pool in stream order: the next allocation on this context's stream comes behind the kernels)
+    ks_scratch sc(ctx);
     u32 *first = nullptr, *run = nullptr;
     const u64 n_first = ((u64)n_queries + 1) * n_blocks, n_run = (u64)n_queries * n_blocks;
-    int st = ks_alloc(ctx, &first, (size_t)n_first);
-    if (st == KS_OK) st = ks_alloc(ctx, &run, (size_t)n_run + 2); // (+ the scan's total, + the count of rows with an id out of range)
-    u32 *const n_dropped = run ? run + n_run + 1 : nullptr;
-    if (st == KS_OK && hipMemsetAsync(n_dropped, 0, sizeof(u32), ctx->stream) != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "merge: memset failed");
-    if (st == KS_OK) {
-        ks_timer_begin(ctx, "hits_merge");
-        hipLaunchKernelGGL(k_hm_starts, dim3((u32)((n_first + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)d_qid, B, n_queries, first);
-        if (n_run) hipLaunchKernelGGL(k_hm_runs, dim3((u32)((n_run + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)first, n_blocks, n_queries, run);
-        ks_timer_end(ctx);
-        if (n_run) st = ks_scan_u32_inplace(ctx, run, n_run, nullptr);
-    }
-    if (st == KS_OK) {
-        ks_timer_begin(ctx, "hits_merge");
-        hipLaunchKernelGGL(k_hm_move, dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)d_qid, (const u32 *)d_tid,
-                           (const u32 *)d_intersect, (const u64 *)d_n_weighted, B, n_queries, (const u32 *)first, (const u32 *)run, d_out_qid,
-                           d_out_tid, d_out_intersect, (u64 *)d_out_n_weighted, n_dropped);
-        ks_timer_end(ctx);
-        if (hipGetLastError() != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "merge launch failed");
-    }
-    if (st == KS_OK) { // a row whose query id lies beyond n_queries has no place in the merged order: the outputs would hold a gap
-        const u32 *dropped = (const u32 *)(ctx->h_pin + KS_PIN_READ);
-        const ks_fetch_seg f = ks_fetch_words(n_dropped, ctx->h_pin + KS_PIN_READ, 1);
-        st = ks_stream_wait_fetch(ctx, &f, 1);
-        if (st == KS_OK && *dropped != 0)
-            st = ks_fail(ctx, KS_ERR_INVALID_ARG, "merge: %u rows carry a query id >= n_queries = %u", *dropped, n_queries);
-    }
-    // (the scratch blocks go back to the pool in stream order: the next allocation on this context's stream comes behind the kernels)
-    ks_pool_free(ctx, first); ks_pool_free(ctx, run);
-    return st;
+    KS_TRY(sc.alloc(&first, (size_t)n_first));
+    KS_TRY(sc.alloc(&run, (size_t)n_run + 2)); // (+ the scan's total, + the count of rows with an id out of range)
+    u32 *const n_dropped = run + n_run + 1;
+    KS_HIP(ctx, hipMemsetAsync(n_dropped, 0, sizeof(u32), ctx->stream));
+    ks_timer_begin(ctx, "hits_merge"); // (one timing row for the two launches)
+    hipLaunchKernelGGL(k_hm_starts, dim3((u32)((n_first + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)d_qid, B, n_queries, first);
+    if (n_run) hipLaunchKernelGGL(k_hm_runs, dim3((u32)((n_run + 255) / 256)), dim3(256), 0, ctx->stream, (const u32 *)first, n_blocks, n_queries, run);
+    ks_timer_end(ctx);
+    KS_HIP(ctx, hipGetLastError());
+    if (n_run) KS_TRY(ks_scan_u32_inplace(ctx, run, n_run, nullptr));
+    KS_LAUNCH(ctx, "hits_merge", k_hm_move, (u32)((n + 255) / 256), 256, (const u32 *)d_qid, (const u32 *)d_tid, (const u32 *)d_intersect,
+              (const u64 *)d_n_weighted, B, n_queries, (const u32 *)first, (const u32 *)run, d_out_qid, d_out_tid, d_out_intersect,
+              (u64 *)d_out_n_weighted, n_dropped);
+    // a row whose query id lies beyond n_queries has no place in the merged order: the outputs would hold a gap
+    const u32 *dropped = (const u32 *)(ctx->h_pin + KS_PIN_READ);
+    const ks_fetch_seg f = ks_fetch_words(n_dropped, ctx->h_pin + KS_PIN_READ, 1);
+    KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
+    if (*dropped != 0) return ks_fail(ctx, KS_ERR_INVALID_ARG, "merge: %u rows carry a query id >= n_queries = %u", *dropped, n_queries);
+    return KS_OK;
     });
 }
 
@@ -643,12 +606,8 @@ extern "C" int ks_hits_copy_abund_stats_to_host(ks_ctx *ctx, const ks_hits *h, u
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!h) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     if (!h->has_stats) return ks_fail(ctx, KS_ERR_INVALID_ARG, "these hits were searched without KS_SEARCH_ABUND_STATS");
-    KS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)h->n_hits;
-    if (n && median2) KS_TRY(ks_copy_d2h(ctx, median2, h->d_median2, n * sizeof(u64)));
-    if (n && ss) KS_TRY(ks_copy_d2h(ctx, ss, h->d_ss, n * sizeof(double)));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    return ks_columns_to_host(ctx, {{median2, h->d_median2, n * sizeof(u64)}, {ss, h->d_ss, n * sizeof(double)}});
     });
 }
 

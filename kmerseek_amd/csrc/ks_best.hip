@@ -314,17 +314,13 @@ extern "C" int ks_hits_best(ks_ctx *ctx, const ks_hits *hits, const ks_sketches 
                        a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
     }
     KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_hits *B = new ks_hits();
-    memset(B, 0, sizeof *B);
-    B->ctx = ctx;
+    ks_result<ks_hits> B(ctx, out, ks_hits_free);
     B->n_pair_instances = hits->n_pair_instances;
     B->partition_path = hits->partition_path;
     B->bucket_posting_bytes = hits->bucket_posting_bytes;
     B->has_stats = hits->has_stats;
-    const int st = best_run(ctx, hits, queries, targets, d_score, opts, B);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_hits_free(B); return st; }
-    *out = B;
-    return KS_OK;
+    KS_TRY(best_run(ctx, hits, queries, targets, d_score, opts, B));
+    return B.commit();
     });
 }
 
@@ -336,11 +332,7 @@ extern "C" int ks_hits_copy_best_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!h) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     if (!h->d_rank) return ks_fail(ctx, KS_ERR_INVALID_ARG, "these hits did not come from ks_hits_best");
-    KS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)h->n_hits;
-    if (n && rank) KS_TRY(ks_copy_d2h(ctx, rank, h->d_rank, n * sizeof(u32)));
-    if (n && src_row) KS_TRY(ks_copy_d2h(ctx, src_row, h->d_src_row, n * sizeof(u32)));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    return ks_columns_to_host(ctx, {{rank, h->d_rank, n * sizeof(u32)}, {src_row, h->d_src_row, n * sizeof(u32)}});
     });
 }

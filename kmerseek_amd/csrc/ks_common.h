@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <new>
 #include <stdexcept>
 #include <string>
@@ -205,6 +206,32 @@ struct ks_scratch {
             if (blk[i] == p) { blk[i] = blk[--n]; return true; }
         return false;
     }
+};
+
+// One lifecycle for every opaque result object (ks_sketches, ks_index, ks_hits, ...).  The constructor clears *out and makes
+// the object: value-initialised, ->ctx set.  The driver fills it through KS_TRY / KS_HIP and ends with `return R.commit();`,
+// which hands the object to *out without a wait.  Every other way out of the scope — a failed status, an exception, a return
+// with KS_OK and nothing produced (search_core's split, sketch_attempt's redo) — waits for the stream (launches already queued
+// may still write the object's blocks) and gives the object to its free function; *out stays nullptr.
+template <typename T>
+struct ks_result {
+    T *obj = nullptr;
+    T **out;
+    void (*free_fn)(T *);
+    ks_result(ks_ctx *ctx, T **out_, void (*f)(T *)) : out(out_), free_fn(f) {
+        *out = nullptr;
+        obj = new T();
+        obj->ctx = ctx;
+    }
+    ks_result(const ks_result &) = delete;
+    ~ks_result() {
+        if (!obj) return;
+        (void)hipStreamSynchronize(obj->ctx->stream);
+        free_fn(obj);
+    }
+    T *operator->() const { return obj; }
+    operator T *() const { return obj; }
+    int commit() { *out = obj; obj = nullptr; return KS_OK; }
 };
 
 // ---- opaque objects ----
@@ -503,4 +530,7 @@ int ks_sketches_make_dense(ks_ctx *ctx, ks_sketches *s);
 // ---- boundary copies (ks_copy.hip): one DMA for pinned host memory, double-buffered pinned staging + copy threads otherwise
 int ks_copy_h2d(ks_ctx *ctx, void *dst_device, const void *src_host, size_t bytes); // enqueued; complete for pageable sources
 int ks_copy_d2h(ks_ctx *ctx, void *dst_host, const void *src_device, size_t bytes); // returns when dst holds the data
+// the body of every *_copy_to_host: each column with a destination and bytes to copy goes through ks_copy_d2h, then one wait
+struct ks_column { void *dst; const void *src; size_t bytes; };
+int ks_columns_to_host(ks_ctx *ctx, std::initializer_list<ks_column> cols);
 void ks_copy_engine_destroy(ks_ctx *ctx);

@@ -352,14 +352,10 @@ extern "C" int ks_match_positions(ks_ctx *ctx, const ks_kmerpos *q_pos, const ks
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "match positions: the tables were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)",
                        a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
     KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_matchpos *M = new ks_matchpos();
-    memset(M, 0, sizeof *M);
-    M->ctx = ctx;
+    ks_result<ks_matchpos> M(ctx, out, ks_matchpos_free);
     M->params = q_pos->params;
-    const int st = mp_run(ctx, q_pos, t_pos, hits, opts ? opts->max_pairs : 0, M);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_matchpos_free(M); return st; }
-    *out = M;
-    return KS_OK;
+    KS_TRY(mp_run(ctx, q_pos, t_pos, hits, opts ? opts->max_pairs : 0, M));
+    return M.commit();
     });
 }
 
@@ -378,17 +374,11 @@ extern "C" int ks_matchpos_copy_to_host(ks_ctx *ctx, const ks_matchpos *m, uint6
                                         uint32_t *q_lo, uint32_t *q_hi, uint32_t *t_lo, uint32_t *t_hi) {
     return ks_guard(ctx, [&]() -> int {
     if (!ctx || !m) return KS_ERR_INVALID_ARG;
-    KS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nr = (size_t)m->n_rows, np = (size_t)m->n_pairs;
-    if (row_offsets) KS_TRY(ks_copy_d2h(ctx, row_offsets, m->d_row_offsets, (nr + 1) * sizeof(u64)));
-    if (np && q_start) KS_TRY(ks_copy_d2h(ctx, q_start, m->d_qstart, np * sizeof(u32)));
-    if (np && t_start) KS_TRY(ks_copy_d2h(ctx, t_start, m->d_tstart, np * sizeof(u32)));
-    if (nr && q_lo) KS_TRY(ks_copy_d2h(ctx, q_lo, m->d_qlo, nr * sizeof(u32)));
-    if (nr && q_hi) KS_TRY(ks_copy_d2h(ctx, q_hi, m->d_qhi, nr * sizeof(u32)));
-    if (nr && t_lo) KS_TRY(ks_copy_d2h(ctx, t_lo, m->d_tlo, nr * sizeof(u32)));
-    if (nr && t_hi) KS_TRY(ks_copy_d2h(ctx, t_hi, m->d_thi, nr * sizeof(u32)));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    return ks_columns_to_host(ctx, {{row_offsets, m->d_row_offsets, (nr + 1) * sizeof(u64)},
+                                    {q_start, m->d_qstart, np * sizeof(u32)}, {t_start, m->d_tstart, np * sizeof(u32)},
+                                    {q_lo, m->d_qlo, nr * sizeof(u32)}, {q_hi, m->d_qhi, nr * sizeof(u32)},
+                                    {t_lo, m->d_tlo, nr * sizeof(u32)}, {t_hi, m->d_thi, nr * sizeof(u32)}});
     });
 }
 

@@ -240,13 +240,9 @@ extern "C" int ks_match_regions(ks_ctx *ctx, const ks_matchpos *mp, const ks_reg
     *out = nullptr;
     if (mp->ctx != ctx) return ks_fail(ctx, KS_ERR_INVALID_ARG, "match regions: an input of another context");
     KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_regions *R = new ks_regions();
-    memset(R, 0, sizeof *R);
-    R->ctx = ctx;
-    const int st = rg_run(ctx, mp, opts ? opts->min_kmers : 0, opts ? opts->max_gap : 0, R);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_regions_free(R); return st; }
-    *out = R;
-    return KS_OK;
+    ks_result<ks_regions> R(ctx, out, ks_regions_free);
+    KS_TRY(rg_run(ctx, mp, opts ? opts->min_kmers : 0, opts ? opts->max_gap : 0, R));
+    return R.commit();
     });
 }
 
@@ -264,16 +260,11 @@ extern "C" int ks_regions_copy_to_host(ks_ctx *ctx, const ks_regions *r, uint64_
                                        uint32_t *length, uint32_t *n_kmers, uint32_t *covered) {
     return ks_guard(ctx, [&]() -> int {
     if (!ctx || !r) return KS_ERR_INVALID_ARG;
-    KS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t nr = (size_t)r->n_rows, ng = (size_t)r->n_regions;
-    if (row_offsets) KS_TRY(ks_copy_d2h(ctx, row_offsets, r->d_row_offsets, (nr + 1) * sizeof(u64)));
-    if (ng && q_start) KS_TRY(ks_copy_d2h(ctx, q_start, r->d_qstart, ng * sizeof(u32)));
-    if (ng && t_start) KS_TRY(ks_copy_d2h(ctx, t_start, r->d_tstart, ng * sizeof(u32)));
-    if (ng && length) KS_TRY(ks_copy_d2h(ctx, length, r->d_length, ng * sizeof(u32)));
-    if (ng && n_kmers) KS_TRY(ks_copy_d2h(ctx, n_kmers, r->d_nkmers, ng * sizeof(u32)));
-    if (ng && covered) KS_TRY(ks_copy_d2h(ctx, covered, r->d_covered, ng * sizeof(u32)));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    return ks_columns_to_host(ctx, {{row_offsets, r->d_row_offsets, (nr + 1) * sizeof(u64)},
+                                    {q_start, r->d_qstart, ng * sizeof(u32)}, {t_start, r->d_tstart, ng * sizeof(u32)},
+                                    {length, r->d_length, ng * sizeof(u32)}, {n_kmers, r->d_nkmers, ng * sizeof(u32)},
+                                    {covered, r->d_covered, ng * sizeof(u32)}});
     });
 }
 

@@ -456,11 +456,8 @@ int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out) {
     if (!in || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_HIP(ctx, hipSetDevice(ctx->device));
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(in)));
-    ks_sketches *U = new ks_sketches();
-    memset(U, 0, sizeof *U);
-    U->ctx = ctx; U->params = in->params; U->n_seqs = 1; U->n_windows = in->n_windows;
-    const int st = union_run(ctx, in, U);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_sketches_free(U); return st; }
-    *out = U;
-    return KS_OK;
+    ks_result<ks_sketches> U(ctx, out, ks_sketches_free);
+    U->params = in->params; U->n_seqs = 1; U->n_windows = in->n_windows;
+    KS_TRY(union_run(ctx, in, U));
+    return U.commit();
 }

@@ -151,16 +151,12 @@ int ks_index_build_impl(ks_ctx *ctx, const ks_sketches *t, ks_index **out) {
     if (!t || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_HIP(ctx, hipSetDevice(ctx->device));
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(t))); // (the sort reads the hashes as one dense array)
-    ks_index *ix = new ks_index();
-    memset(ix, 0, sizeof *ix);
-    ix->ctx = ctx;
+    ks_result<ks_index> ix(ctx, out, ks_index_free);
     ix->params = t->params;
     ix->n_targets = t->n_seqs;
     ix->n_postings = t->n_hashes;
-    const int st = index_build_run(ctx, t, ix);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_index_free(ix); return st; }
-    *out = ix;
-    return KS_OK;
+    KS_TRY(index_build_run(ctx, t, ix));
+    return ix.commit();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1204,18 +1200,17 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
         KS_TRY(sc.alloc(&Q.pk0, (size_t)(seg_cap * n_segs)));
         if (attempt > 0) // (attempt 0: cleared with the flag word above; the flag word survives)
             KS_HIP(ctx, hipMemset2DAsync(Q.cursor, (size_t)JN_CUR_STRIDE * sizeof(u64), 0, sizeof(u64), JN_SEGS, ctx->stream));
-        ks_timer_begin(ctx, "join_buckets");
         // (few query postings per bucket: the table kernel; KS_DEBUG_JOIN_SPARSE = 0 / 1 forces the choice in the tests)
         const bool sparse = ix->fp_layout && (ks_dbg(ctx, KS_DBG_JOIN_SPARSE) ? atoi(ks_dbg(ctx, KS_DBG_JOIN_SPARSE)) != 0
                                                                              : Q.n_q / n_buckets <= (u64)JS_QCAP * 3 / 4);
         if (sparse)
-            hipLaunchKernelGGL(q_fmt == 2 ? k_join_sparse<2> : (q_fmt ? k_join_sparse<1> : k_join_sparse<0>), dim3(n_buckets), dim3(JS_THREADS), 0, ctx->stream, (const u64 *)V.qk,
-                               (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta, V.q_lo,
-                               V.q_hi, dir_t, Q.pk0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
+            KS_LAUNCH(ctx, "join_buckets", (q_fmt == 2 ? k_join_sparse<2> : (q_fmt ? k_join_sparse<1> : k_join_sparse<0>)), n_buckets, JS_THREADS,
+                      (const u64 *)V.qk, (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta,
+                      V.q_lo, V.q_hi, dir_t, Q.pk0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
         else if (ix->fp_layout)
-            hipLaunchKernelGGL(q_fmt == 2 ? k_join_buckets<2> : (q_fmt ? k_join_buckets<1> : k_join_buckets<0>), dim3(n_buckets), dim3(JN_THREADS), 0, ctx->stream, (const u64 *)V.qk,
-                               (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta, V.q_lo,
-                               V.q_hi, dir_t, Q.pk0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
+            KS_LAUNCH(ctx, "join_buckets", (q_fmt == 2 ? k_join_buckets<2> : (q_fmt ? k_join_buckets<1> : k_join_buckets<0>)), n_buckets, JN_THREADS,
+                      (const u64 *)V.qk, (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta,
+                      V.q_lo, V.q_hi, dir_t, Q.pk0, seg_cap, Q.cursor, n_segs - 1, Q.tbits, Q.abits, ix->fp_shift);
         else {
             // workgroups per bucket: the matches per query posting of this context's previous search, when the buckets
             // hold enough query postings to share (KS_DEBUG_JOIN_SPLIT forces it)
@@ -1225,12 +1220,10 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
                 split = dens2 >= 6 ? 4u : (dens2 >= 3 ? 2u : 1u); // 200k x 200k hp: 0.73 / 0.59 / 0.53 / 0.59 ms with 1 / 2 / 4 / 8
             }
             if (const char *f = ks_dbg(ctx, KS_DBG_JOIN_SPLIT)) { const int v = atoi(f); if (v >= 1 && v <= 16) split = (u32)v; }
-            hipLaunchKernelGGL(k_join_buckets_keys, dim3(n_buckets * split), dim3(JN_THREADS), 0, ctx->stream, (const u64 *)V.qk,
-                               (const u32 *)V.qv, (const u64 *)ix->d_keys, (const u32 *)ix->d_tids, (const u32 *)ix->d_abunds,
-                               V.q_lo, V.q_hi, dir_t, Q.pk0, seg_cap, Q.cursor, Q.tbits, Q.abits, split);
+            KS_LAUNCH(ctx, "join_buckets", k_join_buckets_keys, n_buckets * split, JN_THREADS, (const u64 *)V.qk, (const u32 *)V.qv,
+                      (const u64 *)ix->d_keys, (const u32 *)ix->d_tids, (const u32 *)ix->d_abunds, V.q_lo, V.q_hi, dir_t, Q.pk0, seg_cap,
+                      Q.cursor, Q.tbits, Q.abits, split);
         }
-        ks_timer_end(ctx);
-        KS_HIP(ctx, hipGetLastError());
         // the segment counts (+ the flag word beside the first): one copy, strided when the list is segmented
         // (the kernel that stamps the host's flag writes them to the pinned block itself — with the control block of a
         // pending sketch — instead of a copy dispatch per block in front of it)
@@ -1416,14 +1409,10 @@ static int search_core(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, co
         ix->params.moltype != q->params.moltype || ix->params.seed != q->params.seed)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "query sketches and index were built with different parameters");
     KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_hits *H = new ks_hits();
-    memset(H, 0, sizeof *H);
-    H->ctx = ctx;
+    ks_result<ks_hits> H(ctx, out, ks_hits_free);
     bool stop = false;
-    const int st = search_run(ctx, ix, q, opts, H, split, sketch_redo, &stop);
-    if (st != KS_OK || stop) { (void)hipStreamSynchronize(ctx->stream); ks_hits_free(H); return st; }
-    *out = H;
-    return KS_OK;
+    KS_TRY(search_run(ctx, ix, q, opts, H, split, sketch_redo, &stop));
+    return stop ? KS_OK : H.commit(); // (stop: nothing produced, the caller splits or repeats the sketch)
 }
 
 __global__ __launch_bounds__(256) void k_rebase_offsets(const u64 *offs, u64 base, u32 n, u64 *out) {
@@ -1435,6 +1424,93 @@ __global__ __launch_bounds__(256) void k_add_u32(u32 *a, u64 n, u32 v) {
     if (i < n) a[i] += v;
 }
 
+// the view of query sequences [a, b) of a dense batch: its own offsets (made by search_sliced), the batch's hashes and abundances
+static ks_sketches sketches_slice_view(const ks_sketches *q, const std::vector<u64> &offs, u32 a, u32 b) {
+    ks_sketches V = ks_sketches();
+    V.ctx = q->ctx; V.params = q->params; V.n_seqs = b - a; V.n_hashes = offs[b] - offs[a]; V.n_windows = q->n_windows;
+    V.d_hashes = q->d_hashes + offs[a]; V.d_abunds = q->d_abunds + offs[a];
+    return V;
+}
+
+// the hit lists of the slices and the first query of each; the lists are freed with the owner
+struct se_parts {
+    std::vector<ks_hits *> hits;
+    std::vector<u32> firsts;
+    se_parts() = default;
+    se_parts(const se_parts &) = delete;
+    ~se_parts() { for (ks_hits *h : hits) ks_hits_free(h); }
+};
+
+// Slices of roughly equal posting counts, each expected to produce KS_PAIR_LIMIT / 4 records, of at most need.seqs sequences;
+// a slice that still overflows is halved.  offs: the batch's offsets on the host.
+static int search_sliced(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, const ks_search_opts *opts, const se_split &need,
+                         const std::vector<u64> &offs, se_parts &parts) {
+    u64 n_slices = need.pairs / (KS_PAIR_LIMIT / 4) + 1;
+    const u32 max_seqs = need.seqs ? need.seqs : q->n_seqs;
+    u32 a = 0;
+    while (a < q->n_seqs) {
+        const u64 want = q->n_hashes / n_slices + 1;
+        u32 b = a + 1;
+        while (b < q->n_seqs && b - a < max_seqs && offs[b + 1] - offs[a] <= want) b++;
+        for (;;) { // search sequences [a, b); halve the slice while it still overflows
+            ks_sketches V = sketches_slice_view(q, offs, a, b);
+            KS_TRY(ks_alloc(ctx, &V.d_offsets, (size_t)V.n_seqs + 1));
+            hipLaunchKernelGGL(k_rebase_offsets, dim3((V.n_seqs + 256) / 256), dim3(256), 0, ctx->stream, (const u64 *)q->d_offsets + a, offs[a],
+                               V.n_seqs + 1, V.d_offsets);
+            ks_hits *h = nullptr;
+            se_split more;
+            const int st = search_core(ctx, ix, &V, opts, &h, &more);
+            (void)hipStreamSynchronize(ctx->stream);
+            ks_pool_free(ctx, V.d_offsets);
+            KS_TRY(st);
+            if (more.pairs == 0 && more.seqs == 0) { parts.hits.push_back(h); parts.firsts.push_back(a); break; }
+            if (b - a == 1) return ks_fail(ctx, KS_ERR_CAPACITY, "one query sequence matches %llu postings: beyond the match-list limit", (unsigned long long)more.pairs);
+            b = a + (b - a) / 2;
+            n_slices *= 2;
+        }
+        a = b;
+    }
+    return KS_OK;
+}
+
+// the columns of a hit list that a concatenation carries: (member, element size); the last two only with statistics
+struct se_hit_col {
+    size_t member, elem; // where the column's pointer lies in ks_hits, bytes per row
+    u8 *get(const ks_hits *h) const { u8 *p; memcpy(&p, (const char *)h + member, sizeof p); return p; }
+    void set(ks_hits *h, u8 *p) const { memcpy((char *)h + member, &p, sizeof p); }
+};
+static const se_hit_col SE_HIT_COLS[6] = {{offsetof(ks_hits, d_qid), sizeof(u32)},     {offsetof(ks_hits, d_tid), sizeof(u32)},
+                                          {offsetof(ks_hits, d_isect), sizeof(u32)},   {offsetof(ks_hits, d_nw), sizeof(u64)},
+                                          {offsetof(ks_hits, d_median2), sizeof(u64)}, {offsetof(ks_hits, d_ss), sizeof(double)}};
+
+// the slices' hit lists in one (query ids back to batch numbering)
+static int hits_concat(ks_ctx *ctx, const se_parts &parts, bool has_stats, ks_hits **out) {
+    ks_result<ks_hits> H(ctx, out, ks_hits_free);
+    H->partition_path = 3;
+    H->has_stats = has_stats;
+    for (const ks_hits *h : parts.hits) { H->n_hits += h->n_hits; H->n_pair_instances += h->n_pair_instances; }
+    const int n_cols = has_stats ? 6 : 4;
+    for (int c = 0; c < n_cols; c++) {
+        u8 *col = nullptr;
+        KS_TRY(ks_alloc(ctx, &col, (size_t)(H->n_hits ? H->n_hits : 1) * SE_HIT_COLS[c].elem));
+        SE_HIT_COLS[c].set(H, col);
+    }
+    u64 at = 0;
+    for (size_t i = 0; i < parts.hits.size(); i++) {
+        ks_hits *const h = parts.hits[i];
+        const u64 n = h->n_hits;
+        if (!n) continue;
+        hipLaunchKernelGGL(k_add_u32, dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, h->d_qid, n, parts.firsts[i]);
+        for (int c = 0; c < n_cols; c++) {
+            const se_hit_col &C = SE_HIT_COLS[c];
+            KS_HIP(ctx, hipMemcpyAsync(C.get(H) + at * C.elem, C.get(h), n * C.elem, hipMemcpyDeviceToDevice, ctx->stream));
+        }
+        at += n;
+    }
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the copies read the parts, which their owner frees next)
+    return H.commit();
+}
+
 // ks_search: one match list when it fits; otherwise the query sequences are searched in contiguous slices whose lists
 // and records fit (a slice is a view of the batch's CSR: hits of different query ranges are disjoint and stay ordered by
 // qid; its qids are numbered from 0, so a slice of few sequences needs few id bits).  Options apply per slice: a slice's rows are
@@ -1442,80 +1518,15 @@ __global__ __launch_bounds__(256) void k_add_u32(u32 *a, u64 n, u32 v) {
 int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo, const ks_search_opts *opts) {
     if (!out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     se_split need;
-    int st = search_core(ctx, ix, q, opts, out, &need, sketch_redo);
-    if (st != KS_OK || (need.pairs == 0 && need.seqs == 0)) return st;
+    KS_TRY(search_core(ctx, ix, q, opts, out, &need, sketch_redo));
+    if (need.pairs == 0 && need.seqs == 0) return KS_OK;
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(q))); // (a slice is a view of the batch's plain CSR)
-    // ---- slices of roughly equal posting counts, each expected to produce KS_PAIR_LIMIT / 4 records, of at most max_seqs sequences
     std::vector<u64> offs((size_t)q->n_seqs + 1);
     KS_HIP(ctx, hipMemcpyAsync(offs.data(), q->d_offsets, offs.size() * sizeof(u64), hipMemcpyDeviceToHost, ctx->stream));
     KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    u64 n_slices = need.pairs / (KS_PAIR_LIMIT / 4) + 1;
-    const u32 max_seqs = need.seqs ? need.seqs : q->n_seqs;
-    std::vector<ks_hits *> parts;
-    std::vector<u32> firsts;
-    auto cleanup = [&]() { for (auto *h : parts) ks_hits_free(h); };
-    u32 a = 0;
-    while (a < q->n_seqs) {
-        const u64 want = q->n_hashes / n_slices + 1;
-        u32 b = a + 1;
-        while (b < q->n_seqs && b - a < max_seqs && offs[b + 1] - offs[a] <= want) b++;
-        for (;;) { // search sequences [a, b); halve the slice while it still overflows
-            ks_sketches V;
-            memset(&V, 0, sizeof V);
-            V.ctx = ctx; V.params = q->params; V.n_seqs = b - a; V.n_hashes = offs[b] - offs[a]; V.n_windows = q->n_windows;
-            V.d_hashes = q->d_hashes + offs[a]; V.d_abunds = q->d_abunds + offs[a];
-            st = ks_alloc(ctx, &V.d_offsets, (size_t)V.n_seqs + 1);
-            if (st != KS_OK) { cleanup(); return st; }
-            hipLaunchKernelGGL(k_rebase_offsets, dim3((V.n_seqs + 256) / 256), dim3(256), 0, ctx->stream, (const u64 *)q->d_offsets + a, offs[a],
-                               V.n_seqs + 1, V.d_offsets);
-            ks_hits *h = nullptr;
-            se_split more;
-            st = search_core(ctx, ix, &V, opts, &h, &more);
-            (void)hipStreamSynchronize(ctx->stream);
-            ks_pool_free(ctx, V.d_offsets);
-            if (st != KS_OK) { cleanup(); return st; }
-            if (more.pairs == 0 && more.seqs == 0) { parts.push_back(h); firsts.push_back(a); break; }
-            if (b - a == 1) { cleanup(); return ks_fail(ctx, KS_ERR_CAPACITY, "one query sequence matches %llu postings: beyond the match-list limit", (unsigned long long)more.pairs); }
-            b = a + (b - a) / 2;
-            n_slices *= 2;
-        }
-        a = b;
-    }
-    // ---- concatenate (query ids back to batch numbering)
-    ks_hits *H = new ks_hits();
-    memset(H, 0, sizeof *H);
-    H->ctx = ctx;
-    H->partition_path = 3;
-    H->has_stats = opts && (opts->flags & KS_SEARCH_ABUND_STATS);
-    for (auto *h : parts) { H->n_hits += h->n_hits; H->n_pair_instances += h->n_pair_instances; }
-    const size_t tot = H->n_hits ? (size_t)H->n_hits : 1;
-    st = ks_alloc(ctx, &H->d_qid, tot);
-    if (st == KS_OK) st = ks_alloc(ctx, &H->d_tid, tot);
-    if (st == KS_OK) st = ks_alloc(ctx, &H->d_isect, tot);
-    if (st == KS_OK) st = ks_alloc(ctx, &H->d_nw, tot);
-    if (st == KS_OK && H->has_stats) st = ks_alloc(ctx, &H->d_median2, tot);
-    if (st == KS_OK && H->has_stats) st = ks_alloc(ctx, &H->d_ss, tot);
-    u64 at = 0;
-    for (size_t i = 0; i < parts.size() && st == KS_OK; i++) {
-        const u64 n = parts[i]->n_hits;
-        if (n) {
-            hipLaunchKernelGGL(k_add_u32, dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, parts[i]->d_qid, n, firsts[i]);
-            if (hipMemcpyAsync(H->d_qid + at, parts[i]->d_qid, n * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(H->d_tid + at, parts[i]->d_tid, n * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(H->d_isect + at, parts[i]->d_isect, n * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                hipMemcpyAsync(H->d_nw + at, parts[i]->d_nw, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                (H->has_stats &&
-                 (hipMemcpyAsync(H->d_median2 + at, parts[i]->d_median2, n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess ||
-                  hipMemcpyAsync(H->d_ss + at, parts[i]->d_ss, n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)))
-                st = ks_fail(ctx, KS_ERR_HIP, "hit concatenation failed");
-            at += n;
-        }
-    }
-    (void)hipStreamSynchronize(ctx->stream);
-    cleanup();
-    if (st != KS_OK) { ks_hits_free(H); return st; }
-    *out = H;
-    return KS_OK;
+    se_parts parts;
+    KS_TRY(search_sliced(ctx, ix, q, opts, need, offs, parts));
+    return hits_concat(ctx, parts, opts && (opts->flags & KS_SEARCH_ABUND_STATS), out);
 }
 
 int ks_search_opts_check(ks_ctx *ctx, const ks_search_opts *o) {

@@ -98,13 +98,10 @@ extern "C" int ks_corpus_build(ks_ctx *ctx, const ks_sketches *sketches, ks_corp
     if (sketches->ctx != ctx) return ks_fail(ctx, KS_ERR_INVALID_ARG, "corpus: sketches of another context");
     KS_HIP(ctx, hipSetDevice(ctx->device));
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(sketches))); // (the sort reads the hashes as one dense array)
-    ks_corpus *C = new ks_corpus();
-    memset(C, 0, sizeof *C);
-    C->ctx = ctx; C->params = sketches->params; C->n_docs = sketches->n_seqs; C->n_postings = sketches->n_hashes;
-    const int st = corpus_run(ctx, sketches, C);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_corpus_free(C); return st; }
-    *out = C;
-    return KS_OK;
+    ks_result<ks_corpus> C(ctx, out, ks_corpus_free);
+    C->params = sketches->params; C->n_docs = sketches->n_seqs; C->n_postings = sketches->n_hashes;
+    KS_TRY(corpus_run(ctx, sketches, C));
+    return C.commit();
     });
 }
 
@@ -115,13 +112,8 @@ extern "C" uint64_t ks_corpus_total_abund(const ks_corpus *c) { return c ? c->to
 extern "C" int ks_corpus_copy_to_host(ks_ctx *ctx, const ks_corpus *c, uint64_t *hashes, uint64_t *abund_sum, uint32_t *doc_freq) {
     return ks_guard(ctx, [&]() -> int {
     if (!ctx || !c) return KS_ERR_INVALID_ARG;
-    KS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)c->n_hashes;
-    if (n && hashes) KS_TRY(ks_copy_d2h(ctx, hashes, c->d_hash, n * sizeof(u64)));
-    if (n && abund_sum) KS_TRY(ks_copy_d2h(ctx, abund_sum, c->d_sum, n * sizeof(u64)));
-    if (n && doc_freq) KS_TRY(ks_copy_d2h(ctx, doc_freq, c->d_df, n * sizeof(u32)));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    return ks_columns_to_host(ctx, {{hashes, c->d_hash, n * sizeof(u64)}, {abund_sum, c->d_sum, n * sizeof(u64)}, {doc_freq, c->d_df, n * sizeof(u32)}});
     });
 }
 
@@ -320,14 +312,10 @@ extern "C" int ks_hits_significance(ks_ctx *ctx, const ks_sketches *queries, con
     KS_HIP(ctx, hipSetDevice(ctx->device));
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(queries))); // (the passes read both sets as plain CSRs)
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(targets)));
-    ks_signif *S = new ks_signif();
-    memset(S, 0, sizeof *S);
-    S->ctx = ctx;
-    int st = signif_run(ctx, queries, targets, q_corpus, t_corpus, hits, S);
-    if (st == KS_OK && hits->n_hits == 0) st = ks_stream_wait(ctx);
-    if (st != KS_OK) { (void)hipStreamSynchronize(ctx->stream); ks_signif_free(S); return st; }
-    *out = S;
-    return KS_OK;
+    ks_result<ks_signif> S(ctx, out, ks_signif_free);
+    KS_TRY(signif_run(ctx, queries, targets, q_corpus, t_corpus, hits, S));
+    if (hits->n_hits == 0) KS_TRY(ks_stream_wait(ctx));
+    return S.commit();
     });
 }
 
@@ -338,12 +326,8 @@ extern "C" const double *ks_signif_device_tf_idf(const ks_signif *s) { return s 
 extern "C" int ks_signif_copy_to_host(ks_ctx *ctx, const ks_signif *s, double *prob_overlap, double *tf_idf) {
     return ks_guard(ctx, [&]() -> int {
     if (!ctx || !s) return KS_ERR_INVALID_ARG;
-    KS_HIP(ctx, hipSetDevice(ctx->device));
     const size_t n = (size_t)s->n_rows;
-    if (n && prob_overlap) KS_TRY(ks_copy_d2h(ctx, prob_overlap, s->d_prob, n * sizeof(double)));
-    if (n && tf_idf) KS_TRY(ks_copy_d2h(ctx, tf_idf, s->d_tfidf, n * sizeof(double)));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
+    return ks_columns_to_host(ctx, {{prob_overlap, s->d_prob, n * sizeof(double)}, {tf_idf, s->d_tfidf, n * sizeof(double)}});
     });
 }
 

@@ -1731,22 +1731,13 @@ static int sketch_attempt_run(ks_ctx *ctx, ks_sketches *S, const sk_call &C, int
 // overflowed its LDS lists, 2 = the batch kept more hashes than the bounded output arrays hold.
 static int sketch_attempt(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res, u32 max_seq_len, const ks_params *p,
                           int part_pbits, int part_fmt10, int variant, int allow_defer, int *redo, ks_sketches **out) {
-    ks_sketches *S = new ks_sketches();
-    memset(S, 0, sizeof *S);
-    S->ctx = ctx;
+    ks_result<ks_sketches> S(ctx, out, ks_sketches_free);
     S->params = *p;
     S->n_seqs = n_seqs;
-    *out = nullptr;
     *redo = 0;
     const sk_call C{d_res, d_offs, n_seqs, n_res, max_seq_len, p};
-    const int st = sketch_attempt_run(ctx, S, C, part_pbits, part_fmt10, variant, allow_defer, redo);
-    if (st != KS_OK || *redo) {
-        (void)hipStreamSynchronize(ctx->stream);
-        ks_sketches_free(S);
-        return st;
-    }
-    *out = S;
-    return KS_OK;
+    KS_TRY(sketch_attempt_run(ctx, S, C, part_pbits, part_fmt10, variant, allow_defer, redo));
+    return *redo ? KS_OK : S.commit();
 }
 
 ks_fetch_seg ks_sketch_pending_seg(const ks_sketches *S) {
