@@ -112,6 +112,10 @@ int ks_ctx_search_stats(const ks_ctx *ctx, uint64_t out[2]);
 /* ks_sketch_search_device on this context: out[0] = calls whose sketch read-back was folded into the search's first wait,
  * out[1] = calls that had to be repeated with the two plain calls (skewed hashes, an economy that did not fit). */
 int ks_ctx_fused_stats(const ks_ctx *ctx, uint64_t out[2]);
+/* The presence filter of the searches on this context (a fingerprint-layout index carries a bitmap over hash prefixes; the
+ * partition of the query postings drops those the bitmap rules out): out[0] = query postings the filtered partitions read,
+ * out[1] = postings they dropped.  Results never depend on the filter; KS_DEBUG_QFILTER = 0 / 1 forces it off / on. */
+int ks_ctx_qfilter_stats(const ks_ctx *ctx, uint64_t out[2]);
 /* Diagnostics: the KS_DEBUG_* environment variables (they force the rarely taken paths in the tests; results never
  * depend on them) are read once, when the context is created — never on the per-call path.  This reads them again. */
 int ks_ctx_reload_debug_env(ks_ctx *ctx);

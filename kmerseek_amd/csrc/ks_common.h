@@ -46,7 +46,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -94,6 +94,12 @@ struct ks_ctx {
     bool rows_use_ticket = false; u64 rows_ticket_fallbacks = 0; // k_pair_rows_fused: dispatch-order tile ids until a look-back gives up
     u64 fused_deferred = 0, fused_redos = 0; // ks_sketch_search_device: calls that folded the sketch wait into the first wait of the search / were repeated plainly
     u64 join_retries = 0; // searches whose match list outgrew a segment and ran the join twice
+    // The presence filter of the bucket scatter (ks_index::d_presence) pays while most query postings are foreign to the index.
+    // false after a search whose scatter kept more than half of its postings (the probes then cost more than the dropped
+    // bytes save); true again after an unfiltered search with fewer than a quarter as many matches as postings.
+    // KS_DEBUG_QFILTER = 0 / 1 forces either.
+    bool qfilter_pays = true;
+    u64 qfilter_seen = 0, qfilter_dropped = 0; // query postings of the filtered scatters of this context / those they dropped
     // single-launch scans (ks_prims.hip): status ring + ticket counter in device memory, never reset: every entry is
     // tagged with the global tile number that wrote it
     unsigned long long *scan_ring = nullptr;
@@ -341,6 +347,12 @@ struct ks_index {
     u32 max_abund; // largest of them: how many low bits of a packed match record the abundance needs
     u64 *d_dir;    // join-bucket directory: d_dir[b] = first posting whose join prefix is >= b (2^pbits + 1 entries)
     int pbits;     // join prefix bits, a function of n_postings and the layout alone (ks_join_pbits)
+    // fp_layout: presence bitmap over hash prefixes, for the query side's bucket scatter (k_bucket_scatter): bit
+    // ks_join_prefix(hash, pres_K) is set iff some posting has that prefix.  2^pres_bits bits (pres_bits >= pbits: every join
+    // bucket owns 2^(pres_bits - pbits) of them, ~KS_QF_OCC per posting).  nullptr: the index has none (key-column join).
+    u32 *d_presence;
+    u32 pres_K;
+    int pres_bits;
 };
 
 struct ks_hits {
@@ -452,8 +464,13 @@ int ks_radix_sort_keys(ks_ctx *ctx, int tag, const u64 *keys_in, u64 *ka, u64 *k
 // one window of n_hi * bcap records (a handful of pages) instead of 256 * bcap records apart (one page each: 5 M
 // UTCL1 translation misses per launch with the digit-major order, 0.02 M with this one — same run time, though)
 #define KS_BSLOT(d, r, n_hi) ((r) * (n_hi) + (d))
+// status[1] of the bucket scatter: bit 0 = a bucket overflowed; from bit KS_QF_KEPT up = postings that passed the presence filter
+#define KS_QF_KEPT 1
+// presence != nullptr: postings whose bit of the index's presence bitmap (ks_index::d_presence, multiplier presK) is clear are
+// dropped; fix_s: where the region's 8 prefix bits sit in the high word of a hash (vfmt != 0: the keys carry id bits there)
 int ks_bucket_scatter_u32(ks_ctx *ctx, const u64 *keys_in, const u32 *vals_in, const ks_rs_segments *seg, int shift,
-                          u32 pfxK, u64 *bkeys, u32 *bvals, u32 *bcur, u32 bcap, unsigned long long *status, u32 n_hi, int vfmt);
+                          u32 pfxK, u64 *bkeys, u32 *bvals, u32 *bcur, u32 bcap, unsigned long long *status, u32 n_hi, int vfmt,
+                          const u32 *presence, u32 presK, u32 fix_s);
 // index build in three passes (two partition passes + in-LDS bucket sort); *overflowed = 1: use the LSD sort instead
 int ks_index_sort_partitioned(ks_ctx *ctx, const u64 *keys_in, const u64 *vals_in, u64 n, u64 max_hash, u64 *okeys, u32 *otids,
                               u32 *oabunds, u32 *d_max_abund, int *overflowed);

@@ -255,6 +255,14 @@ extern "C" int ks_ctx_search_stats(const ks_ctx *ctx, uint64_t out[2]) {
     });
 }
 
+extern "C" int ks_ctx_qfilter_stats(const ks_ctx *ctx, uint64_t out[2]) {
+    return ks_guard((ks_ctx *)ctx, [&]() -> int {
+    if (!ctx || !out) return KS_ERR_INVALID_ARG;
+    out[0] = ctx->qfilter_seen; out[1] = ctx->qfilter_dropped;
+    return KS_OK;
+    });
+}
+
 extern "C" int ks_ctx_fused_stats(const ks_ctx *ctx, uint64_t out[2]) {
     return ks_guard((ks_ctx *)ctx, [&]() -> int {
     if (!ctx || !out) return KS_ERR_INVALID_ARG;

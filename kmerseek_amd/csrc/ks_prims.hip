@@ -405,13 +405,21 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void k_radix_scatter(const u64
 // V16 = 1: the value column is 16 bits wide, in and out (10-byte query postings: ks_sketches::part_s).
 // V16 = 2: 16 bits in, 8 bits out (9-byte postings; join prefixes of 16 bits only): the bucket implies the key's top byte too —
 // it is this pass's digit —, so the low byte of the value moves there and its high byte is the 8-bit column that leaves.
-template <int V16>
+// QF: the presence filter.  `presence` is the index's bitmap over hash prefixes (ks_index::d_presence: bit umulhi(hash >> 32, presK)
+// is set iff some index posting has that prefix); a query posting whose bit is clear cannot match and becomes "no record" before it
+// is ranked, so the counts, the cursors, the overflow check and the fill counts the join reads describe the survivors only.  A tile's
+// postings share their region's 8 prefix bits: the words it probes are 2^(pbits - 8) chunks of the bitmap, and the tiles an XCD runs
+// at one time belong to one or two regions (ks_xcd_block), whose chunks stay in that XCD's L2.  The sixteen probes are requested
+// together, like the rank atomics behind them: a dropped (or absent) record's atomic goes to a spare counter of its lane, so
+// neither step has a branch to wait in.  The number of survivors is added to status[1] above its overflow bit (KS_QF_KEPT).
+template <int V16, bool QF>
 // (two workgroups of 8 waves per CU by the 70 KB of LDS: 4 waves per SIMD, i.e. a budget of 128 registers)
 __global__ __launch_bounds__(RS_THREADS, 4) void k_bucket_scatter(const u64 *kin, const u32 *vin, u64 *kout, u32 *vout,
                                                                         int shift, const u32 *seg_len, u64 seg_cap,
                                                                         u32 tiles_per_seg, u32 *bcur, u32 bcap,
-                                                                        unsigned long long *status, u32 pfxK, u32 n_hi, u32 sub_shift) {
-    __shared__ u32 cnt[BKS_NB];     // the high digit takes up to BKS_NB values (n_hi of them in use: a power of two)
+                                                                        unsigned long long *status, u32 pfxK, u32 n_hi, u32 sub_shift,
+                                                                        const u32 *presence, u32 presK, u32 fix_s) {
+    __shared__ u32 cnt[BKS_NB + (QF ? 64 : 0)]; // the high digit takes up to BKS_NB values (n_hi of them in use: a power of two); QF: + a spare per lane
     __shared__ u32 dstart[BKS_NB];
     __shared__ u32 gbase[BKS_NB];
     __shared__ u32 scan_smem[RS_WAVES + 1];
@@ -444,8 +452,29 @@ __global__ __launch_bounds__(RS_THREADS, 4) void k_bucket_scatter(const u64 *kin
     // A full tile — all but the last of a sub-region — ranks its records without a guard: sixteen LDS atomics in flight, one wait.
     // (Behind `if (li < nvalid)` every atomic sat in a branch of its own and was waited for in turn: sixteen LDS round trips in a
     // row per thread, with four waves per SIMD to hide them.)
-    const bool full = nvalid == RS_TILE; // (uniform)
-    if (full) {
+    const bool full = !QF && nvalid == RS_TILE; // (uniform)
+    if constexpr (QF) {
+        u32 bit[RS_IPT], dg[RS_IPT];
+#pragma unroll
+        for (int r = 0; r < RS_IPT; r++) {
+            u32 hh = (u32)(key[r] >> 32);
+            // (10-byte postings: the region's prefix bits carry sequence id bits — the hash had the region's number there)
+            if (V16) hh = (hh & ~(0xffu << fix_s)) | (region << fix_s);
+            bit[r] = __umulhi(hh, presK);
+        }
+        u32 w[RS_IPT]; // (a slot behind nvalid holds key 0: it probes a word of the bitmap like any other and is dropped below)
+#pragma unroll
+        for (int r = 0; r < RS_IPT; r++) w[r] = presence[bit[r] >> 5];
+#pragma unroll
+        for (int r = 0; r < RS_IPT; r++) {
+            const bool live = (u32)r * RS_THREADS + tid < nvalid && ((w[r] >> (bit[r] & 31u)) & 1u);
+            dg[r] = live ? ((ks_join_prefix(key[r], pfxK) >> shift) & (n_hi - 1u)) : (u32)BKS_NB + (tid & 63u);
+        }
+#pragma unroll
+        for (int r = 0; r < RS_IPT; r++) rank[r] = atomicAdd(&cnt[dg[r]], 1u);
+#pragma unroll
+        for (int r = 0; r < RS_IPT; r++) rank[r] = dg[r] < BKS_NB ? (rank[r] | (dg[r] << 16)) : 0xffffffffu;
+    } else if (full) {
         u32 dg[RS_IPT];
 #pragma unroll
         for (int r = 0; r < RS_IPT; r++) dg[r] = (ks_join_prefix(key[r], pfxK) >> shift) & (n_hi - 1u);
@@ -465,10 +494,15 @@ __global__ __launch_bounds__(RS_THREADS, 4) void k_bucket_scatter(const u64 *kin
         }
     }
     __syncthreads();
+    u32 n_kept = nvalid; // records of the tile that leave it (QF: the survivors)
     {
         const u32 c = tid < BKS_NB ? cnt[tid] : 0u;
         u32 total;
         const u32 ds = ks_block_excl_scan(c, scan_smem, &total);
+        if constexpr (QF) {
+            n_kept = total;
+            if (tid == 0 && total) atomicAdd(&status[1], (unsigned long long)total << KS_QF_KEPT);
+        }
         if (tid < BKS_NB) {
             dstart[tid] = ds;
             u32 base = 0;
@@ -509,7 +543,7 @@ __global__ __launch_bounds__(RS_THREADS, 4) void k_bucket_scatter(const u64 *kin
     {
         u64 ks_[RS_IPT];
 #pragma unroll
-        for (int i = 0; i < RS_IPT; i++) ks_[i] = stage[(u32)i * RS_THREADS + tid]; // (slots behind nvalid: stale, masked below)
+        for (int i = 0; i < RS_IPT; i++) ks_[i] = stage[(u32)i * RS_THREADS + tid]; // (slots behind n_kept: stale, masked below)
 #pragma unroll
         for (int i = 0; i < RS_IPT; i++) {
             const u32 p = (u32)i * RS_THREADS + tid;
@@ -519,7 +553,7 @@ __global__ __launch_bounds__(RS_THREADS, 4) void k_bucket_scatter(const u64 *kin
 #pragma unroll
         for (int i = 0; i < RS_IPT; i++) {
             const u32 p = (u32)i * RS_THREADS + tid;
-            if (!(p < nvalid && sl[i] < bcap)) sl[i] = 0xffffffffu;
+            if (!(p < n_kept && sl[i] < bcap)) sl[i] = 0xffffffffu;
             if (sl[i] != 0xffffffffu) {
                 const u64 k = ks_[i];
                 const u64 g = (u64)KS_BSLOT(dd[i], region, n_hi) * bcap + sl[i];
@@ -880,16 +914,20 @@ int ks_radix_sort_u64(ks_ctx *ctx, int tag, const u64 *keys_in, const u64 *vals_
 
 // One pass, no histogram: segmented postings (regions by the low digit) -> 2^pbits fixed-capacity buckets.
 int ks_bucket_scatter_u32(ks_ctx *ctx, const u64 *keys_in, const u32 *vals_in, const ks_rs_segments *seg, int shift,
-                          u32 pfxK, u64 *bkeys, u32 *bvals, u32 *bcur, u32 bcap, unsigned long long *status, u32 n_hi, int vfmt) {
+                          u32 pfxK, u64 *bkeys, u32 *bvals, u32 *bcur, u32 bcap, unsigned long long *status, u32 n_hi, int vfmt,
+                          const u32 *presence, u32 presK, u32 fix_s) {
     const u32 tiles_per_seg = (u32)((seg->cap + RS_TILE - 1) / RS_TILE);
     const u32 nblocks = seg->regions * tiles_per_seg;
     ks_timer_begin(ctx, "bucket_scatter");
-#define BKS_LAUNCH(V_) hipLaunchKernelGGL((k_bucket_scatter<V_>), dim3(nblocks), dim3(RS_THREADS), 0, ctx->stream, keys_in, vals_in, bkeys, bvals, \
-                                          shift, seg->len, seg->cap, tiles_per_seg, bcur, bcap, status, pfxK, n_hi, seg->sub_shift)
+#define BKS_LAUNCH_(V_, QF_) hipLaunchKernelGGL((k_bucket_scatter<V_, QF_>), dim3(nblocks), dim3(RS_THREADS), 0, ctx->stream, keys_in, vals_in, bkeys, \
+                                               bvals, shift, seg->len, seg->cap, tiles_per_seg, bcur, bcap, status, pfxK, n_hi, seg->sub_shift,   \
+                                               presence, presK, fix_s)
+#define BKS_LAUNCH(V_) do { if (presence) BKS_LAUNCH_(V_, true); else BKS_LAUNCH_(V_, false); } while (0)
     if (vfmt == 2) BKS_LAUNCH(2); // 16-bit values in, key byte + 8-bit values out (9-byte postings)
     else if (vfmt == 1) BKS_LAUNCH(1);
     else BKS_LAUNCH(0);
 #undef BKS_LAUNCH
+#undef BKS_LAUNCH_
     ks_timer_end(ctx);
     KS_HIP(ctx, hipGetLastError());
     return KS_OK;

@@ -52,6 +52,27 @@ __global__ __launch_bounds__(256) void k_index_finish(const u64 *keys, const u32
                                                       u32 pfxK, int fp_shift, u32 *fp, ks_post *post);
 __global__ __launch_bounds__(256) void k_index_bmeta(const u64 *keys, const u64 *dir, u32 n_buckets, int fp_shift, ks_bmeta *bmeta);
 
+// The presence bitmap of a fingerprint-layout index (ks_index::d_presence): the keys are sorted, so a posting whose predecessor
+// sets the same bit (the same hash in another target, mostly) leaves the atomic out.
+__global__ __launch_bounds__(256) void k_index_presence(const u64 *keys, u64 n, u32 presK, u32 *presence) {
+    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const u32 b = ks_join_prefix(keys[i], presK);
+    if (i > 0 && ks_join_prefix(keys[i - 1], presK) == b) return;
+    atomicOr(&presence[b >> 5], 1u << (b & 31u));
+}
+// Bits of the presence bitmap per index posting: 3 to 6 (the size is a power of two), i.e. 28 to 15 % of the bits set by the time
+// every posting has one — the headline index (295 M postings, 2^16 buckets of ~4.5k) gets 2^30 bits (128 MB), 2^14 per bucket, 24 % set.
+// Measured against 6 to 12 bits per posting (KS_DEBUG_QFILTER_OCC = 6: 2^31 bits, 13 % set): DESIGN.md §3.2.
+#define KS_QF_OCC 3
+static int presence_bits(const ks_ctx *ctx, u64 n_postings, int pbits) {
+    u64 occ = KS_QF_OCC;
+    if (const char *f = ks_dbg(ctx, KS_DBG_QFILTER_OCC)) { const long v = atol(f); if (v >= 1 && v <= 64) occ = (u64)v; } // (tuning aid)
+    int bits = pbits;
+    while (bits < 31 && (1ULL << bits) < occ * n_postings) bits++;
+    return bits;
+}
+
 #define JN_FP_PBITS 15 // indexes with this many join-prefix bits or more (> 50M postings) use the fingerprint layout (see the join)
 
 static int index_build_run(ks_ctx *ctx, const ks_sketches *t, ks_index *ix) {
@@ -135,6 +156,15 @@ static int index_build_run(ks_ctx *ctx, const ks_sketches *t, ks_index *ix) {
             if (n > 0)
                 KS_LAUNCH(ctx, "index_finish", k_index_finish, (u32)((n + 255) / 256), 256, (const u64 *)ix->d_keys, (const u32 *)ix->d_tids,
                           (const u32 *)ix->d_abunds, (const u64 *)ix->d_dir, n, ix->pbits, K, ix->fp_shift, ix->d_fp, ix->d_post);
+            // what the index can say about "absent", once: the query side's bucket scatter drops the postings it rules out
+            ix->pres_bits = presence_bits(ctx, n, ix->pbits);
+            ix->pres_K = ks_join_prefix_mul(ix->pres_bits, ks_max_hash(t->params.scaled));
+            const size_t pres_words = ix->pres_bits > 5 ? (size_t)1 << (ix->pres_bits - 5) : 1;
+            KS_TRY(ks_alloc(ctx, &ix->d_presence, pres_words));
+            KS_HIP(ctx, hipMemsetAsync(ix->d_presence, 0, pres_words * sizeof(u32), ctx->stream));
+            if (n > 0)
+                KS_LAUNCH(ctx, "index_presence", k_index_presence, (u32)((n + 255) / 256), 256, (const u64 *)ix->d_keys, n, ix->pres_K,
+                          ix->d_presence);
         }
     }
     KS_TRY(ks_scan_status_fetch(ctx));
@@ -1066,6 +1096,8 @@ struct se_search {
     int pbits, tbits, qbits, abits;
     u32 n_buckets, pfxK;
     bool pre, f10; // the sketch's postings are the partition's input (pre), in their 10-byte form (f10)
+    bool qf;       // the bucket scatter dropped the postings the index's presence bitmap rules out; qf_kept of them passed
+    u64 qf_kept;
     u64 *dir_q;
     // cursor block: segment s of the pair list counts at word s * JN_CUR_STRIDE; word 1 = "a query bucket overflowed"
     // (k_bucket_scatter) (+ the join buckets' fill counts right behind it, bcur: one allocation, one memset)
@@ -1133,8 +1165,14 @@ static int se_partition(ks_ctx *ctx, se_search &Q, int way, ks_scratch &sc, se_q
         KS_TRY(sc.alloc(&V->qk0, (size_t)n_buckets * bcap));
         KS_TRY(sc.alloc(&V->qv0, (size_t)n_buckets * bcap));
         ks_rs_segments seg{q->part_len, q->part_cap, q->part_regions << q->part_sub_shift, q->part_sub_shift};
+        // The presence filter: on while the previous search against such an index dropped at least half of its postings
+        // (ks_ctx::qfilter_pays).  Buckets keep their unfiltered capacity: how many postings survive is known on the device only.
+        // The dense partition below (way 1, after a bucket overflowed) stays unfiltered: the join confirms on the full key either way.
+        const char *qf_knob = ks_dbg(ctx, KS_DBG_QFILTER);
+        Q.qf = Q.ix->d_presence && (qf_knob ? atoi(qf_knob) != 0 : ctx->qfilter_pays);
         KS_TRY(ks_bucket_scatter_u32(ctx, q->part_keys, q->part_vals, &seg, 8, Q.pfxK, V->qk0, V->qv0, Q.bcur, bcap, Q.cursor, n_buckets >> 8,
-                                     V->q_fmt)); // (10-byte postings stay 10 bytes, or lose one more: the join decodes them)
+                                     V->q_fmt, // (10-byte postings stay 10 bytes, or lose one more: the join decodes them)
+                                     Q.qf ? Q.ix->d_presence : nullptr, Q.ix->pres_K, q_s ? q_s - 32u : 0u));
         V->bucket_posting_bytes = V->q_fmt == 2 ? 9 : (V->q_fmt == 1 ? 10 : 12);
         KS_LAUNCH(ctx, "bucket_dir", k_region_dir, (n_buckets + 255) / 256, 256, (const u32 *)Q.bcur, (u64)bcap, n_buckets, Q.dir_q,
                   Q.dir_q + n_buckets, n_buckets >> 8);
@@ -1200,7 +1238,10 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
         KS_TRY(sc.alloc(&Q.pk0, (size_t)(seg_cap * n_segs)));
         if (attempt > 0) // (attempt 0: cleared with the flag word above; the flag word survives)
             KS_HIP(ctx, hipMemset2DAsync(Q.cursor, (size_t)JN_CUR_STRIDE * sizeof(u64), 0, sizeof(u64), JN_SEGS, ctx->stream));
-        // (few query postings per bucket: the table kernel; KS_DEBUG_JOIN_SPARSE = 0 / 1 forces the choice in the tests)
+        // (few query postings per bucket: the table kernel; KS_DEBUG_JOIN_SPARSE = 0 / 1 forces the choice in the tests.  n_q is
+        // the count BEFORE the presence filter — an upper bound of what the buckets hold, the survivors are counted on the device
+        // only —, so a filtered batch takes the table kernel no sooner than an unfiltered one; both kernels return at once on an
+        // empty bucket and take buckets of any fill.)
         const bool sparse = ix->fp_layout && (ks_dbg(ctx, KS_DBG_JOIN_SPARSE) ? atoi(ks_dbg(ctx, KS_DBG_JOIN_SPARSE)) != 0
                                                                              : Q.n_q / n_buckets <= (u64)JS_QCAP * 3 / 4);
         if (sparse)
@@ -1243,7 +1284,8 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
             Q.n_pairs += Q.seg_count[s_];
             if (Q.seg_count[s_] > seg_max) seg_max = Q.seg_count[s_];
         }
-        *overflowed = way == 0 && pin[1] != 0;
+        *overflowed = way == 0 && (pin[1] & 1ULL) != 0;
+        Q.qf_kept = pin[1] >> KS_QF_KEPT;
         if (!*overflowed && Q.n_pairs >= KS_PAIR_LIMIT) { // saturated alphabets: the caller searches the queries in slices
             *split_pairs = Q.n_pairs;
             Q.stop = true;
@@ -1380,6 +1422,16 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, con
         sc.free(V.qk0); sc.free(V.qk1); sc.free(V.qv0); sc.free(V.qv1);
         if (!overflowed) {
             H->partition_path = V.partition_path;
+            if (way == 0 && Q.qf) { // (n_q is exact behind the join's wait)
+                const u64 dropped = Q.n_q > Q.qf_kept ? Q.n_q - Q.qf_kept : 0;
+                ctx->qfilter_seen += Q.n_q;
+                ctx->qfilter_dropped += dropped;
+                ctx->qfilter_pays = dropped >= Q.n_q / 2;
+            } else if (way == 0 && ix->d_presence && Q.n_pairs < Q.n_q / 4) {
+                // unfiltered: every matching posting makes at least one pair, so fewer than a quarter of them match, and the
+                // bitmap passes at most ~28 % of the rest (KS_QF_OCC): more than half would be dropped
+                ctx->qfilter_pays = true;
+            }
             break;
         }
         // a bucket overflowed (skewed hashes): drop the partial result and partition the dense way

@@ -286,6 +286,12 @@ class Context:
         self._check(st)
         return (Sketches(self, sk) if want_sketches else None), Hits(self, hits)
 
+    def qfilter_stats(self) -> Dict[str, int]:
+        """Query postings the filtered bucket scatters of this context read / dropped (see ks_ctx_qfilter_stats)."""
+        v = (C.c_uint64 * 2)()
+        self._check(self._L.ks_ctx_qfilter_stats(self._h, C.byref(v)))
+        return {"seen": int(v[0]), "dropped": int(v[1])}
+
     def fused_stats(self) -> Dict[str, int]:
         """ks_sketch_search_device calls on this context: with the sketch read-back deferred / repeated the plain way."""
         v = (C.c_uint64 * 2)()
