@@ -525,6 +525,60 @@ const uint32_t *ks_hits_device_src_row(const ks_hits *h);
 /* either destination may be NULL; KS_ERR_INVALID_ARG for hits that did not come from ks_hits_best */
 int ks_hits_copy_best_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t *rank, uint32_t *src_row);
 
+/* ---- clusters: the connected components of an all-vs-all hit list ---------------------------------------------------------- */
+
+/* What an all-vs-all search is run for: which sequences belong together (the `pairwise` + `cluster` step of the sourmash /
+ * branchwater tools).  The nodes are 0 .. n-1, the sequences of ONE set; `hits` comes from searching that set against an index
+ * of the same set, so qid and tid are both ids in it.  Any hit list in that id space is valid: the output of a thresholded
+ * search or of ks_hits_best too, where only one direction of a pair may survive.
+ *   row r = (q, t) is an undirected edge iff q != t and score(r) >= threshold
+ *   score: the KS_BEST_* keys of ks_hits_best, bit for bit (one device function computes both); |q| and |t| are the distinct
+ *          hash counts of nodes[q] and nodes[t].  A NaN score is never an edge; -0.0 equals +0.0; threshold -inf passes
+ *          every row that is not NaN.
+ *   `nodes` may be NULL for KS_BEST_INTERSECT and KS_BEST_SCORE: n then comes from opts->n_nodes.
+ * Clusters are the connected components; a node without an edge is a cluster of one.  An empty hit list gives n singletons.
+ * Result (device-resident, every value an integer):
+ *   label u32[n]                  the smallest node id of the node's cluster
+ *   cluster_id u32[n]             clusters numbered 0 .. n_clusters-1 by ascending smallest member
+ *   offsets u64[n_clusters + 1], members u32[n]    the CSR of the clusters in that order, members ascending inside a cluster
+ *   representative u32[n_clusters]   with `nodes` the member with the most distinct hashes, ties to the smaller id; without,
+ *                                 the smallest member
+ *   n_edges: the rows that passed the threshold, self rows and both directions counted as they occur.
+ * The result never depends on the internal path (wave-uniform or lane-per-row hooking), the launch geometry or the order in
+ * which waves ran: the union-find links by node id alone and everything after it is integer counting and sorting
+ * (KS_DEBUG_CLUSTER_PATH = 1 / 2 force the lane-per-row / the wave-uniform hooking for the tests; unset: lane per row).  The
+ * input is unchanged and stays valid.
+ * KS_ERR_INVALID_ARG (options first, before any device work, also with ctx == NULL): an unknown similarity; non-zero flags /
+ * reserved; a NaN threshold; d_score NULL with KS_BEST_SCORE or non-NULL without it; `nodes` NULL where the key needs sizes;
+ * n_nodes that is neither 0 nor the node set's sequence count; then: a qid or tid >= n; a size of 0 on a row whose key needs
+ * it (ks_last_error names the first such row).  One stream, one wait (the scalars come back with it); scratch comes from the
+ * pool: 36 bytes per node, none per row. */
+typedef struct ks_clusters ks_clusters;
+typedef struct ks_cluster_opts {
+    uint32_t similarity; /* KS_BEST_INTERSECT | _TARGET_CONTAINMENT | _MAX_CONTAINMENT | _JACCARD | _SCORE: the same scores, bit for bit, as ks_hits_best */
+    uint32_t n_nodes;    /* used only when nodes == NULL; with nodes != NULL it must be 0 or ks_sketches_n_seqs(nodes) */
+    double   threshold;  /* a row is an edge iff score >= threshold (NaN scores never are); NaN threshold: KS_ERR_INVALID_ARG */
+    uint32_t flags;      /* 0 */
+    uint32_t reserved;   /* 0 */
+} ks_cluster_opts;
+int ks_hits_cluster(ks_ctx *ctx, const ks_hits *hits, const ks_sketches *nodes, const double *d_score,
+                    const ks_cluster_opts *opts, ks_clusters **out);
+uint32_t ks_clusters_n_nodes(const ks_clusters *c);
+uint32_t ks_clusters_n_clusters(const ks_clusters *c);
+uint64_t ks_clusters_n_edges(const ks_clusters *c);
+/* members of the biggest cluster */
+uint32_t ks_clusters_largest(const ks_clusters *c);
+/* device pointers, valid until ks_clusters_free */
+const uint32_t *ks_clusters_device_label(const ks_clusters *c);
+const uint32_t *ks_clusters_device_cluster_id(const ks_clusters *c);
+const uint64_t *ks_clusters_device_offsets(const ks_clusters *c);
+const uint32_t *ks_clusters_device_members(const ks_clusters *c);
+const uint32_t *ks_clusters_device_representative(const ks_clusters *c);
+/* any destination may be NULL */
+int ks_clusters_copy_to_host(ks_ctx *ctx, const ks_clusters *c, uint32_t *label, uint32_t *cluster_id, uint64_t *offsets,
+                             uint32_t *members, uint32_t *representative);
+void ks_clusters_free(ks_clusters *c);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Per-kernel HIP-event timing on ctx's stream.  enable: 0 off; 1 events bracket every launch (~20 us of idle queue

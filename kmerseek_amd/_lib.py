@@ -63,6 +63,11 @@ class ks_best_opts(C.Structure):
     _fields_ = [("rank_by", C.c_uint32), ("k", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class ks_cluster_opts(C.Structure):
+    _fields_ = [("similarity", C.c_uint32), ("n_nodes", C.c_uint32), ("threshold", C.c_double), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class ks_kernel_time(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -191,6 +196,18 @@ SIGNATURES = {
     "ks_hits_device_rank": (_vp, [_vp]),
     "ks_hits_device_src_row": (_vp, [_vp]),
     "ks_hits_copy_best_to_host": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ks_hits_cluster": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ks_cluster_opts), _pp]),
+    "ks_clusters_n_nodes": (C.c_uint32, [_vp]),
+    "ks_clusters_n_clusters": (C.c_uint32, [_vp]),
+    "ks_clusters_n_edges": (C.c_uint64, [_vp]),
+    "ks_clusters_largest": (C.c_uint32, [_vp]),
+    "ks_clusters_device_label": (_vp, [_vp]),
+    "ks_clusters_device_cluster_id": (_vp, [_vp]),
+    "ks_clusters_device_offsets": (_vp, [_vp]),
+    "ks_clusters_device_members": (_vp, [_vp]),
+    "ks_clusters_device_representative": (_vp, [_vp]),
+    "ks_clusters_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ks_clusters_free": (None, [_vp]),
     "ks_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ks_timing_reset": (C.c_int, [_vp]),
     "ks_timing_get": (C.c_int, [_vp, C.POINTER(ks_kernel_time), C.c_uint32, _u32p]),

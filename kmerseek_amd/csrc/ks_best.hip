@@ -15,7 +15,7 @@
 // Every comparison is on (u64 key, row index): integers.  No f64 atomics, no reductions of scores: a row's rank and whether it
 // is kept do not depend on the path its segment took (KS_DEBUG_BEST_PATH = 1 every segment by a wave, 2 by a workgroup,
 // 3 by a workgroup with a chunk of BH_CHUNK_SMALL rows — the tests reach the streamed case with a few hundred rows).
-#include "ks_device.h"
+#include "ks_score.h" // bh_set, bh_size, bh_row_score: the scores, shared with ks_cluster.hip
 
 #define BH_WAVE_MAX 64     // rows of a segment one wave holds in registers: the longest segment of the wave path
 #define BH_CHUNK 1024      // keys of the workgroup path's LDS chunk (8 KB)
@@ -24,14 +24,6 @@
 #define BH_WG_GRID 2048    // workgroups of k_best_wg (striding likewise)
 #define BH_NONE 0xffffffffu // rank of a row that is not kept
 enum { BH_BAD_ID = 0, BH_BAD_SIZE = 1, BH_KEPT = 2 }; // words of the control block
-
-// the distinct-hash counts of a sketch set: cnt of a gapped set, else the CSR run; off == NULL: no set
-struct bh_set {
-    const u64 *off;
-    const u32 *cnt;
-    u32 n;
-};
-KS_DEV u64 bh_size(const bh_set &S, u32 i) { return S.cnt ? (u64)S.cnt[i] : S.off[i + 1] - S.off[i]; }
 
 // a u64 that orders as the contract orders scores: NaN (every NaN) lowest, then -inf ... -0.0 = +0.0 ... +inf
 KS_DEV u64 bh_sortable(double s) {
@@ -60,21 +52,13 @@ __global__ __launch_bounds__(256) void k_best_keys(bh_in R, int mode, u32 seg_ca
 #pragma clang fp contract(off)
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R.n_rows) return;
-    const u32 q = R.qid[r], t = R.tid[r], is = R.isect[r];
+    const u32 q = R.qid[r], t = R.tid[r];
     u64 kx = 0;
     if ((R.q.off && q >= R.q.n) || (R.t.off && t >= R.t.n)) atomicMin(&bad[BH_BAD_ID], (unsigned long long)r);
     else {
-        double s;
-        if (R.rank_by == KS_BEST_INTERSECT) s = (double)is;
-        else if (R.rank_by == KS_BEST_SCORE) s = R.score[r];
-        else {
-            const u64 nt = bh_size(R.t, t), nq = R.rank_by == KS_BEST_TARGET_CONTAINMENT ? 1ULL : bh_size(R.q, q);
-            u64 den = nt;
-            if (R.rank_by == KS_BEST_MAX_CONTAINMENT) den = nq < nt ? nq : nt;
-            else if (R.rank_by == KS_BEST_JACCARD) den = nq + nt - (u64)is;
-            if (nq == 0 || nt == 0) { atomicMin(&bad[BH_BAD_SIZE], (unsigned long long)r); den = 1; }
-            s = (double)is / (double)den;
-        }
+        bool bad_size;
+        const double s = bh_row_score(R.rank_by, r, q, t, R.isect[r], R.q, R.t, R.score, &bad_size);
+        if (bad_size) atomicMin(&bad[BH_BAD_SIZE], (unsigned long long)r);
         kx = bh_sortable(s);
     }
     key[r] = kx;
@@ -212,11 +196,6 @@ __global__ __launch_bounds__(256) void k_best_move(rf_cols in, u32 n_rows, const
     o_src[o] = r;
 }
 
-static bh_set best_set(const ks_sketches *s) {
-    if (!s) return bh_set{nullptr, nullptr, 0};
-    return bh_set{s->d_offsets, s->gapped ? s->d_counts : nullptr, s->n_seqs};
-}
-
 static int best_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *Q, const ks_sketches *T, const double *d_score, const ks_best_opts *o,
                     ks_hits *B) {
     const u64 n64 = H->n_hits;
@@ -252,7 +231,7 @@ static int best_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *Q, const k
     KS_HIP(ctx, hipMemsetAsync(wave_segs, 0, sizeof(u32), ctx->stream));
     KS_HIP(ctx, hipMemsetAsync(wg_segs, 0, sizeof(u32), ctx->stream));
 
-    const bh_in R = {H->d_qid, H->d_tid, H->d_isect, d_score, n, o->rank_by, o->k, best_set(Q), best_set(T)};
+    const bh_in R = {H->d_qid, H->d_tid, H->d_isect, d_score, n, o->rank_by, o->k, bh_set_of(Q), bh_set_of(T)};
     const u32 g = (n + 255) / 256;
     KS_LAUNCH(ctx, "best_keys", k_best_keys, g, 256, R, mode, seg_cap, key, flags, rank, wave_segs, wg_segs, (unsigned long long *)ctl);
     if (mode != 2)

@@ -46,7 +46,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -305,13 +305,14 @@ enum : u32 {
     KS_PIN_SIGNIF = 200,     // 3 words, significance: first row with an id out of range | first row with another shared count | corpus flag
     KS_PIN_BEST = 203,       // 3 words, best hits: first row with an id out of range | first row with an empty sketch | kept rows
     KS_PIN_REGIONS = 206,    // u32: match regions kept (ks_regions.hip)
-    KS_PIN_END = 207,
+    KS_PIN_CLUSTER = 207,    // 5 words, clusters: first row with an id out of range | first row with an empty sketch | edges | clusters | largest
+    KS_PIN_END = 212,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -401,6 +402,15 @@ struct ks_regions {
     u32 n_slices;
     u64 *d_row_offsets;                                 // n_rows + 1
     u32 *d_qstart, *d_tstart, *d_length, *d_nkmers, *d_covered; // n_regions
+};
+
+// connected components of a hit list read as a graph (ks_cluster.hip)
+struct ks_clusters {
+    ks_ctx *ctx;
+    u32 n_nodes, n_clusters, largest;
+    u64 n_edges;
+    u32 *d_label, *d_cluster_id, *d_members, *d_rep; // n_nodes each (d_rep: the first n_clusters are meaningful)
+    u64 *d_offsets;                                  // n_nodes + 1 (entries past n_clusters repeat n_nodes)
 };
 
 // ---- passes whose sort key is `hit row | fields of the pair` (ks_matchpos.hip, ks_regions.hip) ----

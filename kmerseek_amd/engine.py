@@ -428,6 +428,28 @@ class Context:
                                          None if targets is None else targets._h, d_score, C.byref(opts), C.byref(out)))
         return Hits(self, out)
 
+    def cluster(self, hits: "Hits", similarity: Optional[str] = None, threshold: float = 0.0, nodes: Optional["Sketches"] = None,
+                score=None, n_nodes: int = 0) -> "Clusters":
+        """ks_hits_cluster: the connected components of an all-vs-all hit list.  `hits` comes from searching one set against
+        itself (any list in that id space: thresholded or best-hits output too); row (q, t) is an edge iff q != t and its
+        score >= threshold.  similarity: the key names of best_hits — intersect | target_containment | max_containment |
+        jaccard (these three need `nodes`, the sketch set) | score (`score`: a device column of hits.count f64, a raw pointer
+        or an object with data_ptr()).  similarity left at None is jaccard, or score when a `score` column is given; an explicit
+        key with a column it does not read is refused by the library.  Without `nodes` the node count comes from n_nodes.
+        NaN scores never link."""
+        if similarity is None:
+            similarity = "jaccard" if score is None else "score"
+        if similarity not in BEST_RANK_BY:
+            raise ValueError(f"similarity must be one of {', '.join(BEST_RANK_BY)}, not {similarity!r}")
+        if not 0 <= int(n_nodes) < 2 ** 32:
+            raise ValueError(f"n_nodes = {n_nodes} does not fit 32 bits")
+        d_score = None if score is None else C.c_void_p(int(score.data_ptr()) if hasattr(score, "data_ptr") else int(score))
+        opts = _lib.ks_cluster_opts(BEST_RANK_BY[similarity], int(n_nodes), float(threshold), 0, 0)
+        out = C.c_void_p()
+        self._check(self._L.ks_hits_cluster(self._h, hits._h, None if nodes is None else nodes._h, d_score, C.byref(opts),
+                                            C.byref(out)))
+        return Clusters(self, out)
+
     # ---- index / search ----
     def index_build(self, targets: "Sketches") -> "Index":
         out = C.c_void_p()
@@ -692,6 +714,45 @@ class Regions(_Owned):
         cols = [np.zeros(self.n_regions, np.uint32) for _ in range(5)]
         self._ctx._check(self._ctx._L.ks_regions_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
         return (offs, *cols)
+
+
+class Clusters(_Owned):
+    """Device-resident connected components of a hit list (ks_clusters): per node its label (the smallest id of its cluster)
+    and cluster_id, the clusters as a CSR (offsets, members) ordered by smallest member, and a representative per cluster."""
+    _free = "ks_clusters_free"
+    _COLUMNS = ("label", "cluster_id", "offsets", "members", "representative")
+
+    @property
+    def n_nodes(self) -> int:
+        return int(self._ctx._L.ks_clusters_n_nodes(self._h))
+
+    @property
+    def n_clusters(self) -> int:
+        return int(self._ctx._L.ks_clusters_n_clusters(self._h))
+
+    @property
+    def n_edges(self) -> int:
+        """Rows that passed the threshold: self rows and both directions counted as they occur."""
+        return int(self._ctx._L.ks_clusters_n_edges(self._h))
+
+    @property
+    def largest(self) -> int:
+        return int(self._ctx._L.ks_clusters_largest(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (label / cluster_id u32[n_nodes], offsets u64[n_clusters + 1], members u32[n_nodes],
+        representative u32[n_clusters])."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_clusters_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """(label, cluster_id u32[n_nodes], offsets u64[n_clusters + 1], members u32[n_nodes], representative u32[n_clusters])."""
+        n, nc = self.n_nodes, self.n_clusters
+        label, cid, members = (np.zeros(n, np.uint32) for _ in range(3))
+        offs, rep = np.zeros(nc + 1, np.uint64), np.zeros(nc, np.uint32)
+        self._ctx._check(self._ctx._L.ks_clusters_copy_to_host(self._ctx._h, self._h, _ptr(label), _ptr(cid), _ptr(offs), _ptr(members),
+                                                               _ptr(rep)))
+        return label, cid, offs, members, rep
 
 
 class Corpus(_Owned):

@@ -8,6 +8,8 @@
 * ``do_multisearch()`` — drop-in for src/python/kmerseek/search.py:144-158 (branchwater ``do_multisearch`` with threshold 0, no
                         ANI, probability of overlap on, output_all off): the 16-column CSV of the reference's fixture
                         tests/testdata/index/ced9-bcl2-first25.hp.k16.manysearch.csv.
+* ``do_cluster()``    — all-vs-all search of one .sig.zip, then the connected components at a similarity threshold: a CSV of
+                        clusters in this project's own format (modelled on branchwater ``cluster``; no parity claimed).
 Hashing, sorting, joining and counting all run in the HIP library; this module only formats.  The ratio columns are
 f64 arithmetic on the integer results (formulas: SURVEY.md §8(a) row a10).
 """
@@ -325,7 +327,72 @@ def do_multisearch(query_sig: str, target_sig: str, output: str, ksize: int, sca
 
 
 # ---------------------------------------------------------------------------------------------------------
-# k-mer tables and alignment stitching  — src/python/kmerseek/sig2kmer.py:186-219, search.py:37-121,195-276
+# do_cluster()  — all-vs-all, then the connected components of the similarity graph
+# ---------------------------------------------------------------------------------------------------------
+CLUSTER_COLUMNS = ["cluster", "representative", "size", "nodes"]
+
+
+def cluster_rows(names: Sequence[str], offsets, members, representative) -> List[Tuple[str, str, int, str]]:
+    """One row per cluster of a Clusters.to_host() CSR, in its order: (Component_<i>, name of the representative, size, the
+    members' names joined by ';' in ascending id order)."""
+    offsets = np.asarray(offsets).astype(np.int64).tolist()
+    members = np.asarray(members).tolist()
+    rows = []
+    for i, rep in enumerate(np.asarray(representative).tolist()):
+        ids = members[offsets[i]:offsets[i + 1]]
+        rows.append((f"Component_{i}", names[rep], len(ids), ";".join(names[j] for j in ids)))
+    return rows
+
+
+def cluster_size_histogram(offsets) -> List[Tuple[int, int]]:
+    """[(cluster_size, count)] ascending by size, over every cluster of the CSR."""
+    sizes, counts = np.unique(np.diff(np.asarray(offsets).astype(np.int64)), return_counts=True)
+    return list(zip(sizes.tolist(), counts.tolist()))
+
+
+def do_cluster(sig: str, output: str, ksize: int, scaled: int, moltype: str, similarity: str = "jaccard", threshold: float = 0.0,
+               sizes_output: Optional[str] = None, min_size: int = 1, ctx: Optional[Context] = None) -> int:
+    """Cluster the sketches of one .sig.zip: the set is searched against an index of itself and the hit list becomes a graph
+    (Context.cluster: a pair is joined iff its `similarity` — intersect | target_containment | max_containment | jaccard —
+    is >= threshold); the clusters are its connected components.  Writes a CSV with the columns cluster, representative,
+    size, nodes: one row per cluster of at least min_size members, clusters named Component_<i> by ascending first member,
+    `nodes` the member names joined by ';'.  sizes_output: a second CSV, cluster_size,count, over every cluster.
+    The format is this project's own, modelled on the output of branchwater's `cluster`; no parity with that tool is
+    claimed.  Returns the number of cluster rows written."""
+    own = ctx is None
+    ctx = ctx or Context(0)
+    try:
+        names, so, sm, sa, sk, ss, smol = read_sig_zip(sig)
+        if (sk, ss, smol) != (ksize, scaled, moltype):
+            raise ValueError(f"sketch parameters {(sk, ss, smol)} do not match the requested {(ksize, scaled, moltype)}")
+        made = []
+        try:
+            S = ctx.sketches_from_host(so, sm, sa, ksize, scaled, moltype); made.append(S)
+            ix = ctx.index_build(S); made.append(ix)
+            hits = ctx.search(ix, S); made.append(hits)
+            cl = ctx.cluster(hits, similarity, threshold, nodes=S); made.append(cl)
+            _, _, offsets, members, rep = cl.to_host()
+        finally:
+            for o in reversed(made):
+                o.free()
+        rows = [r for r in cluster_rows(names, offsets, members, rep) if r[2] >= min_size]
+        with open(output, "w", newline="") as f:
+            w = csv.writer(f, lineterminator="\n")
+            w.writerow(CLUSTER_COLUMNS)
+            w.writerows(rows)
+        if sizes_output:
+            with open(sizes_output, "w", newline="") as f:
+                w = csv.writer(f, lineterminator="\n")
+                w.writerow(["cluster_size", "count"])
+                w.writerows(cluster_size_histogram(offsets))
+        return len(rows)
+    finally:
+        if own:
+            ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# k-mer tables and alignment stitching — src/python/kmerseek/sig2kmer.py:186-219, search.py:37-121,195-276
 # ---------------------------------------------------------------------------------------------------------
 _DAYHOFF = {**{c: "a" for c in "C"}, **{c: "b" for c in "AGPST"}, **{c: "c" for c in "DENQ"}, **{c: "d" for c in "HKR"},
             **{c: "e" for c in "ILMV"}, **{c: "f" for c in "FWY"}}
