@@ -525,6 +525,50 @@ const uint32_t *ks_hits_device_src_row(const ks_hits *h);
 /* either destination may be NULL; KS_ERR_INVALID_ARG for hits that did not come from ks_hits_best */
 int ks_hits_copy_best_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t *rank, uint32_t *src_row);
 
+/* ---- gather: the greedy non-redundant targets of every query ----------------------------------------------------------------- */
+
+/* Per query the shortest greedy list of targets that together explain its hashes (the `gather` / `fastmultigather` step of the
+ * sourmash / branchwater tools): every target is credited only with the hashes no earlier target covered.  `hits` comes from
+ * any search of `queries` against an index of `targets`; thresholded and ks_hits_best lists are valid (a missing row simply is
+ * not a candidate).  For every query q with at least one row, in integers only:
+ *   R_0 = the distinct hashes of q.  Round i = 0, 1, ...: for every row r of q not yet picked, c_i(r) = |R_i and hashes(tid(r))|;
+ *   r* = the row with the largest c_i, ties to the smaller tid (the earlier row).  The query stops when
+ *   c_i(r*) < max(min_unique, 1), or i == max_results != 0, or no row is left.  Otherwise r* is kept with
+ *     rank = i, unique_intersect = c_i(r*), unique_weighted = the sum of q's abundances over R_i and hashes(t*) (u64, no
+ *     saturation), R_(i+1) = R_i without hashes(t*), remaining = |R_(i+1)|.
+ * *out: a new ks_hits, built as ks_hits_best builds one: the kept rows STILL ordered by (qid, tid) (a valid input of
+ * ks_match_positions, ks_hits_significance and ks_hits_best), the four row columns, the two statistics columns if the input has
+ * them, `rank` and `src_row` (the accessors of ks_hits_best and ks_hits_copy_best_to_host work on it) and the three gather
+ * columns.  n_pair_instances, partition_path and bucket_posting_bytes are copied; the input is unchanged and stays valid.  An
+ * empty hit list gives a valid empty result.  Passes that copy rows (ks_hits_best, the containment threshold) do NOT carry the
+ * three gather columns: their output has src_row, through which a caller gathers them.
+ * The result never depends on the internal path, the launch geometry or the order in which waves ran: every comparison is on
+ * the integer key (count << 32) | ~row, the weighted sum is an integer sum.  (KS_DEBUG_GATHER_PATH = 1 / 2 / 3 force every
+ * query onto the wave path / the workgroup path / the workgroup path with its live bitmap in global memory, for the tests.)
+ * KS_ERR_INVALID_ARG, options first (before any device work, also with ctx == NULL): non-zero flags / reserved; then NULL
+ * arguments, inputs of another context, sets of different ks_params; then, found on the device: a qid or tid beyond its set,
+ * and a row whose round-0 count is not its `intersect` — hits and sketches do not belong together (ks_last_error names the
+ * first such row).  2^32 - 2 or more rows: KS_ERR_CAPACITY.
+ * One stream, one wait (the kept count and the bad-row words come back with it), synchronous on return.  Scratch from the pool:
+ * 56 bytes per hit row (+ 16 per query for the segment lists), 4 bytes per shared hash — sized by the list's
+ * n_pair_instances, the sum of a search's intersect column — and 1 bit per query hash. */
+typedef struct ks_gather_opts {
+    uint32_t min_unique;   /* stop a query when the best remaining target would add fewer new hashes; 0 = 1 */
+    uint32_t max_results;  /* rows kept per query at most; 0 = no limit */
+    uint32_t flags;        /* 0 */
+    uint32_t reserved;     /* 0 */
+} ks_gather_opts;
+/* opts == NULL: the defaults */
+int ks_hits_gather(ks_ctx *ctx, const ks_hits *hits, const ks_sketches *queries, const ks_sketches *targets,
+                   const ks_gather_opts *opts, ks_hits **out);
+/* device columns (ks_hits_count entries, valid until ks_hits_free); NULL unless h came from ks_hits_gather */
+const uint32_t *ks_hits_device_unique_intersect(const ks_hits *h);
+const uint32_t *ks_hits_device_remaining(const ks_hits *h);
+const uint64_t *ks_hits_device_unique_weighted(const ks_hits *h);
+/* any destination may be NULL; KS_ERR_INVALID_ARG for hits that did not come from ks_hits_gather */
+int ks_hits_copy_gather_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t *unique_intersect, uint32_t *remaining,
+                                uint64_t *unique_weighted);
+
 /* ---- clusters: the connected components of an all-vs-all hit list ---------------------------------------------------------- */
 
 /* What an all-vs-all search is run for: which sequences belong together (the `pairwise` + `cluster` step of the sourmash /

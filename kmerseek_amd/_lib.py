@@ -68,6 +68,10 @@ class ks_cluster_opts(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+class ks_gather_opts(C.Structure):
+    _fields_ = [("min_unique", C.c_uint32), ("max_results", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
+
+
 class ks_kernel_time(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -196,6 +200,11 @@ SIGNATURES = {
     "ks_hits_device_rank": (_vp, [_vp]),
     "ks_hits_device_src_row": (_vp, [_vp]),
     "ks_hits_copy_best_to_host": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ks_hits_gather": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ks_gather_opts), _pp]),
+    "ks_hits_device_unique_intersect": (_vp, [_vp]),
+    "ks_hits_device_remaining": (_vp, [_vp]),
+    "ks_hits_device_unique_weighted": (_vp, [_vp]),
+    "ks_hits_copy_gather_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp]),
     "ks_hits_cluster": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ks_cluster_opts), _pp]),
     "ks_clusters_n_nodes": (C.c_uint32, [_vp]),
     "ks_clusters_n_clusters": (C.c_uint32, [_vp]),

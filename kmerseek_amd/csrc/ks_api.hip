@@ -622,5 +622,8 @@ extern "C" void ks_hits_free(ks_hits *h) {
     ks_pool_free(h->ctx, h->d_ss);
     ks_pool_free(h->ctx, h->d_rank);
     ks_pool_free(h->ctx, h->d_src_row);
+    ks_pool_free(h->ctx, h->d_ga_unique);
+    ks_pool_free(h->ctx, h->d_ga_remaining);
+    ks_pool_free(h->ctx, h->d_ga_weighted);
     delete h;
 }

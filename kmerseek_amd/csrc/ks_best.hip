@@ -22,7 +22,7 @@
 #define BH_CHUNK_SMALL 64  // ... under KS_DEBUG_BEST_PATH = 3
 #define BH_WAVE_GRID 1024  // workgroups of k_best_wave (4 waves each, striding over the listed segments)
 #define BH_WG_GRID 2048    // workgroups of k_best_wg (striding likewise)
-#define BH_NONE 0xffffffffu // rank of a row that is not kept
+#define BH_NONE KS_RANK_NONE // rank of a row that is not kept
 enum { BH_BAD_ID = 0, BH_BAD_SIZE = 1, BH_KEPT = 2 }; // words of the control block
 
 // a u64 that orders as the contract orders scores: NaN (every NaN) lowest, then -inf ... -0.0 = +0.0 ... +inf
@@ -184,9 +184,10 @@ __global__ __launch_bounds__(256) void k_best_wg(const u64 *key, const u32 *segs
     }
 }
 
-// the kept rows to their places: all columns, the rank and the row's index in the input
+// the kept rows to their places: all columns, the rank and the row's index in the input (+ the gather columns: ks_hits_gather)
 __global__ __launch_bounds__(256) void k_best_move(rf_cols in, u32 n_rows, const u32 *dst, const u32 *rank, u32 cap, u32 *qid, u32 *tid, u32 *isect,
-                                                   u64 *nw, u64 *median2, double *ss, u32 *o_rank, u32 *o_src) {
+                                                   u64 *nw, u64 *median2, double *ss, u32 *o_rank, u32 *o_src, ks_gather_cols ga, u32 *o_unique,
+                                                   u32 *o_remaining, u64 *o_weighted) {
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rows) return;
     const u32 rk = rank[r], o = dst[r];
@@ -194,6 +195,16 @@ __global__ __launch_bounds__(256) void k_best_move(rf_cols in, u32 n_rows, const
     rf_move(in, r, o, qid, tid, isect, nw, median2, ss);
     o_rank[o] = rk;
     o_src[o] = r;
+    if (ga.unique) { o_unique[o] = ga.unique[r]; o_remaining[o] = ga.remaining[r]; o_weighted[o] = ga.weighted[r]; }
+}
+
+int ks_hits_move_ranked(ks_ctx *ctx, const ks_hits *H, u32 n_rows, const u32 *dst, const u32 *rank, u32 cap, ks_hits *B,
+                        const ks_gather_cols *ga) {
+    const rf_cols in{H->d_qid, H->d_tid, H->d_isect, H->d_nw, H->has_stats ? H->d_median2 : nullptr, H->has_stats ? H->d_ss : nullptr};
+    KS_LAUNCH(ctx, "best_move", k_best_move, (n_rows + 255) / 256, 256, in, n_rows, dst, rank, cap, B->d_qid, B->d_tid, B->d_isect, B->d_nw,
+              B->d_median2, B->d_ss, B->d_rank, B->d_src_row, ga ? *ga : ks_gather_cols{nullptr, nullptr, nullptr}, B->d_ga_unique,
+              B->d_ga_remaining, B->d_ga_weighted);
+    return KS_OK;
 }
 
 static int best_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *Q, const ks_sketches *T, const double *d_score, const ks_best_opts *o,
@@ -239,9 +250,7 @@ static int best_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *Q, const k
     if (mode != 1)
         KS_LAUNCH(ctx, "best_wg", k_best_wg, BH_WG_GRID, 256, (const u64 *)key, (const u32 *)wg_segs, seg_cap, o->k, chunk, flags, rank, kept_rows);
     KS_TRY(ks_scan_u32_inplace(ctx, flags, n, (u32 *)(ctl + BH_KEPT)));
-    const rf_cols in{H->d_qid, H->d_tid, H->d_isect, H->d_nw, H->has_stats ? H->d_median2 : nullptr, H->has_stats ? H->d_ss : nullptr};
-    KS_LAUNCH(ctx, "best_move", k_best_move, g, 256, in, n, (const u32 *)flags, (const u32 *)rank, (u32)cap, B->d_qid, B->d_tid, B->d_isect, B->d_nw,
-              B->d_median2, B->d_ss, B->d_rank, B->d_src_row);
+    KS_TRY(ks_hits_move_ranked(ctx, H, n, flags, rank, (u32)cap, B, nullptr));
     u64 *const rb = ctx->h_pin + KS_PIN_BEST;
     {
         ks_fetch_seg f[2];

@@ -46,7 +46,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -306,13 +306,14 @@ enum : u32 {
     KS_PIN_BEST = 203,       // 3 words, best hits: first row with an id out of range | first row with an empty sketch | kept rows
     KS_PIN_REGIONS = 206,    // u32: match regions kept (ks_regions.hip)
     KS_PIN_CLUSTER = 207,    // 5 words, clusters: first row with an id out of range | first row with an empty sketch | edges | clusters | largest
-    KS_PIN_END = 212,
+    KS_PIN_GATHER = 212,     // 4 words, gather: first row with an id out of range | first row with another shared count | first row past the incidence array | kept rows
+    KS_PIN_END = 216,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -372,6 +373,10 @@ struct ks_hits {
     double *d_ss;
     // ks_hits_best: per kept row its rank inside its query and its row in the input list; NULL for every other hit list
     u32 *d_rank, *d_src_row;
+    // ks_hits_gather: per kept row the hashes it newly covered, the query's hashes still uncovered after it, and the query's
+    // abundances over the newly covered ones; NULL for every other hit list
+    u32 *d_ga_unique, *d_ga_remaining;
+    u64 *d_ga_weighted;
 };
 
 struct ks_kmerpos {
@@ -439,6 +444,14 @@ int ks_row_slices_plan(ks_ctx *ctx, int dbg_id, const char *what, int low_bits, 
 // the sort of n keys in ka on their nbits live bits (ks_sort_pairs_msd, LSD passes for short lists); kb: scratch of the
 // same size; *sorted = where they ended up (ka or kb)
 int ks_sort_live_keys(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int nbits, u64 **sorted);
+
+// ---- the kept rows of a ranked pass to their places (ks_best.hip; ks_hits_best and ks_hits_gather) ----
+// Row r of H with rank[r] != KS_RANK_NONE goes to row dst[r] (< cap) of B: all columns of H that B holds, the rank and r itself
+// (src_row).  ga != NULL: the three per-row gather columns go with it, into B's.
+#define KS_RANK_NONE 0xffffffffu
+struct ks_gather_cols { const u32 *unique, *remaining; const u64 *weighted; };
+int ks_hits_move_ranked(ks_ctx *ctx, const ks_hits *H, u32 n_rows, const u32 *dst, const u32 *rank, u32 cap, ks_hits *B,
+                        const ks_gather_cols *ga);
 
 // ---- device-wide primitives (ks_scan.hip, ks_sort.hip) ----
 // exclusive scan of n u32 values into u64 (out[n] = total is also written: out has n+1 entries)

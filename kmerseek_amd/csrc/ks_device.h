@@ -153,6 +153,25 @@ KS_DEV u64 ks_wave_sum64(u64 v) {
 #undef KS_SUM64_STEP
     return ((u64)(u32)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (u32)__builtin_amdgcn_readlane((int)lo, 63);
 }
+// Largest of a 64-bit value over the 64 lanes of a wave (uniform result), the same DPP moves: a lane without a source compares
+// with 0.  The argmax of ks_hits_gather: its keys are (count << 32) | ~row.
+KS_DEV u64 ks_wave_max64(u64 v) {
+    u32 lo = (u32)v, hi = (u32)(v >> 32);
+#define KS_MAX64_STEP(CTRL, RMASK, BC) do { \
+        const u32 ol_ = (u32)__builtin_amdgcn_update_dpp(0, (int)lo, CTRL, RMASK, 0xf, BC); \
+        const u32 oh_ = (u32)__builtin_amdgcn_update_dpp(0, (int)hi, CTRL, RMASK, 0xf, BC); \
+        const u64 m_ = ((u64)hi << 32) | lo, o_ = ((u64)oh_ << 32) | ol_; \
+        const u64 s_ = o_ > m_ ? o_ : m_; \
+        lo = (u32)s_; hi = (u32)(s_ >> 32); } while (0)
+    KS_MAX64_STEP(0x111, 0xf, true);  // row_shr:1
+    KS_MAX64_STEP(0x112, 0xf, true);  // row_shr:2
+    KS_MAX64_STEP(0x114, 0xf, true);  // row_shr:4
+    KS_MAX64_STEP(0x118, 0xf, true);  // row_shr:8
+    KS_MAX64_STEP(0x142, 0xa, false); // row_bcast:15 into rows 1 and 3
+    KS_MAX64_STEP(0x143, 0xc, false); // row_bcast:31 into rows 2 and 3
+#undef KS_MAX64_STEP
+    return ((u64)(u32)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (u32)__builtin_amdgcn_readlane((int)lo, 63);
+}
 // value of the lane below (lane 0: 0)
 KS_DEV u32 ks_lane_below(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); } // wave_shr:1
 // largest value over the 64 lanes of a wave (every lane gets it)

@@ -450,6 +450,21 @@ class Context:
                                             C.byref(out)))
         return Clusters(self, out)
 
+    def gather(self, hits: "Hits", queries: "Sketches", targets: "Sketches", min_unique: int = 1, max_results: int = 0) -> "Hits":
+        """ks_hits_gather: per query the greedy non-redundant targets.  Round after round the row of the query that covers the
+        most hashes no earlier pick covered is kept (ties: the smaller tid) and its hashes are taken out; a query stops when the
+        best remaining row would add fewer than min_unique new hashes (0 counts as 1) or after max_results rows (0: no limit).
+        `hits` comes from any search of `queries` against an index of `targets` (thresholded and best-hits lists too).  The
+        result is a Hits like that of best_hits — still in (qid, tid) order, with rank and src_row (Hits.best_to_host) — plus
+        unique_intersect, remaining and unique_weighted per row (Hits.gather_to_host)."""
+        for name, v in (("min_unique", min_unique), ("max_results", max_results)):
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError(f"{name} = {v} does not fit 32 bits")
+        opts = _lib.ks_gather_opts(int(min_unique), int(max_results), 0, 0)
+        out = C.c_void_p()
+        self._check(self._L.ks_hits_gather(self._h, hits._h, queries._h, targets._h, C.byref(opts), C.byref(out)))
+        return Hits(self, out)
+
     # ---- index / search ----
     def index_build(self, targets: "Sketches") -> "Index":
         out = C.c_void_p()
@@ -893,3 +908,14 @@ class Hits(_Owned):
         rank = np.zeros(n, np.uint32); src = np.zeros(n, np.uint32)
         self._ctx._check(self._ctx._L.ks_hits_copy_best_to_host(self._ctx._h, self._h, _ptr(rank), _ptr(src)))
         return rank, src
+
+    def gather_to_host(self) -> Optional[Tuple[np.ndarray, np.ndarray, np.ndarray]]:
+        """(unique_intersect u32, remaining u32, unique_weighted u64) per row of a `Context.gather` result: the hashes the row
+        newly covered, the query's hashes still uncovered after it, and the query's abundances summed over the newly covered
+        ones.  None for hits that did not come from gather."""
+        if not self._ctx._L.ks_hits_device_unique_intersect(self._h):
+            return None
+        n = self.count
+        uniq = np.zeros(n, np.uint32); rem = np.zeros(n, np.uint32); uw = np.zeros(n, np.uint64)
+        self._ctx._check(self._ctx._L.ks_hits_copy_gather_to_host(self._ctx._h, self._h, _ptr(uniq), _ptr(rem), _ptr(uw)))
+        return uniq, rem, uw

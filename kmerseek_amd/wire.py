@@ -10,6 +10,8 @@
                         tests/testdata/index/ced9-bcl2-first25.hp.k16.manysearch.csv.
 * ``do_cluster()``    — all-vs-all search of one .sig.zip, then the connected components at a similarity threshold: a CSV of
                         clusters in this project's own format (modelled on branchwater ``cluster``; no parity claimed).
+* ``do_gather()``     — search, then per query the greedy non-redundant targets (Context.gather): a CSV in this project's own
+                        format (modelled on branchwater ``fastmultigather``; no parity claimed).
 Hashing, sorting, joining and counting all run in the HIP library; this module only formats.  The ratio columns are
 f64 arithmetic on the integer results (formulas: SURVEY.md §8(a) row a10).
 """
@@ -385,6 +387,89 @@ def do_cluster(sig: str, output: str, ksize: int, scaled: int, moltype: str, sim
                 w = csv.writer(f, lineterminator="\n")
                 w.writerow(["cluster_size", "count"])
                 w.writerows(cluster_size_histogram(offsets))
+        return len(rows)
+    finally:
+        if own:
+            ctx.close()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# do_gather()  — search, then per query the greedy non-redundant targets
+# ---------------------------------------------------------------------------------------------------------
+GATHER_COLUMNS = [
+    "query_name", "query_md5", "match_name", "match_md5", "gather_result_rank", "intersect_bp", "unique_intersect_bp",
+    "remaining_bp", "f_orig_query", "f_unique_to_query", "f_match", "f_match_orig", "f_unique_weighted", "average_abund",
+    "ksize", "scaled", "moltype",
+]
+
+
+def gather_rows(q_names, q_off, q_mins, q_abund, t_names, t_off, t_mins, hits, rank, gathered, ksize: int, scaled: int,
+                moltype: str) -> List[dict]:
+    """The 17 CSV columns for every row of a Context.gather result, ordered by (query, rank).  hits: its (qid, tid, intersect,
+    n_weighted) columns; rank: Hits.best_to_host()[0]; gathered: Hits.gather_to_host() = (unique_intersect, remaining,
+    unique_weighted).  The _bp columns are hashes x scaled; every ratio is one f64 division of two integers: f_orig_query =
+    intersect / |q|, f_unique_to_query = unique_intersect / |q|, f_match = unique_intersect / |t|, f_match_orig = intersect / |t|,
+    f_unique_weighted = unique_weighted / (sum of q's abundances), average_abund = unique_weighted / unique_intersect."""
+    qid, tid, isect, _ = hits
+    uniq, rem, uw = gathered
+    order = np.lexsort((np.asarray(rank), np.asarray(qid)))
+    md5_q, md5_t, q_tot = {}, {}, {}
+    rows = []
+    for r in order.tolist():
+        q, t, i, u = int(qid[r]), int(tid[r]), int(isect[r]), int(uniq[r])
+        qm = q_mins[int(q_off[q]):int(q_off[q + 1])]
+        tm = t_mins[int(t_off[t]):int(t_off[t + 1])]
+        nq, nt = len(qm), len(tm)
+        if q not in md5_q:
+            md5_q[q] = sourmash_md5(qm, ksize)
+            q_tot[q] = int(np.asarray(q_abund[int(q_off[q]):int(q_off[q + 1])], np.uint64).sum())
+        if t not in md5_t:
+            md5_t[t] = sourmash_md5(tm, ksize)
+        w = int(uw[r])
+        rows.append({
+            "query_name": q_names[q], "query_md5": md5_q[q], "match_name": t_names[t], "match_md5": md5_t[t],
+            "gather_result_rank": int(rank[r]), "intersect_bp": i * scaled, "unique_intersect_bp": u * scaled,
+            "remaining_bp": int(rem[r]) * scaled, "f_orig_query": format_f64(float(i) / float(nq)),
+            "f_unique_to_query": format_f64(float(u) / float(nq)), "f_match": format_f64(float(u) / float(nt)),
+            "f_match_orig": format_f64(float(i) / float(nt)),
+            "f_unique_weighted": format_f64(float(w) / float(q_tot[q]) if q_tot[q] else math.nan),
+            "average_abund": format_f64(float(w) / float(u)), "ksize": 3 * ksize, "scaled": scaled, "moltype": moltype,
+        })
+    return rows
+
+
+def do_gather(query_sig: str, target_sig: str, output: str, ksize: int, scaled: int, moltype: str, min_unique: int = 1,
+              max_results: int = 0, min_containment: float = 0.0, ctx: Optional[Context] = None) -> int:
+    """Search every sketch of query_sig (.sig.zip) against every sketch of target_sig (min_containment > 0: only the rows at or
+    above that containment are candidates), then per query the greedy non-redundant targets (Context.gather: every target is
+    credited only with the hashes no earlier one covered; min_unique, max_results as there).  Writes one CSV row per kept row,
+    ordered by (query, rank), with the columns GATHER_COLUMNS (gather_rows has the formulas).  The format is this project's
+    own, modelled on the output of branchwater's `fastmultigather`; no parity with that tool is claimed.  Returns the number of
+    rows written."""
+    own = ctx is None
+    ctx = ctx or Context(0)
+    try:
+        qn, qo, qm, qa, qk, qs, qmol = read_sig_zip(query_sig)
+        tn, to, tm, ta, tk, ts, tmol = read_sig_zip(target_sig)
+        for have in ((qk, qs, qmol), (tk, ts, tmol)):
+            if have != (ksize, scaled, moltype):
+                raise ValueError(f"sketch parameters {have} do not match the requested {(ksize, scaled, moltype)}")
+        made = []
+        try:
+            Q = ctx.sketches_from_host(qo, qm, qa, ksize, scaled, moltype); made.append(Q)
+            T = ctx.sketches_from_host(to, tm, ta, ksize, scaled, moltype); made.append(T)
+            ix = ctx.index_build(T); made.append(ix)
+            hits = ctx.search(ix, Q, min_containment=min_containment); made.append(hits)
+            g = ctx.gather(hits, Q, T, min_unique=min_unique, max_results=max_results); made.append(g)
+            rows = gather_rows(qn, qo, qm, qa, tn, to, tm, g.to_host(), g.best_to_host()[0], g.gather_to_host(), ksize, scaled,
+                               moltype)
+        finally:
+            for o in reversed(made):
+                o.free()
+        with open(output, "w", newline="") as f:
+            w = csv.DictWriter(f, fieldnames=GATHER_COLUMNS, lineterminator="\n")
+            w.writeheader()
+            w.writerows(rows)
         return len(rows)
     finally:
         if own:
