@@ -11,7 +11,7 @@
 //            then one sweep in row order keeps the rows above the threshold and, of those equal to it, the first `quota` in row
 //            order (= the smallest tids), then the kept rows are ranked among themselves by counting (every row that beats a
 //            kept row is kept itself, so this is the rank inside the whole segment), BH_CHUNK opponents in LDS at a time;
-//   move     keep flags -> one-launch exclusive scan -> one scatter of all columns (rf_move) + rank + src_row.
+//   move     ks_hits_select_tail: keep flags -> one-launch exclusive scan -> one scatter of all columns (rf_move) + rank + src_row.
 // Every comparison is on (u64 key, row index): integers.  No f64 atomics, no reductions of scores: a row's rank and whether it
 // is kept do not depend on the path its segment took (KS_DEBUG_BEST_PATH = 1 every segment by a wave, 2 by a workgroup,
 // 3 by a workgroup with a chunk of BH_CHUNK_SMALL rows — the tests reach the streamed case with a few hundred rows).
@@ -40,12 +40,6 @@ struct bh_in {
     bh_set q, t;
 };
 
-// a listed segment: (first row, rows); list[0] counts, also past `cap` (only a list of rows that are not a hit list's can)
-KS_DEV void bh_seg_push(u32 *list, u32 cap, u32 b, u32 len) {
-    const u32 i = atomicAdd(&list[0], 1u);
-    if (i < cap) { list[1 + 2 * i] = b; list[2 + 2 * i] = len; }
-}
-
 // mode: 0 by length, 1 every segment to the wave kernel, 2 every segment to the workgroup kernel
 __global__ __launch_bounds__(256) void k_best_keys(bh_in R, int mode, u32 seg_cap, u64 *key, u32 *flags, u32 *rank, u32 *wave_segs, u32 *wg_segs,
                                                    unsigned long long *bad) {
@@ -54,22 +48,21 @@ __global__ __launch_bounds__(256) void k_best_keys(bh_in R, int mode, u32 seg_ca
     if (r >= R.n_rows) return;
     const u32 q = R.qid[r], t = R.tid[r];
     u64 kx = 0;
-    if ((R.q.off && q >= R.q.n) || (R.t.off && t >= R.t.n)) atomicMin(&bad[BH_BAD_ID], (unsigned long long)r);
+    if ((R.q.off && q >= R.q.n) || (R.t.off && t >= R.t.n)) ks_first_bad(bad, BH_BAD_ID, r);
     else {
         bool bad_size;
         const double s = bh_row_score(R.rank_by, r, q, t, R.isect[r], R.q, R.t, R.score, &bad_size);
-        if (bad_size) atomicMin(&bad[BH_BAD_SIZE], (unsigned long long)r);
+        if (bad_size) ks_first_bad(bad, BH_BAD_SIZE, r);
         kx = bh_sortable(s);
     }
     key[r] = kx;
     if (r != 0 && R.qid[r - 1] == q) return;
     // the first row of a segment: where it ends, and which kernel takes it
-    const u32 end = q == 0xffffffffu ? R.n_rows : r + ks_query_row_begin(R.qid + r, R.n_rows - r, q + 1);
-    const u32 len = end - r;
+    const u32 len = ks_seg_len(R.qid, R.n_rows, r, q);
     if (mode == 1 || (mode == 0 && len <= BH_WAVE_MAX)) {
         if (mode == 0 && len == 1) { flags[r] = 1u; rank[r] = 0u; } // (k >= 1)
-        else bh_seg_push(wave_segs, seg_cap, r, len);
-    } else bh_seg_push(wg_segs, seg_cap, r, len);
+        else ks_seg_list_push(wave_segs, seg_cap, r, len);
+    } else ks_seg_list_push(wg_segs, seg_cap, r, len);
 }
 
 // `o` at row index oi beats `s` at row index si
@@ -79,10 +72,9 @@ KS_DEV u32 bh_beats(u64 o, u32 oi, u64 s, u32 si) { return (o > s || (o == s && 
 // lane by lane through v_readlane (a scalar broadcast: no LDS, no ds_bpermute).  A segment of the by-length split is one round
 // of at most 64 steps; a longer one (KS_DEBUG_BEST_PATH = 1) takes ceil(len / 64)^2 rounds.
 __global__ __launch_bounds__(256) void k_best_wave(const u64 *key, const u32 *segs, u32 seg_cap, u32 k, u32 *flags, u32 *rank) {
-    const u32 lane = threadIdx.x & 63, n_waves = gridDim.x * (blockDim.x / 64);
-    const u32 n_list = segs[0] < seg_cap ? segs[0] : seg_cap;
-    for (u32 w = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); w < n_list; w += n_waves) {
-        const u32 b = (u32)__builtin_amdgcn_readfirstlane((int)segs[1 + 2 * w]), len = (u32)__builtin_amdgcn_readfirstlane((int)segs[2 + 2 * w]);
+    const u32 lane = threadIdx.x & 63;
+    for (ks_seg_walk seg = ks_seg_list_by_wave(segs, seg_cap); seg.next();) {
+        const u32 b = seg.b, len = seg.len;
         for (u32 sc = 0; sc < len; sc += 64) {
             const u32 si = sc + lane;
             const u64 skey = si < len ? key[b + si] : 0;
@@ -113,9 +105,8 @@ __global__ __launch_bounds__(256) void k_best_wg(const u64 *key, const u32 *segs
     __shared__ u32 s_scan[8];
     __shared__ u32 s_sel[3];
     const u32 t = threadIdx.x;
-    const u32 n_list = segs[0] < seg_cap ? segs[0] : seg_cap;
-    for (u32 w = blockIdx.x; w < n_list; w += gridDim.x) {
-        const u32 b = segs[1 + 2 * w], len = segs[2 + 2 * w];
+    for (ks_seg_walk seg = ks_seg_list_by_wg(segs, seg_cap); seg.next();) {
+        const u32 b = seg.b, len = seg.len;
         const u32 kk = k < len ? k : len; // rows kept
         const bool staged = len <= chunk;
         __syncthreads(); // (the previous segment's last readers of s_keys)
@@ -198,6 +189,24 @@ __global__ __launch_bounds__(256) void k_best_move(rf_cols in, u32 n_rows, const
     if (ga.unique) { o_unique[o] = ga.unique[r]; o_remaining[o] = ga.remaining[r]; o_weighted[o] = ga.weighted[r]; }
 }
 
+int ks_hits_alloc_cols(ks_ctx *ctx, ks_hits *H, size_t n, u32 extra) {
+    KS_TRY(ks_alloc(ctx, &H->d_qid, n)); KS_TRY(ks_alloc(ctx, &H->d_tid, n));
+    KS_TRY(ks_alloc(ctx, &H->d_isect, n)); KS_TRY(ks_alloc(ctx, &H->d_nw, n));
+    if (H->has_stats) { KS_TRY(ks_alloc(ctx, &H->d_median2, n)); KS_TRY(ks_alloc(ctx, &H->d_ss, n)); }
+    if (extra & KS_COLS_RANKED) { KS_TRY(ks_alloc(ctx, &H->d_rank, n)); KS_TRY(ks_alloc(ctx, &H->d_src_row, n)); }
+    if (extra & KS_COLS_GATHER) {
+        KS_TRY(ks_alloc(ctx, &H->d_ga_unique, n)); KS_TRY(ks_alloc(ctx, &H->d_ga_remaining, n)); KS_TRY(ks_alloc(ctx, &H->d_ga_weighted, n));
+    }
+    return KS_OK;
+}
+
+void ks_hits_inherit(ks_hits *B, const ks_hits *H) {
+    B->n_pair_instances = H->n_pair_instances;
+    B->partition_path = H->partition_path;
+    B->bucket_posting_bytes = H->bucket_posting_bytes;
+    B->has_stats = H->has_stats;
+}
+
 int ks_hits_move_ranked(ks_ctx *ctx, const ks_hits *H, u32 n_rows, const u32 *dst, const u32 *rank, u32 cap, ks_hits *B,
                         const ks_gather_cols *ga) {
     const rf_cols in{H->d_qid, H->d_tid, H->d_isect, H->d_nw, H->has_stats ? H->d_median2 : nullptr, H->has_stats ? H->d_ss : nullptr};
@@ -207,68 +216,64 @@ int ks_hits_move_ranked(ks_ctx *ctx, const ks_hits *H, u32 n_rows, const u32 *ds
     return KS_OK;
 }
 
+int ks_hits_select_plan(ks_ctx *ctx, const char *what, const ks_hits *H, const ks_sketches *Q, u32 per_query, u32 *n, u64 *cap) {
+    if (H->n_hits >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "%s: 2^32 - 2 or more hit rows", what);
+    *n = (u32)H->n_hits;
+    *cap = *n;
+    if (Q && per_query && (u64)Q->n_seqs * per_query < *cap) *cap = (u64)Q->n_seqs * per_query;
+    return KS_OK;
+}
+
+int ks_hits_select_tail(ks_ctx *ctx, const char *what, const ks_hits *H, u32 n_rows, u32 *flags, const u32 *rank, u64 cap,
+                        const ks_gather_cols *ga, const ks_ctl &ctl, u32 kept, const std::function<int()> &checks, ks_hits *B) {
+    KS_TRY(ks_scan_u32_inplace(ctx, flags, n_rows, ctl.low32(kept)));
+    KS_TRY(ks_hits_move_ranked(ctx, H, n_rows, flags, rank, (u32)cap, B, ga));
+    KS_TRY(ks_stream_wait_fetch_scans(ctx, {ctl.fetch()}));
+    KS_TRY(checks());
+    if (ctl[kept] > cap)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "%s: %llu rows kept where at most %llu can be: the rows are not ordered by (qid, tid)", what,
+                       (unsigned long long)ctl[kept], (unsigned long long)cap);
+    B->n_hits = ctl[kept];
+    return KS_OK;
+}
+
 static int best_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *Q, const ks_sketches *T, const double *d_score, const ks_best_opts *o,
                     ks_hits *B) {
-    const u64 n64 = H->n_hits;
-    if (n64 >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "best hits: 2^32 or more hit rows");
-    const u32 n = (u32)n64;
-    // rows the output can hold: every query keeps at most k
-    u64 cap = n;
-    if (Q && (u64)Q->n_seqs * o->k < cap) cap = (u64)Q->n_seqs * o->k;
-    const size_t na = cap ? (size_t)cap : 1;
-    KS_TRY(ks_alloc(ctx, &B->d_qid, na)); KS_TRY(ks_alloc(ctx, &B->d_tid, na));
-    KS_TRY(ks_alloc(ctx, &B->d_isect, na)); KS_TRY(ks_alloc(ctx, &B->d_nw, na));
-    if (B->has_stats) { KS_TRY(ks_alloc(ctx, &B->d_median2, na)); KS_TRY(ks_alloc(ctx, &B->d_ss, na)); }
-    KS_TRY(ks_alloc(ctx, &B->d_rank, na)); KS_TRY(ks_alloc(ctx, &B->d_src_row, na));
+    u32 n;
+    u64 cap; // every query keeps at most k
+    KS_TRY(ks_hits_select_plan(ctx, "best hits", H, Q, o->k, &n, &cap));
+    KS_TRY(ks_hits_alloc_cols(ctx, B, (size_t)cap, KS_COLS_RANKED));
     if (n == 0) return KS_OK;
 
-    int mode = 0;
-    u32 chunk = BH_CHUNK;
-    if (const char *f = ks_dbg(ctx, KS_DBG_BEST_PATH)) { // (tests: every segment one way; 3 = the workgroup path with a small chunk)
-        const int v = atoi(f);
-        mode = v == 1 ? 1 : (v == 2 || v == 3) ? 2 : 0;
-        if (v == 3) chunk = BH_CHUNK_SMALL;
-    }
+    bool small; // (tests: every segment one way; 3 = the workgroup path with a small chunk)
+    const int mode = ks_seg_path_knob(ctx, KS_DBG_BEST_PATH, &small);
+    const u32 chunk = small ? BH_CHUNK_SMALL : BH_CHUNK;
     const u32 seg_cap = Q && Q->n_seqs < n ? Q->n_seqs : n; // segments there can be
     ks_scratch sc(ctx);
-    u64 *key = nullptr, *ctl = nullptr;
+    u64 *key = nullptr;
     u32 *flags = nullptr, *rank = nullptr, *kept_rows = nullptr, *wave_segs = nullptr, *wg_segs = nullptr;
+    ks_ctl ctl; // [BH_BAD_ID], [BH_BAD_SIZE]: the first such row; [BH_KEPT]: the scan's total
     KS_TRY(sc.alloc(&key, (size_t)n)); KS_TRY(sc.alloc(&flags, (size_t)n)); KS_TRY(sc.alloc(&rank, (size_t)n));
     KS_TRY(sc.alloc(&kept_rows, (size_t)n));
-    KS_TRY(sc.alloc(&wave_segs, 2 * (size_t)seg_cap + 1)); KS_TRY(sc.alloc(&wg_segs, 2 * (size_t)seg_cap + 1));
-    KS_TRY(sc.alloc(&ctl, 3)); // [BH_BAD_ID], [BH_BAD_SIZE]: the first such row (all ones: none); [BH_KEPT]: the scan's total
-    KS_HIP(ctx, hipMemsetAsync(ctl, 0xff, 2 * sizeof(u64), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(ctl + BH_KEPT, 0, sizeof(u64), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(wave_segs, 0, sizeof(u32), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(wg_segs, 0, sizeof(u32), ctx->stream));
+    KS_TRY(ks_seg_list_alloc(ctx, sc, seg_cap, &wave_segs)); KS_TRY(ks_seg_list_alloc(ctx, sc, seg_cap, &wg_segs));
+    KS_TRY(ctl.init(ctx, sc, KS_PIN_BEST, 2, 1));
 
     const bh_in R = {H->d_qid, H->d_tid, H->d_isect, d_score, n, o->rank_by, o->k, bh_set_of(Q), bh_set_of(T)};
     const u32 g = (n + 255) / 256;
-    KS_LAUNCH(ctx, "best_keys", k_best_keys, g, 256, R, mode, seg_cap, key, flags, rank, wave_segs, wg_segs, (unsigned long long *)ctl);
+    KS_LAUNCH(ctx, "best_keys", k_best_keys, g, 256, R, mode, seg_cap, key, flags, rank, wave_segs, wg_segs, ctl.words());
     if (mode != 2)
         KS_LAUNCH(ctx, "best_wave", k_best_wave, BH_WAVE_GRID, 256, (const u64 *)key, (const u32 *)wave_segs, seg_cap, o->k, flags, rank);
     if (mode != 1)
         KS_LAUNCH(ctx, "best_wg", k_best_wg, BH_WG_GRID, 256, (const u64 *)key, (const u32 *)wg_segs, seg_cap, o->k, chunk, flags, rank, kept_rows);
-    KS_TRY(ks_scan_u32_inplace(ctx, flags, n, (u32 *)(ctl + BH_KEPT)));
-    KS_TRY(ks_hits_move_ranked(ctx, H, n, flags, rank, (u32)cap, B, nullptr));
-    u64 *const rb = ctx->h_pin + KS_PIN_BEST;
-    {
-        ks_fetch_seg f[2];
-        f[0] = ks_fetch_words(ctl, rb, 6);
-        const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
-        KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
-    }
-    KS_TRY(ks_scan_status_check(ctx));
-    if (rb[BH_BAD_ID] != ~0ULL)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "best hits: hit row %llu names a query or target beyond the sketch sets",
-                       (unsigned long long)rb[BH_BAD_ID]);
-    if (rb[BH_BAD_SIZE] != ~0ULL)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "best hits: hit row %llu names an empty sketch: its score divides by 0", (unsigned long long)rb[BH_BAD_SIZE]);
-    if (rb[BH_KEPT] > cap)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "best hits: %llu rows kept where at most %llu can be: the rows are not ordered by (qid, tid)",
-                       (unsigned long long)rb[BH_KEPT], (unsigned long long)cap);
-    B->n_hits = rb[BH_KEPT];
-    return KS_OK;
+    return ks_hits_select_tail(ctx, "best hits", H, n, flags, rank, cap, nullptr, ctl, BH_KEPT, [&]() -> int {
+        if (ctl.bad(BH_BAD_ID))
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "best hits: hit row %llu names a query or target beyond the sketch sets",
+                           (unsigned long long)ctl[BH_BAD_ID]);
+        if (ctl.bad(BH_BAD_SIZE))
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "best hits: hit row %llu names an empty sketch: its score divides by 0",
+                           (unsigned long long)ctl[BH_BAD_SIZE]);
+        return KS_OK;
+    }, B);
 }
 
 // the option words and what they ask of the other arguments; ctx may be NULL
@@ -294,19 +299,11 @@ extern "C" int ks_hits_best(ks_ctx *ctx, const ks_hits *hits, const ks_sketches 
     KS_TRY(best_opts_check(ctx, opts, queries, targets, d_score));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    if (hits->ctx != ctx || (queries && queries->ctx != ctx) || (targets && targets->ctx != ctx))
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "best hits: an input of another context");
-    if (queries && targets && !ks_same_params(queries->params, targets->params)) {
-        const ks_params &a = queries->params, &b = targets->params;
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "best hits: the sketch sets were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)",
-                       a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
-    }
+    KS_TRY(ks_inputs_check_ctx(ctx, "best hits", hits, queries, targets));
+    if (queries && targets) KS_TRY(ks_params_check_same(ctx, "best hits", "the sketch sets", queries->params, targets->params));
     KS_HIP(ctx, hipSetDevice(ctx->device));
     ks_result<ks_hits> B(ctx, out, ks_hits_free);
-    B->n_pair_instances = hits->n_pair_instances;
-    B->partition_path = hits->partition_path;
-    B->bucket_posting_bytes = hits->bucket_posting_bytes;
-    B->has_stats = hits->has_stats;
+    ks_hits_inherit(B, hits);
     KS_TRY(best_run(ctx, hits, queries, targets, d_score, opts, B));
     return B.commit();
     });

@@ -41,7 +41,7 @@
 
 #define CL_WAVE_UNIFORM_DEFAULT 0 // the wave-uniform query path did not beat the plain one by more than the noise: behind the knob
 #define CL_HOOK_WG_PER_CU 8 // workgroups of k_cluster_hook per CU: 32 waves, what a CU holds
-enum { CL_BAD_ID = 0, CL_BAD_SIZE = 1, CL_EDGES = 2, CL_CLUSTERS = 3, CL_LARGEST = 4, CL_WORDS = 5 }; // u64 words of the control block
+enum { CL_BAD_ID = 0, CL_BAD_SIZE = 1, CL_EDGES = 2, CL_CLUSTERS = 3, CL_LARGEST = 4 }; // words of the control block
 
 struct cl_in {
     const u32 *qid, *tid, *isect;
@@ -101,11 +101,11 @@ __global__ __launch_bounds__(256) void k_cluster_hook(cl_in R, int wave_uniform,
         bool passed = false;
         if (r64 < R.n_rows) {
             q = R.qid[r]; t = R.tid[r];
-            if (q >= R.n || t >= R.n) atomicMin(&ctl[CL_BAD_ID], (unsigned long long)r);
+            if (q >= R.n || t >= R.n) ks_first_bad(ctl, CL_BAD_ID, r);
             else {
                 bool bad_size;
                 const double s = bh_row_score(R.similarity, r, q, t, R.isect[r], R.sizes, R.sizes, R.score, &bad_size);
-                if (bad_size) atomicMin(&ctl[CL_BAD_SIZE], (unsigned long long)r);
+                if (bad_size) ks_first_bad(ctl, CL_BAD_SIZE, r);
                 else passed = s >= R.threshold; // (a NaN score never passes)
             }
         }
@@ -197,7 +197,7 @@ __global__ __launch_bounds__(256) void k_cluster_finish(u32 n, const u64 *sorted
 
 static int cluster_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *N, const double *d_score, const ks_cluster_opts *o, ks_clusters *K) {
     const u64 n64 = H->n_hits;
-    if (n64 >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "cluster: 2^32 or more hit rows");
+    if (n64 >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "cluster: 2^32 - 2 or more hit rows");
     const u32 n_rows = (u32)n64, n = N ? N->n_seqs : o->n_nodes;
     K->n_nodes = n; K->n_clusters = 0; K->largest = 0; K->n_edges = 0;
     KS_TRY(ks_alloc(ctx, &K->d_label, (size_t)n)); KS_TRY(ks_alloc(ctx, &K->d_cluster_id, (size_t)n));
@@ -217,22 +217,21 @@ static int cluster_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *N, cons
 
     ks_scratch sc(ctx);
     u32 *parent = nullptr, *root_idx = nullptr, *sizes = nullptr;
-    u64 *rep = nullptr, *ka = nullptr, *kb = nullptr, *ctl = nullptr;
+    u64 *rep = nullptr, *ka = nullptr, *kb = nullptr;
+    ks_ctl ctl; // [CL_BAD_ID], [CL_BAD_SIZE]: the first such row; the three counts
     KS_TRY(sc.alloc(&parent, (size_t)n)); KS_TRY(sc.alloc(&root_idx, (size_t)n)); KS_TRY(sc.alloc(&sizes, (size_t)n));
     KS_TRY(sc.alloc(&rep, (size_t)n)); KS_TRY(sc.alloc(&ka, (size_t)n)); KS_TRY(sc.alloc(&kb, (size_t)n));
-    KS_TRY(sc.alloc(&ctl, CL_WORDS)); // [CL_BAD_ID], [CL_BAD_SIZE]: the first such row (all ones: none); the counts from 0
-    KS_HIP(ctx, hipMemsetAsync(ctl, 0xff, 2 * sizeof(u64), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(ctl + CL_EDGES, 0, (CL_WORDS - CL_EDGES) * sizeof(u64), ctx->stream));
+    KS_TRY(ctl.init(ctx, sc, KS_PIN_CLUSTER, 2, 3));
 
     const u32 g_n = (n + 255) / 256;
     KS_LAUNCH(ctx, "cluster_init", k_cluster_init, g_n, 256, n, parent, sizes, rep);
     if (n_rows) {
         const cl_in R = {H->d_qid, H->d_tid, H->d_isect, d_score, n_rows, o->similarity, n, o->threshold, bh_set_of(N)};
         const u32 g_rows = (n_rows + 255) / 256, g_max = (u32)ctx->n_cus * CL_HOOK_WG_PER_CU;
-        KS_LAUNCH(ctx, "cluster_hook", k_cluster_hook, g_rows < g_max ? g_rows : g_max, 256, R, wave_uniform, parent, (unsigned long long *)ctl);
+        KS_LAUNCH(ctx, "cluster_hook", k_cluster_hook, g_rows < g_max ? g_rows : g_max, 256, R, wave_uniform, parent, ctl.words());
     }
     KS_LAUNCH(ctx, "cluster_flatten", k_cluster_flatten, g_n, 256, n, (const u32 *)parent, K->d_label, root_idx);
-    KS_TRY(ks_scan_u32_inplace(ctx, root_idx, n, (u32 *)(ctl + CL_CLUSTERS)));
+    KS_TRY(ks_scan_u32_inplace(ctx, root_idx, n, ctl.low32(CL_CLUSTERS)));
     KS_LAUNCH(ctx, "cluster_ids", k_cluster_ids, g_n, 256, n, (const u32 *)K->d_label, (const u32 *)root_idx, bh_set_of(N), K->d_cluster_id, sizes, rep, ka);
     KS_TRY(ks_scan_u32_to_u64(ctx, sizes, K->d_offsets, n));
     // members: the keys are written in id order, so a STABLE sort on the cluster id alone leaves them ordered by (cluster, id).
@@ -244,25 +243,18 @@ static int cluster_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *N, cons
     u64 *sorted = nullptr;
     KS_TRY(ks_radix_sort_keys(ctx, KS_SORT_PAIRS, ka, ka, kb, n, shifts, ns, &sorted));
     KS_LAUNCH(ctx, "cluster_finish", k_cluster_finish, g_n, 256, n, (const u64 *)sorted, (const u32 *)sizes, (const u64 *)rep, K->d_members, K->d_rep,
-              (unsigned long long *)ctl);
-    u64 *const rb = ctx->h_pin + KS_PIN_CLUSTER;
-    {
-        ks_fetch_seg f[2];
-        f[0] = ks_fetch_words(ctl, rb, 2 * CL_WORDS);
-        const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
-        KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
-    }
-    KS_TRY(ks_scan_status_check(ctx));
-    if (rb[CL_BAD_ID] != ~0ULL)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster: hit row %llu names a node beyond the %u nodes of the set", (unsigned long long)rb[CL_BAD_ID], n);
-    if (rb[CL_BAD_SIZE] != ~0ULL)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster: hit row %llu names an empty sketch: its score divides by 0", (unsigned long long)rb[CL_BAD_SIZE]);
-    if (rb[CL_CLUSTERS] == 0 || rb[CL_CLUSTERS] > n || rb[CL_LARGEST] > n)
-        return ks_fail(ctx, KS_ERR_HIP, "internal error: %llu clusters, the largest of %llu, on %u nodes", (unsigned long long)rb[CL_CLUSTERS],
-                       (unsigned long long)rb[CL_LARGEST], n);
-    K->n_edges = rb[CL_EDGES];
-    K->n_clusters = (u32)rb[CL_CLUSTERS];
-    K->largest = (u32)rb[CL_LARGEST];
+              ctl.words());
+    KS_TRY(ks_stream_wait_fetch_scans(ctx, {ctl.fetch()}));
+    if (ctl.bad(CL_BAD_ID))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster: hit row %llu names a node beyond the %u nodes of the set", (unsigned long long)ctl[CL_BAD_ID], n);
+    if (ctl.bad(CL_BAD_SIZE))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster: hit row %llu names an empty sketch: its score divides by 0", (unsigned long long)ctl[CL_BAD_SIZE]);
+    if (ctl[CL_CLUSTERS] == 0 || ctl[CL_CLUSTERS] > n || ctl[CL_LARGEST] > n)
+        return ks_fail(ctx, KS_ERR_HIP, "internal error: %llu clusters, the largest of %llu, on %u nodes", (unsigned long long)ctl[CL_CLUSTERS],
+                       (unsigned long long)ctl[CL_LARGEST], n);
+    K->n_edges = ctl[CL_EDGES];
+    K->n_clusters = (u32)ctl[CL_CLUSTERS];
+    K->largest = (u32)ctl[CL_LARGEST];
     return KS_OK;
 }
 
@@ -288,7 +280,7 @@ extern "C" int ks_hits_cluster(ks_ctx *ctx, const ks_hits *hits, const ks_sketch
     KS_TRY(cluster_opts_check(ctx, opts, nodes, d_score));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    if (hits->ctx != ctx || (nodes && nodes->ctx != ctx)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster: an input of another context");
+    KS_TRY(ks_inputs_check_ctx(ctx, "cluster", hits, nodes));
     KS_HIP(ctx, hipSetDevice(ctx->device));
     ks_result<ks_clusters> K(ctx, out, ks_clusters_free);
     KS_TRY(cluster_run(ctx, hits, nodes, d_score, opts, K));

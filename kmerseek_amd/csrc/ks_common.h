@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <new>
 #include <stdexcept>
@@ -212,6 +213,28 @@ struct ks_scratch {
             if (blk[i] == p) { blk[i] = blk[--n]; return true; }
         return false;
     }
+};
+
+// The control block of a pass over hit rows, u64 words in the pass's scratch: `n_bad` words "the first row that is wrong for
+// reason i" (atomicMin; all ones: none), then `n_count` counters from 0.  fetch() names all of it for the pass's one wait, which
+// brings it to the pass's pinned slot (KS_PIN_*, at least n_bad + n_count words); [] and bad() read that copy.
+struct ks_ctl {
+    u64 *dev = nullptr;
+    u64 *host = nullptr;
+    u32 n_words = 0;
+    int init(ks_ctx *ctx, ks_scratch &sc, u32 pin_slot, u32 n_bad, u32 n_count) {
+        n_words = n_bad + n_count;
+        host = ctx->h_pin + pin_slot;
+        KS_TRY(sc.alloc(&dev, n_words));
+        KS_HIP(ctx, hipMemsetAsync(dev, 0xff, n_bad * sizeof(u64), ctx->stream));
+        KS_HIP(ctx, hipMemsetAsync(dev + n_bad, 0, n_count * sizeof(u64), ctx->stream));
+        return KS_OK;
+    }
+    unsigned long long *words() const { return (unsigned long long *)dev; } // what the kernels take
+    u32 *low32(u32 i) const { return (u32 *)(dev + i); }                    // a counter a u32 scan total is written to
+    ks_fetch_seg fetch() const { return ks_fetch_words(dev, host, 2 * n_words); }
+    u64 operator[](u32 i) const { return host[i]; }
+    bool bad(u32 i) const { return host[i] != ~0ULL; }
 };
 
 // One lifecycle for every opaque result object (ks_sketches, ks_index, ks_hits, ...).  The constructor clears *out and makes
@@ -445,13 +468,26 @@ int ks_row_slices_plan(ks_ctx *ctx, int dbg_id, const char *what, int low_bits, 
 // same size; *sorted = where they ended up (ka or kb)
 int ks_sort_live_keys(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int nbits, u64 **sorted);
 
-// ---- the kept rows of a ranked pass to their places (ks_best.hip; ks_hits_best and ks_hits_gather) ----
+// ---- a pass that keeps some rows of a hit list and returns a hit list (ks_best.hip; ks_hits_best and ks_hits_gather) ----
+// the columns of a hit list of n rows: the four every list has, the statistics if H->has_stats, and what `extra` asks for
+enum : u32 { KS_COLS_RANKED = 1u, KS_COLS_GATHER = 2u }; // rank + src_row; the three gather columns
+int ks_hits_alloc_cols(ks_ctx *ctx, ks_hits *H, size_t n, u32 extra);
+// what a list made of H's rows says about the search that made them
+void ks_hits_inherit(ks_hits *B, const ks_hits *H);
 // Row r of H with rank[r] != KS_RANK_NONE goes to row dst[r] (< cap) of B: all columns of H that B holds, the rank and r itself
 // (src_row).  ga != NULL: the three per-row gather columns go with it, into B's.
 #define KS_RANK_NONE 0xffffffffu
 struct ks_gather_cols { const u32 *unique, *remaining; const u64 *weighted; };
 int ks_hits_move_ranked(ks_ctx *ctx, const ks_hits *H, u32 n_rows, const u32 *dst, const u32 *rank, u32 cap, ks_hits *B,
                         const ks_gather_cols *ga);
+// the hit rows of such a pass: *n, their count as a u32, or "<what>: 2^32 - 2 or more hit rows" (KS_ERR_CAPACITY); *cap: the rows
+// the output can hold, at most `per_query` (0: no limit) for each query of Q (NULL: not known)
+int ks_hits_select_plan(ks_ctx *ctx, const char *what, const ks_hits *H, const ks_sketches *Q, u32 per_query, u32 *n, u64 *cap);
+// The tail of such a pass (`what`, for its messages): the keep flags of H's n_rows rows are scanned in place, the total into
+// ctl's counter `kept`; the kept rows move to B (room for `cap` rows); ONE wait brings ctl home; `checks` — what the pass's own
+// control words refuse — runs before the kept count is held against cap and becomes B->n_hits.
+int ks_hits_select_tail(ks_ctx *ctx, const char *what, const ks_hits *H, u32 n_rows, u32 *flags, const u32 *rank, u64 cap,
+                        const ks_gather_cols *ga, const ks_ctl &ctl, u32 kept, const std::function<int()> &checks, ks_hits *B);
 
 // ---- device-wide primitives (ks_scan.hip, ks_sort.hip) ----
 // exclusive scan of n u32 values into u64 (out[n] = total is also written: out has n+1 entries)
@@ -461,6 +497,9 @@ int ks_scan_u32_to_u64(ks_ctx *ctx, const u32 *in, u64 *out, u64 n);
 // ks_scan_status_fetch before a stream synchronisation they do anyway and call ks_scan_status_check after it.
 int ks_scan_status_fetch(ks_ctx *ctx);
 int ks_scan_status_check(ks_ctx *ctx);
+// ks_stream_wait_fetch of the segments (fewer than KS_FETCH_MAX) and of the scans' give-up word, then ks_scan_status_check: the
+// one wait of a pass that ran one-launch scans
+int ks_stream_wait_fetch_scans(ks_ctx *ctx, std::initializer_list<ks_fetch_seg> segs);
 int ks_scan_u32_inplace(ks_ctx *ctx, u32 *data, u64 n, u32 *d_total);
 
 // Stable LSD radix passes over (key u64, value V) records, one 8-bit digit at each listed shift.
@@ -519,6 +558,10 @@ struct ks_runs { u64 *keys; u32 *vals; u64 *row_start; u32 n_rows; };
 int ks_sorted_runs(ks_ctx *ctx, const ks_sketches *in, ks_scratch &sc, ks_runs *out);
 // a row list for ks_row_list_push (ks_device.h): room for n_rows rows behind its count, the count zeroed
 int ks_row_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t n_rows, u32 **list);
+// a segment list for ks_seg_list_push: room for `cap` segments behind its count, the count zeroed
+int ks_seg_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t cap, u32 **list);
+// the knob that sends every segment one way (tests): 0 by length (unset), 1 by a wave, 2 by a workgroup; 3: 2 with *small set
+int ks_seg_path_knob(const ks_ctx *ctx, int dbg_id, bool *small);
 // what the row half needs from one search; the sorted match list pk becomes H's rows (n_pairs == 0: none, pk is not read)
 struct ks_rows_in { const ks_sketches *q; u64 n_pairs; int tbits, abits; bool stats; double min_c; };
 int ks_search_rows(ks_ctx *ctx, const ks_rows_in &R, ks_hits *H, const u64 *pk);
@@ -533,8 +576,6 @@ int ks_sketch_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n
 int ks_sketch_finish_pending(ks_sketches *S, int *redo);
 // the fetch segment (ks_stream_wait_fetch) that brings a pending sketch's control block to h_pin + KS_PIN_SKETCH
 ks_fetch_seg ks_sketch_pending_seg(const ks_sketches *S);
-// the fetch segment of the one-launch scans' give-up flag (see ks_scan_status_check); false: nothing to fetch
-bool ks_scan_status_seg(ks_ctx *ctx, ks_fetch_seg *out);
 // bits of hash prefix the join against an index of n_postings uses (buckets of ~3k index postings, <= 16)
 int ks_join_pbits(const ks_ctx *ctx, u64 n_postings, u64 per_bucket);
 // multiplier of ks_join_prefix (ks_device.h) for a join on pbits prefix bits of hashes kept below max_hash
@@ -562,6 +603,14 @@ int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out);
 int ks_check_params(ks_ctx *ctx, const ks_params *p);
 // two objects were made with the same parameters: all five fields
 bool ks_same_params(const ks_params &a, const ks_params &b);
+// ... or KS_ERR_INVALID_ARG "<pass>: <the sketch sets / the tables> were made with different parameters (k, scaled, moltype)"
+int ks_params_check_same(ks_ctx *ctx, const char *pass, const char *noun, const ks_params &a, const ks_params &b);
+// every input that is not NULL belongs to ctx, or KS_ERR_INVALID_ARG "<pass>: an input of another context"
+template <typename... In>
+static inline int ks_inputs_check_ctx(ks_ctx *ctx, const char *pass, const In *...in) {
+    if (((!in || in->ctx == ctx) && ...)) return KS_OK;
+    return ks_fail(ctx, KS_ERR_INVALID_ARG, "%s: an input of another context", pass);
+}
 // the flags / reserved words of an options struct: "<what> options: reserved must be 0" / "... unknown flags"; ctx may be NULL
 int ks_opts_words_check(ks_ctx *ctx, const char *what, u32 flags, u32 allowed, u32 reserved);
 // gapped slots -> plain CSR (see ks_sketches); no-op for dense sketches.  Enqueued on ctx's stream.

@@ -60,6 +60,11 @@ extern "C" uint64_t ks_max_hash(uint32_t scaled) {
 bool ks_same_params(const ks_params &a, const ks_params &b) {
     return a.ksize == b.ksize && a.scaled == b.scaled && a.moltype == b.moltype && a.seed == b.seed && a.flags == b.flags;
 }
+int ks_params_check_same(ks_ctx *ctx, const char *pass, const char *noun, const ks_params &a, const ks_params &b) {
+    if (ks_same_params(a, b)) return KS_OK;
+    return ks_fail(ctx, KS_ERR_INVALID_ARG, "%s: %s were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)", pass, noun,
+                   a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
+}
 int ks_opts_words_check(ks_ctx *ctx, const char *what, u32 flags, u32 allowed, u32 reserved) {
     const char *why = reserved ? "reserved must be 0" : (flags & ~allowed) ? "unknown flags" : nullptr;
     if (!why) return KS_OK;

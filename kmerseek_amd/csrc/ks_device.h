@@ -225,6 +225,9 @@ KS_DEV void rf_move(const rf_cols &in, u32 r, u32 o, u32 *qid, u32 *tid, u32 *is
     if (median2) { median2[o] = in.median2[r]; ss[o] = in.ss[r]; }
 }
 
+// the first row that is wrong for reason `why` (a control block's words, ks_ctl; all ones: none)
+KS_DEV void ks_first_bad(unsigned long long *bad, u32 why, u32 r) { atomicMin(&bad[why], (unsigned long long)r); }
+
 // ---- short rows by a lane, long rows by a wave ----
 // A pass with a lane per row pushes the rows that are too long for one lane onto a list (list[0] counts, the rows follow:
 // ks_row_list_alloc on the host); a fixed grid of 4-wave workgroups strides over it, a wave per row, 64 elements per chunk, and
@@ -255,6 +258,86 @@ KS_DEV void ks_wave_add_ordered(u64 m, double &acc, double x, double &acc2, doub
 KS_DEV void ks_wave_add_ordered(u64 m, double &acc, double x) { double none = 0.0; ks_wave_add_ordered(m, acc, x, none, 0.0); }
 // the mask of the lanes below n (n <= 64)
 KS_DEV u64 ks_lanes_below(u32 n) { return n >= 64u ? ~0ULL : (1ULL << n) - 1ULL; }
+
+// ---- a query's rows by a wave or by a workgroup ----
+// A query's rows are one segment.  The lane of its first row finds its length and pushes (first row, rows) onto the list of the
+// kernel that takes it (list[0] counts, also past `cap`: only a list of rows that are not a hit list's can; ks_seg_list_alloc on
+// the host); a fixed grid strides over a list: for (ks_seg_walk seg = ks_seg_list_by_wave(list, cap); seg.next();), or _by_wg.
+// The loop stays in the kernel's own body, unlike ks_row_list_walk's callable: a workgroup's segment code reads the block size
+// (ks_block_excl_scan) in every round, and inside a callable of a function template the compiler reads it with a vector load.
+KS_DEV u32 ks_readfirst(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
+// rows of the segment of query q that begins at row r (q + 1 does not wrap: the last id there is ends the list)
+KS_DEV u32 ks_seg_len(const u32 *qid, u32 n_rows, u32 r, u32 q) {
+    return q == 0xffffffffu ? n_rows - r : ks_query_row_begin(qid + r, n_rows - r, q + 1);
+}
+KS_DEV void ks_seg_list_push(u32 *list, u32 cap, u32 b, u32 len) {
+    const u32 i = atomicAdd(&list[0], 1u);
+    if (i < cap) { list[1 + 2 * i] = b; list[2 + 2 * i] = len; }
+}
+struct ks_seg_walk {
+    const u32 *list;
+    u32 n, w, step, b, len; // (b and len: wave-uniform, in scalar registers)
+    KS_DEV bool next() {
+        if (w >= n) return false;
+        b = ks_readfirst(list[1 + 2 * w]); len = ks_readfirst(list[2 + 2 * w]);
+        w += step;
+        return true;
+    }
+};
+KS_DEV ks_seg_walk ks_seg_list_by_wg(const u32 *list, u32 cap) { return {list, list[0] < cap ? list[0] : cap, blockIdx.x, gridDim.x, 0u, 0u}; }
+KS_DEV ks_seg_walk ks_seg_list_by_wave(const u32 *list, u32 cap) {
+    const u32 per_wg = blockDim.x / 64;
+    return {list, list[0] < cap ? list[0] : cap, blockIdx.x * per_wg + (threadIdx.x >> 6), gridDim.x * per_wg, 0u, 0u};
+}
+
+// ---- the hashes the two sketches of a hit row share ----
+// The shorter run is walked, the longer one searched: both ascend.  Positions are reported INSIDE q's sketch, whichever is walked.
+struct ks_run_pair {
+    const u64 *wh, *sh; // the walked run, the searched run
+    u32 nw, ns;         // their lengths
+    bool walk_q;        // the query's is the walked one
+    u64 qb;             // where q's sketch begins in the query arrays
+};
+KS_DEV ks_run_pair ks_run_pair_of(const u64 *q_off, const u64 *q_hash, const u64 *t_off, const u64 *t_hash, u32 q, u32 t) {
+    const u64 qb = q_off[q], tb = t_off[t];
+    const u32 nq = (u32)(q_off[q + 1] - qb), nt = (u32)(t_off[t + 1] - tb);
+    const bool walk_q = nq <= nt;
+    return {walk_q ? q_hash + qb : t_hash + tb, walk_q ? t_hash + tb : q_hash + qb, walk_q ? nq : nt, walk_q ? nt : nq, walk_q, qb};
+}
+// One lane walks: every search starts where the last one ended.  shared(position, shared hashes before it) once per shared
+// hash, ascending.  Returns their count.
+template <typename Shared> KS_DEV u32 ks_shared_walk_lane(const ks_run_pair &P, Shared shared) {
+    u32 cnt = 0, from = 0;
+    for (u32 i = 0; i < P.nw && from < P.ns; i++) {
+        const u64 h = P.wh[i];
+        from += ks_lower_bound_u64(P.sh + from, P.ns - from, h);
+        if (from < P.ns && P.sh[from] == h) {
+            shared(P.walk_q ? i : from, cnt);
+            cnt++;
+        }
+    }
+    return cnt;
+}
+// One wave walks (all 64 lanes enter), 64 hashes of the walked run per chunk, loaded coalesced; every lane searches the whole
+// other run for its own.  chunk(this lane's hash is shared, its position, the ballot of the lanes that share, shared hashes
+// before the chunk) once per chunk: lane order is ascending hash order.  Returns the count (uniform).
+template <typename Chunk> KS_DEV u32 ks_shared_walk_wave(const ks_run_pair &P, u32 lane, Chunk chunk) {
+    u32 cnt = 0;
+    for (u32 c = 0; c < P.nw; c += 64) {
+        const u32 i = c + lane;
+        bool found = false;
+        u32 at = 0;
+        if (i < P.nw) {
+            const u64 h = P.wh[i];
+            at = ks_lower_bound_u64(P.sh, P.ns, h);
+            found = at < P.ns && P.sh[at] == h;
+        }
+        const u64 m = __ballot(found);
+        chunk(found, P.walk_q ? i : at, m, cnt);
+        cnt += (u32)__popcll((long long)m);
+    }
+    return cnt;
+}
 
 // Block-wide exclusive scan; `smem` must hold (blockDim.x/64 + 1) u32.  Returns the exclusive
 // prefix of v; *total receives the block sum.  Contains three __syncthreads().

@@ -4,8 +4,8 @@
 //
 // Hit rows are ordered by (qid, tid), so a query's rows are one contiguous segment (as in ks_best.hip).
 //   incidence  an exclusive scan of the intersect column gives every row its slice of one u32 array; one pass over the rows (a lane
-//              per short row, a wave per row with |q| + |t| above GA_CUT: the walk-the-shorter / search-the-longer loops of
-//              ks_signif.hip) writes the positions INSIDE q's sketch of the hashes the row shares with its target, ascending.  The
+//              per short row, a wave per row with |q| + |t| above GA_CUT: ks_shared_walk_lane / _wave, as in ks_signif.hip)
+//              writes the positions INSIDE q's sketch of the hashes the row shares with its target, ascending.  The
 //              pass counts what it writes: another count than the row's intersect means hits and sketches do not belong together.
 //              A row never writes outside its slice, and a row whose list is not whole starts dead (count 0): the rounds only
 //              ever read lists that are complete.  The lane of a segment's first row lists the segment for one of:
@@ -19,7 +19,7 @@
 //              count reaches the best fresh count known — counts only fall, so a stale count is an upper bound and every
 //              other row cannot win; a row whose count fell below min_unique is dead for good.  The winner is the same as with
 //              every row recounted every round: the key holds the row, so the maximum is unique.
-//   move       keep flags -> one-launch exclusive scan -> the scatter of ks_best.hip (ks_hits_move_ranked) with the three columns.
+//   move       ks_hits_select_tail (ks_best.hip): keep flags -> one-launch exclusive scan -> ks_hits_move_ranked with the three columns.
 // No look-back, no spin, no dependency between workgroups: every loop is bounded by the segment's rows or a list's length.
 // KS_DEBUG_GATHER_PATH = 1 every segment by a wave (where the bitmap fits GA_WAVE_BITS), 2 by a workgroup, 3 by a workgroup
 // with GA_LIVE_BITS_SMALL LDS positions — the tests reach the streamed bitmap with a few hundred hashes.
@@ -49,14 +49,7 @@ struct ga_in {
     u64 *weighted;
 };
 
-KS_DEV void ga_bad(unsigned long long *bad, u32 r, u32 why) { atomicMin(&bad[why], (unsigned long long)r); }
-// a listed segment: (first row, rows); list[0] counts, also past `cap`
-KS_DEV void ga_seg_push(u32 *list, u32 cap, u32 b, u32 len) {
-    const u32 i = atomicAdd(&list[0], 1u);
-    if (i < cap) { list[1 + 2 * i] = b; list[2 + 2 * i] = len; }
-}
 KS_DEV u64 ga_key(u32 count, u32 row) { return ((u64)count << 32) | (u32)~row; }
-KS_DEV u32 ga_readfirst(u32 v) { return (u32)__builtin_amdgcn_readfirstlane((int)v); }
 // the lanes of one wave have written LDS that its other lanes read next (the LDS operations of a wave execute in order)
 KS_DEV void ga_wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
@@ -71,66 +64,39 @@ __global__ __launch_bounds__(256) void k_ga_rows(ga_in G, int mode, u32 seg_cap,
     if (r >= G.n_rows) return;
     G.flags[r] = 0u; G.rank[r] = KS_RANK_NONE; G.cnt[r] = 0u;
     const u32 q = G.qid[r], t = G.tid[r];
-    if (q >= G.n_q) { ga_bad(bad, r, GA_BAD_ID); return; }
+    if (q >= G.n_q) { ks_first_bad(bad, GA_BAD_ID, r); return; }
     const u64 qb = G.q_off[q];
     const u32 nq = (u32)(G.q_off[q + 1] - qb);
     if (r == 0 || G.qid[r - 1] != q) { // the first row of a segment: where it ends, and which kernel takes it
-        const u32 len = ks_query_row_begin(G.qid + r, G.n_rows - r, q + 1); // (q + 1 <= n_q: no wrap)
+        const u32 len = ks_seg_len(G.qid, G.n_rows, r, q);
         const bool wave = nq <= GA_WAVE_BITS && (mode == 1 || (mode == 0 && len <= GA_WAVE_MAX));
-        ga_seg_push(wave ? wave_segs : wg_segs, seg_cap, r, len);
+        ks_seg_list_push(wave ? wave_segs : wg_segs, seg_cap, r, len);
     }
-    if (t >= G.n_t) { ga_bad(bad, r, GA_BAD_ID); return; }
+    if (t >= G.n_t) { ks_first_bad(bad, GA_BAD_ID, r); return; }
     const u64 base = G.off[r];
     const u32 lim = G.isect[r];
-    if (base > G.inc_cap || lim > G.inc_cap - base) { ga_bad(bad, r, GA_BAD_CAP); return; }
-    const u64 tb = G.t_off[t];
-    const u32 nt = (u32)(G.t_off[t + 1] - tb);
-    if ((u64)nq + nt > GA_CUT) { ks_row_list_push(wave_rows, r); return; }
-    // the shorter run is walked, the longer one searched — from where the last search ended: both ascend, and so do the positions
-    const bool walk_q = nq <= nt;
-    const u64 *wh = walk_q ? G.q_hash + qb : G.t_hash + tb, *sh = walk_q ? G.t_hash + tb : G.q_hash + qb;
-    const u32 nw = walk_q ? nq : nt, ns = walk_q ? nt : nq;
-    u32 c = 0, from = 0;
-    for (u32 i = 0; i < nw && from < ns; i++) {
-        const u64 h = wh[i];
-        from += ks_lower_bound_u64(sh + from, ns - from, h);
-        if (from < ns && sh[from] == h) {
-            if (c < lim) G.inc[base + c] = walk_q ? i : from;
-            c++;
-        }
-    }
-    if (c != lim) ga_bad(bad, r, GA_BAD_COUNT);
+    if (base > G.inc_cap || lim > G.inc_cap - base) { ks_first_bad(bad, GA_BAD_CAP, r); return; }
+    const ks_run_pair P = ks_run_pair_of(G.q_off, G.q_hash, G.t_off, G.t_hash, q, t);
+    if ((u64)P.nw + P.ns > GA_CUT) { ks_row_list_push(wave_rows, r); return; }
+    const u32 c = ks_shared_walk_lane(P, [&](u32 pos, u32 before) { if (before < lim) G.inc[base + before] = pos; }); // (ascending)
+    if (c != lim) ks_first_bad(bad, GA_BAD_COUNT, r);
     else G.cnt[r] = lim;
 }
 
-// The listed rows, a wave per row: 64 hashes of the shorter run per step, every lane searches the longer run for its own.
+// The listed rows, a wave per row (ks_shared_walk_wave): a lane's place in the list is the shared hashes before its own.
 __global__ __launch_bounds__(256) void k_ga_rows_wave(ga_in G, const u32 *wave_rows, unsigned long long *bad) {
     const u32 lane = threadIdx.x & 63;
     ks_row_list_walk(wave_rows, G.n_rows, [&](u32 r) {
         if (r >= G.n_rows) return; // (k_ga_rows lists rows below it, with ids in range and a slice inside inc)
-        const u32 q = G.qid[r], t = G.tid[r];
-        const u64 qb = G.q_off[q], tb = G.t_off[t], base = G.off[r];
-        const u32 nq = (u32)(G.q_off[q + 1] - qb), nt = (u32)(G.t_off[t + 1] - tb), lim = G.isect[r];
-        const bool walk_q = nq <= nt;
-        const u64 *wh = walk_q ? G.q_hash + qb : G.t_hash + tb, *sh = walk_q ? G.t_hash + tb : G.q_hash + qb;
-        const u32 nw = walk_q ? nq : nt, ns = walk_q ? nt : nq;
-        u32 c = 0;
-        for (u32 s = 0; s < nw; s += 64) {
-            const u32 i = s + lane;
-            bool found = false;
-            u32 at = 0;
-            if (i < nw) {
-                const u64 h = wh[i];
-                at = ks_lower_bound_u64(sh, ns, h);
-                found = at < ns && sh[at] == h;
-            }
-            const u64 m = __ballot(found);
-            const u32 mine = c + ks_lane_lt_count(m);
-            if (found && mine < lim) G.inc[base + mine] = walk_q ? i : at;
-            c += (u32)__popcll((long long)m);
-        }
+        const ks_run_pair P = ks_run_pair_of(G.q_off, G.q_hash, G.t_off, G.t_hash, G.qid[r], G.tid[r]);
+        const u64 base = G.off[r];
+        const u32 lim = G.isect[r];
+        const u32 c = ks_shared_walk_wave(P, lane, [&](bool found, u32 pos, u64 m, u32 before) {
+            const u32 mine = before + ks_lane_lt_count(m);
+            if (found && mine < lim) G.inc[base + mine] = pos;
+        });
         if (lane == 0) {
-            if (c != lim) ga_bad(bad, r, GA_BAD_COUNT);
+            if (c != lim) ks_first_bad(bad, GA_BAD_COUNT, r);
             else G.cnt[r] = lim;
         }
     });
@@ -144,14 +110,13 @@ KS_DEV u32 ga_full_word(u32 w, u32 n) { return (w + 1) * 32u <= n ? ~0u : ((1u <
 // ones here too).  Every live row is recounted in every round: a lane's list is short, and the lanes wait for the longest anyway.
 __global__ __launch_bounds__(256) void k_ga_wave(ga_in G, const u32 *segs, u32 seg_cap) {
     __shared__ u32 s_live[4][GA_WAVE_BITS / 32];
-    const u32 lane = threadIdx.x & 63, n_waves = gridDim.x * (blockDim.x / 64);
+    const u32 lane = threadIdx.x & 63;
     u32 *live = s_live[threadIdx.x >> 6];
-    const u32 n_list = segs[0] < seg_cap ? segs[0] : seg_cap;
-    for (u32 w = blockIdx.x * (blockDim.x / 64) + (threadIdx.x >> 6); w < n_list; w += n_waves) {
-        const u32 b = ga_readfirst(segs[1 + 2 * w]), len = ga_readfirst(segs[2 + 2 * w]);
-        const u32 q = ga_readfirst(G.qid[b]);
+    for (ks_seg_walk seg = ks_seg_list_by_wave(segs, seg_cap); seg.next();) {
+        const u32 b = seg.b, len = seg.len;
+        const u32 q = ks_readfirst(G.qid[b]);
         const u64 qb = G.q_off[q];
-        const u32 nq = ga_readfirst((u32)(G.q_off[q + 1] - qb)); // (<= GA_WAVE_BITS: k_ga_rows lists no other segment here)
+        const u32 nq = ks_readfirst((u32)(G.q_off[q + 1] - qb)); // (<= GA_WAVE_BITS: k_ga_rows lists no other segment here)
         ga_wave_sync(); // (the previous segment's last readers)
         for (u32 i = lane; i < (nq + 31) / 32; i += 64) live[i] = ga_full_word(i, nq);
         ga_wave_sync();
@@ -232,9 +197,8 @@ __global__ __launch_bounds__(256) void k_ga_wg(ga_in G, const u32 *segs, u32 seg
     __shared__ u64 s_red[4];
     __shared__ u32 s_f0;
     const u32 t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const u32 n_list = segs[0] < seg_cap ? segs[0] : seg_cap;
-    for (u32 w = blockIdx.x; w < n_list; w += gridDim.x) {
-        const u32 b = segs[1 + 2 * w], len = segs[2 + 2 * w];
+    for (ks_seg_walk seg = ks_seg_list_by_wg(segs, seg_cap); seg.next();) {
+        const u32 b = seg.b, len = seg.len;
         const u32 q = G.qid[b];
         const u64 qb = G.q_off[q];
         const u32 nq = (u32)(G.q_off[q + 1] - qb);
@@ -307,82 +271,56 @@ __global__ __launch_bounds__(256) void k_ga_wg(ga_in G, const u32 *segs, u32 seg
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------
 static int gather_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *Q, const ks_sketches *T, u32 min_u, u32 max_results, ks_hits *B) {
-    const u64 n64 = H->n_hits;
-    if (n64 >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "gather: 2^32 - 2 or more hit rows");
-    const u32 n = (u32)n64;
-    u64 cap = n; // rows the output can hold
-    if (max_results != 0 && (u64)Q->n_seqs * max_results < cap) cap = (u64)Q->n_seqs * max_results;
-    const size_t na = cap ? (size_t)cap : 1;
-    KS_TRY(ks_alloc(ctx, &B->d_qid, na)); KS_TRY(ks_alloc(ctx, &B->d_tid, na));
-    KS_TRY(ks_alloc(ctx, &B->d_isect, na)); KS_TRY(ks_alloc(ctx, &B->d_nw, na));
-    if (B->has_stats) { KS_TRY(ks_alloc(ctx, &B->d_median2, na)); KS_TRY(ks_alloc(ctx, &B->d_ss, na)); }
-    KS_TRY(ks_alloc(ctx, &B->d_rank, na)); KS_TRY(ks_alloc(ctx, &B->d_src_row, na));
-    KS_TRY(ks_alloc(ctx, &B->d_ga_unique, na)); KS_TRY(ks_alloc(ctx, &B->d_ga_remaining, na)); KS_TRY(ks_alloc(ctx, &B->d_ga_weighted, na));
+    u32 n;
+    u64 cap;
+    KS_TRY(ks_hits_select_plan(ctx, "gather", H, Q, max_results, &n, &cap));
+    KS_TRY(ks_hits_alloc_cols(ctx, B, (size_t)cap, KS_COLS_RANKED | KS_COLS_GATHER));
     if (n == 0) return KS_OK;
     if (Q->n_hashes == 0 || T->n_hashes == 0)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: %llu hit rows, but a sketch set is empty: the inputs do not belong together",
-                       (unsigned long long)n64);
+                       (unsigned long long)n);
 
-    int mode = 0;
-    u32 live_cap = GA_LIVE_BITS;
-    if (const char *f = ks_dbg(ctx, KS_DBG_GATHER_PATH)) { // (tests: every segment one way; 3 = the workgroup path with a small LDS bitmap)
-        const int v = atoi(f);
-        mode = v == 1 ? 1 : (v == 2 || v == 3) ? 2 : 0;
-        if (v == 3) live_cap = GA_LIVE_BITS_SMALL;
-    }
+    bool small; // (tests: every segment one way; 3 = the workgroup path with a small LDS bitmap)
+    const int mode = ks_seg_path_knob(ctx, KS_DBG_GATHER_PATH, &small);
+    const u32 live_cap = small ? GA_LIVE_BITS_SMALL : GA_LIVE_BITS;
     // A search's rows share n_pair_instances hashes in all (a thresholded or best-hits list fewer): the size of the incidence
     // array without a round trip for the scan's total.  A list whose counts sum to more is refused by the row pass (GA_BAD_CAP).
     const u64 inc_cap = H->n_pair_instances;
     const u32 seg_cap = Q->n_seqs < n ? Q->n_seqs : n; // segments there can be
     ks_scratch sc(ctx);
-    u64 *off = nullptr, *weighted = nullptr, *ctl = nullptr;
+    u64 *off = nullptr, *weighted = nullptr;
+    ks_ctl ctl; // [GA_BAD_ID], [GA_BAD_COUNT], [GA_BAD_CAP]: the first such row; [GA_KEPT]: the scan's total
     u32 *inc = nullptr, *cnt = nullptr, *flags = nullptr, *rank = nullptr, *unique = nullptr, *remaining = nullptr, *wave_rows = nullptr,
         *wave_segs = nullptr, *wg_segs = nullptr, *gbits = nullptr;
     KS_TRY(sc.alloc(&off, (size_t)n + 1)); KS_TRY(sc.alloc(&inc, (size_t)inc_cap));
     KS_TRY(sc.alloc(&cnt, (size_t)n)); KS_TRY(sc.alloc(&flags, (size_t)n)); KS_TRY(sc.alloc(&rank, (size_t)n));
     KS_TRY(sc.alloc(&unique, (size_t)n)); KS_TRY(sc.alloc(&remaining, (size_t)n)); KS_TRY(sc.alloc(&weighted, (size_t)n));
     KS_TRY(ks_row_list_alloc(ctx, sc, (size_t)n, &wave_rows));
-    KS_TRY(sc.alloc(&wave_segs, 2 * (size_t)seg_cap + 1)); KS_TRY(sc.alloc(&wg_segs, 2 * (size_t)seg_cap + 1));
+    KS_TRY(ks_seg_list_alloc(ctx, sc, seg_cap, &wave_segs)); KS_TRY(ks_seg_list_alloc(ctx, sc, seg_cap, &wg_segs));
     KS_TRY(sc.alloc(&gbits, (size_t)(Q->n_hashes >> 5) + Q->n_seqs + 2));
-    KS_TRY(sc.alloc(&ctl, 4)); // [GA_BAD_ID], [GA_BAD_COUNT], [GA_BAD_CAP]: the first such row (all ones: none); [GA_KEPT]: the scan's total
-    KS_HIP(ctx, hipMemsetAsync(ctl, 0xff, 3 * sizeof(u64), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(ctl + GA_KEPT, 0, sizeof(u64), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(wave_segs, 0, sizeof(u32), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(wg_segs, 0, sizeof(u32), ctx->stream));
+    KS_TRY(ctl.init(ctx, sc, KS_PIN_GATHER, 3, 1));
 
     KS_TRY(ks_scan_u32_to_u64(ctx, H->d_isect, off, n));
     const ga_in G = {Q->d_offsets, Q->d_hashes, T->d_offsets, T->d_hashes, Q->d_abunds, H->d_qid, H->d_tid, H->d_isect, off, inc, inc_cap,
                      n, Q->n_seqs, T->n_seqs, min_u, max_results, cnt, flags, rank, unique, remaining, weighted};
-    KS_LAUNCH(ctx, "gather_rows", k_ga_rows, (n + 255) / 256, 256, G, mode, seg_cap, wave_rows, wave_segs, wg_segs, (unsigned long long *)ctl);
-    KS_LAUNCH(ctx, "gather_rows_wave", k_ga_rows_wave, GA_ROWS_WAVE_GRID, 256, G, (const u32 *)wave_rows, (unsigned long long *)ctl);
+    KS_LAUNCH(ctx, "gather_rows", k_ga_rows, (n + 255) / 256, 256, G, mode, seg_cap, wave_rows, wave_segs, wg_segs, ctl.words());
+    KS_LAUNCH(ctx, "gather_rows_wave", k_ga_rows_wave, GA_ROWS_WAVE_GRID, 256, G, (const u32 *)wave_rows, ctl.words());
     if (mode != 2) KS_LAUNCH(ctx, "gather_wave", k_ga_wave, GA_WAVE_GRID, 256, G, (const u32 *)wave_segs, seg_cap);
     KS_LAUNCH(ctx, "gather_wg", k_ga_wg, GA_WG_GRID, 256, G, (const u32 *)wg_segs, seg_cap, live_cap, gbits);
-    KS_TRY(ks_scan_u32_inplace(ctx, flags, n, (u32 *)(ctl + GA_KEPT)));
     const ks_gather_cols cols = {unique, remaining, weighted};
-    KS_TRY(ks_hits_move_ranked(ctx, H, n, flags, rank, (u32)cap, B, &cols));
-    u64 *const rb = ctx->h_pin + KS_PIN_GATHER;
-    {
-        ks_fetch_seg f[2];
-        f[0] = ks_fetch_words(ctl, rb, 8);
-        const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
-        KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
-    }
-    KS_TRY(ks_scan_status_check(ctx));
-    if (rb[GA_BAD_ID] != ~0ULL)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: hit row %llu names a query or target beyond the sketch sets (%u queries, %u targets)",
-                       (unsigned long long)rb[GA_BAD_ID], Q->n_seqs, T->n_seqs);
-    if (rb[GA_BAD_COUNT] != ~0ULL)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG,
-                       "gather: hit row %llu does not share `intersect` hashes in these sketches: hits and sketches do not belong together",
-                       (unsigned long long)rb[GA_BAD_COUNT]);
-    if (rb[GA_BAD_CAP] != ~0ULL)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: the intersect column sums to more than the list's %llu matched pairs at hit row %llu",
-                       (unsigned long long)inc_cap, (unsigned long long)rb[GA_BAD_CAP]);
-    if (rb[GA_KEPT] > cap)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: %llu rows kept where at most %llu can be: the rows are not ordered by (qid, tid)",
-                       (unsigned long long)rb[GA_KEPT], (unsigned long long)cap);
-    B->n_hits = rb[GA_KEPT];
-    return KS_OK;
+    return ks_hits_select_tail(ctx, "gather", H, n, flags, rank, cap, &cols, ctl, GA_KEPT, [&]() -> int {
+        if (ctl.bad(GA_BAD_ID))
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: hit row %llu names a query or target beyond the sketch sets (%u queries, %u targets)",
+                           (unsigned long long)ctl[GA_BAD_ID], Q->n_seqs, T->n_seqs);
+        if (ctl.bad(GA_BAD_COUNT))
+            return ks_fail(ctx, KS_ERR_INVALID_ARG,
+                           "gather: hit row %llu does not share `intersect` hashes in these sketches: hits and sketches do not belong together",
+                           (unsigned long long)ctl[GA_BAD_COUNT]);
+        if (ctl.bad(GA_BAD_CAP))
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: the intersect column sums to more than the list's %llu matched pairs at hit row %llu",
+                           (unsigned long long)inc_cap, (unsigned long long)ctl[GA_BAD_CAP]);
+        return KS_OK;
+    }, B);
 }
 
 extern "C" int ks_hits_gather(ks_ctx *ctx, const ks_hits *hits, const ks_sketches *queries, const ks_sketches *targets,
@@ -392,19 +330,13 @@ extern "C" int ks_hits_gather(ks_ctx *ctx, const ks_hits *hits, const ks_sketche
     if (opts) KS_TRY(ks_opts_words_check(ctx, "gather", opts->flags, 0, opts->reserved));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!hits || !queries || !targets || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    if (hits->ctx != ctx || queries->ctx != ctx || targets->ctx != ctx) return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: an input of another context");
-    const ks_params &a = queries->params, &b = targets->params;
-    if (!ks_same_params(a, b))
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: the sketch sets were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)",
-                       a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
+    KS_TRY(ks_inputs_check_ctx(ctx, "gather", hits, queries, targets));
+    KS_TRY(ks_params_check_same(ctx, "gather", "the sketch sets", queries->params, targets->params));
     KS_HIP(ctx, hipSetDevice(ctx->device));
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(queries))); // (the passes read both sets as plain CSRs)
     KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(targets)));
     ks_result<ks_hits> B(ctx, out, ks_hits_free);
-    B->n_pair_instances = hits->n_pair_instances;
-    B->partition_path = hits->partition_path;
-    B->bucket_posting_bytes = hits->bucket_posting_bytes;
-    B->has_stats = hits->has_stats;
+    ks_hits_inherit(B, hits);
     const u32 min_u = opts && opts->min_unique ? opts->min_unique : 1u;
     KS_TRY(gather_run(ctx, hits, queries, targets, min_u, opts ? opts->max_results : 0u, B));
     if (hits->n_hits == 0) KS_TRY(ks_stream_wait(ctx)); // (a dense copy may be queued: the pass is synchronous on return)

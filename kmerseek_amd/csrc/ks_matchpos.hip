@@ -258,14 +258,7 @@ static int mp_run(ks_ctx *ctx, const ks_kmerpos *Q, const ks_kmerpos *T, const k
               n_t, top_step, lo, cnt, ctl);
     KS_TRY(ks_scan_u32_to_u64(ctx, cnt, off, n_q));
     u64 *const rb = ctx->h_pin + KS_PIN_READ; // candidate pairs | longest starts
-    {
-        ks_fetch_seg f[3];
-        f[0] = ks_fetch_words(off + n_q, rb, 2);
-        f[1] = ks_fetch_words(ctl, rb + 1, 2);
-        const int nf = ks_scan_status_seg(ctx, &f[2]) ? 3 : 2;
-        KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
-    }
-    KS_TRY(ks_scan_status_check(ctx));
+    KS_TRY(ks_stream_wait_fetch_scans(ctx, {ks_fetch_words(off + n_q, rb, 2), ks_fetch_words(ctl, rb + 1, 2)}));
     const u64 n_cand = rb[0];
     const u32 max_qs = ((const u32 *)(rb + 1))[0], max_ts = ((const u32 *)(rb + 1))[1];
     // the sort's scratch goes back; the value column of the sorted table stays (the passes end in one of the pairs, or — one
@@ -325,14 +318,7 @@ static int mp_run(ks_ctx *ctx, const ks_kmerpos *Q, const ks_kmerpos *T, const k
                   M->d_qstart, M->d_tstart, M->d_qlo, M->d_qhi, M->d_tlo, M->d_thi, ctl + 2,
                   s + 1 == n_slices ? M->d_row_offsets + n_rows : (u64 *)nullptr);
     }
-    {
-        ks_fetch_seg f[3];
-        f[0] = ks_fetch_words(base + n_slices, rb, 2);
-        f[1] = ks_fetch_words(ctl + 2, rb + 1, 1);
-        const int nf = ks_scan_status_seg(ctx, &f[2]) ? 3 : 2;
-        KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
-    }
-    KS_TRY(ks_scan_status_check(ctx));
+    KS_TRY(ks_stream_wait_fetch_scans(ctx, {ks_fetch_words(base + n_slices, rb, 2), ks_fetch_words(ctl + 2, rb + 1, 1)}));
     if (*(const u32 *)(rb + 1) != 0)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "match positions: a hit row shares no k-mer in the tables: hits and tables do not belong together");
     M->n_pairs = rb[0];
@@ -346,11 +332,8 @@ extern "C" int ks_match_positions(ks_ctx *ctx, const ks_kmerpos *q_pos, const ks
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!q_pos || !t_pos || !hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    if (q_pos->ctx != ctx || t_pos->ctx != ctx || hits->ctx != ctx) return ks_fail(ctx, KS_ERR_INVALID_ARG, "match positions: an input of another context");
-    const ks_params &a = q_pos->params, &b = t_pos->params;
-    if (!ks_same_params(a, b))
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "match positions: the tables were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)",
-                       a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
+    KS_TRY(ks_inputs_check_ctx(ctx, "match positions", q_pos, t_pos, hits));
+    KS_TRY(ks_params_check_same(ctx, "match positions", "the tables", q_pos->params, t_pos->params));
     KS_HIP(ctx, hipSetDevice(ctx->device));
     ks_result<ks_matchpos> M(ctx, out, ks_matchpos_free);
     M->params = q_pos->params;

@@ -221,16 +221,21 @@ int ks_scan_status_fetch(ks_ctx *ctx) {
     KS_HIP(ctx, hipMemcpyAsync(ctx->h_pin + KS_PIN_SCAN, ctx->scan_ticket + 1, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
     return KS_OK;
 }
-bool ks_scan_status_seg(ks_ctx *ctx, ks_fetch_seg *out) {
-    if (!ctx->scan_ticket) return false;
-    *out = ks_fetch_words(ctx->scan_ticket + 1, ctx->h_pin + KS_PIN_SCAN, 1);
-    return true;
-}
 int ks_scan_status_check(ks_ctx *ctx) {
     if (!ctx->scan_ticket || *(u32 *)(ctx->h_pin + KS_PIN_SCAN) == 0) return KS_OK;
     *(u32 *)(ctx->h_pin + KS_PIN_SCAN) = 0;
     (void)hipMemsetAsync(ctx->scan_ticket + 1, 0, sizeof(u32), ctx->stream);
     return ks_fail(ctx, KS_ERR_HIP, "scan: look-back gave up waiting for a predecessor tile");
+}
+
+int ks_stream_wait_fetch_scans(ks_ctx *ctx, std::initializer_list<ks_fetch_seg> segs) {
+    if (segs.size() >= KS_FETCH_MAX) return ks_fail(ctx, KS_ERR_INVALID_ARG, "too many fetch segments");
+    ks_fetch_seg f[KS_FETCH_MAX];
+    int n = 0;
+    for (const ks_fetch_seg &s : segs) f[n++] = s;
+    if (ctx->scan_ticket) f[n++] = ks_fetch_words(ctx->scan_ticket + 1, ctx->h_pin + KS_PIN_SCAN, 1);
+    KS_TRY(ks_stream_wait_fetch(ctx, f, n));
+    return ks_scan_status_check(ctx);
 }
 
 int ks_scan_u32_to_u64(ks_ctx *ctx, const u32 *in, u64 *out, u64 n) {

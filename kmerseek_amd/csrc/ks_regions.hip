@@ -189,13 +189,7 @@ static int rg_run(ks_ctx *ctx, const ks_matchpos *M, u32 min_kmers, u32 max_gap,
                   ksize, bias, min_kmers, kept, T);
     }
     u64 *const rb = ctx->h_pin + KS_PIN_REGIONS;
-    {
-        ks_fetch_seg f[2];
-        f[0] = ks_fetch_words(kept, rb, 2);
-        const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
-        KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
-    }
-    KS_TRY(ks_scan_status_check(ctx));
+    KS_TRY(ks_stream_wait_fetch_scans(ctx, {ks_fetch_words(kept, rb, 2)}));
     const u32 nr = *(const u32 *)rb;
     if (nr > n) return ks_fail(ctx, KS_ERR_HIP, "internal error: %u regions of %llu pairs", nr, (unsigned long long)n);
     if (nr == 0) return rg_empty(ctx, R);
@@ -238,7 +232,7 @@ extern "C" int ks_match_regions(ks_ctx *ctx, const ks_matchpos *mp, const ks_reg
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!mp || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    if (mp->ctx != ctx) return ks_fail(ctx, KS_ERR_INVALID_ARG, "match regions: an input of another context");
+    KS_TRY(ks_inputs_check_ctx(ctx, "match regions", mp));
     KS_HIP(ctx, hipSetDevice(ctx->device));
     ks_result<ks_regions> R(ctx, out, ks_regions_free);
     KS_TRY(rg_run(ctx, mp, opts ? opts->min_kmers : 0, opts ? opts->max_gap : 0, R));

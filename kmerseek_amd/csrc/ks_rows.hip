@@ -297,6 +297,13 @@ int ks_row_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t n_rows, u32 **list) {
     KS_HIP(ctx, hipMemsetAsync(*list, 0, sizeof(u32), ctx->stream));
     return KS_OK;
 }
+int ks_seg_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t cap, u32 **list) { return ks_row_list_alloc(ctx, sc, 2 * cap, list); }
+int ks_seg_path_knob(const ks_ctx *ctx, int dbg_id, bool *small) {
+    const char *f = ks_dbg(ctx, dbg_id);
+    const int v = f ? atoi(f) : 0;
+    *small = v == 3;
+    return v == 1 ? 1 : (v == 2 || v == 3) ? 2 : 0;
+}
 
 // Behind the row pass of one attempt and before its wait: the statistics into H's columns (Q.stats) and the rows that pass
 // the containment test into F (Q.min_c > 0).  The kernels take the row count from the device (ticket[2]; an attempt with more
@@ -327,9 +334,8 @@ static int se_rows_post(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits *F
         KS_LAUNCH(ctx, "rows_keep", k_rows_keep, g, 256, in, n_rows_dev, rows_cap, (const u64 *)q->d_offsets, counts, q->n_seqs, Q.min_c,
                   flags);
         KS_TRY(ks_scan_u32_inplace(ctx, flags, rows_cap, ticket + 3));
-        KS_TRY(ks_alloc(ctx, &F->d_qid, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_tid, rows_cap));
-        KS_TRY(ks_alloc(ctx, &F->d_isect, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_nw, rows_cap));
-        if (Q.stats) { KS_TRY(ks_alloc(ctx, &F->d_median2, rows_cap)); KS_TRY(ks_alloc(ctx, &F->d_ss, rows_cap)); }
+        F->has_stats = Q.stats;
+        KS_TRY(ks_hits_alloc_cols(ctx, F, rows_cap, 0));
         KS_LAUNCH(ctx, "rows_filter", k_rows_filter, g, 256, in, n_rows_dev, rows_cap, (const u64 *)q->d_offsets, counts, q->n_seqs, Q.min_c,
                   (const u32 *)flags, F->d_qid, F->d_tid, F->d_isect, F->d_nw, F->d_median2, F->d_ss);
     }
@@ -365,13 +371,7 @@ static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F,
                   (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, pf_ticket + 2,
                   (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
         if (post) KS_TRY(se_rows_post(ctx, Q, H, &F, pk, (u32)rows_cap, pf_ticket, sc));
-        {
-            ks_fetch_seg f[2];
-            f[0] = ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4); // ticket pair + row count + kept count
-            const int nf = ks_scan_status_seg(ctx, &f[1]) ? 2 : 1;
-            KS_TRY(ks_stream_wait_fetch(ctx, f, nf));
-        }
-        KS_TRY(ks_scan_status_check(ctx));
+        KS_TRY(ks_stream_wait_fetch_scans(ctx, {ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4)})); // ticket pair + row count + kept count
         bool gave_up = pin[1] != 0;
         if (ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY) && !ctx->rows_use_ticket) gave_up = true; // (tests)
         if (gave_up) {
@@ -400,15 +400,8 @@ static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F,
     return KS_OK;
 }
 
-static int se_no_hits(ks_ctx *ctx, ks_hits *H) {
-    KS_TRY(ks_alloc(ctx, &H->d_qid, 1)); KS_TRY(ks_alloc(ctx, &H->d_tid, 1));
-    KS_TRY(ks_alloc(ctx, &H->d_isect, 1)); KS_TRY(ks_alloc(ctx, &H->d_nw, 1));
-    if (H->has_stats) { KS_TRY(ks_alloc(ctx, &H->d_median2, 1)); KS_TRY(ks_alloc(ctx, &H->d_ss, 1)); }
-    return KS_OK;
-}
-
 int ks_search_rows(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, const u64 *pk) {
-    if (Q.n_pairs == 0) return se_no_hits(ctx, H);
+    if (Q.n_pairs == 0) return ks_hits_alloc_cols(ctx, H, 0, 0);
     ks_hits F; // the filtered columns (Q.min_c > 0) until they replace H's
     memset(&F, 0, sizeof F);
     const int st = se_rows_run(ctx, Q, H, F, pk);

@@ -166,69 +166,37 @@ struct sg_rows_in {
     u32 n_rows, n_q, n_t;
 };
 
-// bad[why] = the first row that cannot be right for that reason
-KS_DEV void sg_bad(unsigned long long *bad, u32 r, u32 why) { atomicMin(&bad[why], (unsigned long long)r); }
-
 // A lane per row.  mode: 0 every row here, 1 every row to the wave kernel, 2 by length.  wave_rows[0] counts the listed rows.
 __global__ __launch_bounds__(256) void k_sg_rows(sg_rows_in R, int mode, double *prob, double *tfidf, u32 *wave_rows, unsigned long long *bad) {
 #pragma clang fp contract(off)
     const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R.n_rows) return;
     const u32 q = R.qid[r], t = R.tid[r];
-    if (q >= R.n_q || t >= R.n_t) { sg_bad(bad, r, SG_BAD_ID); prob[r] = 0.0; tfidf[r] = 0.0; return; }
-    const u64 qb = R.q_off[q], tb = R.t_off[t];
-    const u32 nq = (u32)(R.q_off[q + 1] - qb), nt = (u32)(R.t_off[t + 1] - tb);
-    if (mode == 1 || (mode == 2 && (u64)nq + nt > SG_CUT)) { ks_row_list_push(wave_rows, r); return; }
-    // the shorter run is walked, the longer one searched — from where the last search ended: both ascend
-    const bool walk_q = nq <= nt;
-    const u64 *wh = walk_q ? R.q_hash + qb : R.t_hash + tb, *sh = walk_q ? R.t_hash + tb : R.q_hash + qb;
-    const u32 nw = walk_q ? nq : nt, ns = walk_q ? nt : nq;
+    if (q >= R.n_q || t >= R.n_t) { ks_first_bad(bad, SG_BAD_ID, r); prob[r] = 0.0; tfidf[r] = 0.0; return; }
+    const ks_run_pair P = ks_run_pair_of(R.q_off, R.q_hash, R.t_off, R.t_hash, q, t);
+    if (mode == 1 || (mode == 2 && (u64)P.nw + P.ns > SG_CUT)) { ks_row_list_push(wave_rows, r); return; }
     double po = 0.0, tf = 0.0;
-    u32 cnt = 0, from = 0;
-    for (u32 i = 0; i < nw && from < ns; i++) {
-        const u64 h = wh[i];
-        from += ks_lower_bound_u64(sh + from, ns - from, h);
-        if (from < ns && sh[from] == h) {
-            const u64 p = qb + (walk_q ? i : from); // the QUERY posting: the weights are its
-            po += R.pw[p];
-            tf += R.tw[p];
-            cnt++;
-        }
-    }
-    if (cnt != R.isect[r]) sg_bad(bad, r, SG_BAD_COUNT);
+    const u32 cnt = ks_shared_walk_lane(P, [&](u32 pos, u32) { // the QUERY posting: the weights are its
+        po += R.pw[P.qb + pos];
+        tf += R.tw[P.qb + pos];
+    });
+    if (cnt != R.isect[r]) ks_first_bad(bad, SG_BAD_COUNT, r);
     prob[r] = po; tfidf[r] = tf;
 }
 
-// The listed rows, a wave per row (ks_row_list_walk).  Each chunk of 64 hashes of the shorter run is loaded coalesced, every lane
-// searches the longer run for its hash, and the shared ones' terms are added in lane order: ascending hash.
+// The listed rows, a wave per row (ks_row_list_walk, ks_shared_walk_wave): the terms of a chunk's shared hashes are added in lane
+// order: ascending hash.
 __global__ __launch_bounds__(256) void k_sg_rows_wave(sg_rows_in R, const u32 *wave_rows, double *prob, double *tfidf, unsigned long long *bad) {
     const u32 lane = threadIdx.x & 63;
     ks_row_list_walk(wave_rows, R.n_rows, [&](u32 r) {
-        const u32 q = R.qid[r], t = R.tid[r]; // (in range: k_sg_rows lists no other row)
-        const u64 qb = R.q_off[q], tb = R.t_off[t];
-        const u32 nq = (u32)(R.q_off[q + 1] - qb), nt = (u32)(R.t_off[t + 1] - tb);
-        const bool walk_q = nq <= nt;
-        const u64 *wh = walk_q ? R.q_hash + qb : R.t_hash + tb, *sh = walk_q ? R.t_hash + tb : R.q_hash + qb;
-        const u32 nw = walk_q ? nq : nt, ns = walk_q ? nt : nq;
+        const ks_run_pair P = ks_run_pair_of(R.q_off, R.q_hash, R.t_off, R.t_hash, R.qid[r], R.tid[r]); // (in range: k_sg_rows lists no other row)
         double po = 0.0, tf = 0.0;
-        u32 cnt = 0;
-        for (u32 c = 0; c < nw; c += 64) {
-            const u32 i = c + lane;
-            bool found = false;
-            u32 at = 0;
-            if (i < nw) {
-                const u64 h = wh[i];
-                at = ks_lower_bound_u64(sh, ns, h);
-                found = at < ns && sh[at] == h;
-            }
-            const u64 p = qb + (walk_q ? i : at);
-            const double x = found ? R.pw[p] : 0.0, y = found ? R.tw[p] : 0.0;
-            const u64 m = __ballot(found);
-            cnt += (u32)__popcll((long long)m);
+        const u32 cnt = ks_shared_walk_wave(P, lane, [&](bool found, u32 pos, u64 m, u32) {
+            const double x = found ? R.pw[P.qb + pos] : 0.0, y = found ? R.tw[P.qb + pos] : 0.0;
             ks_wave_add_ordered(m, po, x, tf, y);
-        }
+        });
         if (lane == 0) {
-            if (cnt != R.isect[r]) sg_bad(bad, r, SG_BAD_COUNT);
+            if (cnt != R.isect[r]) ks_first_bad(bad, SG_BAD_COUNT, r);
             prob[r] = po; tfidf[r] = tf;
         }
     });
@@ -240,7 +208,7 @@ static int signif_run(ks_ctx *ctx, const ks_sketches *Q, const ks_sketches *T, c
     S->n_rows = n_rows;
     KS_TRY(ks_alloc(ctx, &S->d_prob, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &S->d_tfidf, (size_t)n_rows));
     if (n_rows == 0) return KS_OK;
-    if (n_rows >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "significance: 2^32 or more hit rows");
+    if (n_rows >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "significance: 2^32 - 2 or more hit rows");
     if (Q->n_hashes == 0 || T->n_hashes == 0)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: %llu hit rows, but a sketch set is empty: the inputs do not belong together",
                        (unsigned long long)n_rows);
@@ -248,13 +216,11 @@ static int signif_run(ks_ctx *ctx, const ks_sketches *Q, const ks_sketches *T, c
     ks_scratch sc(ctx);
     double *pw = nullptr, *tw = nullptr, *idf = nullptr;
     u32 *wave_rows = nullptr; // the rows of k_sg_rows_wave
-    u64 *ctl = nullptr; // [SG_BAD_ID], [SG_BAD_COUNT]: the first such row (all ones: none); [SG_BAD_CORPUS]: a query hash outside the query corpus
+    ks_ctl ctl; // [SG_BAD_ID], [SG_BAD_COUNT]: the first such row; [SG_BAD_CORPUS]: a query hash outside the query corpus
     KS_TRY(sc.alloc(&pw, (size_t)Q->n_hashes)); KS_TRY(sc.alloc(&tw, (size_t)Q->n_hashes));
     KS_TRY(sc.alloc(&idf, (size_t)CT->max_doc_freq + 1));
     KS_TRY(ks_row_list_alloc(ctx, sc, (size_t)n_rows, &wave_rows));
-    KS_TRY(sc.alloc(&ctl, 3));
-    KS_HIP(ctx, hipMemsetAsync(ctl, 0xff, 2 * sizeof(u64), ctx->stream));
-    KS_HIP(ctx, hipMemsetAsync(ctl + SG_BAD_CORPUS, 0, sizeof(u64), ctx->stream));
+    KS_TRY(ctl.init(ctx, sc, KS_PIN_SIGNIF, 2, 1));
     // smooth idf over the document frequencies the target corpus holds: libm's log, here on the host
     std::vector<double> h_idf((size_t)CT->max_doc_freq + 1);
     for (size_t d = 0; d < h_idf.size(); d++) h_idf[d] = std::log(((double)1 + (double)T->n_seqs) / ((double)1 + (double)d)) + 1.0;
@@ -263,28 +229,27 @@ static int signif_run(ks_ctx *ctx, const ks_sketches *Q, const ks_sketches *T, c
     const sg_table tq = {CQ->d_hash, CQ->d_sum, CQ->d_df, (u32)CQ->n_hashes, (double)CQ->total};
     const sg_table tt = {CT->d_hash, CT->d_sum, CT->d_df, (u32)CT->n_hashes, (double)CT->total};
     KS_LAUNCH(ctx, "signif_weights", k_sg_weights, (Q->n_seqs + 3) / 4, 256, (const u64 *)Q->d_offsets, (const u64 *)Q->d_hashes,
-              (const u32 *)Q->d_abunds, Q->n_seqs, tq, tt, (const double *)idf, pw, tw, (unsigned long long *)(ctl + SG_BAD_CORPUS));
+              (const u32 *)Q->d_abunds, Q->n_seqs, tq, tt, (const double *)idf, pw, tw, ctl.words() + SG_BAD_CORPUS);
     int mode = 2;
     if (const char *f = ks_dbg(ctx, KS_DBG_SIGNIF_WAVE_ROWS)) mode = atoi(f) != 0 ? 1 : 0; // (tests: small inputs take both paths)
     const sg_rows_in R = {Q->d_offsets, Q->d_hashes, T->d_offsets, T->d_hashes, pw, tw, H->d_qid, H->d_tid, H->d_isect,
                           (u32)n_rows, Q->n_seqs, T->n_seqs};
     KS_LAUNCH(ctx, "signif_rows", k_sg_rows, (u32)((n_rows + 255) / 256), 256, R, mode, S->d_prob, S->d_tfidf, wave_rows,
-              (unsigned long long *)ctl);
+              ctl.words());
     if (mode != 0)
         KS_LAUNCH(ctx, "signif_rows_wave", k_sg_rows_wave, SG_WAVE_GRID, 256, R, (const u32 *)wave_rows, S->d_prob, S->d_tfidf,
-                  (unsigned long long *)ctl);
-    u64 *const rb = ctx->h_pin + KS_PIN_SIGNIF;
-    const ks_fetch_seg f = ks_fetch_words(ctl, rb, 6);
+                  ctl.words());
+    const ks_fetch_seg f = ctl.fetch();
     KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
-    if (rb[SG_BAD_ID] != ~0ULL)
+    if (ctl.bad(SG_BAD_ID))
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: hit row %llu names a query or target beyond the sketch sets (%u queries, %u targets)",
-                       (unsigned long long)rb[SG_BAD_ID], Q->n_seqs, T->n_seqs);
-    if (rb[SG_BAD_CORPUS] != 0)
+                       (unsigned long long)ctl[SG_BAD_ID], Q->n_seqs, T->n_seqs);
+    if (ctl[SG_BAD_CORPUS] != 0)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: a query hash is not in the query corpus: the corpus was built from another set");
-    if (rb[SG_BAD_COUNT] != ~0ULL)
+    if (ctl.bad(SG_BAD_COUNT))
         return ks_fail(ctx, KS_ERR_INVALID_ARG,
                        "significance: hit row %llu does not share `intersect` hashes in these sketches: hits and sketches do not belong together",
-                       (unsigned long long)rb[SG_BAD_COUNT]);
+                       (unsigned long long)ctl[SG_BAD_COUNT]);
     return KS_OK;
 }
 
@@ -295,12 +260,8 @@ extern "C" int ks_hits_significance(ks_ctx *ctx, const ks_sketches *queries, con
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (!queries || !targets || !q_corpus || !t_corpus || !hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    if (queries->ctx != ctx || targets->ctx != ctx || q_corpus->ctx != ctx || t_corpus->ctx != ctx || hits->ctx != ctx)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: an input of another context");
-    const ks_params &a = queries->params, &b = targets->params;
-    if (!ks_same_params(a, b))
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "significance: the sketch sets were made with different parameters (k %u / %u, scaled %u / %u, moltype %u / %u)",
-                       a.ksize, b.ksize, a.scaled, b.scaled, a.moltype, b.moltype);
+    KS_TRY(ks_inputs_check_ctx(ctx, "significance", queries, targets, q_corpus, t_corpus, hits));
+    KS_TRY(ks_params_check_same(ctx, "significance", "the sketch sets", queries->params, targets->params));
     const struct { const ks_corpus *c; const ks_sketches *s; const char *side; } pairs[2] = {{q_corpus, queries, "query"}, {t_corpus, targets, "target"}};
     for (const auto &p : pairs) {
         if (p.c->n_docs != p.s->n_seqs)

@@ -205,6 +205,70 @@ def test_wide_abundances(monkeypatch):
         _on_every_path(monkeypatch, c, hits, h, dQ, dT, ref)
 
 
+# ---- the edges of the shared-hash walk (ks_shared_walk_lane / _wave: the significance pass's walk) -----------------------------------
+def _same(a, b):
+    return len(a) == len(b) and all(x.dtype == y.dtype and np.array_equal(x, y) for x, y in zip(a, b))
+
+
+def _searched(c, Q, T):
+    """(the uploaded sets, the search's hits, their host columns) — the rows are ref_join's"""
+    dQ, dT = _upload(c, Q), _upload(c, T)
+    hits = c.search(c.index_build(dT), dQ)
+    h = hits.to_host()
+    for a, b in zip(h, cs.ref_join(T, Q)):
+        assert np.array_equal(a, b)
+    return dQ, dT, hits, h
+
+
+def test_row_length_edges(monkeypatch):
+    """crafted_sketches.row_lengths: query 0 (193 hashes) shares 1, 2, 63, 64, 65, 127, 128, 129, 192 and 193 hashes with its ten
+    targets — the count at every chunk edge, a miscount is a refusal; query 1 (64 hashes) is the walked run of both its rows,
+    one by a lane (|q| + |t| = 128) and one by a wave (129), and its second pick counts positions of both."""
+    name, k, scaled, mol, T, Q = cs.family("row_lengths")
+    assert (k, scaled, mol) == (10, 1, "protein")
+    with ks.Context(0, follow_debug_env=True) as c:
+        dQ, dT, hits, h = _searched(c, Q, T)
+        assert h[0].tolist() == [0] * 10 + [1, 1] and h[2].tolist() == list(cs.ROW_SHARED) + [40, 41]
+        sizes_q, sizes_t = np.diff(Q[0]).astype(np.int64), np.diff(T[0]).astype(np.int64)
+        assert [int(sizes_q[1] + sizes_t[t]) for t in (10, 11)] == [cs.SG_CUT, cs.SG_CUT + 1] and sizes_q[1] <= sizes_t[10:].min()
+        ref = gather_ref.gather(Q, T, h[0], h[1], h[2])
+        assert _same(ref, gather_ref.gather_sets(Q, T, h[0], h[1], h[2]))
+        # in row order: row 9 explains query 0 at once; query 1 takes row 11 (41 shared) first, then row 10 adds 11
+        assert [x.tolist() for x in ref[:4]] == [[9, 10, 11], [0, 1, 0], [193, 11, 41], [0, 12, 23]]
+        _on_every_path(monkeypatch, c, hits, h, dQ, dT, ref)
+
+
+def _staggered():
+    """One query of 193 hashes h[0 .. 193) and six targets: the windows h[0:65], h[1:65], h[2:65], h[64:193], h[65:193], h[66:193],
+    each with three hashes of its own above every h: target hashes ascend, so a window's hashes sit in the lanes 0 .. of its walk."""
+    h = [2 * (1000 + 7 * i) for i in range(193)]
+    windows = [(0, 65), (1, 65), (2, 65), (64, 193), (65, 193), (66, 193)]
+    ts, th = [], []
+    for t, (a, b) in enumerate(windows):
+        own = [h[-1] + 1 + 2 * (3 * t + j) for j in range(3)]
+        ts += [t] * (b - a + 3); th += h[a:b] + own
+    Q = cs._csr([0] * 193, h, [1 + (i * i) % 13 for i in range(193)], 1)
+    T = cs._csr(ts, th, [1] * len(th), len(windows))
+    cs.check_valid(Q, 1); cs.check_valid(T, 1)
+    return Q, T, windows
+
+
+def test_staggered_windows_around_a_chunk_edge(monkeypatch):
+    """Every row takes the wave walk (|q| + |t| > GA_CUT) and searches the query (|t| < |q|).  The first pick is h[64:193], the
+    second what h[0:65] has left: 64 — one more or less if the position written for lane 63 of a chunk or lane 0 of the next is
+    off by one on either side.  Then nothing is left."""
+    Q, T, windows = _staggered()
+    assert all(n < 193 for n in np.diff(T[0]).tolist())
+    with ks.Context(0, follow_debug_env=True) as c:
+        dQ, dT, hits, h = _searched(c, Q, T)
+        assert h[1].tolist() == [0, 1, 2, 3, 4, 5] and h[2].tolist() == [b - a for a, b in windows] == [65, 64, 63, 129, 128, 127]
+        ref = gather_ref.gather(Q, T, h[0], h[1], h[2])
+        assert _same(ref, gather_ref.gather_sets(Q, T, h[0], h[1], h[2]))
+        assert [x.tolist() for x in ref[:4]] == [[0, 3], [1, 0], [64, 129], [0, 64]]
+        assert ref[4].tolist() == [int(Q[2][:64].sum()), int(Q[2][64:].sum())]
+        _on_every_path(monkeypatch, c, hits, h, dQ, dT, ref)
+
+
 # ---- real data, and inputs from other passes --------------------------------------------------------------------------------------
 def _records(name):
     recs = oracle.read_fasta(os.path.join(GOLDEN, name))
