@@ -623,6 +623,60 @@ int ks_clusters_copy_to_host(ks_ctx *ctx, const ks_clusters *c, uint32_t *label,
                              uint32_t *members, uint32_t *representative);
 void ks_clusters_free(ks_clusters *c);
 
+/* ---- clusters: greedy representative clustering of an all-vs-all hit list ------------------------------------------------ */
+
+/* The connected components chain: on proteins a multi-domain sequence links families that share nothing, and at the thresholds
+ * people use one component swallows the set.  This pass clusters the way CD-HIT's incremental clustering and the greedy
+ * set-cover modes of MMseqs2 / linclust do: around representatives.  Nodes, rows, edges and scores are those of
+ * ks_hits_cluster: row r = (q, t) is an undirected edge iff q != t and score(r) >= threshold, rows of one direction only are
+ * valid, a NaN score is never an edge, -0.0 equals +0.0.
+ *   priority: a total order of the nodes.  With `nodes`: more distinct hashes first, ties to the smaller id; without: the
+ *          smaller id first.
+ *   representatives: the nodes are taken in priority order; a node is a representative iff none of its neighbours of higher
+ *          priority is one.  (The lexicographically first maximal independent set of the graph under that order: unique.)
+ *   assignment: every other node has a representative among its neighbours.  KS_GREEDY_ASSIGN_FIRST joins the one of highest
+ *          priority (CD-HIT's default).  KS_GREEDY_ASSIGN_BEST joins the representative at the other end of the passing row
+ *          with the largest score — rows (v, u) and (u, v) are each a candidate, with their own score; ties go to the
+ *          representative of higher priority.
+ * So every member has a passing row with its representative and no passing row joins two representatives; under
+ * KS_GREEDY_ASSIGN_FIRST a representative also has the highest priority of its cluster (ASSIGN_BEST may prefer the better row
+ * of a representative of lower priority).  No reference tool is restated here: no parity is claimed.
+ * Result: a ks_clusters, read through the accessors above (device-resident, every value an integer):
+ *   label u32[n]                  the node's representative; a representative labels itself
+ *   cluster_id u32[n]             clusters numbered 0 .. n_clusters-1 by ascending representative id
+ *   offsets u64[n_clusters + 1], members u32[n]    the CSR of the clusters in that order, members ascending inside a cluster
+ *   representative u32[n_clusters]   the cluster's representative
+ *   n_edges, n_clusters, largest  as for ks_hits_cluster (n_edges: the rows that passed, self rows and both directions
+ *                                 counted as they occur)
+ *   ks_clusters_n_rounds          the rounds the pass took (a diagnostic: it may depend on the schedule; nothing else does)
+ * The pass runs in rounds: in each, every undecided node that no undecided neighbour of higher priority blocks is decided, and
+ * the edges both of whose ends are still undecided go on to the next round.  The number of rounds is the depth of the
+ * dependency chain — small on real data, n on a path in priority order — so once few edges are live one workgroup finishes all
+ * remaining rounds in one launch (KS_DEBUG_GREEDY_PATH = 1 forces rounds over the whole grid only, 2 that single workgroup
+ * straight after the first round, for the tests).  The result never depends on the path, the launch geometry or the order in
+ * which waves ran.  The input is unchanged and stays valid.
+ * KS_ERR_INVALID_ARG, in the order of ks_hits_cluster (options first, before any device work, also with ctx == NULL): non-zero
+ * flags; an unknown assign mode; an unknown similarity; a NaN threshold; d_score NULL with KS_BEST_SCORE or non-NULL without
+ * it; `nodes` NULL where the key needs sizes; n_nodes that is neither 0 nor the node set's sequence count; then: a qid or tid
+ * >= n; a size of 0 on a row whose key needs it (ks_last_error names the first such row).  One stream; the host looks at the
+ * undecided count once per few rounds.  Scratch comes from the pool: 60 bytes per node, 8 bytes per hit row and 8 bytes per
+ * passing non-self row (the two live-edge lists). */
+#define KS_GREEDY_ASSIGN_FIRST 0u
+#define KS_GREEDY_ASSIGN_BEST  1u
+typedef struct ks_greedy_opts {
+    uint32_t similarity; /* KS_BEST_INTERSECT | _TARGET_CONTAINMENT | _MAX_CONTAINMENT | _JACCARD | _SCORE: the same scores, bit for bit, as ks_hits_best / ks_hits_cluster */
+    uint32_t n_nodes;    /* as in ks_cluster_opts: used only when nodes == NULL; with nodes != NULL it must be 0 or ks_sketches_n_seqs(nodes) */
+    double   threshold;  /* a row is an edge iff score >= threshold (NaN scores never are); NaN threshold: KS_ERR_INVALID_ARG */
+    uint32_t assign;     /* KS_GREEDY_ASSIGN_FIRST | KS_GREEDY_ASSIGN_BEST */
+    uint32_t flags;      /* 0 */
+} ks_greedy_opts;
+int ks_hits_cluster_greedy(ks_ctx *ctx, const ks_hits *hits, const ks_sketches *nodes, const double *d_score,
+                           const ks_greedy_opts *opts, ks_clusters **out);
+/* rounds a ks_hits_cluster_greedy result took; 0 for a ks_hits_cluster result */
+uint32_t ks_clusters_n_rounds(const ks_clusters *c);
+/* live edges at or below which one workgroup finishes the greedy rounds (the tests size an edge list on either side of it) */
+uint32_t ks_debug_greedy_tail_edges(void);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Per-kernel HIP-event timing on ctx's stream.  enable: 0 off; 1 events bracket every launch (~20 us of idle queue

@@ -68,6 +68,14 @@ class ks_cluster_opts(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+KS_GREEDY_ASSIGN_FIRST, KS_GREEDY_ASSIGN_BEST = 0, 1
+
+
+class ks_greedy_opts(C.Structure):
+    _fields_ = [("similarity", C.c_uint32), ("n_nodes", C.c_uint32), ("threshold", C.c_double), ("assign", C.c_uint32),
+                ("flags", C.c_uint32)]
+
+
 class ks_gather_opts(C.Structure):
     _fields_ = [("min_unique", C.c_uint32), ("max_results", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -217,6 +225,9 @@ SIGNATURES = {
     "ks_clusters_device_representative": (_vp, [_vp]),
     "ks_clusters_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ks_clusters_free": (None, [_vp]),
+    "ks_hits_cluster_greedy": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ks_greedy_opts), _pp]),
+    "ks_clusters_n_rounds": (C.c_uint32, [_vp]),
+    "ks_debug_greedy_tail_edges": (C.c_uint32, []),
     "ks_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ks_timing_reset": (C.c_int, [_vp]),
     "ks_timing_get": (C.c_int, [_vp, C.POINTER(ks_kernel_time), C.c_uint32, _u32p]),

@@ -11,6 +11,8 @@
 //             (both once per wave and cluster); sizes scanned to offsets (ks_scan_u32_to_u64), keys sorted stably on the live
 //             bits of the cluster id (ks_radix_sort_keys) -> members
 //   finish    members and representatives unpacked, the largest size by atomicMax; the scalars come back with the one wait
+// compact and finish are ks_clusters_from_labels (ks_common.h): the tail of ks_hits_cluster_greedy (ks_greedy.hip) too, whose
+// labels mark their roots the same way (label[i] == i).
 //
 // The union-find is lock-free on parent u32[n] (0.8 MB at 200k nodes: cache-resident).  Its correctness argument:
 //   * parent[x] <= x always.  parent starts as the identity, and
@@ -41,7 +43,6 @@
 
 #define CL_WAVE_UNIFORM_DEFAULT 0 // the wave-uniform query path did not beat the plain one by more than the noise: behind the knob
 #define CL_HOOK_WG_PER_CU 8 // workgroups of k_cluster_hook per CU: 32 waves, what a CU holds
-enum { CL_BAD_ID = 0, CL_BAD_SIZE = 1, CL_EDGES = 2, CL_CLUSTERS = 3, CL_LARGEST = 4 }; // words of the control block
 
 struct cl_in {
     const u32 *qid, *tid, *isect;
@@ -195,14 +196,52 @@ __global__ __launch_bounds__(256) void k_cluster_finish(u32 n, const u64 *sorted
     if ((threadIdx.x & 63) == 0 && sz) atomicMax(&ctl[CL_LARGEST], (unsigned long long)sz);
 }
 
+int ks_clusters_alloc(ks_ctx *ctx, ks_clusters *K, u32 n) {
+    K->n_nodes = n; K->n_clusters = 0; K->largest = 0; K->n_edges = 0;
+    KS_TRY(ks_alloc(ctx, &K->d_label, (size_t)n)); KS_TRY(ks_alloc(ctx, &K->d_cluster_id, (size_t)n));
+    KS_TRY(ks_alloc(ctx, &K->d_members, (size_t)n)); KS_TRY(ks_alloc(ctx, &K->d_rep, (size_t)n));
+    return ks_alloc(ctx, &K->d_offsets, (size_t)n + 1);
+}
+
+int ks_clusters_from_labels(ks_ctx *ctx, ks_clusters *K, const ks_sketches *N, const ks_label_scratch &W, const ks_ctl &ctl) {
+    const u32 n = K->n_nodes, g_n = (n + 255) / 256;
+    KS_TRY(ks_scan_u32_inplace(ctx, W.root_idx, n, ctl.low32(CL_CLUSTERS)));
+    KS_LAUNCH(ctx, "cluster_ids", k_cluster_ids, g_n, 256, n, (const u32 *)K->d_label, (const u32 *)W.root_idx, bh_set_of(N), K->d_cluster_id, W.sizes, W.rep,
+              W.ka);
+    KS_TRY(ks_scan_u32_to_u64(ctx, W.sizes, K->d_offsets, n));
+    // members: the keys are written in id order, so a STABLE sort on the cluster id alone leaves them ordered by (cluster, id).
+    // LSD passes on the live bits of the id field — not ks_sort_live_keys: its MSD variant partitions on the top bits, and a
+    // giant cluster is one bucket that a single workgroup then sorts (2.2 ms at 200k nodes in one component, DESIGN.md §3.3f; these passes
+    // do not care how the ids are distributed).
+    int shifts[4], ns = 0;
+    for (int sh = 0; sh < ks_key_bits((u64)n - 1); sh += 8) shifts[ns++] = 32 + sh;
+    u64 *sorted = nullptr;
+    KS_TRY(ks_radix_sort_keys(ctx, KS_SORT_PAIRS, W.ka, W.ka, W.kb, n, shifts, ns, &sorted));
+    KS_LAUNCH(ctx, "cluster_finish", k_cluster_finish, g_n, 256, n, (const u64 *)sorted, (const u32 *)W.sizes, (const u64 *)W.rep, K->d_members, K->d_rep,
+              ctl.words());
+    return KS_OK;
+}
+
+int ks_clusters_finish(ks_ctx *ctx, const char *what, ks_clusters *K, const ks_ctl &ctl) {
+    const u32 n = K->n_nodes;
+    if (ctl.bad(CL_BAD_ID))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "%s: hit row %llu names a node beyond the %u nodes of the set", what, (unsigned long long)ctl[CL_BAD_ID], n);
+    if (ctl.bad(CL_BAD_SIZE))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "%s: hit row %llu names an empty sketch: its score divides by 0", what, (unsigned long long)ctl[CL_BAD_SIZE]);
+    if (ctl[CL_CLUSTERS] == 0 || ctl[CL_CLUSTERS] > n || ctl[CL_LARGEST] > n)
+        return ks_fail(ctx, KS_ERR_HIP, "internal error: %llu clusters, the largest of %llu, on %u nodes", (unsigned long long)ctl[CL_CLUSTERS],
+                       (unsigned long long)ctl[CL_LARGEST], n);
+    K->n_edges = ctl[CL_EDGES];
+    K->n_clusters = (u32)ctl[CL_CLUSTERS];
+    K->largest = (u32)ctl[CL_LARGEST];
+    return KS_OK;
+}
+
 static int cluster_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *N, const double *d_score, const ks_cluster_opts *o, ks_clusters *K) {
     const u64 n64 = H->n_hits;
     if (n64 >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "cluster: 2^32 - 2 or more hit rows");
     const u32 n_rows = (u32)n64, n = N ? N->n_seqs : o->n_nodes;
-    K->n_nodes = n; K->n_clusters = 0; K->largest = 0; K->n_edges = 0;
-    KS_TRY(ks_alloc(ctx, &K->d_label, (size_t)n)); KS_TRY(ks_alloc(ctx, &K->d_cluster_id, (size_t)n));
-    KS_TRY(ks_alloc(ctx, &K->d_members, (size_t)n)); KS_TRY(ks_alloc(ctx, &K->d_rep, (size_t)n));
-    KS_TRY(ks_alloc(ctx, &K->d_offsets, (size_t)n + 1));
+    KS_TRY(ks_clusters_alloc(ctx, K, n));
     if (n == 0) {
         if (n_rows) return ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster: hit row 0 names a node beyond the 0 nodes of the set");
         KS_HIP(ctx, hipMemsetAsync(K->d_offsets, 0, sizeof(u64), ctx->stream));
@@ -216,61 +255,44 @@ static int cluster_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *N, cons
     }
 
     ks_scratch sc(ctx);
-    u32 *parent = nullptr, *root_idx = nullptr, *sizes = nullptr;
-    u64 *rep = nullptr, *ka = nullptr, *kb = nullptr;
+    u32 *parent = nullptr;
+    ks_label_scratch W = {};
     ks_ctl ctl; // [CL_BAD_ID], [CL_BAD_SIZE]: the first such row; the three counts
-    KS_TRY(sc.alloc(&parent, (size_t)n)); KS_TRY(sc.alloc(&root_idx, (size_t)n)); KS_TRY(sc.alloc(&sizes, (size_t)n));
-    KS_TRY(sc.alloc(&rep, (size_t)n)); KS_TRY(sc.alloc(&ka, (size_t)n)); KS_TRY(sc.alloc(&kb, (size_t)n));
+    KS_TRY(sc.alloc(&parent, (size_t)n)); KS_TRY(sc.alloc(&W.root_idx, (size_t)n)); KS_TRY(sc.alloc(&W.sizes, (size_t)n));
+    KS_TRY(sc.alloc(&W.rep, (size_t)n)); KS_TRY(sc.alloc(&W.ka, (size_t)n)); KS_TRY(sc.alloc(&W.kb, (size_t)n));
     KS_TRY(ctl.init(ctx, sc, KS_PIN_CLUSTER, 2, 3));
 
     const u32 g_n = (n + 255) / 256;
-    KS_LAUNCH(ctx, "cluster_init", k_cluster_init, g_n, 256, n, parent, sizes, rep);
+    KS_LAUNCH(ctx, "cluster_init", k_cluster_init, g_n, 256, n, parent, W.sizes, W.rep);
     if (n_rows) {
         const cl_in R = {H->d_qid, H->d_tid, H->d_isect, d_score, n_rows, o->similarity, n, o->threshold, bh_set_of(N)};
         const u32 g_rows = (n_rows + 255) / 256, g_max = (u32)ctx->n_cus * CL_HOOK_WG_PER_CU;
         KS_LAUNCH(ctx, "cluster_hook", k_cluster_hook, g_rows < g_max ? g_rows : g_max, 256, R, wave_uniform, parent, ctl.words());
     }
-    KS_LAUNCH(ctx, "cluster_flatten", k_cluster_flatten, g_n, 256, n, (const u32 *)parent, K->d_label, root_idx);
-    KS_TRY(ks_scan_u32_inplace(ctx, root_idx, n, ctl.low32(CL_CLUSTERS)));
-    KS_LAUNCH(ctx, "cluster_ids", k_cluster_ids, g_n, 256, n, (const u32 *)K->d_label, (const u32 *)root_idx, bh_set_of(N), K->d_cluster_id, sizes, rep, ka);
-    KS_TRY(ks_scan_u32_to_u64(ctx, sizes, K->d_offsets, n));
-    // members: the keys are written in id order, so a STABLE sort on the cluster id alone leaves them ordered by (cluster, id).
-    // LSD passes on the live bits of the id field — not ks_sort_live_keys: its MSD variant partitions on the top bits, and a
-    // giant cluster is one bucket that a single workgroup then sorts (2.2 ms at 200k nodes in one component, DESIGN.md §3.3f; these passes
-    // do not care how the ids are distributed).
-    int shifts[4], ns = 0;
-    for (int sh = 0; sh < ks_key_bits((u64)n - 1); sh += 8) shifts[ns++] = 32 + sh;
-    u64 *sorted = nullptr;
-    KS_TRY(ks_radix_sort_keys(ctx, KS_SORT_PAIRS, ka, ka, kb, n, shifts, ns, &sorted));
-    KS_LAUNCH(ctx, "cluster_finish", k_cluster_finish, g_n, 256, n, (const u64 *)sorted, (const u32 *)sizes, (const u64 *)rep, K->d_members, K->d_rep,
-              ctl.words());
+    KS_LAUNCH(ctx, "cluster_flatten", k_cluster_flatten, g_n, 256, n, (const u32 *)parent, K->d_label, W.root_idx);
+    KS_TRY(ks_clusters_from_labels(ctx, K, N, W, ctl));
     KS_TRY(ks_stream_wait_fetch_scans(ctx, {ctl.fetch()}));
-    if (ctl.bad(CL_BAD_ID))
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster: hit row %llu names a node beyond the %u nodes of the set", (unsigned long long)ctl[CL_BAD_ID], n);
-    if (ctl.bad(CL_BAD_SIZE))
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster: hit row %llu names an empty sketch: its score divides by 0", (unsigned long long)ctl[CL_BAD_SIZE]);
-    if (ctl[CL_CLUSTERS] == 0 || ctl[CL_CLUSTERS] > n || ctl[CL_LARGEST] > n)
-        return ks_fail(ctx, KS_ERR_HIP, "internal error: %llu clusters, the largest of %llu, on %u nodes", (unsigned long long)ctl[CL_CLUSTERS],
-                       (unsigned long long)ctl[CL_LARGEST], n);
-    K->n_edges = ctl[CL_EDGES];
-    K->n_clusters = (u32)ctl[CL_CLUSTERS];
-    K->largest = (u32)ctl[CL_LARGEST];
+    return ks_clusters_finish(ctx, "cluster", K, ctl);
+}
+
+int ks_cluster_words_check(ks_ctx *ctx, const char *what, u32 similarity, u32 n_nodes, double threshold, const ks_sketches *nodes,
+                           const double *d_score) {
+    const auto bad = [&](const char *why) { return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "%s options: %s", what, why) : KS_ERR_INVALID_ARG; };
+    if (similarity > KS_BEST_SCORE) return bad("unknown similarity");
+    if (threshold != threshold) return bad("the threshold is NaN");
+    if (similarity == KS_BEST_SCORE && !d_score) return bad("KS_BEST_SCORE needs a score column");
+    if (similarity != KS_BEST_SCORE && d_score) return bad("a score column is only read with KS_BEST_SCORE");
+    const bool need_sizes = similarity == KS_BEST_TARGET_CONTAINMENT || similarity == KS_BEST_MAX_CONTAINMENT || similarity == KS_BEST_JACCARD;
+    if (need_sizes && !nodes) return bad("this similarity needs the node sketches");
+    if (nodes && n_nodes != 0 && n_nodes != nodes->n_seqs) return bad("n_nodes is not the node set's sequence count");
     return KS_OK;
 }
 
 // the option words and what they ask of the other arguments; ctx may be NULL
 static int cluster_opts_check(ks_ctx *ctx, const ks_cluster_opts *o, const ks_sketches *nodes, const double *d_score) {
-    const auto bad = [&](const char *why) { return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster options: %s", why) : KS_ERR_INVALID_ARG; };
-    if (!o) return bad("NULL");
+    if (!o) return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "cluster options: NULL") : KS_ERR_INVALID_ARG;
     KS_TRY(ks_opts_words_check(ctx, "cluster", o->flags, 0, o->reserved));
-    if (o->similarity > KS_BEST_SCORE) return bad("unknown similarity");
-    if (o->threshold != o->threshold) return bad("the threshold is NaN");
-    if (o->similarity == KS_BEST_SCORE && !d_score) return bad("KS_BEST_SCORE needs a score column");
-    if (o->similarity != KS_BEST_SCORE && d_score) return bad("a score column is only read with KS_BEST_SCORE");
-    const bool need_sizes = o->similarity == KS_BEST_TARGET_CONTAINMENT || o->similarity == KS_BEST_MAX_CONTAINMENT || o->similarity == KS_BEST_JACCARD;
-    if (need_sizes && !nodes) return bad("this similarity needs the node sketches");
-    if (nodes && o->n_nodes != 0 && o->n_nodes != nodes->n_seqs) return bad("n_nodes is not the node set's sequence count");
-    return KS_OK;
+    return ks_cluster_words_check(ctx, "cluster", o->similarity, o->n_nodes, o->threshold, nodes, d_score);
 }
 
 extern "C" int ks_hits_cluster(ks_ctx *ctx, const ks_hits *hits, const ks_sketches *nodes, const double *d_score, const ks_cluster_opts *opts,
@@ -292,6 +314,7 @@ extern "C" uint32_t ks_clusters_n_nodes(const ks_clusters *c) { return c ? c->n_
 extern "C" uint32_t ks_clusters_n_clusters(const ks_clusters *c) { return c ? c->n_clusters : 0; }
 extern "C" uint64_t ks_clusters_n_edges(const ks_clusters *c) { return c ? c->n_edges : 0; }
 extern "C" uint32_t ks_clusters_largest(const ks_clusters *c) { return c ? c->largest : 0; }
+extern "C" uint32_t ks_clusters_n_rounds(const ks_clusters *c) { return c ? c->n_rounds : 0; }
 extern "C" const uint32_t *ks_clusters_device_label(const ks_clusters *c) { return c ? c->d_label : nullptr; }
 extern "C" const uint32_t *ks_clusters_device_cluster_id(const ks_clusters *c) { return c ? c->d_cluster_id : nullptr; }
 extern "C" const uint64_t *ks_clusters_device_offsets(const ks_clusters *c) { return c ? c->d_offsets : nullptr; }

@@ -47,7 +47,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -330,13 +330,14 @@ enum : u32 {
     KS_PIN_REGIONS = 206,    // u32: match regions kept (ks_regions.hip)
     KS_PIN_CLUSTER = 207,    // 5 words, clusters: first row with an id out of range | first row with an empty sketch | edges | clusters | largest
     KS_PIN_GATHER = 212,     // 4 words, gather: first row with an id out of range | first row with another shared count | first row past the incidence array | kept rows
-    KS_PIN_END = 216,
+    KS_PIN_GREEDY = 216,     // 10 words, greedy clusters: the five of KS_PIN_CLUSTER | the two live-edge counts | undecided nodes | rounds | members without a representative
+    KS_PIN_END = 226,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -432,14 +433,33 @@ struct ks_regions {
     u32 *d_qstart, *d_tstart, *d_length, *d_nkmers, *d_covered; // n_regions
 };
 
-// connected components of a hit list read as a graph (ks_cluster.hip)
+// clusters of a hit list read as a graph: its connected components (ks_cluster.hip) or greedy representative clusters (ks_greedy.hip)
 struct ks_clusters {
     ks_ctx *ctx;
     u32 n_nodes, n_clusters, largest;
     u64 n_edges;
+    u32 n_rounds; // ks_greedy.hip: the rounds the pass took; 0 for connected components
     u32 *d_label, *d_cluster_id, *d_members, *d_rep; // n_nodes each (d_rep: the first n_clusters are meaningful)
     u64 *d_offsets;                                  // n_nodes + 1 (entries past n_clusters repeat n_nodes)
 };
+// ---- labels -> clusters (ks_cluster.hip; ks_hits_cluster and ks_hits_cluster_greedy) ----
+// the first words of the control block of both passes: the first row with an id out of range / with an empty sketch, the rows
+// that passed, and what the tail below counts
+enum { CL_BAD_ID = 0, CL_BAD_SIZE = 1, CL_EDGES = 2, CL_CLUSTERS = 3, CL_LARGEST = 4 };
+// the result arrays of a cluster pass over n nodes (label, cluster_id, members, representative, offsets), scalars zeroed
+int ks_clusters_alloc(ks_ctx *ctx, ks_clusters *K, u32 n);
+// per-node scratch of the tail, n entries each.  On entry sizes and rep are zero and root_idx[i] = (K->d_label[i] == i)
+struct ks_label_scratch { u32 *root_idx, *sizes; u64 *rep, *ka, *kb; };
+// The tail of a cluster pass: K->d_label holds per node the root of its cluster (a root labels itself) -> cluster_id (clusters
+// numbered by ascending root), the CSR (offsets, members ascending), per cluster the member with the most distinct hashes of
+// `nodes` (ties, and without `nodes`: the smallest id), ctl[CL_CLUSTERS] and ctl[CL_LARGEST].  Enqueued; the caller waits
+// (ks_stream_wait_fetch_scans: the scans are one-launch ones).
+int ks_clusters_from_labels(ks_ctx *ctx, ks_clusters *K, const ks_sketches *nodes, const ks_label_scratch &W, const ks_ctl &ctl);
+// what both passes refuse after the wait (the first bad row named) and the scalars of the tail, from ctl's host copy into K
+int ks_clusters_finish(ks_ctx *ctx, const char *what, ks_clusters *K, const ks_ctl &ctl);
+// the option words both passes share and what they ask of the other arguments ("<what> options: ..."); ctx may be NULL
+int ks_cluster_words_check(ks_ctx *ctx, const char *what, u32 similarity, u32 n_nodes, double threshold, const ks_sketches *nodes,
+                           const double *d_score);
 
 // ---- passes whose sort key is `hit row | fields of the pair` (ks_matchpos.hip, ks_regions.hip) ----
 // Row index and fields that do not fit 64 bits together: the hit rows are cut into slices, each sorted with a key of its own

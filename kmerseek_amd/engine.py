@@ -86,6 +86,7 @@ def search_opts(min_containment: float = 0.0, abund_stats: bool = False) -> Opti
 
 BEST_RANK_BY = {"intersect": _lib.KS_BEST_INTERSECT, "target_containment": _lib.KS_BEST_TARGET_CONTAINMENT,
                 "max_containment": _lib.KS_BEST_MAX_CONTAINMENT, "jaccard": _lib.KS_BEST_JACCARD, "score": _lib.KS_BEST_SCORE}
+GREEDY_ASSIGN = {"first": _lib.KS_GREEDY_ASSIGN_FIRST, "best": _lib.KS_GREEDY_ASSIGN_BEST}
 
 
 class _FollowDebugEnv:
@@ -450,6 +451,30 @@ class Context:
                                             C.byref(out)))
         return Clusters(self, out)
 
+    def cluster_greedy(self, hits: "Hits", similarity: Optional[str] = None, threshold: float = 0.0, nodes: Optional["Sketches"] = None,
+                       score=None, n_nodes: int = 0, assign: str = "first") -> "Clusters":
+        """ks_hits_cluster_greedy: greedy representative clusters of an all-vs-all hit list (the clustering of CD-HIT and of
+        the greedy modes of MMseqs2 / linclust).  Hits, edges, similarity, threshold, nodes, score and n_nodes are those of
+        cluster().  The nodes are taken in priority order (with `nodes`: more distinct hashes first, ties to the smaller id;
+        without: the smaller id first); a node with no representative among its neighbours of higher priority becomes one,
+        every other node joins a neighbouring representative: assign="first" the one of highest priority, "best" the one at
+        the other end of its passing row with the largest score (ties: the higher priority).  In the result a label is the
+        representative's id; Clusters.n_rounds says how many rounds the pass took."""
+        if similarity is None:
+            similarity = "jaccard" if score is None else "score"
+        if similarity not in BEST_RANK_BY:
+            raise ValueError(f"similarity must be one of {', '.join(BEST_RANK_BY)}, not {similarity!r}")
+        if assign not in GREEDY_ASSIGN:
+            raise ValueError(f"assign must be one of {', '.join(GREEDY_ASSIGN)}, not {assign!r}")
+        if not 0 <= int(n_nodes) < 2 ** 32:
+            raise ValueError(f"n_nodes = {n_nodes} does not fit 32 bits")
+        d_score = None if score is None else C.c_void_p(int(score.data_ptr()) if hasattr(score, "data_ptr") else int(score))
+        opts = _lib.ks_greedy_opts(BEST_RANK_BY[similarity], int(n_nodes), float(threshold), GREEDY_ASSIGN[assign], 0)
+        out = C.c_void_p()
+        self._check(self._L.ks_hits_cluster_greedy(self._h, hits._h, None if nodes is None else nodes._h, d_score, C.byref(opts),
+                                                   C.byref(out)))
+        return Clusters(self, out)
+
     def gather(self, hits: "Hits", queries: "Sketches", targets: "Sketches", min_unique: int = 1, max_results: int = 0) -> "Hits":
         """ks_hits_gather: per query the greedy non-redundant targets.  Round after round the row of the query that covers the
         most hashes no earlier pick covered is kept (ties: the smaller tid) and its hashes are taken out; a query stops when the
@@ -732,8 +757,9 @@ class Regions(_Owned):
 
 
 class Clusters(_Owned):
-    """Device-resident connected components of a hit list (ks_clusters): per node its label (the smallest id of its cluster)
-    and cluster_id, the clusters as a CSR (offsets, members) ordered by smallest member, and a representative per cluster."""
+    """Device-resident clusters of a hit list (ks_clusters): per node its label and cluster_id, the clusters as a CSR (offsets,
+    members) and a representative per cluster.  From cluster(): connected components, the label is the smallest id of the
+    cluster and orders the clusters.  From cluster_greedy(): the label is the representative's id and orders the clusters."""
     _free = "ks_clusters_free"
     _COLUMNS = ("label", "cluster_id", "offsets", "members", "representative")
 
@@ -753,6 +779,11 @@ class Clusters(_Owned):
     @property
     def largest(self) -> int:
         return int(self._ctx._L.ks_clusters_largest(self._h))
+
+    @property
+    def n_rounds(self) -> int:
+        """Rounds a cluster_greedy() result took (a diagnostic: it may depend on the schedule); 0 for cluster()."""
+        return int(self._ctx._L.ks_clusters_n_rounds(self._h))
 
     def device_ptrs(self) -> Tuple[int, ...]:
         """Raw device pointers (label / cluster_id u32[n_nodes], offsets u64[n_clusters + 1], members u32[n_nodes],

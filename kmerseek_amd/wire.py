@@ -334,15 +334,15 @@ def do_multisearch(query_sig: str, target_sig: str, output: str, ksize: int, sca
 CLUSTER_COLUMNS = ["cluster", "representative", "size", "nodes"]
 
 
-def cluster_rows(names: Sequence[str], offsets, members, representative) -> List[Tuple[str, str, int, str]]:
-    """One row per cluster of a Clusters.to_host() CSR, in its order: (Component_<i>, name of the representative, size, the
+def cluster_rows(names: Sequence[str], offsets, members, representative, prefix: str = "Component") -> List[Tuple[str, str, int, str]]:
+    """One row per cluster of a Clusters.to_host() CSR, in its order: (<prefix>_<i>, name of the representative, size, the
     members' names joined by ';' in ascending id order)."""
     offsets = np.asarray(offsets).astype(np.int64).tolist()
     members = np.asarray(members).tolist()
     rows = []
     for i, rep in enumerate(np.asarray(representative).tolist()):
         ids = members[offsets[i]:offsets[i + 1]]
-        rows.append((f"Component_{i}", names[rep], len(ids), ";".join(names[j] for j in ids)))
+        rows.append((f"{prefix}_{i}", names[rep], len(ids), ";".join(names[j] for j in ids)))
     return rows
 
 
@@ -353,14 +353,19 @@ def cluster_size_histogram(offsets) -> List[Tuple[int, int]]:
 
 
 def do_cluster(sig: str, output: str, ksize: int, scaled: int, moltype: str, similarity: str = "jaccard", threshold: float = 0.0,
-               sizes_output: Optional[str] = None, min_size: int = 1, ctx: Optional[Context] = None) -> int:
+               sizes_output: Optional[str] = None, min_size: int = 1, ctx: Optional[Context] = None, method: str = "components",
+               assign: str = "first") -> int:
     """Cluster the sketches of one .sig.zip: the set is searched against an index of itself and the hit list becomes a graph
     (Context.cluster: a pair is joined iff its `similarity` — intersect | target_containment | max_containment | jaccard —
     is >= threshold); the clusters are its connected components.  Writes a CSV with the columns cluster, representative,
     size, nodes: one row per cluster of at least min_size members, clusters named Component_<i> by ascending first member,
     `nodes` the member names joined by ';'.  sizes_output: a second CSV, cluster_size,count, over every cluster.
     The format is this project's own, modelled on the output of branchwater's `cluster`; no parity with that tool is
-    claimed.  Returns the number of cluster rows written."""
+    claimed.  method="greedy": greedy representative clusters instead (Context.cluster_greedy, with `assign` first | best:
+    every member is within the threshold of its representative, no two representatives are within it of each other), the
+    same columns, clusters named Cluster_<i> by ascending representative.  Returns the number of cluster rows written."""
+    if method not in ("components", "greedy"):
+        raise ValueError(f"method must be components or greedy, not {method!r}")
     own = ctx is None
     ctx = ctx or Context(0)
     try:
@@ -372,12 +377,15 @@ def do_cluster(sig: str, output: str, ksize: int, scaled: int, moltype: str, sim
             S = ctx.sketches_from_host(so, sm, sa, ksize, scaled, moltype); made.append(S)
             ix = ctx.index_build(S); made.append(ix)
             hits = ctx.search(ix, S); made.append(hits)
-            cl = ctx.cluster(hits, similarity, threshold, nodes=S); made.append(cl)
+            if method == "greedy":
+                cl = ctx.cluster_greedy(hits, similarity, threshold, nodes=S, assign=assign); made.append(cl)
+            else:
+                cl = ctx.cluster(hits, similarity, threshold, nodes=S); made.append(cl)
             _, _, offsets, members, rep = cl.to_host()
         finally:
             for o in reversed(made):
                 o.free()
-        rows = [r for r in cluster_rows(names, offsets, members, rep) if r[2] >= min_size]
+        rows = [r for r in cluster_rows(names, offsets, members, rep, "Cluster" if method == "greedy" else "Component") if r[2] >= min_size]
         with open(output, "w", newline="") as f:
             w = csv.writer(f, lineterminator="\n")
             w.writerow(CLUSTER_COLUMNS)
