@@ -226,6 +226,58 @@ int ks_sketches_from_host(ks_ctx *ctx, const uint64_t *offsets, const uint64_t *
 int ks_sketches_union(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out);
 void ks_sketches_free(ks_sketches *s);
 
+/* ---- translated search: nucleotide input for the protein / dayhoff / hp sketches ---------------------------------------- */
+
+/* Six-frame translation of a nucleotide batch on the device: what lets contigs, reads and unannotated genomes be searched
+ * against a protein database.  The sourmash / branchwater family does this inside add_sequence for a protein-type sketch given
+ * DNA; sourmash is not part of this build, the semantics below were restated from its documentation and NO PARITY IS CLAIMED.
+ * For a record of L bases, taken as bytes after ASCII upper-casing:
+ *   base codes  T = 0, C = 1, A = 2, G = 3; every other byte is invalid (N, U, the IUPAC codes and gaps included)
+ *   codon       (b1, b2, b3) -> TABLE[16 b1 + 4 b2 + b3], TABLE = "FFLLSSSSYY**CC*WLLLLPPPPHHQQRRRRIIIMTTTTNNKKSSRRVVVVAAAADDEEGGGG"
+ *               (the standard code, NCBI table 1); a codon with an invalid base gives 'X'.  '*' and 'X' are residues like any
+ *               other: they are not skipped and do not cut the frame (the sketch hashes whatever byte it is given).
+ *   reverse     rc[i] = comp(nt[L - 1 - i]), A <-> T, C <-> G, any other byte maps to itself
+ *   frames      forward frame f in {0, 1, 2}: the codons of nt[f:], max(0, (L - f) / 3) residues, a trailing partial codon
+ *               dropped; reverse frame f: the same on rc[f:]
+ * Record s becomes the six sequences 6 s + f (forward) and 6 s + 3 + f (reverse) of ONE contiguous residue buffer with u64
+ * offsets [6 n_seqs + 1] — the batch layout ks_sketch_batch_device, ks_kmer_positions_device and ks_sketch_queries_device read.
+ * A window that starts at `start` of forward frame f covers the bases from f + 3 start on, one of reverse frame f the bases from
+ * L - f - 3 (start + ksize) on.  d_nt / d_offsets: device, n_seqs + 1 ascending offsets from 0 to n_nt.
+ * KS_ERR_INVALID_ARG: NULL arguments, d_frames not 16-byte aligned (both before any device work); offsets that do not start at
+ * 0, ascend and end at n_nt, or a record beyond 2^32 - 16 bases (found on the device: the output is then incomplete, nothing is
+ * written outside it).  KS_ERR_CAPACITY: 6 n_seqs does not fit a u32.  One stream, one wait, synchronous on return. */
+uint64_t ks_translate6_bound(uint64_t n_nt);          /* residues the frames of n_nt bases can need: 2 * n_nt */
+int ks_translate6_device(ks_ctx *ctx, const uint8_t *d_nt, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_nt,
+                         uint8_t *d_frames /* caller-owned, >= bound, 16-byte aligned */,
+                         uint64_t *d_frame_offsets /* caller-owned, 6 * n_seqs + 1 */, uint64_t *n_residues_out);
+/* The translated sketch: record s's sketch is the union of its six frame sketches at `params` (ksize stays the PROTEIN k), the
+ * abundances of a hash summed over the frames and saturating at 2^32 - 1 as in ks_sketches_union.  A record shorter than
+ * 3 * ksize bases has an empty sketch; a palindromic record counts each window twice.  The result is a plain ks_sketches:
+ * n_seqs records, n_windows the sum over the frames, no postings attached — ks_search, ks_index_build, the hit-list passes and
+ * ks_corpus_build take it unchanged.  max_seq_len: an upper bound on the longest record IN BASES, or 0 to have the batch
+ * measured; the frames are sketched under the bound max_seq_len / 3, and one that is too small fails as it does in
+ * ks_sketch_batch_device.  Parameters, NULL arguments and the u32 range of 6 n_seqs are checked before any device work.  The
+ * frames and the six-fold sketch live in the context's pool and are given back before the call returns. */
+int ks_sketch_translated_device(ks_ctx *ctx, const uint8_t *d_nt, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_nt,
+                                uint32_t max_seq_len /* in bases, 0 = measure */, const ks_params *params, ks_sketches **out);
+/* the same from host arrays (the layout ks_sketch_batch takes, with bases for residues) */
+int ks_sketch_translated(ks_ctx *ctx, const uint8_t *nt, const uint64_t *offsets, uint32_t n_seqs, const ks_params *params,
+                         ks_sketches **out);
+/* Union by group: sketch g of the result is the ascending distinct hashes of the sketches [group_offsets[g], group_offsets[g + 1])
+ * of `in`, abundances summed per hash and saturating at 2^32 - 1 — ks_sketches_union folds a whole set into one sketch, this
+ * folds consecutive runs: the six frames of a record, or all proteins of a genome into the proteome-sized query ks_hits_gather
+ * has a path for.  group_offsets: HOST, n_groups + 1 entries, 0 first, the set's sequence count last, never descending.  The
+ * result is a dense CSR of n_groups sketches with the input's params and n_windows; an empty group gives an empty sketch, a
+ * group of one a copy, n_groups == 0 (on an empty set) a valid empty set.  Groups of at most ks_debug_union_rank_max() members
+ * are merged by binary-search ranks in one kernel, larger ones by two stable radix sorts; the result never depends on the path
+ * (KS_DEBUG_UNION_PATH = 1 / 2 force the rank / the sort path for the tests).
+ * KS_ERR_INVALID_ARG (before any device work): NULL arguments, an input of another context, group_offsets that do not start at
+ * 0, end at the sequence count and ascend.  KS_ERR_CAPACITY: 2^32 - 2 or more hashes.  One stream, one wait; scratch from the
+ * pool: 32 bytes per input hash on the rank path, 56 on the sort path. */
+int ks_sketches_union_groups(ks_ctx *ctx, const ks_sketches *in, const uint32_t *group_offsets, uint32_t n_groups, ks_sketches **out);
+uint32_t ks_debug_translate_chunk(void);   /* bases one workgroup of the translate kernel owns: the tests put record ends around it */
+uint32_t ks_debug_union_rank_max(void);    /* largest group the rank path takes */
+
 /* ---- k-mer positions ----------------------------------------------------------------------- */
 
 /* Replaces ProteomeIndex::process_kmers (src/rust/index.rs:749-786): for every window whose hash

@@ -134,6 +134,13 @@ SIGNATURES = {
     "ks_sketches_from_host": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _parp, _pp]),
     "ks_sketches_union": (C.c_int, [_vp, _vp, _pp]),
     "ks_sketches_free": (None, [_vp]),
+    "ks_translate6_bound": (C.c_uint64, [C.c_uint64]),
+    "ks_translate6_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, _u64p]),
+    "ks_sketch_translated_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, _parp, _pp]),
+    "ks_sketch_translated": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _parp, _pp]),
+    "ks_sketches_union_groups": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, _pp]),
+    "ks_debug_translate_chunk": (C.c_uint32, []),
+    "ks_debug_union_rank_max": (C.c_uint32, []),
     "ks_kmer_positions": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _parp, _pp]),
     "ks_kmer_positions_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _parp, _pp]),
     "ks_kmerpos_count": (C.c_uint64, [_vp]),

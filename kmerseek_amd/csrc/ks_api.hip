@@ -78,6 +78,20 @@ extern "C" int ks_sketch_batch(ks_ctx *ctx, const uint8_t *residues, const uint6
     });
 }
 
+extern "C" int ks_sketch_translated(ks_ctx *ctx, const uint8_t *nt, const uint64_t *offsets, uint32_t n_seqs, const ks_params *params,
+                                    ks_sketches **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "out is NULL");
+    *out = nullptr;
+    KS_TRY(ks_check_params(ctx, params));
+    if (6 * (u64)n_seqs > 0xffffffffULL) return ks_fail(ctx, KS_ERR_CAPACITY, "sketch_translated: the six frames of %u records do not fit 32-bit sequence ids", n_seqs);
+    ks_upload U(ctx);
+    KS_TRY(U.upload(nt, offsets, n_seqs));
+    return ks_sketch_translated_impl(ctx, U.d_res, U.d_offs, n_seqs, U.n_res, U.max_len, params, out);
+    });
+}
+
 // ---- slots -> plain CSR --------------------------------------------------------------------------------------------------
 // A sketch call leaves every sequence a slot as long as its KEPT hashes (ks_common.h: ks_sketches); where a sequence repeats a
 // k-mer its distinct hashes fill only the head of the slot.  One gather (one wave per sequence) closes the gaps: new offsets =

@@ -179,6 +179,11 @@ class Context:
         self._check(self._L.ks_dev_upload(self._h, p, _ptr(a), a.nbytes))
         return buf
 
+    def _device_empty(self, nbytes: int) -> "DeviceBuffer":
+        p = C.c_void_p()
+        self._check(self._L.ks_dev_malloc(self._h, int(nbytes), C.byref(p)))
+        return DeviceBuffer(self, p, int(nbytes))
+
     def pinned_empty(self, n: int, dtype) -> np.ndarray:
         """Uninitialised numpy array of n items in pinned host memory (ks_host_alloc): copies between such an array and the
         device run as one DMA at link rate, where a pageable array is staged through pinned buffers by host threads.
@@ -286,6 +291,49 @@ class Context:
                                              C.byref(sk) if want_sketches else None, C.byref(hits))
         self._check(st)
         return (Sketches(self, sk) if want_sketches else None), Hits(self, hits)
+
+    # ---- translated search: nucleotide input ----
+    def translate6(self, nt: np.ndarray, offsets: np.ndarray) -> Tuple["DeviceBuffer", "DeviceBuffer", int]:
+        """ks_translate6_device on a host batch of nucleotide records (the layout of `pack`): (frames, frame_offsets, n_residues)
+        — two DeviceBuffers, the residues u8 of the 6 x n frames (record s: 6s + f forward, 6s + 3 + f reverse) and their u64
+        offsets [6n + 1], the batch layout every *_device sketch entry reads — and the residue count.  Standard code; any byte
+        but ACGT (after upper-casing) makes its codon X; stops are '*'."""
+        nt = np.ascontiguousarray(nt, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        n, n_nt = len(offsets) - 1, int(offsets[-1])
+        if nt.size != n_nt:
+            raise ValueError(f"offsets end at {n_nt}, the batch holds {nt.size} bases")
+        d_nt = self.to_device(nt if n_nt else np.zeros(16, np.uint8))
+        d_off = self.to_device(offsets)
+        frames = self._device_empty(int(self._L.ks_translate6_bound(n_nt)) + 16)  # (+ 16: the sketch tiles load whole 16-byte words)
+        foff = self._device_empty(8 * (6 * n + 1))
+        n_res = C.c_uint64(0)
+        try:
+            self._check(self._L.ks_translate6_device(self._h, d_nt._p, d_off._p, n, n_nt, frames._p, foff._p, C.byref(n_res)))
+        finally:
+            d_nt.free(); d_off.free()
+        return frames, foff, int(n_res.value)
+
+    def sketch_translated(self, nt: np.ndarray, offsets: np.ndarray, ksize: int, scaled: int, moltype: str,
+                          seed: int = SEED) -> "Sketches":
+        """ks_sketch_translated: protein / dayhoff / hp sketches of NUCLEOTIDE records — every record translated in six frames,
+        its sketch the union of the six frame sketches (abundances summed).  ksize is the protein k."""
+        nt = np.ascontiguousarray(nt, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        p = make_params(ksize, scaled, moltype, seed)
+        out = C.c_void_p()
+        self._check(self._L.ks_sketch_translated(self._h, _ptr(nt), _ptr(offsets), len(offsets) - 1, C.byref(p), C.byref(out)))
+        return Sketches(self, out)
+
+    def sketch_translated_device(self, d_nt: int, d_offsets: int, n_seqs: int, n_nt: int, ksize: int, scaled: int, moltype: str,
+                                 max_seq_len: int = 0, seed: int = SEED) -> "Sketches":
+        """The same with the batch resident on the device (raw pointers); max_seq_len: a bound on the longest record in BASES,
+        or 0 to have it measured."""
+        p = make_params(ksize, scaled, moltype, seed)
+        out = C.c_void_p()
+        self._check(self._L.ks_sketch_translated_device(self._h, C.c_void_p(d_nt), C.c_void_p(d_offsets), n_seqs, n_nt, max_seq_len,
+                                                        C.byref(p), C.byref(out)))
+        return Sketches(self, out)
 
     def qfilter_stats(self) -> Dict[str, int]:
         """Query postings the filtered bucket scatters of this context read / dropped (see ks_ctx_qfilter_stats)."""
@@ -653,6 +701,19 @@ class Sketches(_Owned):
         """Combined sketch: sorted unique hashes of all sequences with summed abundances (one sequence)."""
         out = C.c_void_p()
         self._ctx._check(self._ctx._L.ks_sketches_union(self._ctx._h, self._h, C.byref(out)))
+        return Sketches(self._ctx, out)
+
+    def union_groups(self, group_offsets) -> "Sketches":
+        """ks_sketches_union_groups: sketch g of the result is the union of the sketches [group_offsets[g], group_offsets[g + 1])
+        of this set, abundances summed per hash (saturating) — the proteins of a genome as one proteome sketch, the frames of a
+        record as one.  group_offsets: n_groups + 1 ascending integers from 0 to n_seqs."""
+        go = np.asarray(group_offsets)
+        if go.ndim != 1 or go.size == 0 or (go.size and (go.min() < 0 or go.max() >= 2 ** 32)):
+            raise ValueError("group_offsets must be a non-empty 1-d array of 32-bit offsets")
+        go = np.ascontiguousarray(go, dtype=np.uint32)
+        out = C.c_void_p()
+        self._ctx._check(self._ctx._L.ks_sketches_union_groups(self._ctx._h, self._h, go.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                               len(go) - 1, C.byref(out)))
         return Sketches(self._ctx, out)
 
     def corpus(self) -> "Corpus":

@@ -29,7 +29,7 @@ from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .engine import Context, max_hash
+from .engine import Context, max_hash, pack
 
 MANYSEARCH_COLUMNS = [
     "query_name", "query_md5", "match_name", "containment", "intersect_hashes", "ksize", "scaled", "moltype",
@@ -144,12 +144,27 @@ def _make_sigfile(fasta: str, moltype: str, ksize: int, scaled: int) -> str:
     return f"{fasta}.{moltype}.k{ksize}.scaled{scaled}.sig.zip"
 
 
-def sketch(fasta: str, moltype: str, ksize: int, scaled: int, ctx: Optional[Context] = None) -> str:
+def sketch(fasta: str, moltype: str, ksize: int, scaled: int, ctx: Optional[Context] = None, translate: bool = False) -> str:
     """sketch() of src/python/kmerseek/sketch.py:28-40.  The records go through the native pipelined ingest
-    (csrc/ks_ingest.cpp: parse, pinned staging, H2D and the sketch kernels overlap); `ctx` only picks the device."""
+    (csrc/ks_ingest.cpp: parse, pinned staging, H2D and the sketch kernels overlap); `ctx` only picks the device.
+    translate=True: the records are NUCLEOTIDES; each is translated in six frames on the device and sketched as the union of
+    its frames (Context.sketch_translated).  The .sig.zip is written by the same code: same molecule, same names."""
     from . import host
     sigfile = _make_sigfile(fasta, moltype, ksize, scaled)
     _make_manysketch_csv(fasta)
+    if translate:
+        recs = read_fasta(fasta)
+        own = ctx is None
+        c = Context(0) if own else ctx
+        try:
+            sk = c.sketch_translated(*pack([r for _, r in recs]), ksize, scaled, moltype)
+            o, m, a = sk.to_host()
+            sk.free()
+        finally:
+            if own:
+                c.close()
+        write_sig_zip(sigfile, [n for n, _ in recs], o, m, a, ksize, scaled, moltype, os.path.abspath(fasta))
+        return sigfile
     names, o, m, a, _ = host.sketch_fasta(fasta, ksize, scaled, moltype, validate=False,
                                           device=ctx.device if ctx is not None and hasattr(ctx, "device") else 0)
     write_sig_zip(sigfile, names, o, m, a, ksize, scaled, moltype, os.path.abspath(fasta))
