@@ -107,11 +107,15 @@ int ks_ctx_pool_stats(const ks_ctx *ctx, uint64_t *n_blocks, uint64_t *bytes_hel
 int ks_ctx_sketch_stats(const ks_ctx *ctx, uint64_t out[4]);
 /* The same for ks_search: out[0] = searches that ran their join twice because the match list outgrew its first guess
  * (the list is sized from the previous search of the context), out[1] = searches whose row pass was repeated with
- * ticket-ordered tiles because a look-back gave up (the context then uses tickets for good). */
-int ks_ctx_search_stats(const ks_ctx *ctx, uint64_t out[2]);
+ * ticket-ordered tiles because a look-back gave up (the context then uses tickets for good), out[2] = searches whose rows
+ * came from the aggregate pass over the match sort's first level (taken while the previous search of the context had many
+ * matches per row; a path, not a repeat), out[3] = searches in which that pass gave up (a region with more rows than its
+ * table holds) and the sort was resumed. */
+int ks_ctx_search_stats(const ks_ctx *ctx, uint64_t out[4]);
 /* ks_sketch_search_device on this context: out[0] = calls whose sketch read-back was folded into the search's first wait,
- * out[1] = calls that had to be repeated with the two plain calls (skewed hashes, an economy that did not fit). */
-int ks_ctx_fused_stats(const ks_ctx *ctx, uint64_t out[2]);
+ * out[1] = calls that had to be repeated with the two plain calls (skewed hashes, an economy that did not fit), out[2] = calls
+ * whose rows came from the aggregate pass (out[2] of ks_ctx_search_stats rose during the call). */
+int ks_ctx_fused_stats(const ks_ctx *ctx, uint64_t out[3]);
 /* The presence filter of the searches on this context (a fingerprint-layout index carries a bitmap over hash prefixes; the
  * partition of the query postings drops those the bitmap rules out): out[0] = query postings the filtered partitions read,
  * out[1] = postings they dropped.  Results never depend on the filter; KS_DEBUG_QFILTER = 0 / 1 forces it off / on. */

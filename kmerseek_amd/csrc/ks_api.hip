@@ -341,6 +341,7 @@ static int sketch_search_impl(ks_ctx *ctx, const ks_index *index, const uint8_t 
     const int fmt10 = (index->fp_layout && index->fp_shift == 32 - index->pbits) ? 1 : 0;
     ks_sketches *S = nullptr;
     ks_hits *H = nullptr;
+    const u64 agg_before = ctx->agg_used;
     int st = ks_sketch_device_impl(ctx, d_residues, d_seq_offsets, n_seqs, n_residues, max_seq_len, &index->params, index->pbits, fmt10,
                                    ks_dbg(ctx, KS_DBG_NO_DEFER) ? 0 : 1, &S);
     if (st != KS_OK) return st;
@@ -363,6 +364,7 @@ static int sketch_search_impl(ks_ctx *ctx, const ks_index *index, const uint8_t 
     }
     if (st != KS_OK) { ks_hits_free(H); ks_sketches_free(S); return st; }
     if (deferred) ctx->fused_deferred++;
+    if (ctx->agg_used > agg_before) ctx->fused_aggregated++;
     *hits_out = H;
     if (sketches_out) *sketches_out = S; else ks_sketches_free(S);
     return KS_OK;

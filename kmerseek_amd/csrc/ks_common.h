@@ -47,7 +47,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -94,7 +94,16 @@ struct ks_ctx {
     u64 sketch_ticket_fallbacks = 0, sketch_compact_fallbacks = 0, sketch_cap_fallbacks = 0;
     bool rows_use_ticket = false; u64 rows_ticket_fallbacks = 0; // k_pair_rows_fused: dispatch-order tile ids until a look-back gives up
     u64 fused_deferred = 0, fused_redos = 0; // ks_sketch_search_device: calls that folded the sketch wait into the first wait of the search / were repeated plainly
+    u64 fused_aggregated = 0;                // ... whose rows the aggregate pass made (agg_used below rose)
     u64 join_retries = 0; // searches whose match list outgrew a segment and ran the join twice
+    // The rows of a search come from the match list by sort aggregation (two more partition levels + the run-length pass) or by
+    // hash aggregation of the level-1 regions (k_pairs_aggregate, ks_rows.hip), which pays while many records share a row:
+    // rows_mult is the previous search's records per row (0: no search yet, the first one sorts).  KS_DEBUG_ROWS_PATH = agg /
+    // sort forces either.  agg_used: searches whose rows the aggregate pass made; agg_overflows: searches in which a region's
+    // table overflowed (or its look-back gave up) and the sort resumed on the level-1 output; agg_oflow_rows: the fewest rows
+    // of such a search (0: none yet) — the pass is not tried again until a search expects under half of them.
+    double rows_mult = 0.0;
+    u64 agg_used = 0, agg_overflows = 0, agg_oflow_rows = 0;
     // The presence filter of the bucket scatter (ks_index::d_presence) pays while most query postings are foreign to the index.
     // false after a search whose scatter kept more than half of its postings (the probes then cost more than the dropped
     // bytes save); true again after an unfiltered search with fewer than a quarter as many matches as postings.
@@ -320,7 +329,7 @@ enum : u32 {
     KS_PIN_SKETCH = 128, KS_PIN_SKETCH_WORDS = 32, // the control block of a sketch whose read-back is pending ...
     KS_PIN_SKETCH_SYNC = 160, KS_PIN_SKETCH_SYNC_WORDS = 32, // ... and of a sketch that waits for itself
     KS_PIN_STAGE = 192,      // u32 uploaded by the sketch's ticket repeat (the status bits it keeps)
-    KS_PIN_ROWS = 193,       // 2 words, row pass: u32 (ticket, look-back flag) | u32 row count
+    KS_PIN_ROWS = 193,       // 2 words, row pass: u32 (ticket / an aggregate table overflowed, look-back flag) | u32 (row count, kept rows)
     KS_PIN_SCAN = 195,       // u32: a one-launch scan gave up a look-back (ks_scan_status_check)
     KS_PIN_SORT_OFLOW = 196, // u32: a fixed capacity of the partitioned index sort did not hold
     KS_PIN_READ = 197,       // 2 words, one-call read-backs: index build, union, merge, k-mer positions
@@ -571,6 +580,20 @@ struct ks_msd_segs {
     u64 seg_cap;
 };
 int ks_sort_pairs_msd(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbits, int *done, const ks_msd_segs *segs = nullptr);
+// The same sort in two steps, for a caller that may not need the rest: ks_msd_level1 leaves the list in kb in KS_MSD_REGIONS exact
+// regions on the top 8 key bits (region r ends at P->ends[r], the spent cursors; every key lies wholly inside one region) and
+// ka untouched as scratch; ks_msd_finish runs levels 2 / 3 on those buffers (the sorted list: ka) and ks_msd_drop gives the
+// plan's block back instead.  P->blk == nullptr behind ks_msd_level1: not applicable, nothing was launched.
+#define KS_MSD_REGIONS 256
+struct ks_msd_plan {
+    u64 *ka, *kb, n;
+    int lo_bit, nbits;
+    u32 *blk;        // off1 | off2 | big-list counter | big list (ks_msd.hip)
+    const u32 *ends; // [KS_MSD_REGIONS] inside blk
+};
+int ks_msd_level1(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbits, const ks_msd_segs *segs, ks_msd_plan *P);
+int ks_msd_finish(ks_ctx *ctx, ks_msd_plan *P);
+void ks_msd_drop(ks_ctx *ctx, ks_msd_plan *P);
 int ks_radix_sort_u64(ks_ctx *ctx, int tag, const u64 *keys_in, const u64 *vals_in, u64 *ka, u64 *va, u64 *kb, u64 *vb,
                       u64 n, const int *shifts, int n_shifts, u64 **keys_out, u64 **vals_out);
 
@@ -585,8 +608,16 @@ int ks_seg_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t cap, u32 **list);
 // the knob that sends every segment one way (tests): 0 by length (unset), 1 by a wave, 2 by a workgroup; 3: 2 with *small set
 int ks_seg_path_knob(const ks_ctx *ctx, int dbg_id, bool *small);
 // what the row half needs from one search; the sorted match list pk becomes H's rows (n_pairs == 0: none, pk is not read)
-struct ks_rows_in { const ks_sketches *q; u64 n_pairs; int tbits, abits; bool stats; double min_c; };
+struct ks_rows_in { const ks_sketches *q; u64 n_pairs; int tbits, abits; bool stats; double min_c; int qbits; };
 int ks_search_rows(ks_ctx *ctx, const ks_rows_in &R, ks_hits *H, const u64 *pk);
+// ... and from the level-1 output of the match sort instead (hash aggregation per region, k_pairs_aggregate).  *fell_back: a
+// region's table overflowed or a look-back gave up — H has no rows, the list is untouched: the caller finishes the sort and
+// takes ks_search_rows.
+int ks_search_rows_agg(ks_ctx *ctx, const ks_rows_in &R, ks_hits *H, const ks_msd_plan &P, bool *fell_back);
+// whether the aggregate pass is expected to pay for a list of n_pairs records (the context's history, KS_DEBUG_ROWS_PATH)
+bool ks_rows_agg_wanted(const ks_ctx *ctx, const ks_rows_in &R);
+// a search of n_rows rows overflowed the aggregate pass's tables: remembered, ks_rows_agg_wanted holds back (agg_oflow_rows)
+void ks_rows_agg_overflowed(ks_ctx *ctx, u64 n_rows);
 
 // ---- pipelines (ks_sketch.hip, ks_search.hip) ----
 // part_pbits > 0: also emit postings partitioned for a join on the top part_pbits hash bits

@@ -403,11 +403,13 @@ __global__ __launch_bounds__(ML_THREADS) void k_msd_local_big(u64 *keys, u64 *sc
     }
 }
 
-// Sorts the n packed match records of `ka` on their key bits [lo_bit, lo_bit + nbits) (kb: scratch of the same size).
-// *done = 0 when the list is too small / the key too narrow for this path to pay (the caller takes the LSD sort).
-int ks_sort_pairs_msd(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbits, int *done, const ks_msd_segs *segs) {
-    *done = 0;
-    if (nbits <= 16 || n < 65536 || n >= 0xffffffffULL || ks_dbg(ctx, KS_DBG_PAIRS_LSD)) return KS_OK;
+// what levels 2 / 3 need of a plan: how wide level 2 is (a function of n and nbits alone) and where the words of the block lie
+struct ms_layout {
+    int shift1, shift2;
+    u32 mask2, n_buckets, n_sub, sub_stride;
+    size_t off2_words, n_zero;
+};
+static ms_layout ms_layout_of(u64 n, int lo_bit, int nbits, int *bits2_out) {
     // level 2 is as wide as it takes for ~768 records per bucket (0 .. 8 bits): a short list does not pay 65,536 buckets
     // ... and then as wide as it takes to save a local pass (remaining bits a multiple of 8): passes cost more than buckets
     // (up to 9 bits: 131,072 buckets through a 1024-bin window — lists beyond ~40 M records, where 65,536 buckets would leave
@@ -418,10 +420,70 @@ int ks_sort_pairs_msd(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbit
     for (int b = bits2 + 1; b <= 8 && nbits - 8 - b > 0; b++)
         if ((nbits - 8 - b + 7) / 8 < (nbits - 8 - bits2 + 7) / 8) { bits2 = b; break; }
     if (nbits - 8 - bits2 <= 0) bits2 = nbits - 9 > 0 ? nbits - 9 : 0; // (at least one bit left for the local sort)
-    const int shift1 = lo_bit + nbits - 8, shift2 = shift1 - bits2;
-    const u32 mask2 = (1u << (8 + bits2)) - 1u, n_buckets = 1u << (8 + bits2);
-    const u32 n_tiles = (u32)((n + MS_TILE - 1) / MS_TILE);             // of a dense list (level 2 always reads one)
+    ms_layout L;
+    L.shift1 = lo_bit + nbits - 8; L.shift2 = L.shift1 - bits2;
+    L.mask2 = (1u << (8 + bits2)) - 1u; L.n_buckets = 1u << (8 + bits2);
+    // (level 1 followed by level 2: MS_SUB histograms; level 1 alone — short lists — one, whose spent cursors are the ends)
+    L.n_sub = bits2 > 0 ? MS_SUB : 1u; L.sub_stride = bits2 > 0 ? 256u : 0u;
+    L.off2_words = bits2 > 0 ? (size_t)L.n_buckets + 1 : 0; L.n_zero = 256 * MS_SUB + L.off2_words + 1;
+    *bits2_out = bits2;
+    return L;
+}
+
+// Level 1 of the sort of the n packed match records of `ka` on their key bits [lo_bit, lo_bit + nbits) (kb: scratch of the same
+// size, where the partitioned list lands).  P->blk == nullptr on return: the list is too small / the key too narrow for this path
+// to pay (the caller takes the LSD sort).
+int ks_msd_level1(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbits, const ks_msd_segs *segs, ks_msd_plan *P) {
+    memset(P, 0, sizeof *P);
+    if (nbits <= 16 || n < 65536 || n >= 0xffffffffULL || ks_dbg(ctx, KS_DBG_PAIRS_LSD)) return KS_OK;
+    int bits2;
+    const ms_layout L = ms_layout_of(n, lo_bit, nbits, &bits2);
+    const u32 n_tiles = (u32)((n + MS_TILE - 1) / MS_TILE);             // of a dense list
     const u32 n_tiles1 = segs ? segs->tile_start[segs->n] : n_tiles;    // of level 1
+    ks_msd_segs no_segs;
+    no_segs.n = 0;
+    // The exclusive offsets double as the scatter's cursors: once spent, cursor[b] is the END of bucket b, which is all the
+    // local sort needs (no copy of the offsets is kept).
+    // Layout of the one block: off1 (256 x MS_SUB) | off2 (n_buckets + 1, when there is a level 2) | big-list counter | big list
+    // — everything that starts at zero comes first, so ONE memset clears both histograms and the counter.
+    u32 *blk = nullptr;
+    KS_TRY(ks_alloc(ctx, &blk, L.n_zero + (size_t)(L.n_buckets > 65536u ? L.n_buckets : 65536u) + 1));
+    u32 *off1 = blk;
+    (void)hipMemsetAsync(blk, 0, L.n_zero * sizeof(u32), ctx->stream);
+    ks_timer_begin(ctx, "msd_hist");
+    if (segs) hipLaunchKernelGGL((k_msd_hist<256, 1>), dim3(n_tiles1), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)ka, n, L.shift1, off1, 255u, 0, L.sub_stride, *segs);
+    else hipLaunchKernelGGL((k_msd_hist<256, 0>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)ka, n, L.shift1, off1, 255u, 0, L.sub_stride, no_segs);
+    ks_timer_end(ctx);
+    ks_timer_begin(ctx, "msd_scan");
+    hipLaunchKernelGGL(k_msd_scan256, dim3(1), dim3(256), 0, ctx->stream, off1, L.n_sub);
+    ks_timer_end(ctx);
+    ks_timer_begin(ctx, "msd_scatter");
+    if (segs) hipLaunchKernelGGL((k_msd_scatter<256, 1>), dim3(n_tiles1), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)ka, kb, n, L.shift1, off1, 255u, 0,
+                                 L.sub_stride, *segs);
+    else hipLaunchKernelGGL((k_msd_scatter<256, 0>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)ka, kb, n, L.shift1, off1, 255u, 0,
+                            L.sub_stride, no_segs);
+    ks_timer_end(ctx);
+    P->ka = ka; P->kb = kb; P->n = n;
+    P->lo_bit = lo_bit; P->nbits = nbits;
+    P->blk = blk;
+    P->ends = off1 + (size_t)(L.n_sub - 1u) * 256u; // the cursors of a bin's LAST sub-histogram end where the bin ends
+    return KS_OK;
+}
+
+void ks_msd_drop(ks_ctx *ctx, ks_msd_plan *P) {
+    ks_pool_free(ctx, P->blk);
+    P->blk = nullptr;
+}
+
+// Levels 2 / 3 behind ks_msd_level1: the sorted list ends up in P->ka.  The plan's block goes back to the pool either way.
+int ks_msd_finish(ks_ctx *ctx, ks_msd_plan *P) {
+    u64 *const ka = P->ka, *const kb = P->kb;
+    const u64 n = P->n;
+    const int lo_bit = P->lo_bit;
+    int bits2;
+    const ms_layout L = ms_layout_of(n, lo_bit, P->nbits, &bits2);
+    const u32 n_tiles = (u32)((n + MS_TILE - 1) / MS_TILE); // (level 2 always reads a dense list)
+    const u32 n_buckets = L.n_buckets;
     ks_msd_segs no_segs;
     no_segs.n = 0;
     u32 lds_cap = ML_CAP;
@@ -429,45 +491,20 @@ int ks_sort_pairs_msd(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbit
         const u32 v = (u32)atoi(f);
         if (v >= 2 && v < ML_CAP) lds_cap = v;
     }
-    // The exclusive offsets double as the scatter's cursors: once spent, cursor[b] is the END of bucket b, which is all the
-    // local sort needs (no copy of the offsets is kept).
-    // Layout of the one block: off1 (256 x MS_SUB) | off2 (n_buckets + 1, when there is a level 2) | big-list counter | big list
-    // — everything that starts at zero comes first, so ONE memset clears both histograms and the counter.
-    u32 *blk = nullptr;
-    // (level 1 followed by level 2: MS_SUB histograms; level 1 alone — short lists — one, whose spent cursors are the ends)
-    const u32 n_sub = bits2 > 0 ? MS_SUB : 1u, sub_stride = bits2 > 0 ? 256u : 0u;
-    const size_t off2_words = bits2 > 0 ? (size_t)n_buckets + 1 : 0, n_zero = 256 * MS_SUB + off2_words + 1;
-    int st = ks_alloc(ctx, &blk, n_zero + (size_t)(n_buckets > 65536u ? n_buckets : 65536u) + 1);
-    u32 *off1 = blk, *off2 = blk ? blk + 256 * MS_SUB : nullptr, *big = blk ? blk + 256 * MS_SUB + off2_words : nullptr;
-    u64 *sorted_in = ka; // where the partitioned list ends up
-    if (st == KS_OK) {
-        (void)hipMemsetAsync(blk, 0, n_zero * sizeof(u32), ctx->stream);
-        ks_timer_begin(ctx, "msd_hist");
-        if (segs) hipLaunchKernelGGL((k_msd_hist<256, 1>), dim3(n_tiles1), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)ka, n, shift1, off1, 255u, 0, sub_stride, *segs);
-        else hipLaunchKernelGGL((k_msd_hist<256, 0>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)ka, n, shift1, off1, 255u, 0, sub_stride, no_segs);
-        ks_timer_end(ctx);
-        ks_timer_begin(ctx, "msd_scan");
-        hipLaunchKernelGGL(k_msd_scan256, dim3(1), dim3(256), 0, ctx->stream, off1, n_sub);
-        ks_timer_end(ctx);
-        ks_timer_begin(ctx, "msd_scatter");
-        if (segs) hipLaunchKernelGGL((k_msd_scatter<256, 1>), dim3(n_tiles1), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)ka, kb, n, shift1, off1, 255u, 0,
-                                     sub_stride, *segs);
-        else hipLaunchKernelGGL((k_msd_scatter<256, 0>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)ka, kb, n, shift1, off1, 255u, 0,
-                                sub_stride, no_segs);
-        ks_timer_end(ctx);
-        sorted_in = kb;
-    }
+    u32 *const blk = P->blk, *off1 = blk, *off2 = blk + 256 * MS_SUB, *big = blk + 256 * MS_SUB + L.off2_words;
+    int st = KS_OK;
+    u64 *sorted_in = kb; // where the partitioned list ends up
     const u32 *off = off1;
-    if (st == KS_OK && bits2 > 0) {
+    if (bits2 > 0) {
         ks_timer_begin(ctx, "msd_hist");
-        if (bits2 <= 8) hipLaunchKernelGGL((k_msd_hist<512>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)kb, n, shift2, off2, mask2, bits2, 0u, no_segs);
-        else hipLaunchKernelGGL((k_msd_hist<1024>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)kb, n, shift2, off2, mask2, bits2, 0u, no_segs);
+        if (bits2 <= 8) hipLaunchKernelGGL((k_msd_hist<512>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)kb, n, L.shift2, off2, L.mask2, bits2, 0u, no_segs);
+        else hipLaunchKernelGGL((k_msd_hist<1024>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)kb, n, L.shift2, off2, L.mask2, bits2, 0u, no_segs);
         ks_timer_end(ctx);
         st = ks_scan_u32_inplace(ctx, off2, n_buckets, nullptr);
         if (st == KS_OK) {
             ks_timer_begin(ctx, "msd_scatter");
-            if (bits2 <= 8) hipLaunchKernelGGL((k_msd_scatter<512>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)kb, ka, n, shift2, off2, mask2, bits2, 0u, no_segs);
-            else hipLaunchKernelGGL((k_msd_scatter<1024>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)kb, ka, n, shift2, off2, mask2, bits2, 0u, no_segs);
+            if (bits2 <= 8) hipLaunchKernelGGL((k_msd_scatter<512>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)kb, ka, n, L.shift2, off2, L.mask2, bits2, 0u, no_segs);
+            else hipLaunchKernelGGL((k_msd_scatter<1024>), dim3(n_tiles), dim3(MS_THREADS), 0, ctx->stream, (const u64 *)kb, ka, n, L.shift2, off2, L.mask2, bits2, 0u, no_segs);
             ks_timer_end(ctx);
             sorted_in = ka;
             off = off2;
@@ -477,18 +514,29 @@ int ks_sort_pairs_msd(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbit
         u64 *other = sorted_in == ka ? kb : ka;
         ks_timer_begin(ctx, "msd_local");
         hipLaunchKernelGGL(k_msd_local, dim3((n_buckets + ML_WAVES - 1) / ML_WAVES), dim3(ML_THREADS), 0, ctx->stream, sorted_in, off,
-                           n_buckets, lo_bit, shift2 - lo_bit, lds_cap, big);
+                           n_buckets, lo_bit, L.shift2 - lo_bit, lds_cap, big);
         ks_timer_end(ctx);
         ks_timer_begin(ctx, "msd_local_big");
         hipLaunchKernelGGL(k_msd_local_big, dim3(n_buckets < 2048 ? n_buckets : 2048), dim3(ML_THREADS), 0, ctx->stream, sorted_in, other, off,
-                           (const u32 *)big, lo_bit, shift2 - lo_bit, lds_cap);
+                           (const u32 *)big, lo_bit, L.shift2 - lo_bit, lds_cap);
         ks_timer_end(ctx);
         if (sorted_in != ka) // (one partition level only: the sorted list sits in the scratch buffer)
             if (hipMemcpyAsync(ka, kb, (size_t)n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
                 st = ks_fail(ctx, KS_ERR_HIP, "msd sort: copy back failed");
         if (st == KS_OK && hipGetLastError() != hipSuccess) st = ks_fail(ctx, KS_ERR_HIP, "msd sort launch failed");
-        if (st == KS_OK) *done = 1;
     }
-    ks_pool_free(ctx, blk);
+    ks_msd_drop(ctx, P);
     return st;
+}
+
+// Sorts the n packed match records of `ka` on their key bits [lo_bit, lo_bit + nbits) (kb: scratch of the same size).
+// *done = 0 when the list is too small / the key too narrow for this path to pay (the caller takes the LSD sort).
+int ks_sort_pairs_msd(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbits, int *done, const ks_msd_segs *segs) {
+    *done = 0;
+    ks_msd_plan P;
+    KS_TRY(ks_msd_level1(ctx, ka, kb, n, lo_bit, nbits, segs, &P));
+    if (!P.blk) return KS_OK;
+    KS_TRY(ks_msd_finish(ctx, &P));
+    *done = 1;
+    return KS_OK;
 }

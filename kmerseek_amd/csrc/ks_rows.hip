@@ -185,6 +185,180 @@ __global__ __launch_bounds__(PF_THREADS) void k_pair_rows_fused(const u64 *keys,
 }
 
 // ---------------------------------------------------------------------------------------------
+// Level-1 regions of the match sort -> COO rows by HASH aggregation (k_pairs_aggregate).  The rows need the records grouped by
+// (qid, tid) with a count and an abundance sum, and the groups in order — not a totally ordered list.  Where many records share
+// a row (80 at 1M x 1M protein k = 10) grouping by hash and sorting only the groups is that many times the smaller sort: the
+// two further moves of the list, the in-LDS radix sort and the run-length pass (0.39 ms of that step) become ONE read of the
+// level-1 output.  Workgroup r owns region r (every (qid, tid) lies wholly inside one region, regions ascend in the ids):
+//   1. every record goes into an open-addressing table in LDS, keyed by record >> abits: an LDS compare-and-swap claims the
+//      slot, two LDS adds count the record and sum its abundance.  Linear probing with wrap-around, at most n_slots probes: a
+//      record that finds no slot raises the overflow word, the workgroup stops inserting, and the host resumes the sort on the
+//      untouched list.  No loop here is unbounded.  A thread's eight records of burst t + 1 are requested before burst t is
+//      inserted, and the first probes of a burst's eight records are in flight together: with many records per row nearly
+//      every record finds its key there and is two adds without a return value; only a miss walks the probe loop.
+//   2. the region's group count is published for the decoupled look-back (ks_device.h) BEFORE the sort, so the successors'
+//      walks find it early; the occupied slots are then compacted to the front of the table and sorted by key with a bitonic
+//      network over the next power of two at or above the group count (a quarter of the slots at 1M x 1M: 55 steps of 512
+//      pairs instead of 78 of 2,048)
+//   3. wave 0 walks back for the rows of the regions before this one; the groups leave as rows base .. base + groups - 1
+// The list is read once.  Rows beyond `rows_cap` are dropped and the host repeats the launch, as for k_pair_rows_fused.
+// ---------------------------------------------------------------------------------------------
+#define AG_THREADS 1024
+#define AG_IPT 8
+#define AG_SLOTS 4096 // 20 bytes per slot: 80 KB of the CU's 160 KB LDS
+#define AG_EMPTY (~0ULL) // (a key has at most 63 bits: the records keep at least one abundance bit)
+static_assert(AG_SLOTS % AG_THREADS == 0 && (AG_SLOTS & (AG_SLOTS - 1)) == 0, "the bitonic network walks a power of two");
+
+// key k (abundance w) into the table, probing from `slot`: false = no slot within n_slots probes
+KS_DEV bool ag_insert(unsigned long long *keys, unsigned long long *sums, u32 *cnts, u32 *n_used, unsigned long long k,
+                      unsigned long long w, u32 slot, u32 n_slots) {
+    for (u32 p = 0; p < n_slots; p++) {
+        unsigned long long cur = __hip_atomic_load(&keys[slot], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (cur == AG_EMPTY) {
+            cur = atomicCAS(&keys[slot], AG_EMPTY, k);
+            if (cur == AG_EMPTY) { atomicAdd(n_used, 1u); cur = k; }
+        }
+        if (cur == k) {
+            atomicAdd(&cnts[slot], 1u);
+            atomicAdd(&sums[slot], w);
+            return true;
+        }
+        slot = slot + 1 == n_slots ? 0 : slot + 1;
+    }
+    return false;
+}
+
+__global__ __launch_bounds__(AG_THREADS) void k_pairs_aggregate(const u64 *list, const u32 *ends, u32 n_slots, u32 *qid, u32 *tid, u32 *isect,
+                                                                unsigned long long *nw, int tbits, int abits, u32 rows_cap,
+                                                                unsigned long long *status,
+                                                                u32 *ctl /* [0] a table overflowed, [1] a look-back gave up, [2] rows */) {
+    __shared__ unsigned long long keys[AG_SLOTS];
+    __shared__ unsigned long long sums[AG_SLOTS];
+    __shared__ u32 cnts[AG_SLOTS];
+    __shared__ u32 n_used, n_packed, oflow;
+    __shared__ unsigned long long base_s;
+    const u32 tid_ = threadIdx.x, lane = tid_ & 63, wave = tid_ >> 6, region = blockIdx.x;
+    for (u32 i = tid_; i < AG_SLOTS; i += AG_THREADS) { keys[i] = AG_EMPTY; sums[i] = 0; cnts[i] = 0; }
+    if (tid_ == 0) { n_used = 0; n_packed = 0; oflow = 0; }
+    const u64 s = region ? ends[region - 1] : 0, e = ends[region];
+    const u64 am = (1ULL << abits) - 1ULL;
+    // (every load is issued, past the region's end at a clamped index: loads under a branch cannot be counted, and the wait for
+    // burst t would then also wait for burst t + 1)
+    const u64 last = e ? e - 1 : 0;
+    u64 nxt[AG_IPT];
+#pragma unroll
+    for (int r = 0; r < AG_IPT; r++) {
+        const u64 i = s + (u64)r * AG_THREADS + tid_;
+        nxt[r] = list[i < e ? i : last];
+    }
+    __syncthreads();
+    for (u64 t0 = s; t0 < e; t0 += AG_THREADS * AG_IPT) {
+        u64 rec[AG_IPT];
+#pragma unroll
+        for (int r = 0; r < AG_IPT; r++) rec[r] = nxt[r];
+#pragma unroll
+        for (int r = 0; r < AG_IPT; r++) { // the next burst is on its way while this one is inserted
+            const u64 i = t0 + (u64)(AG_IPT + r) * AG_THREADS + tid_;
+            nxt[r] = list[i < e ? i : last];
+        }
+        if (*(volatile u32 *)&oflow) break; // (once per burst: a region that overflowed is not read to its end)
+        u32 slot[AG_IPT];
+        unsigned long long seen[AG_IPT];
+#pragma unroll
+        for (int r = 0; r < AG_IPT; r++) { // all first probes of the burst together: one LDS latency, not eight
+            const unsigned long long k = rec[r] >> abits;
+            slot[r] = __umulhi((u32)((k * 0x9E3779B97F4A7C15ULL) >> 32), n_slots); // (< n_slots)
+            seen[r] = __hip_atomic_load(&keys[slot[r]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+#pragma unroll
+        for (int r = 0; r < AG_IPT; r++) {
+            const u64 i = t0 + (u64)r * AG_THREADS + tid_;
+            if (i >= e) continue;
+            const unsigned long long k = rec[r] >> abits, w = rec[r] & am;
+            if (seen[r] == k) {
+                atomicAdd(&cnts[slot[r]], 1u);
+                atomicAdd(&sums[slot[r]], w);
+            } else if (!ag_insert(keys, sums, cnts, &n_used, k, w, slot[r], n_slots)) {
+                oflow = 1u;
+            }
+        }
+    }
+    __syncthreads();
+    // an overflowed region publishes no groups: its successors must not wait for it, and the host drops every row anyway
+    const u32 groups = oflow ? 0u : n_used;
+    if (tid_ == 0) {
+        if (oflow) atomicOr(&ctl[0], 1u);
+        __hip_atomic_store(&status[region], (region == 0 ? KS_LB_PRE : KS_LB_AGG) | (u64)groups, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (groups > 0) { // (uniform)
+        // the occupied slots to [0, groups), in any order: every thread takes its slots into registers, then writes where they lay
+        unsigned long long ck[AG_SLOTS / AG_THREADS], cs[AG_SLOTS / AG_THREADS];
+        u32 cc[AG_SLOTS / AG_THREADS];
+#pragma unroll
+        for (int j = 0; j < AG_SLOTS / AG_THREADS; j++) {
+            const u32 i = (u32)j * AG_THREADS + tid_;
+            ck[j] = keys[i]; cs[j] = sums[i]; cc[j] = cnts[i];
+        }
+        u32 p2 = 1;
+        while (p2 < groups) p2 <<= 1; // (groups <= n_slots <= AG_SLOTS)
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < AG_SLOTS / AG_THREADS; j++) {
+            const bool occ = ck[j] != AG_EMPTY;
+            const u64 m = __ballot(occ);
+            u32 b = 0;
+            if (lane == 0 && m) b = atomicAdd(&n_packed, (u32)__popcll(m));
+            b = (u32)__builtin_amdgcn_readfirstlane((int)b);
+            if (occ) {
+                const u32 d = b + ks_lane_lt_count(m); // (< groups: every occupied slot was counted in n_used)
+                keys[d] = ck[j]; sums[d] = cs[j]; cnts[d] = cc[j];
+            }
+        }
+        for (u32 i = groups + tid_; i < p2; i += AG_THREADS) keys[i] = AG_EMPTY; // (empty = the largest key: stays behind the groups)
+        __syncthreads();
+        // bitonic network over [0, p2), a pair per thread and step: ascending, the groups end up in [0, groups)
+        for (u32 k2 = 2; k2 <= p2; k2 <<= 1) {
+            for (u32 j = k2 >> 1; j > 0; j >>= 1) {
+                for (u32 t = tid_; t < p2 / 2; t += AG_THREADS) {
+                    const u32 i = ((t & ~(j - 1)) << 1) | (t & (j - 1)), o = i | j;
+                    const unsigned long long a = keys[i], b = keys[o];
+                    if ((a > b) == ((i & k2) == 0) && a != b) {
+                        keys[i] = b; keys[o] = a;
+                        const unsigned long long sa = sums[i]; sums[i] = sums[o]; sums[o] = sa;
+                        const u32 ca = cnts[i]; cnts[i] = cnts[o]; cnts[o] = ca;
+                    }
+                }
+                __syncthreads();
+            }
+        }
+    }
+    if (wave == 0) {
+        u64 excl = 0;
+        if (region > 0) {
+            excl = ks_lookback_walk(region, lane, ks_lookback_words(status), &ctl[1]); // gave up: the host resumes the sort
+            if (lane == 0)
+                __hip_atomic_store(&status[region], KS_LB_PRE | (excl + groups), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+        if (lane == 0) {
+            base_s = excl;
+            if (region == gridDim.x - 1) ctl[2] = (u32)(excl + groups); // the last region knows the row count
+        }
+    }
+    __syncthreads();
+    const u64 base = base_s;
+    for (u32 i = tid_; i < groups; i += AG_THREADS) {
+        const u64 row = base + i;
+        if (row < rows_cap) {
+            const unsigned long long k = keys[i];
+            qid[row] = (u32)(k >> tbits);
+            tid[row] = (u32)(k & ((1ULL << tbits) - 1ULL));
+            isect[row] = cnts[i];
+            nw[row] = sums[i];
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
 // KS_SEARCH_ABUND_STATS: per-row statistics of the shared target abundances.  The match sort then also orders the abundance
 // bits, so the records of row r — [row_start[r], row_start[r] + isect[r]) of the sorted list — ascend in abundance, and the
 // statistics replay a host loop over the sorted abundances operation for operation: sum += a, mean = sum / n, then
@@ -342,11 +516,46 @@ static int se_rows_post(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits *F
     return KS_OK;
 }
 
-// run-length reduce of the sorted matches into H's rows: one fused pass (k_pair_rows_fused); F: see se_rows_post
-static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F, const u64 *pk) {
+// Above how many records per row of the previous search the aggregate pass is taken.  DESIGN.md 3.2 [r6] has the measurements:
+// the aggregate pass won at every multiplicity that fits the tables, down to 2.5, and nothing below was measured — 8 is that
+// lowest winning point with a margin on the sort's side, not a crossover.  The rows per region it is trusted with: half of
+// the slots, over the regions the batch can fill (the regions are the top 8 id bits: a batch just above a power of two
+// reaches only half of them).  A search whose tables overflowed is remembered by its row count: the pass is not tried again
+// on this context until a search expects under half as many rows (no wasted launch and wait on every search of a steady
+// workload that is skewed beyond the average the capacity rule sees).
+#define KS_AGG_MIN_MULT 8.0
+#define KS_AGG_REGION_ROWS (AG_SLOTS / 2)
+
+bool ks_rows_agg_wanted(const ks_ctx *ctx, const ks_rows_in &Q) {
+    if (Q.stats || Q.n_pairs == 0) return false; // (the statistics read the sorted list)
+    if (const char *f = ks_dbg(ctx, KS_DBG_ROWS_PATH)) return strcmp(f, "agg") == 0;
+    // (a knob that forces a path of the sort's later levels or of its row pass asks for that pass)
+    if (ks_dbg(ctx, KS_DBG_MSD_LDS_CAP) || ks_dbg(ctx, KS_DBG_ROWS_TICKET) || ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY)) return false;
+    if (!(ctx->rows_mult > KS_AGG_MIN_MULT)) return false;
+    const u32 n_q = Q.q->n_seqs;
+    const int qbits = Q.qbits;
+    const u64 regions = qbits >= 8 && n_q ? ((u64)(n_q - 1) >> (qbits - 8)) + 1 : (u64)KS_MSD_REGIONS;
+    const double rows = (double)Q.n_pairs / ctx->rows_mult;
+    if (ctx->agg_oflow_rows && rows * 2.0 > (double)ctx->agg_oflow_rows) return false;
+    return rows <= (double)(regions * KS_AGG_REGION_ROWS);
+}
+
+void ks_rows_agg_overflowed(ks_ctx *ctx, u64 n_rows) {
+    if (ks_dbg(ctx, KS_DBG_ROWS_PATH)) return; // (a forced path leaves no history)
+    if (!ctx->agg_oflow_rows || n_rows < ctx->agg_oflow_rows) ctx->agg_oflow_rows = n_rows ? n_rows : 1;
+}
+
+// the matches into H's rows in one pass: the run-length reduce of the sorted list pk (k_pair_rows_fused), or — A != nullptr — the
+// hash aggregation of the level-1 regions of the match sort (k_pairs_aggregate; *fell_back: see ks_search_rows_agg); F: see se_rows_post
+static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F, const u64 *pk, const ks_msd_plan *A, bool *fell_back) {
     const u64 n_pairs = Q.n_pairs;
     const int tbits = Q.tbits, abits = Q.abits;
-    const u32 pf_tiles = (u32)((n_pairs + PF_TILE - 1) / PF_TILE);
+    const u32 pf_tiles = A ? (u32)KS_MSD_REGIONS : (u32)((n_pairs + PF_TILE - 1) / PF_TILE);
+    u32 agg_slots = AG_SLOTS;
+    if (const char *f = ks_dbg(ctx, KS_DBG_AGG_CAP)) { // (tests: full tables, wrapping probe chains and the overflow on small inputs)
+        const long v = atol(f);
+        if (v >= 1 && v < AG_SLOTS) agg_slots = (u32)v;
+    }
     // The row count is only known on the device here.  Instead of a round trip before the pass, the row arrays take
     // their size from the previous search of this context (+ 25 %) and the count is read with the final
     // synchronisation; a search that produced more rows than that repeats the (cheap) pass with exact arrays.
@@ -367,13 +576,23 @@ static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F,
         unsigned long long *const pf_status = (unsigned long long *)(H->d_block + rows_cap);
         u32 *const pf_ticket = (u32 *)(pf_status + pf_tiles);
         KS_HIP(ctx, hipMemsetAsync(H->d_block, 0, ((size_t)rows_cap + st_words + is_words) * sizeof(u64), ctx->stream));
-        KS_LAUNCH(ctx, "pair_rows", k_pair_rows_fused, pf_tiles, PF_THREADS, pk, n_pairs, H->d_qid, H->d_tid, H->d_isect,
-                  (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, pf_ticket + 2,
-                  (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
+        if (A)
+            KS_LAUNCH(ctx, "pairs_aggregate", k_pairs_aggregate, pf_tiles, AG_THREADS, (const u64 *)A->kb, A->ends, agg_slots, H->d_qid,
+                      H->d_tid, H->d_isect, (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket);
+        else
+            KS_LAUNCH(ctx, "pair_rows", k_pair_rows_fused, pf_tiles, PF_THREADS, pk, n_pairs, H->d_qid, H->d_tid, H->d_isect,
+                      (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, pf_ticket + 2,
+                      (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
         if (post) KS_TRY(se_rows_post(ctx, Q, H, &F, pk, (u32)rows_cap, pf_ticket, sc));
         KS_TRY(ks_stream_wait_fetch_scans(ctx, {ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4)})); // ticket pair + row count + kept count
+        if (A && (pin[0] != 0 || pin[1] != 0)) { // a table overflowed / a region waited in vain: no rows from here
+            se_free_cols(ctx, H);
+            se_free_cols(ctx, &F);
+            *fell_back = true;
+            return KS_OK;
+        }
         bool gave_up = pin[1] != 0;
-        if (ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY) && !ctx->rows_use_ticket) gave_up = true; // (tests)
+        if (!A && ks_dbg(ctx, KS_DBG_FORCE_ROWS_TICKET_RETRY) && !ctx->rows_use_ticket) gave_up = true; // (tests)
         if (gave_up) {
             if (ctx->rows_use_ticket || attempt == 2) return ks_fail(ctx, KS_ERR_HIP, "search: row look-back gave up waiting for a predecessor tile");
             ctx->rows_use_ticket = true; // dispatch order did not hold here: tickets from now on
@@ -390,6 +609,8 @@ static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F,
     H->n_hits = n_rows;
     const u64 want = (u64)n_rows + n_rows / 4 + 4096;
     ctx->rows_hint = want > ctx->rows_hint / 2 ? want : ctx->rows_hint / 2; // follows growth at once, decays slowly
+    ctx->rows_mult = (double)n_pairs / (double)(n_rows ? n_rows : 1u); // (ks_rows_agg_wanted: the next search's path)
+    if (A) ctx->agg_used++;
     if (Q.min_c > 0) { // the kept rows replace the row pass's columns
         se_free_cols(ctx, H);
         H->d_qid = F.d_qid; H->d_tid = F.d_tid; H->d_isect = F.d_isect; H->d_nw = F.d_nw;
@@ -404,8 +625,17 @@ int ks_search_rows(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, const u64 *pk) 
     if (Q.n_pairs == 0) return ks_hits_alloc_cols(ctx, H, 0, 0);
     ks_hits F; // the filtered columns (Q.min_c > 0) until they replace H's
     memset(&F, 0, sizeof F);
-    const int st = se_rows_run(ctx, Q, H, F, pk);
+    const int st = se_rows_run(ctx, Q, H, F, pk, nullptr, nullptr);
     se_free_cols(ctx, &F); // (nothing left after a success)
+    return st;
+}
+
+int ks_search_rows_agg(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, const ks_msd_plan &P, bool *fell_back) {
+    *fell_back = false;
+    ks_hits F;
+    memset(&F, 0, sizeof F);
+    const int st = se_rows_run(ctx, Q, H, F, nullptr, &P, fell_back);
+    se_free_cols(ctx, &F);
     return st;
 }
 

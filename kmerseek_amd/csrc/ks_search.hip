@@ -1302,8 +1302,11 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
     return KS_OK;
 }
 
-// sort matches by (qid, tid) on the live id bits only (with Q.stats: by (qid, tid, abundance), all live bits); *pk: the sorted list
-static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk) {
+// sort matches by (qid, tid) on the live id bits only (with Q.stats: by (qid, tid, abundance), all live bits); *pk: the sorted list.
+// agg != nullptr: the rows are to come from the aggregate pass (ks_search_rows_agg) — where the match sort applies it stops
+// behind its first level and *agg is the plan to go on from (agg->blk != nullptr, *pk stays nullptr); where it does not, the
+// list is sorted as usual.
+static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk, ks_msd_plan *agg) {
     const u64 n_pairs = Q.n_pairs;
     const u32 n_segs = Q.n_segs;
     const int tbits = Q.tbits, qbits = Q.qbits, abits = Q.abits;
@@ -1323,7 +1326,14 @@ static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk) {
         }
         sg.tile_start[n_segs] = t;
         for (u32 s_ = n_segs + 1; s_ <= KS_MSD_MAX_SEGS; s_++) sg.tile_start[s_] = t;
+        if (agg) {
+            KS_TRY(ks_msd_level1(ctx, Q.pk0, Q.pk1, n_pairs, lo_bit, nbits, &sg, agg));
+            if (agg->blk) return KS_OK;
+        }
         KS_TRY(ks_sort_pairs_msd(ctx, Q.pk0, Q.pk1, n_pairs, lo_bit, nbits, &msd, &sg));
+    } else if (agg) {
+        KS_TRY(ks_msd_level1(ctx, Q.pk0, Q.pk1, n_pairs, lo_bit, nbits, nullptr, agg));
+        if (agg->blk) return KS_OK;
     }
     if (n_segs > 1 && !msd) { // the segments -> one dense list (then the roles of the two buffers swap: the segmented one is the scratch)
         jn_seg_table tab;
@@ -1349,7 +1359,7 @@ static int se_sort(ks_ctx *ctx, se_search &Q, ks_scratch &sc, u64 **pk) {
 }
 
 // what the row half (ks_rows.hip) needs from a search; a search that matched nothing has n_pairs == 0
-static ks_rows_in se_rows_in(const se_search &Q) { return ks_rows_in{Q.q, Q.n_pairs, Q.tbits, Q.abits, Q.stats, Q.min_c}; }
+static ks_rows_in se_rows_in(const se_search &Q) { return ks_rows_in{Q.q, Q.n_pairs, Q.tbits, Q.abits, Q.stats, Q.min_c, Q.qbits}; }
 
 // Why a search produced nothing and its query batch has to be searched in slices: the match list would hold `pairs` records
 // (more than one list can), or the records of more than `seqs` query sequences would not fit their width.
@@ -1441,7 +1451,25 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, con
     const u64 want = Q.n_pairs + Q.n_pairs / 8;
     ctx->pair_cap_hint = want > ctx->pair_cap_hint / 2 ? want : ctx->pair_cap_hint / 2; // follows growth at once, decays slowly
     u64 *pk = nullptr;
-    if (Q.n_pairs) KS_TRY(se_sort(ctx, Q, sc, &pk));
+    // Rows by hash aggregation of the sort's level-1 regions where the context's history says it pays (ks_rows_agg_wanted), by
+    // the full sort + run-length pass otherwise — and after a region's table overflowed: the sort then resumes on the untouched
+    // level-1 output, one extra wait in that case only.
+    struct agg_plan : ks_msd_plan {
+        ks_ctx *c;
+        explicit agg_plan(ks_ctx *c_) : ks_msd_plan{}, c(c_) {}
+        ~agg_plan() { ks_msd_drop(c, this); } // (an early return keeps no block of the pool)
+    } A(ctx);
+    if (Q.n_pairs) KS_TRY(se_sort(ctx, Q, sc, &pk, ks_rows_agg_wanted(ctx, se_rows_in(Q)) ? &A : nullptr));
+    if (A.blk) {
+        bool fell_back = false;
+        KS_TRY(ks_search_rows_agg(ctx, se_rows_in(Q), H, A, &fell_back));
+        if (!fell_back) return KS_OK;
+        ctx->agg_overflows++;
+        KS_TRY(ks_msd_finish(ctx, &A));
+        KS_TRY(ks_search_rows(ctx, se_rows_in(Q), H, A.ka));
+        ks_rows_agg_overflowed(ctx, (u64)((double)Q.n_pairs / ctx->rows_mult)); // (rows_mult: of this search's rows, just made)
+        return KS_OK;
+    }
     return ks_search_rows(ctx, se_rows_in(Q), H, pk);
 }
 

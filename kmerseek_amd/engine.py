@@ -225,11 +225,16 @@ class Context:
         """Re-read the KS_DEBUG_* variables (diagnostics: the library reads them only when a context is created)."""
         self._check(self._L.ks_ctx_reload_debug_env(self._h))
 
-    def search_stats(self) -> Dict[str, int]:
-        """Repeats ks_search needed so far on this context (see ks_ctx_search_stats)."""
-        v = (C.c_uint64 * 2)()
+    def search_stats(self, paths: bool = False) -> Dict[str, int]:
+        """Repeats ks_search needed so far on this context (see ks_ctx_search_stats): `agg_overflows` counts the searches whose
+        aggregate row pass gave up and resumed the sort.  paths=True adds `agg_used`, the searches whose rows that pass made: a
+        path taken, not a repeat, so it grows in normal operation while every other counter here stands still."""
+        v = (C.c_uint64 * 4)()
         self._check(self._L.ks_ctx_search_stats(self._h, C.byref(v)))
-        return {"join_retries": int(v[0]), "rows_ticket_fallbacks": int(v[1])}
+        out = {"join_retries": int(v[0]), "rows_ticket_fallbacks": int(v[1]), "agg_overflows": int(v[3])}
+        if paths:
+            out["agg_used"] = int(v[2])
+        return out
 
     # ---- sketch ----
     def sketch_batch(self, residues: np.ndarray, offsets: np.ndarray, ksize: int, scaled: int, moltype: str,
@@ -342,10 +347,11 @@ class Context:
         return {"seen": int(v[0]), "dropped": int(v[1])}
 
     def fused_stats(self) -> Dict[str, int]:
-        """ks_sketch_search_device calls on this context: with the sketch read-back deferred / repeated the plain way."""
-        v = (C.c_uint64 * 2)()
+        """ks_sketch_search_device calls on this context: with the sketch read-back deferred / repeated the plain way / with
+        their rows made by the aggregate pass (`aggregated`: the `agg_used` of search_stats(paths=True), counted per call here)."""
+        v = (C.c_uint64 * 3)()
         self._check(self._L.ks_ctx_fused_stats(self._h, C.byref(v)))
-        return {"deferred": int(v[0]), "redos": int(v[1])}
+        return {"deferred": int(v[0]), "redos": int(v[1]), "aggregated": int(v[2])}
 
     def sketches_from_host(self, offsets: np.ndarray, hashes: np.ndarray, abunds: np.ndarray, ksize: int,
                            scaled: int, moltype: str, seed: int = SEED) -> "Sketches":
