@@ -21,41 +21,7 @@ int ks_fail(ks_ctx *ctx, int status, const char *fmt, ...) {
 
 extern "C" uint32_t ks_abi_version(void) { return KS_ABI_VERSION; }
 
-extern "C" const char *ks_status_string(int s) {
-    switch (s) {
-    case KS_OK: return "ok";
-    case KS_ERR_INVALID_MOLTYPE: return "invalid moltype";
-    case KS_ERR_INVALID_KSIZE: return "invalid k-mer size";
-    case KS_ERR_INVALID_RESIDUE: return "invalid amino acid";
-    case KS_ERR_INVALID_ARG: return "invalid argument";
-    case KS_ERR_OOM: return "out of device memory";
-    case KS_ERR_HIP: return "HIP runtime error";
-    case KS_ERR_NO_DEVICE: return "no HIP device";
-    case KS_ERR_CAPACITY: return "device list capacity exceeded";
-    case KS_ERR_INVALID_SCALED: return "invalid scaled";
-    default: return "unknown status";
-    }
-}
-
-// get_hash_function_from_moltype, src/rust/encoding.rs:17-27
-extern "C" int ks_moltype_from_string(const char *name, uint32_t *out) {
-    return ks_guard(nullptr, [&]() -> int {
-    if (!name || !out) return KS_ERR_INVALID_ARG;
-    if (!strcmp(name, "protein") || !strcmp(name, "raw")) { *out = KS_PROTEIN; return KS_OK; }
-    if (!strcmp(name, "hp")) { *out = KS_HP; return KS_OK; }
-    if (!strcmp(name, "dayhoff")) { *out = KS_DAYHOFF; return KS_OK; }
-    return KS_ERR_INVALID_MOLTYPE;
-    });
-}
-
-// sourmash max_hash_for_scaled: (u64::MAX as f64 / scaled as f64) as u64, saturating
-extern "C" uint64_t ks_max_hash(uint32_t scaled) {
-    if (scaled == 0) return 0;
-    if (scaled == 1) return UINT64_MAX;
-    double v = 18446744073709551616.0 / (double)scaled;
-    if (v >= 18446744073709551616.0) return UINT64_MAX;
-    return (uint64_t)v;
-}
+// (ks_status_string, ks_moltype_from_string, ks_max_hash and ks_validate_and_resolve touch no device: ks_hostfn.cpp)
 
 bool ks_same_params(const ks_params &a, const ks_params &b) {
     return a.ksize == b.ksize && a.scaled == b.scaled && a.moltype == b.moltype && a.seed == b.seed && a.flags == b.flags;
@@ -660,56 +626,5 @@ extern "C" int ks_bench_gather_rates(ks_ctx *ctx, double *gathers_per_s) {
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     return st;
-    });
-}
-
-// ---- host-side pre-step: AminoAcidAmbiguity::validate_and_resolve, src/rust/aminoacid.rs:74-105 ----
-static inline u64 splitmix64(u64 *s) {
-    u64 z = (*s += 0x9e3779b97f4a7c15ULL);
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
-    return z ^ (z >> 31);
-}
-
-extern "C" int ks_validate_and_resolve(const uint8_t *seq, uint64_t len, int upper, uint64_t rng_seed,
-                                       uint8_t *out, uint64_t *out_len, ks_residue_error *err) {
-    return ks_guard(nullptr, [&]() -> int {
-    if ((!seq && len) || !out || !out_len) return KS_ERR_INVALID_ARG;
-    // class LUT: 0 invalid, 1 plain valid (20 standard + X U O), 2 stop, 3/4/5 = B/Z/J.  Called from many packer threads
-    // at once (ks_ingest.cpp, ks_host.cpp): the table is a function-local static built by its initialiser (C++11
-    // guarantees one thread runs it and the others wait), and never written afterwards.
-    struct cls_table {
-        u8 v[256];
-        cls_table() {
-            memset(v, 0, sizeof v);
-            for (const char *p = "ACDEFGHIKLMNPQRSTVWYXUO"; *p; p++) v[(u8)*p] = 1; // aminoacid.rs:8-14
-            v[(u8)'*'] = 2;
-            v[(u8)'B'] = 3; v[(u8)'Z'] = 4; v[(u8)'J'] = 5; // aminoacid.rs:32-36
-        }
-    };
-    static const cls_table cls_tab;
-    const u8 *cls = cls_tab.v;
-    u64 n = 0, rng = rng_seed, bits = 0;
-    int nbits = 0;
-    for (u64 i = 0; i < len; i++) {
-        u8 c = seq[i];
-        if (upper && c >= 'a' && c <= 'z') c = (u8)(c - 32); // index.rs:1000
-        u8 k = cls[c];
-        if (k == 2) { out[n++] = c; break; }                  // aminoacid.rs:79-83
-        if (k == 0) {                                         // aminoacid.rs:85-87
-            if (err) { err->seq_index = 0; err->position = (u32)(n + 1); err->residue = c; }
-            *out_len = n;
-            return KS_ERR_INVALID_RESIDUE;
-        }
-        if (k >= 3) {
-            if (nbits == 0) { bits = splitmix64(&rng); nbits = 64; }
-            int pick = (int)(bits & 1); bits >>= 1; nbits--;
-            static const char *cand[3] = {"DN", "EQ", "IL"};
-            c = (u8)cand[k - 3][pick];
-        }
-        out[n++] = c;
-    }
-    *out_len = n;
-    return KS_OK;
     });
 }

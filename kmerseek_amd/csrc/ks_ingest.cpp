@@ -264,34 +264,48 @@ class Ingest {
     }
 
     // ---- stage 2: packer ------------------------------------------------------------------------------------------
+    // A buffer that is regrown is freed first and its pointer cleared: when the allocation that follows fails, the slot must
+    // not keep the freed pointer for ~Ingest to free a second time.
+    template <typename T>
+    static void drop_host(T *&p) { if (p) (void)hipHostFree(p); p = nullptr; }
+    template <typename T>
+    static void drop_dev(T *&p) { if (p) (void)hipFree(p); p = nullptr; }
     bool ensure_slot(Slot &s, size_t n_res, size_t n_seqs) {
         if (hipSetDevice(device_) != hipSuccess) return false;
         if (n_res + 16 > s.res_cap) {
-            if (s.h_res) (void)hipHostFree(s.h_res);
-            if (s.d_res) (void)hipFree(s.d_res);
-            s.res_cap = (n_res + 16) + (n_res >> 3);
-            if (hipHostMalloc((void **)&s.h_res, s.res_cap) != hipSuccess || hipMalloc((void **)&s.d_res, s.res_cap) != hipSuccess) return false;
+            drop_host(s.h_res);
+            drop_dev(s.d_res);
+            s.res_cap = 0;
+            const size_t cap = (n_res + 16) + (n_res >> 3);
+            if (hipHostMalloc((void **)&s.h_res, cap) != hipSuccess || hipMalloc((void **)&s.d_res, cap) != hipSuccess) return false;
+            s.res_cap = cap;
         }
         if (n_seqs + 1 > s.offs_cap) {
-            if (s.h_offs) (void)hipHostFree(s.h_offs);
-            if (s.d_offs) (void)hipFree(s.d_offs);
-            s.offs_cap = (n_seqs + 1) + (n_seqs >> 3);
-            if (hipHostMalloc((void **)&s.h_offs, s.offs_cap * sizeof(uint64_t)) != hipSuccess ||
-                hipMalloc((void **)&s.d_offs, s.offs_cap * sizeof(uint64_t)) != hipSuccess)
+            drop_host(s.h_offs);
+            drop_dev(s.d_offs);
+            s.offs_cap = 0;
+            const size_t cap = (n_seqs + 1) + (n_seqs >> 3);
+            if (hipHostMalloc((void **)&s.h_offs, cap * sizeof(uint64_t)) != hipSuccess ||
+                hipMalloc((void **)&s.d_offs, cap * sizeof(uint64_t)) != hipSuccess)
                 return false;
+            s.offs_cap = cap;
         }
         if (n_seqs + 1 > s.coffs_cap) {
-            if (s.h_coffs) (void)hipHostFree(s.h_coffs);
-            s.coffs_cap = (n_seqs + 1) + (n_seqs >> 3);
-            if (hipHostMalloc((void **)&s.h_coffs, s.coffs_cap * sizeof(uint64_t)) != hipSuccess) return false;
+            drop_host(s.h_coffs);
+            s.coffs_cap = 0;
+            const size_t cap = (n_seqs + 1) + (n_seqs >> 3);
+            if (hipHostMalloc((void **)&s.h_coffs, cap * sizeof(uint64_t)) != hipSuccess) return false;
+            s.coffs_cap = cap;
         }
         if (n_res + 1 > s.out_cap) { // kept hashes <= windows <= residues
-            if (s.h_hash) (void)hipHostFree(s.h_hash);
-            if (s.h_abund) (void)hipHostFree(s.h_abund);
-            s.out_cap = (n_res + 1) + (n_res >> 3);
-            if (hipHostMalloc((void **)&s.h_hash, s.out_cap * sizeof(uint64_t)) != hipSuccess ||
-                hipHostMalloc((void **)&s.h_abund, s.out_cap * sizeof(uint32_t)) != hipSuccess)
+            drop_host(s.h_hash);
+            drop_host(s.h_abund);
+            s.out_cap = 0;
+            const size_t cap = (n_res + 1) + (n_res >> 3);
+            if (hipHostMalloc((void **)&s.h_hash, cap * sizeof(uint64_t)) != hipSuccess ||
+                hipHostMalloc((void **)&s.h_abund, cap * sizeof(uint32_t)) != hipSuccess)
                 return false;
+            s.out_cap = cap;
         }
         return true;
     }
@@ -407,6 +421,7 @@ class Ingest {
         const unsigned nt = s.n_hashes > (1u << 22) ? 4 : 1;
         auto part = [&](unsigned t) {
             const size_t lo = s.n_hashes * t / nt, hi = s.n_hashes * (t + 1) / nt;
+            if (hi == lo) return; // (a batch that kept no hash: the result arrays may not exist yet, and memcpy takes no NULL)
             memcpy(R.hashes.p + R.hashes.n + lo, s.h_hash + lo, (hi - lo) * sizeof(uint64_t));
             memcpy(R.abunds.p + R.abunds.n + lo, s.h_abund + lo, (hi - lo) * sizeof(uint32_t));
         };
