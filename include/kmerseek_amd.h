@@ -73,6 +73,7 @@ typedef struct ks_hits ks_hits;         /* device-resident COO (qid, tid, inters
 typedef struct ks_kmerpos ks_kmerpos;   /* device-resident (seq, start, hash) triples */
 typedef struct ks_matchpos ks_matchpos; /* device-resident CSR over hit rows: (query start, target start) of shared k-mers */
 typedef struct ks_regions ks_regions;   /* device-resident CSR over hit rows: the colinear regions those pairs chain into */
+typedef struct ks_rscores ks_rscores;   /* device-resident CSR over hit rows: those regions scored and extended (ungapped X-drop) */
 
 /* ---- library / context ------------------------------------------------------------------ */
 
@@ -491,6 +492,74 @@ const uint32_t *ks_regions_device_covered(const ks_regions *r);
 int ks_regions_copy_to_host(ks_ctx *ctx, const ks_regions *r, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
                             uint32_t *length, uint32_t *n_kmers, uint32_t *covered);
 void ks_regions_free(ks_regions *r);
+
+/* ---- region scores: how good is a region?  Substitution-matrix score and ungapped X-drop extension ------------------------- */
+
+/* Scores every region of a ks_regions under a substitution matrix and, on request, extends it without gaps in both
+ * directions under an X-drop rule (the ungapped stage of every seed-and-extend search).  The reference prints the `query`,
+ * `alpha` and `match` strings of a stitched region (src/python/kmerseek/search.py:61-121) and leaves the judging to the eye;
+ * for hp and dayhoff the seeds match in the reduced alphabet only, so the identity in the real alphabet is what this adds.
+ * All arithmetic is in integers: the result is bit-exact against a host loop.
+ *   regions: a ks_regions R;  hits: the ks_hits H whose rows it was chained for — row r = (qid, tid),
+ *            ks_regions_n_rows(R) == ks_hits_count(H)
+ *   the query and the target residue batches on the device (d_res, d_offsets u64[n + 1], n_seqs, n_residues): the layout
+ *   ks_sketch_batch_device and ks_kmer_positions_device read
+ * Residue class of a byte x, after ASCII upper-casing (only a-z change): 'A'..'Z' -> 0..25, '*' -> 26, every other byte -> 27.
+ * Matrix: int8 M[KS_RSCORE_ALPHABET][KS_RSCORE_ALPHABET], row-major, a caller-owned HOST array; the row is the query's class,
+ * the column the target's; it need not be symmetric.  matrix == NULL: M[x][y] = (x == y) ? +1 : -1.
+ * A position pair (i in the query sequence, j in the target sequence): s = M[class(q[i])][class(t[j])]; it is an identity iff
+ * the two upper-cased bytes are equal, a positive iff s > 0.
+ * Region g of row r: a = q_start, b = t_start, n = length; Lq, Lt the lengths of the two sequences.
+ *   core        the n pairs (a + i, b + i);  core_score = the sum of s over them (i64)
+ *   right extension (only with KS_RSCORE_EXTEND): e_max = min(Lq - (a + n), Lt - (b + n));
+ *               S_0 = 0, S_j = S_(j-1) + s(a + n + j - 1, b + n + j - 1) for j = 1 .. e_max;  B_j = max(S_0 .. S_j);
+ *               J = the smallest j >= 1 with B_j - S_j > x_drop, or e_max if there is none;
+ *               right_ext = the smallest j in [0, J] with S_j == B_J (the shortest extension wins a tie);  right_score = B_J
+ *   left extension: the mirror image on the pairs (a - j, b - j), j = 1 .. min(a, b)
+ *   without the flag both extensions are 0
+ * Result (device-resident), the same CSR over hit rows and the same order as R (row_offsets is a copy of R's):
+ *   q_start = a - left_ext, t_start = b - left_ext, length = left_ext + n + right_ext   u32[n_regions]
+ *   score = left_score + core_score + right_score                                        i64[n_regions]
+ *   identities, positives   u32[n_regions]  counted over the extended span
+ *   core_identities         u32[n_regions]  counted over the core alone
+ * Extended regions of one row may overlap or coincide: nothing is merged or de-duplicated.  The result never depends on
+ * the launch geometry or on how many positions a wave examines per step.  An R without rows or regions gives a valid empty
+ * result.
+ * KS_ERR_INVALID_ARG: unknown flags / a non-zero reserved field (checked before any device work, also with ctx == NULL), NULL
+ * arguments, an input of another context, ks_regions_n_rows(R) != ks_hits_count(H); a region that does not lie inside its two
+ * sequences (a + n > Lq or b + n > Lt) or a qid / tid beyond its batch — the inputs do not belong together: ks_last_error
+ * names the first such row, and nothing is read outside the batches.
+ * One stream, synchronous on return, one host wait; all scratch comes from the context's pool. */
+#define KS_RSCORE_ALPHABET 28
+#define KS_RSCORE_EXTEND 1u
+typedef struct ks_rscore_opts {
+    uint32_t flags;        /* KS_RSCORE_EXTEND */
+    uint32_t x_drop;       /* used with KS_RSCORE_EXTEND; 0 stops at the first step below the best */
+    const int8_t *matrix;  /* HOST, 28 x 28 row-major, or NULL: +1 / -1 */
+    uint64_t reserved;     /* 0 */
+} ks_rscore_opts;
+/* opts == NULL: the defaults (no extension, the +1 / -1 matrix) */
+int ks_regions_score(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits,
+                     const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res,
+                     const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res,
+                     const ks_rscore_opts *opts, ks_rscores **out);
+uint64_t ks_rscores_n_rows(const ks_rscores *s);
+uint64_t ks_rscores_n_regions(const ks_rscores *s);
+/* device pointers, valid until ks_rscores_free */
+const uint64_t *ks_rscores_device_row_offsets(const ks_rscores *s);
+const uint32_t *ks_rscores_device_q_start(const ks_rscores *s);
+const uint32_t *ks_rscores_device_t_start(const ks_rscores *s);
+const uint32_t *ks_rscores_device_length(const ks_rscores *s);
+const int64_t *ks_rscores_device_score(const ks_rscores *s);
+const uint32_t *ks_rscores_device_identities(const ks_rscores *s);
+const uint32_t *ks_rscores_device_positives(const ks_rscores *s);
+const uint32_t *ks_rscores_device_core_identities(const ks_rscores *s);
+/* any destination may be NULL */
+int ks_rscores_copy_to_host(ks_ctx *ctx, const ks_rscores *s, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
+                            uint32_t *length, int64_t *score, uint32_t *identities, uint32_t *positives, uint32_t *core_identities);
+void ks_rscores_free(ks_rscores *s);
+/* positions one wave examines per extension step: the tests place terminations around it */
+uint32_t ks_debug_rscore_step(void);
 
 /* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
 

@@ -52,6 +52,14 @@ class ks_regions_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("min_kmers", C.c_uint32), ("max_gap", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+KS_RSCORE_ALPHABET = 28
+KS_RSCORE_EXTEND = 1
+
+
+class ks_rscore_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("x_drop", C.c_uint32), ("matrix", C.POINTER(C.c_int8)), ("reserved", C.c_uint64)]
+
+
 class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -199,6 +207,21 @@ SIGNATURES = {
     "ks_regions_device_covered": (_vp, [_vp]),
     "ks_regions_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ks_regions_free": (None, [_vp]),
+    "ks_regions_score": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64,
+                                   C.POINTER(ks_rscore_opts), _pp]),
+    "ks_rscores_n_rows": (C.c_uint64, [_vp]),
+    "ks_rscores_n_regions": (C.c_uint64, [_vp]),
+    "ks_rscores_device_row_offsets": (_vp, [_vp]),
+    "ks_rscores_device_q_start": (_vp, [_vp]),
+    "ks_rscores_device_t_start": (_vp, [_vp]),
+    "ks_rscores_device_length": (_vp, [_vp]),
+    "ks_rscores_device_score": (_vp, [_vp]),
+    "ks_rscores_device_identities": (_vp, [_vp]),
+    "ks_rscores_device_positives": (_vp, [_vp]),
+    "ks_rscores_device_core_identities": (_vp, [_vp]),
+    "ks_rscores_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ks_rscores_free": (None, [_vp]),
+    "ks_debug_rscore_step": (C.c_uint32, []),
     "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
     "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
     "ks_corpus_n_docs": (C.c_uint32, [_vp]),

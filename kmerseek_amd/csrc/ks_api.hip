@@ -615,6 +615,62 @@ extern "C" int ks_hits_merge_by_qid_device(ks_ctx *ctx, const uint32_t *d_qid, c
     });
 }
 
+// ---------------------------------------------------------------------------------------------
+// region scores (ks_rscore.hip): the regions of a hit list scored under a substitution matrix, extended without gaps
+// ---------------------------------------------------------------------------------------------
+extern "C" int ks_regions_score(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
+                                const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_rscore_opts *opts, ks_rscores **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (opts) KS_TRY(ks_opts_words_check(ctx, "region score", opts->flags, KS_RSCORE_EXTEND, opts->reserved ? 1u : 0u));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!regions || !hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    KS_TRY(ks_inputs_check_ctx(ctx, "region scores", regions, hits));
+    if (regions->n_rows != hits->n_hits)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "region scores: the regions cover %llu hit rows, the hit list holds %llu: regions of another list",
+                       (unsigned long long)regions->n_rows, (unsigned long long)hits->n_hits);
+    if (regions->n_regions && (!d_q_res || !d_q_offs || !d_t_res || !d_t_offs)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL device buffer");
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_rscores> S(ctx, out, ks_rscores_free);
+    KS_TRY(ks_regions_score_impl(ctx, regions, hits, {d_q_res, d_q_offs, n_q, n_q_res}, {d_t_res, d_t_offs, n_t, n_t_res}, opts, S));
+    return S.commit();
+    });
+}
+extern "C" uint64_t ks_rscores_n_rows(const ks_rscores *s) { return s ? s->n_rows : 0; }
+extern "C" uint64_t ks_rscores_n_regions(const ks_rscores *s) { return s ? s->n_regions : 0; }
+extern "C" const uint64_t *ks_rscores_device_row_offsets(const ks_rscores *s) { return s ? s->d_row_offsets : nullptr; }
+extern "C" const uint32_t *ks_rscores_device_q_start(const ks_rscores *s) { return s ? s->d_qstart : nullptr; }
+extern "C" const uint32_t *ks_rscores_device_t_start(const ks_rscores *s) { return s ? s->d_tstart : nullptr; }
+extern "C" const uint32_t *ks_rscores_device_length(const ks_rscores *s) { return s ? s->d_length : nullptr; }
+extern "C" const int64_t *ks_rscores_device_score(const ks_rscores *s) { return s ? s->d_score : nullptr; }
+extern "C" const uint32_t *ks_rscores_device_identities(const ks_rscores *s) { return s ? s->d_identities : nullptr; }
+extern "C" const uint32_t *ks_rscores_device_positives(const ks_rscores *s) { return s ? s->d_positives : nullptr; }
+extern "C" const uint32_t *ks_rscores_device_core_identities(const ks_rscores *s) { return s ? s->d_core_ident : nullptr; }
+
+extern "C" int ks_rscores_copy_to_host(ks_ctx *ctx, const ks_rscores *s, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
+                                       uint32_t *length, int64_t *score, uint32_t *identities, uint32_t *positives,
+                                       uint32_t *core_identities) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !s) return KS_ERR_INVALID_ARG;
+    const size_t nr = (size_t)s->n_rows, ng = (size_t)s->n_regions;
+    return ks_columns_to_host(ctx, {{row_offsets, s->d_row_offsets, (nr + 1) * sizeof(u64)},
+                                    {q_start, s->d_qstart, ng * sizeof(u32)}, {t_start, s->d_tstart, ng * sizeof(u32)},
+                                    {length, s->d_length, ng * sizeof(u32)}, {score, s->d_score, ng * sizeof(i64)},
+                                    {identities, s->d_identities, ng * sizeof(u32)}, {positives, s->d_positives, ng * sizeof(u32)},
+                                    {core_identities, s->d_core_ident, ng * sizeof(u32)}});
+    });
+}
+
+extern "C" void ks_rscores_free(ks_rscores *s) {
+    if (!s) return;
+    ks_pool_free(s->ctx, s->d_row_offsets);
+    ks_pool_free(s->ctx, s->d_qstart); ks_pool_free(s->ctx, s->d_tstart); ks_pool_free(s->ctx, s->d_length);
+    ks_pool_free(s->ctx, s->d_score); ks_pool_free(s->ctx, s->d_identities); ks_pool_free(s->ctx, s->d_positives);
+    ks_pool_free(s->ctx, s->d_core_ident);
+    delete s;
+}
+
 extern "C" int ks_hits_has_abund_stats(const ks_hits *h) { return h && h->has_stats ? 1 : 0; }
 extern "C" const uint64_t *ks_hits_device_median2(const ks_hits *h) { return h && h->has_stats ? h->d_median2 : nullptr; }
 extern "C" const double *ks_hits_device_abund_ss(const ks_hits *h) { return h && h->has_stats ? h->d_ss : nullptr; }

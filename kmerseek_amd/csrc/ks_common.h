@@ -342,13 +342,14 @@ enum : u32 {
     KS_PIN_GREEDY = 216,     // 10 words, greedy clusters: the five of KS_PIN_CLUSTER | the two live-edge counts | undecided nodes | rounds | members without a representative
     KS_PIN_TRANSLATE = 226,  // 4 words, six-frame translation: bad offsets | the frames' residue count (the last frame offset)
     KS_PIN_UNION = 230,      // 2 words, union by group: distinct (group, hash) runs
-    KS_PIN_END = 232,
+    KS_PIN_RSCORE = 232,     // 1 word, region scores: first row whose regions do not lie inside its sequences (ks_rscore.hip)
+    KS_PIN_END = 233,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -443,6 +444,20 @@ struct ks_regions {
     u64 *d_row_offsets;                                 // n_rows + 1
     u32 *d_qstart, *d_tstart, *d_length, *d_nkmers, *d_covered; // n_regions
 };
+
+// the regions of a ks_regions scored under a substitution matrix and extended without gaps (ks_rscore.hip)
+struct ks_rscores {
+    ks_ctx *ctx;
+    u64 n_rows, n_regions;
+    u64 *d_row_offsets;                                                              // n_rows + 1
+    u32 *d_qstart, *d_tstart, *d_length, *d_identities, *d_positives, *d_core_ident; // n_regions
+    i64 *d_score;                                                                    // n_regions
+};
+// one residue batch on the device, as the C ABI passes it
+struct ks_res_batch { const u8 *res; const u64 *offs; u32 n_seqs; u64 n_res; };
+// ks_regions_score behind its argument checks (opts: validated; R, H: of ctx, equal row counts)
+int ks_regions_score_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
+                          const ks_rscore_opts *opts, ks_rscores *S);
 
 // clusters of a hit list read as a graph: its connected components (ks_cluster.hip) or greedy representative clusters (ks_greedy.hip)
 struct ks_clusters {

@@ -442,6 +442,51 @@ class Context:
         self._check(self._L.ks_match_regions(self._h, mp._h, C.byref(opts), C.byref(out)))
         return Regions(self, out)
 
+    @staticmethod
+    def _rscore_opts(matrix, extend: bool, x_drop: int):
+        """(ks_rscore_opts, the int8 array its matrix pointer reads: keep it alive for the call)"""
+        if not 0 <= int(x_drop) < 2 ** 32:
+            raise ValueError(f"x_drop = {x_drop} does not fit 32 bits")
+        m = None
+        if matrix is not None:
+            m = np.asarray(matrix)
+            if m.shape != (_lib.KS_RSCORE_ALPHABET, _lib.KS_RSCORE_ALPHABET) or m.dtype != np.int8:
+                raise ValueError("matrix must be an int8 array of shape (28, 28)")
+            m = np.ascontiguousarray(m)
+        mp = m.ctypes.data_as(C.POINTER(C.c_int8)) if m is not None else None
+        return _lib.ks_rscore_opts(_lib.KS_RSCORE_EXTEND if extend else 0, int(x_drop), mp, 0), m
+
+    def score_regions_device(self, regions: "Regions", hits: "Hits", d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
+                             d_t_res: int, d_t_off: int, n_t: int, n_t_res: int, matrix=None, extend: bool = False,
+                             x_drop: int = 0) -> "RegionScores":
+        """ks_regions_score from device-resident residue batches (raw pointers: residues u8, offsets u64[n + 1]): every region
+        of `regions` — chained for the rows of `hits` — scored under `matrix` (int8 [28, 28], the query's residue class is the
+        row: A..Z, '*', everything else; None: +1 / -1) and, with extend=True, extended without gaps to both sides under the
+        X-drop rule.  Per region the (extended) q_start, t_start, length, the score (i64), identities and positives over the
+        extended span and the identities of the seed region alone; include/kmerseek_amd.h has the definitions."""
+        opts, keep = self._rscore_opts(matrix, extend, x_drop)
+        out = C.c_void_p()
+        self._check(self._L.ks_regions_score(self._h, regions._h, hits._h, C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res),
+                                             C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res), C.byref(opts), C.byref(out)))
+        del keep
+        return RegionScores(self, out)
+
+    def score_regions(self, regions: "Regions", hits: "Hits", q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray,
+                      t_off: np.ndarray, matrix=None, extend: bool = False, x_drop: int = 0) -> "RegionScores":
+        """score_regions_device from host arrays (the batches `hits` was searched on): uploaded, scored, released."""
+        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        self._rscore_opts(matrix, extend, x_drop)  # (refused before anything is uploaded)
+        bufs = []
+        try:
+            for a in (q_res, q_off, t_res, t_off):
+                bufs.append(self.to_device(a))
+            return self.score_regions_device(regions, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res), bufs[2].ptr, bufs[3].ptr,
+                                             len(t_off) - 1, len(t_res), matrix=matrix, extend=extend, x_drop=x_drop)
+        finally:
+            for b in bufs:
+                b.free()
+
     def significance(self, queries: "Sketches", targets: "Sketches", hits: "Hits", q_corpus: Optional["Corpus"] = None,
                      t_corpus: Optional["Corpus"] = None) -> "Significance":
         """ks_hits_significance: per row of `hits` the two f64 sums behind multisearch's prob_overlap and tf_idf_score, over the
@@ -820,6 +865,35 @@ class Regions(_Owned):
         offs = np.zeros(self.n_rows + 1, np.uint64)
         cols = [np.zeros(self.n_regions, np.uint32) for _ in range(5)]
         self._ctx._check(self._ctx._L.ks_regions_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
+        return (offs, *cols)
+
+
+class RegionScores(_Owned):
+    """Device-resident scores of the regions of a hit list (ks_rscores): the CSR of the Regions they were made from, per region
+    the extended placement, the score, identities, positives and the identities of the seed region alone."""
+    _free = "ks_rscores_free"
+    _COLUMNS = ("row_offsets", "q_start", "t_start", "length", "score", "identities", "positives", "core_identities")
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_rscores_n_rows(self._h))
+
+    @property
+    def n_regions(self) -> int:
+        return int(self._ctx._L.ks_rscores_n_regions(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (row_offsets u64[n_rows + 1]; q_start, t_start, length u32, score i64, identities, positives,
+        core_identities u32, each [n_regions])."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_rscores_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """(row_offsets u64[n_rows + 1], q_start, t_start, length u32, score i64, identities, positives, core_identities u32)."""
+        n = self.n_regions
+        offs = np.zeros(self.n_rows + 1, np.uint64)
+        cols = [np.zeros(n, np.int64 if c == "score" else np.uint32) for c in self._COLUMNS[1:]]
+        self._ctx._check(self._ctx._L.ks_rscores_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
         return (offs, *cols)
 
 

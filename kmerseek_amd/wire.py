@@ -665,36 +665,101 @@ def stitch_match_positions(q_records: Sequence[Tuple[str, bytes]], t_records: Se
     return out
 
 
+def read_score_matrix(path: str) -> np.ndarray:
+    """A substitution matrix in the NCBI text format (BLOSUM62, PAM250, ...: `#` comment lines, a header line of symbols, then
+    one row per symbol: the symbol and one integer per header column) as the int8 [28, 28] array of Context.score_regions: row =
+    the query's residue class, column = the target's; classes A..Z -> 0..25, `*` -> 26, everything else -> 27.  Symbols outside
+    A-Z and `*` are ignored; every pair the file does not give gets the file's smallest value.  ValueError: no header, a row
+    whose value count is not the header's, a value that is not an integer or does not fit int8, a symbol given twice."""
+    def cls(sym):
+        if len(sym) == 1 and "A" <= sym <= "Z":
+            return ord(sym) - ord("A")
+        return 26 if sym == "*" else None
+
+    header, seen, given, values = None, set(), {}, []
+    with open(path) as f:
+        for no, line in enumerate(f, 1):
+            line = line.split("#", 1)[0].split()
+            if not line:
+                continue
+            if header is None:
+                header = line
+                if len(set(header)) != len(header):
+                    raise ValueError(f"{path}:{no}: a symbol appears twice in the header")
+                continue
+            sym, cells = line[0], line[1:]
+            if len(cells) != len(header):
+                raise ValueError(f"{path}:{no}: row {sym!r} holds {len(cells)} values, the header names {len(header)} symbols")
+            if sym in seen:
+                raise ValueError(f"{path}:{no}: row {sym!r} appears twice")
+            seen.add(sym)
+            for col, cell in zip(header, cells):
+                try:
+                    v = int(cell)
+                except ValueError:
+                    raise ValueError(f"{path}:{no}: {cell!r} is not an integer") from None
+                if not -128 <= v <= 127:
+                    raise ValueError(f"{path}:{no}: {v} does not fit int8")
+                values.append(v)
+                if cls(sym) is not None and cls(col) is not None:
+                    given[(cls(sym), cls(col))] = v
+    if header is None or not values:
+        raise ValueError(f"{path}: no matrix rows")
+    m = np.full((28, 28), min(values), np.int8)
+    for (x, y), v in given.items():
+        m[x, y] = v
+    return m
+
+
 def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, regions_host,
-                moltype: str) -> List[dict]:
+                moltype: str, scores=None) -> List[dict]:
     """One row per region of the device's chaining (Context.match_regions; regions_host = Regions.to_host()): hit row
     r = (qid[r], tid[r]) owns regions [row_offsets[r], row_offsets[r + 1]).  The stitched columns of search.py:195-240 —
     query / match / encoded are the residues the region spans, sliced from the records (a region lies on one diagonal, so
     no stitching is left to do) — plus n_kmers and covered.  Where a match is one colinear run the row equals the
     reference's stitched row; where it is not, every run gets a row of its own.  Sorted by (query's place in q_records,
-    query_start, query_end)."""
+    query_start, query_end).
+
+    scores = RegionScores.to_host() of the same regions (Context.score_regions): the rows are those of the scored — with
+    extend=True extended — regions: query_start / query_end, match_start / match_end, query / match / encoded and length span
+    the extended region, and the columns score, identities, positives, pident (100 * identities / length) and seed_start /
+    seed_length (the original region's query_start and length) are added."""
     offs, q_start, t_start, length, n_kmers, covered = [np.asarray(c).tolist() for c in regions_host]
+    if scores is not None:
+        s_offs, s_q, s_t, s_len, s_score, s_ident, s_pos, _ = [np.asarray(c).tolist() for c in scores]
+        if s_offs != offs:
+            raise ValueError("scores and regions are not of the same hit rows")
     out = []
     for r, (q, t) in enumerate(zip(np.asarray(qid).tolist(), np.asarray(tid).tolist())):
         qn, qseq = q_records[q]
         tn, tseq = t_records[t]
         for g in range(offs[r], offs[r + 1]):
-            a, b, n = q_start[g], t_start[g], length[g]
+            a, b, n = (q_start[g], t_start[g], length[g]) if scores is None else (s_q[g], s_t[g], s_len[g])
             query = qseq[a:a + n].decode().upper()
-            out.append((q, {"match_name": tn, "query_name": qn, "query_start": a, "query_end": a + n, "query": query,
-                            "match_start": b, "match_end": b + n, "match": tseq[b:b + n].decode().upper(),
-                            "encoded": encode_kmer(query, moltype), "length": n, "n_kmers": n_kmers[g], "covered": covered[g]}))
+            row = {"match_name": tn, "query_name": qn, "query_start": a, "query_end": a + n, "query": query,
+                   "match_start": b, "match_end": b + n, "match": tseq[b:b + n].decode().upper(),
+                   "encoded": encode_kmer(query, moltype), "length": n, "n_kmers": n_kmers[g], "covered": covered[g]}
+            if scores is not None:
+                row.update({"score": s_score[g], "identities": s_ident[g], "positives": s_pos[g],
+                            "pident": format_f64(100.0 * float(s_ident[g]) / float(n) if n else math.nan),
+                            "seed_start": q_start[g], "seed_length": length[g]})
+            out.append((q, row))
     out.sort(key=lambda e: (e[0], e[1]["query_start"], e[1]["query_end"]))
     return [row for _, row in out]
 
 
 def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int, scaled: int, moltype: str,
                                 ctx: Optional[Context] = None, regions: bool = False, max_gap: int = 0,
-                                min_kmers: int = 1) -> List[dict]:
+                                min_kmers: int = 1, score: bool = False, extend: bool = False, x_drop: int = 0,
+                                matrix=None) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
-    max_gap / min_kmers) and only the regions come to the host: the rows of `region_rows`, one per colinear run."""
+    max_gap / min_kmers) and only the regions come to the host: the rows of `region_rows`, one per colinear run.
+    score=True (needs regions=True): the regions are scored on the device too (Context.score_regions with matrix, extend and
+    x_drop) and the rows carry the columns `region_rows` adds for scores."""
+    if score and not regions:
+        raise ValueError("score=True needs regions=True: scores are of regions")
     own = ctx is None
     ctx = ctx or Context(0)
     try:
@@ -712,9 +777,14 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
         if regions:
             rg = ctx.match_regions(mp, max_gap=max_gap, min_kmers=min_kmers)
             rg_host = rg.to_host()
+            sc_host = None
+            if score:
+                sc = ctx.score_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, extend=extend, x_drop=x_drop)
+                sc_host = sc.to_host()
+                sc.free()
             for o in (rg, mp, qp, tp, hits, Q, T):
                 o.free()
-            return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype)
+            return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host)
         offs, qs, ts = mp.to_host()[:3]
         for o in (mp, qp, tp, hits, Q, T):
             o.free()
