@@ -1,5 +1,6 @@
 // ks_api.hip — the extern "C" entry points of include/kmerseek_amd.h that move data across the
-// boundary (host buffers <-> HBM) and own the opaque result objects, plus the k-mer position kernel.
+// boundary (host buffers <-> HBM) and own the opaque result objects (the hit list: ks_hits.hip), plus the k-mer
+// position kernel.
 #include "ks_device.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -408,51 +409,6 @@ extern "C" int ks_sketch_search(ks_ctx *ctx, const ks_index *index, const uint8_
     return ks_sketch_search_ex(ctx, index, residues, seq_offsets, n_seqs, nullptr, sketches_out, hits_out);
     });
 }
-extern "C" uint64_t ks_hits_count(const ks_hits *h) { return h ? h->n_hits : 0; }
-extern "C" uint64_t ks_hits_n_pair_instances(const ks_hits *h) { return h ? h->n_pair_instances : 0; }
-extern "C" int ks_hits_partition_path(const ks_hits *h) {
-    return ks_guard(nullptr, [&]() -> int { return h ? h->partition_path : -1; 
-    });
-}
-extern "C" int ks_hits_bucket_posting_bytes(const ks_hits *h) {
-    return ks_guard(nullptr, [&]() -> int { return h ? h->bucket_posting_bytes : -1;
-    });
-}
-extern "C" int ks_hits_copy_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t *qid, uint32_t *tid, uint32_t *intersect,
-                                    uint64_t *n_weighted) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !h) return KS_ERR_INVALID_ARG;
-    const size_t n = (size_t)h->n_hits;
-    return ks_columns_to_host(ctx, {{qid, h->d_qid, n * sizeof(u32)}, {tid, h->d_tid, n * sizeof(u32)},
-                                    {intersect, h->d_isect, n * sizeof(u32)}, {n_weighted, h->d_nw, n * sizeof(u64)}});
-    });
-}
-extern "C" const uint32_t *ks_hits_device_qid(const ks_hits *h) { return h ? h->d_qid : nullptr; }
-extern "C" const uint32_t *ks_hits_device_tid(const ks_hits *h) { return h ? h->d_tid : nullptr; }
-extern "C" const uint32_t *ks_hits_device_intersect(const ks_hits *h) { return h ? h->d_isect : nullptr; }
-extern "C" const uint64_t *ks_hits_device_n_weighted(const ks_hits *h) { return h ? h->d_nw : nullptr; }
-
-__global__ __launch_bounds__(256) void k_copy_add_u32(const u32 *in, u32 *out, u64 n, u32 add) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = in[i] + add;
-}
-
-extern "C" int ks_hits_copy_to_device(ks_ctx *ctx, const ks_hits *h, uint32_t qid_base, uint32_t tid_base, uint32_t *d_qid,
-                                      uint32_t *d_tid, uint32_t *d_intersect, uint64_t *d_n_weighted) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !h) return KS_ERR_INVALID_ARG;
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    const u64 n = h->n_hits;
-    if (n == 0) return KS_OK;
-    const u32 g = (u32)((n + 255) / 256);
-    if (d_qid) KS_LAUNCH(ctx, "hits_copy", k_copy_add_u32, g, 256, (const u32 *)h->d_qid, d_qid, n, qid_base);
-    if (d_tid) KS_LAUNCH(ctx, "hits_copy", k_copy_add_u32, g, 256, (const u32 *)h->d_tid, d_tid, n, tid_base);
-    if (d_intersect) KS_HIP(ctx, hipMemcpyAsync(d_intersect, h->d_isect, (size_t)n * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
-    if (d_n_weighted) KS_HIP(ctx, hipMemcpyAsync(d_n_weighted, h->d_nw, (size_t)n * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
-    return KS_OK;
-    });
-}
-
 // ---- packed transport records (multi-GPU hit exchange) ---------------------------------------------------------------
 // A COO row is 20 bytes (qid u32, tid u32, intersect u32, n_weighted u64); an all-vs-all of 200k proteins gathers 31 M of
 // them, and over xGMI the exchange — not the kernels — is the step.  For transport a row travels as ONE 64-bit word
@@ -669,33 +625,4 @@ extern "C" void ks_rscores_free(ks_rscores *s) {
     ks_pool_free(s->ctx, s->d_score); ks_pool_free(s->ctx, s->d_identities); ks_pool_free(s->ctx, s->d_positives);
     ks_pool_free(s->ctx, s->d_core_ident);
     delete s;
-}
-
-extern "C" int ks_hits_has_abund_stats(const ks_hits *h) { return h && h->has_stats ? 1 : 0; }
-extern "C" const uint64_t *ks_hits_device_median2(const ks_hits *h) { return h && h->has_stats ? h->d_median2 : nullptr; }
-extern "C" const double *ks_hits_device_abund_ss(const ks_hits *h) { return h && h->has_stats ? h->d_ss : nullptr; }
-extern "C" int ks_hits_copy_abund_stats_to_host(ks_ctx *ctx, const ks_hits *h, uint64_t *median2, double *ss) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (!h) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    if (!h->has_stats) return ks_fail(ctx, KS_ERR_INVALID_ARG, "these hits were searched without KS_SEARCH_ABUND_STATS");
-    const size_t n = (size_t)h->n_hits;
-    return ks_columns_to_host(ctx, {{median2, h->d_median2, n * sizeof(u64)}, {ss, h->d_ss, n * sizeof(double)}});
-    });
-}
-
-extern "C" void ks_hits_free(ks_hits *h) {
-    if (!h) return;
-    ks_pool_free(h->ctx, h->d_qid);
-    ks_pool_free(h->ctx, h->d_tid);
-    if (h->d_block) ks_pool_free(h->ctx, h->d_block); // (d_isect and d_nw lie inside it)
-    else { ks_pool_free(h->ctx, h->d_isect); ks_pool_free(h->ctx, h->d_nw); }
-    ks_pool_free(h->ctx, h->d_median2);
-    ks_pool_free(h->ctx, h->d_ss);
-    ks_pool_free(h->ctx, h->d_rank);
-    ks_pool_free(h->ctx, h->d_src_row);
-    ks_pool_free(h->ctx, h->d_ga_unique);
-    ks_pool_free(h->ctx, h->d_ga_remaining);
-    ks_pool_free(h->ctx, h->d_ga_weighted);
-    delete h;
 }

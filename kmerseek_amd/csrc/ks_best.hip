@@ -11,7 +11,7 @@
 //            then one sweep in row order keeps the rows above the threshold and, of those equal to it, the first `quota` in row
 //            order (= the smallest tids), then the kept rows are ranked among themselves by counting (every row that beats a
 //            kept row is kept itself, so this is the rank inside the whole segment), BH_CHUNK opponents in LDS at a time;
-//   move     ks_hits_select_tail: keep flags -> one-launch exclusive scan -> one scatter of all columns (rf_move) + rank + src_row.
+//   move     ks_hits_select_tail (ks_hits.hip): keep flags -> one-launch exclusive scan -> one scatter of all columns (rf_move) + rank + src_row.
 // Every comparison is on (u64 key, row index): integers.  No f64 atomics, no reductions of scores: a row's rank and whether it
 // is kept do not depend on the path its segment took (KS_DEBUG_BEST_PATH = 1 every segment by a wave, 2 by a workgroup,
 // 3 by a workgroup with a chunk of BH_CHUNK_SMALL rows — the tests reach the streamed case with a few hundred rows).
@@ -175,74 +175,12 @@ __global__ __launch_bounds__(256) void k_best_wg(const u64 *key, const u32 *segs
     }
 }
 
-// the kept rows to their places: all columns, the rank and the row's index in the input (+ the gather columns: ks_hits_gather)
-__global__ __launch_bounds__(256) void k_best_move(rf_cols in, u32 n_rows, const u32 *dst, const u32 *rank, u32 cap, u32 *qid, u32 *tid, u32 *isect,
-                                                   u64 *nw, u64 *median2, double *ss, u32 *o_rank, u32 *o_src, ks_gather_cols ga, u32 *o_unique,
-                                                   u32 *o_remaining, u64 *o_weighted) {
-    const u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rows) return;
-    const u32 rk = rank[r], o = dst[r];
-    if (rk == BH_NONE || o >= cap) return;
-    rf_move(in, r, o, qid, tid, isect, nw, median2, ss);
-    o_rank[o] = rk;
-    o_src[o] = r;
-    if (ga.unique) { o_unique[o] = ga.unique[r]; o_remaining[o] = ga.remaining[r]; o_weighted[o] = ga.weighted[r]; }
-}
-
-int ks_hits_alloc_cols(ks_ctx *ctx, ks_hits *H, size_t n, u32 extra) {
-    KS_TRY(ks_alloc(ctx, &H->d_qid, n)); KS_TRY(ks_alloc(ctx, &H->d_tid, n));
-    KS_TRY(ks_alloc(ctx, &H->d_isect, n)); KS_TRY(ks_alloc(ctx, &H->d_nw, n));
-    if (H->has_stats) { KS_TRY(ks_alloc(ctx, &H->d_median2, n)); KS_TRY(ks_alloc(ctx, &H->d_ss, n)); }
-    if (extra & KS_COLS_RANKED) { KS_TRY(ks_alloc(ctx, &H->d_rank, n)); KS_TRY(ks_alloc(ctx, &H->d_src_row, n)); }
-    if (extra & KS_COLS_GATHER) {
-        KS_TRY(ks_alloc(ctx, &H->d_ga_unique, n)); KS_TRY(ks_alloc(ctx, &H->d_ga_remaining, n)); KS_TRY(ks_alloc(ctx, &H->d_ga_weighted, n));
-    }
-    return KS_OK;
-}
-
-void ks_hits_inherit(ks_hits *B, const ks_hits *H) {
-    B->n_pair_instances = H->n_pair_instances;
-    B->partition_path = H->partition_path;
-    B->bucket_posting_bytes = H->bucket_posting_bytes;
-    B->has_stats = H->has_stats;
-}
-
-int ks_hits_move_ranked(ks_ctx *ctx, const ks_hits *H, u32 n_rows, const u32 *dst, const u32 *rank, u32 cap, ks_hits *B,
-                        const ks_gather_cols *ga) {
-    const rf_cols in{H->d_qid, H->d_tid, H->d_isect, H->d_nw, H->has_stats ? H->d_median2 : nullptr, H->has_stats ? H->d_ss : nullptr};
-    KS_LAUNCH(ctx, "best_move", k_best_move, (n_rows + 255) / 256, 256, in, n_rows, dst, rank, cap, B->d_qid, B->d_tid, B->d_isect, B->d_nw,
-              B->d_median2, B->d_ss, B->d_rank, B->d_src_row, ga ? *ga : ks_gather_cols{nullptr, nullptr, nullptr}, B->d_ga_unique,
-              B->d_ga_remaining, B->d_ga_weighted);
-    return KS_OK;
-}
-
-int ks_hits_select_plan(ks_ctx *ctx, const char *what, const ks_hits *H, const ks_sketches *Q, u32 per_query, u32 *n, u64 *cap) {
-    if (H->n_hits >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "%s: 2^32 - 2 or more hit rows", what);
-    *n = (u32)H->n_hits;
-    *cap = *n;
-    if (Q && per_query && (u64)Q->n_seqs * per_query < *cap) *cap = (u64)Q->n_seqs * per_query;
-    return KS_OK;
-}
-
-int ks_hits_select_tail(ks_ctx *ctx, const char *what, const ks_hits *H, u32 n_rows, u32 *flags, const u32 *rank, u64 cap,
-                        const ks_gather_cols *ga, const ks_ctl &ctl, u32 kept, const std::function<int()> &checks, ks_hits *B) {
-    KS_TRY(ks_scan_u32_inplace(ctx, flags, n_rows, ctl.low32(kept)));
-    KS_TRY(ks_hits_move_ranked(ctx, H, n_rows, flags, rank, (u32)cap, B, ga));
-    KS_TRY(ks_stream_wait_fetch_scans(ctx, {ctl.fetch()}));
-    KS_TRY(checks());
-    if (ctl[kept] > cap)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "%s: %llu rows kept where at most %llu can be: the rows are not ordered by (qid, tid)", what,
-                       (unsigned long long)ctl[kept], (unsigned long long)cap);
-    B->n_hits = ctl[kept];
-    return KS_OK;
-}
-
 static int best_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *Q, const ks_sketches *T, const double *d_score, const ks_best_opts *o,
                     ks_hits *B) {
     u32 n;
     u64 cap; // every query keeps at most k
     KS_TRY(ks_hits_select_plan(ctx, "best hits", H, Q, o->k, &n, &cap));
-    KS_TRY(ks_hits_alloc_cols(ctx, B, (size_t)cap, KS_COLS_RANKED));
+    KS_TRY(B->alloc(ctx, (size_t)cap, B->has_stats, KS_COLS_RANKED));
     if (n == 0) return KS_OK;
 
     bool small; // (tests: every segment one way; 3 = the workgroup path with a small chunk)
@@ -306,18 +244,5 @@ extern "C" int ks_hits_best(ks_ctx *ctx, const ks_hits *hits, const ks_sketches 
     ks_hits_inherit(B, hits);
     KS_TRY(best_run(ctx, hits, queries, targets, d_score, opts, B));
     return B.commit();
-    });
-}
-
-extern "C" const uint32_t *ks_hits_device_rank(const ks_hits *h) { return h ? h->d_rank : nullptr; }
-extern "C" const uint32_t *ks_hits_device_src_row(const ks_hits *h) { return h ? h->d_src_row : nullptr; }
-
-extern "C" int ks_hits_copy_best_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t *rank, uint32_t *src_row) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (!h) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    if (!h->d_rank) return ks_fail(ctx, KS_ERR_INVALID_ARG, "these hits did not come from ks_hits_best");
-    const size_t n = (size_t)h->n_hits;
-    return ks_columns_to_host(ctx, {{rank, h->d_rank, n * sizeof(u32)}, {src_row, h->d_src_row, n * sizeof(u32)}});
     });
 }

@@ -393,18 +393,22 @@ struct ks_index {
     int pres_bits;
 };
 
-struct ks_hits {
-    ks_ctx *ctx;
-    u64 n_hits;
-    u64 n_pair_instances;
-    int partition_path; // how the query postings reached their join buckets (see ks_hits_partition_path)
-    int bucket_posting_bytes; // bytes per query posting inside the join buckets (12, 10 or 9; 0: no bucket scatter ran)
+// the row columns of a hit list as the kernels read them (rf_move, ks_device.h)
+struct rf_cols {
+    const u32 *qid, *tid, *isect;
+    const u64 *nw, *median2;
+    const double *ss;
+};
+
+// The column set of a hit list: the one owner of the pointers.  Every column is a pool block of its own, or NULL (the list
+// does not have it) — except that d_nw and d_isect point INTO d_block where that is not NULL (the row pass: one allocation and
+// one memset with its status words).  The members (ks_hits.hip) are the only code that knows this.
+enum : u32 { KS_COLS_RANKED = 1u, KS_COLS_GATHER = 2u }; // rank + src_row; the three gather columns
+struct ks_hit_cols {
     u32 *d_qid, *d_tid, *d_isect;
     u64 *d_nw;
-    // != NULL: d_nw and d_isect point INTO this block (with the row pass's status words: one allocation, one memset)
     u64 *d_block;
     // KS_SEARCH_ABUND_STATS: per row 2 x median and sum of squared deviations of the shared target abundances
-    bool has_stats;
     u64 *d_median2;
     double *d_ss;
     // ks_hits_best: per kept row its rank inside its query and its row in the input list; NULL for every other hit list
@@ -413,6 +417,24 @@ struct ks_hits {
     // abundances over the newly covered ones; NULL for every other hit list
     u32 *d_ga_unique, *d_ga_remaining;
     u64 *d_ga_weighted;
+
+    int alloc(ks_ctx *ctx, size_t n, bool with_stats, u32 extra); // n rows: the four columns every list has, the statistics, KS_COLS_*
+    void release(ks_ctx *ctx);                                    // every column back to the pool and NULL (an empty set: no-op)
+    void take(ks_ctx *ctx, ks_hit_cols &from) { release(ctx); *this = from; from = ks_hit_cols{}; } // `from`'s columns replace these
+    // the device view of the row columns.  The statistics are NULL unless the list has them (ks_hits::has_stats): every alloc of a
+    // list's columns is called with that flag, and the row pass (se_rows_post) makes them itself only under it
+    rf_cols rows() const { return rf_cols{d_qid, d_tid, d_isect, d_nw, d_median2, d_ss}; }
+    // the first n rows of `from` to rows [at, at + n) of this set, on the context's stream; stats: both sets have the statistics
+    int append(ks_ctx *ctx, u64 at, const ks_hit_cols &from, u64 n, bool stats);
+};
+
+struct ks_hits : ks_hit_cols {
+    ks_ctx *ctx;
+    u64 n_hits;
+    u64 n_pair_instances;
+    int partition_path; // how the query postings reached their join buckets (see ks_hits_partition_path)
+    int bucket_posting_bytes; // bytes per query posting inside the join buckets (12, 10 or 9; 0: no bucket scatter ran)
+    bool has_stats; // KS_SEARCH_ABUND_STATS: the list has d_median2 and d_ss
 };
 
 struct ks_kmerpos {
@@ -514,10 +536,7 @@ int ks_row_slices_plan(ks_ctx *ctx, int dbg_id, const char *what, int low_bits, 
 // same size; *sorted = where they ended up (ka or kb)
 int ks_sort_live_keys(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int nbits, u64 **sorted);
 
-// ---- a pass that keeps some rows of a hit list and returns a hit list (ks_best.hip; ks_hits_best and ks_hits_gather) ----
-// the columns of a hit list of n rows: the four every list has, the statistics if H->has_stats, and what `extra` asks for
-enum : u32 { KS_COLS_RANKED = 1u, KS_COLS_GATHER = 2u }; // rank + src_row; the three gather columns
-int ks_hits_alloc_cols(ks_ctx *ctx, ks_hits *H, size_t n, u32 extra);
+// ---- hit lists (ks_hits.hip): what the passes that return one share (ks_search, ks_hits_best, ks_hits_gather) ----
 // what a list made of H's rows says about the search that made them
 void ks_hits_inherit(ks_hits *B, const ks_hits *H);
 // Row r of H with rank[r] != KS_RANK_NONE goes to row dst[r] (< cap) of B: all columns of H that B holds, the rank and r itself
@@ -534,6 +553,14 @@ int ks_hits_select_plan(ks_ctx *ctx, const char *what, const ks_hits *H, const k
 // control words refuse — runs before the kept count is held against cap and becomes B->n_hits.
 int ks_hits_select_tail(ks_ctx *ctx, const char *what, const ks_hits *H, u32 n_rows, u32 *flags, const u32 *rank, u64 cap,
                         const ks_gather_cols *ga, const ks_ctl &ctl, u32 kept, const std::function<int()> &checks, ks_hits *B);
+// the hit lists of the slices of one query batch (parts[i]: the queries from firsts[i] on) in one, query ids back to batch numbering
+int ks_hits_concat(ks_ctx *ctx, const std::vector<ks_hits *> &parts, const std::vector<u32> &firsts, bool has_stats, ks_hits **out);
+// a row list for ks_row_list_push (ks_device.h): room for n_rows rows behind its count, the count zeroed
+int ks_row_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t n_rows, u32 **list);
+// a segment list for ks_seg_list_push: room for `cap` segments behind its count, the count zeroed
+int ks_seg_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t cap, u32 **list);
+// the knob that sends every segment one way (tests): 0 by length (unset), 1 by a wave, 2 by a workgroup; 3: 2 with *small set
+int ks_seg_path_knob(const ks_ctx *ctx, int dbg_id, bool *small);
 
 // ---- device-wide primitives (ks_scan.hip, ks_sort.hip) ----
 // exclusive scan of n u32 values into u64 (out[n] = total is also written: out has n+1 entries)
@@ -612,16 +639,10 @@ void ks_msd_drop(ks_ctx *ctx, ks_msd_plan *P);
 int ks_radix_sort_u64(ks_ctx *ctx, int tag, const u64 *keys_in, const u64 *vals_in, u64 *ka, u64 *va, u64 *kb, u64 *vb,
                       u64 n, const int *shifts, int n_shifts, u64 **keys_out, u64 **vals_out);
 
-// ---- sorted list -> runs -> one record per run (ks_rows.hip) ----
+// ---- sorted list -> runs -> one record per run; a search's matches -> rows (ks_rows.hip) ----
 // a dense sketch set sorted by hash: keys / vals (hashes, abundances) and row_start[n_rows + 1] in the caller's scratch
 struct ks_runs { u64 *keys; u32 *vals; u64 *row_start; u32 n_rows; };
 int ks_sorted_runs(ks_ctx *ctx, const ks_sketches *in, ks_scratch &sc, ks_runs *out);
-// a row list for ks_row_list_push (ks_device.h): room for n_rows rows behind its count, the count zeroed
-int ks_row_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t n_rows, u32 **list);
-// a segment list for ks_seg_list_push: room for `cap` segments behind its count, the count zeroed
-int ks_seg_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t cap, u32 **list);
-// the knob that sends every segment one way (tests): 0 by length (unset), 1 by a wave, 2 by a workgroup; 3: 2 with *small set
-int ks_seg_path_knob(const ks_ctx *ctx, int dbg_id, bool *small);
 // what the row half needs from one search; the sorted match list pk becomes H's rows (n_pairs == 0: none, pk is not read)
 struct ks_rows_in { const ks_sketches *q; u64 n_pairs; int tbits, abits; bool stats; double min_c; int qbits; };
 int ks_search_rows(ks_ctx *ctx, const ks_rows_in &R, ks_hits *H, const u64 *pk);
@@ -666,8 +687,8 @@ int ks_index_build_impl(ks_ctx *ctx, const ks_sketches *t, ks_index **out);
 int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hits **out, int *sketch_redo = nullptr,
                    const ks_search_opts *opts = nullptr);
 int ks_search_opts_check(ks_ctx *ctx, const ks_search_opts *opts);
+// ---- six-frame translation and the unions (ks_translate.hip, ks_union.hip) ----
 int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out);
-// ---- six-frame translation and the union by group (ks_translate.hip, ks_union.hip) ----
 // group_offsets: host, checked by the caller (0 first, in->n_seqs last, ascending); in: of ctx.  Synchronous on return.
 int ks_union_groups_impl(ks_ctx *ctx, const ks_sketches *in, const u32 *group_offsets, u32 n_groups, ks_sketches **out);
 // the checks of ks_sketch_translated* that need no device, then translate -> sketch the 6 * n_seqs frames -> union by record

@@ -214,12 +214,7 @@ KS_DEV u32 ks_query_row_begin(const u32 *qid, u32 n_rows, u32 q) { return ks_low
 // sum of the abundances of one run [b, e) of a sorted posting list (the union's and the corpus's record per distinct hash)
 KS_DEV u64 ks_run_abund_sum(const u32 *vals, u64 b, u64 e) { u64 w = 0; for (u64 j = b; j < e; j++) w += vals[j]; return w; }
 
-// ---- the row columns of a hit list, and the move of one row (the compactions of min_containment and of ks_hits_best) ----
-struct rf_cols {
-    const u32 *qid, *tid, *isect;
-    const u64 *nw, *median2;
-    const double *ss;
-};
+// ---- the move of one row of a hit list (rf_cols, ks_common.h: the compactions of min_containment and of ks_hits_best) ----
 KS_DEV void rf_move(const rf_cols &in, u32 r, u32 o, u32 *qid, u32 *tid, u32 *isect, u64 *nw, u64 *median2, double *ss) {
     qid[o] = in.qid[r]; tid[o] = in.tid[r]; isect[o] = in.isect[r]; nw[o] = in.nw[r];
     if (median2) { median2[o] = in.median2[r]; ss[o] = in.ss[r]; }

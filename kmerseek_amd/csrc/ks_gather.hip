@@ -19,7 +19,7 @@
 //              count reaches the best fresh count known — counts only fall, so a stale count is an upper bound and every
 //              other row cannot win; a row whose count fell below min_unique is dead for good.  The winner is the same as with
 //              every row recounted every round: the key holds the row, so the maximum is unique.
-//   move       ks_hits_select_tail (ks_best.hip): keep flags -> one-launch exclusive scan -> ks_hits_move_ranked with the three columns.
+//   move       ks_hits_select_tail (ks_hits.hip): keep flags -> one-launch exclusive scan -> ks_hits_move_ranked with the three columns.
 // No look-back, no spin, no dependency between workgroups: every loop is bounded by the segment's rows or a list's length.
 // KS_DEBUG_GATHER_PATH = 1 every segment by a wave (where the bitmap fits GA_WAVE_BITS), 2 by a workgroup, 3 by a workgroup
 // with GA_LIVE_BITS_SMALL LDS positions — the tests reach the streamed bitmap with a few hundred hashes.
@@ -274,7 +274,7 @@ static int gather_run(ks_ctx *ctx, const ks_hits *H, const ks_sketches *Q, const
     u32 n;
     u64 cap;
     KS_TRY(ks_hits_select_plan(ctx, "gather", H, Q, max_results, &n, &cap));
-    KS_TRY(ks_hits_alloc_cols(ctx, B, (size_t)cap, KS_COLS_RANKED | KS_COLS_GATHER));
+    KS_TRY(B->alloc(ctx, (size_t)cap, B->has_stats, KS_COLS_RANKED | KS_COLS_GATHER));
     if (n == 0) return KS_OK;
     if (Q->n_hashes == 0 || T->n_hashes == 0)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "gather: %llu hit rows, but a sketch set is empty: the inputs do not belong together",
@@ -341,21 +341,5 @@ extern "C" int ks_hits_gather(ks_ctx *ctx, const ks_hits *hits, const ks_sketche
     KS_TRY(gather_run(ctx, hits, queries, targets, min_u, opts ? opts->max_results : 0u, B));
     if (hits->n_hits == 0) KS_TRY(ks_stream_wait(ctx)); // (a dense copy may be queued: the pass is synchronous on return)
     return B.commit();
-    });
-}
-
-extern "C" const uint32_t *ks_hits_device_unique_intersect(const ks_hits *h) { return h ? h->d_ga_unique : nullptr; }
-extern "C" const uint32_t *ks_hits_device_remaining(const ks_hits *h) { return h ? h->d_ga_remaining : nullptr; }
-extern "C" const uint64_t *ks_hits_device_unique_weighted(const ks_hits *h) { return h ? h->d_ga_weighted : nullptr; }
-
-extern "C" int ks_hits_copy_gather_to_host(ks_ctx *ctx, const ks_hits *h, uint32_t *unique_intersect, uint32_t *remaining,
-                                           uint64_t *unique_weighted) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (!h) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    if (!h->d_ga_unique) return ks_fail(ctx, KS_ERR_INVALID_ARG, "these hits did not come from ks_hits_gather");
-    const size_t n = (size_t)h->n_hits;
-    return ks_columns_to_host(ctx, {{unique_intersect, h->d_ga_unique, n * sizeof(u32)}, {remaining, h->d_ga_remaining, n * sizeof(u32)},
-                                    {unique_weighted, h->d_ga_weighted, n * sizeof(u64)}});
     });
 }

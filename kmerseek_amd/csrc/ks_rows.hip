@@ -1,6 +1,6 @@
-// ks_rows.hip — from a sorted list to one record per run of equal keys: ks_sorted_runs (a sketch set's hashes: the union, here, and
-// the corpus, ks_signif.hip, emit one record per distinct hash) and ks_search_rows (a search's sorted matches -> rows, then per row
-// the abundance statistics and the containment filter).
+// ks_rows.hip — from a sorted list to one record per run of equal keys: ks_sorted_runs (a sketch set's hashes: the union,
+// ks_union.hip, and the corpus, ks_signif.hip, emit one record per distinct hash) and ks_search_rows / ks_search_rows_agg (a
+// search's matches, sorted or by level-1 region -> rows, then per row the abundance statistics and the containment filter).
 #include "ks_device.h"
 
 // ---------------------------------------------------------------------------------------------
@@ -451,39 +451,15 @@ __global__ __launch_bounds__(256) void k_rows_filter(rf_cols in, const u32 *n_ro
     rf_move(in, r, dst[r], qid, tid, isect, nw, median2, ss);
 }
 
-// the row columns of H (and the statistics) back to the pool
-static void se_free_cols(ks_ctx *ctx, ks_hits *H) {
-    ks_pool_free(ctx, H->d_qid); ks_pool_free(ctx, H->d_tid);
-    if (H->d_block) ks_pool_free(ctx, H->d_block); // (d_isect and d_nw lie inside it)
-    else { ks_pool_free(ctx, H->d_isect); ks_pool_free(ctx, H->d_nw); }
-    ks_pool_free(ctx, H->d_median2); ks_pool_free(ctx, H->d_ss);
-    H->d_qid = H->d_tid = H->d_isect = nullptr;
-    H->d_nw = H->d_block = H->d_median2 = nullptr;
-    H->d_ss = nullptr;
-}
-
 // The wave grids of the two row splits stay two numbers: each is the launch shape its kernel was measured with.  The statistics
 // list the few rows longer than RA_LONG (self-hits); the significance pass lists most rows of a scaled = 1 search (SG_WAVE_GRID).
 #define RA_LONG_GRID 256 // workgroups of k_row_abund_stats_long (4 waves each, striding over the long rows)
-
-int ks_row_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t n_rows, u32 **list) {
-    KS_TRY(sc.alloc(list, n_rows + 1));
-    KS_HIP(ctx, hipMemsetAsync(*list, 0, sizeof(u32), ctx->stream));
-    return KS_OK;
-}
-int ks_seg_list_alloc(ks_ctx *ctx, ks_scratch &sc, size_t cap, u32 **list) { return ks_row_list_alloc(ctx, sc, 2 * cap, list); }
-int ks_seg_path_knob(const ks_ctx *ctx, int dbg_id, bool *small) {
-    const char *f = ks_dbg(ctx, dbg_id);
-    const int v = f ? atoi(f) : 0;
-    *small = v == 3;
-    return v == 1 ? 1 : (v == 2 || v == 3) ? 2 : 0;
-}
 
 // Behind the row pass of one attempt and before its wait: the statistics into H's columns (Q.stats) and the rows that pass
 // the containment test into F (Q.min_c > 0).  The kernels take the row count from the device (ticket[2]; an attempt with more
 // rows than rows_cap is repeated anyway) and the scan of the keep flags writes the kept count to ticket[3], which the row
 // pass's read-back brings home with the row count: no wait of its own.
-static int se_rows_post(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits *F, const u64 *pk, u32 rows_cap, u32 *ticket, ks_scratch &sc) {
+static int se_rows_post(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hit_cols &F, const u64 *pk, u32 rows_cap, u32 *ticket, ks_scratch &sc) {
     const u32 *n_rows_dev = ticket + 2;
     const u32 g = (rows_cap + 255) / 256;
     if (Q.stats) {
@@ -502,16 +478,15 @@ static int se_rows_post(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits *F
     if (Q.min_c > 0) {
         const ks_sketches *q = Q.q;
         const u32 *counts = q->gapped ? q->d_counts : nullptr; // (a gapped batch: distinct hashes per query; else the CSR's runs)
-        const rf_cols in{H->d_qid, H->d_tid, H->d_isect, H->d_nw, H->d_median2, H->d_ss};
+        const rf_cols in = H->rows();
         u32 *flags = nullptr;
         KS_TRY(sc.alloc(&flags, rows_cap));
         KS_LAUNCH(ctx, "rows_keep", k_rows_keep, g, 256, in, n_rows_dev, rows_cap, (const u64 *)q->d_offsets, counts, q->n_seqs, Q.min_c,
                   flags);
         KS_TRY(ks_scan_u32_inplace(ctx, flags, rows_cap, ticket + 3));
-        F->has_stats = Q.stats;
-        KS_TRY(ks_hits_alloc_cols(ctx, F, rows_cap, 0));
+        KS_TRY(F.alloc(ctx, rows_cap, Q.stats, 0));
         KS_LAUNCH(ctx, "rows_filter", k_rows_filter, g, 256, in, n_rows_dev, rows_cap, (const u64 *)q->d_offsets, counts, q->n_seqs, Q.min_c,
-                  (const u32 *)flags, F->d_qid, F->d_tid, F->d_isect, F->d_nw, F->d_median2, F->d_ss);
+                  (const u32 *)flags, F.d_qid, F.d_tid, F.d_isect, F.d_nw, F.d_median2, F.d_ss);
     }
     return KS_OK;
 }
@@ -546,8 +521,8 @@ void ks_rows_agg_overflowed(ks_ctx *ctx, u64 n_rows) {
 }
 
 // the matches into H's rows in one pass: the run-length reduce of the sorted list pk (k_pair_rows_fused), or — A != nullptr — the
-// hash aggregation of the level-1 regions of the match sort (k_pairs_aggregate; *fell_back: see ks_search_rows_agg); F: see se_rows_post
-static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F, const u64 *pk, const ks_msd_plan *A, bool *fell_back) {
+// hash aggregation of the level-1 regions of the match sort (k_pairs_aggregate; *fell_back: see ks_search_rows_agg)
+static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, const u64 *pk, const ks_msd_plan *A, bool *fell_back) {
     const u64 n_pairs = Q.n_pairs;
     const int tbits = Q.tbits, abits = Q.abits;
     const u32 pf_tiles = A ? (u32)KS_MSD_REGIONS : (u32)((n_pairs + PF_TILE - 1) / PF_TILE);
@@ -562,10 +537,17 @@ static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F,
     u64 rows_cap = n_pairs;
     if (ctx->rows_hint && ctx->rows_hint < rows_cap && !ks_dbg(ctx, KS_DBG_NO_ROWS_HINT)) rows_cap = ctx->rows_hint;
     u32 n_rows = 0;
+    bool settled = false;
+    struct se_cols_scope : ks_hit_cols { // the filtered columns (Q.min_c > 0, se_rows_post) until they replace H's: released on every way out
+        ks_ctx *ctx;
+        explicit se_cols_scope(ks_ctx *c) : ks_hit_cols{}, ctx(c) {}
+        ~se_cols_scope() { release(ctx); }
+    } F(ctx);
     const u32 *pin = (const u32 *)(ctx->h_pin + KS_PIN_ROWS); // ticket pair | row count | kept rows (min_containment)
     const bool post = Q.stats || Q.min_c > 0;
     for (int attempt = 0; attempt < 3; attempt++) { // (repeats: more rows than the guess; a look-back that gave up)
         ks_scratch sc(ctx); // (the statistics' and the filter's scratch of this attempt)
+        H->release(ctx); F.release(ctx); // (what the attempt before this one left)
         KS_TRY(ks_alloc(ctx, &H->d_qid, (size_t)rows_cap)); KS_TRY(ks_alloc(ctx, &H->d_tid, (size_t)rows_cap));
         // n_weighted (u64) | status words + ticket pair + row count + kept count (u64) | intersect (u32): one block, zeroed
         // together, per attempt (one memset, one read-back)
@@ -583,11 +565,10 @@ static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F,
             KS_LAUNCH(ctx, "pair_rows", k_pair_rows_fused, pf_tiles, PF_THREADS, pk, n_pairs, H->d_qid, H->d_tid, H->d_isect,
                       (unsigned long long *)H->d_nw, tbits, abits, (u32)rows_cap, pf_status, pf_ticket, pf_ticket + 2,
                       (ctx->rows_use_ticket || ks_dbg(ctx, KS_DBG_ROWS_TICKET)) ? 1 : 0);
-        if (post) KS_TRY(se_rows_post(ctx, Q, H, &F, pk, (u32)rows_cap, pf_ticket, sc));
+        if (post) KS_TRY(se_rows_post(ctx, Q, H, F, pk, (u32)rows_cap, pf_ticket, sc));
         KS_TRY(ks_stream_wait_fetch_scans(ctx, {ks_fetch_words(pf_ticket, ctx->h_pin + KS_PIN_ROWS, 4)})); // ticket pair + row count + kept count
         if (A && (pin[0] != 0 || pin[1] != 0)) { // a table overflowed / a region waited in vain: no rows from here
-            se_free_cols(ctx, H);
-            se_free_cols(ctx, &F);
+            H->release(ctx);
             *fell_back = true;
             return KS_OK;
         }
@@ -599,88 +580,29 @@ static int se_rows_run(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, ks_hits &F,
             ctx->rows_ticket_fallbacks++;
         } else {
             n_rows = pin[2];
-            if (n_rows <= rows_cap) break;
+            if (n_rows <= rows_cap) { settled = true; break; }
             rows_cap = n_rows;
         }
-        se_free_cols(ctx, H);
-        se_free_cols(ctx, &F);
     }
-    if (!H->d_qid) return ks_fail(ctx, KS_ERR_HIP, "search: the row pass did not settle");
+    if (!settled) return ks_fail(ctx, KS_ERR_HIP, "search: the row pass did not settle");
     H->n_hits = n_rows;
     const u64 want = (u64)n_rows + n_rows / 4 + 4096;
     ctx->rows_hint = want > ctx->rows_hint / 2 ? want : ctx->rows_hint / 2; // follows growth at once, decays slowly
     ctx->rows_mult = (double)n_pairs / (double)(n_rows ? n_rows : 1u); // (ks_rows_agg_wanted: the next search's path)
     if (A) ctx->agg_used++;
     if (Q.min_c > 0) { // the kept rows replace the row pass's columns
-        se_free_cols(ctx, H);
-        H->d_qid = F.d_qid; H->d_tid = F.d_tid; H->d_isect = F.d_isect; H->d_nw = F.d_nw;
-        H->d_median2 = F.d_median2; H->d_ss = F.d_ss;
+        H->take(ctx, F);
         H->n_hits = pin[3];
-        memset(&F, 0, sizeof F);
     }
     return KS_OK;
 }
 
 int ks_search_rows(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, const u64 *pk) {
-    if (Q.n_pairs == 0) return ks_hits_alloc_cols(ctx, H, 0, 0);
-    ks_hits F; // the filtered columns (Q.min_c > 0) until they replace H's
-    memset(&F, 0, sizeof F);
-    const int st = se_rows_run(ctx, Q, H, F, pk, nullptr, nullptr);
-    se_free_cols(ctx, &F); // (nothing left after a success)
-    return st;
+    if (Q.n_pairs == 0) return H->alloc(ctx, 0, H->has_stats, 0);
+    return se_rows_run(ctx, Q, H, pk, nullptr, nullptr);
 }
 
 int ks_search_rows_agg(ks_ctx *ctx, const ks_rows_in &Q, ks_hits *H, const ks_msd_plan &P, bool *fell_back) {
     *fell_back = false;
-    ks_hits F;
-    memset(&F, 0, sizeof F);
-    const int st = se_rows_run(ctx, Q, H, F, nullptr, &P, fell_back);
-    se_free_cols(ctx, &F);
-    return st;
-}
-
-// ---------------------------------------------------------------------------------------------
-// union of all sketches with summed abundances: the "combined minhash" of ProteomeIndex::store_signatures
-// (src/rust/index.rs:800-830, add_many_with_abund under a mutex there; here one sort + run-length reduce)
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_union_emit(const u64 *keys, const u32 *vals, const u64 *row_start, u32 n_rows,
-                                                    u64 *hashes, u32 *abunds) {
-    u32 r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n_rows) return;
-    const u64 b = row_start[r], w = ks_run_abund_sum(vals, b, row_start[r + 1]);
-    hashes[r] = keys[b];
-    abunds[r] = w > 0xffffffffULL ? 0xffffffffu : (u32)w;
-}
-
-static int union_run(ks_ctx *ctx, const ks_sketches *in, ks_sketches *U) {
-    const u64 n = in->n_hashes;
-    KS_TRY(ks_alloc(ctx, &U->d_offsets, 2));
-    if (n == 0) {
-        KS_HIP(ctx, hipMemsetAsync(U->d_offsets, 0, 2 * sizeof(u64), ctx->stream));
-        KS_TRY(ks_alloc(ctx, &U->d_hashes, 1)); KS_TRY(ks_alloc(ctx, &U->d_abunds, 1));
-        KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return KS_OK;
-    }
-    ks_scratch sc(ctx);
-    ks_runs R;
-    KS_TRY(ks_sorted_runs(ctx, in, sc, &R));
-    U->n_hashes = U->n_slots = R.n_rows;
-    KS_TRY(ks_alloc(ctx, &U->d_hashes, (size_t)R.n_rows)); KS_TRY(ks_alloc(ctx, &U->d_abunds, (size_t)R.n_rows));
-    KS_LAUNCH(ctx, "union_emit", k_union_emit, (R.n_rows + 255) / 256, 256, (const u64 *)R.keys, (const u32 *)R.vals,
-              (const u64 *)R.row_start, R.n_rows, U->d_hashes, U->d_abunds);
-    u64 *const rb = ctx->h_pin + KS_PIN_READ;
-    rb[0] = 0; rb[1] = R.n_rows;
-    KS_HIP(ctx, hipMemcpyAsync(U->d_offsets, rb, 2 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
-}
-
-int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out) {
-    if (!in || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(in)));
-    ks_result<ks_sketches> U(ctx, out, ks_sketches_free);
-    U->params = in->params; U->n_seqs = 1; U->n_windows = in->n_windows;
-    KS_TRY(union_run(ctx, in, U));
-    return U.commit();
+    return se_rows_run(ctx, Q, H, nullptr, &P, fell_back);
 }

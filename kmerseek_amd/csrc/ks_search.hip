@@ -1499,10 +1499,6 @@ __global__ __launch_bounds__(256) void k_rebase_offsets(const u64 *offs, u64 bas
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = offs[i] - base;
 }
-__global__ __launch_bounds__(256) void k_add_u32(u32 *a, u64 n, u32 v) {
-    const u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) a[i] += v;
-}
 
 // the view of query sequences [a, b) of a dense batch: its own offsets (made by search_sliced), the batch's hashes and abundances
 static ks_sketches sketches_slice_view(const ks_sketches *q, const std::vector<u64> &offs, u32 a, u32 b) {
@@ -1553,44 +1549,6 @@ static int search_sliced(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, 
     return KS_OK;
 }
 
-// the columns of a hit list that a concatenation carries: (member, element size); the last two only with statistics
-struct se_hit_col {
-    size_t member, elem; // where the column's pointer lies in ks_hits, bytes per row
-    u8 *get(const ks_hits *h) const { u8 *p; memcpy(&p, (const char *)h + member, sizeof p); return p; }
-    void set(ks_hits *h, u8 *p) const { memcpy((char *)h + member, &p, sizeof p); }
-};
-static const se_hit_col SE_HIT_COLS[6] = {{offsetof(ks_hits, d_qid), sizeof(u32)},     {offsetof(ks_hits, d_tid), sizeof(u32)},
-                                          {offsetof(ks_hits, d_isect), sizeof(u32)},   {offsetof(ks_hits, d_nw), sizeof(u64)},
-                                          {offsetof(ks_hits, d_median2), sizeof(u64)}, {offsetof(ks_hits, d_ss), sizeof(double)}};
-
-// the slices' hit lists in one (query ids back to batch numbering)
-static int hits_concat(ks_ctx *ctx, const se_parts &parts, bool has_stats, ks_hits **out) {
-    ks_result<ks_hits> H(ctx, out, ks_hits_free);
-    H->partition_path = 3;
-    H->has_stats = has_stats;
-    for (const ks_hits *h : parts.hits) { H->n_hits += h->n_hits; H->n_pair_instances += h->n_pair_instances; }
-    const int n_cols = has_stats ? 6 : 4;
-    for (int c = 0; c < n_cols; c++) {
-        u8 *col = nullptr;
-        KS_TRY(ks_alloc(ctx, &col, (size_t)(H->n_hits ? H->n_hits : 1) * SE_HIT_COLS[c].elem));
-        SE_HIT_COLS[c].set(H, col);
-    }
-    u64 at = 0;
-    for (size_t i = 0; i < parts.hits.size(); i++) {
-        ks_hits *const h = parts.hits[i];
-        const u64 n = h->n_hits;
-        if (!n) continue;
-        hipLaunchKernelGGL(k_add_u32, dim3((u32)((n + 255) / 256)), dim3(256), 0, ctx->stream, h->d_qid, n, parts.firsts[i]);
-        for (int c = 0; c < n_cols; c++) {
-            const se_hit_col &C = SE_HIT_COLS[c];
-            KS_HIP(ctx, hipMemcpyAsync(C.get(H) + at * C.elem, C.get(h), n * C.elem, hipMemcpyDeviceToDevice, ctx->stream));
-        }
-        at += n;
-    }
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream)); // (the copies read the parts, which their owner frees next)
-    return H.commit();
-}
-
 // ks_search: one match list when it fits; otherwise the query sequences are searched in contiguous slices whose lists
 // and records fit (a slice is a view of the batch's CSR: hits of different query ranges are disjoint and stay ordered by
 // qid; its qids are numbered from 0, so a slice of few sequences needs few id bits).  Options apply per slice: a slice's rows are
@@ -1606,7 +1564,7 @@ int ks_search_impl(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, ks_hit
     KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
     se_parts parts;
     KS_TRY(search_sliced(ctx, ix, q, opts, need, offs, parts));
-    return hits_concat(ctx, parts, opts && (opts->flags & KS_SEARCH_ABUND_STATS), out);
+    return ks_hits_concat(ctx, parts.hits, parts.firsts, opts && (opts->flags & KS_SEARCH_ABUND_STATS), out);
 }
 
 int ks_search_opts_check(ks_ctx *ctx, const ks_search_opts *o) {

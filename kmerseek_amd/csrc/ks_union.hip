@@ -1,4 +1,5 @@
-// ks_union.hip — ks_sketches_union_groups: the union of consecutive runs of sketches.  Group g of the host array group_offsets is the
+// ks_union.hip — the unions of sketches.  ks_sketches_union (at the end: one sort + run-length reduce of the whole set) and
+// ks_sketches_union_groups: the union of consecutive runs of sketches.  Group g of the host array group_offsets is the
 // sketches [group_offsets[g], group_offsets[g + 1]) of the input set; its output sketch holds their distinct hashes, ascending,
 // with the abundances of equal hashes summed and saturating at 2^32 - 1 (as ks_sketches_union, which folds the whole set into one
 // sketch).  The six frames of a translated record are one group (ks_translate.hip); the proteins of a genome are another use.
@@ -188,6 +189,52 @@ extern "C" int ks_sketches_union_groups(ks_ctx *ctx, const ks_sketches *in, cons
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "union_groups: group_offsets must end at the set's %u sketches, not at %u", in->n_seqs, group_offsets[n_groups]);
     return ks_union_groups_impl(ctx, in, group_offsets, n_groups, out);
     });
+}
+
+// ---------------------------------------------------------------------------------------------
+// union of all sketches with summed abundances: the "combined minhash" of ProteomeIndex::store_signatures
+// (src/rust/index.rs:800-830, add_many_with_abund under a mutex there; here one sort + run-length reduce)
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_union_emit(const u64 *keys, const u32 *vals, const u64 *row_start, u32 n_rows,
+                                                    u64 *hashes, u32 *abunds) {
+    u32 r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const u64 b = row_start[r], w = ks_run_abund_sum(vals, b, row_start[r + 1]);
+    hashes[r] = keys[b];
+    abunds[r] = w > 0xffffffffULL ? 0xffffffffu : (u32)w;
+}
+
+static int union_run(ks_ctx *ctx, const ks_sketches *in, ks_sketches *U) {
+    const u64 n = in->n_hashes;
+    KS_TRY(ks_alloc(ctx, &U->d_offsets, 2));
+    if (n == 0) {
+        KS_HIP(ctx, hipMemsetAsync(U->d_offsets, 0, 2 * sizeof(u64), ctx->stream));
+        KS_TRY(ks_alloc(ctx, &U->d_hashes, 1)); KS_TRY(ks_alloc(ctx, &U->d_abunds, 1));
+        KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        return KS_OK;
+    }
+    ks_scratch sc(ctx);
+    ks_runs R;
+    KS_TRY(ks_sorted_runs(ctx, in, sc, &R));
+    U->n_hashes = U->n_slots = R.n_rows;
+    KS_TRY(ks_alloc(ctx, &U->d_hashes, (size_t)R.n_rows)); KS_TRY(ks_alloc(ctx, &U->d_abunds, (size_t)R.n_rows));
+    KS_LAUNCH(ctx, "union_emit", k_union_emit, (R.n_rows + 255) / 256, 256, (const u64 *)R.keys, (const u32 *)R.vals,
+              (const u64 *)R.row_start, R.n_rows, U->d_hashes, U->d_abunds);
+    u64 *const rb = ctx->h_pin + KS_PIN_READ;
+    rb[0] = 0; rb[1] = R.n_rows;
+    KS_HIP(ctx, hipMemcpyAsync(U->d_offsets, rb, 2 * sizeof(u64), hipMemcpyHostToDevice, ctx->stream));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KS_OK;
+}
+
+int ks_union_impl(ks_ctx *ctx, const ks_sketches *in, ks_sketches **out) {
+    if (!in || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    KS_TRY(ks_sketches_make_dense(ctx, const_cast<ks_sketches *>(in)));
+    ks_result<ks_sketches> U(ctx, out, ks_sketches_free);
+    U->params = in->params; U->n_seqs = 1; U->n_windows = in->n_windows;
+    KS_TRY(union_run(ctx, in, U));
+    return U.commit();
 }
 
 extern "C" uint32_t ks_debug_union_rank_max(void) { return UN_RANK_MAX; }

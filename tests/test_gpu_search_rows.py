@@ -7,6 +7,8 @@
 - a threshold keeps exactly the rows the host's f64 test keeps, in (qid, tid) order;
 - the same under the forced paths (LSD match sort, small MSD buckets, query slices by record width and by pair count,
   no rows hint, the row pass's ticket repeat, ticket-ordered tiles);
+- a row pass that is repeated with statistics and threshold both on (more rows than the context's hint; a forced ticket repeat)
+  gives the same rows and leaves no pool block behind;
 - the object API (PyProteomeIndex.search_sequences / search_fasta) computes its abundance columns on the device, and its
   threshold keeps the rows with containment >= threshold, in the rows and in the CSV."""
 import csv
@@ -25,6 +27,7 @@ from oracle import oracle
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from crafted_sketches import keep as _keep, replica as _replica  # noqa: E402  (the host's row loop and keep test live there)
+from crafted_sketches import ref_join as _ref_join, ref_stats as _ref_stats  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 PROTEIN = np.frombuffer(b"ACDEFGHIKLMNPQRSTVWY", np.uint8)
@@ -313,3 +316,68 @@ def test_object_api_rows_and_threshold(tmp_path):
     assert p.search_sequences(q_recs, threshold=1.5) == []
     with pytest.raises(Exception, match="min_containment"):
         p.search_sequences(q_recs, threshold=-1.0)
+
+
+# ---- a repeated row pass with both extras on: hand-made sketches (ks_sketches_from_host), exact against the numpy join ----
+H0 = 0x9E3779B97F4A7C15  # the hash every sketch of the 80 x 80 case holds
+
+
+def _square(n=80):
+    """n targets and n queries that all hold H0, and one private hash each (targets: odd ones, queries: even ones, so no other
+    hash is shared); target t holds H0 with abundance t + 1.  Every (query, target) pair is a row of one shared hash: n * n rows,
+    each with containment 1 / 2, median2 = 2 * (t + 1) and ss = 0."""
+    offs = np.arange(0, 2 * n + 1, 2, dtype=np.uint64)
+    t_h, q_h = np.empty(2 * n, np.uint64), np.empty(2 * n, np.uint64)
+    t_h[0::2], q_h[0::2] = 2 * np.arange(n) + 1, 2 * np.arange(n) + 2  # (all below H0: ascending inside a sketch)
+    t_h[1::2] = q_h[1::2] = H0
+    t_ab = np.ones(2 * n, np.uint32)
+    t_ab[1::2] = np.arange(n) + 1
+    T, Q = (offs, t_h, t_ab), (offs.copy(), q_h, np.ones(2 * n, np.uint32))
+    rows = _ref_join(T, Q)
+    assert len(rows[0]) == n * n and np.all(rows[2] == 1)
+    sel = _keep(rows, Q, 0.5)
+    assert sel.all()  # (1 / 2 >= 0.5: the filter runs and keeps every row)
+    m2, ss = _ref_stats(rows, T, Q)
+    assert np.array_equal(m2, 2 * (rows[1].astype(np.uint64) + 1)) and not ss.any()
+    return T, Q, [a[sel] for a in rows], m2[sel], ss[sel]
+
+
+def _search_both_extras(ctx, case, label):
+    """the 80 x 80 search with threshold and statistics on `ctx`, held against the replica's kept rows; the pool is back where it
+    was before the search once the result is freed"""
+    T, Q, rows, m2, ss = case
+    dT, dQ = ctx.sketches_from_host(*T, 10, 1, "protein"), ctx.sketches_from_host(*Q, 10, 1, "protein")
+    ix = ctx.index_build(dT)
+    before = ctx.pool_stats()["bytes_in_use"]
+    H = ctx.search(ix, dQ, min_containment=0.5, abund_stats=True)
+    assert H.count == len(rows[0]) == 6400, (label, H.count)
+    _eq_rows(H.to_host(), rows, label)
+    got_m2, got_ss = H.abund_stats_to_host()
+    assert np.array_equal(got_m2, m2) and np.array_equal(got_ss, ss), label
+    H.free()
+    assert ctx.pool_stats()["bytes_in_use"] == before, label
+
+
+def test_rows_cap_repeat_with_stats_and_threshold():
+    """The first search of the context yields one row, so the second one's row arrays are sized for 1 + 0 + 4096 rows: its 6,400
+    rows do not fit, and the row pass, the statistics and the filter run a second time with exact arrays."""
+    case = _square()
+    with ks.Context(0) as ctx:
+        one = (np.array([0, 1], np.uint64), np.array([H0], np.uint64), np.ones(1, np.uint32))
+        d1 = ctx.sketches_from_host(*one, 10, 1, "protein")
+        H1 = ctx.search(ctx.index_build(d1), d1)
+        assert H1.count == 1
+        ctx.timing_enable(True)
+        _search_both_extras(ctx, case, "rows-cap repeat")
+        assert ctx.timing()["pair_rows"][0] == 2  # (the pass did run twice)
+
+
+def test_forced_ticket_repeat_with_stats_and_threshold(monkeypatch):
+    case = _square()
+    monkeypatch.setenv("KS_DEBUG_FORCE_ROWS_TICKET_RETRY", "1")
+    ctx = ks.Context(0, follow_debug_env=True)  # (fresh: the first search of the context repeats its row pass with tickets)
+    try:
+        _search_both_extras(ctx, case, "ticket repeat")
+        assert ctx.search_stats()["rows_ticket_fallbacks"] == 1
+    finally:
+        ctx.close()
