@@ -73,6 +73,7 @@ typedef struct ks_hits ks_hits;         /* device-resident COO (qid, tid, inters
 typedef struct ks_kmerpos ks_kmerpos;   /* device-resident (seq, start, hash) triples */
 typedef struct ks_matchpos ks_matchpos; /* device-resident CSR over hit rows: (query start, target start) of shared k-mers */
 typedef struct ks_regions ks_regions;   /* device-resident CSR over hit rows: the colinear regions those pairs chain into */
+typedef struct ks_raligns ks_raligns;   /* device-resident CSR over hit rows: those regions aligned with gaps (banded affine X-drop) */
 typedef struct ks_rscores ks_rscores;   /* device-resident CSR over hit rows: those regions scored and extended (ungapped X-drop) */
 
 /* ---- library / context ------------------------------------------------------------------ */
@@ -560,6 +561,83 @@ int ks_rscores_copy_to_host(ks_ctx *ctx, const ks_rscores *s, uint64_t *row_offs
 void ks_rscores_free(ks_rscores *s);
 /* positions one wave examines per extension step: the tests place terminations around it */
 uint32_t ks_debug_rscore_step(void);
+
+/* ---- region alignments: one gapped alignment per region (banded affine-gap extension under an X-drop rule) ---------------- */
+
+/* Extends every region of a ks_regions WITH gaps, from the middle pair of its seed to both sides: the gapped stage of a
+ * seed-and-extend search, behind the ungapped one of ks_regions_score.  An indel moves a match to a neighbouring diagonal and
+ * ks_match_regions then reports fragments; this gives each of them the one alignment it belongs to — its score, extents,
+ * identities, gap count — in the real alphabet.  No traceback or CIGAR.  All arithmetic is in integers: the result is
+ * bit-exact against a host loop (tests/ralign_ref.py).
+ * Inputs, residue classes, the matrix (caller-owned HOST int8 M[28][28], NULL: +1 / -1), identities (equal upper-cased bytes)
+ * and positives (s > 0): those of ks_regions_score, above.
+ * Options: band = W in [0, 31]; gap_open = o and gap_extend = e in [0, 255], a gap of L residues costs o + L * e;
+ * x_drop <= 2^20; flags 0.
+ * Region with seed (a, b, n), n >= 1: the anchor is the pair (ai, bj) = (a + n / 2, b + n / 2) (integer division).  The
+ * alignment is the anchor pair, a right extension over Q = q[ai + 1 ...], T = t[bj + 1 ...] and a left extension — the same
+ * function — over the reversed prefixes Q = q[ai - 1], q[ai - 2], ...; T = t[bj - 1], ...
+ * One extension over Q_1 .. Q_X and T_1 .. T_Y lives on the cells (x, y), 0 <= x <= X, 0 <= y <= Y, |y - x| <= W; every other
+ * cell does not exist and is never a source:
+ *   H~(0, 0) = 0
+ *   F(x, y)  = max(H(x - 1, y) - o - e, F(x - 1, y) - e)                   on a tie the continued gap
+ *   D(x, y)  = H(x - 1, y - 1) + M[class(Q_x)][class(T_y)]
+ *   H~(x, y) = max(D, F)                                                   on a tie D
+ *   E(x, y)  = max over existing y' < y of H~(x, y') - o - (y - y') * e    on a tie the largest y'
+ *   H(x, y)  = max(H~, E)                                                  on a tie H~
+ * (E reads H~ only: for o >= 0 the scores are those of the three-matrix Gotoh recurrence over the same band.)  Every cell
+ * carries the counts of the path that made it through the same choices: identities, positives, gap_opens, gaps (residues).
+ *   R_x = max over y of H(x, y);  B_x = max(R_0 .. R_x);
+ *   J = the first x >= 1 with B_x - R_x > x_drop, or the last row that has a cell (a row-level X-drop: no cell is pruned)
+ *   the extension's result is the cell of rows 0 .. J with the largest H, on a tie the smallest x, then the smallest y:
+ *   its (x, y), its H and its counts.  With W = 0 this is the ungapped rule of ks_regions_score started at the anchor.
+ * Result (device-resident), the same CSR over hit rows and the same order as R (row_offsets is a copy of R's):
+ *   q_start = ai - x_left, q_length = x_left + 1 + x_right, t_start = bj - y_left, t_length = y_left + 1 + y_right   u32
+ *   score = M[anchor pair] + left + right                                                                            i64
+ *   identities, positives (the anchor pair included), gap_opens, gaps, aln_length = aligned pairs + gaps              u32
+ * Alignments of one row may overlap or coincide: nothing is merged.  The result never depends on the launch geometry or on
+ * ks_debug_ralign_chunk().  An R without rows or regions gives a valid empty result.
+ * KS_ERR_INVALID_ARG: an option out of range or unknown flags (checked before any device work, also with ctx == NULL), and
+ * everything ks_regions_score refuses, with the same check: ks_last_error names the first bad row, nothing is read outside
+ * the batches.  KS_ERR_CAPACITY: a hit row with regions whose query or target sequence is longer than 2^20 residues (the bound
+ * that keeps the dynamic program in 32 bits); ks_last_error names the first such row.
+ * One stream, one launch, synchronous on return, one host wait; all scratch comes from the context's pool. */
+#define KS_RALIGN_MAX_BAND 31u
+#define KS_RALIGN_MAX_GAP_COST 255u
+#define KS_RALIGN_MAX_X_DROP (1u << 20)
+typedef struct ks_ralign_opts {
+    const int8_t *matrix;  /* HOST, 28 x 28 row-major, or NULL: +1 / -1 */
+    uint32_t band;         /* W <= KS_RALIGN_MAX_BAND */
+    uint32_t gap_open;     /* o <= KS_RALIGN_MAX_GAP_COST */
+    uint32_t gap_extend;   /* e <= KS_RALIGN_MAX_GAP_COST */
+    uint32_t x_drop;       /* <= KS_RALIGN_MAX_X_DROP */
+    uint32_t flags;        /* 0 */
+} ks_ralign_opts;
+/* opts == NULL: band 16, gap_open 11, gap_extend 1, x_drop 30, the +1 / -1 matrix */
+int ks_regions_align(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits,
+                     const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res,
+                     const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res,
+                     const ks_ralign_opts *opts, ks_raligns **out);
+uint64_t ks_raligns_n_rows(const ks_raligns *s);
+uint64_t ks_raligns_n_regions(const ks_raligns *s);
+/* device pointers, valid until ks_raligns_free */
+const uint64_t *ks_raligns_device_row_offsets(const ks_raligns *s);
+const uint32_t *ks_raligns_device_q_start(const ks_raligns *s);
+const uint32_t *ks_raligns_device_q_length(const ks_raligns *s);
+const uint32_t *ks_raligns_device_t_start(const ks_raligns *s);
+const uint32_t *ks_raligns_device_t_length(const ks_raligns *s);
+const int64_t *ks_raligns_device_score(const ks_raligns *s);
+const uint32_t *ks_raligns_device_identities(const ks_raligns *s);
+const uint32_t *ks_raligns_device_positives(const ks_raligns *s);
+const uint32_t *ks_raligns_device_gap_opens(const ks_raligns *s);
+const uint32_t *ks_raligns_device_gaps(const ks_raligns *s);
+const uint32_t *ks_raligns_device_aln_length(const ks_raligns *s);
+/* any destination may be NULL */
+int ks_raligns_copy_to_host(ks_ctx *ctx, const ks_raligns *s, uint64_t *row_offsets, uint32_t *q_start, uint32_t *q_length,
+                            uint32_t *t_start, uint32_t *t_length, int64_t *score, uint32_t *identities, uint32_t *positives,
+                            uint32_t *gap_opens, uint32_t *gaps, uint32_t *aln_length);
+void ks_raligns_free(ks_raligns *s);
+/* rows of the dynamic program whose residues one wave stages at once: the tests place terminations around it */
+uint32_t ks_debug_ralign_chunk(void);
 
 /* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
 

@@ -60,6 +60,16 @@ class ks_rscore_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("x_drop", C.c_uint32), ("matrix", C.POINTER(C.c_int8)), ("reserved", C.c_uint64)]
 
 
+KS_RALIGN_MAX_BAND = 31
+KS_RALIGN_MAX_GAP_COST = 255
+KS_RALIGN_MAX_X_DROP = 1 << 20
+
+
+class ks_ralign_opts(C.Structure):
+    _fields_ = [("matrix", C.POINTER(C.c_int8)), ("band", C.c_uint32), ("gap_open", C.c_uint32), ("gap_extend", C.c_uint32),
+                ("x_drop", C.c_uint32), ("flags", C.c_uint32)]
+
+
 class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -222,6 +232,24 @@ SIGNATURES = {
     "ks_rscores_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ks_rscores_free": (None, [_vp]),
     "ks_debug_rscore_step": (C.c_uint32, []),
+    "ks_regions_align": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64,
+                                   C.POINTER(ks_ralign_opts), _pp]),
+    "ks_raligns_n_rows": (C.c_uint64, [_vp]),
+    "ks_raligns_n_regions": (C.c_uint64, [_vp]),
+    "ks_raligns_device_row_offsets": (_vp, [_vp]),
+    "ks_raligns_device_q_start": (_vp, [_vp]),
+    "ks_raligns_device_q_length": (_vp, [_vp]),
+    "ks_raligns_device_t_start": (_vp, [_vp]),
+    "ks_raligns_device_t_length": (_vp, [_vp]),
+    "ks_raligns_device_score": (_vp, [_vp]),
+    "ks_raligns_device_identities": (_vp, [_vp]),
+    "ks_raligns_device_positives": (_vp, [_vp]),
+    "ks_raligns_device_gap_opens": (_vp, [_vp]),
+    "ks_raligns_device_gaps": (_vp, [_vp]),
+    "ks_raligns_device_aln_length": (_vp, [_vp]),
+    "ks_raligns_copy_to_host": (C.c_int, [_vp] * 13),
+    "ks_raligns_free": (None, [_vp]),
+    "ks_debug_ralign_chunk": (C.c_uint32, []),
     "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
     "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
     "ks_corpus_n_docs": (C.c_uint32, [_vp]),

@@ -574,22 +574,29 @@ extern "C" int ks_hits_merge_by_qid_device(ks_ctx *ctx, const uint32_t *d_qid, c
 // ---------------------------------------------------------------------------------------------
 // region scores (ks_rscore.hip): the regions of a hit list scored under a substitution matrix, extended without gaps
 // ---------------------------------------------------------------------------------------------
+// what the passes over a ks_regions check alike before any device work: the objects, their context, the row counts, the batches
+static int ks_region_pass_check(ks_ctx *ctx, const char *pass, const ks_regions *regions, const ks_hits *hits, const void *out,
+                                const ks_res_batch &Q, const ks_res_batch &T) {
+    if (!regions || !hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, pass, regions, hits));
+    if (regions->n_rows != hits->n_hits)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "%s: the regions cover %llu hit rows, the hit list holds %llu: regions of another list",
+                       pass, (unsigned long long)regions->n_rows, (unsigned long long)hits->n_hits);
+    if (regions->n_regions && (!Q.res || !Q.offs || !T.res || !T.offs)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL device buffer");
+    return KS_OK;
+}
 extern "C" int ks_regions_score(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
                                 const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
                                 const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_rscore_opts *opts, ks_rscores **out) {
     return ks_guard(ctx, [&]() -> int {
     if (opts) KS_TRY(ks_opts_words_check(ctx, "region score", opts->flags, KS_RSCORE_EXTEND, opts->reserved ? 1u : 0u));
     if (!ctx) return KS_ERR_INVALID_ARG;
-    if (!regions || !hits || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    *out = nullptr;
-    KS_TRY(ks_inputs_check_ctx(ctx, "region scores", regions, hits));
-    if (regions->n_rows != hits->n_hits)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG, "region scores: the regions cover %llu hit rows, the hit list holds %llu: regions of another list",
-                       (unsigned long long)regions->n_rows, (unsigned long long)hits->n_hits);
-    if (regions->n_regions && (!d_q_res || !d_q_offs || !d_t_res || !d_t_offs)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL device buffer");
+    if (out) *out = nullptr;
+    const ks_res_batch Q{d_q_res, d_q_offs, n_q, n_q_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
+    KS_TRY(ks_region_pass_check(ctx, "region scores", regions, hits, out, Q, T));
     KS_HIP(ctx, hipSetDevice(ctx->device));
     ks_result<ks_rscores> S(ctx, out, ks_rscores_free);
-    KS_TRY(ks_regions_score_impl(ctx, regions, hits, {d_q_res, d_q_offs, n_q, n_q_res}, {d_t_res, d_t_offs, n_t, n_t_res}, opts, S));
+    KS_TRY(ks_regions_score_impl(ctx, regions, hits, Q, T, opts, S));
     return S.commit();
     });
 }
@@ -624,5 +631,67 @@ extern "C" void ks_rscores_free(ks_rscores *s) {
     ks_pool_free(s->ctx, s->d_qstart); ks_pool_free(s->ctx, s->d_tstart); ks_pool_free(s->ctx, s->d_length);
     ks_pool_free(s->ctx, s->d_score); ks_pool_free(s->ctx, s->d_identities); ks_pool_free(s->ctx, s->d_positives);
     ks_pool_free(s->ctx, s->d_core_ident);
+    delete s;
+}
+
+// ---------------------------------------------------------------------------------------------
+// region alignments (ks_ralign.hip): the regions of a hit list extended with gaps from the middle of their seeds
+// ---------------------------------------------------------------------------------------------
+extern "C" int ks_regions_align(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
+                                const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_ralign_opts *opts, ks_raligns **out) {
+    return ks_guard(ctx, [&]() -> int {
+    const ks_ralign_opts dflt = {nullptr, 16u, 11u, 1u, 30u, 0u};
+    const ks_ralign_opts o = opts ? *opts : dflt;
+    KS_TRY(ks_opts_words_check(ctx, "region alignment", o.flags, 0u, 0u));
+    if (o.band > KS_RALIGN_MAX_BAND || o.gap_open > KS_RALIGN_MAX_GAP_COST || o.gap_extend > KS_RALIGN_MAX_GAP_COST || o.x_drop > KS_RALIGN_MAX_X_DROP) {
+        if (!ctx) return KS_ERR_INVALID_ARG;
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "region alignment options: band %u (at most %u), gap_open %u, gap_extend %u (at most %u), x_drop %u (at most %u)",
+                       o.band, KS_RALIGN_MAX_BAND, o.gap_open, o.gap_extend, KS_RALIGN_MAX_GAP_COST, o.x_drop, KS_RALIGN_MAX_X_DROP);
+    }
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    const ks_res_batch Q{d_q_res, d_q_offs, n_q, n_q_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
+    KS_TRY(ks_region_pass_check(ctx, "region alignments", regions, hits, out, Q, T));
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_raligns> S(ctx, out, ks_raligns_free);
+    KS_TRY(ks_regions_align_impl(ctx, regions, hits, Q, T, &o, S));
+    return S.commit();
+    });
+}
+extern "C" uint64_t ks_raligns_n_rows(const ks_raligns *s) { return s ? s->n_rows : 0; }
+extern "C" uint64_t ks_raligns_n_regions(const ks_raligns *s) { return s ? s->n_regions : 0; }
+extern "C" const uint64_t *ks_raligns_device_row_offsets(const ks_raligns *s) { return s ? s->d_row_offsets : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_q_start(const ks_raligns *s) { return s ? s->d_qstart : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_q_length(const ks_raligns *s) { return s ? s->d_qlength : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_t_start(const ks_raligns *s) { return s ? s->d_tstart : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_t_length(const ks_raligns *s) { return s ? s->d_tlength : nullptr; }
+extern "C" const int64_t *ks_raligns_device_score(const ks_raligns *s) { return s ? s->d_score : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_identities(const ks_raligns *s) { return s ? s->d_identities : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_positives(const ks_raligns *s) { return s ? s->d_positives : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_gap_opens(const ks_raligns *s) { return s ? s->d_gap_opens : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_gaps(const ks_raligns *s) { return s ? s->d_gaps : nullptr; }
+extern "C" const uint32_t *ks_raligns_device_aln_length(const ks_raligns *s) { return s ? s->d_aln_length : nullptr; }
+
+extern "C" int ks_raligns_copy_to_host(ks_ctx *ctx, const ks_raligns *s, uint64_t *row_offsets, uint32_t *q_start, uint32_t *q_length,
+                                       uint32_t *t_start, uint32_t *t_length, int64_t *score, uint32_t *identities, uint32_t *positives,
+                                       uint32_t *gap_opens, uint32_t *gaps, uint32_t *aln_length) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !s) return KS_ERR_INVALID_ARG;
+    const size_t nr = (size_t)s->n_rows, w = (size_t)s->n_regions * sizeof(u32);
+    return ks_columns_to_host(ctx, {{row_offsets, s->d_row_offsets, (nr + 1) * sizeof(u64)},
+                                    {q_start, s->d_qstart, w}, {q_length, s->d_qlength, w}, {t_start, s->d_tstart, w},
+                                    {t_length, s->d_tlength, w}, {score, s->d_score, (size_t)s->n_regions * sizeof(i64)},
+                                    {identities, s->d_identities, w}, {positives, s->d_positives, w}, {gap_opens, s->d_gap_opens, w},
+                                    {gaps, s->d_gaps, w}, {aln_length, s->d_aln_length, w}});
+    });
+}
+
+extern "C" void ks_raligns_free(ks_raligns *s) {
+    if (!s) return;
+    for (void *p : {(void *)s->d_row_offsets, (void *)s->d_qstart, (void *)s->d_qlength, (void *)s->d_tstart, (void *)s->d_tlength,
+                    (void *)s->d_score, (void *)s->d_identities, (void *)s->d_positives, (void *)s->d_gap_opens, (void *)s->d_gaps,
+                    (void *)s->d_aln_length})
+        ks_pool_free(s->ctx, p);
     delete s;
 }

@@ -343,13 +343,14 @@ enum : u32 {
     KS_PIN_TRANSLATE = 226,  // 4 words, six-frame translation: bad offsets | the frames' residue count (the last frame offset)
     KS_PIN_UNION = 230,      // 2 words, union by group: distinct (group, hash) runs
     KS_PIN_RSCORE = 232,     // 1 word, region scores: first row whose regions do not lie inside its sequences (ks_rscore.hip)
-    KS_PIN_END = 233,
+    KS_PIN_RALIGN = 233,     // 2 words, region alignments: first row whose regions do not lie inside its sequences | first row with a sequence too long (ks_ralign.hip)
+    KS_PIN_END = 235,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -480,6 +481,19 @@ struct ks_res_batch { const u8 *res; const u64 *offs; u32 n_seqs; u64 n_res; };
 // ks_regions_score behind its argument checks (opts: validated; R, H: of ctx, equal row counts)
 int ks_regions_score_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
                           const ks_rscore_opts *opts, ks_rscores *S);
+
+// the regions of a ks_regions aligned with gaps from the middle of their seeds (ks_ralign.hip)
+struct ks_raligns {
+    ks_ctx *ctx;
+    u64 n_rows, n_regions;
+    u64 *d_row_offsets;                                             // n_rows + 1
+    u32 *d_qstart, *d_qlength, *d_tstart, *d_tlength;               // n_regions
+    u32 *d_identities, *d_positives, *d_gap_opens, *d_gaps, *d_aln_length; // n_regions
+    i64 *d_score;                                                   // n_regions
+};
+// ks_regions_align behind its argument checks (opts: not NULL, validated; R, H: of ctx, equal row counts)
+int ks_regions_align_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
+                          const ks_ralign_opts *opts, ks_raligns *S);
 
 // clusters of a hit list read as a graph: its connected components (ks_cluster.hip) or greedy representative clusters (ks_greedy.hip)
 struct ks_clusters {

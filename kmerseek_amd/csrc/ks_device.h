@@ -172,6 +172,20 @@ KS_DEV u64 ks_wave_max64(u64 v) {
 #undef KS_MAX64_STEP
     return ((u64)(u32)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (u32)__builtin_amdgcn_readlane((int)lo, 63);
 }
+// inclusive running maximum over the 64 lanes of a wave, the DPP moves of ks_wave_incl_scan; lanes without a source compare with 0
+KS_DEV u32 ks_wave_incl_max(u32 v) {
+#define KS_MAX_STEP(CTRL, RMASK, BC) do { \
+        const u32 o_ = (u32)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, RMASK, 0xf, BC); \
+        v = o_ > v ? o_ : v; } while (0)
+    KS_MAX_STEP(0x111, 0xf, true);  // row_shr:1
+    KS_MAX_STEP(0x112, 0xf, true);  // row_shr:2
+    KS_MAX_STEP(0x114, 0xf, true);  // row_shr:4
+    KS_MAX_STEP(0x118, 0xf, true);  // row_shr:8
+    KS_MAX_STEP(0x142, 0xa, false); // row_bcast:15 into rows 1 and 3
+    KS_MAX_STEP(0x143, 0xc, false); // row_bcast:31 into rows 2 and 3
+#undef KS_MAX_STEP
+    return v;
+}
 // value of the lane below (lane 0: 0)
 KS_DEV u32 ks_lane_below(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, false); } // wave_shr:1
 // largest value over the 64 lanes of a wave (every lane gets it)

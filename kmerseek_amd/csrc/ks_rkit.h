@@ -1,0 +1,68 @@
+// ks_rkit.h — what the passes over a ks_regions share (ks_rscore.hip, ks_ralign.hip): the inputs of such a pass as its kernel
+// takes them, a region's hit row and its two sequences with the one check that nothing lies outside the batches, the residue
+// classes, and the substitution matrix on the device.  One definition: two passes can never disagree on what a bad row is.
+#pragma once
+#include "ks_device.h"
+
+#define RK_A KS_RSCORE_ALPHABET
+
+struct rk_in {
+    const u64 *row_offs;  // n_rows + 1
+    const u32 *qid, *tid; // n_rows
+    const u32 *a, *b, *n; // n_regions: q_start, t_start, length
+    const u8 *q_res, *t_res;
+    const u64 *q_offs, *t_offs;
+    const signed char *matrix; // device, RK_A x RK_A
+    u64 n_q_res, n_t_res;
+    u32 n_rows, n_regions, n_q, n_t;
+};
+static inline rk_in rk_in_of(const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T, const signed char *d_M) {
+    return rk_in{R->d_row_offsets, H->d_qid, H->d_tid, R->d_qstart, R->d_tstart, R->d_length, Q.res, T.res, Q.offs, T.offs, d_M,
+                 Q.n_res, T.n_res, (u32)R->n_rows, (u32)R->n_regions, Q.n_seqs, T.n_seqs};
+}
+
+KS_DEV u64 rk_readfirst64(u64 v) { return ((u64)ks_readfirst((u32)(v >> 32)) << 32) | ks_readfirst((u32)v); }
+KS_DEV u32 rk_upper(u32 c) { return c - 'a' < 26u ? c - 32u : c; }
+KS_DEV u32 rk_class(u32 x) {
+    const u32 c = rk_upper(x);
+    return c - 'A' < 26u ? c - 'A' : c == '*' ? 26u : 27u;
+}
+// the class table (256 B) and the matrix (RK_A * RK_A B) into LDS, by a workgroup of 256 threads; the caller synchronises
+KS_DEV void rk_stage_tables(const rk_in &I, u8 *s_cls, signed char *s_M) {
+    s_cls[threadIdx.x] = (u8)rk_class(threadIdx.x);
+    for (u32 i = threadIdx.x; i < RK_A * RK_A; i += 256) s_M[i] = I.matrix[i];
+}
+
+// Region g (wave-uniform; every value comes back in scalar registers): its hit row — the last row whose offset is <= g: rows
+// without a region are never found, a row with thousands of regions is found by each of them alike — and its two sequences.
+// ok: the region lies inside its two sequences and the sequences inside their batches: a + n <= Lq and b + n <= Lt hold, and
+// [qb, qb + Lq) x [tb, tb + Lt) is all a caller may read.
+struct rk_at {
+    u32 row, a, b, n;
+    u64 qb, tb, Lq, Lt; // the sequences' first residues in the batches, their lengths
+    bool ok;
+};
+KS_DEV rk_at rk_locate(const rk_in &I, u32 g) {
+    rk_at P;
+    P.row = ks_readfirst(ks_last_le_u64(I.row_offs, 0, I.n_rows - 1, g)); // (row_offs[0] == 0 <= g)
+    const u32 q = ks_readfirst(I.qid[P.row]), t = ks_readfirst(I.tid[P.row]);
+    P.a = ks_readfirst(I.a[g]); P.b = ks_readfirst(I.b[g]); P.n = ks_readfirst(I.n[g]);
+    P.ok = q < I.n_q && t < I.n_t;
+    P.qb = P.tb = P.Lq = P.Lt = 0;
+    if (P.ok) {
+        P.qb = rk_readfirst64(I.q_offs[q]); P.tb = rk_readfirst64(I.t_offs[t]);
+        const u64 qe = rk_readfirst64(I.q_offs[q + 1]), te = rk_readfirst64(I.t_offs[t + 1]);
+        P.ok = P.qb <= qe && qe <= I.n_q_res && P.tb <= te && te <= I.n_t_res;
+        P.Lq = qe - P.qb; P.Lt = te - P.tb;
+        P.ok = P.ok && P.Lq <= 0xffffffffULL && P.Lt <= 0xffffffffULL && (u64)P.a + P.n <= P.Lq && (u64)P.b + P.n <= P.Lt;
+    }
+    return P;
+}
+
+// ---- host side (ks_rscore.hip) ----
+// what both passes refuse before any device work beyond the row-offset copy: more rows or regions than 32 bits index
+int rk_counts_check(ks_ctx *ctx, const char *pass, u64 n_rows, u64 n_regions);
+// the caller's host matrix (NULL: +1 / -1) into a block of `sc`
+int rk_upload_matrix(ks_ctx *ctx, ks_scratch &sc, const int8_t *h_matrix, signed char **d_M);
+// KS_ERR_INVALID_ARG naming `row`, the first row rk_locate refused
+int rk_fail_bad_row(ks_ctx *ctx, const char *pass, u64 row, const ks_res_batch &Q, const ks_res_batch &T);

@@ -12,47 +12,20 @@
 //              strictly larger sum: a maximum attained again later never wins against the shorter extension.
 // The sums inside a step fit 32 bits (64 x 128); across steps S and B are i64.  Everything a wave decides is wave-uniform and
 // kept in scalar registers (readfirstlane): the ballots and the DPP scans see whole waves.
-#include "ks_device.h"
+#include "ks_rkit.h"
 
 #define RS_THREADS 256
 #define RS_STEP 64     // positions a wave examines per extension step (ks_debug_rscore_step)
-#define RS_A KS_RSCORE_ALPHABET
+#define RS_A RK_A
 #define RS_BIAS 8192   // RS_STEP * 128: a step's relative sums + RS_BIAS are >= 0, so a max scan may fill with 0
 
 struct rs_args {
-    const u64 *row_offs; // n_rows + 1
-    const u32 *qid, *tid; // n_rows
-    const u32 *a, *b, *n; // n_regions: q_start, t_start, length
-    const u8 *q_res, *t_res;
-    const u64 *q_offs, *t_offs;
-    const signed char *matrix; // device, RS_A x RS_A
-    u64 n_q_res, n_t_res;
-    u32 n_rows, n_regions, n_q, n_t, extend, x_drop;
+    rk_in in;
+    u32 extend, x_drop;
     u32 *o_a, *o_b, *o_n, *o_ident, *o_pos, *o_core_ident;
     i64 *o_score;
     unsigned long long *bad; // the first row whose regions do not lie inside its sequences
 };
-
-KS_DEV u64 rs_readfirst64(u64 v) { return ((u64)ks_readfirst((u32)(v >> 32)) << 32) | ks_readfirst((u32)v); }
-KS_DEV u32 rs_upper(u32 c) { return c - 'a' < 26u ? c - 32u : c; }
-KS_DEV u32 rs_class(u32 x) {
-    const u32 c = rs_upper(x);
-    return c - 'A' < 26u ? c - 'A' : c == '*' ? 26u : 27u;
-}
-// inclusive running maximum over the 64 lanes of a wave, the DPP moves of ks_wave_incl_scan; lanes without a source compare with 0
-KS_DEV u32 rs_wave_incl_max(u32 v) {
-#define RS_MAX_STEP(CTRL, RMASK, BC) do { \
-        const u32 o_ = (u32)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, RMASK, 0xf, BC); \
-        v = o_ > v ? o_ : v; } while (0)
-    RS_MAX_STEP(0x111, 0xf, true);  // row_shr:1
-    RS_MAX_STEP(0x112, 0xf, true);  // row_shr:2
-    RS_MAX_STEP(0x114, 0xf, true);  // row_shr:4
-    RS_MAX_STEP(0x118, 0xf, true);  // row_shr:8
-    RS_MAX_STEP(0x142, 0xa, false); // row_bcast:15 into rows 1 and 3
-    RS_MAX_STEP(0x143, 0xc, false); // row_bcast:31 into rows 2 and 3
-#undef RS_MAX_STEP
-    return v;
-}
 
 struct rs_ext { u32 len; i64 score; u32 ident, pos; };
 
@@ -70,11 +43,11 @@ KS_DEV rs_ext rs_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 e_max, u32 x_dr
             const i64 o = sgn * (i64)((u64)base + lane + 1);
             const u32 cq = qp[o], ct = tp[o];
             s = s_M[s_cls[cq] * RS_A + s_cls[ct]];
-            idt = rs_upper(cq) == rs_upper(ct);
+            idt = rk_upper(cq) == rk_upper(ct);
         }
         const u32 rel = ks_wave_incl_scan((u32)s); // S_j - S, an i32
         const u32 biased = rel + RS_BIAS;
-        const u32 rmax = rs_wave_incl_max(biased);
+        const u32 rmax = ks_wave_incl_max(biased);
         const i64 Sj = S + (i32)rel, Bs = S + (i64)rmax - RS_BIAS, Bj = Bs > B ? Bs : B;
         const u64 term = __ballot(valid && Bj - Sj > (i64)x_drop);
         const u32 last = ks_readfirst(term ? (u32)__ffsll((long long)term) - 1u : nv - 1u); // the lane of J, or of e_max
@@ -99,40 +72,29 @@ KS_DEV rs_ext rs_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 e_max, u32 x_dr
 __global__ __launch_bounds__(RS_THREADS) void k_rscore(rs_args A) {
     __shared__ u8 s_cls[256];
     __shared__ signed char s_M[RS_A * RS_A];
-    s_cls[threadIdx.x] = (u8)rs_class(threadIdx.x);
-    for (u32 i = threadIdx.x; i < RS_A * RS_A; i += RS_THREADS) s_M[i] = A.matrix[i];
+    rk_stage_tables(A.in, s_cls, s_M);
     __syncthreads();
     const u32 lane = threadIdx.x & 63;
     const u64 g64 = (u64)blockIdx.x * (RS_THREADS / 64) + ks_readfirst(threadIdx.x >> 6);
-    if (g64 >= A.n_regions) return;
+    if (g64 >= A.in.n_regions) return;
     const u32 g = (u32)g64;
-    const u32 row = ks_readfirst(ks_last_le_u64(A.row_offs, 0, A.n_rows - 1, g)); // (row_offs[0] == 0 <= g)
-    const u32 q = ks_readfirst(A.qid[row]), t = ks_readfirst(A.tid[row]);
-    const u32 a = ks_readfirst(A.a[g]), b = ks_readfirst(A.b[g]), n = ks_readfirst(A.n[g]);
-    // the region inside its two sequences, the sequences inside their batches: nothing below reads outside [0, n_res)
-    bool ok = q < A.n_q && t < A.n_t;
-    u64 qb = 0, tb = 0, Lq = 0, Lt = 0;
-    if (ok) {
-        qb = rs_readfirst64(A.q_offs[q]); tb = rs_readfirst64(A.t_offs[t]);
-        const u64 qe = rs_readfirst64(A.q_offs[q + 1]), te = rs_readfirst64(A.t_offs[t + 1]);
-        ok = qb <= qe && qe <= A.n_q_res && tb <= te && te <= A.n_t_res;
-        Lq = qe - qb; Lt = te - tb;
-        ok = ok && Lq <= 0xffffffffULL && Lt <= 0xffffffffULL && (u64)a + n <= Lq && (u64)b + n <= Lt;
-    }
-    if (!ok) {
+    const rk_at P = rk_locate(A.in, g); // nothing below reads outside the two sequences it names
+    const u32 a = P.a, b = P.b, n = P.n;
+    const u64 Lq = P.Lq, Lt = P.Lt;
+    if (!P.ok) {
         if (lane == 0) {
-            ks_first_bad(A.bad, 0, row);
+            ks_first_bad(A.bad, 0, P.row);
             A.o_a[g] = a; A.o_b[g] = b; A.o_n[g] = n; A.o_score[g] = 0; A.o_ident[g] = 0; A.o_pos[g] = 0; A.o_core_ident[g] = 0;
         }
         return;
     }
-    const u8 *qc = A.q_res + qb + a, *tc = A.t_res + tb + b; // the core's first pair
+    const u8 *qc = A.in.q_res + P.qb + a, *tc = A.in.t_res + P.tb + b; // the core's first pair
     i64 sc = 0;
     u32 id = 0, po = 0;
     for (u64 i = lane; i < n; i += 64) {
         const u32 cq = qc[i], ct = tc[i];
         const int s = s_M[s_cls[cq] * RS_A + s_cls[ct]];
-        sc += s; id += rs_upper(cq) == rs_upper(ct) ? 1u : 0u; po += s > 0 ? 1u : 0u;
+        sc += s; id += rk_upper(cq) == rk_upper(ct) ? 1u : 0u; po += s > 0 ? 1u : 0u;
     }
     i64 score = (i64)ks_wave_sum64((u64)sc);
     const u64 counts = ks_wave_sum64(((u64)id << 32) | po); // (each below 2^32: n is a u32)
@@ -161,26 +123,17 @@ int ks_regions_score_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, co
     KS_TRY(ks_alloc(ctx, &S->d_positives, (size_t)ng)); KS_TRY(ks_alloc(ctx, &S->d_core_ident, (size_t)ng));
     KS_HIP(ctx, hipMemcpyAsync(S->d_row_offsets, R->d_row_offsets, ((size_t)n_rows + 1) * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
     if (ng == 0) return ks_stream_wait(ctx);
-    if (n_rows >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "region scores: 2^32 - 2 or more hit rows");
-    if (ng > 0xffffffffULL) return ks_fail(ctx, KS_ERR_CAPACITY, "region scores: more than 2^32 - 1 regions");
+    KS_TRY(rk_counts_check(ctx, "region scores", n_rows, ng));
 
     ks_scratch sc(ctx);
     signed char *d_M = nullptr;
     u64 *bad = nullptr;
-    KS_TRY(sc.alloc(&d_M, (size_t)RS_A * RS_A));
+    KS_TRY(rk_upload_matrix(ctx, sc, opts ? opts->matrix : nullptr, &d_M));
     KS_TRY(sc.alloc(&bad, 1));
     KS_HIP(ctx, hipMemsetAsync(bad, 0xff, sizeof(u64), ctx->stream));
-    signed char h_M[RS_A * RS_A];
-    if (opts && opts->matrix) memcpy(h_M, opts->matrix, sizeof h_M);
-    else for (int i = 0; i < RS_A * RS_A; i++) h_M[i] = (i / RS_A == i % RS_A) ? 1 : -1;
-    KS_TRY(ks_copy_h2d(ctx, d_M, h_M, sizeof h_M)); // (a pageable source: consumed on return)
 
     rs_args A;
-    A.row_offs = R->d_row_offsets; A.qid = H->d_qid; A.tid = H->d_tid;
-    A.a = R->d_qstart; A.b = R->d_tstart; A.n = R->d_length;
-    A.q_res = Q.res; A.t_res = T.res; A.q_offs = Q.offs; A.t_offs = T.offs; A.matrix = d_M;
-    A.n_q_res = Q.n_res; A.n_t_res = T.n_res;
-    A.n_rows = (u32)n_rows; A.n_regions = (u32)ng; A.n_q = Q.n_seqs; A.n_t = T.n_seqs;
+    A.in = rk_in_of(R, H, Q, T, d_M);
     A.extend = opts && (opts->flags & KS_RSCORE_EXTEND) ? 1u : 0u; A.x_drop = opts ? opts->x_drop : 0u;
     A.o_a = S->d_qstart; A.o_b = S->d_tstart; A.o_n = S->d_length; A.o_ident = S->d_identities; A.o_pos = S->d_positives;
     A.o_core_ident = S->d_core_ident; A.o_score = S->d_score; A.bad = (unsigned long long *)bad;
@@ -188,12 +141,28 @@ int ks_regions_score_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, co
     u64 *const hb = ctx->h_pin + KS_PIN_RSCORE;
     const ks_fetch_seg f = ks_fetch_words(bad, hb, 2);
     KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
-    if (*hb != ~0ULL)
-        return ks_fail(ctx, KS_ERR_INVALID_ARG,
-                       "region scores: hit row %llu names a query or target beyond the batches (%u queries, %u targets) or owns a region that "
-                       "does not lie inside its two sequences: regions, hits and batches do not belong together",
-                       (unsigned long long)*hb, Q.n_seqs, T.n_seqs);
+    if (*hb != ~0ULL) return rk_fail_bad_row(ctx, "region scores", *hb, Q, T);
     return KS_OK;
 }
 
 extern "C" uint32_t ks_debug_rscore_step(void) { return RS_STEP; }
+
+// ---- the host side of ks_rkit.h ----
+int rk_counts_check(ks_ctx *ctx, const char *pass, u64 n_rows, u64 n_regions) {
+    if (n_rows >= 0xfffffffeULL) return ks_fail(ctx, KS_ERR_CAPACITY, "%s: 2^32 - 2 or more hit rows", pass);
+    if (n_regions > 0xffffffffULL) return ks_fail(ctx, KS_ERR_CAPACITY, "%s: more than 2^32 - 1 regions", pass);
+    return KS_OK;
+}
+int rk_upload_matrix(ks_ctx *ctx, ks_scratch &sc, const int8_t *h_matrix, signed char **d_M) {
+    KS_TRY(sc.alloc(d_M, (size_t)RK_A * RK_A));
+    signed char h_M[RK_A * RK_A];
+    if (h_matrix) memcpy(h_M, h_matrix, sizeof h_M);
+    else for (int i = 0; i < RK_A * RK_A; i++) h_M[i] = (i / RK_A == i % RK_A) ? 1 : -1;
+    return ks_copy_h2d(ctx, *d_M, h_M, sizeof h_M); // (a pageable source: consumed on return)
+}
+int rk_fail_bad_row(ks_ctx *ctx, const char *pass, u64 row, const ks_res_batch &Q, const ks_res_batch &T) {
+    return ks_fail(ctx, KS_ERR_INVALID_ARG,
+                   "%s: hit row %llu names a query or target beyond the batches (%u queries, %u targets) or owns a region that "
+                   "does not lie inside its two sequences: regions, hits and batches do not belong together",
+                   pass, (unsigned long long)row, Q.n_seqs, T.n_seqs);
+}

@@ -487,6 +487,56 @@ class Context:
             for b in bufs:
                 b.free()
 
+    @staticmethod
+    def _ralign_opts(matrix, band: int, gap_open: int, gap_extend: int, x_drop: int):
+        """(ks_ralign_opts, the int8 array its matrix pointer reads: keep it alive for the call)"""
+        for name, v, top in (("band", band, _lib.KS_RALIGN_MAX_BAND), ("gap_open", gap_open, _lib.KS_RALIGN_MAX_GAP_COST),
+                             ("gap_extend", gap_extend, _lib.KS_RALIGN_MAX_GAP_COST), ("x_drop", x_drop, _lib.KS_RALIGN_MAX_X_DROP)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
+        m = None
+        if matrix is not None:
+            m = np.asarray(matrix)
+            if m.shape != (_lib.KS_RSCORE_ALPHABET, _lib.KS_RSCORE_ALPHABET) or m.dtype != np.int8:
+                raise ValueError("matrix must be an int8 array of shape (28, 28)")
+            m = np.ascontiguousarray(m)
+        mp = m.ctypes.data_as(C.POINTER(C.c_int8)) if m is not None else None
+        return _lib.ks_ralign_opts(mp, int(band), int(gap_open), int(gap_extend), int(x_drop), 0), m
+
+    def align_regions_device(self, regions: "Regions", hits: "Hits", d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
+                             d_t_res: int, d_t_off: int, n_t: int, n_t_res: int, matrix=None, band: int = 16, gap_open: int = 11,
+                             gap_extend: int = 1, x_drop: int = 30) -> "RegionAlignments":
+        """ks_regions_align from device-resident residue batches (raw pointers: residues u8, offsets u64[n + 1]): every region
+        of `regions` — chained for the rows of `hits` — extended with gaps from the middle pair of its seed to both sides: a
+        banded (|diagonal shift| <= band <= 31) affine-gap (a gap of L residues costs gap_open + L * gap_extend, each <= 255)
+        dynamic program under `matrix` (as score_regions), stopped by a row-level X-drop (x_drop <= 2^20).  Per region the
+        alignment's q_start, q_length, t_start, t_length, score (i64), identities, positives, gap_opens, gaps and aln_length;
+        no traceback.  include/kmerseek_amd.h has the definitions."""
+        opts, keep = self._ralign_opts(matrix, band, gap_open, gap_extend, x_drop)
+        out = C.c_void_p()
+        self._check(self._L.ks_regions_align(self._h, regions._h, hits._h, C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res),
+                                             C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res), C.byref(opts), C.byref(out)))
+        del keep
+        return RegionAlignments(self, out)
+
+    def align_regions(self, regions: "Regions", hits: "Hits", q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray,
+                      t_off: np.ndarray, matrix=None, band: int = 16, gap_open: int = 11, gap_extend: int = 1,
+                      x_drop: int = 30) -> "RegionAlignments":
+        """align_regions_device from host arrays (the batches `hits` was searched on): uploaded, aligned, released."""
+        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        self._ralign_opts(matrix, band, gap_open, gap_extend, x_drop)  # (refused before anything is uploaded)
+        bufs = []
+        try:
+            for a in (q_res, q_off, t_res, t_off):
+                bufs.append(self.to_device(a))
+            return self.align_regions_device(regions, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res), bufs[2].ptr, bufs[3].ptr,
+                                             len(t_off) - 1, len(t_res), matrix=matrix, band=band, gap_open=gap_open,
+                                             gap_extend=gap_extend, x_drop=x_drop)
+        finally:
+            for b in bufs:
+                b.free()
+
     def significance(self, queries: "Sketches", targets: "Sketches", hits: "Hits", q_corpus: Optional["Corpus"] = None,
                      t_corpus: Optional["Corpus"] = None) -> "Significance":
         """ks_hits_significance: per row of `hits` the two f64 sums behind multisearch's prob_overlap and tf_idf_score, over the
@@ -894,6 +944,36 @@ class RegionScores(_Owned):
         offs = np.zeros(self.n_rows + 1, np.uint64)
         cols = [np.zeros(n, np.int64 if c == "score" else np.uint32) for c in self._COLUMNS[1:]]
         self._ctx._check(self._ctx._L.ks_rscores_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
+        return (offs, *cols)
+
+
+class RegionAlignments(_Owned):
+    """Device-resident gapped alignments of the regions of a hit list (ks_raligns): the CSR of the Regions they were made from,
+    per region the alignment's extents on both sequences, its score and its counts."""
+    _free = "ks_raligns_free"
+    _COLUMNS = ("row_offsets", "q_start", "q_length", "t_start", "t_length", "score", "identities", "positives", "gap_opens", "gaps",
+                "aln_length")
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_raligns_n_rows(self._h))
+
+    @property
+    def n_regions(self) -> int:
+        return int(self._ctx._L.ks_raligns_n_regions(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (row_offsets u64[n_rows + 1]; score i64 and every other column u32, each [n_regions])."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_raligns_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """(row_offsets u64[n_rows + 1], q_start, q_length, t_start, t_length u32, score i64, identities, positives, gap_opens,
+        gaps, aln_length u32)."""
+        n = self.n_regions
+        offs = np.zeros(self.n_rows + 1, np.uint64)
+        cols = [np.zeros(n, np.int64 if c == "score" else np.uint32) for c in self._COLUMNS[1:]]
+        self._ctx._check(self._ctx._L.ks_raligns_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
         return (offs, *cols)
 
 

@@ -712,7 +712,7 @@ def read_score_matrix(path: str) -> np.ndarray:
 
 
 def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, regions_host,
-                moltype: str, scores=None) -> List[dict]:
+                moltype: str, scores=None, alignments=None) -> List[dict]:
     """One row per region of the device's chaining (Context.match_regions; regions_host = Regions.to_host()): hit row
     r = (qid[r], tid[r]) owns regions [row_offsets[r], row_offsets[r + 1]).  The stitched columns of search.py:195-240 —
     query / match / encoded are the residues the region spans, sliced from the records (a region lies on one diagonal, so
@@ -723,12 +723,21 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
     scores = RegionScores.to_host() of the same regions (Context.score_regions): the rows are those of the scored — with
     extend=True extended — regions: query_start / query_end, match_start / match_end, query / match / encoded and length span
     the extended region, and the columns score, identities, positives, pident (100 * identities / length) and seed_start /
-    seed_length (the original region's query_start and length) are added."""
+    seed_length (the original region's query_start and length) are added.
+
+    alignments = RegionAlignments.to_host() of the same regions (Context.align_regions): every row also carries its region's
+    gapped alignment — aln_score, aln_q_start / aln_q_end and aln_t_start / aln_t_end (half-open), aln_length (aligned pairs +
+    gap residues), aln_identities, aln_positives, aln_mismatches (aligned pairs that are no identity), aln_gap_opens, aln_gaps
+    and aln_pident (100 * aln_identities / aln_length).  The other columns, and the order of the rows, do not change."""
     offs, q_start, t_start, length, n_kmers, covered = [np.asarray(c).tolist() for c in regions_host]
     if scores is not None:
         s_offs, s_q, s_t, s_len, s_score, s_ident, s_pos, _ = [np.asarray(c).tolist() for c in scores]
         if s_offs != offs:
             raise ValueError("scores and regions are not of the same hit rows")
+    if alignments is not None:
+        al = [np.asarray(c).tolist() for c in alignments]
+        if al[0] != offs:
+            raise ValueError("alignments and regions are not of the same hit rows")
     out = []
     for r, (q, t) in enumerate(zip(np.asarray(qid).tolist(), np.asarray(tid).tolist())):
         qn, qseq = q_records[q]
@@ -743,6 +752,12 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
                 row.update({"score": s_score[g], "identities": s_ident[g], "positives": s_pos[g],
                             "pident": format_f64(100.0 * float(s_ident[g]) / float(n) if n else math.nan),
                             "seed_start": q_start[g], "seed_length": length[g]})
+            if alignments is not None:
+                qs_, ql_, ts_, tl_, sc_, id_, po_, go_, ga_, ln_ = [c[g] for c in al[1:]]
+                row.update({"aln_score": sc_, "aln_q_start": qs_, "aln_q_end": qs_ + ql_, "aln_t_start": ts_, "aln_t_end": ts_ + tl_,
+                            "aln_length": ln_, "aln_identities": id_, "aln_positives": po_, "aln_mismatches": ln_ - ga_ - id_,
+                            "aln_gap_opens": go_, "aln_gaps": ga_,
+                            "aln_pident": format_f64(100.0 * float(id_) / float(ln_) if ln_ else math.nan)})
             out.append((q, row))
     out.sort(key=lambda e: (e[0], e[1]["query_start"], e[1]["query_end"]))
     return [row for _, row in out]
@@ -751,15 +766,20 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
 def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int, scaled: int, moltype: str,
                                 ctx: Optional[Context] = None, regions: bool = False, max_gap: int = 0,
                                 min_kmers: int = 1, score: bool = False, extend: bool = False, x_drop: int = 0,
-                                matrix=None) -> List[dict]:
+                                matrix=None, gapped: bool = False, band: int = 16, gap_open: int = 11, gap_extend: int = 1,
+                                gapped_x_drop: int = 30) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
     max_gap / min_kmers) and only the regions come to the host: the rows of `region_rows`, one per colinear run.
     score=True (needs regions=True): the regions are scored on the device too (Context.score_regions with matrix, extend and
-    x_drop) and the rows carry the columns `region_rows` adds for scores."""
+    x_drop) and the rows carry the columns `region_rows` adds for scores.
+    gapped=True (needs regions=True): every region is aligned with gaps on the device (Context.align_regions with matrix, band,
+    gap_open, gap_extend and gapped_x_drop) and the rows carry the aln_* columns `region_rows` adds for alignments."""
     if score and not regions:
         raise ValueError("score=True needs regions=True: scores are of regions")
+    if gapped and not regions:
+        raise ValueError("gapped=True needs regions=True: alignments are of regions")
     own = ctx is None
     ctx = ctx or Context(0)
     try:
@@ -782,8 +802,15 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                 sc = ctx.score_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, extend=extend, x_drop=x_drop)
                 sc_host = sc.to_host()
                 sc.free()
+            if gapped:
+                al = ctx.align_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, band=band, gap_open=gap_open,
+                                       gap_extend=gap_extend, x_drop=gapped_x_drop)
+                al_host = al.to_host()
+                al.free()
             for o in (rg, mp, qp, tp, hits, Q, T):
                 o.free()
+            if gapped:
+                return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host)
             return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host)
         offs, qs, ts = mp.to_host()[:3]
         for o in (mp, qp, tp, hits, Q, T):
