@@ -74,6 +74,7 @@ typedef struct ks_kmerpos ks_kmerpos;   /* device-resident (seq, start, hash) tr
 typedef struct ks_matchpos ks_matchpos; /* device-resident CSR over hit rows: (query start, target start) of shared k-mers */
 typedef struct ks_regions ks_regions;   /* device-resident CSR over hit rows: the colinear regions those pairs chain into */
 typedef struct ks_raligns ks_raligns;   /* device-resident CSR over hit rows: those regions aligned with gaps (banded affine X-drop) */
+typedef struct ks_cigars ks_cigars;     /* device-resident CSR over regions: the path of each alignment as BAM-encoded CIGAR ops */
 typedef struct ks_rscores ks_rscores;   /* device-resident CSR over hit rows: those regions scored and extended (ungapped X-drop) */
 
 /* ---- library / context ------------------------------------------------------------------ */
@@ -567,8 +568,9 @@ uint32_t ks_debug_rscore_step(void);
 /* Extends every region of a ks_regions WITH gaps, from the middle pair of its seed to both sides: the gapped stage of a
  * seed-and-extend search, behind the ungapped one of ks_regions_score.  An indel moves a match to a neighbouring diagonal and
  * ks_match_regions then reports fragments; this gives each of them the one alignment it belongs to — its score, extents,
- * identities, gap count — in the real alphabet.  No traceback or CIGAR.  All arithmetic is in integers: the result is
- * bit-exact against a host loop (tests/ralign_ref.py).
+ * identities, gap count — in the real alphabet.  The path itself is ks_regions_traceback's, below: the result records the
+ * options it was made with for it.  All arithmetic is in integers: the result is bit-exact against a host loop
+ * (tests/ralign_ref.py).
  * Inputs, residue classes, the matrix (caller-owned HOST int8 M[28][28], NULL: +1 / -1), identities (equal upper-cased bytes)
  * and positives (s > 0): those of ks_regions_score, above.
  * Options: band = W in [0, 31]; gap_open = o and gap_extend = e in [0, 255], a gap of L residues costs o + L * e;
@@ -638,6 +640,72 @@ int ks_raligns_copy_to_host(ks_ctx *ctx, const ks_raligns *s, uint64_t *row_offs
 void ks_raligns_free(ks_raligns *s);
 /* rows of the dynamic program whose residues one wave stages at once: the tests place terminations around it */
 uint32_t ks_debug_ralign_chunk(void);
+
+/* ---- region traceback: the path of every region alignment, as a CIGAR ------------------------------------------------------ */
+
+/* Walks back the alignment of every region of a ks_raligns and reports its path: what a PAF / SAM `cg` tag, a printed
+ * alignment or a mask of the aligned residues needs.  ks_regions_align fixes the path by the tie rules of its recurrence
+ * (above) and reports four counts of it; this reports the path those are counts of.  All arithmetic is in integers: the result
+ * is bit-exact against a host loop (tests/rtrace_ref.py).
+ *   regions, hits and the two residue batches: what ks_regions_align took;  alignments: the ks_raligns S it returned.
+ * S records the options it was made with (band, gap_open, gap_extend, x_drop, a copy of the matrix): the traceback runs the
+ * same program and cannot be given others.
+ * Region g with seed (a, b, n) and anchor (ai, bj) = (a + n / 2, b + n / 2): the end cells of its two extensions follow from S:
+ *   x_left = ai - q_start, x_right = q_length - 1 - x_left;  y_left = bj - t_start, y_right = t_length - 1 - y_left
+ * The path of one extension goes from its end cell back to (0, 0) by the choices the recurrence made:
+ *   at H(x, y):   E if H took E — a jump to H~(x, y'), y' the source of E, y - y' target residues — else H~(x, y)
+ *   at H~(x, y):  D — one aligned pair, to H(x - 1, y - 1) — if H~ took D, else F(x, y)
+ *   at F(x, y):   one query residue; to F(x - 1, y) if F continued the gap, else to H(x - 1, y)
+ *   at H(0, y), y > 0: an E of y residues from (0, 0)
+ * with the ties as above: F prefers the continued gap, H~ prefers D, E the largest y', H prefers H~.
+ * The alignment is the left path in forward sequence order, the anchor pair, the right path.  Its columns, the query as the
+ * read and the target as the reference: an aligned pair is M; a query residue without a target residue is I; a target residue
+ * without a query residue is D.  With KS_RTRACE_EQX an aligned pair is = where the two upper-cased bytes are equal and X where
+ * they are not.  Adjacent equal columns are one op, the anchor merges with the runs beside it; an op is len << 4 | code with
+ * the BAM codes M = 0, I = 1, D = 2, = = 7, X = 8 (len <= 2^21 + 31 < 2^28).
+ * Result (device-resident): a CSR over the regions in the order of S: op_offsets u64[n_regions + 1], ops u32[n_ops].
+ * For every region: the ops' lengths sum to aln_length; pairs + I = q_length; pairs + D = t_length; the number of I and D ops
+ * is gap_opens (the recurrence never splits a run; an I run beside a D run is two opens) and their lengths sum to gaps; with
+ * KS_RTRACE_EQX the = columns are identities; re-scoring the ops under the matrix and the gap costs gives score and positives.
+ * The result never depends on the launch geometry, on ks_debug_ralign_chunk() / ks_debug_rtrace_stage() or on
+ * max_scratch_bytes.  An S without rows or regions gives a valid empty result (op_offsets = {0}).
+ * Scratch: one byte per cell of the band for the rows between the two end cells — 64 bytes per row, q_length - 1 rows (each
+ * side's rounded up to an even number) per region.  max_scratch_bytes (0: 1 GiB) bounds it: the regions run in slices of
+ * consecutive regions whose rows fit.  KS_ERR_CAPACITY: a single region that does not fit (ks_last_error names it), and what
+ * ks_regions_align refuses with it.
+ * KS_ERR_INVALID_ARG: unknown flags / a non-zero reserved field (checked before any device work, also with ctx == NULL);
+ * everything ks_regions_align refuses, with the same checks; an S whose row or region count is not that of `regions` (checked
+ * on the host before any device work); an S that does not belong to these regions and batches — an extent outside its
+ * sequence, an anchor outside the extent, an end cell outside the band, or a path whose length or score is not the
+ * alignment's: ks_last_error names the first such region.  The extent and anchor checks run before anything is indexed by
+ * them: no combination of arguments that passes the host checks reads or writes outside the batches and the scratch.
+ * One stream, synchronous on return, three host waits (the layout, the op count, the ops); all memory comes from the
+ * context's pool. */
+#define KS_RTRACE_EQX 1u
+typedef struct ks_rtrace_opts {
+    uint32_t flags;             /* KS_RTRACE_EQX */
+    uint32_t reserved;          /* 0 */
+    uint64_t max_scratch_bytes; /* direction scratch of one slice; 0: 1 GiB */
+} ks_rtrace_opts;
+/* opts == NULL: M / I / D ops, 1 GiB */
+int ks_regions_traceback(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits,
+                         const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res,
+                         const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res,
+                         const ks_raligns *alignments, const ks_rtrace_opts *opts, ks_cigars **out);
+uint64_t ks_cigars_n_rows(const ks_cigars *c);
+uint64_t ks_cigars_n_regions(const ks_cigars *c);
+uint64_t ks_cigars_n_ops(const ks_cigars *c);
+/* diagnostic: the direction scratch the call allocated, and the slices it ran in */
+uint64_t ks_cigars_scratch_bytes(const ks_cigars *c);
+uint32_t ks_cigars_n_slices(const ks_cigars *c);
+/* device pointers, valid until ks_cigars_free */
+const uint64_t *ks_cigars_device_op_offsets(const ks_cigars *c);
+const uint32_t *ks_cigars_device_ops(const ks_cigars *c);
+/* any destination may be NULL */
+int ks_cigars_copy_to_host(ks_ctx *ctx, const ks_cigars *c, uint64_t *op_offsets, uint32_t *ops);
+void ks_cigars_free(ks_cigars *c);
+/* rows of directions one wave stages at once for the walk: the tests place end cells around it */
+uint32_t ks_debug_rtrace_stage(void);
 
 /* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
 

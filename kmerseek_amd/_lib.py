@@ -70,6 +70,13 @@ class ks_ralign_opts(C.Structure):
                 ("x_drop", C.c_uint32), ("flags", C.c_uint32)]
 
 
+KS_RTRACE_EQX = 1
+
+
+class ks_rtrace_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("max_scratch_bytes", C.c_uint64)]
+
+
 class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -250,6 +257,18 @@ SIGNATURES = {
     "ks_raligns_copy_to_host": (C.c_int, [_vp] * 13),
     "ks_raligns_free": (None, [_vp]),
     "ks_debug_ralign_chunk": (C.c_uint32, []),
+    "ks_regions_traceback": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, _vp,
+                                       C.POINTER(ks_rtrace_opts), _pp]),
+    "ks_cigars_n_rows": (C.c_uint64, [_vp]),
+    "ks_cigars_n_regions": (C.c_uint64, [_vp]),
+    "ks_cigars_n_ops": (C.c_uint64, [_vp]),
+    "ks_cigars_scratch_bytes": (C.c_uint64, [_vp]),
+    "ks_cigars_n_slices": (C.c_uint32, [_vp]),
+    "ks_cigars_device_op_offsets": (_vp, [_vp]),
+    "ks_cigars_device_ops": (_vp, [_vp]),
+    "ks_cigars_copy_to_host": (C.c_int, [_vp] * 4),
+    "ks_cigars_free": (None, [_vp]),
+    "ks_debug_rtrace_stage": (C.c_uint32, []),
     "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
     "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
     "ks_corpus_n_docs": (C.c_uint32, [_vp]),

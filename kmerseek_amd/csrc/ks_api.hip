@@ -695,3 +695,51 @@ extern "C" void ks_raligns_free(ks_raligns *s) {
         ks_pool_free(s->ctx, p);
     delete s;
 }
+
+// ---------------------------------------------------------------------------------------------
+// region traceback (ks_rtrace.hip): the path of every alignment of a ks_raligns as a CIGAR
+// ---------------------------------------------------------------------------------------------
+extern "C" int ks_regions_traceback(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
+                                    const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                    const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_raligns *alignments,
+                                    const ks_rtrace_opts *opts, ks_cigars **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (opts) KS_TRY(ks_opts_words_check(ctx, "region traceback", opts->flags, KS_RTRACE_EQX, opts->reserved));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    const ks_res_batch Q{d_q_res, d_q_offs, n_q, n_q_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
+    KS_TRY(ks_region_pass_check(ctx, "region traceback", regions, hits, out, Q, T));
+    if (!alignments) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "region traceback", alignments));
+    if (alignments->n_rows != regions->n_rows || alignments->n_regions != regions->n_regions)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG,
+                       "region traceback: the alignments are of %llu regions in %llu hit rows, the regions are %llu in %llu: "
+                       "alignments of other regions", (unsigned long long)alignments->n_regions, (unsigned long long)alignments->n_rows,
+                       (unsigned long long)regions->n_regions, (unsigned long long)regions->n_rows);
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_cigars> C(ctx, out, ks_cigars_free);
+    KS_TRY(ks_regions_traceback_impl(ctx, regions, hits, Q, T, alignments, opts ? opts->flags : 0u, opts ? opts->max_scratch_bytes : 0, C));
+    return C.commit();
+    });
+}
+extern "C" uint64_t ks_cigars_n_rows(const ks_cigars *c) { return c ? c->n_rows : 0; }
+extern "C" uint64_t ks_cigars_n_regions(const ks_cigars *c) { return c ? c->n_regions : 0; }
+extern "C" uint64_t ks_cigars_n_ops(const ks_cigars *c) { return c ? c->n_ops : 0; }
+extern "C" uint64_t ks_cigars_scratch_bytes(const ks_cigars *c) { return c ? c->dir_bytes : 0; }
+extern "C" uint32_t ks_cigars_n_slices(const ks_cigars *c) { return c ? c->n_slices : 0; }
+extern "C" const uint64_t *ks_cigars_device_op_offsets(const ks_cigars *c) { return c ? c->d_op_offsets : nullptr; }
+extern "C" const uint32_t *ks_cigars_device_ops(const ks_cigars *c) { return c ? c->d_ops : nullptr; }
+
+extern "C" int ks_cigars_copy_to_host(ks_ctx *ctx, const ks_cigars *c, uint64_t *op_offsets, uint32_t *ops) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !c) return KS_ERR_INVALID_ARG;
+    return ks_columns_to_host(ctx, {{op_offsets, c->d_op_offsets, ((size_t)c->n_regions + 1) * sizeof(u64)},
+                                    {ops, c->d_ops, (size_t)c->n_ops * sizeof(u32)}});
+    });
+}
+
+extern "C" void ks_cigars_free(ks_cigars *c) {
+    if (!c) return;
+    ks_pool_free(c->ctx, c->d_op_offsets); ks_pool_free(c->ctx, c->d_ops);
+    delete c;
+}

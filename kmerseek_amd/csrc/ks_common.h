@@ -344,13 +344,14 @@ enum : u32 {
     KS_PIN_UNION = 230,      // 2 words, union by group: distinct (group, hash) runs
     KS_PIN_RSCORE = 232,     // 1 word, region scores: first row whose regions do not lie inside its sequences (ks_rscore.hip)
     KS_PIN_RALIGN = 233,     // 2 words, region alignments: first row whose regions do not lie inside its sequences | first row with a sequence too long (ks_ralign.hip)
-    KS_PIN_END = 235,
+    KS_PIN_RTRACE = 235,     // 8 words, region traceback: bad row | sequence too long | alignment outside its region's sequences | walk that does not close, then the scan totals (ks_rtrace.hip)
+    KS_PIN_END = 243,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -490,10 +491,26 @@ struct ks_raligns {
     u32 *d_qstart, *d_qlength, *d_tstart, *d_tlength;               // n_regions
     u32 *d_identities, *d_positives, *d_gap_opens, *d_gaps, *d_aln_length; // n_regions
     i64 *d_score;                                                   // n_regions
+    // the options the alignments were made with: ks_regions_traceback walks the path of exactly this program
+    u32 band, gap_open, gap_extend, x_drop;
+    int8_t matrix[KS_RSCORE_ALPHABET * KS_RSCORE_ALPHABET];
 };
 // ks_regions_align behind its argument checks (opts: not NULL, validated; R, H: of ctx, equal row counts)
 int ks_regions_align_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
                           const ks_ralign_opts *opts, ks_raligns *S);
+
+// the paths of the alignments of a ks_raligns, one CIGAR per region (ks_rtrace.hip)
+struct ks_cigars {
+    ks_ctx *ctx;
+    u64 n_rows, n_regions, n_ops;
+    u64 *d_op_offsets; // n_regions + 1
+    u32 *d_ops;        // n_ops: len << 4 | op
+    u64 dir_bytes;     // direction scratch the call allocated, the slices it ran in (diagnostic)
+    u32 n_slices;
+};
+// ks_regions_traceback behind its argument checks (flags validated; R, H, S: of ctx, equal counts)
+int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
+                              const ks_raligns *S, u32 flags, u64 max_scratch_bytes, ks_cigars *C);
 
 // clusters of a hit list read as a graph: its connected components (ks_cluster.hip) or greedy representative clusters (ks_greedy.hip)
 struct ks_clusters {

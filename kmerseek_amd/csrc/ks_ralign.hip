@@ -1,42 +1,12 @@
 // ks_ralign.hip — ks_regions_align: every region of a ks_regions extended WITH gaps from the middle pair of its seed, in both
 // directions, by a banded affine-gap dynamic program under a row-level X-drop rule (include/kmerseek_amd.h has the semantics;
-// all of it in integers).  The gapped stage behind ks_rscore.hip's ungapped one; no traceback.
+// all of it in integers).  The gapped stage behind ks_rscore.hip's ungapped one.  The path itself is ks_rtrace.hip's
+// (ks_regions_traceback), from the options this pass records in its result.
 //
 // One kernel, a wave per region, the shape of k_rscore: the class table and the matrix in LDS, the region's row and sequences
-// through rk_locate (ks_rkit.h), everything a wave decides in scalar registers.
-//   lanes      lane k is diagonal k - W of the band (W <= 31: 2W + 1 <= 63 lanes; the others hold the sentinel and only idle
-//              along).  A step is one row x of the program: lane k holds the cell (x, y = x + k - W).
-//   state      H and F of the previous row stay in registers, each with the four counts of the path that made it.
-//              D reads the lane's own H (the same diagonal).  F reads the lane above: every lane first forms what it hands
-//              down, G = max(H - o - e, F - e), and G with its counts moves one lane by DPP (wave_shl:1).
-//              E of a row is one inclusive max scan (DPP, ks_wave_incl_max) of H~ + k * e, moved one lane up.  Only when some
-//              lane takes its E are the source lane — the last lane below that attains the running maximum, from one ballot:
-//              among equal values the largest lane, the tie rule of the contract — and its counts (ds_bpermute) fetched.
-//   residues   RA_CHUNK rows at a time: lane i loads the query byte of row i of the chunk (the row's byte is then a readlane:
-//              wave-uniform), and the chunk's target window — RA_CHUNK + 2W bytes — goes upper-cased and classified into the
-//              wave's own LDS strip; a row reads strip[r + k].  No global load depends on a row.  The left side is the same
-//              function with descending addresses.
-//   result     every lane keeps its best cell, replaced by strictly larger values only (its smallest x); one 64-bit wave
-//              maximum of (H, -x, -lane) at the end picks the largest H, then the smallest x, then the smallest y.  The row
-//              maximum for the X-drop rule is one DPP max scan per row; the exit is wave-uniform.
-//
-// 32 bits are enough, and the sentinel is safe.  Sequences are at most RA_MAX_LEN = 2^20 residues (longer ones are refused),
-// |M| <= 128, o, e <= 255, W <= 31.  Every existing cell (x, y) is reached by min(x, y) diagonal steps and one gap of at most W
-// residues inside the band, so H >= -(2^20 * 128 + 255 + 31 * 255) > -2^27 - 2^14, and H <= 2^20 * 127 < 2^27.  RA_NEG = -2^30
-// stands for "no such cell / state".  It is never carried along: a lane whose cell does not exist is SET to RA_NEG in every
-// row, so what is derived from it in one row is at least RA_NEG - 128 - 2 * 255 - 62 * 255 > -2^31 (no wrap) and at most
-// RA_NEG + 127 + 62 * 255 < -2^27 - 2^14 (below every real value: it never wins a maximum against one, and every existing
-// cell of a row x >= 1 has a real D or a real F).  B - R < 2^28 + 2^14, x_drop <= 2^20: the X-drop test is an i32 compare.
-// Counts: at most 2^21 + 31 steps on a path.
-#include "ks_rkit.h"
-
-#define RA_THREADS 256
-#define RA_CHUNK 64           // rows whose residues are staged at once (ks_debug_ralign_chunk)
-#define RA_WMAX 31
-#define RA_STRIP (RA_CHUNK + 64) // >= RA_CHUNK + 2 * RA_WMAX, two entries per lane
-#define RA_NEG (-(1 << 30))
-#define RA_MAX_LEN (1u << 20)
-static_assert(RA_CHUNK <= 64 && RA_CHUNK + 2 * RA_WMAX <= RA_STRIP && RA_STRIP == 128, "a chunk is a lane per row, its window two entries per lane");
+// through rk_locate (ks_rkit.h), everything a wave decides in scalar registers.  The extension itself — lanes, state, residues,
+// result, and why 32 bits are enough — is ra_extend<false> of ks_ralign_kit.h.
+#include "ks_ralign_kit.h"
 
 struct ra_args {
     rk_in in;
@@ -45,106 +15,6 @@ struct ra_args {
     i64 *o_score;
     unsigned long long *bad; // [0] the first row rk_locate refuses, [1] the first row with a sequence longer than RA_MAX_LEN
 };
-
-struct ra_cnt { u32 id, po, go, ga; }; // identities, positives, gap opens, gap residues of the path into a state
-struct ra_ext { u32 x, y; int score; ra_cnt c; };
-
-// the value of the lane above (lane 63: `none`)
-KS_DEV u32 ra_lane_above(u32 v, u32 none) { return (u32)__builtin_amdgcn_update_dpp((int)none, (int)v, 0x130, 0xf, 0xf, false); } // wave_shl:1
-KS_DEV u32 ra_bias(int v) { return (u32)v ^ 0x80000000u; } // order-preserving i32 -> u32
-KS_DEV int ra_unbias(u32 v) { return (int)(v ^ 0x80000000u); }
-
-// One side's extension (all 64 lanes enter; every argument but `lane` and `strip` is wave-uniform).  Q_x = qp[sgn * x] for
-// x = 1 .. X and T_y = tp[sgn * y] for y = 1 .. Y: the caller points qp / tp at the anchor pair.  strip: the wave's own.
-KS_DEV ra_ext ra_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 X, u32 Y, const ra_args &A, const u8 *s_cls, const signed char *s_M,
-                        unsigned short *strip, u32 lane) {
-    const u32 W = A.W, ke = lane * A.e;
-    const int oe = (int)(A.o + A.e), e = (int)A.e, o = (int)A.o;
-    const bool inband = lane <= 2 * W;
-    // row 0: H(0, 0) = 0, H(0, y) = E from it
-    const int y0 = (int)lane - (int)W;
-    bool ex = inband && y0 >= 0 && (u32)y0 <= Y;
-    int H = ex ? (y0 ? -(o + y0 * e) : 0) : RA_NEG, F = RA_NEG;
-    ra_cnt Hc = {0u, 0u, ex && y0 > 0 ? 1u : 0u, ex ? (u32)y0 : 0u}, Fc = {0u, 0u, 0u, 0u};
-    int bH = H, B = 0; // the lane's best cell; the best row maximum so far (R_0 = H(0, 0) = 0)
-    u32 bx = 0;
-    ra_cnt bc = Hc;
-    const u32 x_max = X < Y + W ? X : Y + W; // the last row that has a cell
-    bool stop = false;
-    for (u32 base = 0; base < x_max && !stop; base += RA_CHUNK) {
-        const u32 left = x_max - base, n_rows = left < RA_CHUNK ? left : RA_CHUNK;
-        u32 qbyte = 0;
-        if (lane < n_rows) qbyte = qp[sgn * (i64)((u64)base + 1 + lane)];
-        __builtin_amdgcn_wave_barrier(); // (the rows of the chunk before have read the strip; same wave: LDS operations execute in order)
-#pragma unroll
-        for (u32 h = 0; h < 2; h++) { // entry j of the strip is T_y, y = base + 1 - W + j
-            const u32 j = lane + 64 * h;
-            const i64 y = (i64)base + 1 - (i64)W + j;
-            u32 v = 0;
-            if (y >= 1 && y <= (i64)Y) {
-                const u32 c = tp[sgn * y];
-                v = rk_upper(c) | ((u32)s_cls[c] << 8);
-            }
-            strip[j] = (unsigned short)v;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (u32 r = 0; r < n_rows; r++) {
-            const u32 x = base + 1 + r;
-            const u32 cq = (u32)__builtin_amdgcn_readlane((int)qbyte, (int)r);
-            const u32 cq_up = rk_upper(cq), cq_row = rk_class(cq) * RK_A;
-            const i64 y = (i64)x + lane - W;
-            ex = inband && y >= 0 && y <= (i64)Y;
-            const u32 tv = strip[r + lane];
-            const int s = s_M[cq_row + (tv >> 8)];
-            const bool idt = (tv & 0xffu) == cq_up;
-            // F: what the lane above hands down from the row before (on a tie the continued gap)
-            const int gH = H - oe, gF = F - e;
-            const bool cont = gF >= gH;
-            const int G = cont ? gF : gH;
-            const ra_cnt Gc = {cont ? Fc.id : Hc.id, cont ? Fc.po : Hc.po, cont ? Fc.go : Hc.go + 1u, (cont ? Fc.ga : Hc.ga) + 1u};
-            const int Fn = (int)ra_lane_above((u32)G, (u32)RA_NEG);
-            const ra_cnt Fnc = {ra_lane_above(Gc.id, 0u), ra_lane_above(Gc.po, 0u), ra_lane_above(Gc.go, 0u), ra_lane_above(Gc.ga, 0u)};
-            // D: the lane's own diagonal; H~ = max(D, F), on a tie D
-            const int D = H + s;
-            const bool diag = D >= Fn;
-            int Ht = diag ? D : Fn;
-            ra_cnt Htc = {diag ? Hc.id + (idt ? 1u : 0u) : Fnc.id, diag ? Hc.po + (s > 0 ? 1u : 0u) : Fnc.po, diag ? Hc.go : Fnc.go,
-                          diag ? Hc.ga : Fnc.ga};
-            if (!ex) Ht = RA_NEG;
-            // E: the best H~ of a lower lane, its gap paid by the lane distance; on a tie the largest lane
-            const u32 key = ra_bias(Ht + (int)ke), inc = ks_wave_incl_max(key);
-            const u32 below = ks_lane_below(inc); // (a DPP move: outside every per-lane condition, all lanes take part)
-            const int E = lane ? ra_unbias(below) - o - (int)ke : RA_NEG;
-            const bool gap = ex && E > Ht; // (on a tie H~)
-            H = Ht; Hc = Htc;
-            if (__ballot(gap)) {
-                // the source: the last lane below this one that attains the running maximum (a lane that equals it is a new
-                // record under >=: the largest lane wins a tie; lane 0 always is one)
-                const u64 rec = __ballot(key == inc) & ks_lanes_below(lane);
-                const u32 src = 63u - (u32)__clzll((long long)(rec | 1ULL));
-                const u32 sid = (u32)__shfl((int)Htc.id, (int)src), spo = (u32)__shfl((int)Htc.po, (int)src);
-                const u32 sgo = (u32)__shfl((int)Htc.go, (int)src), sga = (u32)__shfl((int)Htc.ga, (int)src);
-                if (gap) { H = E; Hc = {sid, spo, sgo + 1u, sga + (lane - src)}; }
-            }
-            F = Fn; Fc = Fnc;
-            if (!ex) { H = RA_NEG; F = RA_NEG; }
-            const int R = ra_unbias((u32)__builtin_amdgcn_readlane((int)ks_wave_incl_max(ra_bias(H)), 63)); // the row's maximum
-            if (ex && H > bH) { bH = H; bx = x; bc = Hc; }
-            B = R > B ? R : B;
-            if (B - R > (int)A.x_drop) { stop = true; break; }
-        }
-    }
-    // the largest H; then the smallest x; then the smallest y = the lowest lane (lane W holds H(0, 0) = 0: there is a real one)
-    const u64 m = ks_wave_max64(((u64)ra_bias(bH) << 32) | ((u64)(0x3ffffffu - bx) << 6) | (63u - lane));
-    const u32 wl = 63u - (u32)(m & 63u);
-    ra_ext out;
-    out.x = 0x3ffffffu - (u32)((m >> 6) & 0x3ffffffu);
-    out.y = out.x + wl - W;
-    out.score = ra_unbias((u32)(m >> 32));
-    out.c = {(u32)__builtin_amdgcn_readlane((int)bc.id, (int)wl), (u32)__builtin_amdgcn_readlane((int)bc.po, (int)wl),
-             (u32)__builtin_amdgcn_readlane((int)bc.go, (int)wl), (u32)__builtin_amdgcn_readlane((int)bc.ga, (int)wl)};
-    return out;
-}
 
 __global__ __launch_bounds__(RA_THREADS) void k_ralign(ra_args A) {
     __shared__ u8 s_cls[256];
@@ -170,8 +40,8 @@ __global__ __launch_bounds__(RA_THREADS) void k_ralign(ra_args A) {
     const u8 *qa = A.in.q_res + P.qb + ai, *ta = A.in.t_res + P.tb + bj;
     const u32 cq = ks_readfirst(*qa), ct = ks_readfirst(*ta);
     const int s = s_M[s_cls[cq] * RK_A + s_cls[ct]];
-    const ra_ext R = ra_extend(qa, ta, 1, Lq - 1 - ai, Lt - 1 - bj, A, s_cls, s_M, s_strip[wave], lane);
-    const ra_ext L = ra_extend(qa, ta, -1, ai, bj, A, s_cls, s_M, s_strip[wave], lane);
+    const ra_ext R = ra_extend<false>(qa, ta, 1, Lq - 1 - ai, Lt - 1 - bj, A, s_cls, s_M, s_strip[wave], lane);
+    const ra_ext L = ra_extend<false>(qa, ta, -1, ai, bj, A, s_cls, s_M, s_strip[wave], lane);
     if (lane == 0) {
         const u32 gaps = L.c.ga + R.c.ga;
         A.o_qs[g] = ai - L.x; A.o_ql[g] = L.x + 1 + R.x; A.o_ts[g] = bj - L.y; A.o_tl[g] = L.y + 1 + R.y;
@@ -187,6 +57,8 @@ int ks_regions_align_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, co
                           const ks_ralign_opts *opts, ks_raligns *S) {
     const u64 n_rows = R->n_rows, ng = R->n_regions;
     S->n_rows = n_rows; S->n_regions = ng;
+    S->band = opts->band; S->gap_open = opts->gap_open; S->gap_extend = opts->gap_extend; S->x_drop = opts->x_drop;
+    for (int i = 0; i < RK_A * RK_A; i++) S->matrix[i] = opts->matrix ? opts->matrix[i] : (i / RK_A == i % RK_A) ? 1 : -1;
     KS_TRY(ks_alloc(ctx, &S->d_row_offsets, (size_t)n_rows + 1));
     for (u32 **col : {&S->d_qstart, &S->d_qlength, &S->d_tstart, &S->d_tlength, &S->d_identities, &S->d_positives, &S->d_gap_opens,
                       &S->d_gaps, &S->d_aln_length})

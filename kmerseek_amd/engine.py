@@ -511,7 +511,7 @@ class Context:
         banded (|diagonal shift| <= band <= 31) affine-gap (a gap of L residues costs gap_open + L * gap_extend, each <= 255)
         dynamic program under `matrix` (as score_regions), stopped by a row-level X-drop (x_drop <= 2^20).  Per region the
         alignment's q_start, q_length, t_start, t_length, score (i64), identities, positives, gap_opens, gaps and aln_length;
-        no traceback.  include/kmerseek_amd.h has the definitions."""
+        the path itself is trace_regions'.  include/kmerseek_amd.h has the definitions."""
         opts, keep = self._ralign_opts(matrix, band, gap_open, gap_extend, x_drop)
         out = C.c_void_p()
         self._check(self._L.ks_regions_align(self._h, regions._h, hits._h, C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res),
@@ -533,6 +533,43 @@ class Context:
             return self.align_regions_device(regions, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res), bufs[2].ptr, bufs[3].ptr,
                                              len(t_off) - 1, len(t_res), matrix=matrix, band=band, gap_open=gap_open,
                                              gap_extend=gap_extend, x_drop=x_drop)
+        finally:
+            for b in bufs:
+                b.free()
+
+    @staticmethod
+    def _rtrace_opts(eqx: bool, max_scratch_bytes: int):
+        if isinstance(max_scratch_bytes, bool) or int(max_scratch_bytes) != max_scratch_bytes or not 0 <= int(max_scratch_bytes) < 2 ** 64:
+            raise ValueError(f"max_scratch_bytes = {max_scratch_bytes} is not an integer in [0, 2^64)")
+        return _lib.ks_rtrace_opts(_lib.KS_RTRACE_EQX if eqx else 0, 0, int(max_scratch_bytes))
+
+    def trace_regions_device(self, regions: "Regions", hits: "Hits", d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
+                             d_t_res: int, d_t_off: int, n_t: int, n_t_res: int, alignments: "RegionAlignments", eqx: bool = False,
+                             max_scratch_bytes: int = 0) -> "RegionCigars":
+        """ks_regions_traceback from device-resident residue batches: the path of every alignment of `alignments` — made by
+        align_regions from these regions, hits and batches, whose options it recorded — as a CIGAR with the query as the read:
+        M (with eqx=True: = and X), I, D.  max_scratch_bytes bounds the direction scratch of one slice of regions (0: 1 GiB).
+        include/kmerseek_amd.h has the definitions."""
+        opts = self._rtrace_opts(eqx, max_scratch_bytes)
+        out = C.c_void_p()
+        self._check(self._L.ks_regions_traceback(self._h, regions._h, hits._h, C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q),
+                                                 int(n_q_res), C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res),
+                                                 alignments._h, C.byref(opts), C.byref(out)))
+        return RegionCigars(self, out)
+
+    def trace_regions(self, regions: "Regions", hits: "Hits", q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray,
+                      t_off: np.ndarray, alignments: "RegionAlignments", eqx: bool = False,
+                      max_scratch_bytes: int = 0) -> "RegionCigars":
+        """trace_regions_device from host arrays (the batches `alignments` was made on): uploaded, traced, released."""
+        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        self._rtrace_opts(eqx, max_scratch_bytes)  # (refused before anything is uploaded)
+        bufs = []
+        try:
+            for a in (q_res, q_off, t_res, t_off):
+                bufs.append(self.to_device(a))
+            return self.trace_regions_device(regions, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res), bufs[2].ptr, bufs[3].ptr,
+                                             len(t_off) - 1, len(t_res), alignments, eqx=eqx, max_scratch_bytes=max_scratch_bytes)
         finally:
             for b in bufs:
                 b.free()
@@ -975,6 +1012,62 @@ class RegionAlignments(_Owned):
         cols = [np.zeros(n, np.int64 if c == "score" else np.uint32) for c in self._COLUMNS[1:]]
         self._ctx._check(self._ctx._L.ks_raligns_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
         return (offs, *cols)
+
+
+CIGAR_OPS = "MIDNSHP=X"  # the BAM op codes
+
+
+def cigar_strings(op_offsets, ops) -> List[str]:
+    """The CIGAR of every region as text ("35M2D17M1I40M") from RegionCigars.to_host(): an op is len << 4 | code."""
+    offs = np.asarray(op_offsets).tolist()
+    ops = np.asarray(ops).tolist()
+    if any(v & 15 >= len(CIGAR_OPS) for v in ops):
+        raise ValueError("an op code beyond the BAM codes")
+    return ["".join(f"{v >> 4}{CIGAR_OPS[v & 15]}" for v in ops[offs[g]:offs[g + 1]]) for g in range(len(offs) - 1)]
+
+
+class RegionCigars(_Owned):
+    """Device-resident paths of the alignments of a hit list's regions (ks_cigars): a CSR over the regions in the order of the
+    RegionAlignments they were traced from, region g owns ops [op_offsets[g], op_offsets[g + 1]), an op is len << 4 | BAM code."""
+    _free = "ks_cigars_free"
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_cigars_n_rows(self._h))
+
+    @property
+    def n_regions(self) -> int:
+        return int(self._ctx._L.ks_cigars_n_regions(self._h))
+
+    @property
+    def n_ops(self) -> int:
+        return int(self._ctx._L.ks_cigars_n_ops(self._h))
+
+    @property
+    def n_slices(self) -> int:
+        """Slices of regions the traceback ran in (1 unless the directions did not fit max_scratch_bytes).  Diagnostic."""
+        return int(self._ctx._L.ks_cigars_n_slices(self._h))
+
+    @property
+    def scratch_bytes(self) -> int:
+        """Direction scratch the traceback allocated.  Diagnostic."""
+        return int(self._ctx._L.ks_cigars_scratch_bytes(self._h))
+
+    def device_ptrs(self) -> Tuple[int, int]:
+        """Raw device pointers (op_offsets u64[n_regions + 1], ops u32[n_ops])."""
+        L = self._ctx._L
+        return (int(L.ks_cigars_device_op_offsets(self._h) or 0), int(L.ks_cigars_device_ops(self._h) or 0))
+
+    def to_host(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(op_offsets u64[n_regions + 1], ops u32[n_ops])."""
+        offs = np.zeros(self.n_regions + 1, np.uint64)
+        ops = np.zeros(self.n_ops, np.uint32)
+        self._ctx._check(self._ctx._L.ks_cigars_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(ops)))
+        return offs, ops
+
+    def strings(self) -> List[str]:
+        """The CIGAR of every region as text, e.g. "35M2D17M1I40M"."""
+        return cigar_strings(*self.to_host())
 
 
 class Clusters(_Owned):

@@ -712,7 +712,7 @@ def read_score_matrix(path: str) -> np.ndarray:
 
 
 def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, regions_host,
-                moltype: str, scores=None, alignments=None) -> List[dict]:
+                moltype: str, scores=None, alignments=None, cigars=None) -> List[dict]:
     """One row per region of the device's chaining (Context.match_regions; regions_host = Regions.to_host()): hit row
     r = (qid[r], tid[r]) owns regions [row_offsets[r], row_offsets[r + 1]).  The stitched columns of search.py:195-240 —
     query / match / encoded are the residues the region spans, sliced from the records (a region lies on one diagonal, so
@@ -728,7 +728,10 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
     alignments = RegionAlignments.to_host() of the same regions (Context.align_regions): every row also carries its region's
     gapped alignment — aln_score, aln_q_start / aln_q_end and aln_t_start / aln_t_end (half-open), aln_length (aligned pairs +
     gap residues), aln_identities, aln_positives, aln_mismatches (aligned pairs that are no identity), aln_gap_opens, aln_gaps
-    and aln_pident (100 * aln_identities / aln_length).  The other columns, and the order of the rows, do not change."""
+    and aln_pident (100 * aln_identities / aln_length).  The other columns, and the order of the rows, do not change.
+
+    cigars = RegionCigars.to_host() of those alignments (Context.trace_regions; needs alignments): every row also carries
+    aln_cigar, its alignment's path as text with the query as the read ("35M2D17M1I40M"; = and X for M when traced with eqx)."""
     offs, q_start, t_start, length, n_kmers, covered = [np.asarray(c).tolist() for c in regions_host]
     if scores is not None:
         s_offs, s_q, s_t, s_len, s_score, s_ident, s_pos, _ = [np.asarray(c).tolist() for c in scores]
@@ -738,6 +741,13 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
         al = [np.asarray(c).tolist() for c in alignments]
         if al[0] != offs:
             raise ValueError("alignments and regions are not of the same hit rows")
+    if cigars is not None:
+        if alignments is None:
+            raise ValueError("cigars need alignments: they are the paths of alignments")
+        from .engine import cigar_strings
+        cg = cigar_strings(*cigars)
+        if len(cg) != len(q_start):
+            raise ValueError("cigars and regions are not of the same regions")
     out = []
     for r, (q, t) in enumerate(zip(np.asarray(qid).tolist(), np.asarray(tid).tolist())):
         qn, qseq = q_records[q]
@@ -758,6 +768,8 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
                             "aln_length": ln_, "aln_identities": id_, "aln_positives": po_, "aln_mismatches": ln_ - ga_ - id_,
                             "aln_gap_opens": go_, "aln_gaps": ga_,
                             "aln_pident": format_f64(100.0 * float(id_) / float(ln_) if ln_ else math.nan)})
+                if cigars is not None:
+                    row["aln_cigar"] = cg[g]
             out.append((q, row))
     out.sort(key=lambda e: (e[0], e[1]["query_start"], e[1]["query_end"]))
     return [row for _, row in out]
@@ -767,7 +779,7 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 ctx: Optional[Context] = None, regions: bool = False, max_gap: int = 0,
                                 min_kmers: int = 1, score: bool = False, extend: bool = False, x_drop: int = 0,
                                 matrix=None, gapped: bool = False, band: int = 16, gap_open: int = 11, gap_extend: int = 1,
-                                gapped_x_drop: int = 30) -> List[dict]:
+                                gapped_x_drop: int = 30, cigar: bool = False, eqx: bool = False) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -775,11 +787,15 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     score=True (needs regions=True): the regions are scored on the device too (Context.score_regions with matrix, extend and
     x_drop) and the rows carry the columns `region_rows` adds for scores.
     gapped=True (needs regions=True): every region is aligned with gaps on the device (Context.align_regions with matrix, band,
-    gap_open, gap_extend and gapped_x_drop) and the rows carry the aln_* columns `region_rows` adds for alignments."""
+    gap_open, gap_extend and gapped_x_drop) and the rows carry the aln_* columns `region_rows` adds for alignments.
+    cigar=True (needs gapped=True): the alignments are traced back on the device too (Context.trace_regions, with eqx) and the
+    rows carry aln_cigar."""
     if score and not regions:
         raise ValueError("score=True needs regions=True: scores are of regions")
     if gapped and not regions:
         raise ValueError("gapped=True needs regions=True: alignments are of regions")
+    if cigar and not gapped:
+        raise ValueError("cigar=True needs gapped=True: CIGARs are of gapped alignments")
     own = ctx is None
     ctx = ctx or Context(0)
     try:
@@ -797,7 +813,7 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
         if regions:
             rg = ctx.match_regions(mp, max_gap=max_gap, min_kmers=min_kmers)
             rg_host = rg.to_host()
-            sc_host = None
+            sc_host = cg_host = None
             if score:
                 sc = ctx.score_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, extend=extend, x_drop=x_drop)
                 sc_host = sc.to_host()
@@ -806,10 +822,16 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                 al = ctx.align_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, band=band, gap_open=gap_open,
                                        gap_extend=gap_extend, x_drop=gapped_x_drop)
                 al_host = al.to_host()
+                if cigar:
+                    cg = ctx.trace_regions(rg, hits, q_res, q_off, t_res, t_off, al, eqx=eqx)
+                    cg_host = cg.to_host()
+                    cg.free()
                 al.free()
             for o in (rg, mp, qp, tp, hits, Q, T):
                 o.free()
             if gapped:
+                if cigar:
+                    return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, cigars=cg_host)
                 return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host)
             return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host)
         offs, qs, ts = mp.to_host()[:3]
