@@ -524,7 +524,8 @@ void ks_regions_free(ks_regions *r);
  *   score = left_score + core_score + right_score                                        i64[n_regions]
  *   identities, positives   u32[n_regions]  counted over the extended span
  *   core_identities         u32[n_regions]  counted over the core alone
- * Extended regions of one row may overlap or coincide: nothing is merged or de-duplicated.  The result never depends on
+ * Extended regions of one row may overlap or coincide: nothing is merged or de-duplicated here (ks_rscores_cull, below, does
+ * that).  The result never depends on
  * the launch geometry or on how many positions a wave examines per step.  An R without rows or regions gives a valid empty
  * result.
  * KS_ERR_INVALID_ARG: unknown flags / a non-zero reserved field (checked before any device work, also with ctx == NULL), NULL
@@ -596,7 +597,8 @@ uint32_t ks_debug_rscore_step(void);
  *   q_start = ai - x_left, q_length = x_left + 1 + x_right, t_start = bj - y_left, t_length = y_left + 1 + y_right   u32
  *   score = M[anchor pair] + left + right                                                                            i64
  *   identities, positives (the anchor pair included), gap_opens, gaps, aln_length = aligned pairs + gaps              u32
- * Alignments of one row may overlap or coincide: nothing is merged.  The result never depends on the launch geometry or on
+ * Alignments of one row may overlap or coincide: nothing is merged here (ks_raligns_cull, below, keeps one of each).  The result
+ * never depends on the launch geometry or on
  * ks_debug_ralign_chunk().  An R without rows or regions gives a valid empty result.
  * KS_ERR_INVALID_ARG: an option out of range or unknown flags (checked before any device work, also with ctx == NULL), and
  * everything ks_regions_score refuses, with the same check: ks_last_error names the first bad row, nothing is read outside
@@ -706,6 +708,91 @@ int ks_cigars_copy_to_host(ks_ctx *ctx, const ks_cigars *c, uint64_t *op_offsets
 void ks_cigars_free(ks_cigars *c);
 /* rows of directions one wave stages at once for the walk: the tests place end cells around it */
 uint32_t ks_debug_rtrace_stage(void);
+
+/* ---- region cull: one row per distinct alignment of a hit, best first ------------------------------------------------------ */
+
+/* What every seed-and-extend search closes its extension stage with (HSP culling): of the regions of one hit row, those that
+ * a better region of the same row covers are removed.  ks_regions_align gives every fragment an indel splits a match into the
+ * one alignment they belong to — the same alignment, once per fragment; a repeat gives alignments inside alignments.  This
+ * pass keeps one of each and says which region stands for which.  It is a pass over extents and scores only: it reads no
+ * residues.  The same pass serves a ks_raligns (both sides have their own length) and a ks_rscores (the ungapped extended
+ * regions: one length for both sides).  All arithmetic is in integers, in 64 bits.
+ * Input: a CSR over hit rows and five columns per region:
+ *   row_offsets u64[n_rows + 1];  q_start, q_length, t_start, t_length u32[n];  score i64[n]
+ *   region g is [q_start, q_start + q_length) in the query and [t_start, t_start + t_length) in the target.
+ * Options: overlap_pct = P in [1, 100], 0 means 100;  max_per_row = N, 0 means no limit;  min_score, used only with the flag
+ * KS_RCULL_MIN_SCORE.
+ * Priority inside a row: g comes before h iff score[g] > score[h], or the scores are equal and g < h by input index.
+ * covers(k, g) holds iff  ovq * 100 >= P * q_length[g]  and  ovt * 100 >= P * t_length[g],  where
+ *   ovq = max(0, min(qe_k, qe_g) - max(qs_k, qs_g))  (qe = q_start + q_length, in u64) and ovt is the same on the target.
+ * The relation is relative to g, the region being removed: it is not symmetric.  With P = 100 it means "g lies inside k on
+ * both sequences".  Overlap on one sequence alone never covers: that is a repeat.
+ * The regions of a row are decided in priority order, each by the first rule that applies:
+ *   1. with the flag, score[g] < min_score: dropped, keeper[g] = KS_RCULL_NONE.  Such a region never covers anything.
+ *   2. a kept region of the row covers g: removed; keeper[g] = the first such kept region in priority order.
+ *   3. the row already keeps N regions (N > 0): dropped, keeper[g] = KS_RCULL_NONE.
+ *   4. otherwise g is kept and keeper[g] = g.
+ * The pass is greedy, not transitive: a removed region covers nothing.  If A removes B and only B would have covered C, C is kept.
+ * Result (device-resident):
+ *   row_offsets u64[n_rows + 1]   a CSR of the kept regions over the same hit rows
+ *   per kept region: src_region u32, its input index — ascending inside a row, so the input's (q_start, t_start) order
+ *                    survives; rank u32, 0 is the row's best kept region; n_merged u32, the input regions that name it as
+ *                    keeper, itself included
+ *   keeper u32[n]                 one per input region
+ *   row_best_score f64[n_rows]    (double)score of the row's rank-0 region, NaN for a row that keeps none: exactly a d_score
+ *                                 column for ks_hits_best with KS_BEST_SCORE, which ranks NaN last
+ * The sum of n_merged plus the regions with keeper KS_RCULL_NONE is n.  The result does not depend on the path a row took
+ * (KS_DEBUG_CULL_PATH = 1 / 2 / 3 force every row of at most 64 regions onto a wave / every row onto a workgroup / that with a
+ * small LDS capacity, for the tests) or on the launch geometry.  An input without rows or regions gives a valid empty result.
+ * Culling a culled list again with the same P, no limit and no min_score keeps everything with n_merged = 1.
+ * KS_ERR_INVALID_ARG: unknown flags, a non-zero reserved field or P > 100 (checked before any device work, also with
+ * ctx == NULL); NULL arguments; an object of another context; row_offsets that is not a non-decreasing CSR from 0 to n — a plan
+ * kernel checks this before anything is indexed by it, ks_last_error names the first bad row; a region with a length of 0
+ * (the first such region is named).  KS_ERR_CAPACITY: 2^32 - 2 or more rows, more than 2^32 - 1 regions.
+ * One stream, synchronous on return, one host wait (the kept count and the bad-row words come back with it); all memory comes
+ * from the context's pool: 28 bytes of scratch per region and 24 per hit row. */
+typedef struct ks_rcull ks_rcull;
+#define KS_RCULL_NONE 0xffffffffu
+#define KS_RCULL_MIN_SCORE 1u
+typedef struct ks_rcull_opts {
+    uint32_t overlap_pct;  /* P in [1, 100]; 0 = 100 */
+    uint32_t max_per_row;  /* N; 0 = no limit */
+    int64_t  min_score;    /* used with KS_RCULL_MIN_SCORE */
+    uint32_t flags;        /* KS_RCULL_MIN_SCORE */
+    uint32_t reserved;     /* 0 */
+} ks_rcull_opts;
+/* opts == NULL: P = 100, no limit, no min_score.  d_t_length == NULL: the target lengths are the query lengths. */
+int ks_regions_cull_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint32_t *d_q_start, const uint32_t *d_q_length,
+                           const uint32_t *d_t_start, const uint32_t *d_t_length, const int64_t *d_score, uint64_t n_rows,
+                           uint64_t n_regions, const ks_rcull_opts *opts, ks_rcull **out);
+/* the same on the columns of an object: the alignments' extents and score; the extended regions' placement, `length` for both
+ * sides, and score */
+int ks_raligns_cull(ks_ctx *ctx, const ks_raligns *alignments, const ks_rcull_opts *opts, ks_rcull **out);
+int ks_rscores_cull(ks_ctx *ctx, const ks_rscores *scores, const ks_rcull_opts *opts, ks_rcull **out);
+uint64_t ks_rcull_n_rows(const ks_rcull *c);
+uint64_t ks_rcull_n_regions(const ks_rcull *c); /* of the input */
+uint64_t ks_rcull_n_kept(const ks_rcull *c);
+/* device pointers, valid until ks_rcull_free */
+const uint64_t *ks_rcull_device_row_offsets(const ks_rcull *c);
+const uint32_t *ks_rcull_device_src_region(const ks_rcull *c);
+const uint32_t *ks_rcull_device_rank(const ks_rcull *c);
+const uint32_t *ks_rcull_device_n_merged(const ks_rcull *c);
+const uint32_t *ks_rcull_device_keeper(const ks_rcull *c);
+const double *ks_rcull_device_row_best_score(const ks_rcull *c);
+/* any destination may be NULL */
+int ks_rcull_copy_to_host(ks_ctx *ctx, const ks_rcull *c, uint64_t *row_offsets, uint32_t *src_region, uint32_t *rank,
+                          uint32_t *n_merged, uint32_t *keeper, double *row_best_score);
+void ks_rcull_free(ks_rcull *c);
+/* The object of the kept regions only: every column gathered by src_region, row_offsets from the cull.  ks_raligns_take
+ * carries the recorded options and the matrix: a taken ks_regions with a taken ks_raligns is a valid input of
+ * ks_regions_traceback, which then traces only what was kept.  KS_ERR_INVALID_ARG: NULL arguments, an object of another
+ * context, an object whose row or region count is not that of the cull's input.  Synchronous on return. */
+int ks_regions_take(ks_ctx *ctx, const ks_regions *regions, const ks_rcull *cull, ks_regions **out);
+int ks_rscores_take(ks_ctx *ctx, const ks_rscores *scores, const ks_rcull *cull, ks_rscores **out);
+int ks_raligns_take(ks_ctx *ctx, const ks_raligns *alignments, const ks_rcull *cull, ks_raligns **out);
+/* regions of a row the workgroup path holds in LDS (returned) and that capacity under KS_DEBUG_CULL_PATH = 3 (*small_rows,
+ * may be NULL): the tests place rows around them */
+uint32_t ks_debug_rcull_lds_rows(uint32_t *small_rows);
 
 /* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
 

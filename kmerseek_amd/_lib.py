@@ -77,6 +77,15 @@ class ks_rtrace_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32), ("max_scratch_bytes", C.c_uint64)]
 
 
+KS_RCULL_NONE = 0xFFFFFFFF
+KS_RCULL_MIN_SCORE = 1
+
+
+class ks_rcull_opts(C.Structure):
+    _fields_ = [("overlap_pct", C.c_uint32), ("max_per_row", C.c_uint32), ("min_score", C.c_int64), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -269,6 +278,24 @@ SIGNATURES = {
     "ks_cigars_copy_to_host": (C.c_int, [_vp] * 4),
     "ks_cigars_free": (None, [_vp]),
     "ks_debug_rtrace_stage": (C.c_uint32, []),
+    "ks_regions_cull_device": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_uint64, C.c_uint64, C.POINTER(ks_rcull_opts), _pp]),
+    "ks_raligns_cull": (C.c_int, [_vp, _vp, C.POINTER(ks_rcull_opts), _pp]),
+    "ks_rscores_cull": (C.c_int, [_vp, _vp, C.POINTER(ks_rcull_opts), _pp]),
+    "ks_rcull_n_rows": (C.c_uint64, [_vp]),
+    "ks_rcull_n_regions": (C.c_uint64, [_vp]),
+    "ks_rcull_n_kept": (C.c_uint64, [_vp]),
+    "ks_rcull_device_row_offsets": (_vp, [_vp]),
+    "ks_rcull_device_src_region": (_vp, [_vp]),
+    "ks_rcull_device_rank": (_vp, [_vp]),
+    "ks_rcull_device_n_merged": (_vp, [_vp]),
+    "ks_rcull_device_keeper": (_vp, [_vp]),
+    "ks_rcull_device_row_best_score": (_vp, [_vp]),
+    "ks_rcull_copy_to_host": (C.c_int, [_vp] * 8),
+    "ks_rcull_free": (None, [_vp]),
+    "ks_regions_take": (C.c_int, [_vp, _vp, _vp, _pp]),
+    "ks_rscores_take": (C.c_int, [_vp, _vp, _vp, _pp]),
+    "ks_raligns_take": (C.c_int, [_vp, _vp, _vp, _pp]),
+    "ks_debug_rcull_lds_rows": (C.c_uint32, [_u32p]),
     "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
     "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
     "ks_corpus_n_docs": (C.c_uint32, [_vp]),

@@ -743,3 +743,155 @@ extern "C" void ks_cigars_free(ks_cigars *c) {
     ks_pool_free(c->ctx, c->d_op_offsets); ks_pool_free(c->ctx, c->d_ops);
     delete c;
 }
+
+// ---------------------------------------------------------------------------------------------
+// region cull (ks_rcull.hip): per hit row the regions no better region of the row covers; the objects of the kept regions
+// ---------------------------------------------------------------------------------------------
+// the options, defaults filled in; refused before any device work, also with ctx == NULL
+static int ks_rcull_opts_check(ks_ctx *ctx, const ks_rcull_opts *opts, ks_rcull_opts *o) {
+    const ks_rcull_opts dflt = {100u, 0u, 0, 0u, 0u};
+    *o = opts ? *opts : dflt;
+    KS_TRY(ks_opts_words_check(ctx, "region cull", o->flags, KS_RCULL_MIN_SCORE, o->reserved));
+    if (o->overlap_pct <= 100u) return KS_OK;
+    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "region cull options: overlap_pct %u (1 .. 100, 0 = 100)", o->overlap_pct) : KS_ERR_INVALID_ARG;
+}
+static int ks_rcull_run(ks_ctx *ctx, const ks_rcull_cols &cols, u64 n_rows, u64 n_regions, const ks_rcull_opts &o, ks_rcull **out) {
+    if (!out || !cols.row_offs || (n_regions && (!cols.qs || !cols.ql || !cols.ts || !cols.tl || !cols.score)))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    if (n_rows == 0 && n_regions != 0)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "region cull: %llu regions in no hit row: row_offsets is not a CSR from 0 to n", (unsigned long long)n_regions);
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_rcull> K(ctx, out, ks_rcull_free);
+    KS_TRY(ks_regions_cull_impl(ctx, cols, n_rows, n_regions, &o, K));
+    return K.commit();
+}
+extern "C" int ks_regions_cull_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint32_t *d_q_start, const uint32_t *d_q_length,
+                                      const uint32_t *d_t_start, const uint32_t *d_t_length, const int64_t *d_score, uint64_t n_rows,
+                                      uint64_t n_regions, const ks_rcull_opts *opts, ks_rcull **out) {
+    return ks_guard(ctx, [&]() -> int {
+    ks_rcull_opts o;
+    KS_TRY(ks_rcull_opts_check(ctx, opts, &o));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    return ks_rcull_run(ctx, {d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length ? d_t_length : d_q_length, d_score}, n_rows, n_regions, o, out);
+    });
+}
+extern "C" int ks_raligns_cull(ks_ctx *ctx, const ks_raligns *s, const ks_rcull_opts *opts, ks_rcull **out) {
+    return ks_guard(ctx, [&]() -> int {
+    ks_rcull_opts o;
+    KS_TRY(ks_rcull_opts_check(ctx, opts, &o));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    if (!s) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "region cull", s));
+    return ks_rcull_run(ctx, {s->d_row_offsets, s->d_qstart, s->d_qlength, s->d_tstart, s->d_tlength, s->d_score}, s->n_rows, s->n_regions, o, out);
+    });
+}
+extern "C" int ks_rscores_cull(ks_ctx *ctx, const ks_rscores *s, const ks_rcull_opts *opts, ks_rcull **out) {
+    return ks_guard(ctx, [&]() -> int {
+    ks_rcull_opts o;
+    KS_TRY(ks_rcull_opts_check(ctx, opts, &o));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    if (!s) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "region cull", s));
+    return ks_rcull_run(ctx, {s->d_row_offsets, s->d_qstart, s->d_length, s->d_tstart, s->d_length, s->d_score}, s->n_rows, s->n_regions, o, out);
+    });
+}
+extern "C" uint64_t ks_rcull_n_rows(const ks_rcull *c) { return c ? c->n_rows : 0; }
+extern "C" uint64_t ks_rcull_n_regions(const ks_rcull *c) { return c ? c->n_regions : 0; }
+extern "C" uint64_t ks_rcull_n_kept(const ks_rcull *c) { return c ? c->n_kept : 0; }
+extern "C" const uint64_t *ks_rcull_device_row_offsets(const ks_rcull *c) { return c ? c->d_row_offsets : nullptr; }
+extern "C" const uint32_t *ks_rcull_device_src_region(const ks_rcull *c) { return c ? c->d_src_region : nullptr; }
+extern "C" const uint32_t *ks_rcull_device_rank(const ks_rcull *c) { return c ? c->d_rank : nullptr; }
+extern "C" const uint32_t *ks_rcull_device_n_merged(const ks_rcull *c) { return c ? c->d_n_merged : nullptr; }
+extern "C" const uint32_t *ks_rcull_device_keeper(const ks_rcull *c) { return c ? c->d_keeper : nullptr; }
+extern "C" const double *ks_rcull_device_row_best_score(const ks_rcull *c) { return c ? c->d_row_best : nullptr; }
+
+extern "C" int ks_rcull_copy_to_host(ks_ctx *ctx, const ks_rcull *c, uint64_t *row_offsets, uint32_t *src_region, uint32_t *rank,
+                                     uint32_t *n_merged, uint32_t *keeper, double *row_best_score) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !c) return KS_ERR_INVALID_ARG;
+    const size_t nr = (size_t)c->n_rows, k = (size_t)c->n_kept * sizeof(u32);
+    return ks_columns_to_host(ctx, {{row_offsets, c->d_row_offsets, (nr + 1) * sizeof(u64)}, {src_region, c->d_src_region, k},
+                                    {rank, c->d_rank, k}, {n_merged, c->d_n_merged, k},
+                                    {keeper, c->d_keeper, (size_t)c->n_regions * sizeof(u32)}, {row_best_score, c->d_row_best, nr * sizeof(double)}});
+    });
+}
+
+extern "C" void ks_rcull_free(ks_rcull *c) {
+    if (!c) return;
+    for (void *p : {(void *)c->d_row_offsets, (void *)c->d_src_region, (void *)c->d_rank, (void *)c->d_n_merged, (void *)c->d_keeper, (void *)c->d_row_best})
+        ks_pool_free(c->ctx, p);
+    delete c;
+}
+
+// what the three takes check alike, and their row_offsets: a copy of the cull's
+template <typename T> static int ks_take_check(ks_ctx *ctx, const T *obj, const ks_rcull *cull, const void *out) {
+    if (!obj || !cull || !out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "region take", obj, cull));
+    if (obj->n_rows != cull->n_rows || obj->n_regions != cull->n_regions)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "region take: the object holds %llu regions in %llu hit rows, the cull was made of %llu in %llu: a cull of other regions",
+                       (unsigned long long)obj->n_regions, (unsigned long long)obj->n_rows, (unsigned long long)cull->n_regions, (unsigned long long)cull->n_rows);
+    return KS_OK;
+}
+template <typename T> static int ks_take_offsets(ks_ctx *ctx, const ks_rcull *cull, T *o) {
+    o->n_rows = cull->n_rows; o->n_regions = cull->n_kept;
+    KS_TRY(ks_alloc(ctx, &o->d_row_offsets, (size_t)cull->n_rows + 1));
+    KS_HIP(ctx, hipMemcpyAsync(o->d_row_offsets, cull->d_row_offsets, ((size_t)cull->n_rows + 1) * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
+    return KS_OK;
+}
+extern "C" int ks_regions_take(ks_ctx *ctx, const ks_regions *regions, const ks_rcull *cull, ks_regions **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    KS_TRY(ks_take_check(ctx, regions, cull, out));
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_regions> R(ctx, out, ks_regions_free);
+    KS_TRY(ks_take_offsets(ctx, cull, R.obj));
+    R->n_slices = regions->n_slices;
+    ks_take_cols C{{regions->d_qstart, regions->d_tstart, regions->d_length, regions->d_nkmers, regions->d_covered}, {}, 5, nullptr, nullptr};
+    u32 **dst[5] = {&R->d_qstart, &R->d_tstart, &R->d_length, &R->d_nkmers, &R->d_covered};
+    for (u32 c = 0; c < 5; c++) { KS_TRY(ks_alloc(ctx, dst[c], (size_t)cull->n_kept)); C.out[c] = *dst[c]; }
+    KS_TRY(ks_rcull_take_launch(ctx, cull, C));
+    KS_TRY(ks_stream_wait(ctx));
+    return R.commit();
+    });
+}
+extern "C" int ks_rscores_take(ks_ctx *ctx, const ks_rscores *scores, const ks_rcull *cull, ks_rscores **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    KS_TRY(ks_take_check(ctx, scores, cull, out));
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_rscores> S(ctx, out, ks_rscores_free);
+    KS_TRY(ks_take_offsets(ctx, cull, S.obj));
+    ks_take_cols C{{scores->d_qstart, scores->d_tstart, scores->d_length, scores->d_identities, scores->d_positives, scores->d_core_ident}, {}, 6, scores->d_score, nullptr};
+    u32 **dst[6] = {&S->d_qstart, &S->d_tstart, &S->d_length, &S->d_identities, &S->d_positives, &S->d_core_ident};
+    for (u32 c = 0; c < 6; c++) { KS_TRY(ks_alloc(ctx, dst[c], (size_t)cull->n_kept)); C.out[c] = *dst[c]; }
+    KS_TRY(ks_alloc(ctx, &S->d_score, (size_t)cull->n_kept)); C.out64 = S->d_score;
+    KS_TRY(ks_rcull_take_launch(ctx, cull, C));
+    KS_TRY(ks_stream_wait(ctx));
+    return S.commit();
+    });
+}
+extern "C" int ks_raligns_take(ks_ctx *ctx, const ks_raligns *s, const ks_rcull *cull, ks_raligns **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    KS_TRY(ks_take_check(ctx, s, cull, out));
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_raligns> S(ctx, out, ks_raligns_free);
+    KS_TRY(ks_take_offsets(ctx, cull, S.obj));
+    S->band = s->band; S->gap_open = s->gap_open; S->gap_extend = s->gap_extend; S->x_drop = s->x_drop;
+    memcpy(S->matrix, s->matrix, sizeof S->matrix);
+    ks_take_cols C{{s->d_qstart, s->d_qlength, s->d_tstart, s->d_tlength, s->d_identities, s->d_positives, s->d_gap_opens, s->d_gaps, s->d_aln_length}, {}, 9,
+                   s->d_score, nullptr};
+    u32 **dst[9] = {&S->d_qstart, &S->d_qlength, &S->d_tstart, &S->d_tlength, &S->d_identities, &S->d_positives, &S->d_gap_opens, &S->d_gaps, &S->d_aln_length};
+    for (u32 c = 0; c < 9; c++) { KS_TRY(ks_alloc(ctx, dst[c], (size_t)cull->n_kept)); C.out[c] = *dst[c]; }
+    KS_TRY(ks_alloc(ctx, &S->d_score, (size_t)cull->n_kept)); C.out64 = S->d_score;
+    KS_TRY(ks_rcull_take_launch(ctx, cull, C));
+    KS_TRY(ks_stream_wait(ctx));
+    return S.commit();
+    });
+}

@@ -47,7 +47,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH) X(CULL_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -345,13 +345,14 @@ enum : u32 {
     KS_PIN_RSCORE = 232,     // 1 word, region scores: first row whose regions do not lie inside its sequences (ks_rscore.hip)
     KS_PIN_RALIGN = 233,     // 2 words, region alignments: first row whose regions do not lie inside its sequences | first row with a sequence too long (ks_ralign.hip)
     KS_PIN_RTRACE = 235,     // 8 words, region traceback: bad row | sequence too long | alignment outside its region's sequences | walk that does not close, then the scan totals (ks_rtrace.hip)
-    KS_PIN_END = 243,
+    KS_PIN_RCULL = 243,      // 3 words, region cull: first row that breaks the CSR | first region with a length of 0 | kept regions (ks_rcull.hip)
+    KS_PIN_END = 246,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -511,6 +512,24 @@ struct ks_cigars {
 // ks_regions_traceback behind its argument checks (flags validated; R, H, S: of ctx, equal counts)
 int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
                               const ks_raligns *S, u32 flags, u64 max_scratch_bytes, ks_cigars *C);
+
+// the regions of a hit row that no better region of the row covers (ks_rcull.hip)
+struct ks_rcull {
+    ks_ctx *ctx;
+    u64 n_rows, n_regions, n_kept;
+    u64 *d_row_offsets;                  // n_rows + 1: the CSR of the kept regions
+    u32 *d_src_region, *d_rank, *d_n_merged; // n_kept (blocks of n_regions entries)
+    u32 *d_keeper;                       // n_regions
+    double *d_row_best;                  // n_rows
+};
+// the columns of a cull's input on the device; tl == ql for regions of one length
+struct ks_rcull_cols { const u64 *row_offs; const u32 *qs, *ql, *ts, *tl; const i64 *score; };
+// ks_regions_cull_device behind its argument checks (opts: validated, defaults filled in; n_regions == 0 where n_rows == 0)
+int ks_regions_cull_impl(ks_ctx *ctx, const ks_rcull_cols &cols, u64 n_rows, u64 n_regions, const ks_rcull_opts *opts, ks_rcull *K);
+// out[c][i] = in[c][src[i]] for i < n and every listed column (at most KS_TAKE_COLS of 32 bits, one of 64), enqueued
+#define KS_TAKE_COLS 10
+struct ks_take_cols { const u32 *in[KS_TAKE_COLS]; u32 *out[KS_TAKE_COLS]; u32 n32; const i64 *in64; i64 *out64; };
+int ks_rcull_take_launch(ks_ctx *ctx, const ks_rcull *K, const ks_take_cols &cols);
 
 // clusters of a hit list read as a graph: its connected components (ks_cluster.hip) or greedy representative clusters (ks_greedy.hip)
 struct ks_clusters {

@@ -574,6 +574,46 @@ class Context:
             for b in bufs:
                 b.free()
 
+    @staticmethod
+    def _rcull_opts(overlap_pct: int, min_score, max_per_row: int):
+        for name, v, top in (("overlap_pct", overlap_pct, 100), ("max_per_row", max_per_row, 2 ** 32 - 1)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
+        if min_score is not None and (isinstance(min_score, bool) or int(min_score) != min_score or not -2 ** 63 <= int(min_score) < 2 ** 63):
+            raise ValueError(f"min_score = {min_score} is not a 64-bit integer")
+        return _lib.ks_rcull_opts(int(overlap_pct), int(max_per_row), 0 if min_score is None else int(min_score),
+                                  0 if min_score is None else _lib.KS_RCULL_MIN_SCORE, 0)
+
+    def cull_regions_device(self, d_row_offsets: int, d_q_start: int, d_q_length: int, d_t_start: int, d_t_length: Optional[int],
+                            d_score: int, n_rows: int, n_regions: int, overlap_pct: int = 100, min_score=None,
+                            max_per_row: int = 0) -> "RegionCull":
+        """ks_regions_cull_device from device-resident columns (raw pointers: row_offsets u64[n_rows + 1]; q_start, q_length,
+        t_start, t_length u32 and score i64, each [n_regions]; d_t_length None or 0: the target lengths are the query lengths).
+        Per hit row the regions are decided best score first (ties: the smaller index): one that a kept region of the row
+        overlaps by at least overlap_pct percent of its own length on BOTH sequences is removed and names that region as its
+        keeper; min_score (None: off) drops regions that score below it; max_per_row (0: no limit) bounds the kept regions of a
+        row.  include/kmerseek_amd.h has the contract."""
+        opts = self._rcull_opts(overlap_pct, min_score, max_per_row)
+        out = C.c_void_p()
+        ptrs = [C.c_void_p(int(p)) if p else None for p in (d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length, d_score)]
+        self._check(self._L.ks_regions_cull_device(self._h, *ptrs, int(n_rows), int(n_regions), C.byref(opts), C.byref(out)))
+        return RegionCull(self, out)
+
+    def cull_regions(self, scored, overlap_pct: int = 100, min_score=None, max_per_row: int = 0) -> "RegionCull":
+        """The cull of cull_regions_device on a RegionAlignments (ks_raligns_cull: the alignments' extents and scores) or a
+        RegionScores (ks_rscores_cull: the extended regions, one length for both sides).  RegionCull.take then gives the
+        Regions / RegionScores / RegionAlignments of the kept regions alone — what trace_regions should be given."""
+        opts = self._rcull_opts(overlap_pct, min_score, max_per_row)
+        if isinstance(scored, RegionAlignments):
+            fn = self._L.ks_raligns_cull
+        elif isinstance(scored, RegionScores):
+            fn = self._L.ks_rscores_cull
+        else:
+            raise TypeError("cull_regions takes a RegionAlignments or a RegionScores")
+        out = C.c_void_p()
+        self._check(fn(self._h, scored._h, C.byref(opts), C.byref(out)))
+        return RegionCull(self, out)
+
     def significance(self, queries: "Sketches", targets: "Sketches", hits: "Hits", q_corpus: Optional["Corpus"] = None,
                      t_corpus: Optional["Corpus"] = None) -> "Significance":
         """ks_hits_significance: per row of `hits` the two f64 sums behind multisearch's prob_overlap and tf_idf_score, over the
@@ -1068,6 +1108,57 @@ class RegionCigars(_Owned):
     def strings(self) -> List[str]:
         """The CIGAR of every region as text, e.g. "35M2D17M1I40M"."""
         return cigar_strings(*self.to_host())
+
+
+class RegionCull(_Owned):
+    """Device-resident result of Context.cull_regions (ks_rcull): a CSR of the kept regions over the input's hit rows — per
+    kept region its input index (src_region), its rank inside the row (0: the best) and how many input regions it stands for
+    (n_merged) — per input region its keeper (0xffffffff: dropped) and per hit row the score of its best kept region as f64
+    (NaN: the row keeps none), a `score=` column for Context.best_hits."""
+    _free = "ks_rcull_free"
+    _COLUMNS = ("row_offsets", "src_region", "rank", "n_merged", "keeper", "row_best_score")
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_rcull_n_rows(self._h))
+
+    @property
+    def n_regions(self) -> int:
+        """Regions of the input."""
+        return int(self._ctx._L.ks_rcull_n_regions(self._h))
+
+    @property
+    def n_kept(self) -> int:
+        return int(self._ctx._L.ks_rcull_n_kept(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (row_offsets u64[n_rows + 1]; src_region, rank, n_merged u32[n_kept]; keeper u32[n_regions];
+        row_best_score f64[n_rows])."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_rcull_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    @property
+    def row_best_score_ptr(self) -> int:
+        """The device column row_best_score f64[n_rows]: pass it to Context.best_hits(score=...)."""
+        return int(self._ctx._L.ks_rcull_device_row_best_score(self._h) or 0)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """(row_offsets u64[n_rows + 1], src_region, rank, n_merged u32[n_kept], keeper u32[n_regions], row_best_score f64[n_rows])."""
+        k = self.n_kept
+        offs = np.zeros(self.n_rows + 1, np.uint64)
+        cols = [np.zeros(k, np.uint32) for _ in range(3)] + [np.zeros(self.n_regions, np.uint32), np.zeros(self.n_rows, np.float64)]
+        self._ctx._check(self._ctx._L.ks_rcull_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
+        return (offs, *cols)
+
+    def take(self, obj):
+        """The Regions, RegionScores or RegionAlignments of the kept regions only (ks_*_take): every column gathered by
+        src_region, the row offsets of this cull.  `obj` must hold the regions the cull was made of."""
+        for cls, fn in ((Regions, "ks_regions_take"), (RegionScores, "ks_rscores_take"), (RegionAlignments, "ks_raligns_take")):
+            if isinstance(obj, cls):
+                out = C.c_void_p()
+                self._ctx._check(getattr(self._ctx._L, fn)(self._ctx._h, obj._h, self._h, C.byref(out)))
+                return cls(self._ctx, out)
+        raise TypeError("take() gathers a Regions, a RegionScores or a RegionAlignments")
 
 
 class Clusters(_Owned):

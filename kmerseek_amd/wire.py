@@ -712,7 +712,7 @@ def read_score_matrix(path: str) -> np.ndarray:
 
 
 def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, regions_host,
-                moltype: str, scores=None, alignments=None, cigars=None) -> List[dict]:
+                moltype: str, scores=None, alignments=None, cigars=None, cull=None) -> List[dict]:
     """One row per region of the device's chaining (Context.match_regions; regions_host = Regions.to_host()): hit row
     r = (qid[r], tid[r]) owns regions [row_offsets[r], row_offsets[r + 1]).  The stitched columns of search.py:195-240 —
     query / match / encoded are the residues the region spans, sliced from the records (a region lies on one diagonal, so
@@ -731,7 +731,13 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
     and aln_pident (100 * aln_identities / aln_length).  The other columns, and the order of the rows, do not change.
 
     cigars = RegionCigars.to_host() of those alignments (Context.trace_regions; needs alignments): every row also carries
-    aln_cigar, its alignment's path as text with the query as the read ("35M2D17M1I40M"; = and X for M when traced with eqx)."""
+    aln_cigar, its alignment's path as text with the query as the read ("35M2D17M1I40M"; = and X for M when traced with eqx).
+
+    cull = RegionCull.to_host() of those alignments — or, without alignments, of those scores (Context.cull_regions; needs one
+    of them): only the kept regions give rows, and every row carries aln_rank (0: the best alignment of its hit row) and
+    aln_n_merged (the alignments it stands for, itself included) — region_rank and region_n_merged for a cull of scores.  The
+    cigars may then be those of all regions or of the kept ones alone (traced from RegionCull.take's objects).  Everything
+    else is unchanged; cull=None gives the rows of every region."""
     offs, q_start, t_start, length, n_kmers, covered = [np.asarray(c).tolist() for c in regions_host]
     if scores is not None:
         s_offs, s_q, s_t, s_len, s_score, s_ident, s_pos, _ = [np.asarray(c).tolist() for c in scores]
@@ -746,13 +752,26 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
             raise ValueError("cigars need alignments: they are the paths of alignments")
         from .engine import cigar_strings
         cg = cigar_strings(*cigars)
-        if len(cg) != len(q_start):
+        if len(cg) != len(q_start) and (cull is None or len(cg) != len(cull[1])):
             raise ValueError("cigars and regions are not of the same regions")
+    kept_at = None
+    if cull is not None:
+        if scores is None and alignments is None:
+            raise ValueError("a cull needs scores or alignments: it is made of one of them")
+        c_offs, c_src = np.asarray(cull[0]).tolist(), np.asarray(cull[1]).tolist()
+        c_rank, c_nm = np.asarray(cull[2]).tolist(), np.asarray(cull[3]).tolist()
+        if len(c_offs) != len(offs) or len(cull[4]) != len(q_start):
+            raise ValueError("cull and regions are not of the same regions")
+        kept_at = {g: i for i, g in enumerate(c_src)}
+        rank_col, nm_col = ("aln_rank", "aln_n_merged") if alignments is not None else ("region_rank", "region_n_merged")
+        cg_kept = cigars is not None and len(cg) != len(q_start)
     out = []
     for r, (q, t) in enumerate(zip(np.asarray(qid).tolist(), np.asarray(tid).tolist())):
         qn, qseq = q_records[q]
         tn, tseq = t_records[t]
         for g in range(offs[r], offs[r + 1]):
+            if kept_at is not None and g not in kept_at:
+                continue
             a, b, n = (q_start[g], t_start[g], length[g]) if scores is None else (s_q[g], s_t[g], s_len[g])
             query = qseq[a:a + n].decode().upper()
             row = {"match_name": tn, "query_name": qn, "query_start": a, "query_end": a + n, "query": query,
@@ -769,7 +788,10 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
                             "aln_gap_opens": go_, "aln_gaps": ga_,
                             "aln_pident": format_f64(100.0 * float(id_) / float(ln_) if ln_ else math.nan)})
                 if cigars is not None:
-                    row["aln_cigar"] = cg[g]
+                    row["aln_cigar"] = cg[kept_at[g]] if kept_at is not None and cg_kept else cg[g]
+            if kept_at is not None:
+                row[rank_col] = c_rank[kept_at[g]]
+                row[nm_col] = c_nm[kept_at[g]]
             out.append((q, row))
     out.sort(key=lambda e: (e[0], e[1]["query_start"], e[1]["query_end"]))
     return [row for _, row in out]
@@ -779,7 +801,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 ctx: Optional[Context] = None, regions: bool = False, max_gap: int = 0,
                                 min_kmers: int = 1, score: bool = False, extend: bool = False, x_drop: int = 0,
                                 matrix=None, gapped: bool = False, band: int = 16, gap_open: int = 11, gap_extend: int = 1,
-                                gapped_x_drop: int = 30, cigar: bool = False, eqx: bool = False) -> List[dict]:
+                                gapped_x_drop: int = 30, cigar: bool = False, eqx: bool = False, cull: bool = False,
+                                cull_overlap: int = 100, min_aln_score=None, max_alns: int = 0) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -789,7 +812,13 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     gapped=True (needs regions=True): every region is aligned with gaps on the device (Context.align_regions with matrix, band,
     gap_open, gap_extend and gapped_x_drop) and the rows carry the aln_* columns `region_rows` adds for alignments.
     cigar=True (needs gapped=True): the alignments are traced back on the device too (Context.trace_regions, with eqx) and the
-    rows carry aln_cigar."""
+    rows carry aln_cigar.
+    cull=True (needs gapped=True or score=True): redundant regions are culled per hit on the device (Context.cull_regions with
+    cull_overlap, min_aln_score and max_alns) — the alignments with gapped=True, otherwise the scored regions — and only the
+    kept ones give rows, with the rank and n_merged columns `region_rows` adds for a cull.  With cigar=True only the kept
+    alignments are traced."""
+    if cull and not (gapped or score):
+        raise ValueError("cull=True needs gapped=True or score=True: a cull is made of alignments or of scored regions")
     if score and not regions:
         raise ValueError("score=True needs regions=True: scores are of regions")
     if gapped and not regions:
@@ -813,27 +842,38 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
         if regions:
             rg = ctx.match_regions(mp, max_gap=max_gap, min_kmers=min_kmers)
             rg_host = rg.to_host()
-            sc_host = cg_host = None
+            sc_host = cg_host = cu = None
+            kw = {}
             if score:
                 sc = ctx.score_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, extend=extend, x_drop=x_drop)
                 sc_host = sc.to_host()
+                if cull and not gapped:
+                    cu = ctx.cull_regions(sc, overlap_pct=cull_overlap, min_score=min_aln_score, max_per_row=max_alns)
                 sc.free()
             if gapped:
                 al = ctx.align_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, band=band, gap_open=gap_open,
                                        gap_extend=gap_extend, x_drop=gapped_x_drop)
                 al_host = al.to_host()
+                if cull:
+                    cu = ctx.cull_regions(al, overlap_pct=cull_overlap, min_score=min_aln_score, max_per_row=max_alns)
                 if cigar:
-                    cg = ctx.trace_regions(rg, hits, q_res, q_off, t_res, t_off, al, eqx=eqx)
+                    t_rg, t_al = (cu.take(rg), cu.take(al)) if cull else (rg, al)  # (trace what is kept, not everything)
+                    cg = ctx.trace_regions(t_rg, hits, q_res, q_off, t_res, t_off, t_al, eqx=eqx)
                     cg_host = cg.to_host()
                     cg.free()
+                    if cull:
+                        t_rg.free(); t_al.free()
                 al.free()
+            if cu is not None:
+                kw["cull"] = cu.to_host()
+                cu.free()
             for o in (rg, mp, qp, tp, hits, Q, T):
                 o.free()
             if gapped:
                 if cigar:
-                    return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, cigars=cg_host)
-                return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host)
-            return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host)
+                    return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, cigars=cg_host, **kw)
+                return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, **kw)
+            return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, **kw)
         offs, qs, ts = mp.to_host()[:3]
         for o in (mp, qp, tp, hits, Q, T):
             o.free()
