@@ -794,6 +794,115 @@ int ks_raligns_take(ks_ctx *ctx, const ks_raligns *alignments, const ks_rcull *c
  * may be NULL): the tests place rows around them */
 uint32_t ks_debug_rcull_lds_rows(uint32_t *small_rows);
 
+/* ---- region chain: one colinear chain of alignments per hit ------------------------------------------------------------------ */
+
+/* What a seed-and-extend search does after the cull to say how the local alignments of one hit fit together (BLAST's HSP
+ * linking, the chains behind qcovs, MMseqs2 -c, CD-HIT -aS / -aL): per hit row the set of regions that can all be true at once —
+ * ascending on BOTH sequences — with the largest sum of scores minus link costs.  Two alignments on either side of a long
+ * insertion chain; two domains in swapped order do not.  Like the cull it reads extents and scores only, no residues, and
+ * serves a ks_raligns and a ks_rscores alike.  The intended input is what the cull kept (ks_raligns_take), any other is taken.
+ * Input: a CSR over hit rows and five columns per region, as for ks_regions_cull_device:
+ *   row_offsets u64[n_rows + 1];  q_start, q_length, t_start, t_length u32[n];  score i64[n]
+ *   d_t_length == NULL: the target lengths are the query lengths.  d_identities, d_aln_length u32[n]: either may be NULL;
+ *   they are only summed over the chain.
+ * Options (opts == NULL: all zero): max_gap (0: no limit), max_overlap, link_cost <= 2^30, skew_cost and overlap_cost <= 2^16;
+ * flags and reserved must be 0.
+ * All arithmetic is in signed 64 bits; an end is start + length.  follows(a, b) holds iff
+ *   q_start[a] < q_start[b], t_start[a] < t_start[b], q_end[a] < q_end[b], t_end[a] < t_end[b]  and, with
+ *   dq = q_start[b] - q_end[a], dt = t_start[b] - t_end[a], ov = max(0, -dq, -dt):
+ *   ov <= max_overlap  and  (max_gap == 0 or max(dq, dt, 0) <= max_gap).
+ * cost(a, b) = link_cost + skew_cost * |dq - dt| + overlap_cost * ov.
+ * Per hit row:
+ *   best[i] = score[i] + max(0, max over j with follows(j, i) of best[j] - cost(j, i))
+ *   a link is taken only when best[j] - cost(j, i) > 0; among equal maxima pred[i] is the smallest input index j;
+ *   pred[i] = KS_RCHAIN_NONE: the chain starts at i.
+ *   The row's chain ends at the region of the largest best (ties: the smaller input index) and is walked back along pred.
+ * follows needs a strictly smaller q_start: any order by q_start is a valid evaluation order, and equal starts never link.
+ * Result (device-resident):
+ *   row_offsets u64[n_rows + 1], src_region u32[n_chained]   the members of each row's chain in chain order (ascending
+ *                                                            q_start); a row without regions has none
+ *   best i64[n], pred u32[n]                                 per input region
+ *   per hit row:
+ *   chain_score i64          the best of the end region, 0 for a row without regions
+ *   q_start, q_length, t_start, t_length u32   the span from the first member's start to the last member's end, zeros for an
+ *                            empty row
+ *   q_aligned, t_aligned u32 the length of the union of the members' intervals: starts and ends both ascend strictly along a
+ *                            chain, so it is the first member's length plus, over successive members a, b,
+ *                            end[b] - max(start[b], end[a])
+ *   identities, aln_length u64   the sums of the optional columns over the members, 0 where the column was not passed
+ *   row_chain_score f64      (double)chain_score, NaN for an empty row: exactly a d_score column for ks_hits_best with
+ *                            KS_BEST_SCORE and for the cluster passes
+ * Every member but the first has its predecessor as pred; chain_score is the sum of the members' scores minus the sum of the
+ * link costs.  The result does not depend on the path a row took (KS_DEBUG_CHAIN_PATH = 1 / 2 / 3 force every row of at most 64
+ * regions onto a wave / every row onto a workgroup / that with a small LDS capacity, for the tests) or on the launch geometry.
+ * An input without rows or regions gives a valid empty result.
+ * KS_ERR_INVALID_ARG: an option out of range, unknown flags or a non-zero reserved field (checked before any device work, also
+ * with ctx == NULL); NULL arguments; an object of another context; row_offsets that is not a non-decreasing CSR from 0 to n
+ * (ks_last_error names the first bad row); a region with a length of 0, with an end beyond 0xffffffff or with |score| > 2^30 —
+ * with that bound and the cost bounds no sum can leave 64 bits — (the plan kernel names the first such region).
+ * KS_ERR_CAPACITY: 2^32 - 2 or more rows, more than 2^32 - 1 regions.
+ * One stream, synchronous on return, one host wait (the chained count and the bad words come back with it); all memory comes
+ * from the context's pool: 24 bytes of scratch per region and 24 per hit row. */
+typedef struct ks_rchain ks_rchain;
+#define KS_RCHAIN_NONE 0xffffffffu
+typedef struct ks_rchain_opts {
+    uint32_t max_gap;      /* the longest gap between two members on either sequence; 0 = no limit */
+    uint32_t max_overlap;  /* the longest overlap of two members on either sequence */
+    uint32_t link_cost;    /* per link, <= 2^30 */
+    uint32_t skew_cost;    /* per position of |dq - dt|, <= 2^16 */
+    uint32_t overlap_cost; /* per overlapping position, <= 2^16 */
+    uint32_t flags;        /* 0 */
+    uint32_t reserved[2];  /* 0 */
+} ks_rchain_opts;
+int ks_regions_chain_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint32_t *d_q_start, const uint32_t *d_q_length,
+                            const uint32_t *d_t_start, const uint32_t *d_t_length, const int64_t *d_score,
+                            const uint32_t *d_identities, const uint32_t *d_aln_length, uint64_t n_rows, uint64_t n_regions,
+                            const ks_rchain_opts *opts, ks_rchain **out);
+/* the same on the columns of an object: the alignments' extents, score, identities and aln_length; the extended regions'
+ * placement, `length` for both sides and as aln_length, score and identities */
+int ks_raligns_chain(ks_ctx *ctx, const ks_raligns *alignments, const ks_rchain_opts *opts, ks_rchain **out);
+int ks_rscores_chain(ks_ctx *ctx, const ks_rscores *scores, const ks_rchain_opts *opts, ks_rchain **out);
+uint64_t ks_rchain_n_rows(const ks_rchain *c);
+uint64_t ks_rchain_n_regions(const ks_rchain *c); /* of the input */
+uint64_t ks_rchain_n_chained(const ks_rchain *c);
+/* device pointers, valid until ks_rchain_free */
+const uint64_t *ks_rchain_device_row_offsets(const ks_rchain *c);
+const uint32_t *ks_rchain_device_src_region(const ks_rchain *c);
+const int64_t *ks_rchain_device_best(const ks_rchain *c);
+const uint32_t *ks_rchain_device_pred(const ks_rchain *c);
+const int64_t *ks_rchain_device_chain_score(const ks_rchain *c);
+const uint32_t *ks_rchain_device_q_start(const ks_rchain *c);
+const uint32_t *ks_rchain_device_q_length(const ks_rchain *c);
+const uint32_t *ks_rchain_device_t_start(const ks_rchain *c);
+const uint32_t *ks_rchain_device_t_length(const ks_rchain *c);
+const uint32_t *ks_rchain_device_q_aligned(const ks_rchain *c);
+const uint32_t *ks_rchain_device_t_aligned(const ks_rchain *c);
+const uint64_t *ks_rchain_device_identities(const ks_rchain *c);
+const uint64_t *ks_rchain_device_aln_length(const ks_rchain *c);
+const double *ks_rchain_device_row_chain_score(const ks_rchain *c);
+const double *ks_rchain_device_row_coverage(const ks_rchain *c); /* NULL before ks_rchain_coverage */
+/* any destination may be NULL */
+int ks_rchain_copy_to_host(ks_ctx *ctx, const ks_rchain *c, uint64_t *row_offsets, uint32_t *src_region, int64_t *best,
+                           uint32_t *pred, int64_t *chain_score, uint32_t *q_start, uint32_t *q_length, uint32_t *t_start,
+                           uint32_t *t_length, uint32_t *q_aligned, uint32_t *t_aligned, uint64_t *identities,
+                           uint64_t *aln_length, double *row_chain_score);
+void ks_rchain_free(ks_rchain *c);
+/* Fills the chain's column row_coverage f64[n_rows], owned by the chain (a later call overwrites it): how much of its two
+ * sequences the chain of each hit row covers.  hits: the hit list the chained regions belong to (its qid / tid name the
+ * sequences); d_q_off u64[n_q + 1], d_t_off u64[n_t + 1]: the sequence offsets ks_regions_align takes.  mode: 0 q_aligned /
+ * len(query), 1 t_aligned / len(target), 2 the smaller of the two, 3 the larger — one IEEE f64 division of two integers per
+ * side.  NaN for a row without a chain or a sequence of length 0.
+ * KS_ERR_INVALID_ARG: NULL arguments, an object of another context, mode > 3, hits of another row count, an id beyond n_q / n_t,
+ * an aligned length beyond its sequence's (ks_last_error names the first such row); a refused call leaves no column.
+ * Synchronous on return, one host wait. */
+int ks_rchain_coverage(ks_ctx *ctx, ks_rchain *chain, const ks_hits *hits, const uint64_t *d_q_off, uint32_t n_q,
+                       const uint64_t *d_t_off, uint32_t n_t, uint32_t mode);
+/* copies row_coverage to the host; KS_ERR_INVALID_ARG before the first ks_rchain_coverage */
+int ks_rchain_coverage_to_host(ks_ctx *ctx, const ks_rchain *c, double *row_coverage);
+/* regions of a row the workgroup path holds in LDS (returned) and that capacity under KS_DEBUG_CHAIN_PATH = 3 (*small_rows,
+ * may be NULL): the tests place rows around them */
+uint32_t ks_debug_rchain_lds_rows(uint32_t *small_rows);
+
 /* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
 
 /* Replaces the two sums behind the columns that branchwater multisearch adds with "calculate probability of overlap between

@@ -6,7 +6,7 @@ built library and a GPU.
 """
 from ._lib import KmerseekLibraryError, SO_PATH  # noqa: F401
 from .engine import (Context, Corpus, Hits, Index, InvalidAminoAcid, KmerPositions, KmerseekError, MatchPositions, Regions,  # noqa: F401
-                     RegionAlignments, RegionCigars, RegionCull, RegionScores, Significance, Sketches, SEED, make_params, max_hash, moltype_id, pack, validate_and_resolve)
+                     RegionAlignments, RegionChain, RegionCigars, RegionCull, RegionScores, Significance, Sketches, SEED, make_params, max_hash, moltype_id, pack, validate_and_resolve)
 
-__all__ = ["Context", "Sketches", "Index", "Hits", "KmerPositions", "MatchPositions", "Regions", "RegionScores", "RegionAlignments", "RegionCigars", "RegionCull", "Corpus", "Significance", "KmerseekError", "InvalidAminoAcid", "KmerseekLibraryError",
+__all__ = ["Context", "Sketches", "Index", "Hits", "KmerPositions", "MatchPositions", "Regions", "RegionScores", "RegionAlignments", "RegionCigars", "RegionCull", "RegionChain", "Corpus", "Significance", "KmerseekError", "InvalidAminoAcid", "KmerseekLibraryError",
            "SEED", "make_params", "max_hash", "moltype_id", "pack", "validate_and_resolve", "SO_PATH"]

@@ -86,6 +86,14 @@ class ks_rcull_opts(C.Structure):
                 ("reserved", C.c_uint32)]
 
 
+KS_RCHAIN_NONE = 0xFFFFFFFF
+
+
+class ks_rchain_opts(C.Structure):
+    _fields_ = [("max_gap", C.c_uint32), ("max_overlap", C.c_uint32), ("link_cost", C.c_uint32), ("skew_cost", C.c_uint32),
+                ("overlap_cost", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
 class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -296,6 +304,32 @@ SIGNATURES = {
     "ks_rscores_take": (C.c_int, [_vp, _vp, _vp, _pp]),
     "ks_raligns_take": (C.c_int, [_vp, _vp, _vp, _pp]),
     "ks_debug_rcull_lds_rows": (C.c_uint32, [_u32p]),
+    "ks_regions_chain_device": (C.c_int, [_vp] * 9 + [C.c_uint64, C.c_uint64, C.POINTER(ks_rchain_opts), _pp]),
+    "ks_raligns_chain": (C.c_int, [_vp, _vp, C.POINTER(ks_rchain_opts), _pp]),
+    "ks_rscores_chain": (C.c_int, [_vp, _vp, C.POINTER(ks_rchain_opts), _pp]),
+    "ks_rchain_n_rows": (C.c_uint64, [_vp]),
+    "ks_rchain_n_regions": (C.c_uint64, [_vp]),
+    "ks_rchain_n_chained": (C.c_uint64, [_vp]),
+    "ks_rchain_device_row_offsets": (_vp, [_vp]),
+    "ks_rchain_device_src_region": (_vp, [_vp]),
+    "ks_rchain_device_best": (_vp, [_vp]),
+    "ks_rchain_device_pred": (_vp, [_vp]),
+    "ks_rchain_device_chain_score": (_vp, [_vp]),
+    "ks_rchain_device_q_start": (_vp, [_vp]),
+    "ks_rchain_device_q_length": (_vp, [_vp]),
+    "ks_rchain_device_t_start": (_vp, [_vp]),
+    "ks_rchain_device_t_length": (_vp, [_vp]),
+    "ks_rchain_device_q_aligned": (_vp, [_vp]),
+    "ks_rchain_device_t_aligned": (_vp, [_vp]),
+    "ks_rchain_device_identities": (_vp, [_vp]),
+    "ks_rchain_device_aln_length": (_vp, [_vp]),
+    "ks_rchain_device_row_chain_score": (_vp, [_vp]),
+    "ks_rchain_device_row_coverage": (_vp, [_vp]),
+    "ks_rchain_copy_to_host": (C.c_int, [_vp] * 16),
+    "ks_rchain_free": (None, [_vp]),
+    "ks_rchain_coverage": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32]),
+    "ks_rchain_coverage_to_host": (C.c_int, [_vp, _vp, _vp]),
+    "ks_debug_rchain_lds_rows": (C.c_uint32, [_u32p]),
     "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
     "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
     "ks_corpus_n_docs": (C.c_uint32, [_vp]),

@@ -895,3 +895,126 @@ extern "C" int ks_raligns_take(ks_ctx *ctx, const ks_raligns *s, const ks_rcull 
     return S.commit();
     });
 }
+
+// ---------------------------------------------------------------------------------------------
+// region chain (ks_rchain.hip): per hit row the best colinear chain of its regions, and how much of the sequences it covers
+// ---------------------------------------------------------------------------------------------
+// the options, defaults filled in; refused before any device work, also with ctx == NULL
+static int ks_rchain_opts_check(ks_ctx *ctx, const ks_rchain_opts *opts, ks_rchain_opts *o) {
+    const ks_rchain_opts dflt = {0u, 0u, 0u, 0u, 0u, 0u, {0u, 0u}};
+    *o = opts ? *opts : dflt;
+    KS_TRY(ks_opts_words_check(ctx, "region chain", o->flags, 0, o->reserved[0] | o->reserved[1]));
+    if (o->link_cost <= (1u << 30) && o->skew_cost <= (1u << 16) && o->overlap_cost <= (1u << 16)) return KS_OK;
+    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "region chain options: link_cost %u (<= 2^30), skew_cost %u, overlap_cost %u (<= 2^16)", o->link_cost,
+                         o->skew_cost, o->overlap_cost)
+               : KS_ERR_INVALID_ARG;
+}
+static int ks_rchain_run(ks_ctx *ctx, const ks_rchain_cols &cols, u64 n_rows, u64 n_regions, const ks_rchain_opts &o, ks_rchain **out) {
+    if (!out || !cols.row_offs || (n_regions && (!cols.qs || !cols.ql || !cols.ts || !cols.tl || !cols.score)))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    if (n_rows == 0 && n_regions != 0)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "region chain: %llu regions in no hit row: row_offsets is not a CSR from 0 to n", (unsigned long long)n_regions);
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_rchain> K(ctx, out, ks_rchain_free);
+    KS_TRY(ks_regions_chain_impl(ctx, cols, n_rows, n_regions, &o, K));
+    return K.commit();
+}
+extern "C" int ks_regions_chain_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint32_t *d_q_start, const uint32_t *d_q_length,
+                                       const uint32_t *d_t_start, const uint32_t *d_t_length, const int64_t *d_score, const uint32_t *d_identities,
+                                       const uint32_t *d_aln_length, uint64_t n_rows, uint64_t n_regions, const ks_rchain_opts *opts, ks_rchain **out) {
+    return ks_guard(ctx, [&]() -> int {
+    ks_rchain_opts o;
+    KS_TRY(ks_rchain_opts_check(ctx, opts, &o));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    return ks_rchain_run(ctx, {d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length ? d_t_length : d_q_length, d_score, d_identities, d_aln_length},
+                         n_rows, n_regions, o, out);
+    });
+}
+extern "C" int ks_raligns_chain(ks_ctx *ctx, const ks_raligns *s, const ks_rchain_opts *opts, ks_rchain **out) {
+    return ks_guard(ctx, [&]() -> int {
+    ks_rchain_opts o;
+    KS_TRY(ks_rchain_opts_check(ctx, opts, &o));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    if (!s) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "region chain", s));
+    return ks_rchain_run(ctx, {s->d_row_offsets, s->d_qstart, s->d_qlength, s->d_tstart, s->d_tlength, s->d_score, s->d_identities, s->d_aln_length},
+                         s->n_rows, s->n_regions, o, out);
+    });
+}
+extern "C" int ks_rscores_chain(ks_ctx *ctx, const ks_rscores *s, const ks_rchain_opts *opts, ks_rchain **out) {
+    return ks_guard(ctx, [&]() -> int {
+    ks_rchain_opts o;
+    KS_TRY(ks_rchain_opts_check(ctx, opts, &o));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    if (!s) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "region chain", s));
+    return ks_rchain_run(ctx, {s->d_row_offsets, s->d_qstart, s->d_length, s->d_tstart, s->d_length, s->d_score, s->d_identities, s->d_length},
+                         s->n_rows, s->n_regions, o, out);
+    });
+}
+extern "C" uint64_t ks_rchain_n_rows(const ks_rchain *c) { return c ? c->n_rows : 0; }
+extern "C" uint64_t ks_rchain_n_regions(const ks_rchain *c) { return c ? c->n_regions : 0; }
+extern "C" uint64_t ks_rchain_n_chained(const ks_rchain *c) { return c ? c->n_chained : 0; }
+extern "C" const uint64_t *ks_rchain_device_row_offsets(const ks_rchain *c) { return c ? c->d_row_offsets : nullptr; }
+extern "C" const uint32_t *ks_rchain_device_src_region(const ks_rchain *c) { return c ? c->d_src_region : nullptr; }
+extern "C" const int64_t *ks_rchain_device_best(const ks_rchain *c) { return c ? c->d_best : nullptr; }
+extern "C" const uint32_t *ks_rchain_device_pred(const ks_rchain *c) { return c ? c->d_pred : nullptr; }
+extern "C" const int64_t *ks_rchain_device_chain_score(const ks_rchain *c) { return c ? c->d_chain_score : nullptr; }
+extern "C" const uint32_t *ks_rchain_device_q_start(const ks_rchain *c) { return c ? c->d_q_start : nullptr; }
+extern "C" const uint32_t *ks_rchain_device_q_length(const ks_rchain *c) { return c ? c->d_q_length : nullptr; }
+extern "C" const uint32_t *ks_rchain_device_t_start(const ks_rchain *c) { return c ? c->d_t_start : nullptr; }
+extern "C" const uint32_t *ks_rchain_device_t_length(const ks_rchain *c) { return c ? c->d_t_length : nullptr; }
+extern "C" const uint32_t *ks_rchain_device_q_aligned(const ks_rchain *c) { return c ? c->d_q_aligned : nullptr; }
+extern "C" const uint32_t *ks_rchain_device_t_aligned(const ks_rchain *c) { return c ? c->d_t_aligned : nullptr; }
+extern "C" const uint64_t *ks_rchain_device_identities(const ks_rchain *c) { return c ? c->d_identities : nullptr; }
+extern "C" const uint64_t *ks_rchain_device_aln_length(const ks_rchain *c) { return c ? c->d_aln_length : nullptr; }
+extern "C" const double *ks_rchain_device_row_chain_score(const ks_rchain *c) { return c ? c->d_row_score : nullptr; }
+extern "C" const double *ks_rchain_device_row_coverage(const ks_rchain *c) { return c ? c->d_row_cov : nullptr; }
+
+extern "C" int ks_rchain_copy_to_host(ks_ctx *ctx, const ks_rchain *c, uint64_t *row_offsets, uint32_t *src_region, int64_t *best, uint32_t *pred,
+                                      int64_t *chain_score, uint32_t *q_start, uint32_t *q_length, uint32_t *t_start, uint32_t *t_length,
+                                      uint32_t *q_aligned, uint32_t *t_aligned, uint64_t *identities, uint64_t *aln_length, double *row_chain_score) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !c) return KS_ERR_INVALID_ARG;
+    const size_t nr = (size_t)c->n_rows, n = (size_t)c->n_regions, r4 = nr * sizeof(u32), r8 = nr * sizeof(u64);
+    return ks_columns_to_host(ctx, {{row_offsets, c->d_row_offsets, (nr + 1) * sizeof(u64)}, {src_region, c->d_src_region, (size_t)c->n_chained * sizeof(u32)},
+                                    {best, c->d_best, n * sizeof(i64)}, {pred, c->d_pred, n * sizeof(u32)}, {chain_score, c->d_chain_score, r8},
+                                    {q_start, c->d_q_start, r4}, {q_length, c->d_q_length, r4}, {t_start, c->d_t_start, r4}, {t_length, c->d_t_length, r4},
+                                    {q_aligned, c->d_q_aligned, r4}, {t_aligned, c->d_t_aligned, r4}, {identities, c->d_identities, r8},
+                                    {aln_length, c->d_aln_length, r8}, {row_chain_score, c->d_row_score, r8}});
+    });
+}
+
+extern "C" void ks_rchain_free(ks_rchain *c) {
+    if (!c) return;
+    for (void *p : {(void *)c->d_row_offsets, (void *)c->d_src_region, (void *)c->d_best, (void *)c->d_pred, (void *)c->d_chain_score, (void *)c->d_q_start,
+                    (void *)c->d_q_length, (void *)c->d_t_start, (void *)c->d_t_length, (void *)c->d_q_aligned, (void *)c->d_t_aligned, (void *)c->d_identities,
+                    (void *)c->d_aln_length, (void *)c->d_row_score, (void *)c->d_row_cov})
+        ks_pool_free(c->ctx, p);
+    delete c;
+}
+
+extern "C" int ks_rchain_coverage(ks_ctx *ctx, ks_rchain *chain, const ks_hits *hits, const uint64_t *d_q_off, uint32_t n_q, const uint64_t *d_t_off,
+                                  uint32_t n_t, uint32_t mode) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!chain || !hits || !d_q_off || !d_t_off) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "chain coverage", chain, hits));
+    if (mode > 3u) return ks_fail(ctx, KS_ERR_INVALID_ARG, "chain coverage: mode %u (0 query, 1 target, 2 the smaller, 3 the larger)", mode);
+    if (hits->n_hits != chain->n_rows)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "chain coverage: the hit list has %llu rows, the chain was made of %llu: hits of other regions",
+                       (unsigned long long)hits->n_hits, (unsigned long long)chain->n_rows);
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    return ks_rchain_coverage_impl(ctx, chain, hits, d_q_off, n_q, d_t_off, n_t, mode);
+    });
+}
+extern "C" int ks_rchain_coverage_to_host(ks_ctx *ctx, const ks_rchain *c, double *row_coverage) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !c) return KS_ERR_INVALID_ARG;
+    if (!c->d_row_cov) return ks_fail(ctx, KS_ERR_INVALID_ARG, "chain coverage: ks_rchain_coverage has not filled the column");
+    return ks_columns_to_host(ctx, {{row_coverage, c->d_row_cov, (size_t)c->n_rows * sizeof(double)}});
+    });
+}

@@ -47,7 +47,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH) X(CULL_PATH)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH) X(CULL_PATH) X(CHAIN_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -346,13 +346,15 @@ enum : u32 {
     KS_PIN_RALIGN = 233,     // 2 words, region alignments: first row whose regions do not lie inside its sequences | first row with a sequence too long (ks_ralign.hip)
     KS_PIN_RTRACE = 235,     // 8 words, region traceback: bad row | sequence too long | alignment outside its region's sequences | walk that does not close, then the scan totals (ks_rtrace.hip)
     KS_PIN_RCULL = 243,      // 3 words, region cull: first row that breaks the CSR | first region with a length of 0 | kept regions (ks_rcull.hip)
-    KS_PIN_END = 246,
+    KS_PIN_RCHAIN = 246,     // 5 words, region chain: first row that breaks the CSR | first region with a length of 0 | with an end beyond 0xffffffff | with a score beyond 2^30 | chained regions (ks_rchain.hip)
+    KS_PIN_RCHAIN_COV = 251, // 2 words, chain coverage: first row with an id beyond the batches | first row whose chain is longer than its sequence (ks_rchain.hip)
+    KS_PIN_END = 253,
 };
 #define KS_PIN_WORDS 256
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -530,6 +532,27 @@ int ks_regions_cull_impl(ks_ctx *ctx, const ks_rcull_cols &cols, u64 n_rows, u64
 #define KS_TAKE_COLS 10
 struct ks_take_cols { const u32 *in[KS_TAKE_COLS]; u32 *out[KS_TAKE_COLS]; u32 n32; const i64 *in64; i64 *out64; };
 int ks_rcull_take_launch(ks_ctx *ctx, const ks_rcull *K, const ks_take_cols &cols);
+
+// the best colinear chain of the regions of each hit row (ks_rchain.hip)
+struct ks_rchain {
+    ks_ctx *ctx;
+    u64 n_rows, n_regions, n_chained;
+    u64 *d_row_offsets;                  // n_rows + 1: the CSR of the chains' members
+    u32 *d_src_region;                   // n_chained (a block of n_regions entries)
+    i64 *d_best;                         // n_regions
+    u32 *d_pred;                         // n_regions
+    i64 *d_chain_score;                  // n_rows, as every column below
+    u32 *d_q_start, *d_q_length, *d_t_start, *d_t_length, *d_q_aligned, *d_t_aligned;
+    u64 *d_identities, *d_aln_length;
+    double *d_row_score;
+    double *d_row_cov;                   // NULL until ks_rchain_coverage has run
+};
+// the columns of a chain's input on the device; tl == ql for regions of one length; ident, alen: NULL or a column to sum
+struct ks_rchain_cols { const u64 *row_offs; const u32 *qs, *ql, *ts, *tl; const i64 *score; const u32 *ident, *alen; };
+// ks_regions_chain_device behind its argument checks (opts: validated, not NULL; n_regions == 0 where n_rows == 0)
+int ks_regions_chain_impl(ks_ctx *ctx, const ks_rchain_cols &cols, u64 n_rows, u64 n_regions, const ks_rchain_opts *opts, ks_rchain *K);
+// ks_rchain_coverage behind its argument checks (H: of ctx, K's row count; mode <= 3)
+int ks_rchain_coverage_impl(ks_ctx *ctx, ks_rchain *K, const ks_hits *H, const u64 *d_q_off, u32 n_q, const u64 *d_t_off, u32 n_t, u32 mode);
 
 // clusters of a hit list read as a graph: its connected components (ks_cluster.hip) or greedy representative clusters (ks_greedy.hip)
 struct ks_clusters {

@@ -614,6 +614,48 @@ class Context:
         self._check(fn(self._h, scored._h, C.byref(opts), C.byref(out)))
         return RegionCull(self, out)
 
+    @staticmethod
+    def _rchain_opts(max_gap: int, max_overlap: int, link_cost: int, skew_cost: int, overlap_cost: int):
+        for name, v, top in (("max_gap", max_gap, 2 ** 32 - 1), ("max_overlap", max_overlap, 2 ** 32 - 1), ("link_cost", link_cost, 2 ** 30),
+                             ("skew_cost", skew_cost, 2 ** 16), ("overlap_cost", overlap_cost, 2 ** 16)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
+        return _lib.ks_rchain_opts(int(max_gap), int(max_overlap), int(link_cost), int(skew_cost), int(overlap_cost), 0, (C.c_uint32 * 2)(0, 0))
+
+    def chain_regions_device(self, d_row_offsets: int, d_q_start: int, d_q_length: int, d_t_start: int, d_t_length: Optional[int],
+                             d_score: int, n_rows: int, n_regions: int, d_identities: Optional[int] = None,
+                             d_aln_length: Optional[int] = None, max_gap: int = 0, max_overlap: int = 0, link_cost: int = 0,
+                             skew_cost: int = 0, overlap_cost: int = 0) -> "RegionChain":
+        """ks_regions_chain_device from device-resident columns (raw pointers: row_offsets u64[n_rows + 1]; q_start, q_length,
+        t_start, t_length u32 and score i64, each [n_regions]; d_t_length None or 0: the target lengths are the query lengths;
+        d_identities, d_aln_length: optional u32 columns that are summed over each chain).  Per hit row the best colinear chain:
+        region b follows region a iff its starts and its ends lie strictly behind a's on both sequences, the two overlap by at
+        most max_overlap positions on either and lie at most max_gap apart (0: no limit); a link costs link_cost + skew_cost *
+        |dq - dt| + overlap_cost * overlap; a chain is worth its scores minus its links.  include/kmerseek_amd.h has the
+        contract."""
+        opts = self._rchain_opts(max_gap, max_overlap, link_cost, skew_cost, overlap_cost)
+        out = C.c_void_p()
+        ptrs = [C.c_void_p(int(p)) if p else None for p in (d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length, d_score,
+                                                            d_identities, d_aln_length)]
+        self._check(self._L.ks_regions_chain_device(self._h, *ptrs, int(n_rows), int(n_regions), C.byref(opts), C.byref(out)))
+        return RegionChain(self, out)
+
+    def chain_regions(self, scored, max_gap: int = 0, max_overlap: int = 0, link_cost: int = 0, skew_cost: int = 0,
+                      overlap_cost: int = 0) -> "RegionChain":
+        """The chain of chain_regions_device on a RegionAlignments (ks_raligns_chain: the alignments' extents and scores; their
+        identities and aln_length are summed) or a RegionScores (ks_rscores_chain: one length for both sides and as
+        aln_length).  The intended input is what a cull kept: chain_regions(cull.take(alignments))."""
+        opts = self._rchain_opts(max_gap, max_overlap, link_cost, skew_cost, overlap_cost)
+        if isinstance(scored, RegionAlignments):
+            fn = self._L.ks_raligns_chain
+        elif isinstance(scored, RegionScores):
+            fn = self._L.ks_rscores_chain
+        else:
+            raise TypeError("chain_regions takes a RegionAlignments or a RegionScores")
+        out = C.c_void_p()
+        self._check(fn(self._h, scored._h, C.byref(opts), C.byref(out)))
+        return RegionChain(self, out)
+
     def significance(self, queries: "Sketches", targets: "Sketches", hits: "Hits", q_corpus: Optional["Corpus"] = None,
                      t_corpus: Optional["Corpus"] = None) -> "Significance":
         """ks_hits_significance: per row of `hits` the two f64 sums behind multisearch's prob_overlap and tf_idf_score, over the
@@ -1159,6 +1201,89 @@ class RegionCull(_Owned):
                 self._ctx._check(getattr(self._ctx._L, fn)(self._ctx._h, obj._h, self._h, C.byref(out)))
                 return cls(self._ctx, out)
         raise TypeError("take() gathers a Regions, a RegionScores or a RegionAlignments")
+
+
+class RegionChain(_Owned):
+    """Device-resident result of Context.chain_regions (ks_rchain): a CSR of the members of each hit row's best colinear chain
+    in chain order (src_region), per input region its best chain value and its predecessor (0xffffffff: none), and per hit row
+    the chain's score, its span and its aligned lengths on both sequences, the sums of identities and aln_length over its
+    members and the score as f64 (NaN: a row without regions), a `score=` column for Context.best_hits and the cluster passes.
+    coverage() adds row_coverage, the share of the sequences the chain covers."""
+    _free = "ks_rchain_free"
+    _COLUMNS = ("row_offsets", "src_region", "best", "pred", "chain_score", "q_start", "q_length", "t_start", "t_length", "q_aligned",
+                "t_aligned", "identities", "aln_length", "row_chain_score")
+    _MODES = {"query": 0, "target": 1, "min": 2, "max": 3}
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_rchain_n_rows(self._h))
+
+    @property
+    def n_regions(self) -> int:
+        """Regions of the input."""
+        return int(self._ctx._L.ks_rchain_n_regions(self._h))
+
+    @property
+    def n_chained(self) -> int:
+        return int(self._ctx._L.ks_rchain_n_chained(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (row_offsets u64[n_rows + 1]; src_region u32[n_chained]; best i64, pred u32 [n_regions]; and
+        [n_rows] each: chain_score i64; q_start, q_length, t_start, t_length, q_aligned, t_aligned u32; identities, aln_length
+        u64; row_chain_score f64)."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_rchain_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    @property
+    def row_chain_score_ptr(self) -> int:
+        """The device column row_chain_score f64[n_rows]: pass it to Context.best_hits(score=...) or a cluster pass."""
+        return int(self._ctx._L.ks_rchain_device_row_chain_score(self._h) or 0)
+
+    @property
+    def row_coverage_ptr(self) -> int:
+        """The device column row_coverage f64[n_rows]; 0 before coverage()."""
+        return int(self._ctx._L.ks_rchain_device_row_coverage(self._h) or 0)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """The columns of device_ptrs() as numpy arrays, in that order."""
+        n, r = self.n_regions, self.n_rows
+        u32 = lambda k: np.zeros(k, np.uint32)
+        cols = [np.zeros(r + 1, np.uint64), u32(self.n_chained), np.zeros(n, np.int64), u32(n), np.zeros(r, np.int64)] + \
+               [u32(r) for _ in range(6)] + [np.zeros(r, np.uint64), np.zeros(r, np.uint64), np.zeros(r, np.float64)]
+        self._ctx._check(self._ctx._L.ks_rchain_copy_to_host(self._ctx._h, self._h, *[_ptr(c) for c in cols]))
+        return tuple(cols)
+
+    def coverage(self, hits: "Hits", d_q_off: int, n_q: int, d_t_off: int, n_t: int, mode="min") -> int:
+        """ks_rchain_coverage: fills the chain's device column row_coverage f64[n_rows] — per hit row q_aligned / len(query)
+        (mode "query" or 0), t_aligned / len(target) ("target", 1), the smaller ("min", 2) or the larger ("max", 3) of the two;
+        NaN for a row without a chain or a sequence of length 0 — and returns its device pointer, a `score=` column for
+        Context.cluster / cluster_greedy.  d_q_off, d_t_off: device pointers of the u64 sequence offsets align_regions_device
+        takes; hits: the hit list of the chained regions."""
+        m = self._MODES.get(mode, mode)
+        if isinstance(m, bool) or not isinstance(m, int) or not 0 <= m <= 3:
+            raise ValueError(f"mode = {mode!r} is not one of 'query', 'target', 'min', 'max' or 0 .. 3")
+        self._ctx._check(self._ctx._L.ks_rchain_coverage(self._ctx._h, self._h, hits._h, C.c_void_p(int(d_q_off)), int(n_q),
+                                                         C.c_void_p(int(d_t_off)), int(n_t), m))
+        return self.row_coverage_ptr
+
+    def coverage_from_host(self, hits: "Hits", q_off: np.ndarray, t_off: np.ndarray, mode="min") -> int:
+        """coverage from host arrays of sequence offsets u64[n + 1] (those of the batches `hits` was searched on): uploaded
+        for the call, as align_regions does."""
+        q_off = np.ascontiguousarray(q_off, dtype=np.uint64); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        bufs = []
+        try:
+            for a in (q_off, t_off):
+                bufs.append(self._ctx.to_device(a))
+            return self.coverage(hits, bufs[0].ptr, len(q_off) - 1, bufs[1].ptr, len(t_off) - 1, mode=mode)
+        finally:
+            for b in bufs:
+                b.free()
+
+    def coverage_to_host(self) -> np.ndarray:
+        """row_coverage f64[n_rows] of the last coverage call."""
+        out = np.zeros(self.n_rows, np.float64)
+        self._ctx._check(self._ctx._L.ks_rchain_coverage_to_host(self._ctx._h, self._h, _ptr(out)))
+        return out
 
 
 class Clusters(_Owned):

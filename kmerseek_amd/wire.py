@@ -712,7 +712,7 @@ def read_score_matrix(path: str) -> np.ndarray:
 
 
 def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, regions_host,
-                moltype: str, scores=None, alignments=None, cigars=None, cull=None) -> List[dict]:
+                moltype: str, scores=None, alignments=None, cigars=None, cull=None, chain=None) -> List[dict]:
     """One row per region of the device's chaining (Context.match_regions; regions_host = Regions.to_host()): hit row
     r = (qid[r], tid[r]) owns regions [row_offsets[r], row_offsets[r + 1]).  The stitched columns of search.py:195-240 —
     query / match / encoded are the residues the region spans, sliced from the records (a region lies on one diagonal, so
@@ -737,7 +737,12 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
     of them): only the kept regions give rows, and every row carries aln_rank (0: the best alignment of its hit row) and
     aln_n_merged (the alignments it stands for, itself included) — region_rank and region_n_merged for a cull of scores.  The
     cigars may then be those of all regions or of the kept ones alone (traced from RegionCull.take's objects).  Everything
-    else is unchanged; cull=None gives the rows of every region."""
+    else is unchanged; cull=None gives the rows of every region.
+
+    chain = RegionChain.to_host() of those alignments — or, without alignments, of those scores (Context.chain_regions; needs
+    one of them): every row also carries chain_pos, its region's place in the colinear chain of its hit row (0: the chain's
+    first member), -1 for a region outside the chain.  With cull= as well the chain is that of the objects RegionCull.take
+    gave: its src_region indexes the kept regions.  Nothing else changes; chain=None adds no column."""
     offs, q_start, t_start, length, n_kmers, covered = [np.asarray(c).tolist() for c in regions_host]
     if scores is not None:
         s_offs, s_q, s_t, s_len, s_score, s_ident, s_pos, _ = [np.asarray(c).tolist() for c in scores]
@@ -765,6 +770,18 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
         kept_at = {g: i for i, g in enumerate(c_src)}
         rank_col, nm_col = ("aln_rank", "aln_n_merged") if alignments is not None else ("region_rank", "region_n_merged")
         cg_kept = cigars is not None and len(cg) != len(q_start)
+    chain_pos = None
+    if chain is not None:
+        if scores is None and alignments is None:
+            raise ValueError("a chain needs scores or alignments: it is made of one of them")
+        h_offs, h_src = np.asarray(chain[0]).tolist(), np.asarray(chain[1]).tolist()
+        if len(h_offs) != len(offs) or len(chain[2]) != (len(q_start) if cull is None else len(c_src)):
+            raise ValueError("chain and regions are not of the same regions" if cull is None else
+                             "chain and cull are not of the same regions: with a cull the chain is that of the kept regions")
+        chain_pos = {}
+        for r in range(len(h_offs) - 1):
+            for i, k in enumerate(h_src[h_offs[r]:h_offs[r + 1]]):
+                chain_pos[k if cull is None else c_src[k]] = i
     out = []
     for r, (q, t) in enumerate(zip(np.asarray(qid).tolist(), np.asarray(tid).tolist())):
         qn, qseq = q_records[q]
@@ -792,9 +809,40 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
             if kept_at is not None:
                 row[rank_col] = c_rank[kept_at[g]]
                 row[nm_col] = c_nm[kept_at[g]]
+            if chain_pos is not None:
+                row["chain_pos"] = chain_pos.get(g, -1)
             out.append((q, row))
     out.sort(key=lambda e: (e[0], e[1]["query_start"], e[1]["query_end"]))
     return [row for _, row in out]
+
+
+def hit_chain_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, chain_host) -> List[dict]:
+    """One row per hit row that has a chain (chain_host = RegionChain.to_host(); hit row r = (qid[r], tid[r])): what the
+    alignments of the hit say together.  query_name, match_name, chain_score, n_alns (the chain's members), query_start /
+    query_end and match_start / match_end (the chain's span, half-open), q_aligned and t_aligned (the positions its members
+    cover), qcov and tcov (their share of the whole sequences) and pident (100 * identities / aln_length summed over the
+    members, NaN where the chain was made without those columns).  Sorted by (query's place in q_records, -chain_score,
+    target's place in t_records)."""
+    cols = [np.asarray(c).tolist() for c in chain_host]
+    offs, score, qs, ql, ts, tl, qa, ta, ident, alen = [cols[i] for i in (0, 4, 5, 6, 7, 8, 9, 10, 11, 12)]
+    qid, tid = np.asarray(qid).tolist(), np.asarray(tid).tolist()
+    if len(offs) != len(qid) + 1 or len(qid) != len(tid):
+        raise ValueError("chain and hits are not of the same hit rows")
+    out = []
+    for r, (q, t) in enumerate(zip(qid, tid)):
+        n = offs[r + 1] - offs[r]
+        if n == 0:
+            continue
+        (qn, qseq), (tn, tseq) = q_records[q], t_records[t]
+        out.append((q, -score[r], t, {
+            "query_name": qn, "match_name": tn, "chain_score": score[r], "n_alns": n,
+            "query_start": qs[r], "query_end": qs[r] + ql[r], "match_start": ts[r], "match_end": ts[r] + tl[r],
+            "q_aligned": qa[r], "t_aligned": ta[r],
+            "qcov": format_f64(float(qa[r]) / float(len(qseq)) if len(qseq) else math.nan),
+            "tcov": format_f64(float(ta[r]) / float(len(tseq)) if len(tseq) else math.nan),
+            "pident": format_f64(100.0 * float(ident[r]) / float(alen[r]) if alen[r] else math.nan)}))
+    out.sort(key=lambda e: e[:3])
+    return [row for *_, row in out]
 
 
 def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int, scaled: int, moltype: str,
@@ -802,7 +850,9 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 min_kmers: int = 1, score: bool = False, extend: bool = False, x_drop: int = 0,
                                 matrix=None, gapped: bool = False, band: int = 16, gap_open: int = 11, gap_extend: int = 1,
                                 gapped_x_drop: int = 30, cigar: bool = False, eqx: bool = False, cull: bool = False,
-                                cull_overlap: int = 100, min_aln_score=None, max_alns: int = 0) -> List[dict]:
+                                cull_overlap: int = 100, min_aln_score=None, max_alns: int = 0, chain: bool = False,
+                                chain_max_gap: int = 0, chain_max_overlap: int = 0, chain_link_cost: int = 0,
+                                chain_skew_cost: int = 0, chain_overlap_cost: int = 0, hit_rows: bool = False) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -816,7 +866,14 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     cull=True (needs gapped=True or score=True): redundant regions are culled per hit on the device (Context.cull_regions with
     cull_overlap, min_aln_score and max_alns) — the alignments with gapped=True, otherwise the scored regions — and only the
     kept ones give rows, with the rank and n_merged columns `region_rows` adds for a cull.  With cigar=True only the kept
-    alignments are traced."""
+    alignments are traced.
+    chain=True (needs gapped=True or score=True): the alignments (with gapped=True, otherwise the scored regions) of each hit
+    are chained on the device (Context.chain_regions with the chain_* options) — those the cull kept with cull=True — and the
+    rows carry chain_pos.  hit_rows=True (needs chain=True): the rows of `hit_chain_rows`, one per hit, instead."""
+    if chain and not (gapped or score):
+        raise ValueError("chain=True needs gapped=True or score=True: a chain is made of alignments or of scored regions")
+    if hit_rows and not chain:
+        raise ValueError("hit_rows=True needs chain=True: the rows are those of the hits' chains")
     if cull and not (gapped or score):
         raise ValueError("cull=True needs gapped=True or score=True: a cull is made of alignments or of scored regions")
     if score and not regions:
@@ -844,11 +901,23 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
             rg_host = rg.to_host()
             sc_host = cg_host = cu = None
             kw = {}
+
+            def chained(obj):  # the chain of obj, or of what the cull kept of it
+                kept = cu.take(obj) if cu is not None else obj
+                ch = ctx.chain_regions(kept, max_gap=chain_max_gap, max_overlap=chain_max_overlap, link_cost=chain_link_cost,
+                                       skew_cost=chain_skew_cost, overlap_cost=chain_overlap_cost)
+                host = ch.to_host()
+                ch.free()
+                if kept is not obj:
+                    kept.free()
+                return host
             if score:
                 sc = ctx.score_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, extend=extend, x_drop=x_drop)
                 sc_host = sc.to_host()
                 if cull and not gapped:
                     cu = ctx.cull_regions(sc, overlap_pct=cull_overlap, min_score=min_aln_score, max_per_row=max_alns)
+                if chain and not gapped:
+                    kw["chain"] = chained(sc)
                 sc.free()
             if gapped:
                 al = ctx.align_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, band=band, gap_open=gap_open,
@@ -863,12 +932,16 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                     cg.free()
                     if cull:
                         t_rg.free(); t_al.free()
+                if chain:
+                    kw["chain"] = chained(al)
                 al.free()
             if cu is not None:
                 kw["cull"] = cu.to_host()
                 cu.free()
             for o in (rg, mp, qp, tp, hits, Q, T):
                 o.free()
+            if hit_rows:
+                return hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"])
             if gapped:
                 if cigar:
                     return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, cigars=cg_host, **kw)
