@@ -903,6 +903,101 @@ int ks_rchain_coverage_to_host(ks_ctx *ctx, const ks_rchain *c, double *row_cove
  * may be NULL): the tests place rows around them */
 uint32_t ks_debug_rchain_lds_rows(uint32_t *small_rows);
 
+/* ---- region stitch: the chain of a hit as ONE gapped alignment with one CIGAR ---------------------------------------------- */
+
+/* What a seed-and-extend search closes its alignment stage with (minimap2 fills between chained anchors, BLAST links HSPs,
+ * MMseqs2 realigns the diagonal range): the members of each hit row's chain keep their paths, what lies between two consecutive
+ * members is aligned globally, and the row becomes one alignment — one CIGAR, one score, a PAF / SAM record.  All arithmetic is
+ * in integers: the result is bit-exact against a host loop (tests/rstitch_ref.py).
+ *   chain: a ks_rchain;  alignments: the ks_raligns it was computed from (the intended input: ks_raligns_take of the cull);
+ *   cigars: the ks_cigars traced from exactly those alignments (the same regions in the same order);  hits and the two residue
+ *   batches: what ks_regions_align took.  The matrix, gap_open = o and gap_extend = e are those recorded in `alignments`; its
+ *   band and x_drop are not used.
+ * Options: max_fill in [0, 4096], 0 means 1024;  flags: KS_RSTITCH_EQX;  max_scratch_bytes, 0 means 1 GiB;  reserved 0.
+ * Per hit row the chain lists the members m_0 .. m_(k-1) (src_region, in chain order); an end is start + length.
+ * Trim: for i >= 1, member i loses the smallest number c of leading columns such that the query position is >= q_end[m_(i-1)]
+ *   and the target position is >= t_end[m_(i-1)] (the ORIGINAL ends of the member before it; tails are never trimmed; with the
+ *   chain's max_overlap 0 nothing is trimmed).  c may be all of its columns: the member then contributes nothing and its end
+ *   still stands.  The trimmed member starts at (q', t').
+ * Link i: X = q' - q_end[m_(i-1)], Y = t' - t_end[m_(i-1)] (both >= 0).  X = Y = 0: nothing;  Y = 0: I x X;  X = 0: D x Y;
+ *   min(X, Y) <= 63 and max(X, Y) <= max_fill: FILLED, below;  otherwise OPEN: I x X, then D x Y.
+ * Fill: the recurrence of ks_regions_align (above: H~, F, D, E, H and every tie rule) on the whole rectangle — every cell
+ *   0 <= x <= |Q|, 0 <= y <= |T| exists, no band, no X-drop — with the end cell (|Q|, |T|) walked back to (0, 0) by the rules of
+ *   ks_regions_traceback.  T is the SHORTER stretch (X == Y: the target's), Q the longer.  A pair always scores
+ *   M[class(query residue)][class(target residue)].  Where T is the target stretch an F step is I and an E jump of L is D x L;
+ *   where T is the query stretch (roles swapped) an F step is D and an E jump of L is I x L.  The optimal score does not depend
+ *   on the orientation, the choice among co-optimal paths does: the orientation is part of the contract.
+ * Splice: the ops of m_0, link 1, the trimmed m_1, ...; adjacent equal ops merge, joints included (an I run beside a D run
+ *   stays two ops).  The pairs of a fill are M; with KS_RSTITCH_EQX they are = / X by upper-cased byte equality, and the
+ *   members' ops must then hold no M — without the flag no = or X.  An op is len << 4 | code, as in ks_cigars.
+ * Result (device-resident): a CSR over the hit rows, op_offsets u64[n_rows + 1] and ops u32[n_ops], and per hit row the columns
+ *   of that alignment, re-scored over the residues:
+ *   q_start, q_length, t_start, t_length u32   from the first member's start to the last member's end: the chain's span
+ *   score i64                = sum of M[pair] - sum over the I / D ops of (o + L * e)
+ *   identities, positives, gap_opens (the I and D ops after merging), gaps, aln_length u32
+ *   n_members, n_filled, n_open, n_trimmed (columns removed) u32
+ *   row_score f64            (double)score, NaN for a row without members: a d_score column for ks_hits_best with
+ *                            KS_BEST_SCORE and for the cluster passes
+ *   A row without members has no ops and zeros.  A row of one member has that member's ops and exactly its alignment's columns.
+ * The result never depends on the launch geometry, on ks_debug_rstitch_stage() or on max_scratch_bytes.
+ * Scratch: 64 bytes per row of Q of every filled link (rounded up to an even number of rows).  max_scratch_bytes bounds it: the
+ * members run in slices of consecutive members whose links fit.
+ * KS_ERR_INVALID_ARG, before any device work and also with ctx == NULL: max_fill > 4096, unknown flags, a non-zero reserved
+ * field.  Then: NULL arguments; an object of another context; row or region counts of chain, alignments, cigars and hits that
+ * disagree.  Found on the device before anything is indexed by it, ks_last_error names the first offender: a src_region outside
+ * its row's alignments; a qid / tid or sequence outside its batch; an extent outside its sequence; a member whose ops do not
+ * consume exactly its q_length / t_length; the M / = / X mismatch; a member that ends before the member in front of it on
+ * either sequence.
+ * KS_ERR_CAPACITY: a single filled link whose directions do not fit max_scratch_bytes; what ks_regions_align refuses with it
+ * (a chained hit row with a sequence of more than 2^20 residues).
+ * One stream, synchronous on return, three host waits (the layout, the op count, the result); all memory comes from the
+ * context's pool. */
+typedef struct ks_hitalns ks_hitalns;
+#define KS_RSTITCH_EQX 1u
+#define KS_RSTITCH_MAX_FILL 4096u
+typedef struct ks_rstitch_opts {
+    uint32_t max_fill;          /* the longer side of a filled rectangle at most; 0: 1024; at most 4096 */
+    uint32_t flags;             /* KS_RSTITCH_EQX */
+    uint64_t max_scratch_bytes; /* direction scratch of one slice; 0: 1 GiB */
+    uint32_t reserved[2];       /* 0 */
+} ks_rstitch_opts;
+/* opts == NULL: the defaults */
+int ks_regions_stitch(ks_ctx *ctx, const ks_rchain *chain, const ks_raligns *alignments, const ks_cigars *cigars, const ks_hits *hits,
+                      const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res,
+                      const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res,
+                      const ks_rstitch_opts *opts, ks_hitalns **out);
+uint64_t ks_hitalns_n_rows(const ks_hitalns *a);
+uint64_t ks_hitalns_n_ops(const ks_hitalns *a);
+/* diagnostic: the direction scratch the call allocated, and the slices it ran in */
+uint64_t ks_hitalns_scratch_bytes(const ks_hitalns *a);
+uint32_t ks_hitalns_n_slices(const ks_hitalns *a);
+/* device pointers, valid until ks_hitalns_free */
+const uint64_t *ks_hitalns_device_op_offsets(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_ops(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_q_start(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_q_length(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_t_start(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_t_length(const ks_hitalns *a);
+const int64_t *ks_hitalns_device_score(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_identities(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_positives(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_gap_opens(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_gaps(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_aln_length(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_n_members(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_n_filled(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_n_open(const ks_hitalns *a);
+const uint32_t *ks_hitalns_device_n_trimmed(const ks_hitalns *a);
+const double *ks_hitalns_device_row_score(const ks_hitalns *a);
+/* any destination may be NULL */
+int ks_hitalns_copy_to_host(ks_ctx *ctx, const ks_hitalns *a, uint64_t *op_offsets, uint32_t *ops, uint32_t *q_start, uint32_t *q_length,
+                            uint32_t *t_start, uint32_t *t_length, int64_t *score, uint32_t *identities, uint32_t *positives,
+                            uint32_t *gap_opens, uint32_t *gaps, uint32_t *aln_length, uint32_t *n_members, uint32_t *n_filled,
+                            uint32_t *n_open, uint32_t *n_trimmed, double *row_score);
+void ks_hitalns_free(ks_hitalns *a);
+/* rows of directions one wave stages at once for the walk of a fill: the tests place rectangles around it */
+uint32_t ks_debug_rstitch_stage(void);
+
 /* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
 
 /* Replaces the two sums behind the columns that branchwater multisearch adds with "calculate probability of overlap between

@@ -94,6 +94,14 @@ class ks_rchain_opts(C.Structure):
                 ("overlap_cost", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+KS_RSTITCH_EQX = 1
+KS_RSTITCH_MAX_FILL = 4096
+
+
+class ks_rstitch_opts(C.Structure):
+    _fields_ = [("max_fill", C.c_uint32), ("flags", C.c_uint32), ("max_scratch_bytes", C.c_uint64), ("reserved", C.c_uint32 * 2)]
+
+
 class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -330,6 +338,31 @@ SIGNATURES = {
     "ks_rchain_coverage": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32]),
     "ks_rchain_coverage_to_host": (C.c_int, [_vp, _vp, _vp]),
     "ks_debug_rchain_lds_rows": (C.c_uint32, [_u32p]),
+    "ks_regions_stitch": (C.c_int, [_vp] * 5 + [_vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(ks_rstitch_opts), _pp]),
+    "ks_hitalns_n_rows": (C.c_uint64, [_vp]),
+    "ks_hitalns_n_ops": (C.c_uint64, [_vp]),
+    "ks_hitalns_scratch_bytes": (C.c_uint64, [_vp]),
+    "ks_hitalns_n_slices": (C.c_uint32, [_vp]),
+    "ks_hitalns_device_op_offsets": (_vp, [_vp]),
+    "ks_hitalns_device_ops": (_vp, [_vp]),
+    "ks_hitalns_device_q_start": (_vp, [_vp]),
+    "ks_hitalns_device_q_length": (_vp, [_vp]),
+    "ks_hitalns_device_t_start": (_vp, [_vp]),
+    "ks_hitalns_device_t_length": (_vp, [_vp]),
+    "ks_hitalns_device_score": (_vp, [_vp]),
+    "ks_hitalns_device_identities": (_vp, [_vp]),
+    "ks_hitalns_device_positives": (_vp, [_vp]),
+    "ks_hitalns_device_gap_opens": (_vp, [_vp]),
+    "ks_hitalns_device_gaps": (_vp, [_vp]),
+    "ks_hitalns_device_aln_length": (_vp, [_vp]),
+    "ks_hitalns_device_n_members": (_vp, [_vp]),
+    "ks_hitalns_device_n_filled": (_vp, [_vp]),
+    "ks_hitalns_device_n_open": (_vp, [_vp]),
+    "ks_hitalns_device_n_trimmed": (_vp, [_vp]),
+    "ks_hitalns_device_row_score": (_vp, [_vp]),
+    "ks_hitalns_copy_to_host": (C.c_int, [_vp] * 19),
+    "ks_hitalns_free": (None, [_vp]),
+    "ks_debug_rstitch_stage": (C.c_uint32, []),
     "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
     "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
     "ks_corpus_n_docs": (C.c_uint32, [_vp]),

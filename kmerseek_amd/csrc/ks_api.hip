@@ -1018,3 +1018,84 @@ extern "C" int ks_rchain_coverage_to_host(ks_ctx *ctx, const ks_rchain *c, doubl
     return ks_columns_to_host(ctx, {{row_coverage, c->d_row_cov, (size_t)c->n_rows * sizeof(double)}});
     });
 }
+
+// ---------------------------------------------------------------------------------------------
+// region stitch (ks_rstitch.hip): the chain of each hit row as one gapped alignment with one CIGAR
+// ---------------------------------------------------------------------------------------------
+extern "C" int ks_regions_stitch(ks_ctx *ctx, const ks_rchain *chain, const ks_raligns *alignments, const ks_cigars *cigars, const ks_hits *hits,
+                                 const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                 const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_rstitch_opts *opts, ks_hitalns **out) {
+    return ks_guard(ctx, [&]() -> int {
+    const ks_rstitch_opts dflt = {0u, 0u, 0u, {0u, 0u}};
+    const ks_rstitch_opts o = opts ? *opts : dflt;
+    KS_TRY(ks_opts_words_check(ctx, "region stitch", o.flags, KS_RSTITCH_EQX, o.reserved[0] | o.reserved[1]));
+    if (o.max_fill > KS_RSTITCH_MAX_FILL)
+        return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "region stitch options: max_fill %u (at most %u, 0 = 1024)", o.max_fill, KS_RSTITCH_MAX_FILL)
+                   : KS_ERR_INVALID_ARG;
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    if (!chain || !alignments || !cigars || !hits || !out || !d_q_offs || !d_t_offs || (n_q_res && !d_q_res) || (n_t_res && !d_t_res))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "region stitch", chain, alignments, cigars, hits));
+    if (chain->n_rows != alignments->n_rows || cigars->n_rows != alignments->n_rows || hits->n_hits != alignments->n_rows ||
+        chain->n_regions != alignments->n_regions || cigars->n_regions != alignments->n_regions)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG,
+                       "region stitch: the chain is of %llu regions in %llu hit rows, the alignments are %llu in %llu, the CIGARs %llu in %llu, "
+                       "the hit list has %llu rows: objects of other regions",
+                       (unsigned long long)chain->n_regions, (unsigned long long)chain->n_rows, (unsigned long long)alignments->n_regions,
+                       (unsigned long long)alignments->n_rows, (unsigned long long)cigars->n_regions, (unsigned long long)cigars->n_rows,
+                       (unsigned long long)hits->n_hits);
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    const ks_res_batch Q{d_q_res, d_q_offs, n_q, n_q_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
+    ks_result<ks_hitalns> R(ctx, out, ks_hitalns_free);
+    KS_TRY(ks_regions_stitch_impl(ctx, chain, alignments, cigars, hits, Q, T, o.max_fill ? o.max_fill : 1024u, o.flags, o.max_scratch_bytes, R));
+    return R.commit();
+    });
+}
+extern "C" uint64_t ks_hitalns_n_rows(const ks_hitalns *a) { return a ? a->n_rows : 0; }
+extern "C" uint64_t ks_hitalns_n_ops(const ks_hitalns *a) { return a ? a->n_ops : 0; }
+extern "C" uint64_t ks_hitalns_scratch_bytes(const ks_hitalns *a) { return a ? a->dir_bytes : 0; }
+extern "C" uint32_t ks_hitalns_n_slices(const ks_hitalns *a) { return a ? a->n_slices : 0; }
+extern "C" const uint64_t *ks_hitalns_device_op_offsets(const ks_hitalns *a) { return a ? a->d_op_offsets : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_ops(const ks_hitalns *a) { return a ? a->d_ops : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_q_start(const ks_hitalns *a) { return a ? a->d_q_start : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_q_length(const ks_hitalns *a) { return a ? a->d_q_length : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_t_start(const ks_hitalns *a) { return a ? a->d_t_start : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_t_length(const ks_hitalns *a) { return a ? a->d_t_length : nullptr; }
+extern "C" const int64_t *ks_hitalns_device_score(const ks_hitalns *a) { return a ? a->d_score : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_identities(const ks_hitalns *a) { return a ? a->d_identities : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_positives(const ks_hitalns *a) { return a ? a->d_positives : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_gap_opens(const ks_hitalns *a) { return a ? a->d_gap_opens : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_gaps(const ks_hitalns *a) { return a ? a->d_gaps : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_aln_length(const ks_hitalns *a) { return a ? a->d_aln_length : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_n_members(const ks_hitalns *a) { return a ? a->d_n_members : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_n_filled(const ks_hitalns *a) { return a ? a->d_n_filled : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_n_open(const ks_hitalns *a) { return a ? a->d_n_open : nullptr; }
+extern "C" const uint32_t *ks_hitalns_device_n_trimmed(const ks_hitalns *a) { return a ? a->d_n_trimmed : nullptr; }
+extern "C" const double *ks_hitalns_device_row_score(const ks_hitalns *a) { return a ? a->d_row_score : nullptr; }
+
+extern "C" int ks_hitalns_copy_to_host(ks_ctx *ctx, const ks_hitalns *a, uint64_t *op_offsets, uint32_t *ops, uint32_t *q_start, uint32_t *q_length,
+                                       uint32_t *t_start, uint32_t *t_length, int64_t *score, uint32_t *identities, uint32_t *positives,
+                                       uint32_t *gap_opens, uint32_t *gaps, uint32_t *aln_length, uint32_t *n_members, uint32_t *n_filled,
+                                       uint32_t *n_open, uint32_t *n_trimmed, double *row_score) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx || !a) return KS_ERR_INVALID_ARG;
+    const size_t nr = (size_t)a->n_rows, r4 = nr * sizeof(u32), r8 = nr * sizeof(u64);
+    return ks_columns_to_host(ctx, {{op_offsets, a->d_op_offsets, (nr + 1) * sizeof(u64)}, {ops, a->d_ops, (size_t)a->n_ops * sizeof(u32)},
+                                    {q_start, a->d_q_start, r4}, {q_length, a->d_q_length, r4}, {t_start, a->d_t_start, r4}, {t_length, a->d_t_length, r4},
+                                    {score, a->d_score, r8}, {identities, a->d_identities, r4}, {positives, a->d_positives, r4},
+                                    {gap_opens, a->d_gap_opens, r4}, {gaps, a->d_gaps, r4}, {aln_length, a->d_aln_length, r4},
+                                    {n_members, a->d_n_members, r4}, {n_filled, a->d_n_filled, r4}, {n_open, a->d_n_open, r4},
+                                    {n_trimmed, a->d_n_trimmed, r4}, {row_score, a->d_row_score, r8}});
+    });
+}
+
+extern "C" void ks_hitalns_free(ks_hitalns *a) {
+    if (!a) return;
+    for (void *p : {(void *)a->d_op_offsets, (void *)a->d_ops, (void *)a->d_score, (void *)a->d_q_start, (void *)a->d_q_length, (void *)a->d_t_start,
+                    (void *)a->d_t_length, (void *)a->d_identities, (void *)a->d_positives, (void *)a->d_gap_opens, (void *)a->d_gaps,
+                    (void *)a->d_aln_length, (void *)a->d_n_members, (void *)a->d_n_filled, (void *)a->d_n_open, (void *)a->d_n_trimmed,
+                    (void *)a->d_row_score})
+        ks_pool_free(a->ctx, p);
+    delete a;
+}

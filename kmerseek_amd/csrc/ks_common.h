@@ -348,13 +348,14 @@ enum : u32 {
     KS_PIN_RCULL = 243,      // 3 words, region cull: first row that breaks the CSR | first region with a length of 0 | kept regions (ks_rcull.hip)
     KS_PIN_RCHAIN = 246,     // 5 words, region chain: first row that breaks the CSR | first region with a length of 0 | with an end beyond 0xffffffff | with a score beyond 2^30 | chained regions (ks_rchain.hip)
     KS_PIN_RCHAIN_COV = 251, // 2 words, chain coverage: first row with an id beyond the batches | first row whose chain is longer than its sequence (ks_rchain.hip)
-    KS_PIN_END = 253,
+    KS_PIN_RSTITCH = 253,    // 11 words, region stitch: the eight first-offender words (ks_rstitch.hip: RS_BAD_*), then the scan totals: direction rows | columns | ops
+    KS_PIN_END = 264,
 };
-#define KS_PIN_WORDS 256
+#define KS_PIN_WORDS 272
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -553,6 +554,24 @@ struct ks_rchain_cols { const u64 *row_offs; const u32 *qs, *ql, *ts, *tl; const
 int ks_regions_chain_impl(ks_ctx *ctx, const ks_rchain_cols &cols, u64 n_rows, u64 n_regions, const ks_rchain_opts *opts, ks_rchain *K);
 // ks_rchain_coverage behind its argument checks (H: of ctx, K's row count; mode <= 3)
 int ks_rchain_coverage_impl(ks_ctx *ctx, ks_rchain *K, const ks_hits *H, const u64 *d_q_off, u32 n_q, const u64 *d_t_off, u32 n_t, u32 mode);
+
+// the chain of each hit row stitched into one gapped alignment with one CIGAR (ks_rstitch.hip)
+struct ks_hitalns {
+    ks_ctx *ctx;
+    u64 n_rows, n_ops;
+    u64 *d_op_offsets;                   // n_rows + 1
+    u32 *d_ops;                          // n_ops: len << 4 | op
+    i64 *d_score;                        // n_rows, as every column below
+    u32 *d_q_start, *d_q_length, *d_t_start, *d_t_length;
+    u32 *d_identities, *d_positives, *d_gap_opens, *d_gaps, *d_aln_length;
+    u32 *d_n_members, *d_n_filled, *d_n_open, *d_n_trimmed;
+    double *d_row_score;
+    u64 dir_bytes;                       // direction scratch the call allocated, the slices it ran in (diagnostic)
+    u32 n_slices;
+};
+// ks_regions_stitch behind its argument checks (options validated, defaults filled in; K, S, G, H: of ctx, equal counts)
+int ks_regions_stitch_impl(ks_ctx *ctx, const ks_rchain *K, const ks_raligns *S, const ks_cigars *G, const ks_hits *H, const ks_res_batch &Q,
+                           const ks_res_batch &T, u32 max_fill, u32 flags, u64 max_scratch_bytes, ks_hitalns *R);
 
 // clusters of a hit list read as a graph: its connected components (ks_cluster.hip) or greedy representative clusters (ks_greedy.hip)
 struct ks_clusters {

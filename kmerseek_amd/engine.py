@@ -656,6 +656,48 @@ class Context:
         self._check(fn(self._h, scored._h, C.byref(opts), C.byref(out)))
         return RegionChain(self, out)
 
+    @staticmethod
+    def _rstitch_opts(max_fill: int, eqx: bool, max_scratch_bytes: int):
+        for name, v, top in (("max_fill", max_fill, _lib.KS_RSTITCH_MAX_FILL), ("max_scratch_bytes", max_scratch_bytes, 2 ** 64 - 1)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
+        return _lib.ks_rstitch_opts(int(max_fill), _lib.KS_RSTITCH_EQX if eqx else 0, int(max_scratch_bytes), (C.c_uint32 * 2)(0, 0))
+
+    def stitch_chains_device(self, chain: "RegionChain", alignments: "RegionAlignments", cigars: "RegionCigars", hits: "Hits",
+                             d_q_res: int, d_q_off: int, n_q: int, n_q_res: int, d_t_res: int, d_t_off: int, n_t: int, n_t_res: int,
+                             max_fill: int = 0, eqx: bool = False, max_scratch_bytes: int = 0) -> "HitAlignments":
+        """ks_regions_stitch from device-resident residue batches: the chain of every hit row made into ONE gapped alignment
+        with one CIGAR.  `alignments` is what `chain` was computed from (chain_regions(cull.take(alignments))), `cigars` what
+        trace_regions gave for exactly those alignments (with eqx=True here they must have been traced with eqx=True).  Between
+        two consecutive members the overlap is trimmed off the later one, and the rectangle left between them is aligned
+        globally (the alignments' matrix and gap costs) where its shorter side is at most 63 and its longer at most max_fill
+        (0: 1024, at most 4096); a longer one stays an open I run beside a D run.  max_scratch_bytes bounds the direction
+        scratch of one slice (0: 1 GiB).  include/kmerseek_amd.h has the contract."""
+        opts = self._rstitch_opts(max_fill, eqx, max_scratch_bytes)
+        out = C.c_void_p()
+        self._check(self._L.ks_regions_stitch(self._h, chain._h, alignments._h, cigars._h, hits._h, C.c_void_p(d_q_res), C.c_void_p(d_q_off),
+                                              int(n_q), int(n_q_res), C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res),
+                                              C.byref(opts), C.byref(out)))
+        return HitAlignments(self, out)
+
+    def stitch_chains(self, chain: "RegionChain", alignments: "RegionAlignments", cigars: "RegionCigars", hits: "Hits",
+                      q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray, t_off: np.ndarray, max_fill: int = 0, eqx: bool = False,
+                      max_scratch_bytes: int = 0) -> "HitAlignments":
+        """stitch_chains_device from host arrays (the batches `alignments` was made on): uploaded, stitched, released."""
+        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        self._rstitch_opts(max_fill, eqx, max_scratch_bytes)  # (refused before anything is uploaded)
+        bufs = []
+        try:
+            for a in (q_res, q_off, t_res, t_off):
+                bufs.append(self.to_device(a))
+            return self.stitch_chains_device(chain, alignments, cigars, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res),
+                                             bufs[2].ptr, bufs[3].ptr, len(t_off) - 1, len(t_res), max_fill=max_fill, eqx=eqx,
+                                             max_scratch_bytes=max_scratch_bytes)
+        finally:
+            for b in bufs:
+                b.free()
+
     def significance(self, queries: "Sketches", targets: "Sketches", hits: "Hits", q_corpus: Optional["Corpus"] = None,
                      t_corpus: Optional["Corpus"] = None) -> "Significance":
         """ks_hits_significance: per row of `hits` the two f64 sums behind multisearch's prob_overlap and tf_idf_score, over the
@@ -1284,6 +1326,65 @@ class RegionChain(_Owned):
         out = np.zeros(self.n_rows, np.float64)
         self._ctx._check(self._ctx._L.ks_rchain_coverage_to_host(self._ctx._h, self._h, _ptr(out)))
         return out
+
+
+class HitAlignments(_Owned):
+    """Device-resident result of Context.stitch_chains (ks_hitalns): per hit row ONE gapped alignment — the members of the
+    row's chain with the links between them filled — as a CSR of BAM-encoded ops (row r owns ops [op_offsets[r],
+    op_offsets[r + 1]), an op is len << 4 | code) and the columns of that alignment: its span on both sequences, score (i64),
+    identities, positives, gap_opens, gaps, aln_length, the chain members, filled and open links and trimmed columns behind it,
+    and the score as f64 (NaN: a row without a chain), a `score=` column for Context.best_hits and the cluster passes."""
+    _free = "ks_hitalns_free"
+    _COLUMNS = ("op_offsets", "ops", "q_start", "q_length", "t_start", "t_length", "score", "identities", "positives", "gap_opens",
+                "gaps", "aln_length", "n_members", "n_filled", "n_open", "n_trimmed", "row_score")
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_hitalns_n_rows(self._h))
+
+    @property
+    def n_ops(self) -> int:
+        return int(self._ctx._L.ks_hitalns_n_ops(self._h))
+
+    @property
+    def n_slices(self) -> int:
+        """Slices of chain members the fills ran in (1 unless the directions did not fit max_scratch_bytes).  Diagnostic."""
+        return int(self._ctx._L.ks_hitalns_n_slices(self._h))
+
+    @property
+    def scratch_bytes(self) -> int:
+        """Direction scratch the call allocated.  Diagnostic."""
+        return int(self._ctx._L.ks_hitalns_scratch_bytes(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (op_offsets u64[n_rows + 1]; ops u32[n_ops]; and [n_rows] each: q_start, q_length, t_start,
+        t_length u32; score i64; identities, positives, gap_opens, gaps, aln_length, n_members, n_filled, n_open, n_trimmed u32;
+        row_score f64)."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_hitalns_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    @property
+    def row_score_ptr(self) -> int:
+        """The device column row_score f64[n_rows]: pass it to Context.best_hits(score=...) or a cluster pass."""
+        return int(self._ctx._L.ks_hitalns_device_row_score(self._h) or 0)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """The columns of device_ptrs() as numpy arrays, in that order."""
+        r = self.n_rows
+        cols = [np.zeros(r + 1, np.uint64), np.zeros(self.n_ops, np.uint32)] + [np.zeros(r, np.uint32) for _ in range(4)] + \
+               [np.zeros(r, np.int64)] + [np.zeros(r, np.uint32) for _ in range(9)] + [np.zeros(r, np.float64)]
+        self._ctx._check(self._ctx._L.ks_hitalns_copy_to_host(self._ctx._h, self._h, *[_ptr(c) for c in cols]))
+        return tuple(cols)
+
+    def ops_to_host(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(op_offsets u64[n_rows + 1], ops u32[n_ops]) alone."""
+        offs, ops = np.zeros(self.n_rows + 1, np.uint64), np.zeros(self.n_ops, np.uint32)
+        self._ctx._check(self._ctx._L.ks_hitalns_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(ops), *([None] * 15)))
+        return offs, ops
+
+    def strings(self) -> List[str]:
+        """The CIGAR of every hit row as text, e.g. "60M40I60M"; "" for a row without a chain."""
+        return cigar_strings(*self.ops_to_host())
 
 
 class Clusters(_Owned):

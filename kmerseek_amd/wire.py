@@ -816,13 +816,26 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
     return [row for _, row in out]
 
 
-def hit_chain_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, chain_host) -> List[dict]:
+def hit_chain_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, chain_host,
+                   stitched=None) -> List[dict]:
     """One row per hit row that has a chain (chain_host = RegionChain.to_host(); hit row r = (qid[r], tid[r])): what the
     alignments of the hit say together.  query_name, match_name, chain_score, n_alns (the chain's members), query_start /
     query_end and match_start / match_end (the chain's span, half-open), q_aligned and t_aligned (the positions its members
     cover), qcov and tcov (their share of the whole sequences) and pident (100 * identities / aln_length summed over the
     members, NaN where the chain was made without those columns).  Sorted by (query's place in q_records, -chain_score,
-    target's place in t_records)."""
+    target's place in t_records).
+    stitched = HitAlignments.to_host() of that chain (Context.stitch_chains): every row also carries the ONE gapped alignment
+    the chain was stitched into — aln_cigar (text, the query as the read), aln_score, aln_identities, aln_positives,
+    aln_gap_opens, aln_gaps, aln_length, aln_pident (100 * identities / aln_length of that alignment: no column is counted
+    twice) — and n_filled / n_open, the links between the chain's members that were aligned / left open.  stitched=None adds
+    no column."""
+    st = None
+    if stitched is not None:
+        from .engine import cigar_strings
+        st = [np.asarray(c).tolist() for c in stitched]
+        if len(st[0]) != len(np.asarray(chain_host[0])) or any(len(c) != len(st[0]) - 1 for c in st[2:]):
+            raise ValueError("stitched alignments and chain are not of the same hit rows")
+        st_cigar = cigar_strings(stitched[0], stitched[1])
     cols = [np.asarray(c).tolist() for c in chain_host]
     offs, score, qs, ql, ts, tl, qa, ta, ident, alen = [cols[i] for i in (0, 4, 5, 6, 7, 8, 9, 10, 11, 12)]
     qid, tid = np.asarray(qid).tolist(), np.asarray(tid).tolist()
@@ -841,6 +854,12 @@ def hit_chain_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[T
             "qcov": format_f64(float(qa[r]) / float(len(qseq)) if len(qseq) else math.nan),
             "tcov": format_f64(float(ta[r]) / float(len(tseq)) if len(tseq) else math.nan),
             "pident": format_f64(100.0 * float(ident[r]) / float(alen[r]) if alen[r] else math.nan)}))
+        if st is not None:
+            out[-1][3].update({
+                "aln_cigar": st_cigar[r], "aln_score": st[6][r], "aln_identities": st[7][r], "aln_positives": st[8][r],
+                "aln_gap_opens": st[9][r], "aln_gaps": st[10][r], "aln_length": st[11][r],
+                "aln_pident": format_f64(100.0 * float(st[7][r]) / float(st[11][r]) if st[11][r] else math.nan),
+                "n_filled": st[13][r], "n_open": st[14][r]})
     out.sort(key=lambda e: e[:3])
     return [row for *_, row in out]
 
@@ -852,7 +871,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 gapped_x_drop: int = 30, cigar: bool = False, eqx: bool = False, cull: bool = False,
                                 cull_overlap: int = 100, min_aln_score=None, max_alns: int = 0, chain: bool = False,
                                 chain_max_gap: int = 0, chain_max_overlap: int = 0, chain_link_cost: int = 0,
-                                chain_skew_cost: int = 0, chain_overlap_cost: int = 0, hit_rows: bool = False) -> List[dict]:
+                                chain_skew_cost: int = 0, chain_overlap_cost: int = 0, hit_rows: bool = False,
+                                stitch: bool = False, stitch_max_fill: int = 0) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -869,7 +889,15 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     alignments are traced.
     chain=True (needs gapped=True or score=True): the alignments (with gapped=True, otherwise the scored regions) of each hit
     are chained on the device (Context.chain_regions with the chain_* options) — those the cull kept with cull=True — and the
-    rows carry chain_pos.  hit_rows=True (needs chain=True): the rows of `hit_chain_rows`, one per hit, instead."""
+    rows carry chain_pos.  hit_rows=True (needs chain=True): the rows of `hit_chain_rows`, one per hit, instead.
+    stitch=True (needs gapped=True, cigar=True, chain=True and hit_rows=True): each hit's chain is stitched into one gapped
+    alignment on the device (Context.stitch_chains with stitch_max_fill and eqx) and the hit rows carry the aln_* columns
+    `hit_chain_rows` adds for stitched=."""
+    if stitch:
+        for name, on in (("gapped", gapped), ("cigar", cigar), ("chain", chain), ("hit_rows", hit_rows)):
+            if not on:
+                raise ValueError(f"stitch=True needs {name}=True: a stitched alignment is made of the traced alignments of a hit's chain "
+                                 "and is a column set of the hit rows")
     if chain and not (gapped or score):
         raise ValueError("chain=True needs gapped=True or score=True: a chain is made of alignments or of scored regions")
     if hit_rows and not chain:
@@ -925,14 +953,23 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                 al_host = al.to_host()
                 if cull:
                     cu = ctx.cull_regions(al, overlap_pct=cull_overlap, min_score=min_aln_score, max_per_row=max_alns)
-                if cigar:
+                if stitch:  # the kept alignments, their paths and their chain stay on the device until they are stitched
+                    t_rg, t_al = (cu.take(rg), cu.take(al)) if cull else (rg, al)
+                    cg = ctx.trace_regions(t_rg, hits, q_res, q_off, t_res, t_off, t_al, eqx=eqx)
+                    ch = ctx.chain_regions(t_al, max_gap=chain_max_gap, max_overlap=chain_max_overlap, link_cost=chain_link_cost,
+                                           skew_cost=chain_skew_cost, overlap_cost=chain_overlap_cost)
+                    st = ctx.stitch_chains(ch, t_al, cg, hits, q_res, q_off, t_res, t_off, max_fill=stitch_max_fill, eqx=eqx)
+                    kw["chain"], st_host = ch.to_host(), st.to_host()
+                    for o in (st, ch, cg) + ((t_rg, t_al) if cull else ()):
+                        o.free()
+                elif cigar:
                     t_rg, t_al = (cu.take(rg), cu.take(al)) if cull else (rg, al)  # (trace what is kept, not everything)
                     cg = ctx.trace_regions(t_rg, hits, q_res, q_off, t_res, t_off, t_al, eqx=eqx)
                     cg_host = cg.to_host()
                     cg.free()
                     if cull:
                         t_rg.free(); t_al.free()
-                if chain:
+                if chain and not stitch:
                     kw["chain"] = chained(al)
                 al.free()
             if cu is not None:
@@ -940,6 +977,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                 cu.free()
             for o in (rg, mp, qp, tp, hits, Q, T):
                 o.free()
+            if stitch:
+                return hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"], stitched=st_host)
             if hit_rows:
                 return hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"])
             if gapped:
