@@ -20,7 +20,7 @@ __global__ __launch_bounds__(RA_THREADS) void k_ralign(ra_args A) {
     __shared__ u8 s_cls[256];
     __shared__ signed char s_M[RK_A * RK_A];
     __shared__ unsigned short s_strip[RA_THREADS / 64][RA_STRIP];
-    rk_stage_tables(A.in, s_cls, s_M);
+    rk_stage_tables(A.in.matrix, s_cls, s_M);
     __syncthreads();
     const u32 lane = threadIdx.x & 63, wave = ks_readfirst(threadIdx.x >> 6);
     const u64 g64 = (u64)blockIdx.x * (RA_THREADS / 64) + wave;

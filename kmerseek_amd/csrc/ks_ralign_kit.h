@@ -1,6 +1,7 @@
 // ks_ralign_kit.h — the one extension of the banded affine-gap program (include/kmerseek_amd.h: region alignments) that
 // ks_ralign.hip and ks_rtrace.hip share: a wave per region, lanes as diagonals.  Two instantiations of one row step, so the
-// pass that reports an alignment and the pass that walks it back can never disagree on a tie.
+// pass that reports an alignment and the pass that walks it back can never disagree on a tie.  The E step of that row step
+// (ra_e_step) and the direction byte are also what the fill of ks_rstitch.hip, lanes as columns, takes and writes.
 //   TR = false  ks_regions_align: every state carries the four counts of its path, the rows run to the X-drop rule's J and
 //               the best cell comes back.
 //   TR = true   ks_regions_traceback: the end cell is known (x_end <= J, y_end), so there is no X-drop rule, no best cell
@@ -42,12 +43,16 @@
 #define RA_MAX_LEN (1u << 20)
 static_assert(RA_CHUNK <= 64 && RA_CHUNK + 2 * RA_WMAX <= RA_STRIP && RA_STRIP == 128, "a chunk is a lane per row, its window two entries per lane");
 
-// The direction byte of the cell (x, lane k), x >= 1 (TR = true), 64 bytes per row:
+// The direction byte of the cell (x, lane k), x >= 1, RA_DIR_ROW bytes per row.  One byte, two lane geometries (the walk that
+// reads it is rp_walk of ks_rpath_kit.h):
 //   RA_DIR_DIAG   H~(x, y) took D (else F)
-//   RA_DIR_CONT   the G this lane handed down in row x — it is the F of the cell one lane below, (x, lane k - 1) — continued
-//                 the gap F(x - 1, lane k) (else it opened one from H(x - 1, lane k)): a walk in state F at (x, lane j)
-//                 reads this bit of lane j + 1 and goes to (x - 1, lane j + 1)
-//   >> RA_DIR_E   0: H(x, y) is H~; d >= 1: H took E from the H~ of lane k - d of the same row (d <= 2W <= 62: 6 bits)
+//   RA_DIR_CONT   a gap F continued F of the row before (else it opened one from H of the row before).  Whose gap:
+//                   lanes as diagonals (ra_extend<true>)  the G this lane HANDED DOWN in row x: it is the F of the cell one lane
+//                                                         below, (x, lane k - 1).  A walk in state F at (x, lane j) reads this
+//                                                         bit of lane j + 1 and goes to (x - 1, lane j + 1)
+//                   lanes as columns (k_rs_fill)          the F of the lane's OWN cell.  A walk in state F at (x, lane j) reads
+//                                                         this bit of lane j and goes to (x - 1, lane j)
+//   >> RA_DIR_E   0: H(x, y) is H~; d >= 1: H took E from the H~ of lane k - d of the same row (d <= 63: 6 bits)
 // The byte of a lane whose cell does not exist means nothing; a walk from an existing cell never reaches one.
 #define RA_DIR_DIAG 1u
 #define RA_DIR_CONT 2u
@@ -61,6 +66,26 @@ struct ra_ext { u32 x, y; int score; ra_cnt c; };
 KS_DEV u32 ra_lane_above(u32 v, u32 none) { return (u32)__builtin_amdgcn_update_dpp((int)none, (int)v, 0x130, 0xf, 0xf, false); } // wave_shl:1
 KS_DEV u32 ra_bias(int v) { return (u32)v ^ 0x80000000u; } // order-preserving i32 -> u32
 KS_DEV int ra_unbias(u32 v) { return (int)(v ^ 0x80000000u); }
+
+// The E step of a row, the one copy of its tie rules (all lanes enter; o is wave-uniform).  Ht: the lane's H~, RA_NEG where
+// its cell does not exist (ex); ke = lane * e.  E is the best H~ of a lower lane, its gap paid by the lane distance: one
+// inclusive max scan of H~ + ke, moved one lane up.  gap: the lane takes it (on a tie H~).  Where E came from is asked only in a
+// row where some lane takes it, behind the wave-uniform guard `if (__ballot(S.gap))` of the caller (all lanes enter
+// ra_e_src): the last lane below this one that attains the running maximum — a lane that equals it is a new record under >=:
+// the largest lane wins a tie; lane 0 always is one.
+struct ra_e { int E; bool gap; u32 key, inc; };
+KS_DEV ra_e ra_e_step(int Ht, u32 lane, int ke, int o, bool ex) {
+    ra_e S;
+    S.key = ra_bias(Ht + ke); S.inc = ks_wave_incl_max(S.key);
+    const u32 below = ks_lane_below(S.inc); // (a DPP move: outside every per-lane condition, all lanes take part)
+    S.E = lane ? ra_unbias(below) - o - ke : RA_NEG;
+    S.gap = ex && S.E > Ht;
+    return S;
+}
+KS_DEV u32 ra_e_src(const ra_e &S, u32 lane) {
+    const u64 rec = __ballot(S.key == S.inc) & ks_lanes_below(lane);
+    return 63u - (u32)__clzll((long long)(rec | 1ULL));
+}
 
 // One side's extension (all 64 lanes enter; every argument but `lane` and `strip` is wave-uniform).  Q_x = qp[sgn * x] for
 // x = 1 .. X and T_y = tp[sgn * y] for y = 1 .. Y: the caller points qp / tp at the anchor pair.  strip: the wave's own.
@@ -123,24 +148,17 @@ KS_DEV ra_ext ra_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 X, u32 Y, const
             ra_cnt Htc = {diag ? Hc.id + (idt ? 1u : 0u) : Fnc.id, diag ? Hc.po + (s > 0 ? 1u : 0u) : Fnc.po, diag ? Hc.go : Fnc.go,
                           diag ? Hc.ga : Fnc.ga};
             if (!ex) Ht = RA_NEG;
-            // E: the best H~ of a lower lane, its gap paid by the lane distance; on a tie the largest lane
-            const u32 key = ra_bias(Ht + (int)ke), inc = ks_wave_incl_max(key);
-            const u32 below = ks_lane_below(inc); // (a DPP move: outside every per-lane condition, all lanes take part)
-            const int E = lane ? ra_unbias(below) - o - (int)ke : RA_NEG;
-            const bool gap = ex && E > Ht; // (on a tie H~)
+            const ra_e S = ra_e_step(Ht, lane, (int)ke, o, ex);
             H = Ht; Hc = Htc;
             u32 code = (diag ? RA_DIR_DIAG : 0u) | (cont ? RA_DIR_CONT : 0u);
-            if (__ballot(gap)) {
-                // the source: the last lane below this one that attains the running maximum (a lane that equals it is a new
-                // record under >=: the largest lane wins a tie; lane 0 always is one)
-                const u64 rec = __ballot(key == inc) & ks_lanes_below(lane);
-                const u32 src = 63u - (u32)__clzll((long long)(rec | 1ULL));
+            if (__ballot(S.gap)) {
+                const u32 src = ra_e_src(S, lane);
                 if (TR) {
-                    if (gap) { H = E; code |= (lane - src) << RA_DIR_E; }
-                } else {
+                    if (S.gap) { H = S.E; code |= (lane - src) << RA_DIR_E; }
+                } else { // the counts of the path into the source
                     const u32 sid = (u32)__shfl((int)Htc.id, (int)src), spo = (u32)__shfl((int)Htc.po, (int)src);
                     const u32 sgo = (u32)__shfl((int)Htc.go, (int)src), sga = (u32)__shfl((int)Htc.ga, (int)src);
-                    if (gap) { H = E; Hc = {sid, spo, sgo + 1u, sga + (lane - src)}; }
+                    if (S.gap) { H = S.E; Hc = {sid, spo, sgo + 1u, sga + (lane - src)}; }
                 }
             }
             F = Fn; Fc = Fnc;

@@ -28,9 +28,23 @@ KS_DEV u32 rk_class(u32 x) {
     return c - 'A' < 26u ? c - 'A' : c == '*' ? 26u : 27u;
 }
 // the class table (256 B) and the matrix (RK_A * RK_A B) into LDS, by a workgroup of 256 threads; the caller synchronises
-KS_DEV void rk_stage_tables(const rk_in &I, u8 *s_cls, signed char *s_M) {
+KS_DEV void rk_stage_tables(const signed char *matrix, u8 *s_cls, signed char *s_M) {
     s_cls[threadIdx.x] = (u8)rk_class(threadIdx.x);
-    for (u32 i = threadIdx.x; i < RK_A * RK_A; i += 256) s_M[i] = I.matrix[i];
+    for (u32 i = threadIdx.x; i < RK_A * RK_A; i += 256) s_M[i] = matrix[i];
+}
+
+// Sequences q < I.n_q and t < I.n_t — the caller has checked the two ids — of the batches of I (any struct with q_offs, t_offs,
+// n_q_res, n_t_res): their first residues in the batches and their lengths.  ok: both lie inside their batches.  UNIFORM: q
+// and t are wave-uniform and every value comes back in scalar registers; a pass with a thread per item asks without it.
+struct rk_seqs { u64 qb, tb, Lq, Lt; bool ok; };
+template <bool UNIFORM, class In> KS_DEV rk_seqs rk_row_seqs(const In &I, u32 q, u32 t) {
+    rk_seqs S;
+    S.qb = I.q_offs[q]; S.tb = I.t_offs[t];
+    u64 qe = I.q_offs[q + 1], te = I.t_offs[t + 1];
+    if (UNIFORM) { S.qb = rk_readfirst64(S.qb); S.tb = rk_readfirst64(S.tb); qe = rk_readfirst64(qe); te = rk_readfirst64(te); }
+    S.ok = S.qb <= qe && qe <= I.n_q_res && S.tb <= te && te <= I.n_t_res;
+    S.Lq = qe - S.qb; S.Lt = te - S.tb;
+    return S;
 }
 
 // Region g (wave-uniform; every value comes back in scalar registers): its hit row — the last row whose offset is <= g: rows
@@ -50,11 +64,9 @@ KS_DEV rk_at rk_locate(const rk_in &I, u32 g) {
     P.ok = q < I.n_q && t < I.n_t;
     P.qb = P.tb = P.Lq = P.Lt = 0;
     if (P.ok) {
-        P.qb = rk_readfirst64(I.q_offs[q]); P.tb = rk_readfirst64(I.t_offs[t]);
-        const u64 qe = rk_readfirst64(I.q_offs[q + 1]), te = rk_readfirst64(I.t_offs[t + 1]);
-        P.ok = P.qb <= qe && qe <= I.n_q_res && P.tb <= te && te <= I.n_t_res;
-        P.Lq = qe - P.qb; P.Lt = te - P.tb;
-        P.ok = P.ok && P.Lq <= 0xffffffffULL && P.Lt <= 0xffffffffULL && (u64)P.a + P.n <= P.Lq && (u64)P.b + P.n <= P.Lt;
+        const rk_seqs S = rk_row_seqs<true>(I, q, t);
+        P.qb = S.qb; P.tb = S.tb; P.Lq = S.Lq; P.Lt = S.Lt;
+        P.ok = S.ok && P.Lq <= 0xffffffffULL && P.Lt <= 0xffffffffULL && (u64)P.a + P.n <= P.Lq && (u64)P.b + P.n <= P.Lt;
     }
     return P;
 }

@@ -72,7 +72,7 @@ KS_DEV rs_ext rs_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 e_max, u32 x_dr
 __global__ __launch_bounds__(RS_THREADS) void k_rscore(rs_args A) {
     __shared__ u8 s_cls[256];
     __shared__ signed char s_M[RS_A * RS_A];
-    rk_stage_tables(A.in, s_cls, s_M);
+    rk_stage_tables(A.in.matrix, s_cls, s_M);
     __syncthreads();
     const u32 lane = threadIdx.x & 63;
     const u64 g64 = (u64)blockIdx.x * (RS_THREADS / 64) + ks_readfirst(threadIdx.x >> 6);

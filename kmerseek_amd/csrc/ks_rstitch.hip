@@ -11,33 +11,25 @@
 //            two exclusive scans (ks_prims.hip) lay both out, one wait brings the totals and the first refused member.
 //   slices   consecutive members whose directions fit the scratch budget run in one launch (as ks_rtrace.hip does).
 //   fill     k_rs_fill, a wave per filled link.  Lane y holds column y of T, the SHORTER stretch (0 .. |T| <= 63); a step is one
-//            row x of Q.  H and F stay in registers: F is the lane's own, D reads the H of the lane below (DPP), E is the kit's
-//            inclusive max scan of H~ + lane * e with the source lane from one ballot (the largest lane on a tie).  Q's residues
-//            are staged 64 rows at a time (a lane per row, a readlane per step), T's class and upper-cased byte are loaded once.
-//            One direction byte per cell; then the wave walks back from (|Q|, |T|) through RS_STAGE rows of directions at a time
-//            in its own LDS, writing one byte per column backward into the link's column slot.  `swap` (the query stretch is T)
-//            exchanges the two gap codes and the matrix index: one program, the orientation is part of the contract.  With
-//            KS_RSTITCH_EQX the pairs become = / X in a pass over the finished columns.
+//            row x of Q.  H and F stay in registers: F is the lane's own, D reads the H of the lane below (DPP), E is ra_e_step of
+//            ks_ralign_kit.h: the tie rules of ks_regions_align, not a copy of them.  Q's residues are staged 64 rows at a time (a
+//            lane per row, a readlane per step), T's class is loaded once.  One direction byte per cell (RA_DIR_*), rp_publish,
+//            then the wave walks back from (|Q|, |T|) — rp_walk<true> of ks_rpath_kit.h — writing one byte per column backward
+//            into the link's column slot.  `swap` (the query stretch is T) exchanges the two gap codes and the matrix index:
+//            one program, the orientation is part of the contract.  With KS_RSTITCH_EQX the pairs become = / X in a pass over
+//            the finished columns (rp_places).
 //            32-bit scores: at most 4096 + 63 steps of |M| <= 128 and gaps of at most 255 + 255 per residue.
 //   emit     k_rs_emit<false / true>, a thread per hit row: the pieces of the row in order — member ops from the first kept
 //            one, link runs or the link's columns — through one run merger; once to count the ops (and the row's link
 //            counts and span), a scan — its output IS op_offsets — and once to write len << 4 | code.
 //   rescore  k_rs_rescore, a wave per hit row: the final ops replayed on the residues, the pairs of an op 64 at a time.
-#include "ks_ralign_kit.h"
-#include <vector>
+#include "ks_rpath_kit.h"
 
 #define RS_THREADS 256
-#define RS_STAGE 64       // rows of directions a walk stages at once (ks_debug_rstitch_stage)
 #define RS_SHORT_MAX 63u  // the shorter side of a filled rectangle: column 0 .. 63 are the lanes
 #define RS_MAX_FILL 4096u
-#define RS_DIR_ROW 64u
-#define RS_DIAG 1u        // H~(x, y) took D
-#define RS_CONT 2u        // F(x, y) continued F(x - 1, y)
-#define RS_E 2            // >> RS_E: 0, or the E jump of H(x, y): d target columns, from H~(x, y - d)
-enum : u32 { RS_M = 0, RS_I = 1, RS_D = 2, RS_EQ = 7, RS_X = 8 };
 enum : u32 { RS_BAD_SRC = 0, RS_BAD_ROW = 1, RS_BAD_LEN = 2, RS_BAD_EXT = 3, RS_BAD_OPS = 4, RS_BAD_CODE = 5, RS_BAD_ASC = 6, RS_BAD_WALK = 7, RS_N_BAD = 8 };
 enum : u32 { RS_L_NONE = 0, RS_L_I = 1, RS_L_D = 2, RS_L_FILL = 3, RS_L_FILL_SWAP = 4, RS_L_OPEN = 5 };
-static_assert(RS_STAGE * RS_DIR_ROW == 64 * 4 * 16, "a stage is four 16-byte loads per lane");
 
 // per chain member: its trim and the link in front of it
 struct rs_link {
@@ -63,22 +55,9 @@ struct rs_args {
     unsigned long long *bad;
 };
 
-KS_DEV bool rs_is_pair(u32 c) { return c == RS_M || c == RS_EQ || c == RS_X; }
+KS_DEV bool rs_is_pair(u32 c) { return c == RP_M || c == RP_EQ || c == RP_X; }
 KS_DEV u32 rs_even(u32 v) { return (v + 1u) & ~1u; }
 KS_DEV double rs_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
-
-// the two sequences of hit row r: first residues in the batches and lengths; ok: they lie inside the batches
-struct rs_seq { u64 qb, tb, Lq, Lt; bool ok; };
-KS_DEV rs_seq rs_row_seqs(const rs_args &A, u32 r) {
-    rs_seq S{0, 0, 0, 0, false};
-    const u32 q = A.qid[r], t = A.tid[r];
-    if (q >= A.n_q || t >= A.n_t) return S;
-    S.qb = A.q_offs[q]; S.tb = A.t_offs[t];
-    const u64 qe = A.q_offs[q + 1], te = A.t_offs[t + 1];
-    S.ok = S.qb <= qe && qe <= A.n_q_res && S.tb <= te && te <= A.n_t_res;
-    S.Lq = qe - S.qb; S.Lt = te - S.tb;
-    return S;
-}
 
 __global__ __launch_bounds__(RS_THREADS) void k_rs_plan(rs_args A, rs_link *links, u32 *rows, u32 *ncols) {
     const u64 j64 = (u64)blockIdx.x * RS_THREADS + threadIdx.x;
@@ -91,7 +70,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_plan(rs_args A, rs_link *link
         const bool first = A.c_offs[r] == j;
         const u32 g = A.c_src[j];
         if (g >= A.n_regions || g < A.a_offs[r] || g >= A.a_offs[r + 1]) { ks_first_bad(A.bad, RS_BAD_SRC, j); return; }
-        const rs_seq S = rs_row_seqs(A, r);
+        const u32 q = A.qid[r], t = A.tid[r];
+        if (q >= A.n_q || t >= A.n_t) { ks_first_bad(A.bad, RS_BAD_ROW, r); return; }
+        const rk_seqs S = rk_row_seqs<false>(A, q, t);
         if (!S.ok) { ks_first_bad(A.bad, RS_BAD_ROW, r); return; }
         if (S.Lq > RA_MAX_LEN || S.Lt > RA_MAX_LEN) { ks_first_bad(A.bad, RS_BAD_LEN, r); return; }
         const u64 qs = A.a_qs[g], ql = A.a_ql[g], ts = A.a_ts[g], tl = A.a_tl[g];
@@ -113,9 +94,9 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_plan(rs_args A, rs_link *link
         for (u32 k = 0; k < nops; k++) {
             const u32 op = A.g_ops[ob + k], len = op >> 4, code = op & 15u;
             const bool pair = rs_is_pair(code);
-            if (!pair && code != RS_I && code != RS_D) bad_op = true;
-            if (pair && (A.eqx ? code == RS_M : code != RS_M)) bad_code = true;
-            const u64 dq = pair || code == RS_I ? 1u : 0u, dt = pair || code == RS_D ? 1u : 0u;
+            if (!pair && code != RP_I && code != RP_D) bad_op = true;
+            if (pair && (A.eqx ? code == RP_M : code != RP_M)) bad_code = true;
+            const u64 dq = pair || code == RP_I ? 1u : 0u, dt = pair || code == RP_D ? 1u : 0u;
             cq += len * dq; ct += len * dt;
             if (done) continue;
             const u64 needq = qpos >= pqe ? 0 : pqe - qpos, needt = tpos >= pte ? 0 : pte - tpos;
@@ -145,13 +126,6 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_plan(rs_args A, rs_link *link
     links[j] = L; rows[j] = nr; ncols[j] = nc;
 }
 
-// the directions a lane stores are read back by other lanes of the SAME wave and by nobody else (ks_rtrace.hip: publish)
-KS_DEV void rs_publish() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
 struct rs_slice {
     const u64 *dir_off, *col_off; // n_chained + 1: rows of directions / columns before member j
     u8 *dir, *cols;
@@ -162,9 +136,8 @@ struct rs_slice {
 __global__ __launch_bounds__(RS_THREADS) void k_rs_fill(rs_args A, rs_link *links, rs_slice Z) {
     __shared__ u8 s_cls[256];
     __shared__ signed char s_M[RK_A * RK_A];
-    __shared__ uint4 s_stage[RS_THREADS / 64][RS_STAGE * RS_DIR_ROW / 16];
-    s_cls[threadIdx.x] = (u8)rk_class(threadIdx.x);
-    for (u32 i = threadIdx.x; i < RK_A * RK_A; i += RS_THREADS) s_M[i] = A.matrix[i];
+    __shared__ uint4 s_stage[RS_THREADS / 64][RP_STAGE * RA_DIR_ROW / 16];
+    rk_stage_tables(A.matrix, s_cls, s_M);
     __syncthreads();
     const u32 lane = threadIdx.x & 63, wave = ks_readfirst(threadIdx.x >> 6);
     const u64 j64 = (u64)Z.j0 + (u64)blockIdx.x * (RS_THREADS / 64) + wave;
@@ -182,7 +155,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_fill(rs_args A, rs_link *link
     const u32 q = ks_readfirst(A.qid[r]), t = ks_readfirst(A.tid[r]);
     const u8 *const qst = A.q_res + rk_readfirst64(A.q_offs[q]) + pqe, *const tst = A.t_res + rk_readfirst64(A.t_offs[t]) + pte;
     const u8 *const Qs = swap ? tst : qst, *const Ts = swap ? qst : tst;
-    u8 *const dir = Z.dir + (rk_readfirst64(Z.dir_off[j]) - Z.dir_base) * RS_DIR_ROW;
+    u8 *const dir = Z.dir + (rk_readfirst64(Z.dir_off[j]) - Z.dir_base) * RA_DIR_ROW;
     const u32 cap = X + Y;
     u8 *const col = Z.cols + rk_readfirst64(Z.col_off[j]);
 
@@ -208,89 +181,37 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_fill(rs_args A, rs_link *link
             const bool diag = D >= Fn; // (on a tie D)
             int Ht = diag ? D : Fn;
             if (!ex) Ht = RA_NEG;
-            const u32 key = ra_bias(Ht + ke), inc = ks_wave_incl_max(key);
-            const u32 below = ks_lane_below(inc);
-            const int E = lane ? ra_unbias(below) - o - ke : RA_NEG;
-            const bool gap = ex && E > Ht; // (on a tie H~)
-            u32 code = (diag ? RS_DIAG : 0u) | (cont ? RS_CONT : 0u);
+            const ra_e S = ra_e_step(Ht, lane, ke, o, ex);
+            u32 code = (diag ? RA_DIR_DIAG : 0u) | (cont ? RA_DIR_CONT : 0u);
             H = Ht;
-            if (__ballot(gap)) { // the source: the last lane below that attains the running maximum
-                const u64 rec = __ballot(key == inc) & ks_lanes_below(lane);
-                const u32 src = 63u - (u32)__clzll((long long)(rec | 1ULL));
-                if (gap) { H = E; code |= (lane - src) << RS_E; }
+            if (__ballot(S.gap)) {
+                const u32 src = ra_e_src(S, lane);
+                if (S.gap) { H = S.E; code |= (lane - src) << RA_DIR_E; }
             }
             F = Fn;
             if (!ex) { H = RA_NEG; F = RA_NEG; }
-            dir[(u64)(x - 1) * RS_DIR_ROW + lane] = (u8)code;
+            dir[(u64)(x - 1) * RA_DIR_ROW + lane] = (u8)code;
         }
     }
-    rs_publish();
+    rp_publish();
 
-    // back from (nQ, nT): wave-uniform; the columns go backward from col[cap - 1]
-    const u32 op_e = swap ? RS_I : RS_D, op_f = swap ? RS_D : RS_I;
-    u32 x = nQ, y = nT, n = 0;
-    bool inF = false, bad = false;
-    auto put = [&](u32 op, u32 cnt) { // cnt <= 63 equal columns
-        if (cnt > cap - n) { bad = true; return; }
-        if (lane < cnt) col[cap - 1u - (n + lane)] = (u8)op;
-        n += cnt;
-    };
-    uint4 *const stage = s_stage[wave];
-    const u8 *const st = (const u8 *)stage;
-    while (x > 0 && !bad) {
-        const u32 cb = (x - 1) & ~(RS_STAGE - 1u), n_rows = x - cb; // rows cb + 1 .. x
-        const uint4 *src = (const uint4 *)(dir + (u64)cb * RS_DIR_ROW);
-        __builtin_amdgcn_wave_barrier();
-#pragma unroll
-        for (u32 h = 0; h < 4; h++) {
-            const u32 i = h * 64 + lane;
-            if (i < n_rows * (RS_DIR_ROW / 16)) stage[i] = src[i];
-        }
-        __builtin_amdgcn_wave_barrier();
-        while (x > cb && !bad) {
-            const u8 *row = st + (x - 1 - cb) * RS_DIR_ROW;
-            if (!inF) {
-                u32 b = row[y];
-                const u32 d = b >> RS_E;
-                if (d) {
-                    if (d > y) { bad = true; break; }
-                    put(op_e, d);
-                    y -= d;
-                    b = row[y];
-                }
-                if (b & RS_DIAG) {
-                    if (y == 0) { bad = true; break; }
-                    put(RS_M, 1u); x -= 1; y -= 1;
-                    continue;
-                }
-                inF = true;
-            }
-            inF = (row[y] & RS_CONT) != 0; // F(x, y): one residue of Q, from F(x - 1, y) or H(x - 1, y)
-            put(op_f, 1u);
-            x -= 1;
-        }
-    }
-    if (inF) bad = true;          // (row 0 has no F)
-    if (!bad && y > 0) put(op_e, y); // H(0, y) is an E of y columns from (0, 0)
-    if (bad) {
+    // back from (nQ, lane nT) to (0, lane 0); the columns go backward from col[cap - 1]
+    const u32 n = rp_walk<true>(dir, nQ, nT, 0u, RS_SHORT_MAX, swap ? RP_I : RP_D, swap ? RP_D : RP_I, col, -1, cap, s_stage[wave], lane);
+    if (n == RP_BAD) {
         if (lane == 0) { ks_first_bad(A.bad, RS_BAD_WALK, j); links[j].ncol = 0; }
         return;
     }
     if (lane == 0) links[j].ncol = n;
     if (!A.eqx) return;
-    rs_publish();
+    rp_publish();
     u8 *const path = col + (cap - n);
     u32 nq = 0, nt = 0;
     for (u32 c = 0; c < n; c += 64) {
         const u32 i = c + lane;
         const bool valid = i < n;
         const u32 code = valid ? path[i] : 0xffu;
-        const u64 mq = __ballot(valid && code != RS_D), mt = __ballot(valid && code != RS_I);
-        if (code == RS_M) {
-            const u32 qi = nq + (u32)__popcll(mq & ks_lanes_below(lane)), ti = nt + (u32)__popcll(mt & ks_lanes_below(lane));
-            if (qi < X && ti < Y) path[i] = (u8)(rk_upper(qst[qi]) == rk_upper(tst[ti]) ? RS_EQ : RS_X);
-        }
-        nq += (u32)__popcll(mq); nt += (u32)__popcll(mt);
+        const rp_place at = rp_places(valid, code, lane, nq, nt);
+        if (code == RP_M && at.q < X && at.t < Y) path[i] = (u8)(rk_upper(qst[at.q]) == rk_upper(tst[at.t]) ? RP_EQ : RP_X);
     }
 }
 
@@ -328,9 +249,9 @@ template <bool WRITE> __global__ __launch_bounds__(RS_THREADS) void k_rs_emit(rs
         const u32 g = A.c_src[j];
         n_trim += L.trim;
         if (j > b) {
-            if (L.cls == RS_L_I) push(RS_I, L.X);
-            else if (L.cls == RS_L_D) push(RS_D, L.Y);
-            else if (L.cls == RS_L_OPEN) { push(RS_I, L.X); push(RS_D, L.Y); n_open++; }
+            if (L.cls == RS_L_I) push(RP_I, L.X);
+            else if (L.cls == RS_L_D) push(RP_D, L.Y);
+            else if (L.cls == RS_L_OPEN) { push(RP_I, L.X); push(RP_D, L.Y); n_open++; }
             else if (L.cls == RS_L_FILL || L.cls == RS_L_FILL_SWAP) {
                 const u8 *path = Z.cols + Z.col_off[j] + (L.X + L.Y - L.ncol);
                 for (u32 c = 0; c < L.ncol; c++) push(path[c], 1u);
@@ -373,8 +294,7 @@ KS_DEV u32 rs_wave_sum(u32 v) {
 __global__ __launch_bounds__(RS_THREADS) void k_rs_rescore(rs_args A, rs_cols Z) {
     __shared__ u8 s_cls[256];
     __shared__ signed char s_M[RK_A * RK_A];
-    s_cls[threadIdx.x] = (u8)rk_class(threadIdx.x);
-    for (u32 i = threadIdx.x; i < RK_A * RK_A; i += RS_THREADS) s_M[i] = A.matrix[i];
+    rk_stage_tables(A.matrix, s_cls, s_M);
     __syncthreads();
     const u32 lane = threadIdx.x & 63, wave = ks_readfirst(threadIdx.x >> 6);
     const u64 r64 = (u64)blockIdx.x * (RS_THREADS / 64) + wave;
@@ -402,7 +322,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_rescore(rs_args A, rs_cols Z)
                 qp += len; tp += len;
             } else {
                 opens++; gaps += len; gap_cost += (i64)A.o + (i64)len * A.e;
-                if (code == RS_I) qp += len; else tp += len;
+                if (code == RP_I) qp += len; else tp += len;
             }
         }
     }
@@ -483,31 +403,18 @@ int ks_regions_stitch_impl(ks_ctx *ctx, const ks_rchain *K, const ks_raligns *S,
                            (unsigned long long)ctl[RS_BAD_ASC]);
         const u64 total_rows = rb[0], total_cols = rb[1];
 
-        // slices of consecutive members whose directions fit the budget (ks_rtrace.hip)
-        const u64 budget_rows = (max_scratch_bytes ? max_scratch_bytes : (u64)1 << 30) / RS_DIR_ROW;
-        std::vector<u64> cut{0}, first_row{0};
-        u64 slice_rows = total_rows;
-        if (total_rows <= budget_rows) cut.push_back(nm);
-        else {
-            std::vector<u64> off((size_t)nm + 1);
-            KS_TRY(ks_copy_d2h(ctx, off.data(), dir_off, off.size() * sizeof(u64)));
-            slice_rows = 0;
-            for (u64 j0 = 0; j0 < nm;) {
-                u64 j1 = j0;
-                while (j1 < nm && off[j1 + 1] - off[j0] <= budget_rows) j1++;
-                if (j1 == j0)
-                    return ks_fail(ctx, KS_ERR_CAPACITY, "region stitch: the link in front of chain member %llu needs %llu bytes of directions, max_scratch_bytes allows %llu",
-                                   (unsigned long long)j0, (unsigned long long)((off[j0 + 1] - off[j0]) * RS_DIR_ROW),
-                                   (unsigned long long)(budget_rows * RS_DIR_ROW));
-                if (off[j1] - off[j0] > slice_rows) slice_rows = off[j1] - off[j0];
-                cut.push_back(j1);
-                if (j1 < nm) first_row.push_back(off[j1]);
-                j0 = j1;
-            }
-        }
-        KS_TRY(sc.alloc(&dir, (size_t)(slice_rows * RS_DIR_ROW)));
+        // slices of consecutive members whose directions fit the budget
+        const u64 budget_rows = (max_scratch_bytes ? max_scratch_bytes : (u64)1 << 30) / RA_DIR_ROW;
+        rp_slices Sl;
+        KS_TRY(rp_slices_of(ctx, dir_off, nm, total_rows, budget_rows, &Sl));
+        if (Sl.bad < nm)
+            return ks_fail(ctx, KS_ERR_CAPACITY, "region stitch: the link in front of chain member %llu needs %llu bytes of directions, max_scratch_bytes allows %llu",
+                           (unsigned long long)Sl.bad, (unsigned long long)(Sl.bad_rows * RA_DIR_ROW), (unsigned long long)(budget_rows * RA_DIR_ROW));
+        const std::vector<u64> &cut = Sl.cut, &first_row = Sl.first_row;
+        const u64 slice_rows = Sl.max_rows;
+        KS_TRY(sc.alloc(&dir, (size_t)(slice_rows * RA_DIR_ROW)));
         KS_TRY(sc.alloc(&cols, (size_t)total_cols));
-        R->dir_bytes = slice_rows * RS_DIR_ROW; R->n_slices = (u32)(cut.size() - 1);
+        R->dir_bytes = slice_rows * RA_DIR_ROW; R->n_slices = (u32)(cut.size() - 1);
         if (total_rows)
             for (size_t i = 0; i + 1 < cut.size(); i++) { // (one block for all slices: the launches are ordered by the stream)
                 const rs_slice Z{dir_off, col_off, dir, cols, first_row[i], (u32)cut[i], (u32)cut[i + 1]};
@@ -535,4 +442,4 @@ int ks_regions_stitch_impl(ks_ctx *ctx, const ks_rchain *K, const ks_raligns *S,
     return ks_stream_wait(ctx);
 }
 
-extern "C" uint32_t ks_debug_rstitch_stage(void) { return RS_STAGE; }
+extern "C" uint32_t ks_debug_rstitch_stage(void) { return RP_STAGE; }

@@ -10,34 +10,20 @@
 //   slices   consecutive regions whose directions fit the scratch budget run in one launch; the launches of a call share one
 //            block of the context's pool, in stream order.  A region's slot is rows of RA_DIR_ROW bytes, the right extension's
 //            then the left one's, each an even number of rows: a slot begins on a 128-byte line and shares none.
-//   trace    k_rt_trace, a wave per region, lanes as diagonals.  Per side: forward rows 1 .. x_end, then the walk.  The walk is
-//            serial and wave-uniform (every lane computes the same steps): RT_STAGE rows of directions at a time come into the
-//            wave's own LDS with four 16-byte loads per lane, and the dependent chain of the walk is LDS reads only.  It
+//   trace    k_rt_trace, a wave per region, lanes as diagonals.  Per side: forward rows 1 .. x_end, rp_publish, then the walk —
+//            rp_walk<false> of ks_rpath_kit.h, which has the fence's argument, the stage and the bounds of every step.  It
 //            writes one byte per alignment column (M, I, D) into the region's column slot (an exclusive scan of aln_length):
 //            the left walk forward from column 0 — walking back from the left end cell IS forward sequence order — the right
-//            walk backward from column aln_length - 1, the anchor between them.  A walk can never leave its slot: every step
-//            is counted against the room left, every lane index against the band.
-//   publish  the directions a lane stores are read back by other lanes of the SAME wave and by nobody else.  Both go through
-//            the one vector-memory path of the wave's compute unit: its L1 is write-through and keeps a line it holds
-//            consistent with a store from its own CU (program order of a single work-item needs no less).  rt_publish orders
-//            them: a workgroup-scope release, an explicit s_waitcnt vmcnt(0) — every direction store is acknowledged by L2
-//            before the first load of the walk is issued — and a workgroup-scope acquire so that the compiler moves no load
-//            above it.  No agent-scope fence: no other CU reads these bytes in this launch, and the next launch starts
-//            with clean L1s.
+//            walk backward from column aln_length - 1, the anchor between them.
 //   verify   left columns + 1 + right columns == aln_length, and anchor + H(left end cell) + H(right end cell) == score: a
 //            ks_raligns used with other sequences than its own is refused, the first such region named.
 //   encode   k_rt_runs, a wave per region, 64 columns at a time: with KS_RTRACE_EQX an M column becomes = or X from the two
-//            residues (their places are ballot counts of the columns before); a run begins where a column differs from the one
+//            residues (rp_places); a run begins where a column differs from the one
 //            before.  Once to count the runs, a scan — its output IS op_offsets — and once to write len << 4 | op.
-#include "ks_ralign_kit.h"
-#include <vector>
+#include "ks_rpath_kit.h"
 
 #define RT_THREADS 256
-#define RT_STAGE 64 // rows of directions a walk stages at once
-#define RT_BAD 0xffffffffu
-enum : u32 { RT_M = 0, RT_I = 1, RT_D = 2, RT_EQ = 7, RT_X = 8 }; // BAM op codes
 enum : u32 { RT_BAD_ROW = 0, RT_BAD_LEN = 1, RT_BAD_ALN = 2, RT_BAD_WALK = 3, RT_N_BAD = 4 };
-static_assert(RT_STAGE * RA_DIR_ROW == 64 * 4 * 16, "a stage is four 16-byte loads per lane");
 
 struct rt_args {
     rk_in in;
@@ -85,61 +71,6 @@ __global__ __launch_bounds__(RT_THREADS) void k_rt_plan(rt_args A, u32 *rows, u3
     if (lane == 0) { rows[g] = nr; ncols[g] = nc; }
 }
 
-// (see `publish` above)
-KS_DEV void rt_publish() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-// The walk of one extension from its end cell (x, y) back to (0, 0) (all lanes enter, every argument but `lane` is wave-uniform
-// and so is every step).  dir: the extension's rows.  Columns go to col[0], col[step], col[2 * step] ...; at most `room` of
-// them.  -> the columns written, or RT_BAD: a step that leaves the band or the room, a walk that does not close.
-KS_DEV u32 rt_walk(const u8 *dir, u32 x, u32 y, u32 W, u8 *col, i64 step, u32 room, uint4 *stage, u32 lane) {
-    u32 k = y + W - x, n = 0; // the lane of the cell: 0 <= k <= 2W (rt_geometry)
-    bool inF = false, bad = false;
-    auto put = [&](u32 op, u32 cnt) { // cnt <= 63 equal columns
-        if (cnt > room - n) { bad = true; return; }
-        if (lane < cnt) col[step * (i64)(n + lane)] = (u8)op;
-        n += cnt;
-    };
-    const u8 *const st = (const u8 *)stage;
-    while (x > 0 && !bad) {
-        const u32 cb = (x - 1) & ~(RT_STAGE - 1u), n_rows = x - cb; // rows cb + 1 .. x
-        const uint4 *src = (const uint4 *)(dir + (u64)cb * RA_DIR_ROW);
-        __builtin_amdgcn_wave_barrier(); // (the steps before have read the stage; same wave: LDS operations execute in order)
-#pragma unroll
-        for (u32 j = 0; j < 4; j++) {
-            const u32 i = j * 64 + lane;
-            if (i < n_rows * (RA_DIR_ROW / 16)) stage[i] = src[i];
-        }
-        __builtin_amdgcn_wave_barrier();
-        while (x > cb && !bad) {
-            const u8 *row = st + (x - 1 - cb) * RA_DIR_ROW;
-            if (!inF) { // H(x, lane k)
-                u32 b = row[k];
-                const u32 d = b >> RA_DIR_E;
-                if (d) { // E: a jump of d target residues from the H~ of lane k - d
-                    if (d > k) { bad = true; break; }
-                    put(RT_D, d);
-                    k -= d;
-                    b = row[k];
-                }
-                if (b & RA_DIR_DIAG) { put(RT_M, 1u); x -= 1; continue; } // D: (x - 1, y - 1), the same lane
-                inF = true;
-            }
-            // F(x, lane k): one query residue, from lane k + 1 of the row before — its F again or its H
-            if (k >= 2 * W) { bad = true; break; }
-            inF = (row[k + 1] & RA_DIR_CONT) != 0;
-            put(RT_I, 1u);
-            x -= 1; k += 1;
-        }
-    }
-    if (bad || inF || k < W) return RT_BAD; // (row 0 has no F, and no cell below y = 0)
-    if (k > W) put(RT_D, k - W);            // H(0, y) is an E of y residues from (0, 0)
-    return bad ? RT_BAD : n;
-}
-
 struct rt_slice {
     const u64 *dir_off, *col_off; // n_regions + 1: rows of directions / columns before region g
     u8 *dir, *cols;
@@ -151,8 +82,8 @@ __global__ __launch_bounds__(RT_THREADS) void k_rt_trace(rt_args A, rt_slice Z) 
     __shared__ u8 s_cls[256];
     __shared__ signed char s_M[RK_A * RK_A];
     __shared__ unsigned short s_strip[RT_THREADS / 64][RA_STRIP];
-    __shared__ uint4 s_stage[RT_THREADS / 64][RT_STAGE * RA_DIR_ROW / 16];
-    rk_stage_tables(A.in, s_cls, s_M);
+    __shared__ uint4 s_stage[RT_THREADS / 64][RP_STAGE * RA_DIR_ROW / 16];
+    rk_stage_tables(A.in.matrix, s_cls, s_M);
     __syncthreads();
     const u32 lane = threadIdx.x & 63, wave = ks_readfirst(threadIdx.x >> 6);
     const u64 g64 = (u64)Z.g0 + (u64)blockIdx.x * (RT_THREADS / 64) + wave;
@@ -169,15 +100,16 @@ __global__ __launch_bounds__(RT_THREADS) void k_rt_trace(rt_args A, rt_slice Z) 
     const u32 cq = ks_readfirst(*qa), ct = ks_readfirst(*ta);
     const int s = s_M[s_cls[cq] * RK_A + s_cls[ct]];
     const ra_ext R = ra_extend<true>(qa, ta, 1, Lq - 1 - G.ai, Lt - 1 - G.bj, A, s_cls, s_M, s_strip[wave], lane, dR, G.xr, G.yr);
-    rt_publish();
-    const u32 nR = rt_walk(dR, G.xr, G.yr, A.W, col + (G.alen - 1), -1, G.alen - 1, s_stage[wave], lane);
-    bool ok = nR != RT_BAD;
+    rp_publish();
+    // (the lane of an end cell, y + W - x, is 0 .. 2W: rt_geometry)
+    const u32 nR = rp_walk<false>(dR, G.xr, G.yr + A.W - G.xr, A.W, 2 * A.W, RP_D, RP_I, col + (G.alen - 1), -1, G.alen - 1, s_stage[wave], lane);
+    bool ok = nR != RP_BAD;
     if (ok) {
         const ra_ext L = ra_extend<true>(qa, ta, -1, G.ai, G.bj, A, s_cls, s_M, s_strip[wave], lane, dL, G.xl, G.yl);
-        rt_publish();
-        const u32 nL = rt_walk(dL, G.xl, G.yl, A.W, col, 1, G.alen - 1 - nR, s_stage[wave], lane);
-        ok = nL != RT_BAD && nL + 1 + nR == G.alen && (i64)s + L.score + R.score == A.s_score[g];
-        if (ok && lane == 0) col[nL] = (u8)RT_M; // the anchor pair
+        rp_publish();
+        const u32 nL = rp_walk<false>(dL, G.xl, G.yl + A.W - G.xl, A.W, 2 * A.W, RP_D, RP_I, col, 1, G.alen - 1 - nR, s_stage[wave], lane);
+        ok = nL != RP_BAD && nL + 1 + nR == G.alen && (i64)s + L.score + R.score == A.s_score[g];
+        if (ok && lane == 0) col[nL] = (u8)RP_M; // the anchor pair
     }
     if (!ok && lane == 0) ks_first_bad(A.bad, RT_BAD_WALK, g);
 }
@@ -216,13 +148,11 @@ template <bool WRITE> __global__ __launch_bounds__(RT_THREADS) void k_rt_runs(rt
         const u32 i = c + lane;
         const bool valid = i < n;
         u32 code = valid ? col[i] : 0xffu;
-        const u64 mq = __ballot(valid && code != RT_D), mt = __ballot(valid && code != RT_I);
-        if (Z.eqx && code == RT_M) {
-            const u32 qi = nq + (u32)__popcll(mq & ks_lanes_below(lane)), ti = nt + (u32)__popcll(mt & ks_lanes_below(lane));
-            code = RT_X;
-            if (qi < G.ql && ti < G.tl && rk_upper(q[qi]) == rk_upper(t[ti])) code = RT_EQ; // (inside the extents: rt_geometry)
+        const rp_place at = rp_places(valid, code, lane, nq, nt);
+        if (Z.eqx && code == RP_M) {
+            code = RP_X;
+            if (at.q < G.ql && at.t < G.tl && rk_upper(q[at.q]) == rk_upper(t[at.t])) code = RP_EQ; // (inside the extents: rt_geometry)
         }
-        nq += (u32)__popcll(mq); nt += (u32)__popcll(mt);
         const u32 below = ks_lane_below(code); // (a DPP move: all lanes take part)
         const bool start = valid && code != (lane ? below : prev);
         const u64 mask = __ballot(start);
@@ -288,29 +218,15 @@ int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H
                        "anchor: alignments, regions and batches do not belong together", (unsigned long long)ctl[RT_BAD_ALN]);
     const u64 total_rows = rb[0], total_cols = rb[1];
 
-    // slices of consecutive regions whose directions fit the budget: `cut` holds their bounds, `first_row` dir_off of each
-    // slice's first region.  Only a call that does not fit in one slice brings the offsets to the host.
+    // slices of consecutive regions whose directions fit the budget
     const u64 budget_rows = (max_scratch_bytes ? max_scratch_bytes : (u64)1 << 30) / RA_DIR_ROW;
-    std::vector<u64> cut{0}, first_row{0};
-    u64 slice_rows = total_rows;
-    if (total_rows <= budget_rows) cut.push_back(ng);
-    else {
-        std::vector<u64> off((size_t)ng + 1);
-        KS_TRY(ks_copy_d2h(ctx, off.data(), dir_off, off.size() * sizeof(u64)));
-        slice_rows = 0;
-        for (u64 g0 = 0; g0 < ng;) {
-            u64 g1 = g0;
-            while (g1 < ng && off[g1 + 1] - off[g0] <= budget_rows) g1++;
-            if (g1 == g0)
-                return ks_fail(ctx, KS_ERR_CAPACITY, "region traceback: region %llu needs %llu bytes of directions, max_scratch_bytes allows %llu",
-                               (unsigned long long)g0, (unsigned long long)((off[g0 + 1] - off[g0]) * RA_DIR_ROW),
-                               (unsigned long long)(budget_rows * RA_DIR_ROW));
-            if (off[g1] - off[g0] > slice_rows) slice_rows = off[g1] - off[g0];
-            cut.push_back(g1);
-            if (g1 < ng) first_row.push_back(off[g1]);
-            g0 = g1;
-        }
-    }
+    rp_slices Sl;
+    KS_TRY(rp_slices_of(ctx, dir_off, ng, total_rows, budget_rows, &Sl));
+    if (Sl.bad < ng)
+        return ks_fail(ctx, KS_ERR_CAPACITY, "region traceback: region %llu needs %llu bytes of directions, max_scratch_bytes allows %llu",
+                       (unsigned long long)Sl.bad, (unsigned long long)(Sl.bad_rows * RA_DIR_ROW), (unsigned long long)(budget_rows * RA_DIR_ROW));
+    const std::vector<u64> &cut = Sl.cut, &first_row = Sl.first_row;
+    const u64 slice_rows = Sl.max_rows;
     u8 *dir = nullptr, *cols = nullptr;
     KS_TRY(sc.alloc(&dir, (size_t)(slice_rows * RA_DIR_ROW)));
     KS_TRY(sc.alloc(&cols, (size_t)total_cols));
@@ -336,4 +252,4 @@ int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H
     return ks_stream_wait(ctx);
 }
 
-extern "C" uint32_t ks_debug_rtrace_stage(void) { return RT_STAGE; }
+extern "C" uint32_t ks_debug_rtrace_stage(void) { return RP_STAGE; }

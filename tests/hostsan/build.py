@@ -80,6 +80,21 @@ def build(out_dir: str, which=("asan", "tsan"), verbose: bool = False) -> dict:
     return result
 
 
+def build_alone(out_dir: str, prog: str, san: str = "asan") -> str:
+    """A program of this directory that needs neither the product's objects nor the stand-in (san_slices: a header's host
+    half), with the same compiler, flags and runtime linkage as the others.  Returns its path, out_dir/<sanitizer>/<prog>."""
+    cxx, _ = compilers()
+    d = os.path.join(out_dir, san)
+    os.makedirs(d, exist_ok=True)
+    exe = os.path.join(d, prog)
+    static = [] if "clang" in os.path.basename(cxx) else STATIC_RUNTIME[san]
+    cmd = [cxx, "-O1", "-g", "-fno-omit-frame-pointer", "-std=c++17"] + SANITIZERS[san] + static + ["-o", exe, os.path.join(HERE, prog + ".cpp")]
+    p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    if p.returncode != 0:
+        raise RuntimeError("command failed: " + " ".join(cmd) + "\n" + p.stdout)
+    return exe
+
+
 if __name__ == "__main__":
     if len(sys.argv) < 2:
         sys.exit("usage: build.py OUT_DIR [asan|tsan ...]")
