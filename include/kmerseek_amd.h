@@ -998,6 +998,141 @@ void ks_hitalns_free(ks_hitalns *a);
 /* rows of directions one wave stages at once for the walk of a fill: the tests place rectangles around it */
 uint32_t ks_debug_rstitch_stage(void);
 
+/* ---- alignment statistics: bit scores and E-values per hit ------------------------------------------------------------------- */
+
+/* Every stage of the region pipeline ends in a raw integer score; these passes make it comparable across queries, databases
+ * and compositions (Karlin & Altschul 1990; composition-based statistics: Schaeffer et al. 2001, BLAST -comp_based_stats 1).
+ * The gapped (lambda, K) of a matrix and its gap costs cannot be derived here: the caller brings them, as it brings the matrix.
+ *
+ * 1. Residue composition of a batch.  The class of a byte is the one of ks_regions_score: after ASCII upper-casing A-Z are
+ *    0-25, '*' is 26, every other byte 27.  Result (device-resident): counts u32[n_seqs][28], length u32[n_seqs] and
+ *    totals u64[28] over the batch.  All integers: the result never depends on the path a sequence took — a wave per sequence
+ *    of at most wave_max residues, a workgroup with a private LDS histogram per sequence of at most group_max, a longer one
+ *    split over several workgroups that add to its 28 counters with integer atomics (KS_DEBUG_COMP_PATH = 1 | 2 | 3 sends every
+ *    sequence one way, read when the context is made and by ks_ctx_reload_debug_env; ks_debug_rcomp_limits gives the two
+ *    thresholds).  An empty batch and empty sequences are valid.  KS_ERR_INVALID_ARG: offsets that descend or pass n_res (the
+ *    first such sequence is named);  KS_ERR_CAPACITY: a sequence of 2^32 residues or more.  Built once per database and reused. */
+typedef struct ks_rcomp ks_rcomp;
+int ks_residue_composition_device(ks_ctx *ctx, const uint8_t *d_res, const uint64_t *d_offs, uint32_t n_seqs, uint64_t n_res,
+                                  ks_rcomp **out);
+uint32_t ks_rcomp_n_seqs(const ks_rcomp *c);
+uint64_t ks_rcomp_n_residues(const ks_rcomp *c);
+/* device pointers, valid until ks_rcomp_free */
+const uint32_t *ks_rcomp_device_counts(const ks_rcomp *c);
+const uint64_t *ks_rcomp_device_totals(const ks_rcomp *c);
+const uint32_t *ks_rcomp_device_length(const ks_rcomp *c);
+/* any destination may be NULL */
+int ks_rcomp_copy_to_host(ks_ctx *ctx, const ks_rcomp *c, uint32_t *counts, uint64_t *totals, uint32_t *length);
+void ks_rcomp_free(ks_rcomp *c);
+/* the longest sequence a wave takes and the longest one workgroup takes: the tests place lengths around them */
+void ks_debug_rcomp_limits(uint32_t *wave_max, uint32_t *group_max);
+
+/* 2. Ungapped Karlin-Altschul parameters, on the host, f64, no context.  matrix: 28 x 28 (the query's class is the row), NULL:
+ *    +1 / -1.  freq_q, freq_t: 28 non-negative weights each, of which only the 20 standard classes count (those of
+ *    ACDEFGHIKLMNPQRSTVWY), renormalised to 1 over them.  P(s) = the sum of fq[i] * ft[j] over the standard (i, j) with
+ *    M[i][j] = s.  lambda: the positive root of sum P(s) e^(lambda s) = 1.  H = lambda * sum s P(s) e^(lambda s).  K by the
+ *    series of Karlin & Altschul as BLAST evaluates it: delta = the gcd of the scores with P(s) > 0, scores divided by delta,
+ *    lambda' = lambda * delta, P_k the k-fold convolution of P,
+ *      sigma = sum over k >= 1 of (1 / k) * [sum over j < 0 of P_k(j) e^(lambda' j) + sum over j >= 0 of P_k(j)]
+ *      K = -exp(-2 sigma) / ((H / lambda') * expm1(-lambda'))
+ *    summed until a term falls below 2^-60, for at most 400 terms.  Any of lambda, K, H may be NULL.
+ *    KS_ERR_INVALID_ARG (ks_karlin_last_error, per thread, says which): NULL, negative or non-finite weights, or none on a
+ *    standard class; no positive score has positive probability; the expected score is >= 0; the 400 terms did not suffice
+ *    ("expected score too close to zero"). */
+int ks_karlin_ungapped(const int8_t *matrix, const double *freq_q, const double *freq_t, double *lambda, double *K, double *H);
+const char *ks_karlin_last_error(void);
+
+/* 3. The statistics of a column of scores: per hit row r = (q, t) a composition-based rescaling of the score, per entry (a
+ *    region, an alignment, a stitched hit) a bit score and an E-value.
+ *    Options: flags KS_ASTATS_NO_COMPOSITION | KS_ASTATS_PAIRWISE | KS_ASTATS_ALLOW_UNGAPPED;  matrix: HOST 28 x 28 or NULL
+ *    (+1 / -1; for ks_raligns_stats and ks_hitalns_stats NULL or byte-equal to the one recorded in `alignments`, which is
+ *    used);  lambda, K: both 0: the library's ungapped values, else both > 0: the caller's, typically gapped;  background: HOST
+ *    f64[28] or NULL: t_comp's totals;  ratio_min, ratio_max: 0 and 0 mean 0.5 and 1.0 (BLAST's bounds for the lambda ratio as
+ *    far as they can be restated; no parity is claimed);  db_residues, 0: the residues of t_comp;  db_seqs, 0: t_comp's
+ *    sequences;  length_adjust, default 0;  reserved 0.
+ *    ks_raligns_stats and ks_hitalns_stats refuse lambda == 0 without KS_ASTATS_ALLOW_UNGAPPED: ungapped parameters understate
+ *    gapped E-values, and nothing here does that silently.
+ *    Per call, on the host: smin and smax over the standard 20 x 20 block of the matrix (KS_ERR_INVALID_ARG if smax <= 0 or
+ *    smin >= 0);  lambda_std — and K_std where no parameters are given — from ks_karlin_ungapped(matrix, background,
+ *    background);  lambda_c, K_c: the caller's values, or those two.
+ *    Per hit row, exact: cq, ct = the standard-class counts of the two sequences;  h_s = the sum of cq[i] * ct[j] over the
+ *    standard (i, j) with M[i][j] = s, in u64;  N = sum h_s.  A row with a sequence of more than 2^20 residues is
+ *    KS_ERR_CAPACITY, so N <= 2^40 and every coefficient below is exact in f64.  The row is REGULAR when N > 0, sum s * h_s < 0
+ *    and some s > 0 has h_s > 0 — three integer tests.  For a regular row, with d = smax - smin,
+ *      f(x) = sum over s of h_s x^(smax - s)  -  N x^smax
+ *    — sum h_s x^(-s) = N, the equation of lambda_r in x = e^(-lambda_r), times x^smax: positive below the root, negative from
+ *    there to the trivial root 1 — (integer coefficients combined per power, then converted to f64), evaluated by Horner from the
+ *    highest power d down in f64, one rounding per operation, no contraction.  Bisection: lo = 0.0, hi = 1.0;  mid = 0.5 * (lo + hi), stop if mid == lo or
+ *    mid == hi or after 128 steps, f(mid) > 0 ? lo = mid : hi = mid;  x_r = lo — e^(-lambda_r) of the pair.  A row that is not
+ *    regular has status KS_ASTATS_ROW_FALLBACK and x_r = 0.0.  status and x are bit-identical to that loop on a host
+ *    (tests/astats_ref.py), whatever the launch geometry.
+ *    Per hit row, f64: lambda_r = -log(x_r);  ratio_r = min(max(lambda_r / lambda_std, ratio_min), ratio_max);  1 for fallback
+ *    rows, and for every row under KS_ASTATS_NO_COMPOSITION (status KS_ASTATS_ROW_SKIPPED, x = 0.0: no histogram is made, and
+ *    t_comp may be NULL when db_residues, db_seqs and background are given and KS_ASTATS_PAIRWISE is not; q_comp is always
+ *    needed: its lengths are m).
+ *    Per entry e of row r with score S:  S' = ratio_r * (double)S;  bit_score = (lambda_c * S' - ln K_c) / ln 2;
+ *      evalue = (K_c * (double)N_eff) * (double)m_eff * exp(-lambda_c * S'),  m_eff = max(Lq - length_adjust, 1),
+ *      N_eff = max(db_residues - db_seqs * length_adjust, 1) in saturating integers; with KS_ASTATS_PAIRWISE
+ *      N_eff = max(Lt - length_adjust, 1).  Lq, Lt: the length columns of the compositions.
+ *    Result (device-resident): per row status u8, x f64, lambda_ratio f64, row_bit_score f64 (the largest bit score of the
+ *    row's entries) and row_evalue f64 (the smallest E-value) — NaN for a row without entries; d_score columns for
+ *    ks_hits_best with KS_BEST_SCORE and the cluster passes;  per entry bit_score and evalue f64.  Scalars: lambda_std,
+ *    lambda_used, K_used, params_source (0 computed, 1 caller), n_fallback.
+ *    d_row_offsets: u64[n_rows + 1], the CSR of the n scores over the hit rows, or NULL: one score per hit row (n == n_rows).
+ *    KS_ERR_INVALID_ARG, before any device work and also with ctx == NULL: unknown flags, a non-zero reserved field, exactly
+ *    one of lambda and K set, negative or NaN lambda, K or ratios, ratio_min > ratio_max, the matrix conflict, the refusal of
+ *    ungapped parameters.  Then: NULL arguments; objects of another context; row counts that disagree with `hits`; a
+ *    row_offsets that is no CSR from 0 to n; a qid or tid beyond its composition (ks_last_error names the first such row).
+ *    One stream, synchronous on return, one host wait; all scratch comes from the context's pool. */
+typedef struct ks_astats ks_astats;
+#define KS_ASTATS_NO_COMPOSITION 1u
+#define KS_ASTATS_PAIRWISE 2u
+#define KS_ASTATS_ALLOW_UNGAPPED 4u
+#define KS_ASTATS_ROW_REGULAR 0u
+#define KS_ASTATS_ROW_FALLBACK 1u
+#define KS_ASTATS_ROW_SKIPPED 2u
+#define KS_ASTATS_MAX_SEQ_LEN (1u << 20)
+typedef struct ks_astats_opts {
+    uint32_t flags;         /* KS_ASTATS_* */
+    uint32_t length_adjust; /* taken off every sequence length; default 0 */
+    const int8_t *matrix;   /* HOST, 28 x 28; NULL: +1 / -1 */
+    double lambda, K;       /* both 0: the ungapped values of the matrix; else both > 0 */
+    const double *background; /* HOST, f64[28]; NULL: t_comp's totals */
+    double ratio_min, ratio_max; /* 0 and 0: 0.5 and 1.0 */
+    uint64_t db_residues;   /* 0: the residues of t_comp */
+    uint64_t db_seqs;       /* 0: the sequences of t_comp */
+    uint64_t reserved;      /* 0 */
+} ks_astats_opts;
+/* opts == NULL: the defaults */
+int ks_scores_stats_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const int64_t *d_score, uint64_t n_rows, uint64_t n,
+                           const ks_hits *hits, const ks_rcomp *q_comp, const ks_rcomp *t_comp, const ks_astats_opts *opts,
+                           ks_astats **out);
+int ks_rscores_stats(ks_ctx *ctx, const ks_rscores *scores, const ks_hits *hits, const ks_rcomp *q_comp, const ks_rcomp *t_comp,
+                     const ks_astats_opts *opts, ks_astats **out);
+int ks_raligns_stats(ks_ctx *ctx, const ks_raligns *alignments, const ks_hits *hits, const ks_rcomp *q_comp, const ks_rcomp *t_comp,
+                     const ks_astats_opts *opts, ks_astats **out);
+int ks_hitalns_stats(ks_ctx *ctx, const ks_hitalns *stitched, const ks_raligns *alignments, const ks_hits *hits, const ks_rcomp *q_comp,
+                     const ks_rcomp *t_comp, const ks_astats_opts *opts, ks_astats **out);
+uint64_t ks_astats_n_rows(const ks_astats *s);
+uint64_t ks_astats_n_entries(const ks_astats *s);
+uint64_t ks_astats_n_fallback(const ks_astats *s);
+double ks_astats_lambda_std(const ks_astats *s);
+double ks_astats_lambda_used(const ks_astats *s);
+double ks_astats_k_used(const ks_astats *s);
+uint32_t ks_astats_params_source(const ks_astats *s);
+/* device pointers, valid until ks_astats_free */
+const uint8_t *ks_astats_device_status(const ks_astats *s);
+const double *ks_astats_device_x(const ks_astats *s);
+const double *ks_astats_device_lambda_ratio(const ks_astats *s);
+const double *ks_astats_device_bit_score(const ks_astats *s);
+const double *ks_astats_device_evalue(const ks_astats *s);
+const double *ks_astats_device_row_bit_score(const ks_astats *s);
+const double *ks_astats_device_row_evalue(const ks_astats *s);
+/* any destination may be NULL */
+int ks_astats_copy_to_host(ks_ctx *ctx, const ks_astats *s, uint8_t *status, double *x, double *lambda_ratio, double *bit_score,
+                           double *evalue, double *row_bit_score, double *row_evalue);
+void ks_astats_free(ks_astats *s);
+
 /* ---- significance: does a hit's overlap mean anything? --------------------------------------------------------------------- */
 
 /* Replaces the two sums behind the columns that branchwater multisearch adds with "calculate probability of overlap between

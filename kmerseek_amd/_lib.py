@@ -102,6 +102,17 @@ class ks_rstitch_opts(C.Structure):
     _fields_ = [("max_fill", C.c_uint32), ("flags", C.c_uint32), ("max_scratch_bytes", C.c_uint64), ("reserved", C.c_uint32 * 2)]
 
 
+KS_ASTATS_NO_COMPOSITION, KS_ASTATS_PAIRWISE, KS_ASTATS_ALLOW_UNGAPPED = 1, 2, 4
+KS_ASTATS_ROW_REGULAR, KS_ASTATS_ROW_FALLBACK, KS_ASTATS_ROW_SKIPPED = 0, 1, 2
+KS_ASTATS_MAX_SEQ_LEN = 1 << 20
+
+
+class ks_astats_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("length_adjust", C.c_uint32), ("matrix", C.POINTER(C.c_int8)), ("lambda_", C.c_double),
+                ("K", C.c_double), ("background", C.POINTER(C.c_double)), ("ratio_min", C.c_double), ("ratio_max", C.c_double),
+                ("db_residues", C.c_uint64), ("db_seqs", C.c_uint64), ("reserved", C.c_uint64)]
+
+
 class ks_signif_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -363,6 +374,38 @@ SIGNATURES = {
     "ks_hitalns_copy_to_host": (C.c_int, [_vp] * 19),
     "ks_hitalns_free": (None, [_vp]),
     "ks_debug_rstitch_stage": (C.c_uint32, []),
+    "ks_residue_composition_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _pp]),
+    "ks_rcomp_n_seqs": (C.c_uint32, [_vp]),
+    "ks_rcomp_n_residues": (C.c_uint64, [_vp]),
+    "ks_rcomp_device_counts": (_vp, [_vp]),
+    "ks_rcomp_device_totals": (_vp, [_vp]),
+    "ks_rcomp_device_length": (_vp, [_vp]),
+    "ks_rcomp_copy_to_host": (C.c_int, [_vp] * 5),
+    "ks_rcomp_free": (None, [_vp]),
+    "ks_debug_rcomp_limits": (None, [_u32p, _u32p]),
+    "ks_karlin_ungapped": (C.c_int, [C.POINTER(C.c_int8), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                     C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ks_karlin_last_error": (C.c_char_p, []),
+    "ks_scores_stats_device": (C.c_int, [_vp, _vp, _vp, C.c_uint64, C.c_uint64, _vp, _vp, _vp, C.POINTER(ks_astats_opts), _pp]),
+    "ks_rscores_stats": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ks_astats_opts), _pp]),
+    "ks_raligns_stats": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(ks_astats_opts), _pp]),
+    "ks_hitalns_stats": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(ks_astats_opts), _pp]),
+    "ks_astats_n_rows": (C.c_uint64, [_vp]),
+    "ks_astats_n_entries": (C.c_uint64, [_vp]),
+    "ks_astats_n_fallback": (C.c_uint64, [_vp]),
+    "ks_astats_lambda_std": (C.c_double, [_vp]),
+    "ks_astats_lambda_used": (C.c_double, [_vp]),
+    "ks_astats_k_used": (C.c_double, [_vp]),
+    "ks_astats_params_source": (C.c_uint32, [_vp]),
+    "ks_astats_device_status": (_vp, [_vp]),
+    "ks_astats_device_x": (_vp, [_vp]),
+    "ks_astats_device_lambda_ratio": (_vp, [_vp]),
+    "ks_astats_device_bit_score": (_vp, [_vp]),
+    "ks_astats_device_evalue": (_vp, [_vp]),
+    "ks_astats_device_row_bit_score": (_vp, [_vp]),
+    "ks_astats_device_row_evalue": (_vp, [_vp]),
+    "ks_astats_copy_to_host": (C.c_int, [_vp] * 9),
+    "ks_astats_free": (None, [_vp]),
     "ks_corpus_build": (C.c_int, [_vp, _vp, _pp]),
     "ks_corpus_n_hashes": (C.c_uint64, [_vp]),
     "ks_corpus_n_docs": (C.c_uint32, [_vp]),

@@ -47,7 +47,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH) X(CULL_PATH) X(CHAIN_PATH)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH) X(CULL_PATH) X(CHAIN_PATH) X(COMP_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -349,13 +349,15 @@ enum : u32 {
     KS_PIN_RCHAIN = 246,     // 5 words, region chain: first row that breaks the CSR | first region with a length of 0 | with an end beyond 0xffffffff | with a score beyond 2^30 | chained regions (ks_rchain.hip)
     KS_PIN_RCHAIN_COV = 251, // 2 words, chain coverage: first row with an id beyond the batches | first row whose chain is longer than its sequence (ks_rchain.hip)
     KS_PIN_RSTITCH = 253,    // 11 words, region stitch: the eight first-offender words (ks_rstitch.hip: RS_BAD_*), then the scan totals: direction rows | columns | ops
-    KS_PIN_END = 264,
+    KS_PIN_RCOMP = 264,      // 2 words, residue composition: first sequence whose offsets descend or pass the batch | first sequence of 2^32 residues or more (ks_astats.hip)
+    KS_PIN_ASTATS = 266,     // 4 words, alignment statistics: first row that breaks the CSR | with an id beyond its composition | with a sequence too long | fallback rows (ks_astats.hip)
+    KS_PIN_END = 270,
 };
 #define KS_PIN_WORDS 272
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -572,6 +574,32 @@ struct ks_hitalns {
 // ks_regions_stitch behind its argument checks (options validated, defaults filled in; K, S, G, H: of ctx, equal counts)
 int ks_regions_stitch_impl(ks_ctx *ctx, const ks_rchain *K, const ks_raligns *S, const ks_cigars *G, const ks_hits *H, const ks_res_batch &Q,
                            const ks_res_batch &T, u32 max_fill, u32 flags, u64 max_scratch_bytes, ks_hitalns *R);
+
+// the residue classes of the sequences of a batch, counted (ks_astats.hip)
+struct ks_rcomp {
+    ks_ctx *ctx;
+    u32 n_seqs;
+    u64 n_res;
+    u32 *d_counts;  // n_seqs x KS_RSCORE_ALPHABET
+    u64 *d_totals;  // KS_RSCORE_ALPHABET
+    u32 *d_length;  // n_seqs
+    u64 h_totals[KS_RSCORE_ALPHABET]; // the totals again: the default background of ks_scores_stats_device
+};
+int ks_residue_composition_impl(ks_ctx *ctx, const ks_res_batch &B, ks_rcomp *C);
+// bit scores and E-values of a column of scores (ks_astats.hip)
+struct ks_astats {
+    ks_ctx *ctx;
+    u64 n_rows, n, n_fallback;
+    double lambda_std, lambda_used, K_used;
+    u32 params_source;
+    u8 *d_status;                                                // n_rows
+    double *d_x, *d_ratio, *d_row_bit, *d_row_evalue;            // n_rows
+    double *d_bit, *d_evalue;                                    // n
+};
+// ks_scores_stats_device behind its argument checks (o: validated, defaults filled in, its matrix the one to use; H, Q, T: of
+// ctx; T may be NULL where the contract allows it)
+int ks_scores_stats_impl(ks_ctx *ctx, const u64 *d_row_offs, const i64 *d_score, u64 n_rows, u64 n, const ks_hits *H, const ks_rcomp *Q,
+                         const ks_rcomp *T, const ks_astats_opts &o, ks_astats *A);
 
 // clusters of a hit list read as a graph: its connected components (ks_cluster.hip) or greedy representative clusters (ks_greedy.hip)
 struct ks_clusters {

@@ -77,6 +77,33 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _matrix28(matrix) -> Optional[np.ndarray]:
+    """A substitution matrix as the C ABI takes it (contiguous int8 [28, 28]), or None."""
+    if matrix is None:
+        return None
+    m = np.asarray(matrix)
+    if m.shape != (_lib.KS_RSCORE_ALPHABET, _lib.KS_RSCORE_ALPHABET) or m.dtype != np.int8:
+        raise ValueError("matrix must be an int8 array of shape (28, 28)")
+    return np.ascontiguousarray(m)
+
+
+def karlin_ungapped(matrix, freq_q, freq_t) -> Tuple[float, float, float]:
+    """ks_karlin_ungapped: (lambda, K, H) of `matrix` (int8 [28, 28], None: +1 / -1) without gaps under the residue-class
+    weights freq_q and freq_t (28 each, of which the 20 standard classes count, renormalised).  Host only, no context."""
+    L = _lib.load()
+    m = _matrix28(matrix)
+    fq = np.ascontiguousarray(freq_q, dtype=np.float64); ft = np.ascontiguousarray(freq_t, dtype=np.float64)
+    if fq.shape != (_lib.KS_RSCORE_ALPHABET,) or ft.shape != (_lib.KS_RSCORE_ALPHABET,):
+        raise ValueError("freq_q and freq_t must hold 28 weights each")
+    lam, K, H = C.c_double(0), C.c_double(0), C.c_double(0)
+    dp = C.POINTER(C.c_double)
+    st = L.ks_karlin_ungapped(m.ctypes.data_as(C.POINTER(C.c_int8)) if m is not None else None, fq.ctypes.data_as(dp), ft.ctypes.data_as(dp),
+                              C.byref(lam), C.byref(K), C.byref(H))
+    if st != _lib.KS_OK:
+        raise KmerseekError(st, "karlin_ungapped: " + (L.ks_karlin_last_error() or L.ks_status_string(st)).decode())
+    return lam.value, K.value, H.value
+
+
 def search_opts(min_containment: float = 0.0, abund_stats: bool = False) -> Optional[_lib.ks_search_opts]:
     """The ks_search_opts of the keyword arguments, or None for the defaults (the plain entry points are called then)."""
     if not abund_stats and min_containment == 0.0:
@@ -697,6 +724,91 @@ class Context:
         finally:
             for b in bufs:
                 b.free()
+
+    def residue_composition_device(self, d_res: int, d_off: int, n_seqs: int, n_res: int) -> "Composition":
+        """ks_residue_composition_device from a device-resident residue batch (raw pointers: residues u8, offsets
+        u64[n_seqs + 1]): per sequence the count of each of the 28 residue classes of score_regions (A..Z, '*', everything else)
+        and its length, and the class totals of the batch.  Build it once per database and reuse it."""
+        out = C.c_void_p()
+        self._check(self._L.ks_residue_composition_device(self._h, C.c_void_p(int(d_res)) if d_res else None, C.c_void_p(int(d_off)),
+                                                          int(n_seqs), int(n_res), C.byref(out)))
+        return Composition(self, out)
+
+    def residue_composition(self, res: np.ndarray, off: np.ndarray) -> "Composition":
+        """residue_composition_device from host arrays: uploaded, counted, released."""
+        res = np.ascontiguousarray(res, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.uint64)
+        bufs = []
+        try:
+            for a in (res if len(res) else np.zeros(1, np.uint8), off):  # (an empty batch still has a buffer to point at)
+                bufs.append(self.to_device(a))
+            return self.residue_composition_device(bufs[0].ptr, bufs[1].ptr, len(off) - 1, len(res))
+        finally:
+            for b in bufs:
+                b.free()
+
+    @staticmethod
+    def _astats_opts(matrix, params, background, composition: bool, pairwise: bool, allow_ungapped: bool, ratio, db_residues: int,
+                     db_seqs: int, length_adjust: int):
+        """(ks_astats_opts, the arrays its pointers read: keep them alive for the call)"""
+        m = _matrix28(matrix)
+        bg = None
+        if background is not None:
+            bg = np.ascontiguousarray(background, dtype=np.float64)
+            if bg.shape != (_lib.KS_RSCORE_ALPHABET,):
+                raise ValueError("background must hold 28 weights")
+        lam, K = (0.0, 0.0) if params is None else (float(params[0]), float(params[1]))
+        for name, v, top in (("db_residues", db_residues, 2 ** 64 - 1), ("db_seqs", db_seqs, 2 ** 64 - 1), ("length_adjust", length_adjust, 2 ** 32 - 1)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
+        flags = ((0 if composition else _lib.KS_ASTATS_NO_COMPOSITION) | (_lib.KS_ASTATS_PAIRWISE if pairwise else 0)
+                 | (_lib.KS_ASTATS_ALLOW_UNGAPPED if allow_ungapped else 0))
+        opts = _lib.ks_astats_opts(flags, int(length_adjust), m.ctypes.data_as(C.POINTER(C.c_int8)) if m is not None else None, lam, K,
+                                   bg.ctypes.data_as(C.POINTER(C.c_double)) if bg is not None else None, float(ratio[0]), float(ratio[1]),
+                                   int(db_residues), int(db_seqs), 0)
+        return opts, (m, bg)
+
+    def alignment_stats_device(self, d_row_offsets: Optional[int], d_score: int, n_rows: int, n: int, hits: "Hits", q_comp: "Composition",
+                               t_comp: Optional["Composition"], matrix=None, params=None, background=None, composition: bool = True,
+                               pairwise: bool = False, ratio=(0.5, 1.0), db_residues: int = 0, db_seqs: int = 0,
+                               length_adjust: int = 0) -> "AlignmentStats":
+        """ks_scores_stats_device from device-resident columns (raw pointers: row_offsets u64[n_rows + 1] or None — one score per
+        hit row —, score i64[n]): per entry a bit score and an E-value, per hit row the composition-based lambda ratio the scores
+        were rescaled with.  params: (lambda, K) of the scoring system, typically the gapped ones of the matrix and its gap
+        costs; None: the ungapped ones the library derives.  include/kmerseek_amd.h has the contract."""
+        opts, keep = self._astats_opts(matrix, params, background, composition, pairwise, False, ratio, db_residues, db_seqs, length_adjust)
+        out = C.c_void_p()
+        self._check(self._L.ks_scores_stats_device(self._h, C.c_void_p(int(d_row_offsets)) if d_row_offsets else None,
+                                                   C.c_void_p(int(d_score)) if d_score else None, int(n_rows), int(n), hits._h, q_comp._h,
+                                                   None if t_comp is None else t_comp._h, C.byref(opts), C.byref(out)))
+        del keep
+        return AlignmentStats(self, out)
+
+    def alignment_stats(self, scored, hits: "Hits", q_comp: "Composition", t_comp: Optional["Composition"], matrix=None, params=None,
+                        background=None, composition: bool = True, pairwise: bool = False, allow_ungapped: bool = False,
+                        ratio=(0.5, 1.0), db_residues: int = 0, db_seqs: int = 0, length_adjust: int = 0,
+                        alignments: Optional["RegionAlignments"] = None) -> "AlignmentStats":
+        """Bit scores and E-values of a RegionScores (ks_rscores_stats: ungapped scores), a RegionAlignments (ks_raligns_stats) or
+        a HitAlignments (ks_hitalns_stats, one entry per hit row; `alignments`: the RegionAlignments it was stitched from, whose
+        matrix is used).  The two gapped kinds need params=(lambda, K) — the gapped values that belong to the matrix and the gap
+        costs — or allow_ungapped=True, which understates their E-values.  q_comp / t_comp: Context.residue_composition of the
+        batches the hits were searched on; composition=False switches the per-pair rescaling off."""
+        opts, keep = self._astats_opts(matrix, params, background, composition, pairwise, allow_ungapped, ratio, db_residues, db_seqs,
+                                       length_adjust)
+        tc = None if t_comp is None else t_comp._h
+        out = C.c_void_p()
+        if isinstance(scored, RegionScores):
+            st = self._L.ks_rscores_stats(self._h, scored._h, hits._h, q_comp._h, tc, C.byref(opts), C.byref(out))
+        elif isinstance(scored, RegionAlignments):
+            st = self._L.ks_raligns_stats(self._h, scored._h, hits._h, q_comp._h, tc, C.byref(opts), C.byref(out))
+        elif isinstance(scored, HitAlignments):
+            if alignments is None:
+                raise TypeError("alignment_stats of a HitAlignments needs alignments=, the RegionAlignments it was stitched from")
+            st = self._L.ks_hitalns_stats(self._h, scored._h, alignments._h, hits._h, q_comp._h, tc, C.byref(opts), C.byref(out))
+        else:
+            raise TypeError("alignment_stats takes a RegionScores, a RegionAlignments or a HitAlignments")
+        self._check(st)
+        del keep
+        return AlignmentStats(self, out)
 
     def significance(self, queries: "Sketches", targets: "Sketches", hits: "Hits", q_corpus: Optional["Corpus"] = None,
                      t_corpus: Optional["Corpus"] = None) -> "Significance":
@@ -1385,6 +1497,96 @@ class HitAlignments(_Owned):
     def strings(self) -> List[str]:
         """The CIGAR of every hit row as text, e.g. "60M40I60M"; "" for a row without a chain."""
         return cigar_strings(*self.ops_to_host())
+
+
+class Composition(_Owned):
+    """Device-resident residue composition of a batch (ks_rcomp): counts u32[n_seqs, 28] over the residue classes of
+    score_regions, length u32[n_seqs] and the class totals u64[28] of the batch."""
+    _free = "ks_rcomp_free"
+
+    @property
+    def n_seqs(self) -> int:
+        return int(self._ctx._L.ks_rcomp_n_seqs(self._h))
+
+    @property
+    def n_residues(self) -> int:
+        return int(self._ctx._L.ks_rcomp_n_residues(self._h))
+
+    def device_ptrs(self) -> Tuple[int, int, int]:
+        """Raw device pointers (counts u32[n_seqs * 28], totals u64[28], length u32[n_seqs])."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_rcomp_device_" + c)(self._h) or 0) for c in ("counts", "totals", "length"))
+
+    def to_host(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(counts u32[n_seqs, 28], totals u64[28], length u32[n_seqs])."""
+        n = self.n_seqs
+        counts = np.zeros((n, _lib.KS_RSCORE_ALPHABET), np.uint32)
+        totals = np.zeros(_lib.KS_RSCORE_ALPHABET, np.uint64)
+        length = np.zeros(n, np.uint32)
+        self._ctx._check(self._ctx._L.ks_rcomp_copy_to_host(self._ctx._h, self._h, _ptr(counts), _ptr(totals), _ptr(length)))
+        return counts, totals, length
+
+
+class AlignmentStats(_Owned):
+    """Device-resident result of Context.alignment_stats (ks_astats): per hit row status u8 (0 regular, 1 fallback, 2 no
+    composition asked for), x f64 (e^-lambda of the pair), lambda_ratio f64, row_bit_score and row_evalue f64 (the row's best;
+    NaN for a row without entries); per entry bit_score and evalue f64."""
+    _free = "ks_astats_free"
+    _COLUMNS = ("status", "x", "lambda_ratio", "bit_score", "evalue", "row_bit_score", "row_evalue")
+
+    @property
+    def n_rows(self) -> int:
+        return int(self._ctx._L.ks_astats_n_rows(self._h))
+
+    @property
+    def n_entries(self) -> int:
+        return int(self._ctx._L.ks_astats_n_entries(self._h))
+
+    @property
+    def n_fallback(self) -> int:
+        """Hit rows whose composition gave no lambda of their own (ratio 1)."""
+        return int(self._ctx._L.ks_astats_n_fallback(self._h))
+
+    @property
+    def lambda_std(self) -> float:
+        return float(self._ctx._L.ks_astats_lambda_std(self._h))
+
+    @property
+    def lambda_used(self) -> float:
+        return float(self._ctx._L.ks_astats_lambda_used(self._h))
+
+    @property
+    def K_used(self) -> float:
+        return float(self._ctx._L.ks_astats_k_used(self._h))
+
+    @property
+    def params_source(self) -> int:
+        """0: lambda and K were computed (ungapped), 1: the caller's."""
+        return int(self._ctx._L.ks_astats_params_source(self._h))
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        """Raw device pointers (status u8, x, lambda_ratio f64 [n_rows]; bit_score, evalue f64 [n_entries]; row_bit_score,
+        row_evalue f64 [n_rows])."""
+        L = self._ctx._L
+        return tuple(int(getattr(L, "ks_astats_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+
+    @property
+    def row_bit_score_ptr(self) -> int:
+        """The device column row_bit_score f64[n_rows]: pass it to Context.best_hits(score=...) or a cluster pass."""
+        return int(self._ctx._L.ks_astats_device_row_bit_score(self._h) or 0)
+
+    @property
+    def row_evalue_ptr(self) -> int:
+        """The device column row_evalue f64[n_rows]."""
+        return int(self._ctx._L.ks_astats_device_row_evalue(self._h) or 0)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        """(status u8, x, lambda_ratio f64 [n_rows], bit_score, evalue f64 [n_entries], row_bit_score, row_evalue f64 [n_rows])."""
+        nr, n = self.n_rows, self.n_entries
+        cols = [np.zeros(nr, np.uint8), np.zeros(nr, np.float64), np.zeros(nr, np.float64), np.zeros(n, np.float64), np.zeros(n, np.float64),
+                np.zeros(nr, np.float64), np.zeros(nr, np.float64)]
+        self._ctx._check(self._ctx._L.ks_astats_copy_to_host(self._ctx._h, self._h, *[_ptr(c) for c in cols]))
+        return tuple(cols)
 
 
 class Clusters(_Owned):

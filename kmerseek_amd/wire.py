@@ -712,7 +712,7 @@ def read_score_matrix(path: str) -> np.ndarray:
 
 
 def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, regions_host,
-                moltype: str, scores=None, alignments=None, cigars=None, cull=None, chain=None) -> List[dict]:
+                moltype: str, scores=None, alignments=None, cigars=None, cull=None, chain=None, stats=None) -> List[dict]:
     """One row per region of the device's chaining (Context.match_regions; regions_host = Regions.to_host()): hit row
     r = (qid[r], tid[r]) owns regions [row_offsets[r], row_offsets[r + 1]).  The stitched columns of search.py:195-240 —
     query / match / encoded are the residues the region spans, sliced from the records (a region lies on one diagonal, so
@@ -742,7 +742,12 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
     chain = RegionChain.to_host() of those alignments — or, without alignments, of those scores (Context.chain_regions; needs
     one of them): every row also carries chain_pos, its region's place in the colinear chain of its hit row (0: the chain's
     first member), -1 for a region outside the chain.  With cull= as well the chain is that of the objects RegionCull.take
-    gave: its src_region indexes the kept regions.  Nothing else changes; chain=None adds no column."""
+    gave: its src_region indexes the kept regions.  Nothing else changes; chain=None adds no column.
+
+    stats = AlignmentStats.to_host() of those alignments — or, without alignments, of those scores (Context.alignment_stats;
+    needs one of them): every row also carries aln_bit_score and aln_evalue (region_bit_score and region_evalue for the
+    statistics of scores) and lambda_ratio, the composition-based factor its hit row's scores were rescaled with, as floats.
+    With cull= the statistics may be those of all regions or of the kept ones alone.  stats=None adds no column."""
     offs, q_start, t_start, length, n_kmers, covered = [np.asarray(c).tolist() for c in regions_host]
     if scores is not None:
         s_offs, s_q, s_t, s_len, s_score, s_ident, s_pos, _ = [np.asarray(c).tolist() for c in scores]
@@ -770,6 +775,14 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
         kept_at = {g: i for i, g in enumerate(c_src)}
         rank_col, nm_col = ("aln_rank", "aln_n_merged") if alignments is not None else ("region_rank", "region_n_merged")
         cg_kept = cigars is not None and len(cg) != len(q_start)
+    if stats is not None:
+        if scores is None and alignments is None:
+            raise ValueError("statistics need scores or alignments: they are made of one of them")
+        st_ratio, st_bit, st_ev = [np.asarray(stats[i]).tolist() for i in (2, 3, 4)]
+        if len(st_ratio) != len(offs) - 1 or (len(st_bit) != len(q_start) and (cull is None or len(st_bit) != len(cull[1]))):
+            raise ValueError("statistics and regions are not of the same regions")
+        st_kept = len(st_bit) != len(q_start)
+        bit_col, ev_col = ("aln_bit_score", "aln_evalue") if alignments is not None else ("region_bit_score", "region_evalue")
     chain_pos = None
     if chain is not None:
         if scores is None and alignments is None:
@@ -811,13 +824,16 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
                 row[nm_col] = c_nm[kept_at[g]]
             if chain_pos is not None:
                 row["chain_pos"] = chain_pos.get(g, -1)
+            if stats is not None:
+                e = kept_at[g] if st_kept else g
+                row.update({bit_col: st_bit[e], ev_col: st_ev[e], "lambda_ratio": st_ratio[r]})
             out.append((q, row))
     out.sort(key=lambda e: (e[0], e[1]["query_start"], e[1]["query_end"]))
     return [row for _, row in out]
 
 
 def hit_chain_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, chain_host,
-                   stitched=None) -> List[dict]:
+                   stitched=None, stats=None) -> List[dict]:
     """One row per hit row that has a chain (chain_host = RegionChain.to_host(); hit row r = (qid[r], tid[r])): what the
     alignments of the hit say together.  query_name, match_name, chain_score, n_alns (the chain's members), query_start /
     query_end and match_start / match_end (the chain's span, half-open), q_aligned and t_aligned (the positions its members
@@ -828,7 +844,15 @@ def hit_chain_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[T
     the chain was stitched into — aln_cigar (text, the query as the read), aln_score, aln_identities, aln_positives,
     aln_gap_opens, aln_gaps, aln_length, aln_pident (100 * identities / aln_length of that alignment: no column is counted
     twice) — and n_filled / n_open, the links between the chain's members that were aligned / left open.  stitched=None adds
-    no column."""
+    no column.
+    stats = AlignmentStats.to_host() of those stitched alignments (Context.alignment_stats; needs stitched): every row also
+    carries aln_bit_score and aln_evalue, as floats.  stats=None adds no column."""
+    if stats is not None:
+        if stitched is None:
+            raise ValueError("statistics need stitched: they are those of the stitched alignments")
+        st_bit, st_ev = np.asarray(stats[3]).tolist(), np.asarray(stats[4]).tolist()
+        if len(st_bit) != len(np.asarray(qid)):
+            raise ValueError("statistics and hits are not of the same hit rows")
     st = None
     if stitched is not None:
         from .engine import cigar_strings
@@ -860,6 +884,8 @@ def hit_chain_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[T
                 "aln_gap_opens": st[9][r], "aln_gaps": st[10][r], "aln_length": st[11][r],
                 "aln_pident": format_f64(100.0 * float(st[7][r]) / float(st[11][r]) if st[11][r] else math.nan),
                 "n_filled": st[13][r], "n_open": st[14][r]})
+            if stats is not None:
+                out[-1][3].update({"aln_bit_score": st_bit[r], "aln_evalue": st_ev[r]})
     out.sort(key=lambda e: e[:3])
     return [row for *_, row in out]
 
@@ -872,7 +898,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 cull_overlap: int = 100, min_aln_score=None, max_alns: int = 0, chain: bool = False,
                                 chain_max_gap: int = 0, chain_max_overlap: int = 0, chain_link_cost: int = 0,
                                 chain_skew_cost: int = 0, chain_overlap_cost: int = 0, hit_rows: bool = False,
-                                stitch: bool = False, stitch_max_fill: int = 0) -> List[dict]:
+                                stitch: bool = False, stitch_max_fill: int = 0, evalue: bool = False, stat_params=None,
+                                max_evalue=None) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -892,7 +919,22 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     rows carry chain_pos.  hit_rows=True (needs chain=True): the rows of `hit_chain_rows`, one per hit, instead.
     stitch=True (needs gapped=True, cigar=True, chain=True and hit_rows=True): each hit's chain is stitched into one gapped
     alignment on the device (Context.stitch_chains with stitch_max_fill and eqx) and the hit rows carry the aln_* columns
-    `hit_chain_rows` adds for stitched=."""
+    `hit_chain_rows` adds for stitched=.
+    evalue=True (needs gapped=True or score=True; with hit_rows=True also stitch=True): the residue compositions of both files
+    are counted on the device and the scores — the stitched alignments', else the alignments', else the scored regions' — get
+    bit scores and E-values (Context.alignment_stats with matrix; the database is the target file) and the rows carry the
+    columns `region_rows` / `hit_chain_rows` add for stats=.  stat_params = (lambda, K): the gapped parameters that belong to
+    the matrix and the gap costs — gapped scores need them; None for scored regions: the ungapped ones the library derives.
+    max_evalue: rows whose E-value is above it are dropped, on the host."""
+    if (stat_params is not None or max_evalue is not None) and not evalue:
+        raise ValueError("stat_params and max_evalue need evalue=True")
+    if evalue:
+        if not (gapped or score):
+            raise ValueError("evalue=True needs gapped=True or score=True: statistics are of scores")
+        if hit_rows and not stitch:
+            raise ValueError("evalue=True with hit_rows=True needs stitch=True: a chain with open links has no one score")
+        if gapped and stat_params is None:
+            raise ValueError("evalue=True with gapped=True needs stat_params=(lambda, K), the gapped parameters of the matrix and gap costs")
     if stitch:
         for name, on in (("gapped", gapped), ("cigar", cigar), ("chain", chain), ("hit_rows", hit_rows)):
             if not on:
@@ -929,6 +971,14 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
             rg_host = rg.to_host()
             sc_host = cg_host = cu = None
             kw = {}
+            if evalue:
+                q_comp, t_comp = ctx.residue_composition(q_res, q_off), ctx.residue_composition(t_res, t_off)
+
+                def stats_of(obj, **more):
+                    s = ctx.alignment_stats(obj, hits, q_comp, t_comp, matrix=matrix, params=stat_params, **more)
+                    host = s.to_host()
+                    s.free()
+                    return host
 
             def chained(obj):  # the chain of obj, or of what the cull kept of it
                 kept = cu.take(obj) if cu is not None else obj
@@ -946,6 +996,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                     cu = ctx.cull_regions(sc, overlap_pct=cull_overlap, min_score=min_aln_score, max_per_row=max_alns)
                 if chain and not gapped:
                     kw["chain"] = chained(sc)
+                if evalue and not gapped:
+                    kw["stats"] = stats_of(sc)
                 sc.free()
             if gapped:
                 al = ctx.align_regions(rg, hits, q_res, q_off, t_res, t_off, matrix=matrix, band=band, gap_open=gap_open,
@@ -960,6 +1012,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                            skew_cost=chain_skew_cost, overlap_cost=chain_overlap_cost)
                     st = ctx.stitch_chains(ch, t_al, cg, hits, q_res, q_off, t_res, t_off, max_fill=stitch_max_fill, eqx=eqx)
                     kw["chain"], st_host = ch.to_host(), st.to_host()
+                    if evalue:
+                        kw["stats"] = stats_of(st, alignments=t_al)
                     for o in (st, ch, cg) + ((t_rg, t_al) if cull else ()):
                         o.free()
                 elif cigar:
@@ -971,21 +1025,31 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                         t_rg.free(); t_al.free()
                 if chain and not stitch:
                     kw["chain"] = chained(al)
+                if evalue and not stitch:
+                    kw["stats"] = stats_of(al)
                 al.free()
             if cu is not None:
                 kw["cull"] = cu.to_host()
                 cu.free()
+            if evalue:
+                q_comp.free(); t_comp.free()
             for o in (rg, mp, qp, tp, hits, Q, T):
                 o.free()
+
+            def below(rows):  # max_evalue: on the host
+                if max_evalue is None:
+                    return rows
+                col = "aln_evalue" if gapped else "region_evalue"
+                return [row for row in rows if not row[col] > max_evalue]
             if stitch:
-                return hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"], stitched=st_host)
+                return below(hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"], stitched=st_host, stats=kw.get("stats")))
             if hit_rows:
                 return hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"])
             if gapped:
                 if cigar:
-                    return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, cigars=cg_host, **kw)
-                return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, **kw)
-            return region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, **kw)
+                    return below(region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, cigars=cg_host, **kw))
+                return below(region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, **kw))
+            return below(region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, **kw))
         offs, qs, ts = mp.to_host()[:3]
         for o in (mp, qp, tp, hits, Q, T):
             o.free()
