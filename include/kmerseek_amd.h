@@ -113,13 +113,16 @@ int ks_ctx_sketch_stats(const ks_ctx *ctx, uint64_t out[4]);
  * ticket-ordered tiles because a look-back gave up (the context then uses tickets for good), out[2] = searches whose rows
  * came from the aggregate pass over the match sort's first level (taken while the previous search of the context had many
  * matches per row; a path, not a repeat), out[3] = searches in which that pass gave up (a region with more rows than its
- * table holds) and the sort was resumed. */
-int ks_ctx_search_stats(const ks_ctx *ctx, uint64_t out[4]);
+ * table holds) and the sort was resumed, out[4] = searches whose join ran the table kernel (taken while the join buckets are
+ * expected to hold few query postings — behind a filtered partition: few survivors, by the previous filtered search of the
+ * context; a path, not a repeat). */
+int ks_ctx_search_stats(const ks_ctx *ctx, uint64_t out[5]); /* (five words — four before out[4] was added: size the array) */
 /* ks_sketch_search_device on this context: out[0] = calls whose sketch read-back was folded into the search's first wait,
  * out[1] = calls that had to be repeated with the two plain calls (skewed hashes, an economy that did not fit), out[2] = calls
- * whose rows came from the aggregate pass (out[2] of ks_ctx_search_stats rose during the call). */
-int ks_ctx_fused_stats(const ks_ctx *ctx, uint64_t out[3]);
-/* The presence filter of the searches on this context (a fingerprint-layout index carries a bitmap over hash prefixes; the
+ * whose rows came from the aggregate pass (out[2] of ks_ctx_search_stats rose during the call), out[3] = calls whose join ran
+ * the table kernel (out[4] of ks_ctx_search_stats rose). */
+int ks_ctx_fused_stats(const ks_ctx *ctx, uint64_t out[4]); /* (four words — three before out[3] was added) */
+/* The presence filter of the searches on this context (a fingerprint-layout index carries a two-bit filter over hash prefixes; the
  * partition of the query postings drops those the bitmap rules out): out[0] = query postings the filtered partitions read,
  * out[1] = postings they dropped.  Results never depend on the filter; KS_DEBUG_QFILTER = 0 / 1 forces it off / on. */
 int ks_ctx_qfilter_stats(const ks_ctx *ctx, uint64_t out[2]);

@@ -312,6 +312,7 @@ extern "C" void ks_index_free(ks_index *ix) {
     ks_pool_free(ix->ctx, ix->d_post);
     ks_pool_free(ix->ctx, ix->d_bmeta);
     ks_pool_free(ix->ctx, ix->d_presence);
+    ks_pool_free(ix->ctx, ix->d_presence_big);
     ks_pool_free(ix->ctx, ix->d_dir);
     delete ix;
 }
@@ -342,7 +343,7 @@ static int sketch_search_impl(ks_ctx *ctx, const ks_index *index, const uint8_t 
     const int fmt10 = (index->fp_layout && index->fp_shift == 32 - index->pbits) ? 1 : 0;
     ks_sketches *S = nullptr;
     ks_hits *H = nullptr;
-    const u64 agg_before = ctx->agg_used;
+    const u64 agg_before = ctx->agg_used, table_before = ctx->join_table;
     int st = ks_sketch_device_impl(ctx, d_residues, d_seq_offsets, n_seqs, n_residues, max_seq_len, &index->params, index->pbits, fmt10,
                                    ks_dbg(ctx, KS_DBG_NO_DEFER) ? 0 : 1, &S);
     if (st != KS_OK) return st;
@@ -366,6 +367,7 @@ static int sketch_search_impl(ks_ctx *ctx, const ks_index *index, const uint8_t 
     if (st != KS_OK) { ks_hits_free(H); ks_sketches_free(S); return st; }
     if (deferred) ctx->fused_deferred++;
     if (ctx->agg_used > agg_before) ctx->fused_aggregated++;
+    if (ctx->join_table > table_before) ctx->fused_table_joined++;
     *hits_out = H;
     if (sketches_out) *sketches_out = S; else ks_sketches_free(S);
     return KS_OK;

@@ -110,6 +110,11 @@ struct ks_ctx {
     // KS_DEBUG_QFILTER = 0 / 1 forces either.
     bool qfilter_pays = true;
     u64 qfilter_seen = 0, qfilter_dropped = 0; // query postings of the filtered scatters of this context / those they dropped
+    // ... and of the latest of them alone (qf_last_seen 0: none yet): its kept / seen fraction is what the next filtered search
+    // expects its join buckets to hold when it picks the join kernel (se_join).  join_table: searches that took the table kernel
+    // (k_join_sparse); fused_table_joined: ks_sketch_search_device calls among them.
+    u64 qf_last_seen = 0, qf_last_kept = 0;
+    u64 join_table = 0, fused_table_joined = 0;
     // single-launch scans (ks_prims.hip): status ring + ticket counter in device memory, never reset: every entry is
     // tagged with the global tile number that wrote it
     unsigned long long *scan_ring = nullptr;
@@ -393,12 +398,20 @@ struct ks_index {
     u32 max_abund; // largest of them: how many low bits of a packed match record the abundance needs
     u64 *d_dir;    // join-bucket directory: d_dir[b] = first posting whose join prefix is >= b (2^pbits + 1 entries)
     int pbits;     // join prefix bits, a function of n_postings and the layout alone (ks_join_pbits)
-    // fp_layout: presence bitmap over hash prefixes, for the query side's bucket scatter (k_bucket_scatter): bit
-    // ks_join_prefix(hash, pres_K) is set iff some posting has that prefix.  2^pres_bits bits (pres_bits >= pbits: every join
-    // bucket owns 2^(pres_bits - pbits) of them, ~KS_QF_OCC per posting).  nullptr: the index has none (key-column join).
+    // fp_layout: presence filter over hash prefixes, for the query side's bucket scatter (k_bucket_scatter): 2^pres_bits bits in
+    // 32-bit words (pres_bits >= pbits: every join bucket owns 2^(pres_bits - pbits) of them, ~KS_QF_OCC per posting; one word at
+    // the least).  A posting with prefix p = ks_join_prefix(hash, pres_K) sets two bits of word p >> 5: bit p & 31 and bit
+    // ks_presence_bit2(hash); a query hash whose two bits are not both set matches no posting.  nullptr: the index has none
+    // (key-column join).
     u32 *d_presence;
     u32 pres_K;
     int pres_bits;
+    // The same at ~KS_QF_OCC_BIG bits per posting, for batches big enough to earn back the fetch of a filter twice the size
+    // (se_partition picks).  nullptr: the index has one size only (both widths round to the same power of two, or
+    // KS_DEBUG_QFILTER_OCC named the one to build).
+    u32 *d_presence_big;
+    u32 pres_big_K;
+    int pres_big_bits;
 };
 
 // the row columns of a hit list as the kernels read them (rf_move, ks_device.h)
@@ -721,8 +734,8 @@ int ks_radix_sort_keys(ks_ctx *ctx, int tag, const u64 *keys_in, u64 *ka, u64 *k
 #define KS_BSLOT(d, r, n_hi) ((r) * (n_hi) + (d))
 // status[1] of the bucket scatter: bit 0 = a bucket overflowed; from bit KS_QF_KEPT up = postings that passed the presence filter
 #define KS_QF_KEPT 1
-// presence != nullptr: postings whose bit of the index's presence bitmap (ks_index::d_presence, multiplier presK) is clear are
-// dropped; fix_s: where the region's 8 prefix bits sit in the high word of a hash (vfmt != 0: the keys carry id bits there)
+// presence != nullptr: postings without both of their bits in the index's presence filter (ks_index::d_presence, multiplier presK)
+// are dropped; fix_s: where the region's 8 prefix bits sit in the high word of a hash (vfmt != 0: the keys carry id bits there)
 int ks_bucket_scatter_u32(ks_ctx *ctx, const u64 *keys_in, const u32 *vals_in, const ks_rs_segments *seg, int shift,
                           u32 pfxK, u64 *bkeys, u32 *bvals, u32 *bcur, u32 bcap, unsigned long long *status, u32 n_hi, int vfmt,
                           const u32 *presence, u32 presK, u32 fix_s);

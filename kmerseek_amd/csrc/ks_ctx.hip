@@ -218,11 +218,12 @@ extern "C" int ks_ctx_sketch_stats(const ks_ctx *ctx, uint64_t out[4]) {
     });
 }
 
-extern "C" int ks_ctx_search_stats(const ks_ctx *ctx, uint64_t out[4]) {
+extern "C" int ks_ctx_search_stats(const ks_ctx *ctx, uint64_t out[5]) {
     return ks_guard((ks_ctx *)ctx, [&]() -> int {
     if (!ctx || !out) return KS_ERR_INVALID_ARG;
     out[0] = ctx->join_retries; out[1] = ctx->rows_ticket_fallbacks;
     out[2] = ctx->agg_used; out[3] = ctx->agg_overflows;
+    out[4] = ctx->join_table;
     return KS_OK;
     });
 }
@@ -235,10 +236,11 @@ extern "C" int ks_ctx_qfilter_stats(const ks_ctx *ctx, uint64_t out[2]) {
     });
 }
 
-extern "C" int ks_ctx_fused_stats(const ks_ctx *ctx, uint64_t out[3]) {
+extern "C" int ks_ctx_fused_stats(const ks_ctx *ctx, uint64_t out[4]) {
     return ks_guard((ks_ctx *)ctx, [&]() -> int {
     if (!ctx || !out) return KS_ERR_INVALID_ARG;
     out[0] = ctx->fused_deferred; out[1] = ctx->fused_redos; out[2] = ctx->fused_aggregated;
+    out[3] = ctx->fused_table_joined;
     return KS_OK;
     });
 }

@@ -470,6 +470,11 @@ KS_DEV u32 ks_match8_rank(u32 d, u32 *wc) {
 // [0, 2^pbits) for every `scaled` (kept hashes only span [0, max_hash], so plain top bits are NOT uniform for scaled > 1).
 // K = floor(2^(pbits+32) / ((max_hash >> 32) + 1)); for scaled = 1 this is exactly h >> (64 - pbits).  Monotone in h.
 KS_DEV u32 ks_join_prefix(u64 h, u32 K) { return __umulhi((u32)(h >> 32), K); }
+// The presence filter (ks_index::d_presence) tests two bits of one 32-bit word per hash: with p = the hash's join prefix at the
+// bitmap's width, bit p & 31 of word p >> 5 and the bit this names — bits [8, 13) of the LOW hash word, which every posting
+// width carries intact (the 10-byte form rewrites a field of the high word only) and which a hash shares with its neighbour
+// h ^ 1.  32-bit words, so that a probe stays a 4-byte gather (8-byte ones measured slower: DESIGN.md §3.2 [r7]).
+KS_DEV u32 ks_presence_bit2(u64 h) { return ((u32)h >> 8) & 31u; }
 // digit of a radix pass: plain key bits (K == 0) or bits [shift, shift + 8) of the join prefix
 KS_DEV u32 ks_rs_digit(u64 key, int shift, u32 K) {
     return K ? ((ks_join_prefix(key, K) >> shift) & 255u) : ((u32)(key >> shift) & 255u);

@@ -410,8 +410,9 @@ __global__ __launch_bounds__(RS_THREADS, RS_MINW) void k_radix_scatter(const u64
 // V16 = 1: the value column is 16 bits wide, in and out (10-byte query postings: ks_sketches::part_s).
 // V16 = 2: 16 bits in, 8 bits out (9-byte postings; join prefixes of 16 bits only): the bucket implies the key's top byte too —
 // it is this pass's digit —, so the low byte of the value moves there and its high byte is the 8-bit column that leaves.
-// QF: the presence filter.  `presence` is the index's bitmap over hash prefixes (ks_index::d_presence: bit umulhi(hash >> 32, presK)
-// is set iff some index posting has that prefix); a query posting whose bit is clear cannot match and becomes "no record" before it
+// QF: the presence filter.  `presence` is the index's bitmap over hash prefixes (ks_index::d_presence: every index posting set two
+// bits of the 32-bit word its prefix umulhi(hash >> 32, presK) falls in — the prefix's own and the one ks_presence_bit2 names —,
+// so one 4-byte probe tests both); a query posting without both cannot match and becomes "no record" before it
 // is ranked, so the counts, the cursors, the overflow check and the fill counts the join reads describe the survivors only.  A tile's
 // postings share their region's 8 prefix bits: the words it probes are 2^(pbits - 8) chunks of the bitmap, and the tiles an XCD runs
 // at one time belong to one or two regions (ks_xcd_block), whose chunks stay in that XCD's L2.  The sixteen probes are requested
@@ -451,7 +452,7 @@ __global__ __launch_bounds__(RS_THREADS, 4) void k_bucket_scatter(const u64 *kin
         const u32 li = (u32)r * RS_THREADS + tid;
         const bool valid = li < nvalid;
         key[r] = valid ? kin[tile_base + li] : 0ULL;
-        val[r] = valid ? (V16 ? (u32)((const u16 *)vin)[tile_base + li] : vin[tile_base + li]) : 0u;
+        if (!QF || V16 == 2) val[r] = valid ? (V16 ? (u32)((const u16 *)vin)[tile_base + li] : vin[tile_base + li]) : 0u; // (else: below)
     }
     __syncthreads();
     // A full tile — all but the last of a sub-region — ranks its records without a guard: sixteen LDS atomics in flight, one wait.
@@ -471,9 +472,24 @@ __global__ __launch_bounds__(RS_THREADS, 4) void k_bucket_scatter(const u64 *kin
 #pragma unroll
         for (int r = 0; r < RS_IPT; r++) w[r] = presence[bit[r] >> 5];
 #pragma unroll
+        for (int r = 0; r < RS_IPT; r++) // bit number -> the two bits' mask (the low hash word is intact in every posting width)
+            bit[r] = (1u << (bit[r] & 31u)) | (1u << ks_presence_bit2(key[r]));
+#pragma unroll
         for (int r = 0; r < RS_IPT; r++) {
-            const bool live = (u32)r * RS_THREADS + tid < nvalid && ((w[r] >> (bit[r] & 31u)) & 1u);
+            const bool live = (u32)r * RS_THREADS + tid < nvalid && (w[r] & bit[r]) == bit[r]; // both, or the index has no such hash
             dg[r] = live ? ((ks_join_prefix(key[r], pfxK) >> shift) & (n_hi - 1u)) : (u32)BKS_NB + (tid & 63u);
+        }
+        // 10-byte postings keep their values to the kernel's end, and with them the probed words do not fit the register budget
+        // (with the loads at the top this variant spills; as written it sits exactly AT the 128 registers of the launch bounds —
+        // check tools/isa_audit.sh --stats for scratch after any change here):
+        // their values are requested here, behind the probes, and arrive while the tile is ranked — nothing reads them before the
+        // records are staged.  (12-byte postings, a diagnostic width with 32-bit values: where they are staged, for the same reason.)
+        if (V16 == 1) {
+#pragma unroll
+            for (int r = 0; r < RS_IPT; r++) {
+                const u32 li = (u32)r * RS_THREADS + tid;
+                val[r] = li < nvalid ? (u32)((const u16 *)vin)[tile_base + li] : 0u;
+            }
         }
 #pragma unroll
         for (int r = 0; r < RS_IPT; r++) rank[r] = atomicAdd(&cnt[dg[r]], 1u);
@@ -575,6 +591,10 @@ __global__ __launch_bounds__(RS_THREADS, 4) void k_bucket_scatter(const u64 *kin
     if (V16 == 2) return;
     __syncthreads();
     u32 *vstage = (u32 *)stage;
+    if constexpr (QF && V16 == 0) {
+#pragma unroll
+        for (int r = 0; r < RS_IPT; r++) val[r] = rank[r] != 0xffffffffu ? vin[tile_base + (u32)r * RS_THREADS + tid] : 0u;
+    }
     if (full) {
 #pragma unroll
         for (int r = 0; r < RS_IPT; r++) vstage[rank[r]] = val[r];

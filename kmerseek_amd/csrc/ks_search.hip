@@ -52,25 +52,38 @@ __global__ __launch_bounds__(256) void k_index_finish(const u64 *keys, const u32
                                                       u32 pfxK, int fp_shift, u32 *fp, ks_post *post);
 __global__ __launch_bounds__(256) void k_index_bmeta(const u64 *keys, const u64 *dir, u32 n_buckets, int fp_shift, ks_bmeta *bmeta);
 
-// The presence bitmap of a fingerprint-layout index (ks_index::d_presence): the keys are sorted, so a posting whose predecessor
-// sets the same bit (the same hash in another target, mostly) leaves the atomic out.
+// The presence bitmap of a fingerprint-layout index (ks_index::d_presence): every posting sets its two bits of one 32-bit word
+// (ks_presence_bit2) with one atomic; the keys are sorted, so a posting whose predecessor has the same hash (in another
+// target) leaves the atomic out.
 __global__ __launch_bounds__(256) void k_index_presence(const u64 *keys, u64 n, u32 presK, u32 *presence) {
     const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
-    const u32 b = ks_join_prefix(keys[i], presK);
-    if (i > 0 && ks_join_prefix(keys[i - 1], presK) == b) return;
-    atomicOr(&presence[b >> 5], 1u << (b & 31u));
+    const u64 k = keys[i];
+    if (i > 0 && keys[i - 1] == k) return;
+    const u32 b = ks_join_prefix(k, presK);
+    atomicOr(&presence[b >> 5], (1u << (b & 31u)) | (1u << ks_presence_bit2(k)));
 }
-// Bits of the presence bitmap per index posting: 3 to 6 (the size is a power of two), i.e. 28 to 15 % of the bits set by the time
-// every posting has one — the headline index (295 M postings, 2^16 buckets of ~4.5k) gets 2^30 bits (128 MB), 2^14 per bucket, 24 % set.
-// Measured against 6 to 12 bits per posting (KS_DEBUG_QFILTER_OCC = 6: 2^31 bits, 13 % set): DESIGN.md §3.2.
+// Bits of the presence bitmap per index posting (the size is the next power of two).  A posting sets two bits of one 32-bit word
+// (one where they coincide), a query posting survives if both of its own are set.  An index carries two sizes: KS_QF_OCC — the
+// headline index (295 M postings, 2^16 buckets of ~4.5k) gets 2^30 bits (128 MB), 2^14 per bucket, ~8.8 postings per word — and
+// KS_QF_OCC_BIG (2^31 bits, ~4.4 per word), which drops more but is fetched once per search whatever the batch: a search takes
+// the big one when its batch earns that back (se_partition).  KS_DEBUG_QFILTER_OCC = n builds the one size n names, for every
+// batch.  The two sizes measured against each other: DESIGN.md §3.2 [r7].
 #define KS_QF_OCC 3
-static int presence_bits(const ks_ctx *ctx, u64 n_postings, int pbits) {
-    u64 occ = KS_QF_OCC;
-    if (const char *f = ks_dbg(ctx, KS_DBG_QFILTER_OCC)) { const long v = atol(f); if (v >= 1 && v <= 64) occ = (u64)v; } // (tuning aid)
+#define KS_QF_OCC_BIG 6
+static int presence_bits(u64 occ, u64 n_postings, int pbits) {
     int bits = pbits;
     while (bits < 31 && (1ULL << bits) < occ * n_postings) bits++;
     return bits;
+}
+// one filter of 2^bits bits over the sorted keys
+static int presence_build(ks_ctx *ctx, const u64 *d_keys, u64 n, int bits, u64 max_hash, u32 **out, u32 *out_K) {
+    *out_K = ks_join_prefix_mul(bits, max_hash);
+    const size_t words = bits > 5 ? (size_t)1 << (bits - 5) : 1;
+    KS_TRY(ks_alloc(ctx, out, words));
+    KS_HIP(ctx, hipMemsetAsync(*out, 0, words * sizeof(u32), ctx->stream));
+    if (n > 0) KS_LAUNCH(ctx, "index_presence", k_index_presence, (u32)((n + 255) / 256), 256, d_keys, n, *out_K, *out);
+    return KS_OK;
 }
 
 #define JN_FP_PBITS 15 // indexes with this many join-prefix bits or more (> 50M postings) use the fingerprint layout (see the join)
@@ -157,14 +170,14 @@ static int index_build_run(ks_ctx *ctx, const ks_sketches *t, ks_index *ix) {
                 KS_LAUNCH(ctx, "index_finish", k_index_finish, (u32)((n + 255) / 256), 256, (const u64 *)ix->d_keys, (const u32 *)ix->d_tids,
                           (const u32 *)ix->d_abunds, (const u64 *)ix->d_dir, n, ix->pbits, K, ix->fp_shift, ix->d_fp, ix->d_post);
             // what the index can say about "absent", once: the query side's bucket scatter drops the postings it rules out
-            ix->pres_bits = presence_bits(ctx, n, ix->pbits);
-            ix->pres_K = ks_join_prefix_mul(ix->pres_bits, ks_max_hash(t->params.scaled));
-            const size_t pres_words = ix->pres_bits > 5 ? (size_t)1 << (ix->pres_bits - 5) : 1;
-            KS_TRY(ks_alloc(ctx, &ix->d_presence, pres_words));
-            KS_HIP(ctx, hipMemsetAsync(ix->d_presence, 0, pres_words * sizeof(u32), ctx->stream));
-            if (n > 0)
-                KS_LAUNCH(ctx, "index_presence", k_index_presence, (u32)((n + 255) / 256), 256, (const u64 *)ix->d_keys, n, ix->pres_K,
-                          ix->d_presence);
+            u64 occ = KS_QF_OCC, occ_big = KS_QF_OCC_BIG;
+            if (const char *f = ks_dbg(ctx, KS_DBG_QFILTER_OCC)) { const long v = atol(f); if (v >= 1 && v <= 64) occ = occ_big = (u64)v; } // (tuning aid)
+            const u64 mh = ks_max_hash(t->params.scaled);
+            ix->pres_bits = presence_bits(occ, n, ix->pbits);
+            KS_TRY(presence_build(ctx, (const u64 *)ix->d_keys, n, ix->pres_bits, mh, &ix->d_presence, &ix->pres_K));
+            ix->pres_big_bits = presence_bits(occ_big, n, ix->pbits);
+            if (ix->pres_big_bits > ix->pres_bits)
+                KS_TRY(presence_build(ctx, (const u64 *)ix->d_keys, n, ix->pres_big_bits, mh, &ix->d_presence_big, &ix->pres_big_K));
         }
     }
     KS_TRY(ks_scan_status_fetch(ctx));
@@ -1098,6 +1111,7 @@ struct se_search {
     bool pre, f10; // the sketch's postings are the partition's input (pre), in their 10-byte form (f10)
     bool qf;       // the bucket scatter dropped the postings the index's presence bitmap rules out; qf_kept of them passed
     u64 qf_kept;
+    bool table;    // the join ran the table kernel (k_join_sparse)
     u64 *dir_q;
     // cursor block: segment s of the pair list counts at word s * JN_CUR_STRIDE; word 1 = "a query bucket overflowed"
     // (k_bucket_scatter) (+ the join buckets' fill counts right behind it, bcur: one allocation, one memset)
@@ -1170,9 +1184,15 @@ static int se_partition(ks_ctx *ctx, se_search &Q, int way, ks_scratch &sc, se_q
         // The dense partition below (way 1, after a bucket overflowed) stays unfiltered: the join confirms on the full key either way.
         const char *qf_knob = ks_dbg(ctx, KS_DBG_QFILTER);
         Q.qf = Q.ix->d_presence && (qf_knob ? atoi(qf_knob) != 0 : ctx->qfilter_pays);
+        // Which size: the big filter drops more of what cannot match, but every search fetches all of it once, whatever the batch
+        // (the headline index: 256 MB against 128).  It is taken where the batch alone would fill the join buckets beyond the
+        // table kernel's reach (se_join's rule on n_q): there its survivors decide the join kernel, and there are postings enough
+        // to earn the fetch back.  Measured on both sides of the rule: DESIGN.md §3.2 [r7].
+        const bool big = Q.ix->d_presence_big && Q.n_q / n_buckets > (u64)JS_QCAP * 3 / 4;
         KS_TRY(ks_bucket_scatter_u32(ctx, q->part_keys, q->part_vals, &seg, 8, Q.pfxK, V->qk0, V->qv0, Q.bcur, bcap, Q.cursor, n_buckets >> 8,
                                      V->q_fmt, // (10-byte postings stay 10 bytes, or lose one more: the join decodes them)
-                                     Q.qf ? Q.ix->d_presence : nullptr, Q.ix->pres_K, q_s ? q_s - 32u : 0u));
+                                     Q.qf ? (big ? Q.ix->d_presence_big : Q.ix->d_presence) : nullptr, big ? Q.ix->pres_big_K : Q.ix->pres_K,
+                                     q_s ? q_s - 32u : 0u));
         V->bucket_posting_bytes = V->q_fmt == 2 ? 9 : (V->q_fmt == 1 ? 10 : 12);
         KS_LAUNCH(ctx, "bucket_dir", k_region_dir, (n_buckets + 255) / 256, 256, (const u32 *)Q.bcur, (u64)bcap, n_buckets, Q.dir_q,
                   Q.dir_q + n_buckets, n_buckets >> 8);
@@ -1233,17 +1253,22 @@ static int se_join(ks_ctx *ctx, se_search &Q, const se_qview &V, int way, u64 ca
     if (ks_dbg(ctx, KS_DBG_JOIN_SEG_CAP)) Q.seg_cap = strtoull(ks_dbg(ctx, KS_DBG_JOIN_SEG_CAP), nullptr, 10); // (tests: the retry)
     const u64 *dir_t = ix->d_dir; // built with the index
     const u64 *pin = ctx->h_pin + KS_PIN_JOIN;
+    // Few query postings per bucket: the table kernel (KS_DEBUG_JOIN_SPARSE = 0 / 1 forces the choice in the tests).  What a bucket
+    // holds behind a filtered scatter is known on the device only, so it is expected from the context's previous filtered search:
+    // that one's kept / seen fraction of this batch's postings per bucket (the idiom of qfilter_pays and rows_hint).  A context's
+    // first filtered search and an unfiltered one go by n_q, the count BEFORE the filter.  Both kernels return at once on an empty
+    // bucket and take buckets of any fill: a wrong guess costs time, never rows.
+    u64 fill = Q.n_q / n_buckets;
+    if (way == 0 && Q.qf && ctx->qf_last_seen)
+        fill = (u64)((double)Q.n_q * ((double)ctx->qf_last_kept / (double)ctx->qf_last_seen)) / n_buckets;
+    const bool sparse = ix->fp_layout && (ks_dbg(ctx, KS_DBG_JOIN_SPARSE) ? atoi(ks_dbg(ctx, KS_DBG_JOIN_SPARSE)) != 0
+                                                                         : fill <= (u64)JS_QCAP * 3 / 4);
+    Q.table = sparse;
     for (int attempt = 0; attempt < 2; attempt++) {
         const u64 seg_cap = Q.seg_cap;
         KS_TRY(sc.alloc(&Q.pk0, (size_t)(seg_cap * n_segs)));
         if (attempt > 0) // (attempt 0: cleared with the flag word above; the flag word survives)
             KS_HIP(ctx, hipMemset2DAsync(Q.cursor, (size_t)JN_CUR_STRIDE * sizeof(u64), 0, sizeof(u64), JN_SEGS, ctx->stream));
-        // (few query postings per bucket: the table kernel; KS_DEBUG_JOIN_SPARSE = 0 / 1 forces the choice in the tests.  n_q is
-        // the count BEFORE the presence filter — an upper bound of what the buckets hold, the survivors are counted on the device
-        // only —, so a filtered batch takes the table kernel no sooner than an unfiltered one; both kernels return at once on an
-        // empty bucket and take buckets of any fill.)
-        const bool sparse = ix->fp_layout && (ks_dbg(ctx, KS_DBG_JOIN_SPARSE) ? atoi(ks_dbg(ctx, KS_DBG_JOIN_SPARSE)) != 0
-                                                                             : Q.n_q / n_buckets <= (u64)JS_QCAP * 3 / 4);
         if (sparse)
             KS_LAUNCH(ctx, "join_buckets", (q_fmt == 2 ? k_join_sparse<2> : (q_fmt ? k_join_sparse<1> : k_join_sparse<0>)), n_buckets, JS_THREADS,
                       (const u64 *)V.qk, (const u32 *)V.qv, (const u32 *)ix->d_fp, (const ks_post *)ix->d_post, (const ks_bmeta *)ix->d_bmeta,
@@ -1432,14 +1457,17 @@ static int search_run(ks_ctx *ctx, const ks_index *ix, const ks_sketches *q, con
         sc.free(V.qk0); sc.free(V.qk1); sc.free(V.qv0); sc.free(V.qv1);
         if (!overflowed) {
             H->partition_path = V.partition_path;
+            if (Q.table) ctx->join_table++;
             if (way == 0 && Q.qf) { // (n_q is exact behind the join's wait)
                 const u64 dropped = Q.n_q > Q.qf_kept ? Q.n_q - Q.qf_kept : 0;
                 ctx->qfilter_seen += Q.n_q;
                 ctx->qfilter_dropped += dropped;
+                ctx->qf_last_seen = Q.n_q;
+                ctx->qf_last_kept = Q.n_q - dropped;
                 ctx->qfilter_pays = dropped >= Q.n_q / 2;
             } else if (way == 0 && ix->d_presence && Q.n_pairs < Q.n_q / 4) {
                 // unfiltered: every matching posting makes at least one pair, so fewer than a quarter of them match, and the
-                // bitmap passes at most ~28 % of the rest (KS_QF_OCC): more than half would be dropped
+                // filter passes under a third of the rest (KS_QF_OCC): more than half would be dropped
                 ctx->qfilter_pays = true;
             }
             break;

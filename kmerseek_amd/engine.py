@@ -254,13 +254,15 @@ class Context:
 
     def search_stats(self, paths: bool = False) -> Dict[str, int]:
         """Repeats ks_search needed so far on this context (see ks_ctx_search_stats): `agg_overflows` counts the searches whose
-        aggregate row pass gave up and resumed the sort.  paths=True adds `agg_used`, the searches whose rows that pass made: a
-        path taken, not a repeat, so it grows in normal operation while every other counter here stands still."""
-        v = (C.c_uint64 * 4)()
+        aggregate row pass gave up and resumed the sort.  paths=True adds `agg_used`, the searches whose rows that pass made, and
+        `join_table`, the searches whose join ran the table kernel: paths taken, not repeats, so they grow in normal operation
+        while every other counter here stands still."""
+        v = (C.c_uint64 * 5)()
         self._check(self._L.ks_ctx_search_stats(self._h, C.byref(v)))
         out = {"join_retries": int(v[0]), "rows_ticket_fallbacks": int(v[1]), "agg_overflows": int(v[3])}
         if paths:
             out["agg_used"] = int(v[2])
+            out["join_table"] = int(v[4])
         return out
 
     # ---- sketch ----
@@ -375,10 +377,11 @@ class Context:
 
     def fused_stats(self) -> Dict[str, int]:
         """ks_sketch_search_device calls on this context: with the sketch read-back deferred / repeated the plain way / with
-        their rows made by the aggregate pass (`aggregated`: the `agg_used` of search_stats(paths=True), counted per call here)."""
-        v = (C.c_uint64 * 3)()
+        their rows made by the aggregate pass (`aggregated`: the `agg_used` of search_stats(paths=True), counted per call here) /
+        with their join run by the table kernel (`table_joined`: the `join_table` of search_stats(paths=True), likewise)."""
+        v = (C.c_uint64 * 4)()
         self._check(self._L.ks_ctx_fused_stats(self._h, C.byref(v)))
-        return {"deferred": int(v[0]), "redos": int(v[1]), "aggregated": int(v[2])}
+        return {"deferred": int(v[0]), "redos": int(v[1]), "aggregated": int(v[2]), "table_joined": int(v[3])}
 
     def sketches_from_host(self, offsets: np.ndarray, hashes: np.ndarray, abunds: np.ndarray, ksize: int,
                            scaled: int, moltype: str, seed: int = SEED) -> "Sketches":
