@@ -277,20 +277,10 @@ extern "C" uint64_t ks_kmerpos_count(const ks_kmerpos *p) { return p ? p->n : 0;
 extern "C" void ks_kmerpos_params(const ks_kmerpos *p, ks_params *out) { if (p && out) *out = p->params; }
 
 extern "C" int ks_kmerpos_copy_to_host(ks_ctx *ctx, const ks_kmerpos *p, uint32_t *seq, uint32_t *start, uint64_t *hash) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !p) return KS_ERR_INVALID_ARG;
-    const size_t n = (size_t)p->n;
-    return ks_columns_to_host(ctx, {{seq, p->d_seq, n * sizeof(u32)}, {start, p->d_start, n * sizeof(u32)}, {hash, p->d_hash, n * sizeof(u64)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, p, seq, start, hash); });
 }
 
-extern "C" void ks_kmerpos_free(ks_kmerpos *p) {
-    if (!p) return;
-    ks_pool_free(p->ctx, p->d_seq);
-    ks_pool_free(p->ctx, p->d_start);
-    ks_pool_free(p->ctx, p->d_hash);
-    delete p;
-}
+extern "C" void ks_kmerpos_free(ks_kmerpos *p) { ks_obj_free(p); }
 
 // ---------------------------------------------------------------------------------------------
 // index + search
@@ -616,25 +606,11 @@ extern "C" const uint32_t *ks_rscores_device_core_identities(const ks_rscores *s
 extern "C" int ks_rscores_copy_to_host(ks_ctx *ctx, const ks_rscores *s, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
                                        uint32_t *length, int64_t *score, uint32_t *identities, uint32_t *positives,
                                        uint32_t *core_identities) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !s) return KS_ERR_INVALID_ARG;
-    const size_t nr = (size_t)s->n_rows, ng = (size_t)s->n_regions;
-    return ks_columns_to_host(ctx, {{row_offsets, s->d_row_offsets, (nr + 1) * sizeof(u64)},
-                                    {q_start, s->d_qstart, ng * sizeof(u32)}, {t_start, s->d_tstart, ng * sizeof(u32)},
-                                    {length, s->d_length, ng * sizeof(u32)}, {score, s->d_score, ng * sizeof(i64)},
-                                    {identities, s->d_identities, ng * sizeof(u32)}, {positives, s->d_positives, ng * sizeof(u32)},
-                                    {core_identities, s->d_core_ident, ng * sizeof(u32)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, s, row_offsets, q_start, t_start, length, score, identities, positives,
+                                                              core_identities); });
 }
 
-extern "C" void ks_rscores_free(ks_rscores *s) {
-    if (!s) return;
-    ks_pool_free(s->ctx, s->d_row_offsets);
-    ks_pool_free(s->ctx, s->d_qstart); ks_pool_free(s->ctx, s->d_tstart); ks_pool_free(s->ctx, s->d_length);
-    ks_pool_free(s->ctx, s->d_score); ks_pool_free(s->ctx, s->d_identities); ks_pool_free(s->ctx, s->d_positives);
-    ks_pool_free(s->ctx, s->d_core_ident);
-    delete s;
-}
+extern "C" void ks_rscores_free(ks_rscores *s) { ks_obj_free(s); }
 
 // ---------------------------------------------------------------------------------------------
 // region alignments (ks_ralign.hip): the regions of a hit list extended with gaps from the middle of their seeds
@@ -678,25 +654,11 @@ extern "C" const uint32_t *ks_raligns_device_aln_length(const ks_raligns *s) { r
 extern "C" int ks_raligns_copy_to_host(ks_ctx *ctx, const ks_raligns *s, uint64_t *row_offsets, uint32_t *q_start, uint32_t *q_length,
                                        uint32_t *t_start, uint32_t *t_length, int64_t *score, uint32_t *identities, uint32_t *positives,
                                        uint32_t *gap_opens, uint32_t *gaps, uint32_t *aln_length) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !s) return KS_ERR_INVALID_ARG;
-    const size_t nr = (size_t)s->n_rows, w = (size_t)s->n_regions * sizeof(u32);
-    return ks_columns_to_host(ctx, {{row_offsets, s->d_row_offsets, (nr + 1) * sizeof(u64)},
-                                    {q_start, s->d_qstart, w}, {q_length, s->d_qlength, w}, {t_start, s->d_tstart, w},
-                                    {t_length, s->d_tlength, w}, {score, s->d_score, (size_t)s->n_regions * sizeof(i64)},
-                                    {identities, s->d_identities, w}, {positives, s->d_positives, w}, {gap_opens, s->d_gap_opens, w},
-                                    {gaps, s->d_gaps, w}, {aln_length, s->d_aln_length, w}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, s, row_offsets, q_start, q_length, t_start, t_length, score, identities,
+                                                              positives, gap_opens, gaps, aln_length); });
 }
 
-extern "C" void ks_raligns_free(ks_raligns *s) {
-    if (!s) return;
-    for (void *p : {(void *)s->d_row_offsets, (void *)s->d_qstart, (void *)s->d_qlength, (void *)s->d_tstart, (void *)s->d_tlength,
-                    (void *)s->d_score, (void *)s->d_identities, (void *)s->d_positives, (void *)s->d_gap_opens, (void *)s->d_gaps,
-                    (void *)s->d_aln_length})
-        ks_pool_free(s->ctx, p);
-    delete s;
-}
+extern "C" void ks_raligns_free(ks_raligns *s) { ks_obj_free(s); }
 
 // ---------------------------------------------------------------------------------------------
 // region traceback (ks_rtrace.hip): the path of every alignment of a ks_raligns as a CIGAR
@@ -733,18 +695,10 @@ extern "C" const uint64_t *ks_cigars_device_op_offsets(const ks_cigars *c) { ret
 extern "C" const uint32_t *ks_cigars_device_ops(const ks_cigars *c) { return c ? c->d_ops : nullptr; }
 
 extern "C" int ks_cigars_copy_to_host(ks_ctx *ctx, const ks_cigars *c, uint64_t *op_offsets, uint32_t *ops) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !c) return KS_ERR_INVALID_ARG;
-    return ks_columns_to_host(ctx, {{op_offsets, c->d_op_offsets, ((size_t)c->n_regions + 1) * sizeof(u64)},
-                                    {ops, c->d_ops, (size_t)c->n_ops * sizeof(u32)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, c, op_offsets, ops); });
 }
 
-extern "C" void ks_cigars_free(ks_cigars *c) {
-    if (!c) return;
-    ks_pool_free(c->ctx, c->d_op_offsets); ks_pool_free(c->ctx, c->d_ops);
-    delete c;
-}
+extern "C" void ks_cigars_free(ks_cigars *c) { ks_obj_free(c); }
 
 // ---------------------------------------------------------------------------------------------
 // region cull (ks_rcull.hip): per hit row the regions no better region of the row covers; the objects of the kept regions
@@ -778,27 +732,21 @@ extern "C" int ks_regions_cull_device(ks_ctx *ctx, const uint64_t *d_row_offsets
     return ks_rcull_run(ctx, {d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length ? d_t_length : d_q_length, d_score}, n_rows, n_regions, o, out);
     });
 }
-extern "C" int ks_raligns_cull(ks_ctx *ctx, const ks_raligns *s, const ks_rcull_opts *opts, ks_rcull **out) {
-    return ks_guard(ctx, [&]() -> int {
+// the cull of an object's own columns (ks_rscores, ks_raligns)
+template <typename T> static int ks_rcull_of(ks_ctx *ctx, const T *s, const ks_rcull_opts *opts, ks_rcull **out) {
     ks_rcull_opts o;
     KS_TRY(ks_rcull_opts_check(ctx, opts, &o));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (out) *out = nullptr;
     if (!s) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_TRY(ks_inputs_check_ctx(ctx, "region cull", s));
-    return ks_rcull_run(ctx, {s->d_row_offsets, s->d_qstart, s->d_qlength, s->d_tstart, s->d_tlength, s->d_score}, s->n_rows, s->n_regions, o, out);
-    });
+    return ks_rcull_run(ctx, s->cols(), s->n_rows, s->n_regions, o, out);
+}
+extern "C" int ks_raligns_cull(ks_ctx *ctx, const ks_raligns *s, const ks_rcull_opts *opts, ks_rcull **out) {
+    return ks_guard(ctx, [&]() -> int { return ks_rcull_of(ctx, s, opts, out); });
 }
 extern "C" int ks_rscores_cull(ks_ctx *ctx, const ks_rscores *s, const ks_rcull_opts *opts, ks_rcull **out) {
-    return ks_guard(ctx, [&]() -> int {
-    ks_rcull_opts o;
-    KS_TRY(ks_rcull_opts_check(ctx, opts, &o));
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    if (!s) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    KS_TRY(ks_inputs_check_ctx(ctx, "region cull", s));
-    return ks_rcull_run(ctx, {s->d_row_offsets, s->d_qstart, s->d_length, s->d_tstart, s->d_length, s->d_score}, s->n_rows, s->n_regions, o, out);
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_rcull_of(ctx, s, opts, out); });
 }
 extern "C" uint64_t ks_rcull_n_rows(const ks_rcull *c) { return c ? c->n_rows : 0; }
 extern "C" uint64_t ks_rcull_n_regions(const ks_rcull *c) { return c ? c->n_regions : 0; }
@@ -812,21 +760,10 @@ extern "C" const double *ks_rcull_device_row_best_score(const ks_rcull *c) { ret
 
 extern "C" int ks_rcull_copy_to_host(ks_ctx *ctx, const ks_rcull *c, uint64_t *row_offsets, uint32_t *src_region, uint32_t *rank,
                                      uint32_t *n_merged, uint32_t *keeper, double *row_best_score) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !c) return KS_ERR_INVALID_ARG;
-    const size_t nr = (size_t)c->n_rows, k = (size_t)c->n_kept * sizeof(u32);
-    return ks_columns_to_host(ctx, {{row_offsets, c->d_row_offsets, (nr + 1) * sizeof(u64)}, {src_region, c->d_src_region, k},
-                                    {rank, c->d_rank, k}, {n_merged, c->d_n_merged, k},
-                                    {keeper, c->d_keeper, (size_t)c->n_regions * sizeof(u32)}, {row_best_score, c->d_row_best, nr * sizeof(double)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, c, row_offsets, src_region, rank, n_merged, keeper, row_best_score); });
 }
 
-extern "C" void ks_rcull_free(ks_rcull *c) {
-    if (!c) return;
-    for (void *p : {(void *)c->d_row_offsets, (void *)c->d_src_region, (void *)c->d_rank, (void *)c->d_n_merged, (void *)c->d_keeper, (void *)c->d_row_best})
-        ks_pool_free(c->ctx, p);
-    delete c;
-}
+extern "C" void ks_rcull_free(ks_rcull *c) { ks_obj_free(c); }
 
 // what the three takes check alike, and their row_offsets: a copy of the cull's
 template <typename T> static int ks_take_check(ks_ctx *ctx, const T *obj, const ks_rcull *cull, const void *out) {
@@ -843,59 +780,50 @@ template <typename T> static int ks_take_offsets(ks_ctx *ctx, const ks_rcull *cu
     KS_HIP(ctx, hipMemcpyAsync(o->d_row_offsets, cull->d_row_offsets, ((size_t)cull->n_rows + 1) * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
     return KS_OK;
 }
-extern "C" int ks_regions_take(ks_ctx *ctx, const ks_regions *regions, const ks_rcull *cull, ks_regions **out) {
-    return ks_guard(ctx, [&]() -> int {
+// the columns of o listed with n_regions: the 32-bit ones to c32[0 .. *n32), the 64-bit score to *c64
+template <typename T, typename P32, typename P64> static constexpr void ks_take_list(T &o, P32 *c32, u32 *n32, P64 *c64) {
+    T::each(o, [&](auto *p, const u64 &n, bool = true) {
+        if (&n != &o.n_regions) return;
+        if constexpr (std::is_convertible_v<decltype(p), P32>) c32[(*n32)++] = p;
+        else if constexpr (std::is_convertible_v<decltype(p), P64>) *c64 = p;
+    });
+}
+template <typename T> static constexpr u32 ks_take_n32() {
+    T z{};
+    const u32 *c32[64] = {};
+    const i64 *c64 = nullptr;
+    u32 k = 0;
+    ks_take_list(z, c32, &k, &c64);
+    return k;
+}
+// The regions a cull kept, of any of the three objects: every column listed with n_regions moves through the cull's src_region into
+// a block of n_kept entries (ks_rcull_take_launch); take_from copies what else the type holds.
+template <typename T> static int ks_obj_take(ks_ctx *ctx, const T *src, const ks_rcull *cull, T **out, void (*free_fn)(T *)) {
+    static_assert(ks_take_n32<T>() <= KS_TAKE_COLS, "a take moves more 32-bit columns than ks_take_cols holds");
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (out) *out = nullptr;
-    KS_TRY(ks_take_check(ctx, regions, cull, out));
+    KS_TRY(ks_take_check(ctx, src, cull, out));
     KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_result<ks_regions> R(ctx, out, ks_regions_free);
+    ks_result<T> R(ctx, out, free_fn);
     KS_TRY(ks_take_offsets(ctx, cull, R.obj));
-    R->n_slices = regions->n_slices;
-    ks_take_cols C{{regions->d_qstart, regions->d_tstart, regions->d_length, regions->d_nkmers, regions->d_covered}, {}, 5, nullptr, nullptr};
-    u32 **dst[5] = {&R->d_qstart, &R->d_tstart, &R->d_length, &R->d_nkmers, &R->d_covered};
-    for (u32 c = 0; c < 5; c++) { KS_TRY(ks_alloc(ctx, dst[c], (size_t)cull->n_kept)); C.out[c] = *dst[c]; }
+    R->take_from(*src);
+    KS_TRY(ks_obj_alloc(ctx, R.obj, R->n_regions));
+    ks_take_cols C{};
+    u32 n_out = 0;
+    ks_take_list(*src, C.in, &C.n32, &C.in64);
+    ks_take_list(*R.obj, C.out, &n_out, &C.out64);
     KS_TRY(ks_rcull_take_launch(ctx, cull, C));
     KS_TRY(ks_stream_wait(ctx));
     return R.commit();
-    });
+}
+extern "C" int ks_regions_take(ks_ctx *ctx, const ks_regions *regions, const ks_rcull *cull, ks_regions **out) {
+    return ks_guard(ctx, [&]() -> int { return ks_obj_take(ctx, regions, cull, out, ks_regions_free); });
 }
 extern "C" int ks_rscores_take(ks_ctx *ctx, const ks_rscores *scores, const ks_rcull *cull, ks_rscores **out) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    KS_TRY(ks_take_check(ctx, scores, cull, out));
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_result<ks_rscores> S(ctx, out, ks_rscores_free);
-    KS_TRY(ks_take_offsets(ctx, cull, S.obj));
-    ks_take_cols C{{scores->d_qstart, scores->d_tstart, scores->d_length, scores->d_identities, scores->d_positives, scores->d_core_ident}, {}, 6, scores->d_score, nullptr};
-    u32 **dst[6] = {&S->d_qstart, &S->d_tstart, &S->d_length, &S->d_identities, &S->d_positives, &S->d_core_ident};
-    for (u32 c = 0; c < 6; c++) { KS_TRY(ks_alloc(ctx, dst[c], (size_t)cull->n_kept)); C.out[c] = *dst[c]; }
-    KS_TRY(ks_alloc(ctx, &S->d_score, (size_t)cull->n_kept)); C.out64 = S->d_score;
-    KS_TRY(ks_rcull_take_launch(ctx, cull, C));
-    KS_TRY(ks_stream_wait(ctx));
-    return S.commit();
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_take(ctx, scores, cull, out, ks_rscores_free); });
 }
 extern "C" int ks_raligns_take(ks_ctx *ctx, const ks_raligns *s, const ks_rcull *cull, ks_raligns **out) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    KS_TRY(ks_take_check(ctx, s, cull, out));
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_result<ks_raligns> S(ctx, out, ks_raligns_free);
-    KS_TRY(ks_take_offsets(ctx, cull, S.obj));
-    S->band = s->band; S->gap_open = s->gap_open; S->gap_extend = s->gap_extend; S->x_drop = s->x_drop;
-    memcpy(S->matrix, s->matrix, sizeof S->matrix);
-    ks_take_cols C{{s->d_qstart, s->d_qlength, s->d_tstart, s->d_tlength, s->d_identities, s->d_positives, s->d_gap_opens, s->d_gaps, s->d_aln_length}, {}, 9,
-                   s->d_score, nullptr};
-    u32 **dst[9] = {&S->d_qstart, &S->d_qlength, &S->d_tstart, &S->d_tlength, &S->d_identities, &S->d_positives, &S->d_gap_opens, &S->d_gaps, &S->d_aln_length};
-    for (u32 c = 0; c < 9; c++) { KS_TRY(ks_alloc(ctx, dst[c], (size_t)cull->n_kept)); C.out[c] = *dst[c]; }
-    KS_TRY(ks_alloc(ctx, &S->d_score, (size_t)cull->n_kept)); C.out64 = S->d_score;
-    KS_TRY(ks_rcull_take_launch(ctx, cull, C));
-    KS_TRY(ks_stream_wait(ctx));
-    return S.commit();
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_take(ctx, s, cull, out, ks_raligns_free); });
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -929,33 +857,25 @@ extern "C" int ks_regions_chain_device(ks_ctx *ctx, const uint64_t *d_row_offset
     KS_TRY(ks_rchain_opts_check(ctx, opts, &o));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (out) *out = nullptr;
-    return ks_rchain_run(ctx, {d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length ? d_t_length : d_q_length, d_score, d_identities, d_aln_length},
+    return ks_rchain_run(ctx, {{d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length ? d_t_length : d_q_length, d_score}, d_identities, d_aln_length},
                          n_rows, n_regions, o, out);
     });
 }
-extern "C" int ks_raligns_chain(ks_ctx *ctx, const ks_raligns *s, const ks_rchain_opts *opts, ks_rchain **out) {
-    return ks_guard(ctx, [&]() -> int {
+// the chain of an object's own columns (ks_rscores, ks_raligns)
+template <typename T> static int ks_rchain_of(ks_ctx *ctx, const T *s, const ks_rchain_opts *opts, ks_rchain **out) {
     ks_rchain_opts o;
     KS_TRY(ks_rchain_opts_check(ctx, opts, &o));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (out) *out = nullptr;
     if (!s) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_TRY(ks_inputs_check_ctx(ctx, "region chain", s));
-    return ks_rchain_run(ctx, {s->d_row_offsets, s->d_qstart, s->d_qlength, s->d_tstart, s->d_tlength, s->d_score, s->d_identities, s->d_aln_length},
-                         s->n_rows, s->n_regions, o, out);
-    });
+    return ks_rchain_run(ctx, s->cols(), s->n_rows, s->n_regions, o, out);
+}
+extern "C" int ks_raligns_chain(ks_ctx *ctx, const ks_raligns *s, const ks_rchain_opts *opts, ks_rchain **out) {
+    return ks_guard(ctx, [&]() -> int { return ks_rchain_of(ctx, s, opts, out); });
 }
 extern "C" int ks_rscores_chain(ks_ctx *ctx, const ks_rscores *s, const ks_rchain_opts *opts, ks_rchain **out) {
-    return ks_guard(ctx, [&]() -> int {
-    ks_rchain_opts o;
-    KS_TRY(ks_rchain_opts_check(ctx, opts, &o));
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    if (!s) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    KS_TRY(ks_inputs_check_ctx(ctx, "region chain", s));
-    return ks_rchain_run(ctx, {s->d_row_offsets, s->d_qstart, s->d_length, s->d_tstart, s->d_length, s->d_score, s->d_identities, s->d_length},
-                         s->n_rows, s->n_regions, o, out);
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_rchain_of(ctx, s, opts, out); });
 }
 extern "C" uint64_t ks_rchain_n_rows(const ks_rchain *c) { return c ? c->n_rows : 0; }
 extern "C" uint64_t ks_rchain_n_regions(const ks_rchain *c) { return c ? c->n_regions : 0; }
@@ -979,25 +899,11 @@ extern "C" const double *ks_rchain_device_row_coverage(const ks_rchain *c) { ret
 extern "C" int ks_rchain_copy_to_host(ks_ctx *ctx, const ks_rchain *c, uint64_t *row_offsets, uint32_t *src_region, int64_t *best, uint32_t *pred,
                                       int64_t *chain_score, uint32_t *q_start, uint32_t *q_length, uint32_t *t_start, uint32_t *t_length,
                                       uint32_t *q_aligned, uint32_t *t_aligned, uint64_t *identities, uint64_t *aln_length, double *row_chain_score) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !c) return KS_ERR_INVALID_ARG;
-    const size_t nr = (size_t)c->n_rows, n = (size_t)c->n_regions, r4 = nr * sizeof(u32), r8 = nr * sizeof(u64);
-    return ks_columns_to_host(ctx, {{row_offsets, c->d_row_offsets, (nr + 1) * sizeof(u64)}, {src_region, c->d_src_region, (size_t)c->n_chained * sizeof(u32)},
-                                    {best, c->d_best, n * sizeof(i64)}, {pred, c->d_pred, n * sizeof(u32)}, {chain_score, c->d_chain_score, r8},
-                                    {q_start, c->d_q_start, r4}, {q_length, c->d_q_length, r4}, {t_start, c->d_t_start, r4}, {t_length, c->d_t_length, r4},
-                                    {q_aligned, c->d_q_aligned, r4}, {t_aligned, c->d_t_aligned, r4}, {identities, c->d_identities, r8},
-                                    {aln_length, c->d_aln_length, r8}, {row_chain_score, c->d_row_score, r8}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, c, row_offsets, src_region, best, pred, chain_score, q_start, q_length, t_start,
+                                                              t_length, q_aligned, t_aligned, identities, aln_length, row_chain_score); });
 }
 
-extern "C" void ks_rchain_free(ks_rchain *c) {
-    if (!c) return;
-    for (void *p : {(void *)c->d_row_offsets, (void *)c->d_src_region, (void *)c->d_best, (void *)c->d_pred, (void *)c->d_chain_score, (void *)c->d_q_start,
-                    (void *)c->d_q_length, (void *)c->d_t_start, (void *)c->d_t_length, (void *)c->d_q_aligned, (void *)c->d_t_aligned, (void *)c->d_identities,
-                    (void *)c->d_aln_length, (void *)c->d_row_score, (void *)c->d_row_cov})
-        ks_pool_free(c->ctx, p);
-    delete c;
-}
+extern "C" void ks_rchain_free(ks_rchain *c) { ks_obj_free(c); }
 
 extern "C" int ks_rchain_coverage(ks_ctx *ctx, ks_rchain *chain, const ks_hits *hits, const uint64_t *d_q_off, uint32_t n_q, const uint64_t *d_t_off,
                                   uint32_t n_t, uint32_t mode) {
@@ -1017,7 +923,8 @@ extern "C" int ks_rchain_coverage_to_host(ks_ctx *ctx, const ks_rchain *c, doubl
     return ks_guard(ctx, [&]() -> int {
     if (!ctx || !c) return KS_ERR_INVALID_ARG;
     if (!c->d_row_cov) return ks_fail(ctx, KS_ERR_INVALID_ARG, "chain coverage: ks_rchain_coverage has not filled the column");
-    return ks_columns_to_host(ctx, {{row_coverage, c->d_row_cov, (size_t)c->n_rows * sizeof(double)}});
+    const ks_column col{row_coverage, c->d_row_cov, (size_t)c->n_rows * sizeof(double)};
+    return ks_columns_to_host(ctx, &col, 1);
     });
 }
 
@@ -1080,24 +987,9 @@ extern "C" int ks_hitalns_copy_to_host(ks_ctx *ctx, const ks_hitalns *a, uint64_
                                        uint32_t *t_start, uint32_t *t_length, int64_t *score, uint32_t *identities, uint32_t *positives,
                                        uint32_t *gap_opens, uint32_t *gaps, uint32_t *aln_length, uint32_t *n_members, uint32_t *n_filled,
                                        uint32_t *n_open, uint32_t *n_trimmed, double *row_score) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !a) return KS_ERR_INVALID_ARG;
-    const size_t nr = (size_t)a->n_rows, r4 = nr * sizeof(u32), r8 = nr * sizeof(u64);
-    return ks_columns_to_host(ctx, {{op_offsets, a->d_op_offsets, (nr + 1) * sizeof(u64)}, {ops, a->d_ops, (size_t)a->n_ops * sizeof(u32)},
-                                    {q_start, a->d_q_start, r4}, {q_length, a->d_q_length, r4}, {t_start, a->d_t_start, r4}, {t_length, a->d_t_length, r4},
-                                    {score, a->d_score, r8}, {identities, a->d_identities, r4}, {positives, a->d_positives, r4},
-                                    {gap_opens, a->d_gap_opens, r4}, {gaps, a->d_gaps, r4}, {aln_length, a->d_aln_length, r4},
-                                    {n_members, a->d_n_members, r4}, {n_filled, a->d_n_filled, r4}, {n_open, a->d_n_open, r4},
-                                    {n_trimmed, a->d_n_trimmed, r4}, {row_score, a->d_row_score, r8}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, a, op_offsets, ops, q_start, q_length, t_start, t_length, score, identities,
+                                                              positives, gap_opens, gaps, aln_length, n_members, n_filled, n_open, n_trimmed,
+                                                              row_score); });
 }
 
-extern "C" void ks_hitalns_free(ks_hitalns *a) {
-    if (!a) return;
-    for (void *p : {(void *)a->d_op_offsets, (void *)a->d_ops, (void *)a->d_score, (void *)a->d_q_start, (void *)a->d_q_length, (void *)a->d_t_start,
-                    (void *)a->d_t_length, (void *)a->d_identities, (void *)a->d_positives, (void *)a->d_gap_opens, (void *)a->d_gaps,
-                    (void *)a->d_aln_length, (void *)a->d_n_members, (void *)a->d_n_filled, (void *)a->d_n_open, (void *)a->d_n_trimmed,
-                    (void *)a->d_row_score})
-        ks_pool_free(a->ctx, p);
-    delete a;
-}
+extern "C" void ks_hitalns_free(ks_hitalns *a) { ks_obj_free(a); }

@@ -191,18 +191,9 @@ extern "C" const uint32_t *ks_rcomp_device_counts(const ks_rcomp *c) { return c 
 extern "C" const uint64_t *ks_rcomp_device_totals(const ks_rcomp *c) { return c ? c->d_totals : nullptr; }
 extern "C" const uint32_t *ks_rcomp_device_length(const ks_rcomp *c) { return c ? c->d_length : nullptr; }
 extern "C" int ks_rcomp_copy_to_host(ks_ctx *ctx, const ks_rcomp *c, uint32_t *counts, uint64_t *totals, uint32_t *length) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !c) return KS_ERR_INVALID_ARG;
-    const size_t ns = c->n_seqs;
-    return ks_columns_to_host(ctx, {{counts, c->d_counts, ns * AC_A * sizeof(u32)}, {totals, c->d_totals, AC_A * sizeof(u64)},
-                                    {length, c->d_length, ns * sizeof(u32)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, c, counts, totals, length); });
 }
-extern "C" void ks_rcomp_free(ks_rcomp *c) {
-    if (!c) return;
-    for (void *p : {(void *)c->d_counts, (void *)c->d_totals, (void *)c->d_length}) ks_pool_free(c->ctx, p);
-    delete c;
-}
+extern "C" void ks_rcomp_free(ks_rcomp *c) { ks_obj_free(c); }
 extern "C" void ks_debug_rcomp_limits(uint32_t *wave_max, uint32_t *group_max) {
     if (wave_max) *wave_max = AC_WAVE_MAX;
     if (group_max) *group_max = AC_GROUP_MAX;
@@ -604,52 +595,43 @@ static int as_run(ks_ctx *ctx, const u64 *d_row_offs, const i64 *d_score, u64 n_
     return S.commit();
 }
 
+// What the four entries do alike, in their order: the options (also without a context), the context, *out, the objects the scores
+// come from (`in`: not NULL, of ctx), then `run`, which reads them.  recorded: the gapped alignments behind the scores, or NULL
+template <typename Run, typename... In>
+static int as_entry(ks_ctx *ctx, const ks_astats_opts *opts, const ks_raligns *recorded, bool gapped, ks_astats **out, Run &&run, const In *...in) {
+    return ks_guard(ctx, [&]() -> int {
+    ks_astats_opts o;
+    KS_TRY(as_opts_check(ctx, opts, recorded ? recorded->matrix : nullptr, gapped, &o));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    if ((!in || ...)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    if constexpr (sizeof...(In) != 0) KS_TRY(ks_inputs_check_ctx(ctx, "alignment statistics", in...));
+    return run(o);
+    });
+}
 extern "C" int ks_scores_stats_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const int64_t *d_score, uint64_t n_rows, uint64_t n,
                                       const ks_hits *hits, const ks_rcomp *q_comp, const ks_rcomp *t_comp, const ks_astats_opts *opts,
                                       ks_astats **out) {
-    return ks_guard(ctx, [&]() -> int {
-    ks_astats_opts o;
-    KS_TRY(as_opts_check(ctx, opts, nullptr, false, &o));
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    return as_run(ctx, d_row_offsets, d_score, n_rows, n, hits, q_comp, t_comp, o, out);
-    });
+    return as_entry(ctx, opts, nullptr, false, out,
+                    [&](const ks_astats_opts &o) { return as_run(ctx, d_row_offsets, d_score, n_rows, n, hits, q_comp, t_comp, o, out); });
 }
 extern "C" int ks_rscores_stats(ks_ctx *ctx, const ks_rscores *scores, const ks_hits *hits, const ks_rcomp *q_comp, const ks_rcomp *t_comp,
                                 const ks_astats_opts *opts, ks_astats **out) {
-    return ks_guard(ctx, [&]() -> int {
-    ks_astats_opts o;
-    KS_TRY(as_opts_check(ctx, opts, nullptr, false, &o));
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    if (!scores) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    KS_TRY(ks_inputs_check_ctx(ctx, "alignment statistics", scores));
-    return as_run(ctx, scores->d_row_offsets, scores->d_score, scores->n_rows, scores->n_regions, hits, q_comp, t_comp, o, out);
-    });
+    return as_entry(ctx, opts, nullptr, false, out, [&](const ks_astats_opts &o) {
+        return as_run(ctx, scores->d_row_offsets, scores->d_score, scores->n_rows, scores->n_regions, hits, q_comp, t_comp, o, out);
+    }, scores);
 }
 extern "C" int ks_raligns_stats(ks_ctx *ctx, const ks_raligns *alignments, const ks_hits *hits, const ks_rcomp *q_comp, const ks_rcomp *t_comp,
                                 const ks_astats_opts *opts, ks_astats **out) {
-    return ks_guard(ctx, [&]() -> int {
-    ks_astats_opts o;
-    KS_TRY(as_opts_check(ctx, opts, alignments ? alignments->matrix : nullptr, true, &o));
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    if (!alignments) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    KS_TRY(ks_inputs_check_ctx(ctx, "alignment statistics", alignments));
-    return as_run(ctx, alignments->d_row_offsets, alignments->d_score, alignments->n_rows, alignments->n_regions, hits, q_comp, t_comp, o, out);
-    });
+    return as_entry(ctx, opts, alignments, true, out, [&](const ks_astats_opts &o) {
+        return as_run(ctx, alignments->d_row_offsets, alignments->d_score, alignments->n_rows, alignments->n_regions, hits, q_comp, t_comp, o, out);
+    }, alignments);
 }
 extern "C" int ks_hitalns_stats(ks_ctx *ctx, const ks_hitalns *stitched, const ks_raligns *alignments, const ks_hits *hits, const ks_rcomp *q_comp,
                                 const ks_rcomp *t_comp, const ks_astats_opts *opts, ks_astats **out) {
-    return ks_guard(ctx, [&]() -> int {
-    ks_astats_opts o;
-    KS_TRY(as_opts_check(ctx, opts, alignments ? alignments->matrix : nullptr, true, &o));
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    if (!stitched || !alignments) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
-    KS_TRY(ks_inputs_check_ctx(ctx, "alignment statistics", stitched, alignments));
-    return as_run(ctx, nullptr, stitched->d_score, stitched->n_rows, stitched->n_rows, hits, q_comp, t_comp, o, out);
-    });
+    return as_entry(ctx, opts, alignments, true, out, [&](const ks_astats_opts &o) {
+        return as_run(ctx, nullptr, stitched->d_score, stitched->n_rows, stitched->n_rows, hits, q_comp, t_comp, o, out);
+    }, stitched, alignments);
 }
 
 extern "C" uint64_t ks_astats_n_rows(const ks_astats *s) { return s ? s->n_rows : 0; }
@@ -668,16 +650,6 @@ extern "C" const double *ks_astats_device_row_bit_score(const ks_astats *s) { re
 extern "C" const double *ks_astats_device_row_evalue(const ks_astats *s) { return s ? s->d_row_evalue : nullptr; }
 extern "C" int ks_astats_copy_to_host(ks_ctx *ctx, const ks_astats *s, uint8_t *status, double *x, double *lambda_ratio, double *bit_score,
                                       double *evalue, double *row_bit_score, double *row_evalue) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !s) return KS_ERR_INVALID_ARG;
-    const size_t nr = (size_t)s->n_rows, rb = nr * sizeof(double), eb = (size_t)s->n * sizeof(double);
-    return ks_columns_to_host(ctx, {{status, s->d_status, nr}, {x, s->d_x, rb}, {lambda_ratio, s->d_ratio, rb}, {bit_score, s->d_bit, eb},
-                                    {evalue, s->d_evalue, eb}, {row_bit_score, s->d_row_bit, rb}, {row_evalue, s->d_row_evalue, rb}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, s, status, x, lambda_ratio, bit_score, evalue, row_bit_score, row_evalue); });
 }
-extern "C" void ks_astats_free(ks_astats *s) {
-    if (!s) return;
-    for (void *p : {(void *)s->d_status, (void *)s->d_x, (void *)s->d_ratio, (void *)s->d_row_bit, (void *)s->d_row_evalue, (void *)s->d_bit, (void *)s->d_evalue})
-        ks_pool_free(s->ctx, p);
-    delete s;
-}
+extern "C" void ks_astats_free(ks_astats *s) { ks_obj_free(s); }

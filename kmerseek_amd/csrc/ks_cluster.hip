@@ -323,18 +323,7 @@ extern "C" const uint32_t *ks_clusters_device_representative(const ks_clusters *
 
 extern "C" int ks_clusters_copy_to_host(ks_ctx *ctx, const ks_clusters *c, uint32_t *label, uint32_t *cluster_id, uint64_t *offsets, uint32_t *members,
                                         uint32_t *representative) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !c) return KS_ERR_INVALID_ARG;
-    const size_t n = (size_t)c->n_nodes, nc = (size_t)c->n_clusters;
-    return ks_columns_to_host(ctx, {{label, c->d_label, n * sizeof(u32)}, {cluster_id, c->d_cluster_id, n * sizeof(u32)},
-                                    {offsets, c->d_offsets, (nc + 1) * sizeof(u64)}, {members, c->d_members, n * sizeof(u32)},
-                                    {representative, c->d_rep, nc * sizeof(u32)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, c, label, cluster_id, offsets, members, representative); });
 }
 
-extern "C" void ks_clusters_free(ks_clusters *c) {
-    if (!c) return;
-    ks_pool_free(c->ctx, c->d_label); ks_pool_free(c->ctx, c->d_cluster_id); ks_pool_free(c->ctx, c->d_members);
-    ks_pool_free(c->ctx, c->d_rep); ks_pool_free(c->ctx, c->d_offsets);
-    delete c;
-}
+extern "C" void ks_clusters_free(ks_clusters *c) { ks_obj_free(c); }

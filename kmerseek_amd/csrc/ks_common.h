@@ -277,6 +277,62 @@ struct ks_result {
     int commit() { *out = obj; obj = nullptr; return KS_OK; }
 };
 
+// the body of every *_copy_to_host: each column with a destination and bytes to copy goes through ks_copy_d2h, then one wait
+struct ks_column { void *dst; const void *src; size_t bytes; };
+int ks_copy_d2h(ks_ctx *ctx, void *dst_host, const void *src_device, size_t bytes);
+static inline int ks_columns_to_host(ks_ctx *ctx, const ks_column *cols, size_t n) {
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    for (const ks_column *c = cols; c < cols + n; c++)
+        if (c->dst && c->bytes) KS_TRY(ks_copy_d2h(ctx, c->dst, c->src, c->bytes));
+    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return KS_OK;
+}
+int ks_columns_to_host(ks_ctx *ctx, std::initializer_list<ks_column> cols); // ks_copy.hip
+
+// ---- the column list of a result object ----
+// A result struct names its device columns ONCE, in its member `each`: f(column, element count) for every column, in the order
+// of the object's copy_to_host parameters; a third argument `false` marks a column made on demand, which copy_to_host does not
+// carry and ks_obj_alloc leaves alone.  The walks below are all that frees, copies out, allocates and (ks_obj_take, ks_api.hip)
+// takes them.  Where the count is a member of the struct, `each` passes that member itself (s.n_regions, no copy of it): a walk
+// over the columns of ONE count knows them by the member's address, so that two counts of equal value stay two.
+// every column back to the pool (NULL: never allocated), then the object
+template <class T>
+static inline void ks_obj_free(T *o) {
+    if (!o) return;
+    T::each(*o, [&](auto *p, const u64 &, bool = true) { ks_pool_free(o->ctx, p); });
+    delete o;
+}
+// the body of ks_<object>_copy_to_host, behind its ks_guard: dst are its destination parameters in their order (NULL: skip that column)
+template <class T, class... D>
+static inline int ks_obj_to_host(ks_ctx *ctx, const T *o, D *...dst) {
+    if (!ctx || !o) return KS_ERR_INVALID_ARG;
+    void *const to[] = {dst...};
+    const size_t elem[] = {sizeof(D)...};
+    ks_column cols[sizeof...(D)];
+    size_t i = 0;
+    bool same = true;
+    T::each(*o, [&](auto *p, const u64 &n, bool copied = true) {
+        if (!copied) return;
+        if (i < sizeof...(D) && elem[i] == sizeof(*p)) cols[i] = ks_column{to[i], p, (size_t)n * sizeof(*p)};
+        else same = false;
+        i++;
+    });
+    if (!same || i != sizeof...(D)) return ks_fail(ctx, KS_ERR_HIP, "internal error: a column list and its copy_to_host differ");
+    return ks_columns_to_host(ctx, cols, i);
+}
+// the columns of o listed with the member `count`, allocated at its value (set before the call)
+template <class T>
+static inline int ks_obj_alloc(ks_ctx *ctx, T *o, const u64 &count) {
+    int st = KS_OK;
+    bool any = false;
+    T::each(*o, [&](auto *&p, const u64 &n, bool up_front = true) {
+        if (&n != &count || !up_front || st != KS_OK) return;
+        st = ks_alloc(ctx, &p, (size_t)n);
+        any = true;
+    });
+    return any ? st : ks_fail(ctx, KS_ERR_HIP, "internal error: no column is listed with that count");
+}
+
 // ---- opaque objects ----
 struct ks_sketches {
     ks_ctx *ctx;
@@ -465,6 +521,7 @@ struct ks_kmerpos {
     u64 n;
     u32 *d_seq, *d_start;
     u64 *d_hash;
+    template <class S, class F> static constexpr void each(S &s, F &&f) { f(s.d_seq, s.n); f(s.d_start, s.n); f(s.d_hash, s.n); }
 };
 
 // pairs of window starts that share a hash, grouped by hit row (ks_matchpos.hip)
@@ -477,6 +534,10 @@ struct ks_matchpos {
     u64 *d_row_offsets;          // n_rows + 1
     u32 *d_qstart, *d_tstart;    // n_pairs
     u32 *d_qlo, *d_qhi, *d_tlo, *d_thi; // n_rows
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_row_offsets, s.n_rows + 1); f(s.d_qstart, s.n_pairs); f(s.d_tstart, s.n_pairs);
+        f(s.d_qlo, s.n_rows); f(s.d_qhi, s.n_rows); f(s.d_tlo, s.n_rows); f(s.d_thi, s.n_rows);
+    }
 };
 
 // chained pairs of one hit row: maximal colinear runs of shared k-mers (ks_regions.hip)
@@ -486,7 +547,17 @@ struct ks_regions {
     u32 n_slices;
     u64 *d_row_offsets;                                 // n_rows + 1
     u32 *d_qstart, *d_tstart, *d_length, *d_nkmers, *d_covered; // n_regions
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_row_offsets, s.n_rows + 1); f(s.d_qstart, s.n_regions); f(s.d_tstart, s.n_regions); f(s.d_length, s.n_regions);
+        f(s.d_nkmers, s.n_regions); f(s.d_covered, s.n_regions);
+    }
+    void take_from(const ks_regions &src) { n_slices = src.n_slices; } // what a take copies besides the columns
 };
+
+// the columns of a cull's input on the device; tl == ql for regions of one length
+struct ks_rcull_cols { const u64 *row_offs; const u32 *qs, *ql, *ts, *tl; const i64 *score; };
+// ... and of a chain's: the same and ident, alen: NULL or a column to sum
+struct ks_rchain_cols : ks_rcull_cols { const u32 *ident, *alen; };
 
 // the regions of a ks_regions scored under a substitution matrix and extended without gaps (ks_rscore.hip)
 struct ks_rscores {
@@ -495,6 +566,13 @@ struct ks_rscores {
     u64 *d_row_offsets;                                                              // n_rows + 1
     u32 *d_qstart, *d_tstart, *d_length, *d_identities, *d_positives, *d_core_ident; // n_regions
     i64 *d_score;                                                                    // n_regions
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_row_offsets, s.n_rows + 1); f(s.d_qstart, s.n_regions); f(s.d_tstart, s.n_regions); f(s.d_length, s.n_regions);
+        f(s.d_score, s.n_regions); f(s.d_identities, s.n_regions); f(s.d_positives, s.n_regions); f(s.d_core_ident, s.n_regions);
+    }
+    void take_from(const ks_rscores &) {}
+    // the view a cull / a chain reads: one length for both sides, which is also the alignment length
+    ks_rchain_cols cols() const { return {{d_row_offsets, d_qstart, d_length, d_tstart, d_length, d_score}, d_identities, d_length}; }
 };
 // one residue batch on the device, as the C ABI passes it
 struct ks_res_batch { const u8 *res; const u64 *offs; u32 n_seqs; u64 n_res; };
@@ -513,6 +591,16 @@ struct ks_raligns {
     // the options the alignments were made with: ks_regions_traceback walks the path of exactly this program
     u32 band, gap_open, gap_extend, x_drop;
     int8_t matrix[KS_RSCORE_ALPHABET * KS_RSCORE_ALPHABET];
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_row_offsets, s.n_rows + 1); f(s.d_qstart, s.n_regions); f(s.d_qlength, s.n_regions); f(s.d_tstart, s.n_regions);
+        f(s.d_tlength, s.n_regions); f(s.d_score, s.n_regions); f(s.d_identities, s.n_regions); f(s.d_positives, s.n_regions);
+        f(s.d_gap_opens, s.n_regions); f(s.d_gaps, s.n_regions); f(s.d_aln_length, s.n_regions);
+    }
+    void take_from(const ks_raligns &src) {
+        band = src.band; gap_open = src.gap_open; gap_extend = src.gap_extend; x_drop = src.x_drop;
+        memcpy(matrix, src.matrix, sizeof matrix);
+    }
+    ks_rchain_cols cols() const { return {{d_row_offsets, d_qstart, d_qlength, d_tstart, d_tlength, d_score}, d_identities, d_aln_length}; }
 };
 // ks_regions_align behind its argument checks (opts: not NULL, validated; R, H: of ctx, equal row counts)
 int ks_regions_align_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
@@ -526,6 +614,7 @@ struct ks_cigars {
     u32 *d_ops;        // n_ops: len << 4 | op
     u64 dir_bytes;     // direction scratch the call allocated, the slices it ran in (diagnostic)
     u32 n_slices;
+    template <class S, class F> static constexpr void each(S &s, F &&f) { f(s.d_op_offsets, s.n_regions + 1); f(s.d_ops, s.n_ops); }
 };
 // ks_regions_traceback behind its argument checks (flags validated; R, H, S: of ctx, equal counts)
 int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
@@ -539,9 +628,11 @@ struct ks_rcull {
     u32 *d_src_region, *d_rank, *d_n_merged; // n_kept (blocks of n_regions entries)
     u32 *d_keeper;                       // n_regions
     double *d_row_best;                  // n_rows
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_row_offsets, s.n_rows + 1); f(s.d_src_region, s.n_kept); f(s.d_rank, s.n_kept); f(s.d_n_merged, s.n_kept);
+        f(s.d_keeper, s.n_regions); f(s.d_row_best, s.n_rows);
+    }
 };
-// the columns of a cull's input on the device; tl == ql for regions of one length
-struct ks_rcull_cols { const u64 *row_offs; const u32 *qs, *ql, *ts, *tl; const i64 *score; };
 // ks_regions_cull_device behind its argument checks (opts: validated, defaults filled in; n_regions == 0 where n_rows == 0)
 int ks_regions_cull_impl(ks_ctx *ctx, const ks_rcull_cols &cols, u64 n_rows, u64 n_regions, const ks_rcull_opts *opts, ks_rcull *K);
 // out[c][i] = in[c][src[i]] for i < n and every listed column (at most KS_TAKE_COLS of 32 bits, one of 64), enqueued
@@ -561,10 +652,14 @@ struct ks_rchain {
     u32 *d_q_start, *d_q_length, *d_t_start, *d_t_length, *d_q_aligned, *d_t_aligned;
     u64 *d_identities, *d_aln_length;
     double *d_row_score;
-    double *d_row_cov;                   // NULL until ks_rchain_coverage has run
+    double *d_row_cov;                   // NULL until ks_rchain_coverage has run: not a column of copy_to_host
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_row_offsets, s.n_rows + 1); f(s.d_src_region, s.n_chained); f(s.d_best, s.n_regions); f(s.d_pred, s.n_regions);
+        f(s.d_chain_score, s.n_rows); f(s.d_q_start, s.n_rows); f(s.d_q_length, s.n_rows); f(s.d_t_start, s.n_rows);
+        f(s.d_t_length, s.n_rows); f(s.d_q_aligned, s.n_rows); f(s.d_t_aligned, s.n_rows); f(s.d_identities, s.n_rows);
+        f(s.d_aln_length, s.n_rows); f(s.d_row_score, s.n_rows); f(s.d_row_cov, s.n_rows, false);
+    }
 };
-// the columns of a chain's input on the device; tl == ql for regions of one length; ident, alen: NULL or a column to sum
-struct ks_rchain_cols { const u64 *row_offs; const u32 *qs, *ql, *ts, *tl; const i64 *score; const u32 *ident, *alen; };
 // ks_regions_chain_device behind its argument checks (opts: validated, not NULL; n_regions == 0 where n_rows == 0)
 int ks_regions_chain_impl(ks_ctx *ctx, const ks_rchain_cols &cols, u64 n_rows, u64 n_regions, const ks_rchain_opts *opts, ks_rchain *K);
 // ks_rchain_coverage behind its argument checks (H: of ctx, K's row count; mode <= 3)
@@ -583,6 +678,13 @@ struct ks_hitalns {
     double *d_row_score;
     u64 dir_bytes;                       // direction scratch the call allocated, the slices it ran in (diagnostic)
     u32 n_slices;
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_op_offsets, s.n_rows + 1); f(s.d_ops, s.n_ops); f(s.d_q_start, s.n_rows); f(s.d_q_length, s.n_rows);
+        f(s.d_t_start, s.n_rows); f(s.d_t_length, s.n_rows); f(s.d_score, s.n_rows); f(s.d_identities, s.n_rows);
+        f(s.d_positives, s.n_rows); f(s.d_gap_opens, s.n_rows); f(s.d_gaps, s.n_rows); f(s.d_aln_length, s.n_rows);
+        f(s.d_n_members, s.n_rows); f(s.d_n_filled, s.n_rows); f(s.d_n_open, s.n_rows); f(s.d_n_trimmed, s.n_rows);
+        f(s.d_row_score, s.n_rows);
+    }
 };
 // ks_regions_stitch behind its argument checks (options validated, defaults filled in; K, S, G, H: of ctx, equal counts)
 int ks_regions_stitch_impl(ks_ctx *ctx, const ks_rchain *K, const ks_raligns *S, const ks_cigars *G, const ks_hits *H, const ks_res_batch &Q,
@@ -597,6 +699,9 @@ struct ks_rcomp {
     u64 *d_totals;  // KS_RSCORE_ALPHABET
     u32 *d_length;  // n_seqs
     u64 h_totals[KS_RSCORE_ALPHABET]; // the totals again: the default background of ks_scores_stats_device
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_counts, (u64)s.n_seqs * KS_RSCORE_ALPHABET); f(s.d_totals, (u64)KS_RSCORE_ALPHABET); f(s.d_length, (u64)s.n_seqs);
+    }
 };
 int ks_residue_composition_impl(ks_ctx *ctx, const ks_res_batch &B, ks_rcomp *C);
 // bit scores and E-values of a column of scores (ks_astats.hip)
@@ -608,6 +713,10 @@ struct ks_astats {
     u8 *d_status;                                                // n_rows
     double *d_x, *d_ratio, *d_row_bit, *d_row_evalue;            // n_rows
     double *d_bit, *d_evalue;                                    // n
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_status, s.n_rows); f(s.d_x, s.n_rows); f(s.d_ratio, s.n_rows); f(s.d_bit, s.n); f(s.d_evalue, s.n);
+        f(s.d_row_bit, s.n_rows); f(s.d_row_evalue, s.n_rows);
+    }
 };
 // ks_scores_stats_device behind its argument checks (o: validated, defaults filled in, its matrix the one to use; H, Q, T: of
 // ctx; T may be NULL where the contract allows it)
@@ -622,6 +731,10 @@ struct ks_clusters {
     u32 n_rounds; // ks_greedy.hip: the rounds the pass took; 0 for connected components
     u32 *d_label, *d_cluster_id, *d_members, *d_rep; // n_nodes each (d_rep: the first n_clusters are meaningful)
     u64 *d_offsets;                                  // n_nodes + 1 (entries past n_clusters repeat n_nodes)
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_label, (u64)s.n_nodes); f(s.d_cluster_id, (u64)s.n_nodes); f(s.d_offsets, (u64)s.n_clusters + 1); f(s.d_members, (u64)s.n_nodes);
+        f(s.d_rep, (u64)s.n_clusters);
+    }
 };
 // ---- labels -> clusters (ks_cluster.hip; ks_hits_cluster and ks_hits_cluster_greedy) ----
 // the first words of the control block of both passes: the first row with an id out of range / with an empty sketch, the rows
@@ -847,7 +960,4 @@ int ks_sketches_make_dense(ks_ctx *ctx, ks_sketches *s);
 // ---- boundary copies (ks_copy.hip): one DMA for pinned host memory, double-buffered pinned staging + copy threads otherwise
 int ks_copy_h2d(ks_ctx *ctx, void *dst_device, const void *src_host, size_t bytes); // enqueued; complete for pageable sources
 int ks_copy_d2h(ks_ctx *ctx, void *dst_host, const void *src_device, size_t bytes); // returns when dst holds the data
-// the body of every *_copy_to_host: each column with a destination and bytes to copy goes through ks_copy_d2h, then one wait
-struct ks_column { void *dst; const void *src; size_t bytes; };
-int ks_columns_to_host(ks_ctx *ctx, std::initializer_list<ks_column> cols);
 void ks_copy_engine_destroy(ks_ctx *ctx);

@@ -156,13 +156,7 @@ int ks_copy_d2h(ks_ctx *ctx, void *dst, const void *src, size_t bytes) {
     return KS_OK;
 }
 
-int ks_columns_to_host(ks_ctx *ctx, std::initializer_list<ks_column> cols) {
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    for (const ks_column &c : cols)
-        if (c.dst && c.bytes) KS_TRY(ks_copy_d2h(ctx, c.dst, c.src, c.bytes));
-    KS_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return KS_OK;
-}
+int ks_columns_to_host(ks_ctx *ctx, std::initializer_list<ks_column> cols) { return ks_columns_to_host(ctx, cols.begin(), cols.size()); }
 
 extern "C" int ks_host_alloc(ks_ctx *ctx, uint64_t bytes, void **out) {
     return ks_guard(ctx, [&]() -> int {

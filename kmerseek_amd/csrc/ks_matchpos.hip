@@ -355,21 +355,7 @@ extern "C" const uint32_t *ks_matchpos_device_t_hi(const ks_matchpos *m) { retur
 
 extern "C" int ks_matchpos_copy_to_host(ks_ctx *ctx, const ks_matchpos *m, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
                                         uint32_t *q_lo, uint32_t *q_hi, uint32_t *t_lo, uint32_t *t_hi) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !m) return KS_ERR_INVALID_ARG;
-    const size_t nr = (size_t)m->n_rows, np = (size_t)m->n_pairs;
-    return ks_columns_to_host(ctx, {{row_offsets, m->d_row_offsets, (nr + 1) * sizeof(u64)},
-                                    {q_start, m->d_qstart, np * sizeof(u32)}, {t_start, m->d_tstart, np * sizeof(u32)},
-                                    {q_lo, m->d_qlo, nr * sizeof(u32)}, {q_hi, m->d_qhi, nr * sizeof(u32)},
-                                    {t_lo, m->d_tlo, nr * sizeof(u32)}, {t_hi, m->d_thi, nr * sizeof(u32)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, m, row_offsets, q_start, t_start, q_lo, q_hi, t_lo, t_hi); });
 }
 
-extern "C" void ks_matchpos_free(ks_matchpos *m) {
-    if (!m) return;
-    ks_pool_free(m->ctx, m->d_row_offsets);
-    ks_pool_free(m->ctx, m->d_qstart); ks_pool_free(m->ctx, m->d_tstart);
-    ks_pool_free(m->ctx, m->d_qlo); ks_pool_free(m->ctx, m->d_qhi);
-    ks_pool_free(m->ctx, m->d_tlo); ks_pool_free(m->ctx, m->d_thi);
-    delete m;
-}
+extern "C" void ks_matchpos_free(ks_matchpos *m) { ks_obj_free(m); }

@@ -60,10 +60,7 @@ int ks_regions_align_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, co
     S->band = opts->band; S->gap_open = opts->gap_open; S->gap_extend = opts->gap_extend; S->x_drop = opts->x_drop;
     for (int i = 0; i < RK_A * RK_A; i++) S->matrix[i] = opts->matrix ? opts->matrix[i] : (i / RK_A == i % RK_A) ? 1 : -1;
     KS_TRY(ks_alloc(ctx, &S->d_row_offsets, (size_t)n_rows + 1));
-    for (u32 **col : {&S->d_qstart, &S->d_qlength, &S->d_tstart, &S->d_tlength, &S->d_identities, &S->d_positives, &S->d_gap_opens,
-                      &S->d_gaps, &S->d_aln_length})
-        KS_TRY(ks_alloc(ctx, col, (size_t)ng));
-    KS_TRY(ks_alloc(ctx, &S->d_score, (size_t)ng));
+    KS_TRY(ks_obj_alloc(ctx, S, S->n_regions));
     KS_HIP(ctx, hipMemcpyAsync(S->d_row_offsets, R->d_row_offsets, ((size_t)n_rows + 1) * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
     if (ng == 0) return ks_stream_wait(ctx);
     KS_TRY(rk_counts_check(ctx, "region alignments", n_rows, ng));

@@ -348,10 +348,9 @@ int ks_regions_chain_impl(ks_ctx *ctx, const ks_rchain_cols &cols, u64 n_rows, u
     K->n_rows = n_rows; K->n_regions = ng; K->n_chained = 0;
     KS_TRY(rk_counts_check(ctx, "region chain", n_rows, ng));
     KS_TRY(ks_alloc(ctx, &K->d_row_offsets, (size_t)n_rows + 1));
-    KS_TRY(ks_alloc(ctx, &K->d_src_region, (size_t)ng)); KS_TRY(ks_alloc(ctx, &K->d_best, (size_t)ng)); KS_TRY(ks_alloc(ctx, &K->d_pred, (size_t)ng));
-    KS_TRY(ks_alloc(ctx, &K->d_chain_score, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &K->d_row_score, (size_t)n_rows));
-    for (u32 **c : {&K->d_q_start, &K->d_q_length, &K->d_t_start, &K->d_t_length, &K->d_q_aligned, &K->d_t_aligned}) KS_TRY(ks_alloc(ctx, c, (size_t)n_rows));
-    KS_TRY(ks_alloc(ctx, &K->d_identities, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &K->d_aln_length, (size_t)n_rows));
+    KS_TRY(ks_alloc(ctx, &K->d_src_region, (size_t)ng)); // (n_chained of them are filled)
+    KS_TRY(ks_obj_alloc(ctx, K, K->n_regions));
+    KS_TRY(ks_obj_alloc(ctx, K, K->n_rows));
     if (n_rows == 0 || ng == 0) KS_HIP(ctx, hipMemsetAsync(K->d_row_offsets, 0, ((size_t)n_rows + 1) * sizeof(u64), ctx->stream));
     if (n_rows == 0) return ks_stream_wait(ctx); // (ng == 0: the caller has checked)
 

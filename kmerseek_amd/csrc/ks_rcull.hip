@@ -227,8 +227,8 @@ int ks_regions_cull_impl(ks_ctx *ctx, const ks_rcull_cols &cols, u64 n_rows, u64
     K->n_rows = n_rows; K->n_regions = ng; K->n_kept = 0;
     KS_TRY(rk_counts_check(ctx, "region cull", n_rows, ng));
     KS_TRY(ks_alloc(ctx, &K->d_row_offsets, (size_t)n_rows + 1));
-    KS_TRY(ks_alloc(ctx, &K->d_row_best, (size_t)n_rows));
-    KS_TRY(ks_alloc(ctx, &K->d_keeper, (size_t)ng));
+    KS_TRY(ks_obj_alloc(ctx, K, K->n_rows));
+    KS_TRY(ks_obj_alloc(ctx, K, K->n_regions));
     KS_TRY(ks_alloc(ctx, &K->d_src_region, (size_t)ng)); KS_TRY(ks_alloc(ctx, &K->d_rank, (size_t)ng)); KS_TRY(ks_alloc(ctx, &K->d_n_merged, (size_t)ng));
     if (n_rows == 0 || ng == 0) KS_HIP(ctx, hipMemsetAsync(K->d_row_offsets, 0, ((size_t)n_rows + 1) * sizeof(u64), ctx->stream));
     if (n_rows == 0) return ks_stream_wait(ctx); // (ng == 0: the caller has checked)

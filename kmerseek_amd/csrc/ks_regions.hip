@@ -140,8 +140,7 @@ __global__ __launch_bounds__(256) void k_rg_csr(const u32 *srow, u32 n, u32 n_ro
 }
 
 static int rg_empty(ks_ctx *ctx, ks_regions *R) {
-    KS_TRY(ks_alloc(ctx, &R->d_qstart, 1)); KS_TRY(ks_alloc(ctx, &R->d_tstart, 1)); KS_TRY(ks_alloc(ctx, &R->d_length, 1));
-    KS_TRY(ks_alloc(ctx, &R->d_nkmers, 1)); KS_TRY(ks_alloc(ctx, &R->d_covered, 1));
+    KS_TRY(ks_obj_alloc(ctx, R, R->n_regions)); // (0 regions: blocks of one entry)
     KS_HIP(ctx, hipMemsetAsync(R->d_row_offsets, 0, ((size_t)R->n_rows + 1) * sizeof(u64), ctx->stream));
     return ks_stream_wait(ctx);
 }
@@ -193,8 +192,8 @@ static int rg_run(ks_ctx *ctx, const ks_matchpos *M, u32 min_kmers, u32 max_gap,
     const u32 nr = *(const u32 *)rb;
     if (nr > n) return ks_fail(ctx, KS_ERR_HIP, "internal error: %u regions of %llu pairs", nr, (unsigned long long)n);
     if (nr == 0) return rg_empty(ctx, R);
-    KS_TRY(ks_alloc(ctx, &R->d_qstart, (size_t)nr)); KS_TRY(ks_alloc(ctx, &R->d_tstart, (size_t)nr)); KS_TRY(ks_alloc(ctx, &R->d_length, (size_t)nr));
-    KS_TRY(ks_alloc(ctx, &R->d_nkmers, (size_t)nr)); KS_TRY(ks_alloc(ctx, &R->d_covered, (size_t)nr));
+    R->n_regions = nr;
+    KS_TRY(ks_obj_alloc(ctx, R, R->n_regions));
 
     // the order: (row, q_start, t_start).  The chain's scratch holds the sort: keys in k0 / k1, the permutation in idx / cov.
     const int pqt = pa + pt, rbits = ks_key_bits(n_rows - 1);
@@ -221,9 +220,7 @@ static int rg_run(ks_ctx *ctx, const ks_matchpos *M, u32 min_kmers, u32 max_gap,
     KS_LAUNCH(ctx, "regions_gather", k_rg_gather, g_r, 256, T, (const u32 *)perm, nr, pos, R->d_qstart, R->d_tstart, R->d_length, R->d_nkmers,
               R->d_covered);
     KS_LAUNCH(ctx, "regions_csr", k_rg_csr, (u32)((n_rows + 256) / 256), 256, (const u32 *)pos, nr, (u32)n_rows, R->d_row_offsets);
-    KS_TRY(ks_stream_wait(ctx));
-    R->n_regions = nr;
-    return KS_OK;
+    return ks_stream_wait(ctx);
 }
 
 extern "C" int ks_match_regions(ks_ctx *ctx, const ks_matchpos *mp, const ks_regions_opts *opts, ks_regions **out) {
@@ -252,20 +249,7 @@ extern "C" const uint32_t *ks_regions_device_covered(const ks_regions *r) { retu
 
 extern "C" int ks_regions_copy_to_host(ks_ctx *ctx, const ks_regions *r, uint64_t *row_offsets, uint32_t *q_start, uint32_t *t_start,
                                        uint32_t *length, uint32_t *n_kmers, uint32_t *covered) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !r) return KS_ERR_INVALID_ARG;
-    const size_t nr = (size_t)r->n_rows, ng = (size_t)r->n_regions;
-    return ks_columns_to_host(ctx, {{row_offsets, r->d_row_offsets, (nr + 1) * sizeof(u64)},
-                                    {q_start, r->d_qstart, ng * sizeof(u32)}, {t_start, r->d_tstart, ng * sizeof(u32)},
-                                    {length, r->d_length, ng * sizeof(u32)}, {n_kmers, r->d_nkmers, ng * sizeof(u32)},
-                                    {covered, r->d_covered, ng * sizeof(u32)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, r, row_offsets, q_start, t_start, length, n_kmers, covered); });
 }
 
-extern "C" void ks_regions_free(ks_regions *r) {
-    if (!r) return;
-    ks_pool_free(r->ctx, r->d_row_offsets);
-    ks_pool_free(r->ctx, r->d_qstart); ks_pool_free(r->ctx, r->d_tstart); ks_pool_free(r->ctx, r->d_length);
-    ks_pool_free(r->ctx, r->d_nkmers); ks_pool_free(r->ctx, r->d_covered);
-    delete r;
-}
+extern "C" void ks_regions_free(ks_regions *r) { ks_obj_free(r); }

@@ -118,9 +118,7 @@ int ks_regions_score_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, co
     const u64 n_rows = R->n_rows, ng = R->n_regions;
     S->n_rows = n_rows; S->n_regions = ng;
     KS_TRY(ks_alloc(ctx, &S->d_row_offsets, (size_t)n_rows + 1));
-    KS_TRY(ks_alloc(ctx, &S->d_qstart, (size_t)ng)); KS_TRY(ks_alloc(ctx, &S->d_tstart, (size_t)ng)); KS_TRY(ks_alloc(ctx, &S->d_length, (size_t)ng));
-    KS_TRY(ks_alloc(ctx, &S->d_score, (size_t)ng)); KS_TRY(ks_alloc(ctx, &S->d_identities, (size_t)ng));
-    KS_TRY(ks_alloc(ctx, &S->d_positives, (size_t)ng)); KS_TRY(ks_alloc(ctx, &S->d_core_ident, (size_t)ng));
+    KS_TRY(ks_obj_alloc(ctx, S, S->n_regions));
     KS_HIP(ctx, hipMemcpyAsync(S->d_row_offsets, R->d_row_offsets, ((size_t)n_rows + 1) * sizeof(u64), hipMemcpyDeviceToDevice, ctx->stream));
     if (ng == 0) return ks_stream_wait(ctx);
     KS_TRY(rk_counts_check(ctx, "region scores", n_rows, ng));

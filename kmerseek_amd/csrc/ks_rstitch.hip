@@ -339,10 +339,7 @@ int ks_regions_stitch_impl(ks_ctx *ctx, const ks_rchain *K, const ks_raligns *S,
     const u64 n_rows = K->n_rows, nm = K->n_chained;
     R->n_rows = n_rows; R->n_ops = 0; R->dir_bytes = 0; R->n_slices = 0;
     KS_TRY(ks_alloc(ctx, &R->d_op_offsets, (size_t)n_rows + 1));
-    KS_TRY(ks_alloc(ctx, &R->d_score, (size_t)n_rows)); KS_TRY(ks_alloc(ctx, &R->d_row_score, (size_t)n_rows));
-    for (u32 **c : {&R->d_q_start, &R->d_q_length, &R->d_t_start, &R->d_t_length, &R->d_identities, &R->d_positives, &R->d_gap_opens, &R->d_gaps,
-                    &R->d_aln_length, &R->d_n_members, &R->d_n_filled, &R->d_n_open, &R->d_n_trimmed})
-        KS_TRY(ks_alloc(ctx, c, (size_t)n_rows));
+    KS_TRY(ks_obj_alloc(ctx, R, R->n_rows));
     if (n_rows == 0) {
         KS_HIP(ctx, hipMemsetAsync(R->d_op_offsets, 0, sizeof(u64), ctx->stream));
         return ks_stream_wait(ctx);

@@ -35,12 +35,14 @@ struct ks_corpus {
     u32 max_doc_freq;
     u64 *d_hash, *d_sum;
     u32 *d_df;
+    template <class S, class F> static constexpr void each(S &s, F &&f) { f(s.d_hash, s.n_hashes); f(s.d_sum, s.n_hashes); f(s.d_df, s.n_hashes); }
 };
 
 struct ks_signif {
     ks_ctx *ctx;
     u64 n_rows;
     double *d_prob, *d_tfidf;
+    template <class S, class F> static constexpr void each(S &s, F &&f) { f(s.d_prob, s.n_rows); f(s.d_tfidf, s.n_rows); }
 };
 
 // ---- corpus ----------------------------------------------------------------------------------------------------------------
@@ -110,18 +112,10 @@ extern "C" uint32_t ks_corpus_n_docs(const ks_corpus *c) { return c ? c->n_docs 
 extern "C" uint64_t ks_corpus_total_abund(const ks_corpus *c) { return c ? c->total : 0; }
 
 extern "C" int ks_corpus_copy_to_host(ks_ctx *ctx, const ks_corpus *c, uint64_t *hashes, uint64_t *abund_sum, uint32_t *doc_freq) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !c) return KS_ERR_INVALID_ARG;
-    const size_t n = (size_t)c->n_hashes;
-    return ks_columns_to_host(ctx, {{hashes, c->d_hash, n * sizeof(u64)}, {abund_sum, c->d_sum, n * sizeof(u64)}, {doc_freq, c->d_df, n * sizeof(u32)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, c, hashes, abund_sum, doc_freq); });
 }
 
-extern "C" void ks_corpus_free(ks_corpus *c) {
-    if (!c) return;
-    ks_pool_free(c->ctx, c->d_hash); ks_pool_free(c->ctx, c->d_sum); ks_pool_free(c->ctx, c->d_df);
-    delete c;
-}
+extern "C" void ks_corpus_free(ks_corpus *c) { ks_obj_free(c); }
 
 // ---- weights ---------------------------------------------------------------------------------------------------------------
 struct sg_table {
@@ -285,15 +279,7 @@ extern "C" const double *ks_signif_device_prob_overlap(const ks_signif *s) { ret
 extern "C" const double *ks_signif_device_tf_idf(const ks_signif *s) { return s ? s->d_tfidf : nullptr; }
 
 extern "C" int ks_signif_copy_to_host(ks_ctx *ctx, const ks_signif *s, double *prob_overlap, double *tf_idf) {
-    return ks_guard(ctx, [&]() -> int {
-    if (!ctx || !s) return KS_ERR_INVALID_ARG;
-    const size_t n = (size_t)s->n_rows;
-    return ks_columns_to_host(ctx, {{prob_overlap, s->d_prob, n * sizeof(double)}, {tf_idf, s->d_tfidf, n * sizeof(double)}});
-    });
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, s, prob_overlap, tf_idf); });
 }
 
-extern "C" void ks_signif_free(ks_signif *s) {
-    if (!s) return;
-    ks_pool_free(s->ctx, s->d_prob); ks_pool_free(s->ctx, s->d_tfidf);
-    delete s;
-}
+extern "C" void ks_signif_free(ks_signif *s) { ks_obj_free(s); }

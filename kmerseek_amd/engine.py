@@ -5,7 +5,9 @@ so nothing here depends on torch.  All compute happens in the HIP library.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import types
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -85,6 +87,13 @@ def _matrix28(matrix) -> Optional[np.ndarray]:
     if m.shape != (_lib.KS_RSCORE_ALPHABET, _lib.KS_RSCORE_ALPHABET) or m.dtype != np.int8:
         raise ValueError("matrix must be an int8 array of shape (28, 28)")
     return np.ascontiguousarray(m)
+
+
+def _int_in(name: str, v, top: int, shown: Optional[str] = None) -> int:
+    """v as an int in [0, top], or ValueError "<name> = <v> is not an integer in [0, <top>]" (shown: the bound as the text says it)."""
+    if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+        raise ValueError(f"{name} = {v} is not an integer in " + (shown or f"[0, {top}]"))
+    return int(v)
 
 
 def karlin_ungapped(matrix, freq_q, freq_t) -> Tuple[float, float, float]:
@@ -205,6 +214,27 @@ class Context:
         buf = DeviceBuffer(self, p, a.nbytes)
         self._check(self._L.ks_dev_upload(self._h, p, _ptr(a), a.nbytes))
         return buf
+
+    @contextlib.contextmanager
+    def _uploaded(self, *arrays):
+        """Host arrays on the device for the time of one call: yields their device pointers, in order; freed on the way out."""
+        bufs = []
+        try:
+            for a in arrays:
+                bufs.append(self.to_device(a))
+            yield [b.ptr for b in bufs]
+        finally:
+            for b in bufs:
+                b.free()
+
+    @contextlib.contextmanager
+    def _batches(self, q_res, q_off, t_res, t_off):
+        """The query and target residue batches of a region pass on the device for one call: yields the eight arguments the
+        *_device variants take for them (d_q_res, d_q_off, n_q, n_q_res, d_t_res, d_t_off, n_t, n_t_res)."""
+        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        with self._uploaded(q_res, q_off, t_res, t_off) as (d_q, d_qo, d_t, d_to):
+            yield d_q, d_qo, len(q_off) - 1, len(q_res), d_t, d_to, len(t_off) - 1, len(t_res)
 
     def _device_empty(self, nbytes: int) -> "DeviceBuffer":
         p = C.c_void_p()
@@ -477,12 +507,7 @@ class Context:
         """(ks_rscore_opts, the int8 array its matrix pointer reads: keep it alive for the call)"""
         if not 0 <= int(x_drop) < 2 ** 32:
             raise ValueError(f"x_drop = {x_drop} does not fit 32 bits")
-        m = None
-        if matrix is not None:
-            m = np.asarray(matrix)
-            if m.shape != (_lib.KS_RSCORE_ALPHABET, _lib.KS_RSCORE_ALPHABET) or m.dtype != np.int8:
-                raise ValueError("matrix must be an int8 array of shape (28, 28)")
-            m = np.ascontiguousarray(m)
+        m = _matrix28(matrix)
         mp = m.ctypes.data_as(C.POINTER(C.c_int8)) if m is not None else None
         return _lib.ks_rscore_opts(_lib.KS_RSCORE_EXTEND if extend else 0, int(x_drop), mp, 0), m
 
@@ -504,34 +529,19 @@ class Context:
     def score_regions(self, regions: "Regions", hits: "Hits", q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray,
                       t_off: np.ndarray, matrix=None, extend: bool = False, x_drop: int = 0) -> "RegionScores":
         """score_regions_device from host arrays (the batches `hits` was searched on): uploaded, scored, released."""
-        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
-        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
         self._rscore_opts(matrix, extend, x_drop)  # (refused before anything is uploaded)
-        bufs = []
-        try:
-            for a in (q_res, q_off, t_res, t_off):
-                bufs.append(self.to_device(a))
-            return self.score_regions_device(regions, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res), bufs[2].ptr, bufs[3].ptr,
-                                             len(t_off) - 1, len(t_res), matrix=matrix, extend=extend, x_drop=x_drop)
-        finally:
-            for b in bufs:
-                b.free()
+        with self._batches(q_res, q_off, t_res, t_off) as b:
+            return self.score_regions_device(regions, hits, *b, matrix=matrix, extend=extend, x_drop=x_drop)
 
     @staticmethod
     def _ralign_opts(matrix, band: int, gap_open: int, gap_extend: int, x_drop: int):
         """(ks_ralign_opts, the int8 array its matrix pointer reads: keep it alive for the call)"""
-        for name, v, top in (("band", band, _lib.KS_RALIGN_MAX_BAND), ("gap_open", gap_open, _lib.KS_RALIGN_MAX_GAP_COST),
-                             ("gap_extend", gap_extend, _lib.KS_RALIGN_MAX_GAP_COST), ("x_drop", x_drop, _lib.KS_RALIGN_MAX_X_DROP)):
-            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
-                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
-        m = None
-        if matrix is not None:
-            m = np.asarray(matrix)
-            if m.shape != (_lib.KS_RSCORE_ALPHABET, _lib.KS_RSCORE_ALPHABET) or m.dtype != np.int8:
-                raise ValueError("matrix must be an int8 array of shape (28, 28)")
-            m = np.ascontiguousarray(m)
+        words = [_int_in(name, v, top) for name, v, top in (
+            ("band", band, _lib.KS_RALIGN_MAX_BAND), ("gap_open", gap_open, _lib.KS_RALIGN_MAX_GAP_COST),
+            ("gap_extend", gap_extend, _lib.KS_RALIGN_MAX_GAP_COST), ("x_drop", x_drop, _lib.KS_RALIGN_MAX_X_DROP))]
+        m = _matrix28(matrix)
         mp = m.ctypes.data_as(C.POINTER(C.c_int8)) if m is not None else None
-        return _lib.ks_ralign_opts(mp, int(band), int(gap_open), int(gap_extend), int(x_drop), 0), m
+        return _lib.ks_ralign_opts(mp, *words, 0), m
 
     def align_regions_device(self, regions: "Regions", hits: "Hits", d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
                              d_t_res: int, d_t_off: int, n_t: int, n_t_res: int, matrix=None, band: int = 16, gap_open: int = 11,
@@ -553,25 +563,13 @@ class Context:
                       t_off: np.ndarray, matrix=None, band: int = 16, gap_open: int = 11, gap_extend: int = 1,
                       x_drop: int = 30) -> "RegionAlignments":
         """align_regions_device from host arrays (the batches `hits` was searched on): uploaded, aligned, released."""
-        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
-        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
         self._ralign_opts(matrix, band, gap_open, gap_extend, x_drop)  # (refused before anything is uploaded)
-        bufs = []
-        try:
-            for a in (q_res, q_off, t_res, t_off):
-                bufs.append(self.to_device(a))
-            return self.align_regions_device(regions, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res), bufs[2].ptr, bufs[3].ptr,
-                                             len(t_off) - 1, len(t_res), matrix=matrix, band=band, gap_open=gap_open,
-                                             gap_extend=gap_extend, x_drop=x_drop)
-        finally:
-            for b in bufs:
-                b.free()
+        with self._batches(q_res, q_off, t_res, t_off) as b:
+            return self.align_regions_device(regions, hits, *b, matrix=matrix, band=band, gap_open=gap_open, gap_extend=gap_extend, x_drop=x_drop)
 
     @staticmethod
     def _rtrace_opts(eqx: bool, max_scratch_bytes: int):
-        if isinstance(max_scratch_bytes, bool) or int(max_scratch_bytes) != max_scratch_bytes or not 0 <= int(max_scratch_bytes) < 2 ** 64:
-            raise ValueError(f"max_scratch_bytes = {max_scratch_bytes} is not an integer in [0, 2^64)")
-        return _lib.ks_rtrace_opts(_lib.KS_RTRACE_EQX if eqx else 0, 0, int(max_scratch_bytes))
+        return _lib.ks_rtrace_opts(_lib.KS_RTRACE_EQX if eqx else 0, 0, _int_in("max_scratch_bytes", max_scratch_bytes, 2 ** 64 - 1, "[0, 2^64)"))
 
     def trace_regions_device(self, regions: "Regions", hits: "Hits", d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
                              d_t_res: int, d_t_off: int, n_t: int, n_t_res: int, alignments: "RegionAlignments", eqx: bool = False,
@@ -591,27 +589,16 @@ class Context:
                       t_off: np.ndarray, alignments: "RegionAlignments", eqx: bool = False,
                       max_scratch_bytes: int = 0) -> "RegionCigars":
         """trace_regions_device from host arrays (the batches `alignments` was made on): uploaded, traced, released."""
-        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
-        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
         self._rtrace_opts(eqx, max_scratch_bytes)  # (refused before anything is uploaded)
-        bufs = []
-        try:
-            for a in (q_res, q_off, t_res, t_off):
-                bufs.append(self.to_device(a))
-            return self.trace_regions_device(regions, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res), bufs[2].ptr, bufs[3].ptr,
-                                             len(t_off) - 1, len(t_res), alignments, eqx=eqx, max_scratch_bytes=max_scratch_bytes)
-        finally:
-            for b in bufs:
-                b.free()
+        with self._batches(q_res, q_off, t_res, t_off) as b:
+            return self.trace_regions_device(regions, hits, *b, alignments, eqx=eqx, max_scratch_bytes=max_scratch_bytes)
 
     @staticmethod
     def _rcull_opts(overlap_pct: int, min_score, max_per_row: int):
-        for name, v, top in (("overlap_pct", overlap_pct, 100), ("max_per_row", max_per_row, 2 ** 32 - 1)):
-            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
-                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
+        overlap_pct, max_per_row = _int_in("overlap_pct", overlap_pct, 100), _int_in("max_per_row", max_per_row, 2 ** 32 - 1)
         if min_score is not None and (isinstance(min_score, bool) or int(min_score) != min_score or not -2 ** 63 <= int(min_score) < 2 ** 63):
             raise ValueError(f"min_score = {min_score} is not a 64-bit integer")
-        return _lib.ks_rcull_opts(int(overlap_pct), int(max_per_row), 0 if min_score is None else int(min_score),
+        return _lib.ks_rcull_opts(overlap_pct, max_per_row, 0 if min_score is None else int(min_score),
                                   0 if min_score is None else _lib.KS_RCULL_MIN_SCORE, 0)
 
     def cull_regions_device(self, d_row_offsets: int, d_q_start: int, d_q_length: int, d_t_start: int, d_t_length: Optional[int],
@@ -646,11 +633,10 @@ class Context:
 
     @staticmethod
     def _rchain_opts(max_gap: int, max_overlap: int, link_cost: int, skew_cost: int, overlap_cost: int):
-        for name, v, top in (("max_gap", max_gap, 2 ** 32 - 1), ("max_overlap", max_overlap, 2 ** 32 - 1), ("link_cost", link_cost, 2 ** 30),
-                             ("skew_cost", skew_cost, 2 ** 16), ("overlap_cost", overlap_cost, 2 ** 16)):
-            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
-                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
-        return _lib.ks_rchain_opts(int(max_gap), int(max_overlap), int(link_cost), int(skew_cost), int(overlap_cost), 0, (C.c_uint32 * 2)(0, 0))
+        words = [_int_in(name, v, top) for name, v, top in (
+            ("max_gap", max_gap, 2 ** 32 - 1), ("max_overlap", max_overlap, 2 ** 32 - 1), ("link_cost", link_cost, 2 ** 30),
+            ("skew_cost", skew_cost, 2 ** 16), ("overlap_cost", overlap_cost, 2 ** 16))]
+        return _lib.ks_rchain_opts(*words, 0, (C.c_uint32 * 2)(0, 0))
 
     def chain_regions_device(self, d_row_offsets: int, d_q_start: int, d_q_length: int, d_t_start: int, d_t_length: Optional[int],
                              d_score: int, n_rows: int, n_regions: int, d_identities: Optional[int] = None,
@@ -688,10 +674,9 @@ class Context:
 
     @staticmethod
     def _rstitch_opts(max_fill: int, eqx: bool, max_scratch_bytes: int):
-        for name, v, top in (("max_fill", max_fill, _lib.KS_RSTITCH_MAX_FILL), ("max_scratch_bytes", max_scratch_bytes, 2 ** 64 - 1)):
-            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
-                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
-        return _lib.ks_rstitch_opts(int(max_fill), _lib.KS_RSTITCH_EQX if eqx else 0, int(max_scratch_bytes), (C.c_uint32 * 2)(0, 0))
+        max_fill = _int_in("max_fill", max_fill, _lib.KS_RSTITCH_MAX_FILL)
+        return _lib.ks_rstitch_opts(max_fill, _lib.KS_RSTITCH_EQX if eqx else 0, _int_in("max_scratch_bytes", max_scratch_bytes, 2 ** 64 - 1),
+                                    (C.c_uint32 * 2)(0, 0))
 
     def stitch_chains_device(self, chain: "RegionChain", alignments: "RegionAlignments", cigars: "RegionCigars", hits: "Hits",
                              d_q_res: int, d_q_off: int, n_q: int, n_q_res: int, d_t_res: int, d_t_off: int, n_t: int, n_t_res: int,
@@ -714,19 +699,9 @@ class Context:
                       q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray, t_off: np.ndarray, max_fill: int = 0, eqx: bool = False,
                       max_scratch_bytes: int = 0) -> "HitAlignments":
         """stitch_chains_device from host arrays (the batches `alignments` was made on): uploaded, stitched, released."""
-        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
-        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
         self._rstitch_opts(max_fill, eqx, max_scratch_bytes)  # (refused before anything is uploaded)
-        bufs = []
-        try:
-            for a in (q_res, q_off, t_res, t_off):
-                bufs.append(self.to_device(a))
-            return self.stitch_chains_device(chain, alignments, cigars, hits, bufs[0].ptr, bufs[1].ptr, len(q_off) - 1, len(q_res),
-                                             bufs[2].ptr, bufs[3].ptr, len(t_off) - 1, len(t_res), max_fill=max_fill, eqx=eqx,
-                                             max_scratch_bytes=max_scratch_bytes)
-        finally:
-            for b in bufs:
-                b.free()
+        with self._batches(q_res, q_off, t_res, t_off) as b:
+            return self.stitch_chains_device(chain, alignments, cigars, hits, *b, max_fill=max_fill, eqx=eqx, max_scratch_bytes=max_scratch_bytes)
 
     def residue_composition_device(self, d_res: int, d_off: int, n_seqs: int, n_res: int) -> "Composition":
         """ks_residue_composition_device from a device-resident residue batch (raw pointers: residues u8, offsets
@@ -740,14 +715,8 @@ class Context:
     def residue_composition(self, res: np.ndarray, off: np.ndarray) -> "Composition":
         """residue_composition_device from host arrays: uploaded, counted, released."""
         res = np.ascontiguousarray(res, dtype=np.uint8); off = np.ascontiguousarray(off, dtype=np.uint64)
-        bufs = []
-        try:
-            for a in (res if len(res) else np.zeros(1, np.uint8), off):  # (an empty batch still has a buffer to point at)
-                bufs.append(self.to_device(a))
-            return self.residue_composition_device(bufs[0].ptr, bufs[1].ptr, len(off) - 1, len(res))
-        finally:
-            for b in bufs:
-                b.free()
+        with self._uploaded(res if len(res) else np.zeros(1, np.uint8), off) as (d_res, d_off):  # (an empty batch still has a buffer to point at)
+            return self.residue_composition_device(d_res, d_off, len(off) - 1, len(res))
 
     @staticmethod
     def _astats_opts(matrix, params, background, composition: bool, pairwise: bool, allow_ungapped: bool, ratio, db_residues: int,
@@ -760,14 +729,13 @@ class Context:
             if bg.shape != (_lib.KS_RSCORE_ALPHABET,):
                 raise ValueError("background must hold 28 weights")
         lam, K = (0.0, 0.0) if params is None else (float(params[0]), float(params[1]))
-        for name, v, top in (("db_residues", db_residues, 2 ** 64 - 1), ("db_seqs", db_seqs, 2 ** 64 - 1), ("length_adjust", length_adjust, 2 ** 32 - 1)):
-            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
-                raise ValueError(f"{name} = {v} is not an integer in [0, {top}]")
+        db_residues, db_seqs = _int_in("db_residues", db_residues, 2 ** 64 - 1), _int_in("db_seqs", db_seqs, 2 ** 64 - 1)
+        length_adjust = _int_in("length_adjust", length_adjust, 2 ** 32 - 1)
         flags = ((0 if composition else _lib.KS_ASTATS_NO_COMPOSITION) | (_lib.KS_ASTATS_PAIRWISE if pairwise else 0)
                  | (_lib.KS_ASTATS_ALLOW_UNGAPPED if allow_ungapped else 0))
-        opts = _lib.ks_astats_opts(flags, int(length_adjust), m.ctypes.data_as(C.POINTER(C.c_int8)) if m is not None else None, lam, K,
+        opts = _lib.ks_astats_opts(flags, length_adjust, m.ctypes.data_as(C.POINTER(C.c_int8)) if m is not None else None, lam, K,
                                    bg.ctypes.data_as(C.POINTER(C.c_double)) if bg is not None else None, float(ratio[0]), float(ratio[1]),
-                                   int(db_residues), int(db_seqs), 0)
+                                   db_residues, db_seqs, 0)
         return opts, (m, bg)
 
     def alignment_stats_device(self, d_row_offsets: Optional[int], d_score: int, n_rows: int, n: int, hits: "Hits", q_comp: "Composition",
@@ -1129,128 +1097,91 @@ class KmerPositions(_Owned):
         return seq, start, h
 
 
-class MatchPositions(_Owned):
+_DTYPE_NAMES = {"u1": "u8", "u4": "u32", "u8": "u64", "i8": "i64", "f8": "f64"}
+
+
+def _with_doc(fn, doc):
+    """A copy of the function `fn` that carries `doc`."""
+    f = types.FunctionType(fn.__code__, fn.__globals__, fn.__name__, fn.__defaults__, fn.__closure__)
+    f.__doc__, f.__annotations__, f.__qualname__ = doc, fn.__annotations__, fn.__qualname__
+    return f
+
+
+class _Columns(_Owned):
+    """A device result object whose columns ONE table lists.  A subclass declares
+        _PREFIX  the C prefix: ks_<prefix>_free, ks_<prefix>_copy_to_host, ks_<prefix>_device_<column>, ks_<prefix>_<count>;
+        _COUNTS  {name of a count: its docstring or ""}: each becomes a read-only property over ks_<prefix>_<name>;
+        _TABLE   one (column, dtype, count) per column in the order of ks_<prefix>_copy_to_host's parameters: dtype a numpy
+                 code (u1, u4, u8, i8, f8), count an expression over the counts ("n_rows + 1"; a tuple gives a 2-d array).
+    device_ptrs(), to_host(), _COLUMNS (the column names) and the count properties come from these; the docstrings of the two
+    methods list the table."""
+    _PREFIX, _COUNTS, _TABLE = None, {}, ()
+
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        cls._free = f"ks_{cls._PREFIX}_free"
+        cls._COLUMNS = tuple(name for name, _, _ in cls._TABLE)
+        for count, doc in cls._COUNTS.items():
+            fn = f"ks_{cls._PREFIX}_{count}"
+            setattr(cls, count, property(lambda self, fn=fn: int(getattr(self._ctx._L, fn)(self._h)), doc=doc or None))
+        listing = ", ".join(f"{name} {_DTYPE_NAMES[dt]}[{n}]" for name, dt, n in cls._TABLE)
+        cls.device_ptrs = _with_doc(_Columns.device_ptrs, f"Raw device pointers ({listing}).")
+        cls.to_host = _with_doc(_Columns.to_host, f"The columns as numpy arrays ({listing}).")
+
+    def device_ptrs(self) -> Tuple[int, ...]:
+        L = self._ctx._L
+        return tuple(int(getattr(L, f"ks_{self._PREFIX}_device_{c}")(self._h) or 0) for c in self._COLUMNS)
+
+    def _copy_out(self, names) -> Tuple[np.ndarray, ...]:
+        """The named columns as numpy arrays (ks_<prefix>_copy_to_host with NULL for every other column)."""
+        counts = {c: getattr(self, c) for c in self._COUNTS}
+        cols = [np.zeros(eval(n, {"__builtins__": {}}, counts), dt) if name in names else None for name, dt, n in self._TABLE]
+        self._ctx._check(getattr(self._ctx._L, f"ks_{self._PREFIX}_copy_to_host")(self._ctx._h, self._h, *[_ptr(c) for c in cols]))
+        return tuple(c for c in cols if c is not None)
+
+    def to_host(self) -> Tuple[np.ndarray, ...]:
+        return self._copy_out(self._COLUMNS)
+
+
+class MatchPositions(_Columns):
     """Device-resident CSR over hit rows (ks_matchpos): row r of the hits owns pairs [row_offsets[r], row_offsets[r + 1])."""
-    _free = "ks_matchpos_free"
-    _COLUMNS = ("row_offsets", "q_start", "t_start", "q_lo", "q_hi", "t_lo", "t_hi")
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_matchpos_n_rows(self._h))
-
-    @property
-    def n_pairs(self) -> int:
-        return int(self._ctx._L.ks_matchpos_n_pairs(self._h))
+    _PREFIX, _COUNTS = "matchpos", {"n_rows": "", "n_pairs": ""}
+    _TABLE = (("row_offsets", "u8", "n_rows + 1"), ("q_start", "u4", "n_pairs"), ("t_start", "u4", "n_pairs"),
+              ("q_lo", "u4", "n_rows"), ("q_hi", "u4", "n_rows"), ("t_lo", "u4", "n_rows"), ("t_hi", "u4", "n_rows"))
 
     @property
     def n_slices(self) -> int:
         """Hit-row slices the call ran in (1 unless row index and starts do not fit one 64-bit key).  Diagnostic."""
         return int(self._ctx._L.ks_matchpos_n_slices(self._h))
 
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (row_offsets u64[n_rows + 1], q_start / t_start u32[n_pairs], q_lo, q_hi, t_lo, t_hi u32[n_rows])."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_matchpos_device_" + c)(self._h) or 0) for c in self._COLUMNS)
 
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """(row_offsets u64[n_rows + 1], q_start, t_start u32[n_pairs], q_lo, q_hi, t_lo, t_hi u32[n_rows])."""
-        nr, npairs = self.n_rows, self.n_pairs
-        offs = np.zeros(nr + 1, np.uint64)
-        qs = np.zeros(npairs, np.uint32); ts = np.zeros(npairs, np.uint32)
-        ext = [np.zeros(nr, np.uint32) for _ in range(4)]
-        self._ctx._check(self._ctx._L.ks_matchpos_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(qs), _ptr(ts),
-                                                               *[_ptr(e) for e in ext]))
-        return (offs, qs, ts, *ext)
-
-
-class Regions(_Owned):
+class Regions(_Columns):
     """Device-resident CSR over hit rows (ks_regions): row r of the hits owns regions [row_offsets[r], row_offsets[r + 1])."""
-    _free = "ks_regions_free"
-    _COLUMNS = ("row_offsets", "q_start", "t_start", "length", "n_kmers", "covered")
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_regions_n_rows(self._h))
-
-    @property
-    def n_regions(self) -> int:
-        return int(self._ctx._L.ks_regions_n_regions(self._h))
+    _PREFIX, _COUNTS = "regions", {"n_rows": "", "n_regions": ""}
+    _TABLE = (("row_offsets", "u8", "n_rows + 1"),) + tuple((c, "u4", "n_regions") for c in ("q_start", "t_start", "length", "n_kmers", "covered"))
 
     @property
     def n_slices(self) -> int:
         """Hit-row slices the chaining ran in (1 unless row index, diagonal and start do not fit one 64-bit key).  Diagnostic."""
         return int(self._ctx._L.ks_regions_n_slices(self._h))
 
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (row_offsets u64[n_rows + 1], q_start / t_start / length / n_kmers / covered u32[n_regions])."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_regions_device_" + c)(self._h) or 0) for c in self._COLUMNS)
 
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """(row_offsets u64[n_rows + 1], q_start, t_start, length, n_kmers, covered u32[n_regions])."""
-        offs = np.zeros(self.n_rows + 1, np.uint64)
-        cols = [np.zeros(self.n_regions, np.uint32) for _ in range(5)]
-        self._ctx._check(self._ctx._L.ks_regions_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
-        return (offs, *cols)
-
-
-class RegionScores(_Owned):
+class RegionScores(_Columns):
     """Device-resident scores of the regions of a hit list (ks_rscores): the CSR of the Regions they were made from, per region
     the extended placement, the score, identities, positives and the identities of the seed region alone."""
-    _free = "ks_rscores_free"
-    _COLUMNS = ("row_offsets", "q_start", "t_start", "length", "score", "identities", "positives", "core_identities")
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_rscores_n_rows(self._h))
-
-    @property
-    def n_regions(self) -> int:
-        return int(self._ctx._L.ks_rscores_n_regions(self._h))
-
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (row_offsets u64[n_rows + 1]; q_start, t_start, length u32, score i64, identities, positives,
-        core_identities u32, each [n_regions])."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_rscores_device_" + c)(self._h) or 0) for c in self._COLUMNS)
-
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """(row_offsets u64[n_rows + 1], q_start, t_start, length u32, score i64, identities, positives, core_identities u32)."""
-        n = self.n_regions
-        offs = np.zeros(self.n_rows + 1, np.uint64)
-        cols = [np.zeros(n, np.int64 if c == "score" else np.uint32) for c in self._COLUMNS[1:]]
-        self._ctx._check(self._ctx._L.ks_rscores_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
-        return (offs, *cols)
+    _PREFIX, _COUNTS = "rscores", {"n_rows": "", "n_regions": ""}
+    _TABLE = (("row_offsets", "u8", "n_rows + 1"), ("q_start", "u4", "n_regions"), ("t_start", "u4", "n_regions"),
+              ("length", "u4", "n_regions"), ("score", "i8", "n_regions"), ("identities", "u4", "n_regions"),
+              ("positives", "u4", "n_regions"), ("core_identities", "u4", "n_regions"))
 
 
-class RegionAlignments(_Owned):
+class RegionAlignments(_Columns):
     """Device-resident gapped alignments of the regions of a hit list (ks_raligns): the CSR of the Regions they were made from,
     per region the alignment's extents on both sequences, its score and its counts."""
-    _free = "ks_raligns_free"
-    _COLUMNS = ("row_offsets", "q_start", "q_length", "t_start", "t_length", "score", "identities", "positives", "gap_opens", "gaps",
-                "aln_length")
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_raligns_n_rows(self._h))
-
-    @property
-    def n_regions(self) -> int:
-        return int(self._ctx._L.ks_raligns_n_regions(self._h))
-
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (row_offsets u64[n_rows + 1]; score i64 and every other column u32, each [n_regions])."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_raligns_device_" + c)(self._h) or 0) for c in self._COLUMNS)
-
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """(row_offsets u64[n_rows + 1], q_start, q_length, t_start, t_length u32, score i64, identities, positives, gap_opens,
-        gaps, aln_length u32)."""
-        n = self.n_regions
-        offs = np.zeros(self.n_rows + 1, np.uint64)
-        cols = [np.zeros(n, np.int64 if c == "score" else np.uint32) for c in self._COLUMNS[1:]]
-        self._ctx._check(self._ctx._L.ks_raligns_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
-        return (offs, *cols)
+    _PREFIX, _COUNTS = "raligns", {"n_rows": "", "n_regions": ""}
+    _TABLE = (("row_offsets", "u8", "n_rows + 1"),) + tuple(
+        (c, "i8" if c == "score" else "u4", "n_regions") for c in ("q_start", "q_length", "t_start", "t_length", "score", "identities",
+                                                                    "positives", "gap_opens", "gaps", "aln_length"))
 
 
 CIGAR_OPS = "MIDNSHP=X"  # the BAM op codes
@@ -1265,22 +1196,11 @@ def cigar_strings(op_offsets, ops) -> List[str]:
     return ["".join(f"{v >> 4}{CIGAR_OPS[v & 15]}" for v in ops[offs[g]:offs[g + 1]]) for g in range(len(offs) - 1)]
 
 
-class RegionCigars(_Owned):
+class RegionCigars(_Columns):
     """Device-resident paths of the alignments of a hit list's regions (ks_cigars): a CSR over the regions in the order of the
     RegionAlignments they were traced from, region g owns ops [op_offsets[g], op_offsets[g + 1]), an op is len << 4 | BAM code."""
-    _free = "ks_cigars_free"
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_cigars_n_rows(self._h))
-
-    @property
-    def n_regions(self) -> int:
-        return int(self._ctx._L.ks_cigars_n_regions(self._h))
-
-    @property
-    def n_ops(self) -> int:
-        return int(self._ctx._L.ks_cigars_n_ops(self._h))
+    _PREFIX, _COUNTS = "cigars", {"n_rows": "", "n_regions": "", "n_ops": ""}
+    _TABLE = (("op_offsets", "u8", "n_regions + 1"), ("ops", "u4", "n_ops"))
 
     @property
     def n_slices(self) -> int:
@@ -1292,104 +1212,48 @@ class RegionCigars(_Owned):
         """Direction scratch the traceback allocated.  Diagnostic."""
         return int(self._ctx._L.ks_cigars_scratch_bytes(self._h))
 
-    def device_ptrs(self) -> Tuple[int, int]:
-        """Raw device pointers (op_offsets u64[n_regions + 1], ops u32[n_ops])."""
-        L = self._ctx._L
-        return (int(L.ks_cigars_device_op_offsets(self._h) or 0), int(L.ks_cigars_device_ops(self._h) or 0))
-
-    def to_host(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(op_offsets u64[n_regions + 1], ops u32[n_ops])."""
-        offs = np.zeros(self.n_regions + 1, np.uint64)
-        ops = np.zeros(self.n_ops, np.uint32)
-        self._ctx._check(self._ctx._L.ks_cigars_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(ops)))
-        return offs, ops
-
     def strings(self) -> List[str]:
         """The CIGAR of every region as text, e.g. "35M2D17M1I40M"."""
         return cigar_strings(*self.to_host())
 
 
-class RegionCull(_Owned):
+class RegionCull(_Columns):
     """Device-resident result of Context.cull_regions (ks_rcull): a CSR of the kept regions over the input's hit rows — per
     kept region its input index (src_region), its rank inside the row (0: the best) and how many input regions it stands for
     (n_merged) — per input region its keeper (0xffffffff: dropped) and per hit row the score of its best kept region as f64
     (NaN: the row keeps none), a `score=` column for Context.best_hits."""
-    _free = "ks_rcull_free"
-    _COLUMNS = ("row_offsets", "src_region", "rank", "n_merged", "keeper", "row_best_score")
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_rcull_n_rows(self._h))
-
-    @property
-    def n_regions(self) -> int:
-        """Regions of the input."""
-        return int(self._ctx._L.ks_rcull_n_regions(self._h))
-
-    @property
-    def n_kept(self) -> int:
-        return int(self._ctx._L.ks_rcull_n_kept(self._h))
-
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (row_offsets u64[n_rows + 1]; src_region, rank, n_merged u32[n_kept]; keeper u32[n_regions];
-        row_best_score f64[n_rows])."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_rcull_device_" + c)(self._h) or 0) for c in self._COLUMNS)
+    _PREFIX, _COUNTS = "rcull", {"n_rows": "", "n_regions": "Regions of the input.", "n_kept": ""}
+    _TABLE = (("row_offsets", "u8", "n_rows + 1"), ("src_region", "u4", "n_kept"), ("rank", "u4", "n_kept"), ("n_merged", "u4", "n_kept"),
+              ("keeper", "u4", "n_regions"), ("row_best_score", "f8", "n_rows"))
 
     @property
     def row_best_score_ptr(self) -> int:
         """The device column row_best_score f64[n_rows]: pass it to Context.best_hits(score=...)."""
         return int(self._ctx._L.ks_rcull_device_row_best_score(self._h) or 0)
 
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """(row_offsets u64[n_rows + 1], src_region, rank, n_merged u32[n_kept], keeper u32[n_regions], row_best_score f64[n_rows])."""
-        k = self.n_kept
-        offs = np.zeros(self.n_rows + 1, np.uint64)
-        cols = [np.zeros(k, np.uint32) for _ in range(3)] + [np.zeros(self.n_regions, np.uint32), np.zeros(self.n_rows, np.float64)]
-        self._ctx._check(self._ctx._L.ks_rcull_copy_to_host(self._ctx._h, self._h, _ptr(offs), *[_ptr(c) for c in cols]))
-        return (offs, *cols)
-
     def take(self, obj):
         """The Regions, RegionScores or RegionAlignments of the kept regions only (ks_*_take): every column gathered by
         src_region, the row offsets of this cull.  `obj` must hold the regions the cull was made of."""
-        for cls, fn in ((Regions, "ks_regions_take"), (RegionScores, "ks_rscores_take"), (RegionAlignments, "ks_raligns_take")):
+        for cls in (Regions, RegionScores, RegionAlignments):
             if isinstance(obj, cls):
                 out = C.c_void_p()
-                self._ctx._check(getattr(self._ctx._L, fn)(self._ctx._h, obj._h, self._h, C.byref(out)))
+                self._ctx._check(getattr(self._ctx._L, f"ks_{cls._PREFIX}_take")(self._ctx._h, obj._h, self._h, C.byref(out)))
                 return cls(self._ctx, out)
         raise TypeError("take() gathers a Regions, a RegionScores or a RegionAlignments")
 
 
-class RegionChain(_Owned):
+class RegionChain(_Columns):
     """Device-resident result of Context.chain_regions (ks_rchain): a CSR of the members of each hit row's best colinear chain
     in chain order (src_region), per input region its best chain value and its predecessor (0xffffffff: none), and per hit row
     the chain's score, its span and its aligned lengths on both sequences, the sums of identities and aln_length over its
     members and the score as f64 (NaN: a row without regions), a `score=` column for Context.best_hits and the cluster passes.
     coverage() adds row_coverage, the share of the sequences the chain covers."""
-    _free = "ks_rchain_free"
-    _COLUMNS = ("row_offsets", "src_region", "best", "pred", "chain_score", "q_start", "q_length", "t_start", "t_length", "q_aligned",
-                "t_aligned", "identities", "aln_length", "row_chain_score")
+    _PREFIX, _COUNTS = "rchain", {"n_rows": "", "n_regions": "Regions of the input.", "n_chained": ""}
+    _TABLE = (("row_offsets", "u8", "n_rows + 1"), ("src_region", "u4", "n_chained"), ("best", "i8", "n_regions"), ("pred", "u4", "n_regions"),
+              ("chain_score", "i8", "n_rows")) + \
+        tuple((c, "u4", "n_rows") for c in ("q_start", "q_length", "t_start", "t_length", "q_aligned", "t_aligned")) + \
+        (("identities", "u8", "n_rows"), ("aln_length", "u8", "n_rows"), ("row_chain_score", "f8", "n_rows"))
     _MODES = {"query": 0, "target": 1, "min": 2, "max": 3}
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_rchain_n_rows(self._h))
-
-    @property
-    def n_regions(self) -> int:
-        """Regions of the input."""
-        return int(self._ctx._L.ks_rchain_n_regions(self._h))
-
-    @property
-    def n_chained(self) -> int:
-        return int(self._ctx._L.ks_rchain_n_chained(self._h))
-
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (row_offsets u64[n_rows + 1]; src_region u32[n_chained]; best i64, pred u32 [n_regions]; and
-        [n_rows] each: chain_score i64; q_start, q_length, t_start, t_length, q_aligned, t_aligned u32; identities, aln_length
-        u64; row_chain_score f64)."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_rchain_device_" + c)(self._h) or 0) for c in self._COLUMNS)
 
     @property
     def row_chain_score_ptr(self) -> int:
@@ -1400,15 +1264,6 @@ class RegionChain(_Owned):
     def row_coverage_ptr(self) -> int:
         """The device column row_coverage f64[n_rows]; 0 before coverage()."""
         return int(self._ctx._L.ks_rchain_device_row_coverage(self._h) or 0)
-
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """The columns of device_ptrs() as numpy arrays, in that order."""
-        n, r = self.n_regions, self.n_rows
-        u32 = lambda k: np.zeros(k, np.uint32)
-        cols = [np.zeros(r + 1, np.uint64), u32(self.n_chained), np.zeros(n, np.int64), u32(n), np.zeros(r, np.int64)] + \
-               [u32(r) for _ in range(6)] + [np.zeros(r, np.uint64), np.zeros(r, np.uint64), np.zeros(r, np.float64)]
-        self._ctx._check(self._ctx._L.ks_rchain_copy_to_host(self._ctx._h, self._h, *[_ptr(c) for c in cols]))
-        return tuple(cols)
 
     def coverage(self, hits: "Hits", d_q_off: int, n_q: int, d_t_off: int, n_t: int, mode="min") -> int:
         """ks_rchain_coverage: fills the chain's device column row_coverage f64[n_rows] — per hit row q_aligned / len(query)
@@ -1427,14 +1282,8 @@ class RegionChain(_Owned):
         """coverage from host arrays of sequence offsets u64[n + 1] (those of the batches `hits` was searched on): uploaded
         for the call, as align_regions does."""
         q_off = np.ascontiguousarray(q_off, dtype=np.uint64); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
-        bufs = []
-        try:
-            for a in (q_off, t_off):
-                bufs.append(self._ctx.to_device(a))
-            return self.coverage(hits, bufs[0].ptr, len(q_off) - 1, bufs[1].ptr, len(t_off) - 1, mode=mode)
-        finally:
-            for b in bufs:
-                b.free()
+        with self._ctx._uploaded(q_off, t_off) as (d_q, d_t):
+            return self.coverage(hits, d_q, len(q_off) - 1, d_t, len(t_off) - 1, mode=mode)
 
     def coverage_to_host(self) -> np.ndarray:
         """row_coverage f64[n_rows] of the last coverage call."""
@@ -1443,23 +1292,17 @@ class RegionChain(_Owned):
         return out
 
 
-class HitAlignments(_Owned):
+class HitAlignments(_Columns):
     """Device-resident result of Context.stitch_chains (ks_hitalns): per hit row ONE gapped alignment — the members of the
     row's chain with the links between them filled — as a CSR of BAM-encoded ops (row r owns ops [op_offsets[r],
     op_offsets[r + 1]), an op is len << 4 | code) and the columns of that alignment: its span on both sequences, score (i64),
     identities, positives, gap_opens, gaps, aln_length, the chain members, filled and open links and trimmed columns behind it,
     and the score as f64 (NaN: a row without a chain), a `score=` column for Context.best_hits and the cluster passes."""
-    _free = "ks_hitalns_free"
-    _COLUMNS = ("op_offsets", "ops", "q_start", "q_length", "t_start", "t_length", "score", "identities", "positives", "gap_opens",
-                "gaps", "aln_length", "n_members", "n_filled", "n_open", "n_trimmed", "row_score")
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_hitalns_n_rows(self._h))
-
-    @property
-    def n_ops(self) -> int:
-        return int(self._ctx._L.ks_hitalns_n_ops(self._h))
+    _PREFIX, _COUNTS = "hitalns", {"n_rows": "", "n_ops": ""}
+    _TABLE = (("op_offsets", "u8", "n_rows + 1"), ("ops", "u4", "n_ops")) + tuple(
+        (c, {"score": "i8", "row_score": "f8"}.get(c, "u4"), "n_rows") for c in (
+            "q_start", "q_length", "t_start", "t_length", "score", "identities", "positives", "gap_opens", "gaps", "aln_length",
+            "n_members", "n_filled", "n_open", "n_trimmed", "row_score"))
 
     @property
     def n_slices(self) -> int:
@@ -1471,84 +1314,35 @@ class HitAlignments(_Owned):
         """Direction scratch the call allocated.  Diagnostic."""
         return int(self._ctx._L.ks_hitalns_scratch_bytes(self._h))
 
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (op_offsets u64[n_rows + 1]; ops u32[n_ops]; and [n_rows] each: q_start, q_length, t_start,
-        t_length u32; score i64; identities, positives, gap_opens, gaps, aln_length, n_members, n_filled, n_open, n_trimmed u32;
-        row_score f64)."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_hitalns_device_" + c)(self._h) or 0) for c in self._COLUMNS)
-
     @property
     def row_score_ptr(self) -> int:
         """The device column row_score f64[n_rows]: pass it to Context.best_hits(score=...) or a cluster pass."""
         return int(self._ctx._L.ks_hitalns_device_row_score(self._h) or 0)
 
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """The columns of device_ptrs() as numpy arrays, in that order."""
-        r = self.n_rows
-        cols = [np.zeros(r + 1, np.uint64), np.zeros(self.n_ops, np.uint32)] + [np.zeros(r, np.uint32) for _ in range(4)] + \
-               [np.zeros(r, np.int64)] + [np.zeros(r, np.uint32) for _ in range(9)] + [np.zeros(r, np.float64)]
-        self._ctx._check(self._ctx._L.ks_hitalns_copy_to_host(self._ctx._h, self._h, *[_ptr(c) for c in cols]))
-        return tuple(cols)
-
     def ops_to_host(self) -> Tuple[np.ndarray, np.ndarray]:
         """(op_offsets u64[n_rows + 1], ops u32[n_ops]) alone."""
-        offs, ops = np.zeros(self.n_rows + 1, np.uint64), np.zeros(self.n_ops, np.uint32)
-        self._ctx._check(self._ctx._L.ks_hitalns_copy_to_host(self._ctx._h, self._h, _ptr(offs), _ptr(ops), *([None] * 15)))
-        return offs, ops
+        return self._copy_out(("op_offsets", "ops"))
 
     def strings(self) -> List[str]:
         """The CIGAR of every hit row as text, e.g. "60M40I60M"; "" for a row without a chain."""
         return cigar_strings(*self.ops_to_host())
 
 
-class Composition(_Owned):
+class Composition(_Columns):
     """Device-resident residue composition of a batch (ks_rcomp): counts u32[n_seqs, 28] over the residue classes of
     score_regions, length u32[n_seqs] and the class totals u64[28] of the batch."""
-    _free = "ks_rcomp_free"
-
-    @property
-    def n_seqs(self) -> int:
-        return int(self._ctx._L.ks_rcomp_n_seqs(self._h))
-
-    @property
-    def n_residues(self) -> int:
-        return int(self._ctx._L.ks_rcomp_n_residues(self._h))
-
-    def device_ptrs(self) -> Tuple[int, int, int]:
-        """Raw device pointers (counts u32[n_seqs * 28], totals u64[28], length u32[n_seqs])."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_rcomp_device_" + c)(self._h) or 0) for c in ("counts", "totals", "length"))
-
-    def to_host(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
-        """(counts u32[n_seqs, 28], totals u64[28], length u32[n_seqs])."""
-        n = self.n_seqs
-        counts = np.zeros((n, _lib.KS_RSCORE_ALPHABET), np.uint32)
-        totals = np.zeros(_lib.KS_RSCORE_ALPHABET, np.uint64)
-        length = np.zeros(n, np.uint32)
-        self._ctx._check(self._ctx._L.ks_rcomp_copy_to_host(self._ctx._h, self._h, _ptr(counts), _ptr(totals), _ptr(length)))
-        return counts, totals, length
+    _PREFIX, _COUNTS = "rcomp", {"n_seqs": "", "n_residues": ""}
+    _TABLE = (("counts", "u4", "n_seqs, 28"), ("totals", "u8", "28"), ("length", "u4", "n_seqs"))
 
 
-class AlignmentStats(_Owned):
+class AlignmentStats(_Columns):
     """Device-resident result of Context.alignment_stats (ks_astats): per hit row status u8 (0 regular, 1 fallback, 2 no
     composition asked for), x f64 (e^-lambda of the pair), lambda_ratio f64, row_bit_score and row_evalue f64 (the row's best;
     NaN for a row without entries); per entry bit_score and evalue f64."""
-    _free = "ks_astats_free"
-    _COLUMNS = ("status", "x", "lambda_ratio", "bit_score", "evalue", "row_bit_score", "row_evalue")
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_astats_n_rows(self._h))
-
-    @property
-    def n_entries(self) -> int:
-        return int(self._ctx._L.ks_astats_n_entries(self._h))
-
-    @property
-    def n_fallback(self) -> int:
-        """Hit rows whose composition gave no lambda of their own (ratio 1)."""
-        return int(self._ctx._L.ks_astats_n_fallback(self._h))
+    _PREFIX = "astats"
+    _COUNTS = {"n_rows": "", "n_entries": "", "n_fallback": "Hit rows whose composition gave no lambda of their own (ratio 1)."}
+    _TABLE = (("status", "u1", "n_rows"), ("x", "f8", "n_rows"), ("lambda_ratio", "f8", "n_rows"), ("bit_score", "f8", "n_entries"),
+              ("evalue", "f8", "n_entries"), ("row_bit_score", "f8", "n_rows"), ("row_evalue", "f8", "n_rows"))
 
     @property
     def lambda_std(self) -> float:
@@ -1567,12 +1361,6 @@ class AlignmentStats(_Owned):
         """0: lambda and K were computed (ungapped), 1: the caller's."""
         return int(self._ctx._L.ks_astats_params_source(self._h))
 
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (status u8, x, lambda_ratio f64 [n_rows]; bit_score, evalue f64 [n_entries]; row_bit_score,
-        row_evalue f64 [n_rows])."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_astats_device_" + c)(self._h) or 0) for c in self._COLUMNS)
-
     @property
     def row_bit_score_ptr(self) -> int:
         """The device column row_bit_score f64[n_rows]: pass it to Context.best_hits(score=...) or a cluster pass."""
@@ -1583,58 +1371,16 @@ class AlignmentStats(_Owned):
         """The device column row_evalue f64[n_rows]."""
         return int(self._ctx._L.ks_astats_device_row_evalue(self._h) or 0)
 
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """(status u8, x, lambda_ratio f64 [n_rows], bit_score, evalue f64 [n_entries], row_bit_score, row_evalue f64 [n_rows])."""
-        nr, n = self.n_rows, self.n_entries
-        cols = [np.zeros(nr, np.uint8), np.zeros(nr, np.float64), np.zeros(nr, np.float64), np.zeros(n, np.float64), np.zeros(n, np.float64),
-                np.zeros(nr, np.float64), np.zeros(nr, np.float64)]
-        self._ctx._check(self._ctx._L.ks_astats_copy_to_host(self._ctx._h, self._h, *[_ptr(c) for c in cols]))
-        return tuple(cols)
 
-
-class Clusters(_Owned):
+class Clusters(_Columns):
     """Device-resident clusters of a hit list (ks_clusters): per node its label and cluster_id, the clusters as a CSR (offsets,
     members) and a representative per cluster.  From cluster(): connected components, the label is the smallest id of the
     cluster and orders the clusters.  From cluster_greedy(): the label is the representative's id and orders the clusters."""
-    _free = "ks_clusters_free"
-    _COLUMNS = ("label", "cluster_id", "offsets", "members", "representative")
-
-    @property
-    def n_nodes(self) -> int:
-        return int(self._ctx._L.ks_clusters_n_nodes(self._h))
-
-    @property
-    def n_clusters(self) -> int:
-        return int(self._ctx._L.ks_clusters_n_clusters(self._h))
-
-    @property
-    def n_edges(self) -> int:
-        """Rows that passed the threshold: self rows and both directions counted as they occur."""
-        return int(self._ctx._L.ks_clusters_n_edges(self._h))
-
-    @property
-    def largest(self) -> int:
-        return int(self._ctx._L.ks_clusters_largest(self._h))
-
-    @property
-    def n_rounds(self) -> int:
-        """Rounds a cluster_greedy() result took (a diagnostic: it may depend on the schedule); 0 for cluster()."""
-        return int(self._ctx._L.ks_clusters_n_rounds(self._h))
-
-    def device_ptrs(self) -> Tuple[int, ...]:
-        """Raw device pointers (label / cluster_id u32[n_nodes], offsets u64[n_clusters + 1], members u32[n_nodes],
-        representative u32[n_clusters])."""
-        L = self._ctx._L
-        return tuple(int(getattr(L, "ks_clusters_device_" + c)(self._h) or 0) for c in self._COLUMNS)
-
-    def to_host(self) -> Tuple[np.ndarray, ...]:
-        """(label, cluster_id u32[n_nodes], offsets u64[n_clusters + 1], members u32[n_nodes], representative u32[n_clusters])."""
-        n, nc = self.n_nodes, self.n_clusters
-        label, cid, members = (np.zeros(n, np.uint32) for _ in range(3))
-        offs, rep = np.zeros(nc + 1, np.uint64), np.zeros(nc, np.uint32)
-        self._ctx._check(self._ctx._L.ks_clusters_copy_to_host(self._ctx._h, self._h, _ptr(label), _ptr(cid), _ptr(offs), _ptr(members),
-                                                               _ptr(rep)))
-        return label, cid, offs, members, rep
+    _PREFIX = "clusters"
+    _COUNTS = {"n_nodes": "", "n_clusters": "", "n_edges": "Rows that passed the threshold: self rows and both directions counted as they occur.",
+               "largest": "", "n_rounds": "Rounds a cluster_greedy() result took (a diagnostic: it may depend on the schedule); 0 for cluster()."}
+    _TABLE = (("label", "u4", "n_nodes"), ("cluster_id", "u4", "n_nodes"), ("offsets", "u8", "n_clusters + 1"), ("members", "u4", "n_nodes"),
+              ("representative", "u4", "n_clusters"))
 
 
 class Corpus(_Owned):
@@ -1662,18 +1408,10 @@ class Corpus(_Owned):
         return h, a, d
 
 
-class Significance(_Owned):
+class Significance(_Columns):
     """Device-resident f64 columns over hit rows (ks_signif): prob_overlap and tf_idf, row r belongs to row r of the hits."""
-    _free = "ks_signif_free"
-
-    @property
-    def n_rows(self) -> int:
-        return int(self._ctx._L.ks_signif_n_rows(self._h))
-
-    def device_ptrs(self) -> Tuple[int, int]:
-        """Raw device pointers of the columns (prob_overlap f64, tf_idf f64), `n_rows` entries each."""
-        L = self._ctx._L
-        return tuple(int(f(self._h) or 0) for f in (L.ks_signif_device_prob_overlap, L.ks_signif_device_tf_idf))
+    _PREFIX, _COUNTS = "signif", {"n_rows": ""}
+    _TABLE = (("prob_overlap", "f8", "n_rows"), ("tf_idf", "f8", "n_rows"))
 
     @property
     def prob_overlap_ptr(self) -> int:
@@ -1684,13 +1422,6 @@ class Significance(_Owned):
     def tf_idf_ptr(self) -> int:
         """Device pointer of the tf_idf column (`Context.best_hits(score=...)`)."""
         return self.device_ptrs()[1]
-
-    def to_host(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(prob_overlap f64, tf_idf f64) per hit row."""
-        n = self.n_rows
-        po = np.zeros(n, np.float64); tf = np.zeros(n, np.float64)
-        self._ctx._check(self._ctx._L.ks_signif_copy_to_host(self._ctx._h, self._h, _ptr(po), _ptr(tf)))
-        return po, tf
 
 
 class Index(_Owned):
