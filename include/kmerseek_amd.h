@@ -1377,6 +1377,44 @@ uint32_t ks_clusters_n_rounds(const ks_clusters *c);
 /* live edges at or below which one workgroup finishes the greedy rounds (the tests size an edge list on either side of it) */
 uint32_t ks_debug_greedy_tail_edges(void);
 
+/* ---- test hooks: the device-wide primitives, called directly ----------------------------------
+ * The exclusive scans, the stable LSD radix sort and the MSD match sort that the passes above stand on, on arrays the caller
+ * chooses (tests/test_gpu_prims.py).  Not part of the product interface.  For all of them: the pointers are the caller's device
+ * memory on ctx's device unless marked HOST; the arguments are checked on the host before anything is launched
+ * (KS_ERR_INVALID_ARG: a NULL, n >= 2^32 - 1, a value outside the range named below); scratch comes from the context's pool and
+ * goes back; the call returns when the work is done and fails with KS_ERR_HIP when a scan's look-back gave up. */
+/* kind 0: exclusive scan u32 -> u64, d_out has n + 1 entries (d_out[n] = the total; the sum must stay below 2^38), d_total is not
+ * used.  kind 1: exclusive scan u32 -> u32 (sums wrap at 2^32) of a copy of d_in in d_out (n entries), in place there;
+ * d_total (may be NULL) receives the total.  kind 2: kind 0 without the bound on the sum (never the one-launch path). */
+int ks_debug_scan(ks_ctx *ctx, int kind, const uint32_t *d_in, void *d_out, uint64_t n, uint32_t *d_total);
+/* The one-launch scans number their tiles from a counter that grows for the life of the context; a tile's status word lives in
+ * slot (number mod 2^20) of a ring that is never cleared and carries the number's low 24 bits as its tag.  This sets the number
+ * the next such scan starts at (the ring and the counter are made if the context has none yet; the ring keeps its words).  The
+ * caller answers for a state the counter could have reached by counting: a word left in a slot must not carry the tag the new
+ * numbering expects there, i.e. no earlier scan on this context used a number that is equal mod 2^24 to one about to be used
+ * unless the slot was rewritten in between (by counting, 2^20 tiles before at the latest). */
+int ks_debug_scan_seek(ks_ctx *ctx, uint32_t global_tile);
+/* *base = the number the next one-launch scan starts at: it advances by a scan's tile count (ceil(n / 2048)) iff the scan took the
+ * one-launch path (a single tile, n == 0 and KS_DEBUG_SCAN_3PASS do not) */
+int ks_debug_scan_ticket(ks_ctx *ctx, uint32_t *base);
+/* Stable LSD passes over n (key u64, value) records, one 8-bit digit per listed shift: shifts (HOST) holds n_shifts (1 .. 8)
+ * values in 0 .. 56.  vbytes 0 (keys only, d_vals / d_vals_out not used), 4 or 8 picks the value width.  vbytes 4 only:
+ * pfxK != 0 — the digits are bits [shift, shift + 8) of umulhi(key >> 32, pfxK) instead of the key's; seg_len != NULL — the input
+ * of the first pass lies in seg_regions regions seg_cap records apart, seg_len[r] of them filled (their sum must be n).
+ * alias_in != 0: the input is first copied into one of the two scratch pairs and sorted from there (the in-place form).
+ * The sorted records are copied to d_keys_out / d_vals_out (n entries each), wherever the passes left them. */
+int ks_debug_radix_sort(ks_ctx *ctx, int vbytes, const uint64_t *d_keys, const void *d_vals, uint64_t n, const int *shifts,
+                        int n_shifts, uint32_t pfxK, const uint32_t *seg_len, uint64_t seg_cap, uint32_t seg_regions,
+                        int alias_in, uint64_t *d_keys_out, void *d_vals_out);
+/* The match sort, in place: d_keys ordered on key bits [lo_bit, lo_bit + nbits), the order among equal keys unspecified
+ * (0 <= lo_bit, 1 <= nbits <= 64 - lo_bit).  seg_count != NULL (HOST, n_segs entries, 1 .. 64): the list lies in n_segs segments
+ * seg_cap records apart, seg_count[s] of them filled (their sum must be n, d_keys spans n_segs * seg_cap records); the sorted list
+ * is dense, d_keys[0, n).  info (HOST) = { done, bits of the second partition level, buckets, buckets that went to the large-bucket
+ * kernel }.  done == 0 (and the other three): this sort does not apply (n < 65,536, nbits <= 16 or KS_DEBUG_PAIRS_LSD) and the
+ * list is untouched. */
+int ks_debug_msd_sort(ks_ctx *ctx, uint64_t *d_keys, uint64_t n, int lo_bit, int nbits, const uint32_t *seg_count, uint32_t n_segs,
+                      uint64_t seg_cap, uint32_t info[4]);
+
 /* ---- measurement --------------------------------------------------------------------------- */
 
 /* Per-kernel HIP-event timing on ctx's stream.  enable: 0 off; 1 events bracket every launch (~20 us of idle queue

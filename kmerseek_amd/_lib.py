@@ -442,6 +442,12 @@ SIGNATURES = {
     "ks_hits_cluster_greedy": (C.c_int, [_vp, _vp, _vp, _vp, C.POINTER(ks_greedy_opts), _pp]),
     "ks_clusters_n_rounds": (C.c_uint32, [_vp]),
     "ks_debug_greedy_tail_edges": (C.c_uint32, []),
+    "ks_debug_scan": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint64, _vp]),
+    "ks_debug_scan_seek": (C.c_int, [_vp, C.c_uint32]),
+    "ks_debug_scan_ticket": (C.c_int, [_vp, _u32p]),
+    "ks_debug_radix_sort": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint64, C.POINTER(C.c_int), C.c_int, C.c_uint32, _vp, C.c_uint64,
+                                      C.c_uint32, C.c_int, _vp, _vp]),
+    "ks_debug_msd_sort": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, C.c_int, _u32p, C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32 * 4)]),
     "ks_timing_enable": (C.c_int, [_vp, C.c_int]),
     "ks_timing_reset": (C.c_int, [_vp]),
     "ks_timing_get": (C.c_int, [_vp, C.POINTER(ks_kernel_time), C.c_uint32, _u32p]),

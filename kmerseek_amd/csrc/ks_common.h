@@ -810,7 +810,17 @@ int ks_seg_path_knob(const ks_ctx *ctx, int dbg_id, bool *small);
 
 // ---- device-wide primitives (ks_scan.hip, ks_sort.hip) ----
 // exclusive scan of n u32 values into u64 (out[n] = total is also written: out has n+1 entries)
+// BOUND: the SUM must stay below 2^38 whenever the one-launch path runs (2 or more tiles of 2048 values, at most 2^19 tiles,
+// KS_DEBUG_SCAN_3PASS unset): a tile's status word carries its running sum in 38 bits under the 24-bit tile tag, and the path is
+// picked by n (n < 2^38), not by the sum — a larger sum runs into the tag, predecessors stop matching and the look-back gives
+// up (ks_scan_status_check reports it; nothing hangs).  A single tile and the 3-pass path have no such limit.  2^38 u32 counts
+// of records that exist in device memory cannot be reached; a sum of sizes that are only COMPUTED (DESIGN.md §"primitives,
+// tested directly" lists the callers) needs a host-side bound of its own.
 int ks_scan_u32_to_u64(ks_ctx *ctx, const u32 *in, u64 *out, u64 n);
+// ... without that bound (never the one-launch path: two more small launches), for sums of sizes that nothing has allocated yet
+int ks_scan_u32_to_u64_wide(ks_ctx *ctx, const u32 *in, u64 *out, u64 n);
+// the status ring + ticket words of the one-launch scans, made by the context's first such scan (or by a test hook before it)
+int ks_scan_ring_make(ks_ctx *ctx);
 // exclusive scan u32 -> u32 in place (n < 2^32 total); optionally writes the total to d_total
 // The one-launch scans cannot report a look-back that gave up (bounded spin) by themselves: callers enqueue
 // ks_scan_status_fetch before a stream synchronisation they do anyway and call ks_scan_status_check after it.
@@ -879,6 +889,14 @@ struct ks_msd_plan {
     u32 *blk;        // off1 | off2 | big-list counter | big list (ks_msd.hip)
     const u32 *ends; // [KS_MSD_REGIONS] inside blk
 };
+// what levels 2 / 3 need of a plan: how wide level 2 is (*bits2_out: a function of n and nbits alone) and where the words of the
+// plan's block lie (n_zero words that start at zero: the histograms, then the big-list counter as the last of them)
+struct ms_layout {
+    int shift1, shift2;
+    u32 mask2, n_buckets, n_sub, sub_stride;
+    size_t off2_words, n_zero;
+};
+ms_layout ms_layout_of(u64 n, int lo_bit, int nbits, int *bits2_out);
 int ks_msd_level1(ks_ctx *ctx, u64 *ka, u64 *kb, u64 n, int lo_bit, int nbits, const ks_msd_segs *segs, ks_msd_plan *P);
 int ks_msd_finish(ks_ctx *ctx, ks_msd_plan *P);
 void ks_msd_drop(ks_ctx *ctx, ks_msd_plan *P);

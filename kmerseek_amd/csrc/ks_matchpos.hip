@@ -256,7 +256,7 @@ static int mp_run(ks_ctx *ctx, const ks_kmerpos *Q, const ks_kmerpos *T, const k
     while (top_step < 0x80000000u && (top_step << 1) <= n_t) top_step <<= 1;
     KS_LAUNCH(ctx, "matchpos_count", k_mp_count, (n_q + 255) / 256, 256, (const u64 *)Q->d_hash, (const u32 *)Q->d_start, n_q, (const u64 *)t_hash,
               n_t, top_step, lo, cnt, ctl);
-    KS_TRY(ks_scan_u32_to_u64(ctx, cnt, off, n_q));
+    KS_TRY(ks_scan_u32_to_u64_wide(ctx, cnt, off, n_q)); // (candidate pairs, counted before the limit below is held against them)
     u64 *const rb = ctx->h_pin + KS_PIN_READ; // candidate pairs | longest starts
     KS_TRY(ks_stream_wait_fetch_scans(ctx, {ks_fetch_words(off + n_q, rb, 2), ks_fetch_words(ctl, rb + 1, 2)}));
     const u64 n_cand = rb[0];

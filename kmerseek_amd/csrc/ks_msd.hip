@@ -404,12 +404,8 @@ __global__ __launch_bounds__(ML_THREADS) void k_msd_local_big(u64 *keys, u64 *sc
 }
 
 // what levels 2 / 3 need of a plan: how wide level 2 is (a function of n and nbits alone) and where the words of the block lie
-struct ms_layout {
-    int shift1, shift2;
-    u32 mask2, n_buckets, n_sub, sub_stride;
-    size_t off2_words, n_zero;
-};
-static ms_layout ms_layout_of(u64 n, int lo_bit, int nbits, int *bits2_out) {
+// (struct ms_layout: ks_common.h)
+ms_layout ms_layout_of(u64 n, int lo_bit, int nbits, int *bits2_out) {
     // level 2 is as wide as it takes for ~768 records per bucket (0 .. 8 bits): a short list does not pay 65,536 buckets
     // ... and then as wide as it takes to save a local pass (remaining bits a multiple of 8): passes cost more than buckets
     // (up to 9 bits: 131,072 buckets through a 1024-bin window — lists beyond ~40 M records, where 65,536 buckets would leave

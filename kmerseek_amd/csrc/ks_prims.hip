@@ -168,8 +168,20 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan_lookback(const TIn *in, T
     if (total_out && tile == n_tiles - 1 && tid == 0) *total_out = (TOut)(base_s + (u64)total);
 }
 
+// the status ring and the ticket words of the one-launch scans, made (and cleared, once) by the context's first such scan
+int ks_scan_ring_make(ks_ctx *ctx) {
+    if (ctx->scan_ring) return KS_OK;
+    KS_HIP(ctx, hipMalloc((void **)&ctx->scan_ring, (size_t)SCAN_RING * sizeof(unsigned long long)));
+    KS_HIP(ctx, hipMalloc((void **)&ctx->scan_ticket, 2 * sizeof(u32)));
+    KS_HIP(ctx, hipMemsetAsync(ctx->scan_ring, 0, (size_t)SCAN_RING * sizeof(unsigned long long), ctx->stream));
+    KS_HIP(ctx, hipMemsetAsync(ctx->scan_ticket, 0, 2 * sizeof(u32), ctx->stream));
+    ctx->scan_ticket_base = 0;
+    return KS_OK;
+}
+
+// one_launch = false: never the look-back path — for 64-bit sums that may reach 2^38, which its status words cannot carry
 template <typename TIn, typename TOut>
-static int scan_generic(ks_ctx *ctx, const TIn *in, TOut *out, u64 n, TOut *d_total) {
+static int scan_generic(ks_ctx *ctx, const TIn *in, TOut *out, u64 n, TOut *d_total, bool one_launch = true) {
     if (n == 0) {
         if (d_total) KS_HIP(ctx, hipMemsetAsync(d_total, 0, sizeof(TOut), ctx->stream));
         return KS_OK;
@@ -179,14 +191,8 @@ static int scan_generic(ks_ctx *ctx, const TIn *in, TOut *out, u64 n, TOut *d_to
         KS_LAUNCH(ctx, "scan_apply", (k_scan_apply<TIn, TOut>), 1, SCAN_THREADS, in, out, (const TOut *)nullptr, n, d_total);
         return KS_OK;
     }
-    if (nblocks <= SCAN_RING / 2 && n < (1ULL << SCAN_VAL_BITS) && !ks_dbg(ctx, KS_DBG_SCAN_3PASS)) {
-        if (!ctx->scan_ring) {
-            KS_HIP(ctx, hipMalloc((void **)&ctx->scan_ring, (size_t)SCAN_RING * sizeof(unsigned long long)));
-            KS_HIP(ctx, hipMalloc((void **)&ctx->scan_ticket, 2 * sizeof(u32)));
-            KS_HIP(ctx, hipMemsetAsync(ctx->scan_ring, 0, (size_t)SCAN_RING * sizeof(unsigned long long), ctx->stream));
-            KS_HIP(ctx, hipMemsetAsync(ctx->scan_ticket, 0, 2 * sizeof(u32), ctx->stream));
-            ctx->scan_ticket_base = 0;
-        }
+    if (one_launch && nblocks <= SCAN_RING / 2 && n < (1ULL << SCAN_VAL_BITS) && !ks_dbg(ctx, KS_DBG_SCAN_3PASS)) {
+        KS_TRY(ks_scan_ring_make(ctx));
         ks_timer_begin(ctx, "scan_lookback");
         hipLaunchKernelGGL((k_scan_lookback<TIn, TOut>), dim3((u32)nblocks), dim3(SCAN_THREADS), 0, ctx->stream, in, out, n, d_total,
                            ctx->scan_ring, ctx->scan_ticket, ctx->scan_ticket_base, (u32)nblocks);
@@ -203,7 +209,8 @@ static int scan_generic(ks_ctx *ctx, const TIn *in, TOut *out, u64 n, TOut *d_to
         KS_LAUNCH(ctx, "scan_small", (k_scan_small<TOut>), 1, SCAN_THREADS, sums, nblocks);
         st = KS_OK;
     } else {
-        st = scan_generic<TOut, TOut>(ctx, sums, sums, nblocks, (TOut *)nullptr);
+        // (the block sums of a list this long add up to anything a u64 holds: only 32-bit sums go back to the look-back path)
+        st = scan_generic<TOut, TOut>(ctx, sums, sums, nblocks, (TOut *)nullptr, sizeof(TOut) == 4);
     }
     if (st == KS_OK) {
         ks_timer_begin(ctx, "scan_apply");
@@ -241,6 +248,10 @@ int ks_stream_wait_fetch_scans(ks_ctx *ctx, std::initializer_list<ks_fetch_seg> 
 int ks_scan_u32_to_u64(ks_ctx *ctx, const u32 *in, u64 *out, u64 n) {
     // out[n] receives the total
     return scan_generic<u32, u64>(ctx, in, out, n, out + n);
+}
+
+int ks_scan_u32_to_u64_wide(ks_ctx *ctx, const u32 *in, u64 *out, u64 n) {
+    return scan_generic<u32, u64>(ctx, in, out, n, out + n, false);
 }
 
 int ks_scan_u32_inplace(ks_ctx *ctx, u32 *data, u64 n, u32 *d_total) {

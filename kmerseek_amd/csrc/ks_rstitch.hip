@@ -375,7 +375,7 @@ int ks_regions_stitch_impl(ks_ctx *ctx, const ks_rchain *K, const ks_raligns *S,
     u8 *dir = nullptr, *cols = nullptr;
     if (nm) {
         KS_LAUNCH(ctx, "rstitch_plan", k_rs_plan, (u32)((nm + RS_THREADS - 1) / RS_THREADS), RS_THREADS, A, links, rows, ncols);
-        KS_TRY(ks_scan_u32_to_u64(ctx, rows, dir_off, nm));
+        KS_TRY(ks_scan_u32_to_u64_wide(ctx, rows, dir_off, nm)); // (the directions are made in slices: no allocation bounds their sum)
         KS_TRY(ks_scan_u32_to_u64(ctx, ncols, col_off, nm));
         KS_TRY(ks_stream_wait_fetch_scans(ctx, {ctl.fetch(), ks_fetch_words(dir_off + nm, rb, 2), ks_fetch_words(col_off + nm, rb + 1, 2)}));
         if (ctl.bad(RS_BAD_SRC))

@@ -204,7 +204,7 @@ int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H
     A.bad = ctl.words();
     const u32 grid = (u32)((ng + RT_THREADS / 64 - 1) / (RT_THREADS / 64));
     KS_LAUNCH(ctx, "rtrace_plan", k_rt_plan, grid, RT_THREADS, A, rows, ncols);
-    KS_TRY(ks_scan_u32_to_u64(ctx, rows, dir_off, ng));
+    KS_TRY(ks_scan_u32_to_u64_wide(ctx, rows, dir_off, ng)); // (the directions are made in slices: no allocation bounds their sum)
     KS_TRY(ks_scan_u32_to_u64(ctx, ncols, col_off, ng));
     u64 *const rb = ctx->h_pin + KS_PIN_RTRACE + RT_N_BAD; // direction rows | columns | ops
     KS_TRY(ks_stream_wait_fetch_scans(ctx, {ctl.fetch(), ks_fetch_words(dir_off + ng, rb, 2), ks_fetch_words(col_off + ng, rb + 1, 2)}));

@@ -295,6 +295,36 @@ class Context:
             out["join_table"] = int(v[4])
         return out
 
+    # ---- test hooks: the device-wide primitives on device pointers (ks_debug_scan ... ks_debug_msd_sort) ----
+    def debug_scan(self, kind: int, d_in: int, d_out: int, n: int, d_total: int = 0):
+        """kind 0: u32 -> u64 into d_out[0 .. n] (d_out[n] = total); kind 1: u32 -> u32 into d_out[0 .. n), total to d_total (0: none);
+        kind 2: kind 0 for sums of 2^38 and more (never the one-launch path)."""
+        self._check(self._L.ks_debug_scan(self._h, int(kind), C.c_void_p(d_in), C.c_void_p(d_out), int(n), C.c_void_p(d_total or None)))
+
+    def debug_scan_seek(self, global_tile: int):
+        self._check(self._L.ks_debug_scan_seek(self._h, int(global_tile) & 0xffffffff))
+
+    def debug_scan_ticket(self) -> int:
+        v = C.c_uint32(0)
+        self._check(self._L.ks_debug_scan_ticket(self._h, C.byref(v)))
+        return int(v.value)
+
+    def debug_radix_sort(self, vbytes: int, d_keys: int, d_vals: int, n: int, shifts: Sequence[int], d_keys_out: int, d_vals_out: int,
+                         pfx_k: int = 0, d_seg_len: int = 0, seg_cap: int = 0, seg_regions: int = 0, alias_in: bool = False):
+        sh = (C.c_int * max(len(shifts), 1))(*[int(s) for s in shifts])
+        self._check(self._L.ks_debug_radix_sort(self._h, int(vbytes), C.c_void_p(d_keys), C.c_void_p(d_vals or None), int(n), sh, len(shifts),
+                                                int(pfx_k), C.c_void_p(d_seg_len or None), int(seg_cap), int(seg_regions), int(bool(alias_in)),
+                                                C.c_void_p(d_keys_out), C.c_void_p(d_vals_out or None)))
+
+    def debug_msd_sort(self, d_keys: int, n: int, lo_bit: int, nbits: int, seg_count: Optional[Sequence[int]] = None,
+                       seg_cap: int = 0) -> Dict[str, int]:
+        """The match sort in place on d_keys; returns {done, bits2, n_buckets, big} as the library reports them."""
+        info = (C.c_uint32 * 4)()
+        sc = None if seg_count is None else (C.c_uint32 * max(len(seg_count), 1))(*[int(c) for c in seg_count])
+        self._check(self._L.ks_debug_msd_sort(self._h, C.c_void_p(d_keys), int(n), int(lo_bit), int(nbits), sc,
+                                              0 if seg_count is None else len(seg_count), int(seg_cap), C.byref(info)))
+        return dict(zip(("done", "bits2", "n_buckets", "big"), (int(x) for x in info)))
+
     # ---- sketch ----
     def sketch_batch(self, residues: np.ndarray, offsets: np.ndarray, ksize: int, scaled: int, moltype: str,
                      seed: int = SEED) -> "Sketches":

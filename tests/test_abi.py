@@ -125,7 +125,7 @@ def test_every_entry_point_with_a_context_is_guarded():
     import re
     csrc = os.path.join(ROOT, "kmerseek_amd", "csrc")
     unguarded = []
-    for f in ("ks_api.hip", "ks_hits.hip", "ks_ctx.hip", "ks_copy.hip"):
+    for f in ("ks_api.hip", "ks_hits.hip", "ks_ctx.hip", "ks_copy.hip", "ks_debug_prims.hip"):
         src = open(os.path.join(csrc, f)).read()
         for m in re.finditer(r'^extern "C" int (\w+)\(([^)]*)\)\s*\{', src, re.M):
             name, params = m.group(1), m.group(2)
