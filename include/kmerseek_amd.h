@@ -288,6 +288,75 @@ int ks_sketches_union_groups(ks_ctx *ctx, const ks_sketches *in, const uint32_t 
 uint32_t ks_debug_translate_chunk(void);   /* bases one workgroup of the translate kernel owns: the tests put record ends around it */
 uint32_t ks_debug_union_rank_max(void);    /* largest group the rank path takes */
 
+/* ---- low-complexity masking: mask, split and the masked sketch ---------------------------------------------------------- */
+
+/* A low-complexity filter applied before sketching, as the search tools of the BLAST family apply SEG.  The rule is THIS
+ * LIBRARY'S OWN, defined in integers: the first stage of SEG (trigger windows, extension over contiguous windows) without the
+ * second-stage trimming.  NCBI seg is not part of this build and NO PARITY IS CLAIMED.
+ *   classes     a residue's class is its letter without case (26), '*' (1) or "any other byte" (1): 28 classes.  X and * are
+ *               classes like any other.
+ *   window      W residues.  T[c] = floor(c log2(c) 65536 + 0.5), T[0] = 0 (a committed table).  The window of record r that
+ *               starts at p is valid iff p + W <= end(r); its complexity is e(p) = T[W] - sum over classes of T[count], W * 65536
+ *               times its Shannon entropy in bits.
+ *   thresholds  in millibits: lo1(p) iff e(p) <= floor(k1 W 65536 / 1000) (the trigger), lo2(p) likewise with k2 >= k1 (the
+ *               extension).  Invalid windows are neither.
+ *   hysteresis  a run is a maximal stretch of consecutive window starts with lo2 (it cannot cross a record: the last W - 1
+ *               starts of a record are invalid); it is hot iff it holds a lo1 window.  A hot run [i, j) masks the residues
+ *               [i, j - 1 + W).  Nothing else is masked.
+ *   segments    of a record: its maximal stretches of unmasked residues of at least min_len residues, in order; possibly none.
+ * Everything is integer arithmetic: the result does not depend on the launch geometry.
+ * ks_mask_opts: window 0 means 12; window, k1 and k2 ALL 0 (and opts == NULL) mean the defaults 12 / 2200 / 2500; otherwise k1
+ * and k2 are taken as given (k1 = k2 = 0 masks exactly the windows of one class).  KS_ERR_INVALID_ARG, before any device work:
+ * window outside [2, KS_MASK_MAX_WINDOW], k2 < k1, NULL arguments; found on the device and named in the message: offsets that do
+ * not start at 0, ascend and end at n_residues, a record beyond 2^32 - 16 residues.  KS_ERR_CAPACITY: 2^32 - 64 or more
+ * residues in one batch.  One stream, one wait per call, synchronous on return. */
+#define KS_MASK_MAX_WINDOW 32
+typedef struct ks_mask_opts { uint32_t window, k1_millibits, k2_millibits; } ks_mask_opts;
+typedef struct ks_mask ks_mask;
+typedef struct ks_segments ks_segments;
+int ks_mask_device(ks_ctx *ctx, const uint8_t *d_residues, const uint64_t *d_seq_offsets, uint32_t n_seqs, uint64_t n_residues,
+                   const ks_mask_opts *opts, ks_mask **out);
+/* the same from host arrays (the layout ks_sketch_batch takes) */
+int ks_mask_batch(ks_ctx *ctx, const uint8_t *residues, const uint64_t *seq_offsets, uint32_t n_seqs, const ks_mask_opts *opts,
+                  ks_mask **out);
+uint32_t ks_mask_n_seqs(const ks_mask *m);
+uint64_t ks_mask_n_residues(const ks_mask *m);
+uint64_t ks_mask_n_masked(const ks_mask *m);
+const uint8_t *ks_mask_device_mask(const ks_mask *m);            /* n_residues bytes, 1 = masked */
+const uint32_t *ks_mask_device_masked_counts(const ks_mask *m);  /* n_seqs */
+int ks_mask_copy_to_host(ks_ctx *ctx, const ks_mask *m, uint8_t *mask, uint32_t *masked_counts); /* either may be NULL */
+void ks_mask_free(ks_mask *m);
+/* The segments of a batch under a mask made from it (same n_seqs and n_residues, or KS_ERR_INVALID_ARG): seg_record and
+ * seg_start (relative to the record) per segment, the segments' residues as one compacted buffer with u64 offsets — the batch
+ * layout every *_device sketch entry reads, 16-byte aligned — and per record the range of its segments.  min_len 0 counts as 1. */
+int ks_mask_split_device(ks_ctx *ctx, const ks_mask *mask, const uint8_t *d_residues, const uint64_t *d_seq_offsets, uint32_t n_seqs,
+                         uint64_t n_residues, uint32_t min_len, ks_segments **out);
+uint64_t ks_segments_n_segs(const ks_segments *s);
+uint64_t ks_segments_n_residues(const ks_segments *s);
+uint32_t ks_segments_n_records(const ks_segments *s);
+const uint32_t *ks_segments_device_seg_record(const ks_segments *s);
+const uint32_t *ks_segments_device_seg_start(const ks_segments *s);
+const uint64_t *ks_segments_device_seg_offsets(const ks_segments *s);   /* n_segs + 1 */
+const uint8_t *ks_segments_device_residues(const ks_segments *s);
+const uint32_t *ks_segments_device_group_offsets(const ks_segments *s); /* n_records + 1 */
+int ks_segments_copy_to_host(ks_ctx *ctx, const ks_segments *s, uint32_t *seg_record, uint32_t *seg_start, uint64_t *seg_offsets,
+                             uint8_t *residues, uint32_t *group_offsets);
+void ks_segments_free(ks_segments *s);
+/* The masked sketch: the hashes of exactly those windows of a record that contain no masked residue, abundances counted over
+ * those windows — mask, split at min_len = ksize, ks_sketch_batch_device on the segments, ks_sketches_union_groups by record.
+ * The result is a plain ks_sketches of n_seqs records; n_windows is the sum over the segments; a record without a segment has
+ * an empty sketch.  Records with more than ks_debug_union_rank_max() segments send the batch's union down its sort path.
+ * max_seq_len as in ks_sketch_batch_device.  All scratch goes back to the context's pool before the call returns. */
+int ks_sketch_masked_device(ks_ctx *ctx, const uint8_t *d_residues, const uint64_t *d_seq_offsets, uint32_t n_seqs, uint64_t n_residues,
+                            uint32_t max_seq_len, const ks_params *params, const ks_mask_opts *opts, ks_sketches **out);
+int ks_sketch_masked(ks_ctx *ctx, const uint8_t *residues, const uint64_t *seq_offsets, uint32_t n_seqs, const ks_params *params,
+                     const ks_mask_opts *opts, ks_sketches **out);
+/* ks_kmer_positions_device on the segments, every triple carried back to its record: seq = the segment's record, start counted
+ * from the record's first residue, ordered by (seq, start) — the table that agrees with a masked sketch in ks_match_positions. */
+int ks_kmer_positions_masked_device(ks_ctx *ctx, const uint8_t *d_residues, const uint64_t *d_seq_offsets, uint32_t n_seqs,
+                                    uint64_t n_residues, const ks_params *params, const ks_mask_opts *opts, ks_kmerpos **out);
+uint32_t ks_debug_mask_chunk(void);        /* residues one workgroup of the mask kernels owns: the tests put runs around it */
+
 /* ---- k-mer positions ----------------------------------------------------------------------- */
 
 /* Replaces ProteomeIndex::process_kmers (src/rust/index.rs:749-786): for every window whose hash

@@ -141,6 +141,13 @@ class ks_gather_opts(C.Structure):
     _fields_ = [("min_unique", C.c_uint32), ("max_results", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+KS_MASK_MAX_WINDOW = 32
+
+
+class ks_mask_opts(C.Structure):
+    _fields_ = [("window", C.c_uint32), ("k1_millibits", C.c_uint32), ("k2_millibits", C.c_uint32)]
+
+
 class ks_kernel_time(C.Structure):
     _fields_ = [("name", C.c_char * 48), ("launches", C.c_uint64), ("total_ms", C.c_double)]
 
@@ -202,6 +209,30 @@ SIGNATURES = {
     "ks_sketches_union_groups": (C.c_int, [_vp, _vp, _u32p, C.c_uint32, _pp]),
     "ks_debug_translate_chunk": (C.c_uint32, []),
     "ks_debug_union_rank_max": (C.c_uint32, []),
+    "ks_mask_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(ks_mask_opts), _pp]),
+    "ks_mask_batch": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.POINTER(ks_mask_opts), _pp]),
+    "ks_mask_n_seqs": (C.c_uint32, [_vp]),
+    "ks_mask_n_residues": (C.c_uint64, [_vp]),
+    "ks_mask_n_masked": (C.c_uint64, [_vp]),
+    "ks_mask_device_mask": (_vp, [_vp]),
+    "ks_mask_device_masked_counts": (_vp, [_vp]),
+    "ks_mask_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "ks_mask_free": (None, [_vp]),
+    "ks_mask_split_device": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, _pp]),
+    "ks_segments_n_segs": (C.c_uint64, [_vp]),
+    "ks_segments_n_residues": (C.c_uint64, [_vp]),
+    "ks_segments_n_records": (C.c_uint32, [_vp]),
+    "ks_segments_device_seg_record": (_vp, [_vp]),
+    "ks_segments_device_seg_start": (_vp, [_vp]),
+    "ks_segments_device_seg_offsets": (_vp, [_vp]),
+    "ks_segments_device_residues": (_vp, [_vp]),
+    "ks_segments_device_group_offsets": (_vp, [_vp]),
+    "ks_segments_copy_to_host": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ks_segments_free": (None, [_vp]),
+    "ks_sketch_masked_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, _parp, C.POINTER(ks_mask_opts), _pp]),
+    "ks_sketch_masked": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _parp, C.POINTER(ks_mask_opts), _pp]),
+    "ks_kmer_positions_masked_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _parp, C.POINTER(ks_mask_opts), _pp]),
+    "ks_debug_mask_chunk": (C.c_uint32, []),
     "ks_kmer_positions": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _parp, _pp]),
     "ks_kmer_positions_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _parp, _pp]),
     "ks_kmerpos_count": (C.c_uint64, [_vp]),

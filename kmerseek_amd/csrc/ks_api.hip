@@ -93,6 +93,33 @@ extern "C" int ks_sketch_translated(ks_ctx *ctx, const uint8_t *nt, const uint64
     });
 }
 
+extern "C" int ks_mask_batch(ks_ctx *ctx, const uint8_t *residues, const uint64_t *seq_offsets, uint32_t n_seqs, const ks_mask_opts *opts,
+                             ks_mask **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "mask: out is NULL");
+    *out = nullptr;
+    KS_TRY(ks_mask_opts_check(ctx, "mask", opts));
+    ks_upload U(ctx);
+    KS_TRY(U.upload(residues, seq_offsets, n_seqs));
+    return ks_mask_device_impl(ctx, U.d_res, U.d_offs, n_seqs, U.n_res, opts, out);
+    });
+}
+
+extern "C" int ks_sketch_masked(ks_ctx *ctx, const uint8_t *residues, const uint64_t *seq_offsets, uint32_t n_seqs, const ks_params *params,
+                                const ks_mask_opts *opts, ks_sketches **out) {
+    return ks_guard(ctx, [&]() -> int {
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (!out) return ks_fail(ctx, KS_ERR_INVALID_ARG, "sketch_masked: out is NULL");
+    *out = nullptr;
+    KS_TRY(ks_check_params(ctx, params));
+    KS_TRY(ks_mask_opts_check(ctx, "sketch_masked", opts));
+    ks_upload U(ctx);
+    KS_TRY(U.upload(residues, seq_offsets, n_seqs));
+    return ks_sketch_masked_impl(ctx, U.d_res, U.d_offs, n_seqs, U.n_res, U.max_len, params, opts, out);
+    });
+}
+
 // ---- slots -> plain CSR --------------------------------------------------------------------------------------------------
 // A sketch call leaves every sequence a slot as long as its KEPT hashes (ks_common.h: ks_sketches); where a sequence repeats a
 // k-mer its distinct hashes fill only the head of the slot.  One gather (one wave per sequence) closes the gaps: new offsets =

@@ -412,13 +412,14 @@ enum : u32 {
     KS_PIN_RSTITCH = 253,    // 11 words, region stitch: the eight first-offender words (ks_rstitch.hip: RS_BAD_*), then the scan totals: direction rows | columns | ops
     KS_PIN_RCOMP = 264,      // 2 words, residue composition: first sequence whose offsets descend or pass the batch | first sequence of 2^32 residues or more (ks_astats.hip)
     KS_PIN_ASTATS = 266,     // 4 words, alignment statistics: first row that breaks the CSR | with an id beyond its composition | with a sequence too long | fallback rows (ks_astats.hip)
-    KS_PIN_END = 270,
+    KS_PIN_MASK = 270,       // 7 words, low-complexity mask and split: first record with bad offsets | masked residues | hot-window runs | raw segments | kept segments, then the segments' residue count (ks_mask.hip)
+    KS_PIN_END = 277,
 };
-#define KS_PIN_WORDS 272
+#define KS_PIN_WORDS 280
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -755,6 +756,32 @@ int ks_clusters_finish(ks_ctx *ctx, const char *what, ks_clusters *K, const ks_c
 int ks_cluster_words_check(ks_ctx *ctx, const char *what, u32 similarity, u32 n_nodes, double threshold, const ks_sketches *nodes,
                            const double *d_score);
 
+// ---- low-complexity masking (ks_mask.hip) ----
+// one byte per residue (1: masked) and the masked residues of every record
+struct ks_mask {
+    ks_ctx *ctx;
+    u32 n_seqs;
+    u64 n_res, n_masked;
+    u32 window, k1, k2; // the options the mask was made with, defaults filled in
+    u8 *d_mask;         // n_res (the block is padded to whole words)
+    u32 *d_counts;      // n_seqs
+    template <class S, class F> static constexpr void each(S &s, F &&f) { f(s.d_mask, s.n_res); f(s.d_counts, (u64)s.n_seqs); }
+};
+// the unmasked stretches of a batch of at least min_len residues, in record order, as a residue batch of their own
+struct ks_segments {
+    ks_ctx *ctx;
+    u32 n_records, min_len;
+    u64 n_segs, n_res;
+    u32 *d_seg_record, *d_seg_start; // n_segs: the record of a segment, its first residue counted from the record's
+    u64 *d_seg_offsets;              // n_segs + 1: the batch layout of d_residues
+    u8 *d_residues;                  // n_res (+ 16: the sketch tiles load whole 16-byte words)
+    u32 *d_group_offsets;            // n_records + 1: record r owns the segments [d_group_offsets[r], d_group_offsets[r + 1])
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_seg_record, s.n_segs); f(s.d_seg_start, s.n_segs); f(s.d_seg_offsets, s.n_segs + 1); f(s.d_residues, s.n_res);
+        f(s.d_group_offsets, (u64)s.n_records + 1);
+    }
+};
+
 // ---- passes whose sort key is `hit row | fields of the pair` (ks_matchpos.hip, ks_regions.hip) ----
 // Row index and fields that do not fit 64 bits together: the hit rows are cut into slices, each sorted with a key of its own
 // whose row field counts from the slice's first row.  A record of another slice carries the row value one past the slice:
@@ -958,6 +985,16 @@ int ks_union_groups_impl(ks_ctx *ctx, const ks_sketches *in, const u32 *group_of
 // the checks of ks_sketch_translated* that need no device, then translate -> sketch the 6 * n_seqs frames -> union by record
 int ks_sketch_translated_impl(ks_ctx *ctx, const u8 *d_nt, const u64 *d_offs, u32 n_seqs, u64 n_nt, u32 max_seq_len, const ks_params *p,
                               ks_sketches **out);
+
+// ---- low-complexity masking (ks_mask.hip): mask -> split at min_len = ksize -> sketch the segments -> union by record ----
+// behind the entry points' NULL checks; opts: NULL for the defaults
+int ks_sketch_masked_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res, u32 max_seq_len, const ks_params *p,
+                          const ks_mask_opts *opts, ks_sketches **out);
+int ks_kmerpos_masked_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res, const ks_params *p,
+                           const ks_mask_opts *opts, ks_kmerpos **out);
+int ks_mask_device_impl(ks_ctx *ctx, const u8 *d_res, const u64 *d_offs, u32 n_seqs, u64 n_res, const ks_mask_opts *opts, ks_mask **out);
+// what the options are refused for ("<what> options: ..."), for the entry points that upload before they call the above
+int ks_mask_opts_check(ks_ctx *ctx, const char *what, const ks_mask_opts *opts);
 
 int ks_check_params(ks_ctx *ctx, const ks_params *p);
 // two objects were made with the same parameters: all five fields

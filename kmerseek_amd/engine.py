@@ -120,6 +120,16 @@ def search_opts(min_containment: float = 0.0, abund_stats: bool = False) -> Opti
     return _lib.ks_search_opts(_lib.KS_SEARCH_ABUND_STATS if abund_stats else 0, 0, float(min_containment))
 
 
+def mask_opts(window: int = 12, k1: float = 2.2, k2: float = 2.5) -> _lib.ks_mask_opts:
+    """The ks_mask_opts of a window length and two thresholds in BITS (millibits by round(1000 k)).  The window is always
+    named — a window below 2 is refused here, 0 included, which in the C struct would stand for the default — so k1 = k2 = 0
+    reaches the library as given: it masks exactly the windows of one residue class."""
+    if _int_in("window", window, _lib.KS_MASK_MAX_WINDOW, f"[2, {_lib.KS_MASK_MAX_WINDOW}]") < 2:
+        raise ValueError(f"window = {window} is not an integer in [2, {_lib.KS_MASK_MAX_WINDOW}]")
+    return _lib.ks_mask_opts(int(window), _int_in("k1 in millibits", round(1000 * k1), 2 ** 32 - 1),
+                             _int_in("k2 in millibits", round(1000 * k2), 2 ** 32 - 1))
+
+
 BEST_RANK_BY = {"intersect": _lib.KS_BEST_INTERSECT, "target_containment": _lib.KS_BEST_TARGET_CONTAINMENT,
                 "max_containment": _lib.KS_BEST_MAX_CONTAINMENT, "jaccard": _lib.KS_BEST_JACCARD, "score": _lib.KS_BEST_SCORE}
 GREEDY_ASSIGN = {"first": _lib.KS_GREEDY_ASSIGN_FIRST, "best": _lib.KS_GREEDY_ASSIGN_BEST}
@@ -428,6 +438,79 @@ class Context:
         self._check(self._L.ks_sketch_translated_device(self._h, C.c_void_p(d_nt), C.c_void_p(d_offsets), n_seqs, n_nt, max_seq_len,
                                                         C.byref(p), C.byref(out)))
         return Sketches(self, out)
+
+    # ---- low-complexity masking ----
+    def mask_low_complexity(self, residues: np.ndarray, offsets: np.ndarray, window: int = 12, k1: float = 2.2, k2: float = 2.5) -> "Mask":
+        """ks_mask_batch: the low-complexity mask of a host batch (the layout of `pack`) under this library's own integer rule
+        (include/kmerseek_amd.h; the first stage of SEG, no parity claimed): windows of `window` residues with at most k1 bits of
+        entropy trigger, neighbouring windows with at most k2 bits extend.  `Mask.to_host()` gives (mask u8, masked_counts u32)."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        o = mask_opts(window, k1, k2)
+        out = C.c_void_p()
+        self._check(self._L.ks_mask_batch(self._h, _ptr(residues), _ptr(offsets), len(offsets) - 1, C.byref(o), C.byref(out)))
+        return Mask(self, out)
+
+    def mask_low_complexity_device(self, d_residues: int, d_offsets: int, n_seqs: int, n_residues: int, window: int = 12, k1: float = 2.2,
+                                   k2: float = 2.5) -> "Mask":
+        """The same with the batch resident on the device (raw pointers)."""
+        o = mask_opts(window, k1, k2)
+        out = C.c_void_p()
+        self._check(self._L.ks_mask_device(self._h, C.c_void_p(d_residues), C.c_void_p(d_offsets), n_seqs, n_residues, C.byref(o), C.byref(out)))
+        return Mask(self, out)
+
+    def split_masked(self, mask: "Mask", residues: np.ndarray, offsets: np.ndarray, min_len: int = 1) -> "Segments":
+        """ks_mask_split_device on a host batch: the unmasked stretches of at least min_len residues of every record, in order, as
+        a residue batch of their own (`Segments`)."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        with self._uploaded(residues if residues.size else np.zeros(16, np.uint8), offsets) as (d_res, d_off):
+            return self.split_masked_device(mask, d_res, d_off, len(offsets) - 1, int(residues.size), min_len)
+
+    def split_masked_device(self, mask: "Mask", d_residues: int, d_offsets: int, n_seqs: int, n_residues: int, min_len: int = 1) -> "Segments":
+        out = C.c_void_p()
+        self._check(self._L.ks_mask_split_device(self._h, mask._h, C.c_void_p(d_residues), C.c_void_p(d_offsets), n_seqs, n_residues,
+                                                 _int_in("min_len", min_len, 2 ** 32 - 1), C.byref(out)))
+        return Segments(self, out)
+
+    def sketch_masked(self, residues: np.ndarray, offsets: np.ndarray, ksize: int, scaled: int, moltype: str, window: int = 12,
+                      k1: float = 2.2, k2: float = 2.5, seed: int = SEED) -> "Sketches":
+        """ks_sketch_masked: the sketches of the records with their low-complexity stretches left out — the hashes of exactly
+        those windows that hold no masked residue, abundances counted over those windows.  A plain `Sketches` of len(offsets) - 1
+        records; a record that is masked throughout has an empty sketch."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        p, o = make_params(ksize, scaled, moltype, seed), mask_opts(window, k1, k2)
+        out = C.c_void_p()
+        self._check(self._L.ks_sketch_masked(self._h, _ptr(residues), _ptr(offsets), len(offsets) - 1, C.byref(p), C.byref(o), C.byref(out)))
+        return Sketches(self, out)
+
+    def sketch_masked_device(self, d_residues: int, d_offsets: int, n_seqs: int, n_residues: int, ksize: int, scaled: int, moltype: str,
+                             max_seq_len: int = 0, window: int = 12, k1: float = 2.2, k2: float = 2.5, seed: int = SEED) -> "Sketches":
+        """The same with the batch resident on the device (raw pointers); max_seq_len as in sketch_batch_device."""
+        p, o = make_params(ksize, scaled, moltype, seed), mask_opts(window, k1, k2)
+        out = C.c_void_p()
+        self._check(self._L.ks_sketch_masked_device(self._h, C.c_void_p(d_residues), C.c_void_p(d_offsets), n_seqs, n_residues, max_seq_len,
+                                                    C.byref(p), C.byref(o), C.byref(out)))
+        return Sketches(self, out)
+
+    def kmer_positions_table_masked(self, residues: np.ndarray, offsets: np.ndarray, ksize: int, scaled: int, moltype: str, window: int = 12,
+                                    k1: float = 2.2, k2: float = 2.5, seed: int = SEED) -> "KmerPositions":
+        """ks_kmer_positions_masked_device on a host batch: the k-mer position table of the windows a masked sketch is made of,
+        in the records' own numbering and coordinates (the input of `match_positions` beside masked sketches)."""
+        residues = np.ascontiguousarray(residues, dtype=np.uint8)
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        with self._uploaded(residues if residues.size else np.zeros(16, np.uint8), offsets) as (d_res, d_off):
+            return self.kmer_positions_table_masked_device(d_res, d_off, len(offsets) - 1, int(residues.size), ksize, scaled, moltype,
+                                                           window, k1, k2, seed)
+
+    def kmer_positions_table_masked_device(self, d_residues: int, d_offsets: int, n_seqs: int, n_residues: int, ksize: int, scaled: int,
+                                           moltype: str, window: int = 12, k1: float = 2.2, k2: float = 2.5, seed: int = SEED) -> "KmerPositions":
+        p, o = make_params(ksize, scaled, moltype, seed), mask_opts(window, k1, k2)
+        out = C.c_void_p()
+        self._check(self._L.ks_kmer_positions_masked_device(self._h, C.c_void_p(d_residues), C.c_void_p(d_offsets), n_seqs, n_residues,
+                                                            C.byref(p), C.byref(o), C.byref(out)))
+        return KmerPositions(self, out)
 
     def qfilter_stats(self) -> Dict[str, int]:
         """Query postings the filtered bucket scatters of this context read / dropped (see ks_ctx_qfilter_stats)."""
@@ -1171,6 +1254,21 @@ class _Columns(_Owned):
 
     def to_host(self) -> Tuple[np.ndarray, ...]:
         return self._copy_out(self._COLUMNS)
+
+
+class Mask(_Columns):
+    """Device-resident low-complexity mask of a residue batch (ks_mask): one byte per residue, 1 = masked, and per record its
+    masked residues."""
+    _PREFIX, _COUNTS = "mask", {"n_seqs": "", "n_residues": "", "n_masked": "masked residues of the whole batch"}
+    _TABLE = (("mask", "u1", "n_residues"), ("masked_counts", "u4", "n_seqs"))
+
+
+class Segments(_Columns):
+    """Device-resident unmasked segments of a batch (ks_segments): per segment its record and its start in the record, the
+    segments' residues as one batch (seg_offsets, residues) and per record the range of its segments (group_offsets)."""
+    _PREFIX, _COUNTS = "segments", {"n_segs": "", "n_residues": "", "n_records": ""}
+    _TABLE = (("seg_record", "u4", "n_segs"), ("seg_start", "u4", "n_segs"), ("seg_offsets", "u8", "n_segs + 1"),
+              ("residues", "u1", "n_residues"), ("group_offsets", "u4", "n_records + 1"))
 
 
 class MatchPositions(_Columns):

@@ -144,20 +144,31 @@ def _make_sigfile(fasta: str, moltype: str, ksize: int, scaled: int) -> str:
     return f"{fasta}.{moltype}.k{ksize}.scaled{scaled}.sig.zip"
 
 
-def sketch(fasta: str, moltype: str, ksize: int, scaled: int, ctx: Optional[Context] = None, translate: bool = False) -> str:
+def sketch(fasta: str, moltype: str, ksize: int, scaled: int, ctx: Optional[Context] = None, translate: bool = False,
+           mask: bool = False, mask_opts: Optional[dict] = None) -> str:
     """sketch() of src/python/kmerseek/sketch.py:28-40.  The records go through the native pipelined ingest
     (csrc/ks_ingest.cpp: parse, pinned staging, H2D and the sketch kernels overlap); `ctx` only picks the device.
     translate=True: the records are NUCLEOTIDES; each is translated in six frames on the device and sketched as the union of
-    its frames (Context.sketch_translated).  The .sig.zip is written by the same code: same molecule, same names."""
+    its frames (Context.sketch_translated).  The .sig.zip is written by the same code: same molecule, same names.
+    mask=True: the low-complexity stretches of every record are left out of its sketch (Context.sketch_masked; mask_opts: its
+    window / k1 / k2 keywords, None for the defaults).  Same file, same names; a record masked throughout has an empty sketch.
+    Not together with translate=True: translated frames are not masked."""
     from . import host
+    if mask and translate:
+        raise ValueError("mask=True and translate=True: masking of translated frames is not built")
+    if mask_opts is not None and not mask:
+        raise ValueError("mask_opts needs mask=True")
     sigfile = _make_sigfile(fasta, moltype, ksize, scaled)
     _make_manysketch_csv(fasta)
-    if translate:
+    if translate or mask:
         recs = read_fasta(fasta)
         own = ctx is None
         c = Context(0) if own else ctx
         try:
-            sk = c.sketch_translated(*pack([r for _, r in recs]), ksize, scaled, moltype)
+            if mask:
+                sk = c.sketch_masked(*pack([r for _, r in recs]), ksize, scaled, moltype, **(mask_opts or {}))
+            else:
+                sk = c.sketch_translated(*pack([r for _, r in recs]), ksize, scaled, moltype)
             o, m, a = sk.to_host()
             sk.free()
         finally:
@@ -899,7 +910,7 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 chain_max_gap: int = 0, chain_max_overlap: int = 0, chain_link_cost: int = 0,
                                 chain_skew_cost: int = 0, chain_overlap_cost: int = 0, hit_rows: bool = False,
                                 stitch: bool = False, stitch_max_fill: int = 0, evalue: bool = False, stat_params=None,
-                                max_evalue=None) -> List[dict]:
+                                max_evalue=None, mask: bool = False, mask_opts: Optional[dict] = None) -> List[dict]:
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -925,7 +936,13 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     bit scores and E-values (Context.alignment_stats with matrix; the database is the target file) and the rows carry the
     columns `region_rows` / `hit_chain_rows` add for stats=.  stat_params = (lambda, K): the gapped parameters that belong to
     the matrix and the gap costs — gapped scores need them; None for scored regions: the ungapped ones the library derives.
-    max_evalue: rows whose E-value is above it are dropped, on the host."""
+    max_evalue: rows whose E-value is above it are dropped, on the host.
+    mask=True: both files are sketched with their low-complexity stretches left out (Context.sketch_masked; mask_opts: its
+    window / k1 / k2 keywords) and the position tables are made of the same windows (Context.kmer_positions_table_masked):
+    hits, pairs and regions are those of the unmasked windows.  The passes that read residues (scores, alignments) read the
+    records as they are."""
+    if mask_opts is not None and not mask:
+        raise ValueError("mask_opts needs mask=True")
     if (stat_params is not None or max_evalue is not None) and not evalue:
         raise ValueError("stat_params and max_evalue need evalue=True")
     if evalue:
@@ -959,11 +976,20 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
         q_recs, t_recs = read_fasta(query_fasta), read_fasta(target_fasta)
         q_res, q_off = pack([s for _, s in q_recs])
         t_res, t_off = pack([s for _, s in t_recs])
-        Q = ctx.sketch_batch(q_res, q_off, ksize, scaled, moltype)
-        T = ctx.sketch_batch(t_res, t_off, ksize, scaled, moltype)
+        if mask:
+            mo = mask_opts or {}
+            Q = ctx.sketch_masked(q_res, q_off, ksize, scaled, moltype, **mo)
+            T = ctx.sketch_masked(t_res, t_off, ksize, scaled, moltype, **mo)
+        else:
+            Q = ctx.sketch_batch(q_res, q_off, ksize, scaled, moltype)
+            T = ctx.sketch_batch(t_res, t_off, ksize, scaled, moltype)
         hits = ctx.search(ctx.index_build(T), Q)
-        qp = ctx.kmer_positions_table(q_res, q_off, ksize, scaled, moltype)
-        tp = ctx.kmer_positions_table(t_res, t_off, ksize, scaled, moltype)
+        if mask:
+            qp = ctx.kmer_positions_table_masked(q_res, q_off, ksize, scaled, moltype, **mo)
+            tp = ctx.kmer_positions_table_masked(t_res, t_off, ksize, scaled, moltype, **mo)
+        else:
+            qp = ctx.kmer_positions_table(q_res, q_off, ksize, scaled, moltype)
+            tp = ctx.kmer_positions_table(t_res, t_off, ksize, scaled, moltype)
         mp = ctx.match_positions(qp, tp, hits)
         qid, tid, _, _ = hits.to_host()
         if regions:
