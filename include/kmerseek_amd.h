@@ -975,6 +975,87 @@ int ks_rchain_coverage_to_host(ks_ctx *ctx, const ks_rchain *c, double *row_cove
  * may be NULL): the tests place rows around them */
 uint32_t ks_debug_rchain_lds_rows(uint32_t *small_rows);
 
+/* ---- frame fold: the hits of a translated search per (record, strand, target), regions in bases -------------------------- */
+
+/* A search whose queries are the 6 n frames of ks_translate6_device (record s: 6 s + f forward, 6 s + 3 + f on the reverse
+ * complement, f = 0, 1, 2) answers per frame, in residues of that frame.  The fold puts the rows of one strand's three frames
+ * against one target into ONE row and their regions onto one coordinate, the strand's bases, so that ks_regions_chain_device
+ * links across frames: two alignments in different frames on either side of a frameshift become one chain (blastx, DIAMOND -F).
+ * Input: frame_hits, ordered by (qid, tid) as every search returns them; d_nt_offsets u64[n_records + 1], the record offsets
+ * in bases (L_s: the length of record s); a CSR of regions over the hit rows as ks_regions_chain_device takes it (row_offsets
+ * u64[n_rows + 1]; q_start, q_length, t_start, t_length u32[n]; d_t_length == NULL: the target lengths are the query lengths)
+ * and the pass-through columns d_score i64[n], d_identities, d_aln_length u32[n], each of which may be NULL.  opts: flags and
+ * reserved, all zero (NULL: the defaults).
+ * Folded rows: one per distinct (2 s + strand, tid) that has at least one frame row (strand = 0 for frames 0 - 2, 1 for 3 - 5),
+ * ordered by (2 s + strand, tid).  TWO objects come back, both NULL after any failure:
+ *   *out_hits   a ks_hits with qid = 2 s + strand, tid, intersect = the sum of the member rows' (saturating at 2^32 - 1),
+ *               n_weighted = their u64 sum; no statistics columns; n_pair_instances, partition_path and bucket_posting_bytes
+ *               are the input's.  A hit list like any other: ks_hits_best with KS_BEST_SCORE and a chain's row_chain_score.
+ *   *out        a ks_ffold:
+ *   src_row u32[3 n_folded]      entry 3 r + j: the input row of frame 3 strand + j of folded row r, or KS_FFOLD_NONE
+ *   row_offsets u64[n_folded + 1]   the CSR of the folded regions: a folded row's regions are those of its frame-0 row, then
+ *                                of its frame-1 row, then frame 2, each in input order
+ *   per folded region:
+ *   src_region u32               the input region
+ *   frame u8                     0 .. 5
+ *   nt_length u32                3 q_length
+ *   s_start u32                  f + 3 q_start: the start in the strand's own orientation (on the record for strand 0, on its
+ *                                reverse complement for strand 1); the coordinate to chain on
+ *   nt_start u32                 the start on the record as given: s_start forward, L_s - f - 3 (q_start + q_length) reverse
+ *   t_start3, t_length3 u32      3 t_start, 3 t_length: the target in the same unit, so that the chain's |dq - dt| is in bases
+ *   score i64, identities, aln_length u32   the input columns through src_region; NULL where the input column was NULL
+ * An empty hit list, records without rows and rows without regions give valid (empty or shorter) results; n_regions of the
+ * result is n of the input.  The result does not depend on the launch geometry.
+ * KS_ERR_INVALID_ARG: unknown flags or a non-zero reserved field (checked first, also with ctx == NULL); NULL arguments; an
+ * object of another context; and, ks_last_error naming the first offending record, row or region: d_nt_offsets that do not
+ * start at 0 and ascend; a record beyond 2^32 - 16 bases; a qid >= 6 n_records; rows not strictly ascending by (qid, tid);
+ * row_offsets that is not a non-decreasing CSR from 0 to n; a region whose q_start + q_length exceeds its frame's length
+ * max(0, (L_s - f) / 3); a region whose 3 (t_start + t_length) exceeds 2^32 - 1.
+ * KS_ERR_CAPACITY: 2^32 - 2 or more rows, more than 2^32 - 1 regions.
+ * One stream, synchronous on return, one host wait (the folded row count and the bad words come back with it); all memory
+ * comes from the context's pool: 32 bytes of scratch per hit row.  The folded count is known only after the wait: the folded
+ * hit list, src_row and row_offsets are allocated for as many rows as the INPUT has (src_row for three times as many) and keep
+ * those blocks until the objects are freed, though n_folded rows are used — up to three times what they need where all three
+ * frames of every strand hit. */
+typedef struct ks_ffold ks_ffold;
+#define KS_FFOLD_NONE 0xffffffffu
+typedef struct ks_ffold_opts {
+    uint32_t flags;       /* 0 */
+    uint32_t reserved[3]; /* 0 */
+} ks_ffold_opts;
+int ks_frames_fold_device(ks_ctx *ctx, const ks_hits *frame_hits, const uint64_t *d_nt_offsets, uint32_t n_records,
+                          const uint64_t *d_row_offsets, const uint32_t *d_q_start, const uint32_t *d_q_length,
+                          const uint32_t *d_t_start, const uint32_t *d_t_length, const int64_t *d_score,
+                          const uint32_t *d_identities, const uint32_t *d_aln_length, uint64_t n_regions,
+                          const ks_ffold_opts *opts, ks_hits **out_hits, ks_ffold **out);
+/* the same on the columns of an object made for the rows of frame_hits: the extended regions' placement, `length` for both
+ * sides and as aln_length, score and identities; the alignments' extents, score, identities and aln_length */
+int ks_rscores_fold_frames(ks_ctx *ctx, const ks_hits *frame_hits, const uint64_t *d_nt_offsets, uint32_t n_records,
+                           const ks_rscores *scores, const ks_ffold_opts *opts, ks_hits **out_hits, ks_ffold **out);
+int ks_raligns_fold_frames(ks_ctx *ctx, const ks_hits *frame_hits, const uint64_t *d_nt_offsets, uint32_t n_records,
+                           const ks_raligns *alignments, const ks_ffold_opts *opts, ks_hits **out_hits, ks_ffold **out);
+uint64_t ks_ffold_n_rows(const ks_ffold *f);     /* folded rows */
+uint64_t ks_ffold_n_regions(const ks_ffold *f);
+uint64_t ks_ffold_n_src_rows(const ks_ffold *f); /* hit rows of the input */
+/* device pointers, valid until ks_ffold_free */
+const uint32_t *ks_ffold_device_src_row(const ks_ffold *f);
+const uint64_t *ks_ffold_device_row_offsets(const ks_ffold *f);
+const uint32_t *ks_ffold_device_src_region(const ks_ffold *f);
+const uint8_t *ks_ffold_device_frame(const ks_ffold *f);
+const uint32_t *ks_ffold_device_nt_length(const ks_ffold *f);
+const uint32_t *ks_ffold_device_s_start(const ks_ffold *f);
+const uint32_t *ks_ffold_device_nt_start(const ks_ffold *f);
+const uint32_t *ks_ffold_device_t_start3(const ks_ffold *f);
+const uint32_t *ks_ffold_device_t_length3(const ks_ffold *f);
+const int64_t *ks_ffold_device_score(const ks_ffold *f);          /* NULL: the fold was made without that column, as the two below */
+const uint32_t *ks_ffold_device_identities(const ks_ffold *f);
+const uint32_t *ks_ffold_device_aln_length(const ks_ffold *f);
+/* any destination may be NULL; the destination of a column the fold does not have is left as it is */
+int ks_ffold_copy_to_host(ks_ctx *ctx, const ks_ffold *f, uint32_t *src_row, uint64_t *row_offsets, uint32_t *src_region,
+                          uint8_t *frame, uint32_t *nt_length, uint32_t *s_start, uint32_t *nt_start, uint32_t *t_start3,
+                          uint32_t *t_length3, int64_t *score, uint32_t *identities, uint32_t *aln_length);
+void ks_ffold_free(ks_ffold *f);
+
 /* ---- region stitch: the chain of a hit as ONE gapped alignment with one CIGAR ---------------------------------------------- */
 
 /* What a seed-and-extend search closes its alignment stage with (minimap2 fills between chained anchors, BLAST links HSPs,

@@ -94,6 +94,13 @@ class ks_rchain_opts(C.Structure):
                 ("overlap_cost", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 2)]
 
 
+KS_FFOLD_NONE = 0xFFFFFFFF
+
+
+class ks_ffold_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 KS_RSTITCH_EQX = 1
 KS_RSTITCH_MAX_FILL = 4096
 
@@ -380,6 +387,26 @@ SIGNATURES = {
     "ks_rchain_coverage": (C.c_int, [_vp, _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32]),
     "ks_rchain_coverage_to_host": (C.c_int, [_vp, _vp, _vp]),
     "ks_debug_rchain_lds_rows": (C.c_uint32, [_u32p]),
+    "ks_frames_fold_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32] + [_vp] * 8 + [C.c_uint64, C.POINTER(ks_ffold_opts), _pp, _pp]),
+    "ks_rscores_fold_frames": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.POINTER(ks_ffold_opts), _pp, _pp]),
+    "ks_raligns_fold_frames": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _vp, C.POINTER(ks_ffold_opts), _pp, _pp]),
+    "ks_ffold_n_rows": (C.c_uint64, [_vp]),
+    "ks_ffold_n_regions": (C.c_uint64, [_vp]),
+    "ks_ffold_n_src_rows": (C.c_uint64, [_vp]),
+    "ks_ffold_device_src_row": (_vp, [_vp]),
+    "ks_ffold_device_row_offsets": (_vp, [_vp]),
+    "ks_ffold_device_src_region": (_vp, [_vp]),
+    "ks_ffold_device_frame": (_vp, [_vp]),
+    "ks_ffold_device_nt_length": (_vp, [_vp]),
+    "ks_ffold_device_s_start": (_vp, [_vp]),
+    "ks_ffold_device_nt_start": (_vp, [_vp]),
+    "ks_ffold_device_t_start3": (_vp, [_vp]),
+    "ks_ffold_device_t_length3": (_vp, [_vp]),
+    "ks_ffold_device_score": (_vp, [_vp]),
+    "ks_ffold_device_identities": (_vp, [_vp]),
+    "ks_ffold_device_aln_length": (_vp, [_vp]),
+    "ks_ffold_copy_to_host": (C.c_int, [_vp] * 14),
+    "ks_ffold_free": (None, [_vp]),
     "ks_regions_stitch": (C.c_int, [_vp] * 5 + [_vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(ks_rstitch_opts), _pp]),
     "ks_hitalns_n_rows": (C.c_uint64, [_vp]),
     "ks_hitalns_n_ops": (C.c_uint64, [_vp]),

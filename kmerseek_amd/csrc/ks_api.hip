@@ -956,6 +956,84 @@ extern "C" int ks_rchain_coverage_to_host(ks_ctx *ctx, const ks_rchain *c, doubl
 }
 
 // ---------------------------------------------------------------------------------------------
+// frame fold (ks_ffold.hip): the frame rows of a translated search as one row per (record, strand, target)
+// ---------------------------------------------------------------------------------------------
+// what both forms do first: the options (refused before anything else, also with ctx == NULL), the context, the outputs cleared
+static int ks_ffold_begin(ks_ctx *ctx, const ks_ffold_opts *opts, ks_hits **out_hits, ks_ffold **out) {
+    if (opts) KS_TRY(ks_opts_words_check(ctx, "frame fold", opts->flags, 0u, opts->reserved[0] | opts->reserved[1] | opts->reserved[2]));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out_hits) *out_hits = nullptr;
+    if (out) *out = nullptr;
+    return KS_OK;
+}
+static int ks_ffold_run(ks_ctx *ctx, const ks_hits *hits, const u64 *d_nt_offsets, u32 n_records, const ks_rchain_cols &cols, u64 n_regions,
+                        ks_hits **out_hits, ks_ffold **out) {
+    if (!hits || !out_hits || !out || !d_nt_offsets || !cols.row_offs || (n_regions && (!cols.qs || !cols.ql || !cols.ts || !cols.tl)))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "frame fold", hits));
+    if (hits->n_hits == 0 && n_regions != 0)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "frame fold: %llu regions in no hit row: row_offsets is not a CSR from 0 to n", (unsigned long long)n_regions);
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_hits> F(ctx, out_hits, ks_hits_free);
+    ks_result<ks_ffold> D(ctx, out, ks_ffold_free);
+    KS_TRY(ks_frames_fold_impl(ctx, hits, d_nt_offsets, n_records, cols, n_regions, F, D));
+    F.commit();
+    return D.commit();
+}
+extern "C" int ks_frames_fold_device(ks_ctx *ctx, const ks_hits *frame_hits, const uint64_t *d_nt_offsets, uint32_t n_records,
+                                     const uint64_t *d_row_offsets, const uint32_t *d_q_start, const uint32_t *d_q_length, const uint32_t *d_t_start,
+                                     const uint32_t *d_t_length, const int64_t *d_score, const uint32_t *d_identities, const uint32_t *d_aln_length,
+                                     uint64_t n_regions, const ks_ffold_opts *opts, ks_hits **out_hits, ks_ffold **out) {
+    return ks_guard(ctx, [&]() -> int {
+    KS_TRY(ks_ffold_begin(ctx, opts, out_hits, out));
+    return ks_ffold_run(ctx, frame_hits, d_nt_offsets, n_records,
+                        {{d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length ? d_t_length : d_q_length, d_score}, d_identities, d_aln_length},
+                        n_regions, out_hits, out);
+    });
+}
+// the fold of an object's own columns (ks_rscores, ks_raligns): the views the chain reads
+template <typename T> static int ks_ffold_of(ks_ctx *ctx, const ks_hits *hits, const u64 *d_nt_offsets, u32 n_records, const T *s, const ks_ffold_opts *opts,
+                                             ks_hits **out_hits, ks_ffold **out) {
+    KS_TRY(ks_ffold_begin(ctx, opts, out_hits, out));
+    if (!s || !hits) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "frame fold", s));
+    if (s->n_rows != hits->n_hits)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "frame fold: the regions cover %llu hit rows, the hit list holds %llu: regions of another list",
+                       (unsigned long long)s->n_rows, (unsigned long long)hits->n_hits);
+    return ks_ffold_run(ctx, hits, d_nt_offsets, n_records, s->cols(), s->n_regions, out_hits, out);
+}
+extern "C" int ks_rscores_fold_frames(ks_ctx *ctx, const ks_hits *frame_hits, const uint64_t *d_nt_offsets, uint32_t n_records, const ks_rscores *scores,
+                                      const ks_ffold_opts *opts, ks_hits **out_hits, ks_ffold **out) {
+    return ks_guard(ctx, [&]() -> int { return ks_ffold_of(ctx, frame_hits, d_nt_offsets, n_records, scores, opts, out_hits, out); });
+}
+extern "C" int ks_raligns_fold_frames(ks_ctx *ctx, const ks_hits *frame_hits, const uint64_t *d_nt_offsets, uint32_t n_records, const ks_raligns *alignments,
+                                      const ks_ffold_opts *opts, ks_hits **out_hits, ks_ffold **out) {
+    return ks_guard(ctx, [&]() -> int { return ks_ffold_of(ctx, frame_hits, d_nt_offsets, n_records, alignments, opts, out_hits, out); });
+}
+extern "C" uint64_t ks_ffold_n_rows(const ks_ffold *f) { return f ? f->n_rows : 0; }
+extern "C" uint64_t ks_ffold_n_regions(const ks_ffold *f) { return f ? f->n_regions : 0; }
+extern "C" uint64_t ks_ffold_n_src_rows(const ks_ffold *f) { return f ? f->n_src_rows : 0; }
+extern "C" const uint32_t *ks_ffold_device_src_row(const ks_ffold *f) { return f ? f->d_src_row : nullptr; }
+extern "C" const uint64_t *ks_ffold_device_row_offsets(const ks_ffold *f) { return f ? f->d_row_offsets : nullptr; }
+extern "C" const uint32_t *ks_ffold_device_src_region(const ks_ffold *f) { return f ? f->d_src_region : nullptr; }
+extern "C" const uint8_t *ks_ffold_device_frame(const ks_ffold *f) { return f ? f->d_frame : nullptr; }
+extern "C" const uint32_t *ks_ffold_device_nt_length(const ks_ffold *f) { return f ? f->d_nt_length : nullptr; }
+extern "C" const uint32_t *ks_ffold_device_s_start(const ks_ffold *f) { return f ? f->d_s_start : nullptr; }
+extern "C" const uint32_t *ks_ffold_device_nt_start(const ks_ffold *f) { return f ? f->d_nt_start : nullptr; }
+extern "C" const uint32_t *ks_ffold_device_t_start3(const ks_ffold *f) { return f ? f->d_t_start3 : nullptr; }
+extern "C" const uint32_t *ks_ffold_device_t_length3(const ks_ffold *f) { return f ? f->d_t_length3 : nullptr; }
+extern "C" const int64_t *ks_ffold_device_score(const ks_ffold *f) { return f ? f->d_score : nullptr; }
+extern "C" const uint32_t *ks_ffold_device_identities(const ks_ffold *f) { return f ? f->d_identities : nullptr; }
+extern "C" const uint32_t *ks_ffold_device_aln_length(const ks_ffold *f) { return f ? f->d_aln_length : nullptr; }
+extern "C" int ks_ffold_copy_to_host(ks_ctx *ctx, const ks_ffold *f, uint32_t *src_row, uint64_t *row_offsets, uint32_t *src_region, uint8_t *frame,
+                                     uint32_t *nt_length, uint32_t *s_start, uint32_t *nt_start, uint32_t *t_start3, uint32_t *t_length3, int64_t *score,
+                                     uint32_t *identities, uint32_t *aln_length) {
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, f, src_row, row_offsets, src_region, frame, nt_length, s_start, nt_start, t_start3,
+                                                              t_length3, score, identities, aln_length); });
+}
+extern "C" void ks_ffold_free(ks_ffold *f) { ks_obj_free(f); }
+
+// ---------------------------------------------------------------------------------------------
 // region stitch (ks_rstitch.hip): the chain of each hit row as one gapped alignment with one CIGAR
 // ---------------------------------------------------------------------------------------------
 extern "C" int ks_regions_stitch(ks_ctx *ctx, const ks_rchain *chain, const ks_raligns *alignments, const ks_cigars *cigars, const ks_hits *hits,

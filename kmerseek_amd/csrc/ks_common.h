@@ -413,13 +413,14 @@ enum : u32 {
     KS_PIN_RCOMP = 264,      // 2 words, residue composition: first sequence whose offsets descend or pass the batch | first sequence of 2^32 residues or more (ks_astats.hip)
     KS_PIN_ASTATS = 266,     // 4 words, alignment statistics: first row that breaks the CSR | with an id beyond its composition | with a sequence too long | fallback rows (ks_astats.hip)
     KS_PIN_MASK = 270,       // 7 words, low-complexity mask and split: first record with bad offsets | masked residues | hot-window runs | raw segments | kept segments, then the segments' residue count (ks_mask.hip)
-    KS_PIN_END = 277,
+    KS_PIN_FFOLD = 277,      // 8 words, frame fold: first record with bad offsets | too long | first row with a qid beyond the frames | out of order | that breaks the CSR | first region beyond its frame | beyond the target bound, then the folded rows (ks_ffold.hip)
+    KS_PIN_END = 285,
 };
-#define KS_PIN_WORDS 280
+#define KS_PIN_WORDS 288
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -665,6 +666,29 @@ struct ks_rchain {
 int ks_regions_chain_impl(ks_ctx *ctx, const ks_rchain_cols &cols, u64 n_rows, u64 n_regions, const ks_rchain_opts *opts, ks_rchain *K);
 // ks_rchain_coverage behind its argument checks (H: of ctx, K's row count; mode <= 3)
 int ks_rchain_coverage_impl(ks_ctx *ctx, ks_rchain *K, const ks_hits *H, const u64 *d_q_off, u32 n_q, const u64 *d_t_off, u32 n_t, u32 mode);
+
+// the frame rows of a translated search folded per (record, strand, target), their regions on the strand's bases (ks_ffold.hip)
+struct ks_ffold {
+    ks_ctx *ctx;
+    u64 n_rows, n_regions, n_src_rows;   // folded rows; regions (all of the input's); hit rows of the input
+    u32 *d_src_row;                      // 3 * n_rows (a block of 3 * n_src_rows entries)
+    u64 *d_row_offsets;                  // n_rows + 1 (a block of n_src_rows + 1)
+    u32 *d_src_region;                   // n_regions, as every column below
+    u8 *d_frame;
+    u32 *d_nt_length, *d_s_start, *d_nt_start, *d_t_start3, *d_t_length3;
+    i64 *d_score;                        // NULL where the input column was not passed, as the two below
+    u32 *d_identities, *d_aln_length;
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_src_row, 3 * s.n_rows); f(s.d_row_offsets, s.n_rows + 1); f(s.d_src_region, s.n_regions); f(s.d_frame, s.n_regions);
+        f(s.d_nt_length, s.n_regions); f(s.d_s_start, s.n_regions); f(s.d_nt_start, s.n_regions); f(s.d_t_start3, s.n_regions);
+        f(s.d_t_length3, s.n_regions); f(s.d_score, (u64)(s.d_score ? s.n_regions : 0)); f(s.d_identities, (u64)(s.d_identities ? s.n_regions : 0));
+        f(s.d_aln_length, (u64)(s.d_aln_length ? s.n_regions : 0));
+    }
+};
+// ks_frames_fold_device behind its argument checks (H: of ctx; n_regions == 0 where H has no rows; cols.score may be NULL): F and D
+// are filled
+int ks_frames_fold_impl(ks_ctx *ctx, const ks_hits *H, const u64 *d_nt_offs, u32 n_records, const ks_rchain_cols &cols, u64 n_regions,
+                        ks_hits *F, ks_ffold *D);
 
 // the chain of each hit row stitched into one gapped alignment with one CIGAR (ks_rstitch.hip)
 struct ks_hitalns {

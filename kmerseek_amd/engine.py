@@ -785,6 +785,56 @@ class Context:
         self._check(fn(self._h, scored._h, C.byref(opts), C.byref(out)))
         return RegionChain(self, out)
 
+    # ---- translated search: frame hits per strand, chained in bases ----
+    def fold_frames_device(self, frame_hits: "Hits", d_nt_offsets: int, n_records: int, d_row_offsets: int, d_q_start: int,
+                           d_q_length: int, d_t_start: int, d_t_length: Optional[int], n_regions: int, d_score: Optional[int] = None,
+                           d_identities: Optional[int] = None, d_aln_length: Optional[int] = None) -> "FrameFold":
+        """ks_frames_fold_device from device-resident columns (raw pointers).  frame_hits: the hits of a search whose queries
+        are the 6 x n frames of translate6; d_nt_offsets: the record offsets u64[n_records + 1] in bases; then the CSR of regions
+        over those hit rows as chain_regions_device takes it (d_t_length None or 0: the target lengths are the query lengths)
+        and the optional columns score i64, identities, aln_length u32, which the fold gathers.  The rows of one strand's three
+        frames against one target become one row — FrameFold.hits, a Hits with qid = 2 * record + strand — and their regions
+        move onto the strand's bases (s_start, nt_length; t_start3, t_length3 the target in the same unit): what chain_frames
+        chains.  include/kmerseek_amd.h has the contract."""
+        out, out_hits = C.c_void_p(), C.c_void_p()
+        ptrs = [C.c_void_p(int(p)) if p else None for p in (d_row_offsets, d_q_start, d_q_length, d_t_start, d_t_length, d_score,
+                                                            d_identities, d_aln_length)]
+        self._check(self._L.ks_frames_fold_device(self._h, frame_hits._h, C.c_void_p(int(d_nt_offsets)), int(n_records), *ptrs,
+                                                  int(n_regions), None, C.byref(out_hits), C.byref(out)))
+        return FrameFold(self, out, Hits(self, out_hits))
+
+    def fold_frames(self, frame_hits: "Hits", scored, nt_offsets: np.ndarray) -> "FrameFold":
+        """The fold of fold_frames_device on a RegionScores (ks_rscores_fold_frames: the extended regions, one length for both
+        sides and as aln_length) or a RegionAlignments (ks_raligns_fold_frames) made for the rows of frame_hits — typically what
+        a cull kept, cull.take(...).  nt_offsets: the host offsets u64[n + 1] of the nucleotide records, uploaded for the call."""
+        if isinstance(scored, RegionAlignments):
+            fn = self._L.ks_raligns_fold_frames
+        elif isinstance(scored, RegionScores):
+            fn = self._L.ks_rscores_fold_frames
+        else:
+            raise TypeError("fold_frames takes a RegionAlignments or a RegionScores")
+        nt_offsets = np.ascontiguousarray(nt_offsets, dtype=np.uint64)
+        if nt_offsets.ndim != 1 or nt_offsets.size == 0:
+            raise ValueError("nt_offsets must be a 1-d array of n + 1 offsets")
+        out, out_hits = C.c_void_p(), C.c_void_p()
+        with self._uploaded(nt_offsets) as (d_off,):
+            self._check(fn(self._h, frame_hits._h, C.c_void_p(d_off), len(nt_offsets) - 1, scored._h, None, C.byref(out_hits), C.byref(out)))
+        return FrameFold(self, out, Hits(self, out_hits))
+
+    def chain_frames(self, fold: "FrameFold", max_gap: int = 0, max_overlap: int = 0, link_cost: int = 0, skew_cost: int = 0,
+                     overlap_cost: int = 0) -> "RegionChain":
+        """chain_regions_device on a fold's (row_offsets, s_start, nt_length, t_start3, t_length3, score, identities,
+        aln_length): per folded row the best colinear chain of its regions on the strand's bases, across frames — the options
+        are in bases.  The chain's rows are the folded rows (fold.hits) and its src_region indexes the fold's regions.  A fold
+        made without a score column is refused."""
+        p = dict(zip(fold._COLUMNS, fold.device_ptrs()))
+        if not p["score"]:
+            raise ValueError("chain_frames needs a fold with a score column")
+        return self.chain_regions_device(p["row_offsets"], p["s_start"], p["nt_length"], p["t_start3"], p["t_length3"], p["score"],
+                                         fold.n_rows, fold.n_regions, d_identities=p["identities"] or None,
+                                         d_aln_length=p["aln_length"] or None, max_gap=max_gap, max_overlap=max_overlap,
+                                         link_cost=link_cost, skew_cost=skew_cost, overlap_cost=overlap_cost)
+
     @staticmethod
     def _rstitch_opts(max_fill: int, eqx: bool, max_scratch_bytes: int):
         max_fill = _int_in("max_fill", max_fill, _lib.KS_RSTITCH_MAX_FILL)
@@ -1418,6 +1468,43 @@ class RegionChain(_Columns):
         out = np.zeros(self.n_rows, np.float64)
         self._ctx._check(self._ctx._L.ks_rchain_coverage_to_host(self._ctx._h, self._h, _ptr(out)))
         return out
+
+
+class FrameFold(_Columns):
+    """Device-resident result of Context.fold_frames (ks_ffold): the frame rows of a translated search folded into one row per
+    (record, strand, target) — `hits`, a Hits with qid = 2 * record + strand, is the folded hit list — and their regions on the
+    strand's bases.  Per folded row src_row (the input rows of its three frames, 0xffffffff: none) and row_offsets, the CSR of
+    its regions (frame 0's, then frame 1's, then frame 2's); per region the input region, its frame 0 .. 5, nt_length, s_start
+    (in the strand's own orientation: what chain_frames chains on), nt_start (on the record as given), t_start3 / t_length3
+    (the target in bases) and the gathered score, identities and aln_length.  A fold made without one of the last three has no
+    such column: its device pointer is 0 and to_host() leaves zeros (has_score, has_identities, has_aln_length tell)."""
+    _PREFIX, _COUNTS = "ffold", {"n_rows": "Folded rows.", "n_regions": "", "n_src_rows": "Hit rows of the input."}
+    _TABLE = (("src_row", "u4", "3 * n_rows"), ("row_offsets", "u8", "n_rows + 1"), ("src_region", "u4", "n_regions"), ("frame", "u1", "n_regions")) + \
+        tuple((c, "u4", "n_regions") for c in ("nt_length", "s_start", "nt_start", "t_start3", "t_length3")) + \
+        (("score", "i8", "n_regions"), ("identities", "u4", "n_regions"), ("aln_length", "u4", "n_regions"))
+
+    def __init__(self, ctx: "Context", handle, hits: "Hits"):
+        super().__init__(ctx, handle)
+        self.hits = hits
+
+    @property
+    def has_score(self) -> bool:
+        return bool(self._ctx._L.ks_ffold_device_score(self._h))
+
+    @property
+    def has_identities(self) -> bool:
+        return bool(self._ctx._L.ks_ffold_device_identities(self._h))
+
+    @property
+    def has_aln_length(self) -> bool:
+        return bool(self._ctx._L.ks_ffold_device_aln_length(self._h))
+
+    def free(self):
+        """Releases the fold and its folded hit list."""
+        hits = getattr(self, "hits", None)
+        if hits is not None:
+            hits.free()
+        super().free()
 
 
 class HitAlignments(_Columns):

@@ -1083,3 +1083,105 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     finally:
         if own:
             ctx.close()
+
+
+def frame_chain_rows(nt_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], fold_hits_host, fold_host,
+                     chain_host, keep_rows=None) -> List[dict]:
+    """One row per folded row of a translated search that has a chain: where on the nucleotide record the protein lies, on which
+    strand and in which frames.  fold_hits_host = FrameFold.hits.to_host() (qid = 2 * record + strand), fold_host =
+    FrameFold.to_host(), chain_host = RegionChain.to_host() of Context.chain_frames on that fold.  Columns: query_name, strand
+    (+ / -), match_name, nt_start / nt_end (on the record as given, 0-based half-open: for - they are L - (the chain's q_start +
+    q_length) and L - q_start), t_start / t_end (residues: the chain's values over 3), chain_score, n_alns, frames (the members'
+    frames in chain order in BLAST's numbering, +1 .. +3 and -1 .. -3, comma-joined), n_frameshifts (consecutive members whose
+    frames differ), identities, aln_length, pident (100 * identities / aln_length, NaN where the fold had no such columns) and
+    intersect_hashes (the shared hashes of the member frame rows, summed).  keep_rows: the folded rows to report (None: all).
+    Sorted by (record, strand, -chain_score, target)."""
+    qid, tid, isect = [np.asarray(c).tolist() for c in fold_hits_host[:3]]
+    frame = np.asarray(fold_host[3]).tolist()
+    cols = [np.asarray(c).tolist() for c in chain_host]
+    offs, src, score, qs, ql, ts, tl, ident, alen = [cols[i] for i in (0, 1, 4, 5, 6, 7, 8, 11, 12)]
+    if len(offs) != len(qid) + 1 or len(qid) != len(tid) or len(np.asarray(fold_host[1])) != len(offs):
+        raise ValueError("chain, fold and folded hits are not of the same rows")
+    keep = None if keep_rows is None else set(np.asarray(keep_rows).tolist())
+    out = []
+    for r, (x, t) in enumerate(zip(qid, tid)):
+        n = offs[r + 1] - offs[r]
+        if n == 0 or (keep is not None and r not in keep):
+            continue
+        s, minus = x // 2, x % 2 == 1
+        (qn, qseq), (tn, _) = nt_records[s], t_records[t]
+        L, a, e = len(qseq), qs[r], qs[r] + ql[r]
+        fr = [frame[g] for g in src[offs[r]:offs[r + 1]]]
+        out.append((s, minus, -score[r], t, {
+            "query_name": qn, "strand": "-" if minus else "+", "match_name": tn,
+            "nt_start": L - e if minus else a, "nt_end": L - a if minus else e, "t_start": ts[r] // 3, "t_end": (ts[r] + tl[r]) // 3,
+            "chain_score": score[r], "n_alns": n, "frames": ",".join(f"{'-' if f >= 3 else '+'}{f % 3 + 1}" for f in fr),
+            "n_frameshifts": sum(1 for u, v in zip(fr, fr[1:]) if u != v), "identities": ident[r], "aln_length": alen[r],
+            "pident": format_f64(100.0 * float(ident[r]) / float(alen[r]) if alen[r] else math.nan), "intersect_hashes": isect[r]}))
+    out.sort(key=lambda e: e[:4])
+    return [row for *_, row in out]
+
+
+def search_translated_device(nt_fasta: str, protein_fasta: str, ksize: int, scaled: int, moltype: str, ctx: Optional[Context] = None,
+                             matrix=None, extend: bool = True, x_drop: int = 20, gapped: bool = False, band: int = 16,
+                             gap_open: int = 11, gap_extend: int = 1, gapped_x_drop: int = 30, cull: bool = True,
+                             cull_overlap: int = 100, max_gap: int = 0, min_kmers: int = 1, chain_max_gap: int = 0,
+                             chain_max_overlap: int = 0, chain_link_cost: int = 0, chain_skew_cost: int = 0,
+                             chain_overlap_cost: int = 0, top_k: int = 0) -> List[dict]:
+    """Translated search to the end, on the device: the records of a nucleotide FASTA against the proteins of a protein FASTA,
+    the rows of `frame_chain_rows` — per (record, strand, protein) where the gene lies in bases, in which frames, and whether a
+    frameshift joins two of them.  The records are translated in six frames (Context.translate6), the frames sketched
+    (ksize, scaled, moltype: the protein sketch parameters) and searched against the index of the proteins; position tables of
+    frames and proteins, match_positions and match_regions (max_gap, min_kmers) give each frame hit its regions, which are scored
+    and extended without gaps (matrix, extend, x_drop) or, with gapped=True, aligned with gaps (matrix, band, gap_open,
+    gap_extend, gapped_x_drop) with the frames as the query residues; cull=True removes redundant ones (cull_overlap);
+    Context.fold_frames folds the frame rows per strand and Context.chain_frames chains their regions in bases (the chain_*
+    options are in bases).  top_k > 0 keeps per (record, strand) the k proteins with the best chain score (Context.best_hits on
+    the folded hits).  Every device object made on the way is freed."""
+    own = ctx is None
+    ctx = ctx or Context(0)
+    made = []
+
+    def keep(o):
+        made.append(o)
+        return o
+    try:
+        nt_recs, t_recs = read_fasta(nt_fasta), read_fasta(protein_fasta)
+        nt, nt_off = pack([s for _, s in nt_recs])
+        t_res, t_off = pack([s for _, s in t_recs])
+        n6, n_t = 6 * len(nt_recs), len(t_recs)
+        frames, foff, n_res = ctx.translate6(nt, nt_off)
+        keep(frames); keep(foff)
+        Q = keep(ctx.sketch_batch_device(frames.ptr, foff.ptr, n6, n_res, ksize, scaled, moltype))
+        T = keep(ctx.sketch_batch(t_res, t_off, ksize, scaled, moltype))
+        ix = keep(ctx.index_build(T))
+        hits = keep(ctx.search(ix, Q))
+        qp = keep(ctx.kmer_positions_table_device(frames.ptr, foff.ptr, n6, n_res, ksize, scaled, moltype))
+        tp = keep(ctx.kmer_positions_table(t_res, t_off, ksize, scaled, moltype))
+        mp = keep(ctx.match_positions(qp, tp, hits))
+        rg = keep(ctx.match_regions(mp, max_gap=max_gap, min_kmers=min_kmers))
+        d_t = keep(ctx.to_device(t_res if len(t_res) else np.zeros(16, np.uint8)))
+        d_to = keep(ctx.to_device(t_off))
+        batches = (frames.ptr, foff.ptr, n6, n_res, d_t.ptr, d_to.ptr, n_t, len(t_res))
+        if gapped:
+            sc = keep(ctx.align_regions_device(rg, hits, *batches, matrix=matrix, band=band, gap_open=gap_open, gap_extend=gap_extend,
+                                               x_drop=gapped_x_drop))
+        else:
+            sc = keep(ctx.score_regions_device(rg, hits, *batches, matrix=matrix, extend=extend, x_drop=x_drop))
+        kept = sc
+        if cull:
+            cu = keep(ctx.cull_regions(sc, overlap_pct=cull_overlap))
+            kept = keep(cu.take(sc))
+        fold = keep(ctx.fold_frames(hits, kept, nt_off))
+        chain = keep(ctx.chain_frames(fold, max_gap=chain_max_gap, max_overlap=chain_max_overlap, link_cost=chain_link_cost,
+                                      skew_cost=chain_skew_cost, overlap_cost=chain_overlap_cost))
+        keep_rows = None
+        if top_k:
+            best = keep(ctx.best_hits(fold.hits, k=top_k, score=chain.row_chain_score_ptr))
+            keep_rows = best.best_to_host()[1]
+        return frame_chain_rows(nt_recs, t_recs, fold.hits.to_host(), fold.to_host(), chain.to_host(), keep_rows=keep_rows)
+    finally:
+        for o in reversed(made):
+            o.free()
+        if own:
+            ctx.close()
