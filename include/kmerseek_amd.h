@@ -1151,6 +1151,115 @@ void ks_hitalns_free(ks_hitalns *a);
 /* rows of directions one wave stages at once for the walk of a fill: the tests place rectangles around it */
 uint32_t ks_debug_rstitch_stage(void);
 
+/* ---- frame stitch: the chain of a translated hit as ONE alignment of the strand's bases, frameshifts marked ------------------ */
+
+/* What a translated search is run for (blastx, DIAMOND -F): per (record strand, protein) one alignment of the strand's bases
+ * against the protein, the frameshift marked at its place and paid for in the score.  The chain of ks_regions_chain_device on a
+ * ks_ffold links alignments that lie in different frames; this pass joins their traced paths across the frames into one CIGAR
+ * in codon columns and re-scores it over the residues.  All arithmetic is in integers: the result is bit-exact against a host
+ * loop (tests/fstitch_ref.py).
+ *   fold: a ks_ffold made from gapped alignments (ks_raligns_fold_frames);  folded_hits: the fold's hit list (qid = 2 record +
+ *   strand, tid);  chain: the ks_rchain of the fold's columns (one row per folded row, src_region indexes the folded regions);
+ *   alignments: the ks_raligns the fold was made of (fold.src_region indexes it: typically ks_raligns_take of the cull);
+ *   cigars: the ks_cigars traced from exactly those alignments;  the frame batch: the residues of ks_translate6_device (6 n
+ *   sequences, what ks_regions_align took as queries);  the target batch.  The matrix, gap_open = o and gap_extend = e are those
+ *   recorded in `alignments`.
+ * Options: max_fill in [0, 4096], 0 means 1024;  flags: KS_RSTITCH_EQX;  frameshift_cost, taken as given, at most 2^16 (the
+ *   caller's parameter like the matrix; opts == NULL: 15, the value DIAMOND's manual suggests for -F);  max_scratch_bytes, 0
+ *   means 1 GiB;  reserved 0.
+ * Coordinates: a strand base position p reads the codon that is residue p / 3 of frame sequence 6 record + 3 strand + p % 3
+ *   (the fold's s_start = f + 3 q_start with f < 3: one rule addresses every frame).  An end is start + length.
+ * Trim (the rule of ks_regions_stitch, in bases): member i >= 1 loses the fewest leading columns such that its strand position is
+ *   >= the ORIGINAL strand end s_start + nt_length of member i - 1 and its target position >= that member's original target end;
+ *   a query-consuming column moves the strand position by 3.  Tails are never trimmed; a member may lose every column, its end
+ *   still stands.  A backward shift therefore shows as a trimmed codon followed by a forward skip.
+ * Link i: E, T_e the previous member's original ends, (p', t') the trimmed member's start; X = p' - E bases, Y = t' - T_e
+ *   residues, c = X / 3, r = X % 3 (r != 0 exactly when the two members' frames differ).  Two parts:
+ *   1. the protein link of ks_regions_stitch on the rectangle (c, Y) — nothing, I x c, D x Y, FILLED (min <= 63, max <= max_fill;
+ *      the same orientation and tie rules) or OPEN (I x c, then D x Y) — whose query stretch is the c codons read in the PREVIOUS
+ *      member's frame directly after its end: residues [E / 3, E / 3 + c) of frame E % 3;
+ *   2. if r != 0, ONE frameshift op of length r directly before the next member: r strand bases skipped, no codon, no target
+ *      residue, BAM code 3 (N), KS_CIGAR_FSHIFT.
+ *   The pass does NOT search for the best place of the shift inside a link.
+ * Splice: the ops of m_0, link 1, the trimmed m_1, ...; adjacent equal ops merge across joints; an N op never merges with
+ *   anything, another N included.  KS_RSTITCH_EQX as in ks_regions_stitch.  M, = and X are one codon against one residue, I a
+ *   codon without a residue, D a residue without a codon:  3 (pairs + I) + sum of N = nt_length,  pairs + D = t_length.
+ *   Worked examples (a gene of n codons, its two parts aligned in two frames, no chance match beside the shift):
+ *     one base inserted after codon m      X = 1, Y = 0            mM 1N (n - m)M
+ *     one base of codon m deleted          X = 2, Y = 1, c = 0     mM 1D 2N (n - m - 1)M
+ * Result (device-resident): a CSR over the folded rows, op_offsets u64[n_rows + 1] and ops u32[n_ops] (len << 4 | code), and per
+ *   folded row:
+ *   s_start, nt_length u32     strand bases: the first member's start to the last member's end
+ *   nt_start u32               bases on the record as given: the first member's nt_start on strand 0, the last member's on strand 1
+ *   t_start, t_length u32      residues of the target
+ *   score i64                  = sum of M[pair] - sum over the I / D ops of (o + L e) - frameshift_cost x (number of N ops)
+ *   identities, positives, gap_opens (I and D ops), gaps (their columns), aln_length (columns; N is not counted) u32
+ *   n_members, n_filled, n_open, n_trimmed (columns removed), n_frameshifts (N ops) u32
+ *   row_score f64              (double)score, NaN for a row without members: a d_score column for ks_hits_best on folded_hits
+ *   A row whose chain lies in one frame has no N op: its ops, score and counts are what ks_regions_stitch gives for the same
+ *   members on that frame's residues.  A row without members has no ops and zeros.
+ * The result never depends on the launch geometry, on ks_debug_rstitch_stage() or on max_scratch_bytes.  Scratch as in
+ * ks_regions_stitch: 64 bytes per row of the longer side of every filled link, in slices that fit max_scratch_bytes.
+ * KS_ERR_INVALID_ARG, before any device work and also with ctx == NULL: max_fill > 4096, frameshift_cost > 2^16, unknown flags,
+ * a non-zero reserved field.  Then: NULL arguments; an object of another context; row or region counts of fold, chain, folded
+ * hits, alignments and cigars that disagree.  Found on the device before anything is indexed by it, ks_last_error names the
+ * first offender: a chain src_region outside its folded row's regions; a fold src_region >= the alignments' region count; a fold
+ * that is not of these alignments (s_start != frame % 3 + 3 q_start, nt_length != 3 q_length, t_start3 != 3 t_start, t_length3
+ * != 3 t_length); frame / 3 != qid & 1; a frame sequence id >= n_f or a tid >= n_t or a sequence outside its batch; an extent
+ * outside its sequence; ops that do not consume exactly the member's extents; the M / = / X mismatch; a member that ends before
+ * the member in front of it on the strand or the target.
+ * KS_ERR_CAPACITY: a chained row with a frame or target sequence of more than 2^20 residues; one filled link whose directions
+ * do not fit max_scratch_bytes.
+ * A refused call leaves no object and nothing held in the pool.  One stream, synchronous on return, three host waits.
+ * Not built: the search for the best shift position inside a link; genetic codes other than table 1; E-values of the stitched
+ * alignment; members without traced paths (ungapped ks_rscores); folding both strands. */
+typedef struct ks_framealns ks_framealns;
+#define KS_CIGAR_FSHIFT 3u
+#define KS_FSTITCH_MAX_COST 65536u
+typedef struct ks_fstitch_opts {
+    uint32_t max_fill;          /* the longer side of a filled rectangle at most; 0: 1024; at most 4096 */
+    uint32_t flags;             /* KS_RSTITCH_EQX */
+    uint32_t frameshift_cost;   /* subtracted per N op; at most 65536 */
+    uint32_t reserved;          /* 0 */
+    uint64_t max_scratch_bytes; /* direction scratch of one slice; 0: 1 GiB */
+} ks_fstitch_opts;
+/* opts == NULL: the defaults, frameshift_cost 15 */
+int ks_frames_stitch(ks_ctx *ctx, const ks_ffold *fold, const ks_hits *folded_hits, const ks_rchain *chain, const ks_raligns *alignments,
+                     const ks_cigars *cigars, const uint8_t *d_f_res, const uint64_t *d_f_offs, uint32_t n_f, uint64_t n_f_res,
+                     const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_fstitch_opts *opts,
+                     ks_framealns **out);
+uint64_t ks_framealns_n_rows(const ks_framealns *a);
+uint64_t ks_framealns_n_ops(const ks_framealns *a);
+/* diagnostic: the direction scratch the call allocated, and the slices it ran in */
+uint64_t ks_framealns_scratch_bytes(const ks_framealns *a);
+uint32_t ks_framealns_n_slices(const ks_framealns *a);
+/* device pointers, valid until ks_framealns_free */
+const uint64_t *ks_framealns_device_op_offsets(const ks_framealns *a);
+const uint32_t *ks_framealns_device_ops(const ks_framealns *a);
+const uint32_t *ks_framealns_device_s_start(const ks_framealns *a);
+const uint32_t *ks_framealns_device_nt_length(const ks_framealns *a);
+const uint32_t *ks_framealns_device_nt_start(const ks_framealns *a);
+const uint32_t *ks_framealns_device_t_start(const ks_framealns *a);
+const uint32_t *ks_framealns_device_t_length(const ks_framealns *a);
+const int64_t *ks_framealns_device_score(const ks_framealns *a);
+const uint32_t *ks_framealns_device_identities(const ks_framealns *a);
+const uint32_t *ks_framealns_device_positives(const ks_framealns *a);
+const uint32_t *ks_framealns_device_gap_opens(const ks_framealns *a);
+const uint32_t *ks_framealns_device_gaps(const ks_framealns *a);
+const uint32_t *ks_framealns_device_aln_length(const ks_framealns *a);
+const uint32_t *ks_framealns_device_n_members(const ks_framealns *a);
+const uint32_t *ks_framealns_device_n_filled(const ks_framealns *a);
+const uint32_t *ks_framealns_device_n_open(const ks_framealns *a);
+const uint32_t *ks_framealns_device_n_trimmed(const ks_framealns *a);
+const uint32_t *ks_framealns_device_n_frameshifts(const ks_framealns *a);
+const double *ks_framealns_device_row_score(const ks_framealns *a);
+/* any destination may be NULL */
+int ks_framealns_copy_to_host(ks_ctx *ctx, const ks_framealns *a, uint64_t *op_offsets, uint32_t *ops, uint32_t *s_start, uint32_t *nt_length,
+                              uint32_t *nt_start, uint32_t *t_start, uint32_t *t_length, int64_t *score, uint32_t *identities,
+                              uint32_t *positives, uint32_t *gap_opens, uint32_t *gaps, uint32_t *aln_length, uint32_t *n_members,
+                              uint32_t *n_filled, uint32_t *n_open, uint32_t *n_trimmed, uint32_t *n_frameshifts, double *row_score);
+void ks_framealns_free(ks_framealns *a);
+
 /* ---- alignment statistics: bit scores and E-values per hit ------------------------------------------------------------------- */
 
 /* Every stage of the region pipeline ends in a raw integer score; these passes make it comparable across queries, databases

@@ -109,6 +109,15 @@ class ks_rstitch_opts(C.Structure):
     _fields_ = [("max_fill", C.c_uint32), ("flags", C.c_uint32), ("max_scratch_bytes", C.c_uint64), ("reserved", C.c_uint32 * 2)]
 
 
+KS_CIGAR_FSHIFT = 3
+KS_FSTITCH_MAX_COST = 65536
+
+
+class ks_fstitch_opts(C.Structure):
+    _fields_ = [("max_fill", C.c_uint32), ("flags", C.c_uint32), ("frameshift_cost", C.c_uint32), ("reserved", C.c_uint32),
+                ("max_scratch_bytes", C.c_uint64)]
+
+
 KS_ASTATS_NO_COMPOSITION, KS_ASTATS_PAIRWISE, KS_ASTATS_ALLOW_UNGAPPED = 1, 2, 4
 KS_ASTATS_ROW_REGULAR, KS_ASTATS_ROW_FALLBACK, KS_ASTATS_ROW_SKIPPED = 0, 1, 2
 KS_ASTATS_MAX_SEQ_LEN = 1 << 20
@@ -432,6 +441,32 @@ SIGNATURES = {
     "ks_hitalns_copy_to_host": (C.c_int, [_vp] * 19),
     "ks_hitalns_free": (None, [_vp]),
     "ks_debug_rstitch_stage": (C.c_uint32, []),
+    "ks_frames_stitch": (C.c_int, [_vp] * 6 + [_vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(ks_fstitch_opts), _pp]),
+    "ks_framealns_n_rows": (C.c_uint64, [_vp]),
+    "ks_framealns_n_ops": (C.c_uint64, [_vp]),
+    "ks_framealns_scratch_bytes": (C.c_uint64, [_vp]),
+    "ks_framealns_n_slices": (C.c_uint32, [_vp]),
+    "ks_framealns_device_op_offsets": (_vp, [_vp]),
+    "ks_framealns_device_ops": (_vp, [_vp]),
+    "ks_framealns_device_s_start": (_vp, [_vp]),
+    "ks_framealns_device_nt_length": (_vp, [_vp]),
+    "ks_framealns_device_nt_start": (_vp, [_vp]),
+    "ks_framealns_device_t_start": (_vp, [_vp]),
+    "ks_framealns_device_t_length": (_vp, [_vp]),
+    "ks_framealns_device_score": (_vp, [_vp]),
+    "ks_framealns_device_identities": (_vp, [_vp]),
+    "ks_framealns_device_positives": (_vp, [_vp]),
+    "ks_framealns_device_gap_opens": (_vp, [_vp]),
+    "ks_framealns_device_gaps": (_vp, [_vp]),
+    "ks_framealns_device_aln_length": (_vp, [_vp]),
+    "ks_framealns_device_n_members": (_vp, [_vp]),
+    "ks_framealns_device_n_filled": (_vp, [_vp]),
+    "ks_framealns_device_n_open": (_vp, [_vp]),
+    "ks_framealns_device_n_trimmed": (_vp, [_vp]),
+    "ks_framealns_device_n_frameshifts": (_vp, [_vp]),
+    "ks_framealns_device_row_score": (_vp, [_vp]),
+    "ks_framealns_copy_to_host": (C.c_int, [_vp] * 21),
+    "ks_framealns_free": (None, [_vp]),
     "ks_residue_composition_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _pp]),
     "ks_rcomp_n_seqs": (C.c_uint32, [_vp]),
     "ks_rcomp_n_residues": (C.c_uint64, [_vp]),

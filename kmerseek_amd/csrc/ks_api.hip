@@ -1098,3 +1098,76 @@ extern "C" int ks_hitalns_copy_to_host(ks_ctx *ctx, const ks_hitalns *a, uint64_
 }
 
 extern "C" void ks_hitalns_free(ks_hitalns *a) { ks_obj_free(a); }
+
+// ---------------------------------------------------------------------------------------------
+// frame stitch (ks_fstitch.hip): the chain of each folded row as one alignment of the strand's bases, frameshifts as N ops
+// ---------------------------------------------------------------------------------------------
+extern "C" int ks_frames_stitch(ks_ctx *ctx, const ks_ffold *fold, const ks_hits *folded_hits, const ks_rchain *chain, const ks_raligns *alignments,
+                                const ks_cigars *cigars, const uint8_t *d_f_res, const uint64_t *d_f_offs, uint32_t n_f, uint64_t n_f_res,
+                                const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_fstitch_opts *opts,
+                                ks_framealns **out) {
+    return ks_guard(ctx, [&]() -> int {
+    const ks_fstitch_opts dflt = {0u, 0u, 15u, 0u, 0u};
+    const ks_fstitch_opts o = opts ? *opts : dflt;
+    KS_TRY(ks_opts_words_check(ctx, "frame stitch", o.flags, KS_RSTITCH_EQX, o.reserved));
+    if (o.max_fill > KS_RSTITCH_MAX_FILL)
+        return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "frame stitch options: max_fill %u (at most %u, 0 = 1024)", o.max_fill, KS_RSTITCH_MAX_FILL)
+                   : KS_ERR_INVALID_ARG;
+    if (o.frameshift_cost > KS_FSTITCH_MAX_COST)
+        return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "frame stitch options: frameshift_cost %u (at most %u)", o.frameshift_cost, KS_FSTITCH_MAX_COST)
+                   : KS_ERR_INVALID_ARG;
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    if (!fold || !folded_hits || !chain || !alignments || !cigars || !out || !d_f_offs || !d_t_offs || (n_f_res && !d_f_res) || (n_t_res && !d_t_res))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, "frame stitch", fold, folded_hits, chain, alignments, cigars));
+    if (chain->n_rows != fold->n_rows || folded_hits->n_hits != fold->n_rows || chain->n_regions != fold->n_regions ||
+        fold->n_regions != alignments->n_regions || fold->n_src_rows != alignments->n_rows || cigars->n_regions != alignments->n_regions ||
+        cigars->n_rows != alignments->n_rows)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG,
+                       "frame stitch: the fold is of %llu regions of %llu frame rows in %llu folded rows, the chain of %llu regions in %llu rows, the "
+                       "folded hit list has %llu rows, the alignments are %llu in %llu frame rows, the CIGARs %llu in %llu: objects of other regions",
+                       (unsigned long long)fold->n_regions, (unsigned long long)fold->n_src_rows, (unsigned long long)fold->n_rows,
+                       (unsigned long long)chain->n_regions, (unsigned long long)chain->n_rows, (unsigned long long)folded_hits->n_hits,
+                       (unsigned long long)alignments->n_regions, (unsigned long long)alignments->n_rows, (unsigned long long)cigars->n_regions,
+                       (unsigned long long)cigars->n_rows);
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    const ks_res_batch Q{d_f_res, d_f_offs, n_f, n_f_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
+    ks_result<ks_framealns> R(ctx, out, ks_framealns_free);
+    KS_TRY(ks_frames_stitch_impl(ctx, fold, folded_hits, chain, alignments, cigars, Q, T, o.max_fill ? o.max_fill : 1024u, o.flags, o.frameshift_cost,
+                                 o.max_scratch_bytes, R));
+    return R.commit();
+    });
+}
+extern "C" uint64_t ks_framealns_n_rows(const ks_framealns *a) { return a ? a->n_rows : 0; }
+extern "C" uint64_t ks_framealns_n_ops(const ks_framealns *a) { return a ? a->n_ops : 0; }
+extern "C" uint64_t ks_framealns_scratch_bytes(const ks_framealns *a) { return a ? a->dir_bytes : 0; }
+extern "C" uint32_t ks_framealns_n_slices(const ks_framealns *a) { return a ? a->n_slices : 0; }
+extern "C" const uint64_t *ks_framealns_device_op_offsets(const ks_framealns *a) { return a ? a->d_op_offsets : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_ops(const ks_framealns *a) { return a ? a->d_ops : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_s_start(const ks_framealns *a) { return a ? a->d_s_start : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_nt_length(const ks_framealns *a) { return a ? a->d_nt_length : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_nt_start(const ks_framealns *a) { return a ? a->d_nt_start : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_t_start(const ks_framealns *a) { return a ? a->d_t_start : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_t_length(const ks_framealns *a) { return a ? a->d_t_length : nullptr; }
+extern "C" const int64_t *ks_framealns_device_score(const ks_framealns *a) { return a ? a->d_score : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_identities(const ks_framealns *a) { return a ? a->d_identities : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_positives(const ks_framealns *a) { return a ? a->d_positives : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_gap_opens(const ks_framealns *a) { return a ? a->d_gap_opens : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_gaps(const ks_framealns *a) { return a ? a->d_gaps : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_aln_length(const ks_framealns *a) { return a ? a->d_aln_length : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_n_members(const ks_framealns *a) { return a ? a->d_n_members : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_n_filled(const ks_framealns *a) { return a ? a->d_n_filled : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_n_open(const ks_framealns *a) { return a ? a->d_n_open : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_n_trimmed(const ks_framealns *a) { return a ? a->d_n_trimmed : nullptr; }
+extern "C" const uint32_t *ks_framealns_device_n_frameshifts(const ks_framealns *a) { return a ? a->d_n_frameshifts : nullptr; }
+extern "C" const double *ks_framealns_device_row_score(const ks_framealns *a) { return a ? a->d_row_score : nullptr; }
+extern "C" int ks_framealns_copy_to_host(ks_ctx *ctx, const ks_framealns *a, uint64_t *op_offsets, uint32_t *ops, uint32_t *s_start, uint32_t *nt_length,
+                                         uint32_t *nt_start, uint32_t *t_start, uint32_t *t_length, int64_t *score, uint32_t *identities,
+                                         uint32_t *positives, uint32_t *gap_opens, uint32_t *gaps, uint32_t *aln_length, uint32_t *n_members,
+                                         uint32_t *n_filled, uint32_t *n_open, uint32_t *n_trimmed, uint32_t *n_frameshifts, double *row_score) {
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, a, op_offsets, ops, s_start, nt_length, nt_start, t_start, t_length, score,
+                                                              identities, positives, gap_opens, gaps, aln_length, n_members, n_filled, n_open,
+                                                              n_trimmed, n_frameshifts, row_score); });
+}
+extern "C" void ks_framealns_free(ks_framealns *a) { ks_obj_free(a); }

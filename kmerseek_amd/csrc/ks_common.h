@@ -414,13 +414,14 @@ enum : u32 {
     KS_PIN_ASTATS = 266,     // 4 words, alignment statistics: first row that breaks the CSR | with an id beyond its composition | with a sequence too long | fallback rows (ks_astats.hip)
     KS_PIN_MASK = 270,       // 7 words, low-complexity mask and split: first record with bad offsets | masked residues | hot-window runs | raw segments | kept segments, then the segments' residue count (ks_mask.hip)
     KS_PIN_FFOLD = 277,      // 8 words, frame fold: first record with bad offsets | too long | first row with a qid beyond the frames | out of order | that breaks the CSR | first region beyond its frame | beyond the target bound, then the folded rows (ks_ffold.hip)
-    KS_PIN_END = 285,
+    KS_PIN_FSTITCH = 285,    // 14 words, frame stitch: the eleven first-offender words (ks_fstitch.hip: FS_BAD_*), then the scan totals: direction rows | columns | ops
+    KS_PIN_END = 299,
 };
-#define KS_PIN_WORDS 288
+#define KS_PIN_WORDS 304
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_FSTITCH && KS_PIN_FSTITCH + 14 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -714,6 +715,32 @@ struct ks_hitalns {
 // ks_regions_stitch behind its argument checks (options validated, defaults filled in; K, S, G, H: of ctx, equal counts)
 int ks_regions_stitch_impl(ks_ctx *ctx, const ks_rchain *K, const ks_raligns *S, const ks_cigars *G, const ks_hits *H, const ks_res_batch &Q,
                            const ks_res_batch &T, u32 max_fill, u32 flags, u64 max_scratch_bytes, ks_hitalns *R);
+
+// the chain of each folded row of a translated search stitched into one alignment of the strand's bases (ks_fstitch.hip)
+struct ks_framealns {
+    ks_ctx *ctx;
+    u64 n_rows, n_ops;
+    u64 *d_op_offsets;                   // n_rows + 1
+    u32 *d_ops;                          // n_ops: len << 4 | op
+    i64 *d_score;                        // n_rows, as every column below
+    u32 *d_s_start, *d_nt_length, *d_nt_start, *d_t_start, *d_t_length;
+    u32 *d_identities, *d_positives, *d_gap_opens, *d_gaps, *d_aln_length;
+    u32 *d_n_members, *d_n_filled, *d_n_open, *d_n_trimmed, *d_n_frameshifts;
+    double *d_row_score;
+    u64 dir_bytes;                       // direction scratch the call allocated, the slices it ran in (diagnostic)
+    u32 n_slices;
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_op_offsets, s.n_rows + 1); f(s.d_ops, s.n_ops); f(s.d_s_start, s.n_rows); f(s.d_nt_length, s.n_rows); f(s.d_nt_start, s.n_rows);
+        f(s.d_t_start, s.n_rows); f(s.d_t_length, s.n_rows); f(s.d_score, s.n_rows); f(s.d_identities, s.n_rows);
+        f(s.d_positives, s.n_rows); f(s.d_gap_opens, s.n_rows); f(s.d_gaps, s.n_rows); f(s.d_aln_length, s.n_rows);
+        f(s.d_n_members, s.n_rows); f(s.d_n_filled, s.n_rows); f(s.d_n_open, s.n_rows); f(s.d_n_trimmed, s.n_rows);
+        f(s.d_n_frameshifts, s.n_rows); f(s.d_row_score, s.n_rows);
+    }
+};
+// ks_frames_stitch behind its argument checks (options validated, defaults filled in; F, H, K, S, G: of ctx, equal counts)
+int ks_frames_stitch_impl(ks_ctx *ctx, const ks_ffold *F, const ks_hits *H, const ks_rchain *K, const ks_raligns *S, const ks_cigars *G,
+                          const ks_res_batch &Q, const ks_res_batch &T, u32 max_fill, u32 flags, u32 frameshift_cost, u64 max_scratch_bytes,
+                          ks_framealns *R);
 
 // the residue classes of the sequences of a batch, counted (ks_astats.hip)
 struct ks_rcomp {

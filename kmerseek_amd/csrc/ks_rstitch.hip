@@ -10,23 +10,17 @@
 //            Then the link's rectangle and its class, and for a filled link the rows of directions and the columns it needs;
 //            two exclusive scans (ks_prims.hip) lay both out, one wait brings the totals and the first refused member.
 //   slices   consecutive members whose directions fit the scratch budget run in one launch (as ks_rtrace.hip does).
-//   fill     k_rs_fill, a wave per filled link.  Lane y holds column y of T, the SHORTER stretch (0 .. |T| <= 63); a step is one
-//            row x of Q.  H and F stay in registers: F is the lane's own, D reads the H of the lane below (DPP), E is ra_e_step of
-//            ks_ralign_kit.h: the tie rules of ks_regions_align, not a copy of them.  Q's residues are staged 64 rows at a time (a
-//            lane per row, a readlane per step), T's class is loaded once.  One direction byte per cell (RA_DIR_*), rp_publish,
-//            then the wave walks back from (|Q|, |T|) — rp_walk<true> of ks_rpath_kit.h — writing one byte per column backward
-//            into the link's column slot.  `swap` (the query stretch is T) exchanges the two gap codes and the matrix index:
-//            one program, the orientation is part of the contract.  With KS_RSTITCH_EQX the pairs become = / X in a pass over
-//            the finished columns (rp_places).
-//            32-bit scores: at most 4096 + 63 steps of |M| <= 128 and gaps of at most 255 + 255 per residue.
+//   fill     k_rs_fill, a wave per filled link: rf_fill of ks_rfill_kit.h on the link's two stretches — the global affine
+//            program with lanes as the columns of the SHORTER stretch, its walk back into the link's column slot and the
+//            = / X pass — which ks_fstitch.hip runs too: one program, the orientation is part of the contract.
 //   emit     k_rs_emit<false / true>, a thread per hit row: the pieces of the row in order — member ops from the first kept
 //            one, link runs or the link's columns — through one run merger; once to count the ops (and the row's link
 //            counts and span), a scan — its output IS op_offsets — and once to write len << 4 | code.
 //   rescore  k_rs_rescore, a wave per hit row: the final ops replayed on the residues, the pairs of an op 64 at a time.
-#include "ks_rpath_kit.h"
+#include "ks_rfill_kit.h"
 
 #define RS_THREADS 256
-#define RS_SHORT_MAX 63u  // the shorter side of a filled rectangle: column 0 .. 63 are the lanes
+#define RS_SHORT_MAX RF_SHORT_MAX
 #define RS_MAX_FILL 4096u
 enum : u32 { RS_BAD_SRC = 0, RS_BAD_ROW = 1, RS_BAD_LEN = 2, RS_BAD_EXT = 3, RS_BAD_OPS = 4, RS_BAD_CODE = 5, RS_BAD_ASC = 6, RS_BAD_WALK = 7, RS_N_BAD = 8 };
 enum : u32 { RS_L_NONE = 0, RS_L_I = 1, RS_L_D = 2, RS_L_FILL = 3, RS_L_FILL_SWAP = 4, RS_L_OPEN = 5 };
@@ -148,71 +142,20 @@ __global__ __launch_bounds__(RS_THREADS) void k_rs_fill(rs_args A, rs_link *link
     // (behind the plan's wait: the member, the one before it and their row have passed every check)
     const bool swap = cls == RS_L_FILL_SWAP;
     const u32 X = ks_readfirst(links[j].X), Y = ks_readfirst(links[j].Y);
-    const u32 nQ = swap ? Y : X, nT = swap ? X : Y; // nT <= 63 <, = nQ <= 4096
+    const rf_rect R = rf_rect_of(X, Y, swap);
     const u32 r = ks_readfirst(ks_last_le_u64(A.c_offs, 0, A.n_rows - 1, j));
     const u32 gp = ks_readfirst(A.c_src[j - 1]);
     const u32 pqe = ks_readfirst(A.a_qs[gp]) + ks_readfirst(A.a_ql[gp]), pte = ks_readfirst(A.a_ts[gp]) + ks_readfirst(A.a_tl[gp]);
     const u32 q = ks_readfirst(A.qid[r]), t = ks_readfirst(A.tid[r]);
     const u8 *const qst = A.q_res + rk_readfirst64(A.q_offs[q]) + pqe, *const tst = A.t_res + rk_readfirst64(A.t_offs[t]) + pte;
-    const u8 *const Qs = swap ? tst : qst, *const Ts = swap ? qst : tst;
     u8 *const dir = Z.dir + (rk_readfirst64(Z.dir_off[j]) - Z.dir_base) * RA_DIR_ROW;
     const u32 cap = X + Y;
     u8 *const col = Z.cols + rk_readfirst64(Z.col_off[j]);
-
-    // forward: rows 1 .. nQ
-    const int o = (int)A.o, e = (int)A.e, oe = o + e, ke = (int)(lane * A.e);
-    const bool ex = lane <= nT;
-    u32 tcls = 0;
-    if (lane >= 1 && lane <= nT) tcls = s_cls[Ts[lane - 1]];
-    int H = ex ? (lane ? -(o + ke) : 0) : RA_NEG, F = RA_NEG;
-    for (u32 base = 0; base < nQ; base += 64) {
-        const u32 left = nQ - base, n_rows = left < 64u ? left : 64u;
-        u32 qbyte = 0;
-        if (lane < n_rows) qbyte = Qs[base + lane];
-        for (u32 rr = 0; rr < n_rows; rr++) {
-            const u32 x = base + 1 + rr;
-            const u32 qcls = rk_class((u32)__builtin_amdgcn_readlane((int)qbyte, (int)rr));
-            const int s = swap ? s_M[tcls * RK_A + qcls] : s_M[qcls * RK_A + tcls]; // M[class(query)][class(target)]
-            const int gH = H - oe, gF = F - e;
-            const bool cont = gF >= gH; // (on a tie the continued gap)
-            const int Fn = cont ? gF : gH;
-            const int Hb = (int)ks_lane_below((u32)H); // (a DPP move: all lanes take part)
-            const int D = lane ? Hb + s : RA_NEG;
-            const bool diag = D >= Fn; // (on a tie D)
-            int Ht = diag ? D : Fn;
-            if (!ex) Ht = RA_NEG;
-            const ra_e S = ra_e_step(Ht, lane, ke, o, ex);
-            u32 code = (diag ? RA_DIR_DIAG : 0u) | (cont ? RA_DIR_CONT : 0u);
-            H = Ht;
-            if (__ballot(S.gap)) {
-                const u32 src = ra_e_src(S, lane);
-                if (S.gap) { H = S.E; code |= (lane - src) << RA_DIR_E; }
-            }
-            F = Fn;
-            if (!ex) { H = RA_NEG; F = RA_NEG; }
-            dir[(u64)(x - 1) * RA_DIR_ROW + lane] = (u8)code;
-        }
-    }
-    rp_publish();
-
-    // back from (nQ, lane nT) to (0, lane 0); the columns go backward from col[cap - 1]
-    const u32 n = rp_walk<true>(dir, nQ, nT, 0u, RS_SHORT_MAX, swap ? RP_I : RP_D, swap ? RP_D : RP_I, col, -1, cap, s_stage[wave], lane);
-    if (n == RP_BAD) {
-        if (lane == 0) { ks_first_bad(A.bad, RS_BAD_WALK, j); links[j].ncol = 0; }
-        return;
-    }
-    if (lane == 0) links[j].ncol = n;
-    if (!A.eqx) return;
-    rp_publish();
-    u8 *const path = col + (cap - n);
-    u32 nq = 0, nt = 0;
-    for (u32 c = 0; c < n; c += 64) {
-        const u32 i = c + lane;
-        const bool valid = i < n;
-        const u32 code = valid ? path[i] : 0xffu;
-        const rp_place at = rp_places(valid, code, lane, nq, nt);
-        if (code == RP_M && at.q < X && at.t < Y) path[i] = (u8)(rk_upper(qst[at.q]) == rk_upper(tst[at.t]) ? RP_EQ : RP_X);
-    }
+    rf_fill(R, qst, tst, A.o, A.e, A.eqx, dir, col, cap, s_cls, s_M, s_stage[wave], lane, [=](u32 n) {
+        if (n == RP_BAD) {
+            if (lane == 0) { ks_first_bad(A.bad, RS_BAD_WALK, j); links[j].ncol = 0; }
+        } else if (lane == 0) links[j].ncol = n;
+    });
 }
 
 struct rs_out {

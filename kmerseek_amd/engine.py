@@ -866,6 +866,43 @@ class Context:
         with self._batches(q_res, q_off, t_res, t_off) as b:
             return self.stitch_chains_device(chain, alignments, cigars, hits, *b, max_fill=max_fill, eqx=eqx, max_scratch_bytes=max_scratch_bytes)
 
+    @staticmethod
+    def _fstitch_opts(max_fill: int, eqx: bool, frameshift_cost: int, max_scratch_bytes: int):
+        max_fill = _int_in("max_fill", max_fill, _lib.KS_RSTITCH_MAX_FILL)
+        return _lib.ks_fstitch_opts(max_fill, _lib.KS_RSTITCH_EQX if eqx else 0, _int_in("frameshift_cost", frameshift_cost, _lib.KS_FSTITCH_MAX_COST),
+                                    0, _int_in("max_scratch_bytes", max_scratch_bytes, 2 ** 64 - 1))
+
+    def stitch_frames_device(self, fold: "FrameFold", chain: "RegionChain", alignments: "RegionAlignments", cigars: "RegionCigars",
+                             d_f_res: int, d_f_off: int, n_f: int, n_f_res: int, d_t_res: int, d_t_off: int, n_t: int, n_t_res: int,
+                             max_fill: int = 0, eqx: bool = False, frameshift_cost: int = 15, max_scratch_bytes: int = 0) -> "FrameAlignments":
+        """ks_frames_stitch from device-resident residue batches: the chain of every folded row of a translated search made into
+        ONE alignment of the strand's bases against the target protein — one CIGAR in codon columns, a frameshift as an N op of
+        1 or 2 bases directly before the member behind it, paid with frameshift_cost in the re-computed score.  `fold` is
+        fold_frames(frame_hits, alignments, ...) — its hits are the rows — `chain` chain_frames(fold), `alignments` the gapped
+        alignments the fold was made of (cull.take(...)), `cigars` what trace_regions gave for exactly those (eqx=True here:
+        traced with eqx=True).  d_f_res / d_f_off: the frame batch of translate6 (n_f = 6 x records), what align_regions took
+        as queries; then the target batch.  max_fill, max_scratch_bytes as in stitch_chains_device.  A row whose chain lies in
+        one frame gives what stitch_chains gives on that frame.  include/kmerseek_amd.h has the contract."""
+        opts = self._fstitch_opts(max_fill, eqx, frameshift_cost, max_scratch_bytes)
+        out = C.c_void_p()
+        self._check(self._L.ks_frames_stitch(self._h, fold._h, fold.hits._h, chain._h, alignments._h, cigars._h, C.c_void_p(d_f_res),
+                                             C.c_void_p(d_f_off), int(n_f), int(n_f_res), C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t),
+                                             int(n_t_res), C.byref(opts), C.byref(out)))
+        return FrameAlignments(self, out)
+
+    def stitch_frames(self, fold: "FrameFold", chain: "RegionChain", alignments: "RegionAlignments", cigars: "RegionCigars",
+                      frames: "DeviceBuffer", frame_offsets: "DeviceBuffer", n_frame_res: int, t_res: np.ndarray, t_off: np.ndarray,
+                      max_fill: int = 0, eqx: bool = False, frameshift_cost: int = 15, max_scratch_bytes: int = 0) -> "FrameAlignments":
+        """stitch_frames_device with the frame batch as translate6 returned it (frames, frame_offsets, n_frame_res: device
+        buffers, 6 frames per record) and the target batch from host arrays, uploaded for the call."""
+        self._fstitch_opts(max_fill, eqx, frameshift_cost, max_scratch_bytes)  # (refused before anything is uploaded)
+        t_res = np.ascontiguousarray(t_res, dtype=np.uint8); t_off = np.ascontiguousarray(t_off, dtype=np.uint64)
+        n_f = frame_offsets.nbytes // 8 - 1
+        with self._uploaded(t_res if t_res.size else np.zeros(1, np.uint8), t_off) as (d_t, d_to):
+            return self.stitch_frames_device(fold, chain, alignments, cigars, frames.ptr, frame_offsets.ptr, n_f, int(n_frame_res), d_t, d_to,
+                                             len(t_off) - 1, int(t_res.size), max_fill=max_fill, eqx=eqx, frameshift_cost=frameshift_cost,
+                                             max_scratch_bytes=max_scratch_bytes)
+
     def residue_composition_device(self, d_res: int, d_off: int, n_seqs: int, n_res: int) -> "Composition":
         """ks_residue_composition_device from a device-resident residue batch (raw pointers: residues u8, offsets
         u64[n_seqs + 1]): per sequence the count of each of the 28 residue classes of score_regions (A..Z, '*', everything else)
@@ -1540,6 +1577,45 @@ class HitAlignments(_Columns):
 
     def strings(self) -> List[str]:
         """The CIGAR of every hit row as text, e.g. "60M40I60M"; "" for a row without a chain."""
+        return cigar_strings(*self.ops_to_host())
+
+
+class FrameAlignments(_Columns):
+    """Device-resident result of Context.stitch_frames (ks_framealns): per folded row of a translated search ONE alignment of
+    the strand's bases against the target protein, as a CSR of BAM-encoded ops in codon columns (row r owns ops
+    [op_offsets[r], op_offsets[r + 1]), an op is len << 4 | code; M, = and X a codon against a residue, I a codon alone, D a
+    residue alone, N a frameshift of 1 or 2 skipped bases) and the columns of that alignment: its span in strand bases (s_start,
+    nt_length), nt_start on the record as given, its span on the target, score (i64: pairs minus gaps minus frameshift_cost per
+    N), identities, positives, gap_opens, gaps, aln_length (N not counted), the chain members, filled and open links, trimmed
+    columns and frameshifts behind it, and the score as f64 (NaN: a row without a chain), a `score=` column for
+    Context.best_hits(fold.hits, ...)."""
+    _PREFIX, _COUNTS = "framealns", {"n_rows": "", "n_ops": ""}
+    _TABLE = (("op_offsets", "u8", "n_rows + 1"), ("ops", "u4", "n_ops")) + tuple(
+        (c, {"score": "i8", "row_score": "f8"}.get(c, "u4"), "n_rows") for c in (
+            "s_start", "nt_length", "nt_start", "t_start", "t_length", "score", "identities", "positives", "gap_opens", "gaps", "aln_length",
+            "n_members", "n_filled", "n_open", "n_trimmed", "n_frameshifts", "row_score"))
+
+    @property
+    def n_slices(self) -> int:
+        """Slices of chain members the fills ran in (1 unless the directions did not fit max_scratch_bytes).  Diagnostic."""
+        return int(self._ctx._L.ks_framealns_n_slices(self._h))
+
+    @property
+    def scratch_bytes(self) -> int:
+        """Direction scratch the call allocated.  Diagnostic."""
+        return int(self._ctx._L.ks_framealns_scratch_bytes(self._h))
+
+    @property
+    def row_score_ptr(self) -> int:
+        """The device column row_score f64[n_rows]: pass it to Context.best_hits(fold.hits, score=...)."""
+        return int(self._ctx._L.ks_framealns_device_row_score(self._h) or 0)
+
+    def ops_to_host(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(op_offsets u64[n_rows + 1], ops u32[n_ops]) alone."""
+        return self._copy_out(("op_offsets", "ops"))
+
+    def strings(self) -> List[str]:
+        """The CIGAR of every folded row as text, e.g. "41M1N59M"; "" for a row without a chain."""
         return cigar_strings(*self.ops_to_host())
 
 

@@ -1086,7 +1086,7 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
 
 
 def frame_chain_rows(nt_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], fold_hits_host, fold_host,
-                     chain_host, keep_rows=None) -> List[dict]:
+                     chain_host, keep_rows=None, stitched=None) -> List[dict]:
     """One row per folded row of a translated search that has a chain: where on the nucleotide record the protein lies, on which
     strand and in which frames.  fold_hits_host = FrameFold.hits.to_host() (qid = 2 * record + strand), fold_host =
     FrameFold.to_host(), chain_host = RegionChain.to_host() of Context.chain_frames on that fold.  Columns: query_name, strand
@@ -1095,7 +1095,13 @@ def frame_chain_rows(nt_records: Sequence[Tuple[str, bytes]], t_records: Sequenc
     frames in chain order in BLAST's numbering, +1 .. +3 and -1 .. -3, comma-joined), n_frameshifts (consecutive members whose
     frames differ), identities, aln_length, pident (100 * identities / aln_length, NaN where the fold had no such columns) and
     intersect_hashes (the shared hashes of the member frame rows, summed).  keep_rows: the folded rows to report (None: all).
-    Sorted by (record, strand, -chain_score, target)."""
+    stitched = FrameAlignments.to_host() of Context.stitch_frames on that chain: every row also carries the one alignment of the
+    strand's bases against the protein — aln_cigar (codon columns; N: skipped bases), aln_score, aln_identities, aln_positives,
+    aln_gap_opens, aln_gaps, aln_length, aln_pident, n_filled, n_open (aln_length then CHANGES its meaning: it is the column count of
+    that one alignment, no longer the members' sum, so that aln_pident = 100 * aln_identities / aln_length; identities and pident
+    stay the members' sums and their ratio to the members' lengths) — and aln_frameshifts, the places of its N ops on the record
+    as given as a comma-joined list of nt_pos:len (the first skipped base on the record, 0-based, and the bases skipped).  Without
+    it the rows are what they were.  Sorted by (record, strand, -chain_score, target)."""
     qid, tid, isect = [np.asarray(c).tolist() for c in fold_hits_host[:3]]
     frame = np.asarray(fold_host[3]).tolist()
     cols = [np.asarray(c).tolist() for c in chain_host]
@@ -1103,6 +1109,12 @@ def frame_chain_rows(nt_records: Sequence[Tuple[str, bytes]], t_records: Sequenc
     if len(offs) != len(qid) + 1 or len(qid) != len(tid) or len(np.asarray(fold_host[1])) != len(offs):
         raise ValueError("chain, fold and folded hits are not of the same rows")
     keep = None if keep_rows is None else set(np.asarray(keep_rows).tolist())
+    if stitched is not None:
+        st = [np.asarray(c).tolist() for c in stitched]
+        if len(st[0]) != len(offs) or any(len(c) != len(qid) for c in st[2:]):
+            raise ValueError("stitched alignments and chain are not of the same rows")
+        from .engine import cigar_strings
+        st_text = cigar_strings(st[0], st[1])
     out = []
     for r, (x, t) in enumerate(zip(qid, tid)):
         n = offs[r + 1] - offs[r]
@@ -1112,12 +1124,26 @@ def frame_chain_rows(nt_records: Sequence[Tuple[str, bytes]], t_records: Sequenc
         (qn, qseq), (tn, _) = nt_records[s], t_records[t]
         L, a, e = len(qseq), qs[r], qs[r] + ql[r]
         fr = [frame[g] for g in src[offs[r]:offs[r + 1]]]
+        more = {}
+        if stitched is not None:
+            p, shifts = st[2][r], []  # the strand position of the next column
+            for v in st[1][st[0][r]:st[0][r + 1]]:
+                k, c = v >> 4, v & 15
+                if c == 3:
+                    shifts.append(f"{L - p - k if minus else p}:{k}")
+                    p += k
+                elif c != 2:
+                    p += 3 * k
+            more = {"aln_cigar": st_text[r], "aln_score": st[7][r], "aln_identities": st[8][r], "aln_positives": st[9][r], "aln_gap_opens": st[10][r],
+                    "aln_gaps": st[11][r], "aln_length": st[12][r],
+                    "aln_pident": format_f64(100.0 * float(st[8][r]) / float(st[12][r]) if st[12][r] else math.nan),
+                    "n_filled": st[14][r], "n_open": st[15][r], "aln_frameshifts": ",".join(shifts)}
         out.append((s, minus, -score[r], t, {
             "query_name": qn, "strand": "-" if minus else "+", "match_name": tn,
             "nt_start": L - e if minus else a, "nt_end": L - a if minus else e, "t_start": ts[r] // 3, "t_end": (ts[r] + tl[r]) // 3,
             "chain_score": score[r], "n_alns": n, "frames": ",".join(f"{'-' if f >= 3 else '+'}{f % 3 + 1}" for f in fr),
             "n_frameshifts": sum(1 for u, v in zip(fr, fr[1:]) if u != v), "identities": ident[r], "aln_length": alen[r],
-            "pident": format_f64(100.0 * float(ident[r]) / float(alen[r]) if alen[r] else math.nan), "intersect_hashes": isect[r]}))
+            "pident": format_f64(100.0 * float(ident[r]) / float(alen[r]) if alen[r] else math.nan), "intersect_hashes": isect[r], **more}))
     out.sort(key=lambda e: e[:4])
     return [row for *_, row in out]
 
@@ -1127,7 +1153,8 @@ def search_translated_device(nt_fasta: str, protein_fasta: str, ksize: int, scal
                              gap_open: int = 11, gap_extend: int = 1, gapped_x_drop: int = 30, cull: bool = True,
                              cull_overlap: int = 100, max_gap: int = 0, min_kmers: int = 1, chain_max_gap: int = 0,
                              chain_max_overlap: int = 0, chain_link_cost: int = 0, chain_skew_cost: int = 0,
-                             chain_overlap_cost: int = 0, top_k: int = 0) -> List[dict]:
+                             chain_overlap_cost: int = 0, top_k: int = 0, cigar: bool = False, eqx: bool = False, stitch: bool = False,
+                             max_fill: int = 0, frameshift_cost: int = 15) -> List[dict]:
     """Translated search to the end, on the device: the records of a nucleotide FASTA against the proteins of a protein FASTA,
     the rows of `frame_chain_rows` — per (record, strand, protein) where the gene lies in bases, in which frames, and whether a
     frameshift joins two of them.  The records are translated in six frames (Context.translate6), the frames sketched
@@ -1137,7 +1164,19 @@ def search_translated_device(nt_fasta: str, protein_fasta: str, ksize: int, scal
     gap_extend, gapped_x_drop) with the frames as the query residues; cull=True removes redundant ones (cull_overlap);
     Context.fold_frames folds the frame rows per strand and Context.chain_frames chains their regions in bases (the chain_*
     options are in bases).  top_k > 0 keeps per (record, strand) the k proteins with the best chain score (Context.best_hits on
-    the folded hits).  Every device object made on the way is freed."""
+    the folded hits).  cigar=True says that paths may be traced; alone it adds nothing to the rows and costs nothing.
+    stitch=True (needs gapped=True and cigar=True) traces the kept alignments (eqx: = / X for M), stitches every
+    chain into ONE alignment of the strand's bases against the protein (Context.stitch_frames: max_fill, frameshift_cost), adds
+    its columns to the rows (frame_chain_rows with stitched=) and ranks top_k by that alignment's score instead of the chain
+    score.  Every device object made on the way is freed."""
+    if stitch:
+        for name, on in (("gapped", gapped), ("cigar", cigar)):
+            if not on:
+                raise ValueError(f"stitch=True needs {name}=True: a stitched alignment is made of the traced alignments of a strand's chain")
+    if cigar and not gapped:
+        raise ValueError("cigar=True needs gapped=True: CIGARs are of gapped alignments")
+    if eqx and not cigar:
+        raise ValueError("eqx=True needs cigar=True: = and X are ops of a CIGAR")
     own = ctx is None
     ctx = ctx or Context(0)
     made = []
@@ -1168,18 +1207,25 @@ def search_translated_device(nt_fasta: str, protein_fasta: str, ksize: int, scal
                                                x_drop=gapped_x_drop))
         else:
             sc = keep(ctx.score_regions_device(rg, hits, *batches, matrix=matrix, extend=extend, x_drop=x_drop))
-        kept = sc
+        kept, kept_rg = sc, rg
         if cull:
             cu = keep(ctx.cull_regions(sc, overlap_pct=cull_overlap))
             kept = keep(cu.take(sc))
+            if stitch:
+                kept_rg = keep(cu.take(rg))
         fold = keep(ctx.fold_frames(hits, kept, nt_off))
         chain = keep(ctx.chain_frames(fold, max_gap=chain_max_gap, max_overlap=chain_max_overlap, link_cost=chain_link_cost,
                                       skew_cost=chain_skew_cost, overlap_cost=chain_overlap_cost))
+        stitched = None
+        if stitch:  # (cigar=True alone traces nothing: the members' own CIGARs are not columns of these rows)
+            cg = keep(ctx.trace_regions_device(kept_rg, hits, *batches, kept, eqx=eqx))
+            stitched = keep(ctx.stitch_frames_device(fold, chain, kept, cg, *batches, max_fill=max_fill, eqx=eqx, frameshift_cost=frameshift_cost))
         keep_rows = None
         if top_k:
-            best = keep(ctx.best_hits(fold.hits, k=top_k, score=chain.row_chain_score_ptr))
+            best = keep(ctx.best_hits(fold.hits, k=top_k, score=stitched.row_score_ptr if stitch else chain.row_chain_score_ptr))
             keep_rows = best.best_to_host()[1]
-        return frame_chain_rows(nt_recs, t_recs, fold.hits.to_host(), fold.to_host(), chain.to_host(), keep_rows=keep_rows)
+        return frame_chain_rows(nt_recs, t_recs, fold.hits.to_host(), fold.to_host(), chain.to_host(), keep_rows=keep_rows,
+                                stitched=stitched.to_host() if stitch else None)
     finally:
         for o in reversed(made):
             o.free()
