@@ -1260,6 +1260,113 @@ int ks_framealns_copy_to_host(ks_ctx *ctx, const ks_framealns *a, uint64_t *op_o
                               uint32_t *n_filled, uint32_t *n_open, uint32_t *n_trimmed, uint32_t *n_frameshifts, double *row_score);
 void ks_framealns_free(ks_framealns *a);
 
+/* ---- coverage: per-residue depth and profile of many alignments, per-sequence breadth ---------------------------------------- */
+
+/* What the alignments are for once there are many of them: taken together, what do they say about a sequence?  Every pass above
+ * works inside one hit row; this one reduces ACROSS the rows onto the residues of one batch — the breadth-of-coverage filter of a
+ * read-to-protein pipeline ("is this protein present" is how much of it the reads cover, and how deep), the per-position depth
+ * that shows a query's domains, and the per-position residue counts that every conservation score, consensus or PSSM starts
+ * from.  Everything but the two quotients is an integer and exact (tests/pileup_ref.py restates it in plain loops).
+ *   The call takes ENTRIES.  An entry is a run of CIGAR ops (len << 4 | BAM code, the query as the read, as in ks_cigars) that
+ *   belongs to a hit row (qid, tid) of `hits`, with a start position on each side, counted from the sequence's first residue.
+ *   A SIDE is chosen, KS_PILEUP_QUERY or KS_PILEUP_TARGET: the entry's sequence is qid or tid of its row in that side's batch;
+ *   the OTHER side is the remaining one.
+ * How the ops consume the two sides:
+ *   M, =, X   PAIR COLUMNS: one residue on both sides
+ *   I         the query only;      D   the target only
+ *   N         (code 3, KS_CIGAR_FSHIFT) nothing on the target.  On the query side it stands for skipped bases of a strand, which
+ *             no residue batch holds: N is legal only where the query side is not read — side == KS_PILEUP_TARGET without the
+ *             profile.
+ *   An op of length 0 consumes nothing and covers nothing.
+ * Per residue p of the side's batch (n_residues of them, batch coordinates offsets[seq] + position):
+ *   depth[p] u32            the pair columns, over all entries taken, that place p.  An entry places a residue at most once;
+ *                           entries of one row that overlap each count.
+ *   counts[p * 28 + c] u32  with KS_PILEUP_PROFILE: those columns whose residue on the OTHER side has class c — the 28 classes of
+ *                           ks_residue_composition_device and the score matrices (A..Z without case, '*', everything else).
+ *                           For every p the 28 counts sum to depth[p].  Without the flag the column has no entries
+ *                           (ks_pileup_n_profile == 0).
+ * Per sequence s of the side's batch (n_seqs):
+ *   length u32;  n_alignments u32  entries taken with at least one pair column on s;  covered u32  positions with depth > 0;
+ *   max_depth u32;  depth_sum u64;  breadth f64 = covered / length;  mean_depth f64 = depth_sum / length — both the correctly
+ *   rounded f64 quotient of the two integers (what numpy gives), NaN for an empty sequence.
+ * Worked examples (one entry, starts 0, depth of the side):
+ *   2M1I2M   query side: 5 residues, depth 1 1 0 1 1 (the inserted residue has no column);  target side: 4 residues, 1 1 1 1
+ *   2M1D2M   query side: 4 residues, 1 1 1 1;  target side: 5 residues, 1 1 0 1 1
+ *   41M1N59M target side: 100 residues of depth 1 — the N moves nothing there
+ * Arguments of ks_pileup_device:
+ *   d_row_offsets u64[n_rows + 1]: the CSR of the entries over the hit rows, or NULL: one entry per row (n_entries == n_rows);
+ *   d_op_offsets u64[n_entries + 1], d_ops u32[n_ops]: the CSR of the ops over the entries;
+ *   d_start u32[n_entries]: the entries' starts on the chosen side;  d_other_start: on the other side (profile only, else NULL);
+ *   d_row_mask u8[n_rows] or NULL: the entries of a row with 0 are skipped (nothing of them is read: a top-k selection of rows);
+ *   hits: n_rows rows, read for qid and tid;  d_offsets, n_seqs, n_res: the side's batch (its residues are not read);
+ *   d_o_res, d_o_offsets, n_o_seqs, n_o_res: the other batch (profile only, else NULL / 0).
+ * The result never depends on the launch geometry, on the order the entries are processed in or on an internal path: every add
+ * is an integer add (KS_DEBUG_PILEUP_PATH = 1 / 2 send every sequence's reduction to a wave / to a workgroup, for the tests).
+ * KS_ERR_INVALID_ARG, options first, before any device work and also with ctx == NULL: unknown flags, a side that is neither,
+ * a non-zero reserved, KS_PILEUP_PROFILE without the other batch or without d_other_start.  Then: NULL arguments; an object of
+ * another context; n_rows that is not the hit list's row count; entries without rows.  Then KS_ERR_CAPACITY: n_res >= 2^32 - 1
+ * (one 32-bit scan takes fewer), 2^32 - 2 or more rows or entries, more than 2^32 - 1 ops.  Then, found on the device before
+ * anything is indexed by it, the first kind that occurs, its lowest index named in ks_last_error:
+ *   a row CSR, then op offsets, that descend or do not end at their count (the index of the offset);
+ *   a hit row whose id lies beyond its batch (the other batch only with the profile);
+ *   an entry with an op code outside M I D N = X, or an N where the query side is read;
+ *   an entry whose ops consume more of either sequence than it has from its start (the other side only with the profile);
+ *   an entry on a sequence whose offsets descend or pass its batch;  a sequence of the side's batch with such offsets.
+ * Whatever the inputs hold, nothing is read or written outside the batches, the entries and the result's arrays.  A refused
+ * call leaves no object and nothing held in the pool.  One stream, synchronous on return, one host wait.  Scratch from the
+ * pool: 8 bytes per residue of the side's batch and 8 per sequence.
+ * Not built: depth in bases on the query side of frame alignments; consensus strings, log-odds or PSSM columns; weighting by
+ * abundance or score. */
+typedef struct ks_pileup ks_pileup;
+#define KS_PILEUP_QUERY   0u
+#define KS_PILEUP_TARGET  1u
+#define KS_PILEUP_PROFILE 1u /* flags: also counts[p][class of the other side's residue] */
+typedef struct ks_pileup_opts {
+    uint32_t flags;    /* KS_PILEUP_PROFILE */
+    uint32_t side;     /* KS_PILEUP_QUERY | KS_PILEUP_TARGET */
+    uint64_t reserved; /* 0 */
+} ks_pileup_opts;
+/* opts == NULL: the depth of the query side */
+int ks_pileup_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint64_t *d_op_offsets, const uint32_t *d_ops, uint64_t n_rows,
+                     uint64_t n_entries, uint64_t n_ops, const uint32_t *d_start, const uint32_t *d_other_start, const uint8_t *d_row_mask,
+                     const ks_hits *hits, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res,
+                     const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs, uint64_t n_o_res,
+                     const ks_pileup_opts *opts, ks_pileup **out);
+/* The three kinds of alignments the passes above make, piled up (thin wrappers, as ks_rscores_stats over ks_scores_stats_device).
+ * ks_cigars_pileup: the entries are the regions of `cigars`; the row CSR and the starts come from `alignments`, the ks_raligns
+ * they were traced from (equal counts).  ks_hitalns_pileup: one entry per hit row, the stitched alignment; a row without members
+ * has no ops and adds nothing.  ks_frames_pileup: one entry per folded row of a translated search on `fold_hits`, TARGET SIDE
+ * ONLY — M and D move the protein by one, I and N by nothing; KS_PILEUP_QUERY and KS_PILEUP_PROFILE are refused by name with the
+ * options (depth in bases on a strand is not built). */
+int ks_cigars_pileup(ks_ctx *ctx, const ks_cigars *cigars, const ks_raligns *alignments, const ks_hits *hits, const uint8_t *d_row_mask,
+                     const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res, const uint8_t *d_o_res, const uint64_t *d_o_offsets,
+                     uint32_t n_o_seqs, uint64_t n_o_res, const ks_pileup_opts *opts, ks_pileup **out);
+int ks_hitalns_pileup(ks_ctx *ctx, const ks_hitalns *stitched, const ks_hits *hits, const uint8_t *d_row_mask, const uint64_t *d_offsets,
+                      uint32_t n_seqs, uint64_t n_res, const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs,
+                      uint64_t n_o_res, const ks_pileup_opts *opts, ks_pileup **out);
+int ks_frames_pileup(ks_ctx *ctx, const ks_framealns *frame_alignments, const ks_hits *fold_hits, const uint8_t *d_row_mask,
+                        const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res, const ks_pileup_opts *opts, ks_pileup **out);
+uint32_t ks_pileup_n_seqs(const ks_pileup *p);
+uint64_t ks_pileup_n_residues(const ks_pileup *p);
+/* entries of `counts`: 28 x n_residues with KS_PILEUP_PROFILE, else 0 */
+uint64_t ks_pileup_n_profile(const ks_pileup *p);
+/* device pointers, valid until ks_pileup_free */
+const uint32_t *ks_pileup_device_depth(const ks_pileup *p);
+const uint32_t *ks_pileup_device_counts(const ks_pileup *p);
+const uint32_t *ks_pileup_device_length(const ks_pileup *p);
+const uint32_t *ks_pileup_device_n_alignments(const ks_pileup *p);
+const uint32_t *ks_pileup_device_covered(const ks_pileup *p);
+const uint32_t *ks_pileup_device_max_depth(const ks_pileup *p);
+const uint64_t *ks_pileup_device_depth_sum(const ks_pileup *p);
+const double *ks_pileup_device_breadth(const ks_pileup *p);
+const double *ks_pileup_device_mean_depth(const ks_pileup *p);
+/* any destination may be NULL */
+int ks_pileup_copy_to_host(ks_ctx *ctx, const ks_pileup *p, uint32_t *depth, uint32_t *counts, uint32_t *length, uint32_t *n_alignments,
+                           uint32_t *covered, uint32_t *max_depth, uint64_t *depth_sum, double *breadth, double *mean_depth);
+void ks_pileup_free(ks_pileup *p);
+/* the longest sequence a wave reduces; a longer one goes to a workgroup (the tests place sequences around it) */
+void ks_debug_pileup_limits(uint32_t *wave_max);
+
 /* ---- alignment statistics: bit scores and E-values per hit ------------------------------------------------------------------- */
 
 /* Every stage of the region pipeline ends in a raw integer score; these passes make it comparable across queries, databases

@@ -118,6 +118,13 @@ class ks_fstitch_opts(C.Structure):
                 ("max_scratch_bytes", C.c_uint64)]
 
 
+KS_PILEUP_QUERY, KS_PILEUP_TARGET, KS_PILEUP_PROFILE = 0, 1, 1
+
+
+class ks_pileup_opts(C.Structure):
+    _fields_ = [("flags", C.c_uint32), ("side", C.c_uint32), ("reserved", C.c_uint64)]
+
+
 KS_ASTATS_NO_COMPOSITION, KS_ASTATS_PAIRWISE, KS_ASTATS_ALLOW_UNGAPPED = 1, 2, 4
 KS_ASTATS_ROW_REGULAR, KS_ASTATS_ROW_FALLBACK, KS_ASTATS_ROW_SKIPPED = 0, 1, 2
 KS_ASTATS_MAX_SEQ_LEN = 1 << 20
@@ -467,6 +474,26 @@ SIGNATURES = {
     "ks_framealns_device_row_score": (_vp, [_vp]),
     "ks_framealns_copy_to_host": (C.c_int, [_vp] * 21),
     "ks_framealns_free": (None, [_vp]),
+    "ks_pileup_device": (C.c_int, [_vp] * 4 + [C.c_uint64] * 3 + [_vp] * 5 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64,
+                                   C.POINTER(ks_pileup_opts), _pp]),
+    "ks_cigars_pileup": (C.c_int, [_vp] * 6 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(ks_pileup_opts), _pp]),
+    "ks_hitalns_pileup": (C.c_int, [_vp] * 5 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(ks_pileup_opts), _pp]),
+    "ks_frames_pileup": (C.c_int, [_vp] * 5 + [C.c_uint32, C.c_uint64, C.POINTER(ks_pileup_opts), _pp]),
+    "ks_pileup_n_seqs": (C.c_uint32, [_vp]),
+    "ks_pileup_n_residues": (C.c_uint64, [_vp]),
+    "ks_pileup_n_profile": (C.c_uint64, [_vp]),
+    "ks_pileup_device_depth": (_vp, [_vp]),
+    "ks_pileup_device_counts": (_vp, [_vp]),
+    "ks_pileup_device_length": (_vp, [_vp]),
+    "ks_pileup_device_n_alignments": (_vp, [_vp]),
+    "ks_pileup_device_covered": (_vp, [_vp]),
+    "ks_pileup_device_max_depth": (_vp, [_vp]),
+    "ks_pileup_device_depth_sum": (_vp, [_vp]),
+    "ks_pileup_device_breadth": (_vp, [_vp]),
+    "ks_pileup_device_mean_depth": (_vp, [_vp]),
+    "ks_pileup_copy_to_host": (C.c_int, [_vp] * 11),
+    "ks_pileup_free": (None, [_vp]),
+    "ks_debug_pileup_limits": (None, [_u32p]),
     "ks_residue_composition_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _pp]),
     "ks_rcomp_n_seqs": (C.c_uint32, [_vp]),
     "ks_rcomp_n_residues": (C.c_uint64, [_vp]),

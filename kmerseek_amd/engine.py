@@ -96,6 +96,16 @@ def _int_in(name: str, v, top: int, shown: Optional[str] = None) -> int:
     return int(v)
 
 
+PILEUP_SIDES = {"query": _lib.KS_PILEUP_QUERY, "target": _lib.KS_PILEUP_TARGET}
+
+
+def _pileup_opts(side: str, profile: bool):
+    """ks_pileup_opts of Context.pileup / pileup_device, or ValueError for a side that is neither."""
+    if side not in PILEUP_SIDES:
+        raise ValueError(f"side = {side!r} is neither \"query\" nor \"target\"")
+    return _lib.ks_pileup_opts(_lib.KS_PILEUP_PROFILE if profile else 0, PILEUP_SIDES[side], 0)
+
+
 def karlin_ungapped(matrix, freq_q, freq_t) -> Tuple[float, float, float]:
     """ks_karlin_ungapped: (lambda, K, H) of `matrix` (int8 [28, 28], None: +1 / -1) without gaps under the residue-class
     weights freq_q and freq_t (28 each, of which the 20 standard classes count, renormalised).  Host only, no context."""
@@ -903,6 +913,74 @@ class Context:
                                              len(t_off) - 1, int(t_res.size), max_fill=max_fill, eqx=eqx, frameshift_cost=frameshift_cost,
                                              max_scratch_bytes=max_scratch_bytes)
 
+    def pileup_device(self, d_row_offsets: Optional[int], d_op_offsets: int, d_ops: int, n_rows: int, n_entries: int, n_ops: int,
+                      d_start: int, d_other_start: Optional[int], d_row_mask: Optional[int], hits: "Hits", d_offsets: int, n_seqs: int,
+                      n_res: int, side: str = "target", profile: bool = False, d_other_res: Optional[int] = None,
+                      d_other_off: Optional[int] = None, n_other: int = 0, n_other_res: int = 0) -> "Pileup":
+        """ks_pileup_device from raw device pointers: the entries (runs of CIGAR ops, each of a hit row of `hits`, with a start on
+        the chosen side) piled up on the residues of that side's batch — per residue the depth, with profile=True also the 28
+        counts of the residue classes aligned to it (the other batch and d_other_start are then needed), per sequence length,
+        n_alignments, covered, max_depth, depth_sum, breadth and mean_depth.  d_row_offsets None: one entry per hit row;
+        d_row_mask: u8 per hit row, the entries of a row with 0 are skipped.  include/kmerseek_amd.h has the contract."""
+        opts = _pileup_opts(side, profile)
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        out = C.c_void_p()
+        self._check(self._L.ks_pileup_device(self._h, vp(d_row_offsets), vp(d_op_offsets), vp(d_ops), int(n_rows), int(n_entries), int(n_ops),
+                                             vp(d_start), vp(d_other_start), vp(d_row_mask), hits._h, vp(d_offsets), int(n_seqs), int(n_res),
+                                             vp(d_other_res), vp(d_other_off), int(n_other), int(n_other_res), C.byref(opts), C.byref(out)))
+        return Pileup(self, out)
+
+    def pileup(self, aligned, hits: "Hits", side: str = "target", offsets=None, alignments: Optional["RegionAlignments"] = None,
+               row_mask=None, profile: bool = False, other_res=None, other_off=None) -> "Pileup":
+        """The coverage of one batch by a RegionCigars (ks_cigars_pileup: every region is an entry; alignments= the
+        RegionAlignments they were traced from, which hold the row CSR and the starts), a HitAlignments (ks_hitalns_pileup: one
+        entry per hit row) or a FrameAlignments (ks_frames_pileup on fold.hits: side="target" only, no profile).
+        side: "query" or "target", the batch the depth is counted on; offsets: its host offsets u64[n + 1], uploaded for the
+        call.  row_mask: None or one truth value per hit row, the rows to take (a top-k selection).  profile=True also counts,
+        per residue, the classes of the residues aligned to it: other_res / other_off are then the host arrays of the other
+        batch."""
+        opts = _pileup_opts(side, profile)
+        if isinstance(aligned, FrameAlignments):
+            if side != "target":
+                raise ValueError("pileup of a FrameAlignments: side=\"query\" is not built (depth in bases on a strand); side=\"target\" only")
+            if profile:
+                raise ValueError("pileup of a FrameAlignments: profile=True is not built (the query side is a strand's bases)")
+        elif isinstance(aligned, RegionCigars):
+            if alignments is None:
+                raise TypeError("pileup of a RegionCigars needs alignments=, the RegionAlignments it was traced from")
+        elif not isinstance(aligned, HitAlignments):
+            raise TypeError("pileup takes a RegionCigars, a HitAlignments or a FrameAlignments")
+        if offsets is None:
+            raise TypeError("pileup needs offsets=, the offsets of the batch on the chosen side")
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offsets.ndim != 1 or offsets.size == 0:
+            raise ValueError("offsets must be a 1-d array of n + 1 offsets")
+        if profile and (other_res is None or other_off is None):
+            raise ValueError("profile=True needs other_res and other_off, the batch on the other side")
+        up = [offsets]
+        if row_mask is not None:
+            row_mask = np.ascontiguousarray(np.asarray(row_mask) != 0, dtype=np.uint8)
+            if row_mask.shape != (hits.count,):
+                raise ValueError(f"row_mask holds {row_mask.size} values for {hits.count} hit rows")
+            up.append(row_mask if row_mask.size else np.zeros(1, np.uint8))
+        if profile:
+            other_res = np.ascontiguousarray(other_res, dtype=np.uint8); other_off = np.ascontiguousarray(other_off, dtype=np.uint64)
+            up += [other_res if other_res.size else np.zeros(1, np.uint8), other_off]
+        with self._uploaded(*up) as d:
+            d_off, d = d[0], list(d[1:])
+            d_mask = C.c_void_p(d.pop(0)) if row_mask is not None else None
+            other = (C.c_void_p(d[0]), C.c_void_p(d[1]), len(other_off) - 1, int(other_res.size)) if profile else (None, None, 0, 0)
+            side_batch = (C.c_void_p(d_off), len(offsets) - 1, int(offsets[-1]))
+            out = C.c_void_p()
+            if isinstance(aligned, RegionCigars):
+                st = self._L.ks_cigars_pileup(self._h, aligned._h, alignments._h, hits._h, d_mask, *side_batch, *other, C.byref(opts), C.byref(out))
+            elif isinstance(aligned, HitAlignments):
+                st = self._L.ks_hitalns_pileup(self._h, aligned._h, hits._h, d_mask, *side_batch, *other, C.byref(opts), C.byref(out))
+            else:
+                st = self._L.ks_frames_pileup(self._h, aligned._h, hits._h, d_mask, *side_batch, C.byref(opts), C.byref(out))
+            self._check(st)
+        return Pileup(self, out)
+
     def residue_composition_device(self, d_res: int, d_off: int, n_seqs: int, n_res: int) -> "Composition":
         """ks_residue_composition_device from a device-resident residue batch (raw pointers: residues u8, offsets
         u64[n_seqs + 1]): per sequence the count of each of the 28 residue classes of score_regions (A..Z, '*', everything else)
@@ -1617,6 +1695,25 @@ class FrameAlignments(_Columns):
     def strings(self) -> List[str]:
         """The CIGAR of every folded row as text, e.g. "41M1N59M"; "" for a row without a chain."""
         return cigar_strings(*self.ops_to_host())
+
+
+class Pileup(_Columns):
+    """Device-resident result of Context.pileup (ks_pileup): the alignments of a hit list piled up on the residues of one
+    batch.  Per residue of the batch (batch coordinates offsets[seq] + position) depth, the pair columns that place it, and —
+    with profile=True, else an empty column — counts, 28 per residue: those columns by the class of the residue aligned to it
+    (reshape(-1, 28); the classes of Composition).  Per sequence length, n_alignments (entries with a pair column on it),
+    covered (positions with depth > 0), max_depth, depth_sum, breadth = covered / length and mean_depth = depth_sum / length
+    (NaN for an empty sequence)."""
+    _PREFIX = "pileup"
+    _COUNTS = {"n_seqs": "", "n_residues": "", "n_profile": "Entries of counts: 28 x n_residues with the profile, else 0."}
+    _TABLE = (("depth", "u4", "n_residues"), ("counts", "u4", "n_profile")) + tuple(
+        (c, {"depth_sum": "u8", "breadth": "f8", "mean_depth": "f8"}.get(c, "u4"), "n_seqs") for c in (
+            "length", "n_alignments", "covered", "max_depth", "depth_sum", "breadth", "mean_depth"))
+
+    @property
+    def depth_ptr(self) -> int:
+        """The device column depth u32[n_residues]."""
+        return int(self._ctx._L.ks_pileup_device_depth(self._h) or 0)
 
 
 class Composition(_Columns):

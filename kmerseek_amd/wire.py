@@ -901,6 +901,29 @@ def hit_chain_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[T
     return [row for *_, row in out]
 
 
+def coverage_rows(records: Sequence[Tuple[str, bytes]], pileup_host) -> List[dict]:
+    """One row per sequence of the batch a Pileup was made on (pileup_host = Pileup.to_host(), records: that batch's, in its
+    order): name, length, n_alignments (the alignments with a pair column on it), covered (positions with depth > 0), breadth
+    (covered / length), depth_sum, mean_depth (depth_sum / length) and max_depth — the breadth-of-coverage table of a read-to-
+    protein pipeline.  The two quotients are the device's f64 as text (NaN for an empty sequence).  In batch order."""
+    length, n_aln, covered, max_depth, depth_sum, breadth, mean_depth = [np.asarray(c).tolist() for c in pileup_host[2:9]]
+    if len(length) != len(records):
+        raise ValueError(f"the pileup is of {len(length)} sequences, the records are {len(records)}")
+    return [{"name": name, "length": length[s], "n_alignments": n_aln[s], "covered": covered[s], "breadth": format_f64(breadth[s]),
+             "depth_sum": depth_sum[s], "mean_depth": format_f64(mean_depth[s]), "max_depth": max_depth[s]}
+            for s, (name, _) in enumerate(records)]
+
+
+def _coverage_check(coverage, allowed, needs) -> None:
+    """coverage= of the two searches: one of `allowed`, and every (name, on) of `needs` switched on."""
+    if coverage not in allowed:
+        raise ValueError(f"coverage = {coverage!r} is none of " + ", ".join(repr(a) for a in allowed))
+    if coverage:
+        for name, on in needs:
+            if not on:
+                raise ValueError(f"coverage needs {name}=True: it is piled up from traced alignments")
+
+
 def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int, scaled: int, moltype: str,
                                 ctx: Optional[Context] = None, regions: bool = False, max_gap: int = 0,
                                 min_kmers: int = 1, score: bool = False, extend: bool = False, x_drop: int = 0,
@@ -910,7 +933,7 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 chain_max_gap: int = 0, chain_max_overlap: int = 0, chain_link_cost: int = 0,
                                 chain_skew_cost: int = 0, chain_overlap_cost: int = 0, hit_rows: bool = False,
                                 stitch: bool = False, stitch_max_fill: int = 0, evalue: bool = False, stat_params=None,
-                                max_evalue=None, mask: bool = False, mask_opts: Optional[dict] = None) -> List[dict]:
+                                max_evalue=None, mask: bool = False, mask_opts: Optional[dict] = None, coverage: Optional[str] = None):
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -940,7 +963,12 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     mask=True: both files are sketched with their low-complexity stretches left out (Context.sketch_masked; mask_opts: its
     window / k1 / k2 keywords) and the position tables are made of the same windows (Context.kmer_positions_table_masked):
     hits, pairs and regions are those of the unmasked windows.  The passes that read residues (scores, alignments) read the
-    records as they are."""
+    records as they are.
+    coverage="query" | "target" (needs cigar=True): the alignments are piled up on that file's sequences on the device
+    (Context.pileup) — the stitched ones with stitch=True, otherwise the traced alignments of the kept regions — and the call
+    returns (rows, coverage_rows): the rows as before and one `coverage_rows` row per sequence of that file.  max_evalue drops
+    rows on the host and does not touch the coverage."""
+    _coverage_check(coverage, (None, "query", "target"), (("cigar", cigar),))
     if mask_opts is not None and not mask:
         raise ValueError("mask_opts needs mask=True")
     if (stat_params is not None or max_evalue is not None) and not evalue:
@@ -995,8 +1023,14 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
         if regions:
             rg = ctx.match_regions(mp, max_gap=max_gap, min_kmers=min_kmers)
             rg_host = rg.to_host()
-            sc_host = cg_host = cu = None
+            sc_host = cg_host = cu = cov_rows = None
             kw = {}
+
+            def covered(aligned, **more):  # coverage=: the rows of the side's file
+                pu = ctx.pileup(aligned, hits, side=coverage, offsets=q_off if coverage == "query" else t_off, **more)
+                host = pu.to_host()
+                pu.free()
+                return coverage_rows(q_recs if coverage == "query" else t_recs, host)
             if evalue:
                 q_comp, t_comp = ctx.residue_composition(q_res, q_off), ctx.residue_composition(t_res, t_off)
 
@@ -1038,6 +1072,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                            skew_cost=chain_skew_cost, overlap_cost=chain_overlap_cost)
                     st = ctx.stitch_chains(ch, t_al, cg, hits, q_res, q_off, t_res, t_off, max_fill=stitch_max_fill, eqx=eqx)
                     kw["chain"], st_host = ch.to_host(), st.to_host()
+                    if coverage:
+                        cov_rows = covered(st)
                     if evalue:
                         kw["stats"] = stats_of(st, alignments=t_al)
                     for o in (st, ch, cg) + ((t_rg, t_al) if cull else ()):
@@ -1046,6 +1082,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                     t_rg, t_al = (cu.take(rg), cu.take(al)) if cull else (rg, al)  # (trace what is kept, not everything)
                     cg = ctx.trace_regions(t_rg, hits, q_res, q_off, t_res, t_off, t_al, eqx=eqx)
                     cg_host = cg.to_host()
+                    if coverage:
+                        cov_rows = covered(cg, alignments=t_al)
                     cg.free()
                     if cull:
                         t_rg.free(); t_al.free()
@@ -1063,14 +1101,15 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                 o.free()
 
             def below(rows):  # max_evalue: on the host
-                if max_evalue is None:
-                    return rows
-                col = "aln_evalue" if gapped else "region_evalue"
-                return [row for row in rows if not row[col] > max_evalue]
+                if max_evalue is not None:
+                    col = "aln_evalue" if gapped else "region_evalue"
+                    rows = [row for row in rows if not row[col] > max_evalue]
+                return (rows, cov_rows) if coverage else rows
             if stitch:
                 return below(hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"], stitched=st_host, stats=kw.get("stats")))
             if hit_rows:
-                return hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"])
+                rows = hit_chain_rows(q_recs, t_recs, qid, tid, kw["chain"])
+                return (rows, cov_rows) if coverage else rows
             if gapped:
                 if cigar:
                     return below(region_rows(q_recs, t_recs, qid, tid, rg_host, moltype, scores=sc_host, alignments=al_host, cigars=cg_host, **kw))
@@ -1154,7 +1193,7 @@ def search_translated_device(nt_fasta: str, protein_fasta: str, ksize: int, scal
                              cull_overlap: int = 100, max_gap: int = 0, min_kmers: int = 1, chain_max_gap: int = 0,
                              chain_max_overlap: int = 0, chain_link_cost: int = 0, chain_skew_cost: int = 0,
                              chain_overlap_cost: int = 0, top_k: int = 0, cigar: bool = False, eqx: bool = False, stitch: bool = False,
-                             max_fill: int = 0, frameshift_cost: int = 15) -> List[dict]:
+                             max_fill: int = 0, frameshift_cost: int = 15, coverage: bool = False):
     """Translated search to the end, on the device: the records of a nucleotide FASTA against the proteins of a protein FASTA,
     the rows of `frame_chain_rows` — per (record, strand, protein) where the gene lies in bases, in which frames, and whether a
     frameshift joins two of them.  The records are translated in six frames (Context.translate6), the frames sketched
@@ -1168,7 +1207,11 @@ def search_translated_device(nt_fasta: str, protein_fasta: str, ksize: int, scal
     stitch=True (needs gapped=True and cigar=True) traces the kept alignments (eqx: = / X for M), stitches every
     chain into ONE alignment of the strand's bases against the protein (Context.stitch_frames: max_fill, frameshift_cost), adds
     its columns to the rows (frame_chain_rows with stitched=) and ranks top_k by that alignment's score instead of the chain
-    score.  Every device object made on the way is freed."""
+    score.
+    coverage=True (needs stitch=True): the stitched alignments are piled up on the proteins on the device (Context.pileup,
+    target side; with top_k only those of the kept rows, through the row mask) and the call returns (rows, coverage_rows): one
+    `coverage_rows` row per protein.  Every device object made on the way is freed."""
+    _coverage_check(coverage, (False, True), (("stitch", stitch),))
     if stitch:
         for name, on in (("gapped", gapped), ("cigar", cigar)):
             if not on:
@@ -1224,8 +1267,16 @@ def search_translated_device(nt_fasta: str, protein_fasta: str, ksize: int, scal
         if top_k:
             best = keep(ctx.best_hits(fold.hits, k=top_k, score=stitched.row_score_ptr if stitch else chain.row_chain_score_ptr))
             keep_rows = best.best_to_host()[1]
-        return frame_chain_rows(nt_recs, t_recs, fold.hits.to_host(), fold.to_host(), chain.to_host(), keep_rows=keep_rows,
+        rows = frame_chain_rows(nt_recs, t_recs, fold.hits.to_host(), fold.to_host(), chain.to_host(), keep_rows=keep_rows,
                                 stitched=stitched.to_host() if stitch else None)
+        if not coverage:
+            return rows
+        row_mask = None
+        if keep_rows is not None:
+            row_mask = np.zeros(fold.hits.count, np.uint8)
+            row_mask[np.asarray(keep_rows, dtype=np.int64)] = 1
+        pu = keep(ctx.pileup(stitched, fold.hits, side="target", offsets=t_off, row_mask=row_mask))
+        return rows, coverage_rows(t_recs, pu.to_host())
     finally:
         for o in reversed(made):
             o.free()
