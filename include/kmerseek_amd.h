@@ -106,8 +106,10 @@ int ks_ctx_pool_stats(const ks_ctx *ctx, uint64_t *n_blocks, uint64_t *bytes_hel
  * out[0] = launches repeated because a tile look-back gave up waiting (dispatch order was not blockIdx order; the context
  *          then takes tile ids from an atomic ticket for good: out[1] = 1),
  * out[2] = batches repeated with plain tiles because a compacting tile (scaled > 1) kept more hashes than its LDS lists take,
- * out[3] = batches repeated with window-count sized outputs because they kept more hashes than the expected 1/scaled. */
-int ks_ctx_sketch_stats(const ks_ctx *ctx, uint64_t out[4]);
+ * out[3] = batches repeated with window-count sized outputs because they kept more hashes than the expected 1/scaled,
+ * out[4] = shared-tile launches whose tiles took the start of their CSR slots from the tile plan instead of a look-back across
+ *          tiles (scaled = 1, packed tiles: a sequence's slot is as long as its k-mer windows; a path, not a repeat). */
+int ks_ctx_sketch_stats(const ks_ctx *ctx, uint64_t out[5]); /* (five words — four before out[4] was added: size the array) */
 /* The same for ks_search: out[0] = searches that ran their join twice because the match list outgrew its first guess
  * (the list is sized from the previous search of the context), out[1] = searches whose row pass was repeated with
  * ticket-ordered tiles because a look-back gave up (the context then uses tickets for good), out[2] = searches whose rows

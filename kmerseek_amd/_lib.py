@@ -193,7 +193,7 @@ SIGNATURES = {
     "ks_last_error": (C.c_char_p, [_vp]),
     "ks_ctx_stream": (_vp, [_vp]),
     "ks_ctx_synchronize": (C.c_int, [_vp]),
-    "ks_ctx_sketch_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64 * 4)]),
+    "ks_ctx_sketch_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64 * 5)]),
     "ks_ctx_search_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64 * 5)]),
     "ks_ctx_fused_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64 * 4)]),
     "ks_ctx_qfilter_stats": (C.c_int, [_vp, C.POINTER(C.c_uint64 * 2)]),

@@ -47,7 +47,7 @@ struct ks_copy_engine; // ks_copy.hip: pinned staging + host copy threads for pa
     X(STAGED_H2D) X(PLAIN_COPIES) X(PAIRS_LSD) X(MSD_LDS_CAP) X(SCAN_3PASS) X(INDEX_LSD) X(JOIN_FP) X(FP_COARSEN)        \
     X(PAIR_LIMIT) X(PBITS_MAX) X(RECORD_BITS) X(ONE_CURSOR) X(JOIN_SEGS) X(JOIN_SEG_CAP) X(JOIN_SPARSE)                \
     X(NO_ROWS_HINT) X(ROWS_TICKET) X(FORCE_ROWS_TICKET_RETRY) X(FORCE_TICKET_RETRY) X(NO_PLAN) X(NO_COMPACT) X(SPAN)      \
-    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH) X(CULL_PATH) X(CHAIN_PATH) X(COMP_PATH) X(PILEUP_PATH)
+    X(NO_PACK) X(PLAN_SYNC) X(TILE_R) X(OUT_CAP) X(POOL_CAP) X(THROW) X(QCAP) X(LOOKBACK_SKIP) X(TILE_LOOKBACK) X(SYNC_API) X(POSTINGS12) X(POSTINGS10) X(NO_DEFER) X(BUCKET) X(JOIN_SPLIT) X(SUBSHIFT) X(MATCHPOS_ROW_BITS) X(SIGNIF_WAVE_ROWS) X(BEST_PATH) X(REGIONS_ROW_BITS) X(QFILTER) X(QFILTER_OCC) X(CLUSTER_PATH) X(GATHER_PATH) X(GREEDY_PATH) X(UNION_PATH) X(AGG_CAP) X(ROWS_PATH) X(CULL_PATH) X(CHAIN_PATH) X(COMP_PATH) X(PILEUP_PATH)
 enum ks_dbg_id {
 #define KS_DBG_ENUM(n) KS_DBG_##n,
     KS_DBG_LIST(KS_DBG_ENUM)
@@ -92,6 +92,7 @@ struct ks_ctx {
     // how often a sketch batch had to be repeated: look-back gave up (-> ticket ids from then on), a compacting tile
     // overflowed its LDS lists (-> plain tiles for that batch), bounded outputs too small (-> window-count sized)
     u64 sketch_ticket_fallbacks = 0, sketch_compact_fallbacks = 0, sketch_cap_fallbacks = 0;
+    u64 sketch_planned_slots = 0; // shared-tile launches whose tiles took their CSR base from the plan (no look-back): a path, not a repeat
     bool rows_use_ticket = false; u64 rows_ticket_fallbacks = 0; // k_pair_rows_fused: dispatch-order tile ids until a look-back gives up
     u64 fused_deferred = 0, fused_redos = 0; // ks_sketch_search_device: calls that folded the sketch wait into the first wait of the search / were repeated plainly
     u64 fused_aggregated = 0;                // ... whose rows the aggregate pass made (agg_used below rose)

@@ -209,11 +209,12 @@ extern "C" int ks_ctx_pool_stats(const ks_ctx *ctx, uint64_t *n_blocks, uint64_t
     });
 }
 
-extern "C" int ks_ctx_sketch_stats(const ks_ctx *ctx, uint64_t out[4]) {
+extern "C" int ks_ctx_sketch_stats(const ks_ctx *ctx, uint64_t out[5]) {
     return ks_guard((ks_ctx *)ctx, [&]() -> int {
     if (!ctx || !out) return KS_ERR_INVALID_ARG;
     out[0] = ctx->sketch_ticket_fallbacks; out[1] = ctx->sketch_use_ticket ? 1 : 0;
     out[2] = ctx->sketch_compact_fallbacks; out[3] = ctx->sketch_cap_fallbacks;
+    out[4] = ctx->sketch_planned_slots;
     return KS_OK;
     });
 }

@@ -21,7 +21,9 @@
 //     repeats are counted on the way: the tile's distinct count is known before anything is read back.
 //   * Tiles with repeats (or with postings to emit) read the sorted run back position-major: representative flags,
 //     abundances and distinct ranks from bitmaps; the others write their sorted run as it stands.  A decoupled
-//     look-back over the tiles' distinct counts gives the tile its place in the final CSR: one coalesced stream out.
+//     look-back over the tiles' kept counts gives the tile its place in the final CSR: one coalesced stream out.  (Packed
+//     tiles without a hash threshold — scaled = 1 — need none: a sequence's slot is as long as its windows, and the plan
+//     pass hands every tile the windows before it, sk_args::tile_wbase.)
 //   * A sequence that starts inside a tile's residue range but does not END inside the tile's LDS window (at most
 //     one per tile, the last) is deferred: if it fits a tile on its own ("medium") it gets one in a second launch of
 //     the same kernel; longer ones take the same algorithm with its arrays in a global scratch slab (k_sketch_long,
@@ -132,14 +134,15 @@ KS_DEV u32 sk_digit(u64 h, u32 K, u32 kshift, u32 mask) {
 // (one memset, one device -> host copy per read-back instead of one per word: each is a dispatch of its own on this runtime).
 // The posting cursors and the tiles' status words sit right behind it, in the same allocation.
 enum : u32 {
-    SK_CTL_WINDOWS = 0, SK_CTL_MAX_LEN = 1, // k-mer windows of the batch, longest sequence (k_seq_stats)
+    SK_CTL_WINDOWS = 0, SK_CTL_MAX_LEN = 1, // k-mer windows of the batch, longest sequence (k_seq_stats; a packed plan: k_pack_walk / k_pack_fill)
     SK_CTL_N_PK_LONG = 2,                   // sequences longer than PK_MAX_LEN (the long ones of a packed plan)
     SK_CTL_MED = 4, SK_CTL_LONG = 4 + SK_NR, // + c: medium (deferred, fit a tile of their own) / long (deferred, do not) sequences under stride c
     SK_CTL_TICKET = 20,   // u32 pair: tile ticket | status bits (SK_ST_*)
     SK_CTL_CLS = 21,      // u32 pair: medium | long sequences found (k_find_long)
     SK_CTL_PK_TILES = 22, // u32: tiles of a packed plan
-    SK_CTL_TOTAL = 23,    // kept hashes (= CSR slots)
+    SK_CTL_TOTAL = 23,    // CSR slots: kept hashes, or k-mer windows where the slots come from the plan (sk_args::tile_wbase)
     SK_CTL_DROPS = 24,    // kept hashes that repeat an earlier one of their sequence (slots the CSR leaves empty): shared tiles
+                          //     (+ with slots from the plan the windows nobody kept: hash 0)
     SK_CTL_LB_ROUNDS = 25, // look-back rounds (SK_LB_STATS builds only)
     SK_CTL_DROPS_DEF = 26, // ... and the same of the medium / long sequences (their launches precede the ticket repeat, which
                            //     clears only the shared tiles' word)
@@ -191,9 +194,12 @@ KS_DEV void sk_load_seq(sk_seq &q, const sk_args &A, const sk_bounds &B, u32 s_e
 }
 
 // bookkeeping for the window at local position p: which sequence, is it a real window, bucket + arrival slot
-KS_DEV u32 sk_place_window(const sk_args &A, u32 p, u64 h, sk_seq &q, const sk_bounds &B, u32 s_end, u32 *cnt) {
+// (*zero: the window is a real one whose hash is 0 — kept by nobody, but it has a place in a slot that is as long as the windows)
+KS_DEV u32 sk_place_window(const sk_args &A, u32 p, u64 h, sk_seq &q, const sk_bounds &B, u32 s_end, u32 *cnt, bool *zero) {
     while (q.s < s_end && p >= q.le) { q.s++; sk_load_seq(q, A, B, s_end); }
-    const bool keep = q.ok && p >= q.ls && p + A.k <= q.le && h != 0 && h <= A.max_hash;
+    const bool real = q.ok && p >= q.ls && p + A.k <= q.le;
+    const bool keep = real && h != 0 && h <= A.max_hash;
+    *zero = real && h == 0;
     u32 bo = 0xffffffffu;
     if (keep) {
         const u32 b = q.ls + __umulhi((u32)(h >> 32), q.mul);
@@ -219,62 +225,161 @@ KS_DEV u32 sk_place_window(const sk_args &A, u32 p, u64 h, sk_seq &q, const sk_b
 // (16-byte aligned) start of the first.  ~95 % of the positions carry windows, ~14 % fewer tiles, and no sequence is
 // ever deferred for its position: only those longer than PK_MAX_LEN go to the global-slab path (as the deferred tail of
 // the tile they follow).  The greedy cut is sequential, so it runs per chunk of PK_CHUNK sequences (a tile never spans
-// chunks: one short tile per 1024 sequences): one wave per chunk walks its offsets in LDS with 64-ary searches;
-// k_pack_fill then lays the chunks' tiles out densely.
+// chunks: one short tile per 1024 sequences).  One workgroup per chunk (k_pack_walk) stages the chunk's offsets in LDS with
+// every load in flight at once; every sequence then finds where a tile that STARTED at it would end (a binary search, all
+// sequences in parallel), and one thread follows those links from the chunk's first sequence: a chain of one LDS read per
+// tile.  The same offsets give what else the launches want to know before they start: the batch's statistics words
+// (windows, longest sequence, long sequences: k_seq_stats is not launched for a packed plan) and, per tile, the k-mer
+// windows of all sequences before its first (tile_wbase: at scaled = 1 a sequence's CSR slot is as long as its windows, so
+// this is where the tile's slots begin, and no tile has to wait for its predecessors to learn it).
+// k_pack_fill then lays the chunks' tiles out densely and adds the chunks' prefixes.
 // ---------------------------------------------------------------------------------------------
 #define PK_CHUNK 1024
+#define PK_THREADS 256
 #define PK_MAX_LEN (SK_MED_MAX - 16) // fits the window wherever its first residue falls inside the aligned 16 bytes
 
-__global__ __launch_bounds__(64) void k_pack_walk(const u64 *offs, u32 n_seqs, u32 chunk /* <= PK_CHUNK sequences per chunk */,
-                                                  u32 *chunk_tiles /* [n_seqs]: tile starts of chunk c from c * chunk */, u32 *chunk_cnt) {
-    __shared__ u64 lo_s[PK_CHUNK + 1];
-    const u32 lane = threadIdx.x;
-    const u32 c0 = blockIdx.x * chunk;
-    const u32 n = (n_seqs - c0) < chunk ? (n_seqs - c0) : chunk; // sequences of this chunk
-    for (u32 i = lane; i <= n; i += 64) lo_s[i] = offs[c0 + i];
-    __builtin_amdgcn_wave_barrier();
-    u32 s = 0, nt = 0;
-    while (s < n) { // (uniform: every lane walks the same chain)
-        const u64 limit = (lo_s[s] & ~15ULL) + SK_MED_MAX; // a sequence fits if it ENDS at or before this residue offset
-        // largest e in [s, n] with lo_s[e] <= limit (lo_s[s] always is): 64-ary search
-        u32 lo = s, hi = n + 1;
-        while (hi - lo > 1) {
-            const u32 step = (hi - lo + 63) / 64;
-            const u32 idx = lo + (lane + 1) * step;
-            const bool ok = idx < hi && lo_s[idx] <= limit;
-            const u64 m = __ballot(ok);
-            const u32 good = m == ~0ULL ? 64u : (u32)__builtin_ctzll(~m); // leading run of lanes that still fit
-            const u32 nlo = lo + good * step;
-            const u32 nhi = lo + (good + 1) * step;
-            lo = nlo < hi ? nlo : hi - 1;
-            hi = nhi < hi ? nhi : hi;
-        }
-        u32 e = lo; // sequences [s, e) fit
-        if (e == s) e = s + 1;                           // a long sequence on its own (it is the tile's deferred tail)
-        else if (e < n && lo_s[e + 1] - lo_s[e] > PK_MAX_LEN) e++; // the long sequence that follows rides along as the tail
-        if (lane == 0) chunk_tiles[c0 + nt] = c0 + s;
-        nt++;
-        s = e;
+// exclusive scan of a 64-bit value over the PK_THREADS threads (one barrier; smem: PK_THREADS / 64 words, the caller's again
+// behind its next barrier)
+KS_DEV u64 pk_block_excl_scan64(u64 v, u64 *smem, u64 *total) {
+    const u32 lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 incl = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u64 o = (u64)__shfl_up((unsigned long long)incl, d, 64);
+        if (lane >= (u32)d) incl += o;
     }
-    if (lane == 0) chunk_cnt[blockIdx.x] = nt;
+    if (lane == 63) smem[wave] = incl;
+    __syncthreads();
+    u64 base = 0, tot = 0;
+#pragma unroll
+    for (u32 w = 0; w < PK_THREADS / 64; w++) {
+        const u64 x = smem[w];
+        base += w < wave ? x : 0;
+        tot += x;
+    }
+    *total = tot;
+    return base + incl - v;
 }
 
-// dense plan: tile_first[t] / tile_g0[t] for the tiles of all chunks in order; tile_first[n_tiles] = n_seqs; *n_tiles_out
-__global__ __launch_bounds__(256) void k_pack_fill(const u64 *offs, u32 n_seqs, u32 chunk, const u32 *chunk_tiles, const u32 *chunk_cnt, u32 n_chunks,
-                                                   u32 *tile_first, u64 *tile_g0, u32 *n_tiles_out) {
+__global__ __launch_bounds__(PK_THREADS) void k_pack_walk(const u64 *offs, u32 n_seqs, u32 chunk /* <= PK_CHUNK sequences per chunk */, u32 k,
+                                                          u32 *chunk_tiles /* [n_seqs]: tile starts of chunk c from c * chunk */,
+                                                          u64 *chunk_wb /* [n_seqs]: ... and the chunk's windows before each */,
+                                                          u32 *chunk_cnt, u64 *chunk_win /* [n_chunks]: tiles / windows of the chunk */,
+                                                          u64 *ctl /* SK_CTL_MAX_LEN, SK_CTL_N_PK_LONG */) {
+    static_assert(PK_CHUNK % PK_THREADS == 0 && PK_CHUNK <= 0xffff, "sequences per thread; 16-bit links");
+    constexpr u32 PER = PK_CHUNK / PK_THREADS;
+    __shared__ u64 lo_s[PK_CHUNK + 1];
+    __shared__ u64 wp_s[PK_CHUNK]; // windows of sequence i, then of the chunk's sequences before i
+    __shared__ u16 nxt_s[PK_CHUNK]; // where a tile that starts at sequence i ends
+    __shared__ u16 tl_s[PK_CHUNK];  // the chunk's tile starts
+    __shared__ u64 scan_s[PK_THREADS / 64];
+    __shared__ u64 mx_s[PK_THREADS / 64];
+    __shared__ u32 npk_s[PK_THREADS / 64];
+    __shared__ u32 nt_s;
+    const u32 tid = threadIdx.x;
+    const u32 c0 = blockIdx.x * chunk;
+    const u32 n = (n_seqs - c0) < chunk ? (n_seqs - c0) : chunk; // sequences of this chunk
+    {
+        u64 v[PER];
+#pragma unroll
+        for (u32 j = 0; j < PER; j++) { // (all requested before the first is stored)
+            const u32 i = tid + j * PK_THREADS;
+            v[j] = i <= n ? offs[c0 + i] : 0;
+        }
+        const u64 vn = tid == 0 ? offs[c0 + n] : 0; // (entry PK_CHUNK of a full chunk)
+#pragma unroll
+        for (u32 j = 0; j < PER; j++) {
+            const u32 i = tid + j * PK_THREADS;
+            if (i <= n) lo_s[i] = v[j];
+        }
+        if (tid == 0) lo_s[n] = vn;
+    }
+    __syncthreads();
+    // every sequence: its windows, the statistics, and the end of the tile that would start at it
+    u64 mx = 0;
+    u32 npk = 0;
+#pragma unroll
+    for (u32 j = 0; j < PER; j++) {
+        const u32 i = tid + j * PK_THREADS;
+        u64 len = 0;
+        if (i < n) {
+            const u64 st = lo_s[i];
+            len = lo_s[i + 1] - st;
+            wp_s[i] = len >= k ? len - k + 1 : 0;
+            const u64 limit = (st & ~15ULL) + SK_MED_MAX; // a sequence fits if it ENDS at or before this residue offset
+            u32 lo = i, hi = n + 1; // largest e in [i, n] with lo_s[e] <= limit (lo_s[i] always is)
+            while (hi - lo > 1) {
+                const u32 mid = (lo + hi) >> 1;
+                if (lo_s[mid] <= limit) lo = mid; else hi = mid;
+            }
+            u32 e = lo; // sequences [i, e) fit
+            if (e == i) e = i + 1;                                     // a long sequence on its own (it is the tile's deferred tail)
+            else if (e < n && lo_s[e + 1] - lo_s[e] > PK_MAX_LEN) e++; // the long sequence that follows rides along as the tail
+            nxt_s[i] = (u16)e;
+        }
+        mx = len > mx ? len : mx;
+        npk += (u32)__popcll(__ballot(len > PK_MAX_LEN)); // (per wave)
+    }
+    mx = ks_wave_max64(mx);
+    if ((tid & 63u) == 0) { mx_s[tid >> 6] = mx; npk_s[tid >> 6] = npk; }
+    __syncthreads();
+    if (tid == 0) { // the chain: tile after tile from the chunk's first sequence (uniform work of one thread; ~1 LDS read per tile)
+        u32 s = 0, nt = 0;
+        while (s < n) { tl_s[nt++] = (u16)s; s = nxt_s[s]; }
+        nt_s = nt;
+    }
+    if (tid == 64) { // (another wave: beside the chain) one set of device atomics per workgroup
+        u64 m = 0;
+        u32 c = 0;
+        for (u32 w = 0; w < PK_THREADS / 64; w++) { m = mx_s[w] > m ? mx_s[w] : m; c += npk_s[w]; }
+        if (m) atomicMax((unsigned long long *)&ctl[SK_CTL_MAX_LEN], (unsigned long long)m);
+        if (c) atomicAdd((unsigned long long *)&ctl[SK_CTL_N_PK_LONG], (unsigned long long)c);
+    }
+    // windows before every sequence of the chunk: thread t scans sequences [PER t, PER t + PER)
+    u64 w[PER], part = 0;
+#pragma unroll
+    for (u32 j = 0; j < PER; j++) { w[j] = tid * PER + j < n ? wp_s[tid * PER + j] : 0; part += w[j]; }
+    u64 total;
+    u64 ex = pk_block_excl_scan64(part, scan_s, &total);
+#pragma unroll
+    for (u32 j = 0; j < PER; j++) { if (tid * PER + j < n) wp_s[tid * PER + j] = ex; ex += w[j]; }
+    __syncthreads(); // (the prefixes and the chain's tile list)
+    const u32 nt = nt_s;
+    for (u32 i = tid; i < nt; i += PK_THREADS) {
+        const u32 s = tl_s[i];
+        chunk_tiles[c0 + i] = c0 + s;
+        chunk_wb[c0 + i] = wp_s[s];
+    }
+    if (tid == 0) { chunk_cnt[blockIdx.x] = nt; chunk_win[blockIdx.x] = total; }
+}
+
+// dense plan: tile_first[t] / tile_g0[t] / tile_wbase[t] for the tiles of all chunks in order; tile_first[n_tiles] = n_seqs,
+// tile_wbase[n_tiles] = ctl[SK_CTL_WINDOWS] = the batch's windows; *n_tiles_out
+__global__ __launch_bounds__(256) void k_pack_fill(const u64 *offs, u32 n_seqs, u32 chunk, const u32 *chunk_tiles, const u64 *chunk_wb,
+                                                   const u32 *chunk_cnt, const u64 *chunk_win, u32 n_chunks, u32 *tile_first, u64 *tile_g0,
+                                                   u64 *tile_wbase, u32 *n_tiles_out, u64 *ctl) {
     __shared__ u32 scan_smem[256 / 64 + 1];
+    __shared__ u64 win_s[256 / 64];
     u32 part = 0;
-    for (u32 c = threadIdx.x; c < blockIdx.x; c += 256) part += chunk_cnt[c];
+    u64 wpart = 0;
+    for (u32 c = threadIdx.x; c < blockIdx.x; c += 256) { part += chunk_cnt[c]; wpart += chunk_win[c]; }
+    wpart = ks_wave_sum64(wpart);
+    if ((threadIdx.x & 63u) == 0) win_s[threadIdx.x >> 6] = wpart;
     u32 total;
     (void)ks_block_excl_scan(part, scan_smem, &total); // total = tiles of the chunks before this one
+    u64 wbase = 0; // ... and their windows
+    for (u32 w = 0; w < 256 / 64; w++) wbase += win_s[w];
     const u32 base = total, mine = chunk_cnt[blockIdx.x];
     for (u32 i = threadIdx.x; i < mine; i += 256) {
         const u32 sf = chunk_tiles[blockIdx.x * chunk + i];
         tile_first[base + i] = sf;
         tile_g0[base + i] = offs[sf] & ~15ULL;
+        tile_wbase[base + i] = wbase + chunk_wb[blockIdx.x * chunk + i];
     }
     if (blockIdx.x == n_chunks - 1 && threadIdx.x == 0) {
         tile_first[base + mine] = n_seqs;
+        tile_wbase[base + mine] = wbase + chunk_win[blockIdx.x];
+        ctl[SK_CTL_WINDOWS] = wbase + chunk_win[blockIdx.x];
         *n_tiles_out = base + mine;
     }
 }
@@ -419,13 +524,15 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
     tile = (u32)__builtin_amdgcn_readfirstlane((int)tile); // (uniform: scalar loads)
     u64 g0p = 0;
     if (packed) g0p = A.tile_g0[tile];
+    // (uniform) the tile's CSR slots start where the plan says: no aggregate to publish, no predecessor to wait for
+    const bool planned = MODE == 0 && !CMP && A.tile_wbase != nullptr;
     u32 s_first, s_end;
     if (MODE == 1) { s_first = A.seq_list[tile]; s_end = s_first + 1; }
     else { s_first = A.seq_list[tile]; s_end = A.seq_list[tile + 1]; }
     if (!A.upper_only && tid < 256) lut_s[tid] = (u8)lut_v;
     if (MODE == 0 && tid < NCH) rv = sk_load16(A.res, A.n_res, (packed ? g0p : (u64)tile * A.R) + (u64)tid * 16); // R is a multiple of 16
     if (s_first >= s_end) {
-        if (MODE == 0 && tid == 0)
+        if (MODE == 0 && tid == 0 && !planned)
             __hip_atomic_store(&A.tile_status[tile], KS_LB_AGG | 0ULL, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         return;
     }
@@ -477,6 +584,17 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
 #endif
     u32 rkp[SK_E / 2] = {0, 0, 0, 0}; // ranks inside (tile, digit) of my windows, 16 bits each
     u32 kept_mask = 0, srel_one = 0;  // one-run threads (k >= SK_E): which of my windows were kept; my sequence (relative, capped)
+    // Slots from the plan are as long as a sequence's WINDOWS, and a window whose hash is 0 (one in 2^64) is kept by nobody:
+    // the slot of its sequence is one entry longer than its fill, and everything behind it in the tile lies one entry further
+    // on than its kept rank says — which is what a deferred sequence does to its tile, so it is noted the same way (ext_*; ext_d
+    // = 1 until phase 6: the gap opens where the NEXT sequence starts).  It also counts as a drop: n_hashes = slots - drops.
+    // More of them than the list holds, and the launch gives up like a look-back that timed out.
+    auto note_zero = [&](u32 s, u32 n) {
+        const u32 e = atomicAdd(&ext_n, 1u);
+        if (e < 4) { ext_seq[e] = s; ext_cnt[e] = n; ext_d[e] = 1; }
+        else atomicOr(&A.ticket[1], SK_ST_LOOKBACK);
+        atomicAdd((unsigned long long *)A.drops_out, (unsigned long long)n);
+    };
     if (CMP) {
         // ---- phase 2, compacting variant: hash sub-tile by sub-tile, keep the windows under the threshold in an LDS list
         // (hash in tmp, its sequence in the counter words, which are not counting yet), then bucket the compacted list
@@ -568,10 +686,12 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
             // counter word instead of sitting out in a branch of its own (which put a wait behind every atomic: eight LDS round
             // trips in a row per thread, sixteen with the posting ranks below).
             u32 bb[SK_E], rt[SK_E];
-            u32 kpm = 0;
+            u32 kpm = 0, zm = 0;
 #pragma unroll
             for (int i = 0; i < SK_E; i++) {
-                bool keep = (q0 + (u32)i - q.ls) < q.nw && h[i] != 0;
+                const bool real = (q0 + (u32)i - q.ls) < q.nw;
+                bool keep = real && h[i] != 0;
+                zm |= (real && !keep) ? (1u << i) : 0u;
                 if (thr) keep = keep && h[i] <= A.max_hash;
                 kpm |= keep ? (1u << i) : 0u;
                 const u32 b = q.ls + __umulhi((u32)(h[i] >> 32), q.mul);
@@ -584,9 +704,20 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
             for (int i = 0; i < SK_E; i++)
                 bo[i] = ((kpm >> i) & 1u) ? (s24 | (bb[i] << 12) | __builtin_amdgcn_ubfe(rt[i], bb[i] << 4, 16u)) : 0xffffffffu;
             kept_mask = kpm; srel_one = s24 >> 24;
+            if (planned && zm) note_zero(q.s, (u32)__popc(zm));
         } else {
+            u32 zm = 0;
 #pragma unroll
-            for (int i = 0; i < SK_E; i++) bo[i] = sk_place_window(A, q0 + i, h[i], q, B, s_end, cnt);
+            for (int i = 0; i < SK_E; i++) {
+                bool zero;
+                bo[i] = sk_place_window(A, q0 + i, h[i], q, B, s_end, cnt, &zero);
+                zm |= zero ? (1u << i) : 0u;
+            }
+            while (planned && zm) { // (the sequence of each such window is looked up again: nothing of this rides in the loop above)
+                const u32 i = (u32)__builtin_ctz(zm);
+                zm &= zm - 1u;
+                note_zero(sk_seq_beyond(s_first, s_end, q0 + i, [&](u32 s) { return B.at(s + 1); }), 1u);
+            }
         }
         // Postings (query side): a kept hash's rank inside its partition digit is one more LDS atomic — taken HERE, while the
         // vector ALU is what the workgroup waits for and the LDS idles.  A tile without repeats (nearly all) then emits its
@@ -621,7 +752,15 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
             const u32 ls = B.at(s), le = B.at(s + 1);
             if (le > A.le_cap || le - ls > A.max_len_tile) {
                 const u32 e = atomicAdd(&ext_n, 1u);
-                if (e < 4) { ext_seq[e] = s; ext_cnt[e] = A.kept[s]; ext_d[e] = 0; }
+                u32 c = A.kept[s];
+                if (planned) { // its slot is as long as its windows too; what it did not keep of them (zero hashes) is a drop
+                    const u64 len = A.offs[s + 1] - A.offs[s]; // (< 2^32: checked by the host)
+                    const u32 nw = len >= A.k ? (u32)(len - A.k + 1) : 0u;
+                    if (nw != c) atomicAdd((unsigned long long *)A.drops_out, (unsigned long long)(nw - c));
+                    c = nw;
+                }
+                if (e < 4) { ext_seq[e] = s; ext_cnt[e] = c; ext_d[e] = 0; }
+                else if (planned) atomicOr(&A.ticket[1], SK_ST_LOOKBACK);
             }
         }
     }
@@ -700,8 +839,16 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
     const u32 ne = MODE == 0 ? (ext_n < 4 ? ext_n : 4) : 0;
     u64 agg = n_kept;
     for (u32 e = 0; e < ne; e++) agg += ext_cnt[e];
-    if (MODE == 0 && tid == 0 && tile != A.debug_skip_tile)
+    if (MODE == 0 && !planned && tid == 0 && tile != A.debug_skip_tile)
         __hip_atomic_store(&A.tile_status[tile], (tile == 0 ? KS_LB_PRE : KS_LB_AGG) | agg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // (slots from the plan: the tile's base is requested HERE, where the look-back publishes, and first used behind the sort.
+    // Asked for in the prologue with the other plan entries it sat in two registers through the hash phase, which has none to
+    // spare — the k = 7 kernel spilled —; behind the first stores the compiler loads it per lane, hence the readfirstlane.)
+    u64 wbase = 0;
+    if (planned) {
+        const u64 wb = __builtin_nontemporal_load(&A.tile_wbase[tile]);
+        wbase = ((u64)(u32)__builtin_amdgcn_readfirstlane((int)(u32)(wb >> 32)) << 32) | (u32)__builtin_amdgcn_readfirstlane((int)(u32)wb);
+    }
 
     SK_STAMP_AT(3);
     // ---- phase 4: scatter kept hashes into bucket order; sorted position at which every sequence's run starts
@@ -1080,7 +1227,11 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
         if (posts) post_reserve();
         if (B.in_lds && any_dup) // distinct rank at every sequence start (dseq keeps the kept ranks: they place the slots)
             for (u32 i = tid; i <= ns; i += SK_THREADS) dsd[i] = (u16)drank(dseq[i]);
-        if (tid < ne) ext_d[tid] = B.in_lds ? (u32)dseq[ext_seq[tid] - s_first] : bstart(B.at(ext_seq[tid])); // kept rank at which the deferred sequence's slot opens
+        if (tid < ne) { // kept rank at which the deferred sequence's slot opens (a zero hash's gap: where the next sequence starts)
+            const u32 sx = ext_seq[tid] + ext_d[tid];
+            const u32 lx = B.in_lds ? 0u : B.at(sx);
+            ext_d[tid] = B.in_lds ? (u32)dseq[sx - s_first] : bstart(lx < SK_TILE ? lx : SK_TILE);
+        }
         if (B.in_lds && any_dup) stage_reps(); // (bucket starts are dead: dseq holds what the CSR needs; phase 6 has read the sorted run)
         SK_STAMP_AT(6);
         // ---- step 2: the predecessors' aggregates are summed back to the nearest inclusive prefix, SK_THREADS predecessors at a
@@ -1093,6 +1244,10 @@ KS_DEV void sk_tile_body(const sk_args &A, const u32 tile_in) {
         excl = (u64)tile * 3600u;
         if (false) {
 #else
+        if (planned) { // (uniform) the plan knows where the tile's slots begin
+            excl = wbase;
+            __syncthreads(); // (orders everything placed above)
+        } else
         if (tile > 0) { // (uniform)
 #endif
             const u32 lane = tid & 63u, wave = tid >> 6;
@@ -1327,6 +1482,8 @@ struct sk_plan {
     bool planned;  // the caller gave max_seq_len
     bool compact;  // compacting variant: bucket space = positions / c_div, span = residues per shared tile (see k_sketch_tiles<0, 1>)
     bool packed;   // packed tiles (whole sequences packed greedily into each tile, see k_pack_walk) for the plain variant
+    bool slots;    // ... whose tiles take the start of their CSR slots from the plan (no hash threshold: a sequence's slot is as long as
+                   // its windows, see sk_args::tile_wbase) instead of a look-back across tiles
     u32 c_div, span, pk_chunk, pk_chunks;
     sk_cands cand;
     // Packed plan without the round trip: with every sequence <= L = max_seq_len <= PK_MAX_LEN a tile is closed by a sequence
@@ -1364,6 +1521,9 @@ static void sk_plan_shape(const ks_ctx *ctx, const sk_call &C, int variant, sk_p
         }
     }
     P->packed = !P->compact && !ks_dbg(ctx, KS_DBG_NO_PACK);
+    // (the knobs that exercise the look-back select it, KS_DEBUG_TILE_LOOKBACK = 1 forces it: A/B runs, tests)
+    P->slots = P->packed && ks_max_hash(p->scaled) == ~0ULL && !ks_dbg(ctx, KS_DBG_TILE_LOOKBACK) && !ks_dbg(ctx, KS_DBG_LOOKBACK_SKIP) &&
+               !ks_dbg(ctx, KS_DBG_FORCE_TICKET_RETRY);
     // (the walk of a chunk is a serial chain, ~0.5 us per tile: small batches take shorter chunks — more waves, shorter
     // chains — at the price of one partly filled tile per chunk)
     P->pk_chunk = C.n_seqs >= 262144 ? PK_CHUNK : (C.n_seqs >= 32768 ? 256u : 64u);
@@ -1473,7 +1633,7 @@ static void sk_plan_outputs(const ks_ctx *ctx, const sk_call &C, int variant, in
 struct sk_bufs {
     u32 *ticket, *d_ntiles; // in the control block (as is def.n_cls)
     u32 *tile_first;
-    u64 *tile_g0;
+    u64 *tile_g0, *tile_wbase;
     ks_deferred def;
 };
 
@@ -1482,23 +1642,34 @@ static int sk_launch_stats(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
     const size_t ctl_words = (size_t)SK_CTL_TILE_STATUS + P.tiles_hint + 1;
     KS_TRY(ks_alloc(ctx, &S->ctl_block, ctl_words));
     u64 *const ctl = S->ctl_block;
-    KS_HIP(ctx, hipMemsetAsync(ctl, 0, ctl_words * sizeof(u64), ctx->stream));
+    // (tiles that take their base from the plan publish nothing: their status words stay as they are, and the launch that
+    // falls back to the look-back clears them itself, see sk_launch_tiles)
+    KS_HIP(ctx, hipMemsetAsync(ctl, 0, (P.slots ? (size_t)SK_CTL_TILE_STATUS : ctl_words) * sizeof(u64), ctx->stream));
     B.ticket = (u32 *)(ctl + SK_CTL_TICKET); B.def.n_cls = (u32 *)(ctl + SK_CTL_CLS); B.d_ntiles = (u32 *)(ctl + SK_CTL_PK_TILES);
-    u32 g = (C.n_seqs + 1023) / 1024;
-    if (g > 512) g = 512;
-    KS_LAUNCH(ctx, "seq_stats", k_seq_stats, g, 256, C.d_offs, C.n_seqs, C.p->ksize, P.span, P.cand, ctl);
-    if (P.packed) {
-        // The tile count of a packed plan is only known on the device and sizes the launch: it is read back with the
-        // statistics (one round trip whether or not the caller gave max_seq_len), unless pk_bound stands in.
+    if (!P.packed) {
+        u32 g = (C.n_seqs + 1023) / 1024;
+        if (g > 512) g = 512;
+        KS_LAUNCH(ctx, "seq_stats", k_seq_stats, g, 256, C.d_offs, C.n_seqs, C.p->ksize, P.span, P.cand, ctl);
+    } else {
+        // The plan pass also leaves the statistics words a packed plan reads (windows, longest sequence, long sequences; the
+        // deferral counts per stride are only read by the other plans).  The tile count is only known on the device and sizes
+        // the launch: it is read back with the statistics (one round trip whether or not the caller gave max_seq_len),
+        // unless pk_bound stands in.
         u32 *pk_tiles = nullptr, *pk_cnt = nullptr;
+        u64 *pk_wb = nullptr, *pk_win = nullptr;
         KS_TRY(sc.alloc(&pk_tiles, (size_t)C.n_seqs));
+        KS_TRY(sc.alloc(&pk_wb, (size_t)C.n_seqs));
         KS_TRY(sc.alloc(&pk_cnt, (size_t)P.pk_chunks));
+        KS_TRY(sc.alloc(&pk_win, (size_t)P.pk_chunks));
         KS_TRY(sc.alloc(&B.tile_first, (size_t)C.n_seqs + 1)); // (a tile holds at least one sequence)
         KS_TRY(sc.alloc(&B.tile_g0, (size_t)C.n_seqs + 1));
+        KS_TRY(sc.alloc(&B.tile_wbase, (size_t)C.n_seqs + 1));
         ks_timer_begin(ctx, "tile_plan");
-        hipLaunchKernelGGL(k_pack_walk, dim3(P.pk_chunks), dim3(64), 0, ctx->stream, C.d_offs, C.n_seqs, P.pk_chunk, pk_tiles, pk_cnt);
+        hipLaunchKernelGGL(k_pack_walk, dim3(P.pk_chunks), dim3(PK_THREADS), 0, ctx->stream, C.d_offs, C.n_seqs, P.pk_chunk, C.p->ksize, pk_tiles,
+                           pk_wb, pk_cnt, pk_win, ctl);
         hipLaunchKernelGGL(k_pack_fill, dim3(P.pk_chunks), dim3(256), 0, ctx->stream, C.d_offs, C.n_seqs, P.pk_chunk, (const u32 *)pk_tiles,
-                           (const u32 *)pk_cnt, P.pk_chunks, B.tile_first, B.tile_g0, B.d_ntiles);
+                           (const u64 *)pk_wb, (const u32 *)pk_cnt, (const u64 *)pk_win, P.pk_chunks, B.tile_first, B.tile_g0, B.tile_wbase,
+                           B.d_ntiles, ctl);
         ks_timer_end(ctx);
         KS_HIP(ctx, hipGetLastError());
     }
@@ -1541,7 +1712,7 @@ static int sk_launch_tiles(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
     unsigned long long *tile_status = (unsigned long long *)(S->ctl_block + SK_CTL_TILE_STATUS); // (zeroed with the control block)
     if (n_tiles > P.tiles_hint) {
         KS_TRY(sc.alloc(&tile_status, (size_t)n_tiles + 1));
-        KS_HIP(ctx, hipMemsetAsync(tile_status, 0, (size_t)n_tiles * sizeof(unsigned long long), ctx->stream));
+        if (!P.slots) KS_HIP(ctx, hipMemsetAsync(tile_status, 0, (size_t)n_tiles * sizeof(unsigned long long), ctx->stream));
     }
     if (!P.packed) {
         KS_TRY(sc.alloc(&B.tile_first, (size_t)n_tiles + 1));
@@ -1562,12 +1733,18 @@ static int sk_launch_tiles(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
     }
     const u64 *rb = ctx->h_pin + KS_PIN_SKETCH_SYNC;
     for (int attempt = 0; attempt < 2; attempt++) {
-        A.use_ticket = (ctx->sketch_use_ticket || attempt == 1) ? 1u : 0u;
+        // Slots from the plan: the first attempt needs no look-back, hence neither dispatch order nor tickets.  (Its only way to
+        // give up: more zero hashes in one tile than it can note, see sk_tile_body; the repeat is an ordinary look-back launch.)
+        const bool slots = P.slots && attempt == 0;
+        A.tile_wbase = slots ? B.tile_wbase : nullptr;
+        A.use_ticket = (!slots && (ctx->sketch_use_ticket || attempt == 1)) ? 1u : 0u;
         A.debug_skip_tile = 0xffffffffu;
         if (!A.use_ticket && ks_dbg(ctx, KS_DBG_LOOKBACK_SKIP)) A.debug_skip_tile = (u32)atoi(ks_dbg(ctx, KS_DBG_LOOKBACK_SKIP)); // (tests: a real expired spin)
         if (attempt == 1) { // the dispatch-order launch gave up a look-back: start the tiles over, ids by ticket
-            ctx->sketch_use_ticket = true;
-            ctx->sketch_ticket_fallbacks++;
+            if (!P.slots) { // (a launch with slots from the plan that gave up says nothing about the dispatch order)
+                ctx->sketch_use_ticket = true;
+                ctx->sketch_ticket_fallbacks++;
+            }
             KS_HIP(ctx, hipMemsetAsync(tile_status, 0, (size_t)n_tiles * sizeof(unsigned long long), ctx->stream));
             // (every tile of the first attempt counted its repeats, and the repeat counts them again)
             KS_HIP(ctx, hipMemsetAsync(A.drops_out, 0, sizeof(u64), ctx->stream));
@@ -1583,6 +1760,7 @@ static int sk_launch_tiles(ks_ctx *ctx, ks_sketches *S, const sk_call &C, const 
             if (part_snap) KS_HIP(ctx, hipMemcpyAsync(A.part_cursor, part_snap, 2048 * sizeof(u32), hipMemcpyDeviceToDevice, ctx->stream));
             else if (A.part_cursor) KS_HIP(ctx, hipMemsetAsync(A.part_cursor, 0, 2048 * sizeof(u32), ctx->stream));
         }
+        if (slots) ctx->sketch_planned_slots++;
         ks_timer_begin(ctx, "sketch_tiles");
         // (the k-mer sizes of the reference's defaults and of BASELINE's configs run kernels with k folded in:
         // src/rust/main.rs:28 k = 10, src/python/kmerseek/index.py:79-81 k = 24; any other size: the generic kernel)

@@ -28,6 +28,8 @@ struct sk_args {
     u32 upper_only; // the table only upper-cases (moltype protein): applied arithmetically
     u32 R;         // tile stride in residues (see sk_r_cand_host, ks_sketch.hip); 0 = packed tiles (tile_g0 gives each tile's first residue)
     const u64 *tile_g0; // packed tiles: 16-byte aligned residue offset the tile's LDS window starts at
+    const u64 *tile_wbase; // packed tiles, no hash threshold, or NULL: k-mer windows of all sequences before the tile's first = where its
+                           // CSR slots begin (slots as long as the sequences' windows: no look-back across tiles, no tile status words)
     u32 span;      // residues a shared tile covers from tile * R: SK_TILE, or more for the compacting variant (scaled > 1)
     u32 c_div, c_rcp; // compacting variant: bucket space is positions / c_div (c_rcp = ceil(2^32 / c_div))
     u64 out_cap;   // capacity of out_hash / out_abund (MODE 0): writes beyond it are dropped and the host repeats larger

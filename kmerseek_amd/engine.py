@@ -278,11 +278,16 @@ class Context:
         self._check(self._L.ks_ctx_pool_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("blocks", "bytes_held", "bytes_in_use", "mallocs"), (int(x.value) for x in v)))
 
-    def sketch_stats(self) -> Dict[str, int]:
-        """Repeats this context needed so far (see ks_ctx_sketch_stats): results never depend on them, run time does."""
-        v = (C.c_uint64 * 4)()
+    def sketch_stats(self, paths: bool = False) -> Dict[str, int]:
+        """Repeats this context needed so far (see ks_ctx_sketch_stats): results never depend on them, run time does.
+        paths=True adds `planned_slots`, the shared-tile launches whose tiles took the start of their CSR slots from the tile
+        plan instead of a look-back across tiles: a path taken, not a repeat, so it grows in normal operation."""
+        v = (C.c_uint64 * 5)()
         self._check(self._L.ks_ctx_sketch_stats(self._h, C.byref(v)))
-        return {"ticket_fallbacks": int(v[0]), "uses_ticket": int(v[1]), "compact_fallbacks": int(v[2]), "cap_fallbacks": int(v[3])}
+        out = {"ticket_fallbacks": int(v[0]), "uses_ticket": int(v[1]), "compact_fallbacks": int(v[2]), "cap_fallbacks": int(v[3])}
+        if paths:
+            out["planned_slots"] = int(v[4])
+        return out
 
     def unpack_hits64_device(self, d_packed: int, n: int, qbits: int, tbits: int, d_qid: int, d_tid: int, d_isect: int, d_nw: int):
         """Transport words -> columns, all device pointers (ks_hits_unpack64_device): the receiving side of the exchange."""
