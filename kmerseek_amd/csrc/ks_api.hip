@@ -1036,16 +1036,19 @@ extern "C" void ks_ffold_free(ks_ffold *f) { ks_obj_free(f); }
 // ---------------------------------------------------------------------------------------------
 // region stitch (ks_rstitch.hip): the chain of each hit row as one gapped alignment with one CIGAR
 // ---------------------------------------------------------------------------------------------
+// the options ks_regions_stitch and ks_frames_stitch share; *max_fill: 0 becomes the default
+static int ks_stitch_opts_check(ks_ctx *ctx, const char *pass, u32 flags, u32 reserved, u32 *max_fill) {
+    KS_TRY(ks_opts_words_check(ctx, pass, flags, KS_RSTITCH_EQX, reserved));
+    if (*max_fill <= KS_RSTITCH_MAX_FILL) { *max_fill = *max_fill ? *max_fill : 1024u; return KS_OK; }
+    return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "%s options: max_fill %u (at most %u, 0 = 1024)", pass, *max_fill, KS_RSTITCH_MAX_FILL) : KS_ERR_INVALID_ARG;
+}
 extern "C" int ks_regions_stitch(ks_ctx *ctx, const ks_rchain *chain, const ks_raligns *alignments, const ks_cigars *cigars, const ks_hits *hits,
                                  const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
                                  const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_rstitch_opts *opts, ks_hitalns **out) {
     return ks_guard(ctx, [&]() -> int {
     const ks_rstitch_opts dflt = {0u, 0u, 0u, {0u, 0u}};
-    const ks_rstitch_opts o = opts ? *opts : dflt;
-    KS_TRY(ks_opts_words_check(ctx, "region stitch", o.flags, KS_RSTITCH_EQX, o.reserved[0] | o.reserved[1]));
-    if (o.max_fill > KS_RSTITCH_MAX_FILL)
-        return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "region stitch options: max_fill %u (at most %u, 0 = 1024)", o.max_fill, KS_RSTITCH_MAX_FILL)
-                   : KS_ERR_INVALID_ARG;
+    ks_rstitch_opts o = opts ? *opts : dflt;
+    KS_TRY(ks_stitch_opts_check(ctx, "region stitch", o.flags, o.reserved[0] | o.reserved[1], &o.max_fill));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (out) *out = nullptr;
     if (!chain || !alignments || !cigars || !hits || !out || !d_q_offs || !d_t_offs || (n_q_res && !d_q_res) || (n_t_res && !d_t_res))
@@ -1062,7 +1065,7 @@ extern "C" int ks_regions_stitch(ks_ctx *ctx, const ks_rchain *chain, const ks_r
     KS_HIP(ctx, hipSetDevice(ctx->device));
     const ks_res_batch Q{d_q_res, d_q_offs, n_q, n_q_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
     ks_result<ks_hitalns> R(ctx, out, ks_hitalns_free);
-    KS_TRY(ks_regions_stitch_impl(ctx, chain, alignments, cigars, hits, Q, T, o.max_fill ? o.max_fill : 1024u, o.flags, o.max_scratch_bytes, R));
+    KS_TRY(ks_regions_stitch_impl(ctx, chain, alignments, cigars, hits, Q, T, o.max_fill, o.flags, o.max_scratch_bytes, R));
     return R.commit();
     });
 }
@@ -1108,11 +1111,8 @@ extern "C" int ks_frames_stitch(ks_ctx *ctx, const ks_ffold *fold, const ks_hits
                                 ks_framealns **out) {
     return ks_guard(ctx, [&]() -> int {
     const ks_fstitch_opts dflt = {0u, 0u, 15u, 0u, 0u};
-    const ks_fstitch_opts o = opts ? *opts : dflt;
-    KS_TRY(ks_opts_words_check(ctx, "frame stitch", o.flags, KS_RSTITCH_EQX, o.reserved));
-    if (o.max_fill > KS_RSTITCH_MAX_FILL)
-        return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "frame stitch options: max_fill %u (at most %u, 0 = 1024)", o.max_fill, KS_RSTITCH_MAX_FILL)
-                   : KS_ERR_INVALID_ARG;
+    ks_fstitch_opts o = opts ? *opts : dflt;
+    KS_TRY(ks_stitch_opts_check(ctx, "frame stitch", o.flags, o.reserved, &o.max_fill));
     if (o.frameshift_cost > KS_FSTITCH_MAX_COST)
         return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "frame stitch options: frameshift_cost %u (at most %u)", o.frameshift_cost, KS_FSTITCH_MAX_COST)
                    : KS_ERR_INVALID_ARG;
@@ -1134,7 +1134,7 @@ extern "C" int ks_frames_stitch(ks_ctx *ctx, const ks_ffold *fold, const ks_hits
     KS_HIP(ctx, hipSetDevice(ctx->device));
     const ks_res_batch Q{d_f_res, d_f_offs, n_f, n_f_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
     ks_result<ks_framealns> R(ctx, out, ks_framealns_free);
-    KS_TRY(ks_frames_stitch_impl(ctx, fold, folded_hits, chain, alignments, cigars, Q, T, o.max_fill ? o.max_fill : 1024u, o.flags, o.frameshift_cost,
+    KS_TRY(ks_frames_stitch_impl(ctx, fold, folded_hits, chain, alignments, cigars, Q, T, o.max_fill, o.flags, o.frameshift_cost,
                                  o.max_scratch_bytes, R));
     return R.commit();
     });

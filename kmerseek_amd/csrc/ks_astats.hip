@@ -331,7 +331,6 @@ struct as_args {
     unsigned long long *ctl; // AS_BAD_*, then the fallback rows
 };
 
-KS_DEV double as_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 
 // The pairs (i, j) of the standard block ordered by power smax - M[i][j] (the host sorts them once per call): lane l takes the
 // AS_RUN consecutive pairs from l * AS_RUN, sums those of one power in registers and sends one atomic per power it meets, so a
@@ -451,7 +450,7 @@ __global__ __launch_bounds__(AC_THREADS) void k_as_emit(as_args A) {
     u64 n_eff = A.n_eff;
     if (A.pairwise) { const u32 Lt = A.t_len[t]; n_eff = Lt > adj && Lt - adj > 1u ? Lt - adj : 1u; }
     const double km = (A.K_c * (double)n_eff) * (double)m_eff;
-    double best_bit = as_nan(), best_e = as_nan();
+    double best_bit = ks_nan(), best_e = ks_nan();
     for (u64 i = b; i < e; i++) { // [b, e) lies inside [0, n)
         const double Sp = rho * (double)A.score[i];
         const double bit = (A.lambda_c * Sp - A.ln_K) / A.ln_2;

@@ -410,20 +410,20 @@ enum : u32 {
     KS_PIN_RCULL = 243,      // 3 words, region cull: first row that breaks the CSR | first region with a length of 0 | kept regions (ks_rcull.hip)
     KS_PIN_RCHAIN = 246,     // 5 words, region chain: first row that breaks the CSR | first region with a length of 0 | with an end beyond 0xffffffff | with a score beyond 2^30 | chained regions (ks_rchain.hip)
     KS_PIN_RCHAIN_COV = 251, // 2 words, chain coverage: first row with an id beyond the batches | first row whose chain is longer than its sequence (ks_rchain.hip)
-    KS_PIN_RSTITCH = 253,    // 11 words, region stitch: the eight first-offender words (ks_rstitch.hip: RS_BAD_*), then the scan totals: direction rows | columns | ops
-    KS_PIN_RCOMP = 264,      // 2 words, residue composition: first sequence whose offsets descend or pass the batch | first sequence of 2^32 residues or more (ks_astats.hip)
-    KS_PIN_ASTATS = 266,     // 4 words, alignment statistics: first row that breaks the CSR | with an id beyond its composition | with a sequence too long | fallback rows (ks_astats.hip)
-    KS_PIN_MASK = 270,       // 7 words, low-complexity mask and split: first record with bad offsets | masked residues | hot-window runs | raw segments | kept segments, then the segments' residue count (ks_mask.hip)
-    KS_PIN_FFOLD = 277,      // 8 words, frame fold: first record with bad offsets | too long | first row with a qid beyond the frames | out of order | that breaks the CSR | first region beyond its frame | beyond the target bound, then the folded rows (ks_ffold.hip)
-    KS_PIN_FSTITCH = 285,    // 14 words, frame stitch: the eleven first-offender words (ks_fstitch.hip: FS_BAD_*), then the scan totals: direction rows | columns | ops
-    KS_PIN_PILEUP = 299,     // 7 words, pileup: the seven first-offender words (ks_pileup.hip: PU_BAD_*)
-    KS_PIN_END = 306,
+    KS_PIN_RSTITCH = 253,    // 14 words, region stitch: the eleven first-offender words (ks_stitch_kit.h: ST_BAD_*), then the scan totals: direction rows | columns | ops
+    KS_PIN_RCOMP = 267,      // 2 words, residue composition: first sequence whose offsets descend or pass the batch | first sequence of 2^32 residues or more (ks_astats.hip)
+    KS_PIN_ASTATS = 269,     // 4 words, alignment statistics: first row that breaks the CSR | with an id beyond its composition | with a sequence too long | fallback rows (ks_astats.hip)
+    KS_PIN_MASK = 273,       // 7 words, low-complexity mask and split: first record with bad offsets | masked residues | hot-window runs | raw segments | kept segments, then the segments' residue count (ks_mask.hip)
+    KS_PIN_FFOLD = 280,      // 8 words, frame fold: first record with bad offsets | too long | first row with a qid beyond the frames | out of order | that breaks the CSR | first region beyond its frame | beyond the target bound, then the folded rows (ks_ffold.hip)
+    KS_PIN_FSTITCH = 288,    // 14 words, frame stitch: the same eleven words, then the scan totals: direction rows | columns | ops
+    KS_PIN_PILEUP = 302,     // 7 words, pileup: the seven first-offender words (ks_pileup.hip: PU_BAD_*)
+    KS_PIN_END = 309,
 };
 #define KS_PIN_WORDS 312
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 11 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_FSTITCH && KS_PIN_FSTITCH + 14 <= KS_PIN_PILEUP && KS_PIN_PILEUP + 7 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 14 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_FSTITCH && KS_PIN_FSTITCH + 14 <= KS_PIN_PILEUP && KS_PIN_PILEUP + 7 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 

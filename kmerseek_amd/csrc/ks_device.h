@@ -153,6 +153,14 @@ KS_DEV u64 ks_wave_sum64(u64 v) {
 #undef KS_SUM64_STEP
     return ((u64)(u32)__builtin_amdgcn_readlane((int)hi, 63) << 32) | (u32)__builtin_amdgcn_readlane((int)lo, 63);
 }
+// Sum of a 32-bit value over the 64 lanes of a wave, in every lane: the end of a row's re-scoring, once per wave
+KS_DEV u32 ks_wave_sum32(u32 v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) v += (u32)__shfl_xor((int)v, d);
+    return v;
+}
+// the quiet NaN of a row that has no value in a double column
+KS_DEV double ks_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 // Largest of a 64-bit value over the 64 lanes of a wave (uniform result), the same DPP moves: a lane without a source compares
 // with 0.  The argmax of ks_hits_gather: its keys are (count << 32) | ~row.
 KS_DEV u64 ks_wave_max64(u64 v) {

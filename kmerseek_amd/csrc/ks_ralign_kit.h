@@ -50,7 +50,7 @@ static_assert(RA_CHUNK <= 64 && RA_CHUNK + 2 * RA_WMAX <= RA_STRIP && RA_STRIP =
 //                   lanes as diagonals (ra_extend<true>)  the G this lane HANDED DOWN in row x: it is the F of the cell one lane
 //                                                         below, (x, lane k - 1).  A walk in state F at (x, lane j) reads this
 //                                                         bit of lane j + 1 and goes to (x - 1, lane j + 1)
-//                   lanes as columns (k_rs_fill)          the F of the lane's OWN cell.  A walk in state F at (x, lane j) reads
+//                   lanes as columns (rf_fill)            the F of the lane's OWN cell.  A walk in state F at (x, lane j) reads
 //                                                         this bit of lane j and goes to (x - 1, lane j)
 //   >> RA_DIR_E   0: H(x, y) is H~; d >= 1: H took E from the H~ of lane k - d of the same row (d <= 63: 6 bits)
 // The byte of a lane whose cell does not exist means nothing; a walk from an existing cell never reaches one.

@@ -63,9 +63,8 @@ struct rh_row {
     u64 qs, qe, ts, te, qa, ta, ident, alen; // (qe - qs, te - ts, qa, ta <= 0xffffffff: the plan admits no end beyond it)
 };
 
-KS_DEV double rh_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 KS_DEV void rh_row_store(const rh_out &O, u32 r, const rh_row &R, bool empty) {
-    O.chain_score[r] = R.score; O.row_score[r] = empty ? rh_nan() : (double)R.score;
+    O.chain_score[r] = R.score; O.row_score[r] = empty ? ks_nan() : (double)R.score;
     O.q_start[r] = (u32)R.qs; O.q_length[r] = (u32)(R.qe - R.qs); O.t_start[r] = (u32)R.ts; O.t_length[r] = (u32)(R.te - R.ts);
     O.q_aligned[r] = (u32)R.qa; O.t_aligned[r] = (u32)R.ta; O.identities[r] = R.ident; O.aln_length[r] = R.alen;
 }
@@ -404,15 +403,15 @@ __global__ __launch_bounds__(RH_THREADS) void k_rh_cover(const u64 *c_offs, cons
     const u64 i = (u64)blockIdx.x * RH_THREADS + threadIdx.x;
     if (i >= n_rows) return;
     const u32 r = (u32)i, q = qid[r], t = tid[r];
-    double v = rh_nan();
+    double v = ks_nan();
     if (q >= n_q || t >= n_t) ks_first_bad(bad, RH_COV_BAD_ID, r);
     else {
         const u64 qb = q_off[q], qe = q_off[q + 1], tb = t_off[t], te = t_off[t + 1];
         const u64 Lq = qe >= qb ? qe - qb : 0, Lt = te >= tb ? te - tb : 0, a = qa[r], c = ta[r];
         if (a > Lq || c > Lt) ks_first_bad(bad, RH_COV_BAD_LEN, r);
         else if (c_offs[r + 1] != c_offs[r]) {
-            const double cq = Lq ? (double)a / (double)Lq : rh_nan(), ct = Lt ? (double)c / (double)Lt : rh_nan();
-            v = mode == 0 ? cq : mode == 1 ? ct : (cq != cq || ct != ct) ? rh_nan() : mode == 2 ? (cq < ct ? cq : ct) : (cq > ct ? cq : ct);
+            const double cq = Lq ? (double)a / (double)Lq : ks_nan(), ct = Lt ? (double)c / (double)Lt : ks_nan();
+            v = mode == 0 ? cq : mode == 1 ? ct : (cq != cq || ct != ct) ? ks_nan() : mode == 2 ? (cq < ct ? cq : ct) : (cq > ct ? cq : ct);
         }
     }
     cov[r] = v;

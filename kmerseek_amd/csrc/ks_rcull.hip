@@ -54,7 +54,6 @@ struct rc_out {
     double *best;                   // per row
 };
 
-KS_DEV double rc_nan() { return __longlong_as_double(0x7ff8000000000000LL); }
 // region k covers region g: the overlap is at least P percent of g on both sequences (ends in u64: start + length may be 2^32)
 KS_DEV bool rc_covers(u32 P, u32 kqs, u32 kql, u32 kts, u32 ktl, u32 gqs, u32 gql, u32 gts, u32 gtl) {
     const u64 kqe = (u64)kqs + kql, gqe = (u64)gqs + gql, kte = (u64)kts + ktl, gte = (u64)gts + gtl;
@@ -76,12 +75,12 @@ __global__ __launch_bounds__(RC_PLAN_THREADS) void k_rc_plan(rc_in I, int mode, 
     if (i < I.n_rows) {
         const u64 b = I.row_offs[r], e = I.row_offs[r + 1];
         if ((r == 0 && b != 0) || b > e || e > I.n || (r == I.n_rows - 1 && e != I.n)) ks_first_bad(bad, RC_BAD_CSR, r);
-        else if (e == b) O.best[r] = rc_nan();
+        else if (e == b) O.best[r] = ks_nan();
         else if (e - b == 1 && mode == 0) { // [b, e) lies inside [0, n)
             const i64 s = I.score[b];
             const bool keep = !(I.use_min && s < I.min_score); // (max_per_row >= 1 where it limits at all)
             O.keeper[b] = keep ? (u32)b : RC_NONE; O.flag[b] = keep ? 1u : 0u; O.rank[b] = 0u; O.nm[b] = 1u;
-            O.best[r] = keep ? (double)s : rc_nan();
+            O.best[r] = keep ? (double)s : ks_nan();
         } else {
             len = (u32)(e - b);
             to = mode == 2 || len > 64 ? 3u : (mode == 1 || len > RC_GROUP_MAX) ? 2u : 1u;
@@ -142,7 +141,7 @@ template <u32 W> __global__ __launch_bounds__(RC_THREADS) void k_rc_lanes(rc_in 
         if (valid) {
             O.keeper[g] = keeper; O.flag[g] = state == RC_KEPT ? 1u : 0u; O.rank[g] = krank; O.nm[g] = nm;
             if (state == RC_KEPT && krank == 0) O.best[r] = (double)sc;
-            if (sub == 0 && nkept == 0) O.best[r] = rc_nan();
+            if (sub == 0 && nkept == 0) O.best[r] = ks_nan();
         }
     }
 }
@@ -186,7 +185,7 @@ KS_DEV void rc_wg_row(const rc_in &I, const rc_out &O, u32 r, u32 b, u32 len, co
         if (st == RC_KEPT || st == RC_REMOVED) atomicAdd(&O.nm[O.keeper[b + j]], 1u); // (this thread's own store; a keeper of this row)
         else O.keeper[b + j] = RC_NONE;
     }
-    if (nkept == 0 && t == 0) O.best[r] = rc_nan();
+    if (nkept == 0 && t == 0) O.best[r] = ks_nan();
 }
 
 // chunk: the longest row that is staged (<= RC_LDS_ROWS); order / state: one u32 per input region, for the longer rows

@@ -1,7 +1,8 @@
-// ks_rfill_kit.h — the fill of a link's rectangle, shared by the two passes that stitch a chain into one alignment
-// (ks_rstitch.hip: members of one protein pair; ks_fstitch.hip: members in the frames of one strand): the global affine
-// program of a wave over the two stretches, its walk back and the = / X pass over the finished columns.  One definition: the
-// recurrence, the tie rules, the orientation and the fence cannot differ between the two passes.
+// ks_rfill_kit.h — the fill of a link's rectangle: the global affine program of a wave over the two stretches, its walk back
+// and the = / X pass over the finished columns.  Its one caller is st_fill of ks_stitch_kit.h, the fill kernel of the two
+// passes that stitch a chain into one alignment (ks_rstitch.hip: members of one protein pair; ks_fstitch.hip: members in the
+// frames of one strand); that kit holds everything else of a stitch once.  One definition: the recurrence, the tie rules, the
+// orientation and the fence cannot differ between the two passes.
 #pragma once
 #include "ks_rpath_kit.h"
 

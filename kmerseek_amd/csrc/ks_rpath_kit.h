@@ -45,6 +45,8 @@ static inline int rp_slices_of(ks_ctx *ctx, const u64 *d_off, u64 n, u64 total_r
 }
 
 enum : u32 { RP_M = 0, RP_I = 1, RP_D = 2, RP_EQ = 7, RP_X = 8 }; // BAM op codes
+KS_DEV bool rp_is_pair(u32 c) { return c == RP_M || c == RP_EQ || c == RP_X; }
+KS_DEV u32 rp_even(u32 v) { return (v + 1u) & ~1u; } // rows of a direction slot: it begins on a 128-byte line and shares none
 #define RP_STAGE 64u // rows of directions a walk stages at once (ks_debug_rtrace_stage, ks_debug_rstitch_stage)
 #define RP_BAD 0xffffffffu
 static_assert(RP_STAGE * RA_DIR_ROW == 64 * 4 * 16, "a stage is four 16-byte loads per lane");

@@ -38,7 +38,6 @@ struct rt_args {
 // aln_length between the longer extent and their sum — everything the forward rows and the column slot are sized by.
 struct rt_geo { bool ok; u32 ai, bj, qs, ql, ts, tl, alen, xl, yl, xr, yr; };
 KS_DEV u32 rt_absdiff(u32 a, u32 b) { return a > b ? a - b : b - a; }
-KS_DEV u32 rt_even(u32 v) { return (v + 1u) & ~1u; }
 KS_DEV rt_geo rt_geometry(const rt_args &A, const rk_at &P, u32 g) {
     rt_geo G;
     G.qs = ks_readfirst(A.s_qs[g]); G.ql = ks_readfirst(A.s_ql[g]); G.ts = ks_readfirst(A.s_ts[g]); G.tl = ks_readfirst(A.s_tl[g]);
@@ -65,7 +64,7 @@ __global__ __launch_bounds__(RT_THREADS) void k_rt_plan(rt_args A, u32 *rows, u3
         if (lane == 0) ks_first_bad(A.bad, P.ok && P.n != 0 ? RT_BAD_LEN : RT_BAD_ROW, P.row);
     } else {
         const rt_geo G = rt_geometry(A, P, g);
-        if (G.ok) { nr = rt_even(G.xr) + rt_even(G.xl); nc = G.alen; }
+        if (G.ok) { nr = rp_even(G.xr) + rp_even(G.xl); nc = G.alen; }
         else if (lane == 0) ks_first_bad(A.bad, RT_BAD_ALN, g);
     }
     if (lane == 0) { rows[g] = nr; ncols[g] = nc; }
@@ -93,7 +92,7 @@ __global__ __launch_bounds__(RT_THREADS) void k_rt_trace(rt_args A, rt_slice Z) 
     if (!rt_row_ok(P)) return;
     const rt_geo G = rt_geometry(A, P, g);
     if (!G.ok) return;
-    u8 *const dR = Z.dir + (rk_readfirst64(Z.dir_off[g]) - Z.dir_base) * RA_DIR_ROW, *const dL = dR + (u64)rt_even(G.xr) * RA_DIR_ROW;
+    u8 *const dR = Z.dir + (rk_readfirst64(Z.dir_off[g]) - Z.dir_base) * RA_DIR_ROW, *const dL = dR + (u64)rp_even(G.xr) * RA_DIR_ROW;
     u8 *const col = Z.cols + rk_readfirst64(Z.col_off[g]);
     const u32 Lq = (u32)P.Lq, Lt = (u32)P.Lt;
     const u8 *qa = A.in.q_res + P.qb + G.ai, *ta = A.in.t_res + P.tb + G.bj;

@@ -1497,18 +1497,11 @@ def cigar_strings(op_offsets, ops) -> List[str]:
 class RegionCigars(_Columns):
     """Device-resident paths of the alignments of a hit list's regions (ks_cigars): a CSR over the regions in the order of the
     RegionAlignments they were traced from, region g owns ops [op_offsets[g], op_offsets[g + 1]), an op is len << 4 | BAM code."""
-    _PREFIX, _COUNTS = "cigars", {"n_rows": "", "n_regions": "", "n_ops": ""}
+    _PREFIX, _COUNTS = "cigars", {
+        "n_rows": "", "n_regions": "", "n_ops": "",
+        "n_slices": "Slices of regions the traceback ran in (1 unless the directions did not fit max_scratch_bytes).  Diagnostic.",
+        "scratch_bytes": "Direction scratch the traceback allocated.  Diagnostic."}
     _TABLE = (("op_offsets", "u8", "n_regions + 1"), ("ops", "u4", "n_ops"))
-
-    @property
-    def n_slices(self) -> int:
-        """Slices of regions the traceback ran in (1 unless the directions did not fit max_scratch_bytes).  Diagnostic."""
-        return int(self._ctx._L.ks_cigars_n_slices(self._h))
-
-    @property
-    def scratch_bytes(self) -> int:
-        """Direction scratch the traceback allocated.  Diagnostic."""
-        return int(self._ctx._L.ks_cigars_scratch_bytes(self._h))
 
     def strings(self) -> List[str]:
         """The CIGAR of every region as text, e.g. "35M2D17M1I40M"."""
@@ -1627,43 +1620,43 @@ class FrameFold(_Columns):
         super().free()
 
 
-class HitAlignments(_Columns):
-    """Device-resident result of Context.stitch_chains (ks_hitalns): per hit row ONE gapped alignment — the members of the
-    row's chain with the links between them filled — as a CSR of BAM-encoded ops (row r owns ops [op_offsets[r],
-    op_offsets[r + 1]), an op is len << 4 | code) and the columns of that alignment: its span on both sequences, score (i64),
-    identities, positives, gap_opens, gaps, aln_length, the chain members, filled and open links and trimmed columns behind it,
-    and the score as f64 (NaN: a row without a chain), a `score=` column for Context.best_hits and the cluster passes."""
-    _PREFIX, _COUNTS = "hitalns", {"n_rows": "", "n_ops": ""}
-    _TABLE = (("op_offsets", "u8", "n_rows + 1"), ("ops", "u4", "n_ops")) + tuple(
-        (c, {"score": "i8", "row_score": "f8"}.get(c, "u4"), "n_rows") for c in (
-            "q_start", "q_length", "t_start", "t_length", "score", "identities", "positives", "gap_opens", "gaps", "aln_length",
-            "n_members", "n_filled", "n_open", "n_trimmed", "row_score"))
+class _StitchedRows:
+    """What the two stitched results share beside a table (HitAlignments, FrameAlignments): the diagnostic counts, the
+    row_score column alone and the CIGARs alone.  A subclass declares _DOCS: the docstrings of row_score_ptr and of strings."""
+    _COUNTS = {"n_rows": "", "n_ops": "",
+               "n_slices": "Slices of chain members the fills ran in (1 unless the directions did not fit max_scratch_bytes).  Diagnostic.",
+               "scratch_bytes": "Direction scratch the call allocated.  Diagnostic."}
 
-    @property
-    def n_slices(self) -> int:
-        """Slices of chain members the fills ran in (1 unless the directions did not fit max_scratch_bytes).  Diagnostic."""
-        return int(self._ctx._L.ks_hitalns_n_slices(self._h))
-
-    @property
-    def scratch_bytes(self) -> int:
-        """Direction scratch the call allocated.  Diagnostic."""
-        return int(self._ctx._L.ks_hitalns_scratch_bytes(self._h))
-
-    @property
-    def row_score_ptr(self) -> int:
-        """The device column row_score f64[n_rows]: pass it to Context.best_hits(score=...) or a cluster pass."""
-        return int(self._ctx._L.ks_hitalns_device_row_score(self._h) or 0)
+    def __init_subclass__(cls, **kw):
+        super().__init_subclass__(**kw)
+        fn = f"ks_{cls._PREFIX}_device_row_score"
+        cls.row_score_ptr = property(lambda self: int(getattr(self._ctx._L, fn)(self._h) or 0), doc=cls._DOCS[0])
+        cls.strings = _with_doc(_StitchedRows.strings, cls._DOCS[1])
 
     def ops_to_host(self) -> Tuple[np.ndarray, np.ndarray]:
         """(op_offsets u64[n_rows + 1], ops u32[n_ops]) alone."""
         return self._copy_out(("op_offsets", "ops"))
 
     def strings(self) -> List[str]:
-        """The CIGAR of every hit row as text, e.g. "60M40I60M"; "" for a row without a chain."""
         return cigar_strings(*self.ops_to_host())
 
 
-class FrameAlignments(_Columns):
+class HitAlignments(_StitchedRows, _Columns):
+    """Device-resident result of Context.stitch_chains (ks_hitalns): per hit row ONE gapped alignment — the members of the
+    row's chain with the links between them filled — as a CSR of BAM-encoded ops (row r owns ops [op_offsets[r],
+    op_offsets[r + 1]), an op is len << 4 | code) and the columns of that alignment: its span on both sequences, score (i64),
+    identities, positives, gap_opens, gaps, aln_length, the chain members, filled and open links and trimmed columns behind it,
+    and the score as f64 (NaN: a row without a chain), a `score=` column for Context.best_hits and the cluster passes."""
+    _PREFIX = "hitalns"
+    _TABLE = (("op_offsets", "u8", "n_rows + 1"), ("ops", "u4", "n_ops")) + tuple(
+        (c, {"score": "i8", "row_score": "f8"}.get(c, "u4"), "n_rows") for c in (
+            "q_start", "q_length", "t_start", "t_length", "score", "identities", "positives", "gap_opens", "gaps", "aln_length",
+            "n_members", "n_filled", "n_open", "n_trimmed", "row_score"))
+    _DOCS = ("The device column row_score f64[n_rows]: pass it to Context.best_hits(score=...) or a cluster pass.",
+             'The CIGAR of every hit row as text, e.g. "60M40I60M"; "" for a row without a chain.')
+
+
+class FrameAlignments(_StitchedRows, _Columns):
     """Device-resident result of Context.stitch_frames (ks_framealns): per folded row of a translated search ONE alignment of
     the strand's bases against the target protein, as a CSR of BAM-encoded ops in codon columns (row r owns ops
     [op_offsets[r], op_offsets[r + 1]), an op is len << 4 | code; M, = and X a codon against a residue, I a codon alone, D a
@@ -1672,34 +1665,13 @@ class FrameAlignments(_Columns):
     N), identities, positives, gap_opens, gaps, aln_length (N not counted), the chain members, filled and open links, trimmed
     columns and frameshifts behind it, and the score as f64 (NaN: a row without a chain), a `score=` column for
     Context.best_hits(fold.hits, ...)."""
-    _PREFIX, _COUNTS = "framealns", {"n_rows": "", "n_ops": ""}
+    _PREFIX = "framealns"
     _TABLE = (("op_offsets", "u8", "n_rows + 1"), ("ops", "u4", "n_ops")) + tuple(
         (c, {"score": "i8", "row_score": "f8"}.get(c, "u4"), "n_rows") for c in (
             "s_start", "nt_length", "nt_start", "t_start", "t_length", "score", "identities", "positives", "gap_opens", "gaps", "aln_length",
             "n_members", "n_filled", "n_open", "n_trimmed", "n_frameshifts", "row_score"))
-
-    @property
-    def n_slices(self) -> int:
-        """Slices of chain members the fills ran in (1 unless the directions did not fit max_scratch_bytes).  Diagnostic."""
-        return int(self._ctx._L.ks_framealns_n_slices(self._h))
-
-    @property
-    def scratch_bytes(self) -> int:
-        """Direction scratch the call allocated.  Diagnostic."""
-        return int(self._ctx._L.ks_framealns_scratch_bytes(self._h))
-
-    @property
-    def row_score_ptr(self) -> int:
-        """The device column row_score f64[n_rows]: pass it to Context.best_hits(fold.hits, score=...)."""
-        return int(self._ctx._L.ks_framealns_device_row_score(self._h) or 0)
-
-    def ops_to_host(self) -> Tuple[np.ndarray, np.ndarray]:
-        """(op_offsets u64[n_rows + 1], ops u32[n_ops]) alone."""
-        return self._copy_out(("op_offsets", "ops"))
-
-    def strings(self) -> List[str]:
-        """The CIGAR of every folded row as text, e.g. "41M1N59M"; "" for a row without a chain."""
-        return cigar_strings(*self.ops_to_host())
+    _DOCS = ("The device column row_score f64[n_rows]: pass it to Context.best_hits(fold.hits, score=...).",
+             'The CIGAR of every folded row as text, e.g. "41M1N59M"; "" for a row without a chain.')
 
 
 class Pileup(_Columns):
