@@ -1317,8 +1317,8 @@ void ks_framealns_free(ks_framealns *a);
  * Whatever the inputs hold, nothing is read or written outside the batches, the entries and the result's arrays.  A refused
  * call leaves no object and nothing held in the pool.  One stream, synchronous on return, one host wait.  Scratch from the
  * pool: 8 bytes per residue of the side's batch and 8 per sequence.
- * Not built: depth in bases on the query side of frame alignments; consensus strings, log-odds or PSSM columns; weighting by
- * abundance or score. */
+ * Not built: depth in bases on the query side of frame alignments; weighting by abundance or score.  (Consensus and PSSM
+ * columns from the counts: ks_profile_build_device, below.) */
 typedef struct ks_pileup ks_pileup;
 #define KS_PILEUP_QUERY   0u
 #define KS_PILEUP_TARGET  1u
@@ -1368,6 +1368,101 @@ int ks_pileup_copy_to_host(ks_ctx *ctx, const ks_pileup *p, uint32_t *depth, uin
 void ks_pileup_free(ks_pileup *p);
 /* the longest sequence a wave reduces; a longer one goes to a workgroup (the tests place sequences around it) */
 void ks_debug_pileup_limits(uint32_t *wave_max);
+
+/* ---- position-specific scores: a profile of the query batch, and the region passes against it ------------------------------- */
+
+/* The counts of a query-side pileup (KS_PILEUP_PROFILE) made into one row of 28 scores per query residue, and the three region
+ * passes run against those rows where they took a matrix: M[class(Q_x)][class(T_y)] becomes P[position of Q_x][class(T_y)].
+ * A candidate that a reduced-alphabet seed brought in and a BLOSUM row scores poorly is re-scored by what the query's confident
+ * alignments say about each of its positions.  Seeding stays exact k-mer matching.
+ *
+ * The build rule is this project's own, in committed constants and a fixed order of f64 operations, bit-exact against a host
+ * loop (tests/profile_ref.py).  No log or exp runs on the device: the caller brings the likelihood ratios R and a table of
+ * ascending thresholds, and a score is the number of thresholds at or below the position's ratio r.
+ * ks_profile_opts, all HOST data:
+ *   matrix      int8[28][28], the fallback (NULL: +1 / -1);  bg f64[28], each >= 0: a class with bg == 0 is UNMODELLED;
+ *   ratio       f64[28][28], R[j][c];  beta f64 >= 0, the weight of the pseudo-counts;
+ *   thresholds  f64[n_thr], strictly ascending, n_thr <= KS_PROFILE_MAX_THRESHOLDS;  base i32;
+ *   flags       KS_PROFILE_INCLUDE_QUERY;  reserved 0.
+ * Per residue p of the batch, a = the class of q_res[p], J = the modelled classes, cnt[j] = counts[p * 28 + j]:
+ *   n0 = sum over j in J of cnt[j] (u64).  n0 == 0: the row is matrix[a][.], n_obs[p] = 0.
+ *   Otherwise, with KS_PROFILE_INCLUDE_QUERY and a in J, cnt[a] += 1;  n = sum over J of cnt;  n_obs[p] = min(n, 2^32 - 1).
+ *   c not in J: scores[p][c] = matrix[a][c].
+ *   c in J, in f64, every operation rounded on its own (no fused multiply-add), in exactly this order:
+ *     g = sum over j in J, ascending, of (f64)cnt[j] * R[j][c], from 0.0;  t = g / (f64)n;  t = bg[c] * t;  t = beta * t;
+ *     num = (f64)cnt[c] + t;  den = (f64)n + beta;  r = (num / den) / bg[c];
+ *     scores[p][c] = clamp(base + #{k : thresholds[k] <= r}, -127, 127)        (a NaN r is at or above no threshold)
+ *   consensus[p]: depth[p] == 0: the residue's own byte, ASCII upper-cased.  Otherwise the class with the largest count once the
+ *     residue's own class has been counted once more (all 28 classes, whatever the flag), ties to the smaller class, as that
+ *     class's letter: 'A' .. 'Z', '*', and 'X' for class 27.
+ * Result: scores int8[n_residues * 28] (the accessor and copy_to_host hand them out as bytes), consensus u8[n_residues],
+ * n_obs u32[n_residues]; the object records the fallback matrix.
+ * ks_profile_build_device: d_counts u32[n_q_res * 28] and d_depth u32[n_q_res] as ks_pileup_device makes them on the query side,
+ * the query batch (d_q_res, d_q_offs u64[n_q + 1], n_q, n_q_res).  ks_profile_build_pileup: the same from a ks_pileup that was
+ * made with KS_PILEUP_PROFILE on a batch of n_q sequences and n_q_res residues.  ks_profile_from_host: a profile whose rows the
+ * caller brings (scores int8[n_q_res * 28]; consensus, n_obs: NULL for zeros; matrix: the fallback to record, NULL: +1 / -1).
+ * KS_ERR_INVALID_ARG, in this order: the options, before any device work and also with ctx == NULL — unknown flags, a non-zero
+ * reserved, thresholds that do not ascend strictly, a NaN among bg, ratio, beta or the thresholds, a negative bg or beta, n_thr
+ * beyond the maximum, a missing bg, ratio or (n_thr != 0) thresholds;  NULL pointers, an object of another context, a pileup
+ * without the profile or of another batch;  n_q_res that is not d_q_offs[n_q] (read before anything is indexed by it).  A
+ * refused call leaves no object.  One stream, synchronous on return. */
+typedef struct ks_profile ks_profile;
+#define KS_PROFILE_INCLUDE_QUERY 1u
+#define KS_PROFILE_MAX_THRESHOLDS 254u
+typedef struct ks_profile_opts {
+    const int8_t *matrix;     /* host, [28][28] or NULL */
+    const double *bg;         /* host, [28] */
+    const double *ratio;      /* host, [28][28] */
+    double beta;
+    const double *thresholds; /* host, [n_thr] */
+    uint32_t n_thr;
+    int32_t base;
+    uint32_t flags;           /* KS_PROFILE_INCLUDE_QUERY */
+    uint32_t reserved;        /* 0 */
+} ks_profile_opts;
+int ks_profile_build_device(ks_ctx *ctx, const uint32_t *d_counts, const uint32_t *d_depth, const uint8_t *d_q_res, const uint64_t *d_q_offs,
+                            uint32_t n_q, uint64_t n_q_res, const ks_profile_opts *opts, ks_profile **out);
+int ks_profile_build_pileup(ks_ctx *ctx, const ks_pileup *pileup, const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q,
+                            uint64_t n_q_res, const ks_profile_opts *opts, ks_profile **out);
+int ks_profile_from_host(ks_ctx *ctx, const int8_t *scores, const uint8_t *consensus, const uint32_t *n_obs, uint32_t n_q, uint64_t n_q_res,
+                         const int8_t *matrix, ks_profile **out);
+uint32_t ks_profile_n_seqs(const ks_profile *p);
+uint64_t ks_profile_n_residues(const ks_profile *p);
+/* entries of `scores`: 28 x n_residues */
+uint64_t ks_profile_n_scores(const ks_profile *p);
+/* device pointers, valid until ks_profile_free.  scores: the int8 values as the bytes they are (every column accessor of the
+ * result objects is one of five unsigned / 64-bit element types): read them as int8_t */
+const uint8_t *ks_profile_device_scores(const ks_profile *p);
+const uint8_t *ks_profile_device_consensus(const ks_profile *p);
+const uint32_t *ks_profile_device_n_obs(const ks_profile *p);
+/* any destination may be NULL */
+int ks_profile_copy_to_host(ks_ctx *ctx, const ks_profile *p, uint8_t *scores, uint8_t *consensus, uint32_t *n_obs);
+void ks_profile_free(ks_profile *p);
+
+/* The three region passes against a profile of the QUERY batch.  The contract of each is its sibling's, word for word —
+ * recurrence, tie rules, X-drop, counts, ops, refusals — with one difference: a pair (Q_x, T_y) scores
+ * P[q_offs[qid] + position of Q_x][class(T_y)], the anchor pair included.  Identities still compare upper-cased bytes, positives
+ * are still s > 0.  Both forms are one code path with two scorers, so a tie never differs between them: a profile whose row p is
+ * matrix[class(q_res[p])][.] gives the sibling's result bit for bit.  opts->matrix is not read.
+ * A ks_raligns made here records that it is profile-made (ks_raligns_by_profile) and the profile's fallback matrix; the cull's
+ * take and the chain, which read extents and scores only, carry the mark through.  The passes that read residues under a matrix
+ * — ks_regions_traceback, ks_regions_stitch, ks_frames_stitch, ks_raligns_fold_frames, ks_raligns_stats, ks_cigars_pileup —
+ * refuse a profile-made ks_raligns by name, before any device work.
+ * Also KS_ERR_INVALID_ARG, before any device work: a NULL profile, one of another context, one whose n_residues is not n_q_res;
+ * for ks_regions_traceback_profile an `alignments` that is not profile-made.
+ * Not built: profile seeds; sequence weighting; stitch, E-values or fold with profile alignments; a profile on the target side. */
+int ks_regions_score_profile(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res, const uint64_t *d_q_offs,
+                             uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res,
+                             const ks_profile *profile, const ks_rscore_opts *opts, ks_rscores **out);
+int ks_regions_align_profile(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res, const uint64_t *d_q_offs,
+                             uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res,
+                             const ks_profile *profile, const ks_ralign_opts *opts, ks_raligns **out);
+int ks_regions_traceback_profile(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res, const uint64_t *d_q_offs,
+                                 uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t,
+                                 uint64_t n_t_res, const ks_raligns *alignments, const ks_profile *profile, const ks_rtrace_opts *opts,
+                                 ks_cigars **out);
+/* 1: the alignments were made by ks_regions_align_profile (or taken from such); 0 otherwise */
+int ks_raligns_by_profile(const ks_raligns *s);
 
 /* ---- alignment statistics: bit scores and E-values per hit ------------------------------------------------------------------- */
 

@@ -125,6 +125,16 @@ class ks_pileup_opts(C.Structure):
     _fields_ = [("flags", C.c_uint32), ("side", C.c_uint32), ("reserved", C.c_uint64)]
 
 
+KS_PROFILE_INCLUDE_QUERY = 1
+KS_PROFILE_MAX_THRESHOLDS = 254
+
+
+class ks_profile_opts(C.Structure):
+    _fields_ = [("matrix", C.POINTER(C.c_int8)), ("bg", C.POINTER(C.c_double)), ("ratio", C.POINTER(C.c_double)), ("beta", C.c_double),
+                ("thresholds", C.POINTER(C.c_double)), ("n_thr", C.c_uint32), ("base", C.c_int32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
 KS_ASTATS_NO_COMPOSITION, KS_ASTATS_PAIRWISE, KS_ASTATS_ALLOW_UNGAPPED = 1, 2, 4
 KS_ASTATS_ROW_REGULAR, KS_ASTATS_ROW_FALLBACK, KS_ASTATS_ROW_SKIPPED = 0, 1, 2
 KS_ASTATS_MAX_SEQ_LEN = 1 << 20
@@ -479,6 +489,24 @@ SIGNATURES = {
     "ks_cigars_pileup": (C.c_int, [_vp] * 6 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(ks_pileup_opts), _pp]),
     "ks_hitalns_pileup": (C.c_int, [_vp] * 5 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, C.POINTER(ks_pileup_opts), _pp]),
     "ks_frames_pileup": (C.c_int, [_vp] * 5 + [C.c_uint32, C.c_uint64, C.POINTER(ks_pileup_opts), _pp]),
+    "ks_profile_build_device": (C.c_int, [_vp] * 5 + [C.c_uint32, C.c_uint64, C.POINTER(ks_profile_opts), _pp]),
+    "ks_profile_build_pileup": (C.c_int, [_vp] * 4 + [C.c_uint32, C.c_uint64, C.POINTER(ks_profile_opts), _pp]),
+    "ks_profile_from_host": (C.c_int, [_vp] * 4 + [C.c_uint32, C.c_uint64, _vp, _pp]),
+    "ks_profile_n_seqs": (C.c_uint32, [_vp]),
+    "ks_profile_n_residues": (C.c_uint64, [_vp]),
+    "ks_profile_n_scores": (C.c_uint64, [_vp]),
+    "ks_profile_device_scores": (_vp, [_vp]),
+    "ks_profile_device_consensus": (_vp, [_vp]),
+    "ks_profile_device_n_obs": (_vp, [_vp]),
+    "ks_profile_copy_to_host": (C.c_int, [_vp] * 5),
+    "ks_profile_free": (None, [_vp]),
+    "ks_regions_score_profile": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, _vp,
+                                           C.POINTER(ks_rscore_opts), _pp]),
+    "ks_regions_align_profile": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, _vp,
+                                           C.POINTER(ks_ralign_opts), _pp]),
+    "ks_regions_traceback_profile": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, _vp, _vp,
+                                               C.POINTER(ks_rtrace_opts), _pp]),
+    "ks_raligns_by_profile": (C.c_int, [_vp]),
     "ks_pileup_n_seqs": (C.c_uint32, [_vp]),
     "ks_pileup_n_residues": (C.c_uint64, [_vp]),
     "ks_pileup_n_profile": (C.c_uint64, [_vp]),

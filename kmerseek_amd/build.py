@@ -13,7 +13,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libkmerseek_amd.so")
-SOURCES = ["ks_ctx.hip", "ks_prims.hip", "ks_msd.hip", "ks_copy.hip", "ks_sketch.hip", "ks_sketch_long.hip", "ks_kmerpos.hip", "ks_search.hip", "ks_rows.hip", "ks_hits.hip", "ks_matchpos.hip", "ks_regions.hip", "ks_rscore.hip", "ks_ralign.hip", "ks_rtrace.hip", "ks_rcull.hip", "ks_rchain.hip", "ks_ffold.hip", "ks_rstitch.hip", "ks_fstitch.hip", "ks_astats.hip", "ks_pileup.hip", "ks_signif.hip", "ks_best.hip", "ks_gather.hip", "ks_cluster.hip", "ks_greedy.hip", "ks_translate.hip", "ks_mask.hip", "ks_union.hip", "ks_api.hip", "ks_debug_prims.hip", "ks_hostfn.cpp", "ks_host.cpp", "ks_ingest.cpp", "ks_input.cpp"]
+SOURCES = ["ks_ctx.hip", "ks_prims.hip", "ks_msd.hip", "ks_copy.hip", "ks_sketch.hip", "ks_sketch_long.hip", "ks_kmerpos.hip", "ks_search.hip", "ks_rows.hip", "ks_hits.hip", "ks_matchpos.hip", "ks_regions.hip", "ks_rscore.hip", "ks_ralign.hip", "ks_rtrace.hip", "ks_rcull.hip", "ks_rchain.hip", "ks_ffold.hip", "ks_rstitch.hip", "ks_fstitch.hip", "ks_astats.hip", "ks_pileup.hip", "ks_profile.hip", "ks_signif.hip", "ks_best.hip", "ks_gather.hip", "ks_cluster.hip", "ks_greedy.hip", "ks_translate.hip", "ks_mask.hip", "ks_union.hip", "ks_api.hip", "ks_debug_prims.hip", "ks_hostfn.cpp", "ks_host.cpp", "ks_ingest.cpp", "ks_input.cpp"]
 HEADERS = ["ks_common.h", "ks_device.h", "ks_tile.h", "ks_score.h", "ks_rkit.h", "ks_ralign_kit.h", "ks_rpath_kit.h", "ks_rfill_kit.h", "ks_stitch_kit.h", "ks_input.h", os.path.join("..", "..", "include", "kmerseek_amd.h"),
            os.path.join("..", "..", "include", "kmerseek_host.hpp"), os.path.join("..", "..", "include", "kmerseek_host_c.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

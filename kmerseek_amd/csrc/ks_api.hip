@@ -604,19 +604,33 @@ static int ks_region_pass_check(ks_ctx *ctx, const char *pass, const ks_regions 
     if (regions->n_regions && (!Q.res || !Q.offs || !T.res || !T.offs)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL device buffer");
     return KS_OK;
 }
+// The three passes under a matrix and against a profile are one body each; by_profile: `profile` scores the pairs (checked
+// behind the pass's own arguments: not NULL, of ctx, of the query batch), otherwise it is NULL and not looked at.
+static int ks_regions_score_any(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const ks_res_batch &Q, const ks_res_batch &T,
+                                bool by_profile, const ks_profile *profile, const ks_rscore_opts *opts, ks_rscores **out) {
+    if (opts) KS_TRY(ks_opts_words_check(ctx, "region score", opts->flags, KS_RSCORE_EXTEND, opts->reserved ? 1u : 0u));
+    if (!ctx) return KS_ERR_INVALID_ARG;
+    if (out) *out = nullptr;
+    KS_TRY(ks_region_pass_check(ctx, "region scores", regions, hits, out, Q, T));
+    if (by_profile) KS_TRY(rk_profile_check(ctx, "region scores", profile, Q));
+    KS_HIP(ctx, hipSetDevice(ctx->device));
+    ks_result<ks_rscores> S(ctx, out, ks_rscores_free);
+    KS_TRY(ks_regions_score_impl(ctx, regions, hits, Q, T, opts, by_profile ? profile : nullptr, S));
+    return S.commit();
+}
 extern "C" int ks_regions_score(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
                                 const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
                                 const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_rscore_opts *opts, ks_rscores **out) {
     return ks_guard(ctx, [&]() -> int {
-    if (opts) KS_TRY(ks_opts_words_check(ctx, "region score", opts->flags, KS_RSCORE_EXTEND, opts->reserved ? 1u : 0u));
-    if (!ctx) return KS_ERR_INVALID_ARG;
-    if (out) *out = nullptr;
-    const ks_res_batch Q{d_q_res, d_q_offs, n_q, n_q_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
-    KS_TRY(ks_region_pass_check(ctx, "region scores", regions, hits, out, Q, T));
-    KS_HIP(ctx, hipSetDevice(ctx->device));
-    ks_result<ks_rscores> S(ctx, out, ks_rscores_free);
-    KS_TRY(ks_regions_score_impl(ctx, regions, hits, Q, T, opts, S));
-    return S.commit();
+        return ks_regions_score_any(ctx, regions, hits, {d_q_res, d_q_offs, n_q, n_q_res}, {d_t_res, d_t_offs, n_t, n_t_res}, false, nullptr, opts, out);
+    });
+}
+extern "C" int ks_regions_score_profile(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
+                                        const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                        const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_profile *profile,
+                                        const ks_rscore_opts *opts, ks_rscores **out) {
+    return ks_guard(ctx, [&]() -> int {
+        return ks_regions_score_any(ctx, regions, hits, {d_q_res, d_q_offs, n_q, n_q_res}, {d_t_res, d_t_offs, n_t, n_t_res}, true, profile, opts, out);
     });
 }
 extern "C" uint64_t ks_rscores_n_rows(const ks_rscores *s) { return s ? s->n_rows : 0; }
@@ -642,10 +656,8 @@ extern "C" void ks_rscores_free(ks_rscores *s) { ks_obj_free(s); }
 // ---------------------------------------------------------------------------------------------
 // region alignments (ks_ralign.hip): the regions of a hit list extended with gaps from the middle of their seeds
 // ---------------------------------------------------------------------------------------------
-extern "C" int ks_regions_align(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
-                                const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
-                                const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_ralign_opts *opts, ks_raligns **out) {
-    return ks_guard(ctx, [&]() -> int {
+static int ks_regions_align_any(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const ks_res_batch &Q, const ks_res_batch &T,
+                                bool by_profile, const ks_profile *profile, const ks_ralign_opts *opts, ks_raligns **out) {
     const ks_ralign_opts dflt = {nullptr, 16u, 11u, 1u, 30u, 0u};
     const ks_ralign_opts o = opts ? *opts : dflt;
     KS_TRY(ks_opts_words_check(ctx, "region alignment", o.flags, 0u, 0u));
@@ -656,14 +668,29 @@ extern "C" int ks_regions_align(ks_ctx *ctx, const ks_regions *regions, const ks
     }
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (out) *out = nullptr;
-    const ks_res_batch Q{d_q_res, d_q_offs, n_q, n_q_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
     KS_TRY(ks_region_pass_check(ctx, "region alignments", regions, hits, out, Q, T));
+    if (by_profile) KS_TRY(rk_profile_check(ctx, "region alignments", profile, Q));
     KS_HIP(ctx, hipSetDevice(ctx->device));
     ks_result<ks_raligns> S(ctx, out, ks_raligns_free);
-    KS_TRY(ks_regions_align_impl(ctx, regions, hits, Q, T, &o, S));
+    KS_TRY(ks_regions_align_impl(ctx, regions, hits, Q, T, &o, by_profile ? profile : nullptr, S));
     return S.commit();
+}
+extern "C" int ks_regions_align(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
+                                const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_ralign_opts *opts, ks_raligns **out) {
+    return ks_guard(ctx, [&]() -> int {
+        return ks_regions_align_any(ctx, regions, hits, {d_q_res, d_q_offs, n_q, n_q_res}, {d_t_res, d_t_offs, n_t, n_t_res}, false, nullptr, opts, out);
     });
 }
+extern "C" int ks_regions_align_profile(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
+                                        const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                        const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_profile *profile,
+                                        const ks_ralign_opts *opts, ks_raligns **out) {
+    return ks_guard(ctx, [&]() -> int {
+        return ks_regions_align_any(ctx, regions, hits, {d_q_res, d_q_offs, n_q, n_q_res}, {d_t_res, d_t_offs, n_t, n_t_res}, true, profile, opts, out);
+    });
+}
+extern "C" int ks_raligns_by_profile(const ks_raligns *s) { return s && s->by_profile ? 1 : 0; }
 extern "C" uint64_t ks_raligns_n_rows(const ks_raligns *s) { return s ? s->n_rows : 0; }
 extern "C" uint64_t ks_raligns_n_regions(const ks_raligns *s) { return s ? s->n_regions : 0; }
 extern "C" const uint64_t *ks_raligns_device_row_offsets(const ks_raligns *s) { return s ? s->d_row_offsets : nullptr; }
@@ -690,18 +717,22 @@ extern "C" void ks_raligns_free(ks_raligns *s) { ks_obj_free(s); }
 // ---------------------------------------------------------------------------------------------
 // region traceback (ks_rtrace.hip): the path of every alignment of a ks_raligns as a CIGAR
 // ---------------------------------------------------------------------------------------------
-extern "C" int ks_regions_traceback(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
-                                    const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
-                                    const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_raligns *alignments,
-                                    const ks_rtrace_opts *opts, ks_cigars **out) {
-    return ks_guard(ctx, [&]() -> int {
+static int ks_regions_traceback_any(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const ks_res_batch &Q, const ks_res_batch &T,
+                                    const ks_raligns *alignments, bool by_profile, const ks_profile *profile, const ks_rtrace_opts *opts,
+                                    ks_cigars **out) {
     if (opts) KS_TRY(ks_opts_words_check(ctx, "region traceback", opts->flags, KS_RTRACE_EQX, opts->reserved));
     if (!ctx) return KS_ERR_INVALID_ARG;
     if (out) *out = nullptr;
-    const ks_res_batch Q{d_q_res, d_q_offs, n_q, n_q_res}, T{d_t_res, d_t_offs, n_t, n_t_res};
     KS_TRY(ks_region_pass_check(ctx, "region traceback", regions, hits, out, Q, T));
     if (!alignments) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_TRY(ks_inputs_check_ctx(ctx, "region traceback", alignments));
+    if (!by_profile) KS_TRY(ks_refuse_by_profile(ctx, "region traceback", alignments));
+    else {
+        if (!alignments->by_profile)
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "region traceback against a profile: the alignments were made under a matrix (ks_regions_align): "
+                                                    "their path is ks_regions_traceback's");
+        KS_TRY(rk_profile_check(ctx, "region traceback", profile, Q));
+    }
     if (alignments->n_rows != regions->n_rows || alignments->n_regions != regions->n_regions)
         return ks_fail(ctx, KS_ERR_INVALID_ARG,
                        "region traceback: the alignments are of %llu regions in %llu hit rows, the regions are %llu in %llu: "
@@ -709,8 +740,26 @@ extern "C" int ks_regions_traceback(ks_ctx *ctx, const ks_regions *regions, cons
                        (unsigned long long)regions->n_regions, (unsigned long long)regions->n_rows);
     KS_HIP(ctx, hipSetDevice(ctx->device));
     ks_result<ks_cigars> C(ctx, out, ks_cigars_free);
-    KS_TRY(ks_regions_traceback_impl(ctx, regions, hits, Q, T, alignments, opts ? opts->flags : 0u, opts ? opts->max_scratch_bytes : 0, C));
+    KS_TRY(ks_regions_traceback_impl(ctx, regions, hits, Q, T, alignments, by_profile ? profile : nullptr, opts ? opts->flags : 0u,
+                                     opts ? opts->max_scratch_bytes : 0, C));
     return C.commit();
+}
+extern "C" int ks_regions_traceback(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
+                                    const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                    const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_raligns *alignments,
+                                    const ks_rtrace_opts *opts, ks_cigars **out) {
+    return ks_guard(ctx, [&]() -> int {
+        return ks_regions_traceback_any(ctx, regions, hits, {d_q_res, d_q_offs, n_q, n_q_res}, {d_t_res, d_t_offs, n_t, n_t_res}, alignments, false,
+                                    nullptr, opts, out);
+    });
+}
+extern "C" int ks_regions_traceback_profile(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res,
+                                            const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res,
+                                            const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res, const ks_raligns *alignments,
+                                            const ks_profile *profile, const ks_rtrace_opts *opts, ks_cigars **out) {
+    return ks_guard(ctx, [&]() -> int {
+        return ks_regions_traceback_any(ctx, regions, hits, {d_q_res, d_q_offs, n_q, n_q_res}, {d_t_res, d_t_offs, n_t, n_t_res}, alignments, true,
+                                    profile, opts, out);
     });
 }
 extern "C" uint64_t ks_cigars_n_rows(const ks_cigars *c) { return c ? c->n_rows : 0; }
@@ -997,6 +1046,7 @@ template <typename T> static int ks_ffold_of(ks_ctx *ctx, const ks_hits *hits, c
     KS_TRY(ks_ffold_begin(ctx, opts, out_hits, out));
     if (!s || !hits) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_TRY(ks_inputs_check_ctx(ctx, "frame fold", s));
+    if constexpr (std::is_same_v<T, ks_raligns>) KS_TRY(ks_refuse_by_profile(ctx, "frame fold", s));
     if (s->n_rows != hits->n_hits)
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "frame fold: the regions cover %llu hit rows, the hit list holds %llu: regions of another list",
                        (unsigned long long)s->n_rows, (unsigned long long)hits->n_hits);
@@ -1054,6 +1104,7 @@ extern "C" int ks_regions_stitch(ks_ctx *ctx, const ks_rchain *chain, const ks_r
     if (!chain || !alignments || !cigars || !hits || !out || !d_q_offs || !d_t_offs || (n_q_res && !d_q_res) || (n_t_res && !d_t_res))
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_TRY(ks_inputs_check_ctx(ctx, "region stitch", chain, alignments, cigars, hits));
+    KS_TRY(ks_refuse_by_profile(ctx, "region stitch", alignments));
     if (chain->n_rows != alignments->n_rows || cigars->n_rows != alignments->n_rows || hits->n_hits != alignments->n_rows ||
         chain->n_regions != alignments->n_regions || cigars->n_regions != alignments->n_regions)
         return ks_fail(ctx, KS_ERR_INVALID_ARG,
@@ -1121,6 +1172,7 @@ extern "C" int ks_frames_stitch(ks_ctx *ctx, const ks_ffold *fold, const ks_hits
     if (!fold || !folded_hits || !chain || !alignments || !cigars || !out || !d_f_offs || !d_t_offs || (n_f_res && !d_f_res) || (n_t_res && !d_t_res))
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_TRY(ks_inputs_check_ctx(ctx, "frame stitch", fold, folded_hits, chain, alignments, cigars));
+    KS_TRY(ks_refuse_by_profile(ctx, "frame stitch", alignments));
     if (chain->n_rows != fold->n_rows || folded_hits->n_hits != fold->n_rows || chain->n_regions != fold->n_regions ||
         fold->n_regions != alignments->n_regions || fold->n_src_rows != alignments->n_rows || cigars->n_regions != alignments->n_regions ||
         cigars->n_rows != alignments->n_rows)

@@ -623,6 +623,7 @@ extern "C" int ks_rscores_stats(ks_ctx *ctx, const ks_rscores *scores, const ks_
 extern "C" int ks_raligns_stats(ks_ctx *ctx, const ks_raligns *alignments, const ks_hits *hits, const ks_rcomp *q_comp, const ks_rcomp *t_comp,
                                 const ks_astats_opts *opts, ks_astats **out) {
     return as_entry(ctx, opts, alignments, true, out, [&](const ks_astats_opts &o) {
+        KS_TRY(ks_refuse_by_profile(ctx, "alignment statistics", alignments)); // ((lambda, K) belong to a matrix, not to a profile's rows)
         return as_run(ctx, alignments->d_row_offsets, alignments->d_score, alignments->n_rows, alignments->n_regions, hits, q_comp, t_comp, o, out);
     }, alignments);
 }

@@ -417,13 +417,14 @@ enum : u32 {
     KS_PIN_FFOLD = 280,      // 8 words, frame fold: first record with bad offsets | too long | first row with a qid beyond the frames | out of order | that breaks the CSR | first region beyond its frame | beyond the target bound, then the folded rows (ks_ffold.hip)
     KS_PIN_FSTITCH = 288,    // 14 words, frame stitch: the same eleven words, then the scan totals: direction rows | columns | ops
     KS_PIN_PILEUP = 302,     // 7 words, pileup: the seven first-offender words (ks_pileup.hip: PU_BAD_*)
-    KS_PIN_END = 309,
+    KS_PIN_PROFILE = 309,    // 1 word, profile build: the last offset of the query batch (ks_profile.hip)
+    KS_PIN_END = 310,
 };
 #define KS_PIN_WORDS 312
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 14 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_FSTITCH && KS_PIN_FSTITCH + 14 <= KS_PIN_PILEUP && KS_PIN_PILEUP + 7 <= KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 14 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_FSTITCH && KS_PIN_FSTITCH + 14 <= KS_PIN_PILEUP && KS_PIN_PILEUP + 7 <= KS_PIN_PROFILE && KS_PIN_PROFILE < KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -564,6 +565,19 @@ struct ks_rcull_cols { const u64 *row_offs; const u32 *qs, *ql, *ts, *tl; const 
 // ... and of a chain's: the same and ident, alen: NULL or a column to sum
 struct ks_rchain_cols : ks_rcull_cols { const u32 *ident, *alen; };
 
+// one row of 28 scores per residue of a query batch (ks_profile.hip)
+struct ks_profile {
+    ks_ctx *ctx;
+    u64 n_seqs, n_residues, n_scores;    // n_scores: 28 x n_residues
+    int8_t *d_scores;                    // n_scores
+    u8 *d_consensus;                     // n_residues
+    u32 *d_n_obs;                        // n_residues
+    int8_t matrix[KS_RSCORE_ALPHABET * KS_RSCORE_ALPHABET]; // the fallback the rows were built with
+    template <class S, class F> static constexpr void each(S &s, F &&f) {
+        f(s.d_scores, s.n_scores); f(s.d_consensus, s.n_residues); f(s.d_n_obs, s.n_residues);
+    }
+};
+
 // the regions of a ks_regions scored under a substitution matrix and extended without gaps (ks_rscore.hip)
 struct ks_rscores {
     ks_ctx *ctx;
@@ -582,8 +596,11 @@ struct ks_rscores {
 // one residue batch on the device, as the C ABI passes it
 struct ks_res_batch { const u8 *res; const u64 *offs; u32 n_seqs; u64 n_res; };
 // ks_regions_score behind its argument checks (opts: validated; R, H: of ctx, equal row counts)
+// what the passes against a profile refuse before any device work (ks_rscore.hip): no profile, one of another context or of another batch than Q
+int rk_profile_check(ks_ctx *ctx, const char *pass, const ks_profile *prof, const ks_res_batch &Q);
+// prof: NULL, or the profile of Q (of ctx, Q.n_res residues) that scores the pairs in the matrix's place
 int ks_regions_score_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
-                          const ks_rscore_opts *opts, ks_rscores *S);
+                          const ks_rscore_opts *opts, const ks_profile *prof, ks_rscores *S);
 
 // the regions of a ks_regions aligned with gaps from the middle of their seeds (ks_ralign.hip)
 struct ks_raligns {
@@ -596,6 +613,9 @@ struct ks_raligns {
     // the options the alignments were made with: ks_regions_traceback walks the path of exactly this program
     u32 band, gap_open, gap_extend, x_drop;
     int8_t matrix[KS_RSCORE_ALPHABET * KS_RSCORE_ALPHABET];
+    // made against a ks_profile (ks_regions_align_profile): `matrix` is the profile's fallback, and a pass that reads residues under
+    // a matrix refuses the object (ks_refuse_by_profile)
+    bool by_profile;
     template <class S, class F> static constexpr void each(S &s, F &&f) {
         f(s.d_row_offsets, s.n_rows + 1); f(s.d_qstart, s.n_regions); f(s.d_qlength, s.n_regions); f(s.d_tstart, s.n_regions);
         f(s.d_tlength, s.n_regions); f(s.d_score, s.n_regions); f(s.d_identities, s.n_regions); f(s.d_positives, s.n_regions);
@@ -604,12 +624,16 @@ struct ks_raligns {
     void take_from(const ks_raligns &src) {
         band = src.band; gap_open = src.gap_open; gap_extend = src.gap_extend; x_drop = src.x_drop;
         memcpy(matrix, src.matrix, sizeof matrix);
+        by_profile = src.by_profile;
     }
     ks_rchain_cols cols() const { return {{d_row_offsets, d_qstart, d_qlength, d_tstart, d_tlength, d_score}, d_identities, d_aln_length}; }
 };
 // ks_regions_align behind its argument checks (opts: not NULL, validated; R, H: of ctx, equal row counts)
+// prof: as ks_regions_score_impl
 int ks_regions_align_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
-                          const ks_ralign_opts *opts, ks_raligns *S);
+                          const ks_ralign_opts *opts, const ks_profile *prof, ks_raligns *S);
+// what every pass that reads residues under the recorded matrix says to a profile-made ks_raligns, before any device work
+int ks_refuse_by_profile(ks_ctx *ctx, const char *pass, const ks_raligns *S);
 
 // the paths of the alignments of a ks_raligns, one CIGAR per region (ks_rtrace.hip)
 struct ks_cigars {
@@ -622,8 +646,9 @@ struct ks_cigars {
     template <class S, class F> static constexpr void each(S &s, F &&f) { f(s.d_op_offsets, s.n_regions + 1); f(s.d_ops, s.n_ops); }
 };
 // ks_regions_traceback behind its argument checks (flags validated; R, H, S: of ctx, equal counts)
+// prof: NULL where S was made under a matrix, the profile (as ks_regions_score_impl) where S is profile-made
 int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
-                              const ks_raligns *S, u32 flags, u64 max_scratch_bytes, ks_cigars *C);
+                              const ks_raligns *S, const ks_profile *prof, u32 flags, u64 max_scratch_bytes, ks_cigars *C);
 
 // the regions of a hit row that no better region of the row covers (ks_rcull.hip)
 struct ks_rcull {

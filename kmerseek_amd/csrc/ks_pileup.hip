@@ -365,6 +365,7 @@ extern "C" int ks_cigars_pileup(ks_ctx *ctx, const ks_cigars *cigars, const ks_r
                                 const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res, const uint8_t *d_o_res, const uint64_t *d_o_offsets,
                                 uint32_t n_o_seqs, uint64_t n_o_res, const ks_pileup_opts *opts, ks_pileup **out) {
     return pu_entry(ctx, opts, pu_has_batch(d_o_res, d_o_offsets, n_o_res), out, pu_any, [&](const ks_pileup_opts &o) {
+        KS_TRY(ks_refuse_by_profile(ctx, "pileup", alignments));
         if (cigars->n_rows != alignments->n_rows || cigars->n_regions != alignments->n_regions)
             return ks_fail(ctx, KS_ERR_INVALID_ARG, "pileup: the cigars hold %llu regions in %llu hit rows, the alignments %llu in %llu: not traced from them",
                            (unsigned long long)cigars->n_regions, (unsigned long long)cigars->n_rows, (unsigned long long)alignments->n_regions,

@@ -20,6 +20,10 @@
 //              wave-uniform), and the chunk's target window — RA_CHUNK + 2W bytes — goes upper-cased and classified into the
 //              wave's own LDS strip; a row reads strip[r + k].  No global load depends on a row.  The left side is the same
 //              function with descending addresses.
+//   scorer     what a pair scores is a policy (SC), as in ks_rkit.h: ra_by_matrix reads the matrix row of the row's query byte
+//              in LDS.  ra_by_profile stages the chunk's RA_CHUNK rows of the profile — 64 x 28 bytes, 7 words a row, a row of
+//              the program after the other, descending batch positions on the left side — into the wave's own LDS rows beside
+//              the target window, and a cell reads rows[r][class(T_y)]: again no global load depends on a row.
 //   result     every lane keeps its best cell, replaced by strictly larger values only (its smallest x); one 64-bit wave
 //              maximum of (H, -x, -lane) at the end picks the largest H, then the smallest x, then the smallest y.  The row
 //              maximum for the X-drop rule is one DPP max scan per row; the exit is wave-uniform.
@@ -87,12 +91,45 @@ KS_DEV u32 ra_e_src(const ra_e &S, u32 lane) {
     return 63u - (u32)__clzll((long long)(rec | 1ULL));
 }
 
+struct ra_by_matrix {
+    const signed char *s_M;
+    KS_DEV void stage(i64, u32, u32, u32) const {}
+    KS_DEV const signed char *row(u32, u32 cq) const { return s_M + rk_class(cq) * RK_A; }
+};
+#define RA_ROW_WORDS (RK_A / 4) // a profile row as u32 words
+static_assert(RK_A % 4 == 0, "a profile row is whole words: rows are staged word by word");
+struct ra_by_profile {
+    const u32 *P; // the profile's scores as words (a pool block: aligned)
+    i64 qx;       // the batch position of Q_0, the anchor's query residue
+    u32 *s_rows;  // the wave's own RA_CHUNK x RA_ROW_WORDS words
+    // rows base + 1 .. base + n_rows of the program: Q_x lies at batch position qx + sgn * x (inside its sequence: x <= X)
+    KS_DEV void stage(i64 sgn, u32 base, u32 n_rows, u32 lane) const {
+        for (u32 w = lane; w < n_rows * RA_ROW_WORDS; w += 64) {
+            const u32 r = w / RA_ROW_WORDS;
+            s_rows[w] = P[(u64)(qx + sgn * (i64)((u64)base + 1 + r)) * RA_ROW_WORDS + (w - r * RA_ROW_WORDS)];
+        }
+    }
+    KS_DEV const signed char *row(u32 r, u32) const { return (const signed char *)(s_rows + r * RA_ROW_WORDS); }
+};
+
+// what k_ralign and k_rt_trace do alike around ra_extend: the scorer of a wave, and the anchor pair's score.  `table`: the
+// kernel's rk_in.matrix (PROFILE: the profile's scores); qx: the batch position of the anchor's query residue
+template <bool PROFILE> using ra_scorer = std::conditional_t<PROFILE, ra_by_profile, ra_by_matrix>;
+template <bool PROFILE> KS_DEV ra_scorer<PROFILE> ra_scorer_of(const signed char *table, u64 qx, const signed char *s_M, u32 *s_rows) {
+    if constexpr (PROFILE) return ra_by_profile{(const u32 *)table, (i64)qx, s_rows};
+    else return ra_by_matrix{s_M};
+}
+template <bool PROFILE> KS_DEV int ra_anchor_score(const signed char *table, u64 qx, const u8 *s_cls, const signed char *s_M, u32 cq, u32 ct) {
+    if constexpr (PROFILE) return rk_by_profile{s_cls, table}.pair(qx, cq, ct);
+    else return rk_by_matrix{s_cls, s_M}.pair(qx, cq, ct);
+}
+
 // One side's extension (all 64 lanes enter; every argument but `lane` and `strip` is wave-uniform).  Q_x = qp[sgn * x] for
 // x = 1 .. X and T_y = tp[sgn * y] for y = 1 .. Y: the caller points qp / tp at the anchor pair.  strip: the wave's own.
 // A: W, o, e, x_drop.  TR: rows 1 .. x_end (the caller has checked x_end <= min(X, Y + W), y_end <= Y, |y_end - x_end| <= W)
 // write their directions to dir[(x - 1) * RA_DIR_ROW + lane]; x, y, score = the end cell and its H, the counts are zero.
-template <bool TR, class Args>
-KS_DEV ra_ext ra_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 X, u32 Y, const Args &A, const u8 *s_cls, const signed char *s_M,
+template <bool TR, class SC, class Args>
+KS_DEV ra_ext ra_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 X, u32 Y, const Args &A, const u8 *s_cls, const SC &sc,
                         unsigned short *strip, u32 lane, u8 *dir = nullptr, u32 x_end = 0, u32 y_end = 0) {
     const u32 W = A.W, ke = lane * A.e;
     const int oe = (int)(A.o + A.e), e = (int)A.e, o = (int)A.o;
@@ -123,15 +160,17 @@ KS_DEV ra_ext ra_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 X, u32 Y, const
             }
             strip[j] = (unsigned short)v;
         }
+        sc.stage(sgn, base, n_rows, lane);
         __builtin_amdgcn_wave_barrier();
         for (u32 r = 0; r < n_rows; r++) {
             const u32 x = base + 1 + r;
             const u32 cq = (u32)__builtin_amdgcn_readlane((int)qbyte, (int)r);
-            const u32 cq_up = rk_upper(cq), cq_row = rk_class(cq) * RK_A;
+            const u32 cq_up = rk_upper(cq);
+            const signed char *const s_row = sc.row(r, cq);
             const i64 y = (i64)x + lane - W;
             ex = inband && y >= 0 && y <= (i64)Y;
             const u32 tv = strip[r + lane];
-            const int s = s_M[cq_row + (tv >> 8)];
+            const int s = s_row[tv >> 8];
             const bool idt = (tv & 0xffu) == cq_up;
             // F: what the lane above hands down from the row before (on a tie the continued gap)
             const int gH = H - oe, gF = F - e;

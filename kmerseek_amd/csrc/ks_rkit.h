@@ -12,7 +12,7 @@ struct rk_in {
     const u32 *a, *b, *n; // n_regions: q_start, t_start, length
     const u8 *q_res, *t_res;
     const u64 *q_offs, *t_offs;
-    const signed char *matrix; // device, RK_A x RK_A
+    const signed char *matrix; // device, RK_A x RK_A; in a pass against a profile its scores, n_q_res x RK_A (rk_by_profile)
     u64 n_q_res, n_t_res;
     u32 n_rows, n_regions, n_q, n_t;
 };
@@ -32,6 +32,26 @@ KS_DEV void rk_stage_tables(const signed char *matrix, u8 *s_cls, signed char *s
     s_cls[threadIdx.x] = (u8)rk_class(threadIdx.x);
     for (u32 i = threadIdx.x; i < RK_A * RK_A; i += 256) s_M[i] = matrix[i];
 }
+
+// The scorer of a pass: what the pair of the query residue at batch position qx (its byte cq) and a target byte ct scores.  Two
+// policies on ONE code path (rs_extend and the core loop of k_rscore; ra_by_matrix / ra_by_profile of ks_ralign_kit.h are the
+// same pair for ra_extend): the pass against a profile can never break a tie in another way than the pass under a matrix.
+//   rk_by_matrix   M[class(Q_x)][class(T_y)], the matrix in LDS; the position is not read
+//   rk_by_profile  P[qx][class(T_y)], the profile's rows in global memory; the query byte is not read
+struct rk_by_matrix {
+    static constexpr bool PROFILE = false;
+    const u8 *s_cls;
+    const signed char *s_M;
+    KS_DEV int pair(u64, u32 cq, u32 ct) const { return s_M[s_cls[cq] * RK_A + s_cls[ct]]; }
+};
+struct rk_by_profile {
+    static constexpr bool PROFILE = true;
+    const u8 *s_cls;
+    const signed char *P;
+    KS_DEV int pair(u64 qx, u32, u32 ct) const { return P[qx * RK_A + s_cls[ct]]; }
+};
+// the class table alone (a pass against a profile stages no matrix)
+KS_DEV void rk_stage_classes(u8 *s_cls) { s_cls[threadIdx.x] = (u8)rk_class(threadIdx.x); }
 
 // Sequences q < I.n_q and t < I.n_t — the caller has checked the two ids — of the batches of I (any struct with q_offs, t_offs,
 // n_q_res, n_t_res): their first residues in the batches and their lengths.  ok: both lie inside their batches.  UNIFORM: q

@@ -12,6 +12,9 @@
 //              strictly larger sum: a maximum attained again later never wins against the shorter extension.
 // The sums inside a step fit 32 bits (64 x 128); across steps S and B are i64.  Everything a wave decides is wave-uniform and
 // kept in scalar registers (readfirstlane): the ballots and the DPP scans see whole waves.
+//
+// ks_regions_score_profile is the same kernel with the other scorer (ks_rkit.h: rk_by_matrix / rk_by_profile): no matrix in LDS,
+// a pair reads P[batch position of Q_x][class(T_y)] from the profile's rows, a gather behind the target byte.
 #include "ks_rkit.h"
 
 #define RS_THREADS 256
@@ -30,8 +33,10 @@ struct rs_args {
 struct rs_ext { u32 len; i64 score; u32 ident, pos; };
 
 // One side's extension (all 64 lanes enter; every argument but `lane` is wave-uniform).  Pair j = 1 .. e_max is
-// (qp[sgn * j], tp[sgn * j]): the caller points qp / tp at the position next to the core on the other side of the walk.
-KS_DEV rs_ext rs_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 e_max, u32 x_drop, const u8 *s_cls, const signed char *s_M, u32 lane) {
+// (qp[sgn * j], tp[sgn * j]): the caller points qp / tp at the position next to the core on the other side of the walk; qx is
+// the batch position of qp[0].
+template <class SC>
+KS_DEV rs_ext rs_extend(const u8 *qp, const u8 *tp, u64 qx, i64 sgn, u32 e_max, u32 x_drop, const SC &sc, u32 lane) {
     i64 S = 0, B = 0;                  // the sum before this step; the best prefix sum so far (S_0 = 0 is one)
     u32 best = 0, id_best = 0, po_best = 0, id_seen = 0, po_seen = 0; // the best prefix's length and counts; the counts before this step
     for (u32 base = 0; base < e_max; base += RS_STEP) {
@@ -42,7 +47,7 @@ KS_DEV rs_ext rs_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 e_max, u32 x_dr
         if (valid) {
             const i64 o = sgn * (i64)((u64)base + lane + 1);
             const u32 cq = qp[o], ct = tp[o];
-            s = s_M[s_cls[cq] * RS_A + s_cls[ct]];
+            s = sc.pair(qx + (u64)o, cq, ct);
             idt = rk_upper(cq) == rk_upper(ct);
         }
         const u32 rel = ks_wave_incl_scan((u32)s); // S_j - S, an i32
@@ -69,11 +74,13 @@ KS_DEV rs_ext rs_extend(const u8 *qp, const u8 *tp, i64 sgn, u32 e_max, u32 x_dr
     return {best, B, id_best, po_best};
 }
 
-__global__ __launch_bounds__(RS_THREADS) void k_rscore(rs_args A) {
+template <bool PROFILE> __global__ __launch_bounds__(RS_THREADS) void k_rscore(rs_args A) {
     __shared__ u8 s_cls[256];
-    __shared__ signed char s_M[RS_A * RS_A];
-    rk_stage_tables(A.in.matrix, s_cls, s_M);
+    __shared__ signed char s_M[PROFILE ? 4 : RS_A * RS_A];
+    if (PROFILE) rk_stage_classes(s_cls);
+    else rk_stage_tables(A.in.matrix, s_cls, s_M);
     __syncthreads();
+    const std::conditional_t<PROFILE, rk_by_profile, rk_by_matrix> sc{s_cls, PROFILE ? A.in.matrix : s_M};
     const u32 lane = threadIdx.x & 63;
     const u64 g64 = (u64)blockIdx.x * (RS_THREADS / 64) + ks_readfirst(threadIdx.x >> 6);
     if (g64 >= A.in.n_regions) return;
@@ -89,21 +96,21 @@ __global__ __launch_bounds__(RS_THREADS) void k_rscore(rs_args A) {
         return;
     }
     const u8 *qc = A.in.q_res + P.qb + a, *tc = A.in.t_res + P.tb + b; // the core's first pair
-    i64 sc = 0;
+    i64 sum = 0;
     u32 id = 0, po = 0;
     for (u64 i = lane; i < n; i += 64) {
         const u32 cq = qc[i], ct = tc[i];
-        const int s = s_M[s_cls[cq] * RS_A + s_cls[ct]];
-        sc += s; id += rk_upper(cq) == rk_upper(ct) ? 1u : 0u; po += s > 0 ? 1u : 0u;
+        const int s = sc.pair(P.qb + a + i, cq, ct);
+        sum += s; id += rk_upper(cq) == rk_upper(ct) ? 1u : 0u; po += s > 0 ? 1u : 0u;
     }
-    i64 score = (i64)ks_wave_sum64((u64)sc);
+    i64 score = (i64)ks_wave_sum64((u64)sum);
     const u64 counts = ks_wave_sum64(((u64)id << 32) | po); // (each below 2^32: n is a u32)
     const u32 core_ident = (u32)(counts >> 32);
     u32 ident = core_ident, pos = (u32)counts, left = 0, right = 0;
     if (A.extend) {
         const u64 er = Lq - ((u64)a + n) < Lt - ((u64)b + n) ? Lq - ((u64)a + n) : Lt - ((u64)b + n);
-        const rs_ext R = rs_extend(qc + n - 1, tc + n - 1, 1, (u32)er, A.x_drop, s_cls, s_M, lane);
-        const rs_ext L = rs_extend(qc, tc, -1, a < b ? a : b, A.x_drop, s_cls, s_M, lane);
+        const rs_ext R = rs_extend(qc + n - 1, tc + n - 1, P.qb + a + n - 1, 1, (u32)er, A.x_drop, sc, lane);
+        const rs_ext L = rs_extend(qc, tc, P.qb + a, -1, a < b ? a : b, A.x_drop, sc, lane);
         left = L.len; right = R.len;
         score += L.score + R.score; ident += L.ident + R.ident; pos += L.pos + R.pos;
     }
@@ -114,7 +121,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_rscore(rs_args A) {
 }
 
 int ks_regions_score_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
-                          const ks_rscore_opts *opts, ks_rscores *S) {
+                          const ks_rscore_opts *opts, const ks_profile *prof, ks_rscores *S) {
     const u64 n_rows = R->n_rows, ng = R->n_regions;
     S->n_rows = n_rows; S->n_regions = ng;
     KS_TRY(ks_alloc(ctx, &S->d_row_offsets, (size_t)n_rows + 1));
@@ -126,16 +133,18 @@ int ks_regions_score_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, co
     ks_scratch sc(ctx);
     signed char *d_M = nullptr;
     u64 *bad = nullptr;
-    KS_TRY(rk_upload_matrix(ctx, sc, opts ? opts->matrix : nullptr, &d_M));
+    if (!prof) KS_TRY(rk_upload_matrix(ctx, sc, opts ? opts->matrix : nullptr, &d_M));
     KS_TRY(sc.alloc(&bad, 1));
     KS_HIP(ctx, hipMemsetAsync(bad, 0xff, sizeof(u64), ctx->stream));
 
     rs_args A;
-    A.in = rk_in_of(R, H, Q, T, d_M);
+    A.in = rk_in_of(R, H, Q, T, prof ? (const signed char *)prof->d_scores : d_M);
     A.extend = opts && (opts->flags & KS_RSCORE_EXTEND) ? 1u : 0u; A.x_drop = opts ? opts->x_drop : 0u;
     A.o_a = S->d_qstart; A.o_b = S->d_tstart; A.o_n = S->d_length; A.o_ident = S->d_identities; A.o_pos = S->d_positives;
     A.o_core_ident = S->d_core_ident; A.o_score = S->d_score; A.bad = (unsigned long long *)bad;
-    KS_LAUNCH(ctx, "rscore", k_rscore, (u32)((ng + RS_THREADS / 64 - 1) / (RS_THREADS / 64)), RS_THREADS, A);
+    const u32 grid = (u32)((ng + RS_THREADS / 64 - 1) / (RS_THREADS / 64));
+    if (prof) KS_LAUNCH(ctx, "rscore_profile", k_rscore<true>, grid, RS_THREADS, A);
+    else KS_LAUNCH(ctx, "rscore", k_rscore<false>, grid, RS_THREADS, A);
     u64 *const hb = ctx->h_pin + KS_PIN_RSCORE;
     const ks_fetch_seg f = ks_fetch_words(bad, hb, 2);
     KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
@@ -157,6 +166,14 @@ int rk_upload_matrix(ks_ctx *ctx, ks_scratch &sc, const int8_t *h_matrix, signed
     if (h_matrix) memcpy(h_M, h_matrix, sizeof h_M);
     else for (int i = 0; i < RK_A * RK_A; i++) h_M[i] = (i / RK_A == i % RK_A) ? 1 : -1;
     return ks_copy_h2d(ctx, *d_M, h_M, sizeof h_M); // (a pageable source: consumed on return)
+}
+int rk_profile_check(ks_ctx *ctx, const char *pass, const ks_profile *prof, const ks_res_batch &Q) {
+    if (!prof) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(ks_inputs_check_ctx(ctx, pass, prof));
+    if (prof->n_residues != Q.n_res)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "%s: the profile holds %llu residues, the query batch %llu: a profile of another batch", pass,
+                       (unsigned long long)prof->n_residues, (unsigned long long)Q.n_res);
+    return KS_OK;
 }
 int rk_fail_bad_row(ks_ctx *ctx, const char *pass, u64 row, const ks_res_batch &Q, const ks_res_batch &T) {
     return ks_fail(ctx, KS_ERR_INVALID_ARG,

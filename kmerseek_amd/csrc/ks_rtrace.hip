@@ -1,5 +1,5 @@
 // ks_rtrace.hip — ks_regions_traceback: the path of every alignment of a ks_raligns, as a CIGAR (include/kmerseek_amd.h has
-// the semantics).  The forward program is the one of ks_regions_align — ra_extend<true> of ks_ralign_kit.h, the same row step
+// the semantics; ks_regions_traceback_profile: k_rt_trace with the scorer the alignments were made with, ra_by_profile).  The forward program is the one of ks_regions_align — ra_extend<true> of ks_ralign_kit.h, the same row step
 // with the counts left out — run again to the end cell the alignment names, writing one direction byte per cell; then a walk
 // back from the end cell to (0, 0).  All of it in integers.
 //
@@ -77,12 +77,14 @@ struct rt_slice {
     u32 g0, g1;
 };
 
-__global__ __launch_bounds__(RT_THREADS) void k_rt_trace(rt_args A, rt_slice Z) {
+template <bool PROFILE> __global__ __launch_bounds__(RT_THREADS) void k_rt_trace(rt_args A, rt_slice Z) {
     __shared__ u8 s_cls[256];
-    __shared__ signed char s_M[RK_A * RK_A];
+    __shared__ signed char s_M[PROFILE ? 4 : RK_A * RK_A];
     __shared__ unsigned short s_strip[RT_THREADS / 64][RA_STRIP];
     __shared__ uint4 s_stage[RT_THREADS / 64][RP_STAGE * RA_DIR_ROW / 16];
-    rk_stage_tables(A.in.matrix, s_cls, s_M);
+    __shared__ u32 s_rows[RT_THREADS / 64][PROFILE ? RA_CHUNK * RA_ROW_WORDS : 1];
+    if (PROFILE) rk_stage_classes(s_cls);
+    else rk_stage_tables(A.in.matrix, s_cls, s_M);
     __syncthreads();
     const u32 lane = threadIdx.x & 63, wave = ks_readfirst(threadIdx.x >> 6);
     const u64 g64 = (u64)Z.g0 + (u64)blockIdx.x * (RT_THREADS / 64) + wave;
@@ -97,14 +99,15 @@ __global__ __launch_bounds__(RT_THREADS) void k_rt_trace(rt_args A, rt_slice Z) 
     const u32 Lq = (u32)P.Lq, Lt = (u32)P.Lt;
     const u8 *qa = A.in.q_res + P.qb + G.ai, *ta = A.in.t_res + P.tb + G.bj;
     const u32 cq = ks_readfirst(*qa), ct = ks_readfirst(*ta);
-    const int s = s_M[s_cls[cq] * RK_A + s_cls[ct]];
-    const ra_ext R = ra_extend<true>(qa, ta, 1, Lq - 1 - G.ai, Lt - 1 - G.bj, A, s_cls, s_M, s_strip[wave], lane, dR, G.xr, G.yr);
+    const ra_scorer<PROFILE> sc = ra_scorer_of<PROFILE>(A.in.matrix, P.qb + G.ai, s_M, s_rows[wave]);
+    const int s = ra_anchor_score<PROFILE>(A.in.matrix, P.qb + G.ai, s_cls, s_M, cq, ct);
+    const ra_ext R = ra_extend<true>(qa, ta, 1, Lq - 1 - G.ai, Lt - 1 - G.bj, A, s_cls, sc, s_strip[wave], lane, dR, G.xr, G.yr);
     rp_publish();
     // (the lane of an end cell, y + W - x, is 0 .. 2W: rt_geometry)
     const u32 nR = rp_walk<false>(dR, G.xr, G.yr + A.W - G.xr, A.W, 2 * A.W, RP_D, RP_I, col + (G.alen - 1), -1, G.alen - 1, s_stage[wave], lane);
     bool ok = nR != RP_BAD;
     if (ok) {
-        const ra_ext L = ra_extend<true>(qa, ta, -1, G.ai, G.bj, A, s_cls, s_M, s_strip[wave], lane, dL, G.xl, G.yl);
+        const ra_ext L = ra_extend<true>(qa, ta, -1, G.ai, G.bj, A, s_cls, sc, s_strip[wave], lane, dL, G.xl, G.yl);
         rp_publish();
         const u32 nL = rp_walk<false>(dL, G.xl, G.yl + A.W - G.xl, A.W, 2 * A.W, RP_D, RP_I, col, 1, G.alen - 1 - nR, s_stage[wave], lane);
         ok = nL != RP_BAD && nL + 1 + nR == G.alen && (i64)s + L.score + R.score == A.s_score[g];
@@ -175,7 +178,7 @@ template <bool WRITE> __global__ __launch_bounds__(RT_THREADS) void k_rt_runs(rt
 }
 
 int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H, const ks_res_batch &Q, const ks_res_batch &T,
-                              const ks_raligns *S, u32 flags, u64 max_scratch_bytes, ks_cigars *C) {
+                              const ks_raligns *S, const ks_profile *prof, u32 flags, u64 max_scratch_bytes, ks_cigars *C) {
     const u64 n_rows = R->n_rows, ng = R->n_regions;
     C->n_rows = n_rows; C->n_regions = ng;
     KS_TRY(ks_alloc(ctx, &C->d_op_offsets, (size_t)ng + 1));
@@ -190,13 +193,13 @@ int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H
     ks_ctl ctl;
     u32 *rows = nullptr, *ncols = nullptr;
     u64 *dir_off = nullptr, *col_off = nullptr;
-    KS_TRY(rk_upload_matrix(ctx, sc, S->matrix, &d_M));
+    if (!prof) KS_TRY(rk_upload_matrix(ctx, sc, S->matrix, &d_M));
     KS_TRY(ctl.init(ctx, sc, KS_PIN_RTRACE, RT_N_BAD, 0));
     KS_TRY(sc.alloc(&rows, (size_t)ng)); KS_TRY(sc.alloc(&ncols, (size_t)ng));
     KS_TRY(sc.alloc(&dir_off, (size_t)ng + 1)); KS_TRY(sc.alloc(&col_off, (size_t)ng + 1));
 
     rt_args A;
-    A.in = rk_in_of(R, H, Q, T, d_M);
+    A.in = rk_in_of(R, H, Q, T, prof ? (const signed char *)prof->d_scores : d_M);
     A.W = S->band; A.o = S->gap_open; A.e = S->gap_extend; A.x_drop = S->x_drop;
     A.s_qs = S->d_qstart; A.s_ql = S->d_qlength; A.s_ts = S->d_tstart; A.s_tl = S->d_tlength; A.s_len = S->d_aln_length;
     A.s_score = S->d_score;
@@ -232,7 +235,9 @@ int ks_regions_traceback_impl(ks_ctx *ctx, const ks_regions *R, const ks_hits *H
     C->dir_bytes = slice_rows * RA_DIR_ROW; C->n_slices = (u32)(cut.size() - 1);
     for (size_t i = 0; i + 1 < cut.size(); i++) { // (one block for all slices: the launches are ordered by the stream)
         const rt_slice Z{dir_off, col_off, dir, cols, first_row[i], (u32)cut[i], (u32)cut[i + 1]};
-        KS_LAUNCH(ctx, "rtrace", k_rt_trace, (u32)((cut[i + 1] - cut[i] + RT_THREADS / 64 - 1) / (RT_THREADS / 64)), RT_THREADS, A, Z);
+        const u32 slice_grid = (u32)((cut[i + 1] - cut[i] + RT_THREADS / 64 - 1) / (RT_THREADS / 64));
+        if (prof) KS_LAUNCH(ctx, "rtrace_profile", k_rt_trace<true>, slice_grid, RT_THREADS, A, Z);
+        else KS_LAUNCH(ctx, "rtrace", k_rt_trace<false>, slice_grid, RT_THREADS, A, Z);
     }
 
     // the runs per region (`rows` is free again), their scan = op_offsets, the ops

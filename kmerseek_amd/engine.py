@@ -96,6 +96,15 @@ def _int_in(name: str, v, top: int, shown: Optional[str] = None) -> int:
     return int(v)
 
 
+def _profile_or_matrix(profile, matrix):
+    """profile= of a region pass: a Profile or None, exclusive with matrix=; returns it."""
+    if profile is not None and not isinstance(profile, Profile):
+        raise TypeError("profile= takes a Profile (Context.build_profile)")
+    if profile is not None and matrix is not None:
+        raise ValueError("profile= and matrix= are exclusive: a pair scores under the one or the other")
+    return profile
+
+
 PILEUP_SIDES = {"query": _lib.KS_PILEUP_QUERY, "target": _lib.KS_PILEUP_TARGET}
 
 
@@ -121,6 +130,73 @@ def karlin_ungapped(matrix, freq_q, freq_t) -> Tuple[float, float, float]:
     if st != _lib.KS_OK:
         raise KmerseekError(st, "karlin_ungapped: " + (L.ks_karlin_last_error() or L.ks_status_string(st)).decode())
     return lam.value, K.value, H.value
+
+
+STANDARD_CLASSES = tuple(ord(c) - 65 for c in "ACDEFGHIKLMNPQRSTVWY")  # the 20 residue classes karlin_ungapped counts
+
+
+class ProfileParams:
+    """The options of Context.build_profile (ks_profile_opts), all host data: matrix int8 [28, 28] (the fallback; None: +1 / -1),
+    bg f64 [28] >= 0 (a class with bg == 0 is unmodelled), ratio f64 [28, 28] (R[j][c]), beta >= 0, thresholds f64 [n <= 254]
+    strictly ascending, base (the score below the first threshold) and include_query.  include/kmerseek_amd.h has the rule;
+    profile_params makes them from a matrix.  ValueError for what the library would refuse."""
+
+    def __init__(self, matrix, bg, ratio, beta: float, thresholds, base: int, include_query: bool = True):
+        A = _lib.KS_RSCORE_ALPHABET
+        self.matrix = _matrix28(matrix)
+        self.bg = np.ascontiguousarray(bg, dtype=np.float64)
+        self.ratio = np.ascontiguousarray(ratio, dtype=np.float64)
+        self.thresholds = np.ascontiguousarray(thresholds, dtype=np.float64)
+        self.beta, self.include_query = float(beta), bool(include_query)
+        if self.bg.shape != (A,) or self.ratio.shape != (A, A) or self.thresholds.ndim != 1:
+            raise ValueError("bg must hold 28 weights, ratio 28 x 28 values, thresholds one row")
+        if len(self.thresholds) > _lib.KS_PROFILE_MAX_THRESHOLDS:
+            raise ValueError(f"{len(self.thresholds)} thresholds: at most {_lib.KS_PROFILE_MAX_THRESHOLDS}")
+        if np.isnan(self.bg).any() or np.isnan(self.ratio).any() or np.isnan(self.thresholds).any() or self.beta != self.beta:
+            raise ValueError("a NaN among bg, ratio, beta or the thresholds")
+        if (self.bg < 0).any() or self.beta < 0:
+            raise ValueError("a negative bg or beta")
+        if not (np.diff(self.thresholds) > 0).all():
+            raise ValueError("the thresholds do not ascend strictly")
+        self.base = _int_in("base + 2^31", int(base) + 2 ** 31, 2 ** 32 - 1, "[0, 2^32): base is a 32-bit integer") - 2 ** 31
+
+    def _opts(self):
+        """(ks_profile_opts, the arrays its pointers read: keep them alive for the call)"""
+        dp = C.POINTER(C.c_double)
+        mp = self.matrix.ctypes.data_as(C.POINTER(C.c_int8)) if self.matrix is not None else None
+        th = self.thresholds.ctypes.data_as(dp) if len(self.thresholds) else None
+        return _lib.ks_profile_opts(mp, self.bg.ctypes.data_as(dp), self.ratio.ctypes.data_as(dp), self.beta, th, len(self.thresholds), self.base,
+                                    _lib.KS_PROFILE_INCLUDE_QUERY if self.include_query else 0, 0), self
+
+
+def profile_params(matrix, freq=None, beta: float = 10.0, include_query: bool = True) -> ProfileParams:
+    """ProfileParams in the units of `matrix` (int8 [28, 28], None: +1 / -1).  freq: 28 background weights of which the 20
+    standard classes count, renormalised (None: uniform over them); every other class is unmodelled and keeps the matrix's
+    entries.  With lambda = karlin_ungapped(matrix, bg, bg): ratio = exp(lambda * matrix), base = min(matrix) - 8 and
+    thresholds[k] = exp(lambda * (base + k + 0.5)) up to max(matrix) + 8 — a score is ln r / lambda rounded to the nearest
+    integer, clamped to that range.  The device and the tests' host loop read these very tables: no libm shows in a result."""
+    A = _lib.KS_RSCORE_ALPHABET
+    m = _matrix28(matrix)
+    if m is None:
+        m = (2 * np.eye(A, dtype=np.int8) - 1).astype(np.int8)
+    w = np.full(A, 1.0) if freq is None else np.ascontiguousarray(freq, dtype=np.float64)
+    if w.shape != (A,) or np.isnan(w).any() or (w < 0).any():
+        raise ValueError("freq must hold 28 weights >= 0")
+    bg = np.zeros(A)
+    bg[list(STANDARD_CLASSES)] = w[list(STANDARD_CLASSES)]
+    if not bg.sum() > 0:
+        raise ValueError("freq gives the 20 standard residue classes no weight")
+    bg /= bg.sum()
+    # lambda alone (ks_karlin_ungapped with K == NULL): the series for K does not settle for every matrix a profile can be made of
+    L, lam, dp = _lib.load(), C.c_double(0), C.POINTER(C.c_double)
+    st = L.ks_karlin_ungapped(m.ctypes.data_as(C.POINTER(C.c_int8)), bg.ctypes.data_as(dp), bg.ctypes.data_as(dp), C.byref(lam), None, None)
+    if st != _lib.KS_OK:
+        raise KmerseekError(st, "profile_params: " + (L.ks_karlin_last_error() or L.ks_status_string(st)).decode())
+    lam = lam.value
+    base = int(m.min()) - 8
+    n_thr = min(int(m.max()) + 8 - base, _lib.KS_PROFILE_MAX_THRESHOLDS)
+    thresholds = np.exp(lam * (base + np.arange(n_thr) + 0.5))
+    return ProfileParams(m, bg, np.exp(lam * m.astype(np.float64)), beta, thresholds, base, include_query)
 
 
 def search_opts(min_containment: float = 0.0, abund_stats: bool = False) -> Optional[_lib.ks_search_opts]:
@@ -641,25 +717,33 @@ class Context:
 
     def score_regions_device(self, regions: "Regions", hits: "Hits", d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
                              d_t_res: int, d_t_off: int, n_t: int, n_t_res: int, matrix=None, extend: bool = False,
-                             x_drop: int = 0) -> "RegionScores":
+                             x_drop: int = 0, profile: Optional["Profile"] = None) -> "RegionScores":
         """ks_regions_score from device-resident residue batches (raw pointers: residues u8, offsets u64[n + 1]): every region
         of `regions` — chained for the rows of `hits` — scored under `matrix` (int8 [28, 28], the query's residue class is the
         row: A..Z, '*', everything else; None: +1 / -1) and, with extend=True, extended without gaps to both sides under the
         X-drop rule.  Per region the (extended) q_start, t_start, length, the score (i64), identities and positives over the
-        extended span and the identities of the seed region alone; include/kmerseek_amd.h has the definitions."""
+        extended span and the identities of the seed region alone; include/kmerseek_amd.h has the definitions.
+        profile= (a Profile of the query batch, exclusive with matrix=): ks_regions_score_profile, a pair scores the profile's
+        row of the query residue's position."""
+        _profile_or_matrix(profile, matrix)
         opts, keep = self._rscore_opts(matrix, extend, x_drop)
         out = C.c_void_p()
-        self._check(self._L.ks_regions_score(self._h, regions._h, hits._h, C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res),
-                                             C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res), C.byref(opts), C.byref(out)))
+        batches = (C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res), C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res))
+        if profile is not None:
+            self._check(self._L.ks_regions_score_profile(self._h, regions._h, hits._h, *batches, profile._h, C.byref(opts), C.byref(out)))
+        else:
+            self._check(self._L.ks_regions_score(self._h, regions._h, hits._h, *batches, C.byref(opts), C.byref(out)))
         del keep
         return RegionScores(self, out)
 
     def score_regions(self, regions: "Regions", hits: "Hits", q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray,
-                      t_off: np.ndarray, matrix=None, extend: bool = False, x_drop: int = 0) -> "RegionScores":
+                      t_off: np.ndarray, matrix=None, extend: bool = False, x_drop: int = 0,
+                      profile: Optional["Profile"] = None) -> "RegionScores":
         """score_regions_device from host arrays (the batches `hits` was searched on): uploaded, scored, released."""
+        _profile_or_matrix(profile, matrix)
         self._rscore_opts(matrix, extend, x_drop)  # (refused before anything is uploaded)
         with self._batches(q_res, q_off, t_res, t_off) as b:
-            return self.score_regions_device(regions, hits, *b, matrix=matrix, extend=extend, x_drop=x_drop)
+            return self.score_regions_device(regions, hits, *b, matrix=matrix, extend=extend, x_drop=x_drop, profile=profile)
 
     @staticmethod
     def _ralign_opts(matrix, band: int, gap_open: int, gap_extend: int, x_drop: int):
@@ -673,27 +757,35 @@ class Context:
 
     def align_regions_device(self, regions: "Regions", hits: "Hits", d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
                              d_t_res: int, d_t_off: int, n_t: int, n_t_res: int, matrix=None, band: int = 16, gap_open: int = 11,
-                             gap_extend: int = 1, x_drop: int = 30) -> "RegionAlignments":
+                             gap_extend: int = 1, x_drop: int = 30, profile: Optional["Profile"] = None) -> "RegionAlignments":
         """ks_regions_align from device-resident residue batches (raw pointers: residues u8, offsets u64[n + 1]): every region
         of `regions` — chained for the rows of `hits` — extended with gaps from the middle pair of its seed to both sides: a
         banded (|diagonal shift| <= band <= 31) affine-gap (a gap of L residues costs gap_open + L * gap_extend, each <= 255)
         dynamic program under `matrix` (as score_regions), stopped by a row-level X-drop (x_drop <= 2^20).  Per region the
         alignment's q_start, q_length, t_start, t_length, score (i64), identities, positives, gap_opens, gaps and aln_length;
-        the path itself is trace_regions'.  include/kmerseek_amd.h has the definitions."""
+        the path itself is trace_regions'.  include/kmerseek_amd.h has the definitions.
+        profile= (a Profile of the query batch, exclusive with matrix=): ks_regions_align_profile; the result is profile-made
+        (RegionAlignments.by_profile) and only trace_regions(..., profile=) walks its paths."""
+        _profile_or_matrix(profile, matrix)
         opts, keep = self._ralign_opts(matrix, band, gap_open, gap_extend, x_drop)
         out = C.c_void_p()
-        self._check(self._L.ks_regions_align(self._h, regions._h, hits._h, C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res),
-                                             C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res), C.byref(opts), C.byref(out)))
+        batches = (C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res), C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res))
+        if profile is not None:
+            self._check(self._L.ks_regions_align_profile(self._h, regions._h, hits._h, *batches, profile._h, C.byref(opts), C.byref(out)))
+        else:
+            self._check(self._L.ks_regions_align(self._h, regions._h, hits._h, *batches, C.byref(opts), C.byref(out)))
         del keep
         return RegionAlignments(self, out)
 
     def align_regions(self, regions: "Regions", hits: "Hits", q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray,
                       t_off: np.ndarray, matrix=None, band: int = 16, gap_open: int = 11, gap_extend: int = 1,
-                      x_drop: int = 30) -> "RegionAlignments":
+                      x_drop: int = 30, profile: Optional["Profile"] = None) -> "RegionAlignments":
         """align_regions_device from host arrays (the batches `hits` was searched on): uploaded, aligned, released."""
+        _profile_or_matrix(profile, matrix)
         self._ralign_opts(matrix, band, gap_open, gap_extend, x_drop)  # (refused before anything is uploaded)
         with self._batches(q_res, q_off, t_res, t_off) as b:
-            return self.align_regions_device(regions, hits, *b, matrix=matrix, band=band, gap_open=gap_open, gap_extend=gap_extend, x_drop=x_drop)
+            return self.align_regions_device(regions, hits, *b, matrix=matrix, band=band, gap_open=gap_open, gap_extend=gap_extend, x_drop=x_drop,
+                                             profile=profile)
 
     @staticmethod
     def _rtrace_opts(eqx: bool, max_scratch_bytes: int):
@@ -701,25 +793,30 @@ class Context:
 
     def trace_regions_device(self, regions: "Regions", hits: "Hits", d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
                              d_t_res: int, d_t_off: int, n_t: int, n_t_res: int, alignments: "RegionAlignments", eqx: bool = False,
-                             max_scratch_bytes: int = 0) -> "RegionCigars":
+                             max_scratch_bytes: int = 0, profile: Optional["Profile"] = None) -> "RegionCigars":
         """ks_regions_traceback from device-resident residue batches: the path of every alignment of `alignments` — made by
         align_regions from these regions, hits and batches, whose options it recorded — as a CIGAR with the query as the read:
         M (with eqx=True: = and X), I, D.  max_scratch_bytes bounds the direction scratch of one slice of regions (0: 1 GiB).
-        include/kmerseek_amd.h has the definitions."""
+        include/kmerseek_amd.h has the definitions.  profile=: the Profile the alignments were made against
+        (ks_regions_traceback_profile); alignments made under a matrix take none."""
         opts = self._rtrace_opts(eqx, max_scratch_bytes)
         out = C.c_void_p()
-        self._check(self._L.ks_regions_traceback(self._h, regions._h, hits._h, C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q),
-                                                 int(n_q_res), C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res),
-                                                 alignments._h, C.byref(opts), C.byref(out)))
+        batches = (C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res), C.c_void_p(d_t_res), C.c_void_p(d_t_off), int(n_t), int(n_t_res))
+        if profile is not None:
+            self._check(self._L.ks_regions_traceback_profile(self._h, regions._h, hits._h, *batches, alignments._h, _profile_or_matrix(profile, None)._h,
+                                                             C.byref(opts), C.byref(out)))
+        else:
+            self._check(self._L.ks_regions_traceback(self._h, regions._h, hits._h, *batches, alignments._h, C.byref(opts), C.byref(out)))
         return RegionCigars(self, out)
 
     def trace_regions(self, regions: "Regions", hits: "Hits", q_res: np.ndarray, q_off: np.ndarray, t_res: np.ndarray,
                       t_off: np.ndarray, alignments: "RegionAlignments", eqx: bool = False,
-                      max_scratch_bytes: int = 0) -> "RegionCigars":
+                      max_scratch_bytes: int = 0, profile: Optional["Profile"] = None) -> "RegionCigars":
         """trace_regions_device from host arrays (the batches `alignments` was made on): uploaded, traced, released."""
+        _profile_or_matrix(profile, None)
         self._rtrace_opts(eqx, max_scratch_bytes)  # (refused before anything is uploaded)
         with self._batches(q_res, q_off, t_res, t_off) as b:
-            return self.trace_regions_device(regions, hits, *b, alignments, eqx=eqx, max_scratch_bytes=max_scratch_bytes)
+            return self.trace_regions_device(regions, hits, *b, alignments, eqx=eqx, max_scratch_bytes=max_scratch_bytes, profile=profile)
 
     @staticmethod
     def _rcull_opts(overlap_pct: int, min_score, max_per_row: int):
@@ -985,6 +1082,57 @@ class Context:
                 st = self._L.ks_frames_pileup(self._h, aligned._h, hits._h, d_mask, *side_batch, C.byref(opts), C.byref(out))
             self._check(st)
         return Pileup(self, out)
+
+    def build_profile_device(self, d_counts: int, d_depth: int, d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
+                             params: ProfileParams) -> "Profile":
+        """ks_profile_build_device from raw device pointers: counts u32[n_q_res * 28] and depth u32[n_q_res] as a query-side
+        Pileup with the profile holds them, and the query batch.  Per residue a row of 28 scores, a consensus byte and the
+        observations behind the row; include/kmerseek_amd.h has the rule, params: ProfileParams (profile_params)."""
+        if not isinstance(params, ProfileParams):
+            raise TypeError("params must be a ProfileParams (profile_params)")
+        opts, keep = params._opts()
+        out = C.c_void_p()
+        self._check(self._L.ks_profile_build_device(self._h, C.c_void_p(d_counts), C.c_void_p(d_depth), C.c_void_p(d_q_res), C.c_void_p(d_q_off),
+                                                    int(n_q), int(n_q_res), C.byref(opts), C.byref(out)))
+        del keep
+        return Profile(self, out)
+
+    def build_profile(self, pileup, q_res: np.ndarray, q_off: np.ndarray, params: ProfileParams) -> "Profile":
+        """The Profile of the query batch (q_res, q_off: host arrays) from a Pileup made on its side with profile=True
+        (ks_profile_build_pileup), or from host arrays (counts, depth) that stand for one."""
+        if not isinstance(params, ProfileParams):
+            raise TypeError("params must be a ProfileParams (profile_params)")
+        q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
+        if isinstance(pileup, Pileup):
+            opts, keep = params._opts()
+            out = C.c_void_p()
+            with self._uploaded(q_res, q_off) as (d_q, d_qo):
+                self._check(self._L.ks_profile_build_pileup(self._h, pileup._h, C.c_void_p(d_q), C.c_void_p(d_qo), len(q_off) - 1, len(q_res),
+                                                            C.byref(opts), C.byref(out)))
+            del keep
+            return Profile(self, out)
+        counts, depth = pileup
+        counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1); depth = np.ascontiguousarray(depth, dtype=np.uint32)
+        if len(counts) != _lib.KS_RSCORE_ALPHABET * len(q_res) or len(depth) != len(q_res):
+            raise ValueError("counts must hold 28 entries and depth one per residue of the batch")
+        with self._uploaded(counts, depth, q_res, q_off) as (d_c, d_d, d_q, d_qo):
+            return self.build_profile_device(d_c, d_d, d_q, d_qo, len(q_off) - 1, len(q_res), params)
+
+    def profile_from_host(self, scores, n_seqs: int, matrix=None, consensus=None, n_obs=None) -> "Profile":
+        """ks_profile_from_host: a Profile whose rows the caller brings — scores int8 [n_residues, 28] of a batch of n_seqs
+        sequences; matrix: the fallback to record (None: +1 / -1)."""
+        sc = np.ascontiguousarray(scores)
+        if sc.dtype != np.int8 or sc.ndim != 2 or sc.shape[1] != _lib.KS_RSCORE_ALPHABET:
+            raise ValueError("scores must be an int8 array of shape (n_residues, 28)")
+        m = _matrix28(matrix)
+        cons = None if consensus is None else np.ascontiguousarray(consensus, dtype=np.uint8)
+        nobs = None if n_obs is None else np.ascontiguousarray(n_obs, dtype=np.uint32)
+        if any(c is not None and c.shape != (len(sc),) for c in (cons, nobs)):
+            raise ValueError("consensus and n_obs hold one entry per residue")
+        out = C.c_void_p()
+        self._check(self._L.ks_profile_from_host(self._h, _ptr(sc), _ptr(cons), _ptr(nobs), _int_in("n_seqs", n_seqs, 2 ** 32 - 1), len(sc), _ptr(m),
+                                                 C.byref(out)))
+        return Profile(self, out)
 
     def residue_composition_device(self, d_res: int, d_off: int, n_seqs: int, n_res: int) -> "Composition":
         """ks_residue_composition_device from a device-resident residue batch (raw pointers: residues u8, offsets
@@ -1399,6 +1547,7 @@ class _Columns(_Owned):
     device_ptrs(), to_host(), _COLUMNS (the column names) and the count properties come from these; the docstrings of the two
     methods list the table."""
     _PREFIX, _COUNTS, _TABLE = None, {}, ()
+    _VIEWS = {}  # {column: dtype}: a column whose bytes to_host() hands out under another dtype of the same size
 
     def __init_subclass__(cls, **kw):
         super().__init_subclass__(**kw)
@@ -1420,7 +1569,7 @@ class _Columns(_Owned):
         counts = {c: getattr(self, c) for c in self._COUNTS}
         cols = [np.zeros(eval(n, {"__builtins__": {}}, counts), dt) if name in names else None for name, dt, n in self._TABLE]
         self._ctx._check(getattr(self._ctx._L, f"ks_{self._PREFIX}_copy_to_host")(self._ctx._h, self._h, *[_ptr(c) for c in cols]))
-        return tuple(c for c in cols if c is not None)
+        return tuple(c.view(self._VIEWS[name]) if name in self._VIEWS else c for c, (name, _, _) in zip(cols, self._TABLE) if c is not None)
 
     def to_host(self) -> Tuple[np.ndarray, ...]:
         return self._copy_out(self._COLUMNS)
@@ -1480,6 +1629,13 @@ class RegionAlignments(_Columns):
     _TABLE = (("row_offsets", "u8", "n_rows + 1"),) + tuple(
         (c, "i8" if c == "score" else "u4", "n_regions") for c in ("q_start", "q_length", "t_start", "t_length", "score", "identities",
                                                                     "positives", "gap_opens", "gaps", "aln_length"))
+
+
+    @property
+    def by_profile(self) -> bool:
+        """Made against a Profile (align_regions(..., profile=)): trace_regions needs that profile, and the passes that read
+        residues under a matrix (stitch, fold, alignment_stats, pileup) refuse the object."""
+        return bool(self._ctx._L.ks_raligns_by_profile(self._h))
 
 
 CIGAR_OPS = "MIDNSHP=X"  # the BAM op codes
@@ -1691,6 +1847,30 @@ class Pileup(_Columns):
     def depth_ptr(self) -> int:
         """The device column depth u32[n_residues]."""
         return int(self._ctx._L.ks_pileup_device_depth(self._h) or 0)
+
+
+class Profile(_Columns):
+    """Device-resident position-specific scores of a query batch (ks_profile, Context.build_profile): per residue of the batch
+    (batch coordinates offsets[seq] + position) a row of 28 scores (reshape(-1, 28); the classes of Composition), the
+    consensus byte and n_obs, the observations behind the row (0: the row is the fallback matrix's).  The C ABI hands the
+    scores out as bytes; to_host() gives them as the int8 they are."""
+    _PREFIX = "profile"
+    _COUNTS = {"n_seqs": "", "n_residues": "", "n_scores": "Entries of scores: 28 x n_residues."}
+    _TABLE = (("scores", "u1", "n_scores"), ("consensus", "u1", "n_residues"), ("n_obs", "u4", "n_residues"))
+    _VIEWS = {"scores": np.int8}
+
+    @property
+    def scores_ptr(self) -> int:
+        """The device column scores i8[n_residues * 28]."""
+        return int(self._ctx._L.ks_profile_device_scores(self._h) or 0)
+
+    def consensus_strings(self, offsets) -> List[str]:
+        """The consensus of every sequence of the batch as text (offsets: the batch's, n_seqs + 1)."""
+        offs = [int(v) for v in np.asarray(offsets).tolist()]
+        if len(offs) != self.n_seqs + 1 or (offs and offs[-1] != self.n_residues):
+            raise ValueError(f"the profile is of {self.n_seqs} sequences and {self.n_residues} residues: offsets of another batch")
+        text = self._copy_out(("consensus",))[0].tobytes().decode("latin-1")
+        return [text[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)]
 
 
 class Composition(_Columns):

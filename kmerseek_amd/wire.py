@@ -723,7 +723,7 @@ def read_score_matrix(path: str) -> np.ndarray:
 
 
 def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tuple[str, bytes]], qid, tid, regions_host,
-                moltype: str, scores=None, alignments=None, cigars=None, cull=None, chain=None, stats=None) -> List[dict]:
+                moltype: str, scores=None, alignments=None, cigars=None, cull=None, chain=None, stats=None, pssm=None) -> List[dict]:
     """One row per region of the device's chaining (Context.match_regions; regions_host = Regions.to_host()): hit row
     r = (qid[r], tid[r]) owns regions [row_offsets[r], row_offsets[r + 1]).  The stitched columns of search.py:195-240 —
     query / match / encoded are the residues the region spans, sliced from the records (a region lies on one diagonal, so
@@ -758,7 +758,12 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
     stats = AlignmentStats.to_host() of those alignments — or, without alignments, of those scores (Context.alignment_stats;
     needs one of them): every row also carries aln_bit_score and aln_evalue (region_bit_score and region_evalue for the
     statistics of scores) and lambda_ratio, the composition-based factor its hit row's scores were rescaled with, as floats.
-    With cull= the statistics may be those of all regions or of the kept ones alone.  stats=None adds no column."""
+    With cull= the statistics may be those of all regions or of the kept ones alone.  stats=None adds no column.
+
+    pssm = (RegionAlignments.to_host(), RegionCigars.to_host()) of the KEPT regions aligned and traced against a Profile of the
+    queries (Context.align_regions / trace_regions with profile= on RegionCull.take's regions; needs cull): every row also carries
+    pssm_score, pssm_identities, pssm_positives, pssm_q_start / pssm_q_end, pssm_t_start / pssm_t_end (half-open) and pssm_cigar.
+    pssm=None adds no column."""
     offs, q_start, t_start, length, n_kmers, covered = [np.asarray(c).tolist() for c in regions_host]
     if scores is not None:
         s_offs, s_q, s_t, s_len, s_score, s_ident, s_pos, _ = [np.asarray(c).tolist() for c in scores]
@@ -794,6 +799,13 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
             raise ValueError("statistics and regions are not of the same regions")
         st_kept = len(st_bit) != len(q_start)
         bit_col, ev_col = ("aln_bit_score", "aln_evalue") if alignments is not None else ("region_bit_score", "region_evalue")
+    if pssm is not None:
+        if cull is None:
+            raise ValueError("pssm needs cull: the profile alignments are those of the kept regions")
+        from .engine import cigar_strings
+        p_al, p_cg = [np.asarray(c).tolist() for c in pssm[0]], cigar_strings(*pssm[1])
+        if len(p_cg) != len(c_src) or any(len(c) != len(c_src) for c in p_al[1:]):
+            raise ValueError("pssm and cull are not of the same regions")
     chain_pos = None
     if chain is not None:
         if scores is None and alignments is None:
@@ -835,6 +847,11 @@ def region_rows(q_records: Sequence[Tuple[str, bytes]], t_records: Sequence[Tupl
                 row[nm_col] = c_nm[kept_at[g]]
             if chain_pos is not None:
                 row["chain_pos"] = chain_pos.get(g, -1)
+            if pssm is not None:
+                e = kept_at[g]
+                row.update({"pssm_score": p_al[5][e], "pssm_identities": p_al[6][e], "pssm_positives": p_al[7][e], "pssm_q_start": p_al[1][e],
+                            "pssm_q_end": p_al[1][e] + p_al[2][e], "pssm_t_start": p_al[3][e], "pssm_t_end": p_al[3][e] + p_al[4][e],
+                            "pssm_cigar": p_cg[e]})
             if stats is not None:
                 e = kept_at[g] if st_kept else g
                 row.update({bit_col: st_bit[e], ev_col: st_ev[e], "lambda_ratio": st_ratio[r]})
@@ -933,7 +950,8 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 chain_max_gap: int = 0, chain_max_overlap: int = 0, chain_link_cost: int = 0,
                                 chain_skew_cost: int = 0, chain_overlap_cost: int = 0, hit_rows: bool = False,
                                 stitch: bool = False, stitch_max_fill: int = 0, evalue: bool = False, stat_params=None,
-                                max_evalue=None, mask: bool = False, mask_opts: Optional[dict] = None, coverage: Optional[str] = None):
+                                max_evalue=None, mask: bool = False, mask_opts: Optional[dict] = None, coverage: Optional[str] = None,
+                                profile: bool = False, profile_beta: float = 10.0):
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -967,8 +985,22 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     coverage="query" | "target" (needs cigar=True): the alignments are piled up on that file's sequences on the device
     (Context.pileup) — the stitched ones with stitch=True, otherwise the traced alignments of the kept regions — and the call
     returns (rows, coverage_rows): the rows as before and one `coverage_rows` row per sequence of that file.  max_evalue drops
-    rows on the host and does not touch the coverage."""
+    rows on the host and does not touch the coverage.
+    profile=True (needs regions, gapped, cigar and cull; not with stitch, evalue or coverage): a second round against a
+    position-specific matrix.  The traced alignments of the kept regions are piled up on the queries with their residue counts
+    (Context.pileup, profile=True), the counts become a Profile (Context.build_profile with profile_params(matrix,
+    beta=profile_beta)), the kept regions are aligned and traced again against it, and the rows carry the pssm_* columns
+    `region_rows` adds for pssm=."""
     _coverage_check(coverage, (None, "query", "target"), (("cigar", cigar),))
+    if profile:
+        for name, on in (("regions", regions), ("gapped", gapped), ("cigar", cigar), ("cull", cull)):
+            if not on:
+                raise ValueError(f"profile=True needs {name}=True: the profile is built from the traced alignments the cull kept")
+        for name, on in (("stitch", stitch), ("evalue", evalue), ("coverage", coverage)):
+            if on:
+                raise ValueError(f"profile=True with {name}: not built (stitch, E-values and coverage read residues under a matrix)")
+    if not profile_beta >= 0:
+        raise ValueError(f"profile_beta = {profile_beta} is not a weight >= 0")
     if mask_opts is not None and not mask:
         raise ValueError("mask_opts needs mask=True")
     if (stat_params is not None or max_evalue is not None) and not evalue:
@@ -1084,6 +1116,16 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                     cg_host = cg.to_host()
                     if coverage:
                         cov_rows = covered(cg, alignments=t_al)
+                    if profile:  # round two: the kept alignments say what each query position likes
+                        from .engine import profile_params
+                        pu = ctx.pileup(cg, hits, side="query", offsets=q_off, alignments=t_al, profile=True, other_res=t_res, other_off=t_off)
+                        pf = ctx.build_profile(pu, q_res, q_off, profile_params(matrix, beta=profile_beta))
+                        p_al = ctx.align_regions(t_rg, hits, q_res, q_off, t_res, t_off, profile=pf, band=band, gap_open=gap_open,
+                                                 gap_extend=gap_extend, x_drop=gapped_x_drop)
+                        p_cg = ctx.trace_regions(t_rg, hits, q_res, q_off, t_res, t_off, p_al, eqx=eqx, profile=pf)
+                        kw["pssm"] = (p_al.to_host(), p_cg.to_host())
+                        for o in (p_cg, p_al, pf, pu):
+                            o.free()
                     cg.free()
                     if cull:
                         t_rg.free(); t_al.free()
