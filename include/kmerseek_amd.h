@@ -1317,8 +1317,9 @@ void ks_framealns_free(ks_framealns *a);
  * Whatever the inputs hold, nothing is read or written outside the batches, the entries and the result's arrays.  A refused
  * call leaves no object and nothing held in the pool.  One stream, synchronous on return, one host wait.  Scratch from the
  * pool: 8 bytes per residue of the side's batch and 8 per sequence.
- * Not built: depth in bases on the query side of frame alignments; weighting by abundance or score.  (Consensus and PSSM
- * columns from the counts: ks_profile_build_device, below.) */
+ * Not built: depth in bases on the query side of frame alignments.  (Weights per entry — Henikoff's, a score, an abundance —
+ * and the pileup that sums them: ks_wpileup_device, below.  Consensus and PSSM columns from the counts:
+ * ks_profile_build_device, below.) */
 typedef struct ks_pileup ks_pileup;
 #define KS_PILEUP_QUERY   0u
 #define KS_PILEUP_TARGET  1u
@@ -1368,6 +1369,83 @@ int ks_pileup_copy_to_host(ks_ctx *ctx, const ks_pileup *p, uint32_t *depth, uin
 void ks_pileup_free(ks_pileup *p);
 /* the longest sequence a wave reduces; a longer one goes to a workgroup (the tests place sequences around it) */
 void ks_debug_pileup_limits(uint32_t *wave_max);
+
+/* ---- sequence weights: one weight per entry of a pileup, and the pileup that sums them ---------------------------------------- */
+
+/* 312 near-copies of one homolog piled up on a query say one thing 312 times.  The two passes here let a profile count them as
+ * what they are: ks_entry_weights_device gives every entry a weight that is small where the entry agrees with many others,
+ * ks_wpileup_device sums such weights — or any others: a score, an abundance — where the pileup counts entries.
+ * A weight is a u32 in units of 2^-30: KS_WEIGHT_ONE is the weight 1.  All of it is integer arithmetic and exact
+ * (tests/pweights_ref.py restates it in plain loops).  For every argument the passes share with ks_pileup_device the contract is
+ * that call's, word for word: the entries, the hit list, the mask, the side and the batches, the refusals in their order and
+ * the offender they name.
+ *
+ * ks_entry_weights_device: position-based (Henikoff) weights, adapted to local alignments; the rule is this project's own.
+ *   It reads the other side as a pileup with KS_PILEUP_PROFILE does (the other batch and d_other_start are needed), and
+ *   d_counts u32[n_res * 28]: the counts of an unweighted pileup with KS_PILEUP_PROFILE of the SAME entries, mask and side.
+ *   flags: KS_PWEIGHTS_INCLUDE_QUERY — the sequence the entries lie on is one more member of each of its columns; d_res, the
+ *   side's residues, is then read (else it may be NULL).
+ *   Per residue p of the side's batch:  cnt[j] = counts[p * 28 + j];  with the flag cnt[class(res[p])] += 1;
+ *     k_p = #{j of all 28 : cnt[j] > 0}.
+ *   Per entry e that is TAKEN — its row is not masked, its ops passed the pileup's judgement, it has np_e >= 1 pair columns:
+ *     S_e = sum over its pair columns (p, c = the class of the other side's residue) of floor(KS_WEIGHT_ONE / ((u64)k_p * cnt[c])),
+ *           a u64 sum of u64 integer divisions (a term may be 0);
+ *     weight[e] = (u32)(S_e / np_e), the mean column term;  n_cols[e] = np_e.
+ *     weight[e] <= KS_WEIGHT_ONE, with equality exactly when the entry is alone in each of its columns.
+ *   An entry that is not taken has weight 0 and n_cols 0; nothing of a masked row is read.
+ *   Worked example: query side, query ACDE, three entries 4M at start 0 against ACDE, ACDE, AGDK, no flag.  Columns 0 and 2:
+ *   k = 1, cnt = 3, every term 357913941.  Columns 1 and 3: k = 2; cnt = 2 for the two that agree, 268435456 each; cnt = 1 for
+ *   the odd one, 536870912.  S = 1252698794, 1252698794, 1789569706;  weight = 313174698, 313174698, 447392426.
+ *   Refused as ks_pileup_device refuses, in its order; unknown flags with the options; a NULL d_counts, or a NULL d_res with the
+ *   flag, with the NULL arguments.  Then, found on the device: a taken entry with a column whose cnt[c] is 0 — the counts were
+ *   not made from these entries — KS_ERR_INVALID_ARG, the lowest such entry named.  A refused call leaves no object and nothing
+ *   held in the pool.  One host wait.  Scratch: one byte per residue of the side's batch.
+ * ks_cigars_pileup_weights: the same for the regions of `cigars` (with the `alignments` they were traced from) and the `pileup`
+ *   made from them, which must hold counts and be of the side's batch.
+ *
+ * ks_wpileup_device, ks_cigars_pileup_weighted, ks_hitalns_pileup_weighted: their siblings' arguments and d_weight
+ *   u32[n_entries] (NULL only without entries).  Every column of the unweighted call is made, identically, and
+ *   wdepth[p] u64            the sum of the weights of the entries that place p (an entry counts once per column it places p in);
+ *   wcounts[p * 28 + c] u64  with KS_PILEUP_PROFILE: the same by the class of the other side's residue; the 28 sum to wdepth[p].
+ *   An entry of weight 0 adds to the unweighted columns and not to these.  Fewer than 2^32 entries of a u32 weight cannot wrap
+ *   a u64; the adds are 64-bit integer atomics, no order shows.  ks_wpileup_n_weighted: the entries of wdepth, 0 for an object
+ *   of the unweighted entry points (whose wdepth and wcounts pointers are NULL).  ks_frames_pileup has no weighted form.
+ * (The functions that take a ks_pileup here are named ks_wpileup_*: what a weighted pileup has beyond ks_pileup_*.) */
+typedef struct ks_pweights ks_pweights;
+#define KS_WEIGHT_ONE (1u << 30)
+#define KS_PWEIGHTS_INCLUDE_QUERY 1u
+int ks_entry_weights_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint64_t *d_op_offsets, const uint32_t *d_ops, uint64_t n_rows,
+                             uint64_t n_entries, uint64_t n_ops, const uint32_t *d_start, const uint32_t *d_other_start, const uint8_t *d_row_mask,
+                             const ks_hits *hits, const uint8_t *d_res, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res,
+                             const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs, uint64_t n_o_res, const uint32_t *d_counts,
+                             uint32_t side, uint32_t flags, ks_pweights **out);
+int ks_cigars_pileup_weights(ks_ctx *ctx, const ks_cigars *cigars, const ks_raligns *alignments, const ks_pileup *pileup, const ks_hits *hits,
+                             const uint8_t *d_row_mask, const uint8_t *d_res, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res,
+                             const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs, uint64_t n_o_res, uint32_t side, uint32_t flags,
+                             ks_pweights **out);
+uint64_t ks_pweights_n_entries(const ks_pweights *w);
+/* device pointers, valid until ks_pweights_free */
+const uint32_t *ks_pweights_device_weight(const ks_pweights *w);
+const uint32_t *ks_pweights_device_n_cols(const ks_pweights *w);
+/* any destination may be NULL */
+int ks_pweights_copy_to_host(ks_ctx *ctx, const ks_pweights *w, uint32_t *weight, uint32_t *n_cols);
+void ks_pweights_free(ks_pweights *w);
+int ks_wpileup_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint64_t *d_op_offsets, const uint32_t *d_ops, uint64_t n_rows,
+                              uint64_t n_entries, uint64_t n_ops, const uint32_t *d_start, const uint32_t *d_other_start, const uint8_t *d_row_mask,
+                              const ks_hits *hits, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res,
+                              const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs, uint64_t n_o_res,
+                              const uint32_t *d_weight, const ks_pileup_opts *opts, ks_pileup **out);
+int ks_cigars_pileup_weighted(ks_ctx *ctx, const ks_cigars *cigars, const ks_raligns *alignments, const ks_hits *hits, const uint8_t *d_row_mask,
+                              const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res, const uint8_t *d_o_res, const uint64_t *d_o_offsets,
+                              uint32_t n_o_seqs, uint64_t n_o_res, const uint32_t *d_weight, const ks_pileup_opts *opts, ks_pileup **out);
+int ks_hitalns_pileup_weighted(ks_ctx *ctx, const ks_hitalns *stitched, const ks_hits *hits, const uint8_t *d_row_mask, const uint64_t *d_offsets,
+                               uint32_t n_seqs, uint64_t n_res, const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs,
+                               uint64_t n_o_res, const uint32_t *d_weight, const ks_pileup_opts *opts, ks_pileup **out);
+uint64_t ks_wpileup_n_weighted(const ks_pileup *p);
+const uint64_t *ks_wpileup_device_wdepth(const ks_pileup *p);
+const uint64_t *ks_wpileup_device_wcounts(const ks_pileup *p);
+/* wdepth u64[n_weighted], wcounts u64[28 x n_weighted with the profile, else 0]; any destination may be NULL */
+int ks_wpileup_copy_to_host(ks_ctx *ctx, const ks_pileup *p, uint64_t *wdepth, uint64_t *wcounts);
 
 /* ---- position-specific scores: a profile of the query batch, and the region passes against it ------------------------------- */
 
@@ -1439,6 +1517,34 @@ const uint32_t *ks_profile_device_n_obs(const ks_profile *p);
 int ks_profile_copy_to_host(ks_ctx *ctx, const ks_profile *p, uint8_t *scores, uint8_t *consensus, uint32_t *n_obs);
 void ks_profile_free(ks_profile *p);
 
+/* The WEIGHTED build: the same options, rows, consensus and n_obs from a weighted pileup of the query side — counts, wcounts
+ * (ks_wpileup_device with KS_PILEUP_PROFILE, e.g. under the weights of ks_entry_weights_device) and depth.  The
+ * observed frequencies are the weighted ones, and the amount of evidence behind them is k, the number of distinct classes seen
+ * at the column, not the number of sequences: 312 copies of one residue are one observation against beta.
+ * Per residue p, a = the class of q_res[p], J = the modelled classes, cnt[j] = counts[p * 28 + j]:
+ *   n0 = sum over j in J of cnt[j] (u64).  n0 == 0: the row is matrix[a][.], n_obs[p] = 0.
+ *   Otherwise, with KS_PROFILE_INCLUDE_QUERY and a in J, cnt[a] += 1;  n = sum over J of cnt;  k = #{j in J : cnt[j] > 0};
+ *   W_j = wcounts[p * 28 + j] (u64), and with the flag and a in J  W_a += floor(KS_WEIGHT_ONE / ((u64)k * cnt[a])), the query's
+ *   own column term;  W = sum over J of W_j, an exact u64.  W == 0: the row is matrix[a][.], n_obs[p] = 0.
+ *   Else n_obs[p] = min(n, 2^32 - 1).  c not in J: scores[p][c] = matrix[a][c].
+ *   c in J, in f64, every operation rounded on its own (no fused multiply-add), in exactly this order:
+ *     x_j = ((f64)W_j / (f64)W) * (f64)k  for j in J;
+ *     g = sum over j in J, ascending, of x_j * R[j][c], from 0.0;  t = g / (f64)k;  t = bg[c] * t;  t = beta * t;
+ *     num = x_c + t;  den = (f64)k + beta;  r = (num / den) / bg[c];
+ *     scores[p][c] = clamp(base + #{k' : thresholds[k'] <= r}, -127, 127)       (a NaN r is at or above no threshold)
+ *   consensus[p]: depth[p] == 0: the residue's own byte, ASCII upper-cased.  Otherwise, over all 28 classes and whatever the
+ *     flag: cq[j] = counts[p * 28 + j], cq[a] += 1;  kq = #{j : cq[j] > 0};  V_j = wcounts[p * 28 + j],
+ *     V_a += floor(KS_WEIGHT_ONE / ((u64)kq * cq[a])) — the query's column term under ks_entry_weights_device's rule with
+ *     KS_PWEIGHTS_INCLUDE_QUERY;  the class with the largest V, ties to the smaller class, as that class's letter.
+ * ks_profile_build_weighted_device: d_counts u32[n_q_res * 28], d_wcounts u64[n_q_res * 28], d_depth u32[n_q_res].
+ * ks_profile_build_weighted_pileup: the same from a ks_pileup of the weighted entry points made with KS_PILEUP_PROFILE; one of
+ * the unweighted entry points (ks_wpileup_n_weighted == 0) is refused by name.  Everything else as the two builds above. */
+int ks_profile_build_weighted_device(ks_ctx *ctx, const uint32_t *d_counts, const uint64_t *d_wcounts, const uint32_t *d_depth,
+                                     const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q, uint64_t n_q_res, const ks_profile_opts *opts,
+                                     ks_profile **out);
+int ks_profile_build_weighted_pileup(ks_ctx *ctx, const ks_pileup *pileup, const uint8_t *d_q_res, const uint64_t *d_q_offs, uint32_t n_q,
+                                     uint64_t n_q_res, const ks_profile_opts *opts, ks_profile **out);
+
 /* The three region passes against a profile of the QUERY batch.  The contract of each is its sibling's, word for word —
  * recurrence, tie rules, X-drop, counts, ops, refusals — with one difference: a pair (Q_x, T_y) scores
  * P[q_offs[qid] + position of Q_x][class(T_y)], the anchor pair included.  Identities still compare upper-cased bytes, positives
@@ -1450,7 +1556,7 @@ void ks_profile_free(ks_profile *p);
  * refuse a profile-made ks_raligns by name, before any device work.
  * Also KS_ERR_INVALID_ARG, before any device work: a NULL profile, one of another context, one whose n_residues is not n_q_res;
  * for ks_regions_traceback_profile an `alignments` that is not profile-made.
- * Not built: profile seeds; sequence weighting; stitch, E-values or fold with profile alignments; a profile on the target side. */
+ * Not built: profile seeds; stitch, E-values or fold with profile alignments; a profile on the target side. */
 int ks_regions_score_profile(ks_ctx *ctx, const ks_regions *regions, const ks_hits *hits, const uint8_t *d_q_res, const uint64_t *d_q_offs,
                              uint32_t n_q, uint64_t n_q_res, const uint8_t *d_t_res, const uint64_t *d_t_offs, uint32_t n_t, uint64_t n_t_res,
                              const ks_profile *profile, const ks_rscore_opts *opts, ks_rscores **out);

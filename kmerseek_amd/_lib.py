@@ -119,6 +119,7 @@ class ks_fstitch_opts(C.Structure):
 
 
 KS_PILEUP_QUERY, KS_PILEUP_TARGET, KS_PILEUP_PROFILE = 0, 1, 1
+KS_WEIGHT_ONE, KS_PWEIGHTS_INCLUDE_QUERY = 1 << 30, 1
 
 
 class ks_pileup_opts(C.Structure):
@@ -491,6 +492,8 @@ SIGNATURES = {
     "ks_frames_pileup": (C.c_int, [_vp] * 5 + [C.c_uint32, C.c_uint64, C.POINTER(ks_pileup_opts), _pp]),
     "ks_profile_build_device": (C.c_int, [_vp] * 5 + [C.c_uint32, C.c_uint64, C.POINTER(ks_profile_opts), _pp]),
     "ks_profile_build_pileup": (C.c_int, [_vp] * 4 + [C.c_uint32, C.c_uint64, C.POINTER(ks_profile_opts), _pp]),
+    "ks_profile_build_weighted_device": (C.c_int, [_vp] * 6 + [C.c_uint32, C.c_uint64, C.POINTER(ks_profile_opts), _pp]),
+    "ks_profile_build_weighted_pileup": (C.c_int, [_vp] * 4 + [C.c_uint32, C.c_uint64, C.POINTER(ks_profile_opts), _pp]),
     "ks_profile_from_host": (C.c_int, [_vp] * 4 + [C.c_uint32, C.c_uint64, _vp, _pp]),
     "ks_profile_n_seqs": (C.c_uint32, [_vp]),
     "ks_profile_n_residues": (C.c_uint64, [_vp]),
@@ -521,6 +524,22 @@ SIGNATURES = {
     "ks_pileup_device_mean_depth": (_vp, [_vp]),
     "ks_pileup_copy_to_host": (C.c_int, [_vp] * 11),
     "ks_pileup_free": (None, [_vp]),
+    "ks_entry_weights_device": (C.c_int, [_vp] * 4 + [C.c_uint64] * 3 + [_vp] * 6 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, _vp,
+                                           C.c_uint32, C.c_uint32, _pp]),
+    "ks_cigars_pileup_weights": (C.c_int, [_vp] * 8 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _pp]),
+    "ks_pweights_n_entries": (C.c_uint64, [_vp]),
+    "ks_pweights_device_weight": (_vp, [_vp]),
+    "ks_pweights_device_n_cols": (_vp, [_vp]),
+    "ks_pweights_copy_to_host": (C.c_int, [_vp] * 4),
+    "ks_pweights_free": (None, [_vp]),
+    "ks_wpileup_device": (C.c_int, [_vp] * 4 + [C.c_uint64] * 3 + [_vp] * 5 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, _vp,
+                                            C.POINTER(ks_pileup_opts), _pp]),
+    "ks_cigars_pileup_weighted": (C.c_int, [_vp] * 6 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, _vp, C.POINTER(ks_pileup_opts), _pp]),
+    "ks_hitalns_pileup_weighted": (C.c_int, [_vp] * 5 + [C.c_uint32, C.c_uint64, _vp, _vp, C.c_uint32, C.c_uint64, _vp, C.POINTER(ks_pileup_opts), _pp]),
+    "ks_wpileup_n_weighted": (C.c_uint64, [_vp]),
+    "ks_wpileup_device_wdepth": (_vp, [_vp]),
+    "ks_wpileup_device_wcounts": (_vp, [_vp]),
+    "ks_wpileup_copy_to_host": (C.c_int, [_vp] * 4),
     "ks_debug_pileup_limits": (None, [_u32p]),
     "ks_residue_composition_device": (C.c_int, [_vp, _vp, _vp, C.c_uint32, C.c_uint64, _pp]),
     "ks_rcomp_n_seqs": (C.c_uint32, [_vp]),

@@ -418,13 +418,14 @@ enum : u32 {
     KS_PIN_FSTITCH = 288,    // 14 words, frame stitch: the same eleven words, then the scan totals: direction rows | columns | ops
     KS_PIN_PILEUP = 302,     // 7 words, pileup: the seven first-offender words (ks_pileup.hip: PU_BAD_*)
     KS_PIN_PROFILE = 309,    // 1 word, profile build: the last offset of the query batch (ks_profile.hip)
-    KS_PIN_END = 310,
+    KS_PIN_PWEIGHTS = 310,   // 8 words, entry weights: the seven of KS_PIN_PILEUP | first entry with a column the counts do not hold (ks_pileup.hip)
+    KS_PIN_END = 318,
 };
-#define KS_PIN_WORDS 312
+#define KS_PIN_WORDS 320
 static_assert(KS_PIN_JOIN + KS_PIN_JOIN_WORDS <= KS_PIN_SKETCH && KS_PIN_SKETCH + KS_PIN_SKETCH_WORDS <= KS_PIN_SKETCH_SYNC &&
                   KS_PIN_SKETCH_SYNC + KS_PIN_SKETCH_SYNC_WORDS <= KS_PIN_STAGE && KS_PIN_STAGE < KS_PIN_ROWS &&
                   KS_PIN_ROWS + 2 <= KS_PIN_SCAN && KS_PIN_SCAN < KS_PIN_SORT_OFLOW && KS_PIN_SORT_OFLOW < KS_PIN_READ &&
-                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 14 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_FSTITCH && KS_PIN_FSTITCH + 14 <= KS_PIN_PILEUP && KS_PIN_PILEUP + 7 <= KS_PIN_PROFILE && KS_PIN_PROFILE < KS_PIN_END &&
+                  KS_PIN_READ + 2 <= KS_PIN_DENSE && KS_PIN_DENSE < KS_PIN_SIGNIF && KS_PIN_SIGNIF + 3 <= KS_PIN_BEST && KS_PIN_BEST + 3 <= KS_PIN_REGIONS && KS_PIN_REGIONS < KS_PIN_CLUSTER && KS_PIN_CLUSTER + 5 <= KS_PIN_GATHER && KS_PIN_GATHER + 4 <= KS_PIN_GREEDY && KS_PIN_GREEDY + 10 <= KS_PIN_TRANSLATE && KS_PIN_TRANSLATE + 4 <= KS_PIN_UNION && KS_PIN_UNION + 2 <= KS_PIN_RSCORE && KS_PIN_RSCORE < KS_PIN_RALIGN && KS_PIN_RALIGN + 2 <= KS_PIN_RTRACE && KS_PIN_RTRACE + 8 <= KS_PIN_RCULL && KS_PIN_RCULL + 3 <= KS_PIN_RCHAIN && KS_PIN_RCHAIN + 5 <= KS_PIN_RCHAIN_COV && KS_PIN_RCHAIN_COV + 2 <= KS_PIN_RSTITCH && KS_PIN_RSTITCH + 14 <= KS_PIN_RCOMP && KS_PIN_RCOMP + 2 <= KS_PIN_ASTATS && KS_PIN_ASTATS + 4 <= KS_PIN_MASK && KS_PIN_MASK + 7 <= KS_PIN_FFOLD && KS_PIN_FFOLD + 8 <= KS_PIN_FSTITCH && KS_PIN_FSTITCH + 14 <= KS_PIN_PILEUP && KS_PIN_PILEUP + 7 <= KS_PIN_PROFILE && KS_PIN_PROFILE < KS_PIN_PWEIGHTS && KS_PIN_PWEIGHTS + 8 <= KS_PIN_END &&
                   KS_PIN_END <= KS_PIN_WORDS,
               "pinned host slots overlap or do not fit KS_PIN_WORDS");
 
@@ -778,10 +779,22 @@ struct ks_pileup {
     u32 *d_length, *d_n_alignments, *d_covered, *d_max_depth; // n_seqs, as every column below
     u64 *d_depth_sum;
     double *d_breadth, *d_mean_depth;
+    // a weighted pileup alone (ks_wpileup_device): the weights of the entries that place a residue, summed
+    u64 n_weighted, n_wprofile;          // n_residues and n_profile of a weighted pileup, else 0
+    u64 *d_wdepth;                       // n_weighted
+    u64 *d_wcounts;                      // n_wprofile
     template <class S, class F> static constexpr void each(S &s, F &&f) {
         f(s.d_depth, s.n_residues); f(s.d_counts, s.n_profile); f(s.d_length, s.n_seqs); f(s.d_n_alignments, s.n_seqs); f(s.d_covered, s.n_seqs);
         f(s.d_max_depth, s.n_seqs); f(s.d_depth_sum, s.n_seqs); f(s.d_breadth, s.n_seqs); f(s.d_mean_depth, s.n_seqs);
+        f(s.d_wdepth, s.n_weighted, false); f(s.d_wcounts, s.n_wprofile, false); // (ks_wpileup_copy_to_host carries them)
     }
+};
+// one weight per entry of a pileup (ks_pileup.hip: ks_entry_weights_device)
+struct ks_pweights {
+    ks_ctx *ctx;
+    u64 n_entries;
+    u32 *d_weight, *d_n_cols;            // n_entries
+    template <class S, class F> static constexpr void each(S &s, F &&f) { f(s.d_weight, s.n_entries); f(s.d_n_cols, s.n_entries); }
 };
 
 // the residue classes of the sequences of a batch, counted (ks_astats.hip)

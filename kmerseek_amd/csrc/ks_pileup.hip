@@ -11,7 +11,11 @@
 //            position; every maximal run of pair ops is one interval, +1 in `begins` at its first residue and +1 in `ends` one
 //            past its last (two atomics per run, not per column: 1= 1X 1= ... is one run).  With the profile the pair ops of
 //            the chunk are replayed one after the other, lanes over the columns: the residue of the other side is read and one
-//            add goes to counts[p][class].
+//            add goes to counts[p][class].  A weighted pileup (k_pu_entries<., PU_W_SUM>) replays the runs also without the
+//            profile: the entry's weight goes to wdepth[p] and, with the profile, to wcounts[p][class], 64-bit integer atomics.
+//   weights  ks_entry_weights_device.  k_pw_classes, 28 lanes a residue: k_p, the classes seen at the residue, one byte.  Then
+//            k_pu_entries<true, PU_W_MAKE>: the same judgement, nothing piled up; the replay reads per column one byte k_p and
+//            one count, each lane sums floor(2^30 / (k_p * cnt)) in 64 bits, the wave reduces, lane 0 stores the mean.
 //   scans    two ks_scan_u32_inplace.  depth[p] = begins up to p - ends up to p.  Two unsigned arrays and not one of signed
 //            marks: the one-launch scan carries a tile's running sum in 38 bits of its status word, a run of "negative" u32
 //            tile sums passes that after 64 tiles.
@@ -26,7 +30,9 @@
 #define PU_WAVE_MAX 1024u  // the longest sequence a wave reduces (ks_debug_pileup_limits)
 #define PU_GROUP_GRID 2048
 enum : u32 { PU_M = 0, PU_I = 1, PU_D = 2, PU_N = KS_CIGAR_FSHIFT, PU_EQ = 7, PU_X = 8 }; // BAM op codes
-enum : u32 { PU_BAD_ROWCSR = 0, PU_BAD_OPCSR = 1, PU_BAD_ID = 2, PU_BAD_OP = 3, PU_BAD_EXTENT = 4, PU_BAD_SEQ = 5, PU_BAD_OFFS = 6, PU_N_BAD = 7 };
+enum : u32 { PU_BAD_ROWCSR = 0, PU_BAD_OPCSR = 1, PU_BAD_ID = 2, PU_BAD_OP = 3, PU_BAD_EXTENT = 4, PU_BAD_SEQ = 5, PU_BAD_OFFS = 6, PU_N_BAD = 7,
+             PU_BAD_COUNTS = 7, PW_N_BAD = 8 }; // (the weights pass alone: a column the counts do not hold)
+enum : int { PU_W_NONE = 0, PU_W_SUM = 1, PU_W_MAKE = 2 }; // k_pu_entries: no weights | the entries' weights summed | the weights made
 
 struct pu_args {
     const u64 *row_offs;            // n_rows + 1, or NULL: entry e is row e
@@ -43,6 +49,14 @@ struct pu_args {
     u32 *begins, *ends;             // n_s_res + 2 each
     u32 *counts, *n_aln;
     unsigned long long *bad;
+    // a weighted pileup: the entries' weights, and where they are summed
+    const u32 *weight;              // n_entries
+    unsigned long long *wdepth, *wcounts;
+    // the weights pass: the side's residues (NULL: the sequence itself is no member of its columns), the classes seen per
+    // residue (k_pw_classes), the counts they were made from, and the two columns made
+    const u8 *s_res, *n_classes;
+    const u32 *in_counts;
+    u32 *out_weight, *out_cols;
 };
 
 KS_DEV bool pu_is_pair(u32 c) { return c == PU_M || c == PU_EQ || c == PU_X; }
@@ -58,7 +72,7 @@ __global__ __launch_bounds__(PU_THREADS) void k_pu_csr(pu_args A) {
     if (i == A.n_entries && A.op_offs[i] != A.n_ops) ks_first_bad(A.bad, PU_BAD_OPCSR, (u32)i);
 }
 
-template <bool PROFILE>
+template <bool PROFILE, int W = PU_W_NONE>
 __global__ __launch_bounds__(PU_THREADS) void k_pu_entries(pu_args A) {
     const u32 lane = threadIdx.x & 63, wave = ks_readfirst(threadIdx.x >> 6);
     const u64 e64 = (u64)blockIdx.x * (PU_THREADS / 64) + wave;
@@ -110,7 +124,10 @@ __global__ __launch_bounds__(PU_THREADS) void k_pu_entries(pu_args A) {
         return;
     }
     if (np == 0) return;
-    if (lane == 0) atomicAdd(&A.n_aln[sid], 1u);
+    if (W != PU_W_MAKE && lane == 0) atomicAdd(&A.n_aln[sid], 1u);
+    const u32 wt = W == PU_W_SUM ? ks_readfirst(A.weight[e]) : 0u;
+    u64 term_sum = 0;     // PU_W_MAKE: this lane's column terms
+    bool no_count = false; //            a column whose count is 0
 
     // (from here on every position lies inside [sb, se] and [ob, oe): 32 bits hold the offsets into the two sequences)
     u32 spos = s0, opos = o0;
@@ -121,14 +138,17 @@ __global__ __launch_bounds__(PU_THREADS) void k_pu_entries(pu_args A) {
         const bool pair = pu_is_pair(c);
         const u32 ds = (pair || c == c_side) ? len : 0u;
         const u32 is = ks_wave_incl_scan(ds), xs = spos + is - ds; // where the op begins on the side
-        if (pair) {
+        if (W != PU_W_MAKE && pair) {
             const bool prev = k > kb && pu_is_pair(A.ops[k - 1] & 15u), next = k + 1 < ke && pu_is_pair(A.ops[k + 1] & 15u);
             if (!prev) atomicAdd(&A.begins[sb + xs], 1u);
             if (!next) atomicAdd(&A.ends[sb + xs + len], 1u);
         }
-        if (PROFILE) {
-            const u32 dx = (pair || c == c_other) ? len : 0u;
-            const u32 io = ks_wave_incl_scan(dx), xo = opos + io - dx;
+        if (PROFILE || (W == PU_W_SUM && wt != 0)) {
+            u32 io = 0, xo = 0;
+            if (PROFILE) {
+                const u32 dx = (pair || c == c_other) ? len : 0u;
+                io = ks_wave_incl_scan(dx); xo = opos + io - dx;
+            }
             u64 m = __ballot(pair && len != 0);
             m = ((u64)ks_readfirst((u32)(m >> 32)) << 32) | ks_readfirst((u32)m);
             while (m) {
@@ -136,12 +156,54 @@ __global__ __launch_bounds__(PU_THREADS) void k_pu_entries(pu_args A) {
                 m &= m - 1;
                 const u32 L = (u32)__builtin_amdgcn_readlane((int)len, j);
                 const u64 ps = sb + (u32)__builtin_amdgcn_readlane((int)xs, j), po = ob + (u32)__builtin_amdgcn_readlane((int)xo, j);
-                for (u32 i = lane; i < L; i += 64) atomicAdd(&A.counts[(ps + i) * PU_A + rk_class(A.o_res[po + i])], 1u);
+                if (W == PU_W_NONE) {
+                    for (u32 i = lane; i < L; i += 64) atomicAdd(&A.counts[(ps + i) * PU_A + rk_class(A.o_res[po + i])], 1u);
+                } else if (W == PU_W_SUM) {
+                    for (u32 i = lane; i < L; i += 64) {
+                        if (PROFILE) {
+                            const u64 at = (ps + i) * PU_A + rk_class(A.o_res[po + i]);
+                            atomicAdd(&A.counts[at], 1u);
+                            if (wt) atomicAdd(&A.wcounts[at], (unsigned long long)wt);
+                        }
+                        if (wt) atomicAdd(&A.wdepth[ps + i], (unsigned long long)wt);
+                    }
+                } else {
+                    for (u32 i = lane; i < L; i += 64) {
+                        const u32 cl = rk_class(A.o_res[po + i]);
+                        const u32 cn = A.in_counts[(ps + i) * PU_A + cl] + ((A.s_res && rk_class(A.s_res[ps + i]) == cl) ? 1u : 0u);
+                        const u32 kp = A.n_classes[ps + i]; // (cn != 0: the class is one of the kp seen, kp >= 1)
+                        if (cn == 0) no_count = true;
+                        else term_sum += (u64)KS_WEIGHT_ONE / ((u64)kp * cn);
+                    }
+                }
             }
-            opos += (u32)__builtin_amdgcn_readlane((int)io, 63);
+            if (PROFILE) opos += (u32)__builtin_amdgcn_readlane((int)io, 63);
         }
         spos += (u32)__builtin_amdgcn_readlane((int)is, 63);
     }
+    if (W == PU_W_MAKE) {
+        if (__ballot(no_count)) {
+            if (lane == 0) ks_first_bad(A.bad, PU_BAD_COUNTS, e);
+            return;
+        }
+        term_sum = ks_wave_sum64(term_sum);
+        if (lane == 0) { A.out_weight[e] = (u32)(term_sum / np); A.out_cols[e] = (u32)np; }
+    }
+}
+
+// the weights pass: per residue of the side's batch the classes with a count, the residue's own class counted in with s_res
+__global__ __launch_bounds__(PU_THREADS) void k_pw_classes(const u32 *counts, const u8 *s_res, u64 n_res, u8 *n_classes) {
+    const u64 p = ((u64)blockIdx.x * PU_THREADS + threadIdx.x) >> 5;
+    const u32 c = threadIdx.x & 31;
+    bool seen = false;
+    if (p < n_res && c < PU_A) seen = counts[p * PU_A + c] != 0 || (s_res && rk_class(s_res[p]) == c);
+    const u64 b = __ballot(seen);
+    if (c == 0 && p < n_res) n_classes[p] = (u8)__popc((u32)(b >> (threadIdx.x & 32)));
+}
+// ... and the offsets of the side's batch, which the pileup judges while it reduces the sequences
+__global__ __launch_bounds__(PU_THREADS) void k_pw_offs(const u64 *offs, u32 n_seqs, u64 n_res, unsigned long long *bad) {
+    const u64 s = (u64)blockIdx.x * PU_THREADS + threadIdx.x;
+    if (s < n_seqs && (offs[s] > offs[s + 1] || offs[s + 1] > n_res)) ks_first_bad(bad, PU_BAD_OFFS, (u32)s);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -230,13 +292,24 @@ struct pu_entries {
     const u32 *start, *other_start;
 };
 
+// the first offender of the first kind, named: what the pileup and the weights pass refuse alike
+static int pu_refuse(ks_ctx *ctx, const ks_ctl &ctl, const pu_entries &E, const ks_res_batch &S, bool profile);
+
+// weighted: d_weight holds one weight per entry, and the pileup also sums them (wdepth, with the profile wcounts)
 static int pu_run(ks_ctx *ctx, const pu_entries &E, const u8 *d_row_mask, const ks_hits *H, const ks_res_batch &S, const ks_res_batch &O, u32 side,
-                  bool profile, ks_pileup *P) {
+                  bool profile, bool weighted, const u32 *d_weight, ks_pileup *P) {
     const u64 ns = S.n_seqs, nr = S.n_res;
     P->n_seqs = ns; P->n_residues = nr; P->n_profile = profile ? nr * PU_A : 0;
     KS_TRY(ks_alloc(ctx, &P->d_depth, (size_t)nr));
     KS_TRY(ks_alloc(ctx, &P->d_counts, (size_t)P->n_profile));
     KS_TRY(ks_obj_alloc(ctx, P, P->n_seqs));
+    if (weighted) {
+        P->n_weighted = nr; P->n_wprofile = P->n_profile;
+        KS_TRY(ks_alloc(ctx, &P->d_wdepth, (size_t)nr));
+        KS_TRY(ks_alloc(ctx, &P->d_wcounts, (size_t)P->n_wprofile));
+        if (nr) KS_HIP(ctx, hipMemsetAsync(P->d_wdepth, 0, (size_t)nr * sizeof(u64), ctx->stream));
+        if (P->n_wprofile) KS_HIP(ctx, hipMemsetAsync(P->d_wcounts, 0, (size_t)P->n_wprofile * sizeof(u64), ctx->stream));
+    }
     KS_HIP(ctx, hipMemsetAsync(P->d_n_alignments, 0, (ns ? ns : 1) * sizeof(u32), ctx->stream));
     if (profile && nr) KS_HIP(ctx, hipMemsetAsync(P->d_counts, 0, (size_t)P->n_profile * sizeof(u32), ctx->stream));
 
@@ -251,12 +324,15 @@ static int pu_run(ks_ctx *ctx, const pu_entries &E, const u8 *d_row_mask, const 
 
     const pu_args A = {E.row_offs, E.op_offs, E.ops, E.start, E.other_start, d_row_mask, H->d_qid, H->d_tid, S.offs, O.res, O.offs,
                        E.n_ops, nr, O.n_res, (u32)E.n_rows, (u32)E.n_entries, S.n_seqs, O.n_seqs, side, begins, ends, P->d_counts,
-                       P->d_n_alignments, ctl.words()};
+                       P->d_n_alignments, ctl.words(), d_weight, (unsigned long long *)P->d_wdepth, (unsigned long long *)P->d_wcounts,
+                       nullptr, nullptr, nullptr, nullptr, nullptr};
     const u64 n_off = (E.n_rows > E.n_entries ? E.n_rows : E.n_entries) + 1;
     KS_LAUNCH(ctx, "pileup_csr", k_pu_csr, (u32)((n_off + PU_THREADS - 1) / PU_THREADS), PU_THREADS, A);
     if (E.n_entries) {
         const u32 grid = (u32)((E.n_entries + PU_THREADS / 64 - 1) / (PU_THREADS / 64));
-        if (profile) KS_LAUNCH(ctx, "pileup_profile", k_pu_entries<true>, grid, PU_THREADS, A);
+        if (weighted && profile) KS_LAUNCH(ctx, "pileup_profile_weighted", (k_pu_entries<true, PU_W_SUM>), grid, PU_THREADS, A);
+        else if (weighted) KS_LAUNCH(ctx, "pileup_marks_weighted", (k_pu_entries<false, PU_W_SUM>), grid, PU_THREADS, A);
+        else if (profile) KS_LAUNCH(ctx, "pileup_profile", k_pu_entries<true>, grid, PU_THREADS, A);
         else KS_LAUNCH(ctx, "pileup_marks", k_pu_entries<false>, grid, PU_THREADS, A);
     }
     KS_TRY(ks_scan_u32_inplace(ctx, begins, nr + 1, nullptr));
@@ -271,7 +347,11 @@ static int pu_run(ks_ctx *ctx, const pu_entries &E, const u8 *d_row_mask, const 
         if (mode != 1) KS_LAUNCH(ctx, "pileup_seq_group", k_pu_seq_group, (u32)(ns < PU_GROUP_GRID ? ns : PU_GROUP_GRID), PU_THREADS, Q);
     }
     KS_TRY(ks_stream_wait_fetch_scans(ctx, {ctl.fetch()}));
+    return pu_refuse(ctx, ctl, E, S, profile);
+}
 
+static int pu_refuse(ks_ctx *ctx, const ks_ctl &ctl, const pu_entries &E, const ks_res_batch &S, bool profile) {
+    const u64 nr = S.n_res;
     const auto at = [&](u32 i) { return (unsigned long long)ctl[i]; };
     if (ctl.bad(PU_BAD_ROWCSR))
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "pileup: row_offsets descends at hit row %llu or does not end at the %llu entries", at(PU_BAD_ROWCSR),
@@ -307,10 +387,41 @@ static int pu_opts_check(ks_ctx *ctx, const ks_pileup_opts *opts, bool has_other
     return ctx ? ks_fail(ctx, KS_ERR_INVALID_ARG, "pileup options: %s", why) : KS_ERR_INVALID_ARG;
 }
 
-// behind the options: NULL arguments, contexts, counts, capacity, then the device
-static int pu_checked(ks_ctx *ctx, const pu_entries &E, const u8 *d_row_mask, const ks_hits *H, const ks_res_batch &S, const ks_res_batch &O,
-                      const ks_pileup_opts &o, ks_pileup **out) {
-    const bool profile = (o.flags & KS_PILEUP_PROFILE) != 0;
+// the weights of the entries (include/kmerseek_amd.h has the rule).  S.res: the side's residues with KS_PWEIGHTS_INCLUDE_QUERY, else NULL
+static int pw_run(ks_ctx *ctx, const pu_entries &E, const u8 *d_row_mask, const ks_hits *H, const ks_res_batch &S, const ks_res_batch &O, u32 side,
+                  const u32 *d_counts, ks_pweights *Wt) {
+    const u64 nr = S.n_res;
+    Wt->n_entries = E.n_entries;
+    KS_TRY(ks_obj_alloc(ctx, Wt, Wt->n_entries));
+    if (E.n_entries) {
+        KS_HIP(ctx, hipMemsetAsync(Wt->d_weight, 0, (size_t)E.n_entries * sizeof(u32), ctx->stream));
+        KS_HIP(ctx, hipMemsetAsync(Wt->d_n_cols, 0, (size_t)E.n_entries * sizeof(u32), ctx->stream));
+    }
+    ks_scratch sc(ctx);
+    ks_ctl ctl;
+    u8 *n_classes = nullptr;
+    KS_TRY(ctl.init(ctx, sc, KS_PIN_PWEIGHTS, PW_N_BAD, 0));
+    KS_TRY(sc.alloc(&n_classes, (size_t)nr + 1));
+    const pu_args A = {E.row_offs, E.op_offs, E.ops, E.start, E.other_start, d_row_mask, H->d_qid, H->d_tid, S.offs, O.res, O.offs,
+                       E.n_ops, nr, O.n_res, (u32)E.n_rows, (u32)E.n_entries, S.n_seqs, O.n_seqs, side, nullptr, nullptr, nullptr,
+                       nullptr, ctl.words(), nullptr, nullptr, nullptr, S.res, n_classes, d_counts, Wt->d_weight, Wt->d_n_cols};
+    const u64 n_off = (E.n_rows > E.n_entries ? E.n_rows : E.n_entries) + 1;
+    KS_LAUNCH(ctx, "pileup_csr", k_pu_csr, (u32)((n_off + PU_THREADS - 1) / PU_THREADS), PU_THREADS, A);
+    if (S.n_seqs) KS_LAUNCH(ctx, "pweights_offsets", k_pw_offs, (u32)(((u64)S.n_seqs + PU_THREADS - 1) / PU_THREADS), PU_THREADS, S.offs, S.n_seqs, nr, ctl.words());
+    if (nr) KS_LAUNCH(ctx, "pweights_classes", k_pw_classes, (u32)((nr * 32 + PU_THREADS - 1) / PU_THREADS), PU_THREADS, d_counts, S.res, nr, n_classes);
+    if (E.n_entries)
+        KS_LAUNCH(ctx, "pweights_entries", (k_pu_entries<true, PU_W_MAKE>), (u32)((E.n_entries + PU_THREADS / 64 - 1) / (PU_THREADS / 64)), PU_THREADS, A);
+    const ks_fetch_seg f = ctl.fetch();
+    KS_TRY(ks_stream_wait_fetch(ctx, &f, 1));
+    KS_TRY(pu_refuse(ctx, ctl, E, S, true));
+    if (ctl.bad(PU_BAD_COUNTS))
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "pileup weights: entry %llu holds a column that the counts do not: counts of other entries, another mask or "
+                                                "another side", (unsigned long long)ctl[PU_BAD_COUNTS]);
+    return KS_OK;
+}
+
+// what every call is refused for behind its options, before the device: NULL arguments, contexts, counts, capacity
+static int pu_precheck(ks_ctx *ctx, const pu_entries &E, const ks_hits *H, const ks_res_batch &S, const void *out) {
     if (!out || !H || !S.offs || !E.op_offs || (E.n_ops && !E.ops) || (E.n_entries && !E.start))
         return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
     KS_TRY(ks_inputs_check_ctx(ctx, "pileup", H));
@@ -328,15 +439,32 @@ static int pu_checked(ks_ctx *ctx, const pu_entries &E, const u8 *d_row_mask, co
     if (E.n_entries >= 0xfffffffeULL || E.n_ops > 0xffffffffULL)
         return ks_fail(ctx, KS_ERR_CAPACITY, "pileup: 2^32 - 2 or more entries, or more than 2^32 - 1 ops");
     KS_HIP(ctx, hipSetDevice(ctx->device));
+    return KS_OK;
+}
+// behind the options: the checks above, then the device.  weighted: d_weight holds a weight per entry
+static int pu_checked(ks_ctx *ctx, const pu_entries &E, const u8 *d_row_mask, const ks_hits *H, const ks_res_batch &S, const ks_res_batch &O,
+                      const ks_pileup_opts &o, ks_pileup **out, bool weighted = false, const u32 *d_weight = nullptr) {
+    const bool profile = (o.flags & KS_PILEUP_PROFILE) != 0;
+    if (weighted && E.n_entries && !d_weight) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(pu_precheck(ctx, E, H, S, out));
     ks_result<ks_pileup> P(ctx, out, ks_pileup_free);
-    KS_TRY(pu_run(ctx, E, d_row_mask, H, S, profile ? O : ks_res_batch{nullptr, nullptr, 0u, 0ull}, o.side, profile, P));
+    KS_TRY(pu_run(ctx, E, d_row_mask, H, S, profile ? O : ks_res_batch{nullptr, nullptr, 0u, 0ull}, o.side, profile, weighted, d_weight, P));
     return P.commit();
+}
+// ... of the weights pass: the counts and, with the flag, the side's residues are arguments like the others
+static int pw_checked(ks_ctx *ctx, const pu_entries &E, const u8 *d_row_mask, const ks_hits *H, const ks_res_batch &S, const ks_res_batch &O,
+                      u32 side, u32 flags, const u32 *d_counts, ks_pweights **out) {
+    if ((S.n_res && !d_counts) || ((flags & KS_PWEIGHTS_INCLUDE_QUERY) && S.n_res && !S.res)) return ks_fail(ctx, KS_ERR_INVALID_ARG, "NULL argument");
+    KS_TRY(pu_precheck(ctx, E, H, S, out));
+    ks_result<ks_pweights> Wt(ctx, out, ks_pweights_free);
+    KS_TRY(pw_run(ctx, E, d_row_mask, H, ks_res_batch{(flags & KS_PWEIGHTS_INCLUDE_QUERY) ? S.res : nullptr, S.offs, S.n_seqs, S.n_res}, O, side, d_counts, Wt));
+    return Wt.commit();
 }
 
 // What the four entries do alike, in their order: the options (also without a context), the context, *out, the objects the
 // entries come from (`in`: not NULL, of ctx), then `run`, which reads them.
-template <typename Refuse, typename Run, typename... In>
-static int pu_entry(ks_ctx *ctx, const ks_pileup_opts *opts, bool has_other, ks_pileup **out, Refuse &&refuse, Run &&run, const In *...in) {
+template <typename Out, typename Refuse, typename Run, typename... In>
+static int pu_entry(ks_ctx *ctx, const ks_pileup_opts *opts, bool has_other, Out **out, Refuse &&refuse, Run &&run, const In *...in) {
     return ks_guard(ctx, [&]() -> int {
     ks_pileup_opts o;
     KS_TRY(pu_opts_check(ctx, opts, has_other, &o));
@@ -386,6 +514,84 @@ extern "C" int ks_hitalns_pileup(ks_ctx *ctx, const ks_hitalns *stitched, const 
                           d_row_mask, hits, ks_res_batch{nullptr, d_offsets, n_seqs, n_res}, ks_res_batch{d_o_res, d_o_offsets, n_o_seqs, n_o_res}, o, out);
     }, stitched);
 }
+extern "C" int ks_wpileup_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint64_t *d_op_offsets, const uint32_t *d_ops,
+                                        uint64_t n_rows, uint64_t n_entries, uint64_t n_ops, const uint32_t *d_start, const uint32_t *d_other_start,
+                                        const uint8_t *d_row_mask, const ks_hits *hits, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res,
+                                        const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs, uint64_t n_o_res,
+                                        const uint32_t *d_weight, const ks_pileup_opts *opts, ks_pileup **out) {
+    return pu_entry(ctx, opts, pu_has_batch(d_o_res, d_o_offsets, n_o_res) && (d_other_start || !n_entries), out, pu_any, [&](const ks_pileup_opts &o) {
+        return pu_checked(ctx, pu_entries{d_row_offsets, d_op_offsets, d_ops, n_rows, n_entries, n_ops, d_start, d_other_start}, d_row_mask, hits,
+                          ks_res_batch{nullptr, d_offsets, n_seqs, n_res}, ks_res_batch{d_o_res, d_o_offsets, n_o_seqs, n_o_res}, o, out, true, d_weight);
+    });
+}
+// the entries of a ks_cigars with the ks_raligns they were traced from, as ks_cigars_pileup and its two siblings read them
+static int pu_cigars_entries(ks_ctx *ctx, const ks_cigars *cigars, const ks_raligns *alignments, u32 side, pu_entries *E) {
+    KS_TRY(ks_refuse_by_profile(ctx, "pileup", alignments));
+    if (cigars->n_rows != alignments->n_rows || cigars->n_regions != alignments->n_regions)
+        return ks_fail(ctx, KS_ERR_INVALID_ARG, "pileup: the cigars hold %llu regions in %llu hit rows, the alignments %llu in %llu: not traced from them",
+                       (unsigned long long)cigars->n_regions, (unsigned long long)cigars->n_rows, (unsigned long long)alignments->n_regions,
+                       (unsigned long long)alignments->n_rows);
+    const bool on_q = side == KS_PILEUP_QUERY;
+    *E = pu_entries{alignments->d_row_offsets, cigars->d_op_offsets, cigars->d_ops, cigars->n_rows, cigars->n_regions, cigars->n_ops,
+                    on_q ? alignments->d_qstart : alignments->d_tstart, on_q ? alignments->d_tstart : alignments->d_qstart};
+    return KS_OK;
+}
+extern "C" int ks_cigars_pileup_weighted(ks_ctx *ctx, const ks_cigars *cigars, const ks_raligns *alignments, const ks_hits *hits,
+                                         const uint8_t *d_row_mask, const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res, const uint8_t *d_o_res,
+                                         const uint64_t *d_o_offsets, uint32_t n_o_seqs, uint64_t n_o_res, const uint32_t *d_weight,
+                                         const ks_pileup_opts *opts, ks_pileup **out) {
+    return pu_entry(ctx, opts, pu_has_batch(d_o_res, d_o_offsets, n_o_res), out, pu_any, [&](const ks_pileup_opts &o) {
+        pu_entries E;
+        KS_TRY(pu_cigars_entries(ctx, cigars, alignments, o.side, &E));
+        return pu_checked(ctx, E, d_row_mask, hits, ks_res_batch{nullptr, d_offsets, n_seqs, n_res}, ks_res_batch{d_o_res, d_o_offsets, n_o_seqs, n_o_res}, o,
+                          out, true, d_weight);
+    }, cigars, alignments);
+}
+extern "C" int ks_hitalns_pileup_weighted(ks_ctx *ctx, const ks_hitalns *stitched, const ks_hits *hits, const uint8_t *d_row_mask,
+                                          const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res, const uint8_t *d_o_res, const uint64_t *d_o_offsets,
+                                          uint32_t n_o_seqs, uint64_t n_o_res, const uint32_t *d_weight, const ks_pileup_opts *opts, ks_pileup **out) {
+    return pu_entry(ctx, opts, pu_has_batch(d_o_res, d_o_offsets, n_o_res), out, pu_any, [&](const ks_pileup_opts &o) {
+        const bool on_q = o.side == KS_PILEUP_QUERY;
+        return pu_checked(ctx, pu_entries{nullptr, stitched->d_op_offsets, stitched->d_ops, stitched->n_rows, stitched->n_rows, stitched->n_ops,
+                                          on_q ? stitched->d_q_start : stitched->d_t_start, on_q ? stitched->d_t_start : stitched->d_q_start},
+                          d_row_mask, hits, ks_res_batch{nullptr, d_offsets, n_seqs, n_res}, ks_res_batch{d_o_res, d_o_offsets, n_o_seqs, n_o_res}, o, out,
+                          true, d_weight);
+    }, stitched);
+}
+
+// The weights pass reads the other side like a pileup with the profile: its options are that pileup's, made from `side`.
+static const char *pw_refuse(u32 flags) { return (flags & ~KS_PWEIGHTS_INCLUDE_QUERY) ? "unknown flags of the weights (KS_PWEIGHTS_INCLUDE_QUERY is the one there is)" : nullptr; }
+extern "C" int ks_entry_weights_device(ks_ctx *ctx, const uint64_t *d_row_offsets, const uint64_t *d_op_offsets, const uint32_t *d_ops,
+                                        uint64_t n_rows, uint64_t n_entries, uint64_t n_ops, const uint32_t *d_start, const uint32_t *d_other_start,
+                                        const uint8_t *d_row_mask, const ks_hits *hits, const uint8_t *d_res, const uint64_t *d_offsets, uint32_t n_seqs,
+                                        uint64_t n_res, const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs, uint64_t n_o_res,
+                                        const uint32_t *d_counts, uint32_t side, uint32_t flags, ks_pweights **out) {
+    const ks_pileup_opts po = {KS_PILEUP_PROFILE, side, 0ull};
+    return pu_entry(ctx, &po, pu_has_batch(d_o_res, d_o_offsets, n_o_res) && (d_other_start || !n_entries), out,
+                    [&](const ks_pileup_opts &) { return pw_refuse(flags); }, [&](const ks_pileup_opts &o) {
+        return pw_checked(ctx, pu_entries{d_row_offsets, d_op_offsets, d_ops, n_rows, n_entries, n_ops, d_start, d_other_start}, d_row_mask, hits,
+                          ks_res_batch{d_res, d_offsets, n_seqs, n_res}, ks_res_batch{d_o_res, d_o_offsets, n_o_seqs, n_o_res}, o.side, flags, d_counts, out);
+    });
+}
+extern "C" int ks_cigars_pileup_weights(ks_ctx *ctx, const ks_cigars *cigars, const ks_raligns *alignments, const ks_pileup *pileup,
+                                        const ks_hits *hits, const uint8_t *d_row_mask, const uint8_t *d_res, const uint64_t *d_offsets, uint32_t n_seqs,
+                                        uint64_t n_res, const uint8_t *d_o_res, const uint64_t *d_o_offsets, uint32_t n_o_seqs, uint64_t n_o_res,
+                                        uint32_t side, uint32_t flags, ks_pweights **out) {
+    const ks_pileup_opts po = {KS_PILEUP_PROFILE, side, 0ull};
+    return pu_entry(ctx, &po, pu_has_batch(d_o_res, d_o_offsets, n_o_res), out, [&](const ks_pileup_opts &) { return pw_refuse(flags); },
+                    [&](const ks_pileup_opts &o) {
+        pu_entries E;
+        KS_TRY(pu_cigars_entries(ctx, cigars, alignments, o.side, &E));
+        if (pileup->n_profile != pileup->n_residues * PU_A)
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "pileup weights: the pileup was made without KS_PILEUP_PROFILE: it holds no counts");
+        if (pileup->n_seqs != n_seqs || pileup->n_residues != n_res)
+            return ks_fail(ctx, KS_ERR_INVALID_ARG, "pileup weights: the pileup is of %llu sequences and %llu residues, the side's batch of %u and %llu: a "
+                                                    "pileup of another batch or of the other side",
+                           (unsigned long long)pileup->n_seqs, (unsigned long long)pileup->n_residues, n_seqs, (unsigned long long)n_res);
+        return pw_checked(ctx, E, d_row_mask, hits, ks_res_batch{d_res, d_offsets, n_seqs, n_res}, ks_res_batch{d_o_res, d_o_offsets, n_o_seqs, n_o_res},
+                          o.side, flags, pileup->d_counts, out);
+    }, cigars, alignments, pileup);
+}
 extern "C" int ks_frames_pileup(ks_ctx *ctx, const ks_framealns *frame_alignments, const ks_hits *fold_hits, const uint8_t *d_row_mask,
                                    const uint64_t *d_offsets, uint32_t n_seqs, uint64_t n_res, const ks_pileup_opts *opts, ks_pileup **out) {
     const auto refuse = [](const ks_pileup_opts &o) -> const char * {
@@ -417,7 +623,23 @@ extern "C" int ks_pileup_copy_to_host(ks_ctx *ctx, const ks_pileup *p, uint32_t 
                                       uint32_t *covered, uint32_t *max_depth, uint64_t *depth_sum, double *breadth, double *mean_depth) {
     return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, p, depth, counts, length, n_alignments, covered, max_depth, depth_sum, breadth, mean_depth); });
 }
+extern "C" uint64_t ks_wpileup_n_weighted(const ks_pileup *p) { return p ? p->n_weighted : 0; }
+extern "C" const uint64_t *ks_wpileup_device_wdepth(const ks_pileup *p) { return p ? p->d_wdepth : nullptr; }
+extern "C" const uint64_t *ks_wpileup_device_wcounts(const ks_pileup *p) { return p ? p->d_wcounts : nullptr; }
+extern "C" int ks_wpileup_copy_to_host(ks_ctx *ctx, const ks_pileup *p, uint64_t *wdepth, uint64_t *wcounts) {
+    return ks_guard(ctx, [&]() -> int {
+        if (!ctx || !p) return KS_ERR_INVALID_ARG;
+        return ks_columns_to_host(ctx, {{wdepth, p->d_wdepth, (size_t)p->n_weighted * sizeof(u64)}, {wcounts, p->d_wcounts, (size_t)p->n_wprofile * sizeof(u64)}});
+    });
+}
 extern "C" void ks_pileup_free(ks_pileup *p) { ks_obj_free(p); }
+extern "C" uint64_t ks_pweights_n_entries(const ks_pweights *w) { return w ? w->n_entries : 0; }
+extern "C" const uint32_t *ks_pweights_device_weight(const ks_pweights *w) { return w ? w->d_weight : nullptr; }
+extern "C" const uint32_t *ks_pweights_device_n_cols(const ks_pweights *w) { return w ? w->d_n_cols : nullptr; }
+extern "C" int ks_pweights_copy_to_host(ks_ctx *ctx, const ks_pweights *w, uint32_t *weight, uint32_t *n_cols) {
+    return ks_guard(ctx, [&]() -> int { return ks_obj_to_host(ctx, w, weight, n_cols); });
+}
+extern "C" void ks_pweights_free(ks_pweights *w) { ks_obj_free(w); }
 extern "C" void ks_debug_pileup_limits(uint32_t *wave_max) {
     if (wave_max) *wave_max = PU_WAVE_MAX;
 }

@@ -106,6 +106,7 @@ def _profile_or_matrix(profile, matrix):
 
 
 PILEUP_SIDES = {"query": _lib.KS_PILEUP_QUERY, "target": _lib.KS_PILEUP_TARGET}
+KS_WEIGHT_ONE = _lib.KS_WEIGHT_ONE  # the weight 1 of an entry: weights are u32 in units of 2^-30
 
 
 def _pileup_opts(side: str, profile: bool):
@@ -1018,30 +1019,47 @@ class Context:
     def pileup_device(self, d_row_offsets: Optional[int], d_op_offsets: int, d_ops: int, n_rows: int, n_entries: int, n_ops: int,
                       d_start: int, d_other_start: Optional[int], d_row_mask: Optional[int], hits: "Hits", d_offsets: int, n_seqs: int,
                       n_res: int, side: str = "target", profile: bool = False, d_other_res: Optional[int] = None,
-                      d_other_off: Optional[int] = None, n_other: int = 0, n_other_res: int = 0) -> "Pileup":
+                      d_other_off: Optional[int] = None, n_other: int = 0, n_other_res: int = 0, d_weight: Optional[int] = None) -> "Pileup":
         """ks_pileup_device from raw device pointers: the entries (runs of CIGAR ops, each of a hit row of `hits`, with a start on
         the chosen side) piled up on the residues of that side's batch — per residue the depth, with profile=True also the 28
         counts of the residue classes aligned to it (the other batch and d_other_start are then needed), per sequence length,
         n_alignments, covered, max_depth, depth_sum, breadth and mean_depth.  d_row_offsets None: one entry per hit row;
-        d_row_mask: u8 per hit row, the entries of a row with 0 are skipped.  include/kmerseek_amd.h has the contract."""
+        d_row_mask: u8 per hit row, the entries of a row with 0 are skipped.  d_weight: None, or u32 per entry (units of 2^-30,
+        KS_WEIGHT_ONE is 1): ks_wpileup_device, which also sums the weights of the entries that place a residue
+        (Pileup.weighted_to_host).  include/kmerseek_amd.h has the contract."""
         opts = _pileup_opts(side, profile)
         vp = lambda p: C.c_void_p(int(p)) if p else None
         out = C.c_void_p()
+        if d_weight is not None:
+            self._check(self._L.ks_wpileup_device(self._h, vp(d_row_offsets), vp(d_op_offsets), vp(d_ops), int(n_rows), int(n_entries),
+                                                          int(n_ops), vp(d_start), vp(d_other_start), vp(d_row_mask), hits._h, vp(d_offsets),
+                                                          int(n_seqs), int(n_res), vp(d_other_res), vp(d_other_off), int(n_other),
+                                                          int(n_other_res), vp(d_weight), C.byref(opts), C.byref(out)))
+            return Pileup(self, out)
         self._check(self._L.ks_pileup_device(self._h, vp(d_row_offsets), vp(d_op_offsets), vp(d_ops), int(n_rows), int(n_entries), int(n_ops),
                                              vp(d_start), vp(d_other_start), vp(d_row_mask), hits._h, vp(d_offsets), int(n_seqs), int(n_res),
                                              vp(d_other_res), vp(d_other_off), int(n_other), int(n_other_res), C.byref(opts), C.byref(out)))
         return Pileup(self, out)
 
     def pileup(self, aligned, hits: "Hits", side: str = "target", offsets=None, alignments: Optional["RegionAlignments"] = None,
-               row_mask=None, profile: bool = False, other_res=None, other_off=None) -> "Pileup":
+               row_mask=None, profile: bool = False, other_res=None, other_off=None, weights=None) -> "Pileup":
         """The coverage of one batch by a RegionCigars (ks_cigars_pileup: every region is an entry; alignments= the
         RegionAlignments they were traced from, which hold the row CSR and the starts), a HitAlignments (ks_hitalns_pileup: one
         entry per hit row) or a FrameAlignments (ks_frames_pileup on fold.hits: side="target" only, no profile).
         side: "query" or "target", the batch the depth is counted on; offsets: its host offsets u64[n + 1], uploaded for the
         call.  row_mask: None or one truth value per hit row, the rows to take (a top-k selection).  profile=True also counts,
         per residue, the classes of the residues aligned to it: other_res / other_off are then the host arrays of the other
-        batch."""
+        batch.  weights: None, an EntryWeights (entry_weights) or a u32 array, one weight per entry in units of 2^-30: the
+        weighted pileup, which makes every column alike and also sums the weights (Pileup.weighted_to_host); not for a
+        FrameAlignments."""
         opts = _pileup_opts(side, profile)
+        if weights is not None and isinstance(aligned, FrameAlignments):
+            raise ValueError("pileup of a FrameAlignments: weights= is not built (ks_frames_pileup has no weighted form)")
+        if weights is not None and not isinstance(weights, EntryWeights):
+            weights = np.asarray(weights)
+            if weights.dtype.kind not in "ui" or weights.ndim != 1 or (weights.size and (int(weights.min()) < 0 or int(weights.max()) > 0xffffffff)):
+                raise ValueError("weights must be an EntryWeights or a 1-d array of u32 values, one weight per entry")
+            weights = np.ascontiguousarray(weights, dtype=np.uint32)
         if isinstance(aligned, FrameAlignments):
             if side != "target":
                 raise ValueError("pileup of a FrameAlignments: side=\"query\" is not built (depth in bases on a strand); side=\"target\" only")
@@ -1068,13 +1086,26 @@ class Context:
         if profile:
             other_res = np.ascontiguousarray(other_res, dtype=np.uint8); other_off = np.ascontiguousarray(other_off, dtype=np.uint64)
             up += [other_res if other_res.size else np.zeros(1, np.uint8), other_off]
+        if isinstance(weights, np.ndarray):
+            n_entries = aligned.n_regions if isinstance(aligned, RegionCigars) else aligned.n_rows
+            if weights.size != n_entries:
+                raise ValueError(f"weights holds {weights.size} values for {n_entries} entries")
+            up.append(weights if weights.size else np.zeros(1, np.uint32))
         with self._uploaded(*up) as d:
             d_off, d = d[0], list(d[1:])
             d_mask = C.c_void_p(d.pop(0)) if row_mask is not None else None
             other = (C.c_void_p(d[0]), C.c_void_p(d[1]), len(other_off) - 1, int(other_res.size)) if profile else (None, None, 0, 0)
             side_batch = (C.c_void_p(d_off), len(offsets) - 1, int(offsets[-1]))
             out = C.c_void_p()
-            if isinstance(aligned, RegionCigars):
+            if weights is not None:
+                d_w = C.c_void_p(weights.weight_ptr if isinstance(weights, EntryWeights) else d[-1])
+                if isinstance(aligned, RegionCigars):
+                    st = self._L.ks_cigars_pileup_weighted(self._h, aligned._h, alignments._h, hits._h, d_mask, *side_batch, *other, d_w,
+                                                           C.byref(opts), C.byref(out))
+                else:
+                    st = self._L.ks_hitalns_pileup_weighted(self._h, aligned._h, hits._h, d_mask, *side_batch, *other, d_w, C.byref(opts),
+                                                            C.byref(out))
+            elif isinstance(aligned, RegionCigars):
                 st = self._L.ks_cigars_pileup(self._h, aligned._h, alignments._h, hits._h, d_mask, *side_batch, *other, C.byref(opts), C.byref(out))
             elif isinstance(aligned, HitAlignments):
                 st = self._L.ks_hitalns_pileup(self._h, aligned._h, hits._h, d_mask, *side_batch, *other, C.byref(opts), C.byref(out))
@@ -1083,34 +1114,117 @@ class Context:
             self._check(st)
         return Pileup(self, out)
 
+    def entry_weights_device(self, d_row_offsets: Optional[int], d_op_offsets: int, d_ops: int, n_rows: int, n_entries: int, n_ops: int,
+                             d_start: int, d_other_start: int, d_row_mask: Optional[int], hits: "Hits", d_offsets: int, n_seqs: int,
+                             n_res: int, d_other_res: int, d_other_off: int, n_other: int, n_other_res: int, d_counts: int,
+                             side: str = "query", include_query: bool = False, d_res: Optional[int] = None) -> "EntryWeights":
+        """ks_entry_weights_device from raw device pointers: one position-based (Henikoff) weight per entry, small where the
+        entry agrees with many others — the arguments of pileup_device with profile=True, d_counts: the counts u32[n_res * 28]
+        of that pileup of the same entries, mask and side, and with include_query=True d_res, the side's residues (the sequence
+        the entries lie on is then one more member of its columns).  include/kmerseek_amd.h has the rule."""
+        if side not in PILEUP_SIDES:
+            raise ValueError(f"side = {side!r} is neither \"query\" nor \"target\"")
+        if include_query and not d_res and n_res:
+            raise ValueError("include_query=True needs d_res, the residues of the batch on the chosen side")
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        out = C.c_void_p()
+        self._check(self._L.ks_entry_weights_device(self._h, vp(d_row_offsets), vp(d_op_offsets), vp(d_ops), int(n_rows), int(n_entries), int(n_ops),
+                                                     vp(d_start), vp(d_other_start), vp(d_row_mask), hits._h, vp(d_res), vp(d_offsets), int(n_seqs),
+                                                     int(n_res), vp(d_other_res), vp(d_other_off), int(n_other), int(n_other_res), vp(d_counts),
+                                                     PILEUP_SIDES[side], _lib.KS_PWEIGHTS_INCLUDE_QUERY if include_query else 0, C.byref(out)))
+        return EntryWeights(self, out)
+
+    def entry_weights(self, aligned: "RegionCigars", hits: "Hits", pileup: "Pileup", side: str = "query", offsets=None,
+                      alignments: Optional["RegionAlignments"] = None, row_mask=None, other_res=None, other_off=None,
+                      include_query: bool = False, res=None) -> "EntryWeights":
+        """One weight per region of a RegionCigars (ks_cigars_pileup_weights) from the Pileup made of them with profile=True on
+        the same side and under the same row_mask: the arguments of pileup(), and with include_query=True res, the host
+        residues of the side's batch.  Pass the result to pileup(..., weights=)."""
+        if side not in PILEUP_SIDES:
+            raise ValueError(f"side = {side!r} is neither \"query\" nor \"target\"")
+        if not isinstance(aligned, RegionCigars):
+            raise TypeError("entry_weights takes a RegionCigars (other entries: entry_weights_device)")
+        if alignments is None:
+            raise TypeError("entry_weights needs alignments=, the RegionAlignments the cigars were traced from")
+        if not isinstance(pileup, Pileup):
+            raise TypeError("entry_weights needs the Pileup made from the same entries with profile=True")
+        if offsets is None or other_res is None or other_off is None:
+            raise TypeError("entry_weights needs offsets=, other_res= and other_off=: the side's offsets and the other batch")
+        if include_query and res is None:
+            raise ValueError("include_query=True needs res=, the residues of the batch on the chosen side")
+        offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
+        if offsets.ndim != 1 or offsets.size == 0:
+            raise ValueError("offsets must be a 1-d array of n + 1 offsets")
+        other_res = np.ascontiguousarray(other_res, dtype=np.uint8); other_off = np.ascontiguousarray(other_off, dtype=np.uint64)
+        up = [offsets, other_res if other_res.size else np.zeros(1, np.uint8), other_off]
+        if row_mask is not None:
+            row_mask = np.ascontiguousarray(np.asarray(row_mask) != 0, dtype=np.uint8)
+            if row_mask.shape != (hits.count,):
+                raise ValueError(f"row_mask holds {row_mask.size} values for {hits.count} hit rows")
+            up.append(row_mask if row_mask.size else np.zeros(1, np.uint8))
+        if include_query:
+            res = np.ascontiguousarray(res, dtype=np.uint8)
+            if res.size != int(offsets[-1]):
+                raise ValueError(f"res holds {res.size} residues, the offsets end at {int(offsets[-1])}")
+            up.append(res if res.size else np.zeros(1, np.uint8))
+        with self._uploaded(*up) as d:
+            d = list(d)
+            d_res = C.c_void_p(d.pop()) if include_query else None
+            d_mask = C.c_void_p(d.pop()) if row_mask is not None else None
+            out = C.c_void_p()
+            self._check(self._L.ks_cigars_pileup_weights(self._h, aligned._h, alignments._h, pileup._h, hits._h, d_mask, d_res, C.c_void_p(d[0]),
+                                                         len(offsets) - 1, int(offsets[-1]), C.c_void_p(d[1]), C.c_void_p(d[2]), len(other_off) - 1,
+                                                         int(other_res.size), PILEUP_SIDES[side],
+                                                         _lib.KS_PWEIGHTS_INCLUDE_QUERY if include_query else 0, C.byref(out)))
+        return EntryWeights(self, out)
+
     def build_profile_device(self, d_counts: int, d_depth: int, d_q_res: int, d_q_off: int, n_q: int, n_q_res: int,
-                             params: ProfileParams) -> "Profile":
+                             params: ProfileParams, d_wcounts: Optional[int] = None) -> "Profile":
         """ks_profile_build_device from raw device pointers: counts u32[n_q_res * 28] and depth u32[n_q_res] as a query-side
         Pileup with the profile holds them, and the query batch.  Per residue a row of 28 scores, a consensus byte and the
-        observations behind the row; include/kmerseek_amd.h has the rule, params: ProfileParams (profile_params)."""
+        observations behind the row; include/kmerseek_amd.h has the rule, params: ProfileParams (profile_params).  d_wcounts:
+        None, or the weighted counts u64[n_q_res * 28] of a weighted pileup: ks_profile_build_weighted_device, whose
+        frequencies are the weighted ones and whose evidence is the number of classes seen."""
         if not isinstance(params, ProfileParams):
             raise TypeError("params must be a ProfileParams (profile_params)")
         opts, keep = params._opts()
         out = C.c_void_p()
+        if d_wcounts is not None:
+            self._check(self._L.ks_profile_build_weighted_device(self._h, C.c_void_p(d_counts), C.c_void_p(d_wcounts), C.c_void_p(d_depth),
+                                                                 C.c_void_p(d_q_res), C.c_void_p(d_q_off), int(n_q), int(n_q_res),
+                                                                 C.byref(opts), C.byref(out)))
+            del keep
+            return Profile(self, out)
         self._check(self._L.ks_profile_build_device(self._h, C.c_void_p(d_counts), C.c_void_p(d_depth), C.c_void_p(d_q_res), C.c_void_p(d_q_off),
                                                     int(n_q), int(n_q_res), C.byref(opts), C.byref(out)))
         del keep
         return Profile(self, out)
 
-    def build_profile(self, pileup, q_res: np.ndarray, q_off: np.ndarray, params: ProfileParams) -> "Profile":
+    def build_profile(self, pileup, q_res: np.ndarray, q_off: np.ndarray, params: ProfileParams, weighted: bool = False) -> "Profile":
         """The Profile of the query batch (q_res, q_off: host arrays) from a Pileup made on its side with profile=True
-        (ks_profile_build_pileup), or from host arrays (counts, depth) that stand for one."""
+        (ks_profile_build_pileup), or from host arrays (counts, depth) that stand for one.  weighted=True: the weighted build
+        (ks_profile_build_weighted_pileup) from a Pileup made with weights=, or from host arrays (counts, wcounts, depth)."""
         if not isinstance(params, ProfileParams):
             raise TypeError("params must be a ProfileParams (profile_params)")
+        if weighted and isinstance(pileup, Pileup) and pileup._h and not pileup.n_weighted and pileup.n_residues:
+            raise ValueError("weighted=True needs a Pileup made with weights= (this one holds no weighted counts)")
         q_res = np.ascontiguousarray(q_res, dtype=np.uint8); q_off = np.ascontiguousarray(q_off, dtype=np.uint64)
         if isinstance(pileup, Pileup):
             opts, keep = params._opts()
             out = C.c_void_p()
             with self._uploaded(q_res, q_off) as (d_q, d_qo):
-                self._check(self._L.ks_profile_build_pileup(self._h, pileup._h, C.c_void_p(d_q), C.c_void_p(d_qo), len(q_off) - 1, len(q_res),
-                                                            C.byref(opts), C.byref(out)))
+                fn = self._L.ks_profile_build_weighted_pileup if weighted else self._L.ks_profile_build_pileup
+                self._check(fn(self._h, pileup._h, C.c_void_p(d_q), C.c_void_p(d_qo), len(q_off) - 1, len(q_res), C.byref(opts), C.byref(out)))
             del keep
             return Profile(self, out)
+        if weighted:
+            counts, wcounts, depth = pileup
+            counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1); depth = np.ascontiguousarray(depth, dtype=np.uint32)
+            wcounts = np.ascontiguousarray(wcounts, dtype=np.uint64).reshape(-1)
+            if len(counts) != _lib.KS_RSCORE_ALPHABET * len(q_res) or len(wcounts) != len(counts) or len(depth) != len(q_res):
+                raise ValueError("counts and wcounts must hold 28 entries and depth one per residue of the batch")
+            with self._uploaded(counts, wcounts, depth, q_res, q_off) as (d_c, d_w, d_d, d_q, d_qo):
+                return self.build_profile_device(d_c, d_d, d_q, d_qo, len(q_off) - 1, len(q_res), params, d_wcounts=d_w)
         counts, depth = pileup
         counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1); depth = np.ascontiguousarray(depth, dtype=np.uint32)
         if len(counts) != _lib.KS_RSCORE_ALPHABET * len(q_res) or len(depth) != len(q_res):
@@ -1847,6 +1961,41 @@ class Pileup(_Columns):
     def depth_ptr(self) -> int:
         """The device column depth u32[n_residues]."""
         return int(self._ctx._L.ks_pileup_device_depth(self._h) or 0)
+
+    @property
+    def n_weighted(self) -> int:
+        """Entries of wdepth: n_residues for a pileup made with weights, else 0."""
+        return int(self._ctx._L.ks_wpileup_n_weighted(self._h))
+
+    @property
+    def wdepth_ptr(self) -> int:
+        """The device column wdepth u64[n_weighted]; 0 without weights."""
+        return int(self._ctx._L.ks_wpileup_device_wdepth(self._h) or 0)
+
+    @property
+    def wcounts_ptr(self) -> int:
+        """The device column wcounts u64[n_weighted * 28] (with the profile); 0 without weights."""
+        return int(self._ctx._L.ks_wpileup_device_wcounts(self._h) or 0)
+
+    def weighted_to_host(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(wdepth u64[n_weighted], wcounts u64[28 * n_weighted with the profile, else 0]) of a pileup made with weights: per
+        residue the weights of the entries that place it, summed, and the same by the class of the residue aligned to it."""
+        wdepth = np.zeros(self.n_weighted, np.uint64)
+        wcounts = np.zeros(self.n_profile if self.n_weighted else 0, np.uint64)
+        self._ctx._check(self._ctx._L.ks_wpileup_copy_to_host(self._ctx._h, self._h, _ptr(wdepth), _ptr(wcounts)))
+        return wdepth, wcounts
+
+
+class EntryWeights(_Columns):
+    """Device-resident result of Context.entry_weights (ks_pweights): per entry of a pileup its weight u32 in units of 2^-30
+    (KS_WEIGHT_ONE is 1; 0 for an entry that was not taken) and n_cols, its pair columns."""
+    _PREFIX, _COUNTS = "pweights", {"n_entries": ""}
+    _TABLE = (("weight", "u4", "n_entries"), ("n_cols", "u4", "n_entries"))
+
+    @property
+    def weight_ptr(self) -> int:
+        """The device column weight u32[n_entries]: pass it to Context.pileup_device(d_weight=)."""
+        return int(self._ctx._L.ks_pweights_device_weight(self._h) or 0)
 
 
 class Profile(_Columns):

@@ -931,6 +931,9 @@ def coverage_rows(records: Sequence[Tuple[str, bytes]], pileup_host) -> List[dic
             for s, (name, _) in enumerate(records)]
 
 
+PROFILE_WEIGHTINGS = (None, "henikoff")  # profile_weighting= of search_extract_kmers_device
+
+
 def _coverage_check(coverage, allowed, needs) -> None:
     """coverage= of the two searches: one of `allowed`, and every (name, on) of `needs` switched on."""
     if coverage not in allowed:
@@ -951,7 +954,7 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                                 chain_skew_cost: int = 0, chain_overlap_cost: int = 0, hit_rows: bool = False,
                                 stitch: bool = False, stitch_max_fill: int = 0, evalue: bool = False, stat_params=None,
                                 max_evalue=None, mask: bool = False, mask_opts: Optional[dict] = None, coverage: Optional[str] = None,
-                                profile: bool = False, profile_beta: float = 10.0):
+                                profile: bool = False, profile_beta: float = 10.0, profile_weighting: Optional[str] = None):
     """`kmerseek search --extract-kmers QUERY TARGET` with the k-mer join on the device: sketch both, search, k-mer position
     tables (left on the GPU), ks_match_positions, then only the pairs of the hit rows come to the host to be stitched.
     Same rows as `search_extract_kmers`.  regions=True: the pairs are chained on the device too (ks_match_regions with
@@ -990,7 +993,16 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
     position-specific matrix.  The traced alignments of the kept regions are piled up on the queries with their residue counts
     (Context.pileup, profile=True), the counts become a Profile (Context.build_profile with profile_params(matrix,
     beta=profile_beta)), the kept regions are aligned and traced again against it, and the rows carry the pssm_* columns
-    `region_rows` adds for pssm=."""
+    `region_rows` adds for pssm=.
+    profile_weighting="henikoff" (needs profile=True): the alignments are weighted before they are counted, so that many
+    near-copies of one homolog say one thing once.  The profile is then made in four steps: the unweighted pileup, one
+    position-based weight per alignment from its counts (Context.entry_weights, include_query=True), the pileup again under
+    those weights (Context.pileup, weights=) and the weighted build (Context.build_profile, weighted=True).  The pssm_*
+    columns keep their names.  None: every alignment counts once, as before."""
+    if profile_weighting not in PROFILE_WEIGHTINGS:
+        raise ValueError(f"profile_weighting = {profile_weighting!r} is none of {', '.join(repr(w) for w in PROFILE_WEIGHTINGS)}")
+    if profile_weighting is not None and not profile:
+        raise ValueError(f"profile_weighting = {profile_weighting!r} needs profile=True: it weights the alignments the profile is built from")
     _coverage_check(coverage, (None, "query", "target"), (("cigar", cigar),))
     if profile:
         for name, on in (("regions", regions), ("gapped", gapped), ("cigar", cigar), ("cull", cull)):
@@ -1119,7 +1131,14 @@ def search_extract_kmers_device(query_fasta: str, target_fasta: str, ksize: int,
                     if profile:  # round two: the kept alignments say what each query position likes
                         from .engine import profile_params
                         pu = ctx.pileup(cg, hits, side="query", offsets=q_off, alignments=t_al, profile=True, other_res=t_res, other_off=t_off)
-                        pf = ctx.build_profile(pu, q_res, q_off, profile_params(matrix, beta=profile_beta))
+                        if profile_weighting == "henikoff":
+                            ew = ctx.entry_weights(cg, hits, pu, side="query", offsets=q_off, alignments=t_al, other_res=t_res, other_off=t_off,
+                                                   include_query=True, res=q_res)
+                            pu.free()
+                            pu = ctx.pileup(cg, hits, side="query", offsets=q_off, alignments=t_al, profile=True, other_res=t_res, other_off=t_off,
+                                            weights=ew)
+                            ew.free()
+                        pf = ctx.build_profile(pu, q_res, q_off, profile_params(matrix, beta=profile_beta), weighted=profile_weighting is not None)
                         p_al = ctx.align_regions(t_rg, hits, q_res, q_off, t_res, t_off, profile=pf, band=band, gap_open=gap_open,
                                                  gap_extend=gap_extend, x_drop=gapped_x_drop)
                         p_cg = ctx.trace_regions(t_rg, hits, q_res, q_off, t_res, t_off, p_al, eqx=eqx, profile=pf)
