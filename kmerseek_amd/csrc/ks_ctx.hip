@@ -97,6 +97,12 @@ static void debug_apply(ks_ctx *ctx) {
     ks_debug_load(&ctx->dbg);
     const char *cap = ks_dbg(ctx, KS_DBG_POOL_CAP);
     ctx->pool_cap = cap ? strtoull(cap, nullptr, 10) : 0;
+    ctx->pool_fill = -1; // (anything but an integer in 0..255 counts as unset)
+    if (const char *fill = ks_dbg(ctx, KS_DBG_POOL_FILL)) {
+        char *end = nullptr;
+        const long v = strtol(fill, &end, 10);
+        if (end != fill && *end == 0 && v >= 0 && v <= 255) ctx->pool_fill = (int)v;
+    }
 }
 extern "C" int ks_ctx_reload_debug_env(ks_ctx *ctx) {
     if (!ctx) return KS_ERR_INVALID_ARG;
@@ -378,12 +384,25 @@ static size_t pool_class(size_t bytes) {
     return (bytes + step - 1) & ~(step - 1);
 }
 
+// KS_DEBUG_POOL_FILL (tests): the whole block, its class size, is filled with the byte on the context's stream before the caller
+// sees it, so that a pass which reads a word it never wrote reads the same poison on a fresh block and on a recycled one.  The
+// frees are host-immediate and stream-ordered: the fill runs behind every earlier reader of the block.
+static void *pool_hand_out(ks_ctx *ctx, ks_pool_block &b) {
+    b.in_use = true;
+    if (ctx->pool_fill < 0) return b.ptr;
+    const hipError_t e = hipMemsetAsync(b.ptr, ctx->pool_fill, b.size, ctx->stream);
+    if (e == hipSuccess) return b.ptr;
+    b.in_use = false;
+    ks_fail(ctx, KS_ERR_HIP, "pool fill: hipMemsetAsync(%zu) failed: %s", b.size, hipGetErrorString(e));
+    return nullptr;
+}
+
 void *ks_pool_alloc(ks_ctx *ctx, size_t bytes) {
     if (bytes == 0) bytes = 256;
     const size_t want = pool_class(bytes);
     for (size_t i = 0; i < ctx->pool.size(); i++) {
         auto &b = ctx->pool[i];
-        if (!b.in_use && b.size == want) { b.in_use = true; return b.ptr; }
+        if (!b.in_use && b.size == want) return pool_hand_out(ctx, b);
     }
     if (ctx->pool_cap) { // KS_DEBUG_POOL_CAP (tests): behave like a device that is full
         size_t held = 0;
@@ -403,7 +422,7 @@ void *ks_pool_alloc(ks_ctx *ctx, size_t bytes) {
             auto &b = ctx->pool[i];
             if (!b.in_use && b.size >= want && (best < 0 || b.size < ctx->pool[best].size)) best = (int)i;
         }
-        if (best >= 0) { ctx->pool[best].in_use = true; return ctx->pool[best].ptr; }
+        if (best >= 0) return pool_hand_out(ctx, ctx->pool[best]);
         ks_pool_trim(ctx); // ... else give the cached blocks back and retry once
         e = hipMalloc(&p, want);
     }
@@ -412,9 +431,9 @@ void *ks_pool_alloc(ks_ctx *ctx, size_t bytes) {
         ks_fail(ctx, KS_ERR_OOM, "hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
         return nullptr;
     }
-    ctx->pool.push_back({p, want, true});
+    ctx->pool.push_back({p, want, false});
     ctx->pool_mallocs++;
-    return p;
+    return pool_hand_out(ctx, ctx->pool.back());
 }
 
 void ks_pool_free(ks_ctx *ctx, void *ptr) {
